@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- clip-pairs/sec of the AVMoE adapter hot path (fwd+bwd) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--dtype bf16|f32] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--dtype bf16|f32] [--dump-outputs DIR] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     (python bench.py --gpus N without a launcher starts that launcher itself, before any GPU call, and relays rank 0's line)
 
@@ -30,6 +30,9 @@ The JSON line also carries
   value_f32     the same step in fp32 (the configuration held to the 1e-3 bar)
   cpu_baseline  oracle/avmoe_oracle.py (eager PyTorch, fp32) timed on this box's host cores on a bounded
                 sample of the same workload (same shapes, B=2 clips), rank 0 at N=1 only
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs); the inputs and parameters are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -478,6 +481,8 @@ def parity_check_(c, material, device, pair_mode="concurrent"):
 SINGLE_SUM_DRAWS = 6          # upstream-gradient draws of the bf16 parity leg's single-sum view (1 = off)
 PARITY_BARS = dict(out_rel_f32=1e-3, grad_rel_f32=1e-3, out_rel_bf16=1e-2, grad_relnorm_bf16_same_mask=5e-2, grad_relnorm_bf16_major=5e-2,
                    grad_relnorm_bf16_tiny_joint=5e-2, grad_relnorm_bf16_rest=5e-2, grad_abs_bf16_structural_zero=1e-2)
+# members that are the same in every parity object: the headline `parity` carries them, the other configurations' objects leave them out
+PARITY_CONSTANT_KEYS = ("measures", "bars", "kernels", "checked_against")
 
 
 def parity_verdict(res):
@@ -557,37 +562,45 @@ class Workload:
                     pr.same_stream = bool(on)
         return prev
 
-    def step(self, sync=True, keep=None):
+    def step(self, sync=True, keep=None, outs=None):
         """keep: a list that receives clones of every gradient of the step (token gradients per pair, then the flat parameter-gradient
-        buckets) -- the two-stream / one-stream comparison after the timed region"""
+        buckets) -- the two-stream / one-stream comparison after the timed region.
+        outs: a list that receives (name, tensor) for what the step hands its caller, per pair: the two sites' returns (outputs, router
+        indices / probabilities / load-balancing losses where the variant returns them) and the two token gradients -- references, no
+        copies (the parameter gradients stay readable after the step: param_grads)"""
         import torch
         c, reducer = self.c, self.reducer
         reducer.begin(sync=sync)
-        for w in self.work:
+        for i, w in enumerate(self.work):
             xa, xv = w["f_a"].permute(0, 2, 1).unsqueeze(-1), w["f_v"].permute(0, 2, 1).unsqueeze(-1)   # the reference's (S,C,N,1) views
-            for a, v, pr in w["mods"]:
+            for j, (a, v, pr) in enumerate(w["mods"]):
                 extra = []
+                idx_a = idx_v = probs_a = probs_v = lb_a = lb_v = None
                 paired = self.pair_mode != "off" and pr is not None
                 if paired and c["variant"] == "avs":
-                    out_a, _, _, lb_a, out_v, _, _, lb_v = pr(xa, xv, is_training=True)
+                    out_a, idx_a, probs_a, lb_a, out_v, idx_v, probs_v, lb_v = pr(xa, xv, is_training=True)
                     extra = [self.lbw * (lb_a + lb_v)]
                 elif paired and c["variant"] == "avvp":
                     out_a, lb_a, out_v, lb_v = pr(xa, xv)
                     extra = [lb_a + lb_v]
                 elif paired:
-                    out_a, _, out_v, _ = pr(xa, xv)          # net_trans_v3.py:695-698 as one autograd node (AdapterPair)
+                    out_a, idx_a, out_v, idx_v = pr(xa, xv)          # net_trans_v3.py:695-698 as one autograd node (AdapterPair)
                 elif c["variant"] == "avs":
-                    out_a, _, _, lb_a = a(xa, xv, is_training=True)
-                    out_v, _, _, lb_v = v(xv, xa, is_training=True)
+                    out_a, idx_a, probs_a, lb_a = a(xa, xv, is_training=True)
+                    out_v, idx_v, probs_v, lb_v = v(xv, xa, is_training=True)
                     extra = [self.lbw * (lb_a + lb_v)]
                 elif c["variant"] == "avvp":
                     out_a, lb_a = a(xa, xv)
                     out_v, lb_v = v(xv, xa)
                     extra = [lb_a + lb_v]
                 else:
-                    out_a, _ = a(xa, xv)                   # net_trans_v3.py:695
-                    out_v, _ = v(xv, xa)                   # net_trans_v3.py:697
+                    out_a, idx_a = a(xa, xv)                   # net_trans_v3.py:695
+                    out_v, idx_v = v(xv, xa)                   # net_trans_v3.py:697
                 torch.autograd.backward([out_a, out_v] + extra, [w["ga4"], w["gv4"]] + [None] * len(extra))
+                if outs is not None:
+                    got = dict(out_a=out_a, idx_a=idx_a, probs_a=probs_a, lb_a=lb_a, out_v=out_v, idx_v=idx_v, probs_v=probs_v, lb_v=lb_v,
+                               grad_f_a=w["f_a"].grad, grad_f_v=w["f_v"].grad)
+                    outs += [(f"pair{i}_{j}_{k}", t.detach()) for k, t in got.items() if torch.is_tensor(t)]
                 # the pairs of a shape share the synthetic inputs, not the modules: every pair's input gradients are its own (in the
                 # model they flow into different layers), so they are dropped here instead of being summed over the pairs
                 if keep is not None:
@@ -613,8 +626,21 @@ class Workload:
         torch.cuda.synchronize()
         return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
 
-    def timed(self, steps, warmup):
-        """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; MAX over the ranks."""
+    def param_grads(self):
+        """(name, tensor) per site: the gradients of all its parameters (what the last step left in `.grad`), flattened and concatenated
+        in parameters() order"""
+        import torch
+        res = []
+        for i, w in enumerate(self.work):
+            for j, (a, v, _pr) in enumerate(w["mods"]):
+                for tag, m in (("a", a), ("v", v)):
+                    gs = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in m.parameters()]
+                    res.append((f"pair{i}_{j}_param_grads_{tag}", torch.cat(gs)))
+        return res
+
+    def timed(self, steps, warmup, outs=None):
+        """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; MAX over the ranks.  outs: receives what
+        the LAST timed step hands its caller (step)."""
         import torch
         import torch.distributed as dist
 
@@ -626,8 +652,8 @@ class Workload:
             self.step()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step()
+        for k in range(steps):
+            self.step(outs=outs if k == steps - 1 else None)
         barrier()
         dt = time.perf_counter() - t0
         if self.world > 1:
@@ -670,12 +696,45 @@ def other_config_line(name, device, pair_mode, steps=3, warmup=2):
     esz = 2 if c["dtype"] == "bf16" else 4
     rl = path_roofline(c, esz, c["dtype"], value, 1)
     cpu, material = cpu_baseline(c, budget_s=0.0, min_timed=1)
-    parity = parity_check(c, material, device, pair_mode)
+    parity = {k: v for k, v in parity_check(c, material, device, pair_mode).items() if k not in PARITY_CONSTANT_KEYS}
+    # the descriptive strings (roofline level, CPU sample, the parity constants) are the headline's: the line stays short enough to be read whole
     return dict(workload=f"{name}: {c['what']}", value=round(value, 2), unit="clip-pairs/s", ms_per_step=round(1e3 * dt / steps, 3), steps=steps,
                 warmup=warmup, dtype=c["dtype"], clips_per_gpu=c["B"], site_pairs=sum(p[4] for p in c["pairs"]),
                 roofline=dict(bound="hbm", frac=rl["frac"], achieved=rl["achieved"], peak=rl["peak"], unit="GB/s",
-                              algorithmic_bytes_per_step=rl["algorithmic_bytes_per_step"], level=rl["level"]),
-                parity=parity, cpu_baseline=dict(value=cpu["value"], unit=cpu["unit"], cores=cpu["cores"], kind=cpu["kind"], sample=cpu["sample"]))
+                              algorithmic_bytes_per_step=rl["algorithmic_bytes_per_step"]),
+                parity=parity, cpu_baseline=dict(value=cpu["value"], unit=cpu["unit"], cores=cpu["cores"], kind=cpu["kind"]))
+
+
+DUMP_BYTES = 60_000_000          # --dump-outputs: the .npy files together stay below this (the documented limit is 64 MB)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every (name, tensor) as out_dir/<name>.npy in float32.  Water-filling over the budget: the smallest arrays whole
+    (in their own shape), the larger ones an equal number of elements each, flat in the tensor's logical order, at sorted positions drawn
+    from a generator seeded with the array's name -- the same positions in every run and every build.  Returns (files, bytes)."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    room = (budget - 128 * len(arrays)) // 4           # float32 elements after the .npy headers (128 bytes each)
+    sizes = sorted(t.numel() for _n, t in arrays)
+    cap = None
+    for i, n in enumerate(sizes):
+        share = room // (len(sizes) - i)
+        if n > share:
+            cap = share
+            break
+        room -= n
+    nbytes = 0
+    for name, t in arrays:
+        if cap is not None and t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            pos = torch.randint(t.numel(), (cap,), generator=g).sort().values.to(t.device)
+            t = t[torch.unravel_index(pos, t.shape)]
+        path = os.path.join(out_dir, f"{name}.npy")
+        np.save(path, t.float().cpu().numpy())
+        nbytes += os.path.getsize(path)
+    return len(arrays), nbytes
 
 
 def lib_stamp():
@@ -703,7 +762,13 @@ def main():
     ap.add_argument("--pair", default="concurrent", choices=["concurrent", "same", "serial", "off"],
                     help="how the two sites of a layer are run: AdapterPair on two streams / the two-stream schedule and kernel variants issued on "
                          "ONE stream (profiling: every launch alone on the GPU) / back to back on one stream / two separate calls")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (per site pair: outputs, router indices / probabilities / "
+                         "losses, token gradients, parameter gradients) as DIR/<name>.npy in float32, under 64 MB in all (a seeded sample of "
+                         "the large arrays); rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])
 
@@ -742,7 +807,12 @@ def main():
     wl = Workload(c, tdt, device, rank, world, args.pair)
     pair_mode = wl.pair_mode
     msg_bytes = wl.reducer.message_bytes()
-    dt = wl.timed(args.steps, args.warmup)                     # THE timed region: W warm-up steps, then exactly K steps
+    last = [] if args.dump_outputs and rank == 0 else None
+    dt = wl.timed(args.steps, args.warmup, outs=last)          # THE timed region: W warm-up steps, then exactly K steps
+    if last is not None:                                       # what the last of the K steps computed (before the repetitions below)
+        n, nbytes = dump_outputs(args.dump_outputs, last + wl.param_grads())
+        last = None
+        print(f"bench.py: --dump-outputs: {n} arrays, {nbytes} bytes in {args.dump_outputs}", file=sys.stderr, flush=True)
     ms_per_step = 1e3 * dt / args.steps
     value = c["B"] * world / (dt / args.steps)
     rep_ms = [ms_per_step] + [1e3 * wl.timed(args.steps, 0) / args.steps for _ in range(max(0, args.reps - 1))]

@@ -59,3 +59,30 @@ def test_parity_verdict_of_the_bf16_gradient_views():
     assert not r["ok"] and "grad_rel_f32" in r["failed"]
     r = bench.parity_verdict(dict(idx_equal=True, out_rel_f32=2e-6, grad_rel_f32=1e-4))                # an fp32 configuration: no bf16 leg
     assert r["ok"] and r["ok_bf16_grads"] is None
+
+
+def test_dump_outputs_whole_or_seeded_sample_within_the_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files under the byte budget; arrays that fit are written whole in their own shape,
+    the larger ones as the same seeded positions every time, taken in the tensor's logical order (a permuted view is sampled as its values)."""
+    import numpy as np
+    import torch
+    big = torch.arange(6 * 500 * 40, dtype=torch.float32).reshape(6, 500, 40)
+    view = big.permute(0, 2, 1).unsqueeze(-1)                                   # the (S, C, N, 1) view a site returns
+    arrays = [("pair0_0_out_a", view), ("pair0_0_idx_a", torch.tensor([[1], [3]])), ("pair0_0_lb_a", torch.tensor(0.25, dtype=torch.bfloat16))]
+    budget = 4 * 30_000
+    n, nbytes = bench.dump_outputs(str(tmp_path / "a"), arrays, budget=budget)
+    assert n == 3 and nbytes <= budget
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) == nbytes
+    out = np.load(tmp_path / "a" / "pair0_0_out_a.npy")
+    idx = np.load(tmp_path / "a" / "pair0_0_idx_a.npy")
+    lb = np.load(tmp_path / "a" / "pair0_0_lb_a.npy")
+    assert out.dtype == idx.dtype == lb.dtype == np.float32
+    assert idx.shape == (2, 1) and idx.ravel().tolist() == [1.0, 3.0] and lb.shape == () and float(lb) == 0.25
+    assert out.ndim == 1 and 20_000 < out.size < view.numel()
+    where = np.argsort(view.reshape(-1).numpy())[out.astype(np.int64)]         # logical position of every sampled (distinct) value
+    assert np.all(np.diff(where) >= 0) and where[0] < view.numel() // 100 and where[-1] > view.numel() * 99 // 100
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    assert np.array_equal(out, np.load(tmp_path / "b" / "pair0_0_out_a.npy"))                # same positions run to run
+    n, nbytes = bench.dump_outputs(str(tmp_path / "c"), arrays)                              # the default budget: everything whole
+    whole = np.load(tmp_path / "c" / "pair0_0_out_a.npy")
+    assert whole.shape == (6, 40, 500, 1) and np.array_equal(whole, view.numpy()) and nbytes <= bench.DUMP_BYTES <= 64 << 20
