@@ -157,7 +157,8 @@ class _SiteBackward:
     writer of dX, 4: every writer of dY), in this order.  finish() returns the parameter gradients in `names` order (None where not needed,
     or for all of them when a gradient sink took them)."""
 
-    def __init__(self, module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, scratch_slot=0, stream=None):
+    def __init__(self, module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, scratch_slot=0, stream=None,
+                 d_probs=None):
         self.L = capi.lib()
         (desc, keep, fwd_ptrs), self.saved, self.X, self.Y = state
         self.desc, self.names, self.module = desc, names, module
@@ -186,7 +187,9 @@ class _SiteBackward:
             self.gptrs = cm.MoePtrs()
             self.grads = {k: (torch.empty_like(v) if needs[i] else None) for i, (k, v) in enumerate(tensors.items())}
             filler.fill(self.gptrs, [self.grads[k] for k in names])
-        self.d_out = d_out.to(self.X.dtype).contiguous()
+        # d_out None: out got no gradient -> the router-only backward (avmoe_moe_backward_ex with dOut = NULL, whole: run(0) only)
+        self.d_out = d_out.to(self.X.dtype).contiguous() if d_out is not None else None
+        self.dprobs = d_probs.to(torch.float32).reshape(desc.S, -1).contiguous() if d_probs is not None else None
         self.lbg = d_lb.to(torch.float32).reshape(1).contiguous() if (d_lb is not None and desc.lb_loss) else None
         wkey = (desc.S, desc.N, desc.M, self.X.dtype, bool(desc.training), bool(desc.shared_gpu))
         sizes = module.__dict__.get("_ws_sizes", {}).get(wkey)
@@ -196,6 +199,16 @@ class _SiteBackward:
     def run(self, parts=0):
         d = self.desc
         d.accumulate_dx, d.accumulate_dy = self.acc
+        if self.d_out is None or self.dprobs is not None:      # a gradient for probs, or none for out: the _ex entry point
+            st = self.L.avmoe_moe_backward_ex(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),
+                                              self.d_out.data_ptr() if self.d_out is not None else None,
+                                              self.dprobs.data_ptr() if self.dprobs is not None else None,
+                                              self.lbg.data_ptr() if self.lbg is not None else None, self.saved.data_ptr(),
+                                              self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
+                                              int(parts), self.stream)
+            d.accumulate_dx = d.accumulate_dy = 0
+            capi.check(st, "avmoe_moe_backward_ex")
+            return self
         st = self.L.avmoe_moe_backward_part(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), self.d_out.data_ptr(),
                                             self.lbg.data_ptr() if self.lbg is not None else None, self.saved.data_ptr(),
                                             self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
@@ -249,9 +262,9 @@ class _SiteBackward:
         return tuple(self.grads[k] for k in self.names)
 
 
-def _site_backward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False):
+def _site_backward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, d_probs=None):
     """The whole backward of one site in one call (see _SiteBackward)."""
-    return _SiteBackward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx, acc_dy).run(0).finish()
+    return _SiteBackward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx, acc_dy, d_probs=d_probs).run(0).finish()
 
 
 class AdapterFunction(torch.autograd.Function):
@@ -266,16 +279,16 @@ class AdapterFunction(torch.autograd.Function):
         if sink is not None and any(ctx.needs_input_grad[5:]):
             sink.calls += 1                              # the site's bucket is complete after as many backward calls
         ctx.save_for_backward(state[2], state[3], *params)
-        ctx.mark_non_differentiable(probs, idx)
+        ctx.mark_non_differentiable(idx)                 # probs is differentiable, as in the reference (F.softmax of the router logits)
         return out, probs, idx, lb
 
     @staticmethod
-    def backward(ctx, d_out, _d_probs, _d_idx, d_lb):
+    def backward(ctx, d_out, d_probs, _d_idx, d_lb):
         X, Y, *params = ctx.saved_tensors
-        if d_out is None:                                # only the load-balancing loss was differentiated
-            d_out = torch.zeros_like(X)
+        # d_out None (only probs and / or the load-balancing loss were differentiated): the router-only backward
         dX, dY = torch.empty_like(X), torch.empty_like(Y)
-        pg = _site_backward(ctx.module, (*ctx.state, X, Y), ctx.names, params, ctx.needs_input_grad[5:], d_out, d_lb, dX, dY)
+        pg = _site_backward(ctx.module, (*ctx.state, X, Y), ctx.names, params, ctx.needs_input_grad[5:], d_out, d_lb, dX, dY,
+                            d_probs=d_probs)
         return (None, dX, dY, None, None) + pg
 
 
@@ -337,14 +350,16 @@ class _PairFunction(torch.autograd.Function):
             if sink is not None and any(needs) and (not ctx.lean or ctx.needs_input_grad[10]):
                 sink.calls += 1
         ctx.save_for_backward(st_a[2], st_a[3], *params)
-        ctx.mark_non_differentiable(idx_a, idx_b, pr_a, pr_b)
+        ctx.mark_non_differentiable(idx_a, idx_b)       # the probabilities are differentiable, as in the reference
         return out_a, out_b, idx_a, idx_b, pr_a, pr_b, lb_a, lb_b
 
     @staticmethod
-    def backward(ctx, d_a, d_b, _ia, _ib, _pa, _pb, d_lba, d_lbb):
+    def backward(ctx, d_a, d_b, _ia, _ib, dp_a, dp_b, d_lba, d_lbb):
         Xa, Xb, *params = ctx.saved_tensors
-        d_a = torch.zeros_like(Xa) if d_a is None else d_a
-        d_b = torch.zeros_like(Xb) if d_b is None else d_b
+        router_only = d_a is None and d_b is None        # neither output got a gradient: the router-only backward for both sites
+        if not router_only:                              # (one output without: zeros for it -- the sections and the fused dX + dY path
+            d_a = torch.zeros_like(Xa) if d_a is None else d_a      # assume a full backward of both sites)
+            d_b = torch.zeros_like(Xb) if d_b is None else d_b
         (site_a, site_b), (names_a, names_b) = ctx.sites, ctx.names
         na = len(names_a)
         gXa, gXb = torch.empty_like(Xa), torch.empty_like(Xb)
@@ -360,6 +375,11 @@ class _PairFunction(torch.autograd.Function):
             needs_a, needs_b = ctx.needs_input_grad[10:10 + na], ctx.needs_input_grad[10 + na:]
         gba = d_a if ctx.has_base[0] else None            # out = base + adapter(...): the residual stream passes the gradient on
         gbb = d_b if ctx.has_base[1] else None
+        if router_only:                                   # both sites on the caller's stream, one after the other: A overwrites, B adds
+            pga = _site_backward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, None, d_lba, gXa, gXb, d_probs=dp_a)
+            pgb = _site_backward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, None, d_lbb, gXb, gXa, acc_dx=True,
+                                 acc_dy=True, d_probs=dp_b)
+            return (None, None, None, gXa, gXb, gba, gbb, None, None, None) + ((None,) if ctx.lean else pga + pgb)
         if ctx.side is not None:
             # Two streams, cross-ordered hand-over: ONE buffer per token tensor, no add kernel.  Each site OVERWRITES its own token
             # gradient with its dX (section 2) and ADDS its dY to the other tensor's buffer (section 16) once the other site's dX is
@@ -372,9 +392,9 @@ class _PairFunction(torch.autograd.Function):
             slot_b = 1 if side.cuda_stream == main.cuda_stream else 0      # (same_stream: the two sites' sections interleave on ONE stream)
             with torch.cuda.stream(side):
                 cbk = _SiteBackward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, d_b, d_lbb, gXb, gXa, acc_dx=False, acc_dy=True,
-                                    scratch_slot=slot_b, stream=side.cuda_stream)
+                                    scratch_slot=slot_b, stream=side.cuda_stream, d_probs=dp_b)
             cak = _SiteBackward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, d_a, d_lba, gXa, gXb, acc_dx=False, acc_dy=True,
-                                stream=main.cuda_stream)
+                                stream=main.cuda_stream, d_probs=dp_a)
             # Round 5: where the library serves it (avmoe_moe_backward_dx_dy: the tuned bf16 shapes), a token gradient is written ONCE -- the
             # dX product of its own site with the other site's dY product folded in as two more contraction segments -- instead of
             # overwritten by one site and read back + added by the other.  That product moves to the END of its site's backward (it
@@ -411,7 +431,7 @@ class _PairFunction(torch.autograd.Function):
                 cak.run(16)
             pga = cak.finish()
             ev_join.record(side); main.wait_event(ev_join)
-            for t_ in tuple(g_ for g_ in pgb if g_ is not None) + (cbk.d_out,):
+            for t_ in tuple(g_ for g_ in pgb if g_ is not None) + (cbk.d_out,) + ((cbk.dprobs,) if cbk.dprobs is not None else ()):
                 t_.record_stream(main)
             gXa.record_stream(side); gXb.record_stream(side)
             return (None, None, None, gXa, gXb, gba, gbb, None, None, None) + ((None,) if ctx.lean else pga + pgb)
@@ -421,10 +441,10 @@ class _PairFunction(torch.autograd.Function):
         first_b = Xa.numel() >= Xb.numel()
         def run_a(acc):
             return _site_backward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, d_a,
-                                  d_lba, gXa, gXb, acc_dx=acc, acc_dy=acc)             # dX -> gXa, dY -> gXb
+                                  d_lba, gXa, gXb, acc_dx=acc, acc_dy=acc, d_probs=dp_a)   # dX -> gXa, dY -> gXb
         def run_b(acc):
             return _site_backward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, d_b,
-                                  d_lbb, gXb, gXa, acc_dx=acc, acc_dy=acc)             # dX -> gXb, dY -> gXa
+                                  d_lbb, gXb, gXa, acc_dx=acc, acc_dy=acc, d_probs=dp_b)   # dX -> gXb, dY -> gXa
         if first_b:
             pgb = run_b(False); pga = run_a(True)
         else:

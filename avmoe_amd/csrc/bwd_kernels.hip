@@ -146,7 +146,8 @@ int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const a
 // router backward (mixture weights, LB loss, 3-layer MLP)   net_trans_v3.py:460-466,477-478
 // rbw layout: dlog [S][E] | dh2r [S][32] | dh1 [S][128] | drin [S][2C]
 // ---------------------------------------------------------------------------------------------
-struct RouterBwdArgs { const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; };
+// dprobs: optional (S, E) upstream gradient of probs itself (a loss on the routing probabilities), added to dp before the softmax Jacobian
+struct RouterBwdArgs { const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; const float* dprobs; };
 // Launch 1: per frame dlog / dh2 / dh1 (softmax, LB loss, the two small layers), one block per frame
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw) {
@@ -174,6 +175,7 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
     for (int e = 0; e < a.E; ++e) {
       dpv[e] = dp[(long)s * a.E + e];
       if (a.lb_loss && a.lb_grad) dpv[e] += a.lb_grad[0] * (-1.f / ((float)a.S * s_pm[e]));
+      if (a.dprobs) dpv[e] += a.dprobs[(long)s * a.E + e];      // (uniform branch: NULL leaves today's sum)
       dot += probs[(long)s * a.E + e] * dpv[e];
     }
     for (int e = 0; e < a.E; ++e) { const float v = probs[(long)s * a.E + e] * (dpv[e] - dot); s_dl[e] = v; dlog[e] = v; }
@@ -264,10 +266,10 @@ __global__ void __launch_bounds__(256) kk_router_bwd_fin(int S, int E, int C2, i
   }
 }
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-                 const float* lb_grad, hipStream_t st) {
+                 const float* lb_grad, const float* dprobs, hipStream_t st) {
   ProfScope ps_("k_router_bwd", 0.0, 0.0, st);
   const Dims& d = pl.d;
-  RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad};
+  RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad, dprobs};
   hipLaunchKernelGGL(kk_router_bwd_a, dim3(d.S), dim3(256), 0, st, a, (const float*)(saved + pl.o_probs),
                      (const float*)(scratch + pl.o_dp), (const float*)(saved + pl.o_rh1), (const float*)(saved + pl.o_rh2),
                      (float*)(scratch + pl.o_rbw));

@@ -80,6 +80,24 @@ int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const voi
   return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts);
 }
 
+int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
+                          const float* dprobs, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
+                          const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
+  Plan pl;
+  AVMOE_TRY(make_plan(desc, &pl));
+  if (!X || !Y || !params || !saved || !scratch || !dX || !dY || !grads || parts < 0 || parts > 127) {
+    set_last_error("avmoe_moe_backward_ex: null pointer or parts not in 0..127"); return ERR_BAD_ARG;
+  }
+  if ((parts & 4) && (parts & 24)) {
+    set_last_error("avmoe_moe_backward_ex: parts %d combines section 4 with its halves 8 / 16", parts); return ERR_BAD_ARG;
+  }
+  if (!dOut) {                              // out gets no gradient: the router-only backward, whole (it has no sections)
+    if (parts != 0 && parts != 7) { set_last_error("avmoe_moe_backward_ex: dOut == NULL serves parts 0 / 7 only, not %d", parts); return ERR_UNSUPPORTED; }
+    return moe_backward_router_only(pl, Y, *params, dprobs, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream);
+  }
+  return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts, dprobs);
+}
+
 int avmoe_moe_backward_dx_dy(const avmoe_moe_desc* desc_a, const void* X_a, void* saved_a, void* scratch_a,
                              const avmoe_moe_desc* desc_b, void* saved_b, void* scratch_b, void* dT, void* stream) {
   Plan pa, pb;

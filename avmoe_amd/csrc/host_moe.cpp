@@ -331,13 +331,22 @@ int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const flo
 
 int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
                             const float* lb_grad, void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads) {
+  if (!dOut) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
+  return avmoe_host_moe_backward_ex(desc, X, Y, params, noise, dOut, nullptr, lb_grad, saved, dX, dY, grads);
+}
+
+int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
+                               const avmoe_moe_ptrs* grads) {
   (void)saved;
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
-  if (!X || !Y || !params || !dOut || !dX || !dY || !grads) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
+  if (!X || !Y || !params || !dX || !dY || !grads) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
   const avmoe_moe_ptrs& P = *params; const avmoe_moe_ptrs& G = *grads;
   const int S = c.S, N = c.N, C = c.C, M = c.M, Cy = c.Cy, E = c.E, K = c.K, d = c.d;
   const long NT = (long)S * N;
+  V zeros;                                                 // dOut == NULL: out gets no gradient, i.e. dOut = 0
+  if (!dOut) { zeros.assign(NT * C, 0.f); dOut = zeros.data(); }
   V out(NT * C);
   float lbv = 0.f;
   if (int rc = forward(c, X, Y, P, noise, out.data(), nullptr, nullptr, &lbv, false)) return rc;
@@ -450,6 +459,7 @@ int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const fl
   }
   // ---- router: p = softmax(logits) ; + the load-balancing loss -sum_e log(mean_s p)
   if (c.lb && lb_grad) for (int e = 0; e < E; ++e) { double m = 0.0; for (int s = 0; s < S; ++s) m += c.p[s * E + e]; m /= S; for (int s = 0; s < S; ++s) dp[s * E + e] -= lb_grad[0] / (float)(S * m); }
+  if (dprobs) for (long i = 0; i < (long)S * E; ++i) dp[i] += dprobs[i];                    // + the upstream gradient of probs itself
   softmax_rows_bwd(c.p.data(), dp.data(), S, E, E);                                            // dp -> dlogits
   V dh2((long)S * 32), dh1((long)S * 128), drin((long)S * 2 * C);
   if (G.r4_w) gemm(true, false, E, 32, S, 1.f, dp.data(), E, c.h2.data(), 32, 0.f, G.r4_w, 32);

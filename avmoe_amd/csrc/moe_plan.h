@@ -71,6 +71,10 @@ struct Dims {
   int fuse_l2;    // ... and so do the hop-2 logits X[s] T[s]^T, as per-group partial sums (L2g) that pre_small adds up: X is read ONCE by the forward's X-side products
 };
 
+// router-only backward (router_only_bwd.hip): frames are cut into chunks of RO_ROWS rows of Y, one block per (chunk, frame)
+constexpr int RO_ROWS = 32;
+inline int ro_chunks(const Dims& d) { return (d.M + RO_ROWS - 1) / RO_ROWS; }
+
 // name, region (0 saved / 1 scratch), element bytes expr (4 or d.esz), element count expr
 #define AVMOE_BUFFERS(X)                                                                      \
   /* ---- weights-derived operands (rebuilt every forward) ---- */                             \
@@ -202,7 +206,8 @@ struct Dims {
   X(dQT, 1, d.esz, (size_t)(d.Kcy ? d.Kcy : 1) * d.Cy)                                          \
   X(dWf, 1, 4, (size_t)d.C * d.Cy)                                                              \
   X(gWd, 1, 4, d.mg ? (size_t)d.E * d.d * d.C : 1)  /* merged groups: gradients of the block-diagonal copies */ \
-  X(gWu, 1, 4, d.mg ? (size_t)d.E * d.C * d.d : 1)
+  X(gWu, 1, 4, d.mg ? (size_t)d.E * d.C * d.d : 1)                                              \
+  X(ro, 1, 4, (size_t)d.S * ((2 + ro_chunks(d)) * (size_t)d.Cy + d.M + 1))   /* router-only backward: u | ybar | ybar chunk partials | dWc rows | sum u, per frame */
 
 size_t slab_floats(const Dims& d);
 // smallest site (token elements) that forks a helper stream inside its calls (side.h; AVMOE_SIDE_MIN)

@@ -53,7 +53,12 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
                 float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st);
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const void* dOut, const float* lb_grad,
-                 char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts = 0);
+                 char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts = 0,
+                 const float* dprobs = nullptr);
+// the backward when `out` gets no gradient (router_only_bwd.hip): only the router and the mean / remap chain carry gradient --
+// the router backward, one pass over Y, one broadcast write of dX, small reductions; every expert gradient is written as 0
+int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,
+                             char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st);
 
 // site A's dX + site B's dY into one token gradient, written once (moe_backward.cpp / dx_stream3.hip); 1 = shapes not served
 int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, const Plan& pb, char* svb, char* scb, void* dX, bool launch, hipStream_t st);

@@ -179,6 +179,22 @@ int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const voi
                             const void* dOut, const float* lb_grad, void* saved, void* scratch,
                             void* dX, void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
 
+/* avmoe_moe_backward_ex (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds it by symbol) -- the backward with two more
+ * upstream gradients: the gradients of  <out, dOut> + <probs, dprobs> + (*lb_grad) * lb.  The reference returns the gating probabilities
+ * as an ordinary autograd tensor (PVT_AVSModel_v2.py:298,312), so a loss built on them (router entropy / z-loss, a balance term,
+ * distillation of the routing) reaches the router, the remap parameters, X and Y.
+ *   dprobs: DEVICE pointer to (S, E) f32, or NULL for 0 (then the launched kernels and every result bit are those of
+ *           avmoe_moe_backward_part with the same `parts`).  The term enters the router backward in section 1.
+ *   dOut:   NULL = out gets no gradient.  Then only the router and the mean / remap chain carry gradient and no expert, Gram or
+ *           token-space product runs: the router backward, one pass over Y that also writes dY, one broadcast write of dX and small
+ *           reductions (csrc/router_only_bwd.hip); every expert parameter gradient is written as 0.  Only parts 0 / 7 are served
+ *           (AVMOE_ERR_UNSUPPORTED otherwise).  accumulate_dx / accumulate_dy are honoured.
+ *   parts, lb_grad and everything else: as avmoe_moe_backward_part.  avmoe_moe_backward(_part) == _ex with dprobs = NULL.         */
+int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                          const void* dOut /* NULL: out gets no gradient */, const float* dprobs /* (S,E) f32 or NULL */,
+                          const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
+                          const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B

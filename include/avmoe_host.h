@@ -32,6 +32,12 @@ int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const flo
 int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                             const float* dOut, const float* lb_grad, void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads);
 
+/* as avmoe_moe_backward_ex: gradients of <out, dOut> + <probs, dprobs> + (*lb_grad) * lb.  dOut == NULL means dOut = 0 (the checker
+ * evaluates the whole reverse pass; it has no router-only path), dprobs: (S, E) HOST pointer or NULL.                                  */
+int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
+                               const avmoe_moe_ptrs* grads);
+
 #ifdef __cplusplus
 }
 #endif
