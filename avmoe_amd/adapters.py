@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Dict
 
+import numbers
 import os
 import torch
 import torch.nn as nn
@@ -141,11 +142,20 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     lb = torch.empty((), device=X.device, dtype=torch.float32)      # always written by the router's kernels (0 without the LB loss)
     if noise is not None:
         noise = noise.to(torch.float32).contiguous()
-    st = L.avmoe_moe_forward(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
-                             noise.data_ptr() if noise is not None else None, out.data_ptr(), probs.data_ptr(),
-                             idx.data_ptr(), lb.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+    top_k = module.router_top_k
+    if top_k is not None and top_k < E:                  # top-k gating of the mixture (k == E: the dense site, the dense entry point)
+        fn = "avmoe_moe_forward_topk"
+        st = L.avmoe_moe_forward_topk(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
+                                      noise.data_ptr() if noise is not None else None, top_k, int(module.router_top_k_renorm),
+                                      out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), saved.data_ptr(),
+                                      scratch.data_ptr(), stream)
+    else:
+        fn = "avmoe_moe_forward"
+        st = L.avmoe_moe_forward(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
+                                 noise.data_ptr() if noise is not None else None, out.data_ptr(), probs.data_ptr(),
+                                 idx.data_ptr(), lb.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
     desc.accumulate_out = 0
-    capi.check(st, "avmoe_moe_forward")
+    capi.check(st, fn)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
     return out, probs, idx, lb, ((desc, keep, ptrs), saved, X, Y)
@@ -519,6 +529,33 @@ class MoEAdapter(nn.Module):
         E = self.num_multimodal_experts + self.num_singlemodal_experts
         self.router = nn.Sequential(nn.Linear(input_dim + linear_out, 128), nn.ReLU(), nn.Linear(128, 32), nn.ReLU(),
                                     nn.Linear(32, E))
+        # top-k gating of the mixture (an extension: the reference mixes densely, net_trans_v3.py:482-486; include/avmoe.h at
+        # avmoe_moe_forward_topk).  Plain attributes, not state: reassigning them switches the mode of the next call.
+        self.router_top_k = getattr(opt, "router_top_k", None)
+        self.router_top_k_renorm = getattr(opt, "router_top_k_renorm", True)
+
+    @property
+    def router_top_k(self):
+        """k of the top-k gating, or None: the dense mixture (also what k == E computes)."""
+        return self.__dict__.get("_router_top_k")          # (.get: a module pickled before the setting existed stays dense)
+
+    @router_top_k.setter
+    def router_top_k(self, k):
+        E = self.num_multimodal_experts + self.num_singlemodal_experts
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= E:
+                raise ValueError(f"router_top_k must be None or an integer in [1, {E}], got {k!r}")
+            k = int(k)
+        self.__dict__["_router_top_k"] = k
+
+    @property
+    def router_top_k_renorm(self):
+        """True: the kept probabilities are renormalised to sum 1 (a softmax over the kept logits); False: taken as they are (Switch)."""
+        return self.__dict__.get("_router_top_k_renorm", True)
+
+    @router_top_k_renorm.setter
+    def router_top_k_renorm(self, v):
+        self.__dict__["_router_top_k_renorm"] = bool(v)
 
     # ---- plumbing ---------------------------------------------------------------------------------
     def _self_attn(self):

@@ -148,11 +148,18 @@ int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const a
 // ---------------------------------------------------------------------------------------------
 // dprobs: optional (S, E) upstream gradient of probs itself (a loss on the routing probabilities), added to dp before the softmax Jacobian
 struct RouterBwdArgs { const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; const float* dprobs; };
-// Launch 1: per frame dlog / dh2 / dh1 (softmax, LB loss, the two small layers), one block per frame
+// Launch 1: per frame dlog / dh2 / dh1 (softmax, LB loss, the two small layers), one block per frame.
+// mode: the forward's mode word [k, renorm].  k = 0 (dense): dp is the gradient of probs = the softmax.  k > 0 (top-k gating):
+// `probs` holds the mixture weights w, psm the softmax p, and dp is dL/dw; it is mapped to dL/dp first (the selection S_k, recomputed
+// from p exactly as the forward made it, carries no gradient):  renorm  dp_e = m_e (dw_e - sum_j w_j dw_j) / sum_j m_j p_j ;
+// otherwise  dp_e = m_e dw_e.  The load-balancing term, dprobs and the softmax Jacobian then act on p.
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
-                                                       const float* rh2, float* rbw) {
-  __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E];
+                                                       const float* rh2, float* rbw, const float* psm, const int* mode) {
+  __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x;
+  const int top_k = mode[0], renorm = mode[1];   // (uniform over the grid)
+  const float* wt = probs;                       // the mixture weights
+  if (top_k) probs = psm;                        // from here on: the softmax
   float* dh1 = rbw + (long)s * 128;
   float* dh2 = rbw + (long)a.S * (128 + a.C2) + (long)s * 32;
   float* dlog = rbw + (long)a.S * (128 + a.C2 + 32) + (long)s * a.E;
@@ -172,8 +179,19 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
   __syncthreads();
   if (threadIdx.x == 0) {
     float dot = 0.f, dpv[MAX_E];
+    if (top_k) {
+      for (int e = 0; e < a.E; ++e) s_p[e] = probs[(long)s * a.E + e];
+      float kept, wd = 0.f;
+      const unsigned m = topk_select(s_p, a.E, top_k, &kept);
+      if (renorm)
+        for (int e = 0; e < a.E; ++e) wd += wt[(long)s * a.E + e] * dp[(long)s * a.E + e];
+      for (int e = 0; e < a.E; ++e) {
+        const float dw = dp[(long)s * a.E + e];
+        dpv[e] = ((m >> e) & 1u) ? (renorm ? (dw - wd) / kept : dw) : 0.f;
+      }
+    }
     for (int e = 0; e < a.E; ++e) {
-      dpv[e] = dp[(long)s * a.E + e];
+      if (!top_k) dpv[e] = dp[(long)s * a.E + e];
       if (a.lb_loss && a.lb_grad) dpv[e] += a.lb_grad[0] * (-1.f / ((float)a.S * s_pm[e]));
       if (a.dprobs) dpv[e] += a.dprobs[(long)s * a.E + e];      // (uniform branch: NULL leaves today's sum)
       dot += probs[(long)s * a.E + e] * dpv[e];
@@ -272,7 +290,7 @@ int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptr
   RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad, dprobs};
   hipLaunchKernelGGL(kk_router_bwd_a, dim3(d.S), dim3(256), 0, st, a, (const float*)(saved + pl.o_probs),
                      (const float*)(scratch + pl.o_dp), (const float*)(saved + pl.o_rh1), (const float*)(saved + pl.o_rh2),
-                     (float*)(scratch + pl.o_rbw));
+                     (float*)(scratch + pl.o_rbw), (const float*)(saved + pl.o_psm), (const int*)(saved + pl.o_mode));
   float* rbw = (float*)(scratch + pl.o_rbw);
   float* dh1 = rbw;
   float* drin = rbw + (long)d.S * 128;

@@ -55,6 +55,17 @@ int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, 
   return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream);
 }
 
+int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                           int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
+                           void* stream) {
+  Plan pl;
+  AVMOE_TRY(make_plan(desc, &pl));
+  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("avmoe_moe_forward_topk: null pointer"); return ERR_BAD_ARG; }
+  if (top_k < 1 || top_k > pl.d.E) { set_last_error("avmoe_moe_forward_topk: top_k %d not in [1, %d]", top_k, pl.d.E); return ERR_BAD_ARG; }
+  const int k = top_k == pl.d.E ? 0 : top_k;            // every expert kept: the dense site, whatever renorm says
+  return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0);
+}
+
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                        const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
                        const avmoe_moe_ptrs* grads, void* stream) {

@@ -15,6 +15,21 @@ __device__ __forceinline__ unsigned short f2bf(float x) {
   return __builtin_bit_cast(unsigned short, (__bf16)x);
 }
 
+// top-k gating of one frame (avmoe_moe_forward_topk) from its E probabilities p: bit e of the result is set when expert e is among the
+// k most probable -- higher probability first, equal probabilities in expert order (kk_router_topk) -- and *kept = the sum of the
+// kept probabilities, added in expert order.  The forward and the router backward call it on the same p: the same selection.
+__device__ __forceinline__ unsigned topk_select(const float* p, int E, int k, float* kept) {
+  unsigned m = 0u;
+  float s = 0.f;
+  for (int e = 0; e < E; ++e) {
+    int rank = 0;                                  // experts that come before e
+    for (int f = 0; f < E; ++f) rank += (p[f] > p[e]) || (p[f] == p[e] && f < e);
+    if (rank < k) { m |= 1u << e; s += p[e]; }
+  }
+  *kept = s;
+  return m;
+}
+
 // element access for the activation / operand type T (float or __bf16)
 template <typename T> __device__ __forceinline__ float ldT(const T* p, long i);
 template <> __device__ __forceinline__ float ldT<float>(const float* p, long i) { return p[i]; }

@@ -778,15 +778,20 @@ int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs&
 // ---------------------------------------------------------------------------------------------
 struct RouterArgs {
   const float *W1, *b1, *W2, *b2, *W3, *b3, *noise;
-  int C2, E, S;
+  int C2, E, S, top_k, renorm;    // top_k: 0 = the dense mixture
 };
 // one block per frame: layer-1 pre-activations from the engine GEMM -- summed here over its split-K slabs, in slab order, when it
 // ran split (no separate reduce pass) --, then bias / ReLU, the two small layers, softmax and first-max argmax.  fp32, fixed order.
+// Top-k gating (a.top_k > 0, avmoe_moe_forward_topk): `probs` (what the post kernels multiply by) receives the mixture weights
+// w_e = m_e p_e / sum_j m_j p_j (renorm) or m_e p_e, and `psm` the dense softmax p for the backward and the load-balancing loss;
+// probs_out / idx_out stay the dense softmax and its argmax.  Block 0 writes the mode word [k, renorm] (k = 0: dense) that the
+// router backward reads.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
-                                                      float* probs_out, int64_t* idx_out, float* lb_zero) {
-  __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E];
+                                                      float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode) {
+  __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
+  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; }
   {
     float pre;
     if (ks > 1) {
@@ -819,11 +824,18 @@ __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, 
     int best = 0; float bp = -1.f;
     for (int e = 0; e < a.E; ++e) {
       const float p = expf(s_lg[e] - mx) / sum;
-      probs[(long)s * a.E + e] = p;
+      if (a.top_k) { psm[(long)s * a.E + e] = p; s_p[e] = p; }
+      else probs[(long)s * a.E + e] = p;
       if (probs_out) probs_out[(long)s * a.E + e] = p;
       if (p > bp) { bp = p; best = e; }            // strict '>' : first maximum wins (torch.argmax)
     }
     if (idx_out) idx_out[s] = best;
+    if (a.top_k) {                                 // (the kept sum holds the frame's largest probability, >= 1 / E: no division by 0)
+      float kept;
+      const unsigned m = topk_select(s_p, a.E, a.top_k, &kept);
+      for (int e = 0; e < a.E; ++e)
+        probs[(long)s * a.E + e] = ((m >> e) & 1u) ? (a.renorm ? s_p[e] / kept : s_p[e]) : 0.f;
+    }
   }
 }
 // load-balancing loss  -sum_e log(mean_s p[s,e])  (reference quirk: PVT_AVSModel_v2.py:314-318)
@@ -839,13 +851,14 @@ __global__ void __launch_bounds__(256) kk_lb_loss(const float* probs, int S, int
   if (threadIdx.x == 0) *lb = total;
 }
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st) {
+             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
     set_last_error("moe: router parameters missing"); return ERR_BAD_ARG;
   }
-  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S};
+  if (top_k < 0 || top_k > d.E) { set_last_error("moe: top_k %d not in [0, %d]", top_k, d.E); return ERR_BAD_ARG; }
+  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, top_k, renorm ? 1 : 0};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;
@@ -858,10 +871,11 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
     AVMOE_TRY(launch_gemm(g, st));
   }
   hipLaunchKernelGGL(kk_router_tail, dim3(d.S), dim3(128), 0, st, a, (float*)(saved + pl.o_rh1), (const float*)(scratch + pl.o_slabs), ks,
-                     (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), probs_out, idx_out, (lb_out && !d.lb_loss) ? lb_out : nullptr);
+                     (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), probs_out, idx_out, (lb_out && !d.lb_loss) ? lb_out : nullptr,
+                     (float*)(saved + pl.o_psm), (int*)(saved + pl.o_mode));
   AVMOE_CHECK_LAUNCH("router");
-  if (lb_out && d.lb_loss) {
-    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, (const float*)(saved + pl.o_probs), d.S, d.E, lb_out);
+  if (lb_out && d.lb_loss) {                               // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
+    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, (const float*)(saved + (top_k ? pl.o_psm : pl.o_probs)), d.S, d.E, lb_out);
     AVMOE_CHECK_LAUNCH("lb_loss");
   }
   return OK;

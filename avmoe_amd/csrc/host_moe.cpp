@@ -150,7 +150,10 @@ struct Ctx {
   bool avvp, v2, v1;
   bool bn, gate, lnb, lnp, train, lb;
   float bn_eps, ln_eps, mom;
+  int topk = 0; bool renorm = true;  // top-k gating (avmoe_host_moe_forward_topk); 0 = the dense mixture
   V Yt, Yf, rin, h1, h2, logit, p;
+  V w;                              // the mixture weights: p, or the top-k weights
+  std::vector<unsigned> sel;        // top-k: the kept experts of each frame (bit e)
   std::vector<Expert> ex;
 };
 
@@ -205,6 +208,21 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
     if (idx) idx[s] = best;
     if (probs) for (int e = 0; e < E; ++e) probs[s * E + e] = c.p[s * E + e];
   }
+  // ---- top-k gating: the k most probable experts (higher probability first, equal probabilities in expert order), their weights
+  //      renormalised over the kept set (renorm) or taken as they are; the dense mixture: w = p
+  c.w = c.p;
+  c.sel.assign(S, 0u);
+  if (c.topk)
+    for (int s = 0; s < S; ++s) {
+      const float* ps = c.p.data() + (long)s * E;
+      float kept = 0.f;
+      for (int e = 0; e < E; ++e) {
+        int rank = 0;
+        for (int f = 0; f < E; ++f) rank += (ps[f] > ps[e]) || (ps[f] == ps[e] && f < e);
+        if (rank < c.topk) { c.sel[s] |= 1u << e; kept += ps[e]; }
+      }
+      for (int e = 0; e < E; ++e) c.w[s * E + e] = ((c.sel[s] >> e) & 1u) ? (c.renorm ? ps[e] / kept : ps[e]) : 0.f;
+    }
   if (lb) {      // -sum_e log(mean_s p): the reference's kl_div against the constant 1 (PVT_AVSModel_v2.py:314-318)
     double v = 0.0;
     if (c.lb) for (int e = 0; e < E; ++e) { double m = 0.0; for (int s = 0; s < S; ++s) m += c.p[s * E + e]; v -= std::log(m / S); }
@@ -306,12 +324,15 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
     x.pre.assign(o, o + NT * C);
     const float gt = (c.gate && q.gate) ? q.gate[0] : 1.f;
     for (int s = 0; s < S; ++s) {
-      const float w = c.p[s * E + e] * gt;
+      const float w = c.w[s * E + e] * gt;
       for (long i = (long)s * N * C; i < (long)(s + 1) * N * C; ++i) out[i] += w * x.pre[i];
     }
   }
   return AVMOE_OK;
 }
+
+int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
+             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm);
 
 }  // namespace
 
@@ -335,12 +356,41 @@ int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const fl
   return avmoe_host_moe_backward_ex(desc, X, Y, params, noise, dOut, nullptr, lb_grad, saved, dX, dY, grads);
 }
 
+int avmoe_host_moe_forward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, void* saved) {
+  (void)saved;
+  Ctx c;
+  if (int rc = setup(desc, c)) return rc;
+  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
+  if (top_k < 1 || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [1, %d]", top_k, c.E);
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
+  return forward(c, X, Y, *params, noise, out, probs, idx, lb, true);
+}
+int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                 const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
+                                 const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
+  (void)saved;
+  if (top_k < 1) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, E]", top_k);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm);
+}
 int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads) {
   (void)saved;
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the reverse pass (the forward recomputed); top_k 0 or E: the dense mixture
+int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
+             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
+  if (top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, %d]", top_k, c.E);
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
   if (!X || !Y || !params || !dX || !dY || !grads) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
   const avmoe_moe_ptrs& P = *params; const avmoe_moe_ptrs& G = *grads;
   const int S = c.S, N = c.N, C = c.C, M = c.M, Cy = c.Cy, E = c.E, K = c.K, d = c.d;
@@ -361,7 +411,7 @@ int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const
     double dgate = 0.0;
     for (int s = 0; s < S; ++s) {
       double a = 0.0;
-      const float pe = c.p[s * E + e];
+      const float pe = c.w[s * E + e];
       for (long i = (long)s * N * C; i < (long)(s + 1) * N * C; ++i) { a += (double)dOut[i] * x.pre[i]; t0[i] = dOut[i] * pe * gt; }
       dp[s * E + e] = (float)(a * gt); dgate += a * pe;
     }
@@ -457,6 +507,16 @@ int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const
       }
     }
   }
+  // ---- top-k gating: dp holds dL/dw so far -> dL/dp (the selection has no gradient)
+  if (c.topk)
+    for (int s = 0; s < S; ++s) {
+      float* d_ = dp.data() + (long)s * E;
+      const float* w = c.w.data() + (long)s * E;
+      float kept = 0.f, wd = 0.f;
+      for (int e = 0; e < E; ++e) if ((c.sel[s] >> e) & 1u) kept += c.p[s * E + e];
+      if (c.renorm) for (int e = 0; e < E; ++e) wd += w[e] * d_[e];
+      for (int e = 0; e < E; ++e) d_[e] = ((c.sel[s] >> e) & 1u) ? (c.renorm ? (d_[e] - wd) / kept : d_[e]) : 0.f;
+    }
   // ---- router: p = softmax(logits) ; + the load-balancing loss -sum_e log(mean_s p)
   if (c.lb && lb_grad) for (int e = 0; e < E; ++e) { double m = 0.0; for (int s = 0; s < S; ++s) m += c.p[s * E + e]; m /= S; for (int s = 0; s < S; ++s) dp[s * E + e] -= lb_grad[0] / (float)(S * m); }
   if (dprobs) for (long i = 0; i < (long)S * E; ++i) dp[i] += dprobs[i];                    // + the upstream gradient of probs itself
@@ -494,4 +554,4 @@ int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const
   return AVMOE_OK;
 }
 
-}  // extern "C"
+}  // namespace

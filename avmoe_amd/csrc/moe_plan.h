@@ -207,7 +207,10 @@ inline int ro_chunks(const Dims& d) { return (d.M + RO_ROWS - 1) / RO_ROWS; }
   X(dWf, 1, 4, (size_t)d.C * d.Cy)                                                              \
   X(gWd, 1, 4, d.mg ? (size_t)d.E * d.d * d.C : 1)  /* merged groups: gradients of the block-diagonal copies */ \
   X(gWu, 1, 4, d.mg ? (size_t)d.E * d.C * d.d : 1)                                              \
-  X(ro, 1, 4, (size_t)d.S * ((2 + ro_chunks(d)) * (size_t)d.Cy + d.M + 1))   /* router-only backward: u | ybar | ybar chunk partials | dWc rows | sum u, per frame */
+  X(ro, 1, 4, (size_t)d.S * ((2 + ro_chunks(d)) * (size_t)d.Cy + d.M + 1))   /* router-only backward: u | ybar | ybar chunk partials | dWc rows | sum u, per frame */ \
+  /* ---- top-k gating (appended: the indices of the buffers above stay) ---- */                                           \
+  X(psm, 0, 4, (size_t)d.S * d.E)                   /* top-k mode: the dense softmax (probs then holds the mixture weights) */ \
+  X(mode, 0, 4, 64)                                 /* [0] = k (0: dense mixture), [1] = renorm; written by every router forward */
 
 size_t slab_floats(const Dims& d);
 // smallest site (token elements) that forks a helper stream inside its calls (side.h; AVMOE_SIDE_MIN)

@@ -49,8 +49,10 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
 int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& ep, const avmoe_expert_ptrs& eg, int slot, const void* dxr,
                         char* saved, char* scratch, float* slabs, size_t slab_cap, void* dX, hipStream_t st);
 
+// top_k > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const float* noise, void* out,
-                float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st);
+                float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st, int top_k = 0,
+                int renorm = 1);
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const void* dOut, const float* lb_grad,
                  char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts = 0,

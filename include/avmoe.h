@@ -154,6 +154,28 @@ int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, 
                       const float* noise, void* out, float* probs, int64_t* idx, float* lb,
                       void* saved, void* scratch, void* stream);
 
+/* avmoe_moe_forward_topk (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds it by symbol) -- top-k gating of the
+ * mixture (Shazeer et al. 2017, Switch, Mixtral; BASELINE config 3 "router top-k=2"; the reference mixes densely,
+ * net_trans_v3.py:482-486).  With p = softmax(router logits) of frame s and S_k(s) its k most probable experts (higher probability
+ * first, equal probabilities in expert order: the order of avmoe_router_topk), m_e = 1[e in S_k(s)]:
+ *     renorm != 0:  w_e = m_e p_e / sum_j m_j p_j      (= a softmax over the kept logits)
+ *     renorm == 0:  w_e = m_e p_e                      (Switch style)
+ *     out = sum_e w_e expert_e(x)
+ * Only the mixture weights change: every expert still runs on every frame (no speed-up), so BatchNorm batch statistics and
+ * running-statistic updates are those of the dense site.  probs stays the dense softmax (bit-equal to avmoe_moe_forward), idx its
+ * first-max argmax, lb the load-balancing loss on the dense softmax.  top_k must be in [1, E] (AVMOE_ERR_BAD_ARG otherwise); top_k == E
+ * is avmoe_moe_forward, whatever renorm says.
+ * The backward entry points (avmoe_moe_backward, _part, _ex with its router-only path; avmoe_moe_backward_dx_dy has no router term)
+ * read the mode from `saved`, where every forward writes it, and keep their signatures.  They give the gradients of <out, dOut> + <probs, dprobs> + (*lb_grad) * lb: the mixture's
+ * gradient dw of the weights is mapped to the softmax --  renorm: dp_e = m_e (dw_e - sum_j w_j dw_j) / sum_j m_j p_j ; otherwise
+ * dp_e = m_e dw_e --, dprobs and the load-balancing term are added, then the softmax Jacobian.  The selection has no gradient.  With
+ * k = 1 and renorm, w is one-hot and the mixture sends no gradient to the router (only dprobs and lb do): renorm = 0 is the setting that
+ * trains the router through the mixture at k = 1.
+ * The sub-ops avmoe_router_forward and avmoe_expert_forward_* stay dense.                                                              */
+int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                           const float* noise, int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb,
+                           void* saved, void* scratch, void* stream);
+
 /* Gradients of  <out, dOut> + (*lb_grad) * lb .  Every pointer in `grads` that is non-NULL is OVERWRITTEN
  * with the gradient of the matching parameter; dX / dY are overwritten.  `saved` must be the buffer the
  * matching forward filled.  lb_grad: DEVICE pointer to the upstream gradient of the load-balancing loss
@@ -254,7 +276,7 @@ int avmoe_expert_histogram(const int64_t* idx, int64_t S, int32_t E, int64_t* co
 int avmoe_add2(void* dst1, const void* src1, int64_t n1, void* dst2, const void* src2, int64_t n2, int32_t dtype, void* stream);
 /* Extension (no reference counterpart; BASELINE config 3 "router top-k=2"): idx (S, k) int64 = the k most probable experts of
  * every frame from probs (S, E) f32, most probable first, equal probabilities in expert order -- column 0 is the forward's
- * first-max argmax.  The mixture itself stays dense (net_trans_v3.py:482-486).                                          */
+ * first-max argmax.  It only reports the selection; a top-k MIXTURE is avmoe_moe_forward_topk.                           */
 int avmoe_router_topk(const float* probs, int64_t S, int32_t E, int32_t k, int64_t* idx, void* stream);
 
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------

@@ -38,6 +38,15 @@ int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads);
 
+/* as avmoe_moe_forward_topk: top-k gating of the mixture (top_k in [1, E]; top_k == E is the dense site).                         */
+int avmoe_host_moe_forward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, void* saved);
+
+/* avmoe_host_moe_backward_ex of a top-k forward: the same top_k / renorm as the forward (it is recomputed).                          */
+int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                 const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
+                                 const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
+
 #ifdef __cplusplus
 }
 #endif
