@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- clip-pairs/sec of the AVMoE adapter hot path (fwd+bwd) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--dtype bf16|f32] [--dump-outputs DIR] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg1|cfg3|cfg4|cfg5] [--dtype bf16|f32] [--dump-outputs DIR] [--full] ...
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     (python bench.py --gpus N without a launcher starts that launcher itself, before any GPU call, and relays rank 0's line)
+
+A plain run does only what the headline needs: it sets up, runs W warm-up steps, times K steps, writes --dump-outputs if asked,
+and prints the line (`value`, `ms_per_step`, the configuration and the path-level roofline fraction, which costs no run of its own).
+Everything else the line can carry -- the repetitions of the K steps, the profiling pass, the fp32 re-run, the B = 2 leg, the CPU
+baseline, the parity legs, the other configurations and the exposed all-reduce time -- runs with --full only (the --no-* options
+then leave single legs out); without it those members are null.
 
 Default workload (BASELINE.json configs[1], "cfg-2"): synthetic token tensors f_a:(S=B*T, N_a=1024, C=768),
 f_v:(S, N_v=196, C=768) with B=32 clips x T=10 frames PER GPU, one adapter site = the audio-side MoEAdapter
@@ -16,10 +22,11 @@ HBM before the timed region.  value = clips processed by all ranks / max-over-ra
 --config cfg1|cfg3|cfg4|cfg5: the multi-site workloads of SURVEY 8(d) (every adapter site pair of the backbone table,
 positions p1 and p2; clip-pairs/s = clips through ALL of them per second).
 
-The JSON line also carries
+The JSON line carries
   roofline      PATH level: algorithmic bytes per clip-pair x clip-pairs/s vs the 8 TB/s HBM peak (`frac`), the
-                reference-formulation FLOPs vs the dense MFMA peak beside it (`mfma`), and the dominant kernel family of a
+                reference-formulation FLOPs vs the dense MFMA peak beside it (`mfma`), and with --full the dominant kernel family of a
                 HIP-event profiling pass over the same step with every launch alone on the GPU (`dominant_kernel`)
+and with --full also
   parity        max errors of this very build against oracle/avmoe_oracle.py at the benchmarked shapes with B = 2 clips, run the
                 way the timed region runs it (AdapterPair in the same --pair mode): fp32 outputs / gradients / router indices,
                 bf16 the same against the oracle on bf16-rounded inputs.  Gradients are compared KINK-AWARE: the oracle is
@@ -746,7 +753,7 @@ def lib_stamp():
         return None
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -754,11 +761,15 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--dtype", default=None, choices=["bf16", "f32"], help="default: the configuration's own (cfg1: f32, else bf16)")
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the configuration's)")
-    ap.add_argument("--reps", type=int, default=3, help="timed repetitions of the K steps (value = the first; the others give the spread)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skips the CPU legs (cpu_baseline and parity)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-f32", action="store_true", help="skips the fp32 re-run (value_f32)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skips the cfg-1 / cfg-4 / cfg-5 legs of the default (cfg-2, N = 1) run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg of the line: repetitions, profiling pass, fp32 re-run, B = 2 leg, CPU baseline, "
+                         "parity, the other configurations, the exposed all-reduce time (default: the headline alone)")
+    ap.add_argument("--reps", type=int, default=None, help="timed repetitions of the K steps (value = the first; the others give the spread); "
+                                                           "default 3 with --full, else 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skips the CPU legs (cpu_baseline, parity, other configurations)")
+    ap.add_argument("--no-roofline", action="store_true", help="no roofline object; --full: also skips the profiling pass and the B = 2 leg")
+    ap.add_argument("--no-f32", action="store_true", help="--full: skips the fp32 re-run (value_f32)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skips the cfg-1 / cfg-3 / cfg-4 / cfg-5 legs of the default (cfg-2, N = 1) run")
     ap.add_argument("--pair", default="concurrent", choices=["concurrent", "same", "serial", "off"],
                     help="how the two sites of a layer are run: AdapterPair on two streams / the two-stream schedule and kernel variants issued on "
                          "ONE stream (profiling: every launch alone on the GPU) / back to back on one stream / two separate calls")
@@ -766,9 +777,16 @@ def main():
                     help="after the timed steps, write what the last of them computed (per site pair: outputs, router indices / probabilities / "
                          "losses, token gradients, parameter gradients) as DIR/<name>.npy in float32, under 64 MB in all (a seeded sample of "
                          "the large arrays); rank 0")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, sys.argv[1:])
 
@@ -817,7 +835,7 @@ def main():
     value = c["B"] * world / (dt / args.steps)
     rep_ms = [ms_per_step] + [1e3 * wl.timed(args.steps, 0) / args.steps for _ in range(max(0, args.reps - 1))]
     rccl = None
-    if world > 1:       # the exchange, outside the timed region: bytes / messages per step and what the backward does not hide of it
+    if world > 1 and args.full:       # the exchange, outside the timed region: bytes / messages per step and what the backward does not hide of it
         wl.reducer.time_exposed = True
         for _ in range(5):
             wl.step()
@@ -832,7 +850,7 @@ def main():
     roofline = None
     if not args.no_roofline:
         roofline = path_roofline(c, esz, dtype, value, world)
-        if rank == 0:
+        if rank == 0 and args.full:
             # Profiling pass: HIP events around every launch (one family per kernel AND launch shape).  The pair keeps the SCHEDULE of
             # the timed region -- in two-stream mode every kernel in the variant that mode launches: dX overwrites, dY adds behind
             # the other site's dX -- but issues it on ONE stream (AdapterPair.same_stream; the helper streams INSIDE a site are off
@@ -900,14 +918,14 @@ def main():
                                                 gbs=round(r["alg_bytes"] / max(r["total_ms"], 1e-9) / 1e6, 1))
                                            for r in rep], key=lambda r: -r["ms_per_step"])[:12]
 
-    if isinstance(roofline, dict) and rank == 0 and pair_mode == "concurrent":
+    if isinstance(roofline, dict) and rank == 0 and pair_mode == "concurrent" and args.full:
         reps = [wl.two_stream_bit_equal() for _ in range(3)]
         roofline["two_stream_bit_equal"] = all(reps)
         roofline["two_stream_note"] = ("3 x (one step on two streams, one with the same schedule on one stream; same inputs): every token and parameter "
                                        "gradient bit-identical -- the co-residency guard of include/avmoe.h (shared_gpu) on the timed configuration")
     wl.release()
     value_f32 = None
-    if dtype == "bf16" and not args.no_f32 and world == 1:
+    if args.full and dtype == "bf16" and not args.no_f32 and world == 1:
         wl = Workload(c, torch.float32, device, rank, world, args.pair)
         k32 = max(3, args.steps // 2)
         dt32 = wl.timed(k32, 2)
@@ -917,7 +935,7 @@ def main():
 
     # the reference's own batch (AVE/train.sh:33: 2 clips): the same step at B = 2, where the launch rate binds -- step time and launches per step
     b2 = None
-    if args.config == "cfg2" and not args.batch and not args.dtype and world == 1 and not args.no_roofline:
+    if args.full and args.config == "cfg2" and not args.batch and not args.dtype and world == 1 and not args.no_roofline:
         wl = Workload(dict(c, B=2), tdt, device, rank, world, args.pair)
         k2 = max(20, args.steps)
         t2 = [1e3 * wl.timed(k2, 5 if i == 0 else 0) / k2 for i in range(3)]
@@ -939,7 +957,7 @@ def main():
 
     cpu = parity = others = None
     exit_code = 0
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu, material = cpu_baseline(c)
         try:
             parity = parity_check(c, material, device, pair_mode)
@@ -985,7 +1003,7 @@ def main():
         if b2:
             line["b2"] = b2
             line["b2_ms_per_step"] = b2["ms_per_step"]
-        if isinstance(roofline, dict):
+        if isinstance(roofline, dict) and args.full:
             # scalar copies INSIDE `roofline` (the driver's record keeps the scalar members of roofline / config / cpu_baseline only)
             roofline["f32_value"] = value_f32["value"] if value_f32 else None
             roofline["f32_ms_per_step"] = value_f32["ms_per_step"] if value_f32 else None

@@ -2,10 +2,10 @@
 # development: per-family launch durations (HIP events, --pair serial) of the working-tree library and of variant libraries, side by side
 #   scripts/fam_ab.sh outdir [libA.so libB.so ...]
 O=$1; shift; mkdir -p $O
-AVMOE_FAMILIES_OUT=$O/fam_work.json python bench.py --pair serial --steps 10 --warmup 3 --reps 1 --no-cpu-baseline --no-f32 > $O/bench_work.json 2>/dev/null
+AVMOE_FAMILIES_OUT=$O/fam_work.json python bench.py --full --pair serial --steps 10 --warmup 3 --reps 1 --no-cpu-baseline --no-f32 > $O/bench_work.json 2>/dev/null
 for L in "$@"; do
   n=$(basename $L .so)
-  AVMOE_LIB=$L AVMOE_FAMILIES_OUT=$O/fam_$n.json python bench.py --pair serial --steps 10 --warmup 3 --reps 1 --no-cpu-baseline --no-f32 > $O/bench_$n.json 2>/dev/null
+  AVMOE_LIB=$L AVMOE_FAMILIES_OUT=$O/fam_$n.json python bench.py --full --pair serial --steps 10 --warmup 3 --reps 1 --no-cpu-baseline --no-f32 > $O/bench_$n.json 2>/dev/null
 done
 python - $O "$@" <<'PY'
 import json, sys, os

@@ -4,7 +4,7 @@ O=gpurun_out/fast_vs_gen; mkdir -p $O
 AVMOE_NO_FAST=1 python -m pytest tests/test_moe_vs_oracle_midsize_gpu.py tests/test_cfg2_shape_gpu.py tests/test_moe_backward_gpu.py -q -m gpu -k "fast or ship or cfg2 or golden or fixture or part" 2>&1 | tail -3
 for v in fast gen; do
   if [ $v = gen ]; then export AVMOE_NO_FAST=1; else unset AVMOE_NO_FAST; fi
-  AVMOE_FAMILIES_OUT=$O/fam_$v.json python bench.py --no-cpu-baseline --no-f32 --reps 1 --pair serial > $O/serial_$v.json 2>$O/err_$v
+  AVMOE_FAMILIES_OUT=$O/fam_$v.json python bench.py --full --no-cpu-baseline --no-f32 --reps 1 --pair serial > $O/serial_$v.json 2>$O/err_$v
   python bench.py --no-cpu-baseline --no-f32 --no-roofline --reps 3 > $O/conc_$v.json 2>>$O/err_$v
   python - $O $v <<'PY'
 import json, sys

@@ -5,7 +5,7 @@
 #   usage: scripts/make_profiles.sh [round tag, default r06]
 R=$PWD; O=$R/gpurun_out/prof_final; T=${1:-r06}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-f32 --reps 1"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-f32 --reps 1"
 # counters: their own runs, kernel trace only (3 steps: 1 warm-up + 2 timed; the profiling pass of bench.py is off)
 S="--steps 2 --warmup 1 --no-roofline --pair same"      # the timed region's kernel variants (dX overwrites, dY accumulates), one stream
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/f -- $B $S > $O/f.log 2>&1
@@ -27,7 +27,7 @@ cp $O/kta/*/*kernel_stats.csv $O/kernel_stats_alone.csv
 cp $O/kt/*/*kernel_stats.csv $O/kernel_stats_default.csv
 cp $O/kts/*/*kernel_stats.csv $O/kernel_stats_serial.csv
 grep -h "^{\"metric\"" $O/kts.log | tail -1 > $O/bench_line_serial.json
-python3 bench.py > $O/bench_line.json 2> $O/bench.err
-python3 bench.py --batch 2 --no-cpu-baseline --no-f32 > $O/bench_line_b2.json 2>> $O/bench.err
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.err
+python3 bench.py --full --batch 2 --no-cpu-baseline --no-f32 > $O/bench_line_b2.json 2>> $O/bench.err
 tail -3 $O/pmc_traffic.txt; head -12 $O/pmc_mfma.txt
 tail -1 $O/bench_line.json | cut -c1-300

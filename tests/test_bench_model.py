@@ -86,3 +86,13 @@ def test_dump_outputs_whole_or_seeded_sample_within_the_budget(tmp_path):
     n, nbytes = bench.dump_outputs(str(tmp_path / "c"), arrays)                              # the default budget: everything whole
     whole = np.load(tmp_path / "c" / "pair0_0_out_a.npy")
     assert whole.shape == (6, 40, 500, 1) and np.array_equal(whole, view.numpy()) and nbytes <= bench.DUMP_BYTES <= 64 << 20
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """bench.parse_args: without --full one repetition of the K steps (the headline's own) and no other leg; --full brings back the three
+    repetitions and every leg the --no-* options do not leave out; an explicit --reps holds either way."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and a.reps == 1 and (a.steps, a.warmup, a.gpus) == (20, 5, 1)
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert a.full and a.reps == 3 and not (a.no_cpu_baseline or a.no_roofline or a.no_f32 or a.no_other_configs)
+    assert bench.parse_args(["--reps", "2"]).reps == 2 and bench.parse_args(["--full", "--reps", "1"]).reps == 1

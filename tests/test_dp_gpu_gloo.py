@@ -101,14 +101,15 @@ def test_data_parallel_step_world2_on_one_gpu():
 
 
 def test_bench_two_ranks_finish_and_print_one_line():
-    """The driver's multi-GPU invocation of bench.py (torch.distributed.run, --gpus N): every rank must reach the end -- rank 0's
+    """The driver's multi-GPU invocation of bench.py (torch.distributed.run, --gpus N) with --full: every rank must reach the end -- rank 0's
     roofline pass may not enter a collective the other ranks never join -- and rank 0 prints exactly one JSON line.  Two ranks on
     one GPU with gloo (AVMOE_BENCH_BACKEND, development switch); RCCL needs one GPU per rank."""
     import json
     import subprocess
     env = dict(os.environ, AVMOE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--reps", "1"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--reps", "1",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -126,7 +127,8 @@ def test_bench_self_launches_its_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(AVMOE_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--reps", "1", "--no-f32"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--reps", "1", "--no-f32",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
