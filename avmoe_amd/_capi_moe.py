@@ -5,6 +5,7 @@ import ctypes as C
 from typing import Dict, List
 
 MAX_EXPERTS = 16
+OPT_CLIP, OPT_SKIP_NONFINITE, OPT_DECOUPLED_DECAY = 1, 2, 4      # flags of avmoe_opt_grad_norm / avmoe_opt_adam_step
 VARIANT = {"ave": 0, "avqa": 0, "avvp": 1, "avs": 2}
 SELF_ATTN = {"none": 0, "v2": 1, "nxn": 2, "v1": 3}
 
@@ -15,6 +16,22 @@ class MoeDesc(C.Structure):
                                          "dtype", "training")] + \
                [(n, C.c_float) for n in ("bn_eps", "ln_eps", "bn_momentum")] + \
                [(n, C.c_int32) for n in ("accumulate_dx", "accumulate_dy", "accumulate_out", "shared_gpu")]
+
+
+class OptRange(C.Structure):
+    """avmoe_opt_range: one flat (param, grad, exp_avg, exp_avg_sq) range of the optimizer with its learning rate and decay"""
+    _fields_ = [(n, C.c_void_p) for n in ("param", "grad", "exp_avg", "exp_avg_sq")] + [("n", C.c_int64), ("lr", C.c_float),
+                                                                                       ("weight_decay", C.c_float)]
+
+
+class OptLayout(C.Structure):
+    _fields_ = [("state_bytes", C.c_size_t), ("table_bytes", C.c_size_t), ("partial_bytes", C.c_size_t), ("n_blocks", C.c_int64)]
+
+
+# avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
+OPT_STATE_BYTES = 64
+OPT_STATE_FIELDS = {"total_norm": (0, "float32"), "clip_coef": (4, "float32"), "bc1": (8, "float32"), "bc2_sqrt": (12, "float32"),
+                    "applied_steps": (16, "int64"), "skipped_steps": (24, "int64"), "skip": (32, "int32")}
 
 
 _EXPERT_FIELDS = ("gate", "my_tokens", "gate_lat", "down_w", "up_w", "bn1_w", "bn1_b", "bn2_w", "bn2_b",
@@ -98,6 +115,17 @@ def declare(L):
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+    if hasattr(L, "avmoe_opt_adam_step"):            # (found by symbol: added under ABI 11 -- the optimizer with device-side state)
+        L.avmoe_opt_workspace_bytes.restype = C.c_size_t
+        L.avmoe_opt_workspace_bytes.argtypes = [C.POINTER(OptRange), C.c_int32, C.POINTER(OptLayout)]
+        L.avmoe_opt_table_build.restype = C.c_int
+        L.avmoe_opt_table_build.argtypes = [C.POINTER(OptRange), C.c_int32, C.c_void_p, C.c_size_t]
+        L.avmoe_opt_grad_norm.restype = C.c_int
+        L.avmoe_opt_grad_norm.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
+                                          C.c_float, C.c_float, C.c_void_p]
+        L.avmoe_opt_adam_step.restype = C.c_int
+        L.avmoe_opt_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          C.c_int32, C.c_void_p]
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

@@ -1,0 +1,46 @@
+// The Adam element update, written ONCE for kk_adam (train_kernels.hip: one flat range per launch, scalars from the host) and kk_opt_adam
+// (opt_kernels.hip: every range of the optimizer in one launch, scalars from the device state block).
+// The fused multiply-adds are spelled out and contraction is switched off around them: left to itself the compiler fuses
+// `b1 * m + (1 - b1) * g` one way in a 16-byte body and another way in a scalar tail loop, and two kernels that serve the same element
+// through different paths (the plain path's merged ranges run over alignment padding, the table's ranges end at the parameter) would
+// differ in the last bit.  The form below is the one kk_adam's 16-byte body has always compiled to, so the plain path computes what it
+// did, and both paths agree bit for bit on equal inputs (tests/test_flat_adam_device_gpu.py holds them to that).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace avmoe {
+
+// DECOUPLED = false: torch.optim.Adam (weight decay joins the gradient).  true: torch.optim.AdamW (p *= 1 - lr * wd first, no wd term).
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                          float bc2_sqrt, float gscale) {
+#pragma clang fp contract(off)
+  float gr;
+  if constexpr (DECOUPLED) {
+    p *= 1.f - lr * wd;
+    gr = g * gscale;
+  } else {
+    gr = __builtin_fmaf(gscale, g, wd * p);
+  }
+  m = __builtin_fmaf(b1, m, (1.f - b1) * gr);
+  v = __builtin_fmaf(b2, v, ((1.f - b2) * gr) * gr);
+  p -= ((lr / bc1) * m) / (sqrtf(v) / bc2_sqrt + eps);
+}
+
+// elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long i0,
+                                          long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
+  if (i0 + 3 < n) {
+    float4 pp = *(float4*)(p + i0), mm = *(float4*)(m + i0), vv = *(float4*)(v + i0);
+    const float4 gg = *(const float4*)(g + i0);
+    float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; const float* G = (const float*)&gg;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) adam_elem<DECOUPLED>(P[k], M[k], V[k], G[k], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+    *(float4*)(p + i0) = pp; *(float4*)(m + i0) = mm; *(float4*)(v + i0) = vv;
+  } else {
+    for (long i = i0; i < n; ++i) adam_elem<DECOUPLED>(p[i], m[i], v[i], g[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+  }
+}
+
+}  // namespace avmoe

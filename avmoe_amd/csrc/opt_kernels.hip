@@ -1,0 +1,219 @@
+// The optimizer with its state on the device (include/avmoe.h, "optimizer with device-side state"): every (param, grad, exp_avg,
+// exp_avg_sq) range the optimizer owns is one entry of a table in device memory, and three launches serve a step whatever the number of
+// buckets and ranges --
+//   kk_opt_sqsum     sum of (grad * grad_scale)^2 per 1024-element block, in double, into the partial-sum workspace
+//   kk_opt_finalize  one block adds the partial sums in a fixed order and writes the state block: norm, clip factor, skip flag, step
+//                    counters, bias corrections
+//   kk_opt_adam      the Adam / AdamW update of every range; reads the state block, writes nothing when the step is skipped
+// Plain bandwidth kernels: 16-byte loads and stores, no matrix pipe, LDS only for the block reduction.  No floating-point atomics: the norm
+// repeats bit for bit.
+#include "../../include/avmoe.h"
+#include "common.h"
+#include "adam_elem.h"
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+namespace avmoe {
+
+constexpr int OPT_BLOCK = 1024;                  // elements per block: 256 threads x 4, as kk_adam
+constexpr uint32_t OPT_MAGIC = 0x4f50544du;      // "OPTM"
+
+// the table image: header, the ranges, then one (range, block inside the range) pair per 1024-element block
+struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
+struct OptBlock { int32_t range, block; };
+static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
+
+__device__ __forceinline__ const avmoe_opt_range* opt_ranges(const void* table) { return (const avmoe_opt_range*)((const char*)table + sizeof(OptHeader)); }
+__device__ __forceinline__ const OptBlock* opt_blocks(const void* table, int n_ranges) {
+  return (const OptBlock*)((const char*)table + sizeof(OptHeader) + (size_t)n_ranges * sizeof(avmoe_opt_range));
+}
+
+// sum over the block's elements of ((double)grad * grad_scale)^2 -> partials[blockIdx.x].  A launch whose grid does not match the table
+// (a stale or foreign image) touches nothing but its own partial sum.
+__global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ table, double* __restrict__ partials, float grad_scale) {
+  __shared__ double red[256];
+  const OptHeader h = *(const OptHeader*)table;
+  double acc = 0.0;
+  if (h.magic == OPT_MAGIC && (long)blockIdx.x < h.n_blocks) {
+    const OptBlock b = opt_blocks(table, h.n_ranges)[blockIdx.x];
+    if (b.range >= 0 && b.range < h.n_ranges) {
+      const avmoe_opt_range r = opt_ranges(table)[b.range];
+      const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
+      const double gs = (double)grad_scale;
+      if (i0 + 3 < r.n) {
+        const float4 g = *(const float4*)(r.grad + i0);
+        const double a = (double)g.x * gs, c = (double)g.y * gs, d = (double)g.z * gs, e = (double)g.w * gs;
+        acc = a * a + c * c + d * d + e * e;
+      } else {
+        for (long i = i0; i < r.n && i < i0 + 4; ++i) { const double a = (double)r.grad[i] * gs; acc += a * a; }
+      }
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+// One block.  Thread t adds partials[t], partials[t + 256], ... in that order, the 256 sums go through the same tree as above: a fixed
+// order.  n_partials == 0 (neither clipping nor skipping asked for): the norm is reported as 0 and only the counters advance.
+__global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
+                                                       float max_norm, int clip, int skip_nonfinite, float beta1, float beta2) {
+  __shared__ double red[256];
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const float total = (float)sqrt(red[0]);
+  float coef = 1.0f;
+  if (clip) {                                           // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1); NaN stays NaN
+    const float c = max_norm / (total + 1e-6f);
+    coef = c < 1.0f ? c : (c != c ? c : 1.0f);
+  }
+  const int skip = (skip_nonfinite && !isfinite(total)) ? 1 : 0;
+  const int64_t applied = state->applied_steps + (skip ? 0 : 1);
+  state->total_norm = total;
+  state->clip_coef = coef;
+  state->skip = skip;
+  state->applied_steps = applied;
+  state->skipped_steps += skip;
+  const double bc1 = 1.0 - pow((double)beta1, (double)applied), bc2 = 1.0 - pow((double)beta2, (double)applied);
+  state->bc1 = (float)bc1;
+  state->bc2_sqrt = (float)sqrt(bc2);
+}
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                   float eps, float grad_scale) {
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return;
+  if (state->skip) return;                              // a skipped step writes nothing: p, m, v stay bit for bit
+  const OptBlock b = opt_blocks(table, h.n_ranges)[blockIdx.x];
+  if (b.range < 0 || b.range >= h.n_ranges) return;
+  const avmoe_opt_range r = opt_ranges(table)[b.range];
+  const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
+  if (i0 >= r.n) return;
+  // one multiplier for the gradient: grad_scale * clip factor (== grad_scale exactly when the factor is 1)
+  adam_quad<DECOUPLED>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, i0, (long)r.n, r.lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
+                       grad_scale * state->clip_coef);
+}
+
+static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
+
+// host-side validation of a range list -> OK and the block count, or the error
+static int check_ranges(const char* who, const avmoe_opt_range* ranges, int32_t n_ranges, int64_t* n_blocks) {
+  if (n_ranges < 0) { set_last_error("%s: negative range count %d", who, (int)n_ranges); return ERR_BAD_ARG; }
+  if (n_ranges > 0 && !ranges) { set_last_error("%s: ranges is NULL", who); return ERR_BAD_ARG; }
+  int64_t nb = 0;
+  for (int32_t i = 0; i < n_ranges; ++i) {
+    const avmoe_opt_range& r = ranges[i];
+    if (r.n < 0) { set_last_error("%s: range %d has negative length %lld", who, (int)i, (long long)r.n); return ERR_BAD_ARG; }
+    if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq) { set_last_error("%s: range %d has a NULL pointer", who, (int)i); return ERR_BAD_ARG; }
+    if (!(r.lr == r.lr) || !(r.weight_decay == r.weight_decay)) { set_last_error("%s: range %d has a NaN lr / weight_decay", who, (int)i); return ERR_BAD_ARG; }
+    if ((((uintptr_t)r.param | (uintptr_t)r.grad | (uintptr_t)r.exp_avg | (uintptr_t)r.exp_avg_sq) & 15u) != 0) {
+      set_last_error("%s: range %d does not start 16-byte aligned", who, (int)i); return ERR_ALIGNMENT;
+    }
+    if (r.n > ((int64_t)INT32_MAX - 1) * OPT_BLOCK) { set_last_error("%s: range %d is too long", who, (int)i); return ERR_UNSUPPORTED; }
+    nb += range_blocks(r.n);
+  }
+  if (nb > (int64_t)INT32_MAX) { set_last_error("%s: more than 2^31 blocks", who); return ERR_UNSUPPORTED; }
+  *n_blocks = nb;
+  return OK;
+}
+
+static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+static size_t table_bytes_of(int32_t n_ranges, int64_t n_blocks) {
+  return round16(sizeof(OptHeader) + (size_t)n_ranges * sizeof(avmoe_opt_range) + (size_t)n_blocks * sizeof(OptBlock));
+}
+
+static int check_launch_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const void* state, float beta1, float beta2) {
+  if (!table || !state) { set_last_error("%s: NULL table / state", who); return ERR_BAD_ARG; }
+  if (n_ranges < 0 || n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("%s: bad range / block count", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)state & 15u) != 0) { set_last_error("%s: the state block must be 16-byte aligned", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)table & 15u) != 0) { set_last_error("%s: the table must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) { set_last_error("%s: betas must be in [0, 1)", who); return ERR_BAD_ARG; }
+  return OK;
+}
+
+}  // namespace avmoe
+
+using namespace avmoe;
+
+extern "C" {
+
+size_t avmoe_opt_workspace_bytes(const avmoe_opt_range* ranges, int32_t n_ranges, avmoe_opt_layout* layout) {
+  int64_t nb = 0;
+  if (check_ranges("avmoe_opt_workspace_bytes", ranges, n_ranges, &nb) != OK) return 0;
+  avmoe_opt_layout l;
+  l.state_bytes = sizeof(avmoe_opt_state);
+  l.table_bytes = table_bytes_of(n_ranges, nb);
+  l.partial_bytes = round16((size_t)(nb > 0 ? nb : 1) * sizeof(double));
+  l.n_blocks = nb;
+  if (layout) *layout = l;
+  return l.state_bytes + l.table_bytes + l.partial_bytes;
+}
+
+int avmoe_opt_table_build(const avmoe_opt_range* ranges, int32_t n_ranges, void* image, size_t image_bytes) {
+  int64_t nb = 0;
+  AVMOE_TRY(check_ranges("avmoe_opt_table_build", ranges, n_ranges, &nb));
+  if (!image) { set_last_error("avmoe_opt_table_build: image is NULL"); return ERR_BAD_ARG; }
+  const size_t need = table_bytes_of(n_ranges, nb);
+  if (image_bytes < need) { set_last_error("avmoe_opt_table_build: image of %zu bytes, %zu needed", image_bytes, need); return ERR_WORKSPACE; }
+  char* p = (char*)image;
+  memset(p, 0, need);
+  OptHeader h{OPT_MAGIC, n_ranges, nb};
+  memcpy(p, &h, sizeof h);
+  if (n_ranges > 0) memcpy(p + sizeof h, ranges, (size_t)n_ranges * sizeof(avmoe_opt_range));
+  OptBlock* bm = (OptBlock*)(p + sizeof h + (size_t)n_ranges * sizeof(avmoe_opt_range));
+  for (int32_t i = 0; i < n_ranges; ++i)
+    for (long b = 0, e = range_blocks(ranges[i].n); b < e; ++b) *bm++ = OptBlock{i, (int32_t)b};
+  return OK;
+}
+
+int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                        float max_norm, int32_t flags, float beta1, float beta2, void* stream) {
+  AVMOE_TRY(check_launch_args("avmoe_opt_grad_norm", table, n_ranges, n_blocks, state, beta1, beta2));
+  const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
+  if ((flags & ~(AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY)) != 0) { set_last_error("avmoe_opt_grad_norm: unknown flag"); return ERR_BAD_ARG; }
+  if (clip && !(max_norm >= 0.f)) { set_last_error("avmoe_opt_grad_norm: max_norm must be >= 0 and not NaN"); return ERR_BAD_ARG; }
+  if (!(grad_scale == grad_scale)) { set_last_error("avmoe_opt_grad_norm: grad_scale is NaN"); return ERR_BAD_ARG; }
+  const bool norm = (clip || skip) && n_blocks > 0;
+  if (norm) {
+    if (!partials) { set_last_error("avmoe_opt_grad_norm: partials is NULL"); return ERR_BAD_ARG; }
+    if (((uintptr_t)partials & 7u) != 0) { set_last_error("avmoe_opt_grad_norm: partials must be 8-byte aligned"); return ERR_ALIGNMENT; }
+    hipLaunchKernelGGL(kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials, grad_scale);
+    AVMOE_CHECK_LAUNCH("opt_sqsum");
+  }
+  hipLaunchKernelGGL(kk_opt_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state, max_norm,
+                     (int)clip, (int)skip, beta1, beta2);
+  AVMOE_CHECK_LAUNCH("opt_finalize");
+  return OK;
+}
+
+int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
+                        float grad_scale, int32_t flags, void* stream) {
+  AVMOE_TRY(check_launch_args("avmoe_opt_adam_step", table, n_ranges, n_blocks, state, beta1, beta2));
+  if ((flags & ~(AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY)) != 0) { set_last_error("avmoe_opt_adam_step: unknown flag"); return ERR_BAD_ARG; }
+  if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("avmoe_opt_adam_step: eps must be >= 0, grad_scale not NaN"); return ERR_BAD_ARG; }
+  if (n_blocks == 0) return OK;
+  if (flags & AVMOE_OPT_DECOUPLED_DECAY)
+    hipLaunchKernelGGL(kk_opt_adam<true>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);
+  else
+    hipLaunchKernelGGL(kk_opt_adam<false>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);
+  AVMOE_CHECK_LAUNCH("opt_adam");
+  return OK;
+}
+
+}  // extern "C"

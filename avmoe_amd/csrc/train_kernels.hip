@@ -3,6 +3,7 @@
 // device-side expert-activation histogram (the reference loops over idx.tolist() on the host, main_trans_v3.py:183-207).
 #include "../../include/avmoe.h"
 #include "common.h"
+#include "adam_elem.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -10,7 +11,8 @@
 
 namespace avmoe {
 
-// torch.optim.Adam semantics (no amsgrad, L2 weight decay added to the gradient), one thread per 4 elements
+// torch.optim.Adam semantics (no amsgrad, L2 weight decay added to the gradient), one thread per 4 elements; the 16-byte body's element
+// update is adam_elem (adam_elem.h), shared with the multi-range kernel of opt_kernels.hip
 __global__ void __launch_bounds__(256) kk_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                                                float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale) {
   const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -20,12 +22,7 @@ __global__ void __launch_bounds__(256) kk_adam(float* __restrict__ p, const floa
     const float4 gg = *(const float4*)(g + i0);
     float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; const float* G = (const float*)&gg;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gr = G[k] * gscale + wd * P[k];
-      M[k] = b1 * M[k] + (1.f - b1) * gr;
-      V[k] = b2 * V[k] + (1.f - b2) * gr * gr;
-      P[k] -= (lr / bc1) * M[k] / (sqrtf(V[k]) / bc2_sqrt + eps);
-    }
+    for (int k = 0; k < 4; ++k) adam_elem<false>(P[k], M[k], V[k], G[k], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
     *(float4*)(p + i0) = pp; *(float4*)(m + i0) = mm; *(float4*)(v + i0) = vv;
   } else {
     for (long i = i0; i < n; ++i) {

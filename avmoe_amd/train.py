@@ -3,23 +3,28 @@
   * `select_trainable`      -- the parameter-freezing / LR-group rule of AVE/main_trans_v3.py:264-315
   * `FlatAdam`              -- torch.optim.Adam semantics as ONE HIP kernel per flat gradient bucket of an
                                `AdapterGradReducer` (parameters are re-pointed to views of a flat buffer with the bucket's
-                               layout), StepLR-style decay; replaces optimizer.step() at main_trans_v3.py:136-138,322-323
+                               layout), StepLR-style decay; replaces optimizer.step() at main_trans_v3.py:136-138,322-323.
+                               Opt-in: global-norm clipping, AdamW, skipping of non-finite steps with the optimizer state on
+                               the device (three launches per step for all buckets, graph-capturable); state_dict() /
+                               load_state_dict() in torch.optim.Adam's format
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
                                site), main_trans_v3.py:155-226
   * `save_adapters` / `load_adapters` / `strip_prefix` -- adapter-only checkpoints with the reference's state_dict keys
                                (strict=False load of released checkpoints, main_trans_v3.py:254; HTS-AT key strip,
                                net_trans_v3.py:560-563)
 
-Everything here is host logic around three tiny C-ABI entry points (avmoe_adam_step, avmoe_expert_histogram); nothing
-falls back to the CPU for GPU tensors."""
+Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm / avmoe_opt_adam_step,
+avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
 import ctypes as C
+from itertools import chain
 from typing import Dict, Iterable, List, Optional
 
 import torch
 
 from . import _capi as capi
+from . import _capi_moe as cm
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -52,11 +57,34 @@ class FlatAdam:
         ...  red.begin(sync); loss.backward(); red.finish()
         if sync: opt.step(); red.zero_grad()
         opt.epoch_end()                      # StepLR.step()
+
+    The device path.  With any of `max_grad_norm`, `decoupled_weight_decay`, `skip_nonfinite` set, a step is three launches for ALL buckets
+    (include/avmoe.h, "optimizer with device-side state"): the squared-gradient sums of every parameter element in double, a one-block
+    finalize that writes norm, clip factor, skip flag, step counters and bias corrections into a 64-byte state block on the device, and
+    one Adam / AdamW update that reads them (without clipping and skipping: finalize + update).  No host synchronisation, no allocation
+    and no step-dependent host scalar, so `step()` can be captured by torch.cuda.graph (one stream, linear) and replayed; the plain path
+    bakes the bias correction of `self.t` into its kernel arguments and is not capturable in a meaningful way.  The clip factor is
+    applied inside the update: the gradient buckets are NOT rescaled (torch.nn.utils.clip_grad_norm_ rescales `.grad` in place).  The
+    norm covers the parameters the reducer holds, alignment padding excluded; parameters outside the reducer (a partly frozen site that
+    falls back to autograd accumulation, anything not handed to AdapterGradReducer) are neither clipped nor counted.  Under data
+    parallelism call `red.finish()` first: the norm is then that of the averaged gradient, identical on every rank.
+    `last_grad_norm`, `applied_steps`, `skipped_steps` are DEVICE tensors (views of the state block): reading them is the caller's sync.
+
+    Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
+    tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
+    counters, options) that torch ignores.  Index i is the position of the parameter in `opt.params` -- the order in which the reducer
+    holds the parameters: bucket by bucket, inside a bucket the sites in reverse execution order with each site's parameters in its
+    grad_layout() order, then the plain parameters in reverse order.  A torch optimizer built as
+    `torch.optim.AdamW(opt.torch_param_groups())` (or `Adam`) loads the dict, and a dict from such an optimizer loads here.
     """
 
     def __init__(self, reducer, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None):
-        """param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
+                 step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
+                 max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False):
+        """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
+        term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  Any of the three
+        selects the device path (class docstring); with all three at their defaults step() is the per-bucket avmoe_adam_step path.
+        param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
         reference's `lr_mlp` for the classifier head vs `lr` for the adapters); parameters not listed use `lr`.  Inside a
         bucket, neighbouring parameters with the same rate share one kernel launch (an adapter site is one range)."""
@@ -64,6 +92,11 @@ class FlatAdam:
         self.step_size, self.gamma, self.grad_scale = step_size, gamma, grad_scale
         self.t, self.epoch = 0, 0
         self.state = []
+        if max_grad_norm is not None and not (float(max_grad_norm) >= 0.0):
+            raise ValueError("max_grad_norm must be >= 0")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.decoupled_weight_decay, self.skip_nonfinite = bool(decoupled_weight_decay), bool(skip_nonfinite)
+        self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
         lr_of = {}
         for grp in (param_groups or []):
             ps = grp["params"]
@@ -74,7 +107,6 @@ class FlatAdam:
             if not flat_g.is_cuda:
                 raise capi.AvmoeError("FlatAdam updates GPU buckets (no CPU fallback)")
             flat_p = torch.zeros_like(flat_g)
-            spans = []                                   # (offset, end, lr) per parameter, in bucket order
             for p in b.params:                           # parameter offsets = offsets of their .grad views in the bucket
                 off = (p.grad.data_ptr() - flat_g.data_ptr()) // 4
                 view = flat_p[off:off + p.numel()].view_as(p)
@@ -83,16 +115,100 @@ class FlatAdam:
                 if view.data_ptr() % 16:
                     raise capi.AvmoeError("FlatAdam: a re-pointed parameter is not 16-byte aligned (the GEMM engine needs "
                                           "aligned operands); build the reducer with aligned buckets (avmoe_amd.dp)")
-                spans.append((off, off + p.numel(), lr_of.get(id(p), float(lr))))
-            spans.sort()
-            ranges = []                                  # merged [begin, end, lr0]: alignment padding rides with its left neighbour
-            for i, (o, e, r) in enumerate(spans):
-                end = spans[i + 1][0] if i + 1 < len(spans) else flat_g.numel()
-                if ranges and ranges[-1][2] == r:
-                    ranges[-1][1] = end
-                else:
-                    ranges.append([o if ranges else 0, end, r])
-            self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=ranges))
+                self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
+            self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
+        self._rebuild_plain_ranges()
+        self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite
+        if self._device:
+            self._build_device_state()
+
+    # ---- the device path ------------------------------------------------------------------------------------------
+    def _opt_ranges(self):
+        """one avmoe_opt_range per parameter (its own elements only: the norm must not see alignment padding)"""
+        arr = (cm.OptRange * len(self._plist))()
+        for r, (p, si, off, lr0) in zip(arr, self._plist):
+            s = self.state[si]
+            r.param, r.grad, r.exp_avg, r.exp_avg_sq = (s[k].data_ptr() + 4 * off for k in ("p", "g", "m", "v"))
+            r.n, r.lr, r.weight_decay = p.numel(), lr0 * self.decay, self.wd
+        return arr
+
+    def _build_device_state(self):
+        L = capi.lib()
+        if not hasattr(L, "avmoe_opt_adam_step"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks the device-side optimizer (avmoe_opt_*): rebuild it")
+        devs = {s["p"].device for s in self.state}
+        if len(devs) != 1:
+            raise capi.AvmoeError("FlatAdam's device path needs every bucket on one GPU")
+        self._dev = devs.pop()
+        lay = cm.OptLayout()
+        total = L.avmoe_opt_workspace_bytes(self._opt_ranges(), len(self._plist), C.byref(lay))
+        if total == 0:
+            capi.check(-1, "avmoe_opt_workspace_bytes")
+        self._n_blocks, self._table_bytes = int(lay.n_blocks), int(lay.table_bytes)
+        self._ws = torch.zeros(total, dtype=torch.uint8, device=self._dev)          # [state block | table | partial sums]
+        sb = int(lay.state_bytes)
+        self._state_ptr, self._table_ptr = self._ws.data_ptr(), self._ws.data_ptr() + sb
+        self._partials_ptr = self._table_ptr + self._table_bytes
+        self._views = {k: self._ws[o:o + (8 if dt == "int64" else 4)].view(getattr(torch, dt))[0]
+                       for k, (o, dt) in cm.OPT_STATE_FIELDS.items()}
+        self._flags = (cm.OPT_CLIP if self.max_grad_norm is not None else 0) | (cm.OPT_SKIP_NONFINITE if self.skip_nonfinite else 0) \
+            | (cm.OPT_DECOUPLED_DECAY if self.decoupled_weight_decay else 0)
+        self._upload_table()
+
+    def _upload_table(self):
+        """(re)build the range table with the learning rates of the current epoch and send it with ONE asynchronous copy"""
+        img = torch.empty(self._table_bytes, dtype=torch.uint8, pin_memory=True)
+        capi.check(capi.lib().avmoe_opt_table_build(self._opt_ranges(), len(self._plist), img.data_ptr(), self._table_bytes),
+                   "avmoe_opt_table_build")
+        sb = cm.OPT_STATE_BYTES
+        self._ws[sb:sb + self._table_bytes].copy_(img, non_blocking=True)
+        self._table_decay = self.decay
+
+    def _state_view(self, name):
+        if not self._device:
+            raise capi.AvmoeError(f"FlatAdam.{name} lives in the device state block: set max_grad_norm, decoupled_weight_decay or "
+                                  "skip_nonfinite")
+        return self._views[name]
+
+    @property
+    def last_grad_norm(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the global norm of (gradient * grad_scale) the last step() saw, before clipping (0 when neither clipping
+        nor skipping is on).  A view of the state block: `.item()` is the caller's synchronisation."""
+        return self._state_view("total_norm")
+
+    @property
+    def applied_steps(self) -> torch.Tensor:
+        """int64 DEVICE scalar: steps that updated the parameters (what the bias correction counts); `self.t` counts step() calls."""
+        return self._state_view("applied_steps")
+
+    @property
+    def skipped_steps(self) -> torch.Tensor:
+        """int64 DEVICE scalar: steps held back because the gradient norm was not finite."""
+        return self._state_view("skipped_steps")
+
+    @property
+    def state_block(self) -> Dict[str, torch.Tensor]:
+        """every field of the device state block (avmoe_opt_state) as a DEVICE scalar view: total_norm, clip_coef, bc1, bc2_sqrt,
+        applied_steps, skipped_steps, skip"""
+        self._state_view("total_norm")
+        return dict(self._views)
+
+    @property
+    def params(self) -> List[torch.nn.Parameter]:
+        """the parameters in the reducer's order -- the index order of state_dict()"""
+        return [e[0] for e in self._plist]
+
+    def _groups(self):
+        """[(lr0, [indices into self.params])]: one group per distinct base learning rate, in order of first appearance"""
+        out = {}
+        for i, e in enumerate(self._plist):
+            out.setdefault(e[3], []).append(i)
+        return list(out.items())
+
+    def torch_param_groups(self) -> List[dict]:
+        """param groups for torch.optim.Adam / AdamW over the same parameters, in the grouping and order state_dict() uses"""
+        ps = self.params
+        return [{"params": [ps[i] for i in idx], "lr": lr0 * self.decay} for lr0, idx in self._groups()]
 
     @property
     def decay(self) -> float:
@@ -108,6 +224,15 @@ class FlatAdam:
         self.t += 1
         # 1 / world of a sum-reducing AdapterGradReducer(average="optimizer") rides in the kernel's gradient scale: no division pass
         scale = self.grad_scale * float(getattr(self.reducer, "grad_scale", 1.0))
+        if self._device:                                 # every bucket at once, scalars from the device state block
+            stream = torch.cuda.current_stream(self._dev).cuda_stream
+            n = len(self._plist)
+            capi.check(L.avmoe_opt_grad_norm(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                             self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream),
+                       "avmoe_opt_grad_norm")
+            capi.check(L.avmoe_opt_adam_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
+                                             self.eps, scale, self._flags, stream), "avmoe_opt_adam_step")
+            return
         for s in self.state:
             for (o, e, r) in s["ranges"]:
                 st = L.avmoe_adam_step(s["p"].data_ptr() + 4 * o, s["g"].data_ptr() + 4 * o, s["m"].data_ptr() + 4 * o,
@@ -119,6 +244,102 @@ class FlatAdam:
 
     def epoch_end(self):
         self.epoch += 1
+        if self._device and self.decay != self._table_decay:      # the learning rates live in the table: one async copy, stream-ordered
+            self._upload_table()
+
+    # ---- resume ---------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """torch.optim.Adam's format (class docstring).  A parameter's `step` is `self.t` on the plain path and `applied_steps` on the
+        device path -- reading it makes state_dict() a synchronisation point, as the copies of the moments to the CPU are anyway."""
+        applied = int(self.applied_steps.item()) if self._device else self.t
+        skipped = int(self.skipped_steps.item()) if self._device else 0
+        state = {}
+        for i, (p, si, off, _lr0) in enumerate(self._plist):
+            s, n = self.state[si], p.numel()
+            state[i] = {"step": torch.tensor(float(applied)),
+                        "exp_avg": s["m"][off:off + n].view_as(p).detach().cpu().clone(),
+                        "exp_avg_sq": s["v"][off:off + n].view_as(p).detach().cpu().clone()}
+        groups = [{"lr": lr0 * self.decay, "initial_lr": lr0, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
+                   "params": list(idx)} for lr0, idx in self._groups()]
+        extra = {"t": self.t, "epoch": self.epoch, "applied_steps": applied, "skipped_steps": skipped,
+                 "max_grad_norm": self.max_grad_norm, "decoupled_weight_decay": self.decoupled_weight_decay,
+                 "skip_nonfinite": self.skip_nonfinite, "step_size": self.step_size, "gamma": self.gamma}
+        return {"state": state, "param_groups": groups, "flat_adam": extra}
+
+    def load_state_dict(self, sd: dict):
+        """Writes the moments into the flat buffers, the counters into the state block, and restores t, epoch and the groups' lr / betas /
+        eps / weight_decay.  Saved parameters are matched to `self.params` by position across the groups, as torch.optim does; the three
+        path options stay what the constructor was given (the saved ones are informative), unknown keys are ignored.  A count or shape
+        mismatch raises ValueError naming the parameter index."""
+        saved_groups, own_groups = sd["param_groups"], self._groups()
+        if len(saved_groups) != len(own_groups):
+            raise ValueError(f"state dict has {len(saved_groups)} parameter groups, this optimizer {len(own_groups)}")
+        for gi, (sg, (_lr0, idx)) in enumerate(zip(saved_groups, own_groups)):
+            if len(sg["params"]) != len(idx):
+                raise ValueError(f"parameter group {gi}: state dict lists {len(sg['params'])} parameters, this optimizer {len(idx)} "
+                                 f"(first own parameter index {idx[0]})")
+        id_map = dict(zip(chain.from_iterable(g["params"] for g in saved_groups), chain.from_iterable(idx for _, idx in own_groups)))
+        todo, steps = [], set()
+        for k, st in sd["state"].items():
+            if k not in id_map:
+                raise ValueError(f"state dict has state for parameter index {k}, which no parameter group lists")
+            i = id_map[k]
+            p, si, off, _lr0 = self._plist[i]
+            for name in ("exp_avg", "exp_avg_sq"):
+                if name not in st or tuple(st[name].shape) != tuple(p.shape):
+                    got = tuple(st[name].shape) if name in st else None
+                    raise ValueError(f"parameter index {i}: {name} has shape {got}, the parameter {tuple(p.shape)}")
+            steps.add(int(float(st["step"])))
+            todo.append((i, st))
+        if todo and len(todo) != len(self._plist):
+            missing = sorted(set(range(len(self._plist))) - {i for i, _ in todo})
+            raise ValueError(f"state dict has no state for parameter index {missing[0]} ({len(missing)} missing; FlatAdam steps all its "
+                             "parameters together)")
+        if len(steps) > 1:
+            raise ValueError(f"parameters carry different step counts {sorted(steps)}: FlatAdam keeps one count for all")
+        extra = sd.get("flat_adam", {})
+        applied = int(extra.get("applied_steps", steps.pop() if steps else 0))
+        with torch.no_grad():
+            if not todo:
+                for s in self.state:
+                    s["m"].zero_(); s["v"].zero_()
+            for i, st in todo:
+                p, si, off, _lr0 = self._plist[i]
+                s, n = self.state[si], p.numel()
+                s["m"][off:off + n].copy_(st["exp_avg"].reshape(-1).to(torch.float32))
+                s["v"][off:off + n].copy_(st["exp_avg_sq"].reshape(-1).to(torch.float32))
+            self.epoch = int(extra.get("epoch", self.epoch))
+            self.step_size, self.gamma = extra.get("step_size", self.step_size), extra.get("gamma", self.gamma)
+            g0 = saved_groups[0]
+            self.betas, self.eps, self.wd = tuple(g0.get("betas", self.betas)), g0.get("eps", self.eps), g0.get("weight_decay", self.wd)
+            lr0s = [float(sg["initial_lr"]) if "initial_lr" in sg else float(sg["lr"]) / self.decay for sg in saved_groups]
+            for (lr_old, idx), lr_new in zip(own_groups, lr0s):
+                for i in idx:
+                    self._plist[i] = self._plist[i][:3] + (lr_new,)
+            if len(own_groups) == 1:
+                self.lr0 = lr0s[0]
+            self._rebuild_plain_ranges()
+            if self._device:
+                self.t = int(extra.get("t", applied + int(extra.get("skipped_steps", 0))))
+                self._views["applied_steps"].fill_(applied)
+                self._views["skipped_steps"].fill_(int(extra.get("skipped_steps", 0)))
+                self._upload_table()
+            else:
+                self.t = applied                          # the plain path's bias correction counts self.t
+
+    def _rebuild_plain_ranges(self):
+        """the plain path's merged [begin, end, lr0] ranges per bucket from the per-parameter learning rates: neighbouring parameters
+        with the same rate share one kernel launch, alignment padding rides with its left neighbour"""
+        for si, s in enumerate(self.state):
+            spans = sorted((off, off + p.numel(), lr0) for (p, sj, off, lr0) in self._plist if sj == si)
+            ranges = []
+            for i, (o, e, r) in enumerate(spans):
+                end = spans[i + 1][0] if i + 1 < len(spans) else s["g"].numel()
+                if ranges and ranges[-1][2] == r:
+                    ranges[-1][1] = end
+                else:
+                    ranges.append([o if ranges else 0, end, r])
+            s["ranges"] = ranges
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -279,6 +279,68 @@ int avmoe_add2(void* dst1, const void* src1, int64_t n1, void* dst2, const void*
  * first-max argmax.  It only reports the selection; a top-k MIXTURE is avmoe_moe_forward_topk.                           */
 int avmoe_router_topk(const float* probs, int64_t S, int32_t E, int32_t k, int64_t* idx, void* stream);
 
+/* ---- optimizer with device-side state (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds these by symbol) ----------
+ * Global-norm gradient clipping, Adam / AdamW, skipping of a step whose gradient is not finite, and a step count that lives on the
+ * device -- over EVERY flat range the optimizer owns in three launches per step whatever the number of buckets and ranges (two when
+ * neither clipping nor skipping is asked for), without a host synchronisation and without a host scalar that changes from step to
+ * step, so a step can be captured into a graph and replayed.  avmoe_adam_step above is unchanged and stays the plain path.
+ *
+ * The range table.  One avmoe_opt_range per flat range: four DEVICE pointers to n fp32 elements each (16-byte aligned: AVMOE_ERR_ALIGNMENT
+ * otherwise), the range's learning rate and weight decay.  A norm counts exactly the n elements of every range: alignment padding
+ * between the parameters of a bucket belongs to no range.  avmoe_opt_table_build writes the table IMAGE (the ranges and a block -> range
+ * map, one block per 1024 elements) into HOST memory of the caller, who copies it to the device -- once, and again when a learning rate
+ * changes (the library never allocates and never copies).  avmoe_opt_workspace_bytes returns the device bytes of state block + table +
+ * partial sums (each a multiple of 16; 0 and an error string on a bad range list) and fills `layout` (may be NULL).
+ *
+ * The state block (device, 16-byte aligned, zeroed by the caller before the first step) is written by avmoe_opt_grad_norm and read by
+ * avmoe_opt_adam_step; a caller may read it back for logging or write the counters to resume a run.                                     */
+typedef struct avmoe_opt_range {
+  float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
+  int64_t n;
+  float lr, weight_decay;
+} avmoe_opt_range;
+
+typedef struct avmoe_opt_state {
+  float total_norm;           /* sqrt(sum (grad * grad_scale)^2) over every element of every range; 0 when no norm was asked for */
+  float clip_coef;            /* min(1, max_norm / (total_norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_; exactly 1 when clipping is off */
+  float bc1, bc2_sqrt;        /* 1 - beta1^applied_steps ; sqrt(1 - beta2^applied_steps): computed in double, rounded to fp32 */
+  int64_t applied_steps;      /* steps that updated the parameters */
+  int64_t skipped_steps;      /* steps held back because the norm was not finite */
+  int32_t skip;               /* this step is held back */
+  int32_t reserved[7];
+} avmoe_opt_state;
+
+typedef struct avmoe_opt_layout { size_t state_bytes, table_bytes, partial_bytes; int64_t n_blocks; } avmoe_opt_layout;
+
+enum { AVMOE_OPT_CLIP = 1, AVMOE_OPT_SKIP_NONFINITE = 2, AVMOE_OPT_DECOUPLED_DECAY = 4 };
+
+size_t avmoe_opt_workspace_bytes(const avmoe_opt_range* ranges /* HOST */, int32_t n_ranges, avmoe_opt_layout* layout /* HOST, or NULL */);
+int avmoe_opt_table_build(const avmoe_opt_range* ranges /* HOST */, int32_t n_ranges, void* image /* HOST, layout.table_bytes */,
+                          size_t image_bytes);
+
+/* The norm pass and its finalize step.  One launch over all ranges squares every element as a double ((double)grad * grad_scale) and
+ * leaves one double per block in `partials` (layout.partial_bytes); one more launch of a single block adds them in a fixed order -- no
+ * floating-point atomics, the same input gives the same bits -- and its last thread writes the state block:
+ *     total_norm, clip_coef (AVMOE_OPT_CLIP; max_norm >= 0), skip = AVMOE_OPT_SKIP_NONFINITE && !isfinite(total_norm),
+ *     applied_steps += !skip, skipped_steps += skip, bc1, bc2_sqrt for the new applied_steps.
+ * With neither flag the norm launch is left out (total_norm = 0) and only the counters and bias corrections advance.  The sum is exact
+ * to double rounding, so total_norm is the true norm to two fp32 roundings.  `table`, n_ranges, n_blocks: the image on the device and
+ * what it was built for (a kernel whose grid does not match its table's header does nothing).
+ *
+ * The update.  One launch walks the table; per element g = grad * (grad_scale * clip_coef), then
+ *     coupled decay (default): exactly avmoe_adam_step's arithmetic (g += weight_decay * p ; exp_avg, exp_avg_sq, p) -- bit-equal to it
+ *                              where clip_coef is 1 and the bias corrections agree;
+ *     AVMOE_OPT_DECOUPLED_DECAY: p *= 1 - lr * weight_decay first, then the update without the decay term (torch.optim.AdamW).
+ * When `skip` is set nothing is written.  The GRADIENT buffers are never written: unlike torch.nn.utils.clip_grad_norm_, which rescales
+ * the gradients in place, the factor is applied inside the update, and a caller that reads the gradients afterwards sees them unclipped.
+ * Call avmoe_opt_grad_norm before avmoe_opt_adam_step on the same stream, with the same grad_scale and betas, every step.
+ * Errors (before any launch): AVMOE_ERR_BAD_ARG for NULL pointers, a negative range count / length, max_norm negative or NaN, betas
+ * outside [0, 1), a state block that is not 16-byte aligned; AVMOE_ERR_ALIGNMENT for a table entry or table that is not.               */
+int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                        float max_norm, int32_t flags, float beta1, float beta2, void* stream);
+int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                        float eps, float grad_scale, int32_t flags, void* stream);
+
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the
  * tiled engine is faster.  force_mask lifts those thresholds so that a test can run the benchmarked kernels on shapes its oracle

@@ -1,0 +1,80 @@
+"""Driver for a kernel trace of the optimizer step (DESIGN_CURRENT.md section 4b):
+
+    rocprofv3 --kernel-trace --stats -d OUT -o NAME -- python scripts/flat_adam_step_profile.py --model eight_site --mode device
+
+--mode device      FlatAdam(max_grad_norm=..., skip_nonfinite=True).step(): three launches whatever the model
+--mode clip_plain  torch.nn.utils.clip_grad_norm_ over the bucket views + the plain FlatAdam.step() (one avmoe_adam_step per merged range)
+--model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
+
+The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
+JSON line: launches per step are the trace's calls / steps; `step_us` is the event-timed mean of --steps steps enqueued back to back,
+`step_wall_us` the host time to enqueue one step (the launch-bound side)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def build(model_name, dev):
+    from avmoe_amd.adapters import MoEAdapter
+    if model_name == "two_bucket":
+        from tests.test_flat_adam_device_gpu import make_model
+        m = make_model(dev)
+        return m.all_params(), [m.site], m
+    from tests.test_training_loop_gpu import TinyModel
+    from avmoe_amd.train import select_trainable
+    torch.manual_seed(11)
+    m = TinyModel(64, 100, 48, 160).to(dev)
+    groups = select_trainable(m, lr=5e-3, lr_mlp=5e-3)
+    return [g["params"] for g in groups if g["params"].requires_grad], [s for s in m.modules() if isinstance(s, MoEAdapter)], m
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=["two_bucket", "eight_site"], default="eight_site")
+    ap.add_argument("--mode", choices=["device", "clip_plain"], default="device")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    from avmoe_amd.dp import AdapterGradReducer
+    from avmoe_amd.train import FlatAdam
+    dev = torch.device("cuda:0")
+    params, sites, model = build(a.model, dev)
+    red = AdapterGradReducer(params, sites=sites)
+    kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if a.mode == "device" else {}
+    opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
+    g = torch.Generator().manual_seed(0)
+    for b in red.buckets:
+        b.flat.copy_(torch.randn(b.flat.numel(), generator=g))
+    grads = [p for p in params]
+
+    def step():
+        if a.mode == "clip_plain":
+            torch.nn.utils.clip_grad_norm_(grads, 1.0)
+        opt.step()
+
+    for _ in range(a.warmup):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0 = time.perf_counter()
+    e0.record()
+    for _ in range(a.steps):
+        step()
+    e1.record()
+    wall = time.perf_counter() - t0
+    torch.cuda.synchronize()
+    print(json.dumps({"model": a.model, "mode": a.mode, "steps": a.steps, "warmup": a.warmup, "buckets": len(red.buckets),
+                      "parameters": len(params), "elements": sum(p.numel() for p in params),
+                      "plain_launches_per_step": sum(len(s["ranges"]) for s in opt.state),
+                      "step_us": round(1e3 * e0.elapsed_time(e1) / a.steps, 2), "step_wall_us": round(1e6 * wall / a.steps, 2)}))
+
+
+if __name__ == "__main__":
+    main()
