@@ -10,22 +10,9 @@
 
 namespace avmoe {
 
-#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
-  do {                                                                                        \
-    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
-    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
-  } while (0)
-
-__device__ __forceinline__ void wave_lds_sync_b() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 template <typename T> __device__ __forceinline__ float roundTb(float v);
 template <> __device__ __forceinline__ float roundTb<float>(float v) { return v; }
 template <> __device__ __forceinline__ float roundTb<__bf16>(float v) { return bf2f(f2bf(v)); }
-
-static inline unsigned grid1db(long n, int cap = 4096) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
 
 // (the per-token backward kernels live in tile_kernels.hip; this file keeps their finalize / weight-space parts)
@@ -278,9 +265,9 @@ __global__ void __launch_bounds__(256) kk_router_bwd_fin(int S, int E, int C2, i
   const long per = 128L * C2;
   const int nb_w = (int)gridDim.x - nb_small - nb_c;
   for (long idx = ((long)(blockIdx.x - nb_small - nb_c) * 256 + threadIdx.x) * 4; idx < per; idx += (long)nb_w * 1024) {
-    f32x4_t acc = *(const f32x4_t*)(slabs + idx);
-    for (int k = 1; k < ks; ++k) { const f32x4_t b = *(const f32x4_t*)(slabs + (long)k * per + idx); acc += b; }
-    *(f32x4_t*)(gW1 + idx) = acc;
+    f32x4 acc = *(const f32x4*)(slabs + idx);
+    for (int k = 1; k < ks; ++k) { const f32x4 b = *(const f32x4*)(slabs + (long)k * per + idx); acc += b; }
+    *(f32x4*)(gW1 + idx) = acc;
   }
 }
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
@@ -313,8 +300,8 @@ int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptr
     AVMOE_TRY(launch_gemm(g, st));
   }
   const int nb_small = cdiv(32 * 128 + d.E * 32 + 160 + d.E, 64);
-  const int nb_c = (int)grid1db((long)d.S * d.C, 512);
-  const int nb_w = (grads.r0_w && ks > 1) ? (int)grid1db(128L * 2 * d.C / 4, 512) : 0;
+  const int nb_c = (int)grid1d((long)d.S * d.C, 512);
+  const int nb_w = (grads.r0_w && ks > 1) ? (int)grid1d(128L * 2 * d.C / 4, 512) : 0;
   hipLaunchKernelGGL(kk_router_bwd_fin, dim3((unsigned)(nb_small + nb_c + nb_w)), dim3(256), 0, st, d.S, d.E, 2 * d.C, nb_small, nb_c,
                      (const float*)(scratch + pl.o_rbw), (const float*)(saved + pl.o_rh1), (const float*)(saved + pl.o_rh2),
                      grads.r0_w, grads.r0_b, grads.r2_w, grads.r2_b, grads.r4_w, grads.r4_b, (const float*)(scratch + pl.o_slabs), ks,
@@ -877,7 +864,7 @@ int k_nxn_rowdot(int bf16, const void* X, const float* y, long rows, int C, void
 int k_nxn_axpy(const Plan& pl, const void* X, char* saved, char* scratch, void* dX, int slot, int replaces, hipStream_t st) {
   ProfScope ps_("k_nxn_axpy", 0.0, 0.0, st);
   const Dims& d = pl.d;
-  DISPATCH_T(d.bf16, kk_nxn_axpy, dim3(grid1db((long)d.NT * d.C, 16384)), dim3(256), 0, st, X,
+  DISPATCH_T(d.bf16, kk_nxn_axpy, dim3(grid1d((long)d.NT * d.C, 16384)), dim3(256), 0, st, X,
              (const void*)(saved + pl.o_xr + (size_t)slot * d.NT * d.C * d.esz), (const float*)(scratch + pl.o_dsr) + (size_t)slot * 3 * d.NT,
              (long)d.NT, d.C, (void*)(scratch + pl.o_dxr), dX, replaces);
   AVMOE_CHECK_LAUNCH("nxn_axpy");

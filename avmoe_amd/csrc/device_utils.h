@@ -1,12 +1,28 @@
 // Small device helpers shared by the bottleneck-space kernels (wave64 reductions, T <-> f32).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include "stream_isa.h"      // the vector types (f32x4, u32x4, u32x2, ...) and the streaming kernels' inline-ISA helpers
+
+// launch KERN<__bf16> or KERN<float> by the run-time operand type
+#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
+  do {                                                                                        \
+    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
+    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
+  } while (0)
 
 namespace avmoe {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+// blocks of 256 threads for n elements, at most `cap` (grid-stride kernels)
+inline unsigned grid1d(long n, int cap = 4096) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
+
+// Wave-level LDS fence: what this wave wrote to the LDS is visible to its own lanes' reads behind it (release fence, wave barrier, acquire
+// fence -- no s_barrier: the other waves of the block are not involved).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 __device__ __forceinline__ float bf2f(unsigned short h) {
   return __builtin_bit_cast(float, ((unsigned int)h) << 16);
@@ -46,16 +62,16 @@ template <> __device__ __forceinline__ void stT<__bf16>(__bf16* p, long i, float
 template <typename T> __device__ __forceinline__ float4 ld4T(const T* p, long i);
 template <> __device__ __forceinline__ float4 ld4T<float>(const float* p, long i) { return *(const float4*)(p + i); }
 template <> __device__ __forceinline__ float4 ld4T<__bf16>(const __bf16* p, long i) {
-  const u32x2_t u = *(const u32x2_t*)((const unsigned short*)p + i);
+  const u32x2 u = *(const u32x2*)((const unsigned short*)p + i);
   return make_float4(__builtin_bit_cast(float, u[0] << 16), __builtin_bit_cast(float, u[0] & 0xffff0000u),
                      __builtin_bit_cast(float, u[1] << 16), __builtin_bit_cast(float, u[1] & 0xffff0000u));
 }
 template <typename T> __device__ __forceinline__ void st4T(T* p, long i, const float4& v);
 template <> __device__ __forceinline__ void st4T<float>(float* p, long i, const float4& v) { *(float4*)(p + i) = v; }
 template <> __device__ __forceinline__ void st4T<__bf16>(__bf16* p, long i, const float4& v) {
-  u32x2_t u;
+  u32x2 u;
   u[0] = (unsigned)f2bf(v.x) | ((unsigned)f2bf(v.y) << 16); u[1] = (unsigned)f2bf(v.z) | ((unsigned)f2bf(v.w) << 16);
-  *(u32x2_t*)((unsigned short*)p + i) = u;
+  *(u32x2*)((unsigned short*)p + i) = u;
 }
 
 // wave64 all-reduce (every lane gets the result)

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -29,14 +30,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
 
 struct DPairArgs {
   const char* dOut; long ldo;            // bf16 [tokens][ldo], group g at column g * 384
@@ -54,8 +47,6 @@ struct DPairArgs {
 constexpr int KS = 12, BM = 64, NTHR = 512, RB = KS * 64 + 16, STG = BM * RB, RBA = 144 * 2 + 16, STGA = BM * RBA;
 constexpr int DPAIR_LDS = 2 * STG + 2 * STGA + KS * 1024;
 
-__device__ __forceinline__ unsigned int f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
-
 __device__ __forceinline__ bf16x8 tr_frag(const char* ad, int rb) {      // [k = 8 rows from ad][16 columns] -> lane (r, q): column r, rows 0 .. 7 (ad already offset by lane)
   const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad));
   const s16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad + 4 * rb));
@@ -66,8 +57,6 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* ad, int rb) {      // [k =
 // The transposing LDS reads of the dBpost phase as inline assembly: for the intrinsic the compiler waits for EVERY outstanding direct-to-LDS
 // load first (it cannot tell that they go to the other buffer), which left the next tile's loads overlapping the dApost phase only.  The waits
 // for these reads are explicit (tr_wait*: the fragments pass through the wait so that their consumers stay behind it).
-template <int OFF>
-__device__ __forceinline__ void tr_issue(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
 template <int TK, int C0>     // three column tiles C0 .. C0 + 2 of the Apost tile, K step TK
 __device__ __forceinline__ void tr_issue_b3(u32x2 (&b)[3][2], unsigned lb) {
   tr_issue<TK * 32 * RBA + (C0 + 0) * 32>(b[0][0], lb); tr_issue<TK * 32 * RBA + (C0 + 0) * 32 + 4 * RBA>(b[0][1], lb);
@@ -80,15 +69,6 @@ __device__ __forceinline__ void tr_issue_a3(u32x2 (&a)[3][2], unsigned la) {
   tr_issue<TK * 32 * RB + 32>(a[1][0], la); tr_issue<TK * 32 * RB + 32 + 4 * RB>(a[1][1], la);
   tr_issue<TK * 32 * RB + 64>(a[2][0], la); tr_issue<TK * 32 * RB + 64 + 4 * RB>(a[2][1], la);
 }
-__device__ __forceinline__ void tr_wait3(u32x2 (&x)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]) :: "memory");
-}
-__device__ __forceinline__ void tr_wait6(u32x2 (&x)[3][2], u32x2 (&y)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]),
-               "+v"(y[0][0]), "+v"(y[0][1]), "+v"(y[1][0]), "+v"(y[1][1]), "+v"(y[2][0]), "+v"(y[2][1]) :: "memory");
-}
-__device__ __forceinline__ bf16x8 tr_pack(const u32x2 (&f)[2]) { return __builtin_bit_cast(bf16x8, u32x4{f[0][0], f[0][1], f[1][0], f[1][1]}); }
-
 __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* sB8 = smem + 2 * STG + 2 * STGA;
@@ -124,8 +104,6 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
   // The tiles go global -> LDS directly (global_load_lds_dwordx4: no staging registers -- the kernel sits at its 256): a wave-instruction
   // fills 1 KB of the LDS image IN ORDER, so lane l of piece j loads whatever belongs at 16-byte slot 64 j + l of the padded image
   // (row = slot / 49, chunk = slot % 49; the pad chunk of a row re-reads its neighbour).  49 pieces for dOut, 19 for Apost, dealt to the waves.
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   const long ldo = p.ldo, lda = p.lda;
   auto gload = [&](int buf, int tile) {
     const long m0 = (long)tile * BM;
@@ -136,11 +114,11 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
     // (i < 6 for every wave, i = 6 for wave 0), the rest Apost's -- no per-piece select between the two sources (a select of loaded
     // strides made the compiler wait for every load in flight in front of the next piece)
 #pragma unroll
-    for (int i = 0; i < 6; ++i) __builtin_amdgcn_global_load_lds((gptr_t)src_o(wave + 8 * i), (lptr_t)(dst + 8192 * i), 16, 0, DPAIR_AUX);
-    if (wave == 0) __builtin_amdgcn_global_load_lds((gptr_t)src_o(48), (lptr_t)(dst + 8192 * 6), 16, 0, DPAIR_AUX);
-    else __builtin_amdgcn_global_load_lds((gptr_t)src_p(wave + 48), (lptr_t)(dst + 8192 * 6), 16, 0, DPAIR_AUX);
-    __builtin_amdgcn_global_load_lds((gptr_t)src_p(wave + 56), (lptr_t)(dst + 8192 * 7), 16, 0, DPAIR_AUX);
-    if (wave < 4) __builtin_amdgcn_global_load_lds((gptr_t)src_p(wave + 64), (lptr_t)(dst + 8192 * 8), 16, 0, DPAIR_AUX);
+    for (int i = 0; i < 6; ++i) glds<16, DPAIR_AUX>(src_o(wave + 8 * i), dst + 8192 * i);
+    if (wave == 0) glds<16, DPAIR_AUX>(src_o(48), dst + 8192 * 6);
+    else glds<16, DPAIR_AUX>(src_p(wave + 48), dst + 8192 * 6);
+    glds<16, DPAIR_AUX>(src_p(wave + 56), dst + 8192 * 7);
+    if (wave < 4) glds<16, DPAIR_AUX>(src_p(wave + 64), dst + 8192 * 8);
   };
 
   int tile = blockIdx.x;
@@ -171,7 +149,7 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
 #pragma unroll
       for (int h = 0; h < DPAIR_CH; ++h) {                 // lane (r, q): token r of the slab, columns 4 q .. 4 q + 3 of the tile
         const long m = m0 + 16 * (DPAIR_CH * mp + h) + r;
-        *(u32x2*)(p.dAp + (m * p.ldc + g * 128 + 16 * wave + 4 * q) * 2) = u32x2{f2bf(acc[h][0]) | (f2bf(acc[h][1]) << 16), f2bf(acc[h][2]) | (f2bf(acc[h][3]) << 16)};
+        *(u32x2*)(p.dAp + (m * p.ldc + g * 128 + 16 * wave + 4 * q) * 2) = u32x2{f2bf_u(acc[h][0]) | (f2bf_u(acc[h][1]) << 16), f2bf_u(acc[h][2]) | (f2bf_u(acc[h][3]) << 16)};
       }
     }
     if ((DPAIR_DISSECT & 1) == 0 && wave < 4) {            // the scalar columns of slab `wave` (one slab per SIMD), two chains over the even / odd K steps
@@ -185,7 +163,7 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
     }
     // ---- dBpost += dOut_tile^T Apost_tile : channel tiles 3 wave .. + 2 x nine column tiles, 32 tokens per step ----
     if constexpr ((DPAIR_DISSECT & 2) == 0) {
-      const unsigned l0 = (unsigned)(size_t)(lptr_t)sA;
+      const unsigned l0 = lds_off(sA);
       const unsigned la = l0 + (8 * q + (r >> 2)) * RB + (3 * wave * 16 + 4 * (r & 3)) * 2;
       const unsigned lb = l0 + STG + (8 * q + (r >> 2)) * RBA + (4 * (r & 3)) * 2;
       u32x2 fa[3][2], fb0[3][2], fb1[3][2];
@@ -196,13 +174,13 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dpair(const DPairArgs p) {
           for (int i = 0; i < 3; ++i) accB[i][c0 + c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tr_pack(fa[i]), tr_pack(fb[c]), accB[i][c0 + c], 0, 0, 0);
       };
       // (the reads of the next three column tiles are in flight during the nine matrix instructions of the current three)
-      tr_issue_a3<0>(fa, la); tr_issue_b3<0, 0>(fb0, lb); tr_wait6(fa, fb0);
-      tr_issue_b3<0, 3>(fb1, lb); mm(0, fb0); tr_wait3(fb1);
-      tr_issue_b3<0, 6>(fb0, lb); mm(3, fb1); tr_wait3(fb0);
+      tr_issue_a3<0>(fa, la); tr_issue_b3<0, 0>(fb0, lb); wait_lgkm<0>(fa, fb0);
+      tr_issue_b3<0, 3>(fb1, lb); mm(0, fb0); wait_lgkm<0>(fb1);
+      tr_issue_b3<0, 6>(fb0, lb); mm(3, fb1); wait_lgkm<0>(fb0);
       mm(6, fb0);
-      tr_issue_a3<1>(fa, la); tr_issue_b3<1, 0>(fb0, lb); tr_wait6(fa, fb0);
-      tr_issue_b3<1, 3>(fb1, lb); mm(0, fb0); tr_wait3(fb1);
-      tr_issue_b3<1, 6>(fb0, lb); mm(3, fb1); tr_wait3(fb0);
+      tr_issue_a3<1>(fa, la); tr_issue_b3<1, 0>(fb0, lb); wait_lgkm<0>(fa, fb0);
+      tr_issue_b3<1, 3>(fb1, lb); mm(0, fb0); wait_lgkm<0>(fb1);
+      tr_issue_b3<1, 6>(fb0, lb); mm(3, fb1); wait_lgkm<0>(fb0);
       mm(6, fb0);
     }
     __syncthreads();                                      // (waits for the direct loads above: the next tile is in place)

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -22,13 +23,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct DX2Args {
   const char* X; long ldx;             // bf16 [tokens][ldx], group g at column g * 384 (the operand of the row-scale term)
@@ -45,10 +39,6 @@ constexpr int BM = 64, NTHR = 512;
 constexpr int RBX = 384 * 2 + 16, RBZ = 128 * 2 + 16, RBL = 72 * 2 + 16;
 constexpr int OFFZ = BM * RBX, OFFL = OFFZ + BM * RBZ, OFFR = OFFL + BM * RBL, BUF = OFFR + 256;      // 76 pieces of 1 KB + the 64 row scales
 constexpr int DX2_LDS = 2 * BUF;
-
-__device__ __forceinline__ unsigned int f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ float bflo(unsigned int u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bfhi(unsigned int u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 
 __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream2(const DX2Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -97,14 +87,15 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream2(const DX2Args p) {
     auto src_z = [&](int j) { const int slot = 64 * j + lane, row = min(slot / 17, last), cc = min(slot % 17, 15); return Zb + ((m0 + row) * ldz + cc * 8) * 2; };
     auto src_l = [&](int j) { const int slot = 64 * j + lane, row = min(slot / 10, last), cc = min(slot % 10, 8); return Lb + ((m0 + row) * ldl + cc * 8) * 2; };
 #pragma unroll
-    for (int i = 0; i < 6; ++i) __builtin_amdgcn_global_load_lds((gptr_t)src_x(wave + 8 * i), (lptr_t)(dst + 8192 * i), 16, 0, DX2_AUX);
-    if (wave == 0) __builtin_amdgcn_global_load_lds((gptr_t)src_x(48), (lptr_t)(dst + 8192 * 6), 16, 0, DX2_AUX);
-    else __builtin_amdgcn_global_load_lds((gptr_t)src_z(wave - 1), (lptr_t)(dst + 8192 * 6), 16, 0, DX2_AUX);
-    __builtin_amdgcn_global_load_lds((gptr_t)src_z(wave + 7), (lptr_t)(dst + 8192 * 7), 16, 0, DX2_AUX);
-    if (wave < 2) __builtin_amdgcn_global_load_lds((gptr_t)src_z(wave + 15), (lptr_t)(dst + 8192 * 8), 16, 0, DX2_AUX);
-    else __builtin_amdgcn_global_load_lds((gptr_t)src_l(wave - 2), (lptr_t)(dst + 8192 * 8), 16, 0, DX2_AUX);
-    if (wave < 4) __builtin_amdgcn_global_load_lds((gptr_t)src_l(wave + 6), (lptr_t)(dst + 8192 * 9), 16, 0, DX2_AUX);
-    else if (wave == 4) __builtin_amdgcn_global_load_lds((gptr_t)(p.rs + m0 + min(lane, last)), (lptr_t)(smem + buf * BUF + OFFR), 4, 0, DX2_AUX);      // the tile's 64 row scales
+    for (int i = 0; i < 6; ++i) glds<16, DX2_AUX>(src_x(wave + 8 * i), dst + 8192 * i);
+    if (wave == 0) glds<16, DX2_AUX>(src_x(48), dst + 8192 * 6);
+    else glds<16, DX2_AUX>(src_z(wave - 1), dst + 8192 * 6);
+    glds<16, DX2_AUX>(src_z(wave + 7), dst + 8192 * 7);
+    if (wave < 2) glds<16, DX2_AUX>(src_z(wave + 15), dst + 8192 * 8);
+    else glds<16, DX2_AUX>(src_l(wave - 2), dst + 8192 * 8);
+    if (wave < 4) glds<16, DX2_AUX>(src_l(wave + 6), dst + 8192 * 9);
+    // the tile's 64 row scales (the builtin written out: through glds<4, ..> this one load comes out with other scalar registers)
+    else if (wave == 4) __builtin_amdgcn_global_load_lds((gptr_t)(p.rs + m0 + min(lane, last)), (lptr_t)(smem + buf * BUF + OFFR), 4, 0, DX2_AUX);
   };
 
   // contiguous tile ranges (few frame changes per block)
@@ -167,8 +158,8 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream2(const DX2Args p) {
         for (int ct = 0; ct < 3; ++ct) {
           const u32x2 xv = *(const u32x2*)(sX + row * RBX + (c0 + 16 * ct + 4 * q) * 2);
           const f32x4 a = acc[h][ct];
-          *(u32x2*)(out + 32 * ct) = u32x2{f2bf(a[0] + rs * bflo(xv[0])) | (f2bf(a[1] + rs * bfhi(xv[0])) << 16),
-                                           f2bf(a[2] + rs * bflo(xv[1])) | (f2bf(a[3] + rs * bfhi(xv[1])) << 16)};
+          *(u32x2*)(out + 32 * ct) = u32x2{f2bf_u(a[0] + rs * bflo(xv[0])) | (f2bf_u(a[1] + rs * bfhi(xv[0])) << 16),
+                                           f2bf_u(a[2] + rs * bflo(xv[1])) | (f2bf_u(a[3] + rs * bfhi(xv[1])) << 16)};
         }
       }
     }

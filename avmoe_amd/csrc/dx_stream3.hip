@@ -18,6 +18,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -30,14 +31,8 @@ namespace avmoe {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct DX3Args {
   // site A (the tensor is its X)
@@ -90,30 +85,6 @@ constexpr int PX = (BM * CHX + 63) / 64, PZ = (BM * CHZ + 63) / 64, PL = (BM * C
 constexpr int OFFZ = PX * 1024, OFFL = OFFZ + PZ * 1024, OFFR = OFFL + PL * 1024, OFFB = OFFR + PR * 1024, OFFS = OFFB + PB * 1024, BUF = OFFS + 256;
 constexpr int DX3_LDS = NBUF * BUF;
 static_assert(DX3_LDS <= 160 * 1024, "the buffers fit one CU's LDS");
-
-__device__ __forceinline__ unsigned int f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ float bflo(unsigned int u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bfhi(unsigned int u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-// s_waitcnt vmcnt(n) for a run-time (wave-uniform) n: the immediate has to be a constant
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-#define W1(k) case k: wait_vm<k>(); break;
-#define W8(k) W1(k) W1(k + 1) W1(k + 2) W1(k + 3) W1(k + 4) W1(k + 5) W1(k + 6) W1(k + 7)
-    W8(0) W8(8) W8(16) W8(24) W8(32) W8(40) W8(48) W1(56) W1(57) W1(58) W1(59) W1(60) W1(61) W1(62)
-#undef W8
-#undef W1
-    default: wait_vm<63>(); break;
-  }
-}
-// LDS reads issued and waited for by hand (the tile is read-only between two barriers: no memory clobber, the compiler's own reads may move)
-template <int OFF>
-__device__ __forceinline__ void tr_issue(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int OFF>
-__device__ __forceinline__ void rd128(u32x4& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-// wait until at most N LDS reads are pending; the registers named are those the reads before them filled (their users stay behind the wait)
-template <int N> __device__ __forceinline__ void wait_lgkm(u32x4& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }
-template <int N> __device__ __forceinline__ void wait_lgkm2(u32x2& a, u32x2& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
 
 __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -200,9 +171,9 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
         const int P = wave + NWV * i;
         if (P >= B5) break;
         const int t = P < B1 ? 0 : P < B2 ? 1 : P < B3 ? 2 : P < B4 ? 3 : 4;
-        __builtin_amdgcn_global_load_lds((gptr_t)(base[t] + off_p(P, lane, last, bmax)), (lptr_t)(dst + 1024 * NWV * i), 16, 0, DX3_AUX);
+        glds<16, DX3_AUX>(base[t] + off_p(P, lane, last, bmax), dst + 1024 * NWV * i);
       }
-      if (wave == NWV - 1) __builtin_amdgcn_global_load_lds((gptr_t)(p.rs + m0 + min(lane, last)), (lptr_t)(smem + buf * BUF + OFFS), 4, 0, DX3_AUX);
+      if (wave == NWV - 1) glds<4, DX3_AUX>(p.rs + m0 + min(lane, last), smem + buf * BUF + OFFS);
       return;
     }
     // piece P = wave + NWV i (i is a constant after unrolling: only the rounds that hold a boundary between two sub-tiles keep a wave-uniform branch)
@@ -220,9 +191,9 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
       if (t < 0) continue;
       unsigned o = voff[i];
       asm volatile("" : "+v"(o));                           // (the zero-extension stays here, beside the scalar base: the load takes `scalar base + 32-bit lane offset` as it is)
-      __builtin_amdgcn_global_load_lds((gptr_t)(base[t] + o), (lptr_t)d, 16, 0, DX3_AUX);
+      glds<16, DX3_AUX>(base[t] + o, d);
     }
-    if (wave == NWV - 1) __builtin_amdgcn_global_load_lds((gptr_t)(p.rs + m0 + min(lane, BM - 1)), (lptr_t)(smem + buf * BUF + OFFS), 4, 0, DX3_AUX);       // the tile's row scales
+    if (wave == NWV - 1) glds<4, DX3_AUX>(p.rs + m0 + min(lane, BM - 1), smem + buf * BUF + OFFS);       // the tile's row scales
   };
 
   // contiguous tile ranges (few frame changes per block)
@@ -300,10 +271,10 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
       // wave has its SIMD to itself, nobody else covers the 100+ cycles of an LDS read (as the compiler schedules it, read -> wait -> six
       // products, the matrix pipe idles for one read latency per step: as long as the products themselves).
       if (!(DX3_DISSECT & 1)) {
-        const unsigned aB = (unsigned)(size_t)(lptr_t)(sX + OFFB) + (8 * q + (r >> 2)) * RBB + (4 * (r & 3)) * 2 + 32 * h;
-        const unsigned aZ = (unsigned)(size_t)(lptr_t)(sZ + (16 * h + r) * RBZ + q * 16);
-        const unsigned aL = (unsigned)(size_t)(lptr_t)(sL + (16 * h + r) * RBL + q * 16);
-        const unsigned aR = (unsigned)(size_t)(lptr_t)(sR + (16 * h + r) * RBR + q * 16);
+        const unsigned aB = lds_off(sX + OFFB) + (8 * q + (r >> 2)) * RBB + (4 * (r & 3)) * 2 + 32 * h;
+        const unsigned aZ = lds_off(sZ + (16 * h + r) * RBZ + q * 16);
+        const unsigned aL = lds_off(sL + (16 * h + r) * RBL + q * 16);
+        const unsigned aR = lds_off(sR + (16 * h + r) * RBR + q * 16);
         u32x2 pa, pb, qa, qb;
         u32x4 u, w;
 #define DX3_MM(frag, ks, af_)                                                                                                     \
@@ -316,24 +287,24 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
     const int nvk = p.K2 - (32 * (ks) + 8 * q);                                                                                   \
     _Pragma("unroll") for (int e = 0; e < 4; ++e) v[e] &= (2 * e + 1 < nvk) ? 0xffffffffu : ((2 * e < nvk) ? 0x0000ffffu : 0u);   \
   }
-        tr_issue<0 * 32 * RBB>(pa, aB); tr_issue<0 * 32 * RBB + 4 * RBB>(pb, aB);
-        tr_issue<1 * 32 * RBB>(qa, aB); tr_issue<1 * 32 * RBB + 4 * RBB>(qb, aB);
-        wait_lgkm2<2>(pa, pb);
+        tr_issue_ro<0 * 32 * RBB>(pa, aB); tr_issue_ro<0 * 32 * RBB + 4 * RBB>(pb, aB);
+        tr_issue_ro<1 * 32 * RBB>(qa, aB); tr_issue_ro<1 * 32 * RBB + 4 * RBB>(qb, aB);
+        wait_lgkm<2>(pa, pb);
         DX3_MM(bv, 0, (u32x4{pa[0], pa[1], pb[0], pb[1]}));
-        tr_issue<2 * 32 * RBB>(pa, aB); tr_issue<2 * 32 * RBB + 4 * RBB>(pb, aB);
-        wait_lgkm2<2>(qa, qb);
+        tr_issue_ro<2 * 32 * RBB>(pa, aB); tr_issue_ro<2 * 32 * RBB + 4 * RBB>(pb, aB);
+        wait_lgkm<2>(qa, qb);
         DX3_MM(bv, 1, (u32x4{qa[0], qa[1], qb[0], qb[1]}));
-        rd128<0>(u, aZ);
-        wait_lgkm2<1>(pa, pb);
+        lds_rd128_ro<0>(u, aZ);
+        wait_lgkm<1>(pa, pb);
         DX3_MM(bv, 2, (u32x4{pa[0], pa[1], pb[0], pb[1]}));
-        rd128<64>(w, aZ);  wait_lgkm<1>(u); DX3_MM(bw, 0, u);
-        rd128<128>(u, aZ); wait_lgkm<1>(w); DX3_MM(bw, 1, w);
-        rd128<192>(w, aZ); wait_lgkm<1>(u); DX3_MM(bw, 2, u);
-        rd128<0>(u, aL);   wait_lgkm<1>(w); DX3_MM(bw, 3, w);
-        rd128<64>(w, aL);  wait_lgkm<1>(u); DX3_MASK(u, 0); DX3_MM(bt, 0, u);
-        rd128<128>(u, aL); wait_lgkm<1>(w); DX3_MASK(w, 1); DX3_MM(bt, 1, w);
-        rd128<0>(w, aR);   wait_lgkm<1>(u); DX3_MASK(u, 2); DX3_MM(bt, 2, u);
-        rd128<64>(u, aR);  wait_lgkm<1>(w); DX3_MM(bq, 0, w);
+        lds_rd128_ro<64>(w, aZ);  wait_lgkm<1>(u); DX3_MM(bw, 0, u);
+        lds_rd128_ro<128>(u, aZ); wait_lgkm<1>(w); DX3_MM(bw, 1, w);
+        lds_rd128_ro<192>(w, aZ); wait_lgkm<1>(u); DX3_MM(bw, 2, u);
+        lds_rd128_ro<0>(u, aL);   wait_lgkm<1>(w); DX3_MM(bw, 3, w);
+        lds_rd128_ro<64>(w, aL);  wait_lgkm<1>(u); DX3_MASK(u, 0); DX3_MM(bt, 0, u);
+        lds_rd128_ro<128>(u, aL); wait_lgkm<1>(w); DX3_MASK(w, 1); DX3_MM(bt, 1, w);
+        lds_rd128_ro<0>(w, aR);   wait_lgkm<1>(u); DX3_MASK(u, 2); DX3_MM(bt, 2, u);
+        lds_rd128_ro<64>(u, aR);  wait_lgkm<1>(w); DX3_MM(bq, 0, w);
         wait_lgkm<0>(u);   DX3_MM(bq, 1, u);
 #undef DX3_MM
 #undef DX3_MASK

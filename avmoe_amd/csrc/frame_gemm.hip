@@ -18,6 +18,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -25,13 +26,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct FGArgs {
   const char* A; long lda, sA1;        // bf16 [frame][rows >= M][lda]
@@ -45,8 +39,6 @@ struct FGArgs {
 #define FG_DISSECT 0      // development (scripts/variant_lib.sh): 1 no stores, 2 no frame loads, 4 no matrix instructions -- wrong results, timing only
 #endif
 __device__ __attribute__((aligned(16))) char fg_dump[64 * 16];      // where the lanes outside C store (nobody reads it): every wave issues exactly eight stores per frame
-
-__device__ __forceinline__ unsigned int fg_f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
 
 template <int NKS> struct FGShape {
   static constexpr int RC = 4 * NKS + 1;             // 16-byte pieces per LDS row (one of padding)
@@ -86,7 +78,7 @@ __global__ void __launch_bounds__(256, 2) kk_frame_gemm(const FGArgs p) {
       unsigned o = voff[i];
       asm volatile("" : "+v"(o));
       const int piece = min(wave + 4 * i, SH::NP - 1);       // (wave-uniform)
-      __builtin_amdgcn_global_load_lds((gptr_t)(ab + o), (lptr_t)(d + 1024 * piece), 16, 0, 0);
+      glds<16, 0>(ab + o, d + 1024 * piece);
     }
   };
   gload(0, s0);
@@ -111,8 +103,8 @@ __global__ void __launch_bounds__(256, 2) kk_frame_gemm(const FGArgs p) {
   for (int s = s0; s < s1; ++s) {
     const int stage = (s - s0) & 1;
     // in-order counter: [NL loads of frame s] [8 stores of frame s - 1]   (issued in the previous iteration, in this order)
-    if (s == s0 || FG_DISSECT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    if (s == s0 || FG_DISSECT) wait_vm<0>();
+    else wait_vm<8>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (s + 1 < s1 && !(FG_DISSECT & 2)) gload(stage ^ 1, s + 1);
@@ -153,10 +145,10 @@ __global__ void __launch_bounds__(256, 2) kk_frame_gemm(const FGArgs p) {
         const long e = (long)s * p.sC1 + (TR ? (long)n * p.ldc + m : (long)m * p.ldc + n);
         if (p.c_bf16) {
           char* dst = ok ? p.C + e * 2 : dump;
-          *(u32x2*)dst = u32x2{fg_f2bf(v[0]) | (fg_f2bf(v[1]) << 16), fg_f2bf(v[2]) | (fg_f2bf(v[3]) << 16)};
+          *(u32x2*)dst = u32x2{f2bf_u(v[0]) | (f2bf_u(v[1]) << 16), f2bf_u(v[2]) | (f2bf_u(v[3]) << 16)};
           if (!ok && in && left > 0) {
 #pragma unroll
-            for (int x = 0; x < 3; ++x) if (x < left) ((unsigned short*)p.C)[e + x] = (unsigned short)fg_f2bf(v[x]);
+            for (int x = 0; x < 3; ++x) if (x < left) ((unsigned short*)p.C)[e + x] = (unsigned short)f2bf_u(v[x]);
           }
         } else {
           char* dst = ok ? p.C + e * 4 : dump;
@@ -256,7 +248,7 @@ __global__ void __launch_bounds__(512, 1) kk_frame_gemm_long(const FLArgs p) {
     for (int i = 0; i < FL_NL; ++i) {
       const char* base = (i < 2 ? p.A : p.B) + offl[i];
       const int c = min(k0 / 8 + cc[i], cmax8);              // (pieces beyond the row's data re-read its last one: masked in the fragments)
-      __builtin_amdgcn_global_load_lds((gptr_t)(base + c * 16), (lptr_t)(d + dst[i]), 16, 0, 0);
+      glds<16, 0>(base + c * 16, d + dst[i]);
     }
   };
 #pragma unroll
@@ -273,8 +265,8 @@ __global__ void __launch_bounds__(512, 1) kk_frame_gemm_long(const FLArgs p) {
   const int fb0 = FL_A + rb * 128 + ((q ^ (rb & 7)) * 16), fb1 = FL_A + rb * 128 + (((4 + q) ^ (rb & 7)) * 16);
   for (int kc = 0; kc < nkc; ++kc) {
     // in-order counter: [6 loads of chunk kc] [6 loads of chunk kc + 1]
-    if (kc + 1 < nkc) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (kc + 1 < nkc) wait_vm<6>();
+    else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (kc + FL_NBUF - 1 < nkc) gload((kc + FL_NBUF - 1) % FL_NBUF, kc + FL_NBUF - 1);
@@ -319,12 +311,12 @@ __global__ void __launch_bounds__(512, 1) kk_frame_gemm_long(const FLArgs p) {
       if (!in || left <= 0) continue;
       const long e = (long)f * p.sC1 + (TR ? (long)n * p.ldc + m : (long)m * p.ldc + n);
       if (left >= 4) {
-        if (p.c_bf16) *(u32x2*)(p.C + e * 2) = u32x2{fg_f2bf(v[0]) | (fg_f2bf(v[1]) << 16), fg_f2bf(v[2]) | (fg_f2bf(v[3]) << 16)};
+        if (p.c_bf16) *(u32x2*)(p.C + e * 2) = u32x2{f2bf_u(v[0]) | (f2bf_u(v[1]) << 16), f2bf_u(v[2]) | (f2bf_u(v[3]) << 16)};
         else *(f32x4*)(p.C + e * 4) = v;
       } else {
 #pragma unroll
         for (int x = 0; x < 3; ++x)
-          if (x < left) { if (p.c_bf16) ((unsigned short*)p.C)[e + x] = (unsigned short)fg_f2bf(v[x]); else ((float*)p.C)[e + x] = v[x]; }
+          if (x < left) { if (p.c_bf16) ((unsigned short*)p.C)[e + x] = (unsigned short)f2bf_u(v[x]); else ((float*)p.C)[e + x] = v[x]; }
       }
     }
 }

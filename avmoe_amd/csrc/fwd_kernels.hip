@@ -12,23 +12,9 @@
 
 namespace avmoe {
 
-#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
-  do {                                                                                        \
-    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
-    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
-  } while (0)
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <typename T> __device__ __forceinline__ float roundT(float v);
 template <> __device__ __forceinline__ float roundT<float>(float v) { return v; }
 template <> __device__ __forceinline__ float roundT<__bf16>(float v) { return bf2f(f2bf(v)); }
-
-static inline unsigned grid1d(long n, int cap = 4096) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
 // ---------------------------------------------------------------------------------------------
 // generic helpers
@@ -351,10 +337,10 @@ __global__ void __launch_bounds__(256) kk_rowstats(const void* X_, long rows, in
   constexpr int EPV = 16 / sizeof(T);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
-    const u32x4_t* p = (const u32x4_t*)(X + row * C);
+    const u32x4* p = (const u32x4*)(X + row * C);
     float s = 0.f, ss = 0.f;
     for (int v = lane; v < C / EPV; v += 64) {
-      const u32x4_t w = p[v];
+      const u32x4 w = p[v];
       if constexpr (sizeof(T) == 4) {
 #pragma unroll
         // NB: __builtin_bit_cast(float, w[e]) on a vector-element lvalue miscompiles (ROCm 7.2): go through a scalar

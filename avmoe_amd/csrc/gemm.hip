@@ -19,18 +19,13 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
 namespace avmoe {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 struct DevArgs {
   const char* A; const char* B; char* C; const char* D; const float* rs; float* slabs;
@@ -204,7 +199,6 @@ __device__ __forceinline__ void gemm_segment(char* smem, const char* Ab, const c
     const char* sA = smem + buf * STAGE;
     const char* sB = sA + A_BYTES;
     if constexpr (ESZ == 2) {
-      typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
 #pragma unroll
       for (int ks = 0; ks < BK / 32; ++ks) {
         bf16x8 af[TM], bfr[TN];
@@ -216,7 +210,6 @@ __device__ __forceinline__ void gemm_segment(char* smem, const char* Ab, const c
             const char* ad = sA + (ks * 32 + 8 * q + (r >> 2)) * A_ROWB + (wm0 + 16 * tm + 4 * (r & 3)) * 2;
             s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad));
             s16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad + 4 * A_ROWB));
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
             s16x8 w = {v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
             af[tm] = __builtin_bit_cast(bf16x8, w);
           }
@@ -229,7 +222,6 @@ __device__ __forceinline__ void gemm_segment(char* smem, const char* Ab, const c
             const char* ad = sB + (ks * 32 + 8 * q + (r >> 2)) * B_ROWB + (wn0 + 16 * tn + 4 * (r & 3)) * 2;
             s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad));
             s16x4 v2 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(ad + 4 * B_ROWB));
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
             s16x8 w = {v1[0], v1[1], v1[2], v1[3], v2[0], v2[1], v2[2], v2[3]};
             bfr[tn] = __builtin_bit_cast(bf16x8, w);
           }
@@ -242,8 +234,6 @@ __device__ __forceinline__ void gemm_segment(char* smem, const char* Ab, const c
       }
     } else if constexpr (std::is_same<T, f32s2>::value) {
       // two planes, split at lstore: bf16 fragments of the hi / lo images (plane offset: half a K-major row / BM (BN) bf16 of an MN-major row)
-      typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
-      typedef __attribute__((ext_vector_type(8))) short s16x8;
 #pragma unroll
       for (int ks = 0; ks < BK / 32; ++ks) {
         bf16x8 ah[TM], al[TM];
@@ -392,8 +382,6 @@ template <int N> __device__ __forceinline__ void gemm_wait_vm() { asm volatile("
 template <int BM, int BN, int NTHR, int WGN, int TM, int TN, int BK, int NST>
 __device__ __forceinline__ void gemm_segment_direct(char* smem, const char* Ab, const char* Bb, long lda, long ldb, int M, int N, int K, int m0, int n0,
                                                     int kbeg, int kend, f32x4 (&acc)[TM][TN]) {
-  typedef __attribute__((address_space(1))) const void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   constexpr int ROWB = 2 * BK, PPR = ROWB / 16, RPP = 64 / PPR;      // bytes / 16-byte pieces per row; rows per 1 KB piece
   constexpr int NW = NTHR / 64, HA = BM * ROWB, HALF = HA, STAGE = (BM + BN) * ROWB, KS = BK / 32;      // K steps per chunk
   constexpr int NLA = HA / 1024 / NW, NLB = BN * ROWB / 1024 / NW;      // 1 KB pieces per wave, of A and of B
@@ -422,10 +410,10 @@ __device__ __forceinline__ void gemm_segment_direct(char* smem, const char* Ab, 
     const int k8 = (kbeg + kt * BK) / 8;
 #pragma unroll
     for (int i = 0; i < NLA; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Ab + offa[i] + min(k8 + ca[i], cmax8) * 16), (lptr_t)(d + 1024 * (NLA * wave + i)), 16, 0, 0);
+      glds<16, 0>(Ab + offa[i] + min(k8 + ca[i], cmax8) * 16, d + 1024 * (NLA * wave + i));
 #pragma unroll
     for (int i = 0; i < NLB; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bb + offb[i] + min(k8 + cb[i], cmax8) * 16), (lptr_t)(d + HALF + 1024 * (NLB * wave + i)), 16, 0, 0);
+      glds<16, 0>(Bb + offb[i] + min(k8 + cb[i], cmax8) * 16, d + HALF + 1024 * (NLB * wave + i));
   };
   int fa[KS], fb[KS];
 #pragma unroll

@@ -15,6 +15,7 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -22,11 +23,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 struct StreamArgs {
   const char* A; const char* B; const char* A2; const char* B2; char* C; const char* D; const float* rs;
@@ -282,9 +278,6 @@ __global__ void __launch_bounds__(NW * 64, MINW) gemm_stream_kernel(const Stream
         // The sample's B2 ([k2][n], MN-major) goes through the LDS, 32 rows (one K step) at a time: coalesced 16-byte row loads (all of
         // them requested up front), stored with the columns in fragment order (a wave's tile t = 16 consecutive LDS columns), read
         // back transposed (ds_read_tr16_b64) -- instead of 8 two-byte gathers per fragment register, a round trip each.
-        typedef __attribute__((ext_vector_type(4))) short s16x4;
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
         constexpr int NCOLS = TPW * NW * 16, CPRB = NCOLS / 8, RB2 = NCOLS * 2 + 16;
         char* sB2 = smem + 2 * STG;
         constexpr bool AHEAD = KS2 * TPW <= 6;             // all K steps requested up front where the registers allow, else one at a time
@@ -500,9 +493,6 @@ __global__ void __launch_bounds__(NW * 64, MINW) gemm_stream_kernel(const Stream
 #else
     if constexpr (STATS) {
 #endif
-      typedef __attribute__((ext_vector_type(4))) short s16x4;
-      typedef __attribute__((ext_vector_type(8))) short s16x8;
-      typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
       float* cdst = p.st_cols + ((long)tile * gridDim.y + g) * p.K;
 #pragma unroll
       for (int cj = 0; cj < (2 * KS + NW - 1) / NW; ++cj) {

@@ -21,12 +21,6 @@ namespace avmoe {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
 constexpr int GG = 2, GD = 32;                                  // groups, bottleneck per group
 constexpr int GT = 64;                                          // tokens per tile
 
@@ -110,7 +104,6 @@ __global__ void __launch_bounds__(256) kg_gram64(const unsigned short* __restric
     }
     if constexpr (WEIGHTED) { if (tid < GE * GT) s_w[buf * GE * GT + tid] = rw; }
   };
-  typedef __attribute__((address_space(3))) s16x4* lds_s16x4;
 
   if (tile0 < tile1) { gload(tile0); lstore(0); }
   __syncthreads();

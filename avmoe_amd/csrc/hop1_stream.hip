@@ -15,6 +15,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -23,15 +24,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-__device__ __forceinline__ unsigned int f2bf(float x) { return (unsigned int)__builtin_bit_cast(unsigned short, (__bf16)x); }
 
 // ======================================================================================================================================
 // yk:  C[s][row][tok] = sum_c A[(s)][row][c] Y[s][tok][c]       (rows <= 16 NRT, Cy = 32 KS channels, M a multiple of 4)
@@ -72,8 +64,6 @@ constexpr int YK_BT = 32, YK_NBUF = 3;
 #define HOP1_DISSECT 0      // development builds (timing only): bit 0 = no matrix phase, bit 1 = no store, bit 2 = no direct loads, bit 3 = tiles dealt round-robin
 #endif
 
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
 template <int KS, int NRT>
 __global__ void __launch_bounds__(128 * NRT, 1) kk_hop1_yk(const YKArgs p) {
   constexpr int NW = 2 * NRT, CH = 4 * KS, RB = 16 * CH, NP = YK_BT * CH / 64, BUF = NP * 1024, NI = (NP + NW - 1) / NW, NLO = NP / NW;
@@ -93,7 +83,7 @@ __global__ void __launch_bounds__(128 * NRT, 1) kk_hop1_yk(const YKArgs p) {
     for (int i = 0; i < NI; ++i) {
       if ((i < NLO || extra) && !(HOP1_DISSECT & 4)) {       // (compile-time true except for the last round of pieces: wave-uniform)
         const int slot = 64 * (wave + NW * i) + lane, row = slot / CH, cc = (slot % CH) ^ (row & 15);
-        __builtin_amdgcn_global_load_lds((gptr_t)(p.Y + ((m0 + min(row, last)) * ldy + cc * 8) * 2), (lptr_t)(dst + 1024 * NW * i), 16, 0, YK_AUX);
+        glds<16, YK_AUX>(p.Y + ((m0 + min(row, last)) * ldy + cc * 8) * 2, dst + 1024 * NW * i);
       }
     }
   };
@@ -158,7 +148,7 @@ __global__ void __launch_bounds__(128 * NRT, 1) kk_hop1_yk(const YKArgs p) {
       const long e = (long)s * p.sC1 + (long)row * p.ldc + t0;
       if (p.c_bf16) {
         char* dst = ok ? p.C + e * 2 : p.dump;
-        *(u32x2*)dst = u32x2{f2bf(a[0]) | (f2bf(a[1]) << 16), f2bf(a[2]) | (f2bf(a[3]) << 16)};
+        *(u32x2*)dst = u32x2{f2bf_u(a[0]) | (f2bf_u(a[1]) << 16), f2bf_u(a[2]) | (f2bf_u(a[3]) << 16)};
       } else {
         char* dst = ok ? p.C + e * 4 : p.dump;
         *(f32x4*)dst = a;
@@ -186,11 +176,6 @@ struct YTArgs {
   long ntok; int ntiles;                           // sum: tokens / tiles in all (the last tile ragged)
 };
 
-template <int OFF>
-__device__ __forceinline__ void tr_issue(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
-template <int OFF, int ROWB>        // one 16-column fragment: token rows 8 q .. 8 q + 7, both halves
-__device__ __forceinline__ void tr_frag2(u32x2 (&f)[2], unsigned base) { tr_issue<OFF>(f[0], base); tr_issue<OFF + 4 * ROWB>(f[1], base); }
-__device__ __forceinline__ bf16x8 tr_pack(const u32x2 (&f)[2]) { return __builtin_bit_cast(bf16x8, u32x4{f[0][0], f[0][1], f[1][0], f[1][1]}); }
 // the explicit wait for transposing reads issued above (every fragment passes through a volatile statement behind the wait, so that its
 // consumers stay behind it)
 template <int N>
@@ -232,16 +217,16 @@ __global__ void __launch_bounds__(512, 1) kk_hop1_yt(const YTArgs p) {
       const int j0 = 8 * i;                                  // pieces j0 .. j0 + 7 of this round: piece j0 + wave is this wave's
       auto ld_y = [&]() {
         const int slot = 64 * (j0 + wave) + lane, row = min(slot / CHY, last), cc = min(slot % CHY, CHY - 2);
-        __builtin_amdgcn_global_load_lds((gptr_t)(Yb + ((m0 + row) * ldy + cc * 8) * 2), (lptr_t)(dst + 8192 * i), 16, 0, (PER_FRAME ? YTF_AUX : YTS_AUX));
+        glds<16, (PER_FRAME ? YTF_AUX : YTS_AUX)>(Yb + ((m0 + row) * ldy + cc * 8) * 2, dst + 8192 * i);
       };
       auto ld_a = [&]() {
         const int slot = 64 * (j0 + wave - NPY) + lane;
         if constexpr (PER_FRAME) {                           // [row][tokens of the tile]: 4 chunks of 8 tokens + the pad chunk
           const int row = min(slot / CHA, p.rows - 1), cc = min(min(slot % CHA, CHA - 2), acol_max);
-          __builtin_amdgcn_global_load_lds((gptr_t)(Asrc + ((long)row * lda + cc * 8) * 2), (lptr_t)(dst + 8192 * i), 16, 0, (PER_FRAME ? YTF_AUX : YTS_AUX));
+          glds<16, (PER_FRAME ? YTF_AUX : YTS_AUX)>(Asrc + ((long)row * lda + cc * 8) * 2, dst + 8192 * i);
         } else {                                             // [token][rows]
           const int row = min(slot / CHA, last), cc = min(slot % CHA, CHA - 2);
-          __builtin_amdgcn_global_load_lds((gptr_t)(Asrc + ((long)row * lda + cc * 8) * 2), (lptr_t)(dst + 8192 * i), 16, 0, (PER_FRAME ? YTF_AUX : YTS_AUX));
+          glds<16, (PER_FRAME ? YTF_AUX : YTS_AUX)>(Asrc + ((long)row * lda + cc * 8) * 2, dst + 8192 * i);
         }
       };
       // (i is a constant after unrolling: only the round that holds the Y / A boundary and the last round keep a wave-uniform branch)
@@ -287,7 +272,7 @@ __global__ void __launch_bounds__(512, 1) kk_hop1_yt(const YTArgs p) {
     if constexpr (PER_FRAME) { const int fj = tile % p.tpf; valid = p.M - fj * BM; }
     else valid = (int)min((long)BM, p.ntok - (long)tile * BM);
     {
-      const unsigned l0 = (unsigned)(size_t)(lptr_t)sY;
+      const unsigned l0 = lds_off(sY);
       const unsigned ly = l0 + (8 * q + (r >> 2)) * RBY + (NCT * wave * 16 + 4 * (r & 3)) * 2;
       const unsigned la = l0 + OFFA + (8 * q + (r >> 2)) * RBA + (4 * (r & 3)) * 2;      // (token-major A: transposed reads, as Y)
       const char* pa = sY + OFFA + r * RBA + q * 16;                                   // (row-major A: plain 16-byte reads)
@@ -340,7 +325,7 @@ __global__ void __launch_bounds__(512, 1) kk_hop1_yt(const YTArgs p) {
               const int row = 16 * i + 4 * q + e;
               const long o = (long)s * p.sC1 + (long)row * p.ldc + (long)blockIdx.y * CB + 16 * (NCT * wave + c) + r;
               if (row < p.rows) {
-                if (p.c_bf16) *(unsigned short*)(p.C + o * 2) = (unsigned short)f2bf(acc[i][c][e]);
+                if (p.c_bf16) *(unsigned short*)(p.C + o * 2) = (unsigned short)f2bf_u(acc[i][c][e]);
                 else *(float*)(p.C + o * 4) = acc[i][c][e];
               }
               acc[i][c][e] = 0.f;
@@ -382,7 +367,7 @@ __global__ void __launch_bounds__(256) kk_hop1_sum(const float* __restrict__ sla
   for (int e = 0; e < 4; ++e) { s[e] += __shfl_xor(s[e], 16, 64); s[e] += __shfl_xor(s[e], 32, 64); }
   if (v < nvec && part == 0) {
     const long o = (long)row * ldo + c4;
-    if (o_bf16) *(u32x2*)(out + o * 2) = u32x2{f2bf(s[0]) | (f2bf(s[1]) << 16), f2bf(s[2]) | (f2bf(s[3]) << 16)};
+    if (o_bf16) *(u32x2*)(out + o * 2) = u32x2{f2bf_u(s[0]) | (f2bf_u(s[1]) << 16), f2bf_u(s[2]) | (f2bf_u(s[3]) << 16)};
     else *(f32x4*)(out + o * 4) = s;
   }
 }

@@ -22,15 +22,7 @@
 
 namespace avmoe {
 
-#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
-  do {                                                                                        \
-    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
-    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
-  } while (0)
-
 namespace {
-
-inline unsigned grid1(long n, int cap = 8192) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
 // rows[t][c] += bias[c]
 template <typename T>
@@ -128,7 +120,7 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
     g.A = X; g.B = b.Win(); g.C = b.QKV(); g.M = d.NT; g.N = 3 * d.C; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.sCi = 3L * d.C;
     AVMOE_TRY(launch_gemm(g, st));
   }
-  DISPATCH_T(d.bf16, km_add_bias, dim3(grid1((long)d.NT * 3 * d.C)), dim3(256), 0, st, (void*)b.QKV(), (const float*)ep.sa_in_b, (long)d.NT, 3 * d.C);
+  DISPATCH_T(d.bf16, km_add_bias, dim3(grid1d((long)d.NT * 3 * d.C, 8192)), dim3(256), 0, st, (void*)b.QKV(), (const float*)ep.sa_in_b, (long)d.NT, 3 * d.C);
   AVMOE_CHECK_LAUNCH("mha add_bias");
   {                                                        // scores[n][h] = q k^T / sqrt(dh)
     GemmArgs g = base();
@@ -140,7 +132,7 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
   AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_mSc), mats * d.S, d.S, d.Sp, b.P(), d.Sp, 1, 1, 1, 1, st));
   const char* Pd = b.P();
   if (ep.sa_keep) {
-    DISPATCH_T(d.bf16, km_keep, dim3(grid1(mats * d.S * d.Sp)), dim3(256), 0, st, (const void*)b.P(), (const float*)ep.sa_keep, (void*)b.Pd(), mats, d.S, d.Sp);
+    DISPATCH_T(d.bf16, km_keep, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, (const void*)b.P(), (const float*)ep.sa_keep, (void*)b.Pd(), mats, d.S, d.Sp);
     AVMOE_CHECK_LAUNCH("mha keep");
     Pd = b.Pd();
   }
@@ -156,7 +148,7 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
     g.A = b.O(); g.B = b.Wout(); g.C = b.xr(); g.M = d.NT; g.N = d.C; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.sCi = d.C;
     AVMOE_TRY(launch_gemm(g, st));
   }
-  DISPATCH_T(d.bf16, km_finish, dim3(grid1((long)d.NT * d.C)), dim3(256), 0, st, (void*)b.xr(), (const float*)ep.sa_out_b, X, (long)d.NT, d.C);
+  DISPATCH_T(d.bf16, km_finish, dim3(grid1d((long)d.NT * d.C, 8192)), dim3(256), 0, st, (void*)b.xr(), (const float*)ep.sa_out_b, X, (long)d.NT, d.C);
   AVMOE_CHECK_LAUNCH("mha finish");
   return OK;
 }
@@ -211,7 +203,7 @@ int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& 
     AVMOE_TRY(run(g, false));
   }
   if (ep.sa_keep) {
-    hipLaunchKernelGGL(km_keep_bwd, dim3(grid1(mats * d.S * d.Sp)), dim3(256), 0, st, dP, (const float*)ep.sa_keep, mats, d.S, d.Sp);
+    hipLaunchKernelGGL(km_keep_bwd, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, dP, (const float*)ep.sa_keep, mats, d.S, d.Sp);
     AVMOE_CHECK_LAUNCH("mha keep_bwd");
   }
   AVMOE_TRY(k_softmax_rows_bwd(d.bf16, b.P(), dP, mats * d.S, d.S, d.Sp, dS, nullptr, 1, 1, st));

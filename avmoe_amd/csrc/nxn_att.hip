@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "common.h"
 #include "prof.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -27,24 +28,9 @@ namespace avmoe {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)a) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)b) << 16);
-}
-
-
 // LDS reads issued and waited for by hand (round 5, from dx_stream3.hip): where a block keeps 450 registers it is alone on its CU, one wave
 // per SIMD, and the compiler's `read -> s_waitcnt lgkmcnt(0) -> products` leaves the matrix pipe idle for one LDS latency per read.  The
 // offsets have to be immediates: the loops run over compile-time indices (static_for).
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-template <int OFF> __device__ __forceinline__ void lds_rd128(u32x4& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int OFF> __device__ __forceinline__ void lds_rdtr(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int N> __device__ __forceinline__ void lds_wait(u32x4& a) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(N)); }
-template <int N> __device__ __forceinline__ void lds_wait2(u32x4& a, u32x4& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
-template <int N> __device__ __forceinline__ void lds_waittr(u32x2& a, u32x2& b) { asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N)); }
 template <int I, int END> struct static_for_t {
   template <typename F> static __device__ __forceinline__ void run(F&& f) { f(std::integral_constant<int, I>{}); static_for_t<I + 1, END>::run(f); }
 };
@@ -103,11 +89,11 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : NXN_ATT_MINB6)) kk_nxn_att
       {   // key row of fragment row r of tile t: column (r >> 2) * 32 + 4 t + (r & 3) of this key tile  ->  lane (r, q) owns columns 32 q + 4 t + e
           // 8 KS steps (ks, t), the fragment reads issued by hand three steps ahead of the two products that use each
         constexpr int NA = 8 * KS;
-        const unsigned aX = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + ((r >> 2) * 32 + (r & 3)) * RB + q * 16);
+        const unsigned aX = lds_off(smem + ((r >> 2) * 32 + (r & 3)) * RB + q * 16);
         u32x4 kfr[4];
         auto issue = [&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ks = st_ / 8, t = st_ % 8;
-          lds_rd128<4 * t * RB + ks * 64>(kfr[st_ % 4], aX);
+          lds_rd128_ro<4 * t * RB + ks * 64>(kfr[st_ % 4], aX);
         };
         issue(std::integral_constant<int, 0>{});
         issue(std::integral_constant<int, 1>{});
@@ -115,7 +101,7 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : NXN_ATT_MINB6)) kk_nxn_att
         static_for<0, NA>([&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ks = st_ / 8, t = st_ % 8;
           if constexpr (st_ + 3 < NA) issue(std::integral_constant<int, st_ + 3>{});
-          lds_wait<(NA - 1 - st_ < 3 ? NA - 1 - st_ : 3)>(kfr[st_ % 4]);
+          wait_lgkm<(NA - 1 - st_ < 3 ? NA - 1 - st_ : 3)>(kfr[st_ % 4]);
           const bf16x8 kf = __builtin_bit_cast(bf16x8, kfr[st_ % 4]);
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm) acc[tm][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[tm][ks], acc[tm][t], 0, 0, 0);
@@ -147,10 +133,8 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : NXN_ATT_MINB6)) kk_nxn_att
             const float l = lse[tm];
             if (att_in) {
               const u32x4 w = *(const u32x4*)(att_in + off + 8 * h);
-              auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-              auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-              *(u32x4*)(dst + 8 * h) = u32x4{pack2(lo(w[0]) * (a[0] - l), hi(w[0]) * (a[1] - l)), pack2(lo(w[1]) * (a[2] - l), hi(w[1]) * (a[3] - l)),
-                                             pack2(lo(w[2]) * (b[0] - l), hi(w[2]) * (b[1] - l)), pack2(lo(w[3]) * (b[2] - l), hi(w[3]) * (b[3] - l))};
+              *(u32x4*)(dst + 8 * h) = u32x4{pack2(bflo(w[0]) * (a[0] - l), bfhi(w[0]) * (a[1] - l)), pack2(bflo(w[1]) * (a[2] - l), bfhi(w[1]) * (a[3] - l)),
+                                             pack2(bflo(w[2]) * (b[0] - l), bfhi(w[2]) * (b[1] - l)), pack2(bflo(w[3]) * (b[2] - l), bfhi(w[3]) * (b[3] - l))};
             } else {
               *(u32x4*)(dst + 8 * h) = u32x4{pack2(__expf(a[0] - l), __expf(a[1] - l)), pack2(__expf(a[2] - l), __expf(a[3] - l)),
                                              pack2(__expf(b[0] - l), __expf(b[1] - l)), pack2(__expf(b[2] - l), __expf(b[3] - l))};
@@ -188,10 +172,6 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : NXN_ATT_MINB6)) kk_nxn_att
 //              -- replaces [att re-formed and stored] + [GEMM att dxr -> fp32 y] + [row-dot kernel]: att is neither written nor read
 //   kk_nxn_ds  dS = att * (X dxr^T - rowdot) with att re-formed the same way (two products per tile) -- replaces the read of att
 // (the two products against dS stay engine GEMMs on the stored dS).
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_t;
-
 template <int KS, int MODE>      // MODE 0: y = att dxr (+ rowdot, dX += y) ; 2: the FORWARD's xr = att^T X (the block owns 128 rows of xr; lse per streamed row)
 __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsigned short* __restrict__ X, const unsigned short* __restrict__ Dx,
                                                                       const float* __restrict__ lse_g, float* __restrict__ rowdot, unsigned short* __restrict__ out,
@@ -255,11 +235,11 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsig
       for (int t = 0; t < 8; ++t) acc[tm][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     {   // 8 KS steps (ks, t): the streamed rows' fragments, three steps ahead of the two products that use each (hand-issued LDS reads)
       constexpr int NA = 8 * KS;
-      const unsigned aX = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sX + ((r >> 2) * 32 + (r & 3)) * RB + q * 16);
+      const unsigned aX = lds_off(sX + ((r >> 2) * 32 + (r & 3)) * RB + q * 16);
       u32x4 kfr[4];
       auto issue = [&](auto ic) {
         constexpr int st_ = decltype(ic)::value, ks = st_ / 8, t = st_ % 8;
-        lds_rd128<4 * t * RB + ks * 64>(kfr[st_ % 4], aX);
+        lds_rd128_ro<4 * t * RB + ks * 64>(kfr[st_ % 4], aX);
       };
       issue(std::integral_constant<int, 0>{});
       issue(std::integral_constant<int, 1>{});
@@ -267,7 +247,7 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsig
       static_for<0, NA>([&](auto ic) {
         constexpr int st_ = decltype(ic)::value, ks = st_ / 8, t = st_ % 8;
         if constexpr (st_ + 3 < NA) issue(std::integral_constant<int, st_ + 3>{});
-        lds_wait<(NA - 1 - st_ < 3 ? NA - 1 - st_ : 3)>(kfr[st_ % 4]);
+        wait_lgkm<(NA - 1 - st_ < 3 ? NA - 1 - st_ : 3)>(kfr[st_ % 4]);
         const bf16x8 kf = __builtin_bit_cast(bf16x8, kfr[st_ % 4]);
 #pragma unroll
         for (int tm = 0; tm < 2; ++tm) acc[tm][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[tm][ks], acc[tm][t], 0, 0, 0);
@@ -303,12 +283,12 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsig
         }
       {   // 4 CT steps (ct, s): dxr^T fragments (channel 16 ct + r, keys 32 q + 8 s + 0 .. 7) by transposing reads, three steps ahead
         constexpr int NC = 4 * CT;
-        const unsigned aT = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sD + (32 * q + (r >> 2)) * RB + (4 * (r & 3)) * 2);
+        const unsigned aT = lds_off(sD + (32 * q + (r >> 2)) * RB + (4 * (r & 3)) * 2);
         u32x2 t1[4], t2[4];
         auto issue = [&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ct = st_ / 4, sidx = st_ % 4, off = 8 * sidx * RB + 32 * ct;
-          lds_rdtr<off>(t1[st_ % 4], aT);
-          lds_rdtr<off + 4 * RB>(t2[st_ % 4], aT);
+          tr_issue_ro<off>(t1[st_ % 4], aT);
+          tr_issue_ro<off + 4 * RB>(t2[st_ % 4], aT);
         };
         issue(std::integral_constant<int, 0>{});
         issue(std::integral_constant<int, 1>{});
@@ -316,7 +296,7 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsig
         static_for<0, NC>([&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ct = st_ / 4, sidx = st_ % 4;
           if constexpr (st_ + 3 < NC) issue(std::integral_constant<int, st_ + 3>{});
-          lds_waittr<2 * (NC - 1 - st_ < 3 ? NC - 1 - st_ : 3)>(t1[st_ % 4], t2[st_ % 4]);
+          wait_lgkm<2 * (NC - 1 - st_ < 3 ? NC - 1 - st_ : 3)>(t1[st_ % 4], t2[st_ % 4]);
           const bf16x8 af = __builtin_bit_cast(bf16x8, u32x4{t1[st_ % 4][0], t1[st_ % 4][1], t2[st_ % 4][0], t2[st_ % 4][1]});
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm) accY[tm][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, pb[tm][sidx], accY[tm][ct], 0, 0, 0);
@@ -346,12 +326,10 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_bwd(const unsig
         const long o = row * C + 16 * ct + 4 * q;
         const unsigned xl = *(const unsigned*)(X + o), xh = *(const unsigned*)(X + o + 2);
         const unsigned ol = *(const unsigned*)(out + o), oh = *(const unsigned*)(out + o + 2);
-        auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-        auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
         const f32x4 y = accY[tm][ct];
-        dot += (lo(xl) * y[0] + hi(xl) * y[1]) + (lo(xh) * y[2] + hi(xh) * y[3]);
-        *(unsigned*)(out + o) = pack2(lo(ol) + y[0], hi(ol) + y[1]);
-        *(unsigned*)(out + o + 2) = pack2(lo(oh) + y[2], hi(oh) + y[3]);
+        dot += (bflo(xl) * y[0] + bfhi(xl) * y[1]) + (bflo(xh) * y[2] + bfhi(xh) * y[3]);
+        *(unsigned*)(out + o) = pack2(bflo(ol) + y[0], bfhi(ol) + y[1]);
+        *(unsigned*)(out + o + 2) = pack2(bflo(oh) + y[2], bfhi(oh) + y[3]);
       }
       dot += __shfl_xor(dot, 16, 64);
       dot += __shfl_xor(dot, 32, 64);
@@ -437,13 +415,13 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_dx(const unsign
         for (int t = 0; t < 4; ++t) { acc[tm][t] = f32x4{0.f, 0.f, 0.f, 0.f}; g[tm][t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
       {   // 4 KS steps (ks, t): the streamed rows' fragments, two steps ahead of the products that use them
         constexpr int NA = 4 * KS, NRD = KEY ? 1 : 2;
-        const unsigned aX = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sX + ((r >> 2) * 32 + 16 * h + (r & 3)) * RB + q * 16);
+        const unsigned aX = lds_off(sX + ((r >> 2) * 32 + 16 * h + (r & 3)) * RB + q * 16);
         const unsigned aD = aX + (unsigned)(sD - sX);
         u32x4 kfr[3], kdr[3];
         auto issue = [&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ks = st_ / 4, t = st_ % 4, off = 4 * t * RB + ks * 64;
-          lds_rd128<off>(kfr[st_ % 3], aX);
-          if constexpr (!KEY) lds_rd128<off>(kdr[st_ % 3], aD);
+          lds_rd128_ro<off>(kfr[st_ % 3], aX);
+          if constexpr (!KEY) lds_rd128_ro<off>(kdr[st_ % 3], aD);
         };
         issue(std::integral_constant<int, 0>{});
         issue(std::integral_constant<int, 1>{});
@@ -451,7 +429,7 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_dx(const unsign
           constexpr int st_ = decltype(ic)::value, ks = st_ / 4, t = st_ % 4;
           if constexpr (st_ + 2 < NA) issue(std::integral_constant<int, st_ + 2>{});
           constexpr int pend = NRD * (NA - 1 - st_ < 2 ? NA - 1 - st_ : 2);
-          if constexpr (KEY) lds_wait<pend>(kfr[st_ % 3]); else lds_wait2<pend>(kfr[st_ % 3], kdr[st_ % 3]);
+          if constexpr (KEY) wait_lgkm<pend>(kfr[st_ % 3]); else wait_lgkm<pend>(kfr[st_ % 3], kdr[st_ % 3]);
           const bf16x8 kf = __builtin_bit_cast(bf16x8, kfr[st_ % 3]);
           if constexpr (KEY) {
 #pragma unroll
@@ -496,12 +474,12 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_dx(const unsign
       }
       {   // 2 CT steps (ct, sp): X^T fragments (channel 16 ct + r, streamed rows 32 q + 16 h + 8 sp + 0 .. 7) by transposing reads, three steps ahead
         constexpr int NC = 2 * CT;
-        const unsigned aT = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sX + (32 * q + 16 * h + (r >> 2)) * RB + (4 * (r & 3)) * 2);
+        const unsigned aT = lds_off(sX + (32 * q + 16 * h + (r >> 2)) * RB + (4 * (r & 3)) * 2);
         u32x2 t1[4], t2[4];
         auto issue = [&](auto ic) {
           constexpr int st_ = decltype(ic)::value, ct = st_ / 2, sp = st_ % 2, off = 8 * sp * RB + 32 * ct;
-          lds_rdtr<off>(t1[st_ % 4], aT);
-          lds_rdtr<off + 4 * RB>(t2[st_ % 4], aT);
+          tr_issue_ro<off>(t1[st_ % 4], aT);
+          tr_issue_ro<off + 4 * RB>(t2[st_ % 4], aT);
         };
         issue(std::integral_constant<int, 0>{});
         issue(std::integral_constant<int, 1>{});
@@ -510,7 +488,7 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_dx(const unsign
           constexpr int st_ = decltype(ic)::value, ct = st_ / 2, sp = st_ % 2;
           if constexpr (st_ + 3 < NC) issue(std::integral_constant<int, st_ + 3>{});
           constexpr int pend = 2 * (NC - 1 - st_ < 3 ? NC - 1 - st_ : 3);
-          lds_waittr<pend>(t1[st_ % 4], t2[st_ % 4]);
+          wait_lgkm<pend>(t1[st_ % 4], t2[st_ % 4]);
           const bf16x8 af = __builtin_bit_cast(bf16x8, u32x4{t1[st_ % 4][0], t1[st_ % 4][1], t2[st_ % 4][0], t2[st_ % 4][1]});
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm) accY[tm][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, pb[tm][sp], accY[tm][ct], 0, 0, 0);
@@ -526,11 +504,9 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : 1)) kk_nxn_dx(const unsign
     for (int ct = 0; ct < CT; ++ct) {
       const long o = row * C + 16 * ct + 4 * q;
       const unsigned ol = *(const unsigned*)(out + o), oh = *(const unsigned*)(out + o + 2);
-      auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-      auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
       const f32x4 y = accY[tm][ct];
-      *(unsigned*)(out + o) = pack2(lo(ol) + y[0], hi(ol) + y[1]);
-      *(unsigned*)(out + o + 2) = pack2(lo(oh) + y[2], hi(oh) + y[3]);
+      *(unsigned*)(out + o) = pack2(bflo(ol) + y[0], bfhi(ol) + y[1]);
+      *(unsigned*)(out + o + 2) = pack2(bflo(oh) + y[2], bfhi(oh) + y[3]);
     }
   }
 }

@@ -196,8 +196,6 @@ __global__ void __launch_bounds__(256) kk_ro_zero(ZeroList z) {
   for (long i = (long)blockIdx.y * 256 + threadIdx.x; i < n; i += (long)gridDim.y * 256) p[i] = 0.f;
 }
 
-unsigned grid1(long n, int cap) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
-
 }  // namespace
 
 int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,
@@ -237,7 +235,7 @@ int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs
   }
   {
     ProfScope ps("k_ro_reduce", 0.0, 0.0, st);
-    hipLaunchKernelGGL(kk_ro_ybar, dim3(grid1((long)d.S * d.Cy, 1024)), dim3(256), 0, st, (const float*)ybp, (const float*)(sv + pl.o_scal),
+    hipLaunchKernelGGL(kk_ro_ybar, dim3(grid1d((long)d.S * d.Cy, 1024)), dim3(256), 0, st, (const float*)ybp, (const float*)(sv + pl.o_scal),
                        ybar, d.S, d.Cy, nch);
     if (grads.fc_b) hipLaunchKernelGGL(kk_ro_bf, dim3((unsigned)cdiv(d.C, 256)), dim3(256), 0, st, drin, grads.fc_b, d.S, d.C);
   }
@@ -261,7 +259,7 @@ int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs
   }
   {
     ProfScope ps("k_ro_dx", (long)d.NT, (double)d.NT * d.C * d.esz * (d.acc_dx ? 2.0 : 1.0), 0.0, st);
-    const unsigned g = grid1((long)d.NT * d.C / 4, 8192);
+    const unsigned g = grid1d((long)d.NT * d.C / 4, 8192);
     if (d.bf16) hipLaunchKernelGGL(kk_ro_dx<__bf16>, dim3(g), dim3(256), 0, st, drin, dX, d.S, d.N, d.C, invN, d.acc_dx);
     else hipLaunchKernelGGL(kk_ro_dx<float>, dim3(g), dim3(256), 0, st, drin, dX, d.S, d.N, d.C, invN, d.acc_dx);
   }

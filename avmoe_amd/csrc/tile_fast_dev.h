@@ -3,7 +3,6 @@
 // the per-block folds of column / scalar accumulators.  Included inside `namespace avmoe`; everything lives in an anonymous namespace
 // (one copy per translation unit).
 #pragma once
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 namespace {
 
@@ -139,8 +138,7 @@ template <int E> __device__ __forceinline__ int zcol(int c, int e, int q) { retu
 #ifndef KF_MMT_BF16
 #define KF_MMT_BF16 1
 #endif
-typedef __attribute__((ext_vector_type(8))) __bf16 kf_bf16x8;
-__device__ __forceinline__ void kf_split8(const float4& v0, const float4& v1, kf_bf16x8& hi, kf_bf16x8& lo) {
+__device__ __forceinline__ void kf_split8(const float4& v0, const float4& v1, bf16x8& hi, bf16x8& lo) {
   const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -156,7 +154,7 @@ __device__ __forceinline__ f32x4 mmT_split(const float* Mt, int ld, int col0, co
   const float* mp = Mt + (col0 + r) * ld + 4 * q;
 #pragma unroll
   for (int j = 0; j < NJ; j += 2) {
-    kf_bf16x8 ah, al, ph, pl;
+    bf16x8 ah, al, ph, pl;
     kf_split8(*(const float4*)(mp + 16 * j), *(const float4*)(mp + 16 * (j + 1)), ah, al);
     kf_split8(p[j], p[j + 1], ph, pl);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, ph, acc, 0, 0, 0);

@@ -22,8 +22,6 @@
 
 namespace avmoe {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 namespace {
 
 struct GenDims { int S, N, C, E, K, Kp, El, KL, KLT, KLp, KPp, NT, per, DZ, XW;
@@ -152,8 +150,7 @@ template <int NC> __device__ __forceinline__ void zero_chunks(float4 (&v)[NC]) {
 // bf16 GEMM of the engine ran on the same compute units from another stream (AdapterPair's two-stream mode; never alone on the
 // GPU, never with the mat-vecs on the vector ALU: tests/dev/race_buffers.py, scripts/mfma_probe.hip, DESIGN.md section 5).  The bf16
 // matrix instructions next to the same neighbours repeat bit for bit.
-typedef __attribute__((ext_vector_type(8))) __bf16 gen_bf16x8;
-__device__ __forceinline__ void split8(const float4& v0, const float4& v1, gen_bf16x8& hi, gen_bf16x8& lo) {
+__device__ __forceinline__ void split8(const float4& v0, const float4& v1, bf16x8& hi, bf16x8& lo) {
   const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
@@ -171,7 +168,7 @@ __device__ __forceinline__ f32x4 mmT_split(const float* Mt, int ld, int col0, co
     const float4 a0 = *(const float4*)(mp + 16 * j);
     const float4 a1 = (j + 1 < NJ) ? *(const float4*)(mp + 16 * (j + 1)) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 p1 = (j + 1 < NJ) ? p[j + 1 < NJ ? j + 1 : j] : make_float4(0.f, 0.f, 0.f, 0.f);
-    gen_bf16x8 ah, al, ph, pl;
+    bf16x8 ah, al, ph, pl;
     split8(a0, a1, ah, al);
     split8(p[j], p1, ph, pl);
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, ph, acc, 0, 0, 0);

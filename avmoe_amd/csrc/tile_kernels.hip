@@ -18,19 +18,6 @@
 
 namespace avmoe {
 
-#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
-  do {                                                                                        \
-    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
-    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
-  } while (0)
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 template <typename T> __device__ __forceinline__ float rndT(float v);
 template <> __device__ __forceinline__ float rndT<float>(float v) { return v; }
 template <> __device__ __forceinline__ float rndT<__bf16>(float v) { return bf2f(f2bf(v)); }
@@ -319,7 +306,7 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
         sum = qsum4(sum);
         const float inv = rowok ? 1.f / sum : 0.f;
         float u1 = 0.f, u2 = 0.f;
-        wsync();
+        wave_lds_sync();
         for (int kk = 0; kk < t.k4; ++kk) {
           const int k = 4 * kk + q;
           float av = 0.f;
@@ -334,7 +321,7 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
         if (rowok) for (int k = K4 + q; k < t.Kp; k += 4) stT<T>(aout, (long)l * t.aL + (t0 + r) * t.Kp + k, 0.f);
         u1 = qsum4(u1); u2 = qsum4(u2);
         if (q == 0) { rv[r] = u1; rv[16 + r] = u2; }
-        wsync();
+        wave_lds_sync();
         // ---- u3 = a^T (T T^T) a  through the matrix pipe ----
         float u3[4] = {0.f, 0.f, 0.f, 0.f};
         for (int ct = 0; ct * 16 < K; ++ct) {
@@ -492,9 +479,9 @@ __global__ void __launch_bounds__(256) kt_post_small(PostTArgs a, const float* _
     const float qv = probs[(long)s * t.E + e] * gate;
     for (int n0 = n_beg + 16 * wave; n0 < n_end; n0 += 64) {
       const long t0 = (long)s * t.N + n0;
-      wsync();
+      wave_lds_sync();
       load_zp_tile(t, e, relu, Z, s_sc, s_sh, t0, n0, Zt, r, q);
-      wsync();
+      wave_lds_sync();
       float rp[4] = {1.f, 1.f, 1.f, 1.f}, mup[4] = {0.f, 0.f, 0.f, 0.f};
       if (a.ln_post) {
         float so[4] = {0.f, 0.f, 0.f, 0.f}, soo[4] = {0.f, 0.f, 0.f, 0.f};
@@ -641,7 +628,7 @@ __global__ void __launch_bounds__(256) kt_post_small_bwd(PostBTArgs a, const flo
     for (int n0 = n_beg + 16 * wave; n0 < n_end; n0 += 16 * nw) {
       const long t0 = (long)s * t.N + n0;
       const int nvalid = min(16, t.N - n0);
-      wsync();
+      wave_lds_sync();
       // ---- phase A: everything this tile needs, in coalesced 16-byte loads ----
       auto zx = [&](int dd, float z) { const float y = z * s_sc[dd] + s_sh[dd]; return relu ? fmaxf(y, 0.f) : y; };
       if constexpr (PF) {
@@ -664,7 +651,7 @@ __global__ void __launch_bounds__(256) kt_post_small_bwd(PostBTArgs a, const flo
           rw[lane] = d1; rw[16 + lane] = d2; rw[32 + lane] = d3; rw[48 + lane] = rpv; rw[64 + lane] = mupv;
         }
       }
-      wsync();
+      wave_lds_sync();
       // ---- phase B: bottleneck-space arithmetic from LDS ----
       float zz[4] = {0.f, 0.f, 0.f, 0.f};
       for (int ct = 0; ct * 16 < DD; ++ct) {
@@ -717,7 +704,7 @@ __global__ void __launch_bounds__(256) kt_post_small_bwd(PostBTArgs a, const flo
           c0 = qsum4(c0); c1 = qsum4(c1);
           if (q == 0 && jp < dgp) { mycol[dd] += c0; mycol[DD + dd] += c1; }
         }
-      wsync();
+      wave_lds_sync();
       // ---- phase C: coalesced stores ----
       slab_store_f32(dzp + t0 * t.DZ, t.DZ, (long)t.E * dgp, e * dgp, t, nvalid, Ot, ld, lane, [](int) { return 1.f; });
       slab_store_T<T>(Zp_, t0 * t.DZ, t.DZ, (long)t.E * dgp, e * dgp, t, nvalid, Zt, ld, lane, [](int) { return 1.f; });
@@ -770,10 +757,10 @@ __global__ void __launch_bounds__(256) kt_mid_bwd(MidBTArgs a, const float* __re
     for (int n0 = n_beg + 16 * wave; n0 < n_end; n0 += 16 * nw) {
       const long t0 = (long)s * t.N + n0;
       const int nvalid = min(16, t.N - n0);
-      wsync();
+      wave_lds_sync();
       slab_load<4>(Z + t0 * t.DZ, t.DZ, (long)t.E * dgp, e * dgp, t, nvalid, Zr, ld, lane, [](int, float v) { return v; });
       slab_load<4>(dzp + t0 * t.DZ, t.DZ, (long)t.E * dgp, e * dgp, t, nvalid, Dt, ld, lane, [](int, float v) { return v; });
-      wsync();
+      wave_lds_sync();
       if (a.moments) {                       // z' tile (A operand of the BN2-moment term)
         for (int ct = 0; ct * 16 < DD; ++ct) {
           const int dd = ct * 16 + r;
@@ -785,7 +772,7 @@ __global__ void __launch_bounds__(256) kt_mid_bwd(MidBTArgs a, const float* __re
             }
           }
         }
-        wsync();
+        wave_lds_sync();
       }
       for (int gi = 0; gi < t.g; ++gi)
         for (int ct = 0; ct * 16 < dgp; ++ct) {
@@ -810,7 +797,7 @@ __global__ void __launch_bounds__(256) kt_mid_bwd(MidBTArgs a, const float* __re
           c0 = qsum4(c0); c1 = qsum4(c1);
           if (q == 0 && jp < dgp) { mycol[dd] += c0; mycol[DD + dd] += c1; }
         }
-      wsync();
+      wave_lds_sync();
       slab_store_f32(dzp + t0 * t.DZ, t.DZ, (long)t.E * dgp, e * dgp, t, nvalid, Dt, ld, lane, [](int) { return 1.f; });
     }
     flush_colacc(t, s_col, 2, e, colpart, blk, 2);
@@ -903,7 +890,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
       }
       // ---- BN1 input gradient, folded-LayerNorm sums, dzraw tile ----
       float s_dr[4] = {0.f, 0.f, 0.f, 0.f}, s_dmu[4] = {0.f, 0.f, 0.f, 0.f}, s_zr[4] = {0.f, 0.f, 0.f, 0.f};
-      wsync();
+      wave_lds_sync();
       for (int ct = 0; ct * 16 < DD; ++ct) {
         const int dd = ct * 16 + r;
         float c0 = 0.f, c1 = 0.f;
@@ -978,7 +965,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
         }
         u1 = qsum4(u1); u2 = qsum4(u2);
         if (q == 0) { rv[r] = u1; rv[16 + r] = u2; }
-        wsync();
+        wave_lds_sync();
         float u3[4] = {0.f, 0.f, 0.f, 0.f}, dgr[4] = {0.f, 0.f, 0.f, 0.f};
         for (int ct = 0; ct * 16 < DD; ++ct) {                       // dzraw . (a TW)
           const f32x4 p = tile_mm(At, t.lda_k, s_TW, t.ldb_d, t.k4, ct * 16, r, q);
@@ -1014,7 +1001,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
           u3[x] = rsum16(u3[x]); dgr[x] = rsum16(dgr[x]);
           if (r == 0 && ok[x]) sdg += dSx[x] * (float)t.C * rv[4 * q + x] + dSxx[x] * (2.f * rv[16 + 4 * q + x] + 2.f * gv * u3[x]) + dgr[x];
         }
-        wsync();
+        wave_lds_sync();
         for (int ct = 0; ct * 16 < t.Kp; ++ct) {
           const int k = ct * 16 + r;
           if (k < t.Kp) {

@@ -19,6 +19,7 @@
 // CU against 4.3 - 4.5 with 1024 - 4096 blocks; the register-resident kernels reach 3.3 - 4.2.
 #include "kernels.h"
 #include "device_utils.h"
+#include "stream_isa.h"
 #include "prof.h"
 #include <algorithm>
 
@@ -41,17 +42,11 @@ namespace avmoe {
 
 namespace {
 
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N < 63 ? N : 63) : "memory"); }
 __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ void glds16(const void* g, char* l) { __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 16, 0, KFS_AUX); }
-__device__ __forceinline__ void glds4(const void* g, char* l) { __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)l, 4, 0, KFS_AUX); }
 
 // waves of a streaming block: tile slots x experts, 8 waves (6 for three experts)
 template <int E> struct WS {
@@ -88,19 +83,12 @@ __device__ __forceinline__ void it_next(TileIt& it, int vb1, int bps, int per, i
 // ---- LDS accesses of the tile loops as inline assembly ---------------------------------------------------------------------------
 // hipcc answers EVERY LDS access it can see that follows a direct global -> LDS load with s_waitcnt vmcnt(0) (it cannot tell the ring from
 // the rest of the LDS), which would drain the ring once per tile: after the prologue no C++-level LDS access exists in these kernels.
-__device__ __forceinline__ unsigned lds_off(const void* p) { return (unsigned)(size_t)(lptr_t)p; }
-template <int OFF> __device__ __forceinline__ void lds_rd16(f32x4& d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
 __device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 // ... and the registers such reads fill pass through an (empty) asm statement behind the wait: volatile asm statements keep their order, so no
 // use of them is scheduled between the read and the wait
 __device__ __forceinline__ void lds_use(f32x4& a) { asm volatile("" : "+v"(a)); }
 template <typename... R> __device__ __forceinline__ void lds_use(f32x4& a, R&... rest) { lds_use(a); lds_use(rest...); }
-__device__ __forceinline__ float lds_rd1(unsigned addr) { float v; asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory"); return v; }
-__device__ __forceinline__ void lds_wr16(unsigned addr, const float4& v) {
-  const f32x4 x = {v.x, v.y, v.z, v.w};
-  asm volatile("ds_write_b128 %0, %1" :: "v"(addr), "v"(x) : "memory");
-}
-__device__ __forceinline__ void lds_wr1(unsigned addr, float v) { asm volatile("ds_write_b32 %0, %1" :: "v"(addr), "v"(v) : "memory"); }
+__device__ __forceinline__ void lds_wr16(unsigned addr, const float4& v) { lds_wr128(addr, f32x4{v.x, v.y, v.z, v.w}); }
 __device__ __forceinline__ uint4 as_u4(const f32x4& v) { return make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])); }
 
 // wait until this wave's tile `it` has landed: `newer` tiles were requested after it, `stored` tiles' stores were issued since its request
@@ -133,9 +121,8 @@ __device__ __forceinline__ void fold_put_cols(unsigned s_x, int k, float4 (&acc)
 }
 template <int NC>
 __device__ __forceinline__ void fold_put_scalar(unsigned s_x, int k, float v, int wave, int lane) {
-  if (lane == 0) lds_wr1(s_x + 4 * (wave * fold_stride<NC>() + NC * FDD + k), v);
+  if (lane == 0) lds_wr32(s_x + 4 * (wave * fold_stride<NC>() + NC * FDD + k), v);
 }
-__device__ __forceinline__ void lds_rd1_issue(float& v, unsigned addr) { asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr) : "memory"); }
 __device__ __forceinline__ void lds_use(float& a) { asm volatile("" : "+v"(a)); }
 // the NV values idx[0 .. NV) of expert e summed over the tile slots in slot order: every read issued, one wait   (idx: k * 64 + dd of a column,
 // NC * 64 + k of a scalar)
@@ -145,7 +132,7 @@ __device__ __forceinline__ void fold_get(unsigned s_x, const int (&idx)[NV], int
 #pragma unroll
   for (int i = 0; i < NV; ++i)
 #pragma unroll
-    for (int u = 0; u < NS; ++u) lds_rd1_issue(v[i][u], s_x + 4 * ((u * E + e) * fold_stride<NC>() + idx[i]));
+    for (int u = 0; u < NS; ++u) lds_rd32(v[i][u], s_x + 4 * ((u * E + e) * fold_stride<NC>() + idx[i]));
   lds_wait();
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -174,8 +161,8 @@ template <int E> constexpr int psb_fixed_floats(int nfr) { return psb_fold_float
 template <int E> constexpr size_t psb_lds(int nfr) { return (size_t)psb_fixed_floats<E>(nfr) * 4 + (size_t)WS<E>::NW * (PSB_GRAM + (KFS_P + 1) * PSB_TILE); }
 
 // one transposed mat-vec step of mmT_split with the matrix operand split into bf16 planes ONCE (registers, whole kernel)
-__device__ __forceinline__ f32x4 mm_presplit(const kf_bf16x8& ah, const kf_bf16x8& al, const float4& p0, const float4& p1) {
-  kf_bf16x8 ph, pl;
+__device__ __forceinline__ f32x4 mm_presplit(const bf16x8& ah, const bf16x8& al, const float4& p0, const float4& p1) {
+  bf16x8 ph, pl;
   kf_split8(p0, p1, ph, pl);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, ph, acc, 0, 0, 0);
@@ -183,10 +170,6 @@ __device__ __forceinline__ f32x4 mm_presplit(const kf_bf16x8& ah, const kf_bf16x
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, ph, acc, 0, 0, 0);
   return acc;
 }
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-template <int OFF> __device__ __forceinline__ void lds_rd_tr(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
-__device__ __forceinline__ void lds_wr8(unsigned addr, const u32x2& v) { asm volatile("ds_write_b64 %0, %1" :: "v"(addr), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_use(u32x2& a) { asm volatile("" : "+v"(a)); }
 
 template <int E>
@@ -229,14 +212,14 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
     const long tk = f0 + min(it.n0 + r, N - 1);      // (rows past the frame's last token re-read it; masked below)
     char* dst = ring + slot * PSB_TILE;
     const char* zs = (const char*)(Z + tk * DZ + e * FDG + seg_off8(q));
-    glds16(zs, dst); glds16(zs + E * FDG * 2, dst + 1024);
+    glds<16, KFS_AUX>(zs, dst); glds<16, KFS_AUX>(zs + E * FDG * 2, dst + 1024);
     const char* ds = (const char*)(dAp16 + tk * 2 * a.dapw + e * FDG + seg_off8(q));
-    glds16(ds, dst + 2048); glds16(ds + a.dapw * 2, dst + 3072);
+    glds<16, KFS_AUX>(ds, dst + 2048); glds<16, KFS_AUX>(ds + a.dapw * 2, dst + 3072);
     const long t2 = f0 + min(it.n0 + (lane >> 2), N - 1);
     const int j = lane & 3;
     const float* pa = j < 3 ? a.dApx + (t2 * 2) * 16 + 3 * e + j : rpmup + (long)e * t.NT + t2;
     const float* pb = j < 3 ? a.dApx + (t2 * 2 + 1) * 16 + 3 * e + j : rpmup + (long)t.NT * E + (long)e * t.NT + t2;
-    glds4(pa, dst + 4096); glds4(pb, dst + 4352);
+    glds<4, KFS_AUX>(pa, dst + 4096); glds<4, KFS_AUX>(pb, dst + 4352);
   };
   TileIt pf = it_first<NS>(vb0, vb1, bps, per, N, ts);
   int nreq = 0;
@@ -246,7 +229,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
 
   // ---- per-expert constants, registers for the whole kernel (the register-resident kernels re-read them from the LDS per tile); their
   // loads fly beside the first requests (hipcc waits for both together: once per block) ----
-  kf_bf16x8 gh[2][2], gl[2][2];                     // Gq^T rows 16 ct + r of group gi, entries 4 q .. + 3 and 16 + 4 q .. + 3, as bf16 planes
+  bf16x8 gh[2][2], gl[2][2];                     // Gq^T rows 16 ct + r of group gi, entries 4 q .. + 3 and 16 + 4 q .. + 3, as bf16 planes
 #pragma unroll
   for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
@@ -276,7 +259,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
   int nfold = 0;
   for (int vb = vb0; vb < vb1; ++vb, s += (vbb + 1 == bps), vbb = (vbb + 1 == bps) ? 0 : vbb + 1) {
     const int n_beg = vbb * per, n_end = min(N, n_beg + per);
-    const float qv = lds_rd1(qv_a + 4 * ((s - s_first) * E + e));
+    const float qv = lds_rd32_wait(qv_a + 4 * ((s - s_first) * E + e));
     int qsel = 0;      // the lane (of the four that hold a token) that takes this tile's scalar terms: four times as many partial sums
     for (int n0 = n_beg + 16 * ts; n0 < n_end; n0 += 16 * NS, qsel = (qsel + 1) & 3, ++it) {
       // In-order counter; issue order per tile i: [wait for tile i] [requests of tile i + P] [stores of tile i]
@@ -286,11 +269,11 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
       const long tok = (long)s * N + n0 + r;
       const unsigned sl = ring_a + (it % D) * PSB_TILE;
       f32x4 rz0, rz1, rd0, rd1, ra, rb;
-      lds_rd16<0>(rz0, sl + lane * 16); lds_rd16<1024>(rz1, sl + lane * 16); lds_rd16<2048>(rd0, sl + lane * 16); lds_rd16<3072>(rd1, sl + lane * 16);
-      lds_rd16<4096>(ra, sl + r * 16); lds_rd16<4352>(rb, sl + r * 16);
+      lds_rd128<0>(rz0, sl + lane * 16); lds_rd128<1024>(rz1, sl + lane * 16); lds_rd128<2048>(rd0, sl + lane * 16); lds_rd128<3072>(rd1, sl + lane * 16);
+      lds_rd128<4096>(ra, sl + r * 16); lds_rd128<4352>(rb, sl + r * 16);
       f32x4 sc[4], sh[4];                            // (row constants of this expert: from the LDS per tile, like us / vh below -- the registers are the Gram's)
-      lds_rd16<512>(sc[0], uv_a + 16 * q); lds_rd16<576>(sc[1], uv_a + 16 * q); lds_rd16<640>(sc[2], uv_a + 16 * q); lds_rd16<704>(sc[3], uv_a + 16 * q);
-      lds_rd16<768>(sh[0], uv_a + 16 * q); lds_rd16<832>(sh[1], uv_a + 16 * q); lds_rd16<896>(sh[2], uv_a + 16 * q); lds_rd16<960>(sh[3], uv_a + 16 * q);
+      lds_rd128<512>(sc[0], uv_a + 16 * q); lds_rd128<576>(sc[1], uv_a + 16 * q); lds_rd128<640>(sc[2], uv_a + 16 * q); lds_rd128<704>(sc[3], uv_a + 16 * q);
+      lds_rd128<768>(sh[0], uv_a + 16 * q); lds_rd128<832>(sh[1], uv_a + 16 * q); lds_rd128<896>(sh[2], uv_a + 16 * q); lds_rd128<960>(sh[3], uv_a + 16 * q);
       lds_wait();
       lds_use(rz0, rz1, rd0, rd1, ra, rb);
       lds_use(sc[0], sc[1], sc[2], sc[3]); lds_use(sh[0], sh[1], sh[2], sh[3]);
@@ -344,19 +327,19 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const u32x2 pk = {(unsigned)f2bf(zp[c].x) | ((unsigned)f2bf(zp[c].y) << 16), (unsigned)f2bf(zp[c].z) | ((unsigned)f2bf(zp[c].w) << 16)};
-          lds_wr8(gram_a + r * PSB_ZPITCH + (16 * c + 4 * q) * 2, pk);
+          lds_wr64(gram_a + r * PSB_ZPITCH + (16 * c + 4 * q) * 2, pk);
         }
-        if (q == 0) lds_wr1(gram_a + 16 * PSB_ZPITCH + 4 * r, dSoo);
+        if (q == 0) lds_wr32(gram_a + 16 * PSB_ZPITCH + 4 * r, dSoo);
         f32x4 us[4], vh[4];                          // (this expert's us / vh rows: read here, used by the last loop of the tile)
-        lds_rd16<0>(us[0], uv_a + 16 * q); lds_rd16<64>(us[1], uv_a + 16 * q); lds_rd16<128>(us[2], uv_a + 16 * q); lds_rd16<192>(us[3], uv_a + 16 * q);
-        lds_rd16<256>(vh[0], uv_a + 16 * q); lds_rd16<320>(vh[1], uv_a + 16 * q); lds_rd16<384>(vh[2], uv_a + 16 * q); lds_rd16<448>(vh[3], uv_a + 16 * q);
+        lds_rd128<0>(us[0], uv_a + 16 * q); lds_rd128<64>(us[1], uv_a + 16 * q); lds_rd128<128>(us[2], uv_a + 16 * q); lds_rd128<192>(us[3], uv_a + 16 * q);
+        lds_rd128<256>(vh[0], uv_a + 16 * q); lds_rd128<320>(vh[1], uv_a + 16 * q); lds_rd128<384>(vh[2], uv_a + 16 * q); lds_rd128<448>(vh[3], uv_a + 16 * q);
         // fragments: lane (r, q) gets [token 4 q + j][column 16 ct + r], j = 0 .. 3 (the lanes of a q group read a 4 x 16 block, transposed)
         u32x2 f[4];
         f32x4 w4;
         const unsigned fa0 = gram_a + (4 * q + (r >> 2)) * PSB_ZPITCH + 8 * (r & 3);
         lds_wait();                                  // (the tile's writes above: same wave, in order -- the wait covers the uv reads too)
-        lds_rd_tr<0>(f[0], fa0); lds_rd_tr<32>(f[1], fa0); lds_rd_tr<64>(f[2], fa0); lds_rd_tr<96>(f[3], fa0);
-        lds_rd16<16 * PSB_ZPITCH>(w4, gram_a + 16 * q);
+        tr_issue<0>(f[0], fa0); tr_issue<32>(f[1], fa0); tr_issue<64>(f[2], fa0); tr_issue<96>(f[3], fa0);
+        lds_rd128<16 * PSB_ZPITCH>(w4, gram_a + 16 * q);
         lds_wait();
         lds_use(f[0]); lds_use(f[1]); lds_use(f[2]); lds_use(f[3]); lds_use(w4);
         lds_use(us[0], us[1], us[2], us[3]); lds_use(vh[0], vh[1], vh[2], vh[3]);
@@ -493,16 +476,16 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_mid_bwd(SMidBArgs a, const
     const long tk = (long)it.s * N + min(it.n0 + r, N - 1);
     char* dst = ring + slot * MDB_TILE;
     const char* zs = (const char*)(Z + tk * DZ + e * FDG + seg_off8(q));
-    glds16(zs, dst); glds16(zs + E * FDG * 2, dst + 1024);
+    glds<16, KFS_AUX>(zs, dst); glds<16, KFS_AUX>(zs + E * FDG * 2, dst + 1024);
     const char* ds = (const char*)(dzp + tk * DZ + e * FDG + seg_off8(q));
-    glds16(ds, dst + 2048); glds16(ds + E * FDG * 2, dst + 3072);
+    glds<16, KFS_AUX>(ds, dst + 2048); glds<16, KFS_AUX>(ds + E * FDG * 2, dst + 3072);
   };
   TileIt pf = it_first<NS>(vb0, vb1, bps, per, N, ts);
   int nreq = 0;
 #pragma unroll
   for (int k = 0; k < KFS_P; ++k)
     if (pf.vb < vb1) { request(nreq % D, pf); ++nreq; it_next<NS>(pf, vb1, bps, per, N, ts); }
-  kf_bf16x8 gh[2][2], gl[2][2];                     // sdSzz^T rows 16 ct + r of group gi as bf16 planes (mm_presplit)
+  bf16x8 gh[2][2], gl[2][2];                     // sdSzz^T rows 16 ct + r of group gi as bf16 planes (mm_presplit)
 #pragma unroll
   for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
@@ -530,9 +513,9 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_mid_bwd(SMidBArgs a, const
       const long tok = (long)s * N + n0 + r;
       const unsigned sl = ring_a + (it % D) * MDB_TILE;
       f32x4 rz0, rz1, rd0, rd1, sc[4], sh[4];
-      lds_rd16<0>(rz0, sl + lane * 16); lds_rd16<1024>(rz1, sl + lane * 16); lds_rd16<2048>(rd0, sl + lane * 16); lds_rd16<3072>(rd1, sl + lane * 16);
-      lds_rd16<512>(sc[0], bn_a + 16 * q); lds_rd16<576>(sc[1], bn_a + 16 * q); lds_rd16<640>(sc[2], bn_a + 16 * q); lds_rd16<704>(sc[3], bn_a + 16 * q);
-      lds_rd16<768>(sh[0], bn_a + 16 * q); lds_rd16<832>(sh[1], bn_a + 16 * q); lds_rd16<896>(sh[2], bn_a + 16 * q); lds_rd16<960>(sh[3], bn_a + 16 * q);
+      lds_rd128<0>(rz0, sl + lane * 16); lds_rd128<1024>(rz1, sl + lane * 16); lds_rd128<2048>(rd0, sl + lane * 16); lds_rd128<3072>(rd1, sl + lane * 16);
+      lds_rd128<512>(sc[0], bn_a + 16 * q); lds_rd128<576>(sc[1], bn_a + 16 * q); lds_rd128<640>(sc[2], bn_a + 16 * q); lds_rd128<704>(sc[3], bn_a + 16 * q);
+      lds_rd128<768>(sh[0], bn_a + 16 * q); lds_rd128<832>(sh[1], bn_a + 16 * q); lds_rd128<896>(sh[2], bn_a + 16 * q); lds_rd128<960>(sh[3], bn_a + 16 * q);
       lds_wait();
       lds_use(rz0, rz1, rd0, rd1);
       lds_use(sc[0], sc[1], sc[2], sc[3]); lds_use(sh[0], sh[1], sh[2], sh[3]);
@@ -547,9 +530,9 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_mid_bwd(SMidBArgs a, const
           at(zp[c], x) = relu ? fmaxf(y, 0.f) : y;
         }
       f32x4 mean[4], rstd[4], dm[4];
-      lds_rd16<0>(mean[0], bn_a + 16 * q); lds_rd16<64>(mean[1], bn_a + 16 * q); lds_rd16<128>(mean[2], bn_a + 16 * q); lds_rd16<192>(mean[3], bn_a + 16 * q);
-      lds_rd16<256>(rstd[0], bn_a + 16 * q); lds_rd16<320>(rstd[1], bn_a + 16 * q); lds_rd16<384>(rstd[2], bn_a + 16 * q); lds_rd16<448>(rstd[3], bn_a + 16 * q);
-      lds_rd16<1024>(dm[0], bn_a + 16 * q); lds_rd16<1088>(dm[1], bn_a + 16 * q); lds_rd16<1152>(dm[2], bn_a + 16 * q); lds_rd16<1216>(dm[3], bn_a + 16 * q);
+      lds_rd128<0>(mean[0], bn_a + 16 * q); lds_rd128<64>(mean[1], bn_a + 16 * q); lds_rd128<128>(mean[2], bn_a + 16 * q); lds_rd128<192>(mean[3], bn_a + 16 * q);
+      lds_rd128<256>(rstd[0], bn_a + 16 * q); lds_rd128<320>(rstd[1], bn_a + 16 * q); lds_rd128<384>(rstd[2], bn_a + 16 * q); lds_rd128<448>(rstd[3], bn_a + 16 * q);
+      lds_rd128<1024>(dm[0], bn_a + 16 * q); lds_rd128<1088>(dm[1], bn_a + 16 * q); lds_rd128<1152>(dm[2], bn_a + 16 * q); lds_rd128<1216>(dm[3], bn_a + 16 * q);
       lds_wait();
       lds_use(mean[0], mean[1], mean[2], mean[3]); lds_use(rstd[0], rstd[1], rstd[2], rstd[3]); lds_use(dm[0], dm[1], dm[2], dm[3]);
 #pragma unroll
@@ -646,14 +629,14 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
     const long tk = (long)it.s * N + min(it.n0 + r, N - 1);
     char* dst = ring + slot * PSF_TILE;
     const char* zs = (const char*)(Z + tk * DZ + e * FDG + seg_off8(q));
-    glds16(zs, dst); glds16(zs + E * FDG * 2, dst + 1024);
+    glds<16, KFS_AUX>(zs, dst); glds<16, KFS_AUX>(zs + E * FDG * 2, dst + 1024);
   };
   TileIt pf = it_first<NS>(vb0, vb1, bps, per, N, ts);
   int nreq = 0;
 #pragma unroll
   for (int k = 0; k < KFS_P; ++k)
     if (pf.vb < vb1) { request(nreq % D, pf); ++nreq; it_next<NS>(pf, vb1, bps, per, N, ts); }
-  kf_bf16x8 gh[2][2], gl[2][2];                     // Gq^T rows as bf16 planes (mm_presplit)
+  bf16x8 gh[2][2], gl[2][2];                     // Gq^T rows as bf16 planes (mm_presplit)
 #pragma unroll
   for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
@@ -670,7 +653,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
   int s = s_first, vbb = vb0 - s_first * bps;
   for (int vb = vb0; vb < vb1; ++vb, s += (vbb + 1 == bps), vbb = (vbb + 1 == bps) ? 0 : vbb + 1) {
     const int n_beg = vbb * per, n_end = min(N, n_beg + per);
-    const float qv = lds_rd1(qv_a + 4 * ((s - s_first) * E + e));
+    const float qv = lds_rd32_wait(qv_a + 4 * ((s - s_first) * E + e));
     for (int n0 = n_beg + 16 * ts; n0 < n_end; n0 += 16 * NS, ++it) {
       wait_tile<PSF_NL, PSF_NST>(min(KFS_P - 1, nreq - it - 1), min(it, KFS_P));
       if (pf.vb < vb1) { request(nreq % D, pf); ++nreq; it_next<NS>(pf, vb1, bps, per, N, ts); }
@@ -678,9 +661,9 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
       const long tok = (long)s * N + n0 + r;
       const unsigned sl = ring_a + (it % D) * PSF_TILE;
       f32x4 rz0, rz1, sc[4], sh[4];
-      lds_rd16<0>(rz0, sl + lane * 16); lds_rd16<1024>(rz1, sl + lane * 16);
-      lds_rd16<512>(sc[0], uv_a + 16 * q); lds_rd16<576>(sc[1], uv_a + 16 * q); lds_rd16<640>(sc[2], uv_a + 16 * q); lds_rd16<704>(sc[3], uv_a + 16 * q);
-      lds_rd16<768>(sh[0], uv_a + 16 * q); lds_rd16<832>(sh[1], uv_a + 16 * q); lds_rd16<896>(sh[2], uv_a + 16 * q); lds_rd16<960>(sh[3], uv_a + 16 * q);
+      lds_rd128<0>(rz0, sl + lane * 16); lds_rd128<1024>(rz1, sl + lane * 16);
+      lds_rd128<512>(sc[0], uv_a + 16 * q); lds_rd128<576>(sc[1], uv_a + 16 * q); lds_rd128<640>(sc[2], uv_a + 16 * q); lds_rd128<704>(sc[3], uv_a + 16 * q);
+      lds_rd128<768>(sh[0], uv_a + 16 * q); lds_rd128<832>(sh[1], uv_a + 16 * q); lds_rd128<896>(sh[2], uv_a + 16 * q); lds_rd128<960>(sh[3], uv_a + 16 * q);
       lds_wait();
       lds_use(rz0, rz1); lds_use(sc[0], sc[1], sc[2], sc[3]); lds_use(sh[0], sh[1], sh[2], sh[3]);
       float4 zraw[4], zp[4];
@@ -695,8 +678,8 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
       float rp = 1.f, mup = 0.f;
       if (a.ln_post) {
         f32x4 us[4], vh[4];
-        lds_rd16<0>(us[0], uv_a + 16 * q); lds_rd16<64>(us[1], uv_a + 16 * q); lds_rd16<128>(us[2], uv_a + 16 * q); lds_rd16<192>(us[3], uv_a + 16 * q);
-        lds_rd16<256>(vh[0], uv_a + 16 * q); lds_rd16<320>(vh[1], uv_a + 16 * q); lds_rd16<384>(vh[2], uv_a + 16 * q); lds_rd16<448>(vh[3], uv_a + 16 * q);
+        lds_rd128<0>(us[0], uv_a + 16 * q); lds_rd128<64>(us[1], uv_a + 16 * q); lds_rd128<128>(us[2], uv_a + 16 * q); lds_rd128<192>(us[3], uv_a + 16 * q);
+        lds_rd128<256>(vh[0], uv_a + 16 * q); lds_rd128<320>(vh[1], uv_a + 16 * q); lds_rd128<384>(vh[2], uv_a + 16 * q); lds_rd128<448>(vh[3], uv_a + 16 * q);
         lds_wait();
         lds_use(us[0], us[1], us[2], us[3]); lds_use(vh[0], vh[1], vh[2], vh[3]);
         float so = 0.f, soo = 0.f;
@@ -717,7 +700,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
       }
       if (q == 2) {                                  // (this virtual block's rp / mup, for its scalar-column pass below)
         const unsigned o = rm_a + 4 * (((n0 - n_beg) + r) * E + e) * 2;
-        lds_wr1(o, rp); lds_wr1(o + 4, mup);
+        lds_wr32(o, rp); lds_wr32(o + 4, mup);
       }
       if (ok) {
         const float scl = qv * rp;
@@ -735,13 +718,13 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
     {
       float qe[E];
 #pragma unroll
-      for (int ee = 0; ee < E; ++ee) qe[ee] = lds_rd1(qv_a + 4 * ((s - s_first) * E + ee));
+      for (int ee = 0; ee < E; ++ee) qe[ee] = lds_rd32_wait(qv_a + 4 * ((s - s_first) * E + ee));
       for (int idx = threadIdx.x; idx < 2 * (n_end - n_beg); idx += NTHR) {
         const int tl = idx >> 1;
         const long tok = (long)s * N + n_beg + tl;
         float v[3 * E], rm[2 * E];
 #pragma unroll
-        for (int ee = 0; ee < 2 * E; ++ee) lds_rd1_issue(rm[ee], rm_a + 4 * (tl * E * 2 + ee));
+        for (int ee = 0; ee < 2 * E; ++ee) lds_rd32(rm[ee], rm_a + 4 * (tl * E * 2 + ee));
         lds_wait();
 #pragma unroll
         for (int ee = 0; ee < E; ++ee) {
@@ -789,10 +772,10 @@ template <int E> constexpr size_t prs_lds(int El) { return (size_t)prs_fixed_flo
 // a transposed mat-vec step with the matrix rows in the LDS (fp32, leading dimension LD32): A-operand rows (col0 + r), entries 4 q .. and 16 + 4 q ..
 __device__ __forceinline__ void mm_lds_issue(f32x4& a0, f32x4& a1, unsigned mt_a, int col0, int r, int q) {
   const unsigned ad = mt_a + 4 * ((col0 + r) * LD32 + 4 * q);
-  lds_rd16<0>(a0, ad); lds_rd16<64>(a1, ad);
+  lds_rd128<0>(a0, ad); lds_rd128<64>(a1, ad);
 }
 __device__ __forceinline__ f32x4 mm_lds_finish(const f32x4& a0, const f32x4& a1, const float4& p0, const float4& p1) {
-  kf_bf16x8 ah, al;
+  bf16x8 ah, al;
   kf_split8(make_float4(a0[0], a0[1], a0[2], a0[3]), make_float4(a1[0], a1[1], a1[2], a1[3]), ah, al);
   return mm_presplit(ah, al, p0, p1);
 }
@@ -847,7 +830,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_small(SPreArgs a, unsi
         if (p < FK * LD32) { const int c = p / LD32, k = p - c * LD32; if (k < FK) src = tt + k * FK + c; }
         else if (p < FK * LD32 + FDD * LD32) { const int pp = p - FK * LD32, dd = pp / LD32, k = pp - dd * LD32; if (k < FK) src = tw + (long)k * DZ + (dd >> 5) * (E * FDG) + ee * FDG + (dd & 31); }
         else if (p < FK * LD32 + FDD * LD32 + FK) src = tsu + (p - FK * LD32 - FDD * LD32);
-        glds4(src, dst + 256 * j);
+        glds<4, KFS_AUX>(src, dst + 256 * j);
       }
     }
   };
@@ -856,13 +839,13 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_small(SPreArgs a, unsi
     const long tk = f0 + min(it.n0 + r, N - 1);
     char* dst = ring + slot * tile_b;
     const char* zs = (const char*)(Z + tk * DZ + e * FDG + seg_off8(q));
-    glds16(zs, dst); glds16(zs + E * FDG * 2, dst + 1024);
+    glds<16, KFS_AUX>(zs, dst); glds<16, KFS_AUX>(zs + E * FDG * 2, dst + 1024);
     const long t2 = f0 + min(it.n0 + (lane >> 2), N - 1);
-    glds4(sxs + ((lane & 1) ? (long)t.NT : 0L) + t2, dst + 2048);          // [token][Sx, Sxx, Sx, Sxx]
+    glds<4, KFS_AUX>(sxs + ((lane & 1) ? (long)t.NT : 0L) + t2, dst + 2048);          // [token][Sx, Sxx, Sx, Sxx]
     if (lat) {
       const char* lg = (const char*)(a.L2g + tk * t.KL + (long)l * FK + 4 * q);
-      glds16(lg, dst + 2304); glds16(lg + 64, dst + 3328);
-      glds16(lg + (long)t.NT * t.KL * 4, dst + 4352); glds16(lg + (long)t.NT * t.KL * 4 + 64, dst + 5376);
+      glds<16, KFS_AUX>(lg, dst + 2304); glds<16, KFS_AUX>(lg + 64, dst + 3328);
+      glds<16, KFS_AUX>(lg + (long)t.NT * t.KL * 4, dst + 4352); glds<16, KFS_AUX>(lg + (long)t.NT * t.KL * 4 + 64, dst + 5376);
     }
   };
   if (El > 0) request_lat(s_first);
@@ -894,9 +877,9 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_small(SPreArgs a, unsi
       const long tok = (long)s * N + n0 + r;
       const unsigned sl = ring_a + (it % D) * tile_b;
       f32x4 rz0, rz1, rs, ws[4], dc[4];
-      lds_rd16<0>(rz0, sl + lane * 16); lds_rd16<1024>(rz1, sl + lane * 16); lds_rd16<2048>(rs, sl + r * 16);
-      lds_rd16<0>(ws[0], ce_a + 16 * q); lds_rd16<64>(ws[1], ce_a + 16 * q); lds_rd16<128>(ws[2], ce_a + 16 * q); lds_rd16<192>(ws[3], ce_a + 16 * q);
-      lds_rd16<256>(dc[0], ce_a + 16 * q); lds_rd16<320>(dc[1], ce_a + 16 * q); lds_rd16<384>(dc[2], ce_a + 16 * q); lds_rd16<448>(dc[3], ce_a + 16 * q);
+      lds_rd128<0>(rz0, sl + lane * 16); lds_rd128<1024>(rz1, sl + lane * 16); lds_rd128<2048>(rs, sl + r * 16);
+      lds_rd128<0>(ws[0], ce_a + 16 * q); lds_rd128<64>(ws[1], ce_a + 16 * q); lds_rd128<128>(ws[2], ce_a + 16 * q); lds_rd128<192>(ws[3], ce_a + 16 * q);
+      lds_rd128<256>(dc[0], ce_a + 16 * q); lds_rd128<320>(dc[1], ce_a + 16 * q); lds_rd128<384>(dc[2], ce_a + 16 * q); lds_rd128<448>(dc[3], ce_a + 16 * q);
       float Sx, Sxx;
       float4 z[4], zo[4], lg[2], av[2] = {zero4(), zero4()};
       f32x4 pw[4];                                   // (a TW) for the four 16-entry chunks
@@ -904,8 +887,8 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_small(SPreArgs a, unsi
       for (int c = 0; c < 4; ++c) pw[c] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (lat) {
         f32x4 a0, a1, b0, b1, tb0, tb1;
-        lds_rd16<2304>(a0, sl + lane * 16); lds_rd16<3328>(a1, sl + lane * 16); lds_rd16<4352>(b0, sl + lane * 16); lds_rd16<5376>(b1, sl + lane * 16);
-        lds_rd16<0>(tb0, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q); lds_rd16<64>(tb1, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q);
+        lds_rd128<2304>(a0, sl + lane * 16); lds_rd128<3328>(a1, sl + lane * 16); lds_rd128<4352>(b0, sl + lane * 16); lds_rd128<5376>(b1, sl + lane * 16);
+        lds_rd128<0>(tb0, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q); lds_rd128<64>(tb1, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q);
         lds_wait();
         lds_use(rz0, rz1, rs, a0, a1, b0, b1, tb0, tb1);
         lds_use(ws[0], ws[1], ws[2], ws[3]); lds_use(dc[0], dc[1], dc[2], dc[3]);
@@ -1105,7 +1088,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
         if (p < FK * LD32) { const int c = p / LD32, k = p - c * LD32; if (k < FK) src = tt + k * FK + c; }
         else if (p < FK * LD32 + FDD * LD32) { const int pp = p - FK * LD32, dd = pp / LD32, k = pp - dd * LD32; if (k < FK) src = tw + (long)k * DZ + (dd >> 5) * (E * FDG) + ee * FDG + (dd & 31); }
         else if (p < FK * LD32 + FDD * LD32 + FK) src = tsu + (p - FK * LD32 - FDD * LD32);
-        glds4(src, dst + 256 * j);
+        glds<4, KFS_AUX>(src, dst + 256 * j);
       }
     }
   };
@@ -1114,15 +1097,15 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
     const long tk = f0 + min(it.n0 + r, N - 1);
     char* dst = ring + slot * tile_b;
     const char* zs = (const char*)(Z + tk * DZ + e * FDG + seg_off8(q));
-    glds16(zs, dst); glds16(zs + E * FDG * 2, dst + 1024);
+    glds<16, KFS_AUX>(zs, dst); glds<16, KFS_AUX>(zs + E * FDG * 2, dst + 1024);
     const char* ys = (const char*)(dy_in + tk * DZ + e * FDG + seg_off8(q));
-    glds16(ys, dst + 2048); glds16(ys + E * FDG * 2, dst + 3072);
+    glds<16, KFS_AUX>(ys, dst + 2048); glds<16, KFS_AUX>(ys + E * FDG * 2, dst + 3072);
     const long t2 = f0 + min(it.n0 + (lane >> 2), N - 1);
-    glds4(rmu + ((lane & 1) ? (long)t.NT * E : 0L) + (long)e * t.NT + t2, dst + 4096);          // [token][rr, mu, rr, mu]
+    glds<4, KFS_AUX>(rmu + ((lane & 1) ? (long)t.NT * E : 0L) + (long)e * t.NT + t2, dst + 4096);          // [token][rr, mu, rr, mu]
     if (lat) {
-      glds16(a.ain + (long)l * t.aL + tk * FK + seg_off8(q), dst + 4352);
+      glds<16, KFS_AUX>(a.ain + (long)l * t.aL + tk * FK + seg_off8(q), dst + 4352);
       const char* lg = (const char*)(a.L2 + tk * t.KL + (long)l * FK + 4 * q);
-      glds16(lg, dst + 5376); glds16(lg + 64, dst + 6400);
+      glds<16, KFS_AUX>(lg, dst + 5376); glds<16, KFS_AUX>(lg + 64, dst + 6400);
     }
   };
   if (El > 0) request_lat(s_first);
@@ -1150,15 +1133,15 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
       const long tok = (long)s * N + n0 + r;
       const unsigned sl = ring_a + (it % D) * tile_b;
       f32x4 rz0, rz1, ry0, ry1, rm;
-      lds_rd16<0>(rz0, sl + lane * 16); lds_rd16<1024>(rz1, sl + lane * 16); lds_rd16<2048>(ry0, sl + lane * 16); lds_rd16<3072>(ry1, sl + lane * 16);
-      lds_rd16<4096>(rm, sl + r * 16);
+      lds_rd128<0>(rz0, sl + lane * 16); lds_rd128<1024>(rz1, sl + lane * 16); lds_rd128<2048>(ry0, sl + lane * 16); lds_rd128<3072>(ry1, sl + lane * 16);
+      lds_rd128<4096>(rm, sl + r * 16);
       f32x4 mean[4], rstd[4], scv[4], mdy[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) { }
-      lds_rd16<0>(mean[0], bn_a + 16 * q); lds_rd16<64>(mean[1], bn_a + 16 * q); lds_rd16<128>(mean[2], bn_a + 16 * q); lds_rd16<192>(mean[3], bn_a + 16 * q);
-      lds_rd16<256>(rstd[0], bn_a + 16 * q); lds_rd16<320>(rstd[1], bn_a + 16 * q); lds_rd16<384>(rstd[2], bn_a + 16 * q); lds_rd16<448>(rstd[3], bn_a + 16 * q);
-      lds_rd16<512>(scv[0], bn_a + 16 * q); lds_rd16<576>(scv[1], bn_a + 16 * q); lds_rd16<640>(scv[2], bn_a + 16 * q); lds_rd16<704>(scv[3], bn_a + 16 * q);
-      lds_rd16<768>(mdy[0], bn_a + 16 * q); lds_rd16<832>(mdy[1], bn_a + 16 * q); lds_rd16<896>(mdy[2], bn_a + 16 * q); lds_rd16<960>(mdy[3], bn_a + 16 * q);
+      lds_rd128<0>(mean[0], bn_a + 16 * q); lds_rd128<64>(mean[1], bn_a + 16 * q); lds_rd128<128>(mean[2], bn_a + 16 * q); lds_rd128<192>(mean[3], bn_a + 16 * q);
+      lds_rd128<256>(rstd[0], bn_a + 16 * q); lds_rd128<320>(rstd[1], bn_a + 16 * q); lds_rd128<384>(rstd[2], bn_a + 16 * q); lds_rd128<448>(rstd[3], bn_a + 16 * q);
+      lds_rd128<512>(scv[0], bn_a + 16 * q); lds_rd128<576>(scv[1], bn_a + 16 * q); lds_rd128<640>(scv[2], bn_a + 16 * q); lds_rd128<704>(scv[3], bn_a + 16 * q);
+      lds_rd128<768>(mdy[0], bn_a + 16 * q); lds_rd128<832>(mdy[1], bn_a + 16 * q); lds_rd128<896>(mdy[2], bn_a + 16 * q); lds_rd128<960>(mdy[3], bn_a + 16 * q);
       lds_wait();
       lds_use(rz0, rz1, ry0, ry1, rm);
       lds_use(mean[0], mean[1], mean[2], mean[3]); lds_use(rstd[0], rstd[1], rstd[2], rstd[3]);
@@ -1171,7 +1154,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
       // ---- BN1 input gradient, first half (needs mdyz) ----
       {
         f32x4 mdyz[4];
-        lds_rd16<1024>(mdyz[0], bn_a + 16 * q); lds_rd16<1088>(mdyz[1], bn_a + 16 * q); lds_rd16<1152>(mdyz[2], bn_a + 16 * q); lds_rd16<1216>(mdyz[3], bn_a + 16 * q);
+        lds_rd128<1024>(mdyz[0], bn_a + 16 * q); lds_rd128<1088>(mdyz[1], bn_a + 16 * q); lds_rd128<1152>(mdyz[2], bn_a + 16 * q); lds_rd128<1216>(mdyz[3], bn_a + 16 * q);
         lds_wait();
         lds_use(mdyz[0], mdyz[1], mdyz[2], mdyz[3]);
 #pragma unroll
@@ -1190,8 +1173,8 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
       float s_dr = 0.f, s_dmu = 0.f;
       if (a.ln_before) {
         f32x4 ws[4], dc[4];
-        lds_rd16<1280>(ws[0], bn_a + 16 * q); lds_rd16<1344>(ws[1], bn_a + 16 * q); lds_rd16<1408>(ws[2], bn_a + 16 * q); lds_rd16<1472>(ws[3], bn_a + 16 * q);
-        lds_rd16<1536>(dc[0], bn_a + 16 * q); lds_rd16<1600>(dc[1], bn_a + 16 * q); lds_rd16<1664>(dc[2], bn_a + 16 * q); lds_rd16<1728>(dc[3], bn_a + 16 * q);
+        lds_rd128<1280>(ws[0], bn_a + 16 * q); lds_rd128<1344>(ws[1], bn_a + 16 * q); lds_rd128<1408>(ws[2], bn_a + 16 * q); lds_rd128<1472>(ws[3], bn_a + 16 * q);
+        lds_rd128<1536>(dc[0], bn_a + 16 * q); lds_rd128<1600>(dc[1], bn_a + 16 * q); lds_rd128<1664>(dc[2], bn_a + 16 * q); lds_rd128<1728>(dc[3], bn_a + 16 * q);
         lds_wait();
         lds_use(ws[0], ws[1], ws[2], ws[3]); lds_use(dc[0], dc[1], dc[2], dc[3]);
 #pragma unroll
@@ -1217,13 +1200,13 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
       if (!ok) { dSx = 0.f; dSxx = 0.f; }
       if (q == 0) {                                  // this expert's sums of the tile's tokens: the per-token pass after the virtual block adds the experts
         const unsigned o = ds_a + 4 * ((((n0 - n_beg) + r) * E + e) * 2);
-        lds_wr1(o, dSx); lds_wr1(o + 4, dSxx);
+        lds_wr32(o, dSx); lds_wr32(o + 4, dSxx);
       }
       if (lat) {
         // ---- the hop-2 block: softmax backward over the latent tokens, mat-vecs against TW / TT (tile_fast.hip::kf_pre_lat_bwd) ----
         f32x4 ra, l0, l1, tb0, tb1;
-        lds_rd16<4352>(ra, sl + lane * 16); lds_rd16<5376>(l0, sl + lane * 16); lds_rd16<6400>(l1, sl + lane * 16);
-        lds_rd16<0>(tb0, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q); lds_rd16<64>(tb1, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q);
+        lds_rd128<4352>(ra, sl + lane * 16); lds_rd128<5376>(l0, sl + lane * 16); lds_rd128<6400>(l1, sl + lane * 16);
+        lds_rd128<0>(tb0, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q); lds_rd128<64>(tb1, lt_a + 4 * (FK * LD32 + FDD * LD32) + 16 * q);
         f32x4 m[12];
         mm_lds_issue(m[0], m[1], lt_a, 0, r, q); mm_lds_issue(m[2], m[3], lt_a, 16, r, q);                 // TT^T rows
 #pragma unroll
@@ -1262,16 +1245,16 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
 #pragma unroll
           for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int x = 0; x < 4; ++x) lds_rd1_issue(tw_[4 * j + x], tw_a + 4 * ((16 * j + 4 * q + x) * LD32));
+            for (int x = 0; x < 4; ++x) lds_rd32(tw_[4 * j + x], tw_a + 4 * ((16 * j + 4 * q + x) * LD32));
           lds_wait();
 #pragma unroll
           for (int i = 0; i < 16; ++i) lds_use(tw_[i]);
-          kf_bf16x8 ah0, al0, ah1, al1;
+          bf16x8 ah0, al0, ah1, al1;
           kf_split8(make_float4(tw_[0], tw_[1], tw_[2], tw_[3]), make_float4(tw_[4], tw_[5], tw_[6], tw_[7]), ah0, al0);
           kf_split8(make_float4(tw_[8], tw_[9], tw_[10], tw_[11]), make_float4(tw_[12], tw_[13], tw_[14], tw_[15]), ah1, al1);
           f32x4 twd;
           {                                                            // tile_fast.hip::mmT_split<4>: chunk pairs (0, 1) and (2, 3) chained
-            kf_bf16x8 ph, pl;
+            bf16x8 ph, pl;
             kf_split8(dzr[0], dzr[1], ph, pl);
             twd = f32x4{0.f, 0.f, 0.f, 0.f};
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al0, ph, twd, 0, 0, 0);
@@ -1336,14 +1319,14 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
           if (r == 0) lds_wr16(fold_a + 4 * (wave * PRB_FOLD + k * FDD + 16 * c + 4 * q), v);
         }
       const float g = wave_sum(sdg);
-      if (lane == 0) lds_wr1(fold_a + 4 * (wave * PRB_FOLD + 2 * FDD + FK), g);
+      if (lane == 0) lds_wr32(fold_a + 4 * (wave * PRB_FOLD + 2 * FDD + FK), g);
     }
     lds_barrier();
     {                                // dL2x[tok][KL] = sum_e dSx, [KL + 1] = 1 ; rs2x = 2 sum_e dSxx   (expert order)
       for (int tl = threadIdx.x; tl < n_end - n_beg; tl += NTHR) {
         float v[2 * E];
 #pragma unroll
-        for (int i = 0; i < 2 * E; ++i) lds_rd1_issue(v[i], ds_a + 4 * (tl * E * 2 + i));
+        for (int i = 0; i < 2 * E; ++i) lds_rd32(v[i], ds_a + 4 * (tl * E * 2 + i));
         lds_wait();
         float accx = 0.f, accxx = 0.f;
 #pragma unroll
@@ -1361,8 +1344,8 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
 #pragma unroll
         for (int u = 0; u < NS; ++u) {
           const unsigned b = fold_a + 4 * ((u * E + e) * PRB_FOLD);
-          lds_rd1_issue(w[0][u], b + 4 * dd); lds_rd1_issue(w[1][u], b + 4 * (FDD + dd));
-          lds_rd1_issue(w[2][u], b + 4 * (2 * FDD + (dd & 31))); lds_rd1_issue(w[3][u], b + 4 * (2 * FDD + FK));
+          lds_rd32(w[0][u], b + 4 * dd); lds_rd32(w[1][u], b + 4 * (FDD + dd));
+          lds_rd32(w[2][u], b + 4 * (2 * FDD + (dd & 31))); lds_rd32(w[3][u], b + 4 * (2 * FDD + FK));
         }
         lds_wait();
 #pragma unroll

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "prof.h"
 #include "kernels.h"
+#include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -32,13 +33,6 @@
 namespace avmoe {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct TP2Args {
   const char* X; long ldx;          // bf16 [tokens][ldx], group g at column g * 384
@@ -67,39 +61,6 @@ constexpr int OFFZ = PX * 1024, OFFL = OFFZ + PZ * 1024, BUF = OFFL + PL * 1024;
 constexpr int TP2_LDS = NBUF * BUF;
 constexpr int NFL = 48;                                                        // stores of a dT flush per wave (4 row tiles x 3 channel tiles x 4 rows)
 static_assert(TP2_LDS <= 160 * 1024, "the buffers fit one CU's LDS");
-
-template <int OFF>
-__device__ __forceinline__ void tr_issue(u32x2& d, unsigned addr) { asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory"); }
-template <int OFF, int ROWB>        // one 16-column fragment: token rows 8 q .. 8 q + 7 (+ the lane's row of four), both halves
-__device__ __forceinline__ void tr_frag2(u32x2 (&f)[2], unsigned base) { tr_issue<OFF>(f[0], base); tr_issue<OFF + 4 * ROWB>(f[1], base); }
-__device__ __forceinline__ void tr_wait3(u32x2 (&x)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]) :: "memory");
-}
-__device__ __forceinline__ void tr_wait6(u32x2 (&x)[3][2], u32x2 (&y)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]),
-               "+v"(y[0][0]), "+v"(y[0][1]), "+v"(y[1][0]), "+v"(y[1][1]), "+v"(y[2][0]), "+v"(y[2][1]) :: "memory");
-}
-template <int N> __device__ __forceinline__ void tr_wait3n(u32x2 (&x)[3][2]) {      // ... until at most N reads are pending
-  asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]) : "n"(N) : "memory");
-}
-template <int N> __device__ __forceinline__ void tr_wait6n(u32x2 (&x)[3][2], u32x2 (&y)[3][2]) {
-  asm volatile("s_waitcnt lgkmcnt(%12)" : "+v"(x[0][0]), "+v"(x[0][1]), "+v"(x[1][0]), "+v"(x[1][1]), "+v"(x[2][0]), "+v"(x[2][1]),
-               "+v"(y[0][0]), "+v"(y[0][1]), "+v"(y[1][0]), "+v"(y[1][1]), "+v"(y[2][0]), "+v"(y[2][1]) : "n"(N) : "memory");
-}
-__device__ __forceinline__ bf16x8 tr_pack(const u32x2 (&f)[2]) { return __builtin_bit_cast(bf16x8, u32x4{f[0][0], f[0][1], f[1][0], f[1][1]}); }
-__device__ __forceinline__ bf16x8 tr_pack_masked(const u32x2 (&f)[2], const u32x4& mk) { return __builtin_bit_cast(bf16x8, u32x4{f[0][0], f[0][1], f[1][0], f[1][1]} & mk); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-// s_waitcnt vmcnt(n) for a run-time (wave-uniform) n: the immediate has to be a constant
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-#define W1(k) case k: wait_vm<k>(); break;
-#define W8(k) W1(k) W1(k + 1) W1(k + 2) W1(k + 3) W1(k + 4) W1(k + 5) W1(k + 6) W1(k + 7)
-    W8(0) W8(8) W8(16) W8(24) W8(32) W8(40) W8(48) W1(56) W1(57) W1(58) W1(59) W1(60) W1(61) W1(62)
-#undef W8
-#undef W1
-    default: wait_vm<63>(); break;        // (the counter's ceiling: waits for more than necessary, never for less)
-  }
-}
 
 // the A fragments (row tiles of the result) of the 32-token step, three at a time: 0 - 7 = dZx column tiles, 8 - 11 = dL2 column tiles
 template <int G3>
@@ -166,7 +127,7 @@ __global__ void __launch_bounds__(NTHR, 1) kk_tok_pair2(const TP2Args p) {
       for (int i = 0; i < NPW; ++i) {
         const int P = wave + 8 * i;
         if (P >= B3) break;
-        __builtin_amdgcn_global_load_lds((gptr_t)(base[P < B1 ? 0 : P < B2 ? 1 : 2] + off_p(P, lane, last)), (lptr_t)(dst + 8192 * i), 16, 0, TP2_AUX);
+        glds<16, TP2_AUX>(base[P < B1 ? 0 : P < B2 ? 1 : 2] + off_p(P, lane, last), dst + 8192 * i);
       }
       return;
     }
@@ -181,7 +142,7 @@ __global__ void __launch_bounds__(NTHR, 1) kk_tok_pair2(const TP2Args p) {
       if (t < 0 || (TP2_DISSECT & 4) || ((TP2_DISSECT & 8) && t != 0) || ((TP2_DISSECT & 16) && t == 0)) continue;      // (bits 3 / 4: the X tiles only / the dZx and dL2 tiles only)
       unsigned o = voff[i];
       asm volatile("" : "+v"(o));                           // (the zero-extension stays here, beside the scalar base: `scalar base + 32-bit lane offset` loads)
-      __builtin_amdgcn_global_load_lds((gptr_t)(base[t] + o), (lptr_t)(dst + 8192 * i), 16, 0, TP2_AUX);
+      glds<16, TP2_AUX>(base[t] + o, dst + 8192 * i);
     }
   };
 
@@ -204,7 +165,7 @@ __global__ void __launch_bounds__(NTHR, 1) kk_tok_pair2(const TP2Args p) {
     if (tile + NBUF - 1 < t1) gload((it + NBUF - 1) % NBUF, tile + NBUF - 1);      // (its buffer was read in the previous iteration: every wave has passed this barrier since)
     const int fj = tile % p.tpf, valid = p.N - fj * BM;     // rows of this tile inside the frame (>= BM: all of them)
     {
-      const unsigned l0 = (unsigned)(size_t)(lptr_t)sX;
+      const unsigned l0 = lds_off(sX);
       const unsigned lx = l0 + (8 * q + (r >> 2)) * RBX + (3 * wave * 16 + 4 * (r & 3)) * 2;
       const unsigned lz = l0 + OFFZ + (8 * q + (r >> 2)) * RBZ + (4 * (r & 3)) * 2;
       const unsigned ll = l0 + OFFL + (8 * q + (r >> 2)) * RBL + (4 * (r & 3)) * 2;
@@ -229,10 +190,10 @@ __global__ void __launch_bounds__(NTHR, 1) kk_tok_pair2(const TP2Args p) {
       if (!(TP2_DISSECT & 2)) {
         // six reads stay in flight behind the nine matrix instructions of the current three row tiles (counted waits: LDS answers in order)
         u32x2 fa2[3][2];
-        issue_b3(fb, lx); issue_a3<0>(fa0, lz, ll); issue_a3<1>(fa1, lz, ll); tr_wait6n<6>(fb, fa0);
-        mm(0, fa0); issue_a3<2>(fa2, lz, ll); tr_wait3n<6>(fa1);
-        mm(3, fa1); issue_a3<3>(fa0, lz, ll); tr_wait3n<6>(fa2);
-        mm(6, fa2); tr_wait3n<0>(fa0);
+        issue_b3(fb, lx); issue_a3<0>(fa0, lz, ll); issue_a3<1>(fa1, lz, ll); wait_lgkm<6>(fb, fa0);
+        mm(0, fa0); issue_a3<2>(fa2, lz, ll); wait_lgkm<6>(fa1);
+        mm(3, fa1); issue_a3<3>(fa0, lz, ll); wait_lgkm<6>(fa2);
+        mm(6, fa2); wait_lgkm<0>(fa0);
         mm(9, fa0);
       }
     }

@@ -11,14 +11,6 @@
 
 namespace avmoe {
 
-#define DISPATCH_T(bf16, KERN, grid, block, shmem, st, ...)                                   \
-  do {                                                                                        \
-    if (bf16) hipLaunchKernelGGL((KERN<__bf16>), grid, block, shmem, st, __VA_ARGS__);        \
-    else hipLaunchKernelGGL((KERN<float>), grid, block, shmem, st, __VA_ARGS__);              \
-  } while (0)
-
-static inline unsigned grid1dw(long n, int cap = 4096) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
-
 constexpr int GCS = 8;       // channel chunks of the Gram kernels
 
 struct WArgs {
@@ -225,7 +217,7 @@ static int run_gram(const Plan& pl, const WArgs& a, int mode, const float* bn2, 
   const size_t sh = (size_t)(cc * d.dgp + 3 * cc) * sizeof(float);
   hipLaunchKernelGGL(kw_gram, dim3(d.g * d.E, GCS), dim3(256), sh, st, a, mode, bn2, dmodv, gpart);
   const long total = (long)d.g * d.E * (d.dgp * d.dgp + 2 * d.dgp + 2);
-  hipLaunchKernelGGL(kw_gram_finish, dim3(grid1dw(total)), dim3(256), 0, st, a, mode, (const float*)gpart, outG, outV);
+  hipLaunchKernelGGL(kw_gram_finish, dim3(grid1d(total)), dim3(256), 0, st, a, mode, (const float*)gpart, outG, outV);
   AVMOE_CHECK_LAUNCH("gram");
   return OK;
 }
@@ -244,11 +236,11 @@ int k_post_prep(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs
   {
     const int ncb = d.g * d.E, cc = cdiv(d.Cg, GCS);
     const size_t shg = (size_t)(cc * d.dgp + 3 * cc) * sizeof(float);
-    const int nb_bp = (int)grid1dw((long)d.C * d.KPp, 1024);
+    const int nb_bp = (int)grid1d((long)d.C * d.KPp, 1024);
     DISPATCH_T(d.bf16, kw_gram_bpost, dim3((unsigned)(ncb * GCS + nb_bp)), dim3(256), shg, st, a, (const float*)(saved + pl.o_bn2),
                (float*)(scratch + pl.o_gpart), (void*)(saved + pl.o_Bpost), ncb);
     const long total = (long)ncb * (d.dgp * d.dgp + 2 * d.dgp + 2);
-    hipLaunchKernelGGL(kw_gram_finish, dim3(grid1dw(total)), dim3(256), 0, st, a, 0, (const float*)(scratch + pl.o_gpart), (float*)(saved + pl.o_Gq),
+    hipLaunchKernelGGL(kw_gram_finish, dim3(grid1d(total)), dim3(256), 0, st, a, 0, (const float*)(scratch + pl.o_gpart), (float*)(saved + pl.o_Gq),
                        (float*)(saved + pl.o_uvh));
   }
   AVMOE_CHECK_LAUNCH("post_prep");
