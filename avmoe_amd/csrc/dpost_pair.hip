@@ -17,7 +17,6 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
-#include "kernels.h"
 #include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
@@ -226,11 +225,26 @@ __global__ void __launch_bounds__(256) kk_dpair_reduce(const float* __restrict__
 
 }  // namespace
 
-// 0 = launched, 1 = shape not served (the caller runs the two kernels), < 0 error
-int k_dpost_pair(const void* dOut, long ldo, const void* Bpost, long ldb, long sBg, const void* Apost, long lda, void* dAp, long ldc, float* dApx, long ldx, int XW,
-                 float* dBp, int ntok, int G, int Cg, int nmain, int KP, int KPp, float* slabs, size_t slab_cap, hipStream_t st) {
-  if (Cg != 384 || nmain != 128 || KPp != 144 || KP <= 128 || KP > 144 || KP % 4 || ((uintptr_t)dBp % 16) || XW < 16 || ntok % BM || ldo % 8 || lda % 8 || !slabs ||
-      ((uintptr_t)dOut % 16) || ((uintptr_t)Apost % 16) || ((uintptr_t)dAp % 8) || ((uintptr_t)dApx % 16) || ldx % 4 || (G * XW) % 4)
+// gb: dBpost = dOut^T Apost (both MN-major, fp32 result); ga: dApost = dOut Bpost in its split-output form (gemm.h: Cx / nsplit -- the
+// bottleneck columns in bf16, the scalar columns in fp32); slab_cap: floats in gb.slabs.  Both descriptors as section 1 of the backward
+// builds them for the two kernels this one replaces.  0 = launched, 1 = not served (the caller runs the two kernels), < 0 error
+int launch_dpost_pair(const GemmArgs& gb, const GemmArgs& ga, size_t slab_cap, hipStream_t st) {
+  const int ntok = ga.M, G = ga.nb2, KP = gb.N, KPp = (int)gb.sCi, XW = (int)ga.sCx2;
+  float* const slabs = gb.slabs;
+  // two plain products in one piece each, over one dOut: ga's rows (the tokens) are gb's contraction, ga's contraction (the group's channels) gb's rows
+  auto plain = [](const GemmArgs& a) {
+    return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb1 == 1 && a.nb3 == 1 && a.sCj == 1 &&
+           !a.row_scale && !a.D && !a.A2 && !a.A3s && !a.A4s && !a.st_rows && !a.st_cols && !a.B3 && !a.C3;
+  };
+  if (!plain(gb) || !plain(ga) || gb.A != ga.A || gb.lda != ga.lda || gb.sA2 != ga.sA2 || gb.K != ga.M || gb.M != ga.K || gb.N != ga.N || gb.nb2 != ga.nb2 || G < 1 ||
+      gb.a_layout != MN_MAJOR || gb.b_layout != MN_MAJOR || gb.out_dtype != GEMM_F32 || gb.Cx || ga.a_layout != K_MAJOR || ga.b_layout != MN_MAJOR ||
+      ga.out_dtype != GEMM_BF16 || !ga.Cx)
+    return 1;
+  // the tuned shape: 384 channels per group, 128 bottleneck columns + <= 16 scalar ones in rows of 144; the groups side by side in dOut, Apost, dApost
+  // and the scalar columns; Bpost and dBpost one (384, 144) block per group
+  if (ga.K != 384 || ga.sA2 != 384 || ga.nsplit != 128 || ga.sC2 != 128 || KPp != 144 || gb.sB2 != 144 || gb.sC2 != 384 * 144 ||
+      KP <= 128 || KP > 144 || KP % 4 || ((uintptr_t)gb.C % 16) || XW < 16 || ntok % BM || ga.lda % 8 || gb.ldb % 8 || !slabs ||
+      ((uintptr_t)ga.A % 16) || ((uintptr_t)gb.B % 16) || ((uintptr_t)ga.C % 8) || ((uintptr_t)ga.Cx % 16) || ga.ldcx % 4 || (G * XW) % 4)
     return 1;
   // small sites: the two kernels (the 128-slab reduction alone costs 11 us; measured at 20 480 tokens: 44 us against 37); avmoe_test_hooks bit 2: test hook
   if (ntok < 32768 && !(ntok >= 4096 && (test_hook_mask() & HOOK_DPAIR_FORCE))) return 1;
@@ -242,8 +256,8 @@ int k_dpost_pair(const void* dOut, long ldo, const void* Bpost, long ldb, long s
   gx = std::min<long>(std::min(gx, ntiles), (long)(slab_cap / per));
   if (gx < 1) return 1;
   DPairArgs p;
-  p.dOut = (const char*)dOut; p.ldo = ldo; p.Bpost = (const char*)Bpost; p.ldb = ldb; p.sBg = sBg; p.Apost = (const char*)Apost; p.lda = lda;
-  p.dAp = (char*)dAp; p.ldc = ldc; p.dApx = dApx; p.ldx = ldx; p.XW = XW; p.slabs = slabs; p.ntok = ntok; p.KP = KP;
+  p.dOut = (const char*)ga.A; p.ldo = ga.lda; p.Bpost = (const char*)ga.B; p.ldb = ga.ldb; p.sBg = ga.sB2; p.Apost = (const char*)gb.B; p.lda = gb.ldb;
+  p.dAp = (char*)ga.C; p.ldc = ga.sCi; p.dApx = ga.Cx; p.ldx = ga.ldcx; p.XW = XW; p.slabs = slabs; p.ntok = ntok; p.KP = KP;
   p.NX = (KP % 4 == 0 ? KP : KPp) - 128; p.ntiles = ntiles;
   static LdsAttrOnce attr;
   AVMOE_TRY(attr.ensure((const void*)kk_dpair, DPAIR_LDS, "dpost_pair"));
@@ -255,7 +269,7 @@ int k_dpost_pair(const void* dOut, long ldo, const void* Bpost, long ldb, long s
   }
   {
     ProfScope ps("k_dpair_reduce", (long)per, (double)per * 4.0 * (gx + 1), 0.0, st);
-    hipLaunchKernelGGL(kk_dpair_reduce, dim3((unsigned)((per / 4 + 63) / 64)), dim3(256), 0, st, slabs, gx, G, KP, KPp, dBp);
+    hipLaunchKernelGGL(kk_dpair_reduce, dim3((unsigned)((per / 4 + 63) / 64)), dim3(256), 0, st, slabs, gx, G, KP, KPp, (float*)gb.C);
     AVMOE_CHECK_LAUNCH("dpair_reduce");
   }
   return OK;

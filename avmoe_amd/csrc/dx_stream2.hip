@@ -10,7 +10,6 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
-#include "kernels.h"
 #include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
@@ -169,18 +168,37 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream2(const DX2Args p) {
 
 }  // namespace
 
-// 0 = launched, 1 = shape not served (the caller runs the twelve-wave streaming GEMM), < 0 error
-int k_dx_stream2(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int K2, const float* rs, const void* Wt, long ldw, long sWg,
-                 const void* Text, long ldt, long sT1, void* dX, long ldc, int S, int N, int G, int Cg, int K1, hipStream_t st) {
-  if (Cg != 384 || K1 != 128 || K2 < 1 || K2 > 72 || ldl < 72 || N < BM || S < 1 || ldx % 8 || ldz % 8 || ldl % 8 || ldc % 4 || !rs ||
-      ((uintptr_t)X % 16) || ((uintptr_t)dZx % 16) || ((uintptr_t)dL2 % 16) || ((uintptr_t)dX % 8) || ((uintptr_t)rs % 4) || (long)S * N < 2048)
-    return 1;
+// Everything the kernel takes for granted of the product's descriptor (moe_backward.cpp::fill_dx_args builds it); anything else is not served.
+static bool dx2_serves(const GemmArgs& a) {
+  const long M = a.M;
+  // dX = dZx Wt in bf16, overwritten, in one piece, nothing else asked of the pass
+  if (a.dtype != GEMM_BF16 || a.out_dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || a.alpha != 1.f || a.accumulate ||
+      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.A3s || a.A4s || a.Cx || a.st_rows || a.st_cols || a.B3 || a.C3)
+    return false;
+  // the tuned shape; frames contiguous (the kernel walks tokens, not frames), groups side by side, one Wt for every frame
+  if (a.N != 384 || a.K != 128 || a.M < BM || a.nb1 < 1 || a.nb2 < 1 || (long)a.nb1 * M < 2048 || a.sA1 != M * a.lda || a.sA2 != a.K || a.sB1 != 0 ||
+      a.sCj != 1 || a.sC1 != M * a.sCi || a.sC2 != a.N)
+    return false;
+  // + rs X (X laid out as dX is) + [dL2 | dsx | 1] T[s] (one dL2 for all groups, T[s] per frame)
+  if (!a.row_scale || !a.D || a.sRS1 != M || a.sRS2 != 0 || a.sD1 != M * a.sDi || a.sD2 != a.N ||
+      !a.A2 || !a.B2 || a.K2 < 1 || a.K2 > 72 || a.lda2 < 72 || a.s2A1 != M * a.lda2 || a.s2A2 != 0 || a.s2B2 != a.N)
+    return false;
+  // 16-byte direct loads, 8-byte stores
+  return !(a.sDi % 8 || a.lda % 8 || a.lda2 % 8 || a.sCi % 4 || ((uintptr_t)a.D % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.A2 % 16) ||
+           ((uintptr_t)a.C % 8) || ((uintptr_t)a.row_scale % 4));
+}
+
+// 0 = launched, 1 = not served (the caller runs the twelve-wave streaming GEMM), < 0 error
+int launch_dx_stream2(const GemmArgs& a, hipStream_t st) {
+  if (!dx2_serves(a)) return 1;
   const int cus = cu_count();                             // (cached per device: common.cpp)
   if (cus <= 0) { set_last_error("dx_stream2: device query"); return ERR_LAUNCH; }
+  const int S = a.nb1, N = a.M, G = a.nb2, K2 = a.K2;
+  const long ldl = a.lda2;
   DX2Args p;
-  p.X = (const char*)X; p.ldx = ldx; p.dZx = (const char*)dZx; p.ldz = ldz; p.dL2 = (const char*)dL2; p.ldl = ldl; p.rs = rs;
-  p.Wt = (const unsigned short*)Wt; p.ldw = ldw; p.sWg = sWg; p.Text = (const unsigned short*)Text; p.ldt = ldt; p.sT1 = sT1;
-  p.dX = (char*)dX; p.ldc = ldc; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2;
+  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)a.A2; p.ldl = ldl; p.rs = a.row_scale;
+  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)a.B2; p.ldt = a.ldb2; p.sT1 = a.s2B1;
+  p.dX = (char*)a.C; p.ldc = a.sCi; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2;
   const int gx = std::min(std::max(1, cus / G), p.ntiles);
   static LdsAttrOnce attr;
   AVMOE_TRY(attr.ensure((const void*)kk_dx_stream2, DX2_LDS, "dx_stream2"));

@@ -17,7 +17,6 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
-#include "kernels.h"
 #include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
@@ -330,24 +329,48 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
 
 }  // namespace
 
-// 0 = launched, 1 = shape not served (the caller runs the dX product and site B's dY product separately), < 0 error
-int k_dx_stream3(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int K2, const float* rs, const void* Wt, long ldw, long sWg,
-                 const void* Text, long ldt, long sT1, const void* Bm, long ldb, long sB1, int KB, const void* dRT, long ldr, const void* dV, long ldv, long sV1,
-                 const void* Q, long ldq, int KQ, void* dX, long ldc, void* dump, int S, int N, int G, int Cg, int K1, hipStream_t st) {
-  if (Cg != 384 || K1 != 128 || K2 < 1 || K2 > 72 || ldl < 72 || KB < 1 || KB > 96 || KQ < 1 || KQ > 64 || ldr < 8 || ldb < N || N < 16 || S < 1 ||      // (N < 16: a ragged tile of a non-final frame would read 32 - 2 N rows past its successor)
-     
-      ldx % 8 || ldz % 8 || ldl % 8 || ldr % 8 || ldb % 8 || sB1 % 8 || ldc % 4 || !rs || !dump ||
-      ((uintptr_t)X % 16) || ((uintptr_t)dZx % 16) || ((uintptr_t)dL2 % 16) || ((uintptr_t)dRT % 16) || ((uintptr_t)Bm % 16) || ((uintptr_t)dX % 8) ||
-      ((uintptr_t)rs % 4) || ((uintptr_t)dump % 16) || (long)S * N < 2048)
+// Everything the kernel takes for granted of the product's descriptor -- four K segments as moe_backward_dx_dy fills them -- except what is
+// a matter of the pointers themselves (launch_dx_stream3): the answer of moe_backward_dx_dy's query, which has no buffers yet.
+bool dx_stream3_serves(const GemmArgs& a) {
+  const long M = a.M;
+  // site A's dX = dZx Wt in bf16, overwritten, in one piece, nothing else asked of the pass
+  if (a.dtype != GEMM_BF16 || a.out_dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || a.alpha != 1.f || a.accumulate ||
+      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.Cx || a.st_rows || a.st_cols || a.N3 != 0)
+    return false;
+  // the tuned shape; frames contiguous (the kernel walks tokens, not frames), groups side by side, one Wt for every frame
+  // (M < 16: a ragged tile of a non-final frame would read 32 - 2 M rows past its successor)
+  if (a.N != 384 || a.K != 128 || a.M < 16 || a.nb1 < 1 || a.nb2 < 1 || (long)a.nb1 * M < 2048 || a.sA1 != M * a.lda || a.sA2 != a.K || a.sB1 != 0 ||
+      a.sCj != 1 || a.sC1 != M * a.sCi || a.sC2 != a.N)
+    return false;
+  // + rs X (X laid out as dX is) + [dL2 | dsx | 1] T[s] (one dL2 for all groups, T[s] per frame)
+  if (a.sRS1 != M || a.sRS2 != 0 || a.sD1 != M * a.sDi || a.sD2 != a.N ||
+      a.K2 < 1 || a.K2 > 72 || a.lda2 < 72 || a.s2A1 != M * a.lda2 || a.s2A2 != 0 || a.s2B2 != a.N)
+    return false;
+  // site B's dY: + [Bm ; wbar][s]^T dV[s] (per frame, the frame's tokens along a row) + dR^T Q (tokens contiguous, one Q)
+  if (a.K3s < 1 || a.K3s > 96 || a.lda3s < M || a.s3sB2 != a.N ||
+      a.K4s < 1 || a.K4s > 64 || a.lda4s < 8 || a.s4sA1 != M * a.lda4s || a.s4sB1 != 0 || a.s4sB2 != a.N)
+    return false;
+  // 16-byte direct loads, 8-byte stores
+  return !(a.sDi % 8 || a.lda % 8 || a.lda2 % 8 || a.lda4s % 8 || a.lda3s % 8 || a.s3sA1 % 8 || a.sCi % 4);
+}
+
+// 0 = launched, 1 = not served (the caller runs the dX product and site B's dY product separately), < 0 error.  GemmArgs::slabs: the dump word.
+int launch_dx_stream3(const GemmArgs& a, hipStream_t st) {
+  if (!dx_stream3_serves(a)) return 1;
+  if (!a.A || !a.B || !a.D || !a.row_scale || !a.A2 || !a.B2 || !a.A3s || !a.B3s || !a.A4s || !a.B4s || !a.C || !a.slabs ||
+      ((uintptr_t)a.D % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.A2 % 16) || ((uintptr_t)a.A4s % 16) || ((uintptr_t)a.A3s % 16) || ((uintptr_t)a.C % 8) ||
+      ((uintptr_t)a.row_scale % 4) || ((uintptr_t)a.slabs % 16))
     return 1;
   const int cus = cu_count();
   if (cus <= 0) { set_last_error("dx_stream3: device query"); return ERR_LAUNCH; }
+  const int S = a.nb1, N = a.M, G = a.nb2, K2 = a.K2, KB = a.K3s, KQ = a.K4s;
+  const long ldl = a.lda2, ldr = a.lda4s;
   DX3Args p;
-  p.X = (const char*)X; p.ldx = ldx; p.dZx = (const char*)dZx; p.ldz = ldz; p.dL2 = (const char*)dL2; p.ldl = ldl; p.rs = rs;
-  p.Wt = (const unsigned short*)Wt; p.ldw = ldw; p.sWg = sWg; p.Text = (const unsigned short*)Text; p.ldt = ldt; p.sT1 = sT1;
-  p.Bm = (const char*)Bm; p.ldb = ldb; p.sB1 = sB1; p.dRT = (const char*)dRT; p.ldr = ldr; p.dV = (const unsigned short*)dV; p.ldv = ldv; p.sV1 = sV1;
-  p.Q = (const unsigned short*)Q; p.ldq = ldq;
-  p.dX = (char*)dX; p.ldc = ldc; p.dump = (char*)dump; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2; p.KB = KB; p.KQ = KQ;
+  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)a.A2; p.ldl = ldl; p.rs = a.row_scale;
+  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)a.B2; p.ldt = a.ldb2; p.sT1 = a.s2B1;
+  p.Bm = (const char*)a.A3s; p.ldb = a.lda3s; p.sB1 = a.s3sA1; p.dRT = (const char*)a.A4s; p.ldr = ldr;
+  p.dV = (const unsigned short*)a.B3s; p.ldv = a.ldb3s; p.sV1 = a.s3sB1; p.Q = (const unsigned short*)a.B4s; p.ldq = a.ldb4s;
+  p.dX = (char*)a.C; p.ldc = a.sCi; p.dump = (char*)a.slabs; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2; p.KB = KB; p.KQ = KQ;
   p.ncr = (int)std::min<long>(8, ldr / 8);
   const int gx = std::min(std::max(1, cus / G), p.ntiles);
   static LdsAttrOnce attr;

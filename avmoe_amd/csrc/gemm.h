@@ -59,7 +59,8 @@ struct GemmArgs {
   // Non-finite operands: an Inf splits into (Inf, NaN, NaN) -- the residual planes are Inf - Inf -- so a product that exact fp32 arithmetic
   // would return as Inf comes out NaN; finite inputs only (as everywhere on this path: workspaces are NaN-poisoned in the tests).
   // 2 = TWO planes (split once at the LDS store), the three plane products of order <= 1: 2^-16 relative per product, half the matrix-pipe work --
-  // available through avmoe_gemm (fp32_planes = 2); the site calls do not use it (moe_run.h: AVMOE_BWD_PLANES has the measurement and the reason).
+  // available through avmoe_gemm (fp32_planes = 2) and used by the site backward for the products nothing downstream forms a cancelling sum
+  // from (moe_run.h: AVMOE_LEAF2 = 26 -- dWt, the hop-1 weight gradients, the token gradients; AVMOE_BWD_PLANES has why not for all of them).
   int split3 = 0;
   int tile = 0;                         // 0 = auto, 64 or 128 = force block tile
   // optional second K segment, accumulated into the same tile before the epilogue:
@@ -143,6 +144,23 @@ struct TokPairArgs {
   float* slabs = nullptr; size_t slab_cap = 0;          // floats
 };
 int launch_gemm_tokpair(const TokPairArgs& args, hipStream_t stream);
+
+// Streaming kernels tuned for ONE product each of the bf16 cfg-2 site (384 channels per group, 128 bottleneck columns, 768-channel Y).  Like
+// launch_gemm_stream they take the engine's descriptor of the product, check everything they assume of it and return 0 = launched,
+// 1 = not served (nothing was launched: the caller goes on to the next form, launch_gemm last), < 0 error.  launch_gemm does not try them.
+int launch_dx_stream2(const GemmArgs& args, hipStream_t stream);     // dX[s] = dZx[s] Wt + dL2x[s] T[s] + rs X[s]: two K segments + row-scale term (dx_stream2.hip)
+// ... with the other site's dY as segments three and four (A3s .. B4s), written once (dx_stream3.hip); slabs: >= 256 bytes the kernel may scribble on
+bool dx_stream3_serves(const GemmArgs& args);                        // the same answer from shape and strides alone (no buffers yet)
+int launch_dx_stream3(const GemmArgs& args, hipStream_t stream);
+// the hop-1 chain's products against Y (hop1_stream.hip): C[s] = A[(s)] Y[s]^T (K-major A and Y, nb1 frames; slabs: 16 bytes the kernel may
+// scribble on), C[s] = A[s] Y[s] (K-major A, MN-major Y, nb1 frames), C = A^T Y over all tokens (MN-major A and Y, one batch; slabs: slab_cap floats)
+int launch_hop1_yk(const GemmArgs& args, hipStream_t stream);
+int launch_hop1_yt_frames(const GemmArgs& args, hipStream_t stream);
+int launch_hop1_yt_sum(const GemmArgs& args, size_t slab_cap, hipStream_t stream);
+int launch_tok_pair2(const TokPairArgs& args, hipStream_t stream);   // launch_gemm_tokpair's two contractions with every accumulator in registers (tok_pair2.hip)
+// dBpost = dOut^T Apost (`dbpost`) and dApost = dOut Bpost in its split-output form (`dapost`: Cx / nsplit) from one pass over dOut
+// (dpost_pair.hip); slab_cap: floats in dbpost.slabs
+int launch_dpost_pair(const GemmArgs& dbpost, const GemmArgs& dapost, size_t slab_cap, hipStream_t stream);
 // Whether the streaming kernel serves a per-sample bf16 product  (M rows per sample, nb1 samples) x (K per group, lda) -> N columns per group
 // WITH the statistics of A (GemmArgs::st_rows / st_cols): what a plan asks before it drops the separate statistics pass.
 bool gemm_stream_stats_ok(int M, int nb1, int N, int K, long lda, long ldc);

@@ -14,7 +14,6 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
-#include "kernels.h"
 #include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
@@ -377,17 +376,28 @@ __global__ void __launch_bounds__(256) kk_hop1_sum(const float* __restrict__ sla
 // per-frame yt 32.9 against ~18).  avmoe_test_hooks bit 4 (test hook): small sites as well.
 bool hop1s_small(long ntok) { return ntok < 32768 && !(test_hook_mask() & HOOK_HOP1S_FORCE); }
 
+// a plain product -- alpha 1, overwritten, in one piece, one batch level, bf16 operands, row-major result -- is all three kernels do
+bool hop1_plain(const GemmArgs& a) {
+  return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb2 == 1 && a.nb3 == 1 && a.sCj == 1 &&
+         !a.row_scale && !a.D && !a.A2 && !a.A3s && !a.A4s && !a.Cx && !a.st_rows && !a.st_cols && !a.B3 && !a.C3;
+}
+
 }  // namespace
 
-// 0 = launched, 1 = shape not served (the caller runs the tiled engine), < 0 error
-int k_hop1_yk(const void* Y, long ldy, int S, int M, int Cy, const void* A, long lda, long sA1, int rows, void* C, long ldc, long sC1, int c_bf16, void* dump, hipStream_t st) {
-  if (Cy != 768 || rows < 1 || rows > 80 || M < 4 || M % 4 || S < 1 || ldy % 8 || lda % 8 || sA1 % 8 || ldc % 4 || sC1 % 4 || !dump ||
-      ((uintptr_t)Y % 16) || ((uintptr_t)A % 16) || ((uintptr_t)C % 16) || ((uintptr_t)dump % 16) || hop1s_small((long)S * M))
+// C[s] = A[(s)] Y[s]^T : A K-major (sA1 = 0: shared by the frames), B = Y K-major with contiguous frames, nb1 = frames; GemmArgs::slabs: the dump word.
+// 0 = launched, 1 = not served (the caller runs the tiled engine), < 0 error
+int launch_hop1_yk(const GemmArgs& a, hipStream_t st) {
+  const int S = a.nb1, M = a.N, Cy = a.K, rows = a.M, c_bf16 = a.out_dtype == GEMM_BF16;
+  const long sA1 = a.sA1;
+  if (!hop1_plain(a) || a.a_layout != K_MAJOR || a.b_layout != K_MAJOR || a.sB1 != (long)M * a.ldb ||
+      Cy != 768 || rows < 1 || rows > 80 || M < 4 || M % 4 || S < 1 || a.ldb % 8 || a.lda % 8 || sA1 % 8 || a.sCi % 4 || a.sC1 % 4 || !a.slabs ||
+      ((uintptr_t)a.B % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.C % 16) || ((uintptr_t)a.slabs % 16) || hop1s_small((long)S * M))
     return 1;
   const int cus = cu_count();
   if (cus <= 0) { set_last_error("hop1_yk: device query"); return ERR_LAUNCH; }
   YKArgs p;
-  p.Y = (const char*)Y; p.ldy = ldy; p.A = (const unsigned short*)A; p.lda = lda; p.sA1 = sA1; p.C = (char*)C; p.ldc = ldc; p.sC1 = sC1; p.c_bf16 = c_bf16; p.dump = (char*)dump;
+  p.Y = (const char*)a.B; p.ldy = a.ldb; p.A = (const unsigned short*)a.A; p.lda = a.lda; p.sA1 = sA1; p.C = (char*)a.C; p.ldc = a.sCi; p.sC1 = a.sC1; p.c_bf16 = c_bf16;
+  p.dump = (char*)a.slabs;
   p.M = M; p.tpf = (M + YK_BT - 1) / YK_BT; p.ntiles = S * p.tpf; p.rows = rows;
   const int gx = std::min(cus, p.ntiles);
   constexpr int KS = 24, LDS = YK_NBUF * (YK_BT * 4 * KS / 64) * 1024;
@@ -418,10 +428,13 @@ int launch_yt(const YTArgs& p, int gx, int gy, hipStream_t st) {
 }
 }  // namespace
 
-// per frame: C[s] (rows x Cy) = A[s] (rows x M, K-major rows of lda elements) Y[s]
-int k_hop1_yt_frames(const void* Y, long ldy, int S, int M, int Cy, const void* A, long lda, long sA1, int rows, void* C, long ldc, long sC1, int c_bf16, hipStream_t st) {
-  if (Cy % 256 || rows < 17 || rows > 80 || M < 1 || S < 1 || ldy % 8 || lda % 8 || sA1 % 8 || lda < M ||
-      ((uintptr_t)Y % 16) || ((uintptr_t)A % 16) || ((uintptr_t)C % 4) || hop1s_small((long)S * M))
+// C[s] = A[s] Y[s] per frame: A K-major (rows of the frame's tokens), B = Y MN-major with contiguous frames, nb1 = frames.
+// 0 = launched, 1 = not served (the caller runs the tiled engine), < 0 error
+int launch_hop1_yt_frames(const GemmArgs& a, hipStream_t st) {
+  const int S = a.nb1, M = a.K, Cy = a.N, rows = a.M, c_bf16 = a.out_dtype == GEMM_BF16;
+  if (!hop1_plain(a) || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || a.sB1 != (long)M * a.ldb ||
+      Cy % 256 || rows < 17 || rows > 80 || M < 1 || S < 1 || a.ldb % 8 || a.lda % 8 || a.sA1 % 8 || a.lda < M ||
+      ((uintptr_t)a.B % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.C % 4) || hop1s_small((long)S * M))
     return 1;
   const int cus = cu_count();
   if (cus <= 0) { set_last_error("hop1_yt: device query"); return ERR_LAUNCH; }
@@ -434,7 +447,7 @@ int k_hop1_yt_frames(const void* Y, long ldy, int S, int M, int Cy, const void* 
   const int cb = eff(384) >= eff(256) ? 384 : 256;
   const int gy = Cy / cb, gx = std::max(1, std::min(S, cus / gy));
   YTArgs p{};
-  p.Y = (const char*)Y; p.ldy = ldy; p.A = (const char*)A; p.lda = lda; p.sA1 = sA1; p.rows = rows; p.C = (char*)C; p.ldc = ldc; p.sC1 = sC1; p.c_bf16 = c_bf16;
+  p.Y = (const char*)a.B; p.ldy = a.ldb; p.A = (const char*)a.A; p.lda = a.lda; p.sA1 = a.sA1; p.rows = rows; p.C = (char*)a.C; p.ldc = a.sCi; p.sC1 = a.sC1; p.c_bf16 = c_bf16;
   p.M = M; p.tpf = (M + YT_BM - 1) / YT_BM; p.S = S;
   const double bytes = (double)S * M * Cy * 2 + (double)S * rows * M * 2 * gy + (double)S * rows * Cy * (c_bf16 ? 2 : 4);
   ProfScope ps("k_hop1_yt_frames", (long)S * M, bytes, 2.0 * S * M * Cy * rows, st);
@@ -442,17 +455,22 @@ int k_hop1_yt_frames(const void* Y, long ldy, int S, int M, int Cy, const void* 
   return cb == 384 ? launch_yt<3, 5, true>(p, gx, gy, st) : launch_yt<2, 5, true>(p, gx, gy, st);
 }
 
-// over all tokens: C (rows x Cy) = A^T Y with A = [token][lda] (columns 0 .. rows - 1), C bf16 or fp32 ; slabs: fp32 workspace
-int k_hop1_yt_sum(const void* Y, long ldy, long ntok, int Cy, const void* A, long lda, int rows, void* C, long ldc, int c_bf16, float* slabs, size_t slab_cap, hipStream_t st) {
-  if (Cy % 384 || rows < 17 || rows > 64 || lda < 64 || ntok < YT_BM || ldy % 8 || lda % 8 || ldc % 4 || !slabs ||
-      ((uintptr_t)Y % 16) || ((uintptr_t)A % 16) || ((uintptr_t)C % 16) || ((uintptr_t)slabs % 16) || hop1s_small(ntok))
+// C = A^T Y over all tokens: A MN-major ([token][lda], columns 0 .. M - 1), B = Y MN-major, one batch; GemmArgs::slabs: fp32 workspace of slab_cap floats.
+// 0 = launched, 1 = not served (the caller runs the tiled engine), < 0 error
+int launch_hop1_yt_sum(const GemmArgs& a, size_t slab_cap, hipStream_t st) {
+  const long ntok = a.K, lda = a.lda, ldc = a.sCi;
+  const int Cy = a.N, rows = a.M, c_bf16 = a.out_dtype == GEMM_BF16;
+  float* slabs = a.slabs;
+  if (!hop1_plain(a) || a.a_layout != MN_MAJOR || a.b_layout != MN_MAJOR || a.nb1 != 1 ||
+      Cy % 384 || rows < 17 || rows > 64 || lda < 64 || ntok < YT_BM || a.ldb % 8 || lda % 8 || ldc % 4 || !slabs ||
+      ((uintptr_t)a.B % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.C % 16) || ((uintptr_t)slabs % 16) || hop1s_small(ntok))
     return 1;
   const int cus = cu_count();
   if (cus <= 0) { set_last_error("hop1_yt: device query"); return ERR_LAUNCH; }
   const int gy = Cy / 384, ntiles = (int)((ntok + YT_BM - 1) / YT_BM), gx = std::max(1, std::min(ntiles, cus / gy));
   if ((size_t)gx * 64 * Cy > slab_cap) return 1;
   YTArgs p{};
-  p.Y = (const char*)Y; p.ldy = ldy; p.A = (const char*)A; p.lda = lda; p.rows = rows; p.slab = slabs; p.ldslab = Cy; p.ntok = ntok; p.ntiles = ntiles;
+  p.Y = (const char*)a.B; p.ldy = a.ldb; p.A = (const char*)a.A; p.lda = lda; p.rows = rows; p.slab = slabs; p.ldslab = Cy; p.ntok = ntok; p.ntiles = ntiles;
   {
     const double bytes = (double)ntok * Cy * 2 + (double)ntok * 64 * 2 * gy + (double)gx * 64 * Cy * 4;
     ProfScope ps("k_hop1_yt_sum", ntok, bytes, 2.0 * ntok * Cy * rows, st);
@@ -461,7 +479,7 @@ int k_hop1_yt_sum(const void* Y, long ldy, long ntok, int Cy, const void* A, lon
   {
     const long nvec = (long)rows * Cy / 4;
     ProfScope ps("k_hop1_sum", (long)rows * Cy, (double)gx * rows * Cy * 4.0, 0.0, st);
-    hipLaunchKernelGGL(kk_hop1_sum, dim3((unsigned)((nvec + 63) / 64)), dim3(256), 0, st, slabs, gx, (long)64 * Cy, rows, Cy, (long)Cy, (char*)C, ldc, c_bf16);
+    hipLaunchKernelGGL(kk_hop1_sum, dim3((unsigned)((nvec + 63) / 64)), dim3(256), 0, st, slabs, gx, (long)64 * Cy, rows, Cy, (long)Cy, (char*)a.C, ldc, c_bf16);
     AVMOE_CHECK_LAUNCH("hop1_sum");
   }
   return OK;

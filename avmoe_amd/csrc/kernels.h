@@ -83,23 +83,6 @@ int k_nxn_att_bwd(const void* X, const void* dxr, int frames, int N, int C, int 
 int k_nxn_y(const void* X, const void* dxr, int frames, int N, int C, int Np, const float* lse, float* rowdot, void* dX, hipStream_t st);   // rowdot = X . (att dxr) ; dX += att dxr
 int k_nxn_xr(const void* X, int frames, int N, int C, int Np, const float* lse, void* xr, hipStream_t st);      // forward: xr = att^T X (lse from k_nxn_att with att == nullptr)
 int k_nxn_dx(int key, const void* X, const void* dxr, int frames, int N, int C, int Np, const float* lse, const float* rowdot, void* dX, hipStream_t st);   // dX += dS X (key = 0) / dS^T X (key = 1), dS in the accumulators
-// dApost = dOut Bpost and dBpost = dOut^T Apost from one pass over dOut (dpost_pair.hip); 1 = shape not served
-int k_dpost_pair(const void* dOut, long ldo, const void* Bpost, long ldb, long sBg, const void* Apost, long lda, void* dAp, long ldc, float* dApx, long ldx, int XW,
-                 float* dBp, int ntok, int G, int Cg, int nmain, int KP, int KPp, float* slabs, size_t slab_cap, hipStream_t st);
-// dWt = dZx^T X and dT[s] = dL2[s]^T X[s] as one streaming pass (tok_pair2.hip); 1 = shape not served
-int k_tok_pair2(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int S, int N, int G, int Cg, int M1, int KL,
-                float* dWt, float* dT, float* slabs, size_t slab_cap, hipStream_t st);
-// dX = dZx Wt + dL2x T[s] + rs X in the eight-wave direct-load form (dx_stream2.hip); 1 = shape not served
-int k_dx_stream2(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int K2, const float* rs, const void* Wt, long ldw, long sWg,
-                 const void* Text, long ldt, long sT1, void* dX, long ldc, int S, int N, int G, int Cg, int K1, hipStream_t st);
-// the hop-1 chain's per-frame products against Y as streaming kernels (hop1_stream.hip; bf16, tuned widths); 1 = shape not served
-int k_hop1_yk(const void* Y, long ldy, int S, int M, int Cy, const void* A, long lda, long sA1, int rows, void* C, long ldc, long sC1, int c_bf16, void* dump, hipStream_t st);   // C[s] = A[(s)] Y[s]^T ; dump: 16 writable bytes
-int k_hop1_yt_frames(const void* Y, long ldy, int S, int M, int Cy, const void* A, long lda, long sA1, int rows, void* C, long ldc, long sC1, int c_bf16, hipStream_t st);   // C[s] = A[s] Y[s]
-int k_hop1_yt_sum(const void* Y, long ldy, long ntok, int Cy, const void* A, long lda, int rows, void* C, long ldc, int c_bf16, float* slabs, size_t slab_cap, hipStream_t st);   // C = A^T Y over all tokens
-// site A's dX product + site B's dY product into one tensor, written once (dx_stream3.hip); 1 = shape not served
-int k_dx_stream3(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int K2, const float* rs, const void* Wt, long ldw, long sWg,
-                 const void* Text, long ldt, long sT1, const void* Bm, long ldb, long sB1, int KB, const void* dRT, long ldr, const void* dV, long ldv, long sV1,
-                 const void* Q, long ldq, int KQ, void* dX, long ldc, void* dump, int S, int N, int G, int Cg, int K1, hipStream_t st);
 int k_nxn_rowdot(int bf16, const void* X, const float* y, long rows, int C, void* dX, float* rowdot, hipStream_t st);   // dX += y ; rowdot = sum_c X y
 // register-resident variants for bottleneck 64 / 2 groups / 32 latent tokens / 4 experts (tile_fast.hip)
 bool tile_fast_ok(const Dims& d);

@@ -15,6 +15,7 @@ namespace avmoe {
   } while (0)
 
 avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* sv);   // moe_forward.cpp
+static const char* at(const char* base, size_t off) { return base ? base + off : nullptr; }      // (the query of moe_backward_dx_dy has no buffers)
 
 // parts: bit mask of the sections to run, 0 = 7 = the whole backward:
 //   1  phases 1-4: the GEMMs against dOut and the bottleneck / weight space (touches neither dX nor dY)
@@ -27,12 +28,12 @@ avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* 
 // the operands of  dX[s] = dZx[s] Wt + [dL2 | dsx | 1][s] [T ; 1 ; dm1/N][s] + 2 dSxx X[s]  (phase 5; moe_backward_dx_dy adds the other site's dY to it)
 static void fill_dx_args(GemmArgs& g, const Plan& pl, const void* X, const char* sv, const char* sc, void* dX) {
   const Dims& d = pl.d;
-  g.A = sc + pl.o_Zw; g.B = sv + pl.o_Wt; g.C = dX;
+  g.A = at(sc, pl.o_Zw); g.B = at(sv, pl.o_Wt); g.C = dX;
   g.M = d.N; g.N = d.Cg; g.K = d.E * d.dgp; g.lda = d.DZ; g.b_layout = MN_MAJOR; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
   g.sA1 = (long)d.N * d.DZ; g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg;
   g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.sC2 = d.Cg; g.out_dtype = d.bf16 ? GEMM_BF16 : GEMM_F32;
-  g.row_scale = (const float*)(sc + pl.o_rs2x); g.sRS1 = d.N; g.D = X; g.sDi = d.C; g.sD1 = (long)d.N * d.C; g.sD2 = d.Cg;
-  g.A2 = sc + pl.o_dL2x; g.B2 = sv + pl.o_Text; g.K2 = d.KLT; g.lda2 = d.KLp; g.ldb2 = d.C;
+  g.row_scale = (const float*)at(sc, pl.o_rs2x); g.sRS1 = d.N; g.D = X; g.sDi = d.C; g.sD1 = (long)d.N * d.C; g.sD2 = d.Cg;
+  g.A2 = at(sc, pl.o_dL2x); g.B2 = at(sv, pl.o_Text); g.K2 = d.KLT; g.lda2 = d.KLp; g.ldb2 = d.C;
   g.s2A1 = (long)d.N * d.KLp; g.s2B1 = (long)d.KLT * d.C; g.s2B2 = d.Cg;
 }
 
@@ -79,41 +80,38 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   // a GEMM of the helper stream runs -- tile_gen.inc::gen_lds_request has the reason)
   const bool fork1 = side && (side_mask() & 2) && (d.gram64 || !d.ln_post) && !d.gen;
   int dap16 = 0;     // dApost stored as [E x 32 bottleneck columns in T | 3 E scalar columns in fp32 (dApx)]: the register-resident bf16 path
-  bool pair1 = false;                                      // both products from one pass over dOut (dpost_pair.hip: the tuned bf16 shape)
+  GemmArgs gb = base();                                    // dBpost = dOut^T Apost
+  gb.A = dOut; gb.B = sv + pl.o_Apost; gb.C = sc + pl.o_dBp;
+  gb.M = d.Cg; gb.N = d.KP; gb.K = d.NT; gb.a_layout = gb.b_layout = MN_MAJOR; gb.lda = d.C; gb.ldb = (long)d.g * d.KPp; gb.nb2 = d.g;
+  gb.sA2 = d.Cg; gb.sB2 = d.KPp; gb.sCi = d.KPp; gb.sC2 = (long)d.Cg * d.KPp;
+  leaf(gb, 1);
+  GemmArgs ga = base();                                    // dApost = dOut Bpost
+  ga.A = dOut; ga.B = sv + pl.o_Bpost; ga.C = sc + pl.o_dAp;
+  // N = KP, or the padded KPp when KP is not a multiple of 4 (2 or 3 experts): Bpost's padding columns are zero, the streaming
+  // kernel wants whole 4-column vectors, and nobody reads the padding of dAp
+  ga.M = d.NT; ga.N = (d.KP % 4 == 0) ? d.KP : d.KPp; ga.K = d.Cg; ga.lda = d.C; ga.b_layout = MN_MAJOR; ga.ldb = d.KPp; ga.nb2 = d.g;
+  ga.sA2 = d.Cg; ga.sB2 = (long)d.Cg * d.KPp; ga.sCi = (long)d.g * d.KPp; ga.sC2 = d.KPp;
+  // ... as bf16 main columns + fp32 scalar columns (sites that keep z in bf16): 640 instead of 1152 bytes per token, written and re-read
+  GemmArgs h = ga;
+  h.out_dtype = GEMM_BF16; h.Cx = (float*)(sc + pl.o_dApx); h.nsplit = d.E * d.dgp; h.ldcx = (long)d.g * d.XW; h.sCx2 = d.XW;
+  h.sCi = (long)d.g * h.nsplit; h.sC2 = h.nsplit;        // the T columns as rows of their own (E * dgp wide: whole 128-byte lines), not inside KPp-wide rows
+  int pair1 = 1;                                           // both products from one pass over dOut (dpost_pair.hip: the tuned bf16 shape); 1 = not served
   if (d.zsz == 2 && d.bf16 && !dev_env("AVMOE_NO_DPAIR")) {
-    const int rc = k_dpost_pair(dOut, d.C, sv + pl.o_Bpost, d.KPp, (long)d.Cg * d.KPp, sv + pl.o_Apost, (long)d.g * d.KPp, sc + pl.o_dAp, (long)d.g * d.E * d.dgp,
-                                (float*)(sc + pl.o_dApx), (long)d.g * d.XW, d.XW, (float*)(sc + pl.o_dBp), d.NT, d.g, d.Cg, d.E * d.dgp, d.KP, d.KPp,
-                                slabs, slab_cap, st);
-    if (rc < 0) return rc;
-    pair1 = rc == OK;
-    if (pair1) dap16 = 1;
+    pair1 = launch_dpost_pair(gb, h, slab_cap, st);
+    if (pair1 < 0) return pair1;
   }
-  if (!pair1) {
-    GemmArgs g = base();
-    g.A = dOut; g.B = sv + pl.o_Apost; g.C = sc + pl.o_dBp;
-    g.M = d.Cg; g.N = d.KP; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.C; g.ldb = (long)d.g * d.KPp; g.nb2 = d.g;
-    g.sA2 = d.Cg; g.sB2 = d.KPp; g.sCi = d.KPp; g.sC2 = (long)d.Cg * d.KPp;
-    leaf(g, 1);
+  if (pair1 == OK) {
+    dap16 = 1;
+  } else {
     if (fork1) AVMOE_TRY(fk1.fork());
-    AVMOE_TRY(run_on(g, true, fork1 ? side->s : st));
-  }
-  if (!pair1) {
-    GemmArgs g = base();
-    g.A = dOut; g.B = sv + pl.o_Bpost; g.C = sc + pl.o_dAp;
-    // N = KP, or the padded KPp when KP is not a multiple of 4 (2 or 3 experts): Bpost's padding columns are zero, the streaming
-    // kernel wants whole 4-column vectors, and nobody reads the padding of dAp
-    g.M = d.NT; g.N = (d.KP % 4 == 0) ? d.KP : d.KPp; g.K = d.Cg; g.lda = d.C; g.b_layout = MN_MAJOR; g.ldb = d.KPp; g.nb2 = d.g;
-    g.sA2 = d.Cg; g.sB2 = (long)d.Cg * d.KPp; g.sCi = (long)d.g * d.KPp; g.sC2 = d.KPp;
+    AVMOE_TRY(run_on(gb, true, fork1 ? side->s : st));
     static const bool dap_f32 = dev_env("AVMOE_DAP_F32") != nullptr;      // dev switch
-    if (d.zsz == 2 && !dap_f32) {          // bf16 main columns + fp32 scalar columns: 640 instead of 1152 bytes per token, written and re-read
-      GemmArgs h = g;
-      h.out_dtype = GEMM_BF16; h.Cx = (float*)(sc + pl.o_dApx); h.nsplit = d.E * d.dgp; h.ldcx = (long)d.g * d.XW; h.sCx2 = d.XW;
-      h.sCi = (long)d.g * h.nsplit; h.sC2 = h.nsplit;      // the T columns as rows of their own (E * dgp wide: whole 128-byte lines), not inside KPp-wide rows
+    if (d.zsz == 2 && !dap_f32) {
       const int r = launch_gemm_stream(h, st);
       if (r < 0) return r;
       dap16 = r == 0;
     }
-    if (!dap16) AVMOE_TRY(run(g, false));
+    if (!dap16) AVMOE_TRY(run(ga, false));
   }
   BWD_STOP(1);
   // ---- phase 2: bottleneck space (LayerNorm-post statistics), then weight space ------------------
@@ -131,7 +129,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     g.nb2 = d.g * d.E; g.sA2 = g.sB2 = d.dgp; g.sCi = d.dgp; g.sC2 = (long)d.dgp * d.dgp;
     AVMOE_TRY(run(g, true));
   }
-  if (fork1 && !pair1) AVMOE_TRY(fk1.join());
+  if (fork1 && pair1 != OK) AVMOE_TRY(fk1.join());
   BWD_STOP(3);
   AVMOE_TRY(k_post_prep_bwd(pl, sv, sc, prm, grads, st));
   BWD_STOP(4);
@@ -158,8 +156,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     if (fork2) AVMOE_TRY(fk2.fork());
     int dx2 = 1;                                           // the eight-wave direct-load form (dx_stream2.hip: tuned bf16 shape, dX overwritten); 1 = not served
     if (d.bf16 && !d.acc_dx && !dev_env("AVMOE_NO_DX2")) {
-      dx2 = k_dx_stream2(X, d.C, dZx, d.DZ, sc + pl.o_dL2x, d.KLp, d.KLT, (const float*)(sc + pl.o_rs2x), sv + pl.o_Wt, d.Cg, (long)d.E * d.dgp * d.Cg,
-                         sv + pl.o_Text, d.C, (long)d.KLT * d.C, dX, d.C, d.S, d.N, d.g, d.Cg, d.E * d.dgp, fork2 ? side->s : st);
+      dx2 = launch_dx_stream2(g, fork2 ? side->s : st);
       if (dx2 < 0) return dx2;
     }
     if (dx2 != OK) AVMOE_TRY(run_on(g, false, fork2 ? side->s : st));
@@ -259,19 +256,15 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     AVMOE_TRY(run(g, false));
   }
   bool pair_done = false;                                  // dWt = dZx^T X and dT[s] = dL2[s]^T X[s] in ONE pass over X (bf16 sites with latent tokens)
-  if (d.bf16 && d.El > 0 && !dev_env("AVMOE_NO_TOKPAIR2")) {      // ... as one streaming pass with every accumulator in registers (tok_pair2.hip: the tuned shape)
-    const int rc = k_tok_pair2(X, d.C, dZx, d.DZ, sc + pl.o_dL2x, d.KLp, d.S, d.N, d.g, d.Cg, d.E * d.dgp, d.KL, (float*)(sc + pl.o_dWt), (float*)(sc + pl.o_dT),
-                               slabs, slab_cap, st);
-    if (rc < 0) return rc;
-    pair_done = rc == OK;
-  }
-  if (d.bf16 && d.El > 0 && !pair_done) {
+  if (d.bf16 && d.El > 0) {
     TokPairArgs t;
     t.A1 = dZx; t.lda1 = d.DZ; t.M1 = d.E * d.dgp; t.sA1g = (long)d.E * d.dgp;
     t.A2 = sc + pl.o_dL2x; t.lda2 = d.KLp; t.M2 = d.KL;
     t.X = X; t.ldx = d.C; t.S = d.S; t.N = d.N; t.g = d.g; t.Cg = d.Cg;
     t.C1 = (float*)(sc + pl.o_dWt); t.C2 = (float*)(sc + pl.o_dT); t.slabs = slabs; t.slab_cap = slab_cap;
-    const int rc = launch_gemm_tokpair(t, st);
+    int rc = 1;                                            // as one streaming pass with every accumulator in registers (tok_pair2.hip: the tuned shape) ...
+    if (!dev_env("AVMOE_NO_TOKPAIR2")) rc = launch_tok_pair2(t, st);
+    if (rc == 1) rc = launch_gemm_tokpair(t, st);          // ... or in the tiled form
     if (rc < 0) return rc;
     pair_done = rc == OK;
   }
@@ -361,13 +354,12 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     AVMOE_TRY(run(g, true));
   }
   {                                                        // dBm[s] = dV[s] Y[s]^T
-    int rc = 1;                                            // (hop1_stream.hip: dV[s] stationary per frame; 1 = shape not served)
-    if (hop1s) rc = k_hop1_yk(Y, d.Cy, d.S, d.M, d.Cy, sc + pl.o_dV, d.Cy, (long)d.Kcyb * d.Cy, d.Kcyb, sc + pl.o_dBm, d.Mb, (long)d.Kcyb * d.Mb, 0, slabs, st);
-    if (rc < 0) return rc;
     GemmArgs g = base();
     g.A = sc + pl.o_dV; g.B = Y; g.C = sc + pl.o_dBm;
     g.M = d.Kcyb; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S;
     g.sA1 = (long)d.Kcyb * d.Cy; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Mb; g.sC1 = (long)d.Kcyb * d.Mb;
+    const int rc = hop1s ? launch_hop1_yk(g, st) : 1;      // (hop1_stream.hip: dV[s] stationary per frame; 1 = not served)
+    if (rc < 0) return rc;
     if (rc != OK) AVMOE_TRY(run(g, false));
   }
   AVMOE_TRY(k_prep_dBm(pl, sc, st));
@@ -408,12 +400,11 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     }
     AVMOE_TRY(k_dqrqb(pl, sc, prm.conv_b, st));
     {                                                      // dQ = sum_s dR[s] Y[s]
-      int rc = 1;                                          // (hop1_stream.hip: one pass over Y with every accumulator in registers + a slab sum)
-      if (hop1s) rc = k_hop1_yt_sum(Y, d.Cy, (long)d.S * d.M, d.Cy, sc + pl.o_dRT, d.Kcyp, d.Kcy, sc + pl.o_dQT, d.Cy, 1, slabs, slab_cap, st);
-      if (rc < 0) return rc;
       GemmArgs g = base();
       g.A = sc + pl.o_dRT; g.B = Y; g.C = sc + pl.o_dQT; g.out_dtype = dt;      // (straight in the operand dtype of its two consumers)
       g.M = d.Kcy; g.N = d.Cy; g.K = d.S * d.M; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Kcyp; g.ldb = d.Cy; g.sCi = d.Cy;
+      const int rc = hop1s ? launch_hop1_yt_sum(g, slab_cap, st) : 1;      // (hop1_stream.hip: one pass over Y with every accumulator in registers + a slab sum)
+      if (rc < 0) return rc;
       if (rc != OK) AVMOE_TRY(run(g, true));
     }
     }
@@ -499,25 +490,22 @@ int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, cons
   const Dims& a = pa.d;
   const Dims& b = pb.d;
   if (a.bf16 != b.bf16 || a.mha || a.nxn || a.Kcx > 0 || b.M != a.N || b.Cy != a.C || b.S != a.S || b.Kcx > 0) return 1;
-  if (!a.bf16 || a.mg || b.mg || a.Cg != 384 || a.E * a.dgp != 128 || a.KLT > 72 || a.KLp < 72 || b.Kcy < 1 || b.Kcy > 64 || b.Kcyb > 96 || (long)a.S * a.N < 2048) {
-    // Any other shape, round 6: the same sum on the tiled engine -- site A's dX product with site B's  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q
-    // as a third and a fourth K segment (gemm.h: A3s ..): the token gradient is written once instead of written by site A and read back + added by
-    // site B.  fp32 sites only (AVMOE_DXDY_GEN = 1; 3 = bf16 sites of the generalised shapes too: measured, moe_run.h).
-    if (!(AVMOE_DXDY_GEN & (a.bf16 ? 2 : 1))) return 1;
-    if (!launch) return OK;
-    GemmArgs g; g.dtype = a.bf16 ? GEMM_BF16 : GEMM_F32; g.split3 = (AVMOE_LEAF2 & 16) ? 2 : AVMOE_BWD_PLANES;
-    fill_dx_args(g, pa, X, sva, sca, dX);
-    g.A3s = svb + pb.o_BmX; g.B3s = scb + pb.o_dV; g.K3s = b.Kcyb; g.lda3s = b.Mb; g.ldb3s = b.Cy;
-    g.s3sA1 = (long)b.Kcyb * b.Mb; g.s3sB1 = (long)b.Kcyb * b.Cy; g.s3sB2 = a.Cg;
-    if (b.Kcy > 0) {
-      g.A4s = scb + pb.o_dRT; g.B4s = svb + pb.o_Qx; g.K4s = b.Kcy; g.lda4s = b.Kcyp; g.ldb4s = b.Cy; g.s4sA1 = (long)b.M * b.Kcyp; g.s4sB1 = 0; g.s4sB2 = a.Cg;
-    }
-    return launch_gemm(g, st);
+  // site A's dX product with site B's  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  as a third and a fourth K segment (gemm.h: A3s ..)
+  GemmArgs g; g.dtype = a.bf16 ? GEMM_BF16 : GEMM_F32; g.split3 = (AVMOE_LEAF2 & 16) ? 2 : AVMOE_BWD_PLANES;
+  g.slabs = (float*)at(sca, pa.o_slabs);                   // (the streaming form's dump word)
+  fill_dx_args(g, pa, X, sva, sca, dX);
+  g.A3s = at(svb, pb.o_BmX); g.B3s = at(scb, pb.o_dV); g.K3s = b.Kcyb; g.lda3s = b.Mb; g.ldb3s = b.Cy;
+  g.s3sA1 = (long)b.Kcyb * b.Mb; g.s3sB1 = (long)b.Kcyb * b.Cy; g.s3sB2 = a.Cg;
+  if (b.Kcy > 0) {
+    g.A4s = at(scb, pb.o_dRT); g.B4s = at(svb, pb.o_Qx); g.K4s = b.Kcy; g.lda4s = b.Kcyp; g.ldb4s = b.Cy; g.s4sA1 = (long)b.M * b.Kcyp; g.s4sB1 = 0; g.s4sB2 = a.Cg;
   }
+  // The streaming form (dx_stream3.hip: the tuned bf16 shape), or, round 6, the same sum on the tiled engine: the token gradient is written
+  // once instead of written by site A and read back + added by site B.  fp32 sites only (AVMOE_DXDY_GEN = 1; 3 = bf16 sites of the
+  // generalised shapes too: measured, moe_run.h).
+  const bool stream = !a.mg && !b.mg && dx_stream3_serves(g);
+  if (!stream && !(AVMOE_DXDY_GEN & (a.bf16 ? 2 : 1))) return 1;
   if (!launch) return OK;
-  return k_dx_stream3(X, a.C, sca + pa.o_Zw, a.DZ, sca + pa.o_dL2x, a.KLp, a.KLT, (const float*)(sca + pa.o_rs2x), sva + pa.o_Wt, a.Cg, (long)a.E * a.dgp * a.Cg,
-                      sva + pa.o_Text, a.C, (long)a.KLT * a.C, svb + pb.o_BmX, b.Mb, (long)b.Kcyb * b.Mb, b.Kcyb, scb + pb.o_dRT, b.Kcyp,
-                      scb + pb.o_dV, b.Cy, (long)b.Kcyb * b.Cy, svb + pb.o_Qx, b.Cy, b.Kcy, dX, a.C, sca + pa.o_slabs, a.S, a.N, a.g, a.Cg, a.E * a.dgp, st);
+  return stream ? launch_dx_stream3(g, st) : launch_gemm(g, st);
 }
 
 }  // namespace avmoe

@@ -92,13 +92,12 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   AVMOE_TRY(k_qrqb_fill(pl, sv, prm.fc_b, st));
   if (d.Kcy > 0) {
     {                                                      // R[s] = Q Y[s]^T
-      int rc = 1;                                          // (hop1_stream.hip: Q stationary, Y streamed in whole token rows; 1 = shape not served)
-      if (hop1s) rc = k_hop1_yk(Y, d.Cy, d.S, d.M, d.Cy, sv + pl.o_Qx, d.Cy, 0, d.Kcy, sv + pl.o_Rext, d.Mk, (long)d.Kcyb * d.Mk, 1, slabs, st);
-      if (rc < 0) return rc;
       GemmArgs g = base();
       g.A = sv + pl.o_Qx; g.B = Y; g.C = sv + pl.o_Rext;
       g.M = d.Kcy; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S; g.sB1 = (long)d.M * d.Cy;
       g.sCi = d.Mk; g.sC1 = (long)d.Kcyb * d.Mk; g.out_dtype = dt;
+      const int rc = hop1s ? launch_hop1_yk(g, st) : 1;    // (hop1_stream.hip: Q stationary, Y streamed in whole token rows; 1 = not served)
+      if (rc < 0) return rc;
       if (rc != OK) AVMOE_TRY(launch_gemm(g, st));
     }
     {                                                      // L1[s] = [R | qr | qb] [Wc | bc | 1]^T
@@ -119,13 +118,12 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     }
   }
   {                                                        // V[s] = [Bm ; wbar][s] Y[s]   (token contraction)
-    int rc = 1;
-    if (hop1s) rc = k_hop1_yt_frames(Y, d.Cy, d.S, d.M, d.Cy, sv + pl.o_BmX, d.Mb, (long)d.Kcyb * d.Mb, d.Kcyb, sv + pl.o_V, d.Cy, (long)d.Kcyb * d.Cy, 1, st);
-    if (rc < 0) return rc;
     GemmArgs g = base();
     g.A = sv + pl.o_BmX; g.B = Y; g.C = sv + pl.o_V;
     g.M = d.Kcyb; g.N = d.Cy; g.K = d.M; g.lda = d.Mb; g.b_layout = MN_MAJOR; g.ldb = d.Cy; g.nb1 = d.S;
     g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.Kcyb * d.Cy; g.out_dtype = dt;
+    const int rc = hop1s ? launch_hop1_yt_frames(g, st) : 1;      // (hop1_stream.hip; 1 = not served)
+    if (rc < 0) return rc;
     if (rc != OK) AVMOE_TRY(launch_gemm(g, st));
   }
   {                                                        // TV = V Wf^T

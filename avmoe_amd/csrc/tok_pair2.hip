@@ -20,7 +20,6 @@
 #include "gemm.h"
 #include "common.h"
 #include "prof.h"
-#include "kernels.h"
 #include "stream_isa.h"
 #include <algorithm>
 #include <cstdlib>
@@ -272,11 +271,16 @@ __global__ void __launch_bounds__(256) kk_tp2_finish(const float* __restrict__ s
 
 }  // namespace
 
-// 0 = launched, 1 = shape not served (the caller runs gemm_tokpair), < 0 error
-int k_tok_pair2(const void* X, long ldx, const void* dZx, long ldz, const void* dL2, long ldl, int S, int N, int G, int Cg, int M1, int KL,
-                float* dWt, float* dT, float* slabs, size_t slab_cap, hipStream_t st) {
-  if (Cg != 384 || M1 != 128 || KL < 1 || KL > 64 || ldl < 72 || N < 16 || S < 1 || ldx % 8 || ldz % 8 || ldl % 8 || !slabs ||
-      ((uintptr_t)X % 16) || ((uintptr_t)dZx % 16) || ((uintptr_t)dL2 % 16) || ((uintptr_t)dWt % 16) || ((uintptr_t)dT % 16) || (G * 384) % 4)
+// The same two contractions as launch_gemm_tokpair, from the same descriptor (gemm.h: TokPairArgs; both results laid out as it says).
+// 0 = launched, 1 = not served (the caller runs launch_gemm_tokpair), < 0 error
+int launch_tok_pair2(const TokPairArgs& a, hipStream_t st) {
+  const int S = a.S, N = a.N, G = a.g, KL = a.M2;
+  const long ldl = a.lda2;
+  float* const slabs = a.slabs; float* const dWt = a.C1; float* const dT = a.C2;
+  const size_t slab_cap = a.slab_cap;
+  // the tuned shape: 384 channels and 128 rows of A1 per group, the groups' rows side by side, <= 64 rows of A2 in rows of >= 72
+  if (a.Cg != 384 || a.M1 != 128 || a.sA1g != 128 || KL < 1 || KL > 64 || ldl < 72 || N < 16 || S < 1 || G < 1 || a.ldx % 8 || a.lda1 % 8 || ldl % 8 || !slabs ||
+      ((uintptr_t)a.X % 16) || ((uintptr_t)a.A1 % 16) || ((uintptr_t)a.A2 % 16) || ((uintptr_t)dWt % 16) || ((uintptr_t)dT % 16) || (G * 384) % 4)
     return 1;
   const bool force = (test_hook_mask() & HOOK_TOKPAIR2_FORCE) != 0;          // test hook (avmoe_test_hooks: tests / bench.py's parity leg switch it inside one process): small sites as well
   if (!force && (long)S * N < 32768) return 1;                              // small sites: the tiled form fills the chip better
@@ -290,7 +294,7 @@ int k_tok_pair2(const void* X, long ldx, const void* dZx, long ldz, const void* 
   const size_t need0 = (size_t)nb * G * (128 + 64) * 384, need = need0 + 64;
   if (need > slab_cap) return 1;
   TP2Args p;
-  p.X = (const char*)X; p.ldx = ldx; p.dZx = (const char*)dZx; p.ldz = ldz; p.dL2 = (const char*)dL2; p.ldl = ldl;
+  p.X = (const char*)a.X; p.ldx = a.ldx; p.dZx = (const char*)a.A1; p.ldz = a.lda1; p.dL2 = (const char*)a.A2; p.ldl = ldl;
   p.dT = dT; p.ldt = (long)G * 384; p.slabW = slabs; p.slabT = slabs + (size_t)nb * G * 128 * 384; p.dump = (char*)(slabs + need0);
   p.N = N; p.tpf = tpf; p.ntiles = S * tpf; p.KL = KL;
   static LdsAttrOnce attr;
