@@ -234,7 +234,7 @@ int launch_dpost_pair(const GemmArgs& gb, const GemmArgs& ga, size_t slab_cap, h
   // two plain products in one piece each, over one dOut: ga's rows (the tokens) are gb's contraction, ga's contraction (the group's channels) gb's rows
   auto plain = [](const GemmArgs& a) {
     return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb1 == 1 && a.nb3 == 1 && a.sCj == 1 &&
-           !a.row_scale && !a.D && !a.A2 && !a.A3s && !a.A4s && !a.st_rows && !a.st_cols && !a.B3 && !a.C3;
+           !a.row_scale && !a.D && !a.seg[0].A && !a.seg[1].A && !a.seg[2].A && !a.st_rows && !a.st_cols && !a.xcols.B && !a.xcols.C;
   };
   if (!plain(gb) || !plain(ga) || gb.A != ga.A || gb.lda != ga.lda || gb.sA2 != ga.sA2 || gb.K != ga.M || gb.M != ga.K || gb.N != ga.N || gb.nb2 != ga.nb2 || G < 1 ||
       gb.a_layout != MN_MAJOR || gb.b_layout != MN_MAJOR || gb.out_dtype != GEMM_F32 || gb.Cx || ga.a_layout != K_MAJOR || ga.b_layout != MN_MAJOR ||

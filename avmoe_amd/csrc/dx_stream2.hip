@@ -170,10 +170,10 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream2(const DX2Args p) {
 
 // Everything the kernel takes for granted of the product's descriptor (moe_backward.cpp::fill_dx_args builds it); anything else is not served.
 static bool dx2_serves(const GemmArgs& a) {
-  const long M = a.M;
+  const long M = a.M; const GemmSeg& l = a.seg[0];         // (l: the latent-token segment)
   // dX = dZx Wt in bf16, overwritten, in one piece, nothing else asked of the pass
   if (a.dtype != GEMM_BF16 || a.out_dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || a.alpha != 1.f || a.accumulate ||
-      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.A3s || a.A4s || a.Cx || a.st_rows || a.st_cols || a.B3 || a.C3)
+      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.seg[1].A || a.seg[2].A || a.Cx || a.st_rows || a.st_cols || a.xcols.B || a.xcols.C)
     return false;
   // the tuned shape; frames contiguous (the kernel walks tokens, not frames), groups side by side, one Wt for every frame
   if (a.N != 384 || a.K != 128 || a.M < BM || a.nb1 < 1 || a.nb2 < 1 || (long)a.nb1 * M < 2048 || a.sA1 != M * a.lda || a.sA2 != a.K || a.sB1 != 0 ||
@@ -181,10 +181,10 @@ static bool dx2_serves(const GemmArgs& a) {
     return false;
   // + rs X (X laid out as dX is) + [dL2 | dsx | 1] T[s] (one dL2 for all groups, T[s] per frame)
   if (!a.row_scale || !a.D || a.sRS1 != M || a.sRS2 != 0 || a.sD1 != M * a.sDi || a.sD2 != a.N ||
-      !a.A2 || !a.B2 || a.K2 < 1 || a.K2 > 72 || a.lda2 < 72 || a.s2A1 != M * a.lda2 || a.s2A2 != 0 || a.s2B2 != a.N)
+      !l.A || !l.B || l.a_layout != K_MAJOR || l.b_layout != MN_MAJOR || l.K < 1 || l.K > 72 || l.lda < 72 || l.sA1 != M * l.lda || l.sA2 != 0 || l.sB2 != a.N)
     return false;
   // 16-byte direct loads, 8-byte stores
-  return !(a.sDi % 8 || a.lda % 8 || a.lda2 % 8 || a.sCi % 4 || ((uintptr_t)a.D % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.A2 % 16) ||
+  return !(a.sDi % 8 || a.lda % 8 || l.lda % 8 || a.sCi % 4 || ((uintptr_t)a.D % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)l.A % 16) ||
            ((uintptr_t)a.C % 8) || ((uintptr_t)a.row_scale % 4));
 }
 
@@ -193,11 +193,11 @@ int launch_dx_stream2(const GemmArgs& a, hipStream_t st) {
   if (!dx2_serves(a)) return 1;
   const int cus = cu_count();                             // (cached per device: common.cpp)
   if (cus <= 0) { set_last_error("dx_stream2: device query"); return ERR_LAUNCH; }
-  const int S = a.nb1, N = a.M, G = a.nb2, K2 = a.K2;
-  const long ldl = a.lda2;
+  const GemmSeg& l = a.seg[0];
+  const int S = a.nb1, N = a.M, G = a.nb2, K2 = l.K; const long ldl = l.lda;
   DX2Args p;
-  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)a.A2; p.ldl = ldl; p.rs = a.row_scale;
-  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)a.B2; p.ldt = a.ldb2; p.sT1 = a.s2B1;
+  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)l.A; p.ldl = ldl; p.rs = a.row_scale;
+  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)l.B; p.ldt = l.ldb; p.sT1 = l.sB1;
   p.dX = (char*)a.C; p.ldc = a.sCi; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2;
   const int gx = std::min(std::max(1, cus / G), p.ntiles);
   static LdsAttrOnce attr;

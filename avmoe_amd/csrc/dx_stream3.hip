@@ -333,9 +333,10 @@ __global__ void __launch_bounds__(NTHR, 1) kk_dx_stream3(const DX3Args p) {
 // a matter of the pointers themselves (launch_dx_stream3): the answer of moe_backward_dx_dy's query, which has no buffers yet.
 bool dx_stream3_serves(const GemmArgs& a) {
   const long M = a.M;
+  const GemmSeg &l = a.seg[0], &v = a.seg[1], &q = a.seg[2];      // the latent-token segment; site B's [Bm ; wbar]^T dV and dR^T Q
   // site A's dX = dZx Wt in bf16, overwritten, in one piece, nothing else asked of the pass
   if (a.dtype != GEMM_BF16 || a.out_dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || a.alpha != 1.f || a.accumulate ||
-      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.Cx || a.st_rows || a.st_cols || a.N3 != 0)
+      a.epi != GEMM_EPI_NONE || a.ksplit > 1 || a.nb3 != 1 || a.Cx || a.st_rows || a.st_cols || a.xcols.B || a.xcols.C)
     return false;
   // the tuned shape; frames contiguous (the kernel walks tokens, not frames), groups side by side, one Wt for every frame
   // (M < 16: a ragged tile of a non-final frame would read 32 - 2 M rows past its successor)
@@ -344,32 +345,33 @@ bool dx_stream3_serves(const GemmArgs& a) {
     return false;
   // + rs X (X laid out as dX is) + [dL2 | dsx | 1] T[s] (one dL2 for all groups, T[s] per frame)
   if (a.sRS1 != M || a.sRS2 != 0 || a.sD1 != M * a.sDi || a.sD2 != a.N ||
-      a.K2 < 1 || a.K2 > 72 || a.lda2 < 72 || a.s2A1 != M * a.lda2 || a.s2A2 != 0 || a.s2B2 != a.N)
+      l.a_layout != K_MAJOR || l.b_layout != MN_MAJOR || l.K < 1 || l.K > 72 || l.lda < 72 || l.sA1 != M * l.lda || l.sA2 != 0 || l.sB2 != a.N)
     return false;
   // site B's dY: + [Bm ; wbar][s]^T dV[s] (per frame, the frame's tokens along a row) + dR^T Q (tokens contiguous, one Q)
-  if (a.K3s < 1 || a.K3s > 96 || a.lda3s < M || a.s3sB2 != a.N ||
-      a.K4s < 1 || a.K4s > 64 || a.lda4s < 8 || a.s4sA1 != M * a.lda4s || a.s4sB1 != 0 || a.s4sB2 != a.N)
+  if (v.a_layout != MN_MAJOR || v.b_layout != MN_MAJOR || v.K < 1 || v.K > 96 || v.lda < M || v.sA2 != 0 || v.sB2 != a.N ||
+      q.a_layout != K_MAJOR || q.b_layout != MN_MAJOR || q.K < 1 || q.K > 64 || q.lda < 8 || q.sA1 != M * q.lda || q.sA2 != 0 || q.sB1 != 0 || q.sB2 != a.N)
     return false;
   // 16-byte direct loads, 8-byte stores
-  return !(a.sDi % 8 || a.lda % 8 || a.lda2 % 8 || a.lda4s % 8 || a.lda3s % 8 || a.s3sA1 % 8 || a.sCi % 4);
+  return !(a.sDi % 8 || a.lda % 8 || l.lda % 8 || q.lda % 8 || v.lda % 8 || v.sA1 % 8 || a.sCi % 4);
 }
 
 // 0 = launched, 1 = not served (the caller runs the dX product and site B's dY product separately), < 0 error.  GemmArgs::slabs: the dump word.
 int launch_dx_stream3(const GemmArgs& a, hipStream_t st) {
   if (!dx_stream3_serves(a)) return 1;
-  if (!a.A || !a.B || !a.D || !a.row_scale || !a.A2 || !a.B2 || !a.A3s || !a.B3s || !a.A4s || !a.B4s || !a.C || !a.slabs ||
-      ((uintptr_t)a.D % 16) || ((uintptr_t)a.A % 16) || ((uintptr_t)a.A2 % 16) || ((uintptr_t)a.A4s % 16) || ((uintptr_t)a.A3s % 16) || ((uintptr_t)a.C % 8) ||
-      ((uintptr_t)a.row_scale % 4) || ((uintptr_t)a.slabs % 16))
+  for (int i = 0; i < 4; ++i)                               // every segment: both operands, A read by 16-byte direct loads
+    if (!a.segment(i).A || !a.segment(i).B || ((uintptr_t)a.segment(i).A % 16)) return 1;
+  if (!a.D || !a.row_scale || !a.C || !a.slabs || ((uintptr_t)a.D % 16) || ((uintptr_t)a.C % 8) || ((uintptr_t)a.row_scale % 4) || ((uintptr_t)a.slabs % 16))
     return 1;
+  const GemmSeg &l = a.seg[0], &v = a.seg[1], &q = a.seg[2];
   const int cus = cu_count();
   if (cus <= 0) { set_last_error("dx_stream3: device query"); return ERR_LAUNCH; }
-  const int S = a.nb1, N = a.M, G = a.nb2, K2 = a.K2, KB = a.K3s, KQ = a.K4s;
-  const long ldl = a.lda2, ldr = a.lda4s;
+  const int S = a.nb1, N = a.M, G = a.nb2, K2 = l.K, KB = v.K, KQ = q.K;
+  const long ldl = l.lda, ldr = q.lda;
   DX3Args p;
-  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)a.A2; p.ldl = ldl; p.rs = a.row_scale;
-  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)a.B2; p.ldt = a.ldb2; p.sT1 = a.s2B1;
-  p.Bm = (const char*)a.A3s; p.ldb = a.lda3s; p.sB1 = a.s3sA1; p.dRT = (const char*)a.A4s; p.ldr = ldr;
-  p.dV = (const unsigned short*)a.B3s; p.ldv = a.ldb3s; p.sV1 = a.s3sB1; p.Q = (const unsigned short*)a.B4s; p.ldq = a.ldb4s;
+  p.X = (const char*)a.D; p.ldx = a.sDi; p.dZx = (const char*)a.A; p.ldz = a.lda; p.dL2 = (const char*)l.A; p.ldl = ldl; p.rs = a.row_scale;
+  p.Wt = (const unsigned short*)a.B; p.ldw = a.ldb; p.sWg = a.sB2; p.Text = (const unsigned short*)l.B; p.ldt = l.ldb; p.sT1 = l.sB1;
+  p.Bm = (const char*)v.A; p.ldb = v.lda; p.sB1 = v.sA1; p.dRT = (const char*)q.A; p.ldr = ldr;
+  p.dV = (const unsigned short*)v.B; p.ldv = v.ldb; p.sV1 = v.sB1; p.Q = (const unsigned short*)q.B; p.ldq = q.ldb;
   p.dX = (char*)a.C; p.ldc = a.sCi; p.dump = (char*)a.slabs; p.N = N; p.tps = (N + BM - 1) / BM; p.ntiles = S * p.tps; p.K2 = K2; p.KB = KB; p.KQ = KQ;
   p.ncr = (int)std::min<long>(8, ldr / 8);
   const int gx = std::min(std::max(1, cus / G), p.ntiles);

@@ -338,7 +338,7 @@ int launch_gemm_frames(const GemmArgs& a, hipStream_t st) {
   const bool tr = a.sCj != 1;                                 // C[s] stored [n][m]
   const long ldc = tr ? a.sCj : a.sCi;
   if (off || a.dtype != GEMM_BF16 || a.epi != GEMM_EPI_NONE || a.nb2 != 1 || a.nb3 > 1 || a.a_layout != K_MAJOR || a.b_layout != K_MAJOR || a.sB1 != 0 ||
-      a.M < 1 || a.nb1 < 32 || a.ksplit > 1 || a.A2 || a.D || a.row_scale || a.accumulate || (tr && a.sCi != 1) || a.Cx || a.st_rows || a.N < 64 || a.K < 1 || (a.K > 256 && a.N > 224) ||
+      a.M < 1 || a.nb1 < 32 || a.ksplit > 1 || a.seg[0].A || a.D || a.row_scale || a.accumulate || (tr && a.sCi != 1) || a.Cx || a.st_rows || a.N < 64 || a.K < 1 || (a.K > 256 && a.N > 224) ||
       a.lda % 8 || a.ldb % 8 || a.sA1 % 8 || ((uintptr_t)a.A % 16) || ((uintptr_t)a.B % 16) || ldc % 4 || a.sC1 % 4 || ((uintptr_t)a.C % 16) ||
       64 * a.lda * 2 >= (1L << 31))
     return 1;

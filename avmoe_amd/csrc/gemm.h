@@ -13,7 +13,7 @@
 //              ds_read_b64_tr_b16 (bf16) / strided ds_read_b32 (f32)
 // C is addressed with explicit (sCi, sCj) strides; one of them must be 1.
 //
-// Contract for callers (checked in gemm.hip::validate):
+// Contract for callers (checked in gemm.hip::launch_gemm, of each of the up to four K segments of a product):
 //   * base pointers 16-byte aligned, ld * sizeof(T) and batch strides * sizeof(T) multiples of 16
 //   * K_MAJOR operands: every row readable (finite) up to roundup(K, 16/sizeof(T)) elements; at
 //     least one of the two operands is ZERO in that padding
@@ -27,19 +27,23 @@ namespace avmoe {
 enum GemmDtype { GEMM_F32 = 0, GEMM_BF16 = 1 };
 enum GemmLayout { K_MAJOR = 0, MN_MAJOR = 1 };
 
-struct GemmArgs {
-  const void* A = nullptr;
-  const void* B = nullptr;
+// One K segment of a product:  sum_k A[b][i][k] * B[b][j][k].  The layouts are per segment and always meant: the engine and the streaming
+// wrappers refuse a segment whose layouts they have no kernel for.
+struct GemmSeg {
+  const void* A = nullptr; const void* B = nullptr; int K = 0;
+  int a_layout = K_MAJOR, b_layout = K_MAJOR;
+  long lda = 0, ldb = 0, sA1 = 0, sA2 = 0, sB1 = 0, sB2 = 0;   // leading dimensions and batch strides, elements
+};
+
+// A product: its first K segment (the base: A, B, K, a_layout .. sB2), up to three further ones (`seg`), the output, the batch levels, optional terms
+struct GemmArgs : GemmSeg {
   void* C = nullptr;
-  int M = 0, N = 0, K = 0;
+  int M = 0, N = 0;
   int nb1 = 1, nb2 = 1;                 // batch = nb1 * nb2 ; b = b1 * nb2 + b2
   int nb3 = 1;                          // optional third batch level (tiled engine only, no D term): batch = nb1 * nb3 * nb2,
   long sA3 = 0, sB3 = 0, sC3 = 0;       // b = (b1 * nb3 + b3) * nb2 + b2 ; strides in elements
   int dtype = GEMM_F32;                 // A, B (and D) element type
   int out_dtype = GEMM_F32;             // C element type
-  int a_layout = K_MAJOR, b_layout = K_MAJOR;
-  long lda = 0, ldb = 0;
-  long sA1 = 0, sA2 = 0, sB1 = 0, sB2 = 0;   // batch strides, elements
   long sCi = 0, sCj = 1, sC1 = 0, sC2 = 0;   // C strides, elements
   float alpha = 1.f;
   int accumulate = 0;                   // C += ...
@@ -63,24 +67,15 @@ struct GemmArgs {
   // from (moe_run.h: AVMOE_LEAF2 = 26 -- dWt, the hop-1 weight gradients, the token gradients; AVMOE_BWD_PLANES has why not for all of them).
   int split3 = 0;
   int tile = 0;                         // 0 = auto, 64 or 128 = force block tile
-  // optional second K segment, accumulated into the same tile before the epilogue:
-  //   C += alpha * A2[b][i][k2] * B2[b][j][k2]   with A2 K_MAJOR (lda2), B2 MN_MAJOR (ldb2), own batch strides.
-  // Fuses e.g. dX = dZx Wt + [dL2|dsx|1] [T;1;dm1/N] so the (NT, C) result is written once.
-  const void* A2 = nullptr;
-  const void* B2 = nullptr;
-  int K2 = 0;
-  long lda2 = 0, ldb2 = 0, s2A1 = 0, s2A2 = 0, s2B1 = 0, s2B2 = 0;
-  // optional THIRD and FOURTH K segments (tiled engine, A K_MAJOR / B MN_MAJOR first segment with a second segment; both or none):
-  //   C += alpha * ( A3[b][i][k3] B3s[b][j][k3]  +  A4[b][i][k4] B4s[b][j][k4] )      A3 MN_MAJOR, A4 K_MAJOR, B3s / B4s MN_MAJOR
-  // -- the OTHER adapter site's dY = [Bm ; wbar]^T dV + dR^T Q folded into this site's dX product (moe_backward_dx_dy): the token gradient is
-  // written once instead of written by one site and read back + added by the other.  K4 may be 0 (no cross-modal chain).
-  const void* A3s = nullptr;
-  const void* B3s = nullptr;
-  const void* A4s = nullptr;
-  const void* B4s = nullptr;
-  int K3s = 0, K4s = 0;
-  long lda3s = 0, ldb3s = 0, s3sA1 = 0, s3sB1 = 0, s3sB2 = 0;
-  long lda4s = 0, ldb4s = 0, s4sA1 = 0, s4sB1 = 0, s4sB2 = 0;
+  // optional second, third and fourth K segments (seg[0 .. 2]; present when A is set, each needs the one before it), accumulated into the
+  // same tile before the epilogue, each with its own layouts and strides:  C += alpha * sum_i seg[i].A[b][i][k] * seg[i].B[b][j][k]
+  // Built on the tiled engine: a second segment (K_MAJOR A, MN_MAJOR B) behind a first one with B MN_MAJOR -- fuses e.g.
+  // dX = dZx Wt + [dL2|dsx|1] [T;1;dm1/N] so the (NT, C) result is written once -- and a third (MN_MAJOR A and B) with an optional fourth
+  // (K_MAJOR A, MN_MAJOR B) behind a K_MAJOR A / MN_MAJOR B first and a second segment (bf16 or a plane form; A strided by sA1 only) -- the
+  // OTHER adapter site's dY = [Bm ; wbar]^T dV + dR^T Q folded into this site's dX product (moe_backward_dx_dy): the token gradient is
+  // written once instead of written by one site and read back + added by the other.
+  GemmSeg seg[3];
+  const GemmSeg& segment(int i) const { return i ? seg[i - 1] : *this; }      // i = 0 .. 3: all four, the first included
   // optional split output (streaming kernel only; launch_gemm_stream returns 1 when it cannot honour it): columns >= nsplit
   // (a multiple of 32) go, in fp32, to Cx[b2][i][j - nsplit] (row stride ldcx, group stride sCx2) instead of C -- lets the
   // wide part of a product be stored in bf16 while a few columns that feed long fp32 sums keep full precision.
@@ -109,15 +104,17 @@ struct GemmArgs {
   int* st_tiles = nullptr;
   // optional EXTRA output columns against a per-sample matrix, from the same pass over A (streaming kernel with statistics only;
   // launch_gemm_stream returns 1 when it cannot honour them):
-  //   C3[b1][b2][i][j] = sum_k A[b1][b2][i][k] * B3[b1][b2][j][k]      j < N3 <= 64, B3 K_MAJOR (ldb3), fp32 result (row stride ldc3)
+  //   xcols.C[b1][b2][i][j] = sum_k A[b1][b2][i][k] * xcols.B[b1][b2][j][k]      j < xcols.N <= 64, B K_MAJOR (ldb), fp32 result (row stride ldc)
   // -- the hop-2 logits of a site, X[s] T[s]^T, as per-group partial sums out of the down projection's pass over X (the caller adds
   // the groups): X is read once instead of twice.
-  const void* B3 = nullptr;
-  int N3 = 0;
-  long ldb3 = 0, s3B1 = 0, s3B2 = 0;
-  float* C3 = nullptr;
-  long ldc3 = 0, s3C1 = 0, s3C2 = 0;
+  struct {
+    const void* B = nullptr; int N = 0; long ldb = 0, sB1 = 0, sB2 = 0;
+    float* C = nullptr; long ldc = 0, sC1 = 0, sC2 = 0;
+  } xcols;
 };
+
+// The block tile launch_gemm picks by itself for an (M, N) product, before it looks at the block count: what sizes split-K slabs (choose_ksplit)
+inline int gemm_auto_tile(int M, int N) { return (M > 64 && N > 64) ? 128 : ((M <= 32 && N <= 32) ? 32 : 64); }
 
 // Returns 0 on success, negative avmoe status otherwise (message through set_last_error).
 int launch_gemm(const GemmArgs& args, hipStream_t stream);
@@ -149,7 +146,7 @@ int launch_gemm_tokpair(const TokPairArgs& args, hipStream_t stream);
 // launch_gemm_stream they take the engine's descriptor of the product, check everything they assume of it and return 0 = launched,
 // 1 = not served (nothing was launched: the caller goes on to the next form, launch_gemm last), < 0 error.  launch_gemm does not try them.
 int launch_dx_stream2(const GemmArgs& args, hipStream_t stream);     // dX[s] = dZx[s] Wt + dL2x[s] T[s] + rs X[s]: two K segments + row-scale term (dx_stream2.hip)
-// ... with the other site's dY as segments three and four (A3s .. B4s), written once (dx_stream3.hip); slabs: >= 256 bytes the kernel may scribble on
+// ... with the other site's dY as segments three and four (seg[1], seg[2]), written once (dx_stream3.hip); slabs: >= 256 bytes the kernel may scribble on
 bool dx_stream3_serves(const GemmArgs& args);                        // the same answer from shape and strides alone (no buffers yet)
 int launch_dx_stream3(const GemmArgs& args, hipStream_t stream);
 // the hop-1 chain's products against Y (hop1_stream.hip): C[s] = A[(s)] Y[s]^T (K-major A and Y, nb1 frames; slabs: 16 bytes the kernel may

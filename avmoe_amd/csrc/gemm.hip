@@ -1052,11 +1052,13 @@ static int launch_big_inst(const DevArgs& d, int batch_z, hipStream_t stream) {
 template <typename T, int BM, int BN>
 static int launch_layout(const GemmArgs& a, const DevArgs& d, int bz, hipStream_t s) {
   const bool amn = a.a_layout == MN_MAJOR, bmn = a.b_layout == MN_MAJOR;
-  if (a.A3s) {
+  for (int i = 1; i < 4; ++i)        // the further segments' instances: A K-major (the third's: MN-major), B MN-major
+    if (const GemmSeg& g = a.segment(i); g.A && (g.a_layout != (i == 2 ? MN_MAJOR : K_MAJOR) || g.b_layout != MN_MAJOR)) { set_last_error("gemm: no instance for the layouts of K segment %d", i + 1); return ERR_UNSUPPORTED; }
+  if (a.seg[1].A) {
     if constexpr (BM == BN && !std::is_same<T, float>::value) return launch_inst<T, BM, BN, false, true, true, true>(d, bz, s);      // (validated: K-major A, MN-major B, a second segment)
     else { set_last_error("gemm: third / fourth K segments are built for the square tiles of the bf16 and the plane forms"); return ERR_UNSUPPORTED; }
   }
-  if (a.A2) {
+  if (a.seg[0].A) {
     if (!amn && bmn) return launch_inst<T, BM, BN, false, true, true>(d, bz, s);
     if (amn && bmn) return launch_inst<T, BM, BN, true, true, true>(d, bz, s);
     set_last_error("gemm: second K segment is built for B MN-major first segments only");
@@ -1070,9 +1072,9 @@ static int launch_layout(const GemmArgs& a, const DevArgs& d, int bz, hipStream_
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
+static int launch_splitk_reduce(const DevArgs& d, bool bf16, hipStream_t stream);      // (below launch_gemm: the kernels keep their order in the code object)
 size_t gemm_slab_bytes(const GemmArgs& a) {
-  if (a.ksplit <= 1) return 0;
-  return (size_t)a.ksplit * a.nb1 * a.nb2 * a.nb3 * (size_t)a.M * a.N * sizeof(float);
+  return a.ksplit <= 1 ? 0 : (size_t)a.ksplit * a.nb1 * a.nb2 * a.nb3 * (size_t)a.M * a.N * sizeof(float);
 }
 
 int launch_gemm(const GemmArgs& a, hipStream_t stream) {
@@ -1085,13 +1087,26 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   if (!(a.sCj == 1 || a.sCi == 1)) { set_last_error("gemm: C needs a unit stride"); return ERR_UNSUPPORTED; }
   const int esz = a.dtype == GEMM_BF16 ? 2 : 4;
   auto mult16 = [&](long elems) { return (elems * esz) % 16 == 0; };
-  if (!aligned16(a.A) || !aligned16(a.B) || !mult16(a.lda) || !mult16(a.ldb) || !mult16(a.sA1) ||
-      !mult16(a.sA2) || !mult16(a.sB1) || !mult16(a.sB2)) {
-    set_last_error("gemm: operand alignment contract violated (A=%p B=%p lda=%ld ldb=%ld)", a.A, a.B, a.lda, a.ldb);
-    return ERR_ALIGNMENT;
+  bool bad_seg = false;                                    // a further segment off the operand contract of gemm.h (refused below: its status is another)
+  for (int i = 0; i < 4; ++i) {
+    const GemmSeg& g = a.segment(i);
+    if (i && !g.A && !g.B) continue;                        // (no such segment)
+    if (g.A && g.B && aligned16(g.A) && aligned16(g.B) && mult16(g.lda) && mult16(g.ldb) && mult16(g.sA1) && mult16(g.sA2) && mult16(g.sB1) && mult16(g.sB2) &&
+        (i < 2 || a.segment(i - 1).A))
+      continue;
+    if (!i) { set_last_error("gemm: operand alignment contract violated (A=%p B=%p lda=%ld ldb=%ld)", a.A, a.B, a.lda, a.ldb); return ERR_ALIGNMENT; }
+    bad_seg = true;
   }
   if (a.ksplit > 1 && !a.slabs) { set_last_error("gemm: split-K without slab workspace"); return ERR_WORKSPACE; }
   if (a.epi != GEMM_EPI_MULSUB && (a.row_scale != nullptr) != (a.D != nullptr)) { set_last_error("gemm: row_scale and D go together"); return ERR_BAD_ARG; }
+  const GemmSeg &s2 = a.seg[0], &s3 = a.seg[1], &s4 = a.seg[2];
+  // more than one K segment: a pair of aligned pointers each and the one before it, one pass, no softmax epilogue, no third batch level; the
+  // third and the fourth behind a K-major A / MN-major B product, bf16 or a plane form, their A shared by the groups
+  if (bad_seg || (s2.A && (a.ksplit > 1 || a.epi != GEMM_EPI_NONE || a.nb3 > 1)) ||
+      (s3.A && (s3.K <= 0 || a.a_layout != K_MAJOR || a.b_layout != MN_MAJOR || !(a.dtype == GEMM_BF16 || a.split3) || s3.sA2 || s4.sA2 || (s4.K != 0 && !s4.A)))) {
+    set_last_error("gemm: bad further K segment (pair of pointers behind its predecessor, no split-K, 16-byte aligned strides; gemm.h: GemmArgs::seg)");
+    return ERR_BAD_ARG;
+  }
 
   DevArgs d;
   d.A = (const char*)a.A; d.B = (const char*)a.B; d.C = (char*)a.C; d.D = (const char*)a.D;
@@ -1099,41 +1114,27 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   d.M = a.M; d.N = a.N; d.K = a.K; d.nb2 = a.nb2; d.nb3 = a.nb3 > 1 ? a.nb3 : 1; d.ksplit = a.ksplit > 1 ? a.ksplit : 1;
   d.nbatch = a.nb1 * a.nb2 * d.nb3;
   d.sA3 = a.sA3; d.sB3 = a.sB3; d.sC3 = a.sC3;
-  if (d.nb3 > 1 && (a.D || a.A2 || a.epi != GEMM_EPI_NONE || a.Cx || a.st_rows || !mult16(a.sA3) || !mult16(a.sB3))) {
+  if (d.nb3 > 1 && (a.D || a.epi != GEMM_EPI_NONE || a.Cx || a.st_rows || !mult16(a.sA3) || !mult16(a.sB3))) {
     set_last_error("gemm: the third batch level serves plain products only (16-byte aligned strides)"); return ERR_BAD_ARG;
   }
   d.lda = a.lda; d.ldb = a.ldb; d.sA1 = a.sA1; d.sA2 = a.sA2; d.sB1 = a.sB1; d.sB2 = a.sB2;
   d.sCi = a.sCi; d.sCj = a.sCj; d.sC1 = a.sC1; d.sC2 = a.sC2;
   d.sRS1 = a.sRS1; d.sRS2 = a.sRS2; d.sDi = a.sDi; d.sD1 = a.sD1; d.sD2 = a.sD2;
   d.alpha = a.alpha; d.accumulate = a.accumulate; d.out_bf16 = a.out_dtype == GEMM_BF16;
-  d.A2 = (const char*)a.A2; d.B2 = (const char*)a.B2; d.K2 = a.K2; d.lda2 = a.lda2; d.ldb2 = a.ldb2;
-  d.s2A1 = a.s2A1; d.s2A2 = a.s2A2; d.s2B1 = a.s2B1; d.s2B2 = a.s2B2;
-  d.A3s = (const char*)a.A3s; d.B3s = (const char*)a.B3s; d.A4s = (const char*)a.A4s; d.B4s = (const char*)a.B4s; d.K3s = a.K3s; d.K4s = a.K4s;
-  d.lda3s = a.lda3s; d.ldb3s = a.ldb3s; d.s3sA1 = a.s3sA1; d.s3sB1 = a.s3sB1; d.s3sB2 = a.s3sB2;
-  d.lda4s = a.lda4s; d.ldb4s = a.ldb4s; d.s4sA1 = a.s4sA1; d.s4sB1 = a.s4sB1; d.s4sB2 = a.s4sB2;
-  if (a.A3s) {
-    const bool ok = a.A2 && a.B3s && a.K3s > 0 && a.a_layout == K_MAJOR && a.b_layout == MN_MAJOR && a.ksplit <= 1 && a.epi == GEMM_EPI_NONE && d.nb3 == 1 &&
-                    (a.dtype == GEMM_BF16 || a.split3) && aligned16(a.A3s) && aligned16(a.B3s) && mult16(a.lda3s) && mult16(a.ldb3s) && mult16(a.s3sA1) &&
-                    mult16(a.s3sB1) && mult16(a.s3sB2) &&
-                    (a.K4s == 0 || (a.A4s && a.B4s && aligned16(a.A4s) && aligned16(a.B4s) && mult16(a.lda4s) && mult16(a.ldb4s) && mult16(a.s4sA1) && mult16(a.s4sB1) && mult16(a.s4sB2)));
-    if (!ok) { set_last_error("gemm: third / fourth K segments need a K-major A / MN-major B product with a second segment, no split-K, aligned operands"); return ERR_BAD_ARG; }
-  }
+  d.A2 = (const char*)s2.A; d.B2 = (const char*)s2.B; d.K2 = s2.K; d.lda2 = s2.lda; d.ldb2 = s2.ldb; d.s2A1 = s2.sA1; d.s2A2 = s2.sA2; d.s2B1 = s2.sB1; d.s2B2 = s2.sB2;
+  d.A3s = (const char*)s3.A; d.B3s = (const char*)s3.B; d.K3s = s3.K; d.lda3s = s3.lda; d.ldb3s = s3.ldb; d.s3sA1 = s3.sA1; d.s3sB1 = s3.sB1; d.s3sB2 = s3.sB2;
+  d.A4s = (const char*)s4.A; d.B4s = (const char*)s4.B; d.K4s = s4.K; d.lda4s = s4.lda; d.ldb4s = s4.ldb; d.s4sA1 = s4.sA1; d.s4sB1 = s4.sB1; d.s4sB2 = s4.sB2;
   d.epi = a.epi; d.row_part = a.row_part; d.row_lse = a.row_lse;
   if (a.epi != GEMM_EPI_NONE) {
-    if (a.ksplit > 1 || a.sCj != 1 || (a.D != nullptr) != (a.epi == GEMM_EPI_MULSUB) || a.row_scale || a.accumulate || a.A2 || a.Cx || a.st_rows ||
+    if (a.ksplit > 1 || a.sCj != 1 || (a.D != nullptr) != (a.epi == GEMM_EPI_MULSUB) || a.row_scale || a.accumulate || a.Cx || a.st_rows ||
         (a.tile != 0 && a.tile != 128) || (a.epi == GEMM_EPI_ROWSTATS && !a.row_part) || (a.epi != GEMM_EPI_ROWSTATS && !a.row_lse)) {
       set_last_error("gemm: softmax epilogue needs a plain row-major single-pass product on the 128 x 128 tile");
       return ERR_BAD_ARG;
     }
   }
-  if ((a.A2 != nullptr) != (a.B2 != nullptr) || (a.A2 && (a.ksplit > 1 || !aligned16(a.A2) || !aligned16(a.B2) || !mult16(a.lda2) || !mult16(a.ldb2) ||
-                                                  !mult16(a.s2A1) || !mult16(a.s2A2) || !mult16(a.s2B1) || !mult16(a.s2B2)))) {
-    set_last_error("gemm: bad second K segment (pair of pointers, no split-K, 16-byte aligned strides)");
-    return ERR_BAD_ARG;
-  }
   {
     static const bool nostream = dev_env("AVMOE_GEMM_NOSTREAM") != nullptr;     // dev switch: A/B against the tiled engine
-    if (!nostream && a.epi == GEMM_EPI_NONE && a.nb3 <= 1 && !a.A3s) {
+    if (!nostream && a.epi == GEMM_EPI_NONE && a.nb3 <= 1 && !s3.A) {
       const int s = launch_gemm_stream(a, stream);
       if (s <= 0) return s;
       const int f = launch_gemm_frames(a, stream);           // a few rows per frame against one shared matrix (frame_gemm.hip)
@@ -1147,10 +1148,10 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   d.fold_rps = d.fold_valid = 0;
   {
     static const bool nofold = dev_env("AVMOE_GEMM_NOFOLD") != nullptr;      // dev switch
-    if (!nofold && a.epi == GEMM_EPI_NONE && a.nb1 > 1 && a.nb2 == 1 && d.nb3 == 1 && a.a_layout == K_MAJOR && a.sB1 == 0 && d.ksplit == 1 && !a.A2 && !a.D && a.lda > 0 &&
+    if (!nofold && a.epi == GEMM_EPI_NONE && a.nb1 > 1 && a.nb2 == 1 && d.nb3 == 1 && a.a_layout == K_MAJOR && a.sB1 == 0 && d.ksplit == 1 && !s2.A && !a.D && a.lda > 0 &&
         a.sA1 > 0 && a.sA1 % a.lda == 0) {
       const long rps = a.sA1 / a.lda, rows = (long)(a.nb1 - 1) * rps + a.M;
-      const int t0 = a.tile ? a.tile : ((a.M > 64 && a.N > 64) ? 128 : 64);      // tile of the unfolded launch
+      const int t0 = a.tile ? a.tile : ((a.M > 64 && a.N > 64) ? 128 : 64);      // tile of the unfolded launch (not gemm_auto_tile: no 32 tile, such a sample is weighed against the 64 one)
       const bool wasteful = round_up(a.M, t0) * 4 >= (long)a.M * 5;             // >= 25 % of its tile rows are padding (measured:
                                                                                   // folding full tiles of the same size gains nothing)
       // ... or the samples' blocks are too short for the 256 x 256 tile while the tall product is not (cfg-5: 384 latent rows per frame
@@ -1172,7 +1173,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
 
   int tile = a.tile;
   if (a.epi != GEMM_EPI_NONE) tile = 128;
-  else if (tile == 0 || d.fold_rps) tile = (d.M > 64 && a.N > 64) ? 128 : ((d.M <= 32 && a.N <= 32) ? 32 : 64);
+  else if (tile == 0 || d.fold_rps) tile = gemm_auto_tile(d.M, a.N);
   const int bz = d.nbatch * d.ksplit;
   if (bz > 65535) { set_last_error("gemm: batch*ksplit=%d exceeds grid.y", bz); return ERR_UNSUPPORTED; }
   // Small products are bound by the latency of their K loop, not by throughput: a tile size that leaves most of the 256 CUs without
@@ -1185,21 +1186,21 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   }
   int st;
   // the 256 x 256 tile for large plain bf16 products (enough tiles of it to fill the chip)
-  const bool big = a.dtype == GEMM_BF16 && a.tile == 0 && tile == 128 && a.epi == GEMM_EPI_NONE && !a.A2 && !a.D && d.M >= GEMM_BIG_MIN && a.N >= GEMM_BIG_MIN &&
+  const bool big = a.dtype == GEMM_BF16 && a.tile == 0 && tile == 128 && a.epi == GEMM_EPI_NONE && !s2.A && !a.D && d.M >= GEMM_BIG_MIN && a.N >= GEMM_BIG_MIN &&
                    a.K >= 256 && (long)cdiv(d.M, 256) * cdiv(a.N, 256) * bz >= 160;
   if (big) {
     d.tiles_n = cdiv(a.N, 256);
     const bool amn = a.a_layout == MN_MAJOR, bmn = a.b_layout == MN_MAJOR;
     st = amn ? (bmn ? launch_big_inst<true, true>(d, bz, stream) : launch_big_inst<true, false>(d, bz, stream))
              : (bmn ? launch_big_inst<false, true>(d, bz, stream) : launch_big_inst<false, false>(d, bz, stream));
-  } else if (tile == 128 && a.tile == 0 && a.dtype == GEMM_F32 && a.split3 == 1 && a.epi == GEMM_EPI_NONE && !a.A2 && a.b_layout == MN_MAJOR &&
+  } else if (tile == 128 && a.tile == 0 && a.dtype == GEMM_F32 && a.split3 == 1 && a.epi == GEMM_EPI_NONE && !s2.A && a.b_layout == MN_MAJOR &&
              round_up(a.N, 160) * 23 <= round_up(a.N, 128) * 20) {
     // 128 x 160 tile (round 6): fp32 three-plane products -- matrix-pipe-bound, six plane products per K step -- whose N leaves the last
     // 128-column tile mostly empty: the 128 + 3 E columns of dApost / dBpost (N = 140: 160 instead of 256 columns computed; fp32 cfg-2,
     // audio tokens: dApost 884 -> 761 us, dBpost 876 -> 630).  Same K order per output element: the same bits as every other tile.
     d.tiles_n = cdiv(a.N, 160);
     st = a.a_layout == MN_MAJOR ? launch_inst<f32s3, 128, 160, true, true>(d, bz, stream) : launch_inst<f32s3, 128, 160, false, true>(d, bz, stream);
-  } else if (tile == 128 && a.tile == 0 && a.dtype == GEMM_F32 && a.split3 == 1 && a.epi == GEMM_EPI_NONE && !a.A2 && a.a_layout == K_MAJOR && !d.fold_rps &&
+  } else if (tile == 128 && a.tile == 0 && a.dtype == GEMM_F32 && a.split3 == 1 && a.epi == GEMM_EPI_NONE && !s2.A && a.a_layout == K_MAJOR && !d.fold_rps &&
              d.ksplit == 1 && round_up(d.M, 96) * 23 <= round_up(d.M, 128) * 20) {
     // 96 x 128 tile: the same for M -- the 65 rows ([latent tokens ; wbar]) of the per-frame hop-1 products against Y fill half of a 128-row tile
     d.tiles_n = cdiv(a.N, 128);
@@ -1222,18 +1223,24 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   }
   if (st != OK) return st;
   if (d.ksplit > 1 && !a.keep_slabs) {
-    const long total = (long)d.nbatch * a.M * a.N;
-    if (total >= (1L << 31)) { set_last_error("gemm: split-K result too large"); return ERR_UNSUPPORTED; }
-    const long nvec = (a.N % 4 == 0) ? total / 4 : total;
-    int lgP = 0;                                             // lanes per output vector: enough threads for ~2 waves per SIMD
-    while (lgP < 4 && (2 << lgP) <= d.ksplit && (nvec << lgP) < 131072) ++lgP;
-    const long nwv = (nvec + (64 >> lgP) - 1) / (64 >> lgP);
-    const int blocks = (int)std::min<long>((nwv + 3) / 4, 4096);
-    ProfScope ps("gemm_splitk_reduce", total, (double)total * 4.0 * (d.ksplit + 1), 0.0, stream);      // (tagged with the result's element count)
-    if (a.dtype == GEMM_BF16) hipLaunchKernelGGL(gemm_splitk_reduce<__bf16>, dim3(blocks), dim3(256), 0, stream, d, lgP);
-    else hipLaunchKernelGGL(gemm_splitk_reduce<float>, dim3(blocks), dim3(256), 0, stream, d, lgP);
-    AVMOE_CHECK_LAUNCH("gemm_splitk_reduce");
+    if ((long)d.nbatch * d.M * d.N >= (1L << 31)) { set_last_error("gemm: split-K result too large"); return ERR_UNSUPPORTED; }
+    return launch_splitk_reduce(d, a.dtype == GEMM_BF16, stream);
   }
+  return OK;
+}
+
+// The sum of the ksplit slabs of d.nbatch (d.M, d.N) results into C (bf16: which instance of the one kernel, as the operands were)
+static int launch_splitk_reduce(const DevArgs& d, bool bf16, hipStream_t stream) {
+  const long total = (long)d.nbatch * d.M * d.N;
+  const long nvec = (d.N % 4 == 0) ? total / 4 : total;
+  int lgP = 0;                                             // lanes per output vector: enough threads for ~2 waves per SIMD
+  while (lgP < 4 && (2 << lgP) <= d.ksplit && (nvec << lgP) < 131072) ++lgP;
+  const long nwv = (nvec + (64 >> lgP) - 1) / (64 >> lgP);
+  const int blocks = (int)std::min<long>((nwv + 3) / 4, 4096);
+  ProfScope ps("gemm_splitk_reduce", total, (double)total * 4.0 * (d.ksplit + 1), 0.0, stream);      // (tagged with the result's element count)
+  if (bf16) hipLaunchKernelGGL(gemm_splitk_reduce<__bf16>, dim3(blocks), dim3(256), 0, stream, d, lgP);
+  else hipLaunchKernelGGL(gemm_splitk_reduce<float>, dim3(blocks), dim3(256), 0, stream, d, lgP);
+  AVMOE_CHECK_LAUNCH("gemm_splitk_reduce");
   return OK;
 }
 
@@ -1291,14 +1298,7 @@ int launch_gemm_tokpair(const TokPairArgs& a, hipStream_t stream) {
   DevArgs d{};
   d.C = (char*)a.C1; d.slabs = a.slabs; d.M = a.M1; d.N = a.Cg; d.nb2 = a.g; d.nb3 = 1; d.sA3 = d.sB3 = d.sC3 = 0; d.nbatch = a.g; d.ksplit = nchunks;
   d.sCi = a.Cg; d.sCj = 1; d.sC1 = 0; d.sC2 = (long)a.M1 * a.Cg; d.alpha = 1.f; d.accumulate = 0; d.out_bf16 = 0;
-  const long total = (long)a.g * a.M1 * a.Cg, nvec = (a.Cg % 4 == 0) ? total / 4 : total;
-  int lgP = 0;
-  while (lgP < 4 && (2 << lgP) <= nchunks && (nvec << lgP) < 131072) ++lgP;
-  const long nwv = (nvec + (64 >> lgP) - 1) / (64 >> lgP);
-  ProfScope ps("gemm_splitk_reduce", total, (double)total * 4.0 * (nchunks + 1), 0.0, stream);
-  hipLaunchKernelGGL(gemm_splitk_reduce<__bf16>, dim3((int)std::min<long>((nwv + 3) / 4, 4096)), dim3(256), 0, stream, d, lgP);
-  AVMOE_CHECK_LAUNCH("gemm_splitk_reduce");
-  return OK;
+  return launch_splitk_reduce(d, true, stream);
 }
 
 }  // namespace avmoe

@@ -571,46 +571,46 @@ int launch_inst(const StreamArgs& s, int nb2, int per_cu, hipStream_t st) {
 // then uses the tiled engine), negative on error.
 int launch_gemm_stream(const GemmArgs& a_in, hipStream_t st) {
   GemmArgs a = a_in;
+  GemmSeg& a2 = a.seg[0];                                  // the second K segment
   bool a2mn = false;
-  if (a.A2 && a.a_layout == MN_MAJOR && a.b_layout == MN_MAJOR && a.s2B1 == 0 && a.sB1 != 0) {
-    // [MN-major A, per-sample B] + [K-major A2, shared B2]  (dY = Bm^T dV + dR^T Q): the shared-B segment becomes the
+  if (a2.A && a.a_layout == MN_MAJOR && a.b_layout == MN_MAJOR && a2.a_layout == K_MAJOR && a2.b_layout == MN_MAJOR && a2.sB1 == 0 && a.sB1 != 0) {
+    // [MN-major A, per-sample B] + [K-major A, shared MN-major B]  (dY = Bm^T dV + dR^T Q): the shared-B segment becomes the
     // stationary first segment, the MN-major one the per-sample second segment
-    std::swap(a.A, a.A2); std::swap(a.B, a.B2); std::swap(a.K, a.K2); std::swap(a.lda, a.lda2); std::swap(a.ldb, a.ldb2);
-    std::swap(a.sA1, a.s2A1); std::swap(a.sA2, a.s2A2); std::swap(a.sB1, a.s2B1); std::swap(a.sB2, a.s2B2);
-    a.a_layout = K_MAJOR; a.b_layout = MN_MAJOR;
+    std::swap<GemmSeg>(a, a2);
     a2mn = true;
   }
+  if (a2.A && (a2.b_layout != MN_MAJOR || (a2.a_layout == MN_MAJOR) != a2mn)) return 1;      // B MN-major; A K-major, or MN-major where the swap has put it
   static const bool dy_whole = dev_env("AVMOE_STREAM_DY_WHOLE") != nullptr;      // dev switch
   if (a2mn && a.nb2 == 1 && a.N > 384 && a.N % 32 == 0 && !a.D && !a.Cx && !dy_whole) {
     // dY over more than 24 column tiles: the two halves of the columns as two "groups" (A shared, B / B2 / C offset by half the
     // columns) -- two tiles per wave instead of four: the 12-wave configuration then has registers for its fragments and for the
     // B2 staging (the four-tile one spills), at the price of reading the skinny A twice
     a.nb2 = 2; a.N /= 2;
-    a.sA2 = 0; a.s2A2 = 0; a.sB2 = a.b_layout == MN_MAJOR ? (long)a.N : (long)a.N * a.ldb; a.s2B2 = a.N; a.sC2 = a.N;
+    a.sA2 = 0; a2.sA2 = 0; a.sB2 = a.b_layout == MN_MAJOR ? (long)a.N : (long)a.N * a.ldb; a2.sB2 = a.N; a.sC2 = a.N;
   }
-  if (a.dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.ksplit > 1 || (a.accumulate && a.out_dtype != GEMM_BF16) || a.sCj != 1 || (long)a.M * a.nb1 < 256 ||
+  if (a.dtype != GEMM_BF16 || a.a_layout != K_MAJOR || a.seg[1].A || a.seg[2].A || a.ksplit > 1 || (a.accumulate && a.out_dtype != GEMM_BF16) || a.sCj != 1 || (long)a.M * a.nb1 < 256 ||
       a.K > 384 || a.N > 768 || (a.nb1 > 1 && (a.sB1 != 0 || a.M < 64)))
     return 1;
-  if (a.A2 && (a.K2 > 96 || a.s2A1 == 0)) return 1;
+  if (a2.A && (a2.K > 96 || a2.sA1 == 0)) return 1;
   if (a.Cx && (a.nb1 != 1 || a.accumulate || a.nsplit % 32 || ((uintptr_t)a.Cx % 16) || a.ldcx % 4 || a.sCx2 % 4)) return 1;
   const int osz = a.out_dtype == GEMM_BF16 ? 2 : 4;
   if (((uintptr_t)a.C % 16) || (a.sCi * osz) % 16 || (a.sC1 * osz) % 16 || (a.sC2 * osz) % 16 || (a.N % 4)) return 1;
   if (a.D && (a.row_scale == nullptr || ((uintptr_t)a.D % 16) || (a.sDi * 2) % 16 || (a.sD1 * 2) % 16 || (a.sD2 * 2) % 16)) return 1;
   if (a.b_layout == K_MAJOR && (((uintptr_t)a.B % 16) || (a.ldb * 2) % 16 || (a.sB2 * 2) % 16)) return 1;
   StreamArgs s;
-  s.A = (const char*)a.A; s.B = (const char*)a.B; s.A2 = (const char*)a.A2; s.B2 = (const char*)a.B2; s.C = (char*)a.C;
+  s.A = (const char*)a.A; s.B = (const char*)a.B; s.A2 = (const char*)a2.A; s.B2 = (const char*)a2.B; s.C = (char*)a.C;
   s.D = (const char*)a.D; s.rs = a.row_scale;
-  s.Mper = a.M; s.nsamp = a.nb1; s.N = a.N; s.K = a.K; s.K2 = a.A2 ? a.K2 : 0;
-  s.lda = a.lda; s.ldb = a.ldb; s.lda2 = a.lda2; s.ldb2 = a.ldb2; s.ldc = a.sCi; s.ldd = a.sDi;
-  s.sA1 = a.sA1; s.sA2 = a.sA2; s.sB2 = a.sB2; s.s2A1 = a.s2A1; s.s2A2 = a.s2A2; s.s2B1 = a.s2B1; s.s2B2 = a.s2B2;
+  s.Mper = a.M; s.nsamp = a.nb1; s.N = a.N; s.K = a.K; s.K2 = a2.A ? a2.K : 0;
+  s.lda = a.lda; s.ldb = a.ldb; s.lda2 = a2.lda; s.ldb2 = a2.ldb; s.ldc = a.sCi; s.ldd = a.sDi;
+  s.sA1 = a.sA1; s.sA2 = a.sA2; s.sB2 = a.sB2; s.s2A1 = a2.sA1; s.s2A2 = a2.sA2; s.s2B1 = a2.sB1; s.s2B2 = a2.sB2;
   s.sC1 = a.sC1; s.sC2 = a.sC2; s.sD1 = a.sD1; s.sD2 = a.sD2; s.sRS1 = a.sRS1; s.sRS2 = a.sRS2;
   s.alpha = a.alpha; s.b_mn = a.b_layout == MN_MAJOR; s.out_bf16 = a.out_dtype == GEMM_BF16;
-  if (a.A2 && (((uintptr_t)a.B2 % 16) || a.ldb2 % 8 || a.s2B1 % 8 || a.s2B2 % 8)) return 1;      // B2 rows are read as 16-byte vectors
-  s.contig = a.A2 != nullptr;
+  if (a2.A && (((uintptr_t)a2.B % 16) || a2.ldb % 8 || a2.sB1 % 8 || a2.sB2 % 8)) return 1;      // its B rows are read as 16-byte vectors
+  s.contig = a2.A != nullptr;
   static const char* contig_env = dev_env("AVMOE_STREAM_CONTIG");          // dev: force the tile-to-block assignment
   if (contig_env) s.contig = atoi(contig_env);
   s.Cx = a.Cx; s.nsplit = a.nsplit; s.ldcx = a.ldcx; s.sCx2 = a.sCx2;
-  const int ks = cdiv(a.K, 32), ks2 = a.A2 ? cdiv(a.K2, 32) : 0, tiles = cdiv(a.N, 16);
+  const int ks = cdiv(a.K, 32), ks2 = a2.A ? cdiv(a2.K, 32) : 0, tiles = cdiv(a.N, 16);
   const double nb = (double)a.nb1 * a.nb2;
   const double abytes = (nb * a.M * (double)(a.K + s.K2) + (double)a.nb2 * a.N * (double)a.K + nb * a.N * (double)s.K2) * 2.0 +
                         nb * a.M * (double)a.N * osz * (a.accumulate ? 2.0 : 1.0) + (a.D ? nb * a.M * (double)a.N * 2.0 : 0.0);
@@ -655,20 +655,20 @@ int launch_gemm_stream(const GemmArgs& a_in, hipStream_t st) {
 #endif
 // (K steps of 32 of segment 1 / 2, column tiles per wave, waves, rows per tile, blocks per CU) -- picked by a sweep on MI355X
 // (scripts/stream_sweep.py): many waves per block and ONE block per CU win for the write-heavy shapes
-  s.st_rows = a.st_rows; s.st_cols = a.st_cols; s.st_ntot = a.st_ntot;
-  s.B3 = (const char*)a.B3; s.C3 = a.C3; s.N3 = a.N3; s.ldb3 = a.ldb3; s.s3B1 = a.s3B1; s.s3B2 = a.s3B2; s.ldc3 = a.ldc3; s.s3C1 = a.s3C1; s.s3C2 = a.s3C2;
-  if (a.B3 && !a.st_rows) return 1;
+  s.st_rows = a.st_rows; s.st_cols = a.st_cols; s.st_ntot = a.st_ntot; const auto& x = a.xcols;
+  s.B3 = (const char*)x.B; s.C3 = x.C; s.N3 = x.N; s.ldb3 = x.ldb; s.s3B1 = x.sB1; s.s3B2 = x.sB2; s.ldc3 = x.ldc; s.s3C1 = x.sC1; s.s3C2 = x.sC2;
+  if (x.B && !a.st_rows) return 1;
   if (a.st_rows) {                  // the product + the statistics of A: the three configurations that serve down projections
-    if (a.A2 || a2mn || a.accumulate || a.D || a.Cx || !a.st_cols || !a.st_tiles || a.out_dtype != GEMM_BF16) return 1;
-    if (a.B3) {                     // + the extra columns against the per-sample B3: the k384_n128 configuration, one more tile per wave
-      if (!a.C3 || a.N3 < 1 || a.N3 > 64 || a.N3 % 4 || a.nb1 < 2 || ((uintptr_t)a.B3 % 16) || (a.ldb3 * 2) % 16 || (a.s3B1 * 2) % 16 || (a.s3B2 * 2) % 16 ||
-          ((uintptr_t)a.C3 % 16) || a.ldc3 % 4 || a.s3C1 % 4 || a.s3C2 % 4 || tiles > 8 || ks > 12 || a.N3 % 16)
+    if (a2.A || a2mn || a.accumulate || a.D || a.Cx || !a.st_cols || !a.st_tiles || a.out_dtype != GEMM_BF16) return 1;
+    if (x.B) {                      // + the extra columns against the per-sample xcols.B: the k384_n128 configuration, one more tile per wave
+      if (!x.C || x.N < 1 || x.N > 64 || x.N % 4 || a.nb1 < 2 || ((uintptr_t)x.B % 16) || (x.ldb * 2) % 16 || (x.sB1 * 2) % 16 || (x.sB2 * 2) % 16 ||
+          ((uintptr_t)x.C % 16) || x.ldc % 4 || x.sC1 % 4 || x.sC2 % 4 || tiles > 8 || ks > 12 || x.N % 16)
         return 1;
       s.contig = 1;                 // (contiguous tile ranges: a block changes sample once or twice)
       if (a.N != 128) return 1;     // (eight stationary tiles + four per-sample ones: twelve waves, one tile each, one 64-row block per CU)
       s.tps = cdiv(a.M, SC_X64_BM); s.ntiles = s.tps * a.nb1; *a.st_tiles = s.tps;
-      const double b3 = nb * a.N3 * (double)a.K * 2.0 + nb * a.M * (double)a.N3 * 4.0;
-      ProfScope ps("gemm_stream_k384_n128+stats+x64", (long)a.M * a.nb1, abytes + b3, flops + 2.0 * nb * a.M * (double)a.N3 * a.K, st);
+      const double b3 = nb * x.N * (double)a.K * 2.0 + nb * a.M * (double)x.N * 4.0;
+      ProfScope ps("gemm_stream_k384_n128+stats+x64", (long)a.M * a.nb1, abytes + b3, flops + 2.0 * nb * a.M * (double)x.N * a.K, st);
       return launch_inst<12, 0, SC_X64_TPW, 12 / SC_X64_TPW, SC_X64_BM, false, false, stream_minw(12 / SC_X64_TPW, SC_X64_PC), true, 1>(s, a.nb2, SC_X64_PC, st);
     }
 #define STATS_CASE(COND, KS_, TPW_, NW_, BM_, PERCU_, NAME)                                                   \

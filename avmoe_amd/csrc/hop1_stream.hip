@@ -379,7 +379,7 @@ bool hop1s_small(long ntok) { return ntok < 32768 && !(test_hook_mask() & HOOK_H
 // a plain product -- alpha 1, overwritten, in one piece, one batch level, bf16 operands, row-major result -- is all three kernels do
 bool hop1_plain(const GemmArgs& a) {
   return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb2 == 1 && a.nb3 == 1 && a.sCj == 1 &&
-         !a.row_scale && !a.D && !a.A2 && !a.A3s && !a.A4s && !a.Cx && !a.st_rows && !a.st_cols && !a.B3 && !a.C3;
+         !a.row_scale && !a.D && !a.seg[0].A && !a.seg[1].A && !a.seg[2].A && !a.Cx && !a.st_rows && !a.st_cols && !a.xcols.B && !a.xcols.C;
 }
 
 }  // namespace

@@ -29,12 +29,12 @@ static const char* at(const char* base, size_t off) { return base ? base + off :
 static void fill_dx_args(GemmArgs& g, const Plan& pl, const void* X, const char* sv, const char* sc, void* dX) {
   const Dims& d = pl.d;
   g.A = at(sc, pl.o_Zw); g.B = at(sv, pl.o_Wt); g.C = dX;
-  g.M = d.N; g.N = d.Cg; g.K = d.E * d.dgp; g.lda = d.DZ; g.b_layout = MN_MAJOR; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
+  g.M = d.N; g.N = d.Cg; g.K = d.E * d.dgp; g.a_layout = K_MAJOR; g.b_layout = MN_MAJOR; g.lda = d.DZ; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
   g.sA1 = (long)d.N * d.DZ; g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg;
   g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.sC2 = d.Cg; g.out_dtype = d.bf16 ? GEMM_BF16 : GEMM_F32;
   g.row_scale = (const float*)at(sc, pl.o_rs2x); g.sRS1 = d.N; g.D = X; g.sDi = d.C; g.sD1 = (long)d.N * d.C; g.sD2 = d.Cg;
-  g.A2 = at(sc, pl.o_dL2x); g.B2 = at(sv, pl.o_Text); g.K2 = d.KLT; g.lda2 = d.KLp; g.ldb2 = d.C;
-  g.s2A1 = (long)d.N * d.KLp; g.s2B1 = (long)d.KLT * d.C; g.s2B2 = d.Cg;
+  GemmSeg& t = g.seg[0]; t.A = at(sc, pl.o_dL2x); t.B = at(sv, pl.o_Text); t.K = d.KLT; t.a_layout = K_MAJOR; t.b_layout = MN_MAJOR; t.lda = d.KLp; t.ldb = d.C;
+  t.sA1 = (long)d.N * d.KLp; t.sB1 = (long)d.KLT * d.C; t.sB2 = d.Cg;
 }
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const void* dOut, const float* lb_grad,
@@ -414,7 +414,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
       g.A = sv + pl.o_BmX; g.B = sc + pl.o_dV; g.C = dY;
       g.M = d.M; g.N = d.Cy; g.K = d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Mb; g.ldb = d.Cy; g.nb1 = d.S;
       g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.Kcyb * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.M * d.Cy; g.out_dtype = dt;
-      g.A2 = sc + pl.o_dRT; g.B2 = sv + pl.o_Qx; g.K2 = d.Kcy; g.lda2 = d.Kcyp; g.ldb2 = d.Cy; g.s2A1 = (long)d.M * d.Kcyp;
+      GemmSeg& q = g.seg[0]; q.A = sc + pl.o_dRT; q.B = sv + pl.o_Qx; q.K = d.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = d.Kcyp; q.ldb = d.Cy; q.sA1 = (long)d.M * d.Kcyp;
       g.accumulate = d.acc_dy;
       leaf(g, 16);
       AVMOE_TRY(run(g, false));
@@ -490,14 +490,15 @@ int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, cons
   const Dims& a = pa.d;
   const Dims& b = pb.d;
   if (a.bf16 != b.bf16 || a.mha || a.nxn || a.Kcx > 0 || b.M != a.N || b.Cy != a.C || b.S != a.S || b.Kcx > 0) return 1;
-  // site A's dX product with site B's  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  as a third and a fourth K segment (gemm.h: A3s ..)
+  // site A's dX product with site B's  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  as a third and a fourth K segment (gemm.h: GemmArgs::seg)
   GemmArgs g; g.dtype = a.bf16 ? GEMM_BF16 : GEMM_F32; g.split3 = (AVMOE_LEAF2 & 16) ? 2 : AVMOE_BWD_PLANES;
   g.slabs = (float*)at(sca, pa.o_slabs);                   // (the streaming form's dump word)
   fill_dx_args(g, pa, X, sva, sca, dX);
-  g.A3s = at(svb, pb.o_BmX); g.B3s = at(scb, pb.o_dV); g.K3s = b.Kcyb; g.lda3s = b.Mb; g.ldb3s = b.Cy;
-  g.s3sA1 = (long)b.Kcyb * b.Mb; g.s3sB1 = (long)b.Kcyb * b.Cy; g.s3sB2 = a.Cg;
+  GemmSeg& v = g.seg[1]; v.A = at(svb, pb.o_BmX); v.B = at(scb, pb.o_dV); v.K = b.Kcyb; v.a_layout = v.b_layout = MN_MAJOR; v.lda = b.Mb; v.ldb = b.Cy;
+  v.sA1 = (long)b.Kcyb * b.Mb; v.sB1 = (long)b.Kcyb * b.Cy; v.sB2 = a.Cg;
   if (b.Kcy > 0) {
-    g.A4s = at(scb, pb.o_dRT); g.B4s = at(svb, pb.o_Qx); g.K4s = b.Kcy; g.lda4s = b.Kcyp; g.ldb4s = b.Cy; g.s4sA1 = (long)b.M * b.Kcyp; g.s4sB1 = 0; g.s4sB2 = a.Cg;
+    GemmSeg& q = g.seg[2]; q.A = at(scb, pb.o_dRT); q.B = at(svb, pb.o_Qx); q.K = b.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = b.Kcyp; q.ldb = b.Cy;
+    q.sA1 = (long)b.M * b.Kcyp; q.sB2 = a.Cg;
   }
   // The streaming form (dx_stream3.hip: the tuned bf16 shape), or, round 6, the same sum on the tiled engine: the token gradient is written
   // once instead of written by site A and read back + added by site B.  fp32 sites only (AVMOE_DXDY_GEN = 1; 3 = bf16 sites of the

@@ -8,7 +8,7 @@
 namespace avmoe {
 
 int choose_ksplit(const GemmArgs& g, size_t slab_floats_cap) {
-  const int tile = (g.tile ? g.tile : ((g.M > 64 && g.N > 64) ? 128 : ((g.M <= 32 && g.N <= 32) ? 32 : 64)));
+  const int tile = g.tile ? g.tile : gemm_auto_tile(g.M, g.N);
   const long nb = (long)g.nb1 * g.nb2 * (g.nb3 > 0 ? g.nb3 : 1);          // (every batch level has its own slabs: gemm_slab_bytes)
   const long tiles = (long)cdiv(g.M, tile) * cdiv(g.N, tile) * nb;
   const int bk = g.dtype == GEMM_BF16 ? 64 : 32;
@@ -58,8 +58,8 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     g.sA1 = (long)d.N * d.C; g.sA2 = d.Cg; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.DZ; g.sC1 = (long)d.N * d.DZ; g.sC2 = (long)d.E * d.dgp;
     g.st_rows = (float*)(sc + pl.o_sxp); g.st_cols = (float*)(sc + pl.o_xpart); g.st_ntot = d.NT; g.st_tiles = &tiles;
     if (d.fuse_l2) {                                       // + L2g[gi][s] = X[s][:, group gi] T[s][:, group gi]^T : the hop-2 logits, per group
-      g.B3 = sv + pl.o_Text; g.N3 = d.KL; g.ldb3 = d.C; g.s3B1 = (long)d.KLT * d.C; g.s3B2 = d.Cg;
-      g.C3 = (float*)(sc + pl.o_L2g); g.ldc3 = d.KL; g.s3C1 = (long)d.N * d.KL; g.s3C2 = (long)d.NT * d.KL;
+      auto& x = g.xcols; x.B = sv + pl.o_Text; x.N = d.KL; x.ldb = d.C; x.sB1 = (long)d.KLT * d.C; x.sB2 = d.Cg;
+      x.C = (float*)(sc + pl.o_L2g); x.ldc = d.KL; x.sC1 = (long)d.N * d.KL; x.sC2 = (long)d.NT * d.KL;
     }
     const int rc = launch_gemm_stream(g, xs);
     if (rc != OK) {
