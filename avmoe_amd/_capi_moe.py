@@ -5,7 +5,8 @@ import ctypes as C
 from typing import Dict, List
 
 MAX_EXPERTS = 16
-OPT_CLIP, OPT_SKIP_NONFINITE, OPT_DECOUPLED_DECAY = 1, 2, 4      # flags of avmoe_opt_grad_norm / avmoe_opt_adam_step
+OPT_CLIP, OPT_SKIP_NONFINITE, OPT_DECOUPLED_DECAY, OPT_LR_SCHEDULE = 1, 2, 4, 8      # flags of avmoe_opt_grad_norm[_sched] / avmoe_opt_adam_step
+SCHED_KINDS = {"none": 0, "cosine": 1, "linear": 2, "step": 3}      # AVMOE_SCHED_*
 VARIANT = {"ave": 0, "avqa": 0, "avvp": 1, "avs": 2}
 SELF_ATTN = {"none": 0, "v2": 1, "nxn": 2, "v1": 3}
 
@@ -28,10 +29,16 @@ class OptLayout(C.Structure):
     _fields_ = [("state_bytes", C.c_size_t), ("table_bytes", C.c_size_t), ("partial_bytes", C.c_size_t), ("n_blocks", C.c_int64)]
 
 
+class OptSchedule(C.Structure):
+    """avmoe_opt_schedule: the host constants of a per-step learning-rate schedule"""
+    _fields_ = [("warmup_steps", C.c_int64), ("warmup_start", C.c_float), ("decay_kind", C.c_int32), ("total_steps", C.c_int64),
+                ("min_factor", C.c_float), ("gamma", C.c_float), ("step_size", C.c_int64)]
+
+
 # avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
 OPT_STATE_BYTES = 64
 OPT_STATE_FIELDS = {"total_norm": (0, "float32"), "clip_coef": (4, "float32"), "bc1": (8, "float32"), "bc2_sqrt": (12, "float32"),
-                    "applied_steps": (16, "int64"), "skipped_steps": (24, "int64"), "skip": (32, "int32")}
+                    "applied_steps": (16, "int64"), "skipped_steps": (24, "int64"), "skip": (32, "int32"), "lr_factor": (36, "float32")}
 
 
 _EXPERT_FIELDS = ("gate", "my_tokens", "gate_lat", "down_w", "up_w", "bn1_w", "bn1_b", "bn2_w", "bn2_b",
@@ -126,6 +133,9 @@ def declare(L):
         L.avmoe_opt_adam_step.restype = C.c_int
         L.avmoe_opt_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_int32, C.c_void_p]
+    if hasattr(L, "avmoe_opt_grad_norm_sched"):      # (found by symbol: the per-step learning-rate schedule)
+        L.avmoe_opt_grad_norm_sched.restype = C.c_int
+        L.avmoe_opt_grad_norm_sched.argtypes = L.avmoe_opt_grad_norm.argtypes + [C.POINTER(OptSchedule)]
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

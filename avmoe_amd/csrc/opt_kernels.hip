@@ -3,7 +3,7 @@
 // buckets and ranges --
 //   kk_opt_sqsum     sum of (grad * grad_scale)^2 per 1024-element block, in double, into the partial-sum workspace
 //   kk_opt_finalize  one block adds the partial sums in a fixed order and writes the state block: norm, clip factor, skip flag, step
-//                    counters, bias corrections
+//                    counters, bias corrections (kk_opt_finalize_sched: and the learning-rate factor of a per-step schedule)
 //   kk_opt_adam      the Adam / AdamW update of every range; reads the state block, writes nothing when the step is skipped
 // Plain bandwidth kernels: 16-byte loads and stores, no matrix pipe, LDS only for the block reduction.  No floating-point atomics: the norm
 // repeats bit for bit.
@@ -61,10 +61,32 @@ __global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ tab
   if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
+// the factor of a per-step schedule at n applied steps (include/avmoe.h, avmoe_opt_schedule), in double.  Contraction is off so that the
+// expression rounds like the same closed form written on a host (LRSchedule.factor in avmoe_amd/train.py).
+__device__ __forceinline__ double sched_factor(const avmoe_opt_schedule& s, int64_t n) {
+#pragma clang fp contract(off)
+  const int64_t W = s.warmup_steps;
+  if (n < W) {
+    const double s0 = (double)s.warmup_start;
+    return s0 + (1.0 - s0) * (double)n / (double)W;
+  }
+  const int64_t u = n - W, D = s.total_steps - W, c = u < D ? u : D;
+  const double fmin = (double)s.min_factor;
+  switch (s.decay_kind) {
+    case AVMOE_SCHED_COSINE: return fmin + (1.0 - fmin) * 0.5 * (1.0 + cos(M_PI * (double)c / (double)D));
+    case AVMOE_SCHED_LINEAR: return 1.0 - (1.0 - fmin) * (double)c / (double)D;
+    case AVMOE_SCHED_STEP: return pow((double)s.gamma, (double)(u / s.step_size));
+    default: return 1.0;
+  }
+}
+
 // One block.  Thread t adds partials[t], partials[t + 256], ... in that order, the 256 sums go through the same tree as above: a fixed
 // order.  n_partials == 0 (neither clipping nor skipping asked for): the norm is reported as 0 and only the counters advance.
-__global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
-                                                       float max_norm, int clip, int skip_nonfinite, float beta1, float beta2) {
+// SCHED: the step that is applied now is number n = applied_steps before it (the first one has n = 0); its factor goes into the state
+// block, rounded once to fp32.  A skipped step leaves the factor alone.
+template <bool SCHED>
+__device__ __forceinline__ void opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state, float max_norm,
+                                             int clip, int skip_nonfinite, float beta1, float beta2, const avmoe_opt_schedule& sched) {
   __shared__ double red[256];
   double acc = 0.0;
   for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
@@ -83,7 +105,7 @@ __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict_
     coef = c < 1.0f ? c : (c != c ? c : 1.0f);
   }
   const int skip = (skip_nonfinite && !isfinite(total)) ? 1 : 0;
-  const int64_t applied = state->applied_steps + (skip ? 0 : 1);
+  const int64_t before = state->applied_steps, applied = before + (skip ? 0 : 1);
   state->total_norm = total;
   state->clip_coef = coef;
   state->skip = skip;
@@ -92,11 +114,27 @@ __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict_
   const double bc1 = 1.0 - pow((double)beta1, (double)applied), bc2 = 1.0 - pow((double)beta2, (double)applied);
   state->bc1 = (float)bc1;
   state->bc2_sqrt = (float)sqrt(bc2);
+  if constexpr (SCHED) {
+    if (!skip) state->lr_factor = (float)sched_factor(sched, before);
+  }
 }
 
-template <bool DECOUPLED>
-__global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
-                                                   float eps, float grad_scale) {
+__global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
+                                                       float max_norm, int clip, int skip_nonfinite, float beta1, float beta2) {
+  opt_finalize<false>(partials, n_partials, state, max_norm, clip, skip_nonfinite, beta1, beta2, avmoe_opt_schedule{});
+}
+
+// the schedule rides in the kernel arguments: constants of the run, so a captured launch replays them
+__global__ void __launch_bounds__(256) kk_opt_finalize_sched(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
+                                                             float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
+                                                             avmoe_opt_schedule sched) {
+  opt_finalize<true>(partials, n_partials, state, max_norm, clip, skip_nonfinite, beta1, beta2, sched);
+}
+
+// SCHED: the range's rate times the state block's lr_factor, for the update and for the decoupled decay term alike
+template <bool DECOUPLED, bool SCHED>
+__device__ __forceinline__ void opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2, float eps,
+                                         float grad_scale) {
   const OptHeader h = *(const OptHeader*)table;
   if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return;
   if (state->skip) return;                              // a skipped step writes nothing: p, m, v stay bit for bit
@@ -105,9 +143,23 @@ __global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ tabl
   const avmoe_opt_range r = opt_ranges(table)[b.range];
   const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
   if (i0 >= r.n) return;
+  float lr = r.lr;
+  if constexpr (SCHED) lr *= state->lr_factor;
   // one multiplier for the gradient: grad_scale * clip factor (== grad_scale exactly when the factor is 1)
-  adam_quad<DECOUPLED>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, i0, (long)r.n, r.lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
+  adam_quad<DECOUPLED>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
                        grad_scale * state->clip_coef);
+}
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                   float eps, float grad_scale) {
+  opt_adam<DECOUPLED, false>(table, state, b1, b2, eps, grad_scale);
+}
+
+template <bool DECOUPLED>
+__global__ void __launch_bounds__(256) kk_opt_adam_sched(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                         float eps, float grad_scale) {
+  opt_adam<DECOUPLED, true>(table, state, b1, b2, eps, grad_scale);
 }
 
 static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
@@ -144,6 +196,55 @@ static int check_launch_args(const char* who, const void* table, int32_t n_range
   if (((uintptr_t)state & 15u) != 0) { set_last_error("%s: the state block must be 16-byte aligned", who); return ERR_BAD_ARG; }
   if (((uintptr_t)table & 15u) != 0) { set_last_error("%s: the table must be 16-byte aligned", who); return ERR_ALIGNMENT; }
   if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) { set_last_error("%s: betas must be in [0, 1)", who); return ERR_BAD_ARG; }
+  return OK;
+}
+
+// host-side validation of a schedule: everything the finalize kernel divides by or raises to a power
+static int check_schedule(const char* who, const avmoe_opt_schedule* s) {
+  if (!s) { set_last_error("%s: AVMOE_OPT_LR_SCHEDULE without a schedule", who); return ERR_BAD_ARG; }
+  if (s->warmup_steps < 0 || s->total_steps < 0 || s->step_size < 0) { set_last_error("%s: negative warmup_steps / total_steps / step_size", who); return ERR_BAD_ARG; }
+  if (!(s->warmup_start >= 0.f && s->warmup_start <= 1.f) || !(s->min_factor >= 0.f && s->min_factor <= 1.f)) {
+    set_last_error("%s: warmup_start and min_factor must be in [0, 1]", who); return ERR_BAD_ARG;
+  }
+  if (!(s->gamma > 0.f && s->gamma <= 1.f)) { set_last_error("%s: gamma must be in (0, 1]", who); return ERR_BAD_ARG; }
+  switch (s->decay_kind) {
+    case AVMOE_SCHED_NONE: break;
+    case AVMOE_SCHED_COSINE: case AVMOE_SCHED_LINEAR:
+      if (s->total_steps <= s->warmup_steps) { set_last_error("%s: total_steps must be larger than warmup_steps for a cosine / linear decay", who); return ERR_BAD_ARG; }
+      break;
+    case AVMOE_SCHED_STEP:
+      if (s->step_size <= 0) { set_last_error("%s: step_size must be positive for a step decay", who); return ERR_BAD_ARG; }
+      break;
+    default: set_last_error("%s: unknown decay_kind %d", who, (int)s->decay_kind); return ERR_BAD_ARG;
+  }
+  return OK;
+}
+
+constexpr int32_t OPT_FLAGS = AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY;
+
+// avmoe_opt_grad_norm (sched == NULL) and avmoe_opt_grad_norm_sched: the same checks and the same norm launch, then one of the two finalize kernels
+static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                     float max_norm, int32_t flags, int32_t known_flags, float beta1, float beta2, const avmoe_opt_schedule* sched, void* stream) {
+  AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
+  const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
+  if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
+  if (clip && !(max_norm >= 0.f)) { set_last_error("%s: max_norm must be >= 0 and not NaN", who); return ERR_BAD_ARG; }
+  if (!(grad_scale == grad_scale)) { set_last_error("%s: grad_scale is NaN", who); return ERR_BAD_ARG; }
+  if (flags & AVMOE_OPT_LR_SCHEDULE) AVMOE_TRY(check_schedule(who, sched));
+  const bool norm = (clip || skip) && n_blocks > 0;
+  if (norm) {
+    if (!partials) { set_last_error("%s: partials is NULL", who); return ERR_BAD_ARG; }
+    if (((uintptr_t)partials & 7u) != 0) { set_last_error("%s: partials must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+    hipLaunchKernelGGL(kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials, grad_scale);
+    AVMOE_CHECK_LAUNCH("opt_sqsum");
+  }
+  if (flags & AVMOE_OPT_LR_SCHEDULE)
+    hipLaunchKernelGGL(kk_opt_finalize_sched, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state,
+                       max_norm, (int)clip, (int)skip, beta1, beta2, *sched);
+  else
+    hipLaunchKernelGGL(kk_opt_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state, max_norm,
+                       (int)clip, (int)skip, beta1, beta2);
+  AVMOE_CHECK_LAUNCH("opt_finalize");
   return OK;
 }
 
@@ -184,31 +285,27 @@ int avmoe_opt_table_build(const avmoe_opt_range* ranges, int32_t n_ranges, void*
 
 int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                         float max_norm, int32_t flags, float beta1, float beta2, void* stream) {
-  AVMOE_TRY(check_launch_args("avmoe_opt_grad_norm", table, n_ranges, n_blocks, state, beta1, beta2));
-  const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
-  if ((flags & ~(AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY)) != 0) { set_last_error("avmoe_opt_grad_norm: unknown flag"); return ERR_BAD_ARG; }
-  if (clip && !(max_norm >= 0.f)) { set_last_error("avmoe_opt_grad_norm: max_norm must be >= 0 and not NaN"); return ERR_BAD_ARG; }
-  if (!(grad_scale == grad_scale)) { set_last_error("avmoe_opt_grad_norm: grad_scale is NaN"); return ERR_BAD_ARG; }
-  const bool norm = (clip || skip) && n_blocks > 0;
-  if (norm) {
-    if (!partials) { set_last_error("avmoe_opt_grad_norm: partials is NULL"); return ERR_BAD_ARG; }
-    if (((uintptr_t)partials & 7u) != 0) { set_last_error("avmoe_opt_grad_norm: partials must be 8-byte aligned"); return ERR_ALIGNMENT; }
-    hipLaunchKernelGGL(kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials, grad_scale);
-    AVMOE_CHECK_LAUNCH("opt_sqsum");
-  }
-  hipLaunchKernelGGL(kk_opt_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state, max_norm,
-                     (int)clip, (int)skip, beta1, beta2);
-  AVMOE_CHECK_LAUNCH("opt_finalize");
-  return OK;
+  return grad_norm("avmoe_opt_grad_norm", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS, beta1, beta2, nullptr, stream);
+}
+
+int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                              float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched) {
+  return grad_norm("avmoe_opt_grad_norm_sched", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE,
+                   beta1, beta2, sched, stream);
 }
 
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
                         float grad_scale, int32_t flags, void* stream) {
   AVMOE_TRY(check_launch_args("avmoe_opt_adam_step", table, n_ranges, n_blocks, state, beta1, beta2));
-  if ((flags & ~(AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY)) != 0) { set_last_error("avmoe_opt_adam_step: unknown flag"); return ERR_BAD_ARG; }
+  if ((flags & ~(OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE)) != 0) { set_last_error("avmoe_opt_adam_step: unknown flag"); return ERR_BAD_ARG; }
   if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("avmoe_opt_adam_step: eps must be >= 0, grad_scale not NaN"); return ERR_BAD_ARG; }
   if (n_blocks == 0) return OK;
-  if (flags & AVMOE_OPT_DECOUPLED_DECAY)
+  const bool sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0;
+  if (sched && (flags & AVMOE_OPT_DECOUPLED_DECAY))
+    hipLaunchKernelGGL(kk_opt_adam_sched<true>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);
+  else if (sched)
+    hipLaunchKernelGGL(kk_opt_adam_sched<false>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);
+  else if (flags & AVMOE_OPT_DECOUPLED_DECAY)
     hipLaunchKernelGGL(kk_opt_adam<true>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);
   else
     hipLaunchKernelGGL(kk_opt_adam<false>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale);

@@ -7,17 +7,22 @@
                                Opt-in: global-norm clipping, AdamW, skipping of non-finite steps with the optimizer state on
                                the device (three launches per step for all buckets, graph-capturable); state_dict() /
                                load_state_dict() in torch.optim.Adam's format
+  * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
+                               device path evaluates on the device from its own step counter
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
                                site), main_trans_v3.py:155-226
   * `save_adapters` / `load_adapters` / `strip_prefix` -- adapter-only checkpoints with the reference's state_dict keys
                                (strict=False load of released checkpoints, main_trans_v3.py:254; HTS-AT key strip,
                                net_trans_v3.py:560-563)
 
-Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm / avmoe_opt_adam_step,
+Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched] / avmoe_opt_adam_step,
 avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import math
+import struct
 from itertools import chain
 from typing import Dict, Iterable, List, Optional
 
@@ -47,6 +52,81 @@ def select_trainable(model: torch.nn.Module, lr: float, lr_mlp: float, is_vit_ln
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+@dataclasses.dataclass
+class LRSchedule:
+    """A per-step learning-rate schedule as a factor f(n) on every learning rate, n = the number of steps applied before this one (the
+    first step has n = 0): avmoe_opt_schedule of include/avmoe.h.
+
+        n <  warmup_steps:  f = warmup_start + (1 - warmup_start) * n / warmup_steps
+        after, with u = n - warmup_steps, D = total_steps - warmup_steps, c = min(u, D):
+            "cosine"  f = min_factor + (1 - min_factor) * (1 + cos(pi c / D)) / 2
+            "linear"  f = 1 - (1 - min_factor) * c / D
+            "step"    f = gamma ** (u // step_size)
+            "none"    f = 1
+
+    Cosine and linear stay at min_factor from total_steps on.  The device holds warmup_start, min_factor and gamma as fp32 and
+    evaluates f in double from them; the constructor therefore rounds these three to fp32 (0.1 becomes 0.10000000149...), so that
+    `factor(n)` is the very function the kernel computes and agrees with it to the final fp32 rounding.  A bad schedule raises
+    ValueError here, with the rules the library checks again."""
+    warmup_steps: int = 0
+    warmup_start: float = 0.0
+    decay_kind: str = "none"
+    total_steps: int = 0
+    min_factor: float = 0.0
+    step_size: int = 0
+    gamma: float = 1.0
+
+    def __post_init__(self):
+        kinds = cm.SCHED_KINDS
+        if isinstance(self.decay_kind, int) and not isinstance(self.decay_kind, bool) and self.decay_kind in kinds.values():
+            self.decay_kind = {v: k for k, v in kinds.items()}[self.decay_kind]
+        if self.decay_kind not in kinds:
+            raise ValueError(f"decay_kind must be one of {sorted(kinds)}, not {self.decay_kind!r}")
+        for name in ("warmup_steps", "total_steps", "step_size"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0, not {v!r}")
+            setattr(self, name, int(v))
+        for name in ("warmup_start", "min_factor"):
+            v = float(getattr(self, name))
+            if not (0.0 <= v <= 1.0):
+                raise ValueError(f"{name} must be in [0, 1], not {v!r}")
+            setattr(self, name, _f32(v))
+        g = float(self.gamma)
+        if not (0.0 < g <= 1.0) or _f32(g) == 0.0:
+            raise ValueError(f"gamma must be in (0, 1], not {g!r}")
+        self.gamma = _f32(g)
+        if self.decay_kind in ("cosine", "linear") and self.total_steps <= self.warmup_steps:
+            raise ValueError(f"a {self.decay_kind} decay needs total_steps > warmup_steps, not {self.total_steps} <= {self.warmup_steps}")
+        if self.decay_kind == "step" and self.step_size <= 0:
+            raise ValueError("a step decay needs step_size > 0")
+
+    def factor(self, n: int) -> float:
+        """f(n) in Python float (double), the closed form of the class docstring in the operation order of the kernel"""
+        n, W = int(n), self.warmup_steps
+        if n < W:
+            return self.warmup_start + (1.0 - self.warmup_start) * n / W
+        u = n - W
+        if self.decay_kind == "none":
+            return 1.0
+        if self.decay_kind == "step":
+            return self.gamma ** (u // self.step_size)
+        D = self.total_steps - W
+        c = min(u, D)
+        if self.decay_kind == "cosine":
+            return self.min_factor + (1.0 - self.min_factor) * 0.5 * (1.0 + math.cos(math.pi * c / D))
+        return 1.0 - (1.0 - self.min_factor) * c / D
+
+    def c_struct(self) -> "cm.OptSchedule":
+        return cm.OptSchedule(warmup_steps=self.warmup_steps, warmup_start=self.warmup_start, decay_kind=cm.SCHED_KINDS[self.decay_kind],
+                              total_steps=self.total_steps, min_factor=self.min_factor, gamma=self.gamma, step_size=self.step_size)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 class FlatAdam:
     """Adam over the flat fp32 buckets of an AdapterGradReducer: per bucket ONE kernel updates parameters, exp_avg and
     exp_avg_sq in place (avmoe_adam_step).  Parameters of a bucket are moved into one flat buffer with the bucket's layout
@@ -70,9 +150,17 @@ class FlatAdam:
     parallelism call `red.finish()` first: the norm is then that of the averaged gradient, identical on every rank.
     `last_grad_norm`, `applied_steps`, `skipped_steps` are DEVICE tensors (views of the state block): reading them is the caller's sync.
 
+    A per-step schedule.  `lr_schedule=LRSchedule(...)` (it selects the device path too) multiplies every learning rate by f(applied_steps):
+    the finalize launch evaluates f in double from the counter it already advances and leaves it in the state block (`last_lr_factor`),
+    the update reads it.  Still three launches and no step-dependent host scalar, so a captured step follows the schedule on replay; a
+    skipped step does not advance it.  It composes multiplicatively with the per-epoch StepLR (`step_size` / `gamma`, `epoch_end()`) and
+    the per-group rates, which stay in the range table.
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
-    counters, options) that torch ignores.  Index i is the position of the parameter in `opt.params` -- the order in which the reducer
+    counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
+    f(applied_steps), and "initial_lr" stays lr0 -- what a torch optimizer + scheduler pair saves; nothing but `applied_steps` is needed
+    to continue the schedule.  Index i is the position of the parameter in `opt.params` -- the order in which the reducer
     holds the parameters: bucket by bucket, inside a bucket the sites in reverse execution order with each site's parameters in its
     grad_layout() order, then the plain parameters in reverse order.  A torch optimizer built as
     `torch.optim.AdamW(opt.torch_param_groups())` (or `Adam`) loads the dict, and a dict from such an optimizer loads here.
@@ -80,10 +168,12 @@ class FlatAdam:
 
     def __init__(self, reducer, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
-                 max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
+                 lr_schedule: Optional[LRSchedule] = None):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
-        term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  Any of the three
-        selects the device path (class docstring); with all three at their defaults step() is the per-bucket avmoe_adam_step path.
+        term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
+        per-step LRSchedule evaluated on the device.  Any of the four selects the device path (class docstring); with all at their
+        defaults step() is the per-bucket avmoe_adam_step path.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
         reference's `lr_mlp` for the classifier head vs `lr` for the adapters); parameters not listed use `lr`.  Inside a
@@ -96,6 +186,9 @@ class FlatAdam:
             raise ValueError("max_grad_norm must be >= 0")
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.decoupled_weight_decay, self.skip_nonfinite = bool(decoupled_weight_decay), bool(skip_nonfinite)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise TypeError("lr_schedule must be an avmoe_amd.train.LRSchedule")
+        self.lr_schedule = lr_schedule
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
         lr_of = {}
         for grp in (param_groups or []):
@@ -118,7 +211,7 @@ class FlatAdam:
                 self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
         self._rebuild_plain_ranges()
-        self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite
+        self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None
         if self._device:
             self._build_device_state()
 
@@ -136,6 +229,8 @@ class FlatAdam:
         L = capi.lib()
         if not hasattr(L, "avmoe_opt_adam_step"):
             raise capi.AvmoeError("this libavmoe_hip.so lacks the device-side optimizer (avmoe_opt_*): rebuild it")
+        if self.lr_schedule is not None and not hasattr(L, "avmoe_opt_grad_norm_sched"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks the per-step schedule (avmoe_opt_grad_norm_sched): rebuild it")
         devs = {s["p"].device for s in self.state}
         if len(devs) != 1:
             raise capi.AvmoeError("FlatAdam's device path needs every bucket on one GPU")
@@ -153,7 +248,14 @@ class FlatAdam:
                        for k, (o, dt) in cm.OPT_STATE_FIELDS.items()}
         self._flags = (cm.OPT_CLIP if self.max_grad_norm is not None else 0) | (cm.OPT_SKIP_NONFINITE if self.skip_nonfinite else 0) \
             | (cm.OPT_DECOUPLED_DECAY if self.decoupled_weight_decay else 0)
+        self._set_schedule(self.lr_schedule)
         self._upload_table()
+
+    def _set_schedule(self, sched: Optional[LRSchedule]):
+        """the schedule as the struct step() hands over, and its flag"""
+        self.lr_schedule = sched
+        self._sched_c = None if sched is None else sched.c_struct()
+        self._flags = (self._flags & ~cm.OPT_LR_SCHEDULE) | (cm.OPT_LR_SCHEDULE if sched is not None else 0)
 
     def _upload_table(self):
         """(re)build the range table with the learning rates of the current epoch and send it with ONE asynchronous copy"""
@@ -187,9 +289,17 @@ class FlatAdam:
         return self._state_view("skipped_steps")
 
     @property
+    def last_lr_factor(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the schedule's factor f(n) the last applied step used (a skipped step leaves it).  A view of the state
+        block, like `last_grad_norm`; only with `lr_schedule`."""
+        if self.lr_schedule is None:
+            raise capi.AvmoeError("FlatAdam.last_lr_factor needs lr_schedule")
+        return self._state_view("lr_factor")
+
+    @property
     def state_block(self) -> Dict[str, torch.Tensor]:
         """every field of the device state block (avmoe_opt_state) as a DEVICE scalar view: total_norm, clip_coef, bc1, bc2_sqrt,
-        applied_steps, skipped_steps, skip"""
+        applied_steps, skipped_steps, skip, lr_factor (written only with `lr_schedule`)"""
         self._state_view("total_norm")
         return dict(self._views)
 
@@ -227,9 +337,14 @@ class FlatAdam:
         if self._device:                                 # every bucket at once, scalars from the device state block
             stream = torch.cuda.current_stream(self._dev).cuda_stream
             n = len(self._plist)
-            capi.check(L.avmoe_opt_grad_norm(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
-                                             self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream),
-                       "avmoe_opt_grad_norm")
+            if self._sched_c is not None:                # the same launches; the finalize kernel also evaluates f(applied_steps)
+                capi.check(L.avmoe_opt_grad_norm_sched(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                                       self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
+                                                       C.byref(self._sched_c)), "avmoe_opt_grad_norm_sched")
+            else:
+                capi.check(L.avmoe_opt_grad_norm(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                                 self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream),
+                           "avmoe_opt_grad_norm")
             capi.check(L.avmoe_opt_adam_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
                                              self.eps, scale, self._flags, stream), "avmoe_opt_adam_step")
             return
@@ -259,16 +374,20 @@ class FlatAdam:
             state[i] = {"step": torch.tensor(float(applied)),
                         "exp_avg": s["m"][off:off + n].view_as(p).detach().cpu().clone(),
                         "exp_avg_sq": s["v"][off:off + n].view_as(p).detach().cpu().clone()}
-        groups = [{"lr": lr0 * self.decay, "initial_lr": lr0, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
-                   "params": list(idx)} for lr0, idx in self._groups()]
+        f = self.lr_schedule.factor(applied) if self.lr_schedule is not None else None      # the rate of the next step
+        groups = [{"lr": lr0 * self.decay if f is None else lr0 * self.decay * f, "initial_lr": lr0, "betas": tuple(self.betas), "eps": self.eps,
+                   "weight_decay": self.wd, "params": list(idx)} for lr0, idx in self._groups()]
         extra = {"t": self.t, "epoch": self.epoch, "applied_steps": applied, "skipped_steps": skipped,
                  "max_grad_norm": self.max_grad_norm, "decoupled_weight_decay": self.decoupled_weight_decay,
                  "skip_nonfinite": self.skip_nonfinite, "step_size": self.step_size, "gamma": self.gamma}
+        if self.lr_schedule is not None:
+            extra["lr_schedule"] = dataclasses.asdict(self.lr_schedule)
         return {"state": state, "param_groups": groups, "flat_adam": extra}
 
     def load_state_dict(self, sd: dict):
         """Writes the moments into the flat buffers, the counters into the state block, and restores t, epoch and the groups' lr / betas /
-        eps / weight_decay.  Saved parameters are matched to `self.params` by position across the groups, as torch.optim does; the three
+        eps / weight_decay.  A saved per-step schedule replaces the one the constructor was given (device path only: on the plain path it
+        raises); with the saved `applied_steps` the run continues it.  Saved parameters are matched to `self.params` by position across the groups, as torch.optim does; the three
         path options stay what the constructor was given (the saved ones are informative), unknown keys are ignored.  A count or shape
         mismatch raises ValueError naming the parameter index."""
         saved_groups, own_groups = sd["param_groups"], self._groups()
@@ -299,6 +418,14 @@ class FlatAdam:
             raise ValueError(f"parameters carry different step counts {sorted(steps)}: FlatAdam keeps one count for all")
         extra = sd.get("flat_adam", {})
         applied = int(extra.get("applied_steps", steps.pop() if steps else 0))
+        saved_sched = extra.get("lr_schedule")
+        if saved_sched is not None:
+            if not self._device:
+                raise ValueError("the state dict carries a per-step lr_schedule, which needs FlatAdam's device path: build the optimizer "
+                                 "with lr_schedule (or max_grad_norm / decoupled_weight_decay / skip_nonfinite)")
+            if not hasattr(capi.lib(), "avmoe_opt_grad_norm_sched"):
+                raise capi.AvmoeError("this libavmoe_hip.so lacks the per-step schedule (avmoe_opt_grad_norm_sched): rebuild it")
+            saved_sched = saved_sched if isinstance(saved_sched, LRSchedule) else LRSchedule(**saved_sched)
         with torch.no_grad():
             if not todo:
                 for s in self.state:
@@ -312,6 +439,10 @@ class FlatAdam:
             self.step_size, self.gamma = extra.get("step_size", self.step_size), extra.get("gamma", self.gamma)
             g0 = saved_groups[0]
             self.betas, self.eps, self.wd = tuple(g0.get("betas", self.betas)), g0.get("eps", self.eps), g0.get("weight_decay", self.wd)
+            if saved_sched is not None:
+                self._set_schedule(saved_sched)
+            # a dict without initial_lr comes from a torch optimizer that never had a scheduler: its lr is a base rate, whatever the
+            # schedule here says (every dict FlatAdam or a torch scheduler wrote carries initial_lr)
             lr0s = [float(sg["initial_lr"]) if "initial_lr" in sg else float(sg["lr"]) / self.decay for sg in saved_groups]
             for (lr_old, idx), lr_new in zip(own_groups, lr0s):
                 for i in idx:
@@ -323,6 +454,8 @@ class FlatAdam:
                 self.t = int(extra.get("t", applied + int(extra.get("skipped_steps", 0))))
                 self._views["applied_steps"].fill_(applied)
                 self._views["skipped_steps"].fill_(int(extra.get("skipped_steps", 0)))
+                if self.lr_schedule is not None:           # what the last applied step used; the next applied step writes its own
+                    self._views["lr_factor"].fill_(self.lr_schedule.factor(applied - 1) if applied > 0 else 0.0)
                 self._upload_table()
             else:
                 self.t = applied                          # the plain path's bias correction counts self.t

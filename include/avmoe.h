@@ -307,12 +307,13 @@ typedef struct avmoe_opt_state {
   int64_t applied_steps;      /* steps that updated the parameters */
   int64_t skipped_steps;      /* steps held back because the norm was not finite */
   int32_t skip;               /* this step is held back */
-  int32_t reserved[7];
+  float lr_factor;            /* AVMOE_OPT_LR_SCHEDULE: the schedule's factor of the last applied step (below); never written without the flag */
+  int32_t reserved[6];
 } avmoe_opt_state;
 
 typedef struct avmoe_opt_layout { size_t state_bytes, table_bytes, partial_bytes; int64_t n_blocks; } avmoe_opt_layout;
 
-enum { AVMOE_OPT_CLIP = 1, AVMOE_OPT_SKIP_NONFINITE = 2, AVMOE_OPT_DECOUPLED_DECAY = 4 };
+enum { AVMOE_OPT_CLIP = 1, AVMOE_OPT_SKIP_NONFINITE = 2, AVMOE_OPT_DECOUPLED_DECAY = 4, AVMOE_OPT_LR_SCHEDULE = 8 };
 
 size_t avmoe_opt_workspace_bytes(const avmoe_opt_range* ranges /* HOST */, int32_t n_ranges, avmoe_opt_layout* layout /* HOST, or NULL */);
 int avmoe_opt_table_build(const avmoe_opt_range* ranges /* HOST */, int32_t n_ranges, void* image /* HOST, layout.table_bytes */,
@@ -322,7 +323,8 @@ int avmoe_opt_table_build(const avmoe_opt_range* ranges /* HOST */, int32_t n_ra
  * leaves one double per block in `partials` (layout.partial_bytes); one more launch of a single block adds them in a fixed order -- no
  * floating-point atomics, the same input gives the same bits -- and its last thread writes the state block:
  *     total_norm, clip_coef (AVMOE_OPT_CLIP; max_norm >= 0), skip = AVMOE_OPT_SKIP_NONFINITE && !isfinite(total_norm),
- *     applied_steps += !skip, skipped_steps += skip, bc1, bc2_sqrt for the new applied_steps.
+ *     applied_steps += !skip, skipped_steps += skip, bc1, bc2_sqrt for the new applied_steps
+ * (and lr_factor under AVMOE_OPT_LR_SCHEDULE: avmoe_opt_grad_norm_sched below).
  * With neither flag the norm launch is left out (total_norm = 0) and only the counters and bias corrections advance.  The sum is exact
  * to double rounding, so total_norm is the true norm to two fp32 roundings.  `table`, n_ranges, n_blocks: the image on the device and
  * what it was built for (a kernel whose grid does not match its table's header does nothing).
@@ -340,6 +342,42 @@ int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, d
                         float max_norm, int32_t flags, float beta1, float beta2, void* stream);
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
                         float eps, float grad_scale, int32_t flags, void* stream);
+
+/* A per-step learning-rate schedule evaluated on the device (added under ABI 11 like the block above; found by symbol).  The schedule is
+ * a function of applied_steps alone, so it costs no launch and no host scalar that changes from step to step: a scheduled step stays 3
+ * launches (2 without a norm) and replays from a captured graph, and a step that is skipped holds the schedule back by itself.
+ * avmoe_opt_schedule holds HOST constants that are fixed for a run.  With n = applied_steps before this update (the first applied step
+ * has n = 0), W = warmup_steps, s0 = warmup_start, fmin = min_factor:
+ *     n <  W:  f = s0 + (1 - s0) * n / W
+ *     n >= W:  u = n - W, D = total_steps - W, c = min(u, D)
+ *              AVMOE_SCHED_COSINE  f = fmin + (1 - fmin) * 0.5 * (1 + cos(pi * c / D))
+ *              AVMOE_SCHED_LINEAR  f = 1 - (1 - fmin) * c / D
+ *              AVMOE_SCHED_STEP    f = gamma ^ (u / step_size), integer division
+ *              AVMOE_SCHED_NONE    f = 1
+ * avmoe_opt_grad_norm_sched is avmoe_opt_grad_norm with one more argument; with AVMOE_OPT_LR_SCHEDULE in `flags` its finalize step
+ * evaluates f in double from the fp32 constants, rounds it once to fp32 and writes state->lr_factor (a skipped step leaves it as it
+ * was); without the flag `sched` is not read and the call is avmoe_opt_grad_norm.  avmoe_opt_adam_step with the flag then uses
+ * lr * lr_factor in place of each range's lr, in the update and in the decoupled decay term alike; f = 1 gives the bits of the
+ * unscheduled step.  Pass the flag to both calls of a step.  avmoe_opt_grad_norm itself refuses the flag (it has no schedule), and
+ * without the flag both entry points launch what they did before and write the same bits.
+ * Errors (AVMOE_ERR_BAD_ARG, before any launch): the flag with sched == NULL, a negative warmup_steps / total_steps / step_size,
+ * warmup_start or min_factor outside [0, 1] or NaN, gamma outside (0, 1] or NaN, total_steps <= warmup_steps for COSINE / LINEAR,
+ * step_size <= 0 for STEP, an unknown decay_kind.  The fields are ordered so that the struct packs into 40 bytes without padding
+ * (gamma ahead of step_size).                                                                                     */
+enum { AVMOE_SCHED_NONE = 0, AVMOE_SCHED_COSINE = 1, AVMOE_SCHED_LINEAR = 2, AVMOE_SCHED_STEP = 3 };
+
+typedef struct avmoe_opt_schedule {
+  int64_t warmup_steps;       /* W: steps of linear warm-up from warmup_start to 1 (0: none) */
+  float warmup_start;         /* s0 in [0, 1] */
+  int32_t decay_kind;         /* AVMOE_SCHED_* */
+  int64_t total_steps;        /* the end of the decay, counted from step 0 (COSINE / LINEAR); the factor stays at min_factor from there on */
+  float min_factor;           /* fmin in [0, 1] */
+  float gamma;                /* STEP: in (0, 1] */
+  int64_t step_size;          /* STEP: > 0 */
+} avmoe_opt_schedule;
+
+int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                              float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched /* HOST */);
 
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the

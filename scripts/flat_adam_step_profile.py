@@ -4,6 +4,9 @@
 
 --mode device      FlatAdam(max_grad_norm=..., skip_nonfinite=True).step(): three launches whatever the model
 --mode clip_plain  torch.nn.utils.clip_grad_norm_ over the bucket views + the plain FlatAdam.step() (one avmoe_adam_step per merged range)
+--schedule         (device mode) a per-step LRSchedule -- warm-up + cosine across the measured steps -- evaluated on the device: still three launches
+--schedule-upload  (device mode) the same schedule WITHOUT the device-side factor: the rates are rewritten into the range table and the
+                   table is re-sent before every step (FlatAdam._upload_table()), the only way to a per-step schedule before --schedule
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
@@ -41,14 +44,27 @@ def main():
     ap.add_argument("--mode", choices=["device", "clip_plain"], default="device")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--schedule", action="store_true")
+    ap.add_argument("--schedule-upload", action="store_true")
     a = ap.parse_args()
+    if (a.schedule or a.schedule_upload) and a.mode != "device":
+        ap.error("--schedule / --schedule-upload go with --mode device")
+    if a.schedule and a.schedule_upload:
+        ap.error("--schedule and --schedule-upload are the two sides of one comparison")
     from avmoe_amd.dp import AdapterGradReducer
-    from avmoe_amd.train import FlatAdam
+    from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
     params, sites, model = build(a.model, dev)
     red = AdapterGradReducer(params, sites=sites)
     kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if a.mode == "device" else {}
+    total = a.warmup + a.steps
+    sched = None
+    if a.schedule or a.schedule_upload:
+        sched = LRSchedule(warmup_steps=total // 4, warmup_start=0.1, decay_kind="cosine", total_steps=max(total, total // 4 + 1), min_factor=0.05)
+    if a.schedule:
+        kw["lr_schedule"] = sched
     opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
+    base_lr = [e[3] for e in opt._plist]
     g = torch.Generator().manual_seed(0)
     for b in red.buckets:
         b.flat.copy_(torch.randn(b.flat.numel(), generator=g))
@@ -57,6 +73,10 @@ def main():
     def step():
         if a.mode == "clip_plain":
             torch.nn.utils.clip_grad_norm_(grads, 1.0)
+        if a.schedule_upload:                            # the host drives the schedule: new rates into the table, the table to the device
+            f = sched.factor(opt.t)                      # opt.t == applied_steps here: the fixed finite gradients never skip a step
+            opt._plist = [e[:3] + (lr0 * f,) for e, lr0 in zip(opt._plist, base_lr)]
+            opt._upload_table()
         opt.step()
 
     for _ in range(a.warmup):
@@ -70,7 +90,11 @@ def main():
     e1.record()
     wall = time.perf_counter() - t0
     torch.cuda.synchronize()
-    print(json.dumps({"model": a.model, "mode": a.mode, "steps": a.steps, "warmup": a.warmup, "buckets": len(red.buckets),
+    extra = {"schedule": "device"} if a.schedule else {"schedule": "table upload per step"} if a.schedule_upload else {}
+    if a.schedule:
+        extra["last_lr_factor"] = float(opt.last_lr_factor.item())
+        extra["want_lr_factor"] = sched.factor(total - 1)
+    print(json.dumps({"model": a.model, "mode": a.mode, **extra, "steps": a.steps, "warmup": a.warmup, "buckets": len(red.buckets),
                       "parameters": len(params), "elements": sum(p.numel() for p in params),
                       "plain_launches_per_step": sum(len(s["ranges"]) for s in opt.state),
                       "step_us": round(1e3 * e0.elapsed_time(e1) / a.steps, 2), "step_wall_us": round(1e6 * wall / a.steps, 2)}))
