@@ -125,6 +125,13 @@ def declare(L):
         L.avmoe_moe_forward_topk.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p, C.c_int32,
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]
+    if hasattr(L, "avmoe_moe_forward_aux"):          # (found by symbol: added under ABI 11 -- the router auxiliary losses: z-loss, balance loss)
+        L.avmoe_moe_forward_aux.restype = C.c_int
+        L.avmoe_moe_forward_aux.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p, C.c_int32,
+                                            C.c_int32] + [C.c_void_p] * 9
+        L.avmoe_moe_backward_aux.restype = C.c_int
+        L.avmoe_moe_backward_aux.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs)] + [C.c_void_p] * 8 + \
+                                            [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

@@ -18,6 +18,7 @@ missing library or a non-GPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Dict
 
 import numbers
@@ -101,8 +102,25 @@ def _shared_gpu_of(module, dev, asked):
     return side
 
 
+RouterAux = namedtuple("RouterAux", ["z_loss", "balance_loss", "load"])
+RouterAux.__doc__ = """The router auxiliary losses of one site call (`site.last_router_aux`; include/avmoe.h at avmoe_moe_forward_aux):
+z_loss = mean_s logsumexp(logits_s)^2 and balance_loss = E sum_e load_e P_e, 0-d fp32 tensors with a grad_fn; load (E,), the share of
+the routing slots each expert received, without gradient."""
+
+
+def _publish_aux(module, aux, load):
+    """site.last_router_aux of the call that just ran: the two losses as views of the autograd output `aux` (their gradients come back
+    as its gradient), or None when the site ran without them."""
+    if aux is None:
+        module.__dict__["_last_router_aux"] = None
+    else:
+        z, b = aux.unbind(0)
+        module.__dict__["_last_router_aux"] = RouterAux(z, b, load)
+
+
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
-    """One avmoe_moe_forward call.  Returns (out, probs, idx, lb, state) with state = what the backward needs.
+    """One avmoe_moe_forward call.  Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or
+    ((2,) [z, balance], load (E,)): the router auxiliary losses of a site with `router_aux` on (avmoe_moe_forward_aux).
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
     stream: the handle (int) of the CURRENT stream when the caller already has it (AdapterPair), else looked up."""
@@ -143,7 +161,15 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     if noise is not None:
         noise = noise.to(torch.float32).contiguous()
     top_k = module.router_top_k
-    if top_k is not None and top_k < E:                  # top-k gating of the mixture (k == E: the dense site, the dense entry point)
+    aux = None
+    if module.router_aux:                                # the router auxiliary losses beside the forward (dense or top-k)
+        fn = "avmoe_moe_forward_aux"
+        aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
+        st = L.avmoe_moe_forward_aux(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
+                                     noise.data_ptr() if noise is not None else None, top_k if (top_k is not None and top_k < E) else 0,
+                                     int(module.router_top_k_renorm), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
+                                     aux[0].data_ptr(), aux[1].data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+    elif top_k is not None and top_k < E:                # top-k gating of the mixture (k == E: the dense site, the dense entry point)
         fn = "avmoe_moe_forward_topk"
         st = L.avmoe_moe_forward_topk(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
                                       noise.data_ptr() if noise is not None else None, top_k, int(module.router_top_k_renorm),
@@ -158,7 +184,7 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     capi.check(st, fn)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
-    return out, probs, idx, lb, ((desc, keep, ptrs), saved, X, Y)
+    return out, probs, idx, lb, ((desc, keep, ptrs), saved, X, Y), aux
 
 
 class _SiteBackward:
@@ -168,7 +194,7 @@ class _SiteBackward:
     or for all of them when a gradient sink took them)."""
 
     def __init__(self, module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, scratch_slot=0, stream=None,
-                 d_probs=None):
+                 d_probs=None, d_aux=None):
         self.L = capi.lib()
         (desc, keep, fwd_ptrs), self.saved, self.X, self.Y = state
         self.desc, self.names, self.module = desc, names, module
@@ -201,6 +227,7 @@ class _SiteBackward:
         self.d_out = d_out.to(self.X.dtype).contiguous() if d_out is not None else None
         self.dprobs = d_probs.to(torch.float32).reshape(desc.S, -1).contiguous() if d_probs is not None else None
         self.lbg = d_lb.to(torch.float32).reshape(1).contiguous() if (d_lb is not None and desc.lb_loss) else None
+        self.daux = d_aux.to(torch.float32).reshape(2).contiguous() if d_aux is not None else None      # [g_z, g_balance]
         wkey = (desc.S, desc.N, desc.M, self.X.dtype, bool(desc.training), bool(desc.shared_gpu))
         sizes = module.__dict__.get("_ws_sizes", {}).get(wkey)
         self.scratch = _scratch(self.X.device, sizes[1] if sizes else self.L.avmoe_moe_scratch_bytes(C.byref(desc)), scratch_slot, stream=self.stream)
@@ -209,6 +236,16 @@ class _SiteBackward:
     def run(self, parts=0):
         d = self.desc
         d.accumulate_dx, d.accumulate_dy = self.acc
+        if self.daux is not None:                              # a gradient for the router auxiliary losses: _ex plus aux_grad
+            st = self.L.avmoe_moe_backward_aux(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),
+                                               self.d_out.data_ptr() if self.d_out is not None else None,
+                                               self.dprobs.data_ptr() if self.dprobs is not None else None,
+                                               self.lbg.data_ptr() if self.lbg is not None else None, self.daux.data_ptr(),
+                                               self.saved.data_ptr(), self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(),
+                                               C.byref(self.gptrs), int(parts), self.stream)
+            d.accumulate_dx = d.accumulate_dy = 0
+            capi.check(st, "avmoe_moe_backward_aux")
+            return self
         if self.d_out is None or self.dprobs is not None:      # a gradient for probs, or none for out: the _ex entry point
             st = self.L.avmoe_moe_backward_ex(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),
                                               self.d_out.data_ptr() if self.d_out is not None else None,
@@ -272,17 +309,19 @@ class _SiteBackward:
         return tuple(self.grads[k] for k in self.names)
 
 
-def _site_backward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, d_probs=None):
+def _site_backward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, d_probs=None, d_aux=None):
     """The whole backward of one site in one call (see _SiteBackward)."""
-    return _SiteBackward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx, acc_dy, d_probs=d_probs).run(0).finish()
+    return _SiteBackward(module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx, acc_dy, d_probs=d_probs, d_aux=d_aux).run(0).finish()
 
 
 class AdapterFunction(torch.autograd.Function):
-    """out, probs, lb = f(X, Y, noise, *params) on token-major X:(S,N,C), Y:(S,M,Cy)."""
+    """out, probs, idx, lb, aux, load = f(X, Y, noise, *params) on token-major X:(S,N,C), Y:(S,M,Cy); aux = [z, balance] and load: the
+    router auxiliary losses of a site with `router_aux` on, else None."""
 
     @staticmethod
     def forward(ctx, module, X, Y, noise, names, *params):
-        out, probs, idx, lb, state = _site_forward(module, X, Y, noise, names, params)
+        out, probs, idx, lb, state, aux = _site_forward(module, X, Y, noise, names, params)
+        aux, load = aux if aux is not None else (None, None)
         ctx.set_materialize_grads(False)                 # no zero tensors (= fill kernels) for the gradients of probs / idx / lb nobody sent
         ctx.module, ctx.names, ctx.state = module, names, state[:2]
         sink = getattr(module, "_grad_sink", None)
@@ -290,15 +329,17 @@ class AdapterFunction(torch.autograd.Function):
             sink.calls += 1                              # the site's bucket is complete after as many backward calls
         ctx.save_for_backward(state[2], state[3], *params)
         ctx.mark_non_differentiable(idx)                 # probs is differentiable, as in the reference (F.softmax of the router logits)
-        return out, probs, idx, lb
+        if load is not None:
+            ctx.mark_non_differentiable(load)
+        return out, probs, idx, lb, aux, load
 
     @staticmethod
-    def backward(ctx, d_out, d_probs, _d_idx, d_lb):
+    def backward(ctx, d_out, d_probs, _d_idx, d_lb, d_aux=None, _d_load=None):
         X, Y, *params = ctx.saved_tensors
-        # d_out None (only probs and / or the load-balancing loss were differentiated): the router-only backward
+        # d_out None (only probs, the load-balancing loss and / or the router auxiliary losses were differentiated): the router-only backward
         dX, dY = torch.empty_like(X), torch.empty_like(Y)
         pg = _site_backward(ctx.module, (*ctx.state, X, Y), ctx.names, params, ctx.needs_input_grad[5:], d_out, d_lb, dX, dY,
-                            d_probs=d_probs)
+                            d_probs=d_probs, d_aux=d_aux)
         return (None, dX, dY, None, None) + pg
 
 
@@ -339,14 +380,15 @@ class _PairFunction(torch.autograd.Function):
             fork(ctx_ev[2])
             two = side.cuda_stream != main.cuda_stream      # (same_stream: the schedule of the two-stream mode on one stream -- nothing overlaps)
             with torch.cuda.stream(side):
-                out_b, pr_b, idx_b, lb_b, st_b = _site_forward(site_b, Xb, Xa, noises[1], names_b, pb, add_to=base_b, shared_gpu=two, stream=side.cuda_stream)
-            out_a, pr_a, idx_a, lb_a, st_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, shared_gpu=two, stream=main.cuda_stream)
+                out_b, pr_b, idx_b, lb_b, st_b, ax_b = _site_forward(site_b, Xb, Xa, noises[1], names_b, pb, add_to=base_b, shared_gpu=two, stream=side.cuda_stream)
+            out_a, pr_a, idx_a, lb_a, st_a, ax_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, shared_gpu=two, stream=main.cuda_stream)
             join(ctx_ev[3])
-            for t_ in (out_b, idx_b, pr_b, lb_b, st_b[1]):
+            for t_ in (out_b, idx_b, pr_b, lb_b, st_b[1]) + (ax_b if ax_b is not None else ()):
                 t_.record_stream(main)
         else:
-            out_a, pr_a, idx_a, lb_a, st_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, stream=main.cuda_stream)
-            out_b, pr_b, idx_b, lb_b, st_b = _site_forward(site_b, st_a[3], st_a[2], noises[1], names_b, pb, add_to=base_b, stream=main.cuda_stream)
+            out_a, pr_a, idx_a, lb_a, st_a, ax_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, stream=main.cuda_stream)
+            out_b, pr_b, idx_b, lb_b, st_b, ax_b = _site_forward(site_b, st_a[3], st_a[2], noises[1], names_b, pb, add_to=base_b, stream=main.cuda_stream)
+        (ax_a, ld_a), (ax_b, ld_b) = (ax_a if ax_a is not None else (None, None)), (ax_b if ax_b is not None else (None, None))
         dirty = [t for t in (base_a, base_b) if t is not None]
         if dirty:
             ctx.mark_dirty(*dirty)
@@ -360,11 +402,11 @@ class _PairFunction(torch.autograd.Function):
             if sink is not None and any(needs) and (not ctx.lean or ctx.needs_input_grad[10]):
                 sink.calls += 1
         ctx.save_for_backward(st_a[2], st_a[3], *params)
-        ctx.mark_non_differentiable(idx_a, idx_b)       # the probabilities are differentiable, as in the reference
-        return out_a, out_b, idx_a, idx_b, pr_a, pr_b, lb_a, lb_b
+        ctx.mark_non_differentiable(idx_a, idx_b, *(t_ for t_ in (ld_a, ld_b) if t_ is not None))       # the probabilities are differentiable, as in the reference
+        return out_a, out_b, idx_a, idx_b, pr_a, pr_b, lb_a, lb_b, ax_a, ax_b, ld_a, ld_b
 
     @staticmethod
-    def backward(ctx, d_a, d_b, _ia, _ib, dp_a, dp_b, d_lba, d_lbb):
+    def backward(ctx, d_a, d_b, _ia, _ib, dp_a, dp_b, d_lba, d_lbb, dx_a=None, dx_b=None, _dla=None, _dlb=None):
         Xa, Xb, *params = ctx.saved_tensors
         router_only = d_a is None and d_b is None        # neither output got a gradient: the router-only backward for both sites
         if not router_only:                              # (one output without: zeros for it -- the sections and the fused dX + dY path
@@ -386,9 +428,9 @@ class _PairFunction(torch.autograd.Function):
         gba = d_a if ctx.has_base[0] else None            # out = base + adapter(...): the residual stream passes the gradient on
         gbb = d_b if ctx.has_base[1] else None
         if router_only:                                   # both sites on the caller's stream, one after the other: A overwrites, B adds
-            pga = _site_backward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, None, d_lba, gXa, gXb, d_probs=dp_a)
+            pga = _site_backward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, None, d_lba, gXa, gXb, d_probs=dp_a, d_aux=dx_a)
             pgb = _site_backward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, None, d_lbb, gXb, gXa, acc_dx=True,
-                                 acc_dy=True, d_probs=dp_b)
+                                 acc_dy=True, d_probs=dp_b, d_aux=dx_b)
             return (None, None, None, gXa, gXb, gba, gbb, None, None, None) + ((None,) if ctx.lean else pga + pgb)
         if ctx.side is not None:
             # Two streams, cross-ordered hand-over: ONE buffer per token tensor, no add kernel.  Each site OVERWRITES its own token
@@ -402,9 +444,9 @@ class _PairFunction(torch.autograd.Function):
             slot_b = 1 if side.cuda_stream == main.cuda_stream else 0      # (same_stream: the two sites' sections interleave on ONE stream)
             with torch.cuda.stream(side):
                 cbk = _SiteBackward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, d_b, d_lbb, gXb, gXa, acc_dx=False, acc_dy=True,
-                                    scratch_slot=slot_b, stream=side.cuda_stream, d_probs=dp_b)
+                                    scratch_slot=slot_b, stream=side.cuda_stream, d_probs=dp_b, d_aux=dx_b)
             cak = _SiteBackward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, d_a, d_lba, gXa, gXb, acc_dx=False, acc_dy=True,
-                                stream=main.cuda_stream, d_probs=dp_a)
+                                stream=main.cuda_stream, d_probs=dp_a, d_aux=dx_a)
             # Round 5: where the library serves it (avmoe_moe_backward_dx_dy: the tuned bf16 shapes), a token gradient is written ONCE -- the
             # dX product of its own site with the other site's dY product folded in as two more contraction segments -- instead of
             # overwritten by one site and read back + added by the other.  That product moves to the END of its site's backward (it
@@ -441,7 +483,7 @@ class _PairFunction(torch.autograd.Function):
                 cak.run(16)
             pga = cak.finish()
             ev_join.record(side); main.wait_event(ev_join)
-            for t_ in tuple(g_ for g_ in pgb if g_ is not None) + (cbk.d_out,) + ((cbk.dprobs,) if cbk.dprobs is not None else ()):
+            for t_ in tuple(g_ for g_ in pgb if g_ is not None) + (cbk.d_out,) + tuple(g_ for g_ in (cbk.dprobs, cbk.daux) if g_ is not None):
                 t_.record_stream(main)
             gXa.record_stream(side); gXb.record_stream(side)
             return (None, None, None, gXa, gXb, gba, gbb, None, None, None) + ((None,) if ctx.lean else pga + pgb)
@@ -451,10 +493,10 @@ class _PairFunction(torch.autograd.Function):
         first_b = Xa.numel() >= Xb.numel()
         def run_a(acc):
             return _site_backward(site_a, (*ctx.states[0], Xa, Xb), names_a, params[:na], needs_a, d_a,
-                                  d_lba, gXa, gXb, acc_dx=acc, acc_dy=acc, d_probs=dp_a)   # dX -> gXa, dY -> gXb
+                                  d_lba, gXa, gXb, acc_dx=acc, acc_dy=acc, d_probs=dp_a, d_aux=dx_a)   # dX -> gXa, dY -> gXb
         def run_b(acc):
             return _site_backward(site_b, (*ctx.states[1], Xb, Xa), names_b, params[na:], needs_b, d_b,
-                                  d_lbb, gXb, gXa, acc_dx=acc, acc_dy=acc, d_probs=dp_b)   # dX -> gXb, dY -> gXa
+                                  d_lbb, gXb, gXa, acc_dx=acc, acc_dy=acc, d_probs=dp_b, d_aux=dx_b)   # dX -> gXb, dY -> gXa
         if first_b:
             pgb = run_b(False); pga = run_a(True)
         else:
@@ -533,6 +575,25 @@ class MoEAdapter(nn.Module):
         # avmoe_moe_forward_topk).  Plain attributes, not state: reassigning them switches the mode of the next call.
         self.router_top_k = getattr(opt, "router_top_k", None)
         self.router_top_k_renorm = getattr(opt, "router_top_k_renorm", True)
+        # the router auxiliary losses (z-loss, Switch balance loss: include/avmoe.h at avmoe_moe_forward_aux) beside every forward; a
+        # plain attribute like the two above.  Off: the entry points and launches of a site without them.
+        self.router_aux = getattr(opt, "router_aux", False)
+
+    @property
+    def router_aux(self):
+        """True: every forward also forms the router z-loss and balance loss and leaves them in `last_router_aux`."""
+        return self.__dict__.get("_router_aux", False)     # (.get: a module pickled before the setting existed has none)
+
+    @router_aux.setter
+    def router_aux(self, v):
+        if not isinstance(v, bool):
+            raise ValueError(f"router_aux must be True or False, got {v!r}")
+        self.__dict__["_router_aux"] = v
+
+    @property
+    def last_router_aux(self):
+        """RouterAux(z_loss, balance_loss, load) of the last forward, or None when it ran with `router_aux` off (or none ran yet)."""
+        return self.__dict__.get("_last_router_aux")
 
     @property
     def router_top_k(self):
@@ -644,7 +705,7 @@ class MoEAdapter(nn.Module):
 
     def __getstate__(self):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
-        for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes"):
+        for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux"):
             st.pop(k, None)
         return st
 
@@ -713,7 +774,8 @@ class MoEAdapter(nn.Module):
         Y = vis_token.squeeze(-1).permute(0, 2, 1)
         P = self._param_tensors()
         names = tuple(P.keys())
-        out, probs, idx, lb = AdapterFunction.apply(self, X, Y, noise, names, *P.values())
+        out, probs, idx, lb, aux, load = AdapterFunction.apply(self, X, Y, noise, names, *P.values())
+        _publish_aux(self, aux, load)
         return out.permute(0, 2, 1).unsqueeze(-1), probs, idx, lb
 
     def forward(self, x, vis_token=None):
@@ -838,8 +900,10 @@ class AdapterPair(nn.Module):
             getattr(m, "_grad_sink", None) is not None and m._grad_sink.flat is not None and all(p.requires_grad for p in P.values())
             and m._grad_sink.matches(tuple(P.keys()), P) for m, P in ((self.site_a, Pa), (self.site_b, Pb)))
         plist = (next(iter(Pa.values())),) if lean and len(Pa) > 1 else (*Pa.values(), *Pb.values())
-        out_a, out_b, idx_a, idx_b, pr_a, pr_b, lb_a, lb_b = _PairFunction.apply(
+        out_a, out_b, idx_a, idx_b, pr_a, pr_b, lb_a, lb_b, ax_a, ax_b, ld_a, ld_b = _PairFunction.apply(
             self.site_a, self.site_b, side, Xa, Xb, add_to[0], add_to[1], tuple(Pa.keys()), tuple(Pb.keys()), noises, *plist)
+        _publish_aux(self.site_a, ax_a, ld_a)               # (each site's own `router_aux` setting decided: read in _site_forward)
+        _publish_aux(self.site_b, ax_b, ld_b)
         out_a, out_b = out_a.permute(0, 2, 1).unsqueeze(-1), out_b.permute(0, 2, 1).unsqueeze(-1)
         if self.variant in ("ave", "avqa"):
             return out_a, idx_a.unsqueeze(-1), out_b, idx_b.unsqueeze(-1)

@@ -33,9 +33,14 @@ class AdapterIndexRecord:
 
     def __init__(self):
         self.entries: Dict[str, Dict[str, List[torch.Tensor]]] = {"audio": {"p1": [], "p2": []}, "video": {"p1": [], "p2": []}}
+        # the router auxiliary losses of the sites that ran with `router_aux` on, in execution order: (modality, position, RouterAux)
+        self.router_aux: List[tuple] = []
 
     def append(self, modality: str, position: str, idx: torch.Tensor):
         self.entries[modality][position].append(idx)
+
+    def append_aux(self, modality: str, position: str, aux):
+        self.router_aux.append((modality, position, aux))
 
     def to_dict(self) -> Dict[str, Dict[str, list]]:
         flat, where = [], []
@@ -134,6 +139,10 @@ class DualBackboneLoop(nn.Module):
             out_a, idx_a, out_v, idx_v = pair(_to_site(f_a), _to_site(f_v))
         record.append("audio", pos, idx_a)
         record.append("video", pos, idx_v)
+        for modality, site in (("audio", pair.site_a), ("video", pair.site_b)):      # (each site's own `router_aux` setting decided)
+            aux = getattr(site, "last_router_aux", None)
+            if aux is not None:
+                record.append_aux(modality, pos, aux)
         out_a, out_v = _from_site(out_a), _from_site(out_v)
         if base_a is None:
             return out_a, out_v                           # bare residuals

@@ -134,7 +134,13 @@ int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const a
 // rbw layout: dlog [S][E] | dh2r [S][32] | dh1 [S][128] | drin [S][2C]
 // ---------------------------------------------------------------------------------------------
 // dprobs: optional (S, E) upstream gradient of probs itself (a loss on the routing probabilities), added to dp before the softmax Jacobian
-struct RouterBwdArgs { const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; const float* dprobs; };
+// aux_grad: optional [g_z, g_balance], the upstream gradients of the router auxiliary losses (avmoe_moe_forward_aux), with the
+// forward's saved lse (S) and load (E):  d balance / d p_se = E load_e / S joins dp before the softmax Jacobian (the selection behind
+// load carries no gradient);  d z / d l_se = (2 / S) lse_s p_se acts on the logits, after it.  NULL: every branch is uniformly skipped.
+struct RouterBwdArgs {
+  const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; const float* dprobs;
+  const float *aux_grad, *lse, *load;
+};
 // Launch 1: per frame dlog / dh2 / dh1 (softmax, LB loss, the two small layers), one block per frame.
 // mode: the forward's mode word [k, renorm].  k = 0 (dense): dp is the gradient of probs = the softmax.  k > 0 (top-k gating):
 // `probs` holds the mixture weights w, psm the softmax p, and dp is dL/dw; it is mapped to dL/dp first (the selection S_k, recomputed
@@ -181,9 +187,15 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
       if (!top_k) dpv[e] = dp[(long)s * a.E + e];
       if (a.lb_loss && a.lb_grad) dpv[e] += a.lb_grad[0] * (-1.f / ((float)a.S * s_pm[e]));
       if (a.dprobs) dpv[e] += a.dprobs[(long)s * a.E + e];      // (uniform branch: NULL leaves today's sum)
+      if (a.aux_grad) dpv[e] += a.aux_grad[1] * ((float)a.E * a.load[e] / (float)a.S);
       dot += probs[(long)s * a.E + e] * dpv[e];
     }
-    for (int e = 0; e < a.E; ++e) { const float v = probs[(long)s * a.E + e] * (dpv[e] - dot); s_dl[e] = v; dlog[e] = v; }
+    const float gz = a.aux_grad ? a.aux_grad[0] * (2.f / (float)a.S) * a.lse[s] : 0.f;
+    for (int e = 0; e < a.E; ++e) {
+      float v = probs[(long)s * a.E + e] * (dpv[e] - dot);
+      if (a.aux_grad) v += gz * probs[(long)s * a.E + e];
+      s_dl[e] = v; dlog[e] = v;
+    }
   }
   __syncthreads();
   if (threadIdx.x < 32) {
@@ -271,10 +283,11 @@ __global__ void __launch_bounds__(256) kk_router_bwd_fin(int S, int E, int C2, i
   }
 }
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-                 const float* lb_grad, const float* dprobs, hipStream_t st) {
+                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad) {
   ProfScope ps_("k_router_bwd", 0.0, 0.0, st);
   const Dims& d = pl.d;
-  RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad, dprobs};
+  RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad, dprobs,
+                  aux_grad, (const float*)(saved + pl.o_lse), (const float*)(saved + pl.o_load)};
   hipLaunchKernelGGL(kk_router_bwd_a, dim3(d.S), dim3(256), 0, st, a, (const float*)(saved + pl.o_probs),
                      (const float*)(scratch + pl.o_dp), (const float*)(saved + pl.o_rh1), (const float*)(saved + pl.o_rh2),
                      (float*)(scratch + pl.o_rbw), (const float*)(saved + pl.o_psm), (const int*)(saved + pl.o_mode));

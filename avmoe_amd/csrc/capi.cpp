@@ -66,6 +66,18 @@ int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void
   return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0);
 }
 
+int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                          int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
+                          void* saved, void* scratch, void* stream) {
+  Plan pl;
+  AVMOE_TRY(make_plan(desc, &pl));
+  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("avmoe_moe_forward_aux: null pointer"); return ERR_BAD_ARG; }
+  if (top_k < 0 || top_k > pl.d.E) { set_last_error("avmoe_moe_forward_aux: top_k %d not in [0, %d]", top_k, pl.d.E); return ERR_BAD_ARG; }
+  const int k = top_k == pl.d.E ? 0 : top_k;            // 0 and E: the dense mixture (the load then counts every frame's first expert)
+  return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0,
+                     aux, aux ? load : nullptr);
+}
+
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                        const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
                        const avmoe_moe_ptrs* grads, void* stream) {
@@ -91,22 +103,40 @@ int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const voi
   return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts);
 }
 
-int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
-                          const float* dprobs, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
-                          const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
+}  // extern "C"
+
+// avmoe_moe_backward_ex / avmoe_moe_backward_aux (`fn`: the name in the error strings)
+static int backward_ex(const char* fn, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
+                       const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved, void* scratch, void* dX, void* dY,
+                       const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
   if (!X || !Y || !params || !saved || !scratch || !dX || !dY || !grads || parts < 0 || parts > 127) {
-    set_last_error("avmoe_moe_backward_ex: null pointer or parts not in 0..127"); return ERR_BAD_ARG;
+    set_last_error("%s: null pointer or parts not in 0..127", fn); return ERR_BAD_ARG;
   }
   if ((parts & 4) && (parts & 24)) {
-    set_last_error("avmoe_moe_backward_ex: parts %d combines section 4 with its halves 8 / 16", parts); return ERR_BAD_ARG;
+    set_last_error("%s: parts %d combines section 4 with its halves 8 / 16", fn, parts); return ERR_BAD_ARG;
   }
   if (!dOut) {                              // out gets no gradient: the router-only backward, whole (it has no sections)
-    if (parts != 0 && parts != 7) { set_last_error("avmoe_moe_backward_ex: dOut == NULL serves parts 0 / 7 only, not %d", parts); return ERR_UNSUPPORTED; }
-    return moe_backward_router_only(pl, Y, *params, dprobs, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream);
+    if (parts != 0 && parts != 7) { set_last_error("%s: dOut == NULL serves parts 0 / 7 only, not %d", fn, parts); return ERR_UNSUPPORTED; }
+    return moe_backward_router_only(pl, Y, *params, dprobs, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, aux_grad);
   }
-  return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts, dprobs);
+  return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts, dprobs,
+                      aux_grad);
+}
+
+extern "C" {
+
+int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
+                          const float* dprobs, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
+                          const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
+  return backward_ex("avmoe_moe_backward_ex", desc, X, Y, params, dOut, dprobs, lb_grad, nullptr, saved, scratch, dX, dY, grads, parts, stream);
+}
+
+int avmoe_moe_backward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
+                           const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved, void* scratch, void* dX,
+                           void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
+  return backward_ex("avmoe_moe_backward_aux", desc, X, Y, params, dOut, dprobs, lb_grad, aux_grad, saved, scratch, dX, dY, grads, parts, stream);
 }
 
 int avmoe_moe_backward_dx_dy(const avmoe_moe_desc* desc_a, const void* X_a, void* saved_a, void* scratch_a,

@@ -771,9 +771,11 @@ struct RouterArgs {
 // Top-k gating (a.top_k > 0, avmoe_moe_forward_topk): `probs` (what the post kernels multiply by) receives the mixture weights
 // w_e = m_e p_e / sum_j m_j p_j (renorm) or m_e p_e, and `psm` the dense softmax p for the backward and the load-balancing loss;
 // probs_out / idx_out stay the dense softmax and its argmax.  Block 0 writes the mode word [k, renorm] (k = 0: dense) that the
-// router backward reads.
+// router backward reads.  Every frame's log-sum-exp of the logits goes to `lse` (the router z-loss and its gradient need it; the
+// softmax alone does not give it back).
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
-                                                      float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode) {
+                                                      float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
+                                                      float* lse) {
   __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
@@ -807,6 +809,7 @@ __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, 
     for (int e = 1; e < a.E; ++e) mx = fmaxf(mx, s_lg[e]);
     float sum = 0.f;
     for (int e = 0; e < a.E; ++e) sum += expf(s_lg[e] - mx);
+    lse[s] = mx + logf(sum);
     int best = 0; float bp = -1.f;
     for (int e = 0; e < a.E; ++e) {
       const float p = expf(s_lg[e] - mx) / sum;
@@ -836,8 +839,63 @@ __global__ void __launch_bounds__(256) kk_lb_loss(const float* probs, int S, int
   }
   if (threadIdx.x == 0) *lb = total;
 }
+// Router auxiliary losses (avmoe_moe_forward_aux) from the dense softmax p (S, E) and the frames' log-sum-exp, ONE block:
+//   aux[0] = z       = (1 / S) sum_s lse_s^2
+//   load_e           = (1 / (S k')) sum_s 1[e in S_k'(s)]      S_k'(s): topk_select on p[s] -- the mixture's own selection and tie rule
+//   aux[1] = balance = E sum_e load_e P_e ,  P_e = (1 / S) sum_s p_se
+// Every sum runs in a fixed order (thread t takes the frames t, t + 256, ...; block_sum256), so the results repeat bit for bit; the
+// counts are integers below 2^24, exact in fp32 in any order.  The column sums of p are formed exactly as kk_lb_loss forms them: with
+// do_lb this launch writes the load-balancing loss too, bit-equal, and kk_lb_loss is not launched.  load goes to `load_sv` (saved:
+// the router backward reads it) and, when asked for, to `load_out`.
+__global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float* lse, int S, int E, int kp, int do_lb, float* lb,
+                                                     float* aux, float* load_out, float* load_sv) {
+  __shared__ float red[4];
+  __shared__ float s_P[MAX_E], s_ld[MAX_E];
+  __shared__ float s_pr[256][MAX_E + 1];                 // one frame's probabilities per thread (+ 1: no bank conflicts)
+  float total = 0.f;
+  for (int e = 0; e < E; ++e) {
+    float acc = 0.f;
+    for (int s = threadIdx.x; s < S; s += 256) acc += p[(long)s * E + e];
+    acc = block_sum256(acc, red);
+    total += -logf(acc / (float)S);
+    if (threadIdx.x == 0) s_P[e] = acc / (float)S;
+  }
+  if (do_lb && threadIdx.x == 0) *lb = total;
+  int cnt[MAX_E];
+#pragma unroll
+  for (int e = 0; e < MAX_E; ++e) cnt[e] = 0;
+  float zz = 0.f;
+  float* pr = s_pr[threadIdx.x];
+  for (int s = threadIdx.x; s < S; s += 256) {
+    for (int e = 0; e < E; ++e) pr[e] = p[(long)s * E + e];
+    float kept;
+    const unsigned m = topk_select(pr, E, kp, &kept);
+#pragma unroll
+    for (int e = 0; e < MAX_E; ++e) cnt[e] += (int)((m >> e) & 1u);
+    const float l = lse[s];
+    zz += l * l;
+  }
+  const float slots = (float)S * (float)kp;
+#pragma unroll
+  for (int e = 0; e < MAX_E; ++e)
+    if (e < E) {                                         // (uniform over the block)
+      const float c = block_sum256((float)cnt[e], red);
+      if (threadIdx.x == 0) s_ld[e] = c / slots;
+    }
+  zz = block_sum256(zz, red);
+  if (threadIdx.x == 0) {
+    float b = 0.f;
+    for (int e = 0; e < E; ++e) {
+      b += s_ld[e] * s_P[e];
+      load_sv[e] = s_ld[e];
+      if (load_out) load_out[e] = s_ld[e];
+    }
+    aux[0] = zz / (float)S;
+    aux[1] = (float)E * b;
+  }
+}
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm) {
+             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
@@ -858,10 +916,15 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
   }
   hipLaunchKernelGGL(kk_router_tail, dim3(d.S), dim3(128), 0, st, a, (float*)(saved + pl.o_rh1), (const float*)(scratch + pl.o_slabs), ks,
                      (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), probs_out, idx_out, (lb_out && !d.lb_loss) ? lb_out : nullptr,
-                     (float*)(saved + pl.o_psm), (int*)(saved + pl.o_mode));
+                     (float*)(saved + pl.o_psm), (int*)(saved + pl.o_mode), (float*)(saved + pl.o_lse));
   AVMOE_CHECK_LAUNCH("router");
-  if (lb_out && d.lb_loss) {                               // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
-    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, (const float*)(saved + (top_k ? pl.o_psm : pl.o_probs)), d.S, d.E, lb_out);
+  const float* dense = (const float*)(saved + (top_k ? pl.o_psm : pl.o_probs));
+  if (aux_out) {                                           // the auxiliary losses -- and the load-balancing loss from the same launch
+    hipLaunchKernelGGL(kk_router_aux, dim3(1), dim3(256), 0, st, dense, (const float*)(saved + pl.o_lse), d.S, d.E, top_k ? top_k : 1,
+                       (lb_out && d.lb_loss) ? 1 : 0, lb_out, aux_out, load_out, (float*)(saved + pl.o_load));
+    AVMOE_CHECK_LAUNCH("router_aux");
+  } else if (lb_out && d.lb_loss) {                        // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
+    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, dense, d.S, d.E, lb_out);
     AVMOE_CHECK_LAUNCH("lb_loss");
   }
   return OK;

@@ -15,6 +15,7 @@
 // Served: every variant, AVS self_attention_version "v1" (MultiheadAttention across the frames) included since round 6 (it was AVMOE_ERR_UNSUPPORTED here; the HIP
 // library and the Python oracle have it), train and eval BatchNorm, every flag of the descriptor.
 #include "../../include/avmoe_host.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -154,6 +155,8 @@ struct Ctx {
   V Yt, Yf, rin, h1, h2, logit, p;
   V w;                              // the mixture weights: p, or the top-k weights
   std::vector<unsigned> sel;        // top-k: the kept experts of each frame (bit e)
+  V lse, load;                      // router auxiliary losses (avmoe_host_moe_forward_aux): log-sum-exp per frame, share of the slots per expert
+  float aux[2] = {0.f, 0.f};        // [z, balance]
   std::vector<Expert> ex;
 };
 
@@ -223,6 +226,35 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
       }
       for (int e = 0; e < E; ++e) c.w[s * E + e] = ((c.sel[s] >> e) & 1u) ? (c.renorm ? ps[e] / kept : ps[e]) : 0.f;
     }
+  // ---- router auxiliary losses: z = mean_s lse_s^2 ; balance = E sum_e load_e P_e, load from the k' = (top-k ? k : 1) most probable
+  //      experts of each frame on the dense softmax (the tie rule above), P the column means of p
+  {
+    const int kp = c.topk ? c.topk : 1;
+    c.lse.assign(S, 0.f); c.load.assign(E, 0.f);
+    double z = 0.0, bal = 0.0;
+    std::vector<long> cnt(E, 0);
+    for (int s = 0; s < S; ++s) {
+      const float* lg = c.logit.data() + (long)s * E;
+      const float* ps = c.p.data() + (long)s * E;
+      double mx = lg[0], sum = 0.0;
+      for (int e = 1; e < E; ++e) mx = std::max(mx, (double)lg[e]);
+      for (int e = 0; e < E; ++e) sum += std::exp((double)lg[e] - mx);
+      const double l = mx + std::log(sum);
+      c.lse[s] = (float)l; z += l * l;
+      for (int e = 0; e < E; ++e) {
+        int rank = 0;
+        for (int f = 0; f < E; ++f) rank += (ps[f] > ps[e]) || (ps[f] == ps[e] && f < e);
+        if (rank < kp) ++cnt[e];
+      }
+    }
+    for (int e = 0; e < E; ++e) {
+      double m = 0.0;
+      for (int s = 0; s < S; ++s) m += c.p[s * E + e];
+      c.load[e] = (float)((double)cnt[e] / ((double)S * kp));
+      bal += (double)c.load[e] * (m / S);
+    }
+    c.aux[0] = (float)(z / S); c.aux[1] = (float)(E * bal);
+  }
   if (lb) {      // -sum_e log(mean_s p): the reference's kl_div against the constant 1 (PVT_AVSModel_v2.py:314-318)
     double v = 0.0;
     if (c.lb) for (int e = 0; e < E; ++e) { double m = 0.0; for (int s = 0; s < S; ++s) m += c.p[s * E + e]; v -= std::log(m / S); }
@@ -332,7 +364,8 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
 }
 
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
-             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm);
+             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
+             const float* aux_grad = nullptr);
 
 }  // namespace
 
@@ -373,6 +406,29 @@ int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, con
   if (top_k < 1) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, E]", top_k);
   return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm);
 }
+int avmoe_host_moe_forward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
+                               void* saved) {
+  (void)saved;
+  Ctx c;
+  if (int rc = setup(desc, c)) return rc;
+  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
+  if (top_k < 0 || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [0, %d]", top_k, c.E);
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
+  if (int rc = forward(c, X, Y, *params, noise, out, probs, idx, lb, true)) return rc;
+  if (aux) {
+    aux[0] = c.aux[0]; aux[1] = c.aux[1];
+    if (load) for (int e = 0; e < c.E; ++e) load[e] = c.load[e];
+  }
+  return AVMOE_OK;
+}
+int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
+                                float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
+  (void)saved;
+  if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad);
+}
 int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads) {
@@ -386,7 +442,8 @@ namespace {
 
 // the reverse pass (the forward recomputed); top_k 0 or E: the dense mixture
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
-             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm) {
+             const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
+             const float* aux_grad) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
   if (top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, %d]", top_k, c.E);
@@ -520,7 +577,9 @@ int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const a
   // ---- router: p = softmax(logits) ; + the load-balancing loss -sum_e log(mean_s p)
   if (c.lb && lb_grad) for (int e = 0; e < E; ++e) { double m = 0.0; for (int s = 0; s < S; ++s) m += c.p[s * E + e]; m /= S; for (int s = 0; s < S; ++s) dp[s * E + e] -= lb_grad[0] / (float)(S * m); }
   if (dprobs) for (long i = 0; i < (long)S * E; ++i) dp[i] += dprobs[i];                    // + the upstream gradient of probs itself
+  if (aux_grad) for (int s = 0; s < S; ++s) for (int e = 0; e < E; ++e) dp[s * E + e] += aux_grad[1] * (float)E * c.load[e] / (float)S;      // balance: on p
   softmax_rows_bwd(c.p.data(), dp.data(), S, E, E);                                            // dp -> dlogits
+  if (aux_grad) for (int s = 0; s < S; ++s) for (int e = 0; e < E; ++e) dp[s * E + e] += aux_grad[0] * (2.f / (float)S) * c.lse[s] * c.p[s * E + e];   // z: on the logits
   V dh2((long)S * 32), dh1((long)S * 128), drin((long)S * 2 * C);
   if (G.r4_w) gemm(true, false, E, 32, S, 1.f, dp.data(), E, c.h2.data(), 32, 0.f, G.r4_w, 32);
   if (G.r4_b) for (int e = 0; e < E; ++e) { double a = 0.0; for (int s = 0; s < S; ++s) a += dp[s * E + e]; G.r4_b[e] = (float)a; }

@@ -38,7 +38,8 @@ static void fill_dx_args(GemmArgs& g, const Plan& pl, const void* X, const char*
 }
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const void* dOut, const float* lb_grad,
-                 char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads_in, hipStream_t st, int parts, const float* dprobs) {
+                 char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads_in, hipStream_t st, int parts, const float* dprobs,
+                 const float* aux_grad) {
   const Dims& d = pl.d;
   if (parts == 0) parts = 7;
   if ((parts & (32 | 64)) && (d.Kcx > 0 || d.mha || d.nxn)) { set_last_error("split backward: sections 32 / 64 serve plain sites only (this one goes on accumulating into dX)"); return ERR_UNSUPPORTED; }
@@ -136,7 +137,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   // ---- phase 3: ReLU / BN1 ; router --------------------------------------------------------------
   AVMOE_TRY(k_mid_bwd(pl, sv, sc, prm, grads, st));
   BWD_STOP(5);
-  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st));
+  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad));
   BWD_STOP(6);
   // ---- phase 4: folded LayerNorm / hop-2 softmax ---------------------------------------------------
   if (d.nxn) MEMSET0(sc + pl.o_dZR, (size_t)d.NT * d.DZ * esz);

@@ -31,7 +31,8 @@ avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* 
 }
 
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const float* noise, void* out,
-                float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm) {
+                float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm,
+                float* aux_out, float* load_out) {
   const Dims& d = pl.d;
   avmoe_moe_ptrs prm = with_unit_gates(pl, prm_in, sv);
   if (d.mg) {                                              // merged groups: run on block-diagonal dense copies of the grouped weights
@@ -182,7 +183,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     AVMOE_TRY(down_gemm(X, d.NT, sv + pl.o_Z, d.zsz == 2 ? GEMM_BF16 : GEMM_F32));                              // Zx = X Wt^T
   }
   // ---- router (its input: the token means of X -- after the statistics above) ----------------------
-  AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm));
+  AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm, aux_out, load_out));
   if (d.KL > 0 && !d.fuse_l2) {                            // L2[s] = X[s] T[s]^T   (fused: per-group partial sums came out of the down projection; pre_small adds them into L2)
     GemmArgs g = base();
     g.A = X; g.B = sv + pl.o_Text; g.C = sv + pl.o_L2;
@@ -307,7 +308,14 @@ int remap_forward(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, void
   const Dims& d = pl.d;
   if (!prm.fc_b) { set_last_error("remap_forward: fc.bias missing"); return ERR_BAD_ARG; }
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
-  AVMOE_TRY(k_prep_all(pl, sv, prm, st));
+  // k_prep_all also prepares the experts' operands, by the plan's group layout: a merged-groups site (Dims::mg) must hand it the dense
+  // block-diagonal copies, as moe_forward does -- with the grouped down_sampler it would read g times the tensor's length
+  avmoe_moe_ptrs p = prm;
+  if (d.mg) {
+    AVMOE_TRY(k_merge_expand(pl, sv, prm, st));
+    p = merged_params(pl, prm, sv);
+  }
+  AVMOE_TRY(k_prep_all(pl, sv, p, st));
   {                                                        // Yt[s] = Wc Y[s]
     GemmArgs g; g.dtype = dt; g.out_dtype = dt; g.slabs = (float*)(sc + pl.o_slabs);
     g.A = sv + pl.o_WcK; g.B = Y; g.C = Yt;

@@ -1,5 +1,5 @@
-// Backward of one site when `out` gets no gradient: only a loss on the routing probabilities and / or the load-balancing loss was
-// differentiated.  Then every expert product, the Gram products and the token-space passes of the full backward would produce exact
+// Backward of one site when `out` gets no gradient: only a loss on the routing probabilities, the load-balancing loss and / or the
+// router auxiliary losses (z-loss, balance loss: avmoe_moe_backward_aux) was differentiated.  Then every expert product, the Gram products and the token-space passes of the full backward would produce exact
 // zeros; only the router and the mean / remap chain carry gradient.  Per frame s, with [g1 | g2] = d rin after the router backward
 // (g1: the mean of X, g2: the mean of Yf = fc(conv_adapter(Y)); C each):
 //   dX[s,n,:]  = g1[s] / N
@@ -199,13 +199,13 @@ __global__ void __launch_bounds__(256) kk_ro_zero(ZeroList z) {
 }  // namespace
 
 int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,
-                             char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st) {
+                             char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, const float* aux_grad) {
   const Dims& d = pl.d;
-  // the mixture's share of d probs is 0: the router backward sees only dprobs and the load-balancing term
+  // the mixture's share of d probs is 0: the router backward sees only dprobs, the load-balancing term and the auxiliary losses
   if (hipMemsetAsync(sc + pl.o_dp, 0, (size_t)d.S * d.E * sizeof(float), st) != hipSuccess) {
     set_last_error("router-only backward: memset failed"); return ERR_LAUNCH;
   }
-  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st));
+  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad));
   const float* drin = (const float*)(sc + pl.o_rbw) + (long)d.S * 128;
   const int nch = ro_chunks(d);
   float* u = (float*)(sc + pl.o_ro);

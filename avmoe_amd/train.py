@@ -656,6 +656,22 @@ def topk_experts(probs: torch.Tensor, k: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+def router_aux_total(sites, z_weight: float = 0.0, balance_weight: float = 0.0) -> torch.Tensor:
+    """sum over `sites` of z_weight * z_loss + balance_weight * balance_loss of their last forward (`site.last_router_aux`: sites with
+    `router_aux` on) as one differentiable scalar -- the term to add to the task loss.  Differentiated alone, it takes the sites'
+    router-only backward.  Raises if a listed site has no results (setting off, or no forward yet)."""
+    terms = []
+    for i, site in enumerate(sites):
+        aux = getattr(site, "last_router_aux", None)
+        if aux is None:
+            raise ValueError(f"router_aux_total: site {i} ({type(site).__name__}) has no router auxiliary losses: set site.router_aux = True "
+                             "before its forward")
+        terms.append(z_weight * aux.z_loss + balance_weight * aux.balance_loss)
+    if not terms:
+        raise ValueError("router_aux_total: no sites")
+    return torch.stack(terms).sum()
+
+
 def adapter_state_dict(model: torch.nn.Module, substrings=("adapter",), ema: Optional[FlatAdam] = None) -> Dict[str, torch.Tensor]:
     """The adapter / router entries of model.state_dict() (keys containing 'adapter': `*_adapter_blocks_p{1,2}.*`).
     ema: a FlatAdam built with `ema_decay` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), everything

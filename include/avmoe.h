@@ -203,8 +203,8 @@ int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const voi
 
 /* avmoe_moe_backward_ex (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds it by symbol) -- the backward with two more
  * upstream gradients: the gradients of  <out, dOut> + <probs, dprobs> + (*lb_grad) * lb.  The reference returns the gating probabilities
- * as an ordinary autograd tensor (PVT_AVSModel_v2.py:298,312), so a loss built on them (router entropy / z-loss, a balance term,
- * distillation of the routing) reaches the router, the remap parameters, X and Y.
+ * as an ordinary autograd tensor (PVT_AVSModel_v2.py:298,312), so a loss built on them (router entropy, a balance term,
+ * distillation of the routing; NOT the router z-loss, which needs the logits: avmoe_moe_forward_aux) reaches the router, the remap parameters, X and Y.
  *   dprobs: DEVICE pointer to (S, E) f32, or NULL for 0 (then the launched kernels and every result bit are those of
  *           avmoe_moe_backward_part with the same `parts`).  The term enters the router backward in section 1.
  *   dOut:   NULL = out gets no gradient.  Then only the router and the mean / remap chain carry gradient and no expert, Gram or
@@ -216,6 +216,35 @@ int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void*
                           const void* dOut /* NULL: out gets no gradient */, const float* dprobs /* (S,E) f32 or NULL */,
                           const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
                           const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
+
+/* avmoe_moe_forward_aux / avmoe_moe_backward_aux (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds them by symbol) --
+ * the router auxiliary losses that go with top-k routing (an extension: ST-MoE's router z-loss, Switch's balance loss).  With l the
+ * router logits of a site call (the AVS noise included), p = softmax(l), S frames, E experts:
+ *     lse_s   = logsumexp_e l_se                          z = (1 / S) sum_s lse_s^2
+ *     k'      = top_k when 0 < top_k < E, else 1
+ *     S_k'(s) = the k' most probable experts of frame s (higher probability first, equal probabilities in expert order: the rule of
+ *               avmoe_router_topk and of the top-k mixture), taken on the dense softmax
+ *     load_e  = (1 / (S k')) sum_s 1[e in S_k'(s)]        (sums to 1)          P_e = (1 / S) sum_s p_se
+ *     balance = E sum_e load_e P_e                        (1 at a uniform router)
+ * avmoe_moe_forward_aux is avmoe_moe_forward (top_k == 0 or E) / avmoe_moe_forward_topk (0 < top_k < E) with two more outputs:
+ *   aux:  DEVICE pointer to 2 floats [z, balance], or NULL: then exactly those entry points, launch for launch.
+ *   load: DEVICE pointer to E floats, or NULL (ignored when aux is NULL).
+ * out, probs, idx and lb have the bits of the call without aux.  The losses come out of one small one-block launch after the router
+ * (fixed summation order: the results repeat bit for bit); on a site with lb_loss that launch forms lb too, in place of its own.
+ * avmoe_moe_backward_aux is avmoe_moe_backward_ex with one more upstream gradient:
+ *   aux_grad: DEVICE pointer to 2 floats [g_z, g_balance], or NULL (then avmoe_moe_backward_ex, bit for bit).  It must follow a
+ *             forward that had aux != NULL (`saved` carries lse and load).  The gradients are those of
+ *             <out, dOut> + <probs, dprobs> + (*lb_grad) * lb + g_z * z + g_balance * balance:
+ *             d balance / d p_se = E load_e / S joins the gradient of p before the softmax Jacobian (the selection carries no gradient,
+ *             as in the mixture), d z / d l_se = (2 / S) lse_s p_se is added to the gradient of the logits after it.  No launch is
+ *             added.  dOut == NULL takes the router-only path as in avmoe_moe_backward_ex.                                          */
+int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                          const float* noise, int32_t top_k /* 0: dense */, int32_t renorm, void* out, float* probs, int64_t* idx,
+                          float* lb, float* aux /* [z, balance] or NULL */, float* load /* (E) or NULL */, void* saved, void* scratch,
+                          void* stream);
+int avmoe_moe_backward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                           const void* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad /* [g_z, g_balance] or NULL */,
+                           void* saved, void* scratch, void* dX, void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
 
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:

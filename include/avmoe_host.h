@@ -47,6 +47,17 @@ int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, con
                                  const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                  const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
 
+/* as avmoe_moe_forward_aux: the router auxiliary losses aux = [z, balance] and load (E) beside the forward's outputs (top_k 0: dense;
+ * aux NULL: avmoe_host_moe_forward / _forward_topk).                                                                              */
+int avmoe_host_moe_forward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
+                               void* saved);
+
+/* as avmoe_moe_backward_aux: avmoe_host_moe_backward_ex / _topk (top_k 0: dense) plus aux_grad = [g_z, g_balance] or NULL.           */
+int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
+                                float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
+
 #ifdef __cplusplus
 }
 #endif
