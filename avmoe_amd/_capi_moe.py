@@ -136,27 +136,18 @@ def declare(L):
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
-    if hasattr(L, "avmoe_opt_adam_step"):            # (found by symbol: added under ABI 11 -- the optimizer with device-side state)
+    if hasattr(L, "avmoe_opt_swap_ema"):             # (found by its newest symbol: the optimizer with device-side state, one tree builds all of it)
+        step_args = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p]
+        norm_args = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p]
         L.avmoe_opt_workspace_bytes.restype = C.c_size_t
         L.avmoe_opt_workspace_bytes.argtypes = [C.POINTER(OptRange), C.c_int32, C.POINTER(OptLayout)]
-        L.avmoe_opt_table_build.restype = C.c_int
-        L.avmoe_opt_table_build.argtypes = [C.POINTER(OptRange), C.c_int32, C.c_void_p, C.c_size_t]
-        L.avmoe_opt_grad_norm.restype = C.c_int
-        L.avmoe_opt_grad_norm.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32,
-                                          C.c_float, C.c_float, C.c_void_p]
-        L.avmoe_opt_adam_step.restype = C.c_int
-        L.avmoe_opt_adam_step.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          C.c_int32, C.c_void_p]
-    if hasattr(L, "avmoe_opt_grad_norm_sched"):      # (found by symbol: the per-step learning-rate schedule)
-        L.avmoe_opt_grad_norm_sched.restype = C.c_int
-        L.avmoe_opt_grad_norm_sched.argtypes = L.avmoe_opt_grad_norm.argtypes + [C.POINTER(OptSchedule)]
-    if hasattr(L, "avmoe_opt_swap_ema"):             # (found by symbol: the weight average kept on the device)
-        L.avmoe_opt_grad_norm_ema.restype = C.c_int
-        L.avmoe_opt_grad_norm_ema.argtypes = L.avmoe_opt_grad_norm.argtypes + [C.POINTER(OptSchedule), C.POINTER(OptEma)]
-        L.avmoe_opt_adam_step_ema.restype = C.c_int
-        L.avmoe_opt_adam_step_ema.argtypes = L.avmoe_opt_adam_step.argtypes + [C.c_void_p]
-        L.avmoe_opt_swap_ema.restype = C.c_int
-        L.avmoe_opt_swap_ema.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+        for name, args in (("table_build", [C.POINTER(OptRange), C.c_int32, C.c_void_p, C.c_size_t]),
+                           ("grad_norm", norm_args), ("grad_norm_sched", norm_args + [C.POINTER(OptSchedule)]),
+                           ("grad_norm_ema", norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma)]),
+                           ("adam_step", step_args), ("adam_step_ema", step_args + [C.c_void_p]),
+                           ("swap_ema", [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p])):
+            fn = getattr(L, "avmoe_opt_" + name)
+            fn.restype, fn.argtypes = C.c_int, args
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

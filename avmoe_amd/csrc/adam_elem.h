@@ -35,11 +35,12 @@ __device__ __forceinline__ void ema_elem(float& e, float p, float d) {
 }
 
 // elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail.
-// EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register.
-template <bool DECOUPLED, bool EMA = false>
+// EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register, with decay d
+// (without it `ema` and `d` are not read).
+template <bool DECOUPLED, bool EMA>
 __device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long i0,
                                           long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale,
-                                          float* __restrict__ ema = nullptr, float d = 0.f) {
+                                          float* __restrict__ ema, float d) {
   if (i0 + 3 < n) {
     float4 pp = *(float4*)(p + i0), mm = *(float4*)(m + i0), vv = *(float4*)(v + i0);
     const float4 gg = *(const float4*)(g + i0);

@@ -1,17 +1,19 @@
 // The optimizer with its state on the device (include/avmoe.h, "optimizer with device-side state"): every (param, grad, exp_avg,
 // exp_avg_sq) range the optimizer owns is one entry of a table in device memory, and three launches serve a step whatever the number of
 // buckets and ranges --
-//   kk_opt_sqsum     sum of (grad * grad_scale)^2 per 1024-element block, in double, into the partial-sum workspace
-//   kk_opt_finalize  one block adds the partial sums in a fixed order and writes the state block: norm, clip factor, skip flag, step
-//                    counters, bias corrections (kk_opt_finalize_sched: and the learning-rate factor of a per-step schedule;
-//                    kk_opt_finalize_ema: and the decay of the weight average for this step)
-//   kk_opt_adam      the Adam / AdamW update of every range; reads the state block, writes nothing when the step is skipped
-//                    (kk_opt_adam_ema: the thread that holds an element's new value also advances its average, ema = d ema + (1 - d) p,
-//                    in a shadow buffer per range -- two more 4-byte streams per element, no launch more)
+//   kk_opt_sqsum                           sum of (grad * grad_scale)^2 per 1024-element block, in double, into the partial-sum workspace
+//   kk_opt_finalize<SCHED, EMA>            one block adds the partial sums in a fixed order and writes the state block: norm, clip factor,
+//                                          skip flag, step counters, bias corrections; SCHED: and the learning-rate factor of a per-step
+//                                          schedule; EMA: and the decay of the weight average for this step
+//   kk_opt_adam<DECOUPLED, SCHED, EMA>     the Adam / AdamW update of every range; reads the state block, writes nothing when the step is
+//                                          skipped; EMA: the thread that holds an element's new value also advances its average,
+//                                          ema = d ema + (1 - d) p, in a shadow buffer per range -- two more 4-byte streams per element
 // and one launch beside the step --
-//   kk_opt_swap      exchanges every range's parameters with their averages (evaluation with the averaged weights, and back)
-// Plain bandwidth kernels: 16-byte loads and stores, no matrix pipe, LDS only for the block reduction.  No floating-point atomics: the norm
-// repeats bit for bit.
+//   kk_opt_swap                            exchanges every range's parameters with their averages (evaluation with the averaged weights,
+//                                          and back)
+// Each body exists once; the host picks an instantiation from a table indexed by the flag bits, and every instantiation of a kernel takes
+// the same arguments (those of an option that is off are not read).  Plain bandwidth kernels: 16-byte loads and stores, no matrix pipe,
+// LDS only for the block reduction.  No floating-point atomics: the norm repeats bit for bit.
 #include "../../include/avmoe.h"
 #include "common.h"
 #include "adam_elem.h"
@@ -30,32 +32,27 @@ struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
 struct OptBlock { int32_t range, block; };
 static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
 
-__device__ __forceinline__ const avmoe_opt_range* opt_ranges(const void* table) { return (const avmoe_opt_range*)((const char*)table + sizeof(OptHeader)); }
-__device__ __forceinline__ const OptBlock* opt_blocks(const void* table, int n_ranges) {
-  return (const OptBlock*)((const char*)table + sizeof(OptHeader) + (size_t)n_ranges * sizeof(avmoe_opt_range));
+// What a thread of a one-block-per-table-block launch serves: elements [i0, min(i0 + 4, r.n)) of range `range`.
+struct OptWork { int32_t n_ranges, range; avmoe_opt_range r; long i0; };
+
+// -> false where the thread has nothing to touch: a launch whose grid does not match the table (a stale or foreign image: wrong magic, a
+// block past n_blocks, a range index outside the table), or a thread past the end of its range.
+__device__ __forceinline__ bool opt_work(const void* __restrict__ table, OptWork& w) {
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return false;
+  const char* ranges = (const char*)table + sizeof(OptHeader);
+  const OptBlock b = ((const OptBlock*)(ranges + (size_t)h.n_ranges * sizeof(avmoe_opt_range)))[blockIdx.x];
+  if (b.range < 0 || b.range >= h.n_ranges) return false;
+  w.n_ranges = h.n_ranges;
+  w.range = b.range;
+  w.r = ((const avmoe_opt_range*)ranges)[b.range];
+  w.i0 = ((long)b.block * 256 + threadIdx.x) * 4;
+  return w.i0 < w.r.n;
 }
 
-// sum over the block's elements of ((double)grad * grad_scale)^2 -> partials[blockIdx.x].  A launch whose grid does not match the table
-// (a stale or foreign image) touches nothing but its own partial sum.
-__global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ table, double* __restrict__ partials, float grad_scale) {
+// one value per thread of a 256-thread block -> their sum, by a tree over LDS: a fixed order of additions
+__device__ __forceinline__ double block_sum_256(double acc) {
   __shared__ double red[256];
-  const OptHeader h = *(const OptHeader*)table;
-  double acc = 0.0;
-  if (h.magic == OPT_MAGIC && (long)blockIdx.x < h.n_blocks) {
-    const OptBlock b = opt_blocks(table, h.n_ranges)[blockIdx.x];
-    if (b.range >= 0 && b.range < h.n_ranges) {
-      const avmoe_opt_range r = opt_ranges(table)[b.range];
-      const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
-      const double gs = (double)grad_scale;
-      if (i0 + 3 < r.n) {
-        const float4 g = *(const float4*)(r.grad + i0);
-        const double a = (double)g.x * gs, c = (double)g.y * gs, d = (double)g.z * gs, e = (double)g.w * gs;
-        acc = a * a + c * c + d * d + e * e;
-      } else {
-        for (long i = i0; i < r.n && i < i0 + 4; ++i) { const double a = (double)r.grad[i] * gs; acc += a * a; }
-      }
-    }
-  }
   red[threadIdx.x] = acc;
   __syncthreads();
 #pragma unroll
@@ -63,7 +60,28 @@ __global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ tab
     if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
     __syncthreads();
   }
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+  return red[0];
+}
+
+// sum over the block's elements of ((double)grad * grad_scale)^2 -> partials[blockIdx.x].  A launch whose grid does not match the table
+// (a stale or foreign image) touches nothing but its own partial sum.
+__global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ table, double* __restrict__ partials, float grad_scale) {
+  OptWork w;
+  double acc = 0.0;
+  if (opt_work(table, w)) {
+    const avmoe_opt_range& r = w.r;
+    const long i0 = w.i0;
+    const double gs = (double)grad_scale;
+    if (i0 + 3 < r.n) {
+      const float4 g = *(const float4*)(r.grad + i0);
+      const double a = (double)g.x * gs, c = (double)g.y * gs, d = (double)g.z * gs, e = (double)g.w * gs;
+      acc = a * a + c * c + d * d + e * e;
+    } else {
+      for (long i = i0; i < r.n; ++i) { const double a = (double)r.grad[i] * gs; acc += a * a; }
+    }
+  }
+  const double sum = block_sum_256(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // the factor of a per-step schedule at n applied steps (include/avmoe.h, avmoe_opt_schedule), in double.  Contraction is off so that the
@@ -98,22 +116,16 @@ __device__ __forceinline__ double ema_decay(const avmoe_opt_ema& e, int64_t n) {
 // SCHED: the step that is applied now is number n = applied_steps before it (the first one has n = 0); its factor goes into the state
 // block, rounded once to fp32.  A skipped step leaves the factor alone.
 // EMA: the average's decay for this step, from n = applied_steps AFTER it (the first one has n = 1), likewise.
-template <bool SCHED, bool EMA = false>
-__device__ __forceinline__ void opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state, float max_norm,
-                                             int clip, int skip_nonfinite, float beta1, float beta2, const avmoe_opt_schedule& sched,
-                                             const avmoe_opt_ema& ema = avmoe_opt_ema{}) {
-  __shared__ double red[256];
+// The schedule and the average's constants ride in the kernel arguments: constants of the run, so a captured launch replays them.
+template <bool SCHED, bool EMA>
+__global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
+                                                       float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
+                                                       avmoe_opt_schedule sched, avmoe_opt_ema ema) {
   double acc = 0.0;
   for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
+  const double sum = block_sum_256(acc);
   if (threadIdx.x != 0) return;
-  const float total = (float)sqrt(red[0]);
+  const float total = (float)sqrt(sum);
   float coef = 1.0f;
   if (clip) {                                           // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1); NaN stays NaN
     const float c = max_norm / (total + 1e-6f);
@@ -137,97 +149,61 @@ __device__ __forceinline__ void opt_finalize(const double* __restrict__ partials
   }
 }
 
-__global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
-                                                       float max_norm, int clip, int skip_nonfinite, float beta1, float beta2) {
-  opt_finalize<false>(partials, n_partials, state, max_norm, clip, skip_nonfinite, beta1, beta2, avmoe_opt_schedule{});
-}
-
-// the schedule rides in the kernel arguments: constants of the run, so a captured launch replays them
-__global__ void __launch_bounds__(256) kk_opt_finalize_sched(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
-                                                             float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
-                                                             avmoe_opt_schedule sched) {
-  opt_finalize<true>(partials, n_partials, state, max_norm, clip, skip_nonfinite, beta1, beta2, sched);
-}
-
-template <bool SCHED>
-__global__ void __launch_bounds__(256) kk_opt_finalize_ema(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
-                                                           float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
-                                                           avmoe_opt_schedule sched, avmoe_opt_ema ema) {
-  opt_finalize<SCHED, true>(partials, n_partials, state, max_norm, clip, skip_nonfinite, beta1, beta2, sched, ema);
-}
-
 // the shadow buffer of range `range`, or NULL where the pointer array was not made for this table (another range count) or the entry
 // cannot take 16-byte accesses: such a launch touches nothing
-__device__ __forceinline__ float* opt_shadow(const OptHeader& h, float* const* __restrict__ shadows, int n_shadows, int range) {
-  if (h.n_ranges != n_shadows) return nullptr;
-  float* e = shadows[range];
+__device__ __forceinline__ float* opt_shadow(const OptWork& w, float* const* __restrict__ shadows, int n_shadows) {
+  if (w.n_ranges != n_shadows) return nullptr;
+  float* e = shadows[w.range];
   return ((uintptr_t)e & 15u) == 0 ? e : nullptr;
 }
 
 // SCHED: the range's rate times the state block's lr_factor, for the update and for the decoupled decay term alike
 // EMA: shadows[range] is the range's average; the state block's ema_decay is this step's d
-template <bool DECOUPLED, bool SCHED, bool EMA = false>
-__device__ __forceinline__ void opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2, float eps,
-                                         float grad_scale, float* const* __restrict__ shadows = nullptr, int n_shadows = 0) {
-  const OptHeader h = *(const OptHeader*)table;
-  if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return;
+template <bool DECOUPLED, bool SCHED, bool EMA>
+__global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                   float eps, float grad_scale, float* const* __restrict__ shadows, int n_shadows) {
   if (state->skip) return;                              // a skipped step writes nothing: p, m, v (and the average) stay bit for bit
-  const OptBlock b = opt_blocks(table, h.n_ranges)[blockIdx.x];
-  if (b.range < 0 || b.range >= h.n_ranges) return;
-  const avmoe_opt_range r = opt_ranges(table)[b.range];
-  const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
-  if (i0 >= r.n) return;
+  OptWork w;
+  if (!opt_work(table, w)) return;
+  const avmoe_opt_range& r = w.r;
   float lr = r.lr;
   if constexpr (SCHED) lr *= state->lr_factor;
-  // one multiplier for the gradient: grad_scale * clip factor (== grad_scale exactly when the factor is 1)
+  float* e = nullptr;
+  float d = 0.f;
   if constexpr (EMA) {
-    float* e = opt_shadow(h, shadows, n_shadows, b.range);
+    e = opt_shadow(w, shadows, n_shadows);
     if (!e) return;
-    adam_quad<DECOUPLED, true>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1,
-                               state->bc2_sqrt, grad_scale * state->clip_coef, e, state->ema_decay);
-  } else {
-    adam_quad<DECOUPLED>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
-                         grad_scale * state->clip_coef);
+    d = state->ema_decay;
   }
-}
-
-template <bool DECOUPLED>
-__global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
-                                                   float eps, float grad_scale) {
-  opt_adam<DECOUPLED, false>(table, state, b1, b2, eps, grad_scale);
-}
-
-template <bool DECOUPLED>
-__global__ void __launch_bounds__(256) kk_opt_adam_sched(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
-                                                         float eps, float grad_scale) {
-  opt_adam<DECOUPLED, true>(table, state, b1, b2, eps, grad_scale);
-}
-
-template <bool DECOUPLED, bool SCHED>
-__global__ void __launch_bounds__(256) kk_opt_adam_ema(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
-                                                       float eps, float grad_scale, float* const* __restrict__ shadows, int n_shadows) {
-  opt_adam<DECOUPLED, SCHED, true>(table, state, b1, b2, eps, grad_scale, shadows, n_shadows);
+  // one multiplier for the gradient: grad_scale * clip factor (== grad_scale exactly when the factor is 1)
+  adam_quad<DECOUPLED, EMA>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, w.i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
+                            grad_scale * state->clip_coef, e, d);
 }
 
 // param[i] <-> shadow[i] for every element of every range; alignment padding belongs to no range and is not touched
 __global__ void __launch_bounds__(256) kk_opt_swap(const void* __restrict__ table, float* const* __restrict__ shadows, int n_shadows) {
-  const OptHeader h = *(const OptHeader*)table;
-  if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return;
-  const OptBlock b = opt_blocks(table, h.n_ranges)[blockIdx.x];
-  if (b.range < 0 || b.range >= h.n_ranges) return;
-  const avmoe_opt_range r = opt_ranges(table)[b.range];
-  const long i0 = ((long)b.block * 256 + threadIdx.x) * 4;
-  if (i0 >= r.n) return;
-  float* __restrict__ e = opt_shadow(h, shadows, n_shadows, b.range);
+  OptWork w;
+  if (!opt_work(table, w)) return;
+  float* __restrict__ e = opt_shadow(w, shadows, n_shadows);
   if (!e) return;
-  float* __restrict__ p = r.param;
-  if (i0 + 3 < r.n) {
+  float* __restrict__ p = w.r.param;
+  const long i0 = w.i0, n = w.r.n;
+  if (i0 + 3 < n) {
     const float4 pp = *(const float4*)(p + i0), ee = *(const float4*)(e + i0);
     *(float4*)(p + i0) = ee; *(float4*)(e + i0) = pp;
   } else {
-    for (long i = i0; i < r.n; ++i) { const float a = p[i]; p[i] = e[i]; e[i] = a; }
+    for (long i = i0; i < n; ++i) { const float a = p[i]; p[i] = e[i]; e[i] = a; }
   }
 }
+
+// the instantiations, indexed by the flag bits: an option more is a template parameter more and an initialiser twice as long
+using FinalizeKernel = decltype(&kk_opt_finalize<false, false>);
+using AdamKernel = decltype(&kk_opt_adam<false, false, false>);
+constexpr FinalizeKernel OPT_FINALIZE[4] = {   // [SCHED | EMA << 1]
+    kk_opt_finalize<false, false>, kk_opt_finalize<true, false>, kk_opt_finalize<false, true>, kk_opt_finalize<true, true>};
+constexpr AdamKernel OPT_ADAM[8] = {           // [DECOUPLED | SCHED << 1 | EMA << 2]
+    kk_opt_adam<false, false, false>, kk_opt_adam<true, false, false>, kk_opt_adam<false, true, false>, kk_opt_adam<true, true, false>,
+    kk_opt_adam<false, false, true>,  kk_opt_adam<true, false, true>,  kk_opt_adam<false, true, true>,  kk_opt_adam<true, true, true>};
 
 static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
 
@@ -257,11 +233,19 @@ static size_t table_bytes_of(int32_t n_ranges, int64_t n_blocks) {
   return round16(sizeof(OptHeader) + (size_t)n_ranges * sizeof(avmoe_opt_range) + (size_t)n_blocks * sizeof(OptBlock));
 }
 
-static int check_launch_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const void* state, float beta1, float beta2) {
-  if (!table || !state) { set_last_error("%s: NULL table / state", who); return ERR_BAD_ARG; }
+// the table half of a launch's arguments: all avmoe_opt_swap_ema has
+static int check_table_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks) {
+  if (!table) { set_last_error("%s: NULL table", who); return ERR_BAD_ARG; }
   if (n_ranges < 0 || n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("%s: bad range / block count", who); return ERR_BAD_ARG; }
-  if (((uintptr_t)state & 15u) != 0) { set_last_error("%s: the state block must be 16-byte aligned", who); return ERR_BAD_ARG; }
   if (((uintptr_t)table & 15u) != 0) { set_last_error("%s: the table must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  return OK;
+}
+
+// the state block first: a misaligned one is a bad argument whatever the table's alignment
+static int check_launch_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const void* state, float beta1, float beta2) {
+  if (!state) { set_last_error("%s: NULL state", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)state & 15u) != 0) { set_last_error("%s: the state block must be 16-byte aligned", who); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_table_args(who, table, n_ranges, n_blocks));
   if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) { set_last_error("%s: betas must be in [0, 1)", who); return ERR_BAD_ARG; }
   return OK;
 }
@@ -302,18 +286,19 @@ static int check_shadows(const char* who, float* const* shadows) {
 
 constexpr int32_t OPT_FLAGS = AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY;
 
-// avmoe_opt_grad_norm (sched == NULL), avmoe_opt_grad_norm_sched and avmoe_opt_grad_norm_ema: the same checks and the same norm launch, then the
-// finalize kernel the flags ask for
+// avmoe_opt_grad_norm (sched == NULL, ema == NULL), avmoe_opt_grad_norm_sched (ema == NULL) and avmoe_opt_grad_norm_ema: the same checks and
+// the same norm launch, then the finalize kernel the flags ask for
 static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
-                     float max_norm, int32_t flags, int32_t known_flags, float beta1, float beta2, const avmoe_opt_schedule* sched, void* stream,
-                     const avmoe_opt_ema* ema = nullptr) {
+                     float max_norm, int32_t flags, int32_t known_flags, float beta1, float beta2, const avmoe_opt_schedule* sched,
+                     const avmoe_opt_ema* ema, void* stream) {
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
   const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
+  const bool with_sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, with_ema = (flags & AVMOE_OPT_EMA) != 0;
   if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
   if (clip && !(max_norm >= 0.f)) { set_last_error("%s: max_norm must be >= 0 and not NaN", who); return ERR_BAD_ARG; }
   if (!(grad_scale == grad_scale)) { set_last_error("%s: grad_scale is NaN", who); return ERR_BAD_ARG; }
-  if (flags & AVMOE_OPT_LR_SCHEDULE) AVMOE_TRY(check_schedule(who, sched));
-  if (flags & AVMOE_OPT_EMA) AVMOE_TRY(check_ema(who, ema));
+  if (with_sched) AVMOE_TRY(check_schedule(who, sched));
+  if (with_ema) AVMOE_TRY(check_ema(who, ema));
   const bool norm = (clip || skip) && n_blocks > 0;
   if (norm) {
     if (!partials) { set_last_error("%s: partials is NULL", who); return ERR_BAD_ARG; }
@@ -321,18 +306,9 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
     hipLaunchKernelGGL(kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials, grad_scale);
     AVMOE_CHECK_LAUNCH("opt_sqsum");
   }
-  if ((flags & AVMOE_OPT_EMA) && (flags & AVMOE_OPT_LR_SCHEDULE))
-    hipLaunchKernelGGL(kk_opt_finalize_ema<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state,
-                       max_norm, (int)clip, (int)skip, beta1, beta2, *sched, *ema);
-  else if (flags & AVMOE_OPT_EMA)
-    hipLaunchKernelGGL(kk_opt_finalize_ema<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state,
-                       max_norm, (int)clip, (int)skip, beta1, beta2, avmoe_opt_schedule{}, *ema);
-  else if (flags & AVMOE_OPT_LR_SCHEDULE)
-    hipLaunchKernelGGL(kk_opt_finalize_sched, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state,
-                       max_norm, (int)clip, (int)skip, beta1, beta2, *sched);
-  else
-    hipLaunchKernelGGL(kk_opt_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, norm ? (long)n_blocks : 0L, state, max_norm,
-                       (int)clip, (int)skip, beta1, beta2);
+  hipLaunchKernelGGL(OPT_FINALIZE[(int)with_sched | (int)with_ema << 1], dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials,
+                     norm ? (long)n_blocks : 0L, state, max_norm, (int)clip, (int)skip, beta1, beta2, with_sched ? *sched : avmoe_opt_schedule{},
+                     with_ema ? *ema : avmoe_opt_ema{});
   AVMOE_CHECK_LAUNCH("opt_finalize");
   return OK;
 }
@@ -343,27 +319,11 @@ static int adam_step(const char* who, const void* table, int32_t n_ranges, int64
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
   if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
   if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("%s: eps must be >= 0, grad_scale not NaN", who); return ERR_BAD_ARG; }
-  const bool ema = (flags & AVMOE_OPT_EMA) != 0;
+  const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
   if (ema) AVMOE_TRY(check_shadows(who, shadows));
   if (n_blocks == 0) return OK;
-  const bool sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0;
-  const dim3 grid((unsigned)n_blocks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (ema) {
-    const int nr = (int)n_ranges;
-    if (sched && dec) hipLaunchKernelGGL((kk_opt_adam_ema<true, true>), grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale, shadows, nr);
-    else if (sched) hipLaunchKernelGGL((kk_opt_adam_ema<false, true>), grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale, shadows, nr);
-    else if (dec) hipLaunchKernelGGL((kk_opt_adam_ema<true, false>), grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale, shadows, nr);
-    else hipLaunchKernelGGL((kk_opt_adam_ema<false, false>), grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale, shadows, nr);
-  } else if (sched && dec) {
-    hipLaunchKernelGGL(kk_opt_adam_sched<true>, grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale);
-  } else if (sched) {
-    hipLaunchKernelGGL(kk_opt_adam_sched<false>, grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale);
-  } else if (dec) {
-    hipLaunchKernelGGL(kk_opt_adam<true>, grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale);
-  } else {
-    hipLaunchKernelGGL(kk_opt_adam<false>, grid, block, 0, st, table, state, beta1, beta2, eps, grad_scale);
-  }
+  hipLaunchKernelGGL(OPT_ADAM[(int)dec | (int)sched << 1 | (int)ema << 2], dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state,
+                     beta1, beta2, eps, grad_scale, shadows, (int)n_ranges);
   AVMOE_CHECK_LAUNCH("opt_adam");
   return OK;
 }
@@ -405,13 +365,14 @@ int avmoe_opt_table_build(const avmoe_opt_range* ranges, int32_t n_ranges, void*
 
 int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                         float max_norm, int32_t flags, float beta1, float beta2, void* stream) {
-  return grad_norm("avmoe_opt_grad_norm", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS, beta1, beta2, nullptr, stream);
+  return grad_norm("avmoe_opt_grad_norm", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS, beta1, beta2, nullptr, nullptr,
+                   stream);
 }
 
 int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                               float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched) {
   return grad_norm("avmoe_opt_grad_norm_sched", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE,
-                   beta1, beta2, sched, stream);
+                   beta1, beta2, sched, nullptr, stream);
 }
 
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
@@ -424,7 +385,7 @@ int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_block
                             float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
                             const avmoe_opt_ema* ema) {
   return grad_norm("avmoe_opt_grad_norm_ema", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
-                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, stream, ema);
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, ema, stream);
 }
 
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
@@ -435,9 +396,7 @@ int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_block
 
 int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, float* const* shadows, void* stream) {
   const char* who = "avmoe_opt_swap_ema";
-  if (!table) { set_last_error("%s: NULL table", who); return ERR_BAD_ARG; }
-  if (n_ranges < 0 || n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("%s: bad range / block count", who); return ERR_BAD_ARG; }
-  if (((uintptr_t)table & 15u) != 0) { set_last_error("%s: the table must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  AVMOE_TRY(check_table_args(who, table, n_ranges, n_blocks));
   AVMOE_TRY(check_shadows(who, shadows));
   if (n_blocks == 0) return OK;
   hipLaunchKernelGGL(kk_opt_swap, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, shadows, (int)n_ranges);

@@ -315,12 +315,8 @@ class FlatAdam:
 
     def _build_device_state(self):
         L = capi.lib()
-        if not hasattr(L, "avmoe_opt_adam_step"):
+        if not hasattr(L, "avmoe_opt_swap_ema"):
             raise capi.AvmoeError("this libavmoe_hip.so lacks the device-side optimizer (avmoe_opt_*): rebuild it")
-        if self.lr_schedule is not None and not hasattr(L, "avmoe_opt_grad_norm_sched"):
-            raise capi.AvmoeError("this libavmoe_hip.so lacks the per-step schedule (avmoe_opt_grad_norm_sched): rebuild it")
-        if self.ema_decay is not None and not hasattr(L, "avmoe_opt_swap_ema"):
-            raise capi.AvmoeError("this libavmoe_hip.so lacks the weight average (avmoe_opt_*_ema): rebuild it")
         devs = {s["p"].device for s in self.state}
         if len(devs) != 1:
             raise capi.AvmoeError("FlatAdam's device path needs every bucket on one GPU")
@@ -447,25 +443,15 @@ class FlatAdam:
         if self._device:                                 # every bucket at once, scalars from the device state block
             stream = torch.cuda.current_stream(self._dev).cuda_stream
             n = len(self._plist)
-            if self.ema_decay is not None:               # the same launches; finalize also writes d_n, the update also averages
-                sched = None if self._sched_c is None else C.byref(self._sched_c)
-                capi.check(L.avmoe_opt_grad_norm_ema(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
-                                                     self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream, sched,
-                                                     C.byref(self._ema_c)), "avmoe_opt_grad_norm_ema")
-                capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
-                                                     self.eps, scale, self._flags, stream, self._shadow_ptrs.data_ptr()),
-                           "avmoe_opt_adam_step_ema")
-                return
-            if self._sched_c is not None:                # the same launches; the finalize kernel also evaluates f(applied_steps)
-                capi.check(L.avmoe_opt_grad_norm_sched(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
-                                                       self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
-                                                       C.byref(self._sched_c)), "avmoe_opt_grad_norm_sched")
-            else:
-                capi.check(L.avmoe_opt_grad_norm(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
-                                                 self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream),
-                           "avmoe_opt_grad_norm")
-            capi.check(L.avmoe_opt_adam_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
-                                             self.eps, scale, self._flags, stream), "avmoe_opt_adam_step")
+            # the entry points that know every flag: an option that is off is a flag not set and a NULL argument, and the flags choose
+            # the kernels (finalize also writes f(applied_steps) and d_n, the update also averages -- the same three launches)
+            capi.check(L.avmoe_opt_grad_norm_ema(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                                 self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
+                                                 None if self._sched_c is None else C.byref(self._sched_c),
+                                                 None if self.ema_decay is None else C.byref(self._ema_c)), "avmoe_opt_grad_norm_ema")
+            capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
+                                                 self.eps, scale, self._flags, stream,
+                                                 None if self.ema_decay is None else self._shadow_ptrs.data_ptr()), "avmoe_opt_adam_step_ema")
             return
         for s in self.state:
             for (o, e, r) in s["ranges"]:
@@ -548,8 +534,6 @@ class FlatAdam:
             if not self._device:
                 raise ValueError("the state dict carries a per-step lr_schedule, which needs FlatAdam's device path: build the optimizer "
                                  "with lr_schedule (or max_grad_norm / decoupled_weight_decay / skip_nonfinite)")
-            if not hasattr(capi.lib(), "avmoe_opt_grad_norm_sched"):
-                raise capi.AvmoeError("this libavmoe_hip.so lacks the per-step schedule (avmoe_opt_grad_norm_sched): rebuild it")
             saved_sched = saved_sched if isinstance(saved_sched, LRSchedule) else LRSchedule(**saved_sched)
         saved_ema = extra.get("ema") if self.ema_decay is not None else None
         if saved_ema is not None:
