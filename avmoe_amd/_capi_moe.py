@@ -7,6 +7,7 @@ from typing import Dict, List
 MAX_EXPERTS = 16
 OPT_CLIP, OPT_SKIP_NONFINITE, OPT_DECOUPLED_DECAY, OPT_LR_SCHEDULE = 1, 2, 4, 8      # flags of avmoe_opt_grad_norm[_sched] / avmoe_opt_adam_step
 OPT_EMA = 16                                                        # ... of avmoe_opt_grad_norm_ema / avmoe_opt_adam_step_ema only
+OPT_REPORT = 32                                                     # ... of avmoe_opt_grad_norm_report only
 SCHED_KINDS = {"none": 0, "cosine": 1, "linear": 2, "step": 3}      # AVMOE_SCHED_*
 VARIANT = {"ave": 0, "avqa": 0, "avvp": 1, "avs": 2}
 SELF_ATTN = {"none": 0, "v2": 1, "nxn": 2, "v1": 3}
@@ -39,6 +40,11 @@ class OptSchedule(C.Structure):
 class OptEma(C.Structure):
     """avmoe_opt_ema: the host constants of the weight average, d_n = min(decay, (1 + n) / (warmup + n))"""
     _fields_ = [("decay", C.c_float), ("warmup", C.c_float)]
+
+
+class OptReportHeader(C.Structure):
+    """avmoe_opt_report_header: what precedes the per-range norms in a report buffer"""
+    _fields_ = [("first_nonfinite", C.c_int32), ("n_ranges", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 # avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
@@ -148,6 +154,10 @@ def declare(L):
                            ("swap_ema", [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p])):
             fn = getattr(L, "avmoe_opt_" + name)
             fn.restype, fn.argtypes = C.c_int, args
+        if hasattr(L, "avmoe_opt_grad_norm_report"):  # (found by symbol: the per-range gradient norms)
+            L.avmoe_opt_report_bytes.restype, L.avmoe_opt_report_bytes.argtypes = C.c_size_t, [C.c_int32]
+            L.avmoe_opt_grad_norm_report.restype = C.c_int
+            L.avmoe_opt_grad_norm_report.argtypes = norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma), C.c_void_p]
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

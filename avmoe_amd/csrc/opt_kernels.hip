@@ -8,9 +8,17 @@
 //   kk_opt_adam<DECOUPLED, SCHED, EMA>     the Adam / AdamW update of every range; reads the state block, writes nothing when the step is
 //                                          skipped; EMA: the thread that holds an element's new value also advances its average,
 //                                          ema = d ema + (1 - d) p, in a shadow buffer per range -- two more 4-byte streams per element
+// one more launch per step under AVMOE_OPT_REPORT --
+//   kk_opt_range_norms                     one wave per range adds the range's block partial sums in a fixed order and writes the range's
+//                                          norm into the report buffer; a range whose norm is not finite lowers the report's
+//                                          first_nonfinite with an integer atomicMin (a minimum does not depend on the order)
 // and one launch beside the step --
 //   kk_opt_swap                            exchanges every range's parameters with their averages (evaluation with the averaged weights,
 //                                          and back)
+// The per-range norms are a kernel of their own, next to finalize, and not a part of it: finalize is ONE block whose additions define the
+// bits of total_norm, and a model has thousands of ranges -- a wave per range over many blocks finishes them in the time finalize takes,
+// inside finalize they would wait on one block's 256 threads and stretch the serial part of every step.  Finalize only resets the
+// report's header (first_nonfinite = -1) before the range kernel runs behind it on the same stream.
 // Each body exists once; the host picks an instantiation from a table indexed by the flag bits, and every instantiation of a kernel takes
 // the same arguments (those of an option that is off are not read).  Plain bandwidth kernels: 16-byte loads and stores, no matrix pipe,
 // LDS only for the block reduction.  No floating-point atomics: the norm repeats bit for bit.
@@ -18,6 +26,7 @@
 #include "common.h"
 #include "adam_elem.h"
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -31,6 +40,7 @@ constexpr uint32_t OPT_MAGIC = 0x4f50544du;      // "OPTM"
 struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
 struct OptBlock { int32_t range, block; };
 static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
+static_assert(sizeof(avmoe_opt_report_header) == 16, "report layout");
 
 // What a thread of a one-block-per-table-block launch serves: elements [i0, min(i0 + 4, r.n)) of range `range`.
 struct OptWork { int32_t n_ranges, range; avmoe_opt_range r; long i0; };
@@ -117,14 +127,17 @@ __device__ __forceinline__ double ema_decay(const avmoe_opt_ema& e, int64_t n) {
 // block, rounded once to fp32.  A skipped step leaves the factor alone.
 // EMA: the average's decay for this step, from n = applied_steps AFTER it (the first one has n = 1), likewise.
 // The schedule and the average's constants ride in the kernel arguments: constants of the run, so a captured launch replays them.
+// report != NULL (AVMOE_OPT_REPORT): the header of the report is reset for kk_opt_range_norms, which follows on the same stream.
 template <bool SCHED, bool EMA>
 __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
                                                        float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
-                                                       avmoe_opt_schedule sched, avmoe_opt_ema ema) {
+                                                       avmoe_opt_schedule sched, avmoe_opt_ema ema, avmoe_opt_report_header* __restrict__ report,
+                                                       int n_ranges) {
   double acc = 0.0;
   for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
   const double sum = block_sum_256(acc);
   if (threadIdx.x != 0) return;
+  if (report) *report = avmoe_opt_report_header{-1, n_ranges, {0, 0}};
   const float total = (float)sqrt(sum);
   float coef = 1.0f;
   if (clip) {                                           // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1); NaN stays NaN
@@ -146,6 +159,41 @@ __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict_
   }
   if constexpr (EMA) {
     if (!skip) state->ema_decay = (float)ema_decay(ema, applied);
+  }
+}
+
+// AVMOE_OPT_REPORT.  One wave per range, grid-strided over the ranges.  The blocks of a range are neighbours in the block map, which is
+// sorted by range: a binary search finds the first, the range's length says how many.  Lane l adds partials l, l + 64, ... of the range
+// in that order and a butterfly over the 64 lanes adds the lane sums -- a fixed order, every lane ends with the same bits.  A range
+// without elements has no block and reports 0.  A launch that does not match its table (wrong magic, other counts) touches nothing, and
+// a range whose blocks are not where the map must have them (a foreign image) is left out.
+__global__ void __launch_bounds__(256) kk_opt_range_norms(const void* __restrict__ table, const double* __restrict__ partials, int n_ranges,
+                                                          long n_blocks, avmoe_opt_report_header* __restrict__ report) {
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_MAGIC || h.n_ranges != n_ranges || h.n_blocks != n_blocks) return;
+  const avmoe_opt_range* ranges = (const avmoe_opt_range*)((const char*)table + sizeof(OptHeader));
+  const OptBlock* map = (const OptBlock*)(ranges + n_ranges);
+  float* norms = (float*)(report + 1);
+  const int lane = threadIdx.x & 63, waves = (int)gridDim.x * 4;
+  for (int r = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6); r < n_ranges; r += waves) {
+    const long nb = (long)((ranges[r].n + OPT_BLOCK - 1) / OPT_BLOCK);
+    long lo = 0, hi = n_blocks;                       // the first block whose range is >= r
+    while (lo < hi) {
+      const long mid = (lo + hi) >> 1;
+      if (map[mid].range < r) lo = mid + 1; else hi = mid;
+    }
+    if (nb < 0 || lo + nb > n_blocks) continue;
+    if (nb > 0 && (map[lo].range != r || map[lo + nb - 1].range != r)) continue;
+    double acc = 0.0;
+    for (long i = lane; i < nb; i += 64) acc += partials[lo + i];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s, 64);
+    if (lane == 0) {
+      const float norm = (float)sqrt(acc);
+      norms[r] = norm;
+      // -1 is the largest unsigned value: the minimum over the ranges that are not finite, or -1 where there is none
+      if (!isfinite(norm)) atomicMin((unsigned int*)&report->first_nonfinite, (unsigned int)r);
+    }
   }
 }
 
@@ -285,21 +333,28 @@ static int check_shadows(const char* who, float* const* shadows) {
 }
 
 constexpr int32_t OPT_FLAGS = AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY;
+constexpr int OPT_REPORT_MAX_GRID = 1024;        // blocks of 4 waves: more ranges than 4096 take a second round
 
-// avmoe_opt_grad_norm (sched == NULL, ema == NULL), avmoe_opt_grad_norm_sched (ema == NULL) and avmoe_opt_grad_norm_ema: the same checks and
-// the same norm launch, then the finalize kernel the flags ask for
+// avmoe_opt_grad_norm (sched == NULL, ema == NULL), avmoe_opt_grad_norm_sched (ema == NULL), avmoe_opt_grad_norm_ema (report == NULL) and
+// avmoe_opt_grad_norm_report: the same checks and the same norm launch, then the finalize kernel the flags ask for, then the per-range norms
 static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                      float max_norm, int32_t flags, int32_t known_flags, float beta1, float beta2, const avmoe_opt_schedule* sched,
-                     const avmoe_opt_ema* ema, void* stream) {
+                     const avmoe_opt_ema* ema, void* report, void* stream) {
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
   const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
   const bool with_sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, with_ema = (flags & AVMOE_OPT_EMA) != 0;
+  const bool with_report = (flags & AVMOE_OPT_REPORT) != 0;
   if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
   if (clip && !(max_norm >= 0.f)) { set_last_error("%s: max_norm must be >= 0 and not NaN", who); return ERR_BAD_ARG; }
   if (!(grad_scale == grad_scale)) { set_last_error("%s: grad_scale is NaN", who); return ERR_BAD_ARG; }
   if (with_sched) AVMOE_TRY(check_schedule(who, sched));
   if (with_ema) AVMOE_TRY(check_ema(who, ema));
-  const bool norm = (clip || skip) && n_blocks > 0;
+  if (with_report) {
+    if (!report) { set_last_error("%s: AVMOE_OPT_REPORT without a report buffer", who); return ERR_BAD_ARG; }
+    if (((uintptr_t)report & 15u) != 0) { set_last_error("%s: the report buffer must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  }
+  avmoe_opt_report_header* rep = with_report ? (avmoe_opt_report_header*)report : nullptr;
+  const bool norm = (clip || skip || with_report) && n_blocks > 0;
   if (norm) {
     if (!partials) { set_last_error("%s: partials is NULL", who); return ERR_BAD_ARG; }
     if (((uintptr_t)partials & 7u) != 0) { set_last_error("%s: partials must be 8-byte aligned", who); return ERR_ALIGNMENT; }
@@ -308,8 +363,14 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
   }
   hipLaunchKernelGGL(OPT_FINALIZE[(int)with_sched | (int)with_ema << 1], dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials,
                      norm ? (long)n_blocks : 0L, state, max_norm, (int)clip, (int)skip, beta1, beta2, with_sched ? *sched : avmoe_opt_schedule{},
-                     with_ema ? *ema : avmoe_opt_ema{});
+                     with_ema ? *ema : avmoe_opt_ema{}, rep, (int)n_ranges);
   AVMOE_CHECK_LAUNCH("opt_finalize");
+  if (rep && n_ranges > 0) {
+    const int grid = (int)std::min<int64_t>(((int64_t)n_ranges + 3) / 4, OPT_REPORT_MAX_GRID);
+    hipLaunchKernelGGL(kk_opt_range_norms, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, table, (const double*)partials, (int)n_ranges,
+                       (long)n_blocks, rep);
+    AVMOE_CHECK_LAUNCH("opt_range_norms");
+  }
   return OK;
 }
 
@@ -366,13 +427,13 @@ int avmoe_opt_table_build(const avmoe_opt_range* ranges, int32_t n_ranges, void*
 int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                         float max_norm, int32_t flags, float beta1, float beta2, void* stream) {
   return grad_norm("avmoe_opt_grad_norm", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS, beta1, beta2, nullptr, nullptr,
-                   stream);
+                   nullptr, stream);
 }
 
 int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                               float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched) {
   return grad_norm("avmoe_opt_grad_norm_sched", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE,
-                   beta1, beta2, sched, nullptr, stream);
+                   beta1, beta2, sched, nullptr, nullptr, stream);
 }
 
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
@@ -385,7 +446,19 @@ int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_block
                             float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
                             const avmoe_opt_ema* ema) {
   return grad_norm("avmoe_opt_grad_norm_ema", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
-                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, ema, stream);
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, ema, nullptr, stream);
+}
+
+size_t avmoe_opt_report_bytes(int32_t n_ranges) {
+  if (n_ranges < 0) { set_last_error("avmoe_opt_report_bytes: negative range count %d", (int)n_ranges); return 0; }
+  return sizeof(avmoe_opt_report_header) + round16((size_t)n_ranges * sizeof(float));
+}
+
+int avmoe_opt_grad_norm_report(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                               float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
+                               const avmoe_opt_ema* ema, void* report) {
+  return grad_norm("avmoe_opt_grad_norm_report", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA | AVMOE_OPT_REPORT, beta1, beta2, sched, ema, report, stream);
 }
 
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,

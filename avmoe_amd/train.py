@@ -7,7 +7,8 @@
                                Opt-in: global-norm clipping, AdamW, skipping of non-finite steps with the optimizer state on
                                the device (three launches per step for all buckets, graph-capturable); state_dict() /
                                load_state_dict() in torch.optim.Adam's format; an exponential moving average of the weights kept
-                               by the update kernel itself, swapped in for evaluation and written by `save_adapters(ema=opt)`
+                               by the update kernel itself, swapped in for evaluation and written by `save_adapters(ema=opt)`;
+                               per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
@@ -16,7 +17,7 @@
                                (strict=False load of released checkpoints, main_trans_v3.py:254; HTS-AT key strip,
                                net_trans_v3.py:560-563)
 
-Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema] /
+Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema|_report] /
 avmoe_opt_adam_step[_ema] / avmoe_opt_swap_ema, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
@@ -169,6 +170,19 @@ class FlatAdam:
     averages under "flat_adam" ("ema": CPU tensors in `params` order, "ema_decay", "ema_warmup"); `load_state_dict()` restores them, and
     a dict without them re-seeds the averages from the current parameters.
 
+    Per-parameter gradient norms.  `report_grad_norms=True` (it selects the device path too) adds ONE launch behind the finalize launch:
+    a wave per parameter adds the block sums the norm pass has left anyway, in a fixed order, and writes the parameter's gradient norm
+    into a report buffer on the device; the lowest index of a parameter whose norm is Inf or NaN goes into its header.  The norm pass then
+    runs on every step, so `last_grad_norm` is the true norm also without clipping and skipping (the clip factor stays exactly 1, and
+    parameters, moments and averages get the bits they get without the option).  `last_param_grad_norms` (fp32, `len(params)`, in `params`
+    order) and `first_nonfinite_param` (int32, -1 for none) are DEVICE tensors, views of the report: both are rewritten by every step, a
+    skipped one included, and by every replay of a captured step.  The norms are those of gradient * grad_scale before clipping -- under
+    data parallelism after `red.finish()`, like `last_grad_norm`.  `param_names(model)` gives the names to index with:
+
+        opt = FlatAdam(red, skip_nonfinite=True, report_grad_norms=True); names = opt.param_names(model)
+        ...
+        if int(opt.skipped_steps) > seen: print("skipped by", names[int(opt.first_nonfinite_param)])
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -182,16 +196,22 @@ class FlatAdam:
     def __init__(self, reducer, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
                  max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
-                 lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0):
+                 lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
+                 report_grad_norms: bool = False):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
-        [0, 1), warmed up over `ema_warmup` >= 1 (1: constant decay); both are held as fp32.  Any of the five selects the device path
-        (class docstring); with all at their defaults step() is the per-bucket avmoe_adam_step path.
+        [0, 1), warmed up over `ema_warmup` >= 1 (1: constant decay); both are held as fp32.  report_grad_norms: every step also leaves
+        each parameter's gradient norm and the index of the first non-finite one on the device (`last_param_grad_norms`,
+        `first_nonfinite_param`).  Any of the six selects the device path (class docstring); with all at their defaults step() is the
+        per-bucket avmoe_adam_step path.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
-        reference's `lr_mlp` for the classifier head vs `lr` for the adapters); parameters not listed use `lr`.  Inside a
-        bucket, neighbouring parameters with the same rate share one kernel launch (an adapter site is one range)."""
+        reference's `lr_mlp` for the classifier head vs `lr` for the adapters); parameters not listed use `lr`.  A group may also
+        carry "weight_decay" (the AdamW recipe {"params": biases_and_norms, "weight_decay": 0.0}): it applies to that group's parameters,
+        on both paths, coupled and decoupled; parameters not listed, or listed without the key, use `weight_decay`.  `betas` and `eps`
+        stay per optimizer: a group's own are ignored.  On the plain path, neighbouring parameters of a bucket with the same rate and
+        decay share one kernel launch (an adapter site is one range)."""
         self.reducer, self.lr0, self.betas, self.eps, self.wd = reducer, lr, betas, eps, weight_decay
         self.step_size, self.gamma, self.grad_scale = step_size, gamma, grad_scale
         self.t, self.epoch = 0, 0
@@ -205,12 +225,16 @@ class FlatAdam:
         self.lr_schedule = lr_schedule
         self.ema_decay, self.ema_warmup = self._check_ema(ema_decay, ema_warmup)
         self._swapped = False                            # the parameters currently hold the averages (swap_ema / ema_weights)
+        self.report_grad_norms = bool(report_grad_norms)
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
-        lr_of = {}
+        self._wds = []                                   # beside it: each parameter's weight decay
+        lr_of, wd_of = {}, {}
         for grp in (param_groups or []):
             ps = grp["params"]
             for p in ([ps] if isinstance(ps, torch.Tensor) else ps):
                 lr_of[id(p)] = float(grp.get("lr", lr))
+                if "weight_decay" in grp:
+                    wd_of[id(p)] = float(grp["weight_decay"])
         for b in reducer.buckets:
             flat_g = b.flat
             if not flat_g.is_cuda:
@@ -225,12 +249,13 @@ class FlatAdam:
                     raise capi.AvmoeError("FlatAdam: a re-pointed parameter is not 16-byte aligned (the GEMM engine needs "
                                           "aligned operands); build the reducer with aligned buckets (avmoe_amd.dp)")
                 self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
+                self._wds.append(wd_of.get(id(p), weight_decay))
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
             if self.ema_decay is not None:               # the averages: the bucket's layout once more, padding zero
                 self.state[-1]["e"] = flat_p.clone()
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
-            or self.ema_decay is not None
+            or self.ema_decay is not None or self.report_grad_norms
         if self._device:
             self._build_device_state()
 
@@ -307,10 +332,10 @@ class FlatAdam:
     def _opt_ranges(self):
         """one avmoe_opt_range per parameter (its own elements only: the norm must not see alignment padding)"""
         arr = (cm.OptRange * len(self._plist))()
-        for r, (p, si, off, lr0) in zip(arr, self._plist):
+        for r, (p, si, off, lr0), wd in zip(arr, self._plist, self._wds):
             s = self.state[si]
             r.param, r.grad, r.exp_avg, r.exp_avg_sq = (s[k].data_ptr() + 4 * off for k in ("p", "g", "m", "v"))
-            r.n, r.lr, r.weight_decay = p.numel(), lr0 * self.decay, self.wd
+            r.n, r.lr, r.weight_decay = p.numel(), lr0 * self.decay, wd
         return arr
 
     def _build_device_state(self):
@@ -338,6 +363,22 @@ class FlatAdam:
         self._upload_table()
         if self.ema_decay is not None:
             self._build_shadows()
+        if self.report_grad_norms:
+            self._build_report()
+
+    def _build_report(self):
+        """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
+        L, n = capi.lib(), len(self._plist)
+        if not hasattr(L, "avmoe_opt_grad_norm_report"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks the per-range gradient norms (avmoe_opt_grad_norm_report): rebuild it")
+        nbytes = L.avmoe_opt_report_bytes(n)
+        if nbytes == 0:
+            capi.check(-1, "avmoe_opt_report_bytes")
+        self._report = torch.zeros(nbytes, dtype=torch.uint8, device=self._dev)
+        self._report[:4].view(torch.int32).fill_(-1)      # until the first step: no parameter
+        hdr = C.sizeof(cm.OptReportHeader)
+        self._report_views = (self._report[hdr:hdr + 4 * n].view(torch.float32), self._report[:4].view(torch.int32)[0])
+        self._flags |= cm.OPT_REPORT
 
     def _build_shadows(self):
         """the views `ema_params` hands out and the device array of one shadow pointer per range, beside the range table"""
@@ -401,6 +442,30 @@ class FlatAdam:
             raise capi.AvmoeError("FlatAdam.last_lr_factor needs lr_schedule")
         return self._state_view("lr_factor")
 
+    def _need_report(self, what):
+        if not self.report_grad_norms:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs report_grad_norms")
+
+    @property
+    def last_param_grad_norms(self) -> torch.Tensor:
+        """fp32 DEVICE tensor of len(params): the norm of (gradient * grad_scale) of every parameter at the last step(), before clipping,
+        in `params` order (`param_names(model)` names them).  A view of the report buffer, rewritten by every step, a skipped one
+        included: reading it is the caller's synchronisation.  Only with `report_grad_norms`."""
+        self._need_report("last_param_grad_norms")
+        return self._report_views[0]
+
+    @property
+    def first_nonfinite_param(self) -> torch.Tensor:
+        """int32 DEVICE scalar: the lowest index into `params` of a parameter whose gradient norm at the last step() was Inf or NaN, -1 when
+        all were finite.  A view of the report buffer, like `last_param_grad_norms`; only with `report_grad_norms`."""
+        self._need_report("first_nonfinite_param")
+        return self._report_views[1]
+
+    def param_names(self, model: torch.nn.Module) -> List[Optional[str]]:
+        """the names of `params`, in that order, from model.named_parameters() by identity; None for a parameter the model does not own"""
+        names = {id(p): k for k, p in model.named_parameters()}
+        return [names.get(id(e[0])) for e in self._plist]
+
     @property
     def state_block(self) -> Dict[str, torch.Tensor]:
         """every field of the device state block (avmoe_opt_state) as a DEVICE scalar view: total_norm, clip_coef, bc1, bc2_sqrt,
@@ -413,17 +478,25 @@ class FlatAdam:
         """the parameters in the reducer's order -- the index order of state_dict()"""
         return [e[0] for e in self._plist]
 
-    def _groups(self):
-        """[(lr0, [indices into self.params])]: one group per distinct base learning rate, in order of first appearance"""
+    def _keyed_groups(self):
+        """[((lr0, weight_decay), [indices into self.params])]: one group per distinct pair, in order of first appearance"""
         out = {}
-        for i, e in enumerate(self._plist):
-            out.setdefault(e[3], []).append(i)
+        for i, (e, wd) in enumerate(zip(self._plist, self._wds)):
+            out.setdefault((e[3], wd), []).append(i)
         return list(out.items())
 
+    def _groups(self):
+        """[(lr0, [indices into self.params])] of the groups above; `_group_decays()` is the list of their weight decays"""
+        return [(k[0], idx) for k, idx in self._keyed_groups()]
+
+    def _group_decays(self):
+        return [k[1] for k, _ in self._keyed_groups()]
+
     def torch_param_groups(self) -> List[dict]:
-        """param groups for torch.optim.Adam / AdamW over the same parameters, in the grouping and order state_dict() uses"""
+        """param groups for torch.optim.Adam / AdamW over the same parameters, in the grouping and order state_dict() uses, each with its
+        learning rate of the current epoch and its weight decay"""
         ps = self.params
-        return [{"params": [ps[i] for i in idx], "lr": lr0 * self.decay} for lr0, idx in self._groups()]
+        return [{"params": [ps[i] for i in idx], "lr": lr0 * self.decay, "weight_decay": wd} for (lr0, wd), idx in self._keyed_groups()]
 
     @property
     def decay(self) -> float:
@@ -445,20 +518,22 @@ class FlatAdam:
             n = len(self._plist)
             # the entry points that know every flag: an option that is off is a flag not set and a NULL argument, and the flags choose
             # the kernels (finalize also writes f(applied_steps) and d_n, the update also averages -- the same three launches)
-            capi.check(L.avmoe_opt_grad_norm_ema(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
-                                                 self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
-                                                 None if self._sched_c is None else C.byref(self._sched_c),
-                                                 None if self.ema_decay is None else C.byref(self._ema_c)), "avmoe_opt_grad_norm_ema")
+            # (and, with the report, one more behind finalize; the update does not know that flag)
+            capi.check(L.avmoe_opt_grad_norm_report(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                                    self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
+                                                    None if self._sched_c is None else C.byref(self._sched_c),
+                                                    None if self.ema_decay is None else C.byref(self._ema_c),
+                                                    self._report.data_ptr() if self.report_grad_norms else None), "avmoe_opt_grad_norm_report")
             capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
-                                                 self.eps, scale, self._flags, stream,
+                                                 self.eps, scale, self._flags & ~cm.OPT_REPORT, stream,
                                                  None if self.ema_decay is None else self._shadow_ptrs.data_ptr()), "avmoe_opt_adam_step_ema")
             return
         for s in self.state:
-            for (o, e, r) in s["ranges"]:
+            for (o, e, r, wd) in s["ranges"]:
                 st = L.avmoe_adam_step(s["p"].data_ptr() + 4 * o, s["g"].data_ptr() + 4 * o, s["m"].data_ptr() + 4 * o,
                                        s["v"].data_ptr() + 4 * o, C.c_int64(e - o), C.c_float(r * self.decay),
                                        C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps),
-                                       C.c_float(self.wd), C.c_int64(self.t), C.c_float(scale),
+                                       C.c_float(wd), C.c_int64(self.t), C.c_float(scale),
                                        torch.cuda.current_stream(s["p"].device).cuda_stream)
                 capi.check(st, "avmoe_adam_step")
 
@@ -482,7 +557,7 @@ class FlatAdam:
                         "exp_avg_sq": s["v"][off:off + n].view_as(p).detach().cpu().clone()}
         f = self.lr_schedule.factor(applied) if self.lr_schedule is not None else None      # the rate of the next step
         groups = [{"lr": lr0 * self.decay if f is None else lr0 * self.decay * f, "initial_lr": lr0, "betas": tuple(self.betas), "eps": self.eps,
-                   "weight_decay": self.wd, "params": list(idx)} for lr0, idx in self._groups()]
+                   "weight_decay": wd, "params": list(idx)} for (lr0, wd), idx in self._keyed_groups()]
         extra = {"t": self.t, "epoch": self.epoch, "applied_steps": applied, "skipped_steps": skipped,
                  "max_grad_norm": self.max_grad_norm, "decoupled_weight_decay": self.decoupled_weight_decay,
                  "skip_nonfinite": self.skip_nonfinite, "step_size": self.step_size, "gamma": self.gamma}
@@ -490,11 +565,13 @@ class FlatAdam:
             extra["lr_schedule"] = dataclasses.asdict(self.lr_schedule)
         if self.ema_decay is not None:
             extra.update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema=[e.detach().cpu().clone() for e in self._ema_views])
+        if self.report_grad_norms:                       # informative, like the other path options; absent when off
+            extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
 
     def load_state_dict(self, sd: dict):
-        """Writes the moments into the flat buffers, the counters into the state block, and restores t, epoch and the groups' lr / betas /
-        eps / weight_decay.  A saved per-step schedule replaces the one the constructor was given (device path only: on the plain path it
+        """Writes the moments into the flat buffers, the counters into the state block, and restores t, epoch, each group's lr and
+        weight_decay (matched by position) and betas / eps (the first group's: they are per optimizer).  A saved per-step schedule replaces the one the constructor was given (device path only: on the plain path it
         raises); with the saved `applied_steps` the run continues it.  Saved parameters are matched to `self.params` by position across the groups, as torch.optim does; the three
         path options stay what the constructor was given (the saved ones are informative), unknown keys are ignored.  A count or shape
         mismatch raises ValueError naming the parameter index.  With `ema_decay`: saved averages ("ema", with "ema_decay" / "ema_warmup",
@@ -556,7 +633,13 @@ class FlatAdam:
             self.epoch = int(extra.get("epoch", self.epoch))
             self.step_size, self.gamma = extra.get("step_size", self.step_size), extra.get("gamma", self.gamma)
             g0 = saved_groups[0]
-            self.betas, self.eps, self.wd = tuple(g0.get("betas", self.betas)), g0.get("eps", self.eps), g0.get("weight_decay", self.wd)
+            self.betas, self.eps = tuple(g0.get("betas", self.betas)), g0.get("eps", self.eps)
+            wds = [sg.get("weight_decay", wd) for sg, wd in zip(saved_groups, self._group_decays())]
+            for (_lr_old, idx), wd in zip(own_groups, wds):
+                for i in idx:
+                    self._wds[i] = wd
+            if len(set(wds)) == 1:                        # one decay for all: the optimizer's own, as the constructor's argument is
+                self.wd = wds[0]
             if saved_sched is not None:
                 self._set_schedule(saved_sched)
             # a dict without initial_lr comes from a torch optimizer that never had a scheduler: its lr is a base rate, whatever the
@@ -588,17 +671,18 @@ class FlatAdam:
                 self.t = applied                          # the plain path's bias correction counts self.t
 
     def _rebuild_plain_ranges(self):
-        """the plain path's merged [begin, end, lr0] ranges per bucket from the per-parameter learning rates: neighbouring parameters
-        with the same rate share one kernel launch, alignment padding rides with its left neighbour"""
+        """the plain path's merged [begin, end, lr0, weight_decay] ranges per bucket from the per-parameter learning rates and decays:
+        neighbouring parameters with the same rate and the same decay share one kernel launch, alignment padding rides with its left
+        neighbour"""
         for si, s in enumerate(self.state):
-            spans = sorted((off, off + p.numel(), lr0) for (p, sj, off, lr0) in self._plist if sj == si)
+            spans = sorted((off, off + p.numel(), lr0, wd) for (p, sj, off, lr0), wd in zip(self._plist, self._wds) if sj == si)
             ranges = []
-            for i, (o, e, r) in enumerate(spans):
+            for i, (o, e, r, wd) in enumerate(spans):
                 end = spans[i + 1][0] if i + 1 < len(spans) else s["g"].numel()
-                if ranges and ranges[-1][2] == r:
+                if ranges and ranges[-1][2:] == [r, wd]:
                     ranges[-1][1] = end
                 else:
-                    ranges.append([o if ranges else 0, end, r])
+                    ranges.append([o if ranges else 0, end, r, wd])
             s["ranges"] = ranges
 
 

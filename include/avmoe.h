@@ -330,7 +330,8 @@ typedef struct avmoe_opt_range {
 } avmoe_opt_range;
 
 typedef struct avmoe_opt_state {
-  float total_norm;           /* sqrt(sum (grad * grad_scale)^2) over every element of every range; 0 when no norm was asked for */
+  float total_norm;           /* sqrt(sum (grad * grad_scale)^2) over every element of every range; 0 when no norm was asked for
+                                 (none of AVMOE_OPT_CLIP, AVMOE_OPT_SKIP_NONFINITE, AVMOE_OPT_REPORT) */
   float clip_coef;            /* min(1, max_norm / (total_norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_; exactly 1 when clipping is off */
   float bc1, bc2_sqrt;        /* 1 - beta1^applied_steps ; sqrt(1 - beta2^applied_steps): computed in double, rounded to fp32 */
   int64_t applied_steps;      /* steps that updated the parameters */
@@ -443,6 +444,40 @@ int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_block
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
                             float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE */);
 int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, float* const* shadows /* DEVICE */, void* stream);
+
+/* The gradient norm of every range and the first range whose norm is not finite (added under ABI 11 like the blocks above; found by
+ * symbol): which parameter made a step skip, or whose gradient is out of line with its neighbours', without a .norm() per tensor.  The
+ * norm pass already leaves one double per 1024-element block and every block belongs to one range, so the per-range norms are a
+ * segmented sum of numbers the step has computed anyway.
+ * The report buffer (DEVICE, 16-byte aligned, avmoe_opt_report_bytes(n_ranges) bytes: the 16-byte header, then n_ranges floats, rounded
+ * up to 16; 0 and an error string on a negative count) needs no initialisation.
+ * avmoe_opt_grad_norm_report is avmoe_opt_grad_norm_ema with one more argument and knows every flag.  With AVMOE_OPT_REPORT in `flags`:
+ *   - the norm launch runs whether or not clipping or skipping is on, and total_norm is the true norm also with neither (it is 0 there
+ *     without the flag -- the one difference; clip_coef stays exactly 1);
+ *   - the finalize launch resets the header, and ONE more launch (a step is 4 launches then) gives a wave to every range: lane l adds the
+ *     range's block sums l, l + 64, ... in order, a fixed butterfly adds the 64 lane sums, and
+ *         norms[r] = (float)sqrt(sum of range r's block sums, in double)          (a range of length 0 reports 0)
+ *     No floating-point atomics: the same input gives the same bits.  first_nonfinite = the lowest r whose norms[r] is Inf or NaN, or -1
+ *     (an integer minimum, which does not depend on the order).  Both are rewritten every step, a skipped step included;
+ *   - every word of the state block but total_norm in the case above, and with it parameters, moments and averages, gets the bits it
+ *     gets without the flag: the global sum keeps its own order of additions and is not rebuilt from the per-range sums.
+ * The norms are those of grad * grad_scale, before clipping.  No host synchronisation, no allocation, no host scalar that changes from
+ * step to step: a captured step rewrites the report on replay.  Without the flag `report` is not read and the call is
+ * avmoe_opt_grad_norm_ema; avmoe_opt_adam_step_ema does not know the flag and needs no change (pass it the flags without it).
+ * Errors (before any launch): AVMOE_ERR_BAD_ARG for the flag with report == NULL, AVMOE_ERR_ALIGNMENT for a report that is not 16-byte
+ * aligned, and everything avmoe_opt_grad_norm_ema refuses.  The older entry points refuse the flag ("unknown flag").                  */
+enum { AVMOE_OPT_REPORT = 32 };
+
+typedef struct avmoe_opt_report_header {
+  int32_t first_nonfinite;    /* the lowest range index whose norm is not finite, or -1 */
+  int32_t n_ranges;           /* the floats that follow the header */
+  int32_t reserved[2];
+} avmoe_opt_report_header;
+
+size_t avmoe_opt_report_bytes(int32_t n_ranges);
+int avmoe_opt_grad_norm_report(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                               float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched /* HOST, or NULL */,
+                               const avmoe_opt_ema* ema /* HOST, or NULL */, void* report /* DEVICE, 16-byte aligned */);
 
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the

@@ -10,6 +10,7 @@
 --ema              (device mode) FlatAdam(ema_decay=0.999): the update launch also advances the weight average -- still three launches
 --ema-foreach      (device mode) the same average kept OUTSIDE the optimizer: the step without it, then torch._foreach_lerp_ over the
                    parameter views with the decay computed on the host (FlatAdam.ema_decay_at), what a user had to write before --ema
+--report           (device mode) FlatAdam(report_grad_norms=True): one more launch behind finalize writes every parameter's gradient norm
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
@@ -51,6 +52,7 @@ def main():
     ap.add_argument("--schedule-upload", action="store_true")
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--ema-foreach", action="store_true")
+    ap.add_argument("--report", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -58,6 +60,8 @@ def main():
         ap.error("--schedule and --schedule-upload are the two sides of one comparison")
     if (a.ema or a.ema_foreach) and a.mode != "device":
         ap.error("--ema / --ema-foreach go with --mode device")
+    if a.report and a.mode != "device":
+        ap.error("--report goes with --mode device")
     if a.ema and a.ema_foreach:
         ap.error("--ema and --ema-foreach are the two sides of one comparison")
     from avmoe_amd.dp import AdapterGradReducer
@@ -75,6 +79,8 @@ def main():
     ema_decay, ema_warmup = 0.999, 10.0
     if a.ema:
         kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
+    if a.report:
+        kw["report_grad_norms"] = True
     opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
@@ -114,6 +120,10 @@ def main():
     if a.ema:
         extra["last_ema_decay"] = float(opt.last_ema_decay.item())
         extra["want_ema_decay"] = FlatAdam.ema_decay_at(total, ema_decay, ema_warmup)
+    if a.report:
+        extra["report"] = "device"
+        extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())
+        extra["param_norms_vs_total"] = float(opt.last_param_grad_norms.double().pow(2).sum().sqrt().item()) / float(opt.last_grad_norm.item())
     if a.schedule:
         extra["last_lr_factor"] = float(opt.last_lr_factor.item())
         extra["want_lr_factor"] = sched.factor(total - 1)
