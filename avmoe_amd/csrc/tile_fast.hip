@@ -542,8 +542,8 @@ __global__ void __launch_bounds__(WE<E>::NTHR, LB_PRE) kf_pre_small(FPreArgs a, 
     if (ll < 0) continue;
     float* lt = s_dyn + ll * LATF;
     const float* tt = TT + ((long)s * t.El + ll) * FK * FK;
-    kf_fill<4>(FK * FK, NTHR, [&](int i) { return tt[i]; }, [&](int i, float v) { lt[(i & 31) * LD32 + (i >> 5)] = v; });     // transposed (mmT)
-    kf_fill<8>(FK * FDD, NTHR,
+    tile_fill<4>(FK * FK, NTHR, [&](int i) { return tt[i]; }, [&](int i, float v) { lt[(i & 31) * LD32 + (i >> 5)] = v; });     // transposed (mmT)
+    tile_fill<8>(FK * FDD, NTHR,
                [&](int i) { const int k = i >> 6, dd = i & 63; return TW[((long)s * t.KLT + (long)ll * FK + k) * DZ + (dd >> 5) * (E * FDG) + ee * FDG + (dd & 31)]; },
                [&](int i, float v) { const int k = i >> 6, dd = i & 63; lt[FK * LD32 + dd * LD32 + k] = v; });
     if (threadIdx.x < FK) lt[FK * LD32 + FDD * LD32 + threadIdx.x] = Tsum[(long)s * t.KLT + (long)ll * FK + threadIdx.x] / (float)t.C;
@@ -874,8 +874,8 @@ __global__ void __launch_bounds__(256, LB_PRELB) kf_pre_lat_bwd(FPreLArgs a, con
     const int ee = a.e_of_lat[ll];
     float* lt = s_dyn + ll * LATF;
     const float* tt = TT + ((long)s * t.El + ll) * FK * FK;
-    kf_fill<4>(FK * FK, 256, [&](int i) { return tt[i]; }, [&](int i, float v) { lt[(i & 31) * LD32 + (i >> 5)] = v; });     // transposed (mmT)
-    kf_fill<8>(FK * FDD, 256,
+    tile_fill<4>(FK * FK, 256, [&](int i) { return tt[i]; }, [&](int i, float v) { lt[(i & 31) * LD32 + (i >> 5)] = v; });     // transposed (mmT)
+    tile_fill<8>(FK * FDD, 256,
                [&](int i) { const int k = i >> 6, dd = i & 63; return TW[((long)s * t.KLT + (long)ll * FK + k) * DZ + (dd >> 5) * (E * FDG) + ee * FDG + (dd & 31)]; },
                [&](int i, float v) { const int k = i >> 6, dd = i & 63; lt[FK * LD32 + k * LD64 + dd] = v; lt[FK * LD32 + FK * LD64 + dd * LD32 + k] = v; });
     if (threadIdx.x < FK) lt[FK * LD32 + FK * LD64 + FDD * LD32 + threadIdx.x] = Tsum[(long)s * t.KLT + (long)ll * FK + threadIdx.x] / (float)t.C;

@@ -22,95 +22,14 @@
 
 namespace avmoe {
 
+#include "tile_lane.h"
+
 namespace {
 
 struct GenDims { int S, N, C, E, K, Kp, El, KL, KLT, KLp, KPp, NT, per, DZ, XW;
                  int R, NS; long aL; };      // experts resident per round, tile slots: a block has 64 * R * NS threads (see "rounds" below)
 
-#ifndef GEN_QSUM_SHFL
-#define GEN_QSUM_SHFL 0        // development builds: 1 = the token-quad reductions through ds_bpermute shuffles instead of the gfx950 row swaps
-#endif
-#ifndef GEN_MMT_BF16
-#define GEN_MMT_BF16 1         // the bf16 instantiations run their mat-vecs on the bf16 matrix pipe in split form (mmT_split); 0 (development builds): exact-fp32 MFMA everywhere
-#endif
-#ifndef GEN_MMT_FENCE
-#define GEN_MMT_FENCE 0        // development builds: 1 = nothing scheduled into the MFMA chain of a mat-vec, 32 idle cycles behind it
-#endif
-#ifndef GEN_MMT_PRIO
-#define GEN_MMT_PRIO 0         // development builds: 1 = wave priority 3 around the MFMA chain
-#endif
-#ifndef GEN_MMT_VALU
-#define GEN_MMT_VALU 0         // development builds: 1 = the per-token mat-vecs as plain FMA loops over LDS (no matrix pipe)
-#endif
-__device__ __forceinline__ float qsum4(float v) {
-#if GEN_QSUM_SHFL
-  v += __shfl_xor(v, 16); v += __shfl_xor(v, 32); return v;
-#endif
-  const unsigned u = __float_as_uint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-  const unsigned x = __float_as_uint(w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-__device__ __forceinline__ float qmax4(float v) {
-#if GEN_QSUM_SHFL
-  v = fmaxf(v, __shfl_xor(v, 16)); v = fmaxf(v, __shfl_xor(v, 32)); return v;
-#endif
-  const unsigned u = __float_as_uint(v);
-  const auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  const float w = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  const unsigned x = __float_as_uint(w);
-  const auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-template <int CTRL> __device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-#ifndef GEN_RSUM_SHFL
-#define GEN_RSUM_SHFL 0        // development builds: 1 = the 16-lane row sums through ds_bpermute shuffles instead of DPP adds
-#endif
-__device__ __forceinline__ float rsum16(float v) {      // sum over the 16 lanes of a row (the tokens of the tile, fixed q)
-#if GEN_RSUM_SHFL
-  v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-  return v;
-#endif
-  v += dpp_f<0xB1>(v); v += dpp_f<0x4E>(v); v += dpp_f<0x141>(v); v += dpp_f<0x140>(v);
-  return v;
-}
-__device__ __forceinline__ int opaque0() { int v = 0; asm volatile("" : "+v"(v)); return v; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-__device__ __forceinline__ float& at(float4& v, int x) { return ((float*)&v)[x]; }
-__device__ __forceinline__ float at(const float4& v, int x) { return ((const float*)&v)[x]; }
-template <typename T> __device__ __forceinline__ float rndT(float v);
-template <> __device__ __forceinline__ float rndT<float>(float v) { return v; }
-template <> __device__ __forceinline__ float rndT<__bf16>(float v) { return bf2f(f2bf(v)); }
-
-// ---- one 16-entry chunk / one 32-entry chunk pair of a row, this lane's 4 (+4) entries ----------------------------------------
-__device__ __forceinline__ int seg_off8(int q) { return (q & 1) * 16 + (q >> 1) * 8; }
-template <typename T> __device__ __forceinline__ void ld_pair(const T* seg, float4& c0, float4& c1, int q);
-template <> __device__ __forceinline__ void ld_pair<float>(const float* seg, float4& c0, float4& c1, int q) {
-  c0 = *(const float4*)(seg + 4 * q); c1 = *(const float4*)(seg + 16 + 4 * q);
-}
-template <> __device__ __forceinline__ void ld_pair<__bf16>(const __bf16* seg, float4& c0, float4& c1, int q) {
-  const uint4 u = *(const uint4*)(seg + seg_off8(q));
-  const auto s0 = __builtin_amdgcn_permlane16_swap(u.x, u.z, false, false);
-  const auto s1 = __builtin_amdgcn_permlane16_swap(u.y, u.w, false, false);
-  c0 = make_float4(__uint_as_float(s0[0] << 16), __uint_as_float(s0[0] & 0xffff0000u), __uint_as_float(s1[0] << 16), __uint_as_float(s1[0] & 0xffff0000u));
-  c1 = make_float4(__uint_as_float(s0[1] << 16), __uint_as_float(s0[1] & 0xffff0000u), __uint_as_float(s1[1] << 16), __uint_as_float(s1[1] & 0xffff0000u));
-}
-template <typename T> __device__ __forceinline__ void st_pair(T* seg, const float4& c0, const float4& c1, int q);
-template <> __device__ __forceinline__ void st_pair<float>(float* seg, const float4& c0, const float4& c1, int q) {
-  *(float4*)(seg + 4 * q) = c0; *(float4*)(seg + 16 + 4 * q) = c1;
-}
-template <> __device__ __forceinline__ void st_pair<__bf16>(__bf16* seg, const float4& c0, const float4& c1, int q) {
-  const unsigned a0 = (unsigned)f2bf(c0.x) | ((unsigned)f2bf(c0.y) << 16), a1 = (unsigned)f2bf(c0.z) | ((unsigned)f2bf(c0.w) << 16);
-  const unsigned b0 = (unsigned)f2bf(c1.x) | ((unsigned)f2bf(c1.y) << 16), b1 = (unsigned)f2bf(c1.z) | ((unsigned)f2bf(c1.w) << 16);
-  const auto s0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);
-  const auto s1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-  *(uint4*)(seg + seg_off8(q)) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
-}
+// ---- one 16-entry chunk of a row, this lane's 4 entries (chunk pairs: ld_seg / st_seg of tile_lane.h) ------------------------------
 template <typename T> __device__ __forceinline__ void ld_one(const T* seg, float4& c0, int q);
 template <> __device__ __forceinline__ void ld_one<float>(const float* seg, float4& c0, int q) { c0 = *(const float4*)(seg + 4 * q); }
 template <> __device__ __forceinline__ void ld_one<__bf16>(const __bf16* seg, float4& c0, int q) {
@@ -125,105 +44,17 @@ template <> __device__ __forceinline__ void st_one<__bf16>(__bf16* seg, const fl
 // NC consecutive chunks starting at `seg` (chunk pairs as one 16-byte access per lane, an odd last chunk as 8 / 16 bytes)
 template <typename T, int NC> __device__ __forceinline__ void ld_chunks(const T* seg, float4 (&v)[NC], int q) {
 #pragma unroll
-  for (int c = 0; c + 1 < NC; c += 2) ld_pair<T>(seg + 16 * c, v[c], v[c + 1], q);
+  for (int c = 0; c + 1 < NC; c += 2) ld_seg<T>(seg + 16 * c, v[c], v[c + 1], q);
   if constexpr (NC & 1) ld_one<T>(seg + 16 * (NC - 1), v[NC - 1], q);
 }
 template <typename T, int NC> __device__ __forceinline__ void st_chunks(T* seg, const float4 (&v)[NC], int q) {
 #pragma unroll
-  for (int c = 0; c + 1 < NC; c += 2) st_pair<T>(seg + 16 * c, v[c], v[c + 1], q);
+  for (int c = 0; c + 1 < NC; c += 2) st_seg<T>(seg + 16 * c, v[c], v[c + 1], q);
   if constexpr (NC & 1) st_one<T>(seg + 16 * (NC - 1), v[NC - 1], q);
 }
 template <int NC> __device__ __forceinline__ void zero_chunks(float4 (&v)[NC]) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) v[c] = zero4();
-}
-
-// W[tok r][col0 + 4 q + x] = sum over NJ chunks of  P[r][16 j + ..] * M[16 j + ..][col0 + ..] ; Mt = M transposed in LDS (Mt[n][k], leading
-// dim ld = 4 mod 32 words so that the 16-byte A-operand reads are conflict-free); p[j] = this lane's chunk registers
-// The same product on the bf16 matrix pipe with fp32-class accuracy: both operands split into two bf16 planes, hi = bf16(v) and
-// lo = bf16(v - hi), and  hi.hi + hi.lo + lo.hi  accumulated in fp32 (the dropped lo.lo term is 2^-16 of a product; measured error of
-// a mat-vec ~4e-6 relative).  One v_mfma_f32_16x16x32_bf16 covers TWO 16-entry chunks: a lane's eight contraction entries are its
-// four of chunk j and its four of chunk j + 1 -- the same permutation of the contraction index for the A operand (two 16-byte LDS
-// reads, as before) and the B operand (the lane's own registers), so nothing moves between lanes and the result lands in the
-// layout of the fp32 form.  An odd last chunk is padded with zeros.
-// WHY (round 4): v_mfma_f32_16x16x4_f32 returned wrong sums in these kernels -- one 16-token tile in ~10^3, off by ~1 % -- whenever a
-// bf16 GEMM of the engine ran on the same compute units from another stream (AdapterPair's two-stream mode; never alone on the
-// GPU, never with the mat-vecs on the vector ALU: tests/dev/race_buffers.py, scripts/mfma_probe.hip, DESIGN.md section 5).  The bf16
-// matrix instructions next to the same neighbours repeat bit for bit.
-__device__ __forceinline__ void split8(const float4& v0, const float4& v1, bf16x8& hi, bf16x8& lo) {
-  const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const __bf16 h = (__bf16)f[i];
-    hi[i] = h;
-    lo[i] = (__bf16)(f[i] - (float)h);
-  }
-}
-template <int NJ>
-__device__ __forceinline__ f32x4 mmT_split(const float* Mt, int ld, int col0, const float4* p, int r, int q) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  const float* mp = Mt + (col0 + r) * ld + 4 * q;
-#pragma unroll
-  for (int j = 0; j < NJ; j += 2) {
-    const float4 a0 = *(const float4*)(mp + 16 * j);
-    const float4 a1 = (j + 1 < NJ) ? *(const float4*)(mp + 16 * (j + 1)) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 p1 = (j + 1 < NJ) ? p[j + 1 < NJ ? j + 1 : j] : make_float4(0.f, 0.f, 0.f, 0.f);
-    bf16x8 ah, al, ph, pl;
-    split8(a0, a1, ah, al);
-    split8(p[j], p1, ph, pl);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, ph, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, pl, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, ph, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// SPLIT: the bf16 instantiations (sizeof(T) == 2); the fp32 ones keep the exact-fp32 matrix instruction (their neighbours on the
-// other stream are fp32 GEMMs: repeatable in every test)
-template <int NJ, bool SPLIT>
-__device__ __forceinline__ f32x4 mmT(const float* Mt, int ld, int col0, const float4* p, int r, int q) {
-#if GEN_MMT_BF16
-  if constexpr (SPLIT) return mmT_split<NJ>(Mt, ld, col0, p, r, q);
-#endif
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#if GEN_MMT_VALU
-  // W[tok r][col0 + 4 q + x] = sum_k P[r][k] Mt[col0 + 4 q + x][k] : the lane needs P[r][all k] -- its own chunk entries and those of the
-  // three other lanes of the token (shuffles)
-#pragma unroll
-  for (int j = 0; j < NJ; ++j)
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-      for (int xx = 0; xx < 4; ++xx) {
-        const float pv = __shfl(at(p[j], xx), r + 16 * qq);
-        const int k = 16 * j + 4 * qq + xx;
-#pragma unroll
-        for (int x = 0; x < 4; ++x) acc[x] += pv * Mt[(col0 + 4 * q + x) * ld + k];
-      }
-  return acc;
-#endif
-  const float* mp = Mt + (col0 + r) * ld + 4 * q;
-#if GEN_MMT_FENCE
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-#if GEN_MMT_PRIO
-  __builtin_amdgcn_s_setprio(3);
-#endif
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    const float4 a = *(const float4*)(mp + 16 * j);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(at(a, x), at(p[j], x), acc, 0, 0, 0);
-  }
-#if GEN_MMT_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
-#if GEN_MMT_FENCE
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 15\n s_nop 15" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-  return acc;
 }
 
 // column of entry jj (0 .. GD) of group gi, expert e inside a Z-space row [group][expert][GD]
@@ -285,25 +116,10 @@ __device__ __forceinline__ void stage_cols(float* dst, const float* src, int e, 
   for (int dd = threadIdx.x; dd < DD; dd += blockDim.x) dst[dd] = src ? src[zcolg(dd / GD, e, E, GD) + dd % GD] : 0.f;
 }
 // a (group, expert) block matrix M[j][l] (GD x GD, row-major in global memory) into LDS transposed for mmT: dst[(gi*GD + l) * ld + j]
-// (Round 5: the staging loops run in BATCHES -- U independent, unconditional loads per thread in flight (clamped indices; what lies outside is
-// replaced afterwards), then their stores.  As plain loops the compiler kept them rolled -- load, s_waitcnt vmcnt(0), store, branch: one memory
-// round trip per element and thread; the latent-token matrices of an 87-token site are 84 of them in a row per block and frame.)
-template <int U, typename LD, typename ST>
-__device__ __forceinline__ void gen_fill(int n, LD&& ld, ST&& st) {
-  const int nthr = blockDim.x;
-  for (int i0 = threadIdx.x; i0 < n; i0 += U * nthr) {
-    float v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = ld(min(i0 + u * nthr, n - 1));
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (i0 + u * nthr < n) st(i0 + u * nthr, v[u]);
-  }
-}
 template <int NG, int NCG>
 __device__ __forceinline__ void stage_blocks_T(float* dst, int ld, const float* src, int e, int E) {
   constexpr int GD = NCG * 16;
-  gen_fill<8>(NG * GD * GD,
+  tile_fill<8>(NG * GD * GD, blockDim.x,
               [&](int i) { const int gi = i / (GD * GD), rem = i % (GD * GD), j = rem / GD, l = rem % GD; return src[((long)(gi * E + e) * GD + j) * GD + l]; },
               [&](int i, float v) { const int gi = i / (GD * GD), rem = i % (GD * GD), j = rem / GD, l = rem % GD; dst[(gi * GD + l) * ld + j] = v; });
 }
@@ -710,10 +526,10 @@ __device__ __forceinline__ void stage_latent(float* s_TT, float* s_TW, float* s_
   constexpr int GD = NCG * 16, DD = NG * GD, Kp = KC * 16, LDK = Kp + 4, LDD = DD + 4;
   const float* tt = TT + ((long)s * t.El + l) * t.K * t.K;
   const int K = t.K;
-  gen_fill<8>(Kp * Kp,
+  tile_fill<8>(Kp * Kp, blockDim.x,
               [&](int i) { const int k1 = i / Kp, k2 = i % Kp; return tt[min(k1, K - 1) * K + min(k2, K - 1)]; },
               [&](int i, float v) { const int k1 = i / Kp, k2 = i % Kp; s_TT[k2 * LDK + k1] = (k1 < K && k2 < K) ? v : 0.f; });
-  gen_fill<8>(Kp * DD,
+  tile_fill<8>(Kp * DD, blockDim.x,
               [&](int i) { const int k = i / DD, dd = i % DD; return TW[((long)s * t.KLT + (long)l * t.Kp + min(k, K - 1)) * t.DZ + zcolg(dd / GD, e, t.E, GD) + dd % GD]; },
               [&](int i, float v0) { const int k = i / DD, dd = i % DD; const float v = k < K ? v0 : 0.f; if constexpr (WT) s_TW[dd * LDK + k] = v; else s_TW[k * LDD + dd] = v; });
   for (int k = threadIdx.x; k < Kp; k += blockDim.x) s_tb[k] = k < t.K ? Tsum[(long)s * t.KLT + (long)l * t.Kp + k] / (float)t.C : 0.f;

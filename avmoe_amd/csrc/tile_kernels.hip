@@ -18,21 +18,20 @@
 
 namespace avmoe {
 
-template <typename T> __device__ __forceinline__ float rndT(float v);
-template <> __device__ __forceinline__ float rndT<float>(float v) { return v; }
-template <> __device__ __forceinline__ float rndT<__bf16>(float v) { return bf2f(f2bf(v)); }
+#include "tile_lane.h"      // rndT
 
+// The reductions of this file's layouts go through xor-shuffles (the register-resident families use tile_lane.h's row swaps and DPP adds):
 // sum over the 16 lanes that share q (all columns of a C-layout row)
-__device__ __forceinline__ float rsum16(float v) {
+__device__ __forceinline__ float rsum16_shfl(float v) {
   v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 8, 64);
   return v;
 }
 // sum over the 4 lanes that share r (A-layout token spread over q, or the 4 row-quads of one column)
-__device__ __forceinline__ float qsum4(float v) {
+__device__ __forceinline__ float qsum4_shfl(float v) {
   v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
   return v;
 }
-__device__ __forceinline__ float qmax4(float v) {
+__device__ __forceinline__ float qmax4_shfl(float v) {
   v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64));
   return v;
 }
@@ -300,10 +299,10 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
         const float* l2 = L2 + (t0 + r) * t.KL + (long)l * t.Kp;
         float mx = -INFINITY;
         for (int kk = 0; kk < t.k4; ++kk) { const int k = 4 * kk + q; if (rowok && k < K) mx = fmaxf(mx, l2[k]); }
-        mx = qmax4(mx);
+        mx = qmax4_shfl(mx);
         float sum = 0.f;
         for (int kk = 0; kk < t.k4; ++kk) { const int k = 4 * kk + q; if (rowok && k < K) sum += __expf(l2[k] - mx); }
-        sum = qsum4(sum);
+        sum = qsum4_shfl(sum);
         const float inv = rowok ? 1.f / sum : 0.f;
         float u1 = 0.f, u2 = 0.f;
         wave_lds_sync();
@@ -319,7 +318,7 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
           if (rowok && k < t.Kp) stT<T>(aout, (long)l * t.aL + (t0 + r) * t.Kp + k, av);
         }
         if (rowok) for (int k = K4 + q; k < t.Kp; k += 4) stT<T>(aout, (long)l * t.aL + (t0 + r) * t.Kp + k, 0.f);
-        u1 = qsum4(u1); u2 = qsum4(u2);
+        u1 = qsum4_shfl(u1); u2 = qsum4_shfl(u2);
         if (q == 0) { rv[r] = u1; rv[16 + r] = u2; }
         wave_lds_sync();
         // ---- u3 = a^T (T T^T) a  through the matrix pipe ----
@@ -331,7 +330,7 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
         }
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-          u3[x] = rsum16(u3[x]);
+          u3[x] = rsum16_shfl(u3[x]);
           Sx[x] += gv * (float)t.C * rv[4 * q + x];
           Sxx[x] += 2.f * gv * rv[16 + 4 * q + x] + gv * gv * u3[x];
         }
@@ -365,7 +364,7 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
             }
           }
         }
-        c0 = qsum4(c0); c1 = qsum4(c1);
+        c0 = qsum4_shfl(c0); c1 = qsum4_shfl(c1);
         if (q == 0 && dd < DD) { mycol[dd] += c0; mycol[DD + dd] += c1; }
       }
       if (r == 0) {
@@ -500,7 +499,7 @@ __global__ void __launch_bounds__(256) kt_post_small(PostTArgs a, const float* _
           }
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-          const float So = rsum16(so[x]) + H1, Soo = rsum16(soo[x]) + H2;
+          const float So = rsum16_shfl(so[x]) + H1, Soo = rsum16_shfl(soo[x]) + H2;
           mup[x] = So / (float)t.C;
           rp[x] = rsqrtf(fmaxf(Soo / (float)t.C - mup[x] * mup[x], 0.f) + a.ln_eps);
         }
@@ -665,7 +664,7 @@ __global__ void __launch_bounds__(256) kt_post_small_bwd(PostBTArgs a, const flo
 #pragma unroll
       for (int x = 0; x < 4; ++x) {
         const int row = 4 * q + x;
-        zz[x] = rsum16(zz[x]);
+        zz[x] = rsum16_shfl(zz[x]);
         rp[x] = rw[48 + row];
         const float mup = rw[64 + row], da1 = rw[row], da2 = rw[16 + row], da3 = rw[32 + row];
         dSo[x] = 0.f; dSoo[x] = 0.f;
@@ -701,7 +700,7 @@ __global__ void __launch_bounds__(256) kt_post_small_bwd(PostBTArgs a, const flo
               Ot[row * ld + dd] = dz;
             }
           }
-          c0 = qsum4(c0); c1 = qsum4(c1);
+          c0 = qsum4_shfl(c0); c1 = qsum4_shfl(c1);
           if (q == 0 && jp < dgp) { mycol[dd] += c0; mycol[DD + dd] += c1; }
         }
       wave_lds_sync();
@@ -794,7 +793,7 @@ __global__ void __launch_bounds__(256) kt_mid_bwd(MidBTArgs a, const float* __re
               c0 += dy; c1 += dy * zh;
             }
           }
-          c0 = qsum4(c0); c1 = qsum4(c1);
+          c0 = qsum4_shfl(c0); c1 = qsum4_shfl(c1);
           if (q == 0 && jp < dgp) { mycol[dd] += c0; mycol[DD + dd] += c1; }
         }
       wave_lds_sync();
@@ -919,7 +918,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
             Dt[(4 * q + x) * t.lda_d + dd] = dzr;
           }
         }
-        c0 = qsum4(c0); c1 = qsum4(c1);
+        c0 = qsum4_shfl(c0); c1 = qsum4_shfl(c1);
         if (q == 0 && dd < DD) { mycol[dd] += c0; mycol[DD + dd] += c1; }
       }
       float dSx[4], dSxx[4];
@@ -927,7 +926,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
       for (int x = 0; x < 4; ++x) {
         dSx[x] = 0.f; dSxx[x] = 0.f;
         if (a.ln_before) {
-          const float sdr = rsum16(s_dr[x]), sdm = rsum16(s_dmu[x]);
+          const float sdr = rsum16_shfl(s_dr[x]), sdm = rsum16_shfl(s_dmu[x]);
           float dmu = -rr[x] * sdm;
           const float dvar = sdr * (-0.5f) * rr[x] * rr[x] * rr[x];
           dSxx[x] = dvar / (float)t.C;
@@ -940,7 +939,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
           else { dsxs[ti] += dSx[x]; dsxs[t.NT + ti] += dSxx[x]; }
         }
         if (nxn) {                   // x' = x + g xr : statistics gradients to (sum xr, sum xr^2, x . xr) and to the gate
-          const float zr = rsum16(s_zr[x]);
+          const float zr = rsum16_shfl(s_zr[x]);
           if (r == 0 && ok[x]) {
             const long ti = t0 + 4 * q + x;
             const float v0 = gv * dSx[x], v1 = 2.f * gv * gv * dSxx[x], v2 = 2.f * gv * dSxx[x];
@@ -963,7 +962,7 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
           if (rowok && k < K) { av = ldT<T>(ain, aplane + k); u1 += av * s_tb[k]; u2 += av * L2[arow + k]; }
           At[r * t.lda_k + k] = av;
         }
-        u1 = qsum4(u1); u2 = qsum4(u2);
+        u1 = qsum4_shfl(u1); u2 = qsum4_shfl(u2);
         if (q == 0) { rv[r] = u1; rv[16 + r] = u2; }
         wave_lds_sync();
         float u3[4] = {0.f, 0.f, 0.f, 0.f}, dgr[4] = {0.f, 0.f, 0.f, 0.f};
@@ -992,13 +991,13 @@ __global__ void __launch_bounds__(256) kt_pre_small_bwd(PreBTArgs a, const float
             }
             Da[(4 * q + x) * t.lda_k + k] = da;
           }
-          ck = qsum4(ck);
+          ck = qsum4_shfl(ck);
           if (q == 0 && k < K) mykcol[k] += ck;
         }
 #pragma unroll
         for (int x = 0; x < 4; ++x) {
-          sada[x] = rsum16(sada[x]);
-          u3[x] = rsum16(u3[x]); dgr[x] = rsum16(dgr[x]);
+          sada[x] = rsum16_shfl(sada[x]);
+          u3[x] = rsum16_shfl(u3[x]); dgr[x] = rsum16_shfl(dgr[x]);
           if (r == 0 && ok[x]) sdg += dSx[x] * (float)t.C * rv[4 * q + x] + dSxx[x] * (2.f * rv[16 + 4 * q + x] + 2.f * gv * u3[x]) + dgr[x];
         }
         wave_lds_sync();

@@ -163,7 +163,7 @@ template <int E> constexpr size_t psb_lds(int nfr) { return (size_t)psb_fixed_fl
 // one transposed mat-vec step of mmT_split with the matrix operand split into bf16 planes ONCE (registers, whole kernel)
 __device__ __forceinline__ f32x4 mm_presplit(const bf16x8& ah, const bf16x8& al, const float4& p0, const float4& p1) {
   bf16x8 ph, pl;
-  kf_split8(p0, p1, ph, pl);
+  split8(p0, p1, ph, pl);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, ph, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, pl, acc, 0, 0, 0);
@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small_bwd(SPostBArgs 
       float4 m0, m1;
 #pragma unroll
       for (int x = 0; x < 4; ++x) { at(m0, x) = g[(4 * q + x) * FDG]; at(m1, x) = g[(16 + 4 * q + x) * FDG]; }
-      kf_split8(m0, m1, gh[gi][ct], gl[gi][ct]);
+      split8(m0, m1, gh[gi][ct], gl[gi][ct]);
     }
   f32x4 gacc[2][3];                                 // weighted Gram of this wave's tokens: [group][16 x 16 tiles (0,0), (0,1), (1,1)] -- symmetric: (1,0) = (0,1)^T
 #pragma unroll
@@ -496,7 +496,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_mid_bwd(SMidBArgs a, const
 #pragma unroll
         for (int x = 0; x < 4; ++x) { at(m0, x) = g[(4 * q + x) * FDG]; at(m1, x) = g[(16 + 4 * q + x) * FDG]; }
       }
-      kf_split8(m0, m1, gh[gi][ct], gl[gi][ct]);
+      split8(m0, m1, gh[gi][ct], gl[gi][ct]);
     }
   const bool relu = a.relu_of_e[e];
   int it = 0;
@@ -645,7 +645,7 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_post_small(SPostArgs a, co
       float4 m0, m1;
 #pragma unroll
       for (int x = 0; x < 4; ++x) { at(m0, x) = g[(4 * q + x) * FDG]; at(m1, x) = g[(16 + 4 * q + x) * FDG]; }
-      kf_split8(m0, m1, gh[gi][ct], gl[gi][ct]);
+      split8(m0, m1, gh[gi][ct], gl[gi][ct]);
     }
   const bool relu = a.relu_of_e[e];
   const float fC = (float)t.C;
@@ -776,7 +776,7 @@ __device__ __forceinline__ void mm_lds_issue(f32x4& a0, f32x4& a1, unsigned mt_a
 }
 __device__ __forceinline__ f32x4 mm_lds_finish(const f32x4& a0, const f32x4& a1, const float4& p0, const float4& p1) {
   bf16x8 ah, al;
-  kf_split8(make_float4(a0[0], a0[1], a0[2], a0[3]), make_float4(a1[0], a1[1], a1[2], a1[3]), ah, al);
+  split8(make_float4(a0[0], a0[1], a0[2], a0[3]), make_float4(a1[0], a1[1], a1[2], a1[3]), ah, al);
   return mm_presplit(ah, al, p0, p1);
 }
 
@@ -1250,17 +1250,17 @@ __global__ void __launch_bounds__(WS<E>::NTHR, 2) kfs_pre_bwd(SPreBArgs a, const
 #pragma unroll
           for (int i = 0; i < 16; ++i) lds_use(tw_[i]);
           bf16x8 ah0, al0, ah1, al1;
-          kf_split8(make_float4(tw_[0], tw_[1], tw_[2], tw_[3]), make_float4(tw_[4], tw_[5], tw_[6], tw_[7]), ah0, al0);
-          kf_split8(make_float4(tw_[8], tw_[9], tw_[10], tw_[11]), make_float4(tw_[12], tw_[13], tw_[14], tw_[15]), ah1, al1);
+          split8(make_float4(tw_[0], tw_[1], tw_[2], tw_[3]), make_float4(tw_[4], tw_[5], tw_[6], tw_[7]), ah0, al0);
+          split8(make_float4(tw_[8], tw_[9], tw_[10], tw_[11]), make_float4(tw_[12], tw_[13], tw_[14], tw_[15]), ah1, al1);
           f32x4 twd;
-          {                                                            // tile_fast.hip::mmT_split<4>: chunk pairs (0, 1) and (2, 3) chained
+          {                                                            // tile_lane.h::mmT_split<4>: chunk pairs (0, 1) and (2, 3) chained
             bf16x8 ph, pl;
-            kf_split8(dzr[0], dzr[1], ph, pl);
+            split8(dzr[0], dzr[1], ph, pl);
             twd = f32x4{0.f, 0.f, 0.f, 0.f};
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al0, ph, twd, 0, 0, 0);
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah0, pl, twd, 0, 0, 0);
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah0, ph, twd, 0, 0, 0);
-            kf_split8(dzr[2], dzr[3], ph, pl);
+            split8(dzr[2], dzr[3], ph, pl);
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al1, ph, twd, 0, 0, 0);
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah1, pl, twd, 0, 0, 0);
             twd = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah1, ph, twd, 0, 0, 0);

@@ -19,7 +19,7 @@ __device__ __forceinline__ int opaque0() { int v = 0; asm volatile("" : "+v"(v))
 __device__ __forceinline__ float& at(float4& v, int x) { return ((float*)&v)[x]; }
 __device__ __forceinline__ float at(const float4& v, int x) { return ((const float*)&v)[x]; }
 
-// MIT 20 / 21 (round 6): the mat-vec in the form the TUNED kernels run (csrc/tile_fast.hip::mmT_split, csrc/tile_stream.hip::mm_presplit): both
+// MIT 20 / 21 (round 6): the mat-vec in the form the TUNED kernels run (csrc/tile_lane.h::mmT_split, csrc/tile_stream.hip::mm_presplit): both
 // operands as two bf16 planes, hi.hi + hi.lo + lo.hi on v_mfma_f32_16x16x32_bf16 -- does THAT form move beside a dense-MFMA aggressor?
 // 21: + the per-block column sums of those kernels (DPP row sums, rsum16) against a shuffle butterfly over the same values.
 __device__ __forceinline__ void split8(const float4& v0, const float4& v1, bf16x8& hi, bf16x8& lo) {

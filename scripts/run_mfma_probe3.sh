@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6: the co-residency probe with the victim in the form the TUNED kernels run (MIT 20: split-bf16 mat-vecs on v_mfma_f32_16x16x32_bf16 as
-# csrc/tile_fast.hip::mmT_split / csrc/tile_stream.hip::mm_presplit; MIT 21: + their DPP column sums), 200 repetitions beside the aggressors
+# csrc/tile_lane.h::mmT_split / csrc/tile_stream.hip::mm_presplit; MIT 21: + their DPP column sums), 200 repetitions beside the aggressors
 # that corrupt the fp32-MFMA form (MIT 0).  Build (container): for m in 0 20 21; do hipcc --offload-arch=gfx950 -O3 -DMIT=$m scripts/mfma_probe.hip
 #   -o avmoe_amd/lib/variants/probe/mfma_probe_mit$m; done ; on the GPU box: bash scripts/run_mfma_probe3.sh -> gpurun_out/r6/mfma_probe3.txt
 P=avmoe_amd/lib/variants/probe; O=gpurun_out/r6; mkdir -p $O; L=$O/mfma_probe3.txt; : > $L

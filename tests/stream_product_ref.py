@@ -9,7 +9,7 @@ contributes error and the bound per element follows from the product's own arith
                                           and K segments only reorder the same sum.
            + 2^-8 * |ref|                 a bf16 store (8 significant bits: unit roundoff 2^-8, reached just above a power of two)
            + 2^-16 * mag                  an fp32 operand fed to the bf16 matrix pipe as two bf16 planes with lo x lo dropped: hi carries 8
-                                          bits, lo 8 more (csrc/tile_fast_dev.h::kf_split8 + csrc/tile_stream.hip::mm_presplit)
+                                          bits, lo 8 more (csrc/tile_lane.h::split8 + csrc/tile_stream.hip::mm_presplit)
 
 Nothing here is fitted to a measured error.  Works on CPU and GPU tensors alike (the GPU tests keep the fp64 products on the device).
 """

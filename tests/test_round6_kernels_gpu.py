@@ -103,7 +103,7 @@ def test_streaming_kernels_repeat_bit_for_bit():
 @pytest.mark.parametrize("stream", [False, True])
 def test_split_bf16_matvecs_with_large_mean_small_variance_activations(stream):
     """The mat-vecs of the bf16 instantiations run on the bf16 matrix pipe with both operands as TWO bf16 planes, lo . lo dropped
-    (csrc/tile_fast.hip::mmT_split, csrc/tile_stream.hip::mm_presplit).  Worst case for them (ADVICE r4): bottleneck activations z' with a
+    (csrc/tile_lane.h::mmT_split, csrc/tile_stream.hip::mm_presplit).  Worst case for them (ADVICE r4): bottleneck activations z' with a
     large mean and a small variance (BatchNorm-1 with bias 4 and weight 0.05 in front of the ReLU: z' ~ 4 +- 0.05), so that the LayerNorm-post
     variance  Soo / C - mup^2 = (z'^T G z' + 2 z' . vh + H2) / C - ((z' . us + H1) / C)^2  is a small difference of large numbers.
     ISOLATED from everything else bf16 does to such activations (the stored z and Apost, the Gram kernel's operands: the oracle comparison

@@ -2,7 +2,7 @@
 on one stream (forward).  Round 4 found v_mfma_f32_16x16x4_f32 returning wrong sums in the bottleneck-space kernels of bf16 sites
 whenever a bf16 GEMM of the engine ran on the same compute units from the other stream (one 16-token tile in ~10^3, off by ~1 %; about
 every second step at the Swin-L / HTS-AT stage-0 shapes; never on one stream): the mat-vecs of the bf16 instantiations now run on the
-bf16 matrix pipe in split form (csrc/tile_gen.inc::mmT_split).  This is the guard: the stage-0 site shape of BASELINE configs 3 / 4
+bf16 matrix pipe in split form (csrc/tile_lane.h::mmT_split).  This is the guard: the stage-0 site shape of BASELINE configs 3 / 4
 (C 96 / 192, 4096 / 2304 tokens, 20 frames), forward + backward, workspaces poisoned."""
 import pytest
 import torch
