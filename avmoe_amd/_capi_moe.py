@@ -121,23 +121,16 @@ def declare(L):
     L.avmoe_moe_backward_part.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoePtrs),
                                           C.c_int32, C.c_void_p]
-    if hasattr(L, "avmoe_moe_backward_ex"):          # (found by symbol: added under ABI 11 -- dprobs, and dOut == NULL for the router-only backward)
-        L.avmoe_moe_backward_ex.restype = C.c_int
-        L.avmoe_moe_backward_ex.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoePtrs),
-                                            C.c_int32, C.c_void_p]
-    if hasattr(L, "avmoe_moe_forward_topk"):         # (found by symbol: added under ABI 11 -- top-k gating of the mixture)
-        L.avmoe_moe_forward_topk.restype = C.c_int
-        L.avmoe_moe_forward_topk.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p, C.c_int32,
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p]
-    if hasattr(L, "avmoe_moe_forward_aux"):          # (found by symbol: added under ABI 11 -- the router auxiliary losses: z-loss, balance loss)
-        L.avmoe_moe_forward_aux.restype = C.c_int
-        L.avmoe_moe_forward_aux.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p, C.c_int32,
-                                            C.c_int32] + [C.c_void_p] * 9
-        L.avmoe_moe_backward_aux.restype = C.c_int
-        L.avmoe_moe_backward_aux.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs)] + [C.c_void_p] * 8 + \
-                                            [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
+    # the site entry points found by symbol (added under ABI 11: dprobs and dOut == NULL, top-k gating, the router auxiliary losses), keyed on the
+    # newest one; avmoe_site_aux: what the facade asks once (a development A/B may load an older library through AVMOE_LIB)
+    L.avmoe_site_aux = hasattr(L, "avmoe_moe_backward_aux")
+    if L.avmoe_site_aux:
+        head = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p]
+        L.avmoe_moe_forward_topk.restype, L.avmoe_moe_forward_topk.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 7
+        L.avmoe_moe_forward_aux.restype, L.avmoe_moe_forward_aux.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 9
+        L.avmoe_moe_backward_ex.restype = L.avmoe_moe_backward_aux.restype = C.c_int
+        L.avmoe_moe_backward_ex.argtypes = head + [C.c_void_p] * 6 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
+        L.avmoe_moe_backward_aux.argtypes = head + [C.c_void_p] * 7 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

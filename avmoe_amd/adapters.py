@@ -118,9 +118,28 @@ def _publish_aux(module, aux, load):
         module.__dict__["_last_router_aux"] = RouterAux(z, b, load)
 
 
+def _ws_sizes(module, L, desc):
+    """(saved_bytes, scratch_bytes) of a call shape, kept on the module (two plan evaluations otherwise).  THE key of that cache: anything
+    else that comes to decide a workspace size joins it here, for the forward and the backward alike."""
+    key = (desc.S, desc.N, desc.M, desc.dtype, desc.training, desc.shared_gpu)
+    cache = module.__dict__.setdefault("_ws_sizes", {})
+    sizes = cache.get(key)
+    if sizes is None:
+        sizes = (L.avmoe_moe_saved_bytes(C.byref(desc)), L.avmoe_moe_scratch_bytes(C.byref(desc)))
+        if sizes[0] == 0:
+            raise capi.AvmoeError(L.avmoe_last_error().decode())
+        cache[key] = sizes
+    return sizes
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
-    """One avmoe_moe_forward call.  Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or
-    ((2,) [z, balance], load (E,)): the router auxiliary losses of a site with `router_aux` on (avmoe_moe_forward_aux).
+    """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
+    losses.  Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
+    the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
     stream: the handle (int) of the CURRENT stream when the caller already has it (AdapterPair), else looked up."""
@@ -139,13 +158,13 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     desc.shared_gpu = int(shared_gpu)                     # (include/avmoe.h: kernels of another stream may be on the GPU during this call and its backward)
     keep = module._attention_keep(S, N, X.device)
     ptrs = module._fill_ptrs(params, keep, names=names, device=X.device)
-    wkey = (S, N, Y.shape[1], X.dtype, module.training, bool(shared_gpu))
-    sizes = module.__dict__.setdefault("_ws_sizes", {}).get(wkey)      # workspace sizes of this call shape (two plan evaluations otherwise)
-    if sizes is None:
-        sizes = (L.avmoe_moe_saved_bytes(C.byref(desc)), L.avmoe_moe_scratch_bytes(C.byref(desc)))
-        if sizes[0] == 0:
-            raise capi.AvmoeError(L.avmoe_last_error().decode())
-        module.__dict__["_ws_sizes"][wkey] = sizes
+    E = module.num_multimodal_experts + module.num_singlemodal_experts
+    top_k = module.router_top_k
+    k = top_k if (top_k is not None and top_k < E) else 0      # 0: the dense mixture (k >= E is the dense mixture too)
+    renorm = int(module.router_top_k_renorm) if k else 1       # (a dense site records renorm = 1 in `saved`, as avmoe_moe_forward does)
+    if not L.avmoe_site_aux and (k or module.router_aux):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_aux: it serves neither top-k gating nor the router auxiliary losses")
+    sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
     if add_to is not None:
@@ -154,31 +173,22 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         out, desc.accumulate_out = add_to, 1
     else:
         out = torch.empty_like(X)
-    E = module.num_multimodal_experts + module.num_singlemodal_experts
     probs = torch.empty(S, E, device=X.device, dtype=torch.float32)
     idx = torch.empty(S, device=X.device, dtype=torch.int64)
     lb = torch.empty((), device=X.device, dtype=torch.float32)      # always written by the router's kernels (0 without the LB loss)
     if noise is not None:
         noise = noise.to(torch.float32).contiguous()
-    top_k = module.router_top_k
     aux = None
     if module.router_aux:                                # the router auxiliary losses beside the forward (dense or top-k)
-        fn = "avmoe_moe_forward_aux"
         aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
-        st = L.avmoe_moe_forward_aux(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
-                                     noise.data_ptr() if noise is not None else None, top_k if (top_k is not None and top_k < E) else 0,
-                                     int(module.router_top_k_renorm), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
-                                     aux[0].data_ptr(), aux[1].data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
-    elif top_k is not None and top_k < E:                # top-k gating of the mixture (k == E: the dense site, the dense entry point)
-        fn = "avmoe_moe_forward_topk"
-        st = L.avmoe_moe_forward_topk(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
-                                      noise.data_ptr() if noise is not None else None, top_k, int(module.router_top_k_renorm),
-                                      out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), saved.data_ptr(),
-                                      scratch.data_ptr(), stream)
-    else:
+    if L.avmoe_site_aux:
+        fn = "avmoe_moe_forward_aux"
+        st = L.avmoe_moe_forward_aux(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, out.data_ptr(),
+                                     probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
+                                     aux[1].data_ptr() if aux else None, saved.data_ptr(), scratch.data_ptr(), stream)
+    else:                                                # a library from before the _aux entry points (AVMOE_LIB): the plain site, the one second path
         fn = "avmoe_moe_forward"
-        st = L.avmoe_moe_forward(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs),
-                                 noise.data_ptr() if noise is not None else None, out.data_ptr(), probs.data_ptr(),
+        st = L.avmoe_moe_forward(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), out.data_ptr(), probs.data_ptr(),
                                  idx.data_ptr(), lb.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
     desc.accumulate_out = 0
     capi.check(st, fn)
@@ -189,7 +199,7 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
 
 class _SiteBackward:
     """One site's backward through the C ABI, writing (or, with acc_*, adding) the token gradients into dX / dY.
-    run(0) = the whole of it; run(mask) = the sections of avmoe_moe_backward_part (1: touches neither dX nor dY, 2: every
+    run(0) = the whole of it; run(mask) = the sections of avmoe_moe_backward_aux / _part (1: touches neither dX nor dY, 2: every
     writer of dX, 4: every writer of dY), in this order.  finish() returns the parameter gradients in `names` order (None where not needed,
     or for all of them when a gradient sink took them)."""
 
@@ -223,45 +233,33 @@ class _SiteBackward:
             self.gptrs = cm.MoePtrs()
             self.grads = {k: (torch.empty_like(v) if needs[i] else None) for i, (k, v) in enumerate(tensors.items())}
             filler.fill(self.gptrs, [self.grads[k] for k in names])
-        # d_out None: out got no gradient -> the router-only backward (avmoe_moe_backward_ex with dOut = NULL, whole: run(0) only)
+        # d_out None: out got no gradient -> the router-only backward (dOut = NULL, whole: run(0) only)
         self.d_out = d_out.to(self.X.dtype).contiguous() if d_out is not None else None
         self.dprobs = d_probs.to(torch.float32).reshape(desc.S, -1).contiguous() if d_probs is not None else None
         self.lbg = d_lb.to(torch.float32).reshape(1).contiguous() if (d_lb is not None and desc.lb_loss) else None
         self.daux = d_aux.to(torch.float32).reshape(2).contiguous() if d_aux is not None else None      # [g_z, g_balance]
-        wkey = (desc.S, desc.N, desc.M, self.X.dtype, bool(desc.training), bool(desc.shared_gpu))
-        sizes = module.__dict__.get("_ws_sizes", {}).get(wkey)
-        self.scratch = _scratch(self.X.device, sizes[1] if sizes else self.L.avmoe_moe_scratch_bytes(C.byref(desc)), scratch_slot, stream=self.stream)
+        if not self.L.avmoe_site_aux and (self.d_out is None or self.dprobs is not None or self.daux is not None):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_backward_aux: it serves neither a gradient for probs or the router "
+                                  "auxiliary losses nor a backward without a gradient for out")
+        self.scratch = _scratch(self.X.device, _ws_sizes(module, self.L, desc)[1], scratch_slot, stream=self.stream)
         self.dX, self.dY, self.acc = dX, dY, (int(acc_dx), int(acc_dy))
 
     def run(self, parts=0):
         d = self.desc
         d.accumulate_dx, d.accumulate_dy = self.acc
-        if self.daux is not None:                              # a gradient for the router auxiliary losses: _ex plus aux_grad
-            st = self.L.avmoe_moe_backward_aux(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),
-                                               self.d_out.data_ptr() if self.d_out is not None else None,
-                                               self.dprobs.data_ptr() if self.dprobs is not None else None,
-                                               self.lbg.data_ptr() if self.lbg is not None else None, self.daux.data_ptr(),
-                                               self.saved.data_ptr(), self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(),
-                                               C.byref(self.gptrs), int(parts), self.stream)
-            d.accumulate_dx = d.accumulate_dy = 0
-            capi.check(st, "avmoe_moe_backward_aux")
-            return self
-        if self.d_out is None or self.dprobs is not None:      # a gradient for probs, or none for out: the _ex entry point
-            st = self.L.avmoe_moe_backward_ex(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),
-                                              self.d_out.data_ptr() if self.d_out is not None else None,
-                                              self.dprobs.data_ptr() if self.dprobs is not None else None,
-                                              self.lbg.data_ptr() if self.lbg is not None else None, self.saved.data_ptr(),
-                                              self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
-                                              int(parts), self.stream)
-            d.accumulate_dx = d.accumulate_dy = 0
-            capi.check(st, "avmoe_moe_backward_ex")
-            return self
-        st = self.L.avmoe_moe_backward_part(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), self.d_out.data_ptr(),
-                                            self.lbg.data_ptr() if self.lbg is not None else None, self.saved.data_ptr(),
-                                            self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
-                                            int(parts), self.stream)
+        if self.L.avmoe_site_aux:                              # NULL for each upstream gradient that is absent
+            fn = "avmoe_moe_backward_aux"
+            st = self.L.avmoe_moe_backward_aux(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), _ptr(self.d_out),
+                                               _ptr(self.dprobs), _ptr(self.lbg), _ptr(self.daux), self.saved.data_ptr(),
+                                               self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
+                                               int(parts), self.stream)
+        else:                                                  # (a library from before the _aux entry points: __init__ has refused what it cannot serve)
+            fn = "avmoe_moe_backward_part"
+            st = self.L.avmoe_moe_backward_part(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), self.d_out.data_ptr(),
+                                                _ptr(self.lbg), self.saved.data_ptr(), self.scratch.data_ptr(), self.dX.data_ptr(),
+                                                self.dY.data_ptr(), C.byref(self.gptrs), int(parts), self.stream)
         d.accumulate_dx = d.accumulate_dy = 0
-        capi.check(st, "avmoe_moe_backward")
+        capi.check(st, fn)
         return self
 
     def fused_ok(self, other):

@@ -46,75 +46,31 @@ size_t avmoe_moe_scratch_bytes(const avmoe_moe_desc* desc) {
   return make_plan(desc, &pl) == OK ? pl.scratch_bytes : 0;
 }
 
-int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
-                      const float* noise, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
-                      void* stream) {
-  Plan pl;
-  AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("avmoe_moe_forward: null pointer"); return ERR_BAD_ARG; }
-  return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream);
-}
+}  // extern "C"
 
-int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
-                           int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
-                           void* stream) {
+// The one forward behind avmoe_moe_forward / _topk / _aux (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
+static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                        const float* noise, int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux,
+                        float* load, void* saved, void* scratch, void* stream) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("avmoe_moe_forward_topk: null pointer"); return ERR_BAD_ARG; }
-  if (top_k < 1 || top_k > pl.d.E) { set_last_error("avmoe_moe_forward_topk: top_k %d not in [1, %d]", top_k, pl.d.E); return ERR_BAD_ARG; }
-  const int k = top_k == pl.d.E ? 0 : top_k;            // every expert kept: the dense site, whatever renorm says
-  return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0);
-}
-
-int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
-                          int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
-                          void* saved, void* scratch, void* stream) {
-  Plan pl;
-  AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("avmoe_moe_forward_aux: null pointer"); return ERR_BAD_ARG; }
-  if (top_k < 0 || top_k > pl.d.E) { set_last_error("avmoe_moe_forward_aux: top_k %d not in [0, %d]", top_k, pl.d.E); return ERR_BAD_ARG; }
-  const int k = top_k == pl.d.E ? 0 : top_k;            // 0 and E: the dense mixture (the load then counts every frame's first expert)
+  if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("%s: null pointer", fn); return ERR_BAD_ARG; }
+  if (top_k < k_min || top_k > pl.d.E) { set_last_error("%s: top_k %d not in [%d, %d]", fn, top_k, k_min, pl.d.E); return ERR_BAD_ARG; }
+  const int k = top_k == pl.d.E ? 0 : top_k;            // 0 and E: the dense mixture, whatever renorm says (the load then counts every frame's first expert)
   return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0,
                      aux, aux ? load : nullptr);
 }
 
-int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
-                       const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
-                       const avmoe_moe_ptrs* grads, void* stream) {
+// The one backward behind avmoe_moe_backward / _part / _ex / _aux (null_dout: dOut == NULL asks for the router-only backward, else it is refused)
+static int site_backward(const char* fn, bool null_dout, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                         const void* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved, void* scratch, void* dX,
+                         void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !dOut || !saved || !scratch || !dX || !dY || !grads) {
-    set_last_error("avmoe_moe_backward: null pointer"); return ERR_BAD_ARG;
-  }
-  return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream);
-}
-
-int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
-                            const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
-                            const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
-  Plan pl;
-  AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !dOut || !saved || !scratch || !dX || !dY || !grads || parts < 0 || parts > 127) {
-    set_last_error("avmoe_moe_backward_part: null pointer or parts not in 0..127"); return ERR_BAD_ARG;
-  }
-  if ((parts & 4) && (parts & 24)) {        // 4 IS sections 8 + 16: asking for both would run the hop-1 chain twice into the same accumulators
-    set_last_error("avmoe_moe_backward_part: parts %d combines section 4 with its halves 8 / 16", parts); return ERR_BAD_ARG;
-  }
-  return moe_backward(pl, X, Y, *params, dOut, lb_grad, (char*)saved, (char*)scratch, dX, dY, *grads, (hipStream_t)stream, parts);
-}
-
-}  // extern "C"
-
-// avmoe_moe_backward_ex / avmoe_moe_backward_aux (`fn`: the name in the error strings)
-static int backward_ex(const char* fn, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
-                       const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved, void* scratch, void* dX, void* dY,
-                       const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
-  Plan pl;
-  AVMOE_TRY(make_plan(desc, &pl));
-  if (!X || !Y || !params || !saved || !scratch || !dX || !dY || !grads || parts < 0 || parts > 127) {
+  if (!X || !Y || !params || (!dOut && !null_dout) || !saved || !scratch || !dX || !dY || !grads || parts < 0 || parts > 127) {
     set_last_error("%s: null pointer or parts not in 0..127", fn); return ERR_BAD_ARG;
   }
-  if ((parts & 4) && (parts & 24)) {
+  if ((parts & 4) && (parts & 24)) {        // 4 IS sections 8 + 16: asking for both would run the hop-1 chain twice into the same accumulators
     set_last_error("%s: parts %d combines section 4 with its halves 8 / 16", fn, parts); return ERR_BAD_ARG;
   }
   if (!dOut) {                              // out gets no gradient: the router-only backward, whole (it has no sections)
@@ -127,16 +83,46 @@ static int backward_ex(const char* fn, const avmoe_moe_desc* desc, const void* X
 
 extern "C" {
 
+int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                      const float* noise, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
+                      void* stream) {
+  return site_forward("avmoe_moe_forward", 0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, saved, scratch, stream);
+}
+
+int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                           int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
+                           void* stream) {
+  return site_forward("avmoe_moe_forward_topk", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, saved, scratch, stream);
+}
+
+int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                          int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
+                          void* saved, void* scratch, void* stream) {
+  return site_forward("avmoe_moe_forward_aux", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, saved, scratch, stream);
+}
+
+int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                       const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
+                       const avmoe_moe_ptrs* grads, void* stream) {
+  return site_backward("avmoe_moe_backward", false, desc, X, Y, params, dOut, nullptr, lb_grad, nullptr, saved, scratch, dX, dY, grads, 0, stream);
+}
+
+int avmoe_moe_backward_part(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                            const void* dOut, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
+                            const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
+  return site_backward("avmoe_moe_backward_part", false, desc, X, Y, params, dOut, nullptr, lb_grad, nullptr, saved, scratch, dX, dY, grads, parts, stream);
+}
+
 int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
                           const float* dprobs, const float* lb_grad, void* saved, void* scratch, void* dX, void* dY,
                           const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
-  return backward_ex("avmoe_moe_backward_ex", desc, X, Y, params, dOut, dprobs, lb_grad, nullptr, saved, scratch, dX, dY, grads, parts, stream);
+  return site_backward("avmoe_moe_backward_ex", true, desc, X, Y, params, dOut, dprobs, lb_grad, nullptr, saved, scratch, dX, dY, grads, parts, stream);
 }
 
 int avmoe_moe_backward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const void* dOut,
                            const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved, void* scratch, void* dX,
                            void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream) {
-  return backward_ex("avmoe_moe_backward_aux", desc, X, Y, params, dOut, dprobs, lb_grad, aux_grad, saved, scratch, dX, dY, grads, parts, stream);
+  return site_backward("avmoe_moe_backward_aux", true, desc, X, Y, params, dOut, dprobs, lb_grad, aux_grad, saved, scratch, dX, dY, grads, parts, stream);
 }
 
 int avmoe_moe_backward_dx_dy(const avmoe_moe_desc* desc_a, const void* X_a, void* saved_a, void* scratch_a,
@@ -157,7 +143,7 @@ int avmoe_router_forward(const avmoe_moe_desc* desc, const float* rin, const avm
   if (hipMemcpyAsync((char*)saved + pl.o_rin, rin, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
     set_last_error("avmoe_router_forward: copy of rin failed"); return ERR_LAUNCH;
   }
-  return k_router(pl, (char*)saved, (char*)scratch, *params, noise, probs, idx, lb, (hipStream_t)stream);
+  return k_router(pl, (char*)saved, (char*)scratch, *params, noise, probs, idx, lb, (hipStream_t)stream, 0, 1, nullptr, nullptr);
 }
 
 int avmoe_expert_forward_cross(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, int32_t j,

@@ -365,7 +365,23 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
 
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
              const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
-             const float* aux_grad = nullptr);
+             const float* aux_grad);
+
+// the one forward behind avmoe_host_moe_forward / _topk / _aux (k_min: the smallest top_k the entry point takes)
+int forward_entry(int k_min, const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, int top_k,
+                  int renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load) {
+  Ctx c;
+  if (int rc = setup(desc, c)) return rc;
+  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
+  if (top_k < k_min || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [%d, %d]", top_k, k_min, c.E);
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
+  if (int rc = forward(c, X, Y, *params, noise, out, probs, idx, lb, true)) return rc;
+  if (aux) {
+    aux[0] = c.aux[0]; aux[1] = c.aux[1];
+    if (load) for (int e = 0; e < c.E; ++e) load[e] = c.load[e];
+  }
+  return AVMOE_OK;
+}
 
 }  // namespace
 
@@ -377,10 +393,7 @@ size_t avmoe_host_moe_saved_bytes(const avmoe_moe_desc* desc) { (void)desc; retu
 int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, float* out,
                            float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  Ctx c;
-  if (int rc = setup(desc, c)) return rc;
-  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
-  return forward(c, X, Y, *params, noise, out, probs, idx, lb, true);
+  return forward_entry(0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr);
 }
 
 int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
@@ -392,35 +405,20 @@ int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const fl
 int avmoe_host_moe_forward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  Ctx c;
-  if (int rc = setup(desc, c)) return rc;
-  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
-  if (top_k < 1 || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [1, %d]", top_k, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
-  return forward(c, X, Y, *params, noise, out, probs, idx, lb, true);
+  return forward_entry(1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr);
 }
 int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                  const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                  const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 1) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, nullptr);
 }
 int avmoe_host_moe_forward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
                                void* saved) {
   (void)saved;
-  Ctx c;
-  if (int rc = setup(desc, c)) return rc;
-  if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
-  if (top_k < 0 || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [0, %d]", top_k, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
-  if (int rc = forward(c, X, Y, *params, noise, out, probs, idx, lb, true)) return rc;
-  if (aux) {
-    aux[0] = c.aux[0]; aux[1] = c.aux[1];
-    if (load) for (int e = 0; e < c.E; ++e) load[e] = c.load[e];
-  }
-  return AVMOE_OK;
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load);
 }
 int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
@@ -433,7 +431,7 @@ int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads) {
   (void)saved;
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1, nullptr);
 }
 
 }  // extern "C"

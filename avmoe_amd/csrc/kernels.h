@@ -39,8 +39,8 @@ int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs&
 int k_onehot_noise(float* noise, int S, int E, int hot, float value, hipStream_t st);      // sub-ops of the C ABI (fwd_kernels.hip)
 int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float* rowb, const float* colb, hipStream_t st);
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k = 0, int renorm = 1,    // top_k 0: the dense mixture
-             float* aux_out = nullptr, float* load_out = nullptr);                               // aux_out: [z, balance] (avmoe_moe_forward_aux)
+             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm,            // top_k 0: the dense mixture
+             float* aux_out, float* load_out);                                                   // aux_out: [z, balance] (avmoe_moe_forward_aux)
 // ---- forward: per token -----------------------------------------------------------------------
 int k_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
 int k_bn1_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
@@ -50,7 +50,7 @@ int k_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptr
 
 // ---- backward ---------------------------------------------------------------------------------
 int k_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
-                     const avmoe_moe_ptrs& grads, hipStream_t st, int dap16 = 0);   // dap16: dApost = [T columns | fp32 dApx]
+                     const avmoe_moe_ptrs& grads, hipStream_t st, int dap16);       // dap16: dApost = [T columns | fp32 dApx]
 int k_post_prep_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
                     const avmoe_moe_ptrs& grads, hipStream_t st);
 int k_mid_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
@@ -64,7 +64,7 @@ int k_mid_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_m
 int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
                              const avmoe_moe_ptrs& grads, hipStream_t st);
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad = nullptr);
+                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad);
 int k_softmax_rows_bwd(int bf16, const void* a, const float* da, long rows, int n, int ld, void* out_dl, void* out_t, int grp,
                        int ldT, hipStream_t st);
 int k_finish_dT(const Plan& pl, char* saved, char* scratch, hipStream_t st);
@@ -90,7 +90,7 @@ bool tile_fast_ok(const Dims& d);
 bool tile_fast_shape(const Dims& d);      // the shape alone (the Gram-fused mode of gram.hip serves it on either kernel family)
 int kf_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
 int kf_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kf_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16 = 0);
+int kf_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16);
 int kf_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st);
 int kf_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
 int kf_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
@@ -112,7 +112,7 @@ int kfs_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
 bool tile_gen_ok(const Dims& d);
 int kg_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
 int kg_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16 = 0);
+int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16);
 int kg_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st);
 int kg_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
 int kg_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);

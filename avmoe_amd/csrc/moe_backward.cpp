@@ -36,6 +36,17 @@ static void fill_dx_args(GemmArgs& g, const Plan& pl, const void* X, const char*
   GemmSeg& t = g.seg[0]; t.A = at(sc, pl.o_dL2x); t.B = at(sv, pl.o_Text); t.K = d.KLT; t.a_layout = K_MAJOR; t.b_layout = MN_MAJOR; t.lda = d.KLp; t.ldb = d.C;
   t.sA1 = (long)d.N * d.KLp; t.sB1 = (long)d.KLT * d.C; t.sB2 = d.Cg;
 }
+// the operands of  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  (phase 6; without a cross-modal expert: wbar (x) d ybar[s] alone, `q` stays unset) as the
+// K segments `v` and `q` of a product.  sB2: what B advances by per group of that product -- 0 for the site's own ungrouped one, the other site's Cg
+// when moe_backward_dx_dy hangs the two behind that site's dX product
+static void fill_dy_args(GemmSeg& v, GemmSeg& q, const Plan& pl, const char* sv, const char* sc, long sB2) {
+  const Dims& d = pl.d;
+  v.A = at(sv, pl.o_BmX); v.B = at(sc, pl.o_dV); v.K = d.Kcyb; v.a_layout = v.b_layout = MN_MAJOR; v.lda = d.Mb; v.ldb = d.Cy;
+  v.sA1 = (long)d.Kcyb * d.Mb; v.sB1 = (long)d.Kcyb * d.Cy; v.sB2 = sB2;
+  if (d.Kcy == 0) return;
+  q.A = at(sc, pl.o_dRT); q.B = at(sv, pl.o_Qx); q.K = d.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = d.Kcyp; q.ldb = d.Cy;
+  q.sA1 = (long)d.M * d.Kcyp; q.sB2 = sB2;
+}
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const void* dOut, const float* lb_grad,
                  char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads_in, hipStream_t st, int parts, const float* dprobs,
@@ -365,8 +376,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   }
   AVMOE_TRY(k_prep_dBm(pl, sc, st));
   }
-  if (d.Kcy > 0) {
-    if (do6a) {
+  if (d.Kcy > 0 && do6a) {
     {                                                      // dA1[s] = [dBm | dab][s] [Wc | bc]^T
       GemmArgs g = base();
       g.A = sc + pl.o_dBmT; g.B = sv + pl.o_WcK; g.C = sc + pl.o_L1;
@@ -408,19 +418,16 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
       if (rc < 0) return rc;
       if (rc != OK) AVMOE_TRY(run(g, true));
     }
-    }
-    if (do6b)
-    {   // dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q   -- one pass over dY (two K segments)
-      GemmArgs g = base();
-      g.A = sv + pl.o_BmX; g.B = sc + pl.o_dV; g.C = dY;
-      g.M = d.M; g.N = d.Cy; g.K = d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Mb; g.ldb = d.Cy; g.nb1 = d.S;
-      g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.Kcyb * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.M * d.Cy; g.out_dtype = dt;
-      GemmSeg& q = g.seg[0]; q.A = sc + pl.o_dRT; q.B = sv + pl.o_Qx; q.K = d.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = d.Kcyp; q.ldb = d.Cy; q.sA1 = (long)d.M * d.Kcyp;
-      g.accumulate = d.acc_dy;
-      leaf(g, 16);
-      AVMOE_TRY(run(g, false));
-    }
-    if (do6a) {
+  }
+  if (do6b) {   // dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q   -- one pass over dY (two K segments; no cross-modal expert: wbar (x) d ybar[s] alone)
+    GemmArgs g = base();
+    fill_dy_args(g, g.seg[0], pl, sv, sc, 0);
+    g.C = dY; g.M = d.M; g.N = d.Cy; g.nb1 = d.S; g.sCi = d.Cy; g.sC1 = (long)d.M * d.Cy; g.out_dtype = dt;
+    g.accumulate = d.acc_dy;
+    if (d.Kcy > 0) leaf(g, 16);                            // (the one-segment product has always stayed on AVMOE_BWD_PLANES)
+    AVMOE_TRY(run(g, false));
+  }
+  if (d.Kcy > 0 && do6a) {
     {                                                      // dT0[y slots] += dQ Wf^T
       GemmArgs g = base();
       g.A = sc + pl.o_dQT; g.B = sv + pl.o_WfT; g.C = sc + pl.o_dT0;
@@ -435,15 +442,6 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
       leaf(g, 8);
       AVMOE_TRY(run(g, false));
     }
-    }
-  }
-  if (d.Kcy == 0 && do6b) {                                // no cross-modal expert: dY[s] = wbar (x) d ybar[s]
-    GemmArgs g = base();
-    g.A = sv + pl.o_BmX; g.B = sc + pl.o_dV; g.C = dY;
-    g.M = d.M; g.N = d.Cy; g.K = d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Mb; g.ldb = d.Cy; g.nb1 = d.S;
-    g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.Kcyb * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.M * d.Cy; g.out_dtype = dt;
-    g.accumulate = d.acc_dy;
-    AVMOE_TRY(run(g, false));
   }
   // ---- phase 6b: latent self attention on X (AVS v2) ----------------------------------------------
   if (d.Kcx > 0) {
@@ -495,12 +493,7 @@ int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, cons
   GemmArgs g; g.dtype = a.bf16 ? GEMM_BF16 : GEMM_F32; g.split3 = (AVMOE_LEAF2 & 16) ? 2 : AVMOE_BWD_PLANES;
   g.slabs = (float*)at(sca, pa.o_slabs);                   // (the streaming form's dump word)
   fill_dx_args(g, pa, X, sva, sca, dX);
-  GemmSeg& v = g.seg[1]; v.A = at(svb, pb.o_BmX); v.B = at(scb, pb.o_dV); v.K = b.Kcyb; v.a_layout = v.b_layout = MN_MAJOR; v.lda = b.Mb; v.ldb = b.Cy;
-  v.sA1 = (long)b.Kcyb * b.Mb; v.sB1 = (long)b.Kcyb * b.Cy; v.sB2 = a.Cg;
-  if (b.Kcy > 0) {
-    GemmSeg& q = g.seg[2]; q.A = at(scb, pb.o_dRT); q.B = at(svb, pb.o_Qx); q.K = b.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = b.Kcyp; q.ldb = b.Cy;
-    q.sA1 = (long)b.M * b.Kcyp; q.sB2 = a.Cg;
-  }
+  fill_dy_args(g.seg[1], g.seg[2], pb, svb, scb, a.Cg);
   // The streaming form (dx_stream3.hip: the tuned bf16 shape), or, round 6, the same sum on the tiled engine: the token gradient is written
   // once instead of written by site A and read back + added by site B.  fp32 sites only (AVMOE_DXDY_GEN = 1; 3 = bf16 sites of the
   // generalised shapes too: measured, moe_run.h).

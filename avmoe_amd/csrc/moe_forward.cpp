@@ -298,7 +298,7 @@ int expert_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe
       q.e[o].bn1_nbt = q.e[o].bn2_nbt = nullptr;
     }
   }
-  return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st);
+  return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st, 0, 1, nullptr, nullptr);
 }
 
 // The remap MATERIALISED (the product path folds it away): Yt = conv_adapter(Y) (S, N, Cy), then

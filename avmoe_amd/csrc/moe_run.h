@@ -49,21 +49,22 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
 int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& ep, const avmoe_expert_ptrs& eg, int slot, const void* dxr,
                         char* saved, char* scratch, float* slabs, size_t slab_cap, void* dX, hipStream_t st);
 
-// top_k > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture
+// Every caller states every option (no defaulted parameters: one that forgets an argument must not compile).
+// top_k > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture (renorm then only lands in the mode word of `saved`, unread for k = 0)
 // aux_out: [z, balance], the router auxiliary losses (avmoe_moe_forward_aux), load_out (E) with them; NULL: not formed
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const float* noise, void* out,
-                float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st, int top_k = 0,
-                int renorm = 1, float* aux_out = nullptr, float* load_out = nullptr);
+                float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st, int top_k,
+                int renorm, float* aux_out, float* load_out);
 
 // aux_grad: [g_z, g_balance] after a forward with aux_out (avmoe_moe_backward_aux), or NULL
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const void* dOut, const float* lb_grad,
-                 char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts = 0,
-                 const float* dprobs = nullptr, const float* aux_grad = nullptr);
+                 char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts,
+                 const float* dprobs, const float* aux_grad);
 // the backward when `out` gets no gradient (router_only_bwd.hip): only the router and the mean / remap chain carry gradient --
 // the router backward, one pass over Y, one broadcast write of dX, small reductions; every expert gradient is written as 0
 int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,
                              char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st,
-                             const float* aux_grad = nullptr);
+                             const float* aux_grad);
 
 // site A's dX + site B's dY into one token gradient, written once (moe_backward.cpp / dx_stream3.hip); 1 = shapes not served
 int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, const Plan& pb, char* svb, char* scb, void* dX, bool launch, hipStream_t st);

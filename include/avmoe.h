@@ -237,7 +237,12 @@ int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void*
  *             <out, dOut> + <probs, dprobs> + (*lb_grad) * lb + g_z * z + g_balance * balance:
  *             d balance / d p_se = E load_e / S joins the gradient of p before the softmax Jacobian (the selection carries no gradient,
  *             as in the mixture), d z / d l_se = (2 / S) lse_s p_se is added to the gradient of the logits after it.  No launch is
- *             added.  dOut == NULL takes the router-only path as in avmoe_moe_backward_ex.                                          */
+ *             added.  dOut == NULL takes the router-only path as in avmoe_moe_backward_ex.
+ * These two are THE site call: the library has one forward and one backward body (csrc/capi.cpp), and the Python facade
+ * (avmoe_amd.adapters) always calls the _aux entry points, with top_k = 0 for a dense site and NULL for every option that is off.
+ * avmoe_moe_forward, _forward_topk, avmoe_moe_backward, _backward_part and _backward_ex remain for C callers as the same bodies with
+ * fewer arguments -- they differ only in what they refuse (_topk: top_k == 0; _backward, _part: dOut == NULL) and have no behaviour of
+ * their own.                                                                                                                          */
 int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                           const float* noise, int32_t top_k /* 0: dense */, int32_t renorm, void* out, float* probs, int64_t* idx,
                           float* lb, float* aux /* [z, balance] or NULL */, float* load /* (E) or NULL */, void* saved, void* scratch,

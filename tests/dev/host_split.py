@@ -21,7 +21,7 @@ def timed(key, fn):
     return w
 L = capi.lib()
 class LW:      # the library with its two hot entry points timed
-    def __init__(s, L): s._L = L; s.avmoe_moe_forward = timed("C forward", L.avmoe_moe_forward); s.avmoe_moe_backward_part = timed("C backward", L.avmoe_moe_backward_part)
+    def __init__(s, L): s._L = L; s.avmoe_moe_forward_aux = timed("C forward", L.avmoe_moe_forward_aux); s.avmoe_moe_backward_aux = timed("C backward", L.avmoe_moe_backward_aux)
     def __getattr__(s, k): return getattr(s._L, k)
 lw = LW(L)
 capi.lib = lambda: lw
