@@ -120,8 +120,9 @@ def _publish_aux(module, aux, load):
 
 def _ws_sizes(module, L, desc):
     """(saved_bytes, scratch_bytes) of a call shape, kept on the module (two plan evaluations otherwise).  THE key of that cache: anything
-    else that comes to decide a workspace size joins it here, for the forward and the backward alike."""
-    key = (desc.S, desc.N, desc.M, desc.dtype, desc.training, desc.shared_gpu)
+    else that comes to decide a workspace size joins it here, for the forward and the backward alike.  The test hooks do: the frames per
+    chunk of the N x N block size three of the plan's buffers."""
+    key = (desc.S, desc.N, desc.M, desc.dtype, desc.training, desc.shared_gpu, *capi._hooks)
     cache = module.__dict__.setdefault("_ws_sizes", {})
     sizes = cache.get(key)
     if sizes is None:
@@ -264,9 +265,9 @@ class _SiteBackward:
 
     def fused_ok(self, other):
         """Does the library serve `token gradient = this site's dX + the other site's dY` as ONE kernel (avmoe_moe_backward_dx_dy)?
-        (asked once per pair of call shapes: the answer is a function of the two descriptors)"""
+        (asked once per pair of call shapes and test-hook state: the answer is a function of the two plans)"""
         da, db = self.desc, other.desc
-        key = (id(other.module), da.S, da.N, da.M, da.dtype, da.training, db.S, db.N, db.M, db.dtype, db.training)
+        key = (id(other.module), da.S, da.N, da.M, da.dtype, da.training, db.S, db.N, db.M, db.dtype, db.training, *capi._hooks)
         cache = self.module.__dict__.setdefault("_fused_ok", {})
         ok = cache.get(key)
         if ok is None:

@@ -186,7 +186,7 @@ int avmoe_moe_buffer_info(const avmoe_moe_desc* desc, int32_t index, const char*
 
 
 uint32_t avmoe_test_hooks(uint32_t force_mask, int32_t nxn_chunk) {
-  const unsigned prev = test_hook_mask();
+  const unsigned prev = switches().hook_mask.load();
   set_test_hooks(force_mask, nxn_chunk);
   return prev;
 }

@@ -1,6 +1,6 @@
 #include "common.h"
 #include <algorithm>
-#include <atomic>
+#include <cstring>
 
 namespace avmoe {
 
@@ -15,12 +15,10 @@ void set_last_error(const char* fmt, ...) {
 
 const char* last_error() { return g_err; }
 
-// test hooks: two process-wide words, seeded from the environment the first time they are asked for
+// The switch table (common.h).  The environment is read here and nowhere else, when the table is first asked for.
 namespace {
-struct Hooks {
-  std::atomic<unsigned> mask;
-  std::atomic<int> nxn_chunk;
-  Hooks() {
+struct Table : Switches {
+  Table() {
     unsigned m = 0;
     if (getenv("AVMOE_TOKPAIR2_FORCE")) m |= HOOK_TOKPAIR2_FORCE;
     if (getenv("AVMOE_DPAIR_FORCE")) m |= HOOK_DPAIR_FORCE;
@@ -28,15 +26,25 @@ struct Hooks {
     if (getenv("AVMOE_KFS_FORCE")) m |= HOOK_KFS_FORCE;
     if (getenv("AVMOE_KFS_OFF")) m |= HOOK_KFS_OFF;
     const char* c = getenv("AVMOE_NXN_CHUNK");
-    mask.store(m);
+    hook_mask.store(m);
     nxn_chunk.store(c ? std::max(0, atoi(c)) : 0);
+#ifdef AVMOE_DEV
+#define X(name, env) name = getenv(env) != nullptr;
+    AVMOE_DEV_FLAGS(X)
+#undef X
+#define X(type, name, env, dflt, nonempty) if (const char* e = getenv(env); e && (*e || !nonempty)) name = (type)atol(e);
+    AVMOE_DEV_NUMS(X)
+#undef X
+#define X(name, env) if (const char* e = getenv(env)) name = strdup(e);      // (a copy: a later setenv must not move it)
+    AVMOE_DEV_TEXTS(X)
+#undef X
+#endif
   }
 };
-Hooks& hooks() { static Hooks h; return h; }
+Table& table() { static Table t; return t; }
 }  // namespace
-unsigned test_hook_mask() { return hooks().mask.load(std::memory_order_relaxed); }
-int test_hook_nxn_chunk() { return hooks().nxn_chunk.load(std::memory_order_relaxed); }
-void set_test_hooks(unsigned mask, int nxn_chunk) { hooks().mask.store(mask); hooks().nxn_chunk.store(std::max(0, nxn_chunk)); }
+const Switches& switches() { return table(); }
+void set_test_hooks(unsigned mask, int nxn_chunk) { table().hook_mask.store(mask); table().nxn_chunk.store(std::max(0, nxn_chunk)); }
 
 int cu_count() {
   static int cus[64] = {};      // (written once per device with the same value: a race between two host threads is benign)

@@ -236,7 +236,7 @@ int launch_dpost_pair(const GemmArgs& gb, const GemmArgs& ga, size_t slab_cap, h
     return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb1 == 1 && a.nb3 == 1 && a.sCj == 1 &&
            !a.row_scale && !a.D && !a.seg[0].A && !a.seg[1].A && !a.seg[2].A && !a.st_rows && !a.st_cols && !a.xcols.B && !a.xcols.C;
   };
-  if (!plain(gb) || !plain(ga) || gb.A != ga.A || gb.lda != ga.lda || gb.sA2 != ga.sA2 || gb.K != ga.M || gb.M != ga.K || gb.N != ga.N || gb.nb2 != ga.nb2 || G < 1 ||
+  if (switches().no_dpair || !plain(gb) || !plain(ga) || gb.A != ga.A || gb.lda != ga.lda || gb.sA2 != ga.sA2 || gb.K != ga.M || gb.M != ga.K || gb.N != ga.N || gb.nb2 != ga.nb2 || G < 1 ||
       gb.a_layout != MN_MAJOR || gb.b_layout != MN_MAJOR || gb.out_dtype != GEMM_F32 || gb.Cx || ga.a_layout != K_MAJOR || ga.b_layout != MN_MAJOR ||
       ga.out_dtype != GEMM_BF16 || !ga.Cx)
     return 1;
@@ -247,7 +247,7 @@ int launch_dpost_pair(const GemmArgs& gb, const GemmArgs& ga, size_t slab_cap, h
       ((uintptr_t)ga.A % 16) || ((uintptr_t)gb.B % 16) || ((uintptr_t)ga.C % 8) || ((uintptr_t)ga.Cx % 16) || ga.ldcx % 4 || (G * XW) % 4)
     return 1;
   // small sites: the two kernels (the 128-slab reduction alone costs 11 us; measured at 20 480 tokens: 44 us against 37); avmoe_test_hooks bit 2: test hook
-  if (ntok < 32768 && !(ntok >= 4096 && (test_hook_mask() & HOOK_DPAIR_FORCE))) return 1;
+  if (ntok < 32768 && !(ntok >= 4096 && switches().hook(HOOK_DPAIR_FORCE))) return 1;
   const int cus = cu_count();                             // (cached per device: common.cpp)
   if (cus <= 0) { set_last_error("dpost_pair: device query"); return ERR_LAUNCH; }
   const int ntiles = cdiv(ntok, BM);

@@ -190,7 +190,7 @@ static bool dx2_serves(const GemmArgs& a) {
 
 // 0 = launched, 1 = not served (the caller runs the twelve-wave streaming GEMM), < 0 error
 int launch_dx_stream2(const GemmArgs& a, hipStream_t st) {
-  if (!dx2_serves(a)) return 1;
+  if (switches().no_dx2 || !dx2_serves(a)) return 1;
   const int cus = cu_count();                             // (cached per device: common.cpp)
   if (cus <= 0) { set_last_error("dx_stream2: device query"); return ERR_LAUNCH; }
   const GemmSeg& l = a.seg[0];

@@ -334,7 +334,7 @@ int fl_launch(const FLArgs& p, hipStream_t st) {
 
 // 0 = launched, 1 = shape not served (the caller runs the tiled engine), < 0 error
 int launch_gemm_frames(const GemmArgs& a, hipStream_t st) {
-  static const bool off = dev_env("AVMOE_NO_FRAME_GEMM") != nullptr;
+  const bool off = switches().no_frame_gemm;
   const bool tr = a.sCj != 1;                                 // C[s] stored [n][m]
   const long ldc = tr ? a.sCj : a.sCi;
   if (off || a.dtype != GEMM_BF16 || a.epi != GEMM_EPI_NONE || a.nb2 != 1 || a.nb3 > 1 || a.a_layout != K_MAJOR || a.b_layout != K_MAJOR || a.sB1 != 0 ||
@@ -356,7 +356,7 @@ int launch_gemm_frames(const GemmArgs& a, hipStream_t st) {
   p.M = a.M; p.N = a.N; p.K = a.K; p.S = a.nb1; p.alpha = a.alpha; p.nct = p.fpb = 0;
   const double nb = (double)a.nb1;
   const double bytes = nb * a.M * (double)a.K * 2 + (double)a.N * a.K * 2 + nb * a.M * (double)a.N * (p.c_bf16 ? 2.0 : 4.0);
-  static const bool shapes = getenv("AVMOE_PROF_SHAPES") != nullptr;
+  const bool shapes = prof_shapes();
   const char* pname = "gemm_frames";
   if (shapes && prof_enabled()) { char* nm = (char*)malloc(96); snprintf(nm, 96, "gemm_frames M%d N%d K%d b%d%s", a.M, a.N, a.K, a.nb1, tr ? " T" : ""); pname = nm; }
   ProfScope ps(pname, bytes, 2.0 * nb * a.M * (double)a.N * a.K, st);

@@ -144,7 +144,7 @@ int launch_gemm_tokpair(const TokPairArgs& args, hipStream_t stream);
 
 // Streaming kernels tuned for ONE product each of the bf16 cfg-2 site (384 channels per group, 128 bottleneck columns, 768-channel Y).  Like
 // launch_gemm_stream they take the engine's descriptor of the product, check everything they assume of it and return 0 = launched,
-// 1 = not served (nothing was launched: the caller goes on to the next form, launch_gemm last), < 0 error.  launch_gemm does not try them.
+// 1 = not served (nothing was launched: the caller goes on to the next form, launch_gemm last -- forms.h: try_forms), < 0 error.  launch_gemm does not try them.
 int launch_dx_stream2(const GemmArgs& args, hipStream_t stream);     // dX[s] = dZx[s] Wt + dL2x[s] T[s] + rs X[s]: two K segments + row-scale term (dx_stream2.hip)
 // ... with the other site's dY as segments three and four (seg[1], seg[2]), written once (dx_stream3.hip); slabs: >= 256 bytes the kernel may scribble on
 bool dx_stream3_serves(const GemmArgs& args);                        // the same answer from shape and strides alone (no buffers yet)

@@ -18,6 +18,7 @@
 // 16 B per lane along the contiguous index of C.
 #include "gemm.h"
 #include "common.h"
+#include "forms.h"
 #include "prof.h"
 #include "stream_isa.h"
 #include <algorithm>
@@ -996,7 +997,7 @@ static int launch_inst(const DevArgs& d, int batch_z, hipStream_t stream) {
     snprintf(name, sizeof(name), "%s%s_%s_%d", names[AMN][BMN], SEG4 ? "+KM+MM+KM" : (SEG2 ? "+KM" : ""), sizeof(T) == 2 ? "bf16" : (std::is_same<T, f32s3>::value ? "f32s3" : (std::is_same<T, f32s2>::value ? "f32s2" : "f32")), BM);
     if (BN != BM) snprintf(name + strlen(name), sizeof(name) - strlen(name), "x%d", BN);
   }
-  static const bool shapes = getenv("AVMOE_PROF_SHAPES") != nullptr;
+  const bool shapes = prof_shapes();
   const char* pname = name;
   if (shapes && prof_enabled()) {            // debug only: one family per distinct call shape (leaks the small strings)
     char* nm = (char*)malloc(96);
@@ -1033,7 +1034,7 @@ static int launch_big_inst(const DevArgs& d, int batch_z, hipStream_t stream) {
   static const char* const names[2][2] = {{"gemm_KK", "gemm_KM"}, {"gemm_MK", "gemm_MM"}};
   static char name[64];
   if (!name[0]) snprintf(name, sizeof(name), "%s_bf16_256", names[AMN][BMN]);
-  static const bool shapes = getenv("AVMOE_PROF_SHAPES") != nullptr;
+  const bool shapes = prof_shapes();
   const char* pname = name;
   if (shapes && prof_enabled()) {
     char* nm = (char*)malloc(96);
@@ -1132,23 +1133,16 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
       return ERR_BAD_ARG;
     }
   }
-  {
-    static const bool nostream = dev_env("AVMOE_GEMM_NOSTREAM") != nullptr;     // dev switch: A/B against the tiled engine
-    if (!nostream && a.epi == GEMM_EPI_NONE && a.nb3 <= 1 && !s3.A) {
-      const int s = launch_gemm_stream(a, stream);
-      if (s <= 0) return s;
-      const int f = launch_gemm_frames(a, stream);           // a few rows per frame against one shared matrix (frame_gemm.hip)
-      if (f <= 0) return f;
-    }
-  }
+  // the streaming forms first (forms.h): B-stationary token streaming, then a few rows per frame against one shared matrix (frame_gemm.hip)
+  if (!switches().gemm_nostream && a.epi == GEMM_EPI_NONE && a.nb3 <= 1 && !s3.A)
+    if (const int rc = try_forms(a, stream, launch_gemm_stream, launch_gemm_frames); rc <= 0) return rc;
   if (a.Cx) { set_last_error("gemm: a split fp32 side output (Cx) is a feature of the streaming kernel only"); return ERR_UNSUPPORTED; }
   // Batch fold: per-sample row blocks of A (K-major, regularly spaced) against ONE shared B are the rows of a single tall
   // GEMM -- used when the per-sample M would leave a quarter or more of its tile rows empty (65 rows on a 128-row tile, 8
   // latent rows on a 64-row tile).  Rows of the gaps between the samples' blocks are computed and not stored.
   d.fold_rps = d.fold_valid = 0;
   {
-    static const bool nofold = dev_env("AVMOE_GEMM_NOFOLD") != nullptr;      // dev switch
-    if (!nofold && a.epi == GEMM_EPI_NONE && a.nb1 > 1 && a.nb2 == 1 && d.nb3 == 1 && a.a_layout == K_MAJOR && a.sB1 == 0 && d.ksplit == 1 && !s2.A && !a.D && a.lda > 0 &&
+    if (!switches().gemm_nofold && a.epi == GEMM_EPI_NONE && a.nb1 > 1 && a.nb2 == 1 && d.nb3 == 1 && a.a_layout == K_MAJOR && a.sB1 == 0 && d.ksplit == 1 && !s2.A && !a.D && a.lda > 0 &&
         a.sA1 > 0 && a.sA1 % a.lda == 0) {
       const long rps = a.sA1 / a.lda, rows = (long)(a.nb1 - 1) * rps + a.M;
       const int t0 = a.tile ? a.tile : ((a.M > 64 && a.N > 64) ? 128 : 64);      // tile of the unfolded launch (not gemm_auto_tile: no 32 tile, such a sample is weighed against the 64 one)
@@ -1263,8 +1257,7 @@ int gemm_row_lse(const float* row_part, long rows, int tiles, float* lse, hipStr
 }
 
 int launch_gemm_tokpair(const TokPairArgs& a, hipStream_t stream) {
-  static const bool off = dev_env("AVMOE_NO_TOKPAIR") != nullptr;      // dev switch: the two engine GEMMs instead
-  if (off || a.M1 <= 0 || a.M1 > 128 || a.M2 <= 0 || a.M2 > 64 ||          // (the 128-row second accumulator spills: not served)
+  if (switches().no_tokpair || a.M1 <= 0 || a.M1 > 128 || a.M2 <= 0 || a.M2 > 64 ||          // (the 128-row second accumulator spills: not served)
        a.M1 % 8 || a.M2 % 8 || a.Cg % 8 || a.lda1 % 8 || a.lda2 % 8 || a.ldx % 8 ||
       a.sA1g % 8 || ((uintptr_t)a.A1 % 16) || ((uintptr_t)a.A2 % 16) || ((uintptr_t)a.X % 16) || a.N < 64 || !a.slabs)
     return 1;
@@ -1280,10 +1273,8 @@ int launch_gemm_tokpair(const TokPairArgs& a, hipStream_t stream) {
   p.A1 = (const char*)a.A1; p.A2 = (const char*)a.A2; p.X = (const char*)a.X; p.C2 = a.C2; p.slabs = a.slabs;
   p.lda1 = a.lda1; p.lda2 = a.lda2; p.ldx = a.ldx; p.sA1g = a.sA1g;
   p.M1 = a.M1; p.M2 = a.M2; p.S = a.S; p.N = a.N; p.g = a.g; p.Cg = a.Cg; p.tiles_n = tiles_n; p.F = F;
-  {
-    static const int tk = [] { const char* e = dev_env("AVMOE_TOKPAIR_TK"); return e && *e ? atoi(e) : 256; }();      // dev switch (multiple of 64)
-    p.TK = tk > 0 ? (tk + 63) / 64 * 64 : a.N;
-  }
+  const int tk = switches().tokpair_tk;                     // (256; a dev override is rounded up to a multiple of 64, <= 0: the whole frame)
+  p.TK = tk > 0 ? (tk + 63) / 64 * 64 : a.N;
   constexpr int LDS = 2 * 2 * 64 * (128 * 2 + 16);          // two stages of the (128, 128) MN-major / MN-major segment
   const double bytes = ((double)a.S * a.N) * ((double)a.g * a.Cg + (double)a.g * a.M1 + a.M2) * 2.0 + (double)a.S * a.M2 * a.g * a.Cg * 4.0;
   const double flops = 2.0 * (double)a.S * a.N * (double)a.g * a.Cg * ((double)a.M1 + a.M2);

@@ -374,11 +374,12 @@ __global__ void __launch_bounds__(256) kk_hop1_sum(const float* __restrict__ sla
 // Sites of fewer than 32 768 tokens of Y keep the tiled engine: a persistent block per CU then has two or three tiles (or a single frame)
 // to amortise its prologue over and the engine's small tiles fill the chip better (measured at 20 480 tokens: yk 20.7 us against 12 - 15,
 // per-frame yt 32.9 against ~18).  avmoe_test_hooks bit 4 (test hook): small sites as well.
-bool hop1s_small(long ntok) { return ntok < 32768 && !(test_hook_mask() & HOOK_HOP1S_FORCE); }
+bool hop1s_small(long ntok) { return ntok < 32768 && !switches().hook(HOOK_HOP1S_FORCE); }
 
 // a plain product -- alpha 1, overwritten, in one piece, one batch level, bf16 operands, row-major result -- is all three kernels do
+// (development: AVMOE_NO_HOP1S, none of the three serves anything)
 bool hop1_plain(const GemmArgs& a) {
-  return a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb2 == 1 && a.nb3 == 1 && a.sCj == 1 &&
+  return !switches().no_hop1s && a.dtype == GEMM_BF16 && a.alpha == 1.f && !a.accumulate && a.epi == GEMM_EPI_NONE && a.ksplit <= 1 && a.nb2 == 1 && a.nb3 == 1 && a.sCj == 1 &&
          !a.row_scale && !a.D && !a.seg[0].A && !a.seg[1].A && !a.seg[2].A && !a.Cx && !a.st_rows && !a.st_cols && !a.xcols.B && !a.xcols.C;
 }
 

@@ -2,7 +2,8 @@
 // phase 1 the two GEMMs against dOut, phases 2-4 bottleneck / weight space, phase 5 GEMMs against X,
 // phase 6 the hop-1 (latent token) chain back to Y and the remap parameters.  Stream-ordered, no
 // allocation, no host sync.
-#include <cstdlib>
+#include <functional>
+#include "forms.h"
 #include "moe_run.h"
 #include "side.h"
 
@@ -68,11 +69,11 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     return launch_gemm(g, on);
   };
   auto run = [&](GemmArgs& g, bool split) { return run_on(g, split, st); };
+  auto engine = [&](bool split) { return [&run_on, split](GemmArgs& g, hipStream_t on) { return run_on(g, split, on); }; };      // ... as the last form of a chain (forms.h)
   // fp32 sites: products whose result is a parameter gradient or a token gradient (nothing downstream forms a cancelling sum from it) in the
   // TWO-plane form (gemm.hip: f32s2; moe_run.h: AVMOE_LEAF2 has the classes and the measurement).  bf16 sites ignore split3.
-  static const int leaf2 = dev_env("AVMOE_LEAF2") ? atoi(dev_env("AVMOE_LEAF2")) : AVMOE_LEAF2;
-  auto leaf = [&](GemmArgs& g, int cls) { if (leaf2 & cls) g.split3 = 2; };
-  const bool hop1s = d.bf16 && !dev_env("AVMOE_NO_HOP1S");    // the per-frame products against Y as streaming kernels (hop1_stream.hip)
+  const Switches& sw = switches();
+  auto leaf = [&](GemmArgs& g, int cls) { if (sw.leaf2 & cls) g.split3 = 2; };
   // Independent branches run on a helper stream (side.h) and are joined before their first consumer and before the section ends:
   //   section 1: dBpost = dOut^T Apost (+ its split-K reduce; the only user of the slabs until the join) beside dApost -> post_small_bwd -> Gram
   //   section 2: the dX GEMM (nothing in this call reads dX) beside the dWt / dT chain
@@ -81,8 +82,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   const size_t esz = d.esz;
   // development builds: AVMOE_BWD_STOP=n returns after the n-th step of section 1 (1 the two GEMMs against dOut, 2 post_small_bwd, 3 the
   // Gram products, 4 post_prep_bwd, 5 mid_bwd, 6 router_bwd) -- workspaces as that step left them (tests/dev/race_buffers.py)
-  static const int bwd_stop = dev_env("AVMOE_BWD_STOP") ? atoi(dev_env("AVMOE_BWD_STOP")) : 0;
-#define BWD_STOP(n) do { if (bwd_stop == (n)) return OK; } while (0)
+#define BWD_STOP(n) do { if (sw.bwd_stop == (n)) return OK; } while (0)
   if (parts & 1) {   // =============================== section 1: phases 1 - 4 ===============================
   // the accumulators that start from zero (dtbp, dTW, dWcK, dqp, dRT) are adjacent in the plan: one memset instead of five
   MEMSET0(sc + pl.o_dtbp, (pl.o_dRT - pl.o_dtbp) + (size_t)d.S * d.M * d.Kcyp * esz);
@@ -90,8 +90,8 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   // ---- phase 1: dApost = dOut Bpost ; dBpost = dOut^T Apost -------------------------------------
   // (the engine's Gram path splits K itself: it needs the slabs; sites on the generalised kernels keep post_small_bwd off the GPU while
   // a GEMM of the helper stream runs -- tile_gen.inc::gen_lds_request has the reason)
-  const bool fork1 = side && (side_mask() & 2) && (d.gram64 || !d.ln_post) && !d.gen;
-  int dap16 = 0;     // dApost stored as [E x 32 bottleneck columns in T | 3 E scalar columns in fp32 (dApx)]: the register-resident bf16 path
+  const bool fork1 = side && (sw.side_mask & 2) && (d.gram64 || !d.ln_post) && !d.gen;
+  int dap16 = 1;     // dApost stored as [E x 32 bottleneck columns in T | 3 E scalar columns in fp32 (dApx)]: the register-resident bf16 path
   GemmArgs gb = base();                                    // dBpost = dOut^T Apost
   gb.A = dOut; gb.B = sv + pl.o_Apost; gb.C = sc + pl.o_dBp;
   gb.M = d.Cg; gb.N = d.KP; gb.K = d.NT; gb.a_layout = gb.b_layout = MN_MAJOR; gb.lda = d.C; gb.ldb = (long)d.g * d.KPp; gb.nb2 = d.g;
@@ -107,24 +107,16 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   GemmArgs h = ga;
   h.out_dtype = GEMM_BF16; h.Cx = (float*)(sc + pl.o_dApx); h.nsplit = d.E * d.dgp; h.ldcx = (long)d.g * d.XW; h.sCx2 = d.XW;
   h.sCi = (long)d.g * h.nsplit; h.sC2 = h.nsplit;        // the T columns as rows of their own (E * dgp wide: whole 128-byte lines), not inside KPp-wide rows
-  int pair1 = 1;                                           // both products from one pass over dOut (dpost_pair.hip: the tuned bf16 shape); 1 = not served
-  if (d.zsz == 2 && d.bf16 && !dev_env("AVMOE_NO_DPAIR")) {
-    pair1 = launch_dpost_pair(gb, h, slab_cap, st);
-    if (pair1 < 0) return pair1;
-  }
-  if (pair1 == OK) {
-    dap16 = 1;
-  } else {
+  // The forms, in order: both products from one pass over dOut (dpost_pair.hip: the tuned bf16 shape); else dBpost on the engine (forked beside) and
+  // dApost in its split form from the streaming GEMM; else dApost in one fp32 array from the engine (dap16 = 0)
+  const bool split = d.zsz == 2;                           // (sites that keep z in bf16: a property of the plan, which no descriptor carries)
+  auto dap_whole = [&](const GemmArgs&, hipStream_t on) { dap16 = 0; return launch_gemm(ga, on); };
+  auto one_by_one = [&](const GemmArgs&, hipStream_t on) -> int {
     if (fork1) AVMOE_TRY(fk1.fork());
-    AVMOE_TRY(run_on(gb, true, fork1 ? side->s : st));
-    static const bool dap_f32 = dev_env("AVMOE_DAP_F32") != nullptr;      // dev switch
-    if (d.zsz == 2 && !dap_f32) {
-      const int r = launch_gemm_stream(h, st);
-      if (r < 0) return r;
-      dap16 = r == 0;
-    }
-    if (!dap16) AVMOE_TRY(run(ga, false));
-  }
+    AVMOE_TRY(run_on(gb, true, fork1 ? side->s : on));
+    return split && !sw.dap_f32 ? try_forms(h, on, launch_gemm_stream, dap_whole) : dap_whole(ga, on);
+  };
+  AVMOE_TRY(split ? try_forms(gb, st, with(launch_dpost_pair, std::cref(h), slab_cap), one_by_one) : one_by_one(gb, st));
   BWD_STOP(1);
   // ---- phase 2: bottleneck space (LayerNorm-post statistics), then weight space ------------------
   AVMOE_TRY(k_post_small_bwd(pl, sv, sc, prm, grads, st, dap16));
@@ -141,7 +133,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     g.nb2 = d.g * d.E; g.sA2 = g.sB2 = d.dgp; g.sCi = d.dgp; g.sC2 = (long)d.dgp * d.dgp;
     AVMOE_TRY(run(g, true));
   }
-  if (fork1 && pair1 != OK) AVMOE_TRY(fk1.join());
+  if (fk1.open) AVMOE_TRY(fk1.join());                     // (forked only when dpost_pair did not serve)
   BWD_STOP(3);
   AVMOE_TRY(k_post_prep_bwd(pl, sv, sc, prm, grads, st));
   BWD_STOP(4);
@@ -157,7 +149,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   if (parts & (2 | 32 | 64)) {   // =============================== section 2: phase 5 ====================================
   const char* dZx = sc + pl.o_Zw;
   const bool do_dx = (parts & (2 | 64)) != 0, do_rest = (parts & (2 | 32)) != 0;
-  const bool fork2 = side && (side_mask() & 4) && !d.mha && !d.nxn && (parts & 2);             // (those variants go on accumulating into dX below)
+  const bool fork2 = side && (sw.side_mask & 4) && !d.mha && !d.nxn && (parts & 2);             // (those variants go on accumulating into dX below)
 
   // ---- phase 5: GEMMs against X --------------------------------------------------------------------
   if (do_dx) {   // dX[s] = dZx[s] Wt + [dL2 | dsx | 1][s] [T ; 1 ; dm1/N][s] + 2 dSxx X[s]   -- one pass: two K segments + row-scale epilogue
@@ -166,12 +158,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     g.accumulate = d.acc_dx;
     leaf(g, 16);
     if (fork2) AVMOE_TRY(fk2.fork());
-    int dx2 = 1;                                           // the eight-wave direct-load form (dx_stream2.hip: tuned bf16 shape, dX overwritten); 1 = not served
-    if (d.bf16 && !d.acc_dx && !dev_env("AVMOE_NO_DX2")) {
-      dx2 = launch_dx_stream2(g, fork2 ? side->s : st);
-      if (dx2 < 0) return dx2;
-    }
-    if (dx2 != OK) AVMOE_TRY(run_on(g, false, fork2 ? side->s : st));
+    AVMOE_TRY(try_forms(g, fork2 ? side->s : st, launch_dx_stream2, engine(false)));      // (dx_stream2.hip: the eight-wave direct-load form of the tuned bf16 shape)
   }
   if (do_rest) {
   if (d.mha) {   // ---- AVS "v1": per expert back through ZR = xr Wt_e^T, the row sums and xr = MHA_e(X) - X -------------------
@@ -267,18 +254,16 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     g.sCi = d.DZ; g.sC1 = (long)d.KLT * d.DZ; g.sC2 = (long)d.E * d.dgp; g.out_dtype = dt;
     AVMOE_TRY(run(g, false));
   }
-  bool pair_done = false;                                  // dWt = dZx^T X and dT[s] = dL2[s]^T X[s] in ONE pass over X (bf16 sites with latent tokens)
-  if (d.bf16 && d.El > 0) {
+  bool pair_done = d.bf16 && d.El > 0;                     // dWt = dZx^T X and dT[s] = dL2[s]^T X[s] in ONE pass over X (bf16 sites with latent tokens: TokPairArgs has no dtype)
+  if (pair_done) {
     TokPairArgs t;
     t.A1 = dZx; t.lda1 = d.DZ; t.M1 = d.E * d.dgp; t.sA1g = (long)d.E * d.dgp;
     t.A2 = sc + pl.o_dL2x; t.lda2 = d.KLp; t.M2 = d.KL;
     t.X = X; t.ldx = d.C; t.S = d.S; t.N = d.N; t.g = d.g; t.Cg = d.Cg;
     t.C1 = (float*)(sc + pl.o_dWt); t.C2 = (float*)(sc + pl.o_dT); t.slabs = slabs; t.slab_cap = slab_cap;
-    int rc = 1;                                            // as one streaming pass with every accumulator in registers (tok_pair2.hip: the tuned shape) ...
-    if (!dev_env("AVMOE_NO_TOKPAIR2")) rc = launch_tok_pair2(t, st);
-    if (rc == 1) rc = launch_gemm_tokpair(t, st);          // ... or in the tiled form
-    if (rc < 0) return rc;
-    pair_done = rc == OK;
+    // as one streaming pass with every accumulator in registers (tok_pair2.hip: the tuned shape), or in the tiled form, or as the two engine products below
+    auto two_products = [&](const TokPairArgs&, hipStream_t) { pair_done = false; return (int)OK; };
+    AVMOE_TRY(try_forms(t, st, launch_tok_pair2, launch_gemm_tokpair, two_products));
   }
   {                                                        // dWt = dZx^T X  + dTW^T Text
     GemmArgs g = base();
@@ -370,9 +355,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     g.A = sc + pl.o_dV; g.B = Y; g.C = sc + pl.o_dBm;
     g.M = d.Kcyb; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S;
     g.sA1 = (long)d.Kcyb * d.Cy; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Mb; g.sC1 = (long)d.Kcyb * d.Mb;
-    const int rc = hop1s ? launch_hop1_yk(g, st) : 1;      // (hop1_stream.hip: dV[s] stationary per frame; 1 = not served)
-    if (rc < 0) return rc;
-    if (rc != OK) AVMOE_TRY(run(g, false));
+    AVMOE_TRY(try_forms(g, st, launch_hop1_yk, engine(false)));      // (hop1_stream.hip: dV[s] stationary per frame)
   }
   AVMOE_TRY(k_prep_dBm(pl, sc, st));
   }
@@ -414,9 +397,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
       GemmArgs g = base();
       g.A = sc + pl.o_dRT; g.B = Y; g.C = sc + pl.o_dQT; g.out_dtype = dt;      // (straight in the operand dtype of its two consumers)
       g.M = d.Kcy; g.N = d.Cy; g.K = d.S * d.M; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Kcyp; g.ldb = d.Cy; g.sCi = d.Cy;
-      const int rc = hop1s ? launch_hop1_yt_sum(g, slab_cap, st) : 1;      // (hop1_stream.hip: one pass over Y with every accumulator in registers + a slab sum)
-      if (rc < 0) return rc;
-      if (rc != OK) AVMOE_TRY(run(g, true));
+      AVMOE_TRY(try_forms(g, st, with(launch_hop1_yt_sum, slab_cap), engine(true)));      // (hop1_stream.hip: one pass over Y with every accumulator in registers + a slab sum)
     }
   }
   if (do6b) {   // dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q   -- one pass over dY (two K segments; no cross-modal expert: wbar (x) d ybar[s] alone)

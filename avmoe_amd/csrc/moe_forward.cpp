@@ -1,7 +1,7 @@
 // Forward orchestration of one MoEAdapter site: a fixed sequence of engine GEMMs and bottleneck-space
 // kernels on the caller's stream (no allocation, no host sync: capturable in a hipGraph).
 // Stage names follow oracle/algebra_ref.py::AlgebraRef.forward.
-#include <cstdlib>
+#include "forms.h"
 #include "moe_run.h"
 #include "side.h"
 
@@ -12,8 +12,7 @@ int choose_ksplit(const GemmArgs& g, size_t slab_floats_cap) {
   const long nb = (long)g.nb1 * g.nb2 * (g.nb3 > 0 ? g.nb3 : 1);          // (every batch level has its own slabs: gemm_slab_bytes)
   const long tiles = (long)cdiv(g.M, tile) * cdiv(g.N, tile) * nb;
   const int bk = g.dtype == GEMM_BF16 ? 64 : 32;
-  static const long target = dev_env("AVMOE_KS_TARGET") ? atol(dev_env("AVMOE_KS_TARGET")) : 512;     // workgroups wanted (dev override)
-  long ks = std::max<long>(1, target / std::max<long>(tiles, 1));
+  long ks = std::max<long>(1, switches().ks_target / std::max<long>(tiles, 1));      // (512 workgroups wanted)
   ks = std::min<long>(ks, std::max<long>(1, g.K / (4 * bk)));
   ks = std::min<long>(ks, 64);
   const size_t per = (size_t)nb * g.M * g.N;
@@ -43,7 +42,6 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   float* slabs = (float*)(sc + pl.o_slabs);
   const size_t slab_cap = slab_floats(d);
   auto base = [&]() { GemmArgs g; g.dtype = dt; g.out_dtype = GEMM_F32; g.slabs = slabs; g.split3 = AVMOE_FWD_SPLIT3; return g; };      // (split3: fp32 sites only, gemm.h)
-  const bool hop1s = d.bf16 && !dev_env("AVMOE_NO_HOP1S");    // the per-frame products against Y as streaming kernels (hop1_stream.hip)
 
   // ---- weights-derived operands --------------------------------------------------------------
   AVMOE_TRY(k_prep_all(pl, sv, prm, st));                  // (also scal[1] = 1: the unit gate of with_unit_gates)
@@ -62,7 +60,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
       auto& x = g.xcols; x.B = sv + pl.o_Text; x.N = d.KL; x.ldb = d.C; x.sB1 = (long)d.KLT * d.C; x.sB2 = d.Cg;
       x.C = (float*)(sc + pl.o_L2g); x.ldc = d.KL; x.sC1 = (long)d.N * d.KL; x.sC2 = (long)d.NT * d.KL;
     }
-    const int rc = launch_gemm_stream(g, xs);
+    const int rc = launch_gemm_stream(g, xs);              // (the one form that leaves the statistics: no chain, no engine behind it)
     if (rc != OK) {
       if (rc == 1) set_last_error("moe_forward: the streaming down projection with statistics does not serve this shape (plan / kernel mismatch)");
       return rc == 1 ? ERR_UNSUPPORTED : rc;
@@ -75,7 +73,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
                         1.f / (float)d.N, xs);
   };
   // (with the logits fused in, the pass needs the latent tokens T: it runs behind the hop-1 chain, on the caller's stream)
-  Side* side = (d.fuse_xs && !d.fuse_l2 && (side_mask() & 1) && side_worth(d)) ? side_acquire(st) : nullptr;
+  Side* side = (d.fuse_xs && !d.fuse_l2 && (switches().side_mask & 1) && side_worth(d)) ? side_acquire(st) : nullptr;
   SideScope fk(side, st);
   if (side) {
     AVMOE_TRY(fk.fork());
@@ -97,9 +95,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
       g.A = sv + pl.o_Qx; g.B = Y; g.C = sv + pl.o_Rext;
       g.M = d.Kcy; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S; g.sB1 = (long)d.M * d.Cy;
       g.sCi = d.Mk; g.sC1 = (long)d.Kcyb * d.Mk; g.out_dtype = dt;
-      const int rc = hop1s ? launch_hop1_yk(g, st) : 1;    // (hop1_stream.hip: Q stationary, Y streamed in whole token rows; 1 = not served)
-      if (rc < 0) return rc;
-      if (rc != OK) AVMOE_TRY(launch_gemm(g, st));
+      AVMOE_TRY(try_forms(g, st, launch_hop1_yk, launch_gemm));      // (hop1_stream.hip: Q stationary, Y streamed in whole token rows)
     }
     {                                                      // L1[s] = [R | qr | qb] [Wc | bc | 1]^T
       GemmArgs g = base();
@@ -123,9 +119,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     g.A = sv + pl.o_BmX; g.B = Y; g.C = sv + pl.o_V;
     g.M = d.Kcyb; g.N = d.Cy; g.K = d.M; g.lda = d.Mb; g.b_layout = MN_MAJOR; g.ldb = d.Cy; g.nb1 = d.S;
     g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.Kcyb * d.Cy; g.out_dtype = dt;
-    const int rc = hop1s ? launch_hop1_yt_frames(g, st) : 1;      // (hop1_stream.hip; 1 = not served)
-    if (rc < 0) return rc;
-    if (rc != OK) AVMOE_TRY(launch_gemm(g, st));
+    AVMOE_TRY(try_forms(g, st, launch_hop1_yt_frames, launch_gemm));      // (hop1_stream.hip)
   }
   {                                                        // TV = V Wf^T
     GemmArgs g = base();

@@ -32,10 +32,11 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
   if (!q || !pl) { set_last_error("moe: null descriptor"); return ERR_BAD_ARG; }
   std::memset(pl, 0, sizeof(Plan));
   Dims& d = pl->d;
+  const Switches& sw = switches();
   d.S = q->S; d.N = q->N; d.C = q->C; d.M = q->M; d.Cy = q->Cy;
   d.E_m = q->E_m; d.E_s = q->E_s; d.E = q->E_m + q->E_s;
   d.g = q->groups; d.d = q->d; d.K = q->K;
-  d.use_bn = q->use_bn; d.use_gate = q->use_gate; d.gate_w = q->use_gate && !dev_env("AVMOE_GATE_TOKEN"); d.ln_before = q->ln_before; d.ln_post = q->ln_post;
+  d.use_bn = q->use_bn; d.use_gate = q->use_gate; d.gate_w = q->use_gate && !sw.gate_token; d.ln_before = q->ln_before; d.ln_post = q->ln_post;
   d.variant = q->variant; d.self_attn = q->self_attn; d.lb_loss = q->lb_loss; d.training = q->training;
   d.bf16 = q->dtype == AVMOE_BF16;
   d.bn_eps = q->bn_eps; d.ln_eps = q->ln_eps; d.bn_momentum = q->bn_momentum;
@@ -93,7 +94,7 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
   d.Ex = d.El - d.Ey;
   if (d.El == 0) d.K = d.K > 0 ? d.K : 1;
   // ---- bottleneck layout ------------------------------------------------------------------------------------------------
-  static const bool no_gen = dev_env("AVMOE_NO_GEN") != nullptr;          // development: without the generalised register-resident kernels
+  const bool no_gen = sw.no_gen;          // development: without the generalised register-resident kernels
   const int g_site = d.g;
   // Merged groups.  A grouped 1x1 convolution is a dense one with a block-diagonal weight.  When the per-group bottleneck is tiny
   // (AVQA: 4 groups, bottleneck 12 -> 3 per group) padding every GROUP to the 16-entry granule of the register-resident kernels
@@ -105,7 +106,7 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
   {
     const int merged = (int)round_up(d.d, 16), dg0 = d.d / g_site, grouped = g_site * (int)round_up(dg0, 16), ncg = merged / 16;
     const bool fast_shape = g_site == 2 && dg0 > 16 && dg0 <= 32 && d.K == 32 && d.E >= 2 && d.E <= 4;
-    try_merge = !no_gen && !dev_env("AVMOE_NO_MERGE") && g_site > 1 && d.C <= 384 && merged < grouped && (ncg <= 4 || ncg == 6) && !fast_shape;
+    try_merge = !no_gen && !sw.no_merge && g_site > 1 && d.C <= 384 && merged < grouped && (ncg <= 4 || ncg == 6) && !fast_shape;
   }
   for (int attempt = try_merge ? 0 : 1; attempt < 2; ++attempt) {
     const bool merge = attempt == 0;
@@ -117,7 +118,7 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
     // that run 1.3-3x faster than the generic ones (HTS-AT / Swin-B sites at r = 8: bottleneck 48: -29 %, 32: -15 %, 24: -19 %,
     // 12 / 16: -4 % of the site step).  Padding columns are zero weights, as for every other padded width.
     // (Per-group bottlenecks up to 16 stay at 16 entries and run on the generalised kernels of tile_gen.hip instead -- half the Z-space bytes.)
-    if (d.g == 2 && d.dg < 32 && (d.dg > 16 || no_gen) && d.K == 32 && d.E >= 2 && d.E <= 4 && !dev_env("AVMOE_NO_PAD32")) d.dgp = 32;
+    if (d.g == 2 && d.dg < 32 && (d.dg > 16 || no_gen) && d.K == 32 && d.E >= 2 && d.E <= 4 && !sw.no_pad32) d.dgp = 32;
     d.Cg = d.C / d.g;
     d.DD = d.g * d.dgp;
     d.DZ = d.E * d.DD;
@@ -125,7 +126,7 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
     // Generalised register-resident kernels (tile_gen.hip) for every other shape they are built for: bottleneck entries per group
     // padded to a multiple of 16, latent-token slots to 16 / 32 / 96 (zero weights / masked slots, as for every padded width).
     d.gen = 0;
-    static const bool no_fast = dev_env("AVMOE_NO_FAST") != nullptr;      // development: the generalised kernels at the tuned shape too (A/B)
+    const bool no_fast = sw.no_fast;      // development: the generalised kernels at the tuned shape too (A/B)
     if (!no_gen && (no_fast || !(d.g == 2 && d.dgp == 32 && d.K == 32 && d.E >= 2 && d.E <= 4))) {
       Dims t = d;
       t.dgp = (int)round_up(d.dg, 16);
@@ -153,16 +154,16 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
   // workspace -- one 4096-token frame per chunk, split-K in every product -- ran 27 % slower at cfg-3): no (S, N, N) tensor in
   // HBM -- at AVVP stage 0 (N = 4096, 640 frames) that would be 21 GB (bf16) + 43 GB (fp32 scores) per site.
   d.nxc = d.S;
-  d.nflash = d.nxn && !d.mha && nxn_att_ok(d.bf16, d.N, d.C, (int)round_up(d.N, 8)) && !dev_env("AVMOE_NXN_OLD_BWD");
+  d.nflash = d.nxn && !d.mha && nxn_att_ok(d.bf16, d.N, d.C, (int)round_up(d.N, 8)) && !sw.nxn_old_bwd;
   if (d.nflash) {
-    if (const int ch = test_hook_nxn_chunk()) d.nxc = std::max(1, std::min(d.S, ch));     // tests (avmoe_test_hooks): the frame loop of the strip kernels
+    if (const int ch = sw.nxn_chunk.load(std::memory_order_relaxed)) d.nxc = std::max(1, std::min(d.S, ch));     // tests (avmoe_test_hooks): the frame loop of the strip kernels
   } else if (d.nxn && !d.mha) {
     const size_t per_frame = (size_t)d.N * round_up(d.N, 8) * (2 * (size_t)d.esz);      // att + dSc (the scores / d att themselves never leave the chip)
     const size_t keep_all = (size_t)256 << 20;
     size_t budget = (size_t)2048 << 20;          // chunk workspace (scratch, reused by every site)
-    if (const char* ev = dev_env("AVMOE_NXN_BUDGET_MB")) budget = (size_t)std::max(1, atoi(ev)) << 20;      // dev: sweep
+    if (const char* ev = sw.nxn_budget_mb) budget = (size_t)std::max(1, atoi(ev)) << 20;      // dev: sweep
     if ((size_t)d.S * per_frame > keep_all) d.nxc = (int)std::max<size_t>(1, std::min<size_t>((size_t)d.S, budget / per_frame));
-    if (const int ch = test_hook_nxn_chunk()) d.nxc = std::max(1, std::min(d.S, ch));     // tests (avmoe_test_hooks): force the chunked path on small shapes
+    if (const int ch = sw.nxn_chunk.load(std::memory_order_relaxed)) d.nxc = std::max(1, std::min(d.S, ch));     // tests (avmoe_test_hooks): force the chunked path on small shapes
   }
   d.Mk = (int)round_up(d.M + 2, 8);
   d.Mb = (int)round_up(d.M + 1, 8);
@@ -170,19 +171,19 @@ int make_plan(const avmoe_moe_desc* q, Plan* pl) {
   // per-token kernels: blocks per sample so that the grid has a few waves per SIMD
   // (A/B at cfg-2 with the wave-per-expert kernels: 256 tokens per block at N = 1024, two blocks for the 196 tokens of the visual side)
   int bps = std::max(1, std::min(cdiv(d.N, 64), std::max(cdiv(d.N, d.N >= 512 ? 256 : 112), cdiv(256, d.S))));
-  if (const char* ev = dev_env("AVMOE_BPS")) {     // development: "<bps for N >= 512>,<bps for N < 512>"
+  if (const char* ev = sw.bps) {     // development: "<bps for N >= 512>,<bps for N < 512>"
     int a = 0, b = 0;
     if (sscanf(ev, "%d,%d", &a, &b) == 2) bps = std::max(1, d.N >= 512 ? a : b);
   }
   d.nblk_tok = bps * d.S;
   d.zsz = (tile_fast_ok(d) || d.gen) ? d.esz : 4;     // Z / dz' in the activation type on the register-resident paths
-  d.gram64 = tile_fast_shape(d) && d.bf16 && (d.E == 4 || d.E == 2) && !dev_env("AVMOE_NO_GRAM64");      // gram.hip is built for 2 and 4 experts
+  d.gram64 = tile_fast_shape(d) && d.bf16 && (d.E == 4 || d.E == 2) && !sw.no_gram64;      // gram.hip is built for 2 and 4 experts
   d.xchunks = std::max(1, std::min(cdiv(d.N, 32), cdiv(4096, d.S)));
-  d.fuse_xs = d.bf16 && d.zsz == 2 && gemm_stream_stats_ok(d.N, d.S, d.E * d.dgp, d.Cg, d.C, d.DZ) && !dev_env("AVMOE_NO_FUSE_XSTATS");
+  d.fuse_xs = d.bf16 && d.zsz == 2 && gemm_stream_stats_ok(d.N, d.S, d.E * d.dgp, d.Cg, d.C, d.DZ) && !sw.no_fuse_xstats;
   // the hop-2 logits out of the same pass over X: the tuned shape (tile_fast.hip's pre_small adds the per-group partial sums), no latent
   // self attention (its latent tokens come from X itself), <= 64 latent rows per frame, the k384_n128 streaming configuration
   d.fuse_l2 = d.fuse_xs && tile_fast_ok(d) && !d.gen && d.El > 0 && d.Ex == 0 && d.KL <= 64 && d.KL % 16 == 0 && d.S >= 2 && d.E * d.dgp == 128 && d.Cg <= 384 &&
-              d.Cg > 160 && !dev_env("AVMOE_NO_FUSE_L2");
+              d.Cg > 160 && !sw.no_fuse_l2;
 
   size_t off[2] = {0, 0};
   int n = 0;

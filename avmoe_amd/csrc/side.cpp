@@ -17,11 +17,6 @@ bool side_disabled() {
 }
 }  // namespace
 
-int side_mask() {
-  static const int m = [] { const char* e = dev_env("AVMOE_SIDE_MASK"); return e && *e ? atoi(e) : 7; }();
-  return m;
-}
-
 Side* side_acquire(hipStream_t st) {
   if (side_disabled() || prof_enabled()) return nullptr;      // (per-launch timing brackets launches on the caller's stream: a forked branch would be timed with its queueing)
   int dev = 0;

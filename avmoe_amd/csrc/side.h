@@ -10,7 +10,6 @@ namespace avmoe {
 struct Side { hipStream_t s; hipEvent_t fork_ev, join_ev; };
 
 Side* side_acquire(hipStream_t st);        // nullptr: disabled or not available -- the caller then stays on its own stream
-int side_mask();                           // dev: AVMOE_SIDE_MASK selects the forks (1 forward, 2 backward section 1, 4 backward section 2; default all)
 int side_fork(Side* sd, hipStream_t st);   // status codes of common.h
 int side_join(Side* sd, hipStream_t st);
 

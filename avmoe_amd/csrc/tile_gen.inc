@@ -1012,7 +1012,7 @@ void pick_round(int E, size_t pe, size_t pw, int max_waves, int per, int* R, int
     const int ns = std::max(1, 4 / c);
     if (c == 1 || (pe * c + pw * c * ns) * 4 <= (size_t)13 * 1024 * c * ns) { r = c; break; }
   }
-  if (const char* ev = dev_env("AVMOE_GEN_R")) r = std::max(1, std::min(top, atoi(ev)));      // development: A/B of the round size
+  if (const char* ev = switches().gen_r) r = std::max(1, std::min(top, atoi(ev)));      // development: A/B of the round size
   // excl (one block per CU, gen_lds_request): as many waves as the instance is compiled for, so that the CU is not left at four waves
   const int waves = (excl && per >= 128) ? max_waves : 4;
   *R = r; *NS = std::max(1, waves / r);
@@ -1028,7 +1028,7 @@ void pick_round(int E, size_t pe, size_t pw, int max_waves, int per, int* R, int
 // (development: AVMOE_GEN_HOG=<bytes> forces a request for every launch)
 constexpr size_t GEN_EXCL_LDS = 150 * 1024;
 static inline size_t gen_lds_request(size_t need, int excl) {
-  static const long hog = dev_env("AVMOE_GEN_HOG") ? atol(dev_env("AVMOE_GEN_HOG")) : -1;
+  const long hog = switches().gen_hog;
   if (hog >= 0) return std::max(need, (size_t)hog);
   return excl ? std::max(need, GEN_EXCL_LDS) : need;
 }

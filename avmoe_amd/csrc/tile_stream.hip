@@ -1390,8 +1390,8 @@ FastDims make_fd_s(const Dims& d, int per) {
 // fast or faster in this form too: mid_bwd 28.6 -> 25.0 us, post_small 19.8 -> 17.0, pre_small_bwd + pre_lat_bwd 19.7 + 19.7 -> 33.8,
 // post_small_bwd + Gram 33.6 + 16.0 -> 39.1; 1.615 -> 1.567 ms of kernel time per pair-step and four launches less.)
 bool tile_stream_ok(const Dims& d) {
-  const unsigned hooks = test_hook_mask();            // (include/avmoe.h: avmoe_test_hooks -- small test shapes through these kernels / the A/B against tile_fast.hip)
-  return tile_fast_ok(d) && d.bf16 && d.zsz == 2 && (d.NT >= 2048 || (hooks & HOOK_KFS_FORCE)) && !(hooks & HOOK_KFS_OFF);
+  const Switches& sw = switches();                    // (include/avmoe.h: avmoe_test_hooks -- small test shapes through these kernels / the A/B against tile_fast.hip)
+  return tile_fast_ok(d) && d.bf16 && d.zsz == 2 && (d.NT >= 2048 || sw.hook(HOOK_KFS_FORCE)) && !sw.hook(HOOK_KFS_OFF);
 }
 
 static bool psf_geom(const Dims& d, int* gx, int* nfr, int* per) {

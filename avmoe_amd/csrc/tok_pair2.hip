@@ -279,10 +279,10 @@ int launch_tok_pair2(const TokPairArgs& a, hipStream_t st) {
   float* const slabs = a.slabs; float* const dWt = a.C1; float* const dT = a.C2;
   const size_t slab_cap = a.slab_cap;
   // the tuned shape: 384 channels and 128 rows of A1 per group, the groups' rows side by side, <= 64 rows of A2 in rows of >= 72
-  if (a.Cg != 384 || a.M1 != 128 || a.sA1g != 128 || KL < 1 || KL > 64 || ldl < 72 || N < 16 || S < 1 || G < 1 || a.ldx % 8 || a.lda1 % 8 || ldl % 8 || !slabs ||
+  if (switches().no_tokpair2 || a.Cg != 384 || a.M1 != 128 || a.sA1g != 128 || KL < 1 || KL > 64 || ldl < 72 || N < 16 || S < 1 || G < 1 || a.ldx % 8 || a.lda1 % 8 || ldl % 8 || !slabs ||
       ((uintptr_t)a.X % 16) || ((uintptr_t)a.A1 % 16) || ((uintptr_t)a.A2 % 16) || ((uintptr_t)dWt % 16) || ((uintptr_t)dT % 16) || (G * 384) % 4)
     return 1;
-  const bool force = (test_hook_mask() & HOOK_TOKPAIR2_FORCE) != 0;          // test hook (avmoe_test_hooks: tests / bench.py's parity leg switch it inside one process): small sites as well
+  const bool force = switches().hook(HOOK_TOKPAIR2_FORCE);          // test hook (avmoe_test_hooks: tests / bench.py's parity leg switch it inside one process): small sites as well
   if (!force && (long)S * N < 32768) return 1;                              // small sites: the tiled form fills the chip better
   const int cus = cu_count();                             // (cached per device: common.cpp)
   if (cus <= 0) { set_last_error("tok_pair2: device query"); return ERR_LAUNCH; }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# development: the whole library built with -DAVMOE_DEV (csrc/common.h: dev_env -- the A/B switches of scripts/README.md compiled in)
+# development: the whole library built with -DAVMOE_DEV (csrc/common.h: the switch table -- the A/B switches of scripts/README.md compiled in)
 #   scripts/dev_lib.sh [extra hipcc flags]  ->  avmoe_amd/lib/variants/libdev.so   (use with AVMOE_LIB=$PWD/avmoe_amd/lib/variants/libdev.so)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd); O=$R/avmoe_amd/lib/variants/dev

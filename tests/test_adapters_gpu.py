@@ -479,3 +479,22 @@ def test_flat_adam_two_lr_groups_and_plain_buckets():
     moved = {k: float((p.detach() - start[k]).abs().max()) for k, p in fused.named_parameters()}
     assert max(v for k, v in moved.items() if "mlp_class" in k) <= 3.5 * lr_mlp          # |Adam update| <= ~lr per step
     assert max(v for k, v in moved.items() if "mlp_class" not in k) > 10 * lr_mlp
+
+
+def test_workspace_size_cache_follows_the_test_hooks():
+    """The facade's cache of (saved, scratch) bytes per call shape (adapters._ws_sizes) under a test hook that changes the plan: the frames per
+    chunk of the AVVP N x N block size three of its buffers.  One module, one shape, chunk 1 and then the library's own choice: each answer
+    equals what the library says under the same hooks.  Sizes only: nothing is launched."""
+    import ctypes as C
+    from avmoe_amd import _capi, adapters
+    meta, cfg, t = load_golden("avvp_train")
+    m = build_module(meta["which"], cfg)
+    L = _capi.lib()
+    desc = m._desc(t["X"].shape[0], t["X"].shape[1], t["Y"].shape[1], False)
+    want = {}
+    for chunk in (1, 0):
+        with _capi.test_hooks(0, chunk):
+            want[chunk] = (L.avmoe_moe_saved_bytes(C.byref(desc)), L.avmoe_moe_scratch_bytes(C.byref(desc)))
+            assert want[chunk][0] > 0, L.avmoe_last_error().decode()
+            assert adapters._ws_sizes(m, L, desc) == want[chunk], chunk
+    assert want[1] != want[0]          # (the hook does change this site's plan: otherwise nothing was checked)

@@ -140,3 +140,44 @@ def test_token_gradient_written_once_equals_the_two_kernel_handover(shape, monke
             assert float((one[k] - ref).norm() / ref.norm()) <= 4e-3, k
         else:
             assert torch.equal(one[k], two[k]), k
+
+
+def test_form_chain_follows_the_hooks_inside_one_process():
+    """One site, one set of workspaces, forward + backward twice: with every size threshold lifted (the streaming forms of the hop-1
+    products and of the token contractions serve it), then with the hooks at 0 (every chain ends in the engine).  The forms a product goes
+    through are chosen per call; the two runs agree within the bounds of test_hop1_streaming_kernels_equal_the_engine above."""
+    from avmoe_amd import _capi
+    from tests.moe_gpu_util import MoeRun
+    S, N, M = TP2_SHAPES["ragged_196"]                     # the smallest site of this file that the streaming forms serve
+    cfg = _cfg(N, M, 2, 2)
+    P, B = O.init_params(cfg, seed=7)
+    g = torch.Generator().manual_seed(107)
+    X, Y, G = (0.3 * torch.randn(S, cfg.Nx, cfg.Cx, generator=g), 0.3 * torch.randn(S, cfg.Ny, cfg.Cy, generator=g),
+               torch.randn(S, cfg.Nx, cfg.Cx, generator=g))
+    run = MoeRun(cfg, P, B, X, Y, bf16=True, training=True)
+    L = _capi.lib()
+
+    def step(mask):
+        L.avmoe_prof_reset(); L.avmoe_prof_enable(1)
+        try:
+            with _capi.test_hooks(mask):
+                got = run.forward().backward(G)
+            ran = {f["name"] for f in _capi.prof_report()}
+        finally:
+            L.avmoe_prof_enable(0); L.avmoe_prof_reset()
+        assert run.guards_intact(), "a kernel wrote past its workspace"
+        return run.out.float().cpu(), run.idx.cpu(), {k: v.float().cpu() for k, v in got.items()}, ran
+
+    streamed = {"k_hop1_yk", "k_hop1_yt_frames", "k_hop1_yt_sum", "k_tok_pair2"}
+    out_s, idx_s, g_s, ran_s = step(_capi.HOOK_ALL_FORCE)
+    out_e, idx_e, g_e, ran_e = step(0)
+    assert streamed <= ran_s, sorted(ran_s)
+    assert not (streamed & ran_e), sorted(ran_e)
+    assert torch.equal(idx_e, idx_s)
+    assert all(torch.isfinite(v).all() for v in g_s.values()) and torch.isfinite(out_s).all()
+    assert float((out_s - out_e).abs().max()) <= 8e-3 * float(out_e.abs().max())
+    assert float((out_s - out_e).norm() / out_e.norm()) <= 3e-3
+    gmax = max(float(v.norm()) for v in g_e.values())
+    for k, v in g_e.items():
+        err = float((g_s[k] - v).norm()) / max(float(v.norm()), 1e-3 * gmax)
+        assert err <= (1e-2 if float(v.norm()) >= 1e-2 * gmax else 6e-2), (k, err)
