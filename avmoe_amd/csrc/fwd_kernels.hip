@@ -2,7 +2,7 @@
 // oracle/algebra_ref.py::AlgebraRef.forward; reference lines are cited there and in DESIGN.md.
 //
 // Buffers of the operand type T (float | __bf16) are passed as void* and cast inside the kernel.
-#include "kernels.h"
+#include "pass.h"
 #include "colsum_fin.h"
 #include "moe_run.h"
 #include "device_utils.h"
@@ -1089,21 +1089,25 @@ avmoe_moe_ptrs merged_params(const Plan& pl, const avmoe_moe_ptrs& prm, char* sa
   return p;
 }
 
-int k_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
-  ProfScope ps_("k_mid", (long)d.NT, (double)d.NT * d.DZ * (double)(d.zsz + d.esz), 0.0, st);
+static int kk_mid_form(PassCall& c, hipStream_t st) {      // any shape: ends the chain
+  const Plan& pl = c.pl; const Dims& d = pl.d;
   MidArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
+  put(a.relu_of_e, c.x.relu_of_e);
   a.E = d.E; a.dgp = d.dgp; a.DZ = d.DZ; a.NT = d.NT;
-  const int nblk = d.nblk_tok;
-  const int rpb = cdiv(d.NT, nblk);
-  if (tile_fast_ok(d)) AVMOE_TRY(kf_mid(pl, saved, scratch, st));
-  else if (d.gen) AVMOE_TRY(kg_mid(pl, saved, scratch, st));
-  else DISPATCH_T(d.bf16, kk_mid, dim3(nblk), dim3(256), 0, st, a, (const float*)(saved + pl.o_Z), (const float*)(saved + pl.o_bn1),
-                  (void*)(scratch + pl.o_Zp), (float*)(scratch + pl.o_colpart), rpb);
-  AVMOE_TRY(k_reduce_colpart(pl, scratch, 0, 1, st));
-  hipLaunchKernelGGL(kk_colsum_finalize, dim3(cdiv(d.DZ, 256)), dim3(256), 0, st, (const float*)(scratch + pl.o_colsum),
-                     d.DZ, 0, 1.f / (float)d.NT, (float*)(saved + pl.o_mz));
+  DISPATCH_T(d.bf16, kk_mid, dim3(d.nblk_tok), dim3(256), 0, st, a, (const float*)(c.saved + pl.o_Z), (const float*)(c.saved + pl.o_bn1),
+             (void*)(c.scratch + pl.o_Zp), (float*)(c.scratch + pl.o_colpart), cdiv(d.NT, d.nblk_tok));
+  c.ran = PASS_TILE;
+  return OK;
+}
+
+int k_mid(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_mid", (long)d.NT, bytes_mid(d), 0.0, st);
+  AVMOE_TRY(try_forms(c, st, kf_mid, kg_mid, kk_mid_form));
+  AVMOE_TRY(k_reduce_colpart(pl, c.scratch, 0, 1, st));
+  hipLaunchKernelGGL(kk_colsum_finalize, dim3(cdiv(d.DZ, 256)), dim3(256), 0, st, (const float*)(c.scratch + pl.o_colsum),
+                     d.DZ, 0, 1.f / (float)d.NT, (float*)(c.saved + pl.o_mz));
   AVMOE_CHECK_LAUNCH("mid");
   return OK;
 }

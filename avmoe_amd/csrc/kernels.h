@@ -42,21 +42,19 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm,            // top_k 0: the dense mixture
              float* aux_out, float* load_out);                                                   // aux_out: [z, balance] (avmoe_moe_forward_aux)
 // ---- forward: per token -----------------------------------------------------------------------
-int k_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
+struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
+int k_pre_small(PassCall& c, hipStream_t st);
 int k_bn1_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int k_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st);
+int k_mid(PassCall& c, hipStream_t st);
 int k_post_prep(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int k_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
+int k_post_small(PassCall& c, hipStream_t st);
 
 // ---- backward ---------------------------------------------------------------------------------
-int k_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
-                     const avmoe_moe_ptrs& grads, hipStream_t st, int dap16);       // dap16: dApost = [T columns | fp32 dApx]
+int k_post_small_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st);       // (each backward pass + its finalize)
 int k_post_prep_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
                     const avmoe_moe_ptrs& grads, hipStream_t st);
-int k_mid_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-              hipStream_t st);
-int k_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
-                    const avmoe_moe_ptrs& grads, hipStream_t st);
+int k_mid_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st);
+int k_pre_small_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st);
 int k_post_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
                               const avmoe_moe_ptrs& grads, hipStream_t st);
 int k_mid_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
@@ -85,37 +83,10 @@ int k_nxn_y(const void* X, const void* dxr, int frames, int N, int C, int Np, co
 int k_nxn_xr(const void* X, int frames, int N, int C, int Np, const float* lse, void* xr, hipStream_t st);      // forward: xr = att^T X (lse from k_nxn_att with att == nullptr)
 int k_nxn_dx(int key, const void* X, const void* dxr, int frames, int N, int C, int Np, const float* lse, const float* rowdot, void* dX, hipStream_t st);   // dX += dS X (key = 0) / dS^T X (key = 1), dS in the accumulators
 int k_nxn_rowdot(int bf16, const void* X, const float* y, long rows, int C, void* dX, float* rowdot, hipStream_t st);   // dX += y ; rowdot = sum_c X y
-// register-resident variants for bottleneck 64 / 2 groups / 32 latent tokens / 4 experts (tile_fast.hip)
+// the shapes the register-resident kernel families serve (tile_fast.hip, tile_gen.inc); their forms are declared in pass.h
 bool tile_fast_ok(const Dims& d);
 bool tile_fast_shape(const Dims& d);      // the shape alone (the Gram-fused mode of gram.hip serves it on either kernel family)
-int kf_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kf_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kf_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16);
-int kf_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st);
-int kf_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
-int kf_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kf_pre_lat_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-// the same kernels in streaming form (tile_stream.hip: one persistent block per CU, wave-private LDS rings filled by direct loads);
-// 0 = launched, 1 = not served (run the kf_* kernel), < 0 error
-bool tile_stream_ok(const Dims& d);
-bool kfs_serves_post_small_bwd(const Dims& d, int dap16);
-int kfs_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16);
-bool kfs_serves_pre_small(const Dims& d);
-int kfs_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-bool kfs_serves_post_small(const Dims& d);
-int kfs_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-bool kfs_serves_pre_bwd(const Dims& d);      // pre_small_bwd + pre_lat_bwd in one pass
-int kfs_pre_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-bool kfs_serves_mid_bwd(const Dims& d);
-int kfs_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
-// register-resident kernels generalised over groups (1 / 2 / 4), per-group bottleneck (16 .. 96) and latent slots (16 / 32 / 96): tile_gen.hip
 bool tile_gen_ok(const Dims& d);
-int kg_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kg_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
-int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16);
-int kg_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st);
-int kg_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st);
-int kg_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
 // streaming Gram of z' for the register-resident shape in bf16 (gram.hip): out[g*E][dgp][dgp] = scale * sum_t w[e][t] z' z'^T
 int k_gram64(const Plan& pl, const void* Zp, const float* w, float scale, float* part, float* out, hipStream_t st, const float* bn1 = nullptr,
              float* colpart = nullptr, float* mz = nullptr);   // bn1: the input is z, z' = act(BN1(z)) on the fly; mz: column means of z' as well

@@ -3,7 +3,7 @@
 // phase 6 the hop-1 (latent token) chain back to Y and the remap parameters.  Stream-ordered, no
 // allocation, no host sync.
 #include <functional>
-#include "forms.h"
+#include "pass.h"
 #include "moe_run.h"
 #include "side.h"
 
@@ -119,9 +119,11 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   AVMOE_TRY(split ? try_forms(gb, st, with(launch_dpost_pair, std::cref(h), slab_cap), one_by_one) : one_by_one(gb, st));
   BWD_STOP(1);
   // ---- phase 2: bottleneck space (LayerNorm-post statistics), then weight space ------------------
-  AVMOE_TRY(k_post_small_bwd(pl, sv, sc, prm, grads, st, dap16));
+  PassCall pass(pl, sv, sc, prm);                          // (pass.h: each pass tries its forms in order)
+  pass.dap16 = dap16;
+  AVMOE_TRY(k_post_small_bwd(pass, grads, st));
   BWD_STOP(2);
-  if (d.ln_post && d.gram64 && tile_fast_ok(d) && kfs_serves_post_small_bwd(d, dap16)) {
+  if (d.ln_post && d.gram64 && pass.streamed()) {
     // (dGq came out of post_small_bwd's own pass: tile_stream.hip)
   } else if (d.ln_post && d.gram64) {                      // dG[i][e] = sum_t dSoo z' z'^T : one streaming pass over z (z' formed on the fly)
     AVMOE_TRY(k_gram64(pl, sv + pl.o_Z, (const float*)(sc + pl.o_dSooT), 1.f, (float*)(sc + pl.o_gpartT), (float*)(sc + pl.o_dGq), st,
@@ -138,13 +140,13 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   AVMOE_TRY(k_post_prep_bwd(pl, sv, sc, prm, grads, st));
   BWD_STOP(4);
   // ---- phase 3: ReLU / BN1 ; router --------------------------------------------------------------
-  AVMOE_TRY(k_mid_bwd(pl, sv, sc, prm, grads, st));
+  AVMOE_TRY(k_mid_bwd(pass, grads, st));
   BWD_STOP(5);
   AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad));
   BWD_STOP(6);
   // ---- phase 4: folded LayerNorm / hop-2 softmax ---------------------------------------------------
   if (d.nxn) MEMSET0(sc + pl.o_dZR, (size_t)d.NT * d.DZ * esz);
-  AVMOE_TRY(k_pre_small_bwd(pl, sv, sc, prm, grads, st));
+  AVMOE_TRY(k_pre_small_bwd(pass, grads, st));
   }
   if (parts & (2 | 32 | 64)) {   // =============================== section 2: phase 5 ====================================
   const char* dZx = sc + pl.o_Zw;

@@ -1,7 +1,7 @@
 // Forward orchestration of one MoEAdapter site: a fixed sequence of engine GEMMs and bottleneck-space
 // kernels on the caller's stream (no allocation, no host sync: capturable in a hipGraph).
 // Stage names follow oracle/algebra_ref.py::AlgebraRef.forward.
-#include "forms.h"
+#include "pass.h"
 #include "moe_run.h"
 #include "side.h"
 
@@ -238,9 +238,10 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     AVMOE_TRY(down_gemm(sv + pl.o_xr, d.NT, sv + pl.o_ZR));
   }
   // ---- bottleneck space --------------------------------------------------------------------------
-  AVMOE_TRY(k_pre_small(pl, sv, sc, prm, st));
+  PassCall pass(pl, sv, sc, prm);                          // (pass.h: each pass tries its forms in order)
+  AVMOE_TRY(k_pre_small(pass, st));
   AVMOE_TRY(k_bn1_finalize(pl, sv, sc, prm, st));
-  if (!d.gram64) AVMOE_TRY(k_mid(pl, sv, sc, st));
+  if (!d.gram64) AVMOE_TRY(k_mid(pass, st));
   if (d.use_bn && d.training && d.gram64) {
     // No MID pass and no stored z' on this path: ONE streaming pass over z forms z' = act(BN1(z)) on the way into LDS and leaves
     // both BatchNorm-2 moments -- Szz[i][e] = z'^T z' / NT and the column means mz (every later kernel recomputes z' from z anyway)
@@ -256,7 +257,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     AVMOE_TRY(launch_gemm(g, st));
   }
   AVMOE_TRY(k_post_prep(pl, sv, sc, prm, st));
-  AVMOE_TRY(k_post_small(pl, sv, sc, prm, st));
+  AVMOE_TRY(k_post_small(pass, st));
   {                                                        // out = Apost Bpost^T  (mixture, gates, BN2, LN-post folded in)
     GemmArgs g = base();
     g.A = sv + pl.o_Apost; g.B = sv + pl.o_Bpost; g.C = out;

@@ -8,10 +8,6 @@
 
 namespace avmoe {
 
-bool tile_fast_ok(const Dims& d);   // tile_fast.hip
-bool tile_fast_shape(const Dims& d);
-bool tile_gen_ok(const Dims& d);    // tile_gen.hip
-
 size_t slab_floats(const Dims& d) {
   // worst split-K user: weight-gradient contractions over all tokens.  Sized generously:
   // ksplit_max * (largest small output), see moe_forward/backward for the actual launches.

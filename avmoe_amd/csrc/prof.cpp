@@ -45,11 +45,15 @@ bool prof_shapes() {
   static const bool on = getenv("AVMOE_PROF_SHAPES") != nullptr;
   return on;
 }
+static std::string tagged_name(const char* name, long tag) {
+  return tag >= 0 && prof_shapes() ? std::string(name) + " NT" + std::to_string(tag) : std::string(name);
+}
 void prof_begin_tagged(const char* name, long tag, double bytes, double flops, hipStream_t st) {
-  if (!prof_shapes()) { prof_begin(name, bytes, flops, st); return; }
-  char buf[96];
-  snprintf(buf, sizeof(buf), "%s NT%ld", name, tag);
-  prof_begin(buf, bytes, flops, st);
+  prof_begin(tagged_name(name, tag).c_str(), bytes, flops, st);
+}
+void prof_relabel(const char* name, long tag, double bytes) {
+  std::lock_guard<std::mutex> l(g_mu);
+  if (g_open) { g_cur.name = tagged_name(name, tag); g_cur.bytes = bytes; }
 }
 void prof_end(hipStream_t st) {
   std::lock_guard<std::mutex> l(g_mu);

@@ -20,16 +20,26 @@ size_t prof_report(char* buf, size_t cap);
 // their token count) instead of one per kernel name
 bool prof_shapes();
 void prof_begin_tagged(const char* name, long tag, double alg_bytes, double flops, hipStream_t st);
+// the open record under another name (tag < 0: untagged) and with other bytes
+void prof_relabel(const char* name, long tag, double alg_bytes);
 
 struct ProfScope {
-  hipStream_t st; bool on;
+  hipStream_t st; bool on; long tag = -1;
   ProfScope(const char* name, double bytes, double flops, hipStream_t s) : st(s), on(prof_enabled()) {
     if (on) prof_begin(name, bytes, flops, s);
   }
-  ProfScope(const char* name, long tokens, double bytes, double flops, hipStream_t s) : st(s), on(prof_enabled()) {
+  ProfScope(const char* name, long tokens, double bytes, double flops, hipStream_t s) : st(s), on(prof_enabled()), tag(tokens) {
     if (on) prof_begin_tagged(name, tokens, bytes, flops, s);
   }
   ~ProfScope() { if (on) prof_end(st); }
+  // A wrapper whose forms differ in what the profiler shows (pass.h): the form that ran is known after the chain.
+  void relabel(const char* name, double bytes) { if (on) prof_relabel(name, tag, bytes); }
+  // ends the record here and opens the next one on the same stream (tagged with this scope's token count, or not)
+  void next(const char* name, bool tagged, double bytes) {
+    if (!on) return;
+    prof_end(st);
+    if (tagged) prof_begin_tagged(name, tag, bytes, 0.0, st); else prof_begin(name, bytes, 0.0, st);
+  }
 };
 
 }  // namespace avmoe

@@ -14,7 +14,7 @@
 //   * sums over the bottleneck index = in-lane + 2 cross-row shuffles; sums over tokens (BatchNorm statistics) are carried
 //     in per-lane accumulators over the whole kernel and folded once at its end (no float atomics: reproducible); sums over the
 //     experts of one token go through LDS in expert order.
-#include "kernels.h"
+#include "pass.h"
 #include "device_utils.h"
 #include "prof.h"
 #include <algorithm>
@@ -997,16 +997,7 @@ __global__ void __launch_bounds__(256, LB_PRELB) kf_pre_lat_bwd(FPreLArgs a, con
   }
 }
 
-FastDims make_fd(const Dims& d, int per) {
-  FastDims t;
-  t.S = d.S; t.N = d.N; t.C = d.C; t.El = d.El; t.KL = d.KL; t.KLT = d.KLT; t.KLp = d.KLp; t.KPp = d.KPp; t.NT = d.NT; t.per = per; t.aL = d.aL;
-  return t;
-}
-void fast_grid(const Dims& d, dim3* grid, int* per) {
-  const int bps = d.nblk_tok / d.S;
-  *per = (int)round_up(cdiv(d.N, bps), 16);
-  *grid = dim3((unsigned)bps, (unsigned)d.S);
-}
+dim3 fast_grid(const Dims& d) { return dim3((unsigned)(d.nblk_tok / d.S), (unsigned)d.S); }
 
 }  // namespace
 
@@ -1098,123 +1089,121 @@ static size_t fast_excl_lds(const void* fn, size_t sh, unsigned nblocks, int exc
     else LAUNCH_TEX2(bf16, KERN, false, SH, __VA_ARGS__);                                              \
   } while (0)
 
-int kf_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_pre_small(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FPreArgs a;
-  for (int e = 0; e < MAX_E; ++e) {
-    a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; a.nxn_of_e[e] = e < d.E ? d.nxn_of_e[e] : 0;
-    a.sxr_off[e] = (e < d.E && d.xr_of_e[e] > 0) ? (long)d.xr_of_e[e] * 3 * d.NT : 0;
-  }
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.sxr_off, c.x.sxr_off);
   a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
   a.L2g = d.fuse_l2 ? (const float*)(scratch + pl.o_L2g) : nullptr; a.L2w = d.fuse_l2 ? (float*)(saved + pl.o_L2) : nullptr;
   if (d.fuse_l2 && d.g != 2) { set_last_error("pre_small: fused logits are built for two groups"); return ERR_UNSUPPORTED; }
-  a.t = make_fd(d, per); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps;
+  a.t = make_fd(d); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps;
   const size_t sh = ((size_t)d.El * (FK * LD32 + FDD * LD32 + FK) + (size_t)d.E * 2 * FDD + 4 * FDD) * sizeof(float);
   LAUNCH_TEX(d.bf16, kf_pre_small, sh, a, (void*)(saved + pl.o_Z), (const float*)(saved + pl.o_L2), (const float*)(saved + pl.o_sx),
             (const float*)(saved + pl.o_TT), (const float*)(saved + pl.o_TW), (const float*)(saved + pl.o_Tsum),
             (const float*)(saved + pl.o_wsum), (const float*)(saved + pl.o_dconst), (void*)(saved + pl.o_a), (float*)(saved + pl.o_rmu),
             (float*)(scratch + pl.o_colpart));
   AVMOE_CHECK_LAUNCH("pre_small (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
-int kf_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_mid(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FMidFArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
-  a.t = make_fd(d, per);
+  put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d);
   LAUNCH_TE(d.bf16, kf_mid, 0, a, (const void*)(saved + pl.o_Z), (const float*)(saved + pl.o_bn1), (void*)(scratch + pl.o_Zp),
             (float*)(scratch + pl.o_colpart));
   AVMOE_CHECK_LAUNCH("mid (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
-int kf_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_post_small(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FPostArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
-  a.t = make_fd(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
   LAUNCH_TE(d.bf16, kf_post_small, 0, a, (const void*)(saved + pl.o_Z), (const float*)(saved + pl.o_bn1), (const float*)(saved + pl.o_Gq),
             (const float*)(saved + pl.o_uvh), (const float*)(saved + pl.o_probs), (void*)(saved + pl.o_Apost), (float*)(saved + pl.o_rpmup));
   AVMOE_CHECK_LAUNCH("post_small (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
-int kf_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_post_small_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FPostBArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
-  a.t = make_fd(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
   a.ZpS = nullptr;          // z' is recomputed from z (no stored copy any more: the Gram kernel forms it on the fly too)
   a.dSooT = d.gram64 ? (float*)(scratch + pl.o_dSooT) : nullptr;
   a.dApx = (const float*)(scratch + pl.o_dApx); a.dapw = d.E * d.dgp;
-  if (dap16 && !d.bf16) { set_last_error("post_small_bwd: split dApost is a bf16 form"); return ERR_BAD_ARG; }
+  if (c.dap16 && !d.bf16) { set_last_error("post_small_bwd: split dApost is a bf16 form"); return ERR_BAD_ARG; }
 #define POSTB_ARGS a, (const void*)(saved + pl.o_Z), (const float*)(saved + pl.o_bn1), (const float*)(saved + pl.o_Gq),                       \
             (const float*)(saved + pl.o_uvh), (const float*)(saved + pl.o_probs), (const float*)(saved + pl.o_rpmup),                     \
             (const void*)(scratch + pl.o_dAp), (void*)(scratch + pl.o_dzp), (void*)(scratch + pl.o_Zp), (void*)(scratch + pl.o_Zw),       \
             (float*)(scratch + pl.o_colpart), (float*)(scratch + pl.o_blkscal)
-  if (dap16) LAUNCH_TEX2(true, kf_post_small_bwd, true, 0, POSTB_ARGS);
+  if (c.dap16) LAUNCH_TEX2(true, kf_post_small_bwd, true, 0, POSTB_ARGS);
   else LAUNCH_TEX2(d.bf16, kf_post_small_bwd, false, 0, POSTB_ARGS);
 #undef POSTB_ARGS
   AVMOE_CHECK_LAUNCH("post_small_bwd (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
-int kf_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_mid_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FMidArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
-  a.t = make_fd(d, per); a.moments = d.use_bn && d.training;
+  put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d); a.moments = d.use_bn && d.training;
   LAUNCH_TE(d.bf16, kf_mid_bwd, 0, a, (const void*)(saved + pl.o_Z), (const float*)(saved + pl.o_bn1),
             (const float*)(scratch + pl.o_dsm), (const float*)(scratch + pl.o_sdSzz), (void*)(scratch + pl.o_dzp),
             (float*)(scratch + pl.o_colpart));
   AVMOE_CHECK_LAUNCH("mid_bwd (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
-int kf_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+int kf_pre_small_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
+  const dim3 grid = fast_grid(d);
   FPreBArgs a;
-  {
-    bool seen[MAX_E] = {};
-    for (int e = 0; e < MAX_E; ++e) {
-      a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e];
-      a.nxn_of_e[e] = 0; a.first_of_slot[e] = 0; a.sxr_off[e] = 0;
-      if (e < d.E && d.nxn_of_e[e]) {
-        const int slot = d.xr_of_e[e];
-        a.nxn_of_e[e] = 1; a.sxr_off[e] = (long)slot * 3 * d.NT;
-        a.first_of_slot[e] = !seen[slot]; seen[slot] = true;
-      }
-    }
-  }
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.first_of_slot, c.x.first_of_slot); put(a.sxr_off, c.x.sxr_off);
   a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
   a.dZR = (void*)(scratch + pl.o_dZR); a.dsr = (float*)(scratch + pl.o_dsr);
-  a.t = make_fd(d, per); a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training;
+  a.t = make_fd(d); a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training;
   LAUNCH_TEX(d.bf16, kf_pre_small_bwd, 0, a, (const void*)(saved + pl.o_Z), (const float*)(saved + pl.o_wsum),
             (const float*)(saved + pl.o_dconst), (const float*)(saved + pl.o_rmu),
             (const float*)(saved + pl.o_bn1), (const float*)(scratch + pl.o_dsm), (const void*)(scratch + pl.o_dzp),
             (void*)(scratch + pl.o_Zw), (void*)(scratch + pl.o_dL2x), (float*)(scratch + pl.o_dslat),
             (float*)(scratch + pl.o_rs2x), (float*)(scratch + pl.o_colpart), (float*)(scratch + pl.o_blkscal));
   AVMOE_CHECK_LAUNCH("pre_small_bwd (64/32)");
+  c.ran = PASS_FAST;
   return OK;
 }
 
 // the hop-2 block of the cross-modal experts; after kf_pre_small_bwd on the same stream (reads dZx and dslat, rewrites the experts'
 // gate partials in blkscal)
-int kf_pre_lat_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
+int kf_pre_lat_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!tile_fast_ok(d)) return 1;
   if (d.KL == 0) return OK;
-  dim3 grid; int per; fast_grid(d, &grid, &per);
+  const dim3 grid = fast_grid(d);
   FPreLArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.glat.p[e] = prm.e[e].gate_lat; a.e_of_lat[e] = 0; }
-  for (int e = 0; e < d.E; ++e) if (d.lat_of_e[e] >= 0) a.e_of_lat[d.lat_of_e[e]] = e;
-  a.t = make_fd(d, per);
+  a.glat = c.x.glat; put(a.e_of_lat, c.x.e_of_lat);
+  a.t = make_fd(d);
   const size_t sh = ((size_t)d.El * (FK * LD32 + FK * LD64 + FDD * LD32 + FK) + 4 * FDD + 4) * sizeof(float);
   LAUNCH_TE256(d.bf16, kf_pre_lat_bwd, sh, a, (const float*)(saved + pl.o_L2), (const float*)(saved + pl.o_TT), (const float*)(saved + pl.o_TW),
             (const float*)(saved + pl.o_Tsum), (const void*)(saved + pl.o_a), (const void*)(scratch + pl.o_Zw),

@@ -15,6 +15,13 @@ constexpr int LD32 = 36;    // leading dim of LDS matrices with 32 columns   (4*
 constexpr int LD64 = 68;    // ... with 64 columns
 
 struct FastDims { int S, N, C, El, KL, KLT, KLp, KPp, NT, per; long aL; };      // aL: plane stride of a / aw / ag ([slot][token][32])
+// per: the tokens of a frame that one virtual block takes (Dims::nblk_tok blocks over the S frames), in whole 16-token tiles
+inline int tok_per_vblock(const Dims& d) { return (int)round_up(cdiv(d.N, d.nblk_tok / d.S), 16); }
+inline FastDims make_fd(const Dims& d) {
+  FastDims t;
+  t.S = d.S; t.N = d.N; t.C = d.C; t.El = d.El; t.KL = d.KL; t.KLT = d.KLT; t.KLp = d.KLp; t.KPp = d.KPp; t.NT = d.NT; t.per = tok_per_vblock(d); t.aL = d.aL;
+  return t;
+}
 
 // one expert's 64 bottleneck entries of a Z-space row ([group][expert][32], element type T): chunks v[0..3]
 template <typename T, int E> __device__ __forceinline__ void ld_row(const T* row, int e, int q, float4 (&v)[4]) {

@@ -12,7 +12,7 @@
 // Template parameters: NG groups, NCG 16-entry chunks per group, KC 16-slot chunks of latent tokens; the expert count, the true
 // number of latent tokens (the padding slots are masked out of the softmax) and every stride are run-time values.
 // Arithmetic and names: oracle/algebra_ref.py.
-#include "kernels.h"
+#include "pass.h"
 #include "device_utils.h"
 #include "prof.h"
 #include <algorithm>
@@ -1088,11 +1088,12 @@ static inline void spread_rounds(dim3* grid, const GenDims& t) {
   } while (0)
 
 #if GEN_PART == 5
-int kg_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
+int kg_mid(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!d.gen) return 1;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   GMidFArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
+  put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_gd(d, per);
   size_t sh; pick_round(d.E, 2 * (size_t)d.DD, (size_t)d.DD, gen_max_waves(d.g, d.dgp / 16, 0), per, &a.t.R, &a.t.NS, &sh, d.excl);
   spread_rounds(&grid, a.t);
@@ -1107,14 +1108,16 @@ int kg_mid(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
 #undef X
   if (!done) { set_last_error("mid: shape not built"); return ERR_UNSUPPORTED; }
   AVMOE_CHECK_LAUNCH("mid (general)");
+  c.ran = PASS_GEN;
   return OK;
 }
 
-int kg_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
+int kg_mid_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!d.gen) return 1;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   GMidArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
+  put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_gd(d, per); a.moments = d.use_bn && d.training;
   size_t sh; pick_round(d.E, (size_t)d.DD * (d.dgp + 4) + 5 * d.DD, (size_t)d.DD, gen_max_waves(d.g, d.dgp / 16, 0), per, &a.t.R, &a.t.NS, &sh, d.excl);
   spread_rounds(&grid, a.t);
@@ -1131,14 +1134,16 @@ int kg_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
 #undef MB_ARGS
   if (!done) { set_last_error("mid_bwd: shape not built"); return ERR_UNSUPPORTED; }
   AVMOE_CHECK_LAUNCH("mid_bwd (general)");
+  c.ran = PASS_GEN;
   return OK;
 }
 
-int kg_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
+int kg_post_small(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!d.gen) return 1;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   GPostArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_gd(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
   size_t sh; pick_round(d.E, (size_t)d.DD * (d.dgp + 4) + 4 * d.DD, 0, gen_max_waves(d.g, d.dgp / 16, 0), per, &a.t.R, &a.t.NS, &sh, d.excl);
   spread_rounds(&grid, a.t);
@@ -1155,18 +1160,20 @@ int kg_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_pt
 #undef PS_ARGS
   if (!done) { set_last_error("post_small: shape not built"); return ERR_UNSUPPORTED; }
   AVMOE_CHECK_LAUNCH("post_small (general)");
+  c.ran = PASS_GEN;
   return OK;
 }
 
-int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16) {
-  const Dims& d = pl.d;
+int kg_post_small_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (!d.gen) return 1;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   GPostBArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_gd(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
   a.dApx = (const float*)(scratch + pl.o_dApx); a.dapw = d.E * d.dgp;
   a.dSooT = d.gram64 ? (float*)(scratch + pl.o_dSooT) : nullptr;
-  if (dap16 && !d.bf16) { set_last_error("post_small_bwd: split dApost is a bf16 form"); return ERR_BAD_ARG; }
+  if (c.dap16 && !d.bf16) { set_last_error("post_small_bwd: split dApost is a bf16 form"); return ERR_BAD_ARG; }
   size_t sh; pick_round(d.E, (size_t)d.DD * (d.dgp + 4) + 4 * d.DD, (size_t)d.DD + 1, gen_max_waves(d.g, d.dgp / 16, 0), per, &a.t.R, &a.t.NS, &sh, d.excl);
   spread_rounds(&grid, a.t);
   const int ncg = d.dgp / 16; bool done = false;
@@ -1176,7 +1183,7 @@ int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_mo
 #define X(NG, NCG)                                                                                                      \
   if (!done && d.g == NG && ncg == NCG) {                                                                               \
     done = true;                                                                                                        \
-    if (dap16) LAUNCH_ONE((kg_post_small_bwd<__bf16, NG, NCG, true>), sh, PB_ARGS);                                     \
+    if (c.dap16) LAUNCH_ONE((kg_post_small_bwd<__bf16, NG, NCG, true>), sh, PB_ARGS);                                     \
     else if (d.bf16) LAUNCH_ONE((kg_post_small_bwd<__bf16, NG, NCG, false>), sh, PB_ARGS);                              \
     else LAUNCH_ONE((kg_post_small_bwd<float, NG, NCG, false>), sh, PB_ARGS);                                           \
   }
@@ -1185,6 +1192,7 @@ int kg_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_mo
 #undef PB_ARGS
   if (!done) { set_last_error("post_small_bwd: shape not built"); return ERR_UNSUPPORTED; }
   AVMOE_CHECK_LAUNCH("post_small_bwd (general)");
+  c.ran = PASS_GEN;
   return OK;
 }
 
@@ -1202,14 +1210,11 @@ typedef __bf16 GenT;
 #endif
 
 #if GEN_PART == 1 || GEN_PART == 2
-int GEN_FN(kg_pre_small)(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
+int GEN_FN(kg_pre_small)(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   GPreArgs a;
-  for (int e = 0; e < MAX_E; ++e) {
-    a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; a.nxn_of_e[e] = e < d.E ? d.nxn_of_e[e] : 0;
-    a.sxr_off[e] = (e < d.E && d.xr_of_e[e] > 0) ? (long)d.xr_of_e[e] * 3 * d.NT : 0;
-  }
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.sxr_off, c.x.sxr_off);
   a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
   a.t = make_gd(d, per); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps;
   const int ncg = d.dgp / 16, kc = kc_of(d); bool done = false;
@@ -1238,22 +1243,13 @@ int GEN_FN(kg_pre_small)(const Plan& pl, char* saved, char* scratch, const avmoe
 #endif   // GEN_PART 1, 2
 
 #if GEN_PART == 3 || GEN_PART == 4
-int GEN_FN(kg_pre_small_bwd)(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
+int GEN_FN(kg_pre_small_bwd)(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
   dim3 grid; int per; gen_grid(d, &grid, &per);
   const int ncg = d.dgp / 16, kc = kc_of(d);
   {   // ---- every expert: BN1 / LayerNorm part ----
     GPreBArgs a;
-    bool seen[MAX_E] = {};
-    for (int e = 0; e < MAX_E; ++e) {
-      a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e];
-      a.nxn_of_e[e] = 0; a.first_of_slot[e] = 0; a.sxr_off[e] = 0;
-      if (e < d.E && d.nxn_of_e[e]) {
-        const int slot = d.xr_of_e[e];
-        a.nxn_of_e[e] = 1; a.sxr_off[e] = (long)slot * 3 * d.NT;
-        a.first_of_slot[e] = !seen[slot]; seen[slot] = true;
-      }
-    }
+    a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.first_of_slot, c.x.first_of_slot); put(a.sxr_off, c.x.sxr_off);
     a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
     a.dZR = (void*)(scratch + pl.o_dZR); a.dsr = (float*)(scratch + pl.o_dsr);
     a.t = make_gd(d, per); a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training;
@@ -1277,8 +1273,7 @@ int GEN_FN(kg_pre_small_bwd)(const Plan& pl, char* saved, char* scratch, const a
   }
   if (d.El > 0) {   // ---- the cross-modal experts' hop-2 block (after the kernel above on the same stream: reads dZx and dslat) ----
     GPreLArgs a;
-    for (int e = 0; e < MAX_E; ++e) { a.glat.p[e] = prm.e[e].gate_lat; a.e_of_lat[e] = 0; }
-    for (int e = 0; e < d.E; ++e) if (d.lat_of_e[e] >= 0) a.e_of_lat[d.lat_of_e[e]] = e;
+    a.glat = c.x.glat; put(a.e_of_lat, c.x.e_of_lat);
     a.t = make_gd(d, per);
     const size_t Kp = (size_t)kc * 16;
     size_t sh; pick_round(d.El, Kp * (Kp + 4) + Kp * ((size_t)d.DD + 4) + Kp, Kp + 1, gen_max_waves(d.g, ncg, kc), per, &a.t.R, &a.t.NS, &sh, d.excl);
@@ -1305,15 +1300,17 @@ int GEN_FN(kg_pre_small_bwd)(const Plan& pl, char* saved, char* scratch, const a
 #endif   // GEN_PART 3, 4
 
 #if GEN_PART == 5
-int kg_pre_small_f32(const Plan&, char*, char*, const avmoe_moe_ptrs&, hipStream_t);
-int kg_pre_small_bf16(const Plan&, char*, char*, const avmoe_moe_ptrs&, hipStream_t);
-int kg_pre_small_bwd_f32(const Plan&, char*, char*, const avmoe_moe_ptrs&, hipStream_t);
-int kg_pre_small_bwd_bf16(const Plan&, char*, char*, const avmoe_moe_ptrs&, hipStream_t);
-int kg_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  return pl.d.bf16 ? kg_pre_small_bf16(pl, saved, scratch, prm, st) : kg_pre_small_f32(pl, saved, scratch, prm, st);
+int kg_pre_small_f32(PassCall&, hipStream_t);
+int kg_pre_small_bf16(PassCall&, hipStream_t);
+int kg_pre_small_bwd_f32(PassCall&, hipStream_t);
+int kg_pre_small_bwd_bf16(PassCall&, hipStream_t);
+int kg_pre_small(PassCall& c, hipStream_t st) {
+  if (!c.pl.d.gen) return 1;
+  return launched(c, PASS_GEN, c.pl.d.bf16 ? kg_pre_small_bf16(c, st) : kg_pre_small_f32(c, st));
 }
-int kg_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  return pl.d.bf16 ? kg_pre_small_bwd_bf16(pl, saved, scratch, prm, st) : kg_pre_small_bwd_f32(pl, saved, scratch, prm, st);
+int kg_pre_small_bwd(PassCall& c, hipStream_t st) {
+  if (!c.pl.d.gen) return 1;
+  return launched(c, PASS_GEN, c.pl.d.bf16 ? kg_pre_small_bwd_bf16(c, st) : kg_pre_small_bwd_f32(c, st));
 }
 #endif
 

@@ -10,7 +10,7 @@
 // Row reductions over columns = in-lane over column tiles, then xor-shuffles 1,2,4,8 inside the 16-lane group.
 // Column sums over tokens (BatchNorm etc.) = xor-shuffles 16,32, then a per-wave LDS accumulator, flushed per block
 // into colpart[blk][slot][col] (summed over blocks by kk_reduce_colpart: no float atomics, reproducible).
-#include "kernels.h"
+#include "pass.h"
 #include "device_utils.h"
 #include "prof.h"
 #include <algorithm>
@@ -378,36 +378,12 @@ __global__ void __launch_bounds__(256) kt_pre_small(PreTArgs a, float* __restric
 }
 
 
-// Algorithmic bytes of the bottleneck-space passes (every element each pass has to read or write, once; zsz / esz are the
-// element sizes of the Z-space and T-typed tensors) -- the numerators of their HBM rooflines.
-static double bytes_pre_small(const Dims& d) { return (double)d.NT * (2.0 * d.DZ * d.zsz + (d.KL ? (double)d.KL * (4 + d.esz) : 0.0) + 8.0 + 8.0 * d.E); }
-static double bytes_post_small(const Dims& d) { return (double)d.NT * ((double)d.DZ * d.zsz + (double)d.g * d.KPp * d.esz + 8.0 * d.E); }
-static double bytes_post_small_bwd(const Dims& d) {
-  const double zspace = d.gram64 ? (double)d.DZ * (d.esz + d.zsz) + 4.0 * d.E       // read the saved z', write dz' and dSoo
-                                 : (double)d.DZ * (2.0 * d.zsz + 2.0 * d.esz);      // read Z, write dz', z', dSoo z'
-  return (double)d.NT * (zspace + (double)d.g * d.KPp * 4.0 + 8.0 * d.E);
-}
-static double bytes_mid_bwd(const Dims& d) { return (double)d.NT * (3.0 * d.DZ * d.zsz); }
-static double bytes_pre_small_bwd(const Dims& d) {
-  return (double)d.NT * ((double)d.DZ * (2.0 * d.zsz + d.esz) + (d.KL ? (double)d.KL * (4 + 4 * d.esz) : 0.0) + 8.0 * d.E + 12.0);
-}
-int k_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  const bool stream = tile_fast_ok(d) && kfs_serves_pre_small(d);
-  ProfScope ps_(stream ? "k_pre_small (stream)" : "k_pre_small", (long)d.NT, bytes_pre_small(d), 0.0, st);
-  for (int e = 0; e < d.E; ++e)
-    if (d.nxn_of_e[e] && !prm.e[e].gate_lat) { set_last_error("moe: expert %d lacks gate_av", e); return ERR_BAD_ARG; }
-  if (tile_fast_ok(d)) {
-    const int rc = kfs_pre_small(pl, saved, scratch, prm, st);       // streaming form (large bf16 sites); 1 = not served
-    return rc == 1 ? kf_pre_small(pl, saved, scratch, prm, st) : rc;
-  }
-  if (d.gen) return kg_pre_small(pl, saved, scratch, prm, st);
+// The any-shape forms: they serve every site, so each ends its pass's chain (pass.h).
+static int kt_pre_small_form(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
   dim3 grid; int per; tile_grid(d, &grid, &per);
   PreTArgs a;
-  for (int e = 0; e < MAX_E; ++e) {
-    a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; a.nxn_of_e[e] = d.nxn_of_e[e];
-    a.sxr_off[e] = (e < d.E && d.xr_of_e[e] > 0) ? (long)d.xr_of_e[e] * 3 * d.NT : 0;
-  }
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.sxr_off, c.x.sxr_off);
   a.t = make_td(d, per); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps;
   a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
   const TileDims& t = a.t;
@@ -419,7 +395,19 @@ int k_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs
              (const float*)(saved + pl.o_Tsum), (const float*)(saved + pl.o_wsum), (const float*)(saved + pl.o_dconst),
              (void*)(saved + pl.o_a), (float*)(saved + pl.o_rmu), (float*)(scratch + pl.o_colpart));
   AVMOE_CHECK_LAUNCH("pre_small");
+  c.ran = PASS_TILE;
   return OK;
+}
+
+int k_pre_small(PassCall& c, hipStream_t st) {
+  const Dims& d = c.pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_pre_small", (long)d.NT, bytes_pre_small(d), 0.0, st);
+  for (int e = 0; e < d.E; ++e)
+    if (d.nxn_of_e[e] && !c.prm.e[e].gate_lat) { set_last_error("moe: expert %d lacks gate_av", e); return ERR_BAD_ARG; }
+  const int rc = try_forms(c, st, kfs_pre_small, kf_pre_small, kg_pre_small, kt_pre_small_form);
+  if (c.streamed()) ps_.relabel("k_pre_small (stream)", bytes_pre_small(d));
+  return rc;
 }
 
 // =====================================================================================================
@@ -530,18 +518,11 @@ __global__ void __launch_bounds__(256) kt_post_small(PostTArgs a, const float* _
   }
 }
 
-int k_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  const bool stream = tile_fast_ok(d) && kfs_serves_post_small(d);
-  ProfScope ps_(stream ? "k_post_small (stream)" : "k_post_small", (long)d.NT, bytes_post_small(d), 0.0, st);
-  if (tile_fast_ok(d)) {
-    const int rc = kfs_post_small(pl, saved, scratch, prm, st);       // streaming form (large bf16 sites); 1 = not served
-    return rc == 1 ? kf_post_small(pl, saved, scratch, prm, st) : rc;
-  }
-  if (d.gen) return kg_post_small(pl, saved, scratch, prm, st);
+static int kt_post_small_form(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved;
   dim3 grid; int per; tile_grid(d, &grid, &per);
   PostTArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_td(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
   const TileDims& t = a.t;
   const int g4 = cdiv(t.dgp, 4);
@@ -551,7 +532,17 @@ int k_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptr
              (const float*)(saved + pl.o_Gq), (const float*)(saved + pl.o_uvh), (const float*)(saved + pl.o_probs),
              (void*)(saved + pl.o_Apost), (float*)(saved + pl.o_rpmup));
   AVMOE_CHECK_LAUNCH("post_small");
+  c.ran = PASS_TILE;
   return OK;
+}
+
+int k_post_small(PassCall& c, hipStream_t st) {
+  const Dims& d = c.pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_post_small", (long)d.NT, bytes_post_small(d), 0.0, st);
+  const int rc = try_forms(c, st, kfs_post_small, kf_post_small, kg_post_small, kt_post_small_form);
+  if (c.streamed()) ps_.relabel("k_post_small (stream)", bytes_post_small(d));
+  return rc;
 }
 
 }  // namespace avmoe
@@ -1064,24 +1055,12 @@ static int pick_waves(size_t fixed_floats, size_t per_wave_floats, size_t* bytes
   return best;
 }
 
-int k_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads, hipStream_t st, int dap16) {
-  const Dims& d = pl.d;
-  const bool stream = tile_fast_ok(d) && kfs_serves_post_small_bwd(d, dap16);
-  ProfScope ps_(stream ? "k_post_small_bwd (stream)" : "k_post_small_bwd", (long)d.NT, bytes_post_small_bwd(d) - (dap16 ? (double)d.NT * d.g * (d.E * d.dgp * 2.0 + (d.KPp - 16) * 4.0 - d.E * d.dgp * 2.0) : 0.0), 0.0, st);
-  if (dap16 && !tile_fast_ok(d) && !d.gen) { set_last_error("post_small_bwd: split dApost needs a register-resident path"); return ERR_BAD_ARG; }
-  if (tile_fast_ok(d)) {
-    const int rc = kfs_post_small_bwd(pl, saved, scratch, prm, st, dap16);       // streaming form (large bf16 sites); 1 = not served
-    if (rc < 0) return rc;
-    if (rc == 1) AVMOE_TRY(kf_post_small_bwd(pl, saved, scratch, prm, st, dap16));
-    return k_post_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
-  if (d.gen) {
-    AVMOE_TRY(kg_post_small_bwd(pl, saved, scratch, prm, st, dap16));
-    return k_post_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
+static int kt_post_small_bwd_form(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  if (c.dap16) { set_last_error("post_small_bwd: split dApost needs a register-resident path"); return ERR_BAD_ARG; }
   dim3 grid; int per; tile_grid(d, &grid, &per);
   PostBTArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_td(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
   const TileDims& t = a.t;
   const int g4 = cdiv(t.dgp, 4);
@@ -1102,26 +1081,24 @@ int k_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe
 #undef LAUNCH_PSB
 #undef KPSB
   AVMOE_CHECK_LAUNCH("post_small_bwd");
-  return k_post_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
+  c.ran = PASS_TILE;
+  return OK;
 }
 
-int k_mid_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads, hipStream_t st) {
-  const Dims& d = pl.d;
-  const bool stream = tile_fast_ok(d) && kfs_serves_mid_bwd(d);
-  ProfScope ps_(stream ? "k_mid_bwd (stream)" : "k_mid_bwd", (long)d.NT, bytes_mid_bwd(d), 0.0, st);
-  if (tile_fast_ok(d)) {
-    const int rc = kfs_mid_bwd(pl, saved, scratch, st);       // streaming form (large bf16 sites); 1 = not served
-    if (rc < 0) return rc;
-    if (rc == 1) AVMOE_TRY(kf_mid_bwd(pl, saved, scratch, st));
-    return k_mid_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
-  if (d.gen) {
-    AVMOE_TRY(kg_mid_bwd(pl, saved, scratch, st));
-    return k_mid_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
+int k_post_small_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st) {
+  const Dims& d = c.pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_post_small_bwd", (long)d.NT, bytes_post_small_bwd(d, c.dap16), 0.0, st);
+  AVMOE_TRY(try_forms(c, st, kfs_post_small_bwd, kf_post_small_bwd, kg_post_small_bwd, kt_post_small_bwd_form));
+  if (c.streamed()) ps_.relabel("k_post_small_bwd (stream)", bytes_post_small_bwd(d, c.dap16));
+  return k_post_small_bwd_finalize(c.pl, c.saved, c.scratch, c.prm, grads, st);
+}
+
+static int kt_mid_bwd_form(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
   dim3 grid; int per; tile_grid(d, &grid, &per);
   MidBTArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
+  put(a.relu_of_e, c.x.relu_of_e);
   a.t = make_td(d, per); a.moments = d.use_bn && d.training;
   const TileDims& t = a.t;
   const int g4 = cdiv(t.dgp, 4);
@@ -1133,51 +1110,24 @@ int k_mid_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& 
              (const float*)(scratch + pl.o_dsm), (const float*)(scratch + pl.o_sdSzz), (float*)(scratch + pl.o_dzp),
              (float*)(scratch + pl.o_colpart));
   AVMOE_CHECK_LAUNCH("mid_bwd");
-  return k_mid_bwd_finalize(pl, saved, scratch, prm, grads, st);
+  c.ran = PASS_TILE;
+  return OK;
 }
 
-int k_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads, hipStream_t st) {
-  const Dims& d = pl.d;
-  if (tile_fast_ok(d) && kfs_serves_pre_bwd(d)) {      // large bf16 sites: both parts in one streaming pass (tile_stream.hip)
-    {
-      ProfScope ps_("k_pre_bwd (stream)", (long)d.NT, (double)d.NT * ((double)d.DZ * (2.0 * d.zsz + d.esz) + 8.0 * d.E + 4.0 + (d.KL ? (double)d.KL * (4 + 4 * d.esz) + d.KLp * d.esz - d.KL * d.esz : 0.0)), 0.0, st);
-      AVMOE_TRY(kfs_pre_bwd(pl, saved, scratch, prm, st));
-    }
-    ProfScope ps_("k_pre_bwd_finalize", 0.0, 0.0, st);
-    return k_pre_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
-  if (tile_fast_ok(d)) {      // two kernels: every expert's BN1 / LayerNorm part, then the cross-modal experts' hop-2 block (tile_fast.hip)
-    const double lat = (double)d.NT * ((double)d.El * d.DD * d.esz + (d.KL ? (double)d.KL * (4 + 4 * d.esz) : 0.0) + 8.0 * d.El);
-    {
-      ProfScope ps_("k_pre_small_bwd", (long)d.NT, (double)d.NT * ((double)d.DZ * (2.0 * d.zsz + d.esz) + 8.0 * d.E + 8.0 * d.El + 12.0), 0.0, st);
-      AVMOE_TRY(kf_pre_small_bwd(pl, saved, scratch, prm, st));
-    }
-    if (d.KL) {
-      ProfScope ps_("k_pre_lat_bwd", (long)d.NT, lat, 0.0, st);
-      AVMOE_TRY(kf_pre_lat_bwd(pl, saved, scratch, prm, st));
-    }
-    ProfScope ps_("k_pre_bwd_finalize", 0.0, 0.0, st);
-    return k_pre_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
-  ProfScope ps_("k_pre_small_bwd", (long)d.NT, bytes_pre_small_bwd(d), 0.0, st);
-  if (d.gen) {
-    AVMOE_TRY(kg_pre_small_bwd(pl, saved, scratch, prm, st));
-    return k_pre_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
-  }
+int k_mid_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st) {
+  const Dims& d = c.pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_mid_bwd", (long)d.NT, bytes_mid_bwd(d), 0.0, st);
+  AVMOE_TRY(try_forms(c, st, kfs_mid_bwd, kf_mid_bwd, kg_mid_bwd, kt_mid_bwd_form));
+  if (c.streamed()) ps_.relabel("k_mid_bwd (stream)", bytes_mid_bwd(d));
+  return k_mid_bwd_finalize(c.pl, c.saved, c.scratch, c.prm, grads, st);
+}
+
+static int kt_pre_small_bwd_form(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
   dim3 grid; int per; tile_grid(d, &grid, &per);
   PreBTArgs a;
-  {
-    bool seen[MAX_E] = {};
-    for (int e = 0; e < MAX_E; ++e) {
-      a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; a.nxn_of_e[e] = d.nxn_of_e[e];
-      a.first_of_slot[e] = 0; a.sxr_off[e] = 0;
-      if (e < d.E && d.nxn_of_e[e]) {
-        const int slot = d.xr_of_e[e];
-        a.sxr_off[e] = (long)slot * 3 * d.NT;
-        a.first_of_slot[e] = !seen[slot]; seen[slot] = true;
-      }
-    }
-  }
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e); put(a.nxn_of_e, c.x.nxn_of_e); put(a.first_of_slot, c.x.first_of_slot); put(a.sxr_off, c.x.sxr_off);
   a.ZR = (const float*)(saved + pl.o_ZR); a.sxr = (const float*)(saved + pl.o_sxr);
   a.dZR = (void*)(scratch + pl.o_dZR); a.dsr = (float*)(scratch + pl.o_dsr);
   a.t = make_td(d, per); a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training; a.dd4 = cdiv(d.DD, 4);
@@ -1196,7 +1146,28 @@ int k_pre_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_
              (void*)(scratch + pl.o_ag), (float*)(scratch + pl.o_dsxs), (float*)(scratch + pl.o_rs2x),
              (float*)(scratch + pl.o_colpart), (float*)(scratch + pl.o_blkscal), (float*)(scratch + pl.o_dtbp));
   AVMOE_CHECK_LAUNCH("pre_small_bwd");
-  return k_pre_small_bwd_finalize(pl, saved, scratch, prm, grads, st);
+  c.ran = PASS_TILE;
+  return OK;
+}
+
+// What the profiler shows differs by form.  The generalised and the any-shape form: one scope, finalize included.  The register-resident
+// family: its kernels under scopes of their own -- k_pre_bwd (stream), or k_pre_small_bwd and (with cross-modal experts) k_pre_lat_bwd --
+// and k_pre_bwd_finalize after them.
+int k_pre_small_bwd(PassCall& c, const avmoe_moe_ptrs& grads, hipStream_t st) {
+  const Dims& d = c.pl.d;
+  c.ran = PASS_NONE;
+  ProfScope ps_("k_pre_small_bwd", (long)d.NT, bytes_pre_small_bwd(d), 0.0, st);
+  auto kf_both = [&](PassCall& pc, hipStream_t on) -> int {      // two kernels: every expert's BN1 / LayerNorm part, then the cross-modal experts' hop-2 block
+    const int rc = kf_pre_small_bwd(pc, on);
+    if (rc) return rc;
+    ps_.relabel("k_pre_small_bwd", bytes_pre_small_bwd_fast(d));
+    if (d.KL) { ps_.next("k_pre_lat_bwd", true, bytes_pre_lat_bwd_fast(d)); AVMOE_TRY(kf_pre_lat_bwd(pc, on)); }
+    return OK;
+  };
+  AVMOE_TRY(try_forms(c, st, kfs_pre_bwd, kf_both, kg_pre_small_bwd, kt_pre_small_bwd_form));
+  if (c.streamed()) ps_.relabel("k_pre_bwd (stream)", bytes_pre_bwd_stream(d));
+  if (c.ran == PASS_STREAM || c.ran == PASS_FAST) ps_.next("k_pre_bwd_finalize", false, 0.0);
+  return k_pre_small_bwd_finalize(c.pl, c.saved, c.scratch, c.prm, grads, st);
 }
 
 }  // namespace avmoe

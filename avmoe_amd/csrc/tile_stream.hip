@@ -17,11 +17,12 @@
 //     scalars are put into the LDS by the prologue.
 // scripts/hbm_probe.hip measured the memory side of these passes (64-byte segments, 2 reads : 1 write) at 5.6 TB/s with one block per
 // CU against 4.3 - 4.5 with 1024 - 4096 blocks; the register-resident kernels reach 3.3 - 4.2.
-#include "kernels.h"
+#include "pass.h"
 #include "device_utils.h"
 #include "stream_isa.h"
 #include "prof.h"
 #include <algorithm>
+#include <type_traits>
 
 #ifndef KFS_AUX
 #define KFS_AUX 0              // cache policy of the ring's loads (common.h: 2 = non-temporal)
@@ -1377,143 +1378,100 @@ int launch_prb(const SPreBArgs& a, int gx, const Plan& pl, char* saved, char* sc
   return OK;
 }
 
-FastDims make_fd_s(const Dims& d, int per) {
-  FastDims t;
-  t.S = d.S; t.N = d.N; t.C = d.C; t.El = d.El; t.KL = d.KL; t.KLT = d.KLT; t.KLp = d.KLp; t.KPp = d.KPp; t.NT = d.NT; t.per = per; t.aL = d.aL;
-  return t;
+// the kernels are built for 2, 3 and 4 experts (tile_fast_shape): f(std::integral_constant<int, E>{})
+template <class F> auto by_experts(int E, F&& f) {
+  if (E == 4) return f(std::integral_constant<int, 4>{});
+  if (E == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
 }
-
-}  // namespace
 
 // Sites the streaming form serves: the tuned shape in bf16 from 2048 tokens on.  (Round 6 first drew the line at 32 768 tokens -- a persistent
 // block amortises its prologue over its range -- but measured at the reference's batch of 2 clips, 20 480 / 3920 tokens, every pass is as
 // fast or faster in this form too: mid_bwd 28.6 -> 25.0 us, post_small 19.8 -> 17.0, pre_small_bwd + pre_lat_bwd 19.7 + 19.7 -> 33.8,
 // post_small_bwd + Gram 33.6 + 16.0 -> 39.1; 1.615 -> 1.567 ms of kernel time per pair-step and four launches less.)
-bool tile_stream_ok(const Dims& d) {
+bool stream_ok(const Dims& d) {
   const Switches& sw = switches();                    // (include/avmoe.h: avmoe_test_hooks -- small test shapes through these kernels / the A/B against tile_fast.hip)
   return tile_fast_ok(d) && d.bf16 && d.zsz == 2 && (d.NT >= 2048 || sw.hook(HOOK_KFS_FORCE)) && !sw.hook(HOOK_KFS_OFF);
 }
 
-static bool psf_geom(const Dims& d, int* gx, int* nfr, int* per) {
+// launch geometry of the streaming kernels: persistent blocks (one per CU at most, gx_cap at most), the frames a block's range of
+// virtual blocks can touch; false when the streaming form does not serve the site or there is no device to ask
+struct SGeom { int bps, nvb, gx, nfr; };
+bool stream_geom(const Dims& d, SGeom* g, int gx_cap = 1 << 30) {
   const int cus = cu_count();
-  if (cus <= 0) return false;
-  const int bps = d.nblk_tok / d.S;
-  *gx = std::min(cus, d.nblk_tok);
-  *nfr = cdiv(cdiv(d.nblk_tok, *gx) + 1, bps) + 1;
-  *per = (int)round_up(cdiv(d.N, bps), 16);
-  const size_t lds = d.E == 4 ? psf_lds<4>(*nfr, *per) : d.E == 2 ? psf_lds<2>(*nfr, *per) : psf_lds<3>(*nfr, *per);
-  return lds <= 160 * 1024;
+  if (!stream_ok(d) || cus <= 0) return false;
+  g->bps = d.nblk_tok / d.S; g->nvb = d.nblk_tok;
+  g->gx = std::min(std::min(cus, g->nvb), gx_cap);
+  g->nfr = cdiv(cdiv(g->nvb, g->gx) + 1, g->bps) + 1;
+  return true;
 }
-bool kfs_serves_post_small(const Dims& d) { int a, b, c; return tile_stream_ok(d) && psf_geom(d, &a, &b, &c); }
-// 0 = launched, 1 = not served (the caller runs tile_fast.hip's kernel), < 0 error
-int kfs_post_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  if (!kfs_serves_post_small(d)) return 1;
-  int gx, nfr, per;
-  psf_geom(d, &gx, &nfr, &per);
+constexpr size_t LDS_MAX = 160 * 1024;
+
+}  // namespace
+
+int kfs_post_small(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d;
+  SGeom gm;
   SPostArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
-  a.t = make_fd_s(d, per); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
-  a.bps = d.nblk_tok / d.S; a.nvb = d.nblk_tok; a.nfr = nfr;
-  if (d.E == 4) return launch_psf<4>(a, gx, pl, saved, st);
-  if (d.E == 2) return launch_psf<2>(a, gx, pl, saved, st);
-  return launch_psf<3>(a, gx, pl, saved, st);
+  a.t = make_fd(d);
+  if (!stream_geom(d, &gm) || by_experts(d.E, [&](auto E) { return psf_lds<E()>(gm.nfr, a.t.per); }) > LDS_MAX) return 1;
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
+  a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w; a.ln_eps = d.ln_eps;
+  a.bps = gm.bps; a.nvb = gm.nvb; a.nfr = gm.nfr;
+  return launched(c, PASS_STREAM, by_experts(d.E, [&](auto E) { return launch_psf<E()>(a, gm.gx, pl, c.saved, st); }));
 }
 
 // (cross-modal experts need the fused hop-2 logits of the down projection's pass: Dims::fuse_l2; no x + g xr experts)
-bool kfs_serves_pre_small(const Dims& d) {
-  if (!tile_stream_ok(d) || d.nxn || (d.El > 0 && !d.fuse_l2) || cu_count() <= 0) return false;
-  const size_t lds = d.E == 4 ? prs_lds<4>(d.El) : d.E == 2 ? prs_lds<2>(d.El) : prs_lds<3>(d.El);
-  return lds <= 160 * 1024;
-}
-// 0 = launched, 1 = not served (the caller runs tile_fast.hip's kernel), < 0 error
-int kfs_pre_small(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  if (!kfs_serves_pre_small(d)) return 1;
-  const int bps = d.nblk_tok / d.S;
+int kfs_pre_small(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d;
+  SGeom gm;
+  if (!stream_geom(d, &gm) || d.nxn || (d.El > 0 && !d.fuse_l2) || by_experts(d.E, [&](auto E) { return prs_lds<E()>(d.El); }) > LDS_MAX) return 1;
   SPreArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; }
-  a.t = make_fd_s(d, (int)round_up(cdiv(d.N, bps), 16)); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps; a.bps = bps; a.nvb = d.nblk_tok;
-  a.L2g = d.El > 0 ? (const float*)(scratch + pl.o_L2g) : nullptr; a.L2w = d.El > 0 ? (float*)(saved + pl.o_L2) : nullptr;
-  const int gx = std::min(cu_count(), a.nvb);
-  if (d.E == 4) return launch_prs<4>(a, gx, pl, saved, scratch, st);
-  if (d.E == 2) return launch_prs<2>(a, gx, pl, saved, scratch, st);
-  return launch_prs<3>(a, gx, pl, saved, scratch, st);
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e);
+  a.t = make_fd(d); a.ln_before = d.ln_before; a.ln_eps = d.ln_eps; a.bps = gm.bps; a.nvb = gm.nvb;
+  a.L2g = d.El > 0 ? (const float*)(c.scratch + pl.o_L2g) : nullptr; a.L2w = d.El > 0 ? (float*)(c.saved + pl.o_L2) : nullptr;
+  return launched(c, PASS_STREAM, by_experts(d.E, [&](auto E) { return launch_prs<E()>(a, gm.gx, pl, c.saved, c.scratch, st); }));
 }
 
-// pre_small_bwd + the cross-modal experts' hop-2 block in one pass
-bool kfs_serves_pre_bwd(const Dims& d) {
-  if (!tile_stream_ok(d) || d.nxn || cu_count() <= 0) return false;
-  const int per = (int)round_up(cdiv(d.N, d.nblk_tok / d.S), 16);
-  const size_t lds = d.E == 4 ? prb_lds<4>(d.El, per) : d.E == 2 ? prb_lds<2>(d.El, per) : prb_lds<3>(d.El, per);
-  return lds <= 160 * 1024;
-}
-// 0 = launched (both kf_pre_small_bwd's and kf_pre_lat_bwd's work), 1 = not served, < 0 error
-int kfs_pre_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st) {
-  const Dims& d = pl.d;
-  if (!kfs_serves_pre_bwd(d)) return 1;
-  const int bps = d.nblk_tok / d.S;
+// pre_small_bwd + the cross-modal experts' hop-2 block in one pass (both kf_pre_small_bwd's and kf_pre_lat_bwd's work)
+int kfs_pre_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d; char* saved = c.saved; char* scratch = c.scratch;
+  SGeom gm;
   SPreBArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.glat.p[e] = prm.e[e].gate_lat; a.lat_of_e[e] = d.lat_of_e[e]; }
-  a.t = make_fd_s(d, (int)round_up(cdiv(d.N, bps), 16)); a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training;
-  a.bps = bps; a.nvb = d.nblk_tok;
+  a.t = make_fd(d);
+  if (!stream_geom(d, &gm) || d.nxn || by_experts(d.E, [&](auto E) { return prb_lds<E()>(d.El, a.t.per); }) > LDS_MAX) return 1;
+  a.glat = c.x.glat; put(a.lat_of_e, c.x.lat_of_e);
+  a.ln_before = d.ln_before; a.use_bn = d.use_bn; a.bn_train = d.use_bn && d.training;
+  a.bps = gm.bps; a.nvb = gm.nvb;
   a.L2 = (const float*)(saved + pl.o_L2); a.TT = (const float*)(saved + pl.o_TT); a.TW = (const float*)(saved + pl.o_TW); a.Tsum = (const float*)(saved + pl.o_Tsum);
   a.ain = (const unsigned short*)(saved + pl.o_a); a.aw = (unsigned short*)(scratch + pl.o_aw); a.ag = (unsigned short*)(scratch + pl.o_ag);
   a.dtbp = (float*)(scratch + pl.o_dtbp);
-  const int gx = std::min(cu_count(), a.nvb);
-  if (d.E == 4) return launch_prb<4>(a, gx, pl, saved, scratch, st);
-  if (d.E == 2) return launch_prb<2>(a, gx, pl, saved, scratch, st);
-  return launch_prb<3>(a, gx, pl, saved, scratch, st);
+  return launched(c, PASS_STREAM, by_experts(d.E, [&](auto E) { return launch_prb<E()>(a, gm.gx, pl, saved, scratch, st); }));
 }
 
-bool kfs_serves_mid_bwd(const Dims& d) { return tile_stream_ok(d) && cu_count() > 0; }
-// 0 = launched, 1 = not served (the caller runs tile_fast.hip's kernel), < 0 error
-int kfs_mid_bwd(const Plan& pl, char* saved, char* scratch, hipStream_t st) {
-  const Dims& d = pl.d;
-  if (!kfs_serves_mid_bwd(d)) return 1;
-  const int bps = d.nblk_tok / d.S;
-  SMidBArgs a;
-  for (int e = 0; e < MAX_E; ++e) a.relu_of_e[e] = d.relu_of_e[e];
-  a.t = make_fd_s(d, (int)round_up(cdiv(d.N, bps), 16)); a.moments = d.use_bn && d.training; a.bps = bps; a.nvb = d.nblk_tok;
-  const int gx = std::min(cu_count(), a.nvb);
-  if (d.E == 4) return launch_mdb<4>(a, gx, pl, saved, scratch, st);
-  if (d.E == 2) return launch_mdb<2>(a, gx, pl, saved, scratch, st);
-  return launch_mdb<3>(a, gx, pl, saved, scratch, st);
-}
-
-// launch geometry of the streaming kernels: persistent blocks, frames a block's range of virtual blocks can touch
-struct SGeom { int bps, nvb, gx, nfr; };
-static bool psb_geom(const Dims& d, SGeom* g) {
-  const int cus = cu_count();
-  if (cus <= 0) return false;
-  const int ns = d.E == 3 ? 2 : 8 / d.E;
-  g->bps = d.nblk_tok / d.S; g->nvb = d.nblk_tok;
-  g->gx = std::min(std::min(cus, g->nvb), GRAM_SLABS / ns);
-  g->nfr = cdiv(cdiv(g->nvb, g->gx) + 1, g->bps) + 1;
-  const size_t lds = d.E == 4 ? psb_lds<4>(g->nfr) : d.E == 2 ? psb_lds<2>(g->nfr) : psb_lds<3>(g->nfr);
-  return lds <= 160 * 1024;
-}
-// (with LayerNorm-post it also leaves dGq, the weighted Gram products: the caller skips gram.hip's pass)
-bool kfs_serves_post_small_bwd(const Dims& d, int dap16) {
-  SGeom g;
-  return tile_stream_ok(d) && dap16 && d.gram64 && psb_geom(d, &g);
-}
-
-// 0 = launched, 1 = not served (the caller runs tile_fast.hip's kernel), < 0 error
-int kfs_post_small_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st, int dap16) {
-  const Dims& d = pl.d;
-  if (!kfs_serves_post_small_bwd(d, dap16)) return 1;
+int kfs_mid_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d;
   SGeom gm;
-  if (!psb_geom(d, &gm)) { set_last_error("post_small_bwd: device query"); return ERR_LAUNCH; }
-  const int bps = gm.bps, gx = gm.gx;
+  if (!stream_geom(d, &gm)) return 1;
+  SMidBArgs a;
+  put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d); a.moments = d.use_bn && d.training; a.bps = gm.bps; a.nvb = gm.nvb;
+  return launched(c, PASS_STREAM, by_experts(d.E, [&](auto E) { return launch_mdb<E()>(a, gm.gx, pl, c.saved, c.scratch, st); }));
+}
+
+// The split dApost of a site with the Gram-fused mode (gram.hip); with LayerNorm-post it also leaves dGq, the weighted Gram products, and
+// the caller skips gram.hip's pass.  (one slab of Gram partials per block and tile slot)
+int kfs_post_small_bwd(PassCall& c, hipStream_t st) {
+  const Plan& pl = c.pl; const Dims& d = pl.d;
+  SGeom gm;
+  if (!c.dap16 || !d.gram64 || !stream_geom(d, &gm, GRAM_SLABS / (d.E == 3 ? 2 : 8 / d.E)) ||
+      by_experts(d.E, [&](auto E) { return psb_lds<E()>(gm.nfr); }) > LDS_MAX) return 1;
   SPostBArgs a;
-  for (int e = 0; e < MAX_E; ++e) { a.gate.p[e] = prm.e[e].gate; a.relu_of_e[e] = d.relu_of_e[e]; }
-  a.t = make_fd_s(d, (int)round_up(cdiv(d.N, bps), 16)); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
-  a.bps = bps; a.nvb = gm.nvb; a.nfr = gm.nfr;
-  a.dApx = (const float*)(scratch + pl.o_dApx); a.dapw = d.E * d.dgp; a.gpart = (float*)(scratch + pl.o_gpartT);
-  if (d.E == 4) return launch_psb<4>(a, gx, pl, saved, scratch, st);
-  if (d.E == 2) return launch_psb<2>(a, gx, pl, saved, scratch, st);
-  return launch_psb<3>(a, gx, pl, saved, scratch, st);
+  a.gate = c.x.gate; put(a.relu_of_e, c.x.relu_of_e);
+  a.t = make_fd(d); a.ln_post = d.ln_post; a.use_gate = d.use_gate && !d.gate_w;
+  a.bps = gm.bps; a.nvb = gm.nvb; a.nfr = gm.nfr;
+  a.dApx = (const float*)(c.scratch + pl.o_dApx); a.dapw = d.E * d.dgp; a.gpart = (float*)(c.scratch + pl.o_gpartT);
+  return launched(c, PASS_STREAM, by_experts(d.E, [&](auto E) { return launch_psb<E()>(a, gm.gx, pl, c.saved, c.scratch, st); }));
 }
 
 }  // namespace avmoe

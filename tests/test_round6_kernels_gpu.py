@@ -4,7 +4,7 @@ csrc/tile_stream.hip runs the bottleneck-space passes of csrc/tile_fast.hip with
 LDS rings filled by direct global -> LDS loads, counted waits) and the SAME per-token arithmetic: per-token outputs must agree bit for bit
 or to the last bf16 bit, sums over tokens to fp32 summation order.  A mis-counted wait (a tile read before it landed), a wrong ring slot or a
 ragged tile that reads the wrong rows shows up as an O(1) error here where the bf16-vs-oracle budget (1e-2) could hide it.  The hooks
-(include/avmoe.h: avmoe_test_hooks) lift the 32 768-token threshold / switch the streaming form off.
+(include/avmoe.h: avmoe_test_hooks) lift the 2048-token threshold / switch the streaming form off.
 """
 import pytest
 import torch
