@@ -42,6 +42,11 @@ class OptEma(C.Structure):
     _fields_ = [("decay", C.c_float), ("warmup", C.c_float)]
 
 
+class OptBuffer(C.Structure):
+    """avmoe_opt_buffer: one averaged buffer (BatchNorm running statistics) with its shadow; a record of the buffer table"""
+    _fields_ = [("buffer", C.c_void_p), ("shadow", C.c_void_p), ("n", C.c_int64)]
+
+
 class OptReportHeader(C.Structure):
     """avmoe_opt_report_header: what precedes the per-range norms in a report buffer"""
     _fields_ = [("first_nonfinite", C.c_int32), ("n_ranges", C.c_int32), ("reserved", C.c_int32 * 2)]
@@ -151,6 +156,14 @@ def declare(L):
             L.avmoe_opt_report_bytes.restype, L.avmoe_opt_report_bytes.argtypes = C.c_size_t, [C.c_int32]
             L.avmoe_opt_grad_norm_report.restype = C.c_int
             L.avmoe_opt_grad_norm_report.argtypes = norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma), C.c_void_p]
+    if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
+        L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
+        L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]
+        for name, args in (("buffer_table_build", [C.POINTER(OptBuffer), C.c_int32, C.c_void_p, C.c_size_t]),
+                           ("ema_buffers", [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+                           ("swap_buffers", [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])):
+            fn = getattr(L, "avmoe_opt_" + name)
+            fn.restype, fn.argtypes = C.c_int, args
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

@@ -27,12 +27,17 @@ __device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g,
   p -= ((lr / bc1) * m) / (sqrtf(v) / bc2_sqrt + eps);
 }
 
+// One step of an exponential moving average, written ONCE for the parameter averages (ema_elem below, inside kk_opt_adam) and the buffer
+// averages (kk_opt_ema_buffers): -> d * avg + (1 - d) * x.  (1 - d) and the product are rounded, then one fused multiply-add; contraction
+// is off so that no caller's surroundings decide how it fuses.
+__device__ __forceinline__ float ema_next(float avg, float x, float d) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(d, avg, (1.f - d) * x);
+}
+
 // The weight average of one element (include/avmoe.h, AVMOE_OPT_EMA): ema = d * ema + (1 - d) * p with the parameter's NEW value.  Spelled
 // like the moments above, for the same reason: the 16-byte body and the scalar tail must round alike.
-__device__ __forceinline__ void ema_elem(float& e, float p, float d) {
-#pragma clang fp contract(off)
-  e = __builtin_fmaf(d, e, (1.f - d) * p);
-}
+__device__ __forceinline__ void ema_elem(float& e, float p, float d) { e = ema_next(e, p, d); }
 
 // elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail.
 // EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register, with decay d

@@ -15,6 +15,10 @@
 // and one launch beside the step --
 //   kk_opt_swap                            exchanges every range's parameters with their averages (evaluation with the averaged weights,
 //                                          and back)
+// and, for tensors that cannot move into the flat buckets (BatchNorm running statistics: buffers at their own addresses, possibly only
+// 4-byte aligned), a table of {buffer, shadow, n} records of its own with one launch per step and one beside it --
+//   kk_opt_ema_buffers                     behind the update: shadow = d shadow + (1 - d) buffer with the state block's d and skip flag
+//   kk_opt_swap_buffers                    exchanges every buffer with its shadow, beside kk_opt_swap
 // The per-range norms are a kernel of their own, next to finalize, and not a part of it: finalize is ONE block whose additions define the
 // bits of total_norm, and a model has thousands of ranges -- a wave per range over many blocks finishes them in the time finalize takes,
 // inside finalize they would wait on one block's 256 threads and stretch the serial part of every step.  Finalize only resets the
@@ -244,6 +248,76 @@ __global__ void __launch_bounds__(256) kk_opt_swap(const void* __restrict__ tabl
   }
 }
 
+// ---- the buffer table (include/avmoe.h, "averaged buffers"): tensors that stay at their own addresses -- BatchNorm running statistics,
+// which the sites' forward kernels write in place -- each with a shadow in one flat allocation of the caller.  A table of its own beside
+// the range table: a buffer has no gradient and no moments, and it may be only 4-byte aligned, so the buffer side is accessed element by
+// element (a block's 256 threads take consecutive elements, four rounds: every access is a full coalesced line anyway).
+constexpr uint32_t OPT_BUF_MAGIC = 0x4f505442u;  // "OPTB"
+static_assert(sizeof(avmoe_opt_buffer) == 24, "buffer table layout");
+
+// What a block of a one-block-per-table-block launch serves: elements [i0, i0 + 1024) of record `rec`, clipped to its n.
+// -> false where the launch does not match the table (wrong magic, other counts, a block or record index outside it, a record without
+// elements): such a launch touches nothing.
+__device__ __forceinline__ bool opt_buffer_work(const void* __restrict__ table, int n_buffers, long n_blocks, avmoe_opt_buffer& rec, long& i0) {
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_BUF_MAGIC || h.n_ranges != n_buffers || h.n_blocks != n_blocks || (long)blockIdx.x >= h.n_blocks) return false;
+  const avmoe_opt_buffer* recs = (const avmoe_opt_buffer*)((const char*)table + sizeof(OptHeader));
+  const OptBlock b = ((const OptBlock*)(recs + h.n_ranges))[blockIdx.x];
+  if (b.range < 0 || b.range >= h.n_ranges || b.block < 0) return false;
+  rec = recs[b.range];
+  i0 = (long)b.block * OPT_BLOCK;
+  return rec.n > 0 && i0 < rec.n;
+}
+
+// shadow = d_n shadow + (1 - d_n) buffer for every element of every record, d_n and the skip flag from the state block the step's
+// finalize launch has just written.  The four loads of a thread are unconditional, at an index clamped into the record, and issued
+// before the first store; only the stores are masked (DESIGN_CURRENT.md section 3).  The buffers are only read.
+__global__ void __launch_bounds__(256) kk_opt_ema_buffers(const void* __restrict__ table, int n_buffers, long n_blocks,
+                                                          const avmoe_opt_state* __restrict__ state) {
+  if (state->skip) return;                              // a skipped step writes nothing
+  avmoe_opt_buffer r;
+  long i0;
+  if (!opt_buffer_work(table, n_buffers, n_blocks, r, i0)) return;
+  const float d = state->ema_decay;
+  const float* __restrict__ b = r.buffer;
+  float* __restrict__ s = r.shadow;
+  const long last = r.n - 1;
+  long idx[4];
+  float x[4], e[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long i = i0 + k * 256 + (long)threadIdx.x;
+    idx[k] = i < last ? i : last;
+    x[k] = b[idx[k]];
+    e[k] = s[idx[k]];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (i0 + k * 256 + (long)threadIdx.x <= last) s[idx[k]] = ema_next(e[k], x[k], d);
+}
+
+// buffer[i] <-> shadow[i] for every element of every record; the same walk
+__global__ void __launch_bounds__(256) kk_opt_swap_buffers(const void* __restrict__ table, int n_buffers, long n_blocks) {
+  avmoe_opt_buffer r;
+  long i0;
+  if (!opt_buffer_work(table, n_buffers, n_blocks, r, i0)) return;
+  float* __restrict__ b = r.buffer;
+  float* __restrict__ s = r.shadow;
+  const long last = r.n - 1;
+  long idx[4];
+  float x[4], e[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long i = i0 + k * 256 + (long)threadIdx.x;
+    idx[k] = i < last ? i : last;
+    x[k] = b[idx[k]];
+    e[k] = s[idx[k]];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (i0 + k * 256 + (long)threadIdx.x <= last) { b[idx[k]] = e[k]; s[idx[k]] = x[k]; }
+}
+
 // the instantiations, indexed by the flag bits: an option more is a template parameter more and an initialiser twice as long
 using FinalizeKernel = decltype(&kk_opt_finalize<false, false>);
 using AdamKernel = decltype(&kk_opt_adam<false, false, false>);
@@ -287,6 +361,29 @@ static int check_table_args(const char* who, const void* table, int32_t n_ranges
   if (n_ranges < 0 || n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("%s: bad range / block count", who); return ERR_BAD_ARG; }
   if (((uintptr_t)table & 15u) != 0) { set_last_error("%s: the table must be 16-byte aligned", who); return ERR_ALIGNMENT; }
   return OK;
+}
+
+// host-side validation of a buffer list -> OK and the block count, or the error
+static int check_buffers(const char* who, const avmoe_opt_buffer* buffers, int32_t n_buffers, int64_t* n_blocks) {
+  if (n_buffers < 0) { set_last_error("%s: negative buffer count %d", who, (int)n_buffers); return ERR_BAD_ARG; }
+  if (n_buffers > 0 && !buffers) { set_last_error("%s: buffers is NULL", who); return ERR_BAD_ARG; }
+  int64_t nb = 0;
+  for (int32_t i = 0; i < n_buffers; ++i) {
+    const avmoe_opt_buffer& r = buffers[i];
+    if (r.n < 0) { set_last_error("%s: buffer %d has negative length %lld", who, (int)i, (long long)r.n); return ERR_BAD_ARG; }
+    if (!r.buffer || !r.shadow) { set_last_error("%s: buffer %d has a NULL pointer", who, (int)i); return ERR_BAD_ARG; }
+    if (((uintptr_t)r.buffer & 3u) != 0) { set_last_error("%s: buffer %d is not 4-byte aligned", who, (int)i); return ERR_ALIGNMENT; }
+    if (((uintptr_t)r.shadow & 15u) != 0) { set_last_error("%s: the shadow of buffer %d is not 16-byte aligned", who, (int)i); return ERR_ALIGNMENT; }
+    if (r.n > ((int64_t)INT32_MAX - 1) * OPT_BLOCK) { set_last_error("%s: buffer %d is too long", who, (int)i); return ERR_UNSUPPORTED; }
+    nb += range_blocks(r.n);
+  }
+  if (nb > (int64_t)INT32_MAX) { set_last_error("%s: more than 2^31 blocks", who); return ERR_UNSUPPORTED; }
+  *n_blocks = nb;
+  return OK;
+}
+
+static size_t buffer_table_bytes_of(int32_t n_buffers, int64_t n_blocks) {
+  return round16(sizeof(OptHeader) + (size_t)n_buffers * sizeof(avmoe_opt_buffer) + (size_t)n_blocks * sizeof(OptBlock));
 }
 
 // the state block first: a misaligned one is a bad argument whatever the table's alignment
@@ -474,6 +571,53 @@ int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, fl
   if (n_blocks == 0) return OK;
   hipLaunchKernelGGL(kk_opt_swap, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, shadows, (int)n_ranges);
   AVMOE_CHECK_LAUNCH("opt_swap");
+  return OK;
+}
+
+size_t avmoe_opt_buffer_table_bytes(const avmoe_opt_buffer* buffers, int32_t n_buffers, int64_t* n_blocks) {
+  int64_t nb = 0;
+  if (check_buffers("avmoe_opt_buffer_table_bytes", buffers, n_buffers, &nb) != OK) return 0;
+  if (n_blocks) *n_blocks = nb;
+  return buffer_table_bytes_of(n_buffers, nb);
+}
+
+int avmoe_opt_buffer_table_build(const avmoe_opt_buffer* buffers, int32_t n_buffers, void* image, size_t image_bytes) {
+  int64_t nb = 0;
+  AVMOE_TRY(check_buffers("avmoe_opt_buffer_table_build", buffers, n_buffers, &nb));
+  if (!image) { set_last_error("avmoe_opt_buffer_table_build: image is NULL"); return ERR_BAD_ARG; }
+  const size_t need = buffer_table_bytes_of(n_buffers, nb);
+  if (image_bytes < need) { set_last_error("avmoe_opt_buffer_table_build: image of %zu bytes, %zu needed", image_bytes, need); return ERR_WORKSPACE; }
+  char* p = (char*)image;
+  memset(p, 0, need);
+  OptHeader h{OPT_BUF_MAGIC, n_buffers, nb};
+  memcpy(p, &h, sizeof h);
+  if (n_buffers > 0) memcpy(p + sizeof h, buffers, (size_t)n_buffers * sizeof(avmoe_opt_buffer));
+  char* bm = p + sizeof h + (size_t)n_buffers * sizeof(avmoe_opt_buffer);     // memcpy: the caller's image need not be aligned
+  for (int32_t i = 0; i < n_buffers; ++i)
+    for (long b = 0, e = range_blocks(buffers[i].n); b < e; ++b, bm += sizeof(OptBlock)) {
+      const OptBlock ob{i, (int32_t)b};
+      memcpy(bm, &ob, sizeof ob);
+    }
+  return OK;
+}
+
+int avmoe_opt_ema_buffers(const void* table, int32_t n_buffers, int64_t n_blocks, const avmoe_opt_state* state, void* stream) {
+  const char* who = "avmoe_opt_ema_buffers";
+  if (!state) { set_last_error("%s: NULL state", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)state & 15u) != 0) { set_last_error("%s: the state block must be 16-byte aligned", who); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_table_args(who, table, n_buffers, n_blocks));
+  if (n_blocks == 0) return OK;
+  hipLaunchKernelGGL(kk_opt_ema_buffers, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, (int)n_buffers, (long)n_blocks, state);
+  AVMOE_CHECK_LAUNCH("opt_ema_buffers");
+  return OK;
+}
+
+int avmoe_opt_swap_buffers(const void* table, int32_t n_buffers, int64_t n_blocks, void* stream) {
+  const char* who = "avmoe_opt_swap_buffers";
+  AVMOE_TRY(check_table_args(who, table, n_buffers, n_blocks));
+  if (n_blocks == 0) return OK;
+  hipLaunchKernelGGL(kk_opt_swap_buffers, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, (int)n_buffers, (long)n_blocks);
+  AVMOE_CHECK_LAUNCH("opt_swap_buffers");
   return OK;
 }
 

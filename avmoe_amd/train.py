@@ -7,7 +7,8 @@
                                Opt-in: global-norm clipping, AdamW, skipping of non-finite steps with the optimizer state on
                                the device (three launches per step for all buckets, graph-capturable); state_dict() /
                                load_state_dict() in torch.optim.Adam's format; an exponential moving average of the weights kept
-                               by the update kernel itself, swapped in for evaluation and written by `save_adapters(ema=opt)`;
+                               by the update kernel itself, swapped in for evaluation and written by `save_adapters(ema=opt)`,
+                               BatchNorm running statistics averaged and swapped with them (`ema_buffers=model`);
                                per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
@@ -18,7 +19,7 @@
                                net_trans_v3.py:560-563)
 
 Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema|_report] /
-avmoe_opt_adam_step[_ema] / avmoe_opt_swap_ema, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
+avmoe_opt_adam_step[_ema] / avmoe_opt_swap_ema, avmoe_opt_ema_buffers / avmoe_opt_swap_buffers, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
 import contextlib
@@ -165,10 +166,23 @@ class FlatAdam:
     the thread of the update launch that has just produced an element's new value p also writes ema = fma(d_n, ema, (1 - d_n) * p).
     Still three launches, capturable, and a skipped step leaves the average alone.  `ema_params` are views of the averages shaped like
     `params`; `swap_ema()` exchanges parameters and averages in one launch and `with opt.ema_weights():` does so around an evaluation;
-    `adapter_state_dict(model, ema=opt)` / `save_adapters(..., ema=opt)` write the averaged values.  NOT averaged: buffers (BatchNorm
-    running statistics stay those of the raw weights' last forward) and parameters outside the reducer.  `state_dict()` carries the
+    `adapter_state_dict(model, ema=opt)` / `save_adapters(..., ema=opt)` write the averaged values.  `state_dict()` carries the
     averages under "flat_adam" ("ema": CPU tensors in `params` order, "ema_decay", "ema_warmup"); `load_state_dict()` restores them, and
-    a dict without them re-seeds the averages from the current parameters.
+    a dict without them re-seeds the averages from the current parameters.  NOT averaged: parameters outside the reducer.
+
+    Averaged buffers.  `ema_buffers=model` (or an iterable of (name, tensor); it needs `ema_decay`) averages the model's floating-point
+    buffers -- the BatchNorm running means and variances, which an evaluation runs on -- along with the weights: timm's ModelEmaV2 on the
+    device.  The buffers stay where they are (`module._buffers[...]` is never re-bound: the sites cache those addresses and their forward
+    kernels write them in place); each has a shadow in one flat fp32 allocation, seeded from the buffer at construction.  A step is ONE
+    launch more, whatever the number of buffers (avmoe_opt_ema_buffers behind the update, same stream): it reads this step's d_n and the
+    skip flag from the state block and computes shadow = fma(d_n, shadow, (1 - d_n) * buffer) -- the parameter average's expression --
+    from the values the forward passes before this step have left.  No step-dependent host scalar, capturable; a skipped step leaves the
+    shadows alone; the buffers themselves are only read.  `swap_ema()` / `ema_weights()` exchange buffers and shadows too (a second
+    launch, in place), so an evaluation inside runs the averaged weights on averaged statistics, and `adapter_state_dict(model, ema=opt)`
+    writes the averaged value of every buffer the optimizer holds.  Integer buffers (`num_batches_tracked`) are never averaged and never
+    swapped.  `ema_buffers` are views of the shadows shaped like the buffers, `ema_buffer_names` their names; `state_dict()` carries them
+    under "flat_adam" ("ema_buffers": CPU tensors, "ema_buffer_names"), `load_state_dict()` restores them, and a dict without them
+    re-seeds the shadows from the current buffers.  Without the option the calls and launches of a step are what they were.
 
     Per-parameter gradient norms.  `report_grad_norms=True` (it selects the device path too) adds ONE launch behind the finalize launch:
     a wave per parameter adds the block sums the norm pass has left anyway, in a fixed order, and writes the parameter's gradient norm
@@ -197,14 +211,16 @@ class FlatAdam:
                  step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
                  max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
                  lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
-                 report_grad_norms: bool = False):
+                 report_grad_norms: bool = False, ema_buffers=None):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
         [0, 1), warmed up over `ema_warmup` >= 1 (1: constant decay); both are held as fp32.  report_grad_norms: every step also leaves
         each parameter's gradient norm and the index of the first non-finite one on the device (`last_param_grad_norms`,
         `first_nonfinite_param`).  Any of the six selects the device path (class docstring); with all at their defaults step() is the
-        per-bucket avmoe_adam_step path.
+        per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
+        and swap with the weights; needs `ema_decay`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
+        otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
         reference's `lr_mlp` for the classifier head vs `lr` for the adapters); parameters not listed use `lr`.  A group may also
@@ -226,6 +242,7 @@ class FlatAdam:
         self.ema_decay, self.ema_warmup = self._check_ema(ema_decay, ema_warmup)
         self._swapped = False                            # the parameters currently hold the averages (swap_ema / ema_weights)
         self.report_grad_norms = bool(report_grad_norms)
+        self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
         self._wds = []                                   # beside it: each parameter's weight decay
         lr_of, wd_of = {}, {}
@@ -287,6 +304,79 @@ class FlatAdam:
         if self.ema_decay is None:
             raise capi.AvmoeError(f"FlatAdam.{what} needs ema_decay")
 
+    def _collect_buffers(self, spec, reducer):
+        """`ema_buffers` -> [(name, tensor)] of what is averaged: contiguous fp32, on the buckets' device, not empty, one per address"""
+        if spec is None:
+            return []
+        if self.ema_decay is None:
+            raise ValueError("ema_buffers needs ema_decay: the buffers are averaged with the decay of the weight average")
+        items = spec.named_buffers() if isinstance(spec, torch.nn.Module) else spec
+        dev = reducer.buckets[0].flat.device if reducer.buckets else None
+        out, seen = [], set()
+        for name, t in items:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"ema_buffers: {name!r} is no tensor")
+            if not t.is_floating_point() or t.numel() == 0:      # counters (num_batches_tracked) are never averaged and never swapped
+                continue
+            if t.dtype != torch.float32:
+                raise ValueError(f"ema_buffers: buffer {name!r} is {t.dtype}, the average is kept in float32")
+            if not t.is_contiguous():
+                raise ValueError(f"ema_buffers: buffer {name!r} is not contiguous")
+            if dev is not None and t.device != dev:
+                raise ValueError(f"ema_buffers: buffer {name!r} is on {t.device}, the optimizer's buckets on {dev}")
+            if t.data_ptr() in seen:
+                continue
+            seen.add(t.data_ptr())
+            out.append((str(name), t))
+        return out
+
+    def _need_ema_buffers(self, what):
+        if not self._ebufs:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs ema_buffers")
+
+    @property
+    def ema_buffers(self) -> List[torch.Tensor]:
+        """the averaged buffers as DEVICE tensors shaped like the buffers, in `ema_buffer_names` order: views of the one flat shadow
+        allocation (inside `ema_weights()` they hold the raw buffers)"""
+        self._need_ema_buffers("ema_buffers")
+        return list(self._ebuf_views)
+
+    @property
+    def ema_buffer_names(self) -> List[str]:
+        """the names of the buffers the optimizer averages, as `named_buffers()` (or the caller's pairs) gave them"""
+        return [name for name, _ in self._ebufs]
+
+    def _build_buffer_table(self):
+        """the shadows (ONE flat fp32 allocation, each 16-byte aligned, seeded from the buffers) and the buffer table on the device"""
+        L = capi.lib()
+        if not hasattr(L, "avmoe_opt_swap_buffers"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks the averaged buffers (avmoe_opt_ema_buffers): rebuild it")
+        offs, total = [], 0
+        for _name, t in self._ebufs:
+            offs.append(total)
+            total += (t.numel() + 3) & ~3
+        self._ebuf_flat = torch.zeros(total, dtype=torch.float32, device=self._dev)
+        self._ebuf_views = [self._ebuf_flat[o:o + t.numel()].view_as(t) for o, (_n, t) in zip(offs, self._ebufs)]
+        recs = (cm.OptBuffer * len(self._ebufs))()
+        for r, (_name, t), v in zip(recs, self._ebufs, self._ebuf_views):
+            r.buffer, r.shadow, r.n = t.data_ptr(), v.data_ptr(), t.numel()
+        nb = C.c_int64(0)
+        nbytes = L.avmoe_opt_buffer_table_bytes(recs, len(recs), C.byref(nb))
+        if nbytes == 0:
+            capi.check(-1, "avmoe_opt_buffer_table_bytes")
+        img = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        capi.check(L.avmoe_opt_buffer_table_build(recs, len(recs), img.data_ptr(), nbytes), "avmoe_opt_buffer_table_build")
+        self._ebuf_table = torch.empty(nbytes, dtype=torch.uint8, device=self._dev)
+        self._ebuf_table.copy_(img, non_blocking=True)
+        self._ebuf_args = (self._ebuf_table.data_ptr(), len(recs), int(nb.value))      # table, n_buffers, n_blocks of both launches
+        self._ebuf_blocks = int(nb.value)
+        self._seed_buffer_shadows()
+
+    def _seed_buffer_shadows(self):
+        with torch.no_grad():
+            for v, (_name, t) in zip(self._ebuf_views, self._ebufs):
+                v.copy_(t)
+
     @property
     def ema_params(self) -> List[torch.Tensor]:
         """the averages as DEVICE tensors shaped like `params` and in that order: views of the shadow buffers (inside `ema_weights()`
@@ -303,19 +393,24 @@ class FlatAdam:
 
     def swap_ema(self):
         """Exchanges every parameter the optimizer holds with its average: ONE launch on the current stream, no copy and no
-        synchronisation.  Call it again to swap back; until then step(), state_dict() and load_state_dict() raise.  Buffers (BatchNorm
-        running statistics) are not parameters, are not averaged and stay as they are."""
+        synchronisation.  Call it again to swap back; until then step(), state_dict() and load_state_dict() raise.  With `ema_buffers` a
+        second launch exchanges the buffers (BatchNorm running statistics) with their averages, in place: no `module._buffers` entry is
+        re-bound.  Without it buffers stay as they are."""
         self._need_ema("swap_ema")
         stream = torch.cuda.current_stream(self._dev).cuda_stream
         capi.check(capi.lib().avmoe_opt_swap_ema(self._table_ptr, len(self._plist), self._n_blocks, self._shadow_ptrs.data_ptr(), stream),
                    "avmoe_opt_swap_ema")
+        if self._ebufs:
+            capi.check(capi.lib().avmoe_opt_swap_buffers(*self._ebuf_args, stream),
+                       "avmoe_opt_swap_buffers")
         self._swapped = not self._swapped
 
     @contextlib.contextmanager
     def ema_weights(self):
         """`with opt.ema_weights(): evaluate(model)` -- the model's parameters are the averages inside (swap_ema), the raw weights again
-        after it, also when the body raises.  step() inside raises.  BatchNorm running statistics are buffers, not parameters: they
-        are not averaged, so an evaluation inside sees the statistics the raw weights' forward passes left."""
+        after it, also when the body raises.  step() inside raises.  With `ema_buffers` the BatchNorm running statistics are their
+        averages inside too, and what the raw weights' forward passes left again after it; without the option they are not averaged, and
+        an evaluation inside sees the raw weights' statistics."""
         self._need_ema("ema_weights")
         self._not_swapped("ema_weights()")
         self.swap_ema()
@@ -363,6 +458,8 @@ class FlatAdam:
         self._upload_table()
         if self.ema_decay is not None:
             self._build_shadows()
+        if self._ebufs:
+            self._build_buffer_table()
         if self.report_grad_norms:
             self._build_report()
 
@@ -527,6 +624,9 @@ class FlatAdam:
             capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
                                                  self.eps, scale, self._flags & ~cm.OPT_REPORT, stream,
                                                  None if self.ema_decay is None else self._shadow_ptrs.data_ptr()), "avmoe_opt_adam_step_ema")
+            if self._ebufs:                              # one launch more: the buffers' averages, with the d_n and skip flag finalize has left
+                capi.check(L.avmoe_opt_ema_buffers(*self._ebuf_args, self._state_ptr, stream),
+                           "avmoe_opt_ema_buffers")
             return
         for s in self.state:
             for (o, e, r, wd) in s["ranges"]:
@@ -565,6 +665,8 @@ class FlatAdam:
             extra["lr_schedule"] = dataclasses.asdict(self.lr_schedule)
         if self.ema_decay is not None:
             extra.update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema=[e.detach().cpu().clone() for e in self._ema_views])
+        if self._ebufs:
+            extra.update(ema_buffers=[v.detach().cpu().clone() for v in self._ebuf_views], ema_buffer_names=self.ema_buffer_names)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
             extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
@@ -576,7 +678,9 @@ class FlatAdam:
         path options stay what the constructor was given (the saved ones are informative), unknown keys are ignored.  A count or shape
         mismatch raises ValueError naming the parameter index.  With `ema_decay`: saved averages ("ema", with "ema_decay" / "ema_warmup",
         which replace the constructor's) are restored; a dict without them re-seeds the averages from the CURRENT parameters, so load the
-        model first.  Without `ema_decay` saved averages are ignored."""
+        model first.  Without `ema_decay` saved averages are ignored.  With `ema_buffers`: saved buffer averages ("ema_buffers", matched by
+        position, "ema_buffer_names" informative) are restored -- a count or shape mismatch raises ValueError naming the buffer -- and a
+        dict without them re-seeds the shadows from the CURRENT buffers; without the option saved ones are ignored."""
         self._not_swapped("load_state_dict()")
         saved_groups, own_groups = sd["param_groups"], self._groups()
         if len(saved_groups) != len(own_groups):
@@ -621,6 +725,14 @@ class FlatAdam:
                     raise ValueError(f"parameter index {i}: ema has shape {tuple(e.shape)}, the parameter {tuple(p.shape)}")
             ema_consts = self._check_ema(self.ema_decay if extra.get("ema_decay") is None else extra["ema_decay"],
                                          self.ema_warmup if extra.get("ema_warmup") is None else extra["ema_warmup"])
+        saved_bufs = extra.get("ema_buffers") if self._ebufs else None
+        if saved_bufs is not None:
+            names = self.ema_buffer_names
+            if len(saved_bufs) != len(names):
+                raise ValueError(f"state dict has {len(saved_bufs)} averaged buffers, this optimizer {len(names)} (first: {names[0]!r})")
+            for name, e, (_n, t) in zip(names, saved_bufs, self._ebufs):
+                if tuple(e.shape) != tuple(t.shape):
+                    raise ValueError(f"buffer {name!r}: the saved average has shape {tuple(e.shape)}, the buffer {tuple(t.shape)}")
         with torch.no_grad():
             if not todo:
                 for s in self.state:
@@ -666,6 +778,12 @@ class FlatAdam:
                         for s in self.state:
                             s["e"].copy_(s["p"])
                     self._views["ema_decay"].fill_(self.ema_decay_at(applied, self.ema_decay, self.ema_warmup) if applied > 0 else 0.0)
+                if self._ebufs:
+                    if saved_bufs is not None:
+                        for view, e in zip(self._ebuf_views, saved_bufs):
+                            view.copy_(e.to(torch.float32))
+                    else:                                 # no buffer averages in the dict: start them from the buffers as they are now
+                        self._seed_buffer_shadows()
                 self._upload_table()
             else:
                 self.t = applied                          # the plain path's bias correction counts self.t
@@ -742,16 +860,24 @@ def router_aux_total(sites, z_weight: float = 0.0, balance_weight: float = 0.0) 
 
 def adapter_state_dict(model: torch.nn.Module, substrings=("adapter",), ema: Optional[FlatAdam] = None) -> Dict[str, torch.Tensor]:
     """The adapter / router entries of model.state_dict() (keys containing 'adapter': `*_adapter_blocks_p{1,2}.*`).
-    ema: a FlatAdam built with `ema_decay` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), everything
-    else (buffers such as BatchNorm running statistics, parameters outside the optimizer) as it is.  The model is not modified, and the
-    result loads with `load_adapters` like any other."""
-    src = {}
+    ema: a FlatAdam built with `ema_decay` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), and with
+    `ema_buffers` every buffer it holds (BatchNorm running statistics) with its averaged value too (`opt.ema_buffers`); everything else
+    (other buffers, parameters outside the optimizer) as it is.  The model is not modified, and the result loads with `load_adapters`
+    like any other."""
+    src, bsrc = {}, {}
     if ema is not None:
-        if not ema._swapped:                             # inside ema_weights() the parameters ARE the averages already
+        if not ema._swapped:                             # inside ema_weights() the parameters and buffers ARE the averages already
             src = {id(p): e for p, e in zip(ema.params, ema.ema_params)}
+            if ema._ebufs:                               # by address and shape: state_dict() hands out the buffer tensors themselves
+                bsrc = {(t.data_ptr(), tuple(t.shape)): e for (_name, t), e in zip(ema._ebufs, ema.ema_buffers)}
         else:
             ema.ema_params                               # (raises without ema_decay)
-    return {k: src.get(id(v), v).detach().cpu().clone() for k, v in model.state_dict(keep_vars=True).items() if any(s in k for s in substrings)}
+
+    def pick(v):
+        if id(v) in src:
+            return src[id(v)]
+        return bsrc.get((v.data_ptr(), tuple(v.shape)), v) if bsrc and v.dtype == torch.float32 else v
+    return {k: pick(v).detach().cpu().clone() for k, v in model.state_dict(keep_vars=True).items() if any(s in k for s in substrings)}
 
 
 def save_adapters(model: torch.nn.Module, path: str, substrings=("adapter",), ema: Optional[FlatAdam] = None):

@@ -437,7 +437,8 @@ int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blo
  * range and is not touched): call it once to evaluate with the averaged weights and once more to go on training.
  * Errors (before any launch): AVMOE_ERR_BAD_ARG for the flag with ema == NULL, decay outside [0, 1) or NaN, warmup < 1, NaN or
  * infinite, shadows == NULL; AVMOE_ERR_ALIGNMENT for a shadow array that is not 8-byte aligned; and everything the older entry points
- * refuse.  Not covered: tensors that are no range of the table (BatchNorm running statistics, parameters the optimizer does not hold). */
+ * refuse.  Tensors that are no range of the table: BatchNorm running statistics are averaged by avmoe_opt_ema_buffers below; parameters
+ * the optimizer does not hold are not covered.                                                                                        */
 typedef struct avmoe_opt_ema {
   float decay;                /* in [0, 1): the decay the average settles at */
   float warmup;               /* W >= 1 */
@@ -449,6 +450,36 @@ int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_block
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
                             float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE */);
 int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, float* const* shadows /* DEVICE */, void* stream);
+
+/* Averaged buffers (added under ABI 11 like the blocks above; found by symbol): the floating-point state of a model that is no parameter
+ * -- BatchNorm running mean and variance -- averaged and swapped together with the weights, so that an evaluation with the averaged
+ * weights runs on statistics that belong to them.  Such a tensor stays where it is (the site kernels write it in place through cached
+ * addresses) and may be only 4-byte aligned, so it cannot be a range of the range table: the BUFFER TABLE is a second table, one
+ * avmoe_opt_buffer per tensor -- the buffer (DEVICE, n fp32, 4-byte aligned), its shadow (DEVICE, n fp32, 16-byte aligned; the caller
+ * keeps all shadows in one flat allocation and initialises them, usually to the buffers) and n -- followed by a block -> record map, one
+ * block per 1024 elements of one buffer.  avmoe_opt_buffer_table_bytes returns the bytes of the image (a multiple of 16; 0 and an error
+ * string on a bad list) and the block count; avmoe_opt_buffer_table_build writes the image into HOST memory of the caller, who copies
+ * it to the device (16-byte aligned) once.  Image layout: {uint32 magic; int32 n_buffers; int64 n_blocks}, the records, then n_blocks
+ * pairs {int32 record; int32 block inside the record}, sorted by record.
+ * avmoe_opt_ema_buffers is ONE launch over all buffers, to be called behind avmoe_opt_adam_step_ema of a step with AVMOE_OPT_EMA, on the
+ * same stream: it reads `skip` and `ema_decay` from the state block that step's finalize launch has written and computes
+ *     shadow = fma(d, shadow, (1 - d) * buffer)       (fp32; the expression of the parameter average, one helper in csrc/adam_elem.h)
+ * for every element; a skipped step writes nothing, and the buffers themselves are only read.  avmoe_opt_swap_buffers exchanges
+ * buffer[i] and shadow[i] for every element in one launch, in place: call it beside avmoe_opt_swap_ema.  No host scalar changes from
+ * step to step, so both replay from a captured graph.  A launch whose n_buffers / n_blocks are not its table's touches nothing.
+ * Errors (before any launch): AVMOE_ERR_BAD_ARG for a NULL table or state, a negative count, a state block that is not 16-byte aligned,
+ * (table functions) a NULL pointer or negative length in a record; AVMOE_ERR_ALIGNMENT for a table that is not 16-byte aligned,
+ * (table functions) a buffer that is not 4-byte or a shadow that is not 16-byte aligned; AVMOE_ERR_WORKSPACE for an image too small.  */
+typedef struct avmoe_opt_buffer {
+  float* buffer;              /* DEVICE: the tensor itself, read by the average, exchanged by the swap */
+  float* shadow;              /* DEVICE: its average */
+  int64_t n;                  /* elements */
+} avmoe_opt_buffer;
+
+size_t avmoe_opt_buffer_table_bytes(const avmoe_opt_buffer* buffers /* HOST */, int32_t n_buffers, int64_t* n_blocks /* HOST, or NULL */);
+int avmoe_opt_buffer_table_build(const avmoe_opt_buffer* buffers /* HOST */, int32_t n_buffers, void* image /* HOST */, size_t image_bytes);
+int avmoe_opt_ema_buffers(const void* table, int32_t n_buffers, int64_t n_blocks, const avmoe_opt_state* state, void* stream);
+int avmoe_opt_swap_buffers(const void* table, int32_t n_buffers, int64_t n_blocks, void* stream);
 
 /* The gradient norm of every range and the first range whose norm is not finite (added under ABI 11 like the blocks above; found by
  * symbol): which parameter made a step skip, or whose gradient is out of line with its neighbours', without a .norm() per tensor.  The

@@ -10,6 +10,10 @@
 --ema              (device mode) FlatAdam(ema_decay=0.999): the update launch also advances the weight average -- still three launches
 --ema-foreach      (device mode) the same average kept OUTSIDE the optimizer: the step without it, then torch._foreach_lerp_ over the
                    parameter views with the decay computed on the host (FlatAdam.ema_decay_at), what a user had to write before --ema
+--ema-buffers      (with --ema) FlatAdam(ema_buffers=model): the model's BatchNorm running statistics are averaged too -- one launch more
+                   (`kk_opt_ema_buffers`), whatever the number of buffers
+--ema-buffers-foreach  (with --ema) the same buffer average kept OUTSIDE the optimizer: the --ema step, then torch._foreach_lerp_ over the
+                   model's fp32 buffers with the decay computed on the host, what a user had to write before --ema-buffers
 --report           (device mode) FlatAdam(report_grad_norms=True): one more launch behind finalize writes every parameter's gradient norm
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
@@ -52,6 +56,8 @@ def main():
     ap.add_argument("--schedule-upload", action="store_true")
     ap.add_argument("--ema", action="store_true")
     ap.add_argument("--ema-foreach", action="store_true")
+    ap.add_argument("--ema-buffers", action="store_true")
+    ap.add_argument("--ema-buffers-foreach", action="store_true")
     ap.add_argument("--report", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
@@ -64,6 +70,10 @@ def main():
         ap.error("--report goes with --mode device")
     if a.ema and a.ema_foreach:
         ap.error("--ema and --ema-foreach are the two sides of one comparison")
+    if (a.ema_buffers or a.ema_buffers_foreach) and not a.ema:
+        ap.error("--ema-buffers / --ema-buffers-foreach go with --ema")
+    if a.ema_buffers and a.ema_buffers_foreach:
+        ap.error("--ema-buffers and --ema-buffers-foreach are the two sides of one comparison")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
@@ -81,6 +91,10 @@ def main():
         kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
     if a.report:
         kw["report_grad_norms"] = True
+    if a.ema_buffers:
+        kw["ema_buffers"] = model
+    buffers = [b for _, b in model.named_buffers() if b.dtype == torch.float32 and b.numel() > 0]
+    buffer_shadows = [b.detach().clone() for b in buffers] if a.ema_buffers_foreach else None
     opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
@@ -100,6 +114,8 @@ def main():
         opt.step()
         if a.ema_foreach:                                # ema += (1 - d) * (p - ema), d of this step from the host's count of steps
             torch._foreach_lerp_(shadows, views, 1.0 - FlatAdam.ema_decay_at(opt.t, ema_decay, ema_warmup))
+        if a.ema_buffers_foreach:
+            torch._foreach_lerp_(buffer_shadows, buffers, 1.0 - FlatAdam.ema_decay_at(opt.t, ema_decay, ema_warmup))
 
     for _ in range(a.warmup):
         step()
@@ -120,6 +136,11 @@ def main():
     if a.ema:
         extra["last_ema_decay"] = float(opt.last_ema_decay.item())
         extra["want_ema_decay"] = FlatAdam.ema_decay_at(total, ema_decay, ema_warmup)
+    if a.ema_buffers or a.ema_buffers_foreach:
+        extra["ema_buffers"] = "device" if a.ema_buffers else "torch._foreach_lerp_ per step"
+        avg = opt.ema_buffers if a.ema_buffers else buffer_shadows
+        extra["buffers"], extra["buffer_elements"] = len(avg), sum(b.numel() for b in avg)
+        extra["buffer_blocks"] = sum((b.numel() + 1023) // 1024 for b in avg)
     if a.report:
         extra["report"] = "device"
         extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())
