@@ -129,6 +129,11 @@ def declare(L):
     # the site entry points found by symbol (added under ABI 11: dprobs and dOut == NULL, top-k gating, the router auxiliary losses), keyed on the
     # newest one; avmoe_site_aux: what the facade asks once (a development A/B may load an older library through AVMOE_LIB)
     L.avmoe_site_aux = hasattr(L, "avmoe_moe_backward_aux")
+    # avmoe_moe_desc.bn_momentum < 0 = torch's momentum=None (found by symbol, ABI 11: an older library would take -1.0 as a number)
+    L.avmoe_bn_cumulative = hasattr(L, "avmoe_bn_cumulative_supported")
+    if L.avmoe_bn_cumulative:
+        L.avmoe_bn_cumulative_supported.restype = C.c_int
+        L.avmoe_bn_cumulative = bool(L.avmoe_bn_cumulative_supported())
     if L.avmoe_site_aux:
         head = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.POINTER(MoePtrs), C.c_void_p]
         L.avmoe_moe_forward_topk.restype, L.avmoe_moe_forward_topk.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 7

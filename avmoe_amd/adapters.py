@@ -661,10 +661,31 @@ class MoEAdapter(nn.Module):
         bn = self.multimodal_experts[0].bn1 if (self.use_bn and self.num_multimodal_experts) else \
             (self.singlemodal_experts[0].bn1 if self.use_bn else None)
         d.bn_eps = bn.eps if bn is not None else 1e-5
-        d.bn_momentum = bn.momentum if bn is not None else 0.1
+        d.bn_momentum = self._bn_momentum() if bn is not None else 0.1
         experts = list(self.multimodal_experts) + list(self.singlemodal_experts)
         d.ln_eps = experts[0].ln_before.eps if self.opt.is_before_layernorm else 1e-5
         return d
+
+    def _bn_momentum(self):
+        """avmoe_moe_desc.bn_momentum of a site with BatchNorm, read from the modules on every call (torch.optim.swa_utils.update_bn and
+        avmoe_amd.train.reestimate_bn set and restore `momentum` between calls): the first BatchNorm's value when all are numbers; -1.0,
+        the cumulative average of include/avmoe.h, when all are None (torch's momentum=None); a mix within one site is refused."""
+        bns = self._site_cache()["bns"]
+        none = [k for k, m in bns if m.momentum is None]
+        if not none:
+            return bns[0][1].momentum
+        if len(none) != len(bns):
+            other = next(k for k, m in bns if m.momentum is not None)
+            raise capi.AvmoeError(f"BatchNorm momentum must be None on every BatchNorm of a site or on none: {none[0]} has momentum=None, "
+                                  f"{other} has momentum={dict(bns)[other].momentum}")
+        for k, m in bns:
+            if m._buffers.get("num_batches_tracked") is None:
+                raise capi.AvmoeError(f"{k} has momentum=None (cumulative average) but no num_batches_tracked: the update factor is "
+                                      "1 / (num_batches_tracked + 1)")
+        if not capi.lib().avmoe_bn_cumulative:
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_bn_cumulative_supported: it takes BatchNorm momentum=None "
+                                  "(cumulative average) as a number")
+        return -1.0
 
     def _site_cache(self):
         """Per-module bookkeeping that does not change from call to call (walking named_parameters / named_buffers and resolving
@@ -693,7 +714,9 @@ class MoEAdapter(nn.Module):
                     elif b is not None and attr == "num_batches_tracked" and isinstance(mod, nn.BatchNorm2d):
                         nbts.append(((mod_name + "." if mod_name else "") + attr, mod, attr))
             E_m, E_s = self.num_multimodal_experts, self.num_singlemodal_experts
-            c = dict(names=tuple(names), owners=owners, bufs=bufs, nbts=nbts, fill_p=cm.PtrFiller(names, E_m, E_s),
+            bns = [(f"{pre}.{n}", getattr(ex, n)) for pre, ex in zip(cm.expert_prefixes(E_m, E_s), list(self.multimodal_experts) +
+                   list(self.singlemodal_experts)) for n in ("bn1", "bn2")] if self.use_bn else []      # every BatchNorm of the site (_bn_momentum)
+            c = dict(names=tuple(names), owners=owners, bufs=bufs, nbts=nbts, bns=bns, fill_p=cm.PtrFiller(names, E_m, E_s),
                      fill_b=cm.PtrFiller([k for k, _, _ in bufs], E_m, E_s), fill_n=cm.PtrFiller([k for k, _, _ in nbts], E_m, E_s))
             self.__dict__["_avmoe_cache"] = c
         return c

@@ -21,6 +21,7 @@ static GemmArgs to_args(const avmoe_gemm_desc* d) {
 extern "C" {
 
 int avmoe_abi_version(void) { return AVMOE_ABI_VERSION; }
+int avmoe_bn_cumulative_supported(void) { return 1; }
 const char* avmoe_last_error(void) { return last_error(); }
 
 size_t avmoe_gemm_workspace_bytes(const avmoe_gemm_desc* desc) {

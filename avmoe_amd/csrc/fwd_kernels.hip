@@ -974,6 +974,11 @@ struct Bn1Args {
 __device__ __forceinline__ void bn1_finalize_col(const Bn1Args& a, int col, float cs0, float cs1, float* bn1) {
   const int i = col / (a.E * a.dgp), e = (col / a.dgp) % a.E, jp = col % a.dgp;
   float mean = 0.f, rstd = 0.f, sc = 0.f, sh = 0.f;
+  // cumulative average (momentum < 0): f = 1 / (n + 1) from the expert's counter, which nobody writes while this kernel runs (k_bn_count
+  // bumps it behind the forward's statistic kernels).  A launch-uniform condition and an expert that every column has: no per-lane branch.
+  const bool cumul = a.use_bn && a.training && a.momentum < 0.f;
+  float f = 0.f;
+  if (cumul) f = 1.0f / (float)(a.nbt.p[e][0] + 1);
   if (jp < a.dg) {
     const int j = i * a.dg + jp;
     if (!a.use_bn) { mean = 0.f; rstd = 1.f; sc = 1.f; sh = 0.f; }
@@ -985,9 +990,14 @@ __device__ __forceinline__ void bn1_finalize_col(const Bn1Args& a, int col, floa
         const double v = fmax(s1 / a.NT - m * m, 0.0);
         mean = (float)m; var = (float)v;
         const double unb = a.NT > 1 ? v * ((double)a.NT / (a.NT - 1)) : v;
+        if (cumul) {
+          a.rm.p[e][j] = (1.f - f) * a.rm.p[e][j] + f * mean;
+          a.rv.p[e][j] = (1.f - f) * a.rv.p[e][j] + f * (float)unb;
+        } else {
         a.rm.p[e][j] = (1.f - a.momentum) * a.rm.p[e][j] + a.momentum * mean;
         a.rv.p[e][j] = (1.f - a.momentum) * a.rv.p[e][j] + a.momentum * (float)unb;
         if (j == 0 && a.nbt.p[e]) a.nbt.p[e][0] += 1;          // bn1.num_batches_tracked (one column per expert gets here)
+        }
       } else { mean = a.rm.p[e][j]; var = a.rv.p[e][j]; }
       rstd = rsqrtf(var + a.eps);
       sc = a.w.p[e][j] * rstd;
@@ -1019,6 +1029,26 @@ int k_bn1_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_p
   hipLaunchKernelGGL(kk_bn1_finalize, dim3(cdiv(d.DZ, 256)), dim3(256), 0, st, a, (const float*)(scratch + pl.o_colsum),
                      (float*)(saved + pl.o_bn1));
   AVMOE_CHECK_LAUNCH("bn1_finalize");
+  return OK;
+}
+
+// Cumulative average (avmoe_moe_desc::bn_momentum < 0, torch's momentum=None): bn1_finalize_col and kw_bn2_stats form
+// f = 1 / (num_batches_tracked + 1) from the counter and leave it alone -- many threads of many blocks read it, so nobody may
+// write it while they run.  This launch, behind both on the same stream, adds 1 to every counter of the site: lane 2 e bumps
+// expert e's bn1 counter, lane 2 e + 1 its bn2 counter.  It exists in cumulative mode only; with a fixed momentum the two
+// statistic kernels bump the counters themselves, as they always did.
+__global__ void kk_bn_count(N16 n1, N16 n2, int E) {
+  const int e = threadIdx.x >> 1;
+  if (e >= E) return;
+  int64_t* p = (threadIdx.x & 1) ? n2.p[e] : n1.p[e];
+  if (p) p[0] += 1;
+}
+int k_bn_count(const Plan& pl, const avmoe_moe_ptrs& prm, hipStream_t st) {
+  ProfScope ps_("k_bn_count", 0.0, 0.0, st);
+  N16 n1, n2;
+  for (int e = 0; e < MAX_E; ++e) { n1.p[e] = prm.e[e].bn1_nbt; n2.p[e] = prm.e[e].bn2_nbt; }
+  hipLaunchKernelGGL(kk_bn_count, dim3(1), dim3(2 * MAX_E), 0, st, n1, n2, pl.d.E);
+  AVMOE_CHECK_LAUNCH("bn_count");
   return OK;
 }
 

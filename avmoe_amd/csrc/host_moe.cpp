@@ -88,9 +88,11 @@ void ln_bwd(const float* x, const float* dy, float* dx, long rows, int C, const 
 }
 struct BN { V mu, rs; };     // per channel
 // train: batch statistics over the rows (biased variance), running statistics updated when `update` ; eval: running statistics
+// mom < 0: torch's momentum=None, the cumulative average -- factor 1 / (*nbt + 1), read before the counter's own bump (forward() has refused a NULL counter)
 void bn_fwd(const float* x, float* y, long rows, int C, const float* w, const float* b, float eps, bool train, float mom, float* rm, float* rv, int64_t* nbt,
             bool update, BN& st) {
   st.mu.assign(C, 0.f); st.rs.assign(C, 0.f);
+  if (mom < 0.f && train && update && nbt) mom = 1.0f / (float)(*nbt + 1);
   for (int c = 0; c < C; ++c) {
     double m, v;
     if (train) {
@@ -180,6 +182,11 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
   const int S = c.S, N = c.N, C = c.C, M = c.M, Cy = c.Cy, E = c.E, K = c.K;
   const long NT = (long)S * N;
   if (!P.conv_w || !P.conv_b || !P.fc_w || !P.fc_b || !P.r0_w || !P.r0_b || !P.r2_w || !P.r2_b || !P.r4_w || !P.r4_b) return fail(AVMOE_ERR_BAD_ARG, "host: remap / router parameter missing");
+  if (c.bn && c.train && update && c.mom < 0.f)      // cumulative average (bn_momentum < 0): the factor comes from the counters, before anything is written
+    for (int e = 0; e < E; ++e) {
+      if (!P.e[e].bn1_nbt) return fail(AVMOE_ERR_BAD_ARG, "host: bn_momentum < 0 (cumulative average) needs expert %d's bn1_nbt (bn1.num_batches_tracked)", e);
+      if (!P.e[e].bn2_nbt) return fail(AVMOE_ERR_BAD_ARG, "host: bn_momentum < 0 (cumulative average) needs expert %d's bn2_nbt (bn2.num_batches_tracked)", e);
+    }
   // ---- remap (net_trans_v3.py:469-471): Yt[s] = Wc Y[s] + bc ; Yf = Yt Wf^T + bf
   c.Yt.assign(NT * Cy, 0.f); c.Yf.assign(NT * C, 0.f);
   for (int s = 0; s < S; ++s) {

@@ -45,6 +45,7 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);
 int k_bn1_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
+int k_bn_count(const Plan& pl, const avmoe_moe_ptrs& prm, hipStream_t st);      // cumulative average only: +1 on every BatchNorm counter of the site
 int k_mid(PassCall& c, hipStream_t st);
 int k_post_prep(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, hipStream_t st);
 int k_post_small(PassCall& c, hipStream_t st);

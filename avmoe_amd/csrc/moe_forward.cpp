@@ -33,6 +33,15 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
                 float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm,
                 float* aux_out, float* load_out) {
   const Dims& d = pl.d;
+  // Cumulative BatchNorm average (bn_momentum < 0): the statistic kernels form 1 / (counter + 1) on the device, so every counter must be there
+  const bool cumul = d.use_bn && d.training && d.bn_momentum < 0.f;
+  if (cumul)
+    for (int e = 0; e < d.E; ++e)
+      if (!prm_in.e[e].bn1_nbt || !prm_in.e[e].bn2_nbt) {
+        set_last_error("moe_forward: bn_momentum < 0 (cumulative average) needs expert %d's %s (%s.num_batches_tracked)", e,
+                       prm_in.e[e].bn1_nbt ? "bn2_nbt" : "bn1_nbt", prm_in.e[e].bn1_nbt ? "bn2" : "bn1");
+        return ERR_BAD_ARG;
+      }
   avmoe_moe_ptrs prm = with_unit_gates(pl, prm_in, sv);
   if (d.mg) {                                              // merged groups: run on block-diagonal dense copies of the grouped weights
     AVMOE_TRY(k_merge_expand(pl, sv, prm_in, st));
@@ -266,6 +275,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     g.accumulate = d.acc_out;
     AVMOE_TRY(launch_gemm(g, st));
   }
+  if (cumul) AVMOE_TRY(k_bn_count(pl, prm_in, st));          // behind k_bn1_finalize / k_post_prep, which only read the counters in this mode
   return OK;
 }
 
@@ -287,10 +297,16 @@ int expert_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe
   avmoe_moe_ptrs q = prm;
   if (d.training && d.use_bn) {
     float* dump = (float*)(sc + pl.o_dWf);               // C x Cy floats >= max(C, d) ; 256-byte aligned
+    // (cumulative average, bn_momentum < 0: the kernels READ a counter per expert -- the others get a zeroed one in another backward-only buffer)
+    int64_t* dump_n = nullptr;
+    if (d.bn_momentum < 0.f) {
+      dump_n = (int64_t*)(sc + pl.o_dsm);
+      if (hipMemsetAsync(dump_n, 0, sizeof(int64_t), st) != hipSuccess) { set_last_error("expert_forward: memset of the dump counter failed"); return ERR_LAUNCH; }
+    }
     for (int o = 0; o < d.E; ++o) {
       if (o == e) continue;
       q.e[o].bn1_rm = q.e[o].bn1_rv = q.e[o].bn2_rm = q.e[o].bn2_rv = dump;
-      q.e[o].bn1_nbt = q.e[o].bn2_nbt = nullptr;
+      q.e[o].bn1_nbt = q.e[o].bn2_nbt = dump_n;
     }
   }
   return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st, 0, 1, nullptr, nullptr);

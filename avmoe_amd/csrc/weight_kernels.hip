@@ -52,7 +52,8 @@ __global__ void __launch_bounds__(256) kw_bn2_stats(WArgs a, const float* mz, co
   const bool on = cl < a.Cg;
   const int c = i * a.Cg + (on ? cl : 0);
   const bool stats = a.use_bn && a.training;
-  if (stats && i == 0 && blockIdx.y == 0 && threadIdx.x == 0 && a.nbt2.p[e]) a.nbt2.p[e][0] += 1;      // bn2.num_batches_tracked
+  const bool cumul = a.momentum < 0.f;      // cumulative average: the counter is only READ below (fwd_kernels.hip: k_bn_count bumps it behind this kernel)
+  if (stats && !cumul && i == 0 && blockIdx.y == 0 && threadIdx.x == 0 && a.nbt2.p[e]) a.nbt2.p[e][0] += 1;      // bn2.num_batches_tracked
   if (stats) {
     for (int k = threadIdx.x; k < dgp * dgp; k += 256) { const int r = k / dgp; s_S[r * ldm + (k - r * dgp)] = Szz[(long)cb * dgp * dgp + k]; }
     for (int k = threadIdx.x; k < dgp; k += 256) s_m[k] = mz[(long)cb * dgp + k];
@@ -77,6 +78,13 @@ __global__ void __launch_bounds__(256) kw_bn2_stats(WArgs a, const float* mz, co
       const double v = fmax(eo2 - dmo * dmo, 0.0);
       v2 = (float)v;
       const double unb = a.NT > 1 ? v * ((double)a.NT / (a.NT - 1)) : v;
+      if (cumul) {
+        const float f = 1.0f / (float)(a.nbt2.p[e][0] + 1);      // (block-uniform read, outside the per-lane branch)
+        if (on && jl == 0) {
+          a.rm.p[e][c] = (1.f - f) * a.rm.p[e][c] + f * mo;
+          a.rv.p[e][c] = (1.f - f) * a.rv.p[e][c] + f * (float)unb;
+        }
+      } else
       if (on && jl == 0) {
         a.rm.p[e][c] = (1.f - a.momentum) * a.rm.p[e][c] + a.momentum * mo;
         a.rv.p[e][c] = (1.f - a.momentum) * a.rv.p[e][c] + a.momentum * (float)unb;

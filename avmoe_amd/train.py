@@ -12,6 +12,8 @@
                                per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
+  * `reestimate_bn`         -- BatchNorm statistics re-estimated with forward passes (momentum=None, torch's update_bn), for the
+                               raw weights or, with `ema=opt`, for FlatAdam's averaged weights
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
                                site), main_trans_v3.py:155-226
   * `save_adapters` / `load_adapters` / `strip_prefix` -- adapter-only checkpoints with the reference's state_dict keys
@@ -856,6 +858,76 @@ def router_aux_total(sites, z_weight: float = 0.0, balance_weight: float = 0.0) 
     if not terms:
         raise ValueError("router_aux_total: no sites")
     return torch.stack(terms).sum()
+
+
+def reestimate_bn(model: torch.nn.Module, batches: Iterable, forward=None, ema: Optional[FlatAdam] = None) -> int:
+    """Re-estimates the running statistics of every BatchNorm in `model` with training-mode forward passes over `batches` -- the last
+    step of weight averaging (torch.optim.swa_utils.update_bn): every `torch.nn.modules.batchnorm._BatchNorm` (the adapter sites' own
+    and any other) is reset in place, switched to `momentum=None` (torch's cumulative average: the sites form 1 / num_batches_tracked
+    on the device, include/avmoe.h at avmoe_moe_desc.bn_momentum) and the batches are run under `torch.no_grad()`.  Returns the number
+    of batches run; every `momentum` and every module's `training` flag is restored, also when a batch raises.
+
+    forward(model, batch) runs one batch; default `model(*batch)` for a tuple or list, else `model(batch)` (update_bn itself passes
+    `batch[0]`, which cannot drive a model that takes two modalities).
+
+    ema=None: update_bn's behaviour -- the model's own statistics are the re-estimated ones and the counters are left at the number of
+    batches.  ema=opt (a FlatAdam with `ema_decay` and `ema_buffers`): everything runs inside `opt.ema_weights()`, so the forward
+    passes see the AVERAGED weights and write the buffers that hold the averaged statistics meanwhile; after the swap back
+    `opt.ema_buffers` are the re-estimated statistics, the model's raw weights and raw statistics are bit for bit what they were, and
+    the counters (integer buffers, outside the optimizer's table: not swapped) are copied back in place.  ValueError, before anything
+    is touched, when `opt` has no `ema_buffers` or a float buffer of a statistics-tracking BatchNorm of `model` is not among them (by
+    address: its raw statistics would be overwritten); RuntimeError while the averages are already swapped in.  When a batch raises,
+    the swap back, the momenta, the flags and the counters are still restored, but `opt.ema_buffers` are left partly re-estimated.
+
+    Empty `batches`: returns 0 and leaves everything as it was.
+
+    Training-mode side effects of the model are the caller's: the AVS "v1" attention dropout draws from the global RNG, and the AVS
+    `is_training` noise flag is set inside `forward`.  Later `opt.step()` calls keep averaging into the re-estimated shadows, so call
+    this right before an evaluation or a checkpoint (`save_adapters(model, path, ema=opt)` then writes the re-estimated statistics)."""
+    bns = [(k, m) for k, m in model.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    if ema is not None:
+        if not getattr(ema, "_ebufs", None):
+            raise ValueError("reestimate_bn: ema has no ema_buffers (FlatAdam(ema_decay=..., ema_buffers=model)): the re-estimated statistics "
+                             "would overwrite the raw ones")
+        have = {t.data_ptr() for _name, t in ema._ebufs}
+        for k, m in bns:
+            for attr in ("running_mean", "running_var"):
+                t = m._buffers.get(attr)
+                if t is not None and t.data_ptr() not in have:
+                    raise ValueError(f"reestimate_bn: buffer {k + '.' if k else ''}{attr} is not among ema's ema_buffers: its raw statistics "
+                                     "would be overwritten")
+        ema._not_swapped("reestimate_bn()")
+    it = iter(batches)
+    try:
+        first = next(it)
+    except StopIteration:
+        return 0
+    if forward is None:
+        forward = lambda mod, batch: mod(*batch) if isinstance(batch, (tuple, list)) else mod(batch)
+    momenta = [m.momentum for _k, m in bns]
+    flags = [(m, m.training) for m in model.modules()]
+    counts = [(m.num_batches_tracked, m.num_batches_tracked.clone()) for _k, m in bns if m.num_batches_tracked is not None]
+    n = 0
+    with (ema.ema_weights() if ema is not None else contextlib.nullcontext()):
+        try:
+            for _k, m in bns:
+                m.reset_running_stats()                  # in place: the sites and FlatAdam's buffer table keep the addresses
+                m.momentum = None
+            model.train()
+            with torch.no_grad():
+                for batch in chain((first,), it):
+                    forward(model, batch)
+                    n += 1
+        finally:
+            for (_k, m), mom in zip(bns, momenta):
+                m.momentum = mom
+            for m, flag in flags:
+                m.training = flag
+            if ema is not None:
+                with torch.no_grad():
+                    for t, old in counts:
+                        t.copy_(old)
+    return n
 
 
 def adapter_state_dict(model: torch.nn.Module, substrings=("adapter",), ema: Optional[FlatAdam] = None) -> Dict[str, torch.Tensor]:

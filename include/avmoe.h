@@ -31,6 +31,7 @@ enum { AVMOE_F32 = 0, AVMOE_BF16 = 1 };
 enum { AVMOE_K_MAJOR = 0, AVMOE_MN_MAJOR = 1 };
 
 int avmoe_abi_version(void);
+int avmoe_bn_cumulative_supported(void); /* 1: avmoe_moe_desc::bn_momentum < 0 selects the cumulative average (a library without the symbol takes it as a number) */
 const char* avmoe_last_error(void);      /* thread-local, valid until the next failing call */
 
 /* ---- sub-op: the strided / batched MFMA GEMM every wide contraction of the path runs on --------
@@ -81,6 +82,16 @@ typedef struct avmoe_moe_desc {
   int32_t dtype;            /* activations */
   int32_t training;         /* 1: BatchNorm batch statistics + running-stat update ; 0: running stats */
   float bn_eps, ln_eps, bn_momentum;
+  /* bn_momentum >= 0: torch's fixed momentum, r <- (1 - m) r + m x.
+   * bn_momentum < 0 (the facade passes -1.0f; added under ABI 11, AVMOE_ABI_VERSION unchanged: avmoe_bn_cumulative_supported): torch's
+   * momentum=None, the CUMULATIVE average.  In a training-mode forward with BatchNorm, with n the value of a BatchNorm's own
+   * num_batches_tracked BEFORE this call, every element of its running mean / variance becomes (1 - f) r + f x with
+   * f = 1.0f / (float)(n + 1) and x the batch mean / the unbiased batch variance, and the counter becomes n + 1; bn1 and bn2 of an
+   * expert each use their own counter (avmoe_expert_ptrs::bn1_nbt / bn2_nbt).  f is formed on the device -- no host read of the
+   * counter, the forward stays capturable.  The statistic kernels only READ the counters in this mode; one small launch behind them,
+   * on the same stream, adds 1 to every counter of the site, so f never depends on which thread got to a counter first.  Such a call
+   * with use_bn && training and an expert's bn1_nbt or bn2_nbt NULL is refused (AVMOE_ERR_BAD_ARG, avmoe_last_error names the
+   * counter) before anything is launched.  Eval mode and use_bn == 0 ignore the field. */
   /* backward only: add dX / dY to what the output buffers already hold instead of overwriting them -- lets a caller whose
    * token tensor feeds several sites (the audio tokens are X of the audio site and Y of the visual site,
    * net_trans_v3.py:695-698) collect the gradient in one buffer without a separate accumulation pass (ABI 2) */
@@ -135,7 +146,8 @@ typedef struct avmoe_expert_ptrs {        /* <list>.{j}.*  ; unused entries NULL
    * no dropout (eval).  The caller draws it (the reference uses the global RNG) and keeps it alive until the backward.  */
   float *sa_in_w, *sa_in_b, *sa_out_w, *sa_out_b, *sa_keep;
   /* ABI 6 -- bn1.num_batches_tracked / bn2.num_batches_tracked (one int64 each), or NULL: a training-mode forward with BatchNorm
-   * adds 1 to each inside its own kernels (torch.nn.BatchNorm2d semantics), so the caller needs no extra launch for the counters. */
+   * adds 1 to each inside its own kernels (torch.nn.BatchNorm2d semantics), so the caller needs no extra launch for the counters.
+   * With avmoe_moe_desc::bn_momentum < 0 they are required: the update factor is 1 / (counter + 1). */
   int64_t *bn1_nbt, *bn2_nbt;
 } avmoe_expert_ptrs;
 

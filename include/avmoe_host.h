@@ -22,7 +22,9 @@ const char* avmoe_host_last_error(void);
 size_t avmoe_host_moe_saved_bytes(const avmoe_moe_desc* desc);       /* the backward recomputes the forward: `saved` may be NULL */
 
 /* as avmoe_moe_forward: out (S, N, C), probs (S, E) or NULL, idx (S) int64 or NULL, lb (1 float) or NULL; in training mode the
- * BatchNorm running statistics / num_batches_tracked in `params` advance.                                                              */
+ * BatchNorm running statistics / num_batches_tracked in `params` advance.  bn_momentum < 0: the cumulative average of avmoe.h, factor
+ * 1.0f / (float)(counter + 1) read before the counter's own bump; a NULL bn1_nbt / bn2_nbt is then AVMOE_ERR_BAD_ARG, named in
+ * avmoe_host_last_error, before anything is written.                                                                                  */
 int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                            float* out, float* probs, int64_t* idx, float* lb, void* saved);
 
