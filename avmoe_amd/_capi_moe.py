@@ -8,6 +8,8 @@ MAX_EXPERTS = 16
 OPT_CLIP, OPT_SKIP_NONFINITE, OPT_DECOUPLED_DECAY, OPT_LR_SCHEDULE = 1, 2, 4, 8      # flags of avmoe_opt_grad_norm[_sched] / avmoe_opt_adam_step
 OPT_EMA = 16                                                        # ... of avmoe_opt_grad_norm_ema / avmoe_opt_adam_step_ema only
 OPT_REPORT = 32                                                     # ... of avmoe_opt_grad_norm_report only
+OPT_SWA, OPT_SWA_LR = 64, 128                                       # ... of avmoe_opt_grad_norm_swa only
+SWA_ANNEAL_KINDS = {"cos": 0, "linear": 1}                          # AVMOE_SWA_ANNEAL_*
 SCHED_KINDS = {"none": 0, "cosine": 1, "linear": 2, "step": 3}      # AVMOE_SCHED_*
 VARIANT = {"ave": 0, "avqa": 0, "avvp": 1, "avs": 2}
 SELF_ATTN = {"none": 0, "v2": 1, "nxn": 2, "v1": 3}
@@ -40,6 +42,12 @@ class OptSchedule(C.Structure):
 class OptEma(C.Structure):
     """avmoe_opt_ema: the host constants of the weight average, d_n = min(decay, (1 + n) / (warmup + n))"""
     _fields_ = [("decay", C.c_float), ("warmup", C.c_float)]
+
+
+class OptSwa(C.Structure):
+    """avmoe_opt_swa: the host constants of stochastic weight averaging -- the uniform average (start, freq) and the annealed rate"""
+    _fields_ = [("start", C.c_int64), ("lr_start", C.c_int64), ("freq", C.c_int32), ("anneal_steps", C.c_int32), ("lr_factor", C.c_float),
+                ("anneal_kind", C.c_int32)]
 
 
 class OptBuffer(C.Structure):
@@ -161,6 +169,9 @@ def declare(L):
             L.avmoe_opt_report_bytes.restype, L.avmoe_opt_report_bytes.argtypes = C.c_size_t, [C.c_int32]
             L.avmoe_opt_grad_norm_report.restype = C.c_int
             L.avmoe_opt_grad_norm_report.argtypes = norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma), C.c_void_p]
+        if hasattr(L, "avmoe_opt_grad_norm_swa"):     # (found by symbol: stochastic weight averaging)
+            L.avmoe_opt_grad_norm_swa.restype = C.c_int
+            L.avmoe_opt_grad_norm_swa.argtypes = norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma), C.c_void_p, C.POINTER(OptSwa)]
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

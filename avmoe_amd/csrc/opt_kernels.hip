@@ -4,7 +4,9 @@
 //   kk_opt_sqsum                           sum of (grad * grad_scale)^2 per 1024-element block, in double, into the partial-sum workspace
 //   kk_opt_finalize<SCHED, EMA>            one block adds the partial sums in a fixed order and writes the state block: norm, clip factor,
 //                                          skip flag, step counters, bias corrections; SCHED: and the learning-rate factor of a per-step
-//                                          schedule; EMA: and the decay of the weight average for this step
+//                                          schedule; EMA: and the decay of the weight average for this step.  Stochastic weight
+//                                          averaging is the same two words by another rule (avmoe_opt_swa: the annealed rate under
+//                                          SCHED, the uniform average's decay under EMA), a launch-uniform branch and no kernel more
 //   kk_opt_adam<DECOUPLED, SCHED, EMA>     the Adam / AdamW update of every range; reads the state block, writes nothing when the step is
 //                                          skipped; EMA: the thread that holds an element's new value also advances its average,
 //                                          ema = d ema + (1 - d) p, in a shadow buffer per range -- two more 4-byte streams per element
@@ -45,6 +47,7 @@ struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
 struct OptBlock { int32_t range, block; };
 static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
 static_assert(sizeof(avmoe_opt_report_header) == 16, "report layout");
+static_assert(sizeof(avmoe_opt_swa) == 32 && sizeof(avmoe_opt_schedule) == 40 && sizeof(avmoe_opt_ema) == 8, "constants of a run");
 
 // What a thread of a one-block-per-table-block launch serves: elements [i0, min(i0 + 4, r.n)) of range `range`.
 struct OptWork { int32_t n_ranges, range; avmoe_opt_range r; long i0; };
@@ -125,18 +128,53 @@ __device__ __forceinline__ double ema_decay(const avmoe_opt_ema& e, int64_t n) {
   return w < d ? w : d;
 }
 
+// Stochastic weight averaging (include/avmoe.h, avmoe_opt_swa).  The copy the finalize kernel gets is the caller's with the half that is
+// off marked by a value the checks refuse from a caller: start = 0 without AVMOE_OPT_SWA, lr_start = -1 without AVMOE_OPT_SWA_LR.
+__device__ __forceinline__ bool swa_averages(const avmoe_opt_swa& w) { return w.start > 0; }
+__device__ __forceinline__ bool swa_anneals(const avmoe_opt_swa& w) { return w.lr_start >= 0; }
+
+// the uniform average's decay at n applied steps, this one included, in double (FlatAdam.swa_decay_at is the host's copy): 0 below
+// `start` (the shadow follows the parameters), k / (k + 1) at the k-th averaging step after the first (torch's AveragedModel with
+// n_averaged = k), 1 between two averaging steps (the shadow keeps its value)
+__device__ __forceinline__ double swa_decay(const avmoe_opt_swa& w, int64_t n) {
+#pragma clang fp contract(off)
+  if (n < w.start) return 0.0;
+  const int64_t u = n - w.start;
+  const int64_t c = w.freq;
+  if (u % c != 0) return 1.0;
+  const double k = (double)(u / c);
+  return k / (k + 1.0);
+}
+
+// the learning-rate factor at n applied steps with the annealing of torch's SWALR from step lr_start on, in closed form and in double
+// (LRSchedule.factor is the host's copy, in this operation order); `s` is the base schedule, all zero for base = 1
+__device__ __forceinline__ double swa_lr_factor(const avmoe_opt_schedule& s, const avmoe_opt_swa& w, int64_t n) {
+#pragma clang fp contract(off)
+  if (n < w.lr_start) return sched_factor(s, n);
+  const double f0 = sched_factor(s, w.lr_start), to = (double)w.lr_factor;
+  double t = 1.0;
+  if (w.anneal_steps > 0) {
+    t = (double)(n - w.lr_start) / (double)w.anneal_steps;
+    t = t < 1.0 ? t : 1.0;
+  }
+  const double alpha = w.anneal_kind == AVMOE_SWA_ANNEAL_LINEAR ? t : (1.0 - cos(M_PI * t)) / 2.0;
+  return f0 + (to - f0) * alpha;
+}
+
 // One block.  Thread t adds partials[t], partials[t + 256], ... in that order, the 256 sums go through the same tree as above: a fixed
 // order.  n_partials == 0 (neither clipping nor skipping asked for): the norm is reported as 0 and only the counters advance.
 // SCHED: the step that is applied now is number n = applied_steps before it (the first one has n = 0); its factor goes into the state
 // block, rounded once to fp32.  A skipped step leaves the factor alone.
 // EMA: the average's decay for this step, from n = applied_steps AFTER it (the first one has n = 1), likewise.
+// swa: where its half is on (see above), the factor is the annealed one and the decay that of the uniform average -- the same words of
+// the state block by another rule, one branch that every launch takes the same way.
 // The schedule and the average's constants ride in the kernel arguments: constants of the run, so a captured launch replays them.
 // report != NULL (AVMOE_OPT_REPORT): the header of the report is reset for kk_opt_range_norms, which follows on the same stream.
 template <bool SCHED, bool EMA>
 __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_state* __restrict__ state,
                                                        float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
                                                        avmoe_opt_schedule sched, avmoe_opt_ema ema, avmoe_opt_report_header* __restrict__ report,
-                                                       int n_ranges) {
+                                                       int n_ranges, avmoe_opt_swa swa) {
   double acc = 0.0;
   for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
   const double sum = block_sum_256(acc);
@@ -159,10 +197,10 @@ __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict_
   state->bc1 = (float)bc1;
   state->bc2_sqrt = (float)sqrt(bc2);
   if constexpr (SCHED) {
-    if (!skip) state->lr_factor = (float)sched_factor(sched, before);
+    if (!skip) state->lr_factor = (float)(swa_anneals(swa) ? swa_lr_factor(sched, swa, before) : sched_factor(sched, before));
   }
   if constexpr (EMA) {
-    if (!skip) state->ema_decay = (float)ema_decay(ema, applied);
+    if (!skip) state->ema_decay = (float)(swa_averages(swa) ? swa_decay(swa, applied) : ema_decay(ema, applied));
   }
 }
 
@@ -423,6 +461,23 @@ static int check_ema(const char* who, const avmoe_opt_ema* e) {
   if (!(e->warmup >= 1.f) || std::isinf(e->warmup)) { set_last_error("%s: the average's warmup must be >= 1 and finite", who); return ERR_BAD_ARG; }
   return OK;
 }
+// host-side validation of the halves of avmoe_opt_swa that the flags switch on
+static int check_swa(const char* who, const avmoe_opt_swa* w, bool average, bool anneal) {
+  if (!w) { set_last_error("%s: AVMOE_OPT_SWA / AVMOE_OPT_SWA_LR without avmoe_opt_swa", who); return ERR_BAD_ARG; }
+  if (average) {
+    if (w->start < 1) { set_last_error("%s: avmoe_opt_swa.start must be >= 1, not %lld", who, (long long)w->start); return ERR_BAD_ARG; }
+    if (w->freq < 1) { set_last_error("%s: avmoe_opt_swa.freq must be >= 1, not %d", who, (int)w->freq); return ERR_BAD_ARG; }
+  }
+  if (anneal) {
+    if (w->lr_start < 0) { set_last_error("%s: avmoe_opt_swa.lr_start must be >= 0, not %lld", who, (long long)w->lr_start); return ERR_BAD_ARG; }
+    if (w->anneal_steps < 0) { set_last_error("%s: avmoe_opt_swa.anneal_steps must be >= 0, not %d", who, (int)w->anneal_steps); return ERR_BAD_ARG; }
+    if (!(w->lr_factor >= 0.f && w->lr_factor <= 1.f)) { set_last_error("%s: avmoe_opt_swa.lr_factor must be in [0, 1]", who); return ERR_BAD_ARG; }
+    if (w->anneal_kind != AVMOE_SWA_ANNEAL_COS && w->anneal_kind != AVMOE_SWA_ANNEAL_LINEAR) {
+      set_last_error("%s: unknown avmoe_opt_swa.anneal_kind %d", who, (int)w->anneal_kind); return ERR_BAD_ARG;
+    }
+  }
+  return OK;
+}
 static int check_shadows(const char* who, float* const* shadows) {
   if (!shadows) { set_last_error("%s: the shadow pointer array is NULL", who); return ERR_BAD_ARG; }
   if (((uintptr_t)shadows & 7u) != 0) { set_last_error("%s: the shadow pointer array must be 8-byte aligned", who); return ERR_ALIGNMENT; }
@@ -433,19 +488,29 @@ constexpr int32_t OPT_FLAGS = AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_
 constexpr int OPT_REPORT_MAX_GRID = 1024;        // blocks of 4 waves: more ranges than 4096 take a second round
 
 // avmoe_opt_grad_norm (sched == NULL, ema == NULL), avmoe_opt_grad_norm_sched (ema == NULL), avmoe_opt_grad_norm_ema (report == NULL) and
-// avmoe_opt_grad_norm_report: the same checks and the same norm launch, then the finalize kernel the flags ask for, then the per-range norms
+// avmoe_opt_grad_norm_report (swa == NULL), avmoe_opt_grad_norm_swa: the same checks and the same norm launch, then the finalize kernel the flags
+// ask for, then the per-range norms.  AVMOE_OPT_SWA_LR takes the SCHED instantiation and AVMOE_OPT_SWA the EMA one.
 static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                      float max_norm, int32_t flags, int32_t known_flags, float beta1, float beta2, const avmoe_opt_schedule* sched,
-                     const avmoe_opt_ema* ema, void* report, void* stream) {
+                     const avmoe_opt_ema* ema, void* report, const avmoe_opt_swa* swa, void* stream) {
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
   const bool clip = (flags & AVMOE_OPT_CLIP) != 0, skip = (flags & AVMOE_OPT_SKIP_NONFINITE) != 0;
   const bool with_sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, with_ema = (flags & AVMOE_OPT_EMA) != 0;
   const bool with_report = (flags & AVMOE_OPT_REPORT) != 0;
+  const bool with_swa = (flags & AVMOE_OPT_SWA) != 0, with_swa_lr = (flags & AVMOE_OPT_SWA_LR) != 0;
   if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
   if (clip && !(max_norm >= 0.f)) { set_last_error("%s: max_norm must be >= 0 and not NaN", who); return ERR_BAD_ARG; }
   if (!(grad_scale == grad_scale)) { set_last_error("%s: grad_scale is NaN", who); return ERR_BAD_ARG; }
   if (with_sched) AVMOE_TRY(check_schedule(who, sched));
   if (with_ema) AVMOE_TRY(check_ema(who, ema));
+  avmoe_opt_swa w{};                                     // the kernel's copy: the half that is off as swa_averages / swa_anneals read it
+  w.lr_start = -1;
+  if (with_swa || with_swa_lr) {
+    AVMOE_TRY(check_swa(who, swa, with_swa, with_swa_lr));
+    if (with_swa && with_ema) { set_last_error("%s: AVMOE_OPT_SWA and AVMOE_OPT_EMA are alternatives: one average, one decay word", who); return ERR_BAD_ARG; }
+    if (with_swa) { w.start = swa->start; w.freq = swa->freq; }
+    if (with_swa_lr) { w.lr_start = swa->lr_start; w.anneal_steps = swa->anneal_steps; w.lr_factor = swa->lr_factor; w.anneal_kind = swa->anneal_kind; }
+  }
   if (with_report) {
     if (!report) { set_last_error("%s: AVMOE_OPT_REPORT without a report buffer", who); return ERR_BAD_ARG; }
     if (((uintptr_t)report & 15u) != 0) { set_last_error("%s: the report buffer must be 16-byte aligned", who); return ERR_ALIGNMENT; }
@@ -458,9 +523,9 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
     hipLaunchKernelGGL(kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials, grad_scale);
     AVMOE_CHECK_LAUNCH("opt_sqsum");
   }
-  hipLaunchKernelGGL(OPT_FINALIZE[(int)with_sched | (int)with_ema << 1], dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials,
+  hipLaunchKernelGGL(OPT_FINALIZE[(int)(with_sched || with_swa_lr) | (int)(with_ema || with_swa) << 1], dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials,
                      norm ? (long)n_blocks : 0L, state, max_norm, (int)clip, (int)skip, beta1, beta2, with_sched ? *sched : avmoe_opt_schedule{},
-                     with_ema ? *ema : avmoe_opt_ema{}, rep, (int)n_ranges);
+                     with_ema ? *ema : avmoe_opt_ema{}, rep, (int)n_ranges, w);
   AVMOE_CHECK_LAUNCH("opt_finalize");
   if (rep && n_ranges > 0) {
     const int grid = (int)std::min<int64_t>(((int64_t)n_ranges + 3) / 4, OPT_REPORT_MAX_GRID);
@@ -524,13 +589,13 @@ int avmoe_opt_table_build(const avmoe_opt_range* ranges, int32_t n_ranges, void*
 int avmoe_opt_grad_norm(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                         float max_norm, int32_t flags, float beta1, float beta2, void* stream) {
   return grad_norm("avmoe_opt_grad_norm", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS, beta1, beta2, nullptr, nullptr,
-                   nullptr, stream);
+                   nullptr, nullptr, stream);
 }
 
 int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                               float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched) {
   return grad_norm("avmoe_opt_grad_norm_sched", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE,
-                   beta1, beta2, sched, nullptr, nullptr, stream);
+                   beta1, beta2, sched, nullptr, nullptr, nullptr, stream);
 }
 
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
@@ -543,7 +608,7 @@ int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_block
                             float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
                             const avmoe_opt_ema* ema) {
   return grad_norm("avmoe_opt_grad_norm_ema", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
-                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, ema, nullptr, stream);
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, beta1, beta2, sched, ema, nullptr, nullptr, stream);
 }
 
 size_t avmoe_opt_report_bytes(int32_t n_ranges) {
@@ -555,7 +620,15 @@ int avmoe_opt_grad_norm_report(const void* table, int32_t n_ranges, int64_t n_bl
                                float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
                                const avmoe_opt_ema* ema, void* report) {
   return grad_norm("avmoe_opt_grad_norm_report", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
-                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA | AVMOE_OPT_REPORT, beta1, beta2, sched, ema, report, stream);
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA | AVMOE_OPT_REPORT, beta1, beta2, sched, ema, report, nullptr, stream);
+}
+
+int avmoe_opt_grad_norm_swa(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                            float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched,
+                            const avmoe_opt_ema* ema, void* report, const avmoe_opt_swa* swa) {
+  return grad_norm("avmoe_opt_grad_norm_swa", table, n_ranges, n_blocks, partials, state, grad_scale, max_norm, flags,
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA | AVMOE_OPT_REPORT | AVMOE_OPT_SWA | AVMOE_OPT_SWA_LR, beta1, beta2, sched, ema, report,
+                   swa, stream);
 }
 
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,

@@ -9,6 +9,8 @@
                                load_state_dict() in torch.optim.Adam's format; an exponential moving average of the weights kept
                                by the update kernel itself, swapped in for evaluation and written by `save_adapters(ema=opt)`,
                                BatchNorm running statistics averaged and swapped with them (`ema_buffers=model`);
+                               stochastic weight averaging (`swa_start` / `swa_freq`: torch's AveragedModel as that same average
+                               with a uniform rule, SWALR as a part of `LRSchedule`), still without a launch more;
                                per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
@@ -20,7 +22,7 @@
                                (strict=False load of released checkpoints, main_trans_v3.py:254; HTS-AT key strip,
                                net_trans_v3.py:560-563)
 
-Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema|_report] /
+Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema|_report|_swa] /
 avmoe_opt_adam_step[_ema] / avmoe_opt_swap_ema, avmoe_opt_ema_buffers / avmoe_opt_swap_buffers, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
@@ -77,7 +79,20 @@ class LRSchedule:
     Cosine and linear stay at min_factor from total_steps on.  The device holds warmup_start, min_factor and gamma as fp32 and
     evaluates f in double from them; the constructor therefore rounds these three to fp32 (0.1 becomes 0.10000000149...), so that
     `factor(n)` is the very function the kernel computes and agrees with it to the final fp32 rounding.  A bad schedule raises
-    ValueError here, with the rules the library checks again."""
+    ValueError here, with the rules the library checks again.
+
+    The SWA learning rate (torch.optim.swa_utils.SWALR; avmoe_opt_swa of include/avmoe.h).  `swa_start=N` (None: off, and `factor` is
+    the closed form above) anneals the factor from step N on to the constant `swa_factor` over `swa_anneal_steps` steps; with base(n)
+    the closed form above:
+
+        n <  N:  f = base(n)
+        n >= N:  f0 = base(N), t = 1 if swa_anneal_steps == 0 else min(1, (n - N) / swa_anneal_steps),
+                 alpha = t ("linear") or (1 - cos(pi t)) / 2 ("cos"), f = f0 + (swa_factor - f0) * alpha
+
+    -- what SWALR(optimizer, swa_lr=swa_factor * lr0, anneal_epochs=swa_anneal_steps, anneal_strategy=swa_anneal) gives when it is
+    constructed as step N is due, after a LambdaLR(base) stepped until then, and stepped once per applied step (its recursion in closed
+    form).  `swa_factor` is held as fp32 like the other factors.  A schedule of the SWA part alone (no warm-up, decay_kind "none":
+    base = 1) is valid."""
     warmup_steps: int = 0
     warmup_start: float = 0.0
     decay_kind: str = "none"
@@ -85,6 +100,10 @@ class LRSchedule:
     min_factor: float = 0.0
     step_size: int = 0
     gamma: float = 1.0
+    swa_start: Optional[int] = None
+    swa_factor: float = 1.0
+    swa_anneal_steps: int = 0
+    swa_anneal: str = "cos"
 
     def __post_init__(self):
         kinds = cm.SCHED_KINDS
@@ -110,10 +129,36 @@ class LRSchedule:
             raise ValueError(f"a {self.decay_kind} decay needs total_steps > warmup_steps, not {self.total_steps} <= {self.warmup_steps}")
         if self.decay_kind == "step" and self.step_size <= 0:
             raise ValueError("a step decay needs step_size > 0")
+        for name in ("swa_start", "swa_anneal_steps"):
+            v = getattr(self, name)
+            if v is None and name == "swa_start":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or int(v) != v or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0, not {v!r}")
+            setattr(self, name, int(v))
+        if self.swa_anneal_steps > 2 ** 31 - 1:
+            raise ValueError(f"swa_anneal_steps must fit 32 bits, not {self.swa_anneal_steps!r}")
+        v = float(self.swa_factor)
+        if not (0.0 <= v <= 1.0):
+            raise ValueError(f"swa_factor must be in [0, 1], not {self.swa_factor!r}")
+        self.swa_factor = _f32(v)
+        if self.swa_anneal not in cm.SWA_ANNEAL_KINDS:
+            raise ValueError(f"swa_anneal must be one of {sorted(cm.SWA_ANNEAL_KINDS)}, not {self.swa_anneal!r}")
 
     def factor(self, n: int) -> float:
         """f(n) in Python float (double), the closed form of the class docstring in the operation order of the kernel"""
-        n, W = int(n), self.warmup_steps
+        n, N = int(n), self.swa_start
+        if N is None or n < N:
+            return self._base(n)
+        f0, t = self._base(N), 1.0
+        if self.swa_anneal_steps > 0:
+            t = min((n - N) / self.swa_anneal_steps, 1.0)
+        alpha = t if self.swa_anneal == "linear" else (1.0 - math.cos(math.pi * t)) / 2.0
+        return f0 + (self.swa_factor - f0) * alpha
+
+    def _base(self, n: int) -> float:
+        """the factor without the SWA part"""
+        W = self.warmup_steps
         if n < W:
             return self.warmup_start + (1.0 - self.warmup_start) * n / W
         u = n - W
@@ -130,6 +175,14 @@ class LRSchedule:
     def c_struct(self) -> "cm.OptSchedule":
         return cm.OptSchedule(warmup_steps=self.warmup_steps, warmup_start=self.warmup_start, decay_kind=cm.SCHED_KINDS[self.decay_kind],
                               total_steps=self.total_steps, min_factor=self.min_factor, gamma=self.gamma, step_size=self.step_size)
+
+    def fill_swa(self, w: "cm.OptSwa") -> bool:
+        """writes the learning-rate half of avmoe_opt_swa into `w`; -> whether the schedule has one (AVMOE_OPT_SWA_LR)"""
+        if self.swa_start is None:
+            return False
+        w.lr_start, w.anneal_steps, w.lr_factor = self.swa_start, self.swa_anneal_steps, self.swa_factor
+        w.anneal_kind = cm.SWA_ANNEAL_KINDS[self.swa_anneal]
+        return True
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -186,6 +239,22 @@ class FlatAdam:
     under "flat_adam" ("ema_buffers": CPU tensors, "ema_buffer_names"), `load_state_dict()` restores them, and a dict without them
     re-seeds the shadows from the current buffers.  Without the option the calls and launches of a step are what they were.
 
+    Stochastic weight averaging.  `swa_start=N, swa_freq=c` (torch.optim.swa_utils.AveragedModel on the device; it selects the device
+    path too, and is the alternative to `ema_decay`: giving both raises ValueError) keeps the UNIFORM average of the parameters after the
+    applied steps N, N + c, N + 2c, ... -- the average over the tail of a run that SWA is defined by, which no decay below 1 expresses.
+    It is the exponential average's machinery with another rule for the decay: with n = applied_steps after the step, the finalize
+    launch writes d = 0 for n < N (the average follows the parameters: an "averaged" checkpoint taken early holds the raw weights),
+    d = k / (k + 1) with k = (n - N) / c on an averaging step (AveragedModel.update_parameters after optimizer.step() with
+    n_averaged = k; the first one copies the parameters) and d = 1 between two of them (the average keeps its value); `swa_decay_at` /
+    `swa_n_averaged_at` are the host's copies, `last_ema_decay` the value on the device.  The number of models averaged is a function of
+    applied_steps alone: no counter more, a skipped step advances nothing, a captured step averages on replay, the launches of a step
+    are those of `ema_decay`.  `ema_params`, `swap_ema()`, `ema_weights()`, `ema_buffers=` (the buffers' shadows get the same d),
+    `adapter_state_dict(model, ema=opt)`, `save_adapters(..., ema=opt)` and `reestimate_bn(model, batches, ema=opt)` -- torch's
+    update_bn for the averaged weights -- serve the uniform average unchanged.  The SWA learning rate is the schedule's part:
+    `LRSchedule(..., swa_start=, swa_factor=, swa_anneal_steps=, swa_anneal=)`; either may be used without the other.  `state_dict()`
+    carries "swa_start" / "swa_freq" beside the averages ("ema") and `load_state_dict()` restores them; a dict with them does not load
+    into an optimizer built without `swa_start` (ValueError), one without them re-seeds the averages from the current parameters.
+
     Per-parameter gradient norms.  `report_grad_norms=True` (it selects the device path too) adds ONE launch behind the finalize launch:
     a wave per parameter adds the block sums the norm pass has left anyway, in a fixed order, and writes the parameter's gradient norm
     into a report buffer on the device; the lowest index of a parameter whose norm is Inf or NaN goes into its header.  The norm pass then
@@ -213,15 +282,18 @@ class FlatAdam:
                  step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
                  max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
                  lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
-                 report_grad_norms: bool = False, ema_buffers=None):
+                 report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
         [0, 1), warmed up over `ema_warmup` >= 1 (1: constant decay); both are held as fp32.  report_grad_norms: every step also leaves
         each parameter's gradient norm and the index of the first non-finite one on the device (`last_param_grad_norms`,
-        `first_nonfinite_param`).  Any of the six selects the device path (class docstring); with all at their defaults step() is the
+        `first_nonfinite_param`).  swa_start: keep the uniform average of the parameters over the applied steps swa_start,
+        swa_start + swa_freq, ... (integers >= 1, steps counted from 1; class docstring, "Stochastic weight averaging") in place of the
+        exponential one: giving it together with `ema_decay` raises ValueError.  Any of the seven selects the device path (class
+        docstring); with all at their defaults step() is the
         per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
-        and swap with the weights; needs `ema_decay`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
+        and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
@@ -242,6 +314,9 @@ class FlatAdam:
             raise TypeError("lr_schedule must be an avmoe_amd.train.LRSchedule")
         self.lr_schedule = lr_schedule
         self.ema_decay, self.ema_warmup = self._check_ema(ema_decay, ema_warmup)
+        self.swa_start, self.swa_freq = self._check_swa(swa_start, swa_freq)
+        if self.swa_start is not None and self.ema_decay is not None:
+            raise ValueError("swa_start and ema_decay are alternatives: the optimizer keeps one average of the weights")
         self._swapped = False                            # the parameters currently hold the averages (swap_ema / ema_weights)
         self.report_grad_norms = bool(report_grad_norms)
         self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
@@ -270,11 +345,11 @@ class FlatAdam:
                 self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
                 self._wds.append(wd_of.get(id(p), weight_decay))
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
-            if self.ema_decay is not None:               # the averages: the bucket's layout once more, padding zero
+            if self._averaging:                          # the averages: the bucket's layout once more, padding zero
                 self.state[-1]["e"] = flat_p.clone()
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
-            or self.ema_decay is not None or self.report_grad_norms
+            or self._averaging or self.report_grad_norms
         if self._device:
             self._build_device_state()
 
@@ -302,16 +377,66 @@ class FlatAdam:
         n = int(n)
         return _f32(min(d, (1.0 + n) / (w + n)))
 
+    @staticmethod
+    def _check_swa(start, freq):
+        """-> (start, freq) as integers, or (None, freq) when the uniform average is off"""
+        for name, v in (("swa_start", start), ("swa_freq", freq)):
+            if v is None and name == "swa_start":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or int(v) != v or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, not {v!r}")
+        if int(freq) > 2 ** 31 - 1:
+            raise ValueError(f"swa_freq must fit 32 bits, not {freq!r}")
+        return (None if start is None else int(start)), int(freq)
+
+    @staticmethod
+    def swa_n_averaged_at(n: int, start: int, freq: int = 1) -> int:
+        """the number of models in the uniform average after n applied steps: the steps start, start + freq, ... up to n (torch's
+        AveragedModel.n_averaged)"""
+        start, freq = FlatAdam._check_swa(start, freq)
+        if start is None:
+            raise ValueError("swa_n_averaged_at needs a start")
+        n = int(n)
+        return 0 if n < start else (n - start) // freq + 1
+
+    @staticmethod
+    def swa_decay_at(n: int, start: int, freq: int = 1) -> float:
+        """the decay d of the uniform average for n applied steps, this one included (the first step has n = 1): 0 below `start` (the
+        average follows the parameters), k / (k + 1) where this step is the k-th averaged one after the first, k = (n - start) / freq,
+        and exactly 1 between two averaged steps.  The finalize kernel's closed form on the host -- formed in double, rounded once to
+        fp32 -- and equal to it bit for bit."""
+        start, freq = FlatAdam._check_swa(start, freq)
+        if start is None:
+            raise ValueError("swa_decay_at needs a start")
+        n = int(n)
+        if n < start:
+            return 0.0
+        if (n - start) % freq:
+            return 1.0
+        k = float((n - start) // freq)
+        return _f32(k / (k + 1.0))
+
+    @property
+    def _averaging(self) -> bool:
+        """the optimizer keeps an average of the weights: the exponential one (ema_decay) or the uniform one (swa_start)"""
+        return self.ema_decay is not None or self.swa_start is not None
+
+    def _decay_at(self, n: int) -> float:
+        """the decay word of the state block after n applied steps, by the rule of the average that is on"""
+        if self.swa_start is not None:
+            return self.swa_decay_at(n, self.swa_start, self.swa_freq)
+        return self.ema_decay_at(n, self.ema_decay, self.ema_warmup)
+
     def _need_ema(self, what):
-        if self.ema_decay is None:
-            raise capi.AvmoeError(f"FlatAdam.{what} needs ema_decay")
+        if not self._averaging:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs ema_decay or swa_start")
 
     def _collect_buffers(self, spec, reducer):
         """`ema_buffers` -> [(name, tensor)] of what is averaged: contiguous fp32, on the buckets' device, not empty, one per address"""
         if spec is None:
             return []
-        if self.ema_decay is None:
-            raise ValueError("ema_buffers needs ema_decay: the buffers are averaged with the decay of the weight average")
+        if not self._averaging:
+            raise ValueError("ema_buffers needs ema_decay or swa_start: the buffers are averaged with the decay of the weight average")
         items = spec.named_buffers() if isinstance(spec, torch.nn.Module) else spec
         dev = reducer.buckets[0].flat.device if reducer.buckets else None
         out, seen = [], set()
@@ -389,7 +514,8 @@ class FlatAdam:
     @property
     def last_ema_decay(self) -> torch.Tensor:
         """fp32 DEVICE scalar: the decay d_n the last applied step averaged with (a skipped step leaves it).  A view of the state block,
-        like `last_lr_factor`; only with `ema_decay`."""
+        like `last_lr_factor`; only with `ema_decay` or `swa_start` (there: 0 before the average starts, k / (k + 1) on an averaging
+        step, 1 between two)."""
         self._need_ema("last_ema_decay")
         return self._state_view("ema_decay")
 
@@ -456,9 +582,10 @@ class FlatAdam:
                        for k, (o, dt) in cm.OPT_STATE_FIELDS.items()}
         self._flags = (cm.OPT_CLIP if self.max_grad_norm is not None else 0) | (cm.OPT_SKIP_NONFINITE if self.skip_nonfinite else 0) \
             | (cm.OPT_DECOUPLED_DECAY if self.decoupled_weight_decay else 0)
+        self._swa_c = cm.OptSwa()                        # both halves of avmoe_opt_swa; a half that is off is not read
         self._set_schedule(self.lr_schedule)
         self._upload_table()
-        if self.ema_decay is not None:
+        if self._averaging:
             self._build_shadows()
         if self._ebufs:
             self._build_buffer_table()
@@ -489,18 +616,32 @@ class FlatAdam:
         if any(q % 16 for q in ptrs):
             raise capi.AvmoeError("FlatAdam: a shadow range is not 16-byte aligned")
         self._shadow_ptrs = torch.tensor(ptrs, dtype=torch.int64).to(self._dev)
-        self._set_ema(self.ema_decay, self.ema_warmup)
+        if self.swa_start is not None:
+            self._set_swa(self.swa_start, self.swa_freq)
+        else:
+            self._set_ema(self.ema_decay, self.ema_warmup)
 
     def _set_ema(self, decay, warmup):
         self.ema_decay, self.ema_warmup = decay, warmup
         self._ema_c = cm.OptEma(decay=decay, warmup=warmup)
         self._flags |= cm.OPT_EMA
 
+    def _set_swa(self, start, freq):
+        if not hasattr(capi.lib(), "avmoe_opt_grad_norm_swa"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks stochastic weight averaging (avmoe_opt_grad_norm_swa): rebuild it")
+        self.swa_start, self.swa_freq = start, freq
+        self._swa_c.start, self._swa_c.freq = start, freq
+        self._flags |= cm.OPT_SWA
+
     def _set_schedule(self, sched: Optional[LRSchedule]):
-        """the schedule as the struct step() hands over, and its flag"""
+        """the schedule as the struct step() hands over, and its flag; with its SWA part the other half of avmoe_opt_swa and that flag"""
         self.lr_schedule = sched
         self._sched_c = None if sched is None else sched.c_struct()
-        self._flags = (self._flags & ~cm.OPT_LR_SCHEDULE) | (cm.OPT_LR_SCHEDULE if sched is not None else 0)
+        self._flags = (self._flags & ~(cm.OPT_LR_SCHEDULE | cm.OPT_SWA_LR)) | (cm.OPT_LR_SCHEDULE if sched is not None else 0)
+        if sched is not None and sched.fill_swa(self._swa_c):
+            if not hasattr(capi.lib(), "avmoe_opt_grad_norm_swa"):
+                raise capi.AvmoeError("this libavmoe_hip.so lacks the SWA learning rate (avmoe_opt_grad_norm_swa): rebuild it")
+            self._flags |= cm.OPT_SWA_LR
 
     def _upload_table(self):
         """(re)build the range table with the learning rates of the current epoch and send it with ONE asynchronous copy"""
@@ -618,6 +759,8 @@ class FlatAdam:
             # the entry points that know every flag: an option that is off is a flag not set and a NULL argument, and the flags choose
             # the kernels (finalize also writes f(applied_steps) and d_n, the update also averages -- the same three launches)
             # (and, with the report, one more behind finalize; the update does not know that flag)
+            if self._flags & (cm.OPT_SWA | cm.OPT_SWA_LR):
+                return self._step_swa(L, stream, n, scale)
             capi.check(L.avmoe_opt_grad_norm_report(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
                                                     self.max_grad_norm or 0.0, self._flags, self.betas[0], self.betas[1], stream,
                                                     None if self._sched_c is None else C.byref(self._sched_c),
@@ -638,6 +781,25 @@ class FlatAdam:
                                        C.c_float(wd), C.c_int64(self.t), C.c_float(scale),
                                        torch.cuda.current_stream(s["p"].device).cuda_stream)
                 capi.check(st, "avmoe_adam_step")
+
+    def _step_swa(self, L, stream, n, scale):
+        """the device step with stochastic weight averaging: the entry point that takes avmoe_opt_swa evaluates the annealed factor and
+        the uniform average's decay in the finalize launch; the update and the buffers' launch are those of the schedule and the
+        exponential average, so the update gets THEIR flags (AVMOE_OPT_LR_SCHEDULE for AVMOE_OPT_SWA_LR, AVMOE_OPT_EMA for AVMOE_OPT_SWA)"""
+        flags = self._flags
+        capi.check(L.avmoe_opt_grad_norm_swa(self._table_ptr, n, self._n_blocks, self._partials_ptr, self._state_ptr, scale,
+                                             self.max_grad_norm or 0.0, flags, self.betas[0], self.betas[1], stream,
+                                             None if self._sched_c is None else C.byref(self._sched_c),
+                                             None if self.ema_decay is None else C.byref(self._ema_c),
+                                             self._report.data_ptr() if self.report_grad_norms else None, C.byref(self._swa_c)),
+                   "avmoe_opt_grad_norm_swa")
+        step_flags = (flags & ~(cm.OPT_REPORT | cm.OPT_SWA | cm.OPT_SWA_LR)) | (cm.OPT_EMA if flags & cm.OPT_SWA else 0) \
+            | (cm.OPT_LR_SCHEDULE if flags & cm.OPT_SWA_LR else 0)
+        capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
+                                             self.eps, scale, step_flags, stream,
+                                             self._shadow_ptrs.data_ptr() if self._averaging else None), "avmoe_opt_adam_step_ema")
+        if self._ebufs:
+            capi.check(L.avmoe_opt_ema_buffers(*self._ebuf_args, self._state_ptr, stream), "avmoe_opt_ema_buffers")
 
     def epoch_end(self):
         self.epoch += 1
@@ -667,6 +829,8 @@ class FlatAdam:
             extra["lr_schedule"] = dataclasses.asdict(self.lr_schedule)
         if self.ema_decay is not None:
             extra.update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema=[e.detach().cpu().clone() for e in self._ema_views])
+        if self.swa_start is not None:                   # the uniform average: the same "ema" list, with the constants that say so
+            extra.update(swa_start=self.swa_start, swa_freq=self.swa_freq, ema=[e.detach().cpu().clone() for e in self._ema_views])
         if self._ebufs:
             extra.update(ema_buffers=[v.detach().cpu().clone() for v in self._ebuf_views], ema_buffer_names=self.ema_buffer_names)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
@@ -718,15 +882,23 @@ class FlatAdam:
                 raise ValueError("the state dict carries a per-step lr_schedule, which needs FlatAdam's device path: build the optimizer "
                                  "with lr_schedule (or max_grad_norm / decoupled_weight_decay / skip_nonfinite)")
             saved_sched = saved_sched if isinstance(saved_sched, LRSchedule) else LRSchedule(**saved_sched)
-        saved_ema = extra.get("ema") if self.ema_decay is not None else None
+        if extra.get("swa_start") is not None and self.swa_start is None:
+            raise ValueError("the state dict carries a uniform weight average (swa_start), which this optimizer does not keep: build it "
+                             "with swa_start (the saved swa_start / swa_freq then replace the constructor's)")
+        # averages of the other kind (an exponential average's into a uniform one, or the reverse) are not this optimizer's: re-seed
+        own_kind = (extra.get("swa_start") is not None) == (self.swa_start is not None)
+        saved_ema = extra.get("ema") if self._averaging and own_kind else None
         if saved_ema is not None:
             if len(saved_ema) != len(self._plist):
                 raise ValueError(f"state dict has {len(saved_ema)} averaged parameters, this optimizer {len(self._plist)}")
             for i, (e, (p, _si, _off, _lr0)) in enumerate(zip(saved_ema, self._plist)):
                 if tuple(e.shape) != tuple(p.shape):
                     raise ValueError(f"parameter index {i}: ema has shape {tuple(e.shape)}, the parameter {tuple(p.shape)}")
-            ema_consts = self._check_ema(self.ema_decay if extra.get("ema_decay") is None else extra["ema_decay"],
-                                         self.ema_warmup if extra.get("ema_warmup") is None else extra["ema_warmup"])
+            if self.swa_start is not None:
+                swa_consts = self._check_swa(extra["swa_start"], extra.get("swa_freq", self.swa_freq))
+            else:
+                ema_consts = self._check_ema(self.ema_decay if extra.get("ema_decay") is None else extra["ema_decay"],
+                                             self.ema_warmup if extra.get("ema_warmup") is None else extra["ema_warmup"])
         saved_bufs = extra.get("ema_buffers") if self._ebufs else None
         if saved_bufs is not None:
             names = self.ema_buffer_names
@@ -771,15 +943,18 @@ class FlatAdam:
                 self._views["skipped_steps"].fill_(int(extra.get("skipped_steps", 0)))
                 if self.lr_schedule is not None:           # what the last applied step used; the next applied step writes its own
                     self._views["lr_factor"].fill_(self.lr_schedule.factor(applied - 1) if applied > 0 else 0.0)
-                if self.ema_decay is not None:
+                if self._averaging:
                     if saved_ema is not None:
-                        self._set_ema(*ema_consts)
+                        if self.swa_start is not None:
+                            self._set_swa(*swa_consts)
+                        else:
+                            self._set_ema(*ema_consts)
                         for view, e in zip(self._ema_views, saved_ema):
                             view.copy_(e.to(torch.float32))
                     else:                                 # no averages in the dict: start them from the parameters as they are now
                         for s in self.state:
                             s["e"].copy_(s["p"])
-                    self._views["ema_decay"].fill_(self.ema_decay_at(applied, self.ema_decay, self.ema_warmup) if applied > 0 else 0.0)
+                    self._views["ema_decay"].fill_(self._decay_at(applied) if applied > 0 else 0.0)
                 if self._ebufs:
                     if saved_bufs is not None:
                         for view, e in zip(self._ebuf_views, saved_bufs):

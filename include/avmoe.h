@@ -354,8 +354,8 @@ typedef struct avmoe_opt_state {
   int64_t applied_steps;      /* steps that updated the parameters */
   int64_t skipped_steps;      /* steps held back because the norm was not finite */
   int32_t skip;               /* this step is held back */
-  float lr_factor;            /* AVMOE_OPT_LR_SCHEDULE: the schedule's factor of the last applied step (below); never written without the flag */
-  float ema_decay;            /* AVMOE_OPT_EMA: the weight average's decay d of the last applied step (below); never written without the flag */
+  float lr_factor;            /* AVMOE_OPT_LR_SCHEDULE / AVMOE_OPT_SWA_LR: the factor of the last applied step (below); never written without one of them */
+  float ema_decay;            /* AVMOE_OPT_EMA / AVMOE_OPT_SWA: the weight average's decay d of the last applied step (below); never written without one of them */
   int32_t reserved[5];
 } avmoe_opt_state;
 
@@ -526,6 +526,53 @@ size_t avmoe_opt_report_bytes(int32_t n_ranges);
 int avmoe_opt_grad_norm_report(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
                                float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched /* HOST, or NULL */,
                                const avmoe_opt_ema* ema /* HOST, or NULL */, void* report /* DEVICE, 16-byte aligned */);
+
+/* Stochastic weight averaging (added under ABI 11 like the blocks above; found by symbol): torch.optim.swa_utils on the device -- the
+ * UNIFORM average of the weights over the tail of a run (AveragedModel), and the learning rate annealed to a constant for that tail
+ * (SWALR).  Both are functions of applied_steps alone, evaluated by the finalize launch into the two words of the state block the
+ * schedule and the exponential average already use, so neither costs a launch, a counter or a host scalar that changes from step to
+ * step: the state block stays 64 bytes, a step stays 3 launches (4 with averaged buffers), replays from a captured graph, and a skipped
+ * step advances nothing.  avmoe_opt_swa holds HOST constants that are fixed for a run.
+ * AVMOE_OPT_SWA, the average.  With n = applied_steps AFTER this update (the first applied step has n = 1), N = start, c = freq:
+ *     n <  N:                     d = 0            the shadow follows the parameters
+ *     n >= N, (n - N) % c == 0:   k = (n - N) / c, d = k / (k + 1)   -- AveragedModel.update_parameters with n_averaged = k; the first
+ *                                                  averaged step copies the parameters
+ *     otherwise:                  d = 1            the shadow keeps its value
+ * d is formed in double, rounded once to fp32 and written to state->ema_decay; the number of models averaged so far is
+ * (n - N) / c + 1 for n >= N, so no counter is kept.  The update is that of AVMOE_OPT_EMA, shadow = fma(d, shadow, (1 - d) * p), by the
+ * same kernels: pass AVMOE_OPT_EMA (not AVMOE_OPT_SWA) to avmoe_opt_adam_step_ema, and call avmoe_opt_ema_buffers / avmoe_opt_swap_ema /
+ * avmoe_opt_swap_buffers as for the exponential average.  AVMOE_OPT_SWA and AVMOE_OPT_EMA in one call are refused.
+ * AVMOE_OPT_SWA_LR, the learning rate.  With n = applied_steps BEFORE this update (the schedule's convention), N' = lr_start,
+ * A = anneal_steps, s = lr_factor, base(n) = the factor of `sched` under AVMOE_OPT_LR_SCHEDULE and 1 without that flag (`sched` is then
+ * not read and may be NULL):
+ *     n <  N':  f = base(n)
+ *     n >= N':  f0 = base(N'), t = A == 0 ? 1 : min(1, (n - N') / A),
+ *               alpha = t (AVMOE_SWA_ANNEAL_LINEAR) or (1 - cos(pi t)) / 2 (AVMOE_SWA_ANNEAL_COS), f = f0 + (s - f0) * alpha
+ * -- SWALR(swa_lr = s * lr0, anneal_epochs = A) constructed when step N' is due and stepped once per applied step, in closed form.  f
+ * is evaluated in double, rounded once to fp32 and written to state->lr_factor: pass AVMOE_OPT_LR_SCHEDULE (not AVMOE_OPT_SWA_LR) to
+ * avmoe_opt_adam_step_ema.  Either flag may be used without the other; the fields of the one that is off are not read.
+ * avmoe_opt_grad_norm_swa is avmoe_opt_grad_norm_report with one more argument and knows every flag; without the two flags `swa` is not
+ * read and the call is avmoe_opt_grad_norm_report: the same kernels are launched and every written bit is the same.  The older entry
+ * points, avmoe_opt_grad_norm_report included, refuse both flags ("unknown flag").
+ * Errors (AVMOE_ERR_BAD_ARG, before any launch): either flag with swa == NULL; AVMOE_OPT_SWA with start < 1 or freq < 1, or together with
+ * AVMOE_OPT_EMA; AVMOE_OPT_SWA_LR with lr_start < 0, anneal_steps < 0, lr_factor outside [0, 1] or NaN, an unknown anneal_kind; and
+ * everything avmoe_opt_grad_norm_report refuses.  32 bytes without padding (the two periods are 32-bit).                                                          */
+enum { AVMOE_OPT_SWA = 64, AVMOE_OPT_SWA_LR = 128 };
+enum { AVMOE_SWA_ANNEAL_COS = 0, AVMOE_SWA_ANNEAL_LINEAR = 1 };
+
+typedef struct avmoe_opt_swa {
+  int64_t start;              /* N >= 1: the first applied step (counted from 1) that enters the average */
+  int64_t lr_start;           /* N' >= 0: the first step (counted from 0) of the annealed learning rate */
+  int32_t freq;               /* c >= 1: every c-th applied step from `start` on enters the average */
+  int32_t anneal_steps;       /* A >= 0: steps from base(N') to lr_factor (0: at once) */
+  float lr_factor;            /* s in [0, 1]: the factor the learning rate settles at */
+  int32_t anneal_kind;        /* AVMOE_SWA_ANNEAL_* */
+} avmoe_opt_swa;
+
+int avmoe_opt_grad_norm_swa(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
+                            float max_norm, int32_t flags, float beta1, float beta2, void* stream, const avmoe_opt_schedule* sched /* HOST, or NULL */,
+                            const avmoe_opt_ema* ema /* HOST, or NULL */, void* report /* DEVICE, 16-byte aligned, or NULL */,
+                            const avmoe_opt_swa* swa /* HOST */);
 
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the

@@ -14,6 +14,9 @@
                    (`kk_opt_ema_buffers`), whatever the number of buffers
 --ema-buffers-foreach  (with --ema) the same buffer average kept OUTSIDE the optimizer: the --ema step, then torch._foreach_lerp_ over the
                    model's fp32 buffers with the decay computed on the host, what a user had to write before --ema-buffers
+--swa              (device mode, in place of --ema) FlatAdam(swa_start=total // 4, swa_freq=5): the uniform average of stochastic weight
+                   averaging -- the launches of --ema, the decay by another rule in the finalize launch; with --schedule the schedule
+                   also anneals to a constant SWA rate from step total // 2 on (LRSchedule(swa_start=...)); goes with --ema-buffers too
 --report           (device mode) FlatAdam(report_grad_norms=True): one more launch behind finalize writes every parameter's gradient norm
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
@@ -59,6 +62,7 @@ def main():
     ap.add_argument("--ema-buffers", action="store_true")
     ap.add_argument("--ema-buffers-foreach", action="store_true")
     ap.add_argument("--report", action="store_true")
+    ap.add_argument("--swa", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -70,8 +74,12 @@ def main():
         ap.error("--report goes with --mode device")
     if a.ema and a.ema_foreach:
         ap.error("--ema and --ema-foreach are the two sides of one comparison")
-    if (a.ema_buffers or a.ema_buffers_foreach) and not a.ema:
-        ap.error("--ema-buffers / --ema-buffers-foreach go with --ema")
+    if a.swa and (a.mode != "device" or a.ema or a.ema_foreach or a.schedule_upload or a.ema_buffers_foreach):
+        ap.error("--swa goes with --mode device and is the alternative to --ema; it combines with --schedule, --ema-buffers and --report")
+    if a.ema_buffers and not (a.ema or a.swa):
+        ap.error("--ema-buffers goes with --ema or --swa")
+    if a.ema_buffers_foreach and not a.ema:
+        ap.error("--ema-buffers-foreach goes with --ema")
     if a.ema_buffers and a.ema_buffers_foreach:
         ap.error("--ema-buffers and --ema-buffers-foreach are the two sides of one comparison")
     from avmoe_amd.dp import AdapterGradReducer
@@ -83,12 +91,17 @@ def main():
     total = a.warmup + a.steps
     sched = None
     if a.schedule or a.schedule_upload:
-        sched = LRSchedule(warmup_steps=total // 4, warmup_start=0.1, decay_kind="cosine", total_steps=max(total, total // 4 + 1), min_factor=0.05)
+        swa_lr = dict(swa_start=total // 2, swa_factor=0.2, swa_anneal_steps=max(1, total // 8)) if a.swa else {}
+        sched = LRSchedule(warmup_steps=total // 4, warmup_start=0.1, decay_kind="cosine", total_steps=max(total, total // 4 + 1), min_factor=0.05,
+                           **swa_lr)
     if a.schedule:
         kw["lr_schedule"] = sched
     ema_decay, ema_warmup = 0.999, 10.0
     if a.ema:
         kw.update(ema_decay=ema_decay, ema_warmup=ema_warmup)
+    swa_start, swa_freq = max(1, total // 4), 5
+    if a.swa:
+        kw.update(swa_start=swa_start, swa_freq=swa_freq)
     if a.report:
         kw["report_grad_norms"] = True
     if a.ema_buffers:
@@ -136,6 +149,12 @@ def main():
     if a.ema:
         extra["last_ema_decay"] = float(opt.last_ema_decay.item())
         extra["want_ema_decay"] = FlatAdam.ema_decay_at(total, ema_decay, ema_warmup)
+    if a.swa:
+        extra["swa"] = "device"
+        extra["swa_models_averaged"] = FlatAdam.swa_n_averaged_at(total, swa_start, swa_freq)
+        extra["ema_minus_param_max"] = max(float((e - p).abs().max()) for e, p in zip(opt.ema_params, views))
+        extra["last_ema_decay"] = float(opt.last_ema_decay.item())
+        extra["want_ema_decay"] = FlatAdam.swa_decay_at(total, swa_start, swa_freq)
     if a.ema_buffers or a.ema_buffers_foreach:
         extra["ema_buffers"] = "device" if a.ema_buffers else "torch._foreach_lerp_ per step"
         avg = opt.ema_buffers if a.ema_buffers else buffer_shadows
