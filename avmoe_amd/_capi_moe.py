@@ -55,6 +55,11 @@ class OptBuffer(C.Structure):
     _fields_ = [("buffer", C.c_void_p), ("shadow", C.c_void_p), ("n", C.c_int64)]
 
 
+class OptSamState(C.Structure):
+    """avmoe_opt_sam_state: what avmoe_opt_sam_perturb's finalize launch leaves on the device"""
+    _fields_ = [("norm", C.c_float), ("scale", C.c_float), ("nonfinite", C.c_int32), ("reserved", C.c_int32)]
+
+
 class OptReportHeader(C.Structure):
     """avmoe_opt_report_header: what precedes the per-range norms in a report buffer"""
     _fields_ = [("first_nonfinite", C.c_int32), ("n_ranges", C.c_int32), ("reserved", C.c_int32 * 2)]
@@ -172,6 +177,11 @@ def declare(L):
         if hasattr(L, "avmoe_opt_grad_norm_swa"):     # (found by symbol: stochastic weight averaging)
             L.avmoe_opt_grad_norm_swa.restype = C.c_int
             L.avmoe_opt_grad_norm_swa.argtypes = norm_args + [C.POINTER(OptSchedule), C.POINTER(OptEma), C.c_void_p, C.POINTER(OptSwa)]
+        if hasattr(L, "avmoe_opt_adam_step_sam"):     # (found by symbol: sharpness-aware minimization)
+            L.avmoe_opt_sam_perturb.restype = L.avmoe_opt_adam_step_sam.restype = C.c_int
+            L.avmoe_opt_sam_perturb.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                                C.c_void_p]
+            L.avmoe_opt_adam_step_sam.argtypes = step_args + [C.c_void_p, C.c_void_p]
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

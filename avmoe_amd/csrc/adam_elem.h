@@ -39,15 +39,33 @@ __device__ __forceinline__ float ema_next(float avg, float x, float d) {
 // like the moments above, for the same reason: the 16-byte body and the scalar tail must round alike.
 __device__ __forceinline__ void ema_elem(float& e, float p, float d) { e = ema_next(e, p, d); }
 
+// Sharpness-aware minimization (include/avmoe.h, avmoe_opt_sam_perturb): the perturbed value p + e of one element, written ONCE for the
+// 16-byte body and the scalar tail of kk_opt_sam_perturb.  e = scale * (g * gscale), ADAPTIVE: e = (scale * (p * p)) * (g * gscale) --
+// every product rounded to fp32 in this order, contraction off, then one addition: at most four roundings in e and one in the sum.
+// e == 0 (a zero gradient, scale == 0) returns p itself, so that a signed zero keeps its bits too.
+template <bool ADAPTIVE>
+__device__ __forceinline__ float sam_elem(float p, float g, float gscale, float scale) {
+#pragma clang fp contract(off)
+  const float gr = g * gscale;
+  float e;
+  if constexpr (ADAPTIVE) e = (scale * (p * p)) * gr;
+  else e = scale * gr;
+  return e == 0.f ? p : p + e;
+}
+
 // elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail.
 // EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register, with decay d
 // (without it `ema` and `d` are not read).
-template <bool DECOUPLED, bool EMA>
+// HOLD: the element's parameter value is READ from `hold` (the unperturbed parameters avmoe_opt_sam_perturb has kept) and the result is
+// written to `p`, which is only written (without it `hold` is not read).  The arithmetic is the same calls on the same values.
+template <bool DECOUPLED, bool EMA, bool HOLD = false>
 __device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long i0,
                                           long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale,
-                                          float* __restrict__ ema, float d) {
+                                          float* __restrict__ ema, float d, const float* __restrict__ hold = nullptr) {
   if (i0 + 3 < n) {
-    float4 pp = *(float4*)(p + i0), mm = *(float4*)(m + i0), vv = *(float4*)(v + i0);
+    float4 pp, mm = *(float4*)(m + i0), vv = *(float4*)(v + i0);
+    if constexpr (HOLD) pp = *(const float4*)(hold + i0);
+    else pp = *(float4*)(p + i0);
     const float4 gg = *(const float4*)(g + i0);
     float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; const float* G = (const float*)&gg;
 #pragma unroll
@@ -62,8 +80,15 @@ __device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __
     }
   } else {
     for (long i = i0; i < n; ++i) {
-      adam_elem<DECOUPLED>(p[i], m[i], v[i], g[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
-      if constexpr (EMA) ema_elem(ema[i], p[i], d);
+      if constexpr (HOLD) {
+        float pv = hold[i];
+        adam_elem<DECOUPLED>(pv, m[i], v[i], g[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+        p[i] = pv;
+        if constexpr (EMA) ema_elem(ema[i], pv, d);
+      } else {
+        adam_elem<DECOUPLED>(p[i], m[i], v[i], g[i], lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+        if constexpr (EMA) ema_elem(ema[i], p[i], d);
+      }
     }
   }
 }

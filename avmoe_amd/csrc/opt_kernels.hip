@@ -21,6 +21,13 @@
 // 4-byte aligned), a table of {buffer, shadow, n} records of its own with one launch per step and one beside it --
 //   kk_opt_ema_buffers                     behind the update: shadow = d shadow + (1 - d) buffer with the state block's d and skip flag
 //   kk_opt_swap_buffers                    exchanges every buffer with its shadow, beside kk_opt_swap
+// and, for sharpness-aware minimization (include/avmoe.h, avmoe_opt_sam_perturb), three launches after the FIRST backward pass of a step --
+//   kk_opt_sqsum (or kk_opt_sqsum_adaptive: of |p| * grad)   the norm pass of the perturbing gradient, into the same partial-sum workspace
+//   kk_opt_sam_finalize                    one block adds the partial sums in finalize's order and writes the 16-byte SAM block: norm,
+//                                          scale = rho / (norm + 1e-12), nonfinite
+//   kk_opt_sam_perturb<ADAPTIVE>           hold = p ; p = p + e for every element of every range, in a hold buffer per range (as the shadows)
+// -- and kk_opt_adam<..., HOLD> for the step behind the second backward pass: it reads every p from hold and writes it to param, so the
+// unperturbed parameters come back exactly (a copy, not p + e - e); a skipped step writes param = hold and nothing else
 // The per-range norms are a kernel of their own, next to finalize, and not a part of it: finalize is ONE block whose additions define the
 // bits of total_norm, and a model has thousands of ranges -- a wave per range over many blocks finishes them in the time finalize takes,
 // inside finalize they would wait on one block's 256 threads and stretch the serial part of every step.  Finalize only resets the
@@ -47,6 +54,7 @@ struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
 struct OptBlock { int32_t range, block; };
 static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
 static_assert(sizeof(avmoe_opt_report_header) == 16, "report layout");
+static_assert(sizeof(avmoe_opt_sam_state) == 16, "SAM block layout");
 static_assert(sizeof(avmoe_opt_swa) == 32 && sizeof(avmoe_opt_schedule) == 40 && sizeof(avmoe_opt_ema) == 8, "constants of a run");
 
 // What a thread of a one-block-per-table-block launch serves: elements [i0, min(i0 + 4, r.n)) of range `range`.
@@ -99,6 +107,37 @@ __global__ void __launch_bounds__(256) kk_opt_sqsum(const void* __restrict__ tab
   }
   const double sum = block_sum_256(acc);
   if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// sum over the block's elements of ((double)(|param| * grad) * grad_scale)^2 -> partials[blockIdx.x]: the norm pass of the adaptive
+// perturbation (ASAM's T_w g with T_w = |w|).  |p| * g is one fp32 product, as the perturbation kernel forms its factors; the rest is
+// kk_opt_sqsum.  The parameters are only read.
+__global__ void __launch_bounds__(256) kk_opt_sqsum_adaptive(const void* __restrict__ table, double* __restrict__ partials, float grad_scale) {
+  OptWork w;
+  double acc = 0.0;
+  if (opt_work(table, w)) {
+    const avmoe_opt_range& r = w.r;
+    const long i0 = w.i0;
+    const double gs = (double)grad_scale;
+    if (i0 + 3 < r.n) {
+      const float4 g = *(const float4*)(r.grad + i0), p = *(const float4*)(r.param + i0);
+      const double a = (double)(fabsf(p.x) * g.x) * gs, c = (double)(fabsf(p.y) * g.y) * gs, d = (double)(fabsf(p.z) * g.z) * gs,
+                   e = (double)(fabsf(p.w) * g.w) * gs;
+      acc = a * a + c * c + d * d + e * e;
+    } else {
+      for (long i = i0; i < r.n; ++i) { const double a = (double)(fabsf(r.param[i]) * r.grad[i]) * gs; acc += a * a; }
+    }
+  }
+  const double sum = block_sum_256(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// One block: the sum of the partial sums.  Thread t adds partials[t], partials[t + 256], ... in that order, the 256 sums go through the
+// tree above: a fixed order, written ONCE for kk_opt_finalize and kk_opt_sam_finalize, so both get the same bits from the same partials.
+__device__ __forceinline__ double opt_total_256(const double* __restrict__ partials, long n_partials) {
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
+  return block_sum_256(acc);
 }
 
 // the factor of a per-step schedule at n applied steps (include/avmoe.h, avmoe_opt_schedule), in double.  Contraction is off so that the
@@ -161,8 +200,8 @@ __device__ __forceinline__ double swa_lr_factor(const avmoe_opt_schedule& s, con
   return f0 + (to - f0) * alpha;
 }
 
-// One block.  Thread t adds partials[t], partials[t + 256], ... in that order, the 256 sums go through the same tree as above: a fixed
-// order.  n_partials == 0 (neither clipping nor skipping asked for): the norm is reported as 0 and only the counters advance.
+// One block.  The partial sums are added by opt_total_256: a fixed order.  n_partials == 0 (neither clipping nor skipping asked for): the
+// norm is reported as 0 and only the counters advance.
 // SCHED: the step that is applied now is number n = applied_steps before it (the first one has n = 0); its factor goes into the state
 // block, rounded once to fp32.  A skipped step leaves the factor alone.
 // EMA: the average's decay for this step, from n = applied_steps AFTER it (the first one has n = 1), likewise.
@@ -175,9 +214,7 @@ __global__ void __launch_bounds__(256) kk_opt_finalize(const double* __restrict_
                                                        float max_norm, int clip, int skip_nonfinite, float beta1, float beta2,
                                                        avmoe_opt_schedule sched, avmoe_opt_ema ema, avmoe_opt_report_header* __restrict__ report,
                                                        int n_ranges, avmoe_opt_swa swa) {
-  double acc = 0.0;
-  for (long i = threadIdx.x; i < n_partials; i += 256) acc += partials[i];
-  const double sum = block_sum_256(acc);
+  const double sum = opt_total_256(partials, n_partials);
   if (threadIdx.x != 0) return;
   if (report) *report = avmoe_opt_report_header{-1, n_ranges, {0, 0}};
   const float total = (float)sqrt(sum);
@@ -247,15 +284,35 @@ __device__ __forceinline__ float* opt_shadow(const OptWork& w, float* const* __r
   return ((uintptr_t)e & 15u) == 0 ? e : nullptr;
 }
 
+// param[i] = hold[i] for elements [i0, min(i0 + 4, n)) of one range: what a skipped step under HOLD does
+__device__ __forceinline__ void restore_quad(float* __restrict__ p, const float* __restrict__ h, long i0, long n) {
+  if (i0 + 3 < n) {
+    *(float4*)(p + i0) = *(const float4*)(h + i0);
+  } else {
+    for (long i = i0; i < n; ++i) p[i] = h[i];
+  }
+}
+
 // SCHED: the range's rate times the state block's lr_factor, for the update and for the decoupled decay term alike
 // EMA: shadows[range] is the range's average; the state block's ema_decay is this step's d
-template <bool DECOUPLED, bool SCHED, bool EMA>
+// HOLD: hold[range] holds the range's unperturbed parameters (kk_opt_sam_perturb): every p is read from there and written to param; a
+// skipped step writes param = hold and nothing else
+template <bool DECOUPLED, bool SCHED, bool EMA, bool HOLD>
 __global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
-                                                   float eps, float grad_scale, float* const* __restrict__ shadows, int n_shadows) {
-  if (state->skip) return;                              // a skipped step writes nothing: p, m, v (and the average) stay bit for bit
+                                                   float eps, float grad_scale, float* const* __restrict__ shadows, int n_shadows,
+                                                   float* const* __restrict__ hold) {
+  if constexpr (!HOLD) {
+    if (state->skip) return;                            // a skipped step writes nothing: p, m, v (and the average) stay bit for bit
+  }
   OptWork w;
   if (!opt_work(table, w)) return;
   const avmoe_opt_range& r = w.r;
+  const float* h = nullptr;
+  if constexpr (HOLD) {
+    h = opt_shadow(w, hold, n_shadows);
+    if (!h) return;
+    if (state->skip) { restore_quad(r.param, h, w.i0, (long)r.n); return; }
+  }
   float lr = r.lr;
   if constexpr (SCHED) lr *= state->lr_factor;
   float* e = nullptr;
@@ -266,8 +323,52 @@ __global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ tabl
     d = state->ema_decay;
   }
   // one multiplier for the gradient: grad_scale * clip factor (== grad_scale exactly when the factor is 1)
-  adam_quad<DECOUPLED, EMA>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, w.i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
-                            grad_scale * state->clip_coef, e, d);
+  adam_quad<DECOUPLED, EMA, HOLD>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, w.i0, (long)r.n, lr, b1, b2, eps, r.weight_decay, state->bc1,
+                                  state->bc2_sqrt, grad_scale * state->clip_coef, e, d, h);
+}
+
+// One block: the SAM block from the partial sums of the perturbing gradient's norm pass.  The sum, the square root and its rounding are
+// those of kk_opt_finalize, so `norm` has the bits total_norm gets from the same partial sums.
+__global__ void __launch_bounds__(256) kk_opt_sam_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_sam_state* __restrict__ sam,
+                                                           float rho) {
+  const double sum = opt_total_256(partials, n_partials);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(sum);
+  const bool fin = isfinite(norm);
+  *sam = avmoe_opt_sam_state{norm, fin ? (float)((double)rho / ((double)norm + 1e-12)) : 0.f, fin ? 0 : 1, 0};
+}
+
+// hold[i] = param[i], then param[i] = param[i] + e (sam_elem, adam_elem.h) for every element of every range; with the block's
+// `nonfinite` set only hold is written.  Gradients are only read; alignment padding belongs to no range and is not touched.
+template <bool ADAPTIVE>
+__global__ void __launch_bounds__(256) kk_opt_sam_perturb(const void* __restrict__ table, const avmoe_opt_sam_state* __restrict__ sam, float grad_scale,
+                                                          float* const* __restrict__ hold, int n_hold) {
+  OptWork w;
+  if (!opt_work(table, w)) return;
+  float* __restrict__ h = opt_shadow(w, hold, n_hold);
+  if (!h) return;
+  const float scale = sam->scale;
+  const bool move = sam->nonfinite == 0;
+  float* __restrict__ p = w.r.param;
+  const float* __restrict__ g = w.r.grad;
+  const long i0 = w.i0, n = w.r.n;
+  if (i0 + 3 < n) {
+    float4 pp = *(const float4*)(p + i0);
+    const float4 gg = *(const float4*)(g + i0);
+    *(float4*)(h + i0) = pp;
+    if (move) {
+      float* P = (float*)&pp; const float* G = (const float*)&gg;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) P[k] = sam_elem<ADAPTIVE>(P[k], G[k], grad_scale, scale);
+      *(float4*)(p + i0) = pp;
+    }
+  } else {
+    for (long i = i0; i < n; ++i) {
+      const float a = p[i];
+      h[i] = a;
+      if (move) p[i] = sam_elem<ADAPTIVE>(a, g[i], grad_scale, scale);
+    }
+  }
 }
 
 // param[i] <-> shadow[i] for every element of every range; alignment padding belongs to no range and is not touched
@@ -358,12 +459,16 @@ __global__ void __launch_bounds__(256) kk_opt_swap_buffers(const void* __restric
 
 // the instantiations, indexed by the flag bits: an option more is a template parameter more and an initialiser twice as long
 using FinalizeKernel = decltype(&kk_opt_finalize<false, false>);
-using AdamKernel = decltype(&kk_opt_adam<false, false, false>);
+using AdamKernel = decltype(&kk_opt_adam<false, false, false, false>);
 constexpr FinalizeKernel OPT_FINALIZE[4] = {   // [SCHED | EMA << 1]
     kk_opt_finalize<false, false>, kk_opt_finalize<true, false>, kk_opt_finalize<false, true>, kk_opt_finalize<true, true>};
-constexpr AdamKernel OPT_ADAM[8] = {           // [DECOUPLED | SCHED << 1 | EMA << 2]
-    kk_opt_adam<false, false, false>, kk_opt_adam<true, false, false>, kk_opt_adam<false, true, false>, kk_opt_adam<true, true, false>,
-    kk_opt_adam<false, false, true>,  kk_opt_adam<true, false, true>,  kk_opt_adam<false, true, true>,  kk_opt_adam<true, true, true>};
+constexpr AdamKernel OPT_ADAM[16] = {          // [DECOUPLED | SCHED << 1 | EMA << 2 | HOLD << 3]
+    kk_opt_adam<false, false, false, false>, kk_opt_adam<true, false, false, false>, kk_opt_adam<false, true, false, false>,
+    kk_opt_adam<true, true, false, false>,   kk_opt_adam<false, false, true, false>, kk_opt_adam<true, false, true, false>,
+    kk_opt_adam<false, true, true, false>,   kk_opt_adam<true, true, true, false>,   kk_opt_adam<false, false, false, true>,
+    kk_opt_adam<true, false, false, true>,   kk_opt_adam<false, true, false, true>,  kk_opt_adam<true, true, false, true>,
+    kk_opt_adam<false, false, true, true>,   kk_opt_adam<true, false, true, true>,   kk_opt_adam<false, true, true, true>,
+    kk_opt_adam<true, true, true, true>};
 
 static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
 
@@ -484,6 +589,12 @@ static int check_shadows(const char* who, float* const* shadows) {
   return OK;
 }
 
+static int check_hold(const char* who, float* const* hold) {
+  if (!hold) { set_last_error("%s: the hold pointer array is NULL", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)hold & 7u) != 0) { set_last_error("%s: the hold pointer array must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+  return OK;
+}
+
 constexpr int32_t OPT_FLAGS = AVMOE_OPT_CLIP | AVMOE_OPT_SKIP_NONFINITE | AVMOE_OPT_DECOUPLED_DECAY;
 constexpr int OPT_REPORT_MAX_GRID = 1024;        // blocks of 4 waves: more ranges than 4096 take a second round
 
@@ -536,17 +647,20 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
   return OK;
 }
 
-// avmoe_opt_adam_step (shadows == NULL, the flag unknown) and avmoe_opt_adam_step_ema: the same checks, then the update kernel the flags ask for
+// avmoe_opt_adam_step (shadows == NULL, the flag unknown), avmoe_opt_adam_step_ema and avmoe_opt_adam_step_sam (with_hold: the HOLD
+// instantiations): the same checks, then the update kernel the flags ask for
 static int adam_step(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
-                     float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, void* stream) {
+                     float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, bool with_hold, float* const* hold,
+                     void* stream) {
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
   if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
   if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("%s: eps must be >= 0, grad_scale not NaN", who); return ERR_BAD_ARG; }
   const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
   if (ema) AVMOE_TRY(check_shadows(who, shadows));
+  if (with_hold) AVMOE_TRY(check_hold(who, hold));
   if (n_blocks == 0) return OK;
-  hipLaunchKernelGGL(OPT_ADAM[(int)dec | (int)sched << 1 | (int)ema << 2], dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state,
-                     beta1, beta2, eps, grad_scale, shadows, (int)n_ranges);
+  hipLaunchKernelGGL(OPT_ADAM[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
+                     (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale, shadows, (int)n_ranges, with_hold ? hold : nullptr);
   AVMOE_CHECK_LAUNCH("opt_adam");
   return OK;
 }
@@ -601,7 +715,7 @@ int avmoe_opt_grad_norm_sched(const void* table, int32_t n_ranges, int64_t n_blo
 int avmoe_opt_adam_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
                         float grad_scale, int32_t flags, void* stream) {
   return adam_step("avmoe_opt_adam_step", table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE, nullptr,
-                   stream);
+                   false, nullptr, stream);
 }
 
 int avmoe_opt_grad_norm_ema(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_state* state, float grad_scale,
@@ -634,7 +748,39 @@ int avmoe_opt_grad_norm_swa(const void* table, int32_t n_ranges, int64_t n_block
 int avmoe_opt_adam_step_ema(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
                             float grad_scale, int32_t flags, void* stream, float* const* shadows) {
   return adam_step("avmoe_opt_adam_step_ema", table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags,
-                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, shadows, stream);
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, shadows, false, nullptr, stream);
+}
+
+int avmoe_opt_sam_perturb(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_sam_state* sam, float grad_scale, float rho,
+                          int32_t adaptive, float* const* hold, void* stream) {
+  const char* who = "avmoe_opt_sam_perturb";
+  if (!sam) { set_last_error("%s: NULL sam block", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)sam & 15u) != 0) { set_last_error("%s: the sam block must be 16-byte aligned", who); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_table_args(who, table, n_ranges, n_blocks));
+  if (!(rho >= 0.f) || std::isinf(rho)) { set_last_error("%s: rho must be >= 0 and finite", who); return ERR_BAD_ARG; }
+  if (!(grad_scale == grad_scale)) { set_last_error("%s: grad_scale is NaN", who); return ERR_BAD_ARG; }
+  if (adaptive != 0 && adaptive != 1) { set_last_error("%s: adaptive must be 0 or 1, not %d", who, (int)adaptive); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_hold(who, hold));
+  if (n_blocks > 0) {
+    if (!partials) { set_last_error("%s: partials is NULL", who); return ERR_BAD_ARG; }
+    if (((uintptr_t)partials & 7u) != 0) { set_last_error("%s: partials must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+    hipLaunchKernelGGL(adaptive ? kk_opt_sqsum_adaptive : kk_opt_sqsum, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, partials,
+                       grad_scale);
+    AVMOE_CHECK_LAUNCH("opt_sqsum");
+  }
+  hipLaunchKernelGGL(kk_opt_sam_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)partials, (long)n_blocks, sam, rho);
+  AVMOE_CHECK_LAUNCH("opt_sam_finalize");
+  if (n_blocks == 0) return OK;
+  hipLaunchKernelGGL(adaptive ? kk_opt_sam_perturb<true> : kk_opt_sam_perturb<false>, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table,
+                     (const avmoe_opt_sam_state*)sam, grad_scale, hold, (int)n_ranges);
+  AVMOE_CHECK_LAUNCH("opt_sam_perturb");
+  return OK;
+}
+
+int avmoe_opt_adam_step_sam(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
+                            float grad_scale, int32_t flags, void* stream, float* const* shadows, float* const* hold) {
+  return adam_step("avmoe_opt_adam_step_sam", table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags,
+                   OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, shadows, true, hold, stream);
 }
 
 int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, float* const* shadows, void* stream) {

@@ -11,7 +11,11 @@
                                BatchNorm running statistics averaged and swapped with them (`ema_buffers=model`);
                                stochastic weight averaging (`swa_start` / `swa_freq`: torch's AveragedModel as that same average
                                with a uniform rule, SWALR as a part of `LRSchedule`), still without a launch more;
-                               per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter
+                               per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter;
+                               sharpness-aware minimization (`sam_rho`, `sam_adaptive`: `sam_perturb()` between the two backward
+                               passes of a step, the unperturbed weights kept on the device and restored exactly by `step()`)
+  * `hold_bn_stats`         -- a context in which training-mode forward passes leave the BatchNorm running statistics alone (SAM's
+                               second pass)
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
   * `reestimate_bn`         -- BatchNorm statistics re-estimated with forward passes (momentum=None, torch's update_bn), for the
@@ -23,7 +27,7 @@
                                net_trans_v3.py:560-563)
 
 Everything here is host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm[_sched|_ema|_report|_swa] /
-avmoe_opt_adam_step[_ema] / avmoe_opt_swap_ema, avmoe_opt_ema_buffers / avmoe_opt_swap_buffers, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
+avmoe_opt_adam_step[_ema|_sam] / avmoe_opt_swap_ema / avmoe_opt_sam_perturb, avmoe_opt_ema_buffers / avmoe_opt_swap_buffers, avmoe_expert_histogram); nothing falls back to the CPU for GPU tensors."""
 from __future__ import annotations
 
 import contextlib
@@ -268,6 +272,40 @@ class FlatAdam:
         ...
         if int(opt.skipped_steps) > seen: print("skipped by", names[int(opt.first_nonfinite_param)])
 
+    Sharpness-aware minimization.  `sam_rho=rho` (SAM, Foret et al. 2021; `sam_adaptive=True`: ASAM, Kwon et al. 2021; it selects the
+    device path too) lets a step use the gradient at w + e, the worst point of the rho-ball around the weights that a first gradient g
+    points to: e = rho g / ||g||, adaptive e = rho w^2 g / || |w| g ||.  A step is then two backward passes with `sam_perturb()` between
+    them:
+
+        red.begin(sync); loss_fn(model(batch)).backward(); red.finish()
+        opt.sam_perturb()                                   # w <- w + e, the originals kept on the device
+        red.zero_grad(lazy=True); red.begin(sync)
+        with hold_bn_stats(model): loss_fn(model(batch)).backward()
+        red.finish(); opt.step()                            # w restored exactly, then Adam with the gradient at w + e
+
+    `sam_perturb()` is three launches for ALL buckets (include/avmoe.h, avmoe_opt_sam_perturb): the norm pass of the step over the first
+    gradient (adaptive: over |w| g), a one-block finalize that leaves norm, scale = rho / (norm + 1e-12) and a non-finite flag in a
+    16-byte block on the device, and one pass that copies every parameter into a flat HOLD buffer per bucket (the bucket's layout once
+    more, like the averages) and adds e in place -- the sites see the perturbed weights through the pointers they cache.  It uses the
+    gradient scale of `step()`.  The `step()` behind it makes its usual norm call on the SECOND gradient (clipping, skipping, schedule,
+    averages: all unchanged) and then ONE update launch that reads every parameter from the hold buffer and writes it to the parameter:
+    the weights the update starts from are the unperturbed ones bit for bit (a copy, where w + e - e would drift), parameters, moments
+    and averages get the bits a step without SAM gets from the same gradient, and the launches of a step are those without SAM.  A step
+    that is skipped (`skip_nonfinite`) still writes the held weights back.  A first gradient that is not finite perturbs nothing
+    (`sam_nonfinite` is 1, `last_sam_scale` 0) and the step goes on as usual; a zero one leaves every bit.  No host synchronisation and
+    no step-dependent host scalar: both calls can be captured into graphs.  `step()` without a `sam_perturb()` before it is the step
+    without SAM, with the same calls -- SAM on every k-th step is the caller's `if`.  `sam_restore()` abandons a perturbation in one
+    launch.  `perturbed` is host state; `last_sam_norm`, `last_sam_scale`, `sam_nonfinite` are DEVICE views of the 16-byte block.  While
+    perturbed, `swap_ema()`, `ema_weights()`, `state_dict()`, `load_state_dict()`, a second `sam_perturb()` and
+    `adapter_state_dict(..., ema=opt)` / `save_adapters(..., ema=opt)` raise RuntimeError.  `state_dict()` carries "sam_rho" and
+    "sam_adaptive" under "flat_adam" (the hold buffers are transient: no tensor state) and `load_state_dict()` into an optimizer built
+    with `sam_rho` restores them; a dict without them loads as before.  The second pass must not advance the BatchNorm running
+    statistics a second time, and on perturbed weights: run it inside `hold_bn_stats(model)`.
+    Under data parallelism `sam_perturb()` after `red.finish()` perturbs with the averaged gradient, identically on every rank -- two
+    all-reduces per step; after `red.begin(sync=False)` for the first pass each rank perturbs with its own gradient (m-sharpness), which
+    is safe because the weights come back from the hold buffers and not by subtraction: the ranks' weights agree again after `step()`.
+    NOT covered: the plain (non-device) path, a per-group rho, parameters outside the reducer.
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -282,7 +320,8 @@ class FlatAdam:
                  step_size: Optional[int] = None, gamma: float = 0.1, grad_scale: float = 1.0, param_groups=None,
                  max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
                  lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
-                 report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1):
+                 report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1,
+                 sam_rho: Optional[float] = None, sam_adaptive: bool = False):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -290,9 +329,10 @@ class FlatAdam:
         each parameter's gradient norm and the index of the first non-finite one on the device (`last_param_grad_norms`,
         `first_nonfinite_param`).  swa_start: keep the uniform average of the parameters over the applied steps swa_start,
         swa_start + swa_freq, ... (integers >= 1, steps counted from 1; class docstring, "Stochastic weight averaging") in place of the
-        exponential one: giving it together with `ema_decay` raises ValueError.  Any of the seven selects the device path (class
-        docstring); with all at their defaults step() is the
-        per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
+        exponential one: giving it together with `ema_decay` raises ValueError.  sam_rho: the radius rho >= 0 (held as fp32) of
+        sharpness-aware minimization, `sam_perturb()` between two backward passes (class docstring); sam_adaptive: its adaptive form
+        (ValueError without `sam_rho`).  Any of the eight selects the device path (class docstring); with all at their defaults step()
+        is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
         and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
@@ -318,6 +358,8 @@ class FlatAdam:
         if self.swa_start is not None and self.ema_decay is not None:
             raise ValueError("swa_start and ema_decay are alternatives: the optimizer keeps one average of the weights")
         self._swapped = False                            # the parameters currently hold the averages (swap_ema / ema_weights)
+        self.sam_rho, self.sam_adaptive = self._check_sam(sam_rho, sam_adaptive)
+        self._perturbed = False                          # the parameters currently hold w + e, the hold buffers w (sam_perturb)
         self.report_grad_norms = bool(report_grad_norms)
         self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
@@ -347,9 +389,11 @@ class FlatAdam:
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
             if self._averaging:                          # the averages: the bucket's layout once more, padding zero
                 self.state[-1]["e"] = flat_p.clone()
+            if self.sam_rho is not None:                 # the hold buffers: the bucket's layout once more, written by every sam_perturb()
+                self.state[-1]["h"] = torch.zeros_like(flat_p)
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
-            or self._averaging or self.report_grad_norms
+            or self._averaging or self.report_grad_norms or self.sam_rho is not None
         if self._device:
             self._build_device_state()
 
@@ -525,6 +569,7 @@ class FlatAdam:
         second launch exchanges the buffers (BatchNorm running statistics) with their averages, in place: no `module._buffers` entry is
         re-bound.  Without it buffers stay as they are."""
         self._need_ema("swap_ema")
+        self._not_perturbed("swap_ema()")
         stream = torch.cuda.current_stream(self._dev).cuda_stream
         capi.check(capi.lib().avmoe_opt_swap_ema(self._table_ptr, len(self._plist), self._n_blocks, self._shadow_ptrs.data_ptr(), stream),
                    "avmoe_opt_swap_ema")
@@ -541,6 +586,7 @@ class FlatAdam:
         an evaluation inside sees the raw weights' statistics."""
         self._need_ema("ema_weights")
         self._not_swapped("ema_weights()")
+        self._not_perturbed("ema_weights()")
         self.swap_ema()
         try:
             yield self
@@ -550,6 +596,100 @@ class FlatAdam:
     def _not_swapped(self, what):
         if self._swapped:
             raise RuntimeError(f"FlatAdam.{what} while the averaged weights are swapped in (swap_ema / ema_weights): swap back first")
+
+    # ---- sharpness-aware minimization -----------------------------------------------------------------------------
+    @staticmethod
+    def _check_sam(rho, adaptive):
+        """-> (rho as the fp32 value the device gets, adaptive), or (None, False) when SAM is off"""
+        if rho is None:
+            if adaptive:
+                raise ValueError("sam_adaptive needs sam_rho: the adaptive perturbation has a radius too")
+            return None, False
+        r = float(rho)
+        if not (r >= 0.0) or math.isinf(r) or r > 3.4028234663852886e38:
+            raise ValueError(f"sam_rho must be a finite number >= 0 (as fp32), not {rho!r}")
+        return _f32(r), bool(adaptive)
+
+    def _need_sam(self, what):
+        if self.sam_rho is None:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs sam_rho")
+
+    def _not_perturbed(self, what):
+        if self._perturbed:
+            raise RuntimeError(f"FlatAdam.{what} while the weights are perturbed (sam_perturb): call step() or sam_restore() first")
+
+    def _build_sam(self):
+        """the device array of one hold pointer per range, beside the shadows', and the 16-byte block sam_perturb()'s finalize writes"""
+        if not hasattr(capi.lib(), "avmoe_opt_adam_step_sam"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks sharpness-aware minimization (avmoe_opt_sam_perturb): rebuild it")
+        ptrs = [self.state[si]["h"].data_ptr() + 4 * off for _p, si, off, _lr0 in self._plist]
+        if any(q % 16 for q in ptrs):
+            raise capi.AvmoeError("FlatAdam: a hold range is not 16-byte aligned")
+        self._hold_ptrs = torch.tensor(ptrs, dtype=torch.int64).to(self._dev)
+        self._sam_block = torch.zeros(C.sizeof(cm.OptSamState), dtype=torch.uint8, device=self._dev)
+        self._sam_views = {"norm": self._sam_block[0:4].view(torch.float32)[0], "scale": self._sam_block[4:8].view(torch.float32)[0],
+                           "nonfinite": self._sam_block[8:12].view(torch.int32)[0]}
+
+    @property
+    def perturbed(self) -> bool:
+        """host state: sam_perturb() has moved the weights and neither step() nor sam_restore() has brought them back yet"""
+        return self._perturbed
+
+    @property
+    def last_sam_norm(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the norm of (gradient * grad_scale) the last sam_perturb() saw (adaptive: of |w| * gradient * grad_scale).
+        A view of the 16-byte SAM block: `.item()` is the caller's synchronisation.  Only with `sam_rho`."""
+        self._need_sam("last_sam_norm")
+        return self._sam_views["norm"]
+
+    @property
+    def last_sam_scale(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: rho / (norm + 1e-12) of the last sam_perturb(), formed in double and rounded once; 0 where the norm was
+        not finite.  Only with `sam_rho`."""
+        self._need_sam("last_sam_scale")
+        return self._sam_views["scale"]
+
+    @property
+    def sam_nonfinite(self) -> torch.Tensor:
+        """int32 DEVICE scalar: 1 where the last sam_perturb() found a norm that is Inf or NaN and left the weights as they were."""
+        self._need_sam("sam_nonfinite")
+        return self._sam_views["nonfinite"]
+
+    def sam_perturb(self):
+        """Moves every parameter the optimizer holds to w + e with the gradient the buckets hold now (class docstring, "Sharpness-aware
+        minimization") and keeps w in the hold buffers: three launches on the current stream, no synchronisation.  The next step()
+        updates w; sam_restore() gives w back without a step.  A second call before either raises RuntimeError."""
+        self._need_sam("sam_perturb()")
+        self._not_swapped("sam_perturb()")
+        self._not_perturbed("sam_perturb()")
+        scale = self.grad_scale * float(getattr(self.reducer, "grad_scale", 1.0))        # what step() hands its kernels
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        capi.check(capi.lib().avmoe_opt_sam_perturb(self._table_ptr, len(self._plist), self._n_blocks, self._partials_ptr,
+                                                    self._sam_block.data_ptr(), scale, self.sam_rho, int(self.sam_adaptive),
+                                                    self._hold_ptrs.data_ptr(), stream), "avmoe_opt_sam_perturb")
+        self._perturbed = True
+
+    def sam_restore(self):
+        """Abandons a perturbation: ONE launch on the current stream (avmoe_opt_swap_ema with the hold buffers) gives every parameter
+        its unperturbed value back bit for bit.  Raises RuntimeError when the weights are not perturbed."""
+        self._need_sam("sam_restore()")
+        if not self._perturbed:
+            raise RuntimeError("FlatAdam.sam_restore() without a perturbation: call sam_perturb() first")
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        capi.check(capi.lib().avmoe_opt_swap_ema(self._table_ptr, len(self._plist), self._n_blocks, self._hold_ptrs.data_ptr(), stream),
+                   "avmoe_opt_swap_ema")
+        self._perturbed = False
+
+    def _update(self, L, stream, n, scale, flags, shadows):
+        """the update launch of a device step: avmoe_opt_adam_step_ema, or behind a sam_perturb() avmoe_opt_adam_step_sam, which reads
+        the parameters from the hold buffers and so brings the unperturbed weights back"""
+        if self._perturbed:
+            capi.check(L.avmoe_opt_adam_step_sam(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
+                                                 self.eps, scale, flags, stream, shadows, self._hold_ptrs.data_ptr()), "avmoe_opt_adam_step_sam")
+            self._perturbed = False
+            return
+        capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
+                                             self.eps, scale, flags, stream, shadows), "avmoe_opt_adam_step_ema")
 
     # ---- the device path ------------------------------------------------------------------------------------------
     def _opt_ranges(self):
@@ -591,6 +731,8 @@ class FlatAdam:
             self._build_buffer_table()
         if self.report_grad_norms:
             self._build_report()
+        if self.sam_rho is not None:
+            self._build_sam()
 
     def _build_report(self):
         """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
@@ -766,9 +908,7 @@ class FlatAdam:
                                                     None if self._sched_c is None else C.byref(self._sched_c),
                                                     None if self.ema_decay is None else C.byref(self._ema_c),
                                                     self._report.data_ptr() if self.report_grad_norms else None), "avmoe_opt_grad_norm_report")
-            capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
-                                                 self.eps, scale, self._flags & ~cm.OPT_REPORT, stream,
-                                                 None if self.ema_decay is None else self._shadow_ptrs.data_ptr()), "avmoe_opt_adam_step_ema")
+            self._update(L, stream, n, scale, self._flags & ~cm.OPT_REPORT, None if self.ema_decay is None else self._shadow_ptrs.data_ptr())
             if self._ebufs:                              # one launch more: the buffers' averages, with the d_n and skip flag finalize has left
                 capi.check(L.avmoe_opt_ema_buffers(*self._ebuf_args, self._state_ptr, stream),
                            "avmoe_opt_ema_buffers")
@@ -795,9 +935,7 @@ class FlatAdam:
                    "avmoe_opt_grad_norm_swa")
         step_flags = (flags & ~(cm.OPT_REPORT | cm.OPT_SWA | cm.OPT_SWA_LR)) | (cm.OPT_EMA if flags & cm.OPT_SWA else 0) \
             | (cm.OPT_LR_SCHEDULE if flags & cm.OPT_SWA_LR else 0)
-        capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
-                                             self.eps, scale, step_flags, stream,
-                                             self._shadow_ptrs.data_ptr() if self._averaging else None), "avmoe_opt_adam_step_ema")
+        self._update(L, stream, n, scale, step_flags, self._shadow_ptrs.data_ptr() if self._averaging else None)
         if self._ebufs:
             capi.check(L.avmoe_opt_ema_buffers(*self._ebuf_args, self._state_ptr, stream), "avmoe_opt_ema_buffers")
 
@@ -811,6 +949,7 @@ class FlatAdam:
         """torch.optim.Adam's format (class docstring).  A parameter's `step` is `self.t` on the plain path and `applied_steps` on the
         device path -- reading it makes state_dict() a synchronisation point, as the copies of the moments to the CPU are anyway."""
         self._not_swapped("state_dict()")
+        self._not_perturbed("state_dict()")
         applied = int(self.applied_steps.item()) if self._device else self.t
         skipped = int(self.skipped_steps.item()) if self._device else 0
         state = {}
@@ -833,6 +972,8 @@ class FlatAdam:
             extra.update(swa_start=self.swa_start, swa_freq=self.swa_freq, ema=[e.detach().cpu().clone() for e in self._ema_views])
         if self._ebufs:
             extra.update(ema_buffers=[v.detach().cpu().clone() for v in self._ebuf_views], ema_buffer_names=self.ema_buffer_names)
+        if self.sam_rho is not None:                     # constants only: the hold buffers are transient
+            extra.update(sam_rho=self.sam_rho, sam_adaptive=self.sam_adaptive)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
             extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
@@ -846,8 +987,11 @@ class FlatAdam:
         which replace the constructor's) are restored; a dict without them re-seeds the averages from the CURRENT parameters, so load the
         model first.  Without `ema_decay` saved averages are ignored.  With `ema_buffers`: saved buffer averages ("ema_buffers", matched by
         position, "ema_buffer_names" informative) are restored -- a count or shape mismatch raises ValueError naming the buffer -- and a
-        dict without them re-seeds the shadows from the CURRENT buffers; without the option saved ones are ignored."""
+        dict without them re-seeds the shadows from the CURRENT buffers; without the option saved ones are ignored.  With `sam_rho`: saved
+        "sam_rho" / "sam_adaptive" replace the constructor's (ValueError for a bad value); a dict without them leaves them, and
+        without the option saved ones are ignored."""
         self._not_swapped("load_state_dict()")
+        self._not_perturbed("load_state_dict()")
         saved_groups, own_groups = sd["param_groups"], self._groups()
         if len(saved_groups) != len(own_groups):
             raise ValueError(f"state dict has {len(saved_groups)} parameter groups, this optimizer {len(own_groups)}")
@@ -899,6 +1043,9 @@ class FlatAdam:
             else:
                 ema_consts = self._check_ema(self.ema_decay if extra.get("ema_decay") is None else extra["ema_decay"],
                                              self.ema_warmup if extra.get("ema_warmup") is None else extra["ema_warmup"])
+        sam_consts = None
+        if self.sam_rho is not None and extra.get("sam_rho") is not None:
+            sam_consts = self._check_sam(extra["sam_rho"], extra.get("sam_adaptive", self.sam_adaptive))
         saved_bufs = extra.get("ema_buffers") if self._ebufs else None
         if saved_bufs is not None:
             names = self.ema_buffer_names
@@ -937,6 +1084,8 @@ class FlatAdam:
             if len(own_groups) == 1:
                 self.lr0 = lr0s[0]
             self._rebuild_plain_ranges()
+            if sam_consts is not None:
+                self.sam_rho, self.sam_adaptive = sam_consts
             if self._device:
                 self.t = int(extra.get("t", applied + int(extra.get("skipped_steps", 0))))
                 self._views["applied_steps"].fill_(applied)
@@ -1035,6 +1184,30 @@ def router_aux_total(sites, z_weight: float = 0.0, balance_weight: float = 0.0) 
     return torch.stack(terms).sum()
 
 
+@contextlib.contextmanager
+def hold_bn_stats(model: torch.nn.Module):
+    """`with hold_bn_stats(model): loss_fn(model(batch)).backward()` -- inside, every `torch.nn.modules.batchnorm._BatchNorm` of `model`
+    has `momentum = 0.0`: a training-mode forward pass normalises with the batch statistics as ever and leaves `running_mean` /
+    `running_var` as they are (running = (1 - 0) * running + 0 * batch).  The second pass of a sharpness-aware step (FlatAdam,
+    "Sharpness-aware minimization") runs on perturbed weights and must not move the statistics a second time.  The adapter sites read
+    `momentum` on every call (MoEAdapter._bn_momentum), torch's own BatchNorm modules likewise.  The momenta are restored on exit, also
+    when the body raises.  `num_batches_tracked` still advances inside, as torch's does with momentum 0: the counter only matters to
+    momentum=None, which this context refuses.  A batch statistic that is Inf or NaN still reaches the running one (0 * Inf is NaN).
+    ValueError, before anything is touched, when a BatchNorm has `momentum=None`: a cumulative average has no factor to hold it with."""
+    bns = [(k, m) for k, m in model.named_modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+    for k, m in bns:
+        if m.momentum is None:
+            raise ValueError(f"hold_bn_stats: BatchNorm {k!r} has momentum=None (the cumulative average), which cannot be held")
+    momenta = [m.momentum for _k, m in bns]
+    try:
+        for _k, m in bns:
+            m.momentum = 0.0
+        yield model
+    finally:
+        for (_k, m), mom in zip(bns, momenta):
+            m.momentum = mom
+
+
 def reestimate_bn(model: torch.nn.Module, batches: Iterable, forward=None, ema: Optional[FlatAdam] = None) -> int:
     """Re-estimates the running statistics of every BatchNorm in `model` with training-mode forward passes over `batches` -- the last
     step of weight averaging (torch.optim.swa_utils.update_bn): every `torch.nn.modules.batchnorm._BatchNorm` (the adapter sites' own
@@ -1110,9 +1283,10 @@ def adapter_state_dict(model: torch.nn.Module, substrings=("adapter",), ema: Opt
     ema: a FlatAdam built with `ema_decay` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), and with
     `ema_buffers` every buffer it holds (BatchNorm running statistics) with its averaged value too (`opt.ema_buffers`); everything else
     (other buffers, parameters outside the optimizer) as it is.  The model is not modified, and the result loads with `load_adapters`
-    like any other."""
+    like any other.  RuntimeError while `ema` holds perturbed weights (sam_perturb)."""
     src, bsrc = {}, {}
     if ema is not None:
+        ema._not_perturbed("adapter_state_dict(ema=...)")
         if not ema._swapped:                             # inside ema_weights() the parameters and buffers ARE the averages already
             src = {id(p): e for p, e in zip(ema.params, ema.ema_params)}
             if ema._ebufs:                               # by address and shape: state_dict() hands out the buffer tensors themselves

@@ -574,6 +574,50 @@ int avmoe_opt_grad_norm_swa(const void* table, int32_t n_ranges, int64_t n_block
                             const avmoe_opt_ema* ema /* HOST, or NULL */, void* report /* DEVICE, 16-byte aligned, or NULL */,
                             const avmoe_opt_swa* swa /* HOST */);
 
+/* Sharpness-aware minimization, SAM and its adaptive form ASAM (added under ABI 11 like the blocks above; found by symbol): a step takes
+ * the gradient at w + e, the point in the ball of radius rho around the weights w where a first gradient g says the loss is highest, and
+ * applies it to w itself.  Two calls serve it, beside the calls of a step: avmoe_opt_sam_perturb after the first backward pass moves the
+ * parameters to w + e and keeps w, avmoe_opt_adam_step_sam after the second one updates w.  Every range has a HOLD buffer of n fp32
+ * elements (device, 16-byte aligned, needs no initialisation); `hold` is a DEVICE array of n_ranges float*, entry i belonging to range i
+ * of the table, under the rules of `shadows` above.  No flag: the norm pass of the second gradient is avmoe_opt_grad_norm_swa (or an
+ * older one) unchanged, and every entry point above keeps refusing the flags it refuses.
+ * avmoe_opt_sam_perturb is THREE launches on `stream`, whatever the number of ranges, without a host synchronisation and without a host
+ * scalar that changes from step to step (rho, grad_scale and `adaptive` are constants of a run), so it replays from a captured graph:
+ *   1. the norm pass: one double per 1024-element block in `partials`, the sum of ((double)grad * grad_scale)^2 -- the very kernel of
+ *      avmoe_opt_grad_norm -- or, adaptive, of ((double)(|p| * grad) * grad_scale)^2 with |p| * grad rounded to fp32;
+ *   2. one block adds the partial sums in the order of avmoe_opt_grad_norm's finalize launch (the same helper) and writes *sam:
+ *          norm = (float)sqrt(sum), scale = (float)(rho / ((double)norm + 1e-12)), nonfinite = 0
+ *      or, when norm is Inf or NaN, scale = 0 and nonfinite = 1.  Not adaptive, `norm` has the bits state->total_norm gets from the same
+ *      gradient and grad_scale under AVMOE_OPT_REPORT;
+ *   3. per element of every range, in fp32 with every product rounded (one helper in csrc/adam_elem.h):
+ *          hold = p ;  e = scale * (grad * grad_scale)   or, adaptive,   e = (scale * (p * p)) * (grad * grad_scale) ;  p = p + e
+ *      With `nonfinite` set hold is still written and p is not; e == 0 (a zero gradient) leaves p's bits as they are.
+ * Gradients and moments are only read, the optimizer's state block is not touched, alignment padding belongs to no range and is not
+ * touched.  `partials` is the workspace of the norm pass (layout.partial_bytes): the step's own norm pass overwrites it later.
+ * avmoe_opt_adam_step_sam is avmoe_opt_adam_step_ema in which every element's p is READ from hold and the result is written to param:
+ * still one launch, the flags of avmoe_opt_adam_step_ema, and param, exp_avg, exp_avg_sq and the shadows get exactly the bits
+ * avmoe_opt_adam_step_ema gives from the unperturbed parameters with the same gradient -- the restoration is a copy, not p + e - e.
+ * When state->skip is set it writes param = hold and NOTHING else: a skipped step still undoes the perturbation.  A step without a
+ * perturbation before it is avmoe_opt_adam_step_ema.  avmoe_opt_swap_ema with `hold` in place of `shadows` abandons a perturbation (param
+ * gets the kept values back; hold gets the perturbed ones, which nobody reads).
+ * Errors (before any launch).  avmoe_opt_sam_perturb: AVMOE_ERR_BAD_ARG for a NULL table, partials (with n_blocks > 0), sam or hold, a
+ * negative count, rho negative, NaN or infinite, grad_scale NaN, `adaptive` not 0 or 1, a sam block that is not 16-byte aligned;
+ * AVMOE_ERR_ALIGNMENT for a hold array or partials that are not 8-byte aligned or a table that is not 16-byte aligned.
+ * avmoe_opt_adam_step_sam: AVMOE_ERR_BAD_ARG for hold == NULL, AVMOE_ERR_ALIGNMENT for a hold array that is not 8-byte aligned, and
+ * everything avmoe_opt_adam_step_ema refuses.                                                                                        */
+typedef struct avmoe_opt_sam_state {   /* DEVICE, 16 bytes, 16-byte aligned, needs no initialisation */
+  float norm;                 /* ||g * grad_scale||  (adaptive: |||p| * g * grad_scale||) of the perturbing gradient */
+  float scale;                /* rho / (norm + 1e-12) formed in double, rounded once to fp32; 0 when norm is Inf / NaN */
+  int32_t nonfinite;          /* 1: the norm was not finite and the parameters were left as they are */
+  int32_t reserved;
+} avmoe_opt_sam_state;
+
+int avmoe_opt_sam_perturb(const void* table, int32_t n_ranges, int64_t n_blocks, double* partials, avmoe_opt_sam_state* sam, float grad_scale,
+                          float rho, int32_t adaptive, float* const* hold /* DEVICE array of n_ranges float*, as `shadows` */, void* stream);
+int avmoe_opt_adam_step_sam(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                            float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
+                            float* const* hold /* DEVICE */);
+
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the
  * tiled engine is faster.  force_mask lifts those thresholds so that a test can run the benchmarked kernels on shapes its oracle

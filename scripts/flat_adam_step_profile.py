@@ -17,12 +17,21 @@
 --swa              (device mode, in place of --ema) FlatAdam(swa_start=total // 4, swa_freq=5): the uniform average of stochastic weight
                    averaging -- the launches of --ema, the decay by another rule in the finalize launch; with --schedule the schedule
                    also anneals to a constant SWA rate from step total // 2 on (LRSchedule(swa_start=...)); goes with --ema-buffers too
+--sam              (device mode) FlatAdam(sam_rho=0.05): every iteration is sam_perturb() -- three launches: the norm pass of the first
+                   gradient, a one-block finalize, hold = w ; w += e -- and then step(), whose update launch reads the weights from the
+                   hold buffers; --adaptive with it: the ASAM perturbation.  Combines with --ema, --swa, --schedule, --report
+--sam-foreach      (device mode) the same perturbation done OUTSIDE the optimizer with torch._foreach_* ops over the parameter views
+                   (norm, scale, clone, add), then the weights copied back and the step without SAM: what a user had to write before --sam
+--per-step-events  an event pair around every step() (and, with --sam / --sam-foreach, around every perturbation): `step_seg_us` and
+                   `perturb_us` are the means of those segments -- the way to time the step of a --sam iteration alone, and the
+                   counterpart without --sam measured the same way
 --report           (device mode) FlatAdam(report_grad_norms=True): one more launch behind finalize writes every parameter's gradient norm
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
 JSON line: launches per step are the trace's calls / steps; `step_us` is the event-timed mean of --steps steps enqueued back to back,
-`step_wall_us` the host time to enqueue one step (the launch-bound side)."""
+`step_wall_us` the host time to enqueue one step (the launch-bound side).  With --sam / --sam-foreach a "step" of both is a whole
+iteration, perturbation included; `perturb_us` and `step_seg_us` are its two parts."""
 import argparse
 import json
 import os
@@ -63,6 +72,10 @@ def main():
     ap.add_argument("--ema-buffers-foreach", action="store_true")
     ap.add_argument("--report", action="store_true")
     ap.add_argument("--swa", action="store_true")
+    ap.add_argument("--sam", action="store_true")
+    ap.add_argument("--adaptive", action="store_true")
+    ap.add_argument("--sam-foreach", action="store_true")
+    ap.add_argument("--per-step-events", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -82,6 +95,12 @@ def main():
         ap.error("--ema-buffers-foreach goes with --ema")
     if a.ema_buffers and a.ema_buffers_foreach:
         ap.error("--ema-buffers and --ema-buffers-foreach are the two sides of one comparison")
+    if (a.sam or a.sam_foreach) and a.mode != "device":
+        ap.error("--sam / --sam-foreach go with --mode device")
+    if a.sam and a.sam_foreach:
+        ap.error("--sam and --sam-foreach are the two sides of one comparison")
+    if a.adaptive and not a.sam:
+        ap.error("--adaptive goes with --sam")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
@@ -106,6 +125,9 @@ def main():
         kw["report_grad_norms"] = True
     if a.ema_buffers:
         kw["ema_buffers"] = model
+    sam_rho = 0.05
+    if a.sam:
+        kw.update(sam_rho=sam_rho, sam_adaptive=a.adaptive)
     buffers = [b for _, b in model.named_buffers() if b.dtype == torch.float32 and b.numel() > 0]
     buffer_shadows = [b.detach().clone() for b in buffers] if a.ema_buffers_foreach else None
     opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
@@ -116,6 +138,39 @@ def main():
     for b in red.buckets:
         b.flat.copy_(torch.randn(b.flat.numel(), generator=g))
     grads = [p for p in params]
+    grads_of = [p.grad for p in opt.params]
+
+    split = a.per_step_events or a.sam or a.sam_foreach
+    marks = []                                           # four events per measured iteration: around the perturbation, around the step
+
+    def perturb():
+        if a.sam:
+            opt.sam_perturb()
+            return None
+        # the host's way: a norm per tensor and the norm of those, the scale kept on the device (no synchronisation), a clone of every
+        # parameter, e = scale * g per tensor and the sum in place
+        norm = torch.linalg.vector_norm(torch.stack(torch._foreach_norm(grads_of)))
+        held = [v.clone() for v in views]
+        torch._foreach_add_(views, torch._foreach_mul(grads_of, sam_rho / (norm + 1e-12)))
+        return held
+
+    def iteration(measured):
+        if not split:
+            return step()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if measured else None
+        if ev:
+            ev[0].record()
+        held = perturb() if (a.sam or a.sam_foreach) else None
+        if ev:
+            ev[1].record()
+        if held is not None:
+            torch._foreach_copy_(views, held)            # the weights back, outside both timed segments
+        if ev:
+            ev[2].record()
+        step()
+        if ev:
+            ev[3].record()
+            marks.append(ev)
 
     def step():
         if a.mode == "clip_plain":
@@ -131,13 +186,13 @@ def main():
             torch._foreach_lerp_(buffer_shadows, buffers, 1.0 - FlatAdam.ema_decay_at(opt.t, ema_decay, ema_warmup))
 
     for _ in range(a.warmup):
-        step()
+        iteration(False)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     e0.record()
     for _ in range(a.steps):
-        step()
+        iteration(True)
     e1.record()
     wall = time.perf_counter() - t0
     torch.cuda.synchronize()
@@ -160,6 +215,14 @@ def main():
         avg = opt.ema_buffers if a.ema_buffers else buffer_shadows
         extra["buffers"], extra["buffer_elements"] = len(avg), sum(b.numel() for b in avg)
         extra["buffer_blocks"] = sum((b.numel() + 1023) // 1024 for b in avg)
+    if split:
+        extra["step_seg_us"] = round(1e3 * sum(e[2].elapsed_time(e[3]) for e in marks) / len(marks), 2)
+    if a.sam or a.sam_foreach:
+        extra["sam"] = ("device, adaptive" if a.adaptive else "device") if a.sam else "torch._foreach_* per step"
+        extra["perturb_us"] = round(1e3 * sum(e[0].elapsed_time(e[1]) for e in marks) / len(marks), 2)
+    if a.sam:
+        extra["last_sam_norm"], extra["last_sam_scale"] = float(opt.last_sam_norm.item()), float(opt.last_sam_scale.item())
+        extra["sam_nonfinite"], extra["perturbed"] = int(opt.sam_nonfinite.item()), opt.perturbed
     if a.report:
         extra["report"] = "device"
         extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())
