@@ -65,6 +65,16 @@ class OptReportHeader(C.Structure):
     _fields_ = [("first_nonfinite", C.c_int32), ("n_ranges", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class OptLambHeader(C.Structure):
+    """avmoe_opt_lamb_header: what precedes w_norm[n], u_norm[n], ratio[n] in a trust report buffer"""
+    _fields_ = [("n_ranges", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class OptLambLayout(C.Structure):
+    """avmoe_opt_lamb_layout: the bytes of avmoe_opt_lamb_step's workspace and report"""
+    _fields_ = [("workspace_bytes", C.c_size_t), ("report_bytes", C.c_size_t)]
+
+
 # avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
 OPT_STATE_BYTES = 64
 OPT_STATE_FIELDS = {"total_norm": (0, "float32"), "clip_coef": (4, "float32"), "bc1": (8, "float32"), "bc2_sqrt": (12, "float32"),
@@ -182,6 +192,10 @@ def declare(L):
             L.avmoe_opt_sam_perturb.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p,
                                                 C.c_void_p]
             L.avmoe_opt_adam_step_sam.argtypes = step_args + [C.c_void_p, C.c_void_p]
+        if hasattr(L, "avmoe_opt_lamb_step"):         # (found by symbol: layer-wise trust ratios)
+            L.avmoe_opt_lamb_bytes.restype, L.avmoe_opt_lamb_bytes.argtypes = C.c_size_t, [C.c_int32, C.c_int64, C.POINTER(OptLambLayout)]
+            L.avmoe_opt_lamb_step.restype = C.c_int
+            L.avmoe_opt_lamb_step.argtypes = step_args + [C.c_void_p] * 5       # shadows, hold, limits, workspace, report
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

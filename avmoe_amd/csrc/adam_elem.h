@@ -53,6 +53,73 @@ __device__ __forceinline__ float sam_elem(float p, float g, float gscale, float 
   return e == 0.f ? p : p + e;
 }
 
+// Layer-wise trust ratios (include/avmoe.h, avmoe_opt_lamb_step).  The moments of one element, by adam_elem's expressions in adam_elem's
+// spelling -- the gradient with grad_scale * clip factor (coupled decay: and wd * p), then the two fused multiply-adds -- so that a run
+// with the trust ratio keeps the moments Adam gets from the same gradients, bit for bit.  p is only read.
+template <bool DECOUPLED>
+__device__ __forceinline__ void lamb_moments(float p, float& m, float& v, float g, float b1, float b2, float wd, float gscale) {
+#pragma clang fp contract(off)
+  float gr;
+  if constexpr (DECOUPLED) gr = g * gscale;
+  else gr = __builtin_fmaf(gscale, g, wd * p);
+  m = __builtin_fmaf(b1, m, (1.f - b1) * gr);
+  v = __builtin_fmaf(b2, v, ((1.f - b2) * gr) * gr);
+}
+
+// The update direction u of one element from its STORED moments, written ONCE for the kernel that norms it (kk_opt_lamb_moments) and the
+// one that applies it (kk_opt_lamb_apply): both call this on the same fp32 values, so the u that is normed and the u that is applied have
+// the same bits.  u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps), DECOUPLED (the paper's LAMB): + wd * p.  Every operation is rounded to
+// fp32 in this order, contraction off: five roundings (m / bc1, the root, / bc2_sqrt, + eps, the quotient), seven with the decay term
+// and its addition.  This is another order of operations than adam_elem's ((lr / bc1) * m) / (...): the update is NOT Adam's bits.
+template <bool DECOUPLED>
+__device__ __forceinline__ float lamb_dir(float p, float m, float v, float wd, float bc1, float bc2_sqrt, float eps) {
+#pragma clang fp contract(off)
+  const float u = (m / bc1) / (sqrtf(v) / bc2_sqrt + eps);
+  if constexpr (DECOUPLED) return u + wd * p;
+  else return u;
+}
+
+// p - step * u with step = (lr * lr_factor) * ratio of the element's range: the product and the difference are rounded, contraction off,
+// so the 16-byte body and the scalar tail round alike
+__device__ __forceinline__ float lamb_next(float p, float u, float step) {
+#pragma clang fp contract(off)
+  return p - step * u;
+}
+
+// elements [i0, min(i0 + 4, n)) of one range, the applying half of a step with trust ratios: reads p (HOLD: from `hold`), m and v, forms
+// u with lamb_dir and writes p; EMA: the same thread advances the shadow from the new p, as adam_quad does.  m and v are only read.
+template <bool DECOUPLED, bool EMA, bool HOLD>
+__device__ __forceinline__ void lamb_quad(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v, long i0, long n, float step,
+                                          float eps, float wd, float bc1, float bc2_sqrt, float* __restrict__ ema, float d,
+                                          const float* __restrict__ hold) {
+  if (i0 + 3 < n) {
+    float4 pp;
+    const float4 mm = *(const float4*)(m + i0), vv = *(const float4*)(v + i0);
+    if constexpr (HOLD) pp = *(const float4*)(hold + i0);
+    else pp = *(float4*)(p + i0);
+    float* P = (float*)&pp; const float* M = (const float*)&mm; const float* V = (const float*)&vv;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) P[k] = lamb_next(P[k], lamb_dir<DECOUPLED>(P[k], M[k], V[k], wd, bc1, bc2_sqrt, eps), step);
+    *(float4*)(p + i0) = pp;
+    if constexpr (EMA) {
+      float4 ee = *(float4*)(ema + i0);
+      float* E = (float*)&ee;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ema_elem(E[k], P[k], d);
+      *(float4*)(ema + i0) = ee;
+    }
+  } else {
+    for (long i = i0; i < n; ++i) {
+      float pv;
+      if constexpr (HOLD) pv = hold[i];
+      else pv = p[i];
+      pv = lamb_next(pv, lamb_dir<DECOUPLED>(pv, m[i], v[i], wd, bc1, bc2_sqrt, eps), step);
+      p[i] = pv;
+      if constexpr (EMA) ema_elem(ema[i], pv, d);
+    }
+  }
+}
+
 // elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail.
 // EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register, with decay d
 // (without it `ema` and `d` are not read).

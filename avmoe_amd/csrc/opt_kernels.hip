@@ -28,6 +28,15 @@
 //   kk_opt_sam_perturb<ADAPTIVE>           hold = p ; p = p + e for every element of every range, in a hold buffer per range (as the shadows)
 // -- and kk_opt_adam<..., HOLD> for the step behind the second backward pass: it reads every p from hold and writes it to param, so the
 // unperturbed parameters come back exactly (a copy, not p + e - e); a skipped step writes param = hold and nothing else
+// and, for layer-wise trust ratios (LAMB; include/avmoe.h, avmoe_opt_lamb_step), three launches in place of kk_opt_adam --
+//   kk_opt_lamb_moments<DECOUPLED, HOLD>   the moments of every element, by adam_elem's expressions, and per 1024-element block the sums
+//                                          of u^2 and p^2 in double, u = lamb_dir (adam_elem.h) of the values just stored
+//   kk_opt_lamb_ratio                      one wave per range, the walk of kk_opt_range_norms over both sums: ||p||, ||u|| and
+//                                          ratio = ||p|| / ||u|| (formed in double, rounded once; 1 for a range that is not adapted or
+//                                          has a zero or non-finite norm; clamped where the range has a limit) into the trust report
+//   kk_opt_lamb_apply<DECOUPLED, SCHED, EMA, HOLD>   p = p - (lr * lr_factor * ratio) * u with u recomputed by the same helper from the
+//                                          same stored values; EMA and HOLD as in kk_opt_adam
+// The update is NOT Adam's bits (u is formed in another order of operations); the moments are.
 // The per-range norms are a kernel of their own, next to finalize, and not a part of it: finalize is ONE block whose additions define the
 // bits of total_norm, and a model has thousands of ranges -- a wave per range over many blocks finishes them in the time finalize takes,
 // inside finalize they would wait on one block's 256 threads and stretch the serial part of every step.  Finalize only resets the
@@ -327,6 +336,142 @@ __global__ void __launch_bounds__(256) kk_opt_adam(const void* __restrict__ tabl
                                   state->bc2_sqrt, grad_scale * state->clip_coef, e, d, h);
 }
 
+// ---- layer-wise trust ratios (include/avmoe.h, avmoe_opt_lamb_step) ----
+static_assert(sizeof(avmoe_opt_lamb_header) == 16 && sizeof(avmoe_opt_lamb_layout) == 16, "trust report layout");
+
+// The moments of every element and the block's sums for the two norms: sums[2 b] = sum of (double)u^2, sums[2 b + 1] = sum of (double)p^2
+// over the elements of table block b, each through block_sum_256 (a fixed order).  p is read from param, under HOLD from hold[range];
+// m and v are written, p is not.  u is formed from the m and v that have just been stored (lamb_dir).  A skipped step writes nothing;
+// a launch that does not match its table, or whose hold / shadow entry for the range cannot take 16-byte accesses, touches nothing
+// (`shadows` is NULL without the average: kk_opt_lamb_apply would refuse such a range, so its moments must stay too).
+template <bool DECOUPLED, bool HOLD>
+__global__ void __launch_bounds__(256) kk_opt_lamb_moments(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                           float eps, float grad_scale, float* const* __restrict__ shadows,
+                                                           float* const* __restrict__ hold, int n_ranges, double* __restrict__ sums) {
+  if (state->skip) return;
+  OptWork w;
+  bool ok = opt_work(table, w) && w.n_ranges == n_ranges;
+  const float* __restrict__ src = nullptr;
+  if (ok) {
+    src = w.r.param;
+    if constexpr (HOLD) { src = opt_shadow(w, hold, n_ranges); ok = src != nullptr; }
+    if (ok && shadows) ok = opt_shadow(w, shadows, n_ranges) != nullptr;
+  }
+  double su = 0.0, sp = 0.0;
+  if (ok) {
+    const avmoe_opt_range& r = w.r;
+    const long i0 = w.i0, n = r.n;
+    const float bc1 = state->bc1, bc2_sqrt = state->bc2_sqrt, gscale = grad_scale * state->clip_coef, wd = r.weight_decay;
+    if (i0 + 3 < n) {
+      const float4 pp = *(const float4*)(src + i0), gg = *(const float4*)(r.grad + i0);
+      float4 mm = *(float4*)(r.exp_avg + i0), vv = *(float4*)(r.exp_avg_sq + i0);
+      const float* P = (const float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        lamb_moments<DECOUPLED>(P[k], M[k], V[k], G[k], b1, b2, wd, gscale);
+        const double u = (double)lamb_dir<DECOUPLED>(P[k], M[k], V[k], wd, bc1, bc2_sqrt, eps), q = (double)P[k];
+        su += u * u;
+        sp += q * q;
+      }
+      *(float4*)(r.exp_avg + i0) = mm; *(float4*)(r.exp_avg_sq + i0) = vv;
+    } else {
+      for (long i = i0; i < n; ++i) {
+        const float pv = src[i];
+        float mv = r.exp_avg[i], vv = r.exp_avg_sq[i];
+        lamb_moments<DECOUPLED>(pv, mv, vv, r.grad[i], b1, b2, wd, gscale);
+        r.exp_avg[i] = mv; r.exp_avg_sq[i] = vv;
+        const double u = (double)lamb_dir<DECOUPLED>(pv, mv, vv, wd, bc1, bc2_sqrt, eps), q = (double)pv;
+        su += u * u;
+        sp += q * q;
+      }
+    }
+  }
+  // thread 0 of a block that has work serves the block's first element, so its `ok` is the block's
+  const double tu = block_sum_256(su);
+  __syncthreads();                                      // the tree's LDS is used a second time
+  const double tp = block_sum_256(sp);
+  if (threadIdx.x == 0 && ok) { sums[2 * (long)blockIdx.x] = tu; sums[2 * (long)blockIdx.x + 1] = tp; }
+}
+
+// One wave per range, grid-strided over the ranges: the walk of kk_opt_range_norms over the two sums of every block of the range (binary
+// search of the block map, lane l adds blocks l, l + 64, ..., a fixed butterfly: no floating-point atomics, the same bits every time).
+// The report: the 16-byte header, then w_norm[n_ranges], u_norm[n_ranges], ratio[n_ranges].  The norms are the double square roots rounded
+// to fp32; the ratio is formed in double from the double norms and rounded once.  limits[r] < 0 (or NaN): the range is not adapted,
+// ratio exactly 1; 0: adapted; > 0: the ratio is clamped to it.  A skipped step leaves the report as it was.
+__global__ void __launch_bounds__(256) kk_opt_lamb_ratio(const void* __restrict__ table, const double* __restrict__ sums, int n_ranges, long n_blocks,
+                                                         const float* __restrict__ limits, const avmoe_opt_state* __restrict__ state,
+                                                         avmoe_opt_lamb_header* __restrict__ report) {
+  if (state->skip) return;
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_MAGIC || h.n_ranges != n_ranges || h.n_blocks != n_blocks) return;
+  const avmoe_opt_range* ranges = (const avmoe_opt_range*)((const char*)table + sizeof(OptHeader));
+  const OptBlock* map = (const OptBlock*)(ranges + n_ranges);
+  float* w_norm = (float*)(report + 1);
+  float* u_norm = w_norm + n_ranges;
+  float* ratio = u_norm + n_ranges;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *report = avmoe_opt_lamb_header{n_ranges, {0, 0, 0}};
+  const int lane = threadIdx.x & 63, waves = (int)gridDim.x * 4;
+  for (int r = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6); r < n_ranges; r += waves) {
+    const long nb = (long)((ranges[r].n + OPT_BLOCK - 1) / OPT_BLOCK);
+    long lo = 0, hi = n_blocks;                       // the first block whose range is >= r
+    while (lo < hi) {
+      const long mid = (lo + hi) >> 1;
+      if (map[mid].range < r) lo = mid + 1; else hi = mid;
+    }
+    if (nb < 0 || lo + nb > n_blocks) continue;
+    if (nb > 0 && (map[lo].range != r || map[lo + nb - 1].range != r)) continue;
+    double au = 0.0, ap = 0.0;
+    for (long i = lane; i < nb; i += 64) { au += sums[2 * (lo + i)]; ap += sums[2 * (lo + i) + 1]; }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) { au += __shfl_xor(au, s, 64); ap += __shfl_xor(ap, s, 64); }
+    if (lane == 0) {
+      const double wn = sqrt(ap), un = sqrt(au);
+      const float lim = limits[r];
+      double q = 1.0;
+      if (lim >= 0.f && wn > 0.0 && un > 0.0 && isfinite(wn) && isfinite(un)) {
+        q = wn / un;
+        if (lim > 0.f && q > (double)lim) q = (double)lim;
+      }
+      w_norm[r] = (float)wn;
+      u_norm[r] = (float)un;
+      ratio[r] = (float)q;
+    }
+  }
+}
+
+// p = p - ((lr * lr_factor) * ratio) * u for every element of every range, u recomputed by lamb_dir from the m and v kk_opt_lamb_moments
+// has stored and the p it read: the bits that were normed.  SCHED, EMA and HOLD as in kk_opt_adam; m, v and the gradients are not
+// touched.  A skipped step writes nothing, under HOLD param = hold and nothing else.
+template <bool DECOUPLED, bool SCHED, bool EMA, bool HOLD>
+__global__ void __launch_bounds__(256) kk_opt_lamb_apply(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float eps,
+                                                         float* const* __restrict__ shadows, float* const* __restrict__ hold, int n_ranges,
+                                                         const avmoe_opt_lamb_header* __restrict__ report) {
+  if constexpr (!HOLD) {
+    if (state->skip) return;
+  }
+  OptWork w;
+  if (!opt_work(table, w) || w.n_ranges != n_ranges) return;
+  const avmoe_opt_range& r = w.r;
+  const float* h = nullptr;
+  if constexpr (HOLD) {
+    h = opt_shadow(w, hold, n_ranges);
+    if (!h) return;
+    if (state->skip) { restore_quad(r.param, h, w.i0, (long)r.n); return; }
+  }
+  float lr = r.lr;
+  if constexpr (SCHED) lr *= state->lr_factor;
+  float* e = nullptr;
+  float d = 0.f;
+  if constexpr (EMA) {
+    e = opt_shadow(w, shadows, n_ranges);
+    if (!e) return;
+    d = state->ema_decay;
+  }
+  const float ratio = ((const float*)(report + 1))[2 * (long)n_ranges + w.range];
+  lamb_quad<DECOUPLED, EMA, HOLD>(r.param, r.exp_avg, r.exp_avg_sq, w.i0, (long)r.n, lr * ratio, eps, r.weight_decay, state->bc1, state->bc2_sqrt,
+                                  e, d, h);
+}
+
 // One block: the SAM block from the partial sums of the perturbing gradient's norm pass.  The sum, the square root and its rounding are
 // those of kk_opt_finalize, so `norm` has the bits total_norm gets from the same partial sums.
 __global__ void __launch_bounds__(256) kk_opt_sam_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_sam_state* __restrict__ sam,
@@ -469,6 +614,18 @@ constexpr AdamKernel OPT_ADAM[16] = {          // [DECOUPLED | SCHED << 1 | EMA 
     kk_opt_adam<true, false, false, true>,   kk_opt_adam<false, true, false, true>,  kk_opt_adam<true, true, false, true>,
     kk_opt_adam<false, false, true, true>,   kk_opt_adam<true, false, true, true>,   kk_opt_adam<false, true, true, true>,
     kk_opt_adam<true, true, true, true>};
+
+using LambMomentsKernel = decltype(&kk_opt_lamb_moments<false, false>);
+using LambApplyKernel = decltype(&kk_opt_lamb_apply<false, false, false, false>);
+constexpr LambMomentsKernel OPT_LAMB_MOMENTS[4] = {   // [DECOUPLED | HOLD << 1]
+    kk_opt_lamb_moments<false, false>, kk_opt_lamb_moments<true, false>, kk_opt_lamb_moments<false, true>, kk_opt_lamb_moments<true, true>};
+constexpr LambApplyKernel OPT_LAMB_APPLY[16] = {      // [DECOUPLED | SCHED << 1 | EMA << 2 | HOLD << 3]
+    kk_opt_lamb_apply<false, false, false, false>, kk_opt_lamb_apply<true, false, false, false>, kk_opt_lamb_apply<false, true, false, false>,
+    kk_opt_lamb_apply<true, true, false, false>,   kk_opt_lamb_apply<false, false, true, false>, kk_opt_lamb_apply<true, false, true, false>,
+    kk_opt_lamb_apply<false, true, true, false>,   kk_opt_lamb_apply<true, true, true, false>,   kk_opt_lamb_apply<false, false, false, true>,
+    kk_opt_lamb_apply<true, false, false, true>,   kk_opt_lamb_apply<false, true, false, true>,  kk_opt_lamb_apply<true, true, false, true>,
+    kk_opt_lamb_apply<false, false, true, true>,   kk_opt_lamb_apply<true, false, true, true>,   kk_opt_lamb_apply<false, true, true, true>,
+    kk_opt_lamb_apply<true, true, true, true>};
 
 static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
 
@@ -647,17 +804,25 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
   return OK;
 }
 
+// what every update entry point refuses, in one order: adam_step below and avmoe_opt_lamb_step
+static int check_step_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1,
+                           float beta2, float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, bool with_hold,
+                           float* const* hold) {
+  AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
+  if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
+  if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("%s: eps must be >= 0, grad_scale not NaN", who); return ERR_BAD_ARG; }
+  if ((flags & AVMOE_OPT_EMA) != 0) AVMOE_TRY(check_shadows(who, shadows));
+  if (with_hold) AVMOE_TRY(check_hold(who, hold));
+  return OK;
+}
+
 // avmoe_opt_adam_step (shadows == NULL, the flag unknown), avmoe_opt_adam_step_ema and avmoe_opt_adam_step_sam (with_hold: the HOLD
 // instantiations): the same checks, then the update kernel the flags ask for
 static int adam_step(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
                      float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, bool with_hold, float* const* hold,
                      void* stream) {
-  AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));
-  if ((flags & ~known_flags) != 0) { set_last_error("%s: unknown flag", who); return ERR_BAD_ARG; }
-  if (!(eps >= 0.f) || !(grad_scale == grad_scale)) { set_last_error("%s: eps must be >= 0, grad_scale not NaN", who); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_step_args(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, known_flags, shadows, with_hold, hold));
   const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
-  if (ema) AVMOE_TRY(check_shadows(who, shadows));
-  if (with_hold) AVMOE_TRY(check_hold(who, hold));
   if (n_blocks == 0) return OK;
   hipLaunchKernelGGL(OPT_ADAM[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
                      (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale, shadows, (int)n_ranges, with_hold ? hold : nullptr);
@@ -781,6 +946,50 @@ int avmoe_opt_adam_step_sam(const void* table, int32_t n_ranges, int64_t n_block
                             float grad_scale, int32_t flags, void* stream, float* const* shadows, float* const* hold) {
   return adam_step("avmoe_opt_adam_step_sam", table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags,
                    OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA, shadows, true, hold, stream);
+}
+
+size_t avmoe_opt_lamb_bytes(int32_t n_ranges, int64_t n_blocks, avmoe_opt_lamb_layout* layout) {
+  if (n_ranges < 0) { set_last_error("avmoe_opt_lamb_bytes: negative range count %d", (int)n_ranges); return 0; }
+  if (n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("avmoe_opt_lamb_bytes: bad block count %lld", (long long)n_blocks); return 0; }
+  avmoe_opt_lamb_layout l;
+  l.workspace_bytes = round16((size_t)(n_blocks > 0 ? n_blocks : 1) * 2 * sizeof(double));
+  l.report_bytes = sizeof(avmoe_opt_lamb_header) + round16((size_t)n_ranges * 3 * sizeof(float));
+  if (layout) *layout = l;
+  return l.workspace_bytes + l.report_bytes;
+}
+
+int avmoe_opt_lamb_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
+                        float grad_scale, int32_t flags, void* stream, float* const* shadows, float* const* hold, const float* limits,
+                        double* workspace, void* report) {
+  const char* who = "avmoe_opt_lamb_step";
+  const bool with_hold = hold != nullptr;
+  AVMOE_TRY(check_step_args(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA,
+                            shadows, with_hold, hold));
+  if (!limits) { set_last_error("%s: the limits array is NULL", who); return ERR_BAD_ARG; }
+  if (!workspace) { set_last_error("%s: the workspace is NULL", who); return ERR_BAD_ARG; }
+  if (!report) { set_last_error("%s: the trust report buffer is NULL", who); return ERR_BAD_ARG; }
+  if (((uintptr_t)limits & 3u) != 0) { set_last_error("%s: the limits array must be 4-byte aligned", who); return ERR_ALIGNMENT; }
+  if (((uintptr_t)workspace & 7u) != 0) { set_last_error("%s: the workspace must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+  if (((uintptr_t)report & 15u) != 0) { set_last_error("%s: the trust report buffer must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
+  avmoe_opt_lamb_header* rep = (avmoe_opt_lamb_header*)report;
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(OPT_LAMB_MOMENTS[(int)dec | (int)with_hold << 1], dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, table, state,
+                       beta1, beta2, eps, grad_scale, ema ? shadows : nullptr, hold, (int)n_ranges, workspace);
+    AVMOE_CHECK_LAUNCH("opt_lamb_moments");
+  }
+  if (n_ranges > 0) {
+    const int grid = (int)std::min<int64_t>(((int64_t)n_ranges + 3) / 4, OPT_REPORT_MAX_GRID);
+    hipLaunchKernelGGL(kk_opt_lamb_ratio, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, table, (const double*)workspace, (int)n_ranges,
+                       (long)n_blocks, limits, state, rep);
+    AVMOE_CHECK_LAUNCH("opt_lamb_ratio");
+  }
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(OPT_LAMB_APPLY[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
+                       (hipStream_t)stream, table, state, eps, ema ? shadows : nullptr, hold, (int)n_ranges, (const avmoe_opt_lamb_header*)rep);
+    AVMOE_CHECK_LAUNCH("opt_lamb_apply");
+  }
+  return OK;
 }
 
 int avmoe_opt_swap_ema(const void* table, int32_t n_ranges, int64_t n_blocks, float* const* shadows, void* stream) {

@@ -306,6 +306,35 @@ class FlatAdam:
     is safe because the weights come back from the hold buffers and not by subtraction: the ranks' weights agree again after `step()`.
     NOT covered: the plain (non-device) path, a per-group rho, parameters outside the reducer.
 
+    Layer-wise trust ratios.  `trust_ratio=True` (LAMB, You et al. 2020; it selects the device path too) rescales every adapted
+    parameter's step by ||w|| / ||u||, the norm of the parameter over the norm of its update direction -- the tool for batch sizes far
+    above the one a recipe was tuned at, where Adam with a linearly scaled rate fails.  Per parameter, with g' = g * grad_scale * clip
+    factor and the moments formed exactly as without the option:
+
+        coupled decay:                    u = m_hat / (sqrt(v_hat) + eps)              (the decay joined the gradient, as in Adam)
+        decoupled_weight_decay (LAMB):    u = m_hat / (sqrt(v_hat) + eps) + wd * w
+        ratio = ||w|| / ||u||; 1 where either norm is 0 or not finite; min(ratio, trust_clip) with `trust_clip`
+        w = w - lr * lr_factor * ratio * u
+
+    with w the weights before the step (behind `sam_perturb()` the held ones, for the norm too) and the bias corrections of Adam, as in
+    the paper and in NVIDIA's implementation.  Adapted by default: parameters with `dim() >= 2` -- conv / linear weights and
+    `my_tokens`.  Not adapted: gates, biases, BatchNorm / LayerNorm weights -- scalars and vectors whose norm says nothing about a step
+    size (the gates start at exactly 0); they take ratio exactly 1 through the same kernels.  A `param_groups` entry may carry
+    "trust_ratio": True | False for its parameters.  The recipe: `FlatAdam(red, lr=..., weight_decay=0.01, decoupled_weight_decay=True,
+    trust_ratio=True, max_grad_norm=1.0, lr_schedule=LRSchedule(warmup_steps=...))`.
+    A step is the unchanged norm call and then THREE launches in place of the update (include/avmoe.h, avmoe_opt_lamb_step): the moments
+    with per-block sums of u^2 and w^2 in double, a wave per parameter that adds them in a fixed order and writes norms and ratio, and
+    the update, which recomputes u from the stored moments by the same helper -- 5 launches with clipping or skipping on, no host
+    synchronisation, no step-dependent host scalar, capturable; a host implementation needs two norms per tensor per step.  The moments
+    are bit-equal to Adam's from the same inputs; the parameters are NOT bit-equal to the Adam update even at ratio 1, because u is
+    formed in another order of operations (tests hold it to an fp64 bound from its own operands).  Schedule, averages, averaged
+    buffers, skipping, per-parameter gradient norms and SAM compose unchanged.  `last_trust_ratios`, `last_param_norms`,
+    `last_update_norms` are fp32 DEVICE views (`len(params)`, `params` order) of the last applied step; `adapted` is host state;
+    `trust_ratio_of(w_norm, u_norm, clip)` is the host's copy of the rule.  `state_dict()` carries "trust_ratio" / "trust_clip" under
+    "flat_adam" (no tensors), `load_state_dict()` into an optimizer built with the option restores the clamp, a dict without them loads
+    as before.  Under data parallelism the gradients agree on every rank after `red.finish()`, and so do moments, norms and ratios: no
+    communication is added.  NOT covered: the plain (non-device) path, parameters outside the reducer.
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -321,7 +350,8 @@ class FlatAdam:
                  max_grad_norm: Optional[float] = None, decoupled_weight_decay: bool = False, skip_nonfinite: bool = False,
                  lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
                  report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1,
-                 sam_rho: Optional[float] = None, sam_adaptive: bool = False):
+                 sam_rho: Optional[float] = None, sam_adaptive: bool = False, trust_ratio: bool = False,
+                 trust_clip: Optional[float] = None):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -331,8 +361,10 @@ class FlatAdam:
         swa_start + swa_freq, ... (integers >= 1, steps counted from 1; class docstring, "Stochastic weight averaging") in place of the
         exponential one: giving it together with `ema_decay` raises ValueError.  sam_rho: the radius rho >= 0 (held as fp32) of
         sharpness-aware minimization, `sam_perturb()` between two backward passes (class docstring); sam_adaptive: its adaptive form
-        (ValueError without `sam_rho`).  Any of the eight selects the device path (class docstring); with all at their defaults step()
-        is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
+        (ValueError without `sam_rho`).  trust_ratio: layer-wise trust ratios (LAMB; class docstring): every adapted parameter's step is
+        scaled by ||w|| / ||update||, computed on the device; trust_clip: the largest ratio allowed (a finite number > 0, held as fp32;
+        None: no clamp; ValueError without `trust_ratio`).  Any of the nine selects the device path (class docstring); with all at their
+        defaults step() is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
         and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
@@ -341,7 +373,8 @@ class FlatAdam:
         carry "weight_decay" (the AdamW recipe {"params": biases_and_norms, "weight_decay": 0.0}): it applies to that group's parameters,
         on both paths, coupled and decoupled; parameters not listed, or listed without the key, use `weight_decay`.  `betas` and `eps`
         stay per optimizer: a group's own are ignored.  On the plain path, neighbouring parameters of a bucket with the same rate and
-        decay share one kernel launch (an adapter site is one range)."""
+        decay share one kernel launch (an adapter site is one range).  With `trust_ratio` a group may carry "trust_ratio": True | False,
+        which overrides the default (adapted: `dim() >= 2`) for that group's parameters."""
         self.reducer, self.lr0, self.betas, self.eps, self.wd = reducer, lr, betas, eps, weight_decay
         self.step_size, self.gamma, self.grad_scale = step_size, gamma, grad_scale
         self.t, self.epoch = 0, 0
@@ -360,15 +393,22 @@ class FlatAdam:
         self._swapped = False                            # the parameters currently hold the averages (swap_ema / ema_weights)
         self.sam_rho, self.sam_adaptive = self._check_sam(sam_rho, sam_adaptive)
         self._perturbed = False                          # the parameters currently hold w + e, the hold buffers w (sam_perturb)
+        self.trust_ratio, self.trust_clip = self._check_trust(trust_ratio, trust_clip)
+        for grp in (param_groups or []):                 # before anything is touched
+            if "trust_ratio" in grp and not isinstance(grp["trust_ratio"], bool):
+                raise ValueError(f"a parameter group's \"trust_ratio\" must be True or False, not {grp['trust_ratio']!r}")
         self.report_grad_norms = bool(report_grad_norms)
         self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
         self._wds = []                                   # beside it: each parameter's weight decay
-        lr_of, wd_of = {}, {}
+        self._adapted = []                               # beside it: whether the parameter's step takes its trust ratio (trust_ratio)
+        lr_of, wd_of, adapt_of = {}, {}, {}
         for grp in (param_groups or []):
             ps = grp["params"]
             for p in ([ps] if isinstance(ps, torch.Tensor) else ps):
                 lr_of[id(p)] = float(grp.get("lr", lr))
+                if "trust_ratio" in grp:
+                    adapt_of[id(p)] = grp["trust_ratio"]
                 if "weight_decay" in grp:
                     wd_of[id(p)] = float(grp["weight_decay"])
         for b in reducer.buckets:
@@ -386,6 +426,7 @@ class FlatAdam:
                                           "aligned operands); build the reducer with aligned buckets (avmoe_amd.dp)")
                 self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
                 self._wds.append(wd_of.get(id(p), weight_decay))
+                self._adapted.append(adapt_of.get(id(p), p.dim() >= 2))
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
             if self._averaging:                          # the averages: the bucket's layout once more, padding zero
                 self.state[-1]["e"] = flat_p.clone()
@@ -393,7 +434,7 @@ class FlatAdam:
                 self.state[-1]["h"] = torch.zeros_like(flat_p)
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
-            or self._averaging or self.report_grad_norms or self.sam_rho is not None
+            or self._averaging or self.report_grad_norms or self.sam_rho is not None or self.trust_ratio
         if self._device:
             self._build_device_state()
 
@@ -682,7 +723,15 @@ class FlatAdam:
 
     def _update(self, L, stream, n, scale, flags, shadows):
         """the update launch of a device step: avmoe_opt_adam_step_ema, or behind a sam_perturb() avmoe_opt_adam_step_sam, which reads
-        the parameters from the hold buffers and so brings the unperturbed weights back"""
+        the parameters from the hold buffers and so brings the unperturbed weights back; with `trust_ratio` avmoe_opt_lamb_step serves
+        both cases"""
+        if self.trust_ratio:                             # three launches in place of one; the hold buffers only behind a sam_perturb()
+            capi.check(L.avmoe_opt_lamb_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1], self.eps, scale,
+                                             flags, stream, shadows, self._hold_ptrs.data_ptr() if self._perturbed else None,
+                                             self._trust_limits.data_ptr(), self._trust_ws.data_ptr(), self._trust_report.data_ptr()),
+                       "avmoe_opt_lamb_step")
+            self._perturbed = False
+            return
         if self._perturbed:
             capi.check(L.avmoe_opt_adam_step_sam(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
                                                  self.eps, scale, flags, stream, shadows, self._hold_ptrs.data_ptr()), "avmoe_opt_adam_step_sam")
@@ -690,6 +739,83 @@ class FlatAdam:
             return
         capi.check(L.avmoe_opt_adam_step_ema(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1],
                                              self.eps, scale, flags, stream, shadows), "avmoe_opt_adam_step_ema")
+
+    # ---- layer-wise trust ratios ----------------------------------------------------------------------------------
+    @staticmethod
+    def _check_trust(on, clip):
+        """-> (trust_ratio, trust_clip as the fp32 value the device gets or None)"""
+        if not isinstance(on, bool):
+            raise ValueError(f"trust_ratio must be True or False, not {on!r}")
+        if clip is None:
+            return on, None
+        if not on:
+            raise ValueError("trust_clip needs trust_ratio: there is no ratio to clamp")
+        c = float(clip)
+        if not (c > 0.0) or math.isinf(c) or c > 3.4028234663852886e38 or _f32(c) == 0.0:
+            raise ValueError(f"trust_clip must be a finite number > 0 (as fp32), not {clip!r}")
+        return on, _f32(c)
+
+    @staticmethod
+    def trust_ratio_of(w_norm: float, u_norm: float, clip: Optional[float] = None) -> float:
+        """The host's copy of the rule kk_opt_lamb_ratio applies to an adapted parameter: ||w|| / ||u|| formed in double and rounded once
+        to fp32; 1 where either norm is 0 or not finite; min(ratio, fp32(clip)) with a clamp."""
+        w, u = float(w_norm), float(u_norm)
+        if not (w > 0.0 and u > 0.0 and math.isfinite(w) and math.isfinite(u)):
+            return 1.0
+        q = w / u
+        if clip is not None and q > _f32(float(clip)):
+            q = _f32(float(clip))
+        return float(torch.tensor(q, dtype=torch.float64).to(torch.float32))
+
+    def _need_trust(self, what):
+        if not self.trust_ratio:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs trust_ratio")
+
+    def _trust_limit_values(self):
+        """one float per parameter as avmoe_opt_lamb_step reads it: < 0 not adapted, 0 adapted, > 0 adapted and clamped to it"""
+        return [(-1.0 if not a else (0.0 if self.trust_clip is None else self.trust_clip)) for a in self._adapted]
+
+    def _build_trust(self):
+        """the limits, the workspace of two doubles per table block and the report (header, then w_norm, u_norm, ratio) with its views"""
+        L, n = capi.lib(), len(self._plist)
+        if not hasattr(L, "avmoe_opt_lamb_step"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks the layer-wise trust ratios (avmoe_opt_lamb_step): rebuild it")
+        lay = cm.OptLambLayout()
+        if L.avmoe_opt_lamb_bytes(n, self._n_blocks, C.byref(lay)) == 0:
+            capi.check(-1, "avmoe_opt_lamb_bytes")
+        self._trust_limits = torch.tensor(self._trust_limit_values(), dtype=torch.float32).to(self._dev)
+        self._trust_ws = torch.zeros(int(lay.workspace_bytes), dtype=torch.uint8, device=self._dev)
+        self._trust_report = torch.zeros(int(lay.report_bytes), dtype=torch.uint8, device=self._dev)
+        hdr = C.sizeof(cm.OptLambHeader)
+        w, u, r = (self._trust_report[hdr + 4 * n * k:hdr + 4 * n * (k + 1)].view(torch.float32) for k in range(3))
+        r.fill_(1.0)                                     # until the first step: every ratio 1
+        self._trust_views = {"w_norm": w, "u_norm": u, "ratio": r}
+
+    @property
+    def adapted(self) -> List[bool]:
+        """host state, in `params` order: whether the parameter's step takes its trust ratio (the others take exactly 1)"""
+        return list(self._adapted)
+
+    @property
+    def last_trust_ratios(self) -> torch.Tensor:
+        """fp32 DEVICE tensor of len(params), in `params` order: the trust ratio of every parameter at the last applied step() -- exactly 1
+        for a parameter that is not adapted or whose weights or update had norm 0.  A view of the trust report, rewritten by every
+        applied step and by every replay of a captured one (a skipped step leaves it): reading it is the caller's synchronisation.  Only with `trust_ratio`."""
+        self._need_trust("last_trust_ratios")
+        return self._trust_views["ratio"]
+
+    @property
+    def last_param_norms(self) -> torch.Tensor:
+        """fp32 DEVICE tensor of len(params): ||w|| of every parameter BEFORE the last applied step(), summed in double.  As `last_trust_ratios`."""
+        self._need_trust("last_param_norms")
+        return self._trust_views["w_norm"]
+
+    @property
+    def last_update_norms(self) -> torch.Tensor:
+        """fp32 DEVICE tensor of len(params): ||u|| of every parameter's update direction at the last applied step() (decoupled: the decay
+        term included), summed in double.  As `last_trust_ratios`."""
+        self._need_trust("last_update_norms")
+        return self._trust_views["u_norm"]
 
     # ---- the device path ------------------------------------------------------------------------------------------
     def _opt_ranges(self):
@@ -733,6 +859,8 @@ class FlatAdam:
             self._build_report()
         if self.sam_rho is not None:
             self._build_sam()
+        if self.trust_ratio:
+            self._build_trust()
 
     def _build_report(self):
         """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
@@ -974,6 +1102,8 @@ class FlatAdam:
             extra.update(ema_buffers=[v.detach().cpu().clone() for v in self._ebuf_views], ema_buffer_names=self.ema_buffer_names)
         if self.sam_rho is not None:                     # constants only: the hold buffers are transient
             extra.update(sam_rho=self.sam_rho, sam_adaptive=self.sam_adaptive)
+        if self.trust_ratio:                             # constants only: norms and ratios are rewritten by every step
+            extra.update(trust_ratio=True, trust_clip=self.trust_clip)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
             extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
@@ -989,7 +1119,8 @@ class FlatAdam:
         position, "ema_buffer_names" informative) are restored -- a count or shape mismatch raises ValueError naming the buffer -- and a
         dict without them re-seeds the shadows from the CURRENT buffers; without the option saved ones are ignored.  With `sam_rho`: saved
         "sam_rho" / "sam_adaptive" replace the constructor's (ValueError for a bad value); a dict without them leaves them, and
-        without the option saved ones are ignored."""
+        without the option saved ones are ignored.  With `trust_ratio`: a saved "trust_clip" (beside "trust_ratio": True) replaces the
+        constructor's, likewise; which parameters are adapted stays what the constructor's groups say."""
         self._not_swapped("load_state_dict()")
         self._not_perturbed("load_state_dict()")
         saved_groups, own_groups = sd["param_groups"], self._groups()
@@ -1046,6 +1177,9 @@ class FlatAdam:
         sam_consts = None
         if self.sam_rho is not None and extra.get("sam_rho") is not None:
             sam_consts = self._check_sam(extra["sam_rho"], extra.get("sam_adaptive", self.sam_adaptive))
+        trust_consts = None
+        if self.trust_ratio and extra.get("trust_ratio") is True:
+            trust_consts = self._check_trust(True, extra.get("trust_clip"))
         saved_bufs = extra.get("ema_buffers") if self._ebufs else None
         if saved_bufs is not None:
             names = self.ema_buffer_names
@@ -1086,6 +1220,9 @@ class FlatAdam:
             self._rebuild_plain_ranges()
             if sam_consts is not None:
                 self.sam_rho, self.sam_adaptive = sam_consts
+            if trust_consts is not None:
+                self.trust_clip = trust_consts[1]
+                self._trust_limits.copy_(torch.tensor(self._trust_limit_values(), dtype=torch.float32))
             if self._device:
                 self.t = int(extra.get("t", applied + int(extra.get("skipped_steps", 0))))
                 self._views["applied_steps"].fill_(applied)

@@ -618,6 +618,56 @@ int avmoe_opt_adam_step_sam(const void* table, int32_t n_ranges, int64_t n_block
                             float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
                             float* const* hold /* DEVICE */);
 
+/* Layer-wise trust ratios, LAMB (You et al. 2020; added under ABI 11 like the blocks above; found by symbol): every range's step is
+ * rescaled by ||p|| / ||u||, the norm of the range's parameters over the norm of its update direction, which keeps the relative change of
+ * every tensor near lr whatever the batch size has done to the gradient's scale.  No flag and no new word in the state block:
+ * avmoe_opt_lamb_step is called IN PLACE of avmoe_opt_adam_step_ema / avmoe_opt_adam_step_sam, behind the unchanged norm call of a step
+ * (avmoe_opt_grad_norm_report / avmoe_opt_grad_norm_swa), on the same stream with the same grad_scale and betas, and every entry point
+ * above keeps refusing the flags it refuses.  With g' = grad * (grad_scale * clip_coef), per element of range r, every operation rounded to
+ * fp32 in the order written (csrc/adam_elem.h: lamb_moments, lamb_dir, lamb_next; contraction off):
+ *     coupled decay:                                gr = fma(gscale, grad, wd * p) ;  m, v from gr as avmoe_opt_adam_step forms them ;
+ *                                                   u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps)
+ *     AVMOE_OPT_DECOUPLED_DECAY (the paper's LAMB):  gr = grad * gscale ;  m, v from gr ;  u = (m / bc1) / (sqrt(v) / bc2_sqrt + eps) + wd * p
+ *     ratio_r = ||p_r|| / ||u_r||, both norms summed in double and the quotient formed in double, rounded once to fp32 ;
+ *               1 where either norm is 0 or not finite, and for a range that is not adapted ; min(ratio, limit) where the range has one
+ *     p = p - ((lr_r * lr_factor) * ratio_r) * u                     (lr_factor under AVMOE_OPT_LR_SCHEDULE)
+ * p is the value before the step, for the norm too -- with hold != NULL (the step behind avmoe_opt_sam_perturb) the held value.  Bias
+ * correction stays, as in the paper.  exp_avg and exp_avg_sq get the bits avmoe_opt_adam_step_ema gives them from the same p, gradient
+ * and state block; the parameters do NOT (u is formed in another order than Adam's ((lr / bc1) * m) / (...)).
+ * `limits` is a DEVICE array of n_ranges floats: < 0 the range is not adapted (ratio exactly 1.0f, through the same kernels), 0 adapted
+ * without a clamp, > 0 the ratio is clamped to it.  `workspace` (DEVICE, 8-byte aligned) takes two doubles per table block; `report`
+ * (DEVICE, 16-byte aligned) is the 16-byte avmoe_opt_lamb_header, then three arrays of n_ranges floats: w_norm, u_norm (the double square
+ * roots rounded to fp32) and ratio.  Neither needs initialisation.  avmoe_opt_lamb_bytes returns both sizes (each a multiple of 16; 0 and
+ * an error string on a negative count or more than 2^31 - 1 blocks) and their sum.
+ * avmoe_opt_lamb_step is THREE launches on `stream` whatever the number of ranges, without a host synchronisation and without a host
+ * scalar that changes from step to step, so it replays from a captured graph:
+ *   1. one block per table block: the moments, and the block's sums of (double)u^2 and (double)p^2 into the workspace, u formed from the
+ *      moments just stored;
+ *   2. one wave per range adds the range's block sums in a fixed order (the walk of AVMOE_OPT_REPORT's launch; no floating-point atomics)
+ *      and writes w_norm, u_norm and ratio into the report;
+ *   3. one block per table block: u again, by the same helper from the same stored values, and the update; with AVMOE_OPT_EMA the shadow
+ *      advances from the new p as in avmoe_opt_adam_step_ema.
+ * When state->skip is set nothing is written, the report included -- with hold != NULL param = hold and nothing else.  Gradients are only
+ * read; alignment padding belongs to no range and is not touched.  A launch that does not match its table's header, a shadow / hold entry
+ * that is not 16-byte aligned or a pointer array made for another range count touches nothing, as in the kernels above.
+ * `flags` are those of avmoe_opt_adam_step_ema; `shadows` may be NULL without AVMOE_OPT_EMA; hold == NULL is the step without a
+ * perturbation before it.
+ * Errors (before any launch): everything avmoe_opt_adam_step_sam refuses (hold != NULL) or avmoe_opt_adam_step_ema refuses (hold == NULL);
+ * AVMOE_ERR_BAD_ARG for NULL limits, workspace or report; AVMOE_ERR_ALIGNMENT for limits that are not 4-byte, a workspace that is not
+ * 8-byte or a report that is not 16-byte aligned.                                                                                     */
+typedef struct avmoe_opt_lamb_header {
+  int32_t n_ranges;           /* the floats in each of the three arrays that follow the header */
+  int32_t reserved[3];
+} avmoe_opt_lamb_header;
+
+typedef struct avmoe_opt_lamb_layout { size_t workspace_bytes, report_bytes; } avmoe_opt_lamb_layout;
+
+size_t avmoe_opt_lamb_bytes(int32_t n_ranges, int64_t n_blocks, avmoe_opt_lamb_layout* layout /* HOST, or NULL */);
+int avmoe_opt_lamb_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                        float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
+                        float* const* hold /* DEVICE, or NULL */, const float* limits /* DEVICE, n_ranges floats */,
+                        double* workspace /* DEVICE */, void* report /* DEVICE, 16-byte aligned */);
+
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the
  * tiled engine is faster.  force_mask lifts those thresholds so that a test can run the benchmarked kernels on shapes its oracle

@@ -26,6 +26,9 @@
                    `perturb_us` are the means of those segments -- the way to time the step of a --sam iteration alone, and the
                    counterpart without --sam measured the same way
 --report           (device mode) FlatAdam(report_grad_norms=True): one more launch behind finalize writes every parameter's gradient norm
+--lamb             (device mode) FlatAdam(trust_ratio=True, trust_clip=10.0): layer-wise trust ratios -- three launches (moments and block
+                   sums, a wave per parameter for norms and ratio, the update) in place of the one update launch: 5 per step.
+                   Combines with --schedule, --ema, --swa, --report, --sam
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
@@ -76,6 +79,7 @@ def main():
     ap.add_argument("--adaptive", action="store_true")
     ap.add_argument("--sam-foreach", action="store_true")
     ap.add_argument("--per-step-events", action="store_true")
+    ap.add_argument("--lamb", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -101,6 +105,8 @@ def main():
         ap.error("--sam and --sam-foreach are the two sides of one comparison")
     if a.adaptive and not a.sam:
         ap.error("--adaptive goes with --sam")
+    if a.lamb and a.mode != "device":
+        ap.error("--lamb goes with --mode device")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
@@ -128,6 +134,8 @@ def main():
     sam_rho = 0.05
     if a.sam:
         kw.update(sam_rho=sam_rho, sam_adaptive=a.adaptive)
+    if a.lamb:
+        kw.update(trust_ratio=True, trust_clip=10.0)
     buffers = [b for _, b in model.named_buffers() if b.dtype == torch.float32 and b.numel() > 0]
     buffer_shadows = [b.detach().clone() for b in buffers] if a.ema_buffers_foreach else None
     opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
@@ -223,6 +231,11 @@ def main():
     if a.sam:
         extra["last_sam_norm"], extra["last_sam_scale"] = float(opt.last_sam_norm.item()), float(opt.last_sam_scale.item())
         extra["sam_nonfinite"], extra["perturbed"] = int(opt.sam_nonfinite.item()), opt.perturbed
+    if a.lamb:
+        r = opt.last_trust_ratios
+        extra["lamb"] = "device"
+        extra["adapted"], extra["ratio_min"], extra["ratio_max"] = sum(opt.adapted), float(r.min().item()), float(r.max().item())
+        extra["ratios_not_one"] = int((r != 1.0).sum().item())
     if a.report:
         extra["report"] = "device"
         extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())
