@@ -118,6 +118,10 @@ TOP_KEY_TO_FIELD = {
 }
 
 
+# include/avmoe.h: AVMOE_NXN_* (avmoe_nxn_strip)
+NXN_OP = {"STATS": 0, "ATT": 1, "ATT_FROM_LSE": 2, "XR": 3, "Y": 4, "DXQ": 5, "DXK": 6, "ATT_BWD": 7}
+
+
 def declare(L):
     L.avmoe_adam_step.restype = C.c_int
     L.avmoe_adam_step.argtypes = [C.c_void_p] * 4 + [C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_float, C.c_void_p]
@@ -204,6 +208,9 @@ def declare(L):
                            ("swap_buffers", [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])):
             fn = getattr(L, "avmoe_opt_" + name)
             fn.restype, fn.argtypes = C.c_int, args
+    if hasattr(L, "avmoe_nxn_strip"):                # (found by symbol: one strip kernel of the N x N block on raw operands, tests only)
+        L.avmoe_nxn_strip.restype = C.c_int
+        L.avmoe_nxn_strip.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5
     L.avmoe_moe_buffer_info.restype = C.c_int
     L.avmoe_moe_buffer_info.argtypes = [C.POINTER(MoeDesc), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]

@@ -192,6 +192,36 @@ uint32_t avmoe_test_hooks(uint32_t force_mask, int32_t nxn_chunk) {
   return prev;
 }
 
+// One strip kernel of the AVVP N x N block (nxn_att.hip) on raw operands, Np = N: no arithmetic of its own -- the pointers the op needs,
+// then the wrapper and its status (shapes the kernels do not serve: ERR_UNSUPPORTED from the wrappers' own check).
+int avmoe_nxn_strip(int32_t op, const void* X, const void* dxr, int32_t frames, int32_t N, int32_t C, float* lse, float* rowdot, void* out,
+                    const void* att_in, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  bool ok = X != nullptr;
+  switch (op) {
+    case AVMOE_NXN_STATS:        ok = ok && lse; break;
+    case AVMOE_NXN_ATT:
+    case AVMOE_NXN_ATT_FROM_LSE:
+    case AVMOE_NXN_XR:           ok = ok && lse && out; break;
+    case AVMOE_NXN_Y:
+    case AVMOE_NXN_DXQ:
+    case AVMOE_NXN_DXK:          ok = ok && dxr && lse && rowdot && out; break;
+    case AVMOE_NXN_ATT_BWD:      ok = ok && dxr && rowdot && out && att_in; break;
+    default: set_last_error("avmoe_nxn_strip: unknown op %d", op); return ERR_BAD_ARG;
+  }
+  if (!ok) { set_last_error("avmoe_nxn_strip: op %d: null pointer", op); return ERR_BAD_ARG; }
+  switch (op) {
+    case AVMOE_NXN_STATS:        return k_nxn_att(X, frames, N, C, N, lse, nullptr, 0, st);
+    case AVMOE_NXN_ATT:          return k_nxn_att(X, frames, N, C, N, lse, out, 0, st);
+    case AVMOE_NXN_ATT_FROM_LSE: return k_nxn_att(X, frames, N, C, N, lse, out, 1, st);
+    case AVMOE_NXN_XR:           return k_nxn_xr(X, frames, N, C, N, lse, out, st);
+    case AVMOE_NXN_Y:            return k_nxn_y(X, dxr, frames, N, C, N, lse, rowdot, out, st);
+    case AVMOE_NXN_DXQ:          return k_nxn_dx(0, X, dxr, frames, N, C, N, lse, rowdot, out, st);
+    case AVMOE_NXN_DXK:          return k_nxn_dx(1, X, dxr, frames, N, C, N, lse, rowdot, out, st);
+    default:                     return k_nxn_att_bwd(X, dxr, frames, N, C, N, rowdot, att_in, out, st);
+  }
+}
+
 void avmoe_prof_enable(int on) { prof_enable(on != 0); }
 void avmoe_prof_reset(void) { prof_reset(); }
 size_t avmoe_prof_report(char* buf, size_t cap) { return prof_report(buf, cap); }

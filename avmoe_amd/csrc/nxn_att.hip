@@ -154,6 +154,9 @@ __global__ void __launch_bounds__(256, (KS <= 3 ? 2 : NXN_ATT_MINB6)) kk_nxn_att
           l = l * __expf(m - mn) + l2 * __expf(m2 - mn); m = mn;
         }
         lse[tm] = m + __logf(l);
+        // the four q lanes of a row merged in four different orders (l * e + l2 * e2 contracts to an fma whose rounding depends on which
+        // partner is `l`): sweep 2 takes lane q == 0's value, the one that is stored, so that the sweep from the kept lse gives the same bits
+        if (att) lse[tm] = __shfl(lse[tm], r, 64);
         if (q == 0) lse_g[f * N + i0 + 16 * tm + r] = lse[tm];
       }
     }

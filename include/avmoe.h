@@ -679,6 +679,25 @@ int avmoe_opt_lamb_step(const void* table, int32_t n_ranges, int64_t n_blocks, c
 enum { AVMOE_HOOK_TOKPAIR2_FORCE = 1, AVMOE_HOOK_DPAIR_FORCE = 2, AVMOE_HOOK_HOP1S_FORCE = 4, AVMOE_HOOK_KFS_FORCE = 8, AVMOE_HOOK_KFS_OFF = 16 };
 uint32_t avmoe_test_hooks(uint32_t force_mask, int32_t nxn_chunk);
 
+/* avmoe_nxn_strip (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds it by symbol; tests only) -- ONE strip kernel of the
+ * AVVP N x N block (csrc/nxn_att.hip) on raw operands, so that each can be checked alone (tests/test_nxn_strips_fp64_gpu.py).  bf16
+ * operands, att[i][j] = exp(X_i . X_j - lse_i) per frame, rows of att / dS are N wide.  No site call goes through it.
+ *   X, dxr, out (XR / Y / DXQ / DXK): (frames, N, C) bf16;  lse, rowdot: (frames, N) fp32;  att_in, out (ATT / ATT_FROM_LSE / ATT_BWD): (frames, N, N) bf16
+ *   STATS         lse = row log-sum-exp of X X^T                              (writes lse)
+ *   ATT           the same, then out = att                                    (writes lse, out)
+ *   ATT_FROM_LSE  out = att from the given lse                                (reads lse)
+ *   XR            out = att^T X                                               (reads lse)
+ *   Y             y = att dxr: rowdot = X . y, out += y                       (reads lse, writes rowdot, read-modify-writes out)
+ *   DXQ / DXK     out += dS X / dS^T X, dS = att * (X dxr^T - rowdot)         (reads lse, rowdot, read-modify-writes out)
+ *   ATT_BWD       out = dS = att_in * (X dxr^T - rowdot)                      (reads rowdot, att_in)
+ * It adds no arithmetic: AVMOE_ERR_BAD_ARG for an unknown op or a NULL pointer among those the op uses (unused ones may be NULL), then the
+ * kernel's own wrapper and its status -- AVMOE_ERR_UNSUPPORTED unless C is 96 or 192 and N a positive multiple of 128; frames <= 0 is
+ * AVMOE_OK without a launch.                                                                                                    */
+enum { AVMOE_NXN_STATS = 0, AVMOE_NXN_ATT = 1, AVMOE_NXN_ATT_FROM_LSE = 2, AVMOE_NXN_XR = 3, AVMOE_NXN_Y = 4, AVMOE_NXN_DXQ = 5,
+       AVMOE_NXN_DXK = 6, AVMOE_NXN_ATT_BWD = 7 };
+int avmoe_nxn_strip(int32_t op, const void* X, const void* dxr, int32_t frames, int32_t N, int32_t C, float* lse, float* rowdot, void* out,
+                    const void* att_in, void* stream);
+
 /* ---- optional per-launch timing (HIP events on the launch stream; off by default; process-wide) --------
  * avmoe_prof_report writes a JSON array of {"name","calls","total_ms","alg_bytes","flops"} per kernel family
  * into buf (NUL-terminated, truncated to cap) and returns the full length.  Used by bench.py for the roofline. */

@@ -69,7 +69,8 @@ CASES = {
     "cfg5_stage3_visual_k87_v2": dict(cfg=dict(Cx=512, Nx=49, Cy=768, Ny=64, reduction=4, groups=2, K=87, variant="avs", self_attn="v2", E_m=4, E_s=4, lb_loss=True), S=5),
     "cfg5_stage3_visual_k87_v1": dict(cfg=dict(Cx=512, Nx=49, Cy=768, Ny=64, reduction=4, groups=2, K=87, variant="avs", self_attn="v1", E_m=4, E_s=4, lb_loss=True), S=5, keep=True),
     # cfg-3 stage 0 at its REAL token counts (N = 4096 / 2304, mgn.py:132-139): the strip kernel kk_nxn_att over 32 / 18 key tiles per
-    # query strip, two frames (kept: (frames, N, N) fits; the chunked form of the same sites: test_avvp_nxn_block_in_frame_chunks)
+    # query strip, two frames (nflash: the strip kernels keep the row log-sum-exp only, no (frames, N, N) tensor exists at any frame count;
+    # the same sites with the frames in chunks: test_avvp_nxn_block_in_frame_chunks; the kernels one by one: test_nxn_strips_fp64_gpu.py)
     "cfg3_avvp_stage0_audio_full": dict(cfg=dict(Cx=96, Nx=4096, Cy=192, Ny=2304, reduction=8, groups=2, K=32, variant="avvp", lb_loss=True), S=2),
     "cfg3_avvp_stage0_visual_full": dict(cfg=dict(Cx=192, Nx=2304, Cy=96, Ny=4096, reduction=8, groups=2, K=32, variant="avvp", lb_loss=True), S=2),
     # AVS self_attention_version "v1" (the S4 training script's default): MultiheadAttention across the frames, PVT-v2 stage shapes
