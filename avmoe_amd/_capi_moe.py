@@ -168,6 +168,14 @@ def declare(L):
         L.avmoe_moe_backward_ex.restype = L.avmoe_moe_backward_aux.restype = C.c_int
         L.avmoe_moe_backward_ex.argtypes = head + [C.c_void_p] * 6 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
         L.avmoe_moe_backward_aux.argtypes = head + [C.c_void_p] * 7 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
+    # the mixture regularisers (found by symbol: a multiplier on the mixture weights, and its draw on the device)
+    L.avmoe_site_reg = L.avmoe_site_aux and hasattr(L, "avmoe_moe_forward_reg") and hasattr(L, "avmoe_mix_drop_draw")
+    if L.avmoe_site_reg:
+        L.avmoe_moe_forward_reg.restype, L.avmoe_moe_forward_reg.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 10
+        L.avmoe_moe_backward_reg.restype = C.c_int
+        L.avmoe_moe_backward_reg.argtypes = head + [C.c_void_p] * 8 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
+        L.avmoe_mix_drop_draw.restype = C.c_int
+        L.avmoe_mix_drop_draw.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

@@ -18,6 +18,7 @@ missing library or a non-GPU tensor raises.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 from collections import namedtuple
 from typing import Dict
 
@@ -30,6 +31,7 @@ from . import _capi as capi
 from . import _capi_moe as cm
 
 _SCRATCH: Dict[tuple, torch.Tensor] = {}
+_MIX_SITES = itertools.count()       # construction order of the sites of this process: the per-site index behind the default `mix_seed`
 _SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
 
 
@@ -137,9 +139,35 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _rate(name, v):
+    """a drop rate of the mixture regularisers: a real number in [0, 1)"""
+    if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= float(v) < 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1), got {v!r}")
+    return float(v)
+
+
+def _draw_mix(module, L, S, E, p, q, dev, stream):
+    """The (S, E) multiplier of one training-mode call, drawn on `stream` by avmoe_mix_drop_draw into the site's cached tensor.  The site
+    owns the generator's state block {seed, calls} on the device: nothing the host writes changes between two calls, so a captured
+    forward draws afresh on every replay.  The block is made on the first call (a host-to-device copy: before any graph capture) and
+    made anew -- calls = 0 -- when `mix_seed` is assigned or the site has moved to another device."""
+    d = module.__dict__
+    state = d.get("_mix_state")
+    if state is None or state.device != dev:
+        seed = module.mix_seed
+        state = d["_mix_state"] = torch.tensor([seed - (1 << 64) if seed >= (1 << 63) else seed, 0], dtype=torch.int64, device=dev)
+    buf = d.get("_mix_buf")
+    if buf is None or buf.shape != (S, E) or buf.device != dev:
+        buf = d["_mix_buf"] = torch.empty(S, E, dtype=torch.float32, device=dev)
+    capi.check(L.avmoe_mix_drop_draw(state.data_ptr(), S, E, p, q, buf.data_ptr(), stream), "avmoe_mix_drop_draw")
+    d["_mix_draws"] = d.get("_mix_draws", 0) + 1        # which draw the cached tensor holds: a backward checks that it is still its forward's
+    return buf
+
+
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
     """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
-    losses.  Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
+    losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call.
+    Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
@@ -165,6 +193,10 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     renorm = int(module.router_top_k_renorm) if k else 1       # (a dense site records renorm = 1 in `saved`, as avmoe_moe_forward does)
     if not L.avmoe_site_aux and (k or module.router_aux):
         raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_aux: it serves neither top-k gating nor the router auxiliary losses")
+    drop_p, drop_q = module.drop_path, module.expert_dropout
+    reg = bool(module.training and (drop_p > 0.0 or drop_q > 0.0))      # (eval mode ignores both settings)
+    if reg and not getattr(L, "avmoe_site_reg", False):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_reg / avmoe_mix_drop_draw: it serves neither drop_path nor expert_dropout")
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -182,7 +214,14 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     aux = None
     if module.router_aux:                                # the router auxiliary losses beside the forward (dense or top-k)
         aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
-    if L.avmoe_site_aux:
+    mix = _draw_mix(module, L, S, E, drop_p, drop_q, X.device, stream) if reg else None
+    module.__dict__["_mix_last"] = mix
+    if mix is not None:                                  # the multiplier on the mixture weights, drawn just above on the same stream
+        fn = "avmoe_moe_forward_reg"
+        st = L.avmoe_moe_forward_reg(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, mix.data_ptr(),
+                                     out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
+                                     aux[1].data_ptr() if aux else None, saved.data_ptr(), scratch.data_ptr(), stream)
+    elif L.avmoe_site_aux:
         fn = "avmoe_moe_forward_aux"
         st = L.avmoe_moe_forward_aux(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, out.data_ptr(),
                                      probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
@@ -195,7 +234,8 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     capi.check(st, fn)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
-    return out, probs, idx, lb, ((desc, keep, ptrs), saved, X, Y), aux
+    mix = (mix, module.__dict__["_mix_draws"]) if mix is not None else None      # (the tensor is the site's cached one: with its draw number)
+    return out, probs, idx, lb, ((desc, keep, ptrs, mix), saved, X, Y), aux
 
 
 class _SiteBackward:
@@ -207,7 +247,13 @@ class _SiteBackward:
     def __init__(self, module, state, names, params, needs, d_out, d_lb, dX, dY, acc_dx=False, acc_dy=False, scratch_slot=0, stream=None,
                  d_probs=None, d_aux=None):
         self.L = capi.lib()
-        (desc, keep, fwd_ptrs), self.saved, self.X, self.Y = state
+        (desc, keep, fwd_ptrs, mix), self.saved, self.X, self.Y = state
+        self.mix = None                                  # the forward's multiplier on the mixture weights (drop_path / expert_dropout), given again
+        if mix is not None:
+            if module.__dict__.get("_mix_draws") != mix[1]:
+                raise capi.AvmoeError("drop_path / expert_dropout: the site ran another training forward before this one's backward, and the "
+                                      "site's one multiplier tensor now holds that call's draw (run each forward's backward before the next forward)")
+            self.mix = mix[0]
         self.desc, self.names, self.module = desc, names, module
         self.stream = stream if stream is not None else torch.cuda.current_stream(self.X.device).cuda_stream      # (the stream this object is built AND run on)
         tensors = dict(zip(names, params))
@@ -248,7 +294,13 @@ class _SiteBackward:
     def run(self, parts=0):
         d = self.desc
         d.accumulate_dx, d.accumulate_dy = self.acc
-        if self.L.avmoe_site_aux:                              # NULL for each upstream gradient that is absent
+        if self.mix is not None:
+            fn = "avmoe_moe_backward_reg"
+            st = self.L.avmoe_moe_backward_reg(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), _ptr(self.d_out),
+                                               _ptr(self.dprobs), _ptr(self.lbg), _ptr(self.daux), self.mix.data_ptr(), self.saved.data_ptr(),
+                                               self.scratch.data_ptr(), self.dX.data_ptr(), self.dY.data_ptr(), C.byref(self.gptrs),
+                                               int(parts), self.stream)
+        elif self.L.avmoe_site_aux:                            # NULL for each upstream gradient that is absent
             fn = "avmoe_moe_backward_aux"
             st = self.L.avmoe_moe_backward_aux(C.byref(d), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), _ptr(self.d_out),
                                                _ptr(self.dprobs), _ptr(self.lbg), _ptr(self.daux), self.saved.data_ptr(),
@@ -577,6 +629,64 @@ class MoEAdapter(nn.Module):
         # the router auxiliary losses (z-loss, Switch balance loss: include/avmoe.h at avmoe_moe_forward_aux) beside every forward; a
         # plain attribute like the two above.  Off: the entry points and launches of a site without them.
         self.router_aux = getattr(opt, "router_aux", False)
+        # the regularisers of the mixture (include/avmoe.h at avmoe_moe_forward_reg): stochastic depth on the adapter branch and expert
+        # dropout, training mode only.  Plain attributes like the ones above, not state: no state_dict key, no buffer.
+        self.__dict__["_mix_index"] = next(_MIX_SITES)
+        self.drop_path = getattr(opt, "adapter_drop_path", 0.0)
+        self.expert_dropout = getattr(opt, "adapter_expert_dropout", 0.0)
+
+    @property
+    def drop_path(self):
+        """p in [0, 1): in training mode every frame's whole adapter output is dropped with probability p (with `add_to`, nothing is
+        added) and the kept frames are scaled by 1 / (1 - p).  Eval mode ignores it."""
+        return self.__dict__.get("_drop_path", 0.0)       # (.get: a module pickled before the setting existed has none)
+
+    @drop_path.setter
+    def drop_path(self, v):
+        self.__dict__["_drop_path"] = _rate("drop_path", v)
+
+    @property
+    def expert_dropout(self):
+        """q in [0, 1): in training mode every (frame, expert) pair of the mixture is dropped independently with probability q and the
+        kept ones are scaled by 1 / (1 - q); no renormalisation, no rescue of a frame that loses every expert.  Eval mode ignores it."""
+        return self.__dict__.get("_expert_dropout", 0.0)
+
+    @expert_dropout.setter
+    def expert_dropout(self, v):
+        self.__dict__["_expert_dropout"] = _rate("expert_dropout", v)
+
+    @property
+    def mix_seed(self):
+        """The 64-bit seed of the site's generator.  Unless assigned: derived from torch.initial_seed() and the site's index in this process's
+        construction order, so that two sites do not share their draws.  Assigning it restarts the site's generator (mix_calls = 0).  The
+        generator's state is no buffer and is not saved: a resumed run starts it again from its seed."""
+        s = self.__dict__.get("_mix_seed")
+        if s is None:
+            s = (torch.initial_seed() * 0x9E3779B97F4A7C15 + (self.__dict__.get("_mix_index", 0) + 1) * 0xD1B54A32D192ED03) & ((1 << 64) - 1)
+        return s
+
+    @mix_seed.setter
+    def mix_seed(self, s):
+        if s is not None:
+            if isinstance(s, bool) or not isinstance(s, numbers.Integral) or not 0 <= int(s) < (1 << 64):
+                raise ValueError(f"mix_seed must be None or an integer in [0, 2^64), got {s!r}")
+            s = int(s)
+        self.__dict__["_mix_seed"] = s
+        for k in ("_mix_state", "_mix_last"):
+            self.__dict__.pop(k, None)
+
+    @property
+    def last_mix_scale(self):
+        """The (S, E) multiplier on the mixture weights the last forward drew (a view of the site's own tensor, which the next training
+        forward overwrites: read it, do not write it), or None when that forward ran without one (both rates 0, or eval mode)."""
+        t = self.__dict__.get("_mix_last")
+        return t.detach() if t is not None else None
+
+    @property
+    def mix_calls(self):
+        """How many multipliers the site's generator has drawn since it was (re)started, read from the device (synchronises)."""
+        st = self.__dict__.get("_mix_state")
+        return int(st[1].item()) if st is not None else 0
 
     @property
     def router_aux(self):
@@ -727,7 +837,8 @@ class MoEAdapter(nn.Module):
 
     def __getstate__(self):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
-        for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux"):
+        for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux", "_mix_state", "_mix_buf",
+                  "_mix_last", "_mix_draws"):
             st.pop(k, None)
         return st
 

@@ -130,6 +130,25 @@ int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const a
 }
 
 // ---------------------------------------------------------------------------------------------
+// zero fill of a workspace range (the backward's zero-initialised accumulators; the router-only backward's dp): 16-byte stores over the
+// whole vectors, block 0 takes the bytes behind them.  ptr: 16-byte aligned (every workspace buffer is).
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) kk_zero_bytes(char* p, size_t n16, size_t n) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) ((f32x4*)p)[i] = z;
+  if (blockIdx.x == 0)
+    for (size_t j = n16 * 16 + threadIdx.x; j < n; j += 256) p[j] = 0;
+}
+int k_zero_bytes(void* ptr, size_t bytes, hipStream_t st) {
+  if (bytes == 0) return OK;
+  if (!ptr || ((size_t)ptr & 15)) { set_last_error("zero fill: pointer not 16-byte aligned"); return ERR_ALIGNMENT; }
+  const size_t n16 = bytes / 16;
+  hipLaunchKernelGGL(kk_zero_bytes, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n16 + 255) / 256, 2048))), dim3(256), 0, st, (char*)ptr, n16, bytes);
+  AVMOE_CHECK_LAUNCH("zero_bytes");
+  return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // router backward (mixture weights, LB loss, 3-layer MLP)   net_trans_v3.py:460-466,477-478
 // rbw layout: dlog [S][E] | dh2r [S][32] | dh1 [S][128] | drin [S][2C]
 // ---------------------------------------------------------------------------------------------
@@ -140,12 +159,15 @@ int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const a
 struct RouterBwdArgs {
   const float *W1, *W2, *W3; int C2, E, S, lb_loss; const float* lb_grad; const float* dprobs;
   const float *aux_grad, *lse, *load;
+  const float* mix;               // (S, E) multiplier the forward put on the mixture weights (avmoe_moe_backward_reg), or NULL
 };
 // Launch 1: per frame dlog / dh2 / dh1 (softmax, LB loss, the two small layers), one block per frame.
 // mode: the forward's mode word [k, renorm].  k = 0 (dense): dp is the gradient of probs = the softmax.  k > 0 (top-k gating):
 // `probs` holds the mixture weights w, psm the softmax p, and dp is dL/dw; it is mapped to dL/dp first (the selection S_k, recomputed
 // from p exactly as the forward made it, carries no gradient):  renorm  dp_e = m_e (dw_e - sum_j w_j dw_j) / sum_j m_j p_j ;
 // otherwise  dp_e = m_e dw_e.  The load-balancing term, dprobs and the softmax Jacobian then act on p.
+// a.mix: the forward's multiplier c on the mixture weights (such a forward always leaves k > 0: k_router).  `probs` then holds c w and dp is
+// dL/d(c w): dw_e = c_e dp_e, while sum_j w_j dw_j = sum_j (c w)_j dp_j needs no factor.  c has no gradient.  NULL: a uniform branch not taken.
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
@@ -179,7 +201,8 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
       if (renorm)
         for (int e = 0; e < a.E; ++e) wd += wt[(long)s * a.E + e] * dp[(long)s * a.E + e];
       for (int e = 0; e < a.E; ++e) {
-        const float dw = dp[(long)s * a.E + e];
+        float dw = dp[(long)s * a.E + e];
+        if (a.mix) dw *= a.mix[(long)s * a.E + e];
         dpv[e] = ((m >> e) & 1u) ? (renorm ? (dw - wd) / kept : dw) : 0.f;
       }
     }
@@ -283,11 +306,11 @@ __global__ void __launch_bounds__(256) kk_router_bwd_fin(int S, int E, int C2, i
   }
 }
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad) {
+                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad, const float* mix_scale) {
   ProfScope ps_("k_router_bwd", 0.0, 0.0, st);
   const Dims& d = pl.d;
   RouterBwdArgs a{prm.r0_w, prm.r2_w, prm.r4_w, 2 * d.C, d.E, d.S, d.lb_loss, lb_grad, dprobs,
-                  aux_grad, (const float*)(saved + pl.o_lse), (const float*)(saved + pl.o_load)};
+                  aux_grad, (const float*)(saved + pl.o_lse), (const float*)(saved + pl.o_load), mix_scale};
   hipLaunchKernelGGL(kk_router_bwd_a, dim3(d.S), dim3(256), 0, st, a, (const float*)(saved + pl.o_probs),
                      (const float*)(scratch + pl.o_dp), (const float*)(saved + pl.o_rh1), (const float*)(saved + pl.o_rh2),
                      (float*)(scratch + pl.o_rbw), (const float*)(saved + pl.o_psm), (const int*)(saved + pl.o_mode));

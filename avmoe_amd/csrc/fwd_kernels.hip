@@ -765,6 +765,7 @@ int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs&
 struct RouterArgs {
   const float *W1, *b1, *W2, *b2, *W3, *b3, *noise;
   int C2, E, S, top_k, renorm;    // top_k: 0 = the dense mixture
+  const float* mix;               // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg), or NULL; k_router then runs the top-k form
 };
 // one block per frame: layer-1 pre-activations from the engine GEMM -- summed here over its split-K slabs, in slab order, when it
 // ran split (no separate reduce pass) --, then bias / ReLU, the two small layers, softmax and first-max argmax.  fp32, fixed order.
@@ -773,6 +774,9 @@ struct RouterArgs {
 // probs_out / idx_out stay the dense softmax and its argmax.  Block 0 writes the mode word [k, renorm] (k = 0: dense) that the
 // router backward reads.  Every frame's log-sum-exp of the logits goes to `lse` (the router z-loss and its gradient need it; the
 // softmax alone does not give it back).
+// a.mix (avmoe_moe_forward_reg: stochastic depth / expert dropout) multiplies the weights that go to `probs`, behind top-k; psm,
+// probs_out, idx_out and lse do not see it.  k_router gives a.top_k = E, a.renorm = 0 for a dense site with a multiplier (w = p, every
+// expert kept), so that psm keeps the softmax for the backward and the losses.  NULL: a uniform branch not taken.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
@@ -822,8 +826,11 @@ __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, 
     if (a.top_k) {                                 // (the kept sum holds the frame's largest probability, >= 1 / E: no division by 0)
       float kept;
       const unsigned m = topk_select(s_p, a.E, a.top_k, &kept);
-      for (int e = 0; e < a.E; ++e)
-        probs[(long)s * a.E + e] = ((m >> e) & 1u) ? (a.renorm ? s_p[e] / kept : s_p[e]) : 0.f;
+      for (int e = 0; e < a.E; ++e) {
+        float w = ((m >> e) & 1u) ? (a.renorm ? s_p[e] / kept : s_p[e]) : 0.f;
+        if (a.mix) w *= a.mix[(long)s * a.E + e];
+        probs[(long)s * a.E + e] = w;
+      }
     }
   }
 }
@@ -895,14 +902,19 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
   }
 }
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out) {
+             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out,
+             const float* mix_scale) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
     set_last_error("moe: router parameters missing"); return ERR_BAD_ARG;
   }
   if (top_k < 0 || top_k > d.E) { set_last_error("moe: top_k %d not in [0, %d]", top_k, d.E); return ERR_BAD_ARG; }
-  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, top_k, renorm ? 1 : 0};
+  // A dense site with a multiplier runs as top-k with k = E without renormalisation: w = p exactly, every expert kept, and the softmax
+  // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
+  const bool mix_dense = mix_scale && !top_k;
+  const int k_mix = mix_dense ? d.E : top_k;
+  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0, mix_scale};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;
@@ -918,7 +930,7 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
                      (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), probs_out, idx_out, (lb_out && !d.lb_loss) ? lb_out : nullptr,
                      (float*)(saved + pl.o_psm), (int*)(saved + pl.o_mode), (float*)(saved + pl.o_lse));
   AVMOE_CHECK_LAUNCH("router");
-  const float* dense = (const float*)(saved + (top_k ? pl.o_psm : pl.o_probs));
+  const float* dense = (const float*)(saved + (k_mix ? pl.o_psm : pl.o_probs));
   if (aux_out) {                                           // the auxiliary losses -- and the load-balancing loss from the same launch
     hipLaunchKernelGGL(kk_router_aux, dim3(1), dim3(256), 0, st, dense, (const float*)(saved + pl.o_lse), d.S, d.E, top_k ? top_k : 1,
                        (lb_out && d.lb_loss) ? 1 : 0, lb_out, aux_out, load_out, (float*)(saved + pl.o_load));

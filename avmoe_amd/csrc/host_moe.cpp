@@ -156,6 +156,8 @@ struct Ctx {
   int topk = 0; bool renorm = true;  // top-k gating (avmoe_host_moe_forward_topk); 0 = the dense mixture
   V Yt, Yf, rin, h1, h2, logit, p;
   V w;                              // the mixture weights: p, or the top-k weights
+  const float* mix = nullptr;       // (S, E) multiplier on the mixture weights (avmoe_host_moe_forward_reg: stochastic depth / expert dropout), or NULL
+  V wm;                             // mix * w: what the experts' outputs are multiplied by (= w without mix)
   std::vector<unsigned> sel;        // top-k: the kept experts of each frame (bit e)
   V lse, load;                      // router auxiliary losses (avmoe_host_moe_forward_aux): log-sum-exp per frame, share of the slots per expert
   float aux[2] = {0.f, 0.f};        // [z, balance]
@@ -233,6 +235,8 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
       }
       for (int e = 0; e < E; ++e) c.w[s * E + e] = ((c.sel[s] >> e) & 1u) ? (c.renorm ? ps[e] / kept : ps[e]) : 0.f;
     }
+  c.wm = c.w;                        // the regularisers' multiplier, behind the top-k weights; probs / idx / lb / aux stay those of the dense site
+  if (c.mix) for (long i = 0; i < (long)S * E; ++i) c.wm[i] = c.mix[i] * c.w[i];
   // ---- router auxiliary losses: z = mean_s lse_s^2 ; balance = E sum_e load_e P_e, load from the k' = (top-k ? k : 1) most probable
   //      experts of each frame on the dense softmax (the tie rule above), P the column means of p
   {
@@ -363,7 +367,7 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
     x.pre.assign(o, o + NT * C);
     const float gt = (c.gate && q.gate) ? q.gate[0] : 1.f;
     for (int s = 0; s < S; ++s) {
-      const float w = c.w[s * E + e] * gt;
+      const float w = c.wm[s * E + e] * gt;
       for (long i = (long)s * N * C; i < (long)(s + 1) * N * C; ++i) out[i] += w * x.pre[i];
     }
   }
@@ -372,16 +376,16 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
 
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
              const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
-             const float* aux_grad);
+             const float* aux_grad, const float* mix_scale);
 
-// the one forward behind avmoe_host_moe_forward / _topk / _aux (k_min: the smallest top_k the entry point takes)
+// the one forward behind avmoe_host_moe_forward / _topk / _aux / _reg (k_min: the smallest top_k the entry point takes)
 int forward_entry(int k_min, const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, int top_k,
-                  int renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load) {
+                  int renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, const float* mix_scale) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
   if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
   if (top_k < k_min || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [%d, %d]", top_k, k_min, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale;
   if (int rc = forward(c, X, Y, *params, noise, out, probs, idx, lb, true)) return rc;
   if (aux) {
     aux[0] = c.aux[0]; aux[1] = c.aux[1];
@@ -400,7 +404,7 @@ size_t avmoe_host_moe_saved_bytes(const avmoe_moe_desc* desc) { (void)desc; retu
 int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, float* out,
                            float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  return forward_entry(0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr);
+  return forward_entry(0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr);
 }
 
 int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
@@ -412,33 +416,46 @@ int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const fl
 int avmoe_host_moe_forward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  return forward_entry(1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr);
+  return forward_entry(1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr);
 }
 int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                  const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                  const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 1) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, nullptr);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, nullptr, nullptr);
 }
 int avmoe_host_moe_forward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
                                void* saved) {
   (void)saved;
-  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load);
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr);
 }
 int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
                                 float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, nullptr);
+}
+int avmoe_host_moe_forward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, const float* mix_scale, float* out, float* probs, int64_t* idx, float* lb,
+                               float* aux, float* load, void* saved) {
+  (void)saved;
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale);
+}
+int avmoe_host_moe_backward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
+                                void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
+  (void)saved;
+  if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, mix_scale);
 }
 int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads) {
   (void)saved;
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1, nullptr);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1, nullptr, nullptr);
 }
 
 }  // extern "C"
@@ -448,11 +465,11 @@ namespace {
 // the reverse pass (the forward recomputed); top_k 0 or E: the dense mixture
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
              const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
-             const float* aux_grad) {
+             const float* aux_grad, const float* mix_scale) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
   if (top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, %d]", top_k, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0;
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale;
   if (!X || !Y || !params || !dX || !dY || !grads) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
   const avmoe_moe_ptrs& P = *params; const avmoe_moe_ptrs& G = *grads;
   const int S = c.S, N = c.N, C = c.C, M = c.M, Cy = c.Cy, E = c.E, K = c.K, d = c.d;
@@ -473,9 +490,9 @@ int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const a
     double dgate = 0.0;
     for (int s = 0; s < S; ++s) {
       double a = 0.0;
-      const float pe = c.w[s * E + e];
+      const float pe = c.wm[s * E + e];
       for (long i = (long)s * N * C; i < (long)(s + 1) * N * C; ++i) { a += (double)dOut[i] * x.pre[i]; t0[i] = dOut[i] * pe * gt; }
-      dp[s * E + e] = (float)(a * gt); dgate += a * pe;
+      dp[s * E + e] = (float)(a * gt) * (c.mix ? c.mix[s * E + e] : 1.f); dgate += a * pe;      // d(mix w) -> dw: mix has no gradient
     }
     if (c.gate && gq.gate) gq.gate[0] = (float)dgate;
     float* g = t0.data(); float* h = t1.data();            // g: gradient of the current stage's output, h: scratch for its input's
@@ -569,7 +586,7 @@ int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const a
       }
     }
   }
-  // ---- top-k gating: dp holds dL/dw so far -> dL/dp (the selection has no gradient)
+  // ---- top-k gating: dp holds dL/dw so far (already through mix: w, not mix * w, below) -> dL/dp (the selection has no gradient)
   if (c.topk)
     for (int s = 0; s < S; ++s) {
       float* d_ = dp.data() + (long)s * E;

@@ -40,7 +40,8 @@ int k_onehot_noise(float* noise, int S, int E, int hot, float value, hipStream_t
 int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float* rowb, const float* colb, hipStream_t st);
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm,            // top_k 0: the dense mixture
-             float* aux_out, float* load_out);                                                   // aux_out: [z, balance] (avmoe_moe_forward_aux)
+             float* aux_out, float* load_out,                                                    // aux_out: [z, balance] (avmoe_moe_forward_aux)
+             const float* mix_scale);                                                            // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg) or NULL
 // ---- forward: per token -----------------------------------------------------------------------
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);
@@ -63,7 +64,7 @@ int k_mid_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_m
 int k_pre_small_bwd_finalize(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm,
                              const avmoe_moe_ptrs& grads, hipStream_t st);
 int k_router_bwd(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const avmoe_moe_ptrs& grads,
-                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad);
+                 const float* lb_grad, const float* dprobs, hipStream_t st, const float* aux_grad, const float* mix_scale);
 int k_softmax_rows_bwd(int bf16, const void* a, const float* da, long rows, int n, int ld, void* out_dl, void* out_t, int grp,
                        int ldT, hipStream_t st);
 int k_finish_dT(const Plan& pl, char* saved, char* scratch, hipStream_t st);

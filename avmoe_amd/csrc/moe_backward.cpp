@@ -9,13 +9,13 @@
 
 namespace avmoe {
 
-#define MEMSET0(ptr, bytes)                                                                 \
-  do {                                                                                      \
-    hipError_t e__ = hipMemsetAsync((ptr), 0, (bytes), st);                                 \
-    if (e__ != hipSuccess) { set_last_error("memset: %s", hipGetErrorString(e__)); return ERR_LAUNCH; } \
-  } while (0)
+// Zero fill of a workspace range by a kernel of the library (bwd_kernels.hip), not hipMemsetAsync: in a captured graph the runtime's memset
+// node cleared the range on the first replay only -- from the second replay on the accumulators started from garbage
+// (tests/test_mix_drop_gpu.py replays a captured step three times; a kernel node replays like every other launch of the call).
+#define MEMSET0(ptr, bytes) AVMOE_TRY(k_zero_bytes((ptr), (bytes), st))
 
 avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* sv);   // moe_forward.cpp
+int k_zero_bytes(void* ptr, size_t bytes, hipStream_t st);                                // bwd_kernels.hip
 static const char* at(const char* base, size_t off) { return base ? base + off : nullptr; }      // (the query of moe_backward_dx_dy has no buffers)
 
 // parts: bit mask of the sections to run, 0 = 7 = the whole backward:
@@ -51,7 +51,7 @@ static void fill_dy_args(GemmSeg& v, GemmSeg& q, const Plan& pl, const char* sv,
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const void* dOut, const float* lb_grad,
                  char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads_in, hipStream_t st, int parts, const float* dprobs,
-                 const float* aux_grad) {
+                 const float* aux_grad, const float* mix_scale) {
   const Dims& d = pl.d;
   if (parts == 0) parts = 7;
   if ((parts & (32 | 64)) && (d.Kcx > 0 || d.mha || d.nxn)) { set_last_error("split backward: sections 32 / 64 serve plain sites only (this one goes on accumulating into dX)"); return ERR_UNSUPPORTED; }
@@ -142,7 +142,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   // ---- phase 3: ReLU / BN1 ; router --------------------------------------------------------------
   AVMOE_TRY(k_mid_bwd(pass, grads, st));
   BWD_STOP(5);
-  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad));
+  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad, mix_scale));
   BWD_STOP(6);
   // ---- phase 4: folded LayerNorm / hop-2 softmax ---------------------------------------------------
   if (d.nxn) MEMSET0(sc + pl.o_dZR, (size_t)d.NT * d.DZ * esz);

@@ -52,14 +52,15 @@ int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& 
 // Every caller states every option (no defaulted parameters: one that forgets an argument must not compile).
 // top_k > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture (renorm then only lands in the mode word of `saved`, unread for k = 0)
 // aux_out: [z, balance], the router auxiliary losses (avmoe_moe_forward_aux), load_out (E) with them; NULL: not formed
+// mix_scale: (S, E) multiplier on the mixture weights behind top-k (avmoe_moe_forward_reg / _backward_reg: stochastic depth, expert dropout); NULL: off
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const float* noise, void* out,
                 float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st, int top_k,
-                int renorm, float* aux_out, float* load_out);
+                int renorm, float* aux_out, float* load_out, const float* mix_scale);
 
 // aux_grad: [g_z, g_balance] after a forward with aux_out (avmoe_moe_backward_aux), or NULL
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const void* dOut, const float* lb_grad,
                  char* saved, char* scratch, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, int parts,
-                 const float* dprobs, const float* aux_grad);
+                 const float* dprobs, const float* aux_grad, const float* mix_scale);
 // the backward when `out` gets no gradient (router_only_bwd.hip): only the router and the mean / remap chain carry gradient --
 // the router backward, one pass over Y, one broadcast write of dX, small reductions; every expert gradient is written as 0
 int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,

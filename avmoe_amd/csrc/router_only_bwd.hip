@@ -10,6 +10,9 @@
 //   dWc[n,m]   = sum_s <u[s], Y[s,m,:]>       dbc[n] = sum_s sum u[s]     (the same for every n)
 // and every expert parameter gradient is 0.  Memory-bound: one pass over Y (read once, dY written in the same pass), one broadcast
 // write of dX, small reductions.
+// The multiplier on the mixture weights (avmoe_moe_backward_reg: mix_scale) scales the gradient of the mixture weights alone, and this
+// path has none (dp is zero-filled below): it does not take the tensor.  After a forward with a multiplier the router backward still
+// finds the softmax in psm, because that forward wrote the top-k mode word (fwd_kernels.hip: k_router).
 #include "kernels.h"
 #include "moe_run.h"
 #include "device_utils.h"
@@ -198,14 +201,14 @@ __global__ void __launch_bounds__(256) kk_ro_zero(ZeroList z) {
 
 }  // namespace
 
+int k_zero_bytes(void* ptr, size_t bytes, hipStream_t st);      // bwd_kernels.hip
+
 int moe_backward_router_only(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, const float* dprobs, const float* lb_grad,
                              char* sv, char* sc, void* dX, void* dY, const avmoe_moe_ptrs& grads, hipStream_t st, const float* aux_grad) {
   const Dims& d = pl.d;
   // the mixture's share of d probs is 0: the router backward sees only dprobs, the load-balancing term and the auxiliary losses
-  if (hipMemsetAsync(sc + pl.o_dp, 0, (size_t)d.S * d.E * sizeof(float), st) != hipSuccess) {
-    set_last_error("router-only backward: memset failed"); return ERR_LAUNCH;
-  }
-  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad));
+  AVMOE_TRY(k_zero_bytes(sc + pl.o_dp, (size_t)d.S * d.E * sizeof(float), st));      // (a kernel, not hipMemsetAsync: moe_backward.cpp has the reason)
+  AVMOE_TRY(k_router_bwd(pl, sv, sc, prm, grads, lb_grad, dprobs, st, aux_grad, nullptr));
   const float* drin = (const float*)(sc + pl.o_rbw) + (long)d.S * 128;
   const int nch = ro_chunks(d);
   float* u = (float*)(sc + pl.o_ro);

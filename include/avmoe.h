@@ -250,10 +250,11 @@ int avmoe_moe_backward_ex(const avmoe_moe_desc* desc, const void* X, const void*
  *             d balance / d p_se = E load_e / S joins the gradient of p before the softmax Jacobian (the selection carries no gradient,
  *             as in the mixture), d z / d l_se = (2 / S) lse_s p_se is added to the gradient of the logits after it.  No launch is
  *             added.  dOut == NULL takes the router-only path as in avmoe_moe_backward_ex.
- * These two are THE site call: the library has one forward and one backward body (csrc/capi.cpp), and the Python facade
- * (avmoe_amd.adapters) always calls the _aux entry points, with top_k = 0 for a dense site and NULL for every option that is off.
- * avmoe_moe_forward, _forward_topk, avmoe_moe_backward, _backward_part and _backward_ex remain for C callers as the same bodies with
- * fewer arguments -- they differ only in what they refuse (_topk: top_k == 0; _backward, _part: dOut == NULL) and have no behaviour of
+ * The library has one forward and one backward body (csrc/capi.cpp): since the mixture regularisers they are reached in full through
+ * avmoe_moe_forward_reg / avmoe_moe_backward_reg below, which are these two plus mix_scale.  The Python facade (avmoe_amd.adapters) calls
+ * the _aux entry points, with top_k = 0 for a dense site and NULL for every option that is off, and the _reg ones for a site call with a
+ * multiplier.  avmoe_moe_forward, _forward_topk, _forward_aux, avmoe_moe_backward, _backward_part, _backward_ex and _backward_aux remain as
+ * the same bodies with fewer arguments -- they differ only in what they refuse (_topk: top_k == 0; _backward, _part: dOut == NULL) and have no behaviour of
  * their own.                                                                                                                          */
 int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                           const float* noise, int32_t top_k /* 0: dense */, int32_t renorm, void* out, float* probs, int64_t* idx,
@@ -262,6 +263,46 @@ int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void*
 int avmoe_moe_backward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                            const void* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad /* [g_z, g_balance] or NULL */,
                            void* saved, void* scratch, void* dX, void* dY, const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
+
+/* avmoe_moe_forward_reg / avmoe_moe_backward_reg (ABI 12 in the project's count of boundary revisions; like every addition since 11 they
+ * are found by symbol and AVMOE_ABI_VERSION stays 11) -- the regularisers of the mixture: stochastic depth (drop_path) on the adapter
+ * branch and expert dropout.  Both are one per-(frame, expert) multiplier on the mixture weights, applied behind top-k:
+ *     out[s] = sum_e mix_scale[s, e] w[s, e] expert_e(x)[s]          w: the dense softmax, or the top-k weights
+ *   mix_scale: DEVICE pointer to (S, E) f32, or NULL.  The site call consumes the tensor and does not draw (the convention of `noise` and
+ *              sa_keep); avmoe_mix_drop_draw below fills it.  Any finite values are served.  NULL: avmoe_moe_forward_aux /
+ *              avmoe_moe_backward_aux, launch for launch and instruction for instruction (one uniform branch on the pointer in two router
+ *              kernels, not taken).  A tensor of ones gives the bits of NULL in every output.
+ * Only the weights the experts' outputs are mixed with change.  Every expert still runs on every frame, and BatchNorm batch and running
+ * statistics, probs, idx, lb, aux and load are those of the call without the multiplier, bit for bit.  A frame whose multipliers are all 0
+ * gets out[s] = 0 exactly (with accumulation into a residual stream at the caller, nothing is added).  A dense site (top_k 0 or E) with
+ * a multiplier is run as top-k with k = E without renormalisation -- w = p exactly -- so that `saved` keeps the softmax beside the
+ * multiplied weights; the mode word of `saved` then reads [E, 0].
+ * avmoe_moe_backward_reg takes the SAME tensor again (it is not kept in `saved`): the gradient of the mixture with respect to the weights
+ * is multiplied by mix_scale before it joins what avmoe_moe_backward_aux does (the top-k map, dprobs, lb, the auxiliary losses, the
+ * softmax Jacobian).  mix_scale itself has no gradient.  A frame whose multipliers are all 0 has dOut[s] multiplied by exactly 0 on its way
+ * into the experts; the router-side terms are untouched.  Without train-mode BatchNorm such a frame's dX / dY are therefore the router's
+ * term alone.  With it the frame's tokens still enter the batch statistics (the statistics stay dense), and the kept frames' gradients
+ * reach them through those: that part of dX / dY is not zero, and it is the derivative.  dOut == NULL (the router-only path) forms no gradient of the weights and
+ * does not read mix_scale.  A backward that follows a forward with a multiplier must be given it; every older backward entry point passes NULL. */
+int avmoe_moe_forward_reg(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                          const float* noise, int32_t top_k /* 0: dense */, int32_t renorm, const float* mix_scale /* (S,E) f32 or NULL */,
+                          void* out, float* probs, int64_t* idx, float* lb, float* aux /* [z, balance] or NULL */,
+                          float* load /* (E) or NULL */, void* saved, void* scratch, void* stream);
+int avmoe_moe_backward_reg(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                           const void* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad,
+                           const float* mix_scale /* the forward's, or NULL */, void* saved, void* scratch, void* dX, void* dY,
+                           const avmoe_moe_ptrs* grads, int32_t parts, void* stream);
+
+/* avmoe_mix_drop_draw (found by symbol, as above) -- draws mix_scale on the device, ONE launch (csrc/mix_drop.hip):
+ *     mix_scale[s, e] = a[s] b[s, e]     a[s] = 0 with probability p, else 1 / (1 - p)     b[s, e] = 0 with probability q, else 1 / (1 - q)
+ * (p: drop_path, per frame; q: expert dropout, per pair, independent, no renormalisation and no rescue of a frame that loses every
+ * expert.)  state: DEVICE pointer to 16 bytes {uint64 seed, uint64 calls}, owned by the caller, 8-byte aligned.  Generator:
+ * Philox-4x32-10, key = (seed low, seed high), counter = (calls low, calls high, s, e / 4), lane e % 4 serves expert e; the frame's draw
+ * uses counter word 3 = 0xFFFFFFFF, lane 0.  A uniform is (x >> 8) * 2^-24; dropped when u < q / u < p.  Kept values are exactly
+ * fl(fl(1 / (1 - p)) * fl(1 / (1 - q))) in fp32.  The kernel reads `calls` and stores calls + 1 itself: no host scalar changes between
+ * two calls, so a captured launch draws a fresh multiplier on every replay.  Calls on one state block must be ordered (one stream, or events).
+ * AVMOE_ERR_BAD_ARG, with nothing launched and nothing written: a NULL pointer, p or q outside [0, 1), S < 1, E outside [1, 16].       */
+int avmoe_mix_drop_draw(void* state, int64_t S, int32_t E, float p, float q, float* mix_scale, void* stream);
 
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:

@@ -60,6 +60,18 @@ int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, cons
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
                                 float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
 
+/* as avmoe_moe_forward_reg: avmoe_host_moe_forward_aux plus mix_scale, the (S, E) multiplier on the mixture weights behind top-k
+ * (stochastic depth / expert dropout), HOST pointer or NULL (= avmoe_host_moe_forward_aux).  The multiplier is an input: the host
+ * side has no generator.  probs / idx / lb / aux / load and the BatchNorm statistics do not depend on it.                           */
+int avmoe_host_moe_forward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, const float* mix_scale, float* out, float* probs, int64_t* idx, float* lb,
+                               float* aux, float* load, void* saved);
+
+/* as avmoe_moe_backward_reg: avmoe_host_moe_backward_aux with the forward's mix_scale (it carries no gradient).                     */
+int avmoe_host_moe_backward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
+                                void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
+
 #ifdef __cplusplus
 }
 #endif
