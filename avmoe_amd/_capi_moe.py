@@ -75,6 +75,24 @@ class OptLambLayout(C.Structure):
     _fields_ = [("workspace_bytes", C.c_size_t), ("report_bytes", C.c_size_t)]
 
 
+class OptProdigy(C.Structure):
+    """avmoe_opt_prodigy: the host constants of Prodigy learning-rate estimation (growth 0: no limit)"""
+    _fields_ = [("d0", C.c_float), ("d_coef", C.c_float), ("growth", C.c_float), ("safeguard_warmup", C.c_int32)]
+
+
+class OptProdigyState(C.Structure):
+    """avmoe_opt_prodigy_state: the 32-byte block avmoe_opt_prodigy_step's finalize launch keeps on the device"""
+    _fields_ = [("d", C.c_float), ("d_max", C.c_float), ("d_hat", C.c_float), ("reserved", C.c_int32), ("num", C.c_double), ("den", C.c_double)]
+
+
+class OptProdigyLayout(C.Structure):
+    """avmoe_opt_prodigy_layout: the bytes of avmoe_opt_prodigy_step's workspace and block"""
+    _fields_ = [("workspace_bytes", C.c_size_t), ("block_bytes", C.c_size_t)]
+
+
+# avmoe_opt_prodigy_state: field -> (byte offset, torch dtype name); 32 bytes
+OPT_PRODIGY_FIELDS = {"d": (0, "float32"), "d_max": (4, "float32"), "d_hat": (8, "float32"), "num": (16, "float64"), "den": (24, "float64")}
+
 # avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
 OPT_STATE_BYTES = 64
 OPT_STATE_FIELDS = {"total_norm": (0, "float32"), "clip_coef": (4, "float32"), "bc1": (8, "float32"), "bc2_sqrt": (12, "float32"),
@@ -208,6 +226,11 @@ def declare(L):
             L.avmoe_opt_lamb_bytes.restype, L.avmoe_opt_lamb_bytes.argtypes = C.c_size_t, [C.c_int32, C.c_int64, C.POINTER(OptLambLayout)]
             L.avmoe_opt_lamb_step.restype = C.c_int
             L.avmoe_opt_lamb_step.argtypes = step_args + [C.c_void_p] * 5       # shadows, hold, limits, workspace, report
+        if hasattr(L, "avmoe_opt_prodigy_step"):      # (found by symbol: Prodigy learning-rate estimation)
+            L.avmoe_opt_prodigy_bytes.restype, L.avmoe_opt_prodigy_bytes.argtypes = C.c_size_t, [C.c_int64, C.POINTER(OptProdigyLayout)]
+            L.avmoe_opt_prodigy_step.restype = C.c_int
+            # shadows, hold, x0, s, consts (HOST), block, workspace
+            L.avmoe_opt_prodigy_step.argtypes = step_args + [C.c_void_p] * 4 + [C.POINTER(OptProdigy), C.c_void_p, C.c_void_p]
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

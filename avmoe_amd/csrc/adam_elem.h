@@ -120,6 +120,83 @@ __device__ __forceinline__ void lamb_quad(float* __restrict__ p, const float* __
   }
 }
 
+// Prodigy learning-rate estimation (include/avmoe.h, avmoe_opt_prodigy_step).  What a thread reads once for all its elements: the
+// estimate d of this step, step = (lr * lr_factor) * d of its range, c = step * (d / d0) (safeguard_warmup: d * (d / d0)), deps = d * eps,
+// every product rounded to fp32 in this order by the kernel, and the constants of the run.
+struct ProdigyScal { float d, step, c, deps, b1, b2, beta3, wd, gscale; };
+
+// One element of a step, written ONCE for the 16-byte body and the scalar tail of kk_opt_prodigy_update (prodigy_quad below).  Every
+// operation is rounded to fp32 in the order written, contraction off:
+//     gr = fma(gscale, g, wd * p)          (DECOUPLED: gr = g * gscale, and p <- p * (1 - step * wd) before the Adam term)
+//     dg = d * gr ;  cg = c * gr
+//     m  = fma(b1, m, (1 - b1) * dg) ;  v = fma(b2, v, ((1 - b2) * dg) * dg)      -- adam_elem's spelling on d * gr: with d == 1 its bits
+//     s  = fma(beta3, s, cg)
+//     dot += (double)cg * ((double)x0 - (double)p)   with p as it was BEFORE the step ;   l1 += (double)|s|   with the new s
+//     den = sqrt(v) + deps ;  p = p - (step * m) / den
+// (d * gr)^2 may underflow fp32: v then takes what IEEE gradual underflow leaves, possibly 0.  Where den is not > 0 -- v == 0 and
+// d * eps == 0, or a NaN -- the quotient is not formed and the Adam term of this element is dropped: p keeps its value (DECOUPLED: its
+// decayed value), m, v, s and both sums advance as above.
+template <bool DECOUPLED>
+__device__ __forceinline__ void prodigy_elem(float& p, float& m, float& v, float& s, float g, float x0, const ProdigyScal& k, double& dot, double& l1) {
+#pragma clang fp contract(off)
+  float gr;
+  if constexpr (DECOUPLED) gr = g * k.gscale;
+  else gr = __builtin_fmaf(k.gscale, g, k.wd * p);
+  const float dg = k.d * gr, cg = k.c * gr;
+  dot += (double)cg * ((double)x0 - (double)p);
+  if constexpr (DECOUPLED) p *= 1.f - k.step * k.wd;
+  m = __builtin_fmaf(k.b1, m, (1.f - k.b1) * dg);
+  v = __builtin_fmaf(k.b2, v, ((1.f - k.b2) * dg) * dg);
+  s = __builtin_fmaf(k.beta3, s, cg);
+  l1 += (double)fabsf(s);
+  const float den = sqrtf(v) + k.deps;
+  if (den > 0.f) p -= (k.step * m) / den;
+}
+
+// elements [i0, min(i0 + 4, n)) of one range (i0 < n): reads p (HOLD: from `hold`), g, m, v, s and x0, writes p, m, v and s and adds the
+// elements' terms to `dot` and `l1`; EMA: the same thread advances the shadow from the new p with decay `decay`, as adam_quad does.
+// Four elements left: 16-byte loads, all issued before the first store.  At the tail: four loads per stream all the same, unconditional
+// at an index clamped into the range and issued before the first store; only the arithmetic and the stores are masked.
+template <bool DECOUPLED, bool EMA, bool HOLD>
+__device__ __forceinline__ void prodigy_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                             float* __restrict__ s, const float* __restrict__ x0, long i0, long n, const ProdigyScal& k,
+                                             float* __restrict__ ema, float decay, const float* __restrict__ hold, double& dot, double& l1) {
+  const float* __restrict__ src = p;
+  if constexpr (HOLD) src = hold;
+  if (i0 + 3 < n) {
+    float4 pp = *(const float4*)(src + i0), mm = *(float4*)(m + i0), vv = *(float4*)(v + i0), ss = *(float4*)(s + i0), ee;
+    const float4 gg = *(const float4*)(g + i0), xx = *(const float4*)(x0 + i0);
+    if constexpr (EMA) ee = *(float4*)(ema + i0);
+    float* P = (float*)&pp; float* M = (float*)&mm; float* V = (float*)&vv; float* S = (float*)&ss; float* E = (float*)&ee;
+    const float* G = (const float*)&gg; const float* X = (const float*)&xx;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      prodigy_elem<DECOUPLED>(P[j], M[j], V[j], S[j], G[j], X[j], k, dot, l1);
+      if constexpr (EMA) ema_elem(E[j], P[j], decay);
+    }
+    *(float4*)(p + i0) = pp; *(float4*)(m + i0) = mm; *(float4*)(v + i0) = vv; *(float4*)(s + i0) = ss;
+    if constexpr (EMA) *(float4*)(ema + i0) = ee;
+  } else {
+    const long last = n - 1;
+    long idx[4];
+    float P[4], G[4], M[4], V[4], S[4], X[4], E[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      idx[j] = i0 + j < last ? i0 + j : last;
+      P[j] = src[idx[j]]; G[j] = g[idx[j]]; M[j] = m[idx[j]]; V[j] = v[idx[j]]; S[j] = s[idx[j]]; X[j] = x0[idx[j]];
+      if constexpr (EMA) E[j] = ema[idx[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (i0 + j <= last) {
+        prodigy_elem<DECOUPLED>(P[j], M[j], V[j], S[j], G[j], X[j], k, dot, l1);
+        p[idx[j]] = P[j]; m[idx[j]] = M[j]; v[idx[j]] = V[j]; s[idx[j]] = S[j];
+        if constexpr (EMA) { ema_elem(E[j], P[j], decay); ema[idx[j]] = E[j]; }
+      }
+    }
+  }
+}
+
 // elements [i0, min(i0 + 4, n)) of one range: 16-byte loads and stores where four elements are left, element by element at the tail.
 // EMA: the same thread also advances the shadow value of each element from the parameter value it still holds in a register, with decay d
 // (without it `ema` and `d` are not read).

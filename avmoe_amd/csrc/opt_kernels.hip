@@ -37,6 +37,12 @@
 //   kk_opt_lamb_apply<DECOUPLED, SCHED, EMA, HOLD>   p = p - (lr * lr_factor * ratio) * u with u recomputed by the same helper from the
 //                                          same stored values; EMA and HOLD as in kk_opt_adam
 // The update is NOT Adam's bits (u is formed in another order of operations); the moments are.
+// and, for Prodigy learning-rate estimation (include/avmoe.h, avmoe_opt_prodigy_step), two launches in place of kk_opt_adam --
+//   kk_opt_prodigy_update<DECOUPLED, SCHED, EMA, HOLD>   the step of every element with the estimate d of the 32-byte Prodigy block in
+//                                          every rate (prodigy_elem, adam_elem.h), the running gradient sum s beside the moments, and per
+//                                          1024-element block the sums of c gr (x0 - p) and |s| in double
+//   kk_opt_prodigy_finalize                one block adds both sums in finalize's order and writes num, den, d_hat, d_max and the d of the
+//                                          NEXT step into the Prodigy block
 // The per-range norms are a kernel of their own, next to finalize, and not a part of it: finalize is ONE block whose additions define the
 // bits of total_norm, and a model has thousands of ranges -- a wave per range over many blocks finishes them in the time finalize takes,
 // inside finalize they would wait on one block's 256 threads and stretch the serial part of every step.  Finalize only resets the
@@ -472,6 +478,99 @@ __global__ void __launch_bounds__(256) kk_opt_lamb_apply(const void* __restrict_
                                   e, d, h);
 }
 
+// ---- Prodigy learning-rate estimation (include/avmoe.h, avmoe_opt_prodigy_step) ----
+static_assert(sizeof(avmoe_opt_prodigy_state) == 32 && sizeof(avmoe_opt_prodigy) == 16 && sizeof(avmoe_opt_prodigy_layout) == 16, "Prodigy layout");
+
+// The step of every element of every range with this step's d, read from the Prodigy block, and the block's two sums:
+// sums[2 b] = sum of (double)(c gr) * ((double)x0 - (double)p), sums[2 b + 1] = sum of (double)|s| over the elements of table block b, each
+// through block_sum_256 (a fixed order).  SCHED, EMA and HOLD as in kk_opt_adam; x0s[range] and ss[range] are the range's x0 and s, under
+// the rules of the shadows.  A skipped step writes nothing, the sums included; under HOLD param = hold and nothing else.  A launch that
+// does not match its table, or a range one of whose side buffers cannot take 16-byte accesses, touches nothing but its own two sums,
+// which are written as 0: kk_opt_prodigy_finalize adds every block's.
+template <bool DECOUPLED, bool SCHED, bool EMA, bool HOLD>
+__global__ void __launch_bounds__(256) kk_opt_prodigy_update(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
+                                                             float beta3, float eps, float grad_scale, float* const* __restrict__ shadows,
+                                                             float* const* __restrict__ hold, float* const* __restrict__ x0s,
+                                                             float* const* __restrict__ ss, int n_ranges, float d0, int safeguard,
+                                                             const avmoe_opt_prodigy_state* __restrict__ blk, double* __restrict__ sums) {
+  const bool skip = state->skip != 0;
+  if constexpr (!HOLD) {
+    if (skip) return;
+  }
+  OptWork w;
+  bool ok = opt_work(table, w) && w.n_ranges == n_ranges;
+  const float* x0 = nullptr; const float* h = nullptr;
+  float* s = nullptr; float* e = nullptr;
+  if (ok) {
+    x0 = opt_shadow(w, x0s, n_ranges);
+    s = opt_shadow(w, ss, n_ranges);
+    ok = x0 != nullptr && s != nullptr;
+    if constexpr (HOLD) { h = opt_shadow(w, hold, n_ranges); ok = ok && h != nullptr; }
+    if constexpr (EMA) { e = opt_shadow(w, shadows, n_ranges); ok = ok && e != nullptr; }
+  }
+  if constexpr (HOLD) {
+    if (skip) {                                          // the whole launch takes this branch: no sum is formed
+      if (ok) restore_quad(w.r.param, h, w.i0, (long)w.r.n);
+      return;
+    }
+  }
+  double dot = 0.0, l1 = 0.0;
+  if (ok) {
+#pragma clang fp contract(off)
+    const avmoe_opt_range& r = w.r;
+    float lr = r.lr;
+    if constexpr (SCHED) lr *= state->lr_factor;
+    ProdigyScal k;
+    k.d = blk->d;
+    k.step = lr * k.d;
+    const float dd0 = k.d / d0;
+    k.c = (safeguard ? k.d : k.step) * dd0;
+    k.deps = k.d * eps;
+    k.b1 = b1; k.b2 = b2; k.beta3 = beta3; k.wd = r.weight_decay;
+    k.gscale = grad_scale * state->clip_coef;
+    float decay = 0.f;
+    if constexpr (EMA) decay = state->ema_decay;
+    prodigy_quad<DECOUPLED, EMA, HOLD>(r.param, r.grad, r.exp_avg, r.exp_avg_sq, s, x0, w.i0, (long)r.n, k, e, decay, h, dot, l1);
+  }
+  const double td = block_sum_256(dot);
+  __syncthreads();                                      // the tree's LDS is used a second time
+  const double ta = block_sum_256(l1);
+  if (threadIdx.x == 0) { sums[2 * (long)blockIdx.x] = td; sums[2 * (long)blockIdx.x + 1] = ta; }
+}
+
+// One block.  Thread t adds sums of blocks t, t + 256, ... in that order, the 256 thread sums go through block_sum_256: opt_total_256's
+// order over each of the two interleaved sums.  Then, in double unless stated (FlatAdam.prodigy_d_next in avmoe_amd/train.py is the
+// host's copy; contraction off):
+//     num = beta3 * num + sum_dot ;  den = sum_abs
+//     d_hat = fp32(d_coef * num / den)      left as it is when den is not > 0 or num, den or the quotient is not a finite fp32
+//     d_max = max(d_max, d_hat) ;  d = min(d_max, fp32(d * growth))      growth == 0: d = d_max
+// A skipped step, or a launch that does not match its table's header, leaves the block as it is.
+__global__ void __launch_bounds__(256) kk_opt_prodigy_finalize(const void* __restrict__ table, int n_ranges, long n_blocks,
+                                                               const double* __restrict__ sums, const avmoe_opt_state* __restrict__ state,
+                                                               avmoe_opt_prodigy_state* __restrict__ blk, float beta3, float d_coef, float growth) {
+#pragma clang fp contract(off)
+  if (state->skip) return;
+  const OptHeader h = *(const OptHeader*)table;
+  if (h.magic != OPT_MAGIC || h.n_ranges != n_ranges || h.n_blocks != n_blocks) return;
+  double ad = 0.0, aa = 0.0;
+  for (long i = threadIdx.x; i < n_blocks; i += 256) { ad += sums[2 * i]; aa += sums[2 * i + 1]; }
+  const double sum_dot = block_sum_256(ad);
+  __syncthreads();
+  const double sum_abs = block_sum_256(aa);
+  if (threadIdx.x != 0) return;
+  const double num = (double)beta3 * blk->num + sum_dot, den = sum_abs;
+  float d_hat = blk->d_hat, d_max = blk->d_max, d = blk->d;
+  if (den > 0.0 && isfinite(num) && isfinite(den)) {
+    const double q = (double)d_coef * num / den;
+    if (fabs(q) <= 3.4028234663852886e38) d_hat = (float)q;
+  }
+  d_max = d_hat > d_max ? d_hat : d_max;
+  if (growth > 0.f) { const float g = d * growth; d = g < d_max ? g : d_max; }
+  else d = d_max;
+  blk->num = num; blk->den = den;
+  blk->d_hat = d_hat; blk->d_max = d_max; blk->d = d;
+}
+
 // One block: the SAM block from the partial sums of the perturbing gradient's norm pass.  The sum, the square root and its rounding are
 // those of kk_opt_finalize, so `norm` has the bits total_norm gets from the same partial sums.
 __global__ void __launch_bounds__(256) kk_opt_sam_finalize(const double* __restrict__ partials, long n_partials, avmoe_opt_sam_state* __restrict__ sam,
@@ -626,6 +725,17 @@ constexpr LambApplyKernel OPT_LAMB_APPLY[16] = {      // [DECOUPLED | SCHED << 1
     kk_opt_lamb_apply<true, false, false, true>,   kk_opt_lamb_apply<false, true, false, true>,  kk_opt_lamb_apply<true, true, false, true>,
     kk_opt_lamb_apply<false, false, true, true>,   kk_opt_lamb_apply<true, false, true, true>,   kk_opt_lamb_apply<false, true, true, true>,
     kk_opt_lamb_apply<true, true, true, true>};
+
+using ProdigyKernel = decltype(&kk_opt_prodigy_update<false, false, false, false>);
+constexpr ProdigyKernel OPT_PRODIGY[16] = {           // [DECOUPLED | SCHED << 1 | EMA << 2 | HOLD << 3]
+    kk_opt_prodigy_update<false, false, false, false>, kk_opt_prodigy_update<true, false, false, false>,
+    kk_opt_prodigy_update<false, true, false, false>,  kk_opt_prodigy_update<true, true, false, false>,
+    kk_opt_prodigy_update<false, false, true, false>,  kk_opt_prodigy_update<true, false, true, false>,
+    kk_opt_prodigy_update<false, true, true, false>,   kk_opt_prodigy_update<true, true, true, false>,
+    kk_opt_prodigy_update<false, false, false, true>,  kk_opt_prodigy_update<true, false, false, true>,
+    kk_opt_prodigy_update<false, true, false, true>,   kk_opt_prodigy_update<true, true, false, true>,
+    kk_opt_prodigy_update<false, false, true, true>,   kk_opt_prodigy_update<true, false, true, true>,
+    kk_opt_prodigy_update<false, true, true, true>,    kk_opt_prodigy_update<true, true, true, true>};
 
 static long range_blocks(int64_t n) { return (long)((n + OPT_BLOCK - 1) / OPT_BLOCK); }
 
@@ -989,6 +1099,51 @@ int avmoe_opt_lamb_step(const void* table, int32_t n_ranges, int64_t n_blocks, c
                        (hipStream_t)stream, table, state, eps, ema ? shadows : nullptr, hold, (int)n_ranges, (const avmoe_opt_lamb_header*)rep);
     AVMOE_CHECK_LAUNCH("opt_lamb_apply");
   }
+  return OK;
+}
+
+size_t avmoe_opt_prodigy_bytes(int64_t n_blocks, avmoe_opt_prodigy_layout* layout) {
+  if (n_blocks < 0 || n_blocks > (int64_t)INT32_MAX) { set_last_error("avmoe_opt_prodigy_bytes: bad block count %lld", (long long)n_blocks); return 0; }
+  avmoe_opt_prodigy_layout l;
+  l.workspace_bytes = round16((size_t)(n_blocks > 0 ? n_blocks : 1) * 2 * sizeof(double));
+  l.block_bytes = sizeof(avmoe_opt_prodigy_state);
+  if (layout) *layout = l;
+  return l.workspace_bytes + l.block_bytes;
+}
+
+int avmoe_opt_prodigy_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2, float eps,
+                           float grad_scale, int32_t flags, void* stream, float* const* shadows, float* const* hold, float* const* x0,
+                           float* const* s, const avmoe_opt_prodigy* consts, avmoe_opt_prodigy_state* block, double* workspace) {
+  const char* who = "avmoe_opt_prodigy_step";
+  const bool with_hold = hold != nullptr;
+  AVMOE_TRY(check_step_args(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, OPT_FLAGS | AVMOE_OPT_LR_SCHEDULE | AVMOE_OPT_EMA,
+                            shadows, with_hold, hold));
+  if (!x0 || !s) { set_last_error("%s: the x0 / s pointer array is NULL", who); return ERR_BAD_ARG; }
+  if (!consts) { set_last_error("%s: the constants are NULL", who); return ERR_BAD_ARG; }
+  if (!block) { set_last_error("%s: the Prodigy block is NULL", who); return ERR_BAD_ARG; }
+  if (!workspace) { set_last_error("%s: the workspace is NULL", who); return ERR_BAD_ARG; }
+  if (!(consts->d0 > 0.f) || std::isinf(consts->d0)) { set_last_error("%s: d0 must be a finite number > 0", who); return ERR_BAD_ARG; }
+  if (!(consts->d_coef > 0.f) || std::isinf(consts->d_coef)) { set_last_error("%s: d_coef must be a finite number > 0", who); return ERR_BAD_ARG; }
+  if (!(consts->growth == 0.f || consts->growth >= 1.f) || std::isinf(consts->growth)) {
+    set_last_error("%s: growth must be 0 (none) or a finite number >= 1", who); return ERR_BAD_ARG;
+  }
+  if (consts->safeguard_warmup != 0 && consts->safeguard_warmup != 1) {
+    set_last_error("%s: safeguard_warmup must be 0 or 1, not %d", who, (int)consts->safeguard_warmup); return ERR_BAD_ARG;
+  }
+  if ((((uintptr_t)x0 | (uintptr_t)s) & 7u) != 0) { set_last_error("%s: the x0 / s pointer arrays must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+  if (((uintptr_t)block & 15u) != 0) { set_last_error("%s: the Prodigy block must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  if (((uintptr_t)workspace & 7u) != 0) { set_last_error("%s: the workspace must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+  const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
+  const float beta3 = (float)sqrt((double)beta2);
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(OPT_PRODIGY[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
+                       (hipStream_t)stream, table, state, beta1, beta2, beta3, eps, grad_scale, ema ? shadows : nullptr, hold, x0, s, (int)n_ranges,
+                       consts->d0, (int)consts->safeguard_warmup, (const avmoe_opt_prodigy_state*)block, workspace);
+    AVMOE_CHECK_LAUNCH("opt_prodigy_update");
+  }
+  hipLaunchKernelGGL(kk_opt_prodigy_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, table, (int)n_ranges, (long)n_blocks,
+                     (const double*)workspace, state, block, beta3, consts->d_coef, consts->growth);
+  AVMOE_CHECK_LAUNCH("opt_prodigy_finalize");
   return OK;
 }
 

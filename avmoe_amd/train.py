@@ -335,6 +335,36 @@ class FlatAdam:
     as before.  Under data parallelism the gradients agree on every rank after `red.finish()`, and so do moments, norms and ratios: no
     communication is added.  NOT covered: the plain (non-device) path, parameters outside the reducer.
 
+    Learning-rate estimation.  `prodigy=True` (Prodigy, Mishchenko & Defazio 2024; it selects the device path too) replaces the base
+    rate by an estimate d that the step maintains: every rate -- `lr`, a group's "lr", times the schedule's factor -- is a MULTIPLIER of
+    d (default use: `lr=1.0`; the reference's lr / lr_mlp ratio between groups keeps its meaning).  With g' the gradient as the update
+    sees it (scale, clip factor, coupled decay), step = lr * lr_factor * d and c = step * d / d0 (`prodigy_safeguard_warmup`:
+    c = d * d / d0):
+
+        m = b1 m + (1 - b1) d g' ;  v = b2 v + (1 - b2) (d g')^2 ;  s = beta3 s + c g'          beta3 = sqrt(b2)
+        num = beta3 num + sum c g' (x0 - w) ;  den = sum |s| ;  d_hat = d_coef num / den
+        w = w - step m / (sqrt(v) + d eps)
+        d_max = max(d_max, d_hat) ;  d = min(d_max, d * growth)        (without `prodigy_growth`: d = d_max)
+
+    with w the weights before the step (behind `sam_perturb()` the held ones) and x0 the weights when the optimizer was built or its
+    state loaded.  d starts at `prodigy_d0` and never falls; step k uses d_k.  There is NO bias correction, as in the paper: use
+    `lr_schedule=LRSchedule(warmup_steps=...)`, and `prodigy_safeguard_warmup=True` with it.  The recipe: `FlatAdam(red, lr=1.0,
+    prodigy=True, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0, lr_schedule=LRSchedule(warmup_steps=...))`.
+    A step is the unchanged norm call and then TWO launches in place of the update (include/avmoe.h, avmoe_opt_prodigy_step): the update
+    with per-block sums of both reductions in double, and one block that adds them in a fixed order and writes d for the next step --
+    no host synchronisation, no step-dependent host scalar, capturable; a host implementation needs a dot product and an L1 norm over
+    every tensor and a host read of d per step.  One flat x0 and one flat s buffer per bucket, with the bucket's layout.  Clipping,
+    skipping (a skipped step leaves d, num, s and everything else bit for bit), both decays, schedule, averages, averaged buffers,
+    per-parameter gradient norms and SAM compose unchanged; `trust_ratio` together with it raises ValueError (two rules for the step
+    size).  `prodigy_d`, `prodigy_d_hat` are fp32 DEVICE scalars (views of the 32-byte Prodigy block; `prodigy_d` is the d of the NEXT
+    step), `prodigy_x0`, `prodigy_s` lists of DEVICE views in `params` order; `prodigy_d_next(...)` is the host's copy of the finalize
+    rule.  `state_dict()` carries the constants, "prodigy_d" / "prodigy_d_max" / "prodigy_d_hat" / "prodigy_num" / "prodigy_den",
+    "prodigy_x0" and "prodigy_s" under "flat_adam"; `load_state_dict()` restores them, a dict without them re-seeds (x0 = the CURRENT
+    parameters, s = 0, d = d0: load the model first), and a dict saved with the option does not load into an optimizer built without
+    it (ValueError).  Under data parallelism the gradients agree on every rank after `red.finish()` and the parameters start equal, so
+    x0, s, both sums and d agree too: no communication is added (verified on one rank).  NOT covered: `trust_ratio` together with it,
+    bias correction, the plain (non-device) path, parameters outside the reducer.
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -351,7 +381,8 @@ class FlatAdam:
                  lr_schedule: Optional[LRSchedule] = None, ema_decay: Optional[float] = None, ema_warmup: float = 10.0,
                  report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1,
                  sam_rho: Optional[float] = None, sam_adaptive: bool = False, trust_ratio: bool = False,
-                 trust_clip: Optional[float] = None):
+                 trust_clip: Optional[float] = None, prodigy: bool = False, prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0,
+                 prodigy_growth: Optional[float] = None, prodigy_safeguard_warmup: bool = False):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -363,7 +394,11 @@ class FlatAdam:
         sharpness-aware minimization, `sam_perturb()` between two backward passes (class docstring); sam_adaptive: its adaptive form
         (ValueError without `sam_rho`).  trust_ratio: layer-wise trust ratios (LAMB; class docstring): every adapted parameter's step is
         scaled by ||w|| / ||update||, computed on the device; trust_clip: the largest ratio allowed (a finite number > 0, held as fp32;
-        None: no clamp; ValueError without `trust_ratio`).  Any of the nine selects the device path (class docstring); with all at their
+        None: no clamp; ValueError without `trust_ratio`).  prodigy: Prodigy learning-rate estimation (class docstring): every rate is a
+        multiplier of an estimate d kept on the device; prodigy_d0 > 0: its start, prodigy_d_coef > 0: a factor on the estimate,
+        prodigy_growth >= 1 or None: the largest factor d may grow by per step, prodigy_safeguard_warmup: leave the rate out of a step's
+        weight in the estimate (all held as fp32; ValueError for a bad value, for one given without `prodigy`, and for `prodigy` with
+        `trust_ratio`).  Any of the ten selects the device path (class docstring); with all at their
         defaults step() is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
         and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
@@ -394,6 +429,10 @@ class FlatAdam:
         self.sam_rho, self.sam_adaptive = self._check_sam(sam_rho, sam_adaptive)
         self._perturbed = False                          # the parameters currently hold w + e, the hold buffers w (sam_perturb)
         self.trust_ratio, self.trust_clip = self._check_trust(trust_ratio, trust_clip)
+        self.prodigy, self.prodigy_d0, self.prodigy_d_coef, self.prodigy_growth, self.prodigy_safeguard_warmup = \
+            self._check_prodigy(prodigy, prodigy_d0, prodigy_d_coef, prodigy_growth, prodigy_safeguard_warmup)
+        if self.prodigy and self.trust_ratio:
+            raise ValueError("prodigy and trust_ratio are two rules for the step size: choose one")
         for grp in (param_groups or []):                 # before anything is touched
             if "trust_ratio" in grp and not isinstance(grp["trust_ratio"], bool):
                 raise ValueError(f"a parameter group's \"trust_ratio\" must be True or False, not {grp['trust_ratio']!r}")
@@ -432,9 +471,13 @@ class FlatAdam:
                 self.state[-1]["e"] = flat_p.clone()
             if self.sam_rho is not None:                 # the hold buffers: the bucket's layout once more, written by every sam_perturb()
                 self.state[-1]["h"] = torch.zeros_like(flat_p)
+            if self.prodigy:                             # x0 and the running gradient sum: the bucket's layout twice more, padding zero
+                self.state[-1]["x0"] = flat_p.clone()
+                self.state[-1]["s"] = torch.zeros_like(flat_p)
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
-            or self._averaging or self.report_grad_norms or self.sam_rho is not None or self.trust_ratio
+            or self._averaging or self.report_grad_norms or self.sam_rho is not None or self.trust_ratio \
+            or self.prodigy
         if self._device:
             self._build_device_state()
 
@@ -723,8 +766,15 @@ class FlatAdam:
 
     def _update(self, L, stream, n, scale, flags, shadows):
         """the update launch of a device step: avmoe_opt_adam_step_ema, or behind a sam_perturb() avmoe_opt_adam_step_sam, which reads
-        the parameters from the hold buffers and so brings the unperturbed weights back; with `trust_ratio` avmoe_opt_lamb_step serves
-        both cases"""
+        the parameters from the hold buffers and so brings the unperturbed weights back; with `trust_ratio` avmoe_opt_lamb_step and
+        with `prodigy` avmoe_opt_prodigy_step serve both cases"""
+        if self.prodigy:                                 # two launches in place of one; the hold buffers only behind a sam_perturb()
+            capi.check(L.avmoe_opt_prodigy_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1], self.eps, scale,
+                                                flags, stream, shadows, self._hold_ptrs.data_ptr() if self._perturbed else None,
+                                                self._prodigy_x0_ptrs.data_ptr(), self._prodigy_s_ptrs.data_ptr(), C.byref(self._prodigy_c),
+                                                self._prodigy_block.data_ptr(), self._prodigy_ws.data_ptr()), "avmoe_opt_prodigy_step")
+            self._perturbed = False
+            return
         if self.trust_ratio:                             # three launches in place of one; the hold buffers only behind a sam_perturb()
             capi.check(L.avmoe_opt_lamb_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1], self.eps, scale,
                                              flags, stream, shadows, self._hold_ptrs.data_ptr() if self._perturbed else None,
@@ -817,6 +867,124 @@ class FlatAdam:
         self._need_trust("last_update_norms")
         return self._trust_views["u_norm"]
 
+    # ---- Prodigy learning-rate estimation ---------------------------------------------------------------------------
+    @staticmethod
+    def _check_prodigy(on, d0, d_coef, growth, safeguard):
+        """-> (prodigy, d0, d_coef, growth or None, safeguard_warmup) with the numbers as the fp32 values the device gets"""
+        if not isinstance(on, bool):
+            raise ValueError(f"prodigy must be True or False, not {on!r}")
+        if not isinstance(safeguard, bool):
+            raise ValueError(f"prodigy_safeguard_warmup must be True or False, not {safeguard!r}")
+        big = 3.4028234663852886e38
+        a, c = float(d0), float(d_coef)
+        if not (a > 0.0) or a > big or _f32(a) == 0.0:
+            raise ValueError(f"prodigy_d0 must be a finite number > 0 (as fp32), not {d0!r}")
+        if not (c > 0.0) or c > big or _f32(c) == 0.0:
+            raise ValueError(f"prodigy_d_coef must be a finite number > 0 (as fp32), not {d_coef!r}")
+        g = None
+        if growth is not None:
+            g = float(growth)
+            if not (g >= 1.0) or g > big:
+                raise ValueError(f"prodigy_growth must be a finite number >= 1 or None, not {growth!r}")
+            g = _f32(g)
+        if not on and (_f32(a) != _f32(1e-6) or c != 1.0 or g is not None or safeguard):
+            raise ValueError("prodigy_d0 / prodigy_d_coef / prodigy_growth / prodigy_safeguard_warmup need prodigy: there is no estimate to shape")
+        return on, _f32(a), _f32(c), g, safeguard
+
+    @staticmethod
+    def prodigy_d_next(d: float, d_max: float, d_hat: float, num: float, sum_dot: float, sum_abs: float, beta2: float,
+                       d_coef: float = 1.0, growth: Optional[float] = None) -> dict:
+        """The host's copy of the rule kk_opt_prodigy_finalize applies after an applied step: from the block's words before the step
+        (d, d_max, d_hat as fp32 values, num) and the step's two sums -> {"d", "d_max", "d_hat", "num", "den"} as the block holds them
+        after it.  num = beta3 num + sum_dot and den = sum_abs in double with beta3 = fp32(sqrt(beta2)); d_hat = fp32(d_coef num / den),
+        left where den is not > 0 or a term is not a finite fp32; d_max = max(d_max, d_hat); d = min(d_max, fp32(d * growth)),
+        without `growth` d_max."""
+        beta3 = _f32(math.sqrt(float(beta2)))
+        num1, den = beta3 * float(num) + float(sum_dot), float(sum_abs)
+        if den > 0.0 and math.isfinite(num1) and math.isfinite(den):
+            q = _f32(float(d_coef)) * num1 / den
+            if abs(q) <= 3.4028234663852886e38:
+                d_hat = _f32(q)
+        d_max = max(float(d_max), float(d_hat))
+        d1 = d_max if growth is None else min(d_max, _f32(float(d) * _f32(float(growth))))
+        return {"d": d1, "d_max": d_max, "d_hat": float(d_hat), "num": num1, "den": den}
+
+    def _need_prodigy(self, what):
+        if not self.prodigy:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs prodigy")
+
+    def _build_prodigy(self):
+        """the device arrays of one x0 and one s pointer per range, beside the shadows', the 32-byte block (d = d_max = d0), the
+        workspace of two doubles per table block and the constants step() hands over"""
+        L = capi.lib()
+        if not hasattr(L, "avmoe_opt_prodigy_step"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks Prodigy learning-rate estimation (avmoe_opt_prodigy_step): rebuild it")
+        lay = cm.OptProdigyLayout()
+        if L.avmoe_opt_prodigy_bytes(self._n_blocks, C.byref(lay)) == 0:
+            capi.check(-1, "avmoe_opt_prodigy_bytes")
+        self._prodigy_x0_views, self._prodigy_s_views, px, ps = [], [], [], []
+        for p, si, off, _lr0 in self._plist:
+            x, s = self.state[si]["x0"], self.state[si]["s"]
+            self._prodigy_x0_views.append(x[off:off + p.numel()].view_as(p))
+            self._prodigy_s_views.append(s[off:off + p.numel()].view_as(p))
+            px.append(x.data_ptr() + 4 * off)
+            ps.append(s.data_ptr() + 4 * off)
+        if any(q % 16 for q in px + ps):
+            raise capi.AvmoeError("FlatAdam: an x0 / s range is not 16-byte aligned")
+        self._prodigy_x0_ptrs = torch.tensor(px, dtype=torch.int64).to(self._dev)
+        self._prodigy_s_ptrs = torch.tensor(ps, dtype=torch.int64).to(self._dev)
+        self._prodigy_ws = torch.zeros(int(lay.workspace_bytes), dtype=torch.uint8, device=self._dev)
+        self._prodigy_block = torch.zeros(int(lay.block_bytes), dtype=torch.uint8, device=self._dev)
+        self._prodigy_views = {k: self._prodigy_block[o:o + (8 if dt == "float64" else 4)].view(getattr(torch, dt))[0]
+                               for k, (o, dt) in cm.OPT_PRODIGY_FIELDS.items()}
+        self._set_prodigy(self.prodigy_d0, self.prodigy_d_coef, self.prodigy_growth, self.prodigy_safeguard_warmup)
+        self._seed_prodigy()
+
+    def _set_prodigy(self, d0, d_coef, growth, safeguard):
+        self.prodigy_d0, self.prodigy_d_coef, self.prodigy_growth, self.prodigy_safeguard_warmup = d0, d_coef, growth, safeguard
+        self._prodigy_c = cm.OptProdigy(d0=d0, d_coef=d_coef, growth=0.0 if growth is None else growth, safeguard_warmup=int(safeguard))
+
+    def _seed_prodigy(self):
+        """the start of a run: x0 = the parameters as they are now, s = 0, the block {d0, d0, 0, 0, 0.0, 0.0}"""
+        for s in self.state:
+            s["x0"].copy_(s["p"])
+            s["s"].zero_()
+        self._prodigy_block.zero_()
+        self._prodigy_views["d"].fill_(self.prodigy_d0)
+        self._prodigy_views["d_max"].fill_(self.prodigy_d0)
+
+    @property
+    def prodigy_d(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the estimate d the NEXT applied step uses (d0 until the first one).  A view of the 32-byte Prodigy block,
+        rewritten by every applied step and by every replay of a captured one (a skipped step leaves it): `.item()` is the caller's
+        synchronisation.  Only with `prodigy`."""
+        self._need_prodigy("prodigy_d")
+        return self._prodigy_views["d"]
+
+    @property
+    def prodigy_d_hat(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: d_coef * num / den of the last applied step, which may lie below d or be negative.  As `prodigy_d`."""
+        self._need_prodigy("prodigy_d_hat")
+        return self._prodigy_views["d_hat"]
+
+    @property
+    def prodigy_block(self) -> Dict[str, torch.Tensor]:
+        """every word of the Prodigy block as DEVICE scalars: d, d_max, d_hat (fp32), num, den (fp64).  As `prodigy_d`."""
+        self._need_prodigy("prodigy_block")
+        return dict(self._prodigy_views)
+
+    @property
+    def prodigy_x0(self) -> List[torch.Tensor]:
+        """DEVICE views in `params` order: the parameters as they were when the optimizer was built or its state loaded"""
+        self._need_prodigy("prodigy_x0")
+        return list(self._prodigy_x0_views)
+
+    @property
+    def prodigy_s(self) -> List[torch.Tensor]:
+        """DEVICE views in `params` order: the running gradient sum s of every parameter"""
+        self._need_prodigy("prodigy_s")
+        return list(self._prodigy_s_views)
+
     # ---- the device path ------------------------------------------------------------------------------------------
     def _opt_ranges(self):
         """one avmoe_opt_range per parameter (its own elements only: the norm must not see alignment padding)"""
@@ -861,6 +1029,8 @@ class FlatAdam:
             self._build_sam()
         if self.trust_ratio:
             self._build_trust()
+        if self.prodigy:
+            self._build_prodigy()
 
     def _build_report(self):
         """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
@@ -1104,6 +1274,13 @@ class FlatAdam:
             extra.update(sam_rho=self.sam_rho, sam_adaptive=self.sam_adaptive)
         if self.trust_ratio:                             # constants only: norms and ratios are rewritten by every step
             extra.update(trust_ratio=True, trust_clip=self.trust_clip)
+        if self.prodigy:                                 # the constants, the block and the two per-element buffers
+            blk = {k: v.item() for k, v in self._prodigy_views.items()}
+            extra.update(prodigy=True, prodigy_d0=self.prodigy_d0, prodigy_d_coef=self.prodigy_d_coef, prodigy_growth=self.prodigy_growth,
+                         prodigy_safeguard_warmup=self.prodigy_safeguard_warmup, prodigy_d=blk["d"], prodigy_d_max=blk["d_max"],
+                         prodigy_d_hat=blk["d_hat"], prodigy_num=blk["num"], prodigy_den=blk["den"],
+                         prodigy_x0=[x.detach().cpu().clone() for x in self._prodigy_x0_views],
+                         prodigy_s=[x.detach().cpu().clone() for x in self._prodigy_s_views])
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
             extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
@@ -1120,7 +1297,11 @@ class FlatAdam:
         dict without them re-seeds the shadows from the CURRENT buffers; without the option saved ones are ignored.  With `sam_rho`: saved
         "sam_rho" / "sam_adaptive" replace the constructor's (ValueError for a bad value); a dict without them leaves them, and
         without the option saved ones are ignored.  With `trust_ratio`: a saved "trust_clip" (beside "trust_ratio": True) replaces the
-        constructor's, likewise; which parameters are adapted stays what the constructor's groups say."""
+        constructor's, likewise; which parameters are adapted stays what the constructor's groups say.  With `prodigy`: the saved constants,
+        block ("prodigy_d", "prodigy_d_max", "prodigy_d_hat", "prodigy_num", "prodigy_den"), "prodigy_x0" and "prodigy_s" are restored
+        (a count or shape mismatch raises ValueError naming the parameter); a dict without "prodigy" re-seeds: x0 = the CURRENT
+        parameters, s = 0, d = d0, so load the model first.  Without the option a dict that carries "prodigy" raises ValueError: its
+        rates are multipliers of d, not learning rates."""
         self._not_swapped("load_state_dict()")
         self._not_perturbed("load_state_dict()")
         saved_groups, own_groups = sd["param_groups"], self._groups()
@@ -1180,6 +1361,27 @@ class FlatAdam:
         trust_consts = None
         if self.trust_ratio and extra.get("trust_ratio") is True:
             trust_consts = self._check_trust(True, extra.get("trust_clip"))
+        if extra.get("prodigy") is True and not self.prodigy:
+            raise ValueError("the state dict was saved with prodigy (its rates are multipliers of the estimate d), which this optimizer "
+                             "was built without: build it with prodigy=True")
+        prodigy_saved = None
+        if self.prodigy and extra.get("prodigy") is True:
+            consts = self._check_prodigy(True, extra.get("prodigy_d0", self.prodigy_d0), extra.get("prodigy_d_coef", self.prodigy_d_coef),
+                                         extra.get("prodigy_growth"), extra.get("prodigy_safeguard_warmup", False))[1:]
+            lists = {}
+            for key in ("prodigy_x0", "prodigy_s"):
+                lst = extra.get(key)
+                if lst is None or len(lst) != len(self._plist):
+                    raise ValueError(f"state dict has {0 if lst is None else len(lst)} tensors under {key!r}, this optimizer {len(self._plist)} parameters")
+                for i, (x, (p, _si, _off, _lr0)) in enumerate(zip(lst, self._plist)):
+                    if tuple(x.shape) != tuple(p.shape):
+                        raise ValueError(f"parameter index {i}: {key} has shape {tuple(x.shape)}, the parameter {tuple(p.shape)}")
+                lists[key] = lst
+            d, d_max = float(extra["prodigy_d"]), float(extra.get("prodigy_d_max", extra["prodigy_d"]))
+            if not (d > 0.0 and d_max >= d and math.isfinite(d_max)):
+                raise ValueError(f"the state dict's prodigy_d / prodigy_d_max must be finite with 0 < d <= d_max, not {d!r} / {d_max!r}")
+            prodigy_saved = (consts, lists, {"d": d, "d_max": d_max, "d_hat": float(extra.get("prodigy_d_hat", 0.0)),
+                                             "num": float(extra.get("prodigy_num", 0.0)), "den": float(extra.get("prodigy_den", 0.0))})
         saved_bufs = extra.get("ema_buffers") if self._ebufs else None
         if saved_bufs is not None:
             names = self.ema_buffer_names
@@ -1247,6 +1449,17 @@ class FlatAdam:
                             view.copy_(e.to(torch.float32))
                     else:                                 # no buffer averages in the dict: start them from the buffers as they are now
                         self._seed_buffer_shadows()
+                if self.prodigy:
+                    if prodigy_saved is not None:
+                        consts, lists, blk = prodigy_saved
+                        self._set_prodigy(*consts)
+                        for views, key in ((self._prodigy_x0_views, "prodigy_x0"), (self._prodigy_s_views, "prodigy_s")):
+                            for view, x in zip(views, lists[key]):
+                                view.copy_(x.to(torch.float32))
+                        for k, val in blk.items():
+                            self._prodigy_views[k].fill_(val)
+                    else:                                 # nothing saved: the run starts here, from the parameters as they are now
+                        self._seed_prodigy()
                 self._upload_table()
             else:
                 self.t = applied                          # the plain path's bias correction counts self.t

@@ -709,6 +709,77 @@ int avmoe_opt_lamb_step(const void* table, int32_t n_ranges, int64_t n_blocks, c
                         float* const* hold /* DEVICE, or NULL */, const float* limits /* DEVICE, n_ranges floats */,
                         double* workspace /* DEVICE */, void* report /* DEVICE, 16-byte aligned */);
 
+/* Prodigy learning-rate estimation (Mishchenko & Defazio, "Prodigy: An Expeditiously Adaptive Parameter-Free Learner"; added under ABI 11
+ * like the blocks above; found by symbol): the step size is lr_r * d with an estimate d of the distance to the solution that the step
+ * itself maintains, from two global sums per step.  No flag and no new word in the state block: avmoe_opt_prodigy_step is called IN PLACE
+ * of avmoe_opt_adam_step_ema / avmoe_opt_adam_step_sam, behind the unchanged norm call of a step, on the same stream with the same
+ * grad_scale and betas, and every entry point above keeps refusing what it refuses.
+ * State beyond Adam's: per element x0 (the parameter where the run started) and s (a running gradient sum, zero at the start), in flat
+ * side buffers addressed by DEVICE arrays of n_ranges float* under the rules of `shadows`; and the 32-byte avmoe_opt_prodigy_state on the
+ * device, which starts as {d0, d0, 0, 0, 0.0, 0.0}.  Constants of a run (avmoe_opt_prodigy, HOST): d0 > 0, d_coef > 0, growth >= 1 or
+ * 0 for none, safeguard_warmup 0 / 1; and beta3 = fp32(sqrt((double)beta2)).
+ * An applied step reads d from the block.  With gscale = grad_scale * clip_coef, per range r
+ *     step_r = (lr_r * lr_factor) * d          (lr_factor under AVMOE_OPT_LR_SCHEDULE)
+ *     c_r    = step_r * (d / d0)               (safeguard_warmup: c_r = d * (d / d0))
+ * and per element, every operation rounded to fp32 in the order written (csrc/adam_elem.h: prodigy_elem; contraction off):
+ *     coupled decay:              gr = fma(gscale, grad, wd * p)
+ *     AVMOE_OPT_DECOUPLED_DECAY:  gr = grad * gscale ;  p <- p * (1 - step_r * wd) before the Adam term
+ *     dg = d * gr ;  cg = c_r * gr
+ *     m  = fma(b1, m, (1 - b1) * dg) ;  v = fma(b2, v, ((1 - b2) * dg) * dg) ;  s = fma(beta3, s, cg)
+ *     p  = p - (step_r * m) / (sqrt(v) + d * eps)
+ * and, in double, per 1024-element table block:  sum of (double)cg * ((double)x0 - (double)p) with p BEFORE the step (with hold != NULL
+ * the held value), and sum of (double)|s| with the new s.  There is no bias correction, as in the paper.  With d == 1 the moments are
+ * the bits avmoe_opt_adam_step forms from the same gradient.
+ * Underflow: (d * gr)^2 may underflow fp32 (a small d0 times a small gradient); v then holds what gradual underflow leaves, possibly 0.
+ * Where sqrt(v) + d * eps is not > 0 (v == 0 with d * eps == 0, or a NaN) the quotient is not formed and the element's Adam term is
+ * dropped: p keeps its (decayed) value while m, v, s and the sums advance.
+ * Then ONE block adds the block sums in a fixed order (thread t blocks t, t + 256, ..., then a tree; no floating-point atomics) and
+ * writes the block, in double unless stated:
+ *     num   = beta3 * num + sum_dot ;  den = sum_abs
+ *     d_hat = fp32(d_coef * num / den)         left as it is when den is not > 0, or num, den or the quotient is not a finite fp32
+ *     d_max = max(d_max, d_hat)
+ *     d     = min(d_max, fp32(d * growth))     growth == 0: d = d_max
+ * so d never falls; the update of step k uses d_k, and step k + 1 reads d_{k+1}.
+ * avmoe_opt_prodigy_step is TWO launches on `stream` whatever the number of ranges (kk_opt_prodigy_update<DECOUPLED, SCHED, EMA, HOLD>,
+ * kk_opt_prodigy_finalize), without a host synchronisation and without a host scalar that changes from step to step, so it replays
+ * from a captured graph.  `workspace` (DEVICE, 8-byte aligned) takes two doubles per table block and needs no initialisation;
+ * avmoe_opt_prodigy_bytes returns its size and the block's (each a multiple of 16; 0 and an error string on a negative count or more
+ * than 2^31 - 1 blocks) and their sum.
+ * When state->skip is set nothing is written: d, num, den, s, x0, moments, parameters and the workspace keep their values -- with
+ * hold != NULL param = hold and nothing else.  Gradients and x0 are only read; alignment padding belongs to no range and is not touched.
+ * A launch that does not match its table's header touches nothing but the workspace; a range whose shadow / hold / x0 / s entry is not
+ * 16-byte aligned, or pointer arrays made for another range count, are left out likewise (their block sums count as 0).
+ * `flags` are those of avmoe_opt_adam_step_ema; `shadows` may be NULL without AVMOE_OPT_EMA; hold == NULL is the step without a
+ * perturbation before it.
+ * Errors (before any launch): everything avmoe_opt_adam_step_sam refuses (hold != NULL) or avmoe_opt_adam_step_ema refuses (hold == NULL);
+ * AVMOE_ERR_BAD_ARG for NULL x0, s, consts, block or workspace, for a d0 or d_coef that is not a finite number > 0 (NaN included), a
+ * growth that is neither 0 nor a finite number >= 1, a safeguard_warmup that is neither 0 nor 1; AVMOE_ERR_ALIGNMENT for pointer arrays
+ * or a workspace that are not 8-byte or a block that is not 16-byte aligned.                                                          */
+typedef struct avmoe_opt_prodigy_state {
+  float d;                    /* the estimate the NEXT applied step uses */
+  float d_max;                /* the largest d_hat so far (at least d0) */
+  float d_hat;                /* the last estimate, which may be below d or negative */
+  int32_t reserved;
+  double num;                 /* the decayed sum of <c g, x0 - x> */
+  double den;                 /* sum of |s| at the last applied step */
+} avmoe_opt_prodigy_state;
+
+typedef struct avmoe_opt_prodigy {
+  float d0;                   /* > 0 */
+  float d_coef;               /* > 0 */
+  float growth;               /* >= 1: d grows by at most this factor per step; 0: no limit */
+  int32_t safeguard_warmup;   /* 1: the weight of a step in s and num leaves the learning rate out (for use with a warm-up) */
+} avmoe_opt_prodigy;
+
+typedef struct avmoe_opt_prodigy_layout { size_t workspace_bytes, block_bytes; } avmoe_opt_prodigy_layout;
+
+size_t avmoe_opt_prodigy_bytes(int64_t n_blocks, avmoe_opt_prodigy_layout* layout /* HOST, or NULL */);
+int avmoe_opt_prodigy_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                           float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
+                           float* const* hold /* DEVICE, or NULL */, float* const* x0 /* DEVICE */, float* const* s /* DEVICE */,
+                           const avmoe_opt_prodigy* consts /* HOST */, avmoe_opt_prodigy_state* block /* DEVICE, 16-byte aligned */,
+                           double* workspace /* DEVICE */);
+
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the
  * tiled engine is faster.  force_mask lifts those thresholds so that a test can run the benchmarked kernels on shapes its oracle

@@ -29,6 +29,9 @@
 --lamb             (device mode) FlatAdam(trust_ratio=True, trust_clip=10.0): layer-wise trust ratios -- three launches (moments and block
                    sums, a wave per parameter for norms and ratio, the update) in place of the one update launch: 5 per step.
                    Combines with --schedule, --ema, --swa, --report, --sam
+--prodigy          (device mode) FlatAdam(lr=1.0, prodigy=True): Prodigy learning-rate estimation -- two launches (the update with both block
+                   sums, a one-block finalize that writes d) in place of the one update launch: 4 per step.  The alternative to --lamb;
+                   combines with --schedule, --ema, --swa, --report, --sam
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
@@ -80,6 +83,7 @@ def main():
     ap.add_argument("--sam-foreach", action="store_true")
     ap.add_argument("--per-step-events", action="store_true")
     ap.add_argument("--lamb", action="store_true")
+    ap.add_argument("--prodigy", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -107,6 +111,8 @@ def main():
         ap.error("--adaptive goes with --sam")
     if a.lamb and a.mode != "device":
         ap.error("--lamb goes with --mode device")
+    if a.prodigy and (a.mode != "device" or a.lamb):
+        ap.error("--prodigy goes with --mode device and is the alternative to --lamb")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
@@ -138,7 +144,9 @@ def main():
         kw.update(trust_ratio=True, trust_clip=10.0)
     buffers = [b for _, b in model.named_buffers() if b.dtype == torch.float32 and b.numel() > 0]
     buffer_shadows = [b.detach().clone() for b in buffers] if a.ema_buffers_foreach else None
-    opt = FlatAdam(red, lr=1e-3, weight_decay=1e-2, **kw)
+    if a.prodigy:
+        kw.update(prodigy=True)
+    opt = FlatAdam(red, lr=1.0 if a.prodigy else 1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
     base_lr = [e[3] for e in opt._plist]
@@ -236,6 +244,9 @@ def main():
         extra["lamb"] = "device"
         extra["adapted"], extra["ratio_min"], extra["ratio_max"] = sum(opt.adapted), float(r.min().item()), float(r.max().item())
         extra["ratios_not_one"] = int((r != 1.0).sum().item())
+    if a.prodigy:
+        extra["prodigy"] = "device"
+        extra["d0"], extra["d"], extra["d_hat"] = opt.prodigy_d0, float(opt.prodigy_d.item()), float(opt.prodigy_d_hat.item())
     if a.report:
         extra["report"] = "device"
         extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())

@@ -1,0 +1,441 @@
+"""Prodigy learning-rate estimation in FlatAdam on the device (avmoe_amd.train.FlatAdam(prodigy=True, ...); include/avmoe.h:
+avmoe_opt_prodigy_step) on two buckets of plain parameters, the smallest that reach every path of the two kernels (a block serves 1024
+elements, a thread four):
+    1, 3, 4, 5, 1023, 1024, 1025 and 2049 elements -- the ranges of 1 and 3 elements are served by the scalar tail alone, 1025 and 2049
+    end in a block of one element, 2049 has three blocks and a bucket of its own.
+Every rate is a multiplier of d: lr = 1, and 0.5 for a group of three.  The gradients of a run are one seeded direction per parameter
+plus noise of 0.3 of its size, so that consecutive gradients agree and d rises within the six steps (tests/prodigy_ref.py's fp32
+emulation of the same run says so before a device is asked).
+
+The fp64 bounds and the rounding count they come from are tests/prodigy_ref.py's.  Everything that is the same kernels on the same bits
+is held to bit-equality.  AVMOE_PRODIGY_MARGINS=<file> appends the worst observed fraction of each bound, and the behaviour test's
+figures, to that file."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import prodigy_ref as ref
+from tests.test_flat_adam_ema_gpu import assert_flats_equal, bits, flats, padding_mask, set_grads
+from tests.test_flat_adam_swa_gpu import poison
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = ((3, 683), (1,), (3,), (2, 2), (5,), (3, 341), (32, 32), (25, 41))
+LR, LR_X, WD, RHO = 1.0, 0.5, 1e-2, 0.05
+STEPS = 6
+MAX_NORM = 20.0                                  # gradients over 5134 elements, about 1.04 each: norm about 75, so every step clips
+BUCKET_MB = 4 * 3300 / (1 << 20)                 # the seven small ones (3085 elements and their alignment padding) fill the first bucket
+POISONED = 3                                     # the step of the "clip_skip" and "sam" runs whose gradient carries an Inf
+_GRADS = {}
+
+
+def make_params(dev, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return [torch.nn.Parameter(torch.randn(s, generator=g).to(dev)) for s in SHAPES]
+
+
+def clone_params(params):
+    return [torch.nn.Parameter(p.detach().clone()) for p in params]
+
+
+def warmup():
+    from avmoe_amd.train import LRSchedule
+    return LRSchedule(warmup_steps=4, warmup_start=0.5)
+
+
+def make_opt(params, **kw):
+    from avmoe_amd.dp import AdapterGradReducer
+    from avmoe_amd.train import FlatAdam
+    red = AdapterGradReducer(params, bucket_mb=BUCKET_MB)
+    assert len(red.buckets) == 2 and sorted(p.numel() for b in red.buckets for p in b.params) == sorted(int(np.prod(s)) for s in SHAPES)
+    kw.setdefault("lr", LR)
+    kw.setdefault("prodigy", True)
+    return red, FlatAdam(red, param_groups=[{"params": params[1:4], "lr": LR_X}], **kw)
+
+
+def host_grads(seed=5, steps=STEPS):
+    """`steps` seeded gradient sets, drawn once per seed on the host and shared: a direction per parameter plus noise"""
+    if (seed, steps) not in _GRADS:
+        g = torch.Generator().manual_seed(seed)
+        base = [torch.randn(s, generator=g) for s in SHAPES]
+        _GRADS[(seed, steps)] = [[b + 0.3 * torch.randn(s, generator=g) for b, s in zip(base, SHAPES)] for _ in range(steps)]
+    return _GRADS[(seed, steps)]
+
+
+def grads(dev, seed=5, steps=STEPS):
+    return [[t.to(dev) for t in step] for step in host_grads(seed, steps)]
+
+
+OPTION_SETS = {
+    "plain": dict(weight_decay=WD),
+    "clip_skip": dict(weight_decay=WD, max_grad_norm=MAX_NORM, skip_nonfinite=True),
+    "decoupled": dict(weight_decay=WD, decoupled_weight_decay=True, prodigy_growth=4.0, prodigy_d_coef=2.0),
+    "schedule": dict(weight_decay=WD, lr_schedule="warmup", prodigy_safeguard_warmup=True, prodigy_d0=1e-5),
+    "ema": dict(weight_decay=WD, ema_decay=0.9),
+    "sam": dict(weight_decay=WD, sam_rho=RHO, skip_nonfinite=True),
+}
+
+
+def settings(name):
+    kw = dict(OPTION_SETS[name])
+    if kw.get("lr_schedule") == "warmup":
+        kw["lr_schedule"] = warmup()
+    return kw
+
+
+def block_of(opt):
+    return {k: v.item() for k, v in opt.prodigy_block.items()}
+
+
+def block_bits(opt):
+    return opt._prodigy_block.clone()
+
+
+def snapshot(opt):
+    """every range's arrays as the device holds them now, in table order, and the Prodigy block"""
+    ranges = []
+    for (p, si, off, lr0), wd in zip(opt._plist, opt._wds):
+        s, n = opt.state[si], p.numel()
+        r = {k: s[k][off:off + n].cpu().numpy().copy() for k in ("p", "g", "m", "v", "s", "x0") + (("e",) if "e" in s else ())}
+        r["lr"], r["wd"] = lr0 * opt.decay, wd
+        ranges.append(r)
+    return {"ranges": ranges, "block": block_of(opt)}
+
+
+def sums_of(opt):
+    return opt._prodigy_ws.view(torch.float64)[:2 * opt._n_blocks].cpu().numpy().reshape(-1, 2).copy()
+
+
+def step(opt, params, g2, g1=None, bad=False):
+    """one step; -> the operands as stored before it (behind a perturbation: the held weights, taken before it)"""
+    held = None
+    if g1 is not None:
+        set_grads(params, g1)
+        held = snapshot(opt)
+        opt.sam_perturb()
+    set_grads(params, g2)
+    if bad:
+        poison(params[6])
+    before = snapshot(opt)
+    if held is not None:
+        for r, h in zip(before["ranges"], held["ranges"]):
+            r["p"] = h["p"]
+    opt.step()
+    return before
+
+
+def consts_of(opt, before, name):
+    sb = {k: v.item() for k, v in opt.state_block.items()}
+    kw = OPTION_SETS[name]
+    return ref.consts(d=before["block"]["d"], d0=opt.prodigy_d0, b1=opt.betas[0], b2=opt.betas[1], eps=opt.eps,
+                      gscale=ref.f32(np.float32(opt.grad_scale) * np.float32(sb["clip_coef"])),
+                      lr_factor=sb["lr_factor"] if "lr_schedule" in kw else 1.0, decoupled=opt.decoupled_weight_decay,
+                      safeguard=opt.prodigy_safeguard_warmup, d_coef=opt.prodigy_d_coef, growth=opt.prodigy_growth, skip=bool(sb["skip"]),
+                      ema_decay=sb["ema_decay"] if "ema_decay" in kw else None)
+
+
+def record(line):
+    print(line)
+    path = os.environ.get("AVMOE_PRODIGY_MARGINS")
+    if path:
+        with open(path, "a") as fh:
+            fh.write(line + "\n")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(OPTION_SETS))
+def test_every_step_against_fp64_from_the_operands_stored_before_it(name):
+    """tests/prodigy_ref.py's check_step after each of the six steps: every element of m, v, s, p (and the shadow), both sums of every
+    block, num, den, d_hat, d_max and d; alignment padding of every flat buffer keeps its bits; d rises"""
+    dev = torch.device("cuda:0")
+    a = make_params(dev)
+    red, opt = make_opt(a, **settings(name))
+    assert opt.prodigy is True and len(opt.params) == len(SHAPES) and opt._n_blocks == 11
+    assert all(torch.equal(x, p.data) for x, p in zip(opt.prodigy_x0, opt.params)) and all(not s.any() for s in opt.prodigy_s)
+    assert float(opt.prodigy_d.item()) == opt.prodigy_d0 and opt.prodigy_d.is_cuda and opt.prodigy_d.dtype == torch.float32
+    g2s, g1s = grads(dev, seed=5), grads(dev, seed=6)
+    pads = [padding_mask(b, dev) for b in red.buckets]
+    keys = [k for k in ("p", "m", "v", "s", "x0", "e", "h") if k in opt.state[0]]
+    pad_before = [[s[k][pad].clone() for k in keys] for s, pad in zip(opt.state, pads)]
+    worst, ds, skipped = {}, [opt.prodigy_d0], 0
+    for k in range(STEPS):
+        bad = k == POISONED and name in ("clip_skip", "sam")
+        before = step(opt, a, g2s[k], g1s[k] if name == "sam" else None, bad)
+        torch.cuda.synchronize()
+        K = consts_of(opt, before, name)
+        assert K.skip == bad
+        skipped += int(bad)
+        after = snapshot(opt)
+        after["sums"] = None if K.skip else sums_of(opt)
+        used = ref.check_step(before, after, K)
+        for key, val in used.items():
+            worst[key] = max(worst.get(key, 0.0), val)
+        ds.append(after["block"]["d"])
+        assert float(opt.prodigy_d.item()) == after["block"]["d"] and float(opt.prodigy_d_hat.item()) == after["block"]["d_hat"]
+        if not K.skip:                                        # the host's copy of the finalize rule, from the device's own sums: the same bits
+            host = type(opt).prodigy_d_next(before["block"]["d"], before["block"]["d_max"], before["block"]["d_hat"], before["block"]["num"],
+                                            after["block"]["num"] - K.beta3 * before["block"]["num"], after["block"]["den"], opt.betas[1],
+                                            opt.prodigy_d_coef, opt.prodigy_growth)
+            assert abs(host["d"] - after["block"]["d"]) <= 4 * ref.U * after["block"]["d"], (host, after["block"])
+    for s, pad, old in zip(opt.state, pads, pad_before):
+        assert int(pad.sum()) > 0
+        for key, o in zip(keys, old):
+            assert torch.equal(bits(s[key][pad]), bits(o)), ("alignment padding", key)
+    assert int(opt.applied_steps.item()) == STEPS - skipped and int(opt.skipped_steps.item()) == skipped
+    assert all(y >= x for x, y in zip(ds, ds[1:])) and ds[1] == ds[0] and ds[-1] > 2 * ds[0], ds      # step 0 has x = x0: d stays d0
+    record(f"{name}: " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()) + f", d {ds[0]:.3g} -> {ds[-1]:.3g}")
+
+
+def test_where_the_second_moment_underflows_the_adam_term_is_dropped():
+    """gradients of 1e-30 at d = 1e-6: (d g)^2 is 0 in fp32, and with eps = 0 so is the denominator.  The header's rule: no quotient is
+    formed, p keeps its bits, m and s advance -- and the fp64 reference, which applies the same rule, agrees within its bounds"""
+    dev = torch.device("cuda:0")
+    a = make_params(dev)
+    _, opt = make_opt(a, eps=0.0)
+    before = step(opt, a, [torch.full_like(p, 1e-30) for p in a])
+    torch.cuda.synchronize()
+    K = consts_of(opt, before, "plain")
+    after = snapshot(opt)
+    after["sums"] = sums_of(opt)
+    ref.check_step(before, after, K)
+    for b, r in zip(before["ranges"], after["ranges"]):
+        assert np.array_equal(b["p"].view(np.int32), r["p"].view(np.int32)) and not r["v"].any()
+        assert (r["m"] > 0).all() and (r["s"] > 0).all() and np.isfinite(r["p"]).all()
+    assert int(opt.applied_steps.item()) == 1 and float(opt.prodigy_d.item()) == opt.prodigy_d0
+
+
+def raw_step(opt):
+    """one step of an optimizer built WITHOUT the option through the entry points it has always used"""
+    from avmoe_amd import _capi as capi
+    from avmoe_amd import _capi_moe as cm
+    L, n = capi.lib(), len(opt.params)
+    stream = torch.cuda.current_stream().cuda_stream
+    capi.check(L.avmoe_opt_grad_norm_report(opt._table_ptr, n, opt._n_blocks, opt._partials_ptr, opt._state_ptr, opt.grad_scale,
+                                            opt.max_grad_norm or 0.0, opt._flags, opt.betas[0], opt.betas[1], stream, None, None, None),
+               "avmoe_opt_grad_norm_report")
+    capi.check(L.avmoe_opt_adam_step_ema(opt._table_ptr, n, opt._n_blocks, opt._state_ptr, opt.betas[0], opt.betas[1], opt.eps, opt.grad_scale,
+                                         opt._flags & ~cm.OPT_REPORT, stream, None), "avmoe_opt_adam_step_ema")
+
+
+def test_with_the_option_off_the_step_is_the_one_it_was():
+    """prodigy=False: no x0, no s, no block, and step() gives the bits of the entry points it has always called"""
+    from avmoe_amd import _capi as capi
+    dev = torch.device("cuda:0")
+    kw = dict(prodigy=False, lr=3e-3, weight_decay=WD, max_grad_norm=MAX_NORM, skip_nonfinite=True)
+    a = make_params(dev)
+    b = clone_params(a)
+    _, oa = make_opt(a, **kw)
+    _, ob = make_opt(b, **kw)
+    assert oa.prodigy is False and not any(k in s for s in oa.state for k in ("x0", "s")) and not hasattr(oa, "_prodigy_block")
+    gs = grads(dev)
+    for k in range(3):
+        set_grads(a, gs[k]); set_grads(b, gs[k])
+        oa.step(); raw_step(ob)
+        assert_flats_equal(flats(oa, "pmv"), flats(ob, "pmv"), k, "pmv")
+    assert not any(k.startswith("prodigy") for k in oa.state_dict()["flat_adam"])
+    for what in (lambda: oa.prodigy_d, lambda: oa.prodigy_d_hat, lambda: oa.prodigy_x0, lambda: oa.prodigy_s):
+        with pytest.raises(capi.AvmoeError, match="prodigy"):
+            what()
+
+
+def test_with_d_frozen_at_one_the_moments_are_adams():
+    """d0 = 1 and growth = 1: d stays exactly 1, d * gr == gr, and m and v get the bits adam_elem's expressions give -- with decoupled
+    decay they do not depend on p, so they are bit-equal to a FlatAdam's without the option after every one of 4 steps"""
+    dev = torch.device("cuda:0")
+    kw = dict(lr=3e-3, weight_decay=WD, decoupled_weight_decay=True, max_grad_norm=MAX_NORM)
+    a = make_params(dev)
+    b = clone_params(a)
+    _, oa = make_opt(a, prodigy_d0=1.0, prodigy_growth=1.0, **kw)
+    _, ob = make_opt(b, prodigy=False, **kw)
+    gs = grads(dev)
+    for k in range(4):
+        set_grads(a, gs[k]); set_grads(b, gs[k])
+        oa.step(); ob.step()
+        assert_flats_equal(flats(oa, "mv"), flats(ob, "mv"), k, "mv")
+        assert float(oa.prodigy_d.item()) == 1.0
+        assert torch.equal(bits(oa.last_grad_norm), bits(ob.last_grad_norm))
+    assert float(oa.prodigy_d_hat.item()) != 0.0
+    assert any(not torch.equal(x["p"], y["p"]) for x, y in zip(oa.state, ob.state))      # no bias correction: another update
+
+
+@pytest.mark.parametrize("sam", [False, True], ids=["plain", "sam"])
+def test_a_poisoned_gradient_changes_no_bit(sam):
+    dev = torch.device("cuda:0")
+    a = make_params(dev)
+    _, opt = make_opt(a, weight_decay=WD, max_grad_norm=MAX_NORM, skip_nonfinite=True, ema_decay=0.9, **(dict(sam_rho=RHO) if sam else {}))
+    g2s, g1s = grads(dev, seed=5), grads(dev, seed=6)
+    for k in range(3):
+        step(opt, a, g2s[k], g1s[k] if sam else None)
+    assert float(opt.prodigy_d.item()) > opt.prodigy_d0
+    names = ("p", "m", "v", "s", "e", "x0")
+    before, blk, ws = [tuple(s[k].clone() for k in names) for s in opt.state], block_bits(opt), opt._prodigy_ws.clone()
+    step(opt, a, g2s[3], g1s[3] if sam else None, bad=True)
+    after = [tuple(s[k].clone() for k in names) for s in opt.state]
+    assert_flats_equal(before, after, "skipped step", names)      # under SAM: the held weights came back
+    assert torch.equal(blk, block_bits(opt)) and torch.equal(ws, opt._prodigy_ws) and not opt.perturbed
+    assert int(opt.skipped_steps.item()) == 1 and int(opt.applied_steps.item()) == 3 and int(opt.state_block["skip"].item()) == 1
+    step(opt, a, g2s[4], g1s[4] if sam else None)             # and the run goes on
+    assert int(opt.applied_steps.item()) == 4 and not torch.equal(blk, block_bits(opt))
+
+
+def test_two_identical_runs_agree_bit_for_bit():
+    """fixed-order sums, no floating-point atomics"""
+    dev = torch.device("cuda:0")
+    kw = dict(weight_decay=WD, max_grad_norm=MAX_NORM, ema_decay=0.9, lr_schedule=warmup())
+    a = make_params(dev)
+    b = clone_params(a)
+    _, oa = make_opt(a, **kw)
+    _, ob = make_opt(b, **kw)
+    gs = grads(dev)
+    for k in range(STEPS):
+        step(oa, a, gs[k]); step(ob, b, gs[k])
+        assert torch.equal(block_bits(oa), block_bits(ob)) and torch.equal(oa._prodigy_ws, ob._prodigy_ws), k
+    assert_flats_equal(flats(oa, "pmvse"), flats(ob, "pmvse"), "second run", "pmvse")
+    assert float(oa.prodigy_d.item()) > oa.prodigy_d0
+
+
+def test_a_captured_step_replays_bit_equal_to_the_eager_run():
+    dev = torch.device("cuda:0")
+    kw = dict(weight_decay=WD, decoupled_weight_decay=True, max_grad_norm=MAX_NORM, skip_nonfinite=True, ema_decay=0.9, lr_schedule=warmup(),
+              prodigy_safeguard_warmup=True)
+    a = make_params(dev)
+    b = clone_params(a)
+    _, oa = make_opt(a, **kw)
+    _, ob = make_opt(b, **kw)
+    gs = grads(dev)
+    start = flats(ob, "pmvse")
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    eager = []
+    with torch.cuda.stream(st):                              # the eager run (it also loads the kernels before the capture)
+        for k in range(STEPS):
+            step(oa, a, gs[k])
+            eager.append(block_bits(oa))
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=st):
+        ob.step()
+    torch.cuda.synchronize()
+    assert int(ob.applied_steps.item()) == 0 and float(ob.prodigy_d.item()) == ob.prodigy_d0      # capturing runs nothing
+    assert_flats_equal(start, flats(ob, "pmvse"), "capture", "pmvse")
+    for k in range(STEPS):
+        set_grads(b, gs[k])
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(block_bits(ob), eager[k]), k
+    assert int(ob.applied_steps.item()) == STEPS
+    assert_flats_equal(flats(oa, "pmvse"), flats(ob, "pmvse"), "graph replay", "pmvse")
+    assert len({tuple(e.tolist()) for e in eager}) >= STEPS - 1 and float(ob.prodigy_d.item()) > ob.prodigy_d0      # d changed from replay to replay
+
+
+def test_resume_continues_bit_equal():
+    from avmoe_amd.train import FlatAdam
+    dev = torch.device("cuda:0")
+    kw = dict(weight_decay=WD, decoupled_weight_decay=True, max_grad_norm=MAX_NORM, ema_decay=0.9, prodigy_growth=4.0)
+    a = make_params(dev)
+    b = clone_params(a)
+    _, oa = make_opt(a, **kw)
+    _, ob = make_opt(b, **kw)
+    gs = grads(dev)
+    for k in range(3):
+        step(oa, a, gs[k]); step(ob, b, gs[k])
+    sd = ob.state_dict()
+    extra = sd["flat_adam"]
+    assert extra["prodigy"] is True and extra["prodigy_growth"] == 4.0 and extra["prodigy_d"] == float(ob.prodigy_d.item()) > ob.prodigy_d0
+    assert len(extra["prodigy_x0"]) == len(extra["prodigy_s"]) == len(SHAPES) and extra["prodigy_num"] != 0.0
+    c = clone_params(b)                                      # the model as saved; the optimizer built with OTHER constants: the saved ones win
+    _, oc = make_opt(c, **dict(kw, prodigy_growth=None, prodigy_d0=1e-3))
+    assert not torch.equal(oc.prodigy_x0[0], ob.prodigy_x0[0])      # built from the trained weights: x0 is not the run's
+    oc.load_state_dict(copy.deepcopy(sd))
+    assert oc.prodigy_growth == 4.0 and oc.prodigy_d0 == ob.prodigy_d0 and torch.equal(block_bits(oc), block_bits(ob))
+    for k in range(3, STEPS):
+        step(oa, a, gs[k]); step(oc, c, gs[k])
+        assert torch.equal(block_bits(oa), block_bits(oc)), k
+    assert_flats_equal(flats(oa, "pmvse"), flats(oc, "pmvse"), "resumed run", "pmvse")
+    assert all(torch.equal(x, y) for x, y in zip(oa.prodigy_x0, oc.prodigy_x0))
+    # a dict without the keys re-seeds: x0 = the current parameters, s = 0, d = d0
+    bare = copy.deepcopy(sd)
+    for key in [k for k in bare["flat_adam"] if k.startswith("prodigy")]:
+        del bare["flat_adam"][key]
+    d = clone_params(b)
+    _, od = make_opt(d, **kw)
+    od.state[0]["s"].fill_(1.0)
+    od.load_state_dict(bare)
+    assert float(od.prodigy_d.item()) == od.prodigy_d0 and int(od.applied_steps.item()) == 3
+    assert all(torch.equal(x, p.data) for x, p in zip(od.prodigy_x0, od.params)) and all(not s.any() for s in od.prodigy_s)
+    # and a dict saved with the option does not load into an optimizer built without it
+    _, oe = make_opt(clone_params(b), **dict(kw, prodigy=False, prodigy_growth=None))
+    with pytest.raises(ValueError, match="prodigy"):
+        oe.load_state_dict(copy.deepcopy(sd))
+    assert isinstance(FlatAdam.prodigy_d_next(1.0, 1.0, 0.0, 0.0, 1.0, 2.0, 0.999), dict)
+
+
+def test_a_launch_that_does_not_match_touches_nothing():
+    """a table whose header is not this launch's (wrong magic) leaves parameters, moments, s, averages and the Prodigy block bit for bit;
+    an x0 entry that cannot take 16-byte accesses leaves that range out, and its blocks count as 0 in both sums"""
+    from avmoe_amd import _capi as capi
+    from avmoe_amd import _capi_moe as cm
+    dev = torch.device("cuda:0")
+    a = make_params(dev)
+    _, opt = make_opt(a, weight_decay=WD, max_grad_norm=MAX_NORM, ema_decay=0.9)
+    gs = grads(dev)
+    step(opt, a, gs[0]); step(opt, a, gs[1])
+    before, blk = flats(opt, "pmvse"), block_bits(opt)
+    set_grads(a, gs[2])
+    magic = opt._ws[cm.OPT_STATE_BYTES:cm.OPT_STATE_BYTES + 4].clone()
+    opt._ws[cm.OPT_STATE_BYTES:cm.OPT_STATE_BYTES + 4] = 0
+    opt.step()                                                # finalize still counts the step; the table's kernels refuse
+    opt._ws[cm.OPT_STATE_BYTES:cm.OPT_STATE_BYTES + 4] = magic
+    assert_flats_equal(before, flats(opt, "pmvse"), "stale table", "pmvse")
+    assert torch.equal(blk, block_bits(opt))
+    L, n = capi.lib(), len(opt.params)
+    bent = opt._prodigy_x0_ptrs.clone()
+    victim = max(range(n), key=lambda i: opt.params[i].numel())          # the three-block range, a bucket of its own
+    bent[victim] += 4
+    capi.check(L.avmoe_opt_prodigy_step(opt._table_ptr, n, opt._n_blocks, opt._state_ptr, opt.betas[0], opt.betas[1], opt.eps, 1.0,
+                                        cm.OPT_CLIP | cm.OPT_EMA, torch.cuda.current_stream().cuda_stream, opt._shadow_ptrs.data_ptr(), None,
+                                        bent.data_ptr(), opt._prodigy_s_ptrs.data_ptr(), cm.C.byref(opt._prodigy_c),
+                                        opt._prodigy_block.data_ptr(), opt._prodigy_ws.data_ptr()), "avmoe_opt_prodigy_step")
+    torch.cuda.synchronize()
+    p, si, off, _lr0 = opt._plist[victim]
+    for k, old in zip("pmvse", before[si]):
+        assert torch.equal(bits(old[off:off + p.numel()]), bits(opt.state[si][k][off:off + p.numel()])), ("the range with the bent x0 entry", k)
+    assert not torch.equal(before[1 - si][0], opt.state[1 - si]["p"])    # the other ranges took their step
+    sums = sums_of(opt)
+    first = sum((q.numel() + 1023) // 1024 for q, _si, _off, _lr in opt._plist[:victim])
+    assert not sums[first:first + 3].any() and sums[:first, 1].all() and not torch.equal(blk, block_bits(opt))
+
+
+def test_d_rises_and_the_loss_falls_as_in_the_fp64_run():
+    """least squares, 48 x 12, full-batch gradients, T = 150 steps at lr = 1: d at step T within a factor of 2 of the fp64 reference's own
+    run of the same problem and the loss ratio at most twice its (fp32 trajectories of an adaptive rule drift from fp64 over hundreds
+    of steps: the factor is the issue's)"""
+    from avmoe_amd.dp import AdapterGradReducer
+    from avmoe_amd.train import FlatAdam
+    dev, T = torch.device("cuda:0"), 150
+    rng = np.random.default_rng(2)
+    A = rng.standard_normal((48, 12)).astype(np.float32)
+    y = (A.astype(np.float64) @ rng.standard_normal(12) + 0.05 * rng.standard_normal(48)).astype(np.float32)
+    A64, y64 = A.astype(np.float64), y.astype(np.float64)
+    loss64 = lambda w: 0.5 * float(np.mean((A64 @ w - y64) ** 2))
+    host = ref.Prodigy64([np.zeros(12)], lr=1.0, betas=(0.9, 0.999), eps=1e-8)
+    for _ in range(T):
+        host.step([A64.T @ (A64 @ host.p[0] - y64) / 48])
+    want_d, want_ratio = host.d, loss64(host.p[0]) / loss64(np.zeros(12))
+    assert want_d > 1e3 * host.d0 and want_ratio < 0.1        # the reference itself: d rose and the loss fell
+    w = torch.nn.Parameter(torch.zeros(12, device=dev))
+    At, yt = torch.from_numpy(A).to(dev), torch.from_numpy(y).to(dev)
+    red = AdapterGradReducer([w], bucket_mb=1.0)
+    opt = FlatAdam(red, lr=1.0, prodigy=True)
+    with torch.no_grad():
+        for _ in range(T):
+            w.grad.copy_(At.t() @ (At @ w - yt) / 48)
+            opt.step()
+    d, ratio = float(opt.prodigy_d.item()), loss64(w.detach().double().cpu().numpy()) / loss64(np.zeros(12))
+    record(f"behaviour: d {d:.6g} (fp64 {want_d:.6g}), loss ratio {ratio:.6g} (fp64 {want_ratio:.6g})")
+    assert d > opt.prodigy_d0 and want_d / 2 <= d <= 2 * want_d, (d, want_d)
+    assert ratio < 1.0 and ratio <= 2 * want_ratio, (ratio, want_ratio)
