@@ -90,6 +90,21 @@ class OptProdigyLayout(C.Structure):
     _fields_ = [("workspace_bytes", C.c_size_t), ("block_bytes", C.c_size_t)]
 
 
+class OptMuonMat(C.Structure):
+    """avmoe_opt_muon_mat: one orthogonalised matrix: the range it is, read as row-major rows x cols"""
+    _fields_ = [("range", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OptMuon(C.Structure):
+    """avmoe_opt_muon: the host constants of orthogonalised momentum (scale: 0 match_rms_adamw, 1 original)"""
+    _fields_ = [("momentum", C.c_float), ("nesterov", C.c_int32), ("ns_steps", C.c_int32), ("scale", C.c_int32)]
+
+
+class OptMuonLayout(C.Structure):
+    """avmoe_opt_muon_layout: the bytes of the matrix image, avmoe_opt_muon_step's workspace and its report"""
+    _fields_ = [("table_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t), ("report_bytes", C.c_size_t)]
+
+
 # avmoe_opt_prodigy_state: field -> (byte offset, torch dtype name); 32 bytes
 OPT_PRODIGY_FIELDS = {"d": (0, "float32"), "d_max": (4, "float32"), "d_hat": (8, "float32"), "num": (16, "float64"), "den": (24, "float64")}
 
@@ -231,6 +246,16 @@ def declare(L):
             L.avmoe_opt_prodigy_step.restype = C.c_int
             # shadows, hold, x0, s, consts (HOST), block, workspace
             L.avmoe_opt_prodigy_step.argtypes = step_args + [C.c_void_p] * 4 + [C.POINTER(OptProdigy), C.c_void_p, C.c_void_p]
+        if hasattr(L, "avmoe_opt_muon_step"):         # (found by symbol: orthogonalised momentum)
+            L.avmoe_opt_muon_bytes.restype = C.c_size_t
+            L.avmoe_opt_muon_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(OptMuonLayout)]
+            L.avmoe_opt_muon_table_build.restype = C.c_int
+            L.avmoe_opt_muon_table_build.argtypes = [C.POINTER(OptRange), C.c_int32, C.POINTER(OptMuonMat), C.c_int32, C.c_void_p, C.c_size_t]
+            L.avmoe_opt_muon_step.restype = C.c_int
+            # shadows, hold, mats (the DEVICE image), n_mats, work, consts (HOST), workspace, report
+            L.avmoe_opt_muon_step.argtypes = step_args + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.POINTER(OptMuon), C.c_void_p, C.c_void_p]
+            L.avmoe_opt_muon_ns.restype = C.c_int
+            L.avmoe_opt_muon_ns.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

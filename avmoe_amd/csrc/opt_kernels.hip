@@ -53,6 +53,7 @@
 #include "../../include/avmoe.h"
 #include "common.h"
 #include "adam_elem.h"
+#include "opt_table.h"
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -60,48 +61,6 @@
 #include <cstring>
 
 namespace avmoe {
-
-constexpr int OPT_BLOCK = 1024;                  // elements per block: 256 threads x 4, as kk_adam
-constexpr uint32_t OPT_MAGIC = 0x4f50544du;      // "OPTM"
-
-// the table image: header, the ranges, then one (range, block inside the range) pair per 1024-element block
-struct OptHeader { uint32_t magic; int32_t n_ranges; int64_t n_blocks; };
-struct OptBlock { int32_t range, block; };
-static_assert(sizeof(OptHeader) == 16 && sizeof(avmoe_opt_range) == 48 && sizeof(avmoe_opt_state) == 64, "table / state layout");
-static_assert(sizeof(avmoe_opt_report_header) == 16, "report layout");
-static_assert(sizeof(avmoe_opt_sam_state) == 16, "SAM block layout");
-static_assert(sizeof(avmoe_opt_swa) == 32 && sizeof(avmoe_opt_schedule) == 40 && sizeof(avmoe_opt_ema) == 8, "constants of a run");
-
-// What a thread of a one-block-per-table-block launch serves: elements [i0, min(i0 + 4, r.n)) of range `range`.
-struct OptWork { int32_t n_ranges, range; avmoe_opt_range r; long i0; };
-
-// -> false where the thread has nothing to touch: a launch whose grid does not match the table (a stale or foreign image: wrong magic, a
-// block past n_blocks, a range index outside the table), or a thread past the end of its range.
-__device__ __forceinline__ bool opt_work(const void* __restrict__ table, OptWork& w) {
-  const OptHeader h = *(const OptHeader*)table;
-  if (h.magic != OPT_MAGIC || (long)blockIdx.x >= h.n_blocks) return false;
-  const char* ranges = (const char*)table + sizeof(OptHeader);
-  const OptBlock b = ((const OptBlock*)(ranges + (size_t)h.n_ranges * sizeof(avmoe_opt_range)))[blockIdx.x];
-  if (b.range < 0 || b.range >= h.n_ranges) return false;
-  w.n_ranges = h.n_ranges;
-  w.range = b.range;
-  w.r = ((const avmoe_opt_range*)ranges)[b.range];
-  w.i0 = ((long)b.block * 256 + threadIdx.x) * 4;
-  return w.i0 < w.r.n;
-}
-
-// one value per thread of a 256-thread block -> their sum, by a tree over LDS: a fixed order of additions
-__device__ __forceinline__ double block_sum_256(double acc) {
-  __shared__ double red[256];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // sum over the block's elements of ((double)grad * grad_scale)^2 -> partials[blockIdx.x].  A launch whose grid does not match the table
 // (a stale or foreign image) touches nothing but its own partial sum.
@@ -288,23 +247,6 @@ __global__ void __launch_bounds__(256) kk_opt_range_norms(const void* __restrict
       // -1 is the largest unsigned value: the minimum over the ranges that are not finite, or -1 where there is none
       if (!isfinite(norm)) atomicMin((unsigned int*)&report->first_nonfinite, (unsigned int)r);
     }
-  }
-}
-
-// the shadow buffer of range `range`, or NULL where the pointer array was not made for this table (another range count) or the entry
-// cannot take 16-byte accesses: such a launch touches nothing
-__device__ __forceinline__ float* opt_shadow(const OptWork& w, float* const* __restrict__ shadows, int n_shadows) {
-  if (w.n_ranges != n_shadows) return nullptr;
-  float* e = shadows[w.range];
-  return ((uintptr_t)e & 15u) == 0 ? e : nullptr;
-}
-
-// param[i] = hold[i] for elements [i0, min(i0 + 4, n)) of one range: what a skipped step under HOLD does
-__device__ __forceinline__ void restore_quad(float* __restrict__ p, const float* __restrict__ h, long i0, long n) {
-  if (i0 + 3 < n) {
-    *(float4*)(p + i0) = *(const float4*)(h + i0);
-  } else {
-    for (long i = i0; i < n; ++i) p[i] = h[i];
   }
 }
 
@@ -760,7 +702,6 @@ static int check_ranges(const char* who, const avmoe_opt_range* ranges, int32_t 
   return OK;
 }
 
-static size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 static size_t table_bytes_of(int32_t n_ranges, int64_t n_blocks) {
   return round16(sizeof(OptHeader) + (size_t)n_ranges * sizeof(avmoe_opt_range) + (size_t)n_blocks * sizeof(OptBlock));
 }
@@ -914,8 +855,9 @@ static int grad_norm(const char* who, const void* table, int32_t n_ranges, int64
   return OK;
 }
 
-// what every update entry point refuses, in one order: adam_step below and avmoe_opt_lamb_step
-static int check_step_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1,
+// what every update entry point refuses, in one order: adam_step below, avmoe_opt_lamb_step, avmoe_opt_prodigy_step and (opt_muon.hip)
+// avmoe_opt_muon_step
+int check_step_args(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1,
                            float beta2, float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, bool with_hold,
                            float* const* hold) {
   AVMOE_TRY(check_launch_args(who, table, n_ranges, n_blocks, state, beta1, beta2));

@@ -365,6 +365,36 @@ class FlatAdam:
     x0, s, both sums and d agree too: no communication is added (verified on one rank).  NOT covered: `trust_ratio` together with it,
     bias correction, the plain (non-device) path, parameters outside the reducer.
 
+    Orthogonalised momentum.  `muon=True` (Muon, Jordan et al. 2024; torch.optim.Muon's rule with the iteration in fp32; it selects the
+    device path too) steps the small hidden matrices -- the experts' down_sampler / up_sampler, the latent tokens, the router's Linear
+    layers -- along the nearest semi-orthogonal matrix of their momentum.  A parameter is orthogonalised when `dim() >= 2` and, with
+    rows = shape[0], cols = numel // rows (a conv weight flattened), min(rows, cols) <= 128 and numel <= `muon_max_numel`
+    (`muon_shape_of`, `muon_select`); a group's "muon": True | False overrides, True on a parameter that does not fit raises ValueError
+    naming it.  Every other parameter takes the unchanged Adam / AdamW step, bit for bit.  With g' the gradient as the update sees it
+    (scale, clip factor, coupled decay), mu = `muon_momentum` and w the weights before the step (behind `sam_perturb()` the held ones):
+
+        m = mu m + (1 - mu) g' ;  u = (1 - mu) g' + mu m   (`muon_nesterov`; else u = m)         m lives in exp_avg, exp_avg_sq stays zero
+        X = u / (||u||_F + 1e-7) ;  `muon_ns_steps` times  X <- a X + (b A + c A A) X,  A = X X^T      (a, b, c) = (3.4445, -4.7750, 2.0315)
+        s = 0.2 sqrt(max(rows, cols))   ("match_rms_adamw": the recipe's Adam learning rates keep their meaning)
+          = sqrt(max(1, rows / cols))   (`muon_scale="original"`)
+        w = w (1 - lr lr_factor wd)   (decoupled decay only) ;  w = w - (lr lr_factor s) X
+
+    without a bias correction; `betas` and `eps` keep serving the other parameters; a zero u gives a zero step.  The recipe:
+    `FlatAdam(red, lr=args.lr, muon=True, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0)`.  A step is the unchanged
+    norm call and then TWO launches in place of the update whatever the number of parameters (include/avmoe.h, avmoe_opt_muon_step):
+    one over the table that updates the other parameters and leaves m, u and per-block sums of u^2, and one with a workgroup per
+    matrix that keeps the Gram matrix in LDS, streams the matrix through it and applies the step -- no host synchronisation, no
+    step-dependent host scalar, capturable; a host implementation needs about fifteen small GEMM launches per matrix.  One flat work
+    buffer per bucket, with the bucket's layout.  Clipping, skipping (a skipped step leaves every bit; behind a perturbation it writes
+    the held weights back and nothing else), both decays, schedule, averages, averaged buffers, per-parameter gradient norms and SAM
+    compose unchanged; `trust_ratio` or `prodigy` together with it raises ValueError.  `orthogonalized` and `muon_scales` are host lists
+    in `params` order, `last_muon_updates` DEVICE views of the applied direction X per parameter (None where not orthogonalised),
+    `last_muon_norms` an fp32 DEVICE tensor of ||u||_F.  `state_dict()` keeps torch's format (exp_avg is the momentum) and carries the
+    constants under "flat_adam"; a dict saved with the option does not load into an optimizer built without it (ValueError).  Under
+    data parallelism the gradients agree on every rank after `red.finish()` and so does every step: no communication is added
+    (verified on one rank only).  NOT covered: a short side above 128, a matrix split across workgroups, the plain (non-device) path,
+    an iteration in bf16 and with it torch.optim.Muon's bits.
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -382,7 +412,9 @@ class FlatAdam:
                  report_grad_norms: bool = False, ema_buffers=None, swa_start: Optional[int] = None, swa_freq: int = 1,
                  sam_rho: Optional[float] = None, sam_adaptive: bool = False, trust_ratio: bool = False,
                  trust_clip: Optional[float] = None, prodigy: bool = False, prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0,
-                 prodigy_growth: Optional[float] = None, prodigy_safeguard_warmup: bool = False):
+                 prodigy_growth: Optional[float] = None, prodigy_safeguard_warmup: bool = False, muon: bool = False,
+                 muon_momentum: float = 0.95, muon_nesterov: bool = True, muon_ns_steps: int = 5, muon_scale: str = "match_rms_adamw",
+                 muon_max_numel: int = 262144):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -398,7 +430,11 @@ class FlatAdam:
         multiplier of an estimate d kept on the device; prodigy_d0 > 0: its start, prodigy_d_coef > 0: a factor on the estimate,
         prodigy_growth >= 1 or None: the largest factor d may grow by per step, prodigy_safeguard_warmup: leave the rate out of a step's
         weight in the estimate (all held as fp32; ValueError for a bad value, for one given without `prodigy`, and for `prodigy` with
-        `trust_ratio`).  Any of the ten selects the device path (class docstring); with all at their
+        `trust_ratio`).  muon: orthogonalised momentum for the small hidden matrices (class docstring): a parameter with `dim() >= 2`
+        whose short side is at most 128 and whose numel is at most `muon_max_numel` steps along the nearest semi-orthogonal matrix of
+        its momentum; muon_momentum in [0, 1) (held as fp32), muon_nesterov, muon_ns_steps in 1..16, muon_scale "match_rms_adamw" |
+        "original" (ValueError for a bad value, for one given without `muon`, and for `muon` with `trust_ratio` or `prodigy`).
+        Any of the eleven selects the device path (class docstring); with all at their
         defaults step() is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
         and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
@@ -409,7 +445,8 @@ class FlatAdam:
         on both paths, coupled and decoupled; parameters not listed, or listed without the key, use `weight_decay`.  `betas` and `eps`
         stay per optimizer: a group's own are ignored.  On the plain path, neighbouring parameters of a bucket with the same rate and
         decay share one kernel launch (an adapter site is one range).  With `trust_ratio` a group may carry "trust_ratio": True | False,
-        which overrides the default (adapted: `dim() >= 2`) for that group's parameters."""
+        which overrides the default (adapted: `dim() >= 2`) for that group's parameters.  With `muon` a group may carry
+        "muon": True | False likewise; True on a parameter that does not fit raises ValueError naming it."""
         self.reducer, self.lr0, self.betas, self.eps, self.wd = reducer, lr, betas, eps, weight_decay
         self.step_size, self.gamma, self.grad_scale = step_size, gamma, grad_scale
         self.t, self.epoch = 0, 0
@@ -433,14 +470,20 @@ class FlatAdam:
             self._check_prodigy(prodigy, prodigy_d0, prodigy_d_coef, prodigy_growth, prodigy_safeguard_warmup)
         if self.prodigy and self.trust_ratio:
             raise ValueError("prodigy and trust_ratio are two rules for the step size: choose one")
+        self.muon, self.muon_momentum, self.muon_nesterov, self.muon_ns_steps, self.muon_scale, self.muon_max_numel = \
+            self._check_muon(muon, muon_momentum, muon_nesterov, muon_ns_steps, muon_scale, muon_max_numel)
+        if self.muon and (self.trust_ratio or self.prodigy):
+            raise ValueError("muon and trust_ratio / prodigy are different rules for the step: choose one")
         for grp in (param_groups or []):                 # before anything is touched
             if "trust_ratio" in grp and not isinstance(grp["trust_ratio"], bool):
                 raise ValueError(f"a parameter group's \"trust_ratio\" must be True or False, not {grp['trust_ratio']!r}")
+        self.muon_select([], param_groups, self.muon_max_numel)          # the groups' "muon" keys, likewise
         self.report_grad_norms = bool(report_grad_norms)
         self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
         self._plist = []                                 # (parameter, index into self.state, offset, lr0) in the reducer's order
         self._wds = []                                   # beside it: each parameter's weight decay
         self._adapted = []                               # beside it: whether the parameter's step takes its trust ratio (trust_ratio)
+        self._muon_shapes = []                           # beside it: (rows, cols) of an orthogonalised parameter, None for the others (muon)
         lr_of, wd_of, adapt_of = {}, {}, {}
         for grp in (param_groups or []):
             ps = grp["params"]
@@ -466,6 +509,7 @@ class FlatAdam:
                 self._plist.append((p, len(self.state), off, lr_of.get(id(p), float(lr))))
                 self._wds.append(wd_of.get(id(p), weight_decay))
                 self._adapted.append(adapt_of.get(id(p), p.dim() >= 2))
+                self._muon_shapes.append(self.muon_select([p], param_groups, self.muon_max_numel)[0] if self.muon else None)
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
             if self._averaging:                          # the averages: the bucket's layout once more, padding zero
                 self.state[-1]["e"] = flat_p.clone()
@@ -474,10 +518,12 @@ class FlatAdam:
             if self.prodigy:                             # x0 and the running gradient sum: the bucket's layout twice more, padding zero
                 self.state[-1]["x0"] = flat_p.clone()
                 self.state[-1]["s"] = torch.zeros_like(flat_p)
+            if self.muon:                                # the work buffer: the bucket's layout once more; holds O after a step
+                self.state[-1]["o"] = torch.zeros_like(flat_p)
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
             or self._averaging or self.report_grad_norms or self.sam_rho is not None or self.trust_ratio \
-            or self.prodigy
+            or self.prodigy or self.muon
         if self._device:
             self._build_device_state()
 
@@ -767,7 +813,14 @@ class FlatAdam:
     def _update(self, L, stream, n, scale, flags, shadows):
         """the update launch of a device step: avmoe_opt_adam_step_ema, or behind a sam_perturb() avmoe_opt_adam_step_sam, which reads
         the parameters from the hold buffers and so brings the unperturbed weights back; with `trust_ratio` avmoe_opt_lamb_step and
-        with `prodigy` avmoe_opt_prodigy_step serve both cases"""
+        with `prodigy` avmoe_opt_prodigy_step serve both cases, and with `muon` avmoe_opt_muon_step"""
+        if self.muon:                                    # two launches in place of one; the hold buffers only behind a sam_perturb()
+            capi.check(L.avmoe_opt_muon_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1], self.eps, scale,
+                                             flags, stream, shadows, self._hold_ptrs.data_ptr() if self._perturbed else None,
+                                             self._muon_image.data_ptr(), len(self._muon_order), self._muon_work_ptrs.data_ptr(),
+                                             C.byref(self._muon_c), self._muon_ws.data_ptr(), self._muon_report.data_ptr()), "avmoe_opt_muon_step")
+            self._perturbed = False
+            return
         if self.prodigy:                                 # two launches in place of one; the hold buffers only behind a sam_perturb()
             capi.check(L.avmoe_opt_prodigy_step(self._table_ptr, n, self._n_blocks, self._state_ptr, self.betas[0], self.betas[1], self.eps, scale,
                                                 flags, stream, shadows, self._hold_ptrs.data_ptr() if self._perturbed else None,
@@ -985,6 +1038,139 @@ class FlatAdam:
         self._need_prodigy("prodigy_s")
         return list(self._prodigy_s_views)
 
+    # ---- orthogonalised momentum (Muon) ---------------------------------------------------------------------------
+    MUON_MAX_DIM = 128                                   # AVMOE_MUON_MAX_DIM: the short side one workgroup's LDS holds the Gram matrix of
+    MUON_SCALES = ("match_rms_adamw", "original")        # AVMOE_MUON_SCALE_*
+
+    @staticmethod
+    def _check_muon(on, momentum, nesterov, ns_steps, scale, max_numel):
+        """-> (muon, momentum as the fp32 value the device gets, nesterov, ns_steps, scale, max_numel)"""
+        if not isinstance(on, bool):
+            raise ValueError(f"muon must be True or False, not {on!r}")
+        if not isinstance(nesterov, bool):
+            raise ValueError(f"muon_nesterov must be True or False, not {nesterov!r}")
+        mu = float(momentum)
+        if not (0.0 <= mu < 1.0) or _f32(mu) >= 1.0:
+            raise ValueError(f"muon_momentum must be in [0, 1) (as fp32), not {momentum!r}")
+        if isinstance(ns_steps, bool) or not isinstance(ns_steps, int) or not (1 <= ns_steps <= 16):
+            raise ValueError(f"muon_ns_steps must be an integer in 1..16, not {ns_steps!r}")
+        if scale not in FlatAdam.MUON_SCALES:
+            raise ValueError(f"muon_scale must be one of {FlatAdam.MUON_SCALES}, not {scale!r}")
+        if isinstance(max_numel, bool) or not isinstance(max_numel, int) or max_numel < 1:
+            raise ValueError(f"muon_max_numel must be an integer >= 1, not {max_numel!r}")
+        if not on and (_f32(mu) != _f32(0.95) or nesterov is not True or ns_steps != 5 or scale != "match_rms_adamw" or max_numel != 262144):
+            raise ValueError("muon_momentum / muon_nesterov / muon_ns_steps / muon_scale / muon_max_numel need muon: there is no matrix to orthogonalise")
+        return on, _f32(mu), nesterov, ns_steps, scale, max_numel
+
+    @staticmethod
+    def muon_shape_of(p, max_numel: int = 262144):
+        """(rows, cols) as which a parameter is orthogonalised -- rows = shape[0], cols = numel // rows, a conv weight flattened as
+        torch.optim.Muon's users do -- or None where it does not fit: dim() < 2, no elements, min(rows, cols) > 128 or numel > max_numel."""
+        if p.dim() < 2 or p.numel() == 0:
+            return None
+        rows = int(p.shape[0])
+        cols = p.numel() // rows
+        if min(rows, cols) > FlatAdam.MUON_MAX_DIM or p.numel() > max_numel:
+            return None
+        return rows, cols
+
+    @staticmethod
+    def muon_select(params, param_groups=None, muon_max_numel: int = 262144) -> list:
+        """The selection rule of `muon=True`, in `params` order: (rows, cols) for a parameter that is orthogonalised, None for one that
+        takes Adam / AdamW.  Default: `muon_shape_of`; a group's "muon": False switches its parameters off, True insists -- ValueError
+        naming the parameter where it does not fit, and for a "muon" that is not a bool."""
+        override = {}
+        for gi, grp in enumerate(param_groups or []):
+            if "muon" not in grp:
+                continue
+            if not isinstance(grp["muon"], bool):
+                raise ValueError(f"a parameter group's \"muon\" must be True or False, not {grp['muon']!r}")
+            ps = grp["params"]
+            for k, p in enumerate([ps] if isinstance(ps, torch.Tensor) else ps):
+                if grp["muon"] and FlatAdam.muon_shape_of(p, muon_max_numel) is None:
+                    raise ValueError(f"parameter group {gi} asks for muon on its parameter {k} of shape {tuple(p.shape)}, which does not fit: it "
+                                     f"needs dim() >= 2, a short side <= {FlatAdam.MUON_MAX_DIM} and numel <= muon_max_numel = {muon_max_numel}")
+                override[id(p)] = grp["muon"]
+        return [FlatAdam.muon_shape_of(p, muon_max_numel) if override.get(id(p), True) else None for p in params]
+
+    @staticmethod
+    def muon_scale_of(rows: int, cols: int, scale: str = "match_rms_adamw") -> float:
+        """the factor s on an orthogonalised parameter's rate, as the fp32 value kk_opt_muon_ns forms: 0.2 sqrt(max(rows, cols))
+        ("match_rms_adamw": an Adam learning rate keeps its meaning) or sqrt(max(1, rows / cols)) ("original")"""
+        if scale == "original":
+            return _f32(math.sqrt(max(1.0, rows / cols)))
+        return _f32(0.2 * math.sqrt(float(max(rows, cols))))
+
+    def _need_muon(self, what):
+        if not self.muon:
+            raise capi.AvmoeError(f"FlatAdam.{what} needs muon")
+
+    def _set_muon(self, momentum, nesterov, ns_steps, scale):
+        self.muon_momentum, self.muon_nesterov, self.muon_ns_steps, self.muon_scale = momentum, nesterov, ns_steps, scale
+        self._muon_c = cm.OptMuon(momentum=momentum, nesterov=int(nesterov), ns_steps=ns_steps, scale=self.MUON_SCALES.index(scale))
+
+    def _build_muon(self):
+        """the matrix list (longest first, so that the long ones start first), its image on the device, one work pointer per range,
+        the workspace of one double per table block and the report (header, then ||u||_F per matrix)"""
+        L, n = capi.lib(), len(self._plist)
+        if not hasattr(L, "avmoe_opt_muon_step"):
+            raise capi.AvmoeError("this libavmoe_hip.so lacks orthogonalised momentum (avmoe_opt_muon_step): rebuild it")
+        order = [i for i, sh in enumerate(self._muon_shapes) if sh is not None]
+        order.sort(key=lambda i: -self._plist[i][0].numel())          # (stable: equal sizes keep the parameters' order)
+        self._muon_order = order
+        mats = (cm.OptMuonMat * max(1, len(order)))()
+        for m, i in zip(mats, order):
+            m.range, (m.rows, m.cols) = i, self._muon_shapes[i]
+        lay = cm.OptMuonLayout()
+        if L.avmoe_opt_muon_bytes(n, self._n_blocks, len(order), C.byref(lay)) == 0:
+            capi.check(-1, "avmoe_opt_muon_bytes")
+        img = torch.zeros(int(lay.table_bytes), dtype=torch.uint8)
+        capi.check(L.avmoe_opt_muon_table_build(self._opt_ranges(), n, mats, len(order), img.data_ptr(), int(lay.table_bytes)),
+                   "avmoe_opt_muon_table_build")
+        self._muon_image = img.to(self._dev)
+        self._muon_views, ptrs = [], []
+        for (p, si, off, _lr0), sh in zip(self._plist, self._muon_shapes):
+            o = self.state[si]["o"]
+            self._muon_views.append(None if sh is None else o[off:off + p.numel()].view_as(p))
+            ptrs.append(o.data_ptr() + 4 * off)
+        if any(q % 16 for q in ptrs):
+            raise capi.AvmoeError("FlatAdam: a work range is not 16-byte aligned")
+        self._muon_work_ptrs = torch.tensor(ptrs, dtype=torch.int64).to(self._dev)
+        self._muon_ws = torch.zeros(int(lay.workspace_bytes), dtype=torch.uint8, device=self._dev)
+        self._muon_report = torch.zeros(int(lay.report_bytes), dtype=torch.uint8, device=self._dev)
+        self._muon_norms = self._muon_report[16:16 + 4 * len(order)].view(torch.float32)       # in the list's order
+        self._muon_index = torch.tensor(order, dtype=torch.int64).to(self._dev)
+        self._set_muon(self.muon_momentum, self.muon_nesterov, self.muon_ns_steps, self.muon_scale)
+
+    @property
+    def orthogonalized(self) -> List[bool]:
+        """host state, in `params` order: whether the parameter steps along its orthogonalised momentum (the others take Adam / AdamW)"""
+        return [sh is not None for sh in self._muon_shapes]
+
+    @property
+    def muon_scales(self) -> List[float]:
+        """host floats, in `params` order: the factor s on every orthogonalised parameter's rate (`muon_scale_of`); 0 for the others"""
+        return [0.0 if sh is None else self.muon_scale_of(sh[0], sh[1], self.muon_scale) for sh in self._muon_shapes]
+
+    @property
+    def last_muon_updates(self) -> list:
+        """in `params` order: DEVICE views, shaped like the parameter, of the orthogonalised direction O the last applied step() moved
+        it along (w = w - lr s O); None for a parameter that is not orthogonalised.  Views of the work buffers, rewritten by every
+        applied step and every replay of a captured one (a skipped step leaves them).  Only with `muon`."""
+        self._need_muon("last_muon_updates")
+        return list(self._muon_views)
+
+    @property
+    def last_muon_norms(self) -> torch.Tensor:
+        """fp32 DEVICE tensor of len(params), in `params` order: ||u||_F of every orthogonalised parameter's direction before the
+        iteration at the last applied step(), summed in double; 0 for the others.  Gathered from the report on the current stream at
+        every call (no synchronisation).  Only with `muon`."""
+        self._need_muon("last_muon_norms")
+        out = torch.zeros(len(self._plist), dtype=torch.float32, device=self._dev)
+        if self._muon_order:
+            out.index_copy_(0, self._muon_index, self._muon_norms)
+        return out
+
     # ---- the device path ------------------------------------------------------------------------------------------
     def _opt_ranges(self):
         """one avmoe_opt_range per parameter (its own elements only: the norm must not see alignment padding)"""
@@ -1031,6 +1217,8 @@ class FlatAdam:
             self._build_trust()
         if self.prodigy:
             self._build_prodigy()
+        if self.muon:
+            self._build_muon()
 
     def _build_report(self):
         """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
@@ -1281,6 +1469,9 @@ class FlatAdam:
                          prodigy_d_hat=blk["d_hat"], prodigy_num=blk["num"], prodigy_den=blk["den"],
                          prodigy_x0=[x.detach().cpu().clone() for x in self._prodigy_x0_views],
                          prodigy_s=[x.detach().cpu().clone() for x in self._prodigy_s_views])
+        if self.muon:                                    # constants only: exp_avg IS the momentum, O and the norms are rewritten by every step
+            extra.update(muon=True, muon_momentum=self.muon_momentum, muon_nesterov=self.muon_nesterov, muon_ns_steps=self.muon_ns_steps,
+                         muon_scale=self.muon_scale, muon_max_numel=self.muon_max_numel)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
             extra["report_grad_norms"] = True
         return {"state": state, "param_groups": groups, "flat_adam": extra}
@@ -1301,7 +1492,9 @@ class FlatAdam:
         block ("prodigy_d", "prodigy_d_max", "prodigy_d_hat", "prodigy_num", "prodigy_den"), "prodigy_x0" and "prodigy_s" are restored
         (a count or shape mismatch raises ValueError naming the parameter); a dict without "prodigy" re-seeds: x0 = the CURRENT
         parameters, s = 0, d = d0, so load the model first.  Without the option a dict that carries "prodigy" raises ValueError: its
-        rates are multipliers of d, not learning rates."""
+        rates are multipliers of d, not learning rates.  With `muon`: the saved constants ("muon_momentum", "muon_nesterov", "muon_ns_steps",
+        "muon_scale") replace the constructor's; which parameters are orthogonalised stays what the constructor says; a dict without
+        "muon" loads as before.  Without the option a dict that carries "muon" raises ValueError."""
         self._not_swapped("load_state_dict()")
         self._not_perturbed("load_state_dict()")
         saved_groups, own_groups = sd["param_groups"], self._groups()
@@ -1382,6 +1575,14 @@ class FlatAdam:
                 raise ValueError(f"the state dict's prodigy_d / prodigy_d_max must be finite with 0 < d <= d_max, not {d!r} / {d_max!r}")
             prodigy_saved = (consts, lists, {"d": d, "d_max": d_max, "d_hat": float(extra.get("prodigy_d_hat", 0.0)),
                                              "num": float(extra.get("prodigy_num", 0.0)), "den": float(extra.get("prodigy_den", 0.0))})
+        if extra.get("muon") is True and not self.muon:
+            raise ValueError("the state dict was saved with muon (exp_avg of its matrices is a momentum with no second moment beside it), which "
+                             "this optimizer was built without: build it with muon=True")
+        muon_consts = None
+        if self.muon and extra.get("muon") is True:
+            muon_consts = self._check_muon(True, extra.get("muon_momentum", self.muon_momentum), extra.get("muon_nesterov", self.muon_nesterov),
+                                           extra.get("muon_ns_steps", self.muon_ns_steps), extra.get("muon_scale", self.muon_scale),
+                                           self.muon_max_numel)[1:5]
         saved_bufs = extra.get("ema_buffers") if self._ebufs else None
         if saved_bufs is not None:
             names = self.ema_buffer_names
@@ -1449,6 +1650,8 @@ class FlatAdam:
                             view.copy_(e.to(torch.float32))
                     else:                                 # no buffer averages in the dict: start them from the buffers as they are now
                         self._seed_buffer_shadows()
+                if muon_consts is not None:
+                    self._set_muon(*muon_consts)
                 if self.prodigy:
                     if prodigy_saved is not None:
                         consts, lists, blk = prodigy_saved

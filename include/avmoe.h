@@ -780,6 +780,91 @@ int avmoe_opt_prodigy_step(const void* table, int32_t n_ranges, int64_t n_blocks
                            const avmoe_opt_prodigy* consts /* HOST */, avmoe_opt_prodigy_state* block /* DEVICE, 16-byte aligned */,
                            double* workspace /* DEVICE */);
 
+/* Muon: orthogonalised momentum for small hidden matrices (Jordan et al. 2024; torch.optim.Muon's rule with the iteration in fp32; added
+ * under ABI 11 like the blocks above; found by symbol).  A range that is listed as a matrix steps along the nearest semi-orthogonal
+ * matrix of its momentum, found by Newton-Schulz iterations; every other range takes the unchanged Adam / AdamW update.  No flag and
+ * no new word in the state block: avmoe_opt_muon_step is called IN PLACE of avmoe_opt_adam_step_ema / avmoe_opt_adam_step_sam, behind
+ * the unchanged norm call of a step, on the same stream with the same grad_scale and betas.
+ * The matrices are described once, on the host: avmoe_opt_muon_table_build checks a list of avmoe_opt_muon_mat {range, rows, cols} --
+ * the range's elements read as a row-major rows x cols matrix -- and writes an image (header, the matrices in the caller's order, a
+ * range -> matrix map) that the caller copies to DEVICE memory; that image is the `mats` of the two calls below.  The checks need the
+ * host's copy, which is why they are made there and not by the calls that launch: a call that launches reads no device memory on the
+ * host.  Callers sort the list by rows * cols descending, so that the long matrices start first.
+ * With gscale = grad_scale * clip_coef, mu = momentum, lr = lr_r * lr_factor (under AVMOE_OPT_LR_SCHEDULE), w the parameter before the
+ * step (with hold != NULL the held value), per element of a listed range, every operation rounded to fp32 in the order written,
+ * contraction off:
+ *     gr = fma(gscale, grad, wd * w)          AVMOE_OPT_DECOUPLED_DECAY: gr = grad * gscale
+ *     m  = fma(mu, m, (1 - mu) * gr)          m is exp_avg; exp_avg_sq is neither read nor written; there is no bias correction
+ *     u  = fma(mu, m, (1 - mu) * gr)          nesterov == 0: u = m
+ * and per matrix, with d = min(rows, cols), Y the d x L view of u (Y = u for rows <= cols, Y = u^T otherwise):
+ *     Y0 = Y * fp32(1 / (||u||_F + 1e-7))     ||u||_F: the sum of (double)u^2 in a fixed order, its double square root
+ *     ns_steps times:  A = Y Y^T ;  B = b A + c (A A) ;  Y = a Y + B Y        (a, b, c) = (3.4445, -4.7750, 2.0315)
+ *     O  = the rows x cols view of Y ;  s = fp32(0.2 * sqrt((double)max(rows, cols)))     (AVMOE_MUON_SCALE_MATCH_RMS_ADAMW)
+ *                                       s = fp32(sqrt(max(1.0, (double)rows / cols)))     (AVMOE_MUON_SCALE_ORIGINAL)
+ *     w  = w * (1 - lr * wd)                  (AVMOE_OPT_DECOUPLED_DECAY only)
+ *     w  = w - (lr * s) * O                   under AVMOE_OPT_EMA then shadow = d shadow + (1 - d) w as avmoe_opt_adam_step_ema does
+ * The products run on v_mfma_f32_16x16x4_f32 (exact fp32, fp32 accumulation in chains along the contraction index).  A zero u gives O = 0.
+ * avmoe_opt_muon_step is TWO launches on `stream` whatever the number of ranges, without a host synchronisation and without a host
+ * scalar that changes from step to step, so it replays from a captured graph:
+ *   kk_opt_muon_update<DECOUPLED, SCHED, EMA, HOLD>   one block per table block.  A range that is not listed gets exactly the update of
+ *       avmoe_opt_adam_step_ema / _sam (the same helpers of csrc/adam_elem.h, the same bits, the shadow included).  A listed range gets
+ *       m, and u into work[range] -- one flat fp32 buffer per bucket in the bucket's layout, addressed by a DEVICE array of n_ranges
+ *       float* under the rules of `shadows`; entries of ranges that are not listed are not read -- and the block's sum of (double)u^2
+ *       into `workspace` (one double per table block, no initialisation needed).
+ *   kk_opt_muon_ns<STEP>   one workgroup of 512 threads per matrix.  It adds its range's block sums in a fixed order (thread t blocks
+ *       t, t + 512, ..., then a tree; no floating-point atomics: the same input gives the same bits), runs the iteration in place in
+ *       the work buffer, and in the last pass applies decay and update to the parameter.  O stays in the work buffer.  A and B stay in
+ *       LDS as d_pad x d_pad fp32 (d padded to a multiple of 16 by zero rows); Y is streamed from global memory in chunks along its
+ *       long side, each chunk updated in place in LDS and the next iteration's Gram matrix accumulated from the chunk just produced
+ *       (one pass over Y per iteration).  The launch ALWAYS asks for 160 KB of dynamic LDS, whatever d: a workgroup that issues
+ *       v_mfma_f32_16x16x4_f32 must have its compute unit to itself (avmoe_moe_desc::shared_gpu above), and an all-reduce or a backbone
+ *       kernel may be on the GPU during a step.
+ * `report` (DEVICE, 16-byte aligned): a 16-byte header {n_mats, 0, 0, 0}, then ||u||_F of every matrix as fp32, in the list's order.
+ * avmoe_opt_muon_bytes returns the bytes of the image, the workspace and the report (each a multiple of 16; 0 and an error string on a
+ * negative count or more than 2^31 - 1 blocks) and their sum.
+ * When state->skip is set nothing is written: moments, parameters, work buffers, workspace and report keep their values -- with
+ * hold != NULL param = hold (every range, listed or not) and nothing else.  Gradients are only read; alignment padding belongs to no
+ * range and is not touched, in the work buffers neither.  A launch that does not match its table's or its image's header touches
+ * nothing; a listed range whose work / shadow / hold entry is not 16-byte aligned is left out by both launches.
+ * avmoe_opt_muon_ns is the second launch alone, for tests: on matrices already in the work buffers it computes ||u||_F itself (thread t
+ * elements t, t + 512, ..., then the tree), normalises and iterates; no table, no parameter, no report.
+ * Errors of avmoe_opt_muon_table_build: AVMOE_ERR_BAD_ARG for NULL mats (with n_mats > 0) or image, negative counts, a range index
+ * outside [0, n_ranges), rows or cols < 1, min(rows, cols) > 128, rows * cols != n of the range (where `ranges` is given), a range
+ * named twice; AVMOE_ERR_WORKSPACE for an image that is too small.
+ * Errors of the two calls (before any launch): everything avmoe_opt_adam_step_sam refuses (hold != NULL) or avmoe_opt_adam_step_ema
+ * refuses (hold == NULL); AVMOE_ERR_BAD_ARG for NULL mats, work, consts, workspace or report, a negative n_mats, a momentum outside
+ * [0, 1), nesterov not 0 / 1, ns_steps outside 1..16, an unknown scale; AVMOE_ERR_ALIGNMENT for an image or report that is not 16-byte
+ * or a work pointer array or workspace that is not 8-byte aligned.
+ * NOT covered: min(rows, cols) > 128, a matrix split across workgroups, an iteration in bf16.                                           */
+#define AVMOE_MUON_MAX_DIM 128
+#define AVMOE_MUON_SCALE_MATCH_RMS_ADAMW 0
+#define AVMOE_MUON_SCALE_ORIGINAL 1
+
+typedef struct avmoe_opt_muon_mat {
+  int32_t range;              /* index into the optimizer's table */
+  int32_t rows, cols;         /* rows * cols == n of the range */
+  int32_t reserved;           /* 0 */
+} avmoe_opt_muon_mat;
+
+typedef struct avmoe_opt_muon {
+  float momentum;             /* mu, in [0, 1) */
+  int32_t nesterov;           /* 0 / 1 */
+  int32_t ns_steps;           /* 1 .. 16 */
+  int32_t scale;              /* AVMOE_MUON_SCALE_* */
+} avmoe_opt_muon;
+
+typedef struct avmoe_opt_muon_layout { size_t table_bytes, workspace_bytes, report_bytes; } avmoe_opt_muon_layout;
+
+size_t avmoe_opt_muon_bytes(int32_t n_ranges, int64_t n_blocks, int32_t n_mats, avmoe_opt_muon_layout* layout /* HOST, or NULL */);
+int avmoe_opt_muon_table_build(const avmoe_opt_range* ranges /* HOST, or NULL */, int32_t n_ranges, const avmoe_opt_muon_mat* mats /* HOST */,
+                               int32_t n_mats, void* image /* HOST */, size_t image_bytes);
+int avmoe_opt_muon_step(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                        float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
+                        float* const* hold /* DEVICE, or NULL */, const void* mats /* DEVICE: the image */, int32_t n_mats,
+                        float* const* work /* DEVICE */, const avmoe_opt_muon* consts /* HOST */, double* workspace /* DEVICE */,
+                        void* report /* DEVICE, 16-byte aligned */);
+int avmoe_opt_muon_ns(const void* mats /* DEVICE: the image */, int32_t n_mats, float* const* work /* DEVICE */, int32_t ns_steps, void* stream);
+
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the
  * tiled engine is faster.  force_mask lifts those thresholds so that a test can run the benchmarked kernels on shapes its oracle

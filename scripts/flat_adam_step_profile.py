@@ -32,6 +32,12 @@
 --prodigy          (device mode) FlatAdam(lr=1.0, prodigy=True): Prodigy learning-rate estimation -- two launches (the update with both block
                    sums, a one-block finalize that writes d) in place of the one update launch: 4 per step.  The alternative to --lamb;
                    combines with --schedule, --ema, --swa, --report, --sam
+--adamw            (device mode) decoupled weight decay (torch.optim.AdamW's rule): the baseline of --muon
+--muon             (device mode) FlatAdam(muon=True, decoupled_weight_decay=True): orthogonalised momentum for the hidden matrices -- two
+                   launches (the table walk with m, u and block sums; a workgroup per matrix for the Newton-Schulz iteration and the
+                   update) in place of the one update launch: 4 per step.  The alternative to --lamb / --prodigy; combines with
+                   --schedule, --ema, --swa, --report, --sam.  Time it with --per-step-events: `step_seg_median_us` is the median of the
+                   event pairs around every step()
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
@@ -84,6 +90,8 @@ def main():
     ap.add_argument("--per-step-events", action="store_true")
     ap.add_argument("--lamb", action="store_true")
     ap.add_argument("--prodigy", action="store_true")
+    ap.add_argument("--adamw", action="store_true")
+    ap.add_argument("--muon", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -113,6 +121,10 @@ def main():
         ap.error("--lamb goes with --mode device")
     if a.prodigy and (a.mode != "device" or a.lamb):
         ap.error("--prodigy goes with --mode device and is the alternative to --lamb")
+    if a.muon and (a.mode != "device" or a.lamb or a.prodigy):
+        ap.error("--muon goes with --mode device and is the alternative to --lamb / --prodigy")
+    if a.adamw and a.mode != "device":
+        ap.error("--adamw goes with --mode device")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
@@ -146,6 +158,10 @@ def main():
     buffer_shadows = [b.detach().clone() for b in buffers] if a.ema_buffers_foreach else None
     if a.prodigy:
         kw.update(prodigy=True)
+    if a.adamw or a.muon:
+        kw.update(decoupled_weight_decay=True)
+    if a.muon:
+        kw.update(muon=True)
     opt = FlatAdam(red, lr=1.0 if a.prodigy else 1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
@@ -232,7 +248,10 @@ def main():
         extra["buffers"], extra["buffer_elements"] = len(avg), sum(b.numel() for b in avg)
         extra["buffer_blocks"] = sum((b.numel() + 1023) // 1024 for b in avg)
     if split:
-        extra["step_seg_us"] = round(1e3 * sum(e[2].elapsed_time(e[3]) for e in marks) / len(marks), 2)
+        segs = sorted(e[2].elapsed_time(e[3]) for e in marks)
+        extra["step_seg_us"] = round(1e3 * sum(segs) / len(segs), 2)
+        extra["step_seg_median_us"] = round(1e3 * segs[len(segs) // 2], 2)
+        extra["step_seg_min_us"], extra["step_seg_max_us"] = round(1e3 * segs[0], 2), round(1e3 * segs[-1], 2)
     if a.sam or a.sam_foreach:
         extra["sam"] = ("device, adaptive" if a.adaptive else "device") if a.sam else "torch._foreach_* per step"
         extra["perturb_us"] = round(1e3 * sum(e[0].elapsed_time(e[1]) for e in marks) / len(marks), 2)
@@ -247,6 +266,15 @@ def main():
     if a.prodigy:
         extra["prodigy"] = "device"
         extra["d0"], extra["d"], extra["d_hat"] = opt.prodigy_d0, float(opt.prodigy_d.item()), float(opt.prodigy_d_hat.item())
+    if a.muon:
+        shapes = [sh for sh in opt._muon_shapes if sh is not None]
+        extra["muon"] = "device"
+        extra["matrices"], extra["matrix_elements"] = len(shapes), sum(r * c for r, c in shapes)
+        extra["largest_matrix"] = list(max(shapes, key=lambda sh: sh[0] * sh[1]))
+        extra["widest_short_side"] = max(min(sh) for sh in shapes)
+        extra["muon_norm_min"] = float(opt.last_muon_norms[opt._muon_index].min().item())
+    if a.adamw or a.muon:
+        extra["decay"] = "decoupled"
     if a.report:
         extra["report"] = "device"
         extra["first_nonfinite_param"] = int(opt.first_nonfinite_param.item())
