@@ -165,7 +165,7 @@ def main():
     opt = FlatAdam(red, lr=1.0 if a.prodigy else 1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
-    base_lr = [e[3] for e in opt._plist]
+    base_lr = [r.lr0 for r in opt._recs]
     g = torch.Generator().manual_seed(0)
     for b in red.buckets:
         b.flat.copy_(torch.randn(b.flat.numel(), generator=g))
@@ -209,7 +209,8 @@ def main():
             torch.nn.utils.clip_grad_norm_(grads, 1.0)
         if a.schedule_upload:                            # the host drives the schedule: new rates into the table, the table to the device
             f = sched.factor(opt.t)                      # opt.t == applied_steps here: the fixed finite gradients never skip a step
-            opt._plist = [e[:3] + (lr0 * f,) for e, lr0 in zip(opt._plist, base_lr)]
+            for r, lr0 in zip(opt._recs, base_lr):
+                r.lr0 = lr0 * f
             opt._upload_table()
         opt.step()
         if a.ema_foreach:                                # ema += (1 - d) * (p - ema), d of this step from the host's count of steps
@@ -267,7 +268,7 @@ def main():
         extra["prodigy"] = "device"
         extra["d0"], extra["d"], extra["d_hat"] = opt.prodigy_d0, float(opt.prodigy_d.item()), float(opt.prodigy_d_hat.item())
     if a.muon:
-        shapes = [sh for sh in opt._muon_shapes if sh is not None]
+        shapes = [r.muon_shape for r in opt._recs if r.muon_shape is not None]
         extra["muon"] = "device"
         extra["matrices"], extra["matrix_elements"] = len(shapes), sum(r * c for r, c in shapes)
         extra["largest_matrix"] = list(max(shapes, key=lambda sh: sh[0] * sh[1]))

@@ -43,7 +43,7 @@ def make_group_opt(model, groups, **kw):
 
 
 def rate_of(opt, i):
-    return opt._plist[i][3] * opt.decay
+    return opt._recs[i].lr0 * opt.decay
 
 
 @pytest.mark.parametrize("path,decoupled", [("device", False), ("device", True), ("plain", False)])
@@ -89,7 +89,7 @@ def test_a_parameter_of_the_zero_decay_group_is_not_decayed():
         set_grads(model, zero)
         opt.step()
     kept = changed = 0
-    for p, old, wd in zip(opt.params, before, opt._wds):
+    for p, old, wd in zip(opt.params, before, (r.wd for r in opt._recs)):
         same = torch.equal(bits(p), old)
         assert same or wd != 0.0, (tuple(p.shape), wd)      # (a decayed parameter that is all zeros stays as it is, too)
         kept, changed = kept + (wd == 0.0), changed + (not same)

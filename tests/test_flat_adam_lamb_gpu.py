@@ -135,7 +135,7 @@ def test_the_last_step_against_fp64_from_its_own_operands(name, decoupled):
     w_norms, u_norms, ratios = (t.cpu().tolist() for t in (opt.last_param_norms, opt.last_update_norms, opt.last_trust_ratios))
     worst, cases = {"w_norm": 0.0, "u_norm": 0.0, "ratio": 0.0, "p": 0.0}, {}
     assert len(opt.params) == len(SHAPES)
-    for i, ((p, si, off, lr0), wd) in enumerate(zip(opt._plist, opt._wds)):
+    for i, (p, si, off, lr0, wd) in enumerate((r.p, r.bucket, r.off, r.lr0, r.wd) for r in opt._recs):
         s, n = opt.state[si], p.numel()
         m1, v1 = (s[k][off:off + n].view_as(p).cpu() for k in "mv")
         used, case = lamb_ref.check_range(p0[i], p.detach().cpu(), m1, v1, w_norms[i], u_norms[i], ratios[i], lamb_ref.f32(lr0), lr_factor,
@@ -383,7 +383,7 @@ def test_a_launch_that_does_not_match_touches_nothing():
     bent[victim] += 4
     call(n, bent)
     torch.cuda.synchronize()
-    p, si, off, _lr0 = opt._plist[victim]
+    p, si, off = opt._recs[victim].p, opt._recs[victim].bucket, opt._recs[victim].off
     for k, (old, s) in zip("pmve", zip(before[si], (opt.state[si][k] for k in "pmve"))):
         assert torch.equal(bits(old[off:off + p.numel()]), bits(s[off:off + p.numel()])), ("the range with the bent shadow entry", k)
     other = 1 - si

@@ -180,7 +180,7 @@ def test_the_last_step_against_fp64_from_its_own_operands(name, decoupled):
     for k in range(STEPS - 1):
         step(opt, a, g2s[k], g1s[k] if name == "sam" else None)
     p0 = [p.detach().cpu().numpy().copy() for p in opt.params]             # behind sam_perturb() the held value: taken before it
-    m0 = [s["m"][off:off + p.numel()].view_as(p).cpu().numpy().copy() for p, si, off, _ in opt._plist for s in [opt.state[si]]]
+    m0 = [r.view("m").cpu().numpy().copy() for r in opt._recs]
     pads = [padding_mask(b, dev) for b in red.buckets]
     keys = "pmvoe" if name == "composed" else "pmvo"
     pad_before = [[s[k][pad].clone() for k in keys] for s, pad in zip(opt.state, pads)]
@@ -198,7 +198,7 @@ def test_the_last_step_against_fp64_from_its_own_operands(name, decoupled):
     assert opt.last_muon_norms.dtype == torch.float32 and opt.last_muon_norms.is_cuda and len(norms) == len(SHAPES)
     worst = {"m": 0.0, "norm": 0.0, "O": 0.0, "w": 0.0}
     seen = 0
-    for i, ((p, si, off, lr0), wd) in enumerate(zip(opt._plist, opt._wds)):
+    for i, (p, si, off, lr0, wd) in enumerate((r.p, r.bucket, r.off, r.lr0, r.wd) for r in opt._recs):
         s, n = opt.state[si], p.numel()
         assert not s["v"][off:off + n].any() or not opt.orthogonalized[i]  # exp_avg_sq of an orthogonalised parameter stays zero
         if not opt.orthogonalized[i]:
@@ -253,7 +253,7 @@ def test_the_other_parameters_take_adams_bits(decoupled):
     gs = grads(dev)
     for k in range(STEPS):
         step(oa, a, gs[k]); step(ob, b, gs[k])
-        for i, ((p, si, off, _), (q, sj, offb, _)) in enumerate(zip(oa._plist, ob._plist)):
+        for i, ((p, si, off), (q, sj, offb)) in enumerate(zip(((r.p, r.bucket, r.off) for r in oa._recs), ((r.p, r.bucket, r.off) for r in ob._recs))):
             assert p.shape == q.shape
             n = p.numel()
             if oa.orthogonalized[i]:
@@ -497,8 +497,8 @@ def test_a_launch_that_does_not_match_touches_nothing():
     bent[victim] += 4
     call(work=bent)
     torch.cuda.synchronize()
-    p, si, off, _lr0 = opt._plist[victim]
+    p, si, off = opt._recs[victim].p, opt._recs[victim].bucket, opt._recs[victim].off
     for k, (old, s) in zip("pmveo", zip(before[si], (opt.state[si][k] for k in "pmveo"))):
         assert torch.equal(bits(old[off:off + p.numel()]), bits(s[off:off + p.numel()])), ("the matrix with the bent work entry", k)
-    q, sj, offq, _ = opt._plist[next(i for i, x in enumerate(opt.params) if tuple(x.shape) == (200, 87))]
+    q, sj, offq = next((r.p, r.bucket, r.off) for r in opt._recs if tuple(r.p.shape) == (200, 87))
     assert not torch.equal(before[sj][0][offq:offq + q.numel()], opt.state[sj]["p"][offq:offq + q.numel()])      # the others took their step

@@ -97,7 +97,7 @@ def block_bits(opt):
 def snapshot(opt):
     """every range's arrays as the device holds them now, in table order, and the Prodigy block"""
     ranges = []
-    for (p, si, off, lr0), wd in zip(opt._plist, opt._wds):
+    for p, si, off, lr0, wd in ((r.p, r.bucket, r.off, r.lr0, r.wd) for r in opt._recs):
         s, n = opt.state[si], p.numel()
         r = {k: s[k][off:off + n].cpu().numpy().copy() for k in ("p", "g", "m", "v", "s", "x0") + (("e",) if "e" in s else ())}
         r["lr"], r["wd"] = lr0 * opt.decay, wd
@@ -401,12 +401,12 @@ def test_a_launch_that_does_not_match_touches_nothing():
                                         bent.data_ptr(), opt._prodigy_s_ptrs.data_ptr(), cm.C.byref(opt._prodigy_c),
                                         opt._prodigy_block.data_ptr(), opt._prodigy_ws.data_ptr()), "avmoe_opt_prodigy_step")
     torch.cuda.synchronize()
-    p, si, off, _lr0 = opt._plist[victim]
+    p, si, off = opt._recs[victim].p, opt._recs[victim].bucket, opt._recs[victim].off
     for k, old in zip("pmvse", before[si]):
         assert torch.equal(bits(old[off:off + p.numel()]), bits(opt.state[si][k][off:off + p.numel()])), ("the range with the bent x0 entry", k)
     assert not torch.equal(before[1 - si][0], opt.state[1 - si]["p"])    # the other ranges took their step
     sums = sums_of(opt)
-    first = sum((q.numel() + 1023) // 1024 for q, _si, _off, _lr in opt._plist[:victim])
+    first = sum((q.numel() + 1023) // 1024 for q in opt.params[:victim])
     assert not sums[first:first + 3].any() and sums[:first, 1].all() and not torch.equal(blk, block_bits(opt))
 
 

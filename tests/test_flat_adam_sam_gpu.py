@@ -63,7 +63,7 @@ def assert_state_blocks_equal(oa, ob, what=""):
 
 
 def hold_views(opt):
-    return [opt.state[si]["h"][off:off + p.numel()].view_as(p) for p, si, off, _lr0 in opt._plist]
+    return [r.view("h") for r in opt._recs]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
