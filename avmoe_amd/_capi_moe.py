@@ -105,6 +105,17 @@ class OptMuonLayout(C.Structure):
     _fields_ = [("table_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t), ("report_bytes", C.c_size_t)]
 
 
+class OptMuonLargeLayout(C.Structure):
+    """avmoe_opt_muon_large_layout: the bytes of the large-matrix image, the staging workspace and the report; the class count"""
+    _fields_ = [("table_bytes", C.c_size_t), ("workspace_bytes", C.c_size_t), ("report_bytes", C.c_size_t), ("n_classes", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class OptMuonClass(C.Structure):
+    """avmoe_opt_muon_class: one class of equal-shaped large matrices after orientation (d = the short side)"""
+    _fields_ = [("d", C.c_int32), ("L", C.c_int32), ("count", C.c_int32), ("ksplit", C.c_int32)]
+
+
 # avmoe_opt_prodigy_state: field -> (byte offset, torch dtype name); 32 bytes
 OPT_PRODIGY_FIELDS = {"d": (0, "float32"), "d_max": (4, "float32"), "d_hat": (8, "float32"), "num": (16, "float64"), "den": (24, "float64")}
 
@@ -256,6 +267,19 @@ def declare(L):
             L.avmoe_opt_muon_step.argtypes = step_args + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.POINTER(OptMuon), C.c_void_p, C.c_void_p]
             L.avmoe_opt_muon_ns.restype = C.c_int
             L.avmoe_opt_muon_ns.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        if hasattr(L, "avmoe_opt_muon_step_large"):   # (found by symbol: orthogonalised momentum for the large matrices)
+            L.avmoe_opt_muon_large_bytes.restype = C.c_size_t
+            L.avmoe_opt_muon_large_bytes.argtypes = [C.c_int32, C.POINTER(OptMuonMat), C.c_int32, C.POINTER(OptMuonLargeLayout)]
+            L.avmoe_opt_muon_large_table_build.restype = C.c_int
+            L.avmoe_opt_muon_large_table_build.argtypes = [C.POINTER(OptRange), C.c_int32, C.POINTER(OptMuonMat), C.c_int32, C.POINTER(OptMuonMat),
+                                                           C.c_int32, C.c_void_p, C.c_size_t]
+            L.avmoe_opt_muon_large_classes.restype = C.c_int
+            L.avmoe_opt_muon_large_classes.argtypes = [C.c_void_p, C.POINTER(OptMuonClass), C.c_int32, C.POINTER(C.c_int32)]
+            L.avmoe_opt_muon_step_large.restype = C.c_int
+            # ... avmoe_opt_muon_step's, then the large image (DEVICE, HOST), n_large, the large workspace and report
+            L.avmoe_opt_muon_step_large.argtypes = L.avmoe_opt_muon_step.argtypes + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+            L.avmoe_opt_muon_ns_large.restype = C.c_int
+            L.avmoe_opt_muon_ns_large.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     if hasattr(L, "avmoe_opt_swap_buffers"):         # (found by symbol: the averaged buffers)
         L.avmoe_opt_buffer_table_bytes.restype = C.c_size_t
         L.avmoe_opt_buffer_table_bytes.argtypes = [C.POINTER(OptBuffer), C.c_int32, C.POINTER(C.c_int64)]

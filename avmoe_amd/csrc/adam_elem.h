@@ -237,4 +237,12 @@ __device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __
   }
 }
 
+// Orthogonalised momentum (include/avmoe.h, avmoe_opt_muon_step): the parameter's new value from the finished direction O, written ONCE for
+// kk_opt_muon_ns (opt_muon.hip) and kk_opt_muon_large_apply (opt_muon_large.hip): decay (decoupled), then p - step * O with step = lr * s; as lamb_next
+__device__ __forceinline__ float muon_next(float p, float o, float lr, float wd, float step, bool decoupled) {
+#pragma clang fp contract(off)
+  if (decoupled) p *= 1.f - lr * wd;
+  return p - step * o;
+}
+
 }  // namespace avmoe

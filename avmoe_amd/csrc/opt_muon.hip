@@ -3,7 +3,8 @@
 //   kk_opt_muon_update<DECOUPLED, SCHED, EMA, HOLD>   one block per table block (the table walk of opt_table.h).  A range that is not
 //                                          listed: adam_quad with kk_opt_adam's arguments, so kk_opt_adam's bits.  A listed range: the
 //                                          momentum m (into exp_avg), the direction u into the range's slice of the work buffer, and the
-//                                          block's sum of (double)u^2
+//                                          block's sum of (double)u^2.  Listed: in the image's map, or in the second map that
+//                                          avmoe_opt_muon_step_large (opt_muon_large.hip) hands in for the large matrices
 //   kk_opt_muon_ns<STEP>                   one workgroup per matrix: ||u||_F from the block sums in a fixed order, then the Newton-Schulz
 //                                          iteration in place in the work buffer, then (STEP) decay and update of the parameter
 // The first optimizer kernel here whose hot path is matrix-shaped.  With Y the d x L view of a matrix (d = its short side <= 128):
@@ -68,18 +69,12 @@ __device__ __forceinline__ float muon_elem(float p, float& m, float g, float mu,
   return nesterov ? __builtin_fmaf(mu, m, t) : m;
 }
 
-// the parameter's new value from the finished direction O: decay (DECOUPLED), then p - step * O with step = lr * s; as lamb_next
-__device__ __forceinline__ float muon_next(float p, float o, float lr, float wd, float step, bool decoupled) {
-#pragma clang fp contract(off)
-  if (decoupled) p *= 1.f - lr * wd;
-  return p - step * o;
-}
-
 template <bool DECOUPLED, bool SCHED, bool EMA, bool HOLD>
 __global__ void __launch_bounds__(256) kk_opt_muon_update(const void* __restrict__ table, const avmoe_opt_state* __restrict__ state, float b1, float b2,
                                                           float eps, float grad_scale, float* const* __restrict__ shadows,
                                                           float* const* __restrict__ hold, int n_ranges, const void* __restrict__ image, int n_mats,
-                                                          float* const* __restrict__ work, float mu, int nesterov, double* __restrict__ sums) {
+                                                          float* const* __restrict__ work, float mu, int nesterov, double* __restrict__ sums,
+                                                          const void* __restrict__ large, int n_large) {
   const bool skip = state->skip != 0;
   if constexpr (!HOLD) {
     if (skip) return;
@@ -90,7 +85,12 @@ __global__ void __launch_bounds__(256) kk_opt_muon_update(const void* __restrict
   if (w.range < 0 || w.n_ranges != n_ranges) return;      // block-uniform from here on
   const MuonHeader mh = *(const MuonHeader*)image;
   if (mh.magic != MUON_MAGIC || mh.n_mats != n_mats || mh.n_ranges != n_ranges) return;
-  const int mat = ((const int32_t*)((const avmoe_opt_muon_mat*)((const char*)image + sizeof(MuonHeader)) + n_mats))[w.range];
+  int mat = ((const int32_t*)((const avmoe_opt_muon_mat*)((const char*)image + sizeof(MuonHeader)) + n_mats))[w.range];
+  if (large) {                                            // avmoe_opt_muon_step_large: a range of the large image's map is listed too
+    const int32_t* large_map = muonl_map(large, n_large, n_ranges);
+    if (!large_map) return;
+    if (mat < 0) mat = large_map[w.range];
+  }
   const avmoe_opt_range& r = w.r;
   const float* h = nullptr;
   if constexpr (HOLD) {
@@ -188,6 +188,8 @@ struct MuonStep {
   long n_blocks;
   int n_ranges;
   int decoupled, sched, ema, with_hold, scale;
+  const void* large;              // avmoe_opt_muon_step_large: the image of n_large large matrices the table walk has checked, else NULL
+  int n_large;
 };
 
 // One workgroup of 512 threads per matrix (see the head of this file).  STEP: the norm from launch 1's block sums, the report, and in
@@ -199,6 +201,7 @@ __global__ void __launch_bounds__(MUON_THREADS) kk_opt_muon_ns(const void* __res
   extern __shared__ __align__(16) float lds[];
   if constexpr (STEP) {
     if (sa.state->skip) return;
+    if (sa.large && !muonl_map(sa.large, sa.n_large, sa.n_ranges)) return;      // the table walk has left no u and no sums then
   }
   const MuonHeader mh = *(const MuonHeader*)image;
   if (mh.magic != MUON_MAGIC || mh.n_mats != n_mats || (int)gridDim.x != n_mats) return;
@@ -481,6 +484,52 @@ static int check_muon_args(const char* who, const void* mats, int32_t n_mats, fl
 
 static LdsAttrOnce g_muon_lds_step, g_muon_lds_ns;
 
+// avmoe_opt_muon_step in two halves (opt_table.h): avmoe_opt_muon_step_large makes its own checks between them
+int muon_step_check(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                    float eps, float grad_scale, int32_t flags, float* const* shadows, float* const* hold, const void* mats, int32_t n_mats,
+                    float* const* work, const avmoe_opt_muon* consts, const double* workspace, const void* report) {
+  const bool with_hold = hold != nullptr;
+  AVMOE_TRY(check_step_args(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, OPT_STEP_FLAGS, shadows, with_hold, hold));
+  if (!consts) { set_last_error("%s: the constants are NULL", who); return ERR_BAD_ARG; }
+  if (!workspace) { set_last_error("%s: the workspace is NULL", who); return ERR_BAD_ARG; }
+  if (!report) { set_last_error("%s: the report buffer is NULL", who); return ERR_BAD_ARG; }
+  AVMOE_TRY(check_muon_args(who, mats, n_mats, work, consts->ns_steps));
+  if (!(consts->momentum >= 0.f && consts->momentum < 1.f)) { set_last_error("%s: momentum must be in [0, 1)", who); return ERR_BAD_ARG; }
+  if (consts->nesterov != 0 && consts->nesterov != 1) { set_last_error("%s: nesterov must be 0 or 1, not %d", who, (int)consts->nesterov); return ERR_BAD_ARG; }
+  if (consts->scale != AVMOE_MUON_SCALE_MATCH_RMS_ADAMW && consts->scale != AVMOE_MUON_SCALE_ORIGINAL) {
+    set_last_error("%s: unknown scale %d", who, (int)consts->scale); return ERR_BAD_ARG;
+  }
+  if (((uintptr_t)workspace & 7u) != 0) { set_last_error("%s: the workspace must be 8-byte aligned", who); return ERR_ALIGNMENT; }
+  if (((uintptr_t)report & 15u) != 0) { set_last_error("%s: the report buffer must be 16-byte aligned", who); return ERR_ALIGNMENT; }
+  return OK;
+}
+
+int muon_step_launch(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                     float eps, float grad_scale, int32_t flags, hipStream_t stream, float* const* shadows, float* const* hold, const void* mats,
+                     int32_t n_mats, float* const* work, const avmoe_opt_muon* consts, double* workspace, void* report, const void* large,
+                     int32_t n_large) {
+  const bool with_hold = hold != nullptr;
+  const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
+  if (n_mats > 0) AVMOE_TRY(g_muon_lds_step.ensure((const void*)kk_opt_muon_ns<true>, MUON_LDS_BYTES, who));
+  if (n_blocks > 0) {
+    hipLaunchKernelGGL(OPT_MUON[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
+                       stream, table, state, beta1, beta2, eps, grad_scale, ema ? shadows : nullptr, hold, (int)n_ranges, mats, (int)n_mats,
+                       work, consts->momentum, (int)consts->nesterov, workspace, large, (int)n_large);
+    AVMOE_CHECK_LAUNCH("opt_muon_update");
+  }
+  if (n_mats > 0 && n_blocks > 0) {
+    MuonStep sa;
+    sa.table = table; sa.state = state; sa.sums = workspace; sa.shadows = ema ? shadows : nullptr; sa.hold = hold; sa.report = report;
+    sa.n_blocks = (long)n_blocks; sa.n_ranges = (int)n_ranges;
+    sa.decoupled = (int)dec; sa.sched = (int)sched; sa.ema = (int)ema; sa.with_hold = (int)with_hold; sa.scale = (int)consts->scale;
+    sa.large = large; sa.n_large = (int)n_large;
+    hipLaunchKernelGGL(kk_opt_muon_ns<true>, dim3((unsigned)n_mats), dim3(MUON_THREADS), MUON_LDS_BYTES, stream, mats, (int)n_mats, work,
+                       (int)consts->ns_steps, sa);
+    AVMOE_CHECK_LAUNCH("opt_muon_ns");
+  }
+  return OK;
+}
+
 }  // namespace avmoe
 
 using namespace avmoe;
@@ -540,37 +589,10 @@ int avmoe_opt_muon_step(const void* table, int32_t n_ranges, int64_t n_blocks, c
                         float grad_scale, int32_t flags, void* stream, float* const* shadows, float* const* hold, const void* mats, int32_t n_mats,
                         float* const* work, const avmoe_opt_muon* consts, double* workspace, void* report) {
   const char* who = "avmoe_opt_muon_step";
-  const bool with_hold = hold != nullptr;
-  AVMOE_TRY(check_step_args(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, OPT_STEP_FLAGS, shadows, with_hold, hold));
-  if (!consts) { set_last_error("%s: the constants are NULL", who); return ERR_BAD_ARG; }
-  if (!workspace) { set_last_error("%s: the workspace is NULL", who); return ERR_BAD_ARG; }
-  if (!report) { set_last_error("%s: the report buffer is NULL", who); return ERR_BAD_ARG; }
-  AVMOE_TRY(check_muon_args(who, mats, n_mats, work, consts->ns_steps));
-  if (!(consts->momentum >= 0.f && consts->momentum < 1.f)) { set_last_error("%s: momentum must be in [0, 1)", who); return ERR_BAD_ARG; }
-  if (consts->nesterov != 0 && consts->nesterov != 1) { set_last_error("%s: nesterov must be 0 or 1, not %d", who, (int)consts->nesterov); return ERR_BAD_ARG; }
-  if (consts->scale != AVMOE_MUON_SCALE_MATCH_RMS_ADAMW && consts->scale != AVMOE_MUON_SCALE_ORIGINAL) {
-    set_last_error("%s: unknown scale %d", who, (int)consts->scale); return ERR_BAD_ARG;
-  }
-  if (((uintptr_t)workspace & 7u) != 0) { set_last_error("%s: the workspace must be 8-byte aligned", who); return ERR_ALIGNMENT; }
-  if (((uintptr_t)report & 15u) != 0) { set_last_error("%s: the report buffer must be 16-byte aligned", who); return ERR_ALIGNMENT; }
-  const bool dec = (flags & AVMOE_OPT_DECOUPLED_DECAY) != 0, sched = (flags & AVMOE_OPT_LR_SCHEDULE) != 0, ema = (flags & AVMOE_OPT_EMA) != 0;
-  if (n_mats > 0) AVMOE_TRY(g_muon_lds_step.ensure((const void*)kk_opt_muon_ns<true>, MUON_LDS_BYTES, who));
-  if (n_blocks > 0) {
-    hipLaunchKernelGGL(OPT_MUON[(int)dec | (int)sched << 1 | (int)ema << 2 | (int)with_hold << 3], dim3((unsigned)n_blocks), dim3(256), 0,
-                       (hipStream_t)stream, table, state, beta1, beta2, eps, grad_scale, ema ? shadows : nullptr, hold, (int)n_ranges, mats, (int)n_mats,
-                       work, consts->momentum, (int)consts->nesterov, workspace);
-    AVMOE_CHECK_LAUNCH("opt_muon_update");
-  }
-  if (n_mats > 0 && n_blocks > 0) {
-    MuonStep sa;
-    sa.table = table; sa.state = state; sa.sums = workspace; sa.shadows = ema ? shadows : nullptr; sa.hold = hold; sa.report = report;
-    sa.n_blocks = (long)n_blocks; sa.n_ranges = (int)n_ranges;
-    sa.decoupled = (int)dec; sa.sched = (int)sched; sa.ema = (int)ema; sa.with_hold = (int)with_hold; sa.scale = (int)consts->scale;
-    hipLaunchKernelGGL(kk_opt_muon_ns<true>, dim3((unsigned)n_mats), dim3(MUON_THREADS), MUON_LDS_BYTES, (hipStream_t)stream, mats, (int)n_mats, work,
-                       (int)consts->ns_steps, sa);
-    AVMOE_CHECK_LAUNCH("opt_muon_ns");
-  }
-  return OK;
+  AVMOE_TRY(muon_step_check(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, shadows, hold, mats, n_mats, work, consts,
+                            workspace, report));
+  return muon_step_launch(who, table, n_ranges, n_blocks, state, beta1, beta2, eps, grad_scale, flags, (hipStream_t)stream, shadows, hold, mats,
+                          n_mats, work, consts, workspace, report, nullptr, 0);
 }
 
 int avmoe_opt_muon_ns(const void* mats, int32_t n_mats, float* const* work, int32_t ns_steps, void* stream) {

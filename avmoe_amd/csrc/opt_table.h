@@ -79,4 +79,30 @@ int check_step_args(const char* who, const void* table, int32_t n_ranges, int64_
                     float beta2, float eps, float grad_scale, int32_t flags, int32_t known_flags, float* const* shadows, bool with_hold,
                     float* const* hold);
 
+// The head of the image avmoe_opt_muon_large_table_build writes (opt_muon_large.hip: header, n_mats matrices of 64 bytes, n_classes classes
+// of 64 bytes, then n_ranges int32: the large matrix of a range, or -1), here because the table walk of opt_muon.hip reads that map too.
+constexpr uint32_t MUONL_MAGIC = 0x4d554c47u;    // "MULG"
+constexpr size_t MUONL_MAT_BYTES = 64, MUONL_CLASS_BYTES = 64;
+struct MuonLargeHeader { uint32_t magic; int32_t n_mats, n_ranges, n_classes; int64_t sums_off, ws_bytes; };
+static_assert(sizeof(MuonLargeHeader) == 32, "large Muon image header");
+
+// the range -> matrix map of a large image, or NULL where the image is not one of n_mats matrices and n_ranges ranges
+__host__ __device__ inline const int32_t* muonl_map(const void* image, int n_mats, int n_ranges) {
+  const MuonLargeHeader h = *(const MuonLargeHeader*)image;
+  if (h.magic != MUONL_MAGIC || h.n_mats != n_mats || h.n_ranges != n_ranges || h.n_classes < 0) return nullptr;
+  return (const int32_t*)((const char*)image + sizeof(MuonLargeHeader) + (size_t)n_mats * MUONL_MAT_BYTES + (size_t)h.n_classes * MUONL_CLASS_BYTES);
+}
+
+// avmoe_opt_muon_step in two halves (opt_muon.hip), so that avmoe_opt_muon_step_large (opt_muon_large.hip) makes every check before its
+// first launch: what the call refuses, then the table walk and the one-workgroup-per-matrix kernel.  large (DEVICE, or NULL): the image
+// of n_large large matrices; the table walk treats the ranges of its map as listed too, and touches nothing where the image is not this
+// launch's.
+int muon_step_check(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                    float eps, float grad_scale, int32_t flags, float* const* shadows, float* const* hold, const void* mats, int32_t n_mats,
+                    float* const* work, const avmoe_opt_muon* consts, const double* workspace, const void* report);
+int muon_step_launch(const char* who, const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                     float eps, float grad_scale, int32_t flags, hipStream_t stream, float* const* shadows, float* const* hold, const void* mats,
+                     int32_t n_mats, float* const* work, const avmoe_opt_muon* consts, double* workspace, void* report, const void* large,
+                     int32_t n_large);
+
 }  // namespace avmoe

@@ -182,6 +182,7 @@ class _ParamRecord:
     wd: float                                            # its weight decay
     adapted: bool                                        # whether its step takes its trust ratio (trust_ratio)
     muon_shape: Optional[tuple]                          # (rows, cols) of an orthogonalised parameter, None for the others (muon)
+    muon_path: Optional[str]                             # "small": the one-workgroup kernel, "large": the tiled engine (muon_large), or None
     state: list = dataclasses.field(repr=False)          # FlatAdam.state itself: what view() and ptr() look the buffers up in
 
     def view(self, key: str) -> torch.Tensor:
@@ -395,8 +396,24 @@ class FlatAdam:
     `last_muon_norms` an fp32 DEVICE tensor of ||u||_F.  `state_dict()` keeps torch's format (exp_avg is the momentum) and carries the
     constants under "flat_adam"; a dict saved with the option does not load into an optimizer built without it (ValueError).  Under
     data parallelism the gradients agree on every rank after `red.finish()` and so does every step: no communication is added
-    (verified on one rank only).  NOT covered: a short side above 128, a matrix split across workgroups, the plain (non-device) path,
+    (verified on one rank only).  NOT covered here: a short side above 128 (`muon_large` below), a matrix split across workgroups, the plain (non-device) path,
     an iteration in bf16 and with it torch.optim.Muon's bits.
+
+    The large matrices.  `muon=True, muon_large=True` also orthogonalises what the small rule declines -- for its short side or for its
+    numel: every site's conv_adapter and fc, the "v1" attention projections, a 128 x 4096 matrix -- where min(rows, cols) <= 2048
+    (`MUON_LARGE_MAX_DIM`) and numel <= `muon_large_max_numel` (`muon_large_shape_of`, `muon_select_paths`; `muon_paths` says "small" |
+    "large" | None per parameter).  The small rule stays first and keeps its kernel and its bits; a group's "muon": True on a parameter
+    only the large path fits is accepted.  The rule is the one above, exactly; only the three products of an iteration differ: they run
+    on the library's tiled engine with fp32 operands in three-plane form (5.8e-9 relative per product; include/avmoe.h,
+    avmoe_opt_muon_step_large).  The matrices are grouped into classes of equal (short side, long side); one launch normalises and
+    packs all of them into a staging area that gives each class a uniform batch stride, three engine launches per class and iteration
+    run batched over the class, one launch applies decay, update and shadow: 2 + 1 + 3 * ns_steps * classes (+ the engine's split-K
+    reduces) + 1 launches behind the norm call (avmoe_opt_muon_step's two when no parameter is large), no allocation, no host
+    synchronisation, no step-dependent host scalar, capturable.  Clipping, skipping, both decays, schedule, averages, SAM and
+    `orthogonalized`, `muon_scales`, `last_muon_updates`, `last_muon_norms` cover large matrices like small ones.  `state_dict()`
+    carries "muon_large" and "muon_large_max_numel"; a dict saved with the option does not load into an optimizer built without it
+    (ValueError), one without it loads as before.  A library without the entry point raises AvmoeError.  The data-parallel statement
+    above holds unchanged (documented from the code, verified on one rank only).  NOT covered: a short side above 2048.
 
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
@@ -417,7 +434,7 @@ class FlatAdam:
                  trust_clip: Optional[float] = None, prodigy: bool = False, prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0,
                  prodigy_growth: Optional[float] = None, prodigy_safeguard_warmup: bool = False, muon: bool = False,
                  muon_momentum: float = 0.95, muon_nesterov: bool = True, muon_ns_steps: int = 5, muon_scale: str = "match_rms_adamw",
-                 muon_max_numel: int = 262144):
+                 muon_max_numel: int = 262144, muon_large: bool = False, muon_large_max_numel: int = 1 << 23):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -437,6 +454,9 @@ class FlatAdam:
         whose short side is at most 128 and whose numel is at most `muon_max_numel` steps along the nearest semi-orthogonal matrix of
         its momentum; muon_momentum in [0, 1) (held as fp32), muon_nesterov, muon_ns_steps in 1..16, muon_scale "match_rms_adamw" |
         "original" (ValueError for a bad value, for one given without `muon`, and for `muon` with `trust_ratio` or `prodigy`).
+        muon_large: also orthogonalise the matrices the small rule declines, on the tiled engine (class docstring, "The large
+        matrices"): short side at most 2048 and numel at most `muon_large_max_numel` (ValueError for a non-bool, without `muon`, for a
+        bad `muon_large_max_numel` or one given without `muon_large`).
         Any of the eleven selects the device path (class docstring); with all at their
         defaults step() is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
         and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
@@ -475,12 +495,13 @@ class FlatAdam:
             raise ValueError("prodigy and trust_ratio are two rules for the step size: choose one")
         self.muon, self.muon_momentum, self.muon_nesterov, self.muon_ns_steps, self.muon_scale, self.muon_max_numel = \
             self._check_muon(muon, muon_momentum, muon_nesterov, muon_ns_steps, muon_scale, muon_max_numel)
+        self.muon_large, self.muon_large_max_numel = self._check_muon_large(muon_large, muon_large_max_numel, self.muon)
         if self.muon and (self.trust_ratio or self.prodigy):
             raise ValueError("muon and trust_ratio / prodigy are different rules for the step: choose one")
         for grp in (param_groups or []):                 # before anything is touched
             if "trust_ratio" in grp and not isinstance(grp["trust_ratio"], bool):
                 raise ValueError(f"a parameter group's \"trust_ratio\" must be True or False, not {grp['trust_ratio']!r}")
-        self.muon_select([], param_groups, self.muon_max_numel)          # the groups' "muon" keys, likewise
+        self._muon_paths_of([], param_groups)            # the groups' "muon" keys, likewise
         self.report_grad_norms = bool(report_grad_norms)
         self._ebufs = self._collect_buffers(ema_buffers, reducer)      # [(name, tensor)]: the buffers averaged with the weights
         self._recs: List[_ParamRecord] = []              # one record per parameter, in the reducer's order
@@ -506,10 +527,10 @@ class FlatAdam:
                 if view.data_ptr() % 16:
                     raise capi.AvmoeError("FlatAdam: a re-pointed parameter is not 16-byte aligned (the GEMM engine needs "
                                           "aligned operands); build the reducer with aligned buckets (avmoe_amd.dp)")
+                path, shape = (self._muon_paths_of([p], param_groups)[0] or (None, None)) if self.muon else (None, None)
                 self._recs.append(_ParamRecord(
                     p=p, bucket=len(self.state), off=off, lr0=lr_of.get(id(p), float(lr)), wd=wd_of.get(id(p), weight_decay),
-                    adapted=adapt_of.get(id(p), p.dim() >= 2),
-                    muon_shape=self.muon_select([p], param_groups, self.muon_max_numel)[0] if self.muon else None, state=self.state))
+                    adapted=adapt_of.get(id(p), p.dim() >= 2), muon_shape=shape, muon_path=path, state=self.state))
             self.state.append(dict(p=flat_p, g=flat_g, m=torch.zeros_like(flat_g), v=torch.zeros_like(flat_g), ranges=None))
         if self._averaging:                              # the averages: the bucket's layout once more, padding zero
             self._add_side_buffer("e", clone=True)
@@ -908,6 +929,10 @@ class FlatAdam:
         if self.muon:
             entry, tail = L.avmoe_opt_muon_step, (hold, self._muon_image.data_ptr(), len(self._muon_order), self._muon_work_ptrs.data_ptr(),
                                                   C.byref(self._muon_c), self._muon_ws.data_ptr(), self._muon_report.data_ptr())
+            if self._muon_large_order:                   # only then: without a large matrix a step is avmoe_opt_muon_step's two launches
+                entry = L.avmoe_opt_muon_step_large
+                tail += (self._muon_large_image.data_ptr(), self._muon_large_host.data_ptr(), len(self._muon_large_order),
+                         self._muon_large_ws.data_ptr(), self._muon_large_report.data_ptr())
         elif self.prodigy:
             entry, tail = L.avmoe_opt_prodigy_step, (hold, self._prodigy_x0_ptrs.data_ptr(), self._prodigy_s_ptrs.data_ptr(),
                                                      C.byref(self._prodigy_c), self._prodigy_block.data_ptr(), self._prodigy_ws.data_ptr())
@@ -1156,6 +1181,7 @@ class FlatAdam:
 
     # ---- orthogonalised momentum (Muon) ---------------------------------------------------------------------------
     MUON_MAX_DIM = 128                                   # AVMOE_MUON_MAX_DIM: the short side one workgroup's LDS holds the Gram matrix of
+    MUON_LARGE_MAX_DIM = 2048                            # AVMOE_MUON_LARGE_MAX_DIM: the short side the engine path takes (muon_large)
     MUON_SCALES = ("match_rms_adamw", "original")        # AVMOE_MUON_SCALE_*
 
     @staticmethod
@@ -1210,6 +1236,67 @@ class FlatAdam:
         return [FlatAdam.muon_shape_of(p, muon_max_numel) if override.get(id(p), True) else None for p in params]
 
     @staticmethod
+    def _check_muon_large(on, max_numel, muon):
+        """-> (muon_large, muon_large_max_numel)"""
+        if not isinstance(on, bool):
+            raise ValueError(f"muon_large must be True or False, not {on!r}")
+        if isinstance(max_numel, bool) or not isinstance(max_numel, int) or max_numel < 1:
+            raise ValueError(f"muon_large_max_numel must be an integer >= 1, not {max_numel!r}")
+        if on and not muon:
+            raise ValueError("muon_large needs muon: it widens muon's selection to the large matrices")
+        if not on and max_numel != 1 << 23:
+            raise ValueError("muon_large_max_numel needs muon_large: there is no large matrix to orthogonalise")
+        return on, max_numel
+
+    @staticmethod
+    def muon_large_shape_of(p, max_numel: int = 1 << 23):
+        """(rows, cols) as which the engine path of `muon_large` orthogonalises a parameter -- rows = shape[0], cols = numel // rows -- or
+        None where it does not fit: dim() < 2, no elements, min(rows, cols) > 2048 or numel > max_numel.  The rule of the large path
+        alone: `muon_select_paths` asks the small rule first."""
+        if p.dim() < 2 or p.numel() == 0:
+            return None
+        rows = int(p.shape[0])
+        cols = p.numel() // rows
+        if min(rows, cols) > FlatAdam.MUON_LARGE_MAX_DIM or p.numel() > max_numel:
+            return None
+        return rows, cols
+
+    @staticmethod
+    def muon_select_paths(params, param_groups=None, muon_max_numel: int = 262144, muon_large: bool = False,
+                          muon_large_max_numel: int = 1 << 23) -> list:
+        """The selection of `muon=True, muon_large=...`, in `params` order: ("small", (rows, cols)) for a parameter the one-workgroup
+        kernel orthogonalises, ("large", (rows, cols)) for one the engine path does, None for one that takes Adam / AdamW.  The small
+        rule (`muon_shape_of`) comes first and keeps what it takes; with `muon_large` a parameter it declines -- for its short side or
+        for its numel -- goes to the large path where `muon_large_shape_of` fits.  A group's "muon": False switches its parameters
+        off, True insists: ValueError naming the parameter where neither rule fits.  Without `muon_large` this is `muon_select`."""
+        if not muon_large:
+            return [None if s is None else ("small", s) for s in FlatAdam.muon_select(params, param_groups, muon_max_numel)]
+
+        def path_of(p):
+            s = FlatAdam.muon_shape_of(p, muon_max_numel)
+            if s is not None:
+                return "small", s
+            s = FlatAdam.muon_large_shape_of(p, muon_large_max_numel)
+            return None if s is None else ("large", s)
+        override = {}
+        for gi, grp in enumerate(param_groups or []):
+            if "muon" not in grp:
+                continue
+            if not isinstance(grp["muon"], bool):
+                raise ValueError(f"a parameter group's \"muon\" must be True or False, not {grp['muon']!r}")
+            ps = grp["params"]
+            for k, p in enumerate([ps] if isinstance(ps, torch.Tensor) else ps):
+                if grp["muon"] and path_of(p) is None:
+                    raise ValueError(f"parameter group {gi} asks for muon on its parameter {k} of shape {tuple(p.shape)}, which does not fit: it "
+                                     f"needs dim() >= 2, a short side <= {FlatAdam.MUON_LARGE_MAX_DIM} and numel <= muon_large_max_numel = "
+                                     f"{muon_large_max_numel}")
+                override[id(p)] = grp["muon"]
+        return [path_of(p) if override.get(id(p), True) else None for p in params]
+
+    def _muon_paths_of(self, params, param_groups):
+        return self.muon_select_paths(params, param_groups, self.muon_max_numel, self.muon_large, self.muon_large_max_numel)
+
+    @staticmethod
     def muon_scale_of(rows: int, cols: int, scale: str = "match_rms_adamw") -> float:
         """the factor s on an orthogonalised parameter's rate, as the fp32 value kk_opt_muon_ns forms: 0.2 sqrt(max(rows, cols))
         ("match_rms_adamw": an Adam learning rate keeps its meaning) or sqrt(max(1, rows / cols)) ("original")"""
@@ -1225,12 +1312,17 @@ class FlatAdam:
         """state_dict(): constants only -- exp_avg IS the momentum, O and the norms are rewritten by every step"""
         extra.update(muon=True, muon_momentum=self.muon_momentum, muon_nesterov=self.muon_nesterov, muon_ns_steps=self.muon_ns_steps,
                      muon_scale=self.muon_scale, muon_max_numel=self.muon_max_numel)
+        if self.muon_large:
+            extra.update(muon_large=True, muon_large_max_numel=self.muon_large_max_numel)
 
     def _check_saved_muon(self, extra):
         """load_state_dict(): -> the saved (momentum, nesterov, ns_steps, scale), or None where the constructor's stay"""
         if extra.get("muon") is True and not self.muon:
             raise ValueError("the state dict was saved with muon (exp_avg of its matrices is a momentum with no second moment beside it), which "
                              "this optimizer was built without: build it with muon=True")
+        if extra.get("muon_large") is True and not self.muon_large:
+            raise ValueError("the state dict was saved with muon_large (exp_avg of its large matrices is a momentum with no second moment beside "
+                             "it), which this optimizer was built without: build it with muon=True, muon_large=True")
         if not (self.muon and extra.get("muon") is True):
             return None
         return self._check_muon(True, extra.get("muon_momentum", self.muon_momentum), extra.get("muon_nesterov", self.muon_nesterov),
@@ -1245,7 +1337,7 @@ class FlatAdam:
         """the matrix list (longest first, so that the long ones start first), its image on the device, one work pointer per range,
         the workspace of one double per table block and the report (header, then ||u||_F per matrix)"""
         L, n = self._lib_with("avmoe_opt_muon_step", "orthogonalised momentum"), len(self._recs)
-        order = [i for i, r in enumerate(self._recs) if r.muon_shape is not None]
+        order = [i for i, r in enumerate(self._recs) if r.muon_path == "small"]
         order.sort(key=lambda i: -self._recs[i].p.numel())            # (stable: equal sizes keep the parameters' order)
         self._muon_order = order
         mats = (cm.OptMuonMat * max(1, len(order)))()
@@ -1265,6 +1357,40 @@ class FlatAdam:
         self._muon_norms = self._muon_report[16:16 + 4 * len(order)].view(torch.float32)       # in the list's order
         self._muon_index = torch.tensor(order, dtype=torch.int64).to(self._dev)
         self._set_muon(self.muon_momentum, self.muon_nesterov, self.muon_ns_steps, self.muon_scale)
+        self._muon_large_order = []
+        if self.muon_large:
+            self._build_muon_large(mats, len(order))
+
+    def _build_muon_large(self, small, n_small):
+        """the large matrices (longest first), their image on the host and on the device (the step call shapes the engine's launches
+        from the host copy), the staging workspace and the report (header, then ||u||_F per large matrix)"""
+        L, n = self._lib_with("avmoe_opt_muon_step_large", "orthogonalised momentum for the large matrices"), len(self._recs)
+        order = [i for i, r in enumerate(self._recs) if r.muon_path == "large"]
+        order.sort(key=lambda i: -self._recs[i].p.numel())
+        if not order:
+            return
+        mats = (cm.OptMuonMat * len(order))()
+        for m, i in zip(mats, order):
+            m.range, (m.rows, m.cols) = i, self._recs[i].muon_shape
+        lay = cm.OptMuonLargeLayout()
+        if L.avmoe_opt_muon_large_bytes(n, mats, len(order), C.byref(lay)) == 0:
+            capi.check(-1, "avmoe_opt_muon_large_bytes")
+        img = torch.zeros(int(lay.table_bytes), dtype=torch.uint8)
+        capi.check(L.avmoe_opt_muon_large_table_build(self._opt_ranges(), n, mats, len(order), small, n_small, img.data_ptr(),
+                                                      int(lay.table_bytes)), "avmoe_opt_muon_large_table_build")
+        self._muon_large_host, self._muon_large_image = img, img.to(self._dev)
+        self._muon_large_ws = torch.zeros(int(lay.workspace_bytes), dtype=torch.uint8, device=self._dev)
+        self._muon_large_report = torch.zeros(int(lay.report_bytes), dtype=torch.uint8, device=self._dev)
+        self._muon_large_norms = self._muon_large_report[16:16 + 4 * len(order)].view(torch.float32)
+        self._muon_large_index = torch.tensor(order, dtype=torch.int64).to(self._dev)
+        self._muon_large_classes = int(lay.n_classes)
+        self._muon_large_order = order
+
+    @property
+    def muon_paths(self) -> list:
+        """host state, in `params` order: "small" for a parameter the one-workgroup kernel orthogonalises, "large" for one the engine
+        path does (`muon_large`), None for one that takes Adam / AdamW"""
+        return [r.muon_path for r in self._recs]
 
     @property
     def orthogonalized(self) -> List[bool]:
@@ -1293,6 +1419,8 @@ class FlatAdam:
         out = torch.zeros(len(self._recs), dtype=torch.float32, device=self._dev)
         if self._muon_order:
             out.index_copy_(0, self._muon_index, self._muon_norms)
+        if self._muon_large_order:
+            out.index_copy_(0, self._muon_large_index, self._muon_large_norms)
         return out
 
     # ---- the device path ------------------------------------------------------------------------------------------

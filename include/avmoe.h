@@ -835,7 +835,8 @@ int avmoe_opt_prodigy_step(const void* table, int32_t n_ranges, int64_t n_blocks
  * refuses (hold == NULL); AVMOE_ERR_BAD_ARG for NULL mats, work, consts, workspace or report, a negative n_mats, a momentum outside
  * [0, 1), nesterov not 0 / 1, ns_steps outside 1..16, an unknown scale; AVMOE_ERR_ALIGNMENT for an image or report that is not 16-byte
  * or a work pointer array or workspace that is not 8-byte aligned.
- * NOT covered: min(rows, cols) > 128, a matrix split across workgroups, an iteration in bf16.                                           */
+ * NOT covered by these calls: min(rows, cols) > 128 (avmoe_opt_muon_step_large below serves it), a matrix split across workgroups, an
+ * iteration in bf16.                                                                                                                    */
 #define AVMOE_MUON_MAX_DIM 128
 #define AVMOE_MUON_SCALE_MATCH_RMS_ADAMW 0
 #define AVMOE_MUON_SCALE_ORIGINAL 1
@@ -864,6 +865,83 @@ int avmoe_opt_muon_step(const void* table, int32_t n_ranges, int64_t n_blocks, c
                         float* const* work /* DEVICE */, const avmoe_opt_muon* consts /* HOST */, double* workspace /* DEVICE */,
                         void* report /* DEVICE, 16-byte aligned */);
 int avmoe_opt_muon_ns(const void* mats /* DEVICE: the image */, int32_t n_mats, float* const* work /* DEVICE */, int32_t ns_steps, void* stream);
+
+/* Muon for the LARGE matrices: a short side above AVMOE_MUON_MAX_DIM (or a numel the caller keeps from the one-workgroup kernel), up to
+ * AVMOE_MUON_LARGE_MAX_DIM (added under ABI 11; found by symbol; csrc/opt_muon_large.hip).  The rule is EXACTLY the one stated above for
+ * a listed range -- gr, m, u per element, ||u||_F from the block sums in double in a fixed order, Y0, the iteration, the scale with
+ * max(rows, cols), decay, update, shadow -- only the arithmetic of the three products differs: they run on the tiled engine
+ * (csrc/gemm.hip, launch_gemm) with fp32 operands in THREE-PLANE form (avmoe_gemm's fp32_planes = 3: every value as three bf16 planes,
+ * 5.8e-9 relative per product, fp32 accumulation).  That form and not v_mfma_f32_16x16x4_f32 because the engine's exact-fp32 tiles
+ * would need their compute unit to themselves (avmoe_moe_desc::shared_gpu) and the engine makes no whole-CU LDS request; its error
+ * is a fortieth of the fp32 rounding of the sums themselves.  A d x d Gram matrix at d = 768 is 2.4 MB: nothing of this path is
+ * LDS-resident.
+ * avmoe_opt_muon_large_table_build (HOST) checks the list -- range index, rows, cols >= 1, min(rows, cols) <= 2048, rows * cols == n of
+ * the range (where `ranges` is given), no range named twice, in this list or in `small` (the list the caller gave
+ * avmoe_opt_muon_table_build, or NULL) -- orients every matrix short side first (d = min(rows, cols), L = the other side) and groups
+ * the matrices into CLASSES of equal (d, L), in the order of first appearance.  The image: header, the matrices in the caller's order
+ * (with their class and slot), the classes (with their offsets into the workspace), a range -> matrix map.  The caller keeps the HOST
+ * image and copies it to DEVICE memory: the calls below take both, because the engine's launches are shaped on the host from the
+ * classes and a call that launches reads no device memory on the host.  avmoe_opt_muon_large_bytes returns image, workspace and
+ * report bytes (each a multiple of 16) and the class count; the workspace depends on the shapes, so the query takes the list.
+ * The workspace (DEVICE, 16-byte aligned, no initialisation needed) holds two constant vectors (a and b, 2048 floats each), the block
+ * sums of avmoe_opt_muon_ns_large, and per class two staging buffers Y (count x d4 x L4 floats: d4, L4 = d, L rounded up to 4, the
+ * padding rows and columns zero, which the iteration keeps zero, so the padding is exact), A and B (count x d x d4) and the slabs of a
+ * split-K Gram product.  Equal-shaped matrices of different sites lie at unrelated offsets in the flat buckets: the staging area is
+ * what gives the engine a uniform batch stride.
+ * avmoe_opt_muon_step_large is avmoe_opt_muon_step (same arguments, same checks, same bits for every range that is not large) plus:
+ *   1  kk_opt_muon_update, which treats the ranges of the large map as listed too (m, u into work[range], the block's sum of u^2)
+ *   2  kk_opt_muon_ns<STEP> over the small matrices (when n_mats > 0)
+ *   3  kk_opt_muon_large_pack<STEP>: one launch for all large matrices.  Every workgroup of a matrix adds the matrix's block sums in
+ *      the same fixed order (thread t blocks t, t + 256, ..., then a tree; no floating-point atomics), forms inv = fp32(1 / (||u||_F +
+ *      1e-7)), writes the norm to the report and Y0 = Y * inv into the first staging buffer (32 x 32 tiles through LDS, transposed on
+ *      the way for rows > cols), zeroes the padding of both staging buffers and of A and B, and writes the constant vectors
+ *   4  per class and iteration THREE engine launches, batched over the class:  A = Y Y^T (both operands K-major, M = N = d, K = L;
+ *      split-K with slabs from the workspace where L is long and the tiles are few: one reduce launch more);  B = c (A A^T) + b A
+ *      (A is symmetric; the b A term is the engine's row_scale * D epilogue with the constant vector b);  Y' = B Y + a Y into the
+ *      other staging buffer (Y the MN-major operand and D, row_scale the constant vector a)
+ *   5  kk_opt_muon_large_apply<DECOUPLED, SCHED, EMA, HOLD>: one launch for all large matrices.  It reads O from staging (transposing
+ *      back), writes O into work[range], decay and update on the parameter (read from hold[range] with hold != NULL) with muon_next of
+ *      csrc/adam_elem.h, and the shadow with ema_next
+ * -- 2 + 1 + 3 * ns_steps * classes (+ the engine's split-K reduces) + 1 launches (one less without small matrices), without an
+ * allocation, a host synchronisation or a host scalar that changes per step: it replays from a captured graph.  When state->skip is
+ * set launches 3 and 5 write nothing (launch 1 has written param = hold under hold != NULL, for every range); the engine launches of
+ * a skipped step run on the staging buffers and are harmless.  `large_report`: {n_large, 0, 0, 0}, then ||u||_F per large matrix as
+ * fp32, in the list's order.  A launch that does not match its image or table, or a matrix whose work / hold / shadow entry is not
+ * 16-byte aligned, touches nothing of that matrix.
+ * avmoe_opt_muon_ns_large is the iteration alone, for tests: on matrices already in the work buffers it takes the block sums itself
+ * (one launch more, sums in the workspace), packs, iterates and writes O back into the work buffers; no table, no parameter, no report.
+ * Errors of avmoe_opt_muon_large_table_build: AVMOE_ERR_BAD_ARG for NULL mats (with n_mats > 0) or image, negative counts, a range
+ * index outside [0, n_ranges), rows or cols < 1, min(rows, cols) > 2048, rows * cols != n of the range, a range named twice (either
+ * list); AVMOE_ERR_WORKSPACE for an image that is too small.  avmoe_opt_muon_table_build keeps refusing a short side above 128.
+ * Errors of the two launching calls (before any launch): everything avmoe_opt_muon_step refuses; AVMOE_ERR_BAD_ARG for a NULL large
+ * image (either copy), workspace or report, a negative n_large, a HOST image whose header does not say n_large matrices and n_ranges
+ * ranges; AVMOE_ERR_ALIGNMENT for a large image, workspace or report that is not 16-byte aligned; the engine's own status where it
+ * refuses a product.
+ * NOT covered: min(rows, cols) > 2048, an iteration in bf16.                                                                            */
+#define AVMOE_MUON_LARGE_MAX_DIM 2048
+
+typedef struct avmoe_opt_muon_large_layout { size_t table_bytes, workspace_bytes, report_bytes; int32_t n_classes, reserved; } avmoe_opt_muon_large_layout;
+
+/* one class of an image, as avmoe_opt_muon_large_classes reports it (tests, tools) */
+typedef struct avmoe_opt_muon_class { int32_t d, L, count, ksplit; } avmoe_opt_muon_class;
+
+size_t avmoe_opt_muon_large_bytes(int32_t n_ranges, const avmoe_opt_muon_mat* mats /* HOST */, int32_t n_mats,
+                                  avmoe_opt_muon_large_layout* layout /* HOST, or NULL */);
+int avmoe_opt_muon_large_table_build(const avmoe_opt_range* ranges /* HOST, or NULL */, int32_t n_ranges, const avmoe_opt_muon_mat* mats /* HOST */,
+                                     int32_t n_mats, const avmoe_opt_muon_mat* small /* HOST, or NULL */, int32_t n_small, void* image /* HOST */,
+                                     size_t image_bytes);
+/* the classes of a HOST image into out[0 .. cap) and the class of every matrix into cls_of[0 .. n_mats) (either may be NULL); returns
+ * the class count, or a negative status for an image that is not one */
+int avmoe_opt_muon_large_classes(const void* image /* HOST */, avmoe_opt_muon_class* out, int32_t cap, int32_t* cls_of);
+int avmoe_opt_muon_step_large(const void* table, int32_t n_ranges, int64_t n_blocks, const avmoe_opt_state* state, float beta1, float beta2,
+                              float eps, float grad_scale, int32_t flags, void* stream, float* const* shadows /* DEVICE, or NULL without AVMOE_OPT_EMA */,
+                              float* const* hold /* DEVICE, or NULL */, const void* mats /* DEVICE: the small image */, int32_t n_mats,
+                              float* const* work /* DEVICE */, const avmoe_opt_muon* consts /* HOST */, double* workspace /* DEVICE */,
+                              void* report /* DEVICE, 16-byte aligned */, const void* large /* DEVICE: the large image */,
+                              const void* large_host /* HOST: the same image */, int32_t n_large, void* large_workspace /* DEVICE, 16-byte aligned */,
+                              void* large_report /* DEVICE, 16-byte aligned */);
+int avmoe_opt_muon_ns_large(const void* large /* DEVICE: the large image */, const void* large_host /* HOST: the same image */, int32_t n_large,
+                            float* const* work /* DEVICE */, int32_t ns_steps, void* large_workspace /* DEVICE, 16-byte aligned */, void* stream);
 
 /* ---- test hooks (ABI 11; process-wide; tests and bench.py's parity leg only) ---------------------------
  * The streaming kernels (csrc/dpost_pair.hip, tok_pair2.hip, hop1_stream.hip) serve sites from 32 768 tokens on; below that the

@@ -38,7 +38,11 @@
                    update) in place of the one update launch: 4 per step.  The alternative to --lamb / --prodigy; combines with
                    --schedule, --ema, --swa, --report, --sam.  Time it with --per-step-events: `step_seg_median_us` is the median of the
                    event pairs around every step()
---model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py
+--muon-large       (with --muon) FlatAdam(muon=True, muon_large=True): the matrices the small rule declines go through the tiled engine --
+                   2 + 1 + 3 * ns_steps * classes (+ split-K reduces) + 1 launches in place of the one update launch
+--model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py ;
+        wide_site  one AVE MoEAdapter at Swin-L / HTS-AT widths (C = 768, 196 x 1024 tokens, a 768-wide other modality), parameters as
+                   plain ranges: conv_adapter is 196 x 1024 and fc 768 x 768, the matrices only --muon-large orthogonalises
 
 The gradients are random values written into the buckets once (no backward: the trace holds the optimizer's launches only).  Prints one
 JSON line: launches per step are the trace's calls / steps; `step_us` is the event-timed mean of --steps steps enqueued back to back,
@@ -58,6 +62,14 @@ import torch  # noqa: E402
 
 def build(model_name, dev):
     from avmoe_amd.adapters import MoEAdapter
+    if model_name == "wide_site":
+        from tests.golden_util import load_golden
+        from tests.test_adapters_api import _opt
+        _, cfg, _ = load_golden("ave_train")
+        torch.manual_seed(11)
+        m = MoEAdapter(input_dim=768, output_dim=768, adapter_kind="bottleneck", dim_list=None, layer_idx=0, opt=_opt(cfg), conv_dim_in=1024,
+                       conv_dim_out=196, linear_in=768, linear_out=768, reduction_factor=8, use_bn=True, use_gate=True, num_tk=87).to(dev)
+        return [p for p in m.parameters() if p.requires_grad], None, m
     if model_name == "two_bucket":
         from tests.test_flat_adam_device_gpu import make_model
         m = make_model(dev)
@@ -72,7 +84,7 @@ def build(model_name, dev):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=["two_bucket", "eight_site"], default="eight_site")
+    ap.add_argument("--model", choices=["two_bucket", "eight_site", "wide_site"], default="eight_site")
     ap.add_argument("--mode", choices=["device", "clip_plain"], default="device")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
@@ -92,6 +104,7 @@ def main():
     ap.add_argument("--prodigy", action="store_true")
     ap.add_argument("--adamw", action="store_true")
     ap.add_argument("--muon", action="store_true")
+    ap.add_argument("--muon-large", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -123,13 +136,15 @@ def main():
         ap.error("--prodigy goes with --mode device and is the alternative to --lamb")
     if a.muon and (a.mode != "device" or a.lamb or a.prodigy):
         ap.error("--muon goes with --mode device and is the alternative to --lamb / --prodigy")
+    if a.muon_large and not a.muon:
+        ap.error("--muon-large goes with --muon")
     if a.adamw and a.mode != "device":
         ap.error("--adamw goes with --mode device")
     from avmoe_amd.dp import AdapterGradReducer
     from avmoe_amd.train import FlatAdam, LRSchedule
     dev = torch.device("cuda:0")
     params, sites, model = build(a.model, dev)
-    red = AdapterGradReducer(params, sites=sites)
+    red = AdapterGradReducer(params, sites=sites) if sites is not None else AdapterGradReducer(params)
     kw = dict(max_grad_norm=1.0, skip_nonfinite=True) if a.mode == "device" else {}
     total = a.warmup + a.steps
     sched = None
@@ -162,6 +177,8 @@ def main():
         kw.update(decoupled_weight_decay=True)
     if a.muon:
         kw.update(muon=True)
+    if a.muon_large:
+        kw.update(muon_large=True)
     opt = FlatAdam(red, lr=1.0 if a.prodigy else 1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
@@ -274,6 +291,9 @@ def main():
         extra["largest_matrix"] = list(max(shapes, key=lambda sh: sh[0] * sh[1]))
         extra["widest_short_side"] = max(min(sh) for sh in shapes)
         extra["muon_norm_min"] = float(opt.last_muon_norms[opt._muon_index].min().item())
+    if a.muon_large:
+        extra["large_matrices"] = [list(r.muon_shape) for r in opt._recs if r.muon_path == "large"]
+        extra["large_classes"] = getattr(opt, "_muon_large_classes", 0)
     if a.adamw or a.muon:
         extra["decay"] = "decoupled"
     if a.report:
