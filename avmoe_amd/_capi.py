@@ -26,6 +26,19 @@ class GemmDesc(C.Structure):
                                          "sRS1", "sRS2", "sDi", "sD1", "sD2")]
 
 
+class GemmFormSeg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("K", "a_layout", "b_layout", "reserved")] + \
+               [(n, C.c_int64) for n in ("lda", "ldb", "sA1", "sA2", "sB1", "sB2")]
+
+
+class GemmFormDesc(C.Structure):
+    """avmoe_gemm_form_desc (include/avmoe.h; tests only): avmoe_gemm_desc + third batch level, softmax epilogue, kept slabs, K segments 2 .. 4"""
+    _fields_ = [("base", GemmDesc)] + [(n, C.c_int32) for n in ("nb3", "epi", "keep_slabs", "reserved")] + \
+               [(n, C.c_int64) for n in ("sA3", "sB3", "sC3")] + [("seg", GemmFormSeg * 3)]
+
+
+EPI_NONE, EPI_ROWSTATS, EPI_EXP, EPI_MULSUB = 0, 1, 2, 3
+
 _lib = None
 
 
@@ -56,6 +69,11 @@ def lib():
     if hasattr(L, "avmoe_test_hooks"):          # (ABI 11; a development A/B may load an older library through AVMOE_LIB)
         L.avmoe_test_hooks.restype = C.c_uint32
         L.avmoe_test_hooks.argtypes = [C.c_uint32, C.c_int32]
+    if hasattr(L, "avmoe_gemm_form"):           # (found by symbol: the tiled engine's further forms on raw operands, tests only)
+        L.avmoe_gemm_form.restype = C.c_int
+        L.avmoe_gemm_form.argtypes = [C.POINTER(GemmFormDesc), C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4)] + [C.c_void_p] * 7
+        L.avmoe_gemm_row_lse.restype = C.c_int
+        L.avmoe_gemm_row_lse.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     from . import _capi_moe
     _capi_moe.declare(L)
     _lib = L

@@ -234,6 +234,29 @@ int avmoe_nxn_strip(int32_t op, const void* X, const void* dxr, int32_t frames, 
   }
 }
 
+// The tiled engine's further forms on raw operands (tests only): fills a GemmArgs from the descriptor and calls launch_gemm -- no arithmetic and
+// no check of its own beyond the NULL descriptor / pointer arrays; every refusal and status is the engine's.
+int avmoe_gemm_form(const avmoe_gemm_form_desc* desc, const void* const* A, const void* const* B, void* C, const float* row_scale, const void* D,
+                    void* workspace, float* row_part, const float* row_lse, void* stream) {
+  if (!desc || !A || !B) { set_last_error("avmoe_gemm_form: null desc or pointer array"); return ERR_BAD_ARG; }
+  GemmArgs a = to_args(&desc->base);
+  a.A = A[0]; a.B = B[0]; a.C = C; a.row_scale = row_scale; a.D = D; a.slabs = (float*)workspace;
+  a.nb3 = desc->nb3; a.sA3 = desc->sA3; a.sB3 = desc->sB3; a.sC3 = desc->sC3;
+  a.epi = desc->epi; a.keep_slabs = desc->keep_slabs; a.row_part = row_part; a.row_lse = row_lse;
+  for (int i = 0; i < 3; ++i) {
+    const avmoe_gemm_form_seg& s = desc->seg[i];
+    GemmSeg& g = a.seg[i];
+    g.A = A[i + 1]; g.B = B[i + 1]; g.K = s.K; g.a_layout = s.a_layout; g.b_layout = s.b_layout;
+    g.lda = s.lda; g.ldb = s.ldb; g.sA1 = s.sA1; g.sA2 = s.sA2; g.sB1 = s.sB1; g.sB2 = s.sB2;
+  }
+  return launch_gemm(a, (hipStream_t)stream);
+}
+
+int avmoe_gemm_row_lse(const float* row_part, int64_t rows, int32_t tiles, float* lse, void* stream) {
+  if (rows > 0 && (!row_part || !lse || tiles <= 0)) { set_last_error("avmoe_gemm_row_lse: null pointer or tiles <= 0"); return ERR_BAD_ARG; }
+  return gemm_row_lse(row_part, (long)rows, tiles, lse, (hipStream_t)stream);
+}
+
 void avmoe_prof_enable(int on) { prof_enable(on != 0); }
 void avmoe_prof_reset(void) { prof_reset(); }
 size_t avmoe_prof_report(char* buf, size_t cap) { return prof_report(buf, cap); }

@@ -1159,7 +1159,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream) {
   const int osz = d.out_bf16 ? 2 : 4;
   const int vecb = 4 * osz;    // bytes of a 4-element output vector
   d.vec_c = (a.sCj == 1) && (((uintptr_t)a.C) % vecb == 0) && ((a.sCi * osz) % vecb == 0) &&
-            ((a.sC1 * osz) % vecb == 0) && ((a.sC2 * osz) % vecb == 0);
+            ((a.sC1 * osz) % vecb == 0) && ((a.sC2 * osz) % vecb == 0) && (d.nb3 == 1 || (a.sC3 * osz) % vecb == 0);
   d.vec_d = a.D && (((uintptr_t)a.D) % (4 * esz) == 0) && ((a.sDi * esz) % (4 * esz) == 0) &&
             ((a.sD1 * esz) % (4 * esz) == 0) && ((a.sD2 * esz) % (4 * esz) == 0);
   const int bk = 256 / esz;          // (the longest K step of any instance)

@@ -973,6 +973,36 @@ enum { AVMOE_NXN_STATS = 0, AVMOE_NXN_ATT = 1, AVMOE_NXN_ATT_FROM_LSE = 2, AVMOE
 int avmoe_nxn_strip(int32_t op, const void* X, const void* dxr, int32_t frames, int32_t N, int32_t C, float* lse, float* rowdot, void* out,
                     const void* att_in, void* stream);
 
+/* avmoe_gemm_form / avmoe_gemm_row_lse (added under ABI 11; AVMOE_ABI_VERSION unchanged, a binding finds them by symbol; tests only) -- the
+ * forms of the tiled engine (csrc/gemm.hip, launch_gemm) that avmoe_gemm_desc has no field for, on raw operands, so that each can be checked
+ * alone against fp64 of its own operands (tests/test_engine_forms_fp64_gpu.py).  No site call goes through either.  They add no arithmetic:
+ * avmoe_gemm_form fills the engine's descriptor (csrc/gemm.h: GemmArgs) and calls launch_gemm, whose refusals and status codes come back
+ * unchanged (AVMOE_ERR_BAD_ARG of its own only for a NULL desc / A / B array).
+ *   base            the first K segment and everything avmoe_gemm takes (A[0], B[0] are its operands)
+ *   seg[0 .. 2]     the second, third and fourth K segment: K, both layouts, leading dimensions and the two batch strides of each; segment
+ *                   i + 1 is present when A[i + 1] / B[i + 1] are set (NULL otherwise), and the engine wants the one before it present
+ *   nb3, sA3 .. sC3 the third batch level: batch = nb1 * nb3 * nb2, b = (b1 * nb3 + b3) * nb2 + b2 (plain products only)
+ *   epi             AVMOE_GEMM_EPI_*: ROWSTATS writes row_part[((b * M + i) * tiles + t) * 2 + {0, 1}] = (max, sum of exp(v - max)) of column tile t
+ *                   (tiles = ceil(N / 128)) of v = alpha * (A B^T) and leaves C alone; EXP stores exp(v - row_lse[b * M + i]); MULSUB stores
+ *                   D * (v - row_lse[b * M + i]) (D without row_scale)
+ *   keep_slabs      split-K (base.ksplit > 1) whose fp32 partial sums stay in `workspace` as [ksplit][batch][M][N]; C is not written
+ * avmoe_gemm_row_lse: lse[r] = log sum_j exp(v[r][j]) from the (max, sum) parts of ROWSTATS, rows = batch * M (gemm_row_lse; rows <= 0:
+ * AVMOE_OK without a launch; AVMOE_ERR_BAD_ARG for a NULL pointer or tiles <= 0).                                                         */
+enum { AVMOE_GEMM_EPI_NONE = 0, AVMOE_GEMM_EPI_ROWSTATS = 1, AVMOE_GEMM_EPI_EXP = 2, AVMOE_GEMM_EPI_MULSUB = 3 };
+typedef struct avmoe_gemm_form_seg {
+  int32_t K, a_layout, b_layout, reserved;
+  int64_t lda, ldb, sA1, sA2, sB1, sB2;
+} avmoe_gemm_form_seg;
+typedef struct avmoe_gemm_form_desc {
+  avmoe_gemm_desc base;
+  int32_t nb3, epi, keep_slabs, reserved;
+  int64_t sA3, sB3, sC3;
+  avmoe_gemm_form_seg seg[3];
+} avmoe_gemm_form_desc;
+int avmoe_gemm_form(const avmoe_gemm_form_desc* desc, const void* const* A /* [4] */, const void* const* B /* [4] */, void* C,
+                    const float* row_scale, const void* D, void* workspace, float* row_part, const float* row_lse, void* stream);
+int avmoe_gemm_row_lse(const float* row_part, int64_t rows, int32_t tiles, float* lse, void* stream);
+
 /* ---- optional per-launch timing (HIP events on the launch stream; off by default; process-wide) --------
  * avmoe_prof_report writes a JSON array of {"name","calls","total_ms","alg_bytes","flops"} per kernel family
  * into buf (NUL-terminated, truncated to cap) and returns the full length.  Used by bench.py for the roofline. */
