@@ -1,52 +1,8 @@
-"""fp64 references and per-element bounds for the per-token bottleneck-space passes of the tuned shape (bottleneck 64 in 2 groups, 32 latent
-tokens): post_small, the post_small_bwd + mid_bwd composite and pre_small_bwd, in their three forms (csrc/tile_stream.hip kfs_*,
-csrc/tile_fast.hip kf_*<bf16>, kf_*<float>), which share one arithmetic.  In the style of tests/stream_product_ref.py, whose check_bound /
-EPS_* this module reuses: every function takes the operands AS STORED (bf16 and fp32 are exact in fp64) and returns (ref, bound) per output,
-
-    ref   = the formula of oracle/algebra_ref.py (forward :182-265, POST_SMALL backward :305-325, phase 3 :353-364, phase 4 :365-382)
-    bound = sum over the kernel's roundings of  eps_i * (magnitude of what that rounding rounds),  propagated to first order,
-
-the roundings counted from the kernel text (tile_fast.hip line numbers in the comments below; the streamed kernels repeat the same
-expressions: tile_stream.hip:676-700 / :296-370 / :530-550 / :1150-1199).  Unit roundoffs:
-
-    U32        2^-24   one fp32 operation (round to nearest); an fp32 division: hipcc compiles HIP device code with
-                       -fhip-fp32-correctly-rounded-divide-sqrt on by default (clang command-line reference), so `x / C` and `1.f / x` are
-                       correctly rounded
-    EPS_ACC    2^-23   per term of an fp32 sum of k terms in any order (stream_product_ref.py)
-    EPS_BF16   2^-8    a bf16 store
-    EPS_PLANES 2^-16   a two-plane mat-vec, bf16 forms only (tile_lane.h:113 mmT_split, tile_stream.hip:165 mm_presplit)
-    EPS_RSQRT  2^-22   rsqrtf: __clang_hip_math.h:671 maps it to __ocml_rsqrt_f32, which the ROCm device libraries build to the OpenCL C
-                       accuracy table (rsqrt: <= 2 ulp; an ulp of fp32 is 2^-23 relative)
-
-Nothing is fitted to a measured error.  Layouts here are token-major: Z-space tensors (NT, g, E, GD), per-token scalars (NT, E), per-column
-constants (g, E, GD), d x d matrices (g, E, GD, GD) indexed [k][c] as the kernels read them (W[c] = sum_k P[k] M[k][c], tile_lane.h:82).
-Works on CPU and GPU tensors alike.
-
-Every width comes from the operands: GD entries per group (the last axis of a Z-space tensor), g groups (1 when the plan merged them), Kp
-latent slots per expert (the last axis of a / L2) of which the first K are real (the side of TT), and the contraction lengths in the EPS_ACC
-terms (`_nsum`).  At the tuned shape (g = 2, GD = Kp = K = 32) every count below is the number it was when this module spelled 32.
-
-The same functions serve the other two links of every pass's form chain, the generalised register-resident kernels kg_* (csrc/tile_gen.inc,
-fp32 and bf16) and the any-shape kernels kt_* (csrc/tile_kernels.hip, Z-space tensors always fp32).  They were read against tile_fast.hip
-expression by expression; where they round differently the difference is named here, with its line, and is either inside a count the
-bound already carries or an argument of the function:
-    planes=False       kg_*<float> (tile_lane.h:143-147 mmT<.., false>) and every kt_* (tile_kernels.hip:40-47 tile_mm) run their mat-vecs on
-                       the exact-fp32 matrix pipe: no plane term.  kg_*<bf16>: mmT_split (tile_lane.h:113-128), an odd last chunk padded with
-                       zeros, EPS_PLANES as in the tuned forms.
-    order of the sums  tile_gen.inc:335-343 adds a lane's products over ALL groups and chunks before the fold over the four lanes (tile_fast
-                       folds per group); tile_kernels.hip:483-490 adds per column tile and folds over sixteen lanes.  The bounds count
-                       terms in ANY order (EPS_ACC per term), so neither needs a term of its own.
-    softmax            tile_gen.inc:603-614: padding slots contribute an exact 0 to the sum, `inv = 1.f / sum` then `ex * inv`, as tile_fast
-                       (two roundings, counted); tile_kernels.hip:304-314 evaluates __expf twice with the same argument (same value).
-                       The sum has K non-zero terms; Kp + 2 are counted.
-    1 / rr             tile_gen.inc:742,768 multiplies by irr = 1.f / rr (two roundings, as tile_fast); tile_kernels.hip:901 divides (one):
-                       three are counted for zc either way.
-    token sums         flush_cols (tile_gen.inc:93-99) folds the tile slots of an expert in LDS, flush_colacc (tile_kernels.hip:97-107) the
-                       waves of the block, before the block partial is written: a sum of NT terms has NT - 1 additions however it is
-                       bracketed, so the extra fold is inside colsum_ref's (NT + 2) EPS_ACC.  expert_scalar (tile_gen.inc:103-111) only
-                       feeds blkscal, which no per-token output reads.
-    rounds of experts  dL2x[:, KL] / rs2x add the experts round by round through dsxs (tile_gen.inc:822-831; tile_kernels.hip:929-930 expert by
-                       expert): still E terms in expert order, an fp32 partial in between (no extra rounding)."""
+"""tests/pass_ref.py as it stood while it spelled the tuned shape (32 entries per group, 2 groups, 32 latent tokens) as constants -- FDG = 32,
+2 * FDG + 3 and the like -- kept for ONE purpose: tests/test_gen_pass_checker.py::test_tuned_shape_refs_and_bounds_are_bit_identical runs
+every function of both modules on the operands of tests/test_pass_checker.py and asserts torch.equal on every ref and every bound, which
+is what lets tests/test_passes_fp64_gpu.py go on meaning what it meant after pass_ref.py began to take its widths from the operands.
+Nothing else imports this module; it is not to be edited (a change of a tuned-shape bound is made in pass_ref.py and shows there)."""
 import torch
 
 from tests.stream_product_ref import EPS_ACC, EPS_BF16, EPS_PLANES, ProductMismatch, check_bound
@@ -55,11 +11,7 @@ U32 = 2.0 ** -24
 EPS_RSQRT = 2.0 ** -22
 KINK = 2.0 ** -22          # |y_ref| <= KINK * (|z * scale| + |shift|): the ReLU may fall on either side
 KINK_CAP = 1e-5            # at most this share of a tensor's elements (expected ~1e-7: z is continuous at O(1))
-
-def _nsum(g, gd):
-    """terms of an fp32 sum over one token's g * gd bottleneck entries of an expert (in-lane partials, then the fold over the lanes that
-    hold the token): 2 * 32 at the tuned shape"""
-    return g * gd
+FDG = 32
 
 
 def _store(ref, pre, out_bf16):
@@ -79,12 +31,11 @@ def zprime(Z, bn1, relu):
 
 
 def matvec(zp, ezp, M, planes):
-    """w[t, g, e, c] = sum_k zp[t, g, e, k] M[g, e, k, c] on the matrix pipe: GD terms in fp32 (32 at the tuned shape), two bf16 planes in
-    the bf16 register-resident forms -> (w, mag, err)"""
+    """w[t, g, e, c] = sum_k zp[t, g, e, k] M[g, e, k, c] on the matrix pipe: 32 terms in fp32, two bf16 planes in the bf16 forms -> (w, mag, err)"""
     M = M.double()
     w = torch.einsum("tgek,gekc->tgec", zp, M)
     mag = torch.einsum("tgek,gekc->tgec", zp.abs(), M.abs())
-    err = torch.einsum("tgek,gekc->tgec", ezp, M.abs()) + (M.shape[-2] * EPS_ACC + (EPS_PLANES if planes else 0.0)) * mag
+    err = torch.einsum("tgek,gekc->tgec", ezp, M.abs()) + (FDG * EPS_ACC + (EPS_PLANES if planes else 0.0)) * mag
     return w, mag, err
 
 
@@ -95,16 +46,14 @@ def _first_order(r, evar, what):
 
 
 def post_small_ref(Z, bn1, Gq, us, vh, H1p, H2p, qv, relu, C, ln_eps, *, planes, out_bf16):
-    """tile_fast.hip:274-311 (tile_gen.inc:300-361, tile_kernels.hip:457-516).  Z (NT, g, E, GD); Gq (g, E, GD, GD); us, vh (g, E, GD);
-    H1p, H2p (g, E): the per-group parts the kernel adds (:256; tile_gen.inc:301); qv (NT, E) = probs * gate.
-    -> {"rp", "mup": (NT, E); "Apost": (NT, g, E, GD)}, each (ref, bound)"""
+    """tile_fast.hip:274-311.  Z (NT, g, E, 32); Gq (g, E, 32, 32); us, vh (g, E, 32); H1p, H2p (g, E): the per-group parts the kernel adds
+    (:256); qv (NT, E) = probs * gate.  -> {"rp", "mup": (NT, E); "Apost": (NT, g, E, 32)}, each (ref, bound)"""
     zp, ezp, _y, _ym, _k = zprime(Z, bn1, relu)
     us, vh, qv = us.double(), vh.double(), qv.double()
     w, wmag, ew = matvec(zp, ezp, Gq, planes)                                  # :288
     H1, H2 = H1p.double().sum(0), H2p.double().sum(0)
     H1m, H2m = H1p.double().abs().sum(0), H2p.double().abs().sum(0)
-    g = Z.shape[1]
-    k = _nsum(g, Z.shape[3]) + 1 + g                                         # the products (64 at the tuned shape), the fold of the lanes' partials, H (g parts)
+    k = 2 * FDG + 3                                                          # 64 products, the fold of the four lanes' partials, H (two parts)
     So = (zp * us).sum((1, 3)) + H1                                          # :293, :297
     So_mag = (zp.abs() * us.abs()).sum((1, 3)) + H1m
     eSo = (ezp * us.abs()).sum((1, 3)) + k * EPS_ACC * So_mag
@@ -138,19 +87,16 @@ def scalar_cols_ref(qv, rp, mup, *, out_bf16):
 
 def post_mid_bwd_ref(dAp, dApx, Z, bn1, Gq, us, vh, qv, rp, mup, dm, sdSzz, relu, C, *, planes, out_bf16):
     """post_small_bwd (tile_fast.hip:434-506) followed by mid_bwd (:133-161) as ONE map to the final dzp; the first pass's store of dz' is one
-    named rounding of the intermediate.  dAp (NT, g, E, GD); dApx (NT, g, E, 3); rp, mup (NT, E) as stored; dm = dsm[2] (g, E, GD).
-    The generalised kernels spell the same expressions (tile_gen.inc:451-458, :483-485, :254-255), the any-shape ones too
-    (tile_kernels.hip:663-670, :686-688, :781-782) but keep dz' in fp32 whatever the site's type (out_bf16=False there).
-    -> {"dSoo": (ref, bound) (NT, E); "dzp": (unmasked ref, bound, mask, kink) (NT, g, E, GD)}"""
+    named rounding of the intermediate.  dAp (NT, g, E, 32); dApx (NT, g, E, 3); rp, mup (NT, E) as stored; dm = dsm[2] (g, E, 32).
+    -> {"dSoo": (ref, bound) (NT, E); "dzp": (unmasked ref, bound, mask, kink) (NT, g, E, 32)}"""
     zp, ezp, y, _ym, kink = zprime(Z, bn1, relu)
     d, us, vh, qv, rp, mup, dm = dAp.double(), us.double(), vh.double(), qv.double(), rp.double(), mup.double(), dm.double()
-    g = Z.shape[1]
-    da = dApx.double().sum(1)                                                # :423 / :449: group 0 + group 1, one rounding (tile_gen.inc:444: g - 1 of them)
+    da = dApx.double().sum(1)                                                # :423 / :449: group 0 + group 1, one rounding
     dam = dApx.double().abs().sum(1)
-    eda = (g - 1) * U32 * dam
+    eda = U32 * dam
     zz = (d * zp).sum((1, 3))                                                # :457-458
     zzm = (d.abs() * zp.abs()).sum((1, 3))
-    ezz = (d.abs() * ezp).sum((1, 3)) + (_nsum(g, Z.shape[3]) + 2) * EPS_ACC * zzm
+    ezz = (d.abs() * ezp).sum((1, 3)) + (2 * FDG + 2) * EPS_ACC * zzm
     drp = qv * (zz + da[..., 0] - mup * da[..., 1])                          # :463: four products, two sums
     drpm = qv.abs() * (zzm + dam[..., 0] + mup.abs() * dam[..., 1])
     edrp = qv.abs() * (ezz + eda[..., 0] + mup.abs() * eda[..., 1]) + 6 * U32 * drpm
@@ -184,9 +130,9 @@ def post_mid_bwd_ref(dAp, dApx, Z, bn1, Gq, us, vh, qv, rp, mup, dm, sdSzz, relu
 
 
 def pre_small_bwd_ref(dy, Z, bn1, mdy, mdyz, rr, mu, wsum, dconst, C, *, out_bf16):
-    """tile_fast.hip:753-838, tile_gen.inc:740-831, tile_kernels.hip:876-931, :1012-1020 (training-mode BatchNorm-1, folded LayerNorm).
-    dy: the final dzp as stored (NT, g, E, GD); mdy, mdyz = dsm[3], dsm[4] (g, E, GD); rr, mu (NT, E) as stored; `zraw - mu wsum` is (z - dconst) / rr from the STORED z, as in the kernel (:770).
-    -> {"Zw": (NT, g, E, GD), "dzr": the same before its store (what the fused streamed pass hands to its hop-2 block); "dSx", "dSxx": (NT, E) (dslat holds the cross-modal experts' pair); "dL2x_KL", "rs2x": (NT,)}"""
+    """tile_fast.hip:753-838 (training-mode BatchNorm-1, folded LayerNorm).  dy: the final dzp as stored (NT, g, E, 32); mdy, mdyz = dsm[3],
+    dsm[4] (g, E, 32); rr, mu (NT, E) as stored; `zraw - mu wsum` is (z - dconst) / rr from the STORED z, as in the kernel (:770).
+    -> {"Zw": (NT, g, E, 32), "dzr": the same before its store (what the fused streamed pass hands to its hop-2 block); "dSx", "dSxx": (NT, E) (dslat holds the cross-modal experts' pair); "dL2x_KL", "rs2x": (NT,)}"""
     dy, z = dy.double(), Z.double()
     mean, rstd, sc = bn1[0].double(), bn1[1].double(), bn1[2].double()
     mdy, mdyz, ws, dc = mdy.double(), mdyz.double(), wsum.double(), dconst.double()
@@ -198,7 +144,7 @@ def pre_small_bwd_ref(dy, Z, bn1, mdy, mdyz, rr, mu, wsum, dconst, C, *, out_bf1
     edz = 6 * U32 * dzm
     zc = (z - dc) / rr                                                       # :747, :770: 1 / rr, the difference, the product
     ezc = 3 * U32 * zc.abs()
-    k = _nsum(Z.shape[1], Z.shape[3]) + 2
+    k = 2 * FDG + 2
     sdr = (dz * zc).sum((1, 3))                                              # :772, :800
     sdrm = (dzm * zc.abs()).sum((1, 3))
     esdr = (edz * zc.abs() + dzm * ezc).sum((1, 3)) + k * EPS_ACC * sdrm
@@ -287,53 +233,41 @@ EPS_EXP = 2.0 ** -23       # __expf(x) = __builtin_amdgcn_exp2f(log2e * x) (__cl
 TINY = 2.0 ** -126         # ... and it flushes a denormal result to zero
 
 
-def softmax_ref(L2, *, out_bf16, K=None):
-    """a = softmax over each latent slot's logits as stored (tile_fast.hip:592-613): max, __expf(l - max), the fp32 sum of Kp terms (32 at
-    the tuned shape), inv = 1 / sum, a = rnd_T(ex * inv).  L2 (NT, El, Kp).  K: the real latent tokens of a slot (default: all Kp); the
-    generalised kernels keep slots K..Kp out of the maximum and give them ex = 0 (tile_gen.inc:594, :603; tile_kernels.hip:301-317 never
-    visits them and stores 0, :318-320), so a is EXACTLY 0 there (bound 0) whatever the logits buffer holds.  -> (ref, bound)"""
-    Kp = L2.shape[-1]
-    lg = L2.double() if K is None or K == Kp else L2[..., :K].double()
+def softmax_ref(L2, *, out_bf16):
+    """a = softmax over each latent slot's 32 logits as stored (tile_fast.hip:592-613): max, __expf(l - max), the fp32 sum of 32 terms,
+    inv = 1 / sum, a = rnd_T(ex * inv).  L2 (NT, El, 32) -> (ref, bound)"""
+    lg = L2.double()
     x = lg - lg.max(-1, keepdim=True).values
     ex = torch.exp(x)
     rel = 3 * U32 * x.abs() + EPS_EXP
     eex = ex * rel + TINY
     sm = ex.sum(-1, keepdim=True)
-    esm = eex.sum(-1, keepdim=True) + (Kp + 2) * EPS_ACC * sm
+    esm = eex.sum(-1, keepdim=True) + (FDG + 2) * EPS_ACC * sm
     a = ex / sm
     pre = a * (rel + esm / sm + 2 * U32) + TINY / sm                         # 1 / sum and the product: two roundings
-    bound = _store(a, pre, out_bf16)
-    if lg.shape[-1] < Kp:
-        pad = torch.zeros(*a.shape[:-1], Kp - a.shape[-1], dtype=a.dtype, device=a.device)
-        a, bound = torch.cat([a, pad], -1), torch.cat([bound, pad], -1)
-    return a, bound
+    return a, _store(a, pre, out_bf16)
 
 
 def rmu_ref(sx, L2, a, TT, Tsum, gv, C, ln_eps, *, planes):
     """rmu = (rr, mu) of every expert (tile_fast.hip:572-637) from the stored row sums of X, the logits and a AS STORED (the kernel forms
-    u1, u2, u3 from the rounded a, :612-614).  sx (2, NT); L2, a (NT, El, Kp); TT (NT, El, K, K) -- the token's frame's -- or per frame
-    (S, El, K, K), K <= Kp the real latent tokens of a slot; Tsum (NT, El, Kp); gv (E,): the latent gate (gate_av / gate_self) of the experts
-    that own a latent slot, 0 for the others (the first El experts own the slots).  The generalised kernels index TT with the true K and
-    everything else with Kp (tile_gen.inc:527-535 stage_latent; tile_kernels.hip:269-278); slots K..Kp enter no sum (u2 is masked,
-    tile_gen.inc:617; tb and TT are staged as 0 there and a is exactly 0: softmax_ref), so the sums here run over the K real slots while
-    the term counts stay those of the Kp-wide loops.  -> {"rr", "mu": (ref, bound)}, each (NT, E)"""
+    u1, u2, u3 from the rounded a, :612-614).  sx (2, NT); L2, a (NT, El, 32); TT (NT, El, 32, 32) -- the token's frame's -- or per frame
+    (S, El, 32, 32); Tsum (NT, El, 32); gv (E,): gate_av of the cross-modal experts, 0 for the others (the first El experts own the latent slots).
+    -> {"rr", "mu": (ref, bound)}, each (NT, E)"""
     s0, s1, lg, a, TT, gv = sx[0].double(), sx[1].double(), L2.double(), a.double(), TT.double(), gv.double().to(sx.device)
-    NT, El, Kp, K = a.shape[0], a.shape[1], a.shape[2], TT.shape[-1]
+    NT, El = a.shape[0], a.shape[1]
     E = gv.shape[0]
     tb = Tsum.double() / C                                                   # :549: one rounding
-    if K < Kp:
-        a, lg, tb = a[..., :K], lg[..., :K], tb[..., :K]
-    k = (Kp + 2) * EPS_ACC
+    k = (FDG + 2) * EPS_ACC
     u1, u1m = (a * tb).sum(-1), (a * tb).abs().sum(-1)                       # :614
     eu1 = (k + U32) * u1m
     u2, u2m = (a * lg).sum(-1), (a * lg).abs().sum(-1)
     eu2 = k * u2m
     if TT.shape[0] == NT:                                                    # :621
         w, wm = torch.einsum("tlk,tlkn->tln", a, TT), torch.einsum("tlk,tlkn->tln", a.abs(), TT.abs())
-    else:                                                                    # per frame (S, El, K, K): tokens are frame-major
-        af = a.reshape(TT.shape[0], -1, El, K)
-        w, wm = torch.einsum("snlk,slkm->snlm", af, TT).reshape(NT, El, K), torch.einsum("snlk,slkm->snlm", af.abs(), TT.abs()).reshape(NT, El, K)
-    ew = (Kp * EPS_ACC + (EPS_PLANES if planes else 0.0)) * wm
+    else:                                                                    # per frame (S, El, 32, 32): tokens are frame-major
+        af = a.reshape(TT.shape[0], -1, El, FDG)
+        w, wm = torch.einsum("snlk,slkm->snlm", af, TT).reshape(NT, El, FDG), torch.einsum("snlk,slkm->snlm", af.abs(), TT.abs()).reshape(NT, El, FDG)
+    ew = (FDG * EPS_ACC + (EPS_PLANES if planes else 0.0)) * wm
     u3, u3m = (w * a).sum(-1), (wm * a.abs()).sum(-1)                        # :623
     eu3 = (a.abs() * ew).sum(-1) + k * u3m
     z = torch.zeros(NT, E - El, dtype=torch.float64, device=a.device)
@@ -356,29 +290,25 @@ def rmu_ref(sx, L2, a, TT, Tsum, gv, C, ln_eps, *, planes):
 
 
 def pre_lat_bwd_ref(a, L2, TT, TW, Tsum, gv, dzr, edzr, dSx, edSx, dSxx, edSxx, C, *, planes, out_bf16):
-    """dL2x[:, :KL], the hop-2 block of the experts with a latent slot (tile_fast.hip:924-974, tile_stream.hip:1219-1294, tile_gen.inc:886-950,
-    tile_kernels.hip:945-1010).  a, L2 (NT, El, Kp) as stored; TT (S, El, K, K), TW (S, El, Kp, g, GD): slot l's rows of TW in its expert's
-    columns, [k][group][entry]; Tsum (NT, El, Kp); gv (El,); dzr (NT, g, El, GD) and dSx, dSxx (NT, El) with their error bounds: the
-    register-resident forms read them back as stored (Zw, dslat: errors 0), the streamed and the any-shape form keep them in fp32 (registers /
-    the wave's LDS tile: pre_small_bwd_ref's values and bounds, Zw's without its store).  The padding slots K..Kp: every kernel writes them,
-    as zero (tile_gen.inc:931 leaves d = 0 and a is exactly 0 there, so :948 stores du2 * 0 + 0 * (0 - sada); tile_kernels.hip:1002-1007
-    stores a literal 0): reference 0, bound 0.  -> (ref, bound), (NT, El, Kp)"""
+    """dL2x[:, :KL], the hop-2 block of the cross-modal experts (tile_fast.hip:924-974, tile_stream.hip:1219-1294).  a, L2 (NT, El, 32) as
+    stored; TT (S, El, 32, 32), TW (S, El, 32, g, 32): slot l's rows of TW in expert l's columns, [k][group][entry]; Tsum (NT, El, 32);
+    gv (El,); dzr (NT, g, El, 32) and dSx, dSxx (NT, El) with their error bounds: the register-resident form reads them back as stored
+    (Zw, dslat: errors 0), the streamed form keeps them in fp32 registers (pre_small_bwd_ref's values and bounds, Zw's without its store).
+    -> (ref, bound), (NT, El, 32)"""
     a, lg, TT, TW, dzr = a.double(), L2.double(), TT.double(), TW.double(), dzr.double()
-    NT, El, Kp, K, GD = a.shape[0], a.shape[1], a.shape[2], TT.shape[-1], dzr.shape[-1]
+    NT, El = a.shape[0], a.shape[1]
     S = TT.shape[0]
     g = gv.double().to(a.device)[None]
     tb = Tsum.double() / C                                                   # :881 (:1222): one rounding
-    if K < Kp:
-        a, lg, tb, TW = a[..., :K], lg[..., :K], tb[..., :K], TW[:, :, :K]
     pl = EPS_PLANES if planes else 0.0
-    af = a.reshape(S, -1, El, K)
-    ta = torch.einsum("snlk,slkm->snlm", af, TT).reshape(NT, El, K)         # :946
-    tam = torch.einsum("snlk,slkm->snlm", af.abs(), TT.abs()).reshape(NT, El, K)
-    eta = (Kp * EPS_ACC + pl) * tam
-    df = dzr.reshape(S, -1, dzr.shape[1], El, GD)
-    twd = torch.einsum("slkic,snilc->snlk", TW, df).reshape(NT, El, K)      # :947: g * GD terms (64 at the tuned shape)
-    twdm = torch.einsum("slkic,snilc->snlk", TW.abs(), df.abs()).reshape(NT, El, K)
-    etwd = torch.einsum("slkic,snilc->snlk", TW.abs(), edzr.reshape(df.shape)).reshape(NT, El, K) + (_nsum(dzr.shape[1], GD) * EPS_ACC + pl) * twdm
+    af = a.reshape(S, -1, El, FDG)
+    ta = torch.einsum("snlk,slkm->snlm", af, TT).reshape(NT, El, FDG)       # :946
+    tam = torch.einsum("snlk,slkm->snlm", af.abs(), TT.abs()).reshape(NT, El, FDG)
+    eta = (FDG * EPS_ACC + pl) * tam
+    df = dzr.reshape(S, -1, dzr.shape[1], El, FDG)
+    twd = torch.einsum("slkic,snilc->snlk", TW, df).reshape(NT, El, FDG)    # :947: 64 terms
+    twdm = torch.einsum("slkic,snilc->snlk", TW.abs(), df.abs()).reshape(NT, El, FDG)
+    etwd = torch.einsum("slkic,snilc->snlk", TW.abs(), edzr.reshape(df.shape)).reshape(NT, El, FDG) + (2 * FDG * EPS_ACC + pl) * twdm
     du1, du2, du3 = dSx * g * C, 2 * g * dSxx, g * g * dSxx                  # :941
     edu1 = edSx * g.abs() * C + 2 * U32 * du1.abs()
     edu2 = 2 * g.abs() * edSxx + U32 * du2.abs()
@@ -389,15 +319,11 @@ def pre_lat_bwd_ref(a, L2, TT, TW, Tsum, gv, dzr, edzr, dSx, edSx, dSxx, edSxx, 
     ed = x(g.abs()) * etwd + x(edu1) * tb.abs() + U32 * (x(du1) * tb).abs() + x(edu2) * lg.abs() + 2 * x(edu3) * tam + 2 * x(du3.abs()) * eta + 8 * U32 * dm
     sada = (a * d).sum(-1, keepdim=True)                                     # :955, :961
     sadam = (a.abs() * dm).sum(-1, keepdim=True)
-    esada = (a.abs() * ed).sum(-1, keepdim=True) + (Kp + 2) * EPS_ACC * sadam
+    esada = (a.abs() * ed).sum(-1, keepdim=True) + (FDG + 2) * EPS_ACC * sadam
     v0 = x(du2) * a + a * (d - sada)                                         # :971: four roundings
     v0m = (x(du2) * a).abs() + a.abs() * (dm + sadam)
     pre = x(edu2) * a.abs() + a.abs() * (ed + esada) + 4 * U32 * v0m
-    bound = _store(v0, pre, out_bf16)
-    if K < Kp:
-        pad = torch.zeros(NT, El, Kp - K, dtype=v0.dtype, device=v0.device)
-        v0, bound = torch.cat([v0, pad], -1), torch.cat([bound, pad], -1)
-    return v0, bound
+    return v0, _store(v0, pre, out_bf16)
 
 
 def zprime_bf16(Z, bn1, relu):
