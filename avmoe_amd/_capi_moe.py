@@ -85,6 +85,16 @@ class OptProdigyState(C.Structure):
     _fields_ = [("d", C.c_float), ("d_max", C.c_float), ("d_hat", C.c_float), ("reserved", C.c_int32), ("num", C.c_double), ("den", C.c_double)]
 
 
+class OptSf(C.Structure):
+    """avmoe_opt_sf: the host constants of schedule-free AdamW (the averaging weight of step n is n^r * f_max^lr_power)"""
+    _fields_ = [("r", C.c_float), ("lr_power", C.c_float)]
+
+
+class OptSfState(C.Structure):
+    """avmoe_opt_sf_state: the 32-byte block avmoe_opt_sf_step's weights launch keeps on the device (all zero at the start)"""
+    _fields_ = [("weight_sum", C.c_double), ("f_max", C.c_float), ("c", C.c_float), ("d", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class OptProdigyLayout(C.Structure):
     """avmoe_opt_prodigy_layout: the bytes of avmoe_opt_prodigy_step's workspace and block"""
     _fields_ = [("workspace_bytes", C.c_size_t), ("block_bytes", C.c_size_t)]
@@ -118,6 +128,9 @@ class OptMuonClass(C.Structure):
 
 # avmoe_opt_prodigy_state: field -> (byte offset, torch dtype name); 32 bytes
 OPT_PRODIGY_FIELDS = {"d": (0, "float32"), "d_max": (4, "float32"), "d_hat": (8, "float32"), "num": (16, "float64"), "den": (24, "float64")}
+
+# avmoe_opt_sf_state: field -> (byte offset, torch dtype name); 32 bytes
+OPT_SF_FIELDS = {"weight_sum": (0, "float64"), "f_max": (8, "float32"), "c": (12, "float32"), "d": (16, "float32")}
 
 # avmoe_opt_state: field -> (byte offset, torch dtype name); 64 bytes
 OPT_STATE_BYTES = 64
@@ -257,6 +270,9 @@ def declare(L):
             L.avmoe_opt_prodigy_step.restype = C.c_int
             # shadows, hold, x0, s, consts (HOST), block, workspace
             L.avmoe_opt_prodigy_step.argtypes = step_args + [C.c_void_p] * 4 + [C.POINTER(OptProdigy), C.c_void_p, C.c_void_p]
+        if hasattr(L, "avmoe_opt_sf_step"):           # (found by symbol: schedule-free AdamW)
+            L.avmoe_opt_sf_step.restype = C.c_int
+            L.avmoe_opt_sf_step.argtypes = step_args + [C.c_void_p, C.c_void_p, C.POINTER(OptSf), C.c_void_p]      # x, hold, consts (HOST), block
         if hasattr(L, "avmoe_opt_muon_step"):         # (found by symbol: orthogonalised momentum)
             L.avmoe_opt_muon_bytes.restype = C.c_size_t
             L.avmoe_opt_muon_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.POINTER(OptMuonLayout)]

@@ -237,6 +237,60 @@ __device__ __forceinline__ void adam_quad(float* __restrict__ p, const float* __
   }
 }
 
+// Schedule-free AdamW (include/avmoe.h, avmoe_opt_sf_step).  What a thread reads once for all its elements: step = lr * lr_factor of its
+// range, d = 1 - c of this step from the 32-byte block, and the constants of the run.
+struct SfScal { float step, d, b1, b2, eps, wd, bc2_sqrt, gscale; };
+
+// One element of a step, written ONCE for the 16-byte body and the scalar tail of kk_opt_sf_update (sf_quad below).  y is the parameter
+// as the sites see it (the gradient was taken there), z the base sequence (it lives in exp_avg), x the average (the shadow).  Every
+// operation is rounded to fp32 in the order written, contraction off:
+//     gr = fma(gscale, g, wd * y)          (DECOUPLED: gr = g * gscale)
+//     v  = fma(b2, v, ((1 - b2) * gr) * gr)                                       -- adam_elem's spelling: Adam's bits for v from the same gr
+//     u  = gr / (sqrt(v) / bc2_sqrt + eps)                                        (DECOUPLED: u = u + wd * y)
+//     z  = z - step * u
+//     x  = fma(d, x, (1 - d) * z)                                                 -- ema_next: the average's own expression
+//     y  = fma(b1, x, (1 - b1) * z)
+// There is no momentum buffer and no first-moment bias correction: b1 is the interpolation.  d == 0 gives x == z and b1 == 0 gives
+// y == z, bit for bit.
+template <bool DECOUPLED>
+__device__ __forceinline__ void sf_elem(float& y, float& z, float& v, float& x, float g, const SfScal& k) {
+#pragma clang fp contract(off)
+  float gr;
+  if constexpr (DECOUPLED) gr = g * k.gscale;
+  else gr = __builtin_fmaf(k.gscale, g, k.wd * y);
+  v = __builtin_fmaf(k.b2, v, ((1.f - k.b2) * gr) * gr);
+  float u = gr / (sqrtf(v) / k.bc2_sqrt + k.eps);
+  if constexpr (DECOUPLED) u = u + k.wd * y;
+  z = z - k.step * u;
+  x = ema_next(x, z, k.d);
+  y = __builtin_fmaf(k.b1, x, (1.f - k.b1) * z);
+}
+
+// elements [i0, min(i0 + 4, n)) of one range (i0 < n): reads y (HOLD: from `hold`, else from p), g, z, v and x, writes p, z, v and x --
+// five streams in, four out.  Four elements left: 16-byte loads, all issued before the first store.  At the tail: element by element.
+template <bool DECOUPLED, bool HOLD>
+__device__ __forceinline__ void sf_quad(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ z, float* __restrict__ v,
+                                        float* __restrict__ x, long i0, long n, const SfScal& k, const float* __restrict__ hold) {
+  if (i0 + 3 < n) {
+    float4 yy, zz = *(float4*)(z + i0), vv = *(float4*)(v + i0), xx = *(float4*)(x + i0);
+    if constexpr (HOLD) yy = *(const float4*)(hold + i0);
+    else yy = *(float4*)(p + i0);
+    const float4 gg = *(const float4*)(g + i0);
+    float* Y = (float*)&yy; float* Z = (float*)&zz; float* V = (float*)&vv; float* X = (float*)&xx; const float* G = (const float*)&gg;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sf_elem<DECOUPLED>(Y[j], Z[j], V[j], X[j], G[j], k);
+    *(float4*)(p + i0) = yy; *(float4*)(z + i0) = zz; *(float4*)(v + i0) = vv; *(float4*)(x + i0) = xx;
+  } else {
+    for (long i = i0; i < n; ++i) {
+      float yv, zv = z[i], vv = v[i], xv = x[i];
+      if constexpr (HOLD) yv = hold[i];
+      else yv = p[i];
+      sf_elem<DECOUPLED>(yv, zv, vv, xv, g[i], k);
+      p[i] = yv; z[i] = zv; v[i] = vv; x[i] = xv;
+    }
+  }
+}
+
 // Orthogonalised momentum (include/avmoe.h, avmoe_opt_muon_step): the parameter's new value from the finished direction O, written ONCE for
 // kk_opt_muon_ns (opt_muon.hip) and kk_opt_muon_large_apply (opt_muon_large.hip): decay (decoupled), then p - step * O with step = lr * s; as lamb_next
 __device__ __forceinline__ float muon_next(float p, float o, float lr, float wd, float step, bool decoupled) {

@@ -13,13 +13,14 @@
                                per-group weight decay; opt-in per-parameter gradient norms and the first non-finite parameter;
                                sharpness-aware minimization (`sam_rho`, `sam_adaptive`: `sam_perturb()` between the two backward
                                passes of a step, the unperturbed weights kept on the device and restored exactly by `step()`);
-                               layer-wise trust ratios (`trust_ratio`), Prodigy learning-rate estimation (`prodigy`) and
-                               orthogonalised momentum (`muon`)
+                               layer-wise trust ratios (`trust_ratio`), Prodigy learning-rate estimation (`prodigy`),
+                               orthogonalised momentum (`muon`) and schedule-free AdamW (`schedule_free`: no run length in the
+                               recipe, the evaluated average kept where the averages are)
   * `LRSchedule`            -- a per-step learning-rate schedule (linear warm-up, then cosine / linear / step decay) that FlatAdam's
                                device path evaluates on the device from its own step counter
 
 Host logic around a few small C-ABI entry points (avmoe_adam_step, avmoe_opt_grad_norm_swa / avmoe_opt_adam_step[_ema|_sam] /
-avmoe_opt_lamb_step / avmoe_opt_prodigy_step / avmoe_opt_muon_step / avmoe_opt_swap_ema / avmoe_opt_sam_perturb,
+avmoe_opt_lamb_step / avmoe_opt_prodigy_step / avmoe_opt_muon_step / avmoe_opt_sf_step / avmoe_opt_swap_ema / avmoe_opt_sam_perturb,
 avmoe_opt_ema_buffers / avmoe_opt_swap_buffers); nothing falls back to the CPU for GPU tensors.
 
 A parameter is one `_ParamRecord` in `FlatAdam._recs` (its bucket, offset, rate, decay and per-option settings); a per-element side
@@ -415,6 +416,44 @@ class FlatAdam:
     (ValueError), one without it loads as before.  A library without the entry point raises AvmoeError.  The data-parallel statement
     above holds unchanged (documented from the code, verified on one rank only).  NOT covered: a short side above 2048.
 
+    Schedule-free.  `schedule_free=True` (Schedule-Free AdamW, Defazio et al. 2024, "The Road Less Scheduled"; it selects the device
+    path too) removes the run length from the recipe: a constant rate after a warm-up, and the weights one evaluates are as good as a
+    tuned decay's at whatever step the run stops.  Three sequences per parameter: z, the base sequence that takes the steps (it lives in
+    exp_avg); x, the running average of z that is evaluated (it lives in the shadow buffers of the averages); and y, an interpolation
+    of the two at which the gradient is taken -- the parameter as the sites see it.  With g' the gradient as the update sees it
+    (scale, clip factor, coupled decay at y), n = applied_steps after the step and f the schedule's factor (1 without one):
+
+        f_max = max(f_max, f) ;  w = n^sf_r * f_max^sf_lr_power ;  weight_sum += w ;  c = w / weight_sum ;  d = 1 - c
+        v = b2 v + (1 - b2) g'^2 ;  u = g' / (sqrt(v_hat) + eps)     (decoupled_weight_decay: u = u + wd * y)
+        z = z - lr * f * u ;  x = d x + c z ;  y = b1 x + (1 - b1) z
+
+    There is no momentum buffer and no first-moment bias correction: betas[0] is the interpolation.  The first applied step has c = 1
+    and x = z exactly; betas[0] = 0 gives y = z exactly; with sf_r = 0 and a constant factor x is the uniform mean of z.  The recipe:
+    `FlatAdam(red, lr=args.lr, schedule_free=True, weight_decay=0.01, decoupled_weight_decay=True, max_grad_norm=1.0,
+    lr_schedule=LRSchedule(warmup_steps=...))` -- a warm-up and NO decay.  The protocol: train on the parameters as they are (y), and
+    evaluate or checkpoint inside `with opt.ema_weights():` after `reestimate_bn(model, batches, ema=opt)` -- the swap is the averages'
+    exact exchange launch, not a back-conversion from y, and it gives every byte back.
+    A step is the unchanged norm call (without the averages' flags) and then TWO launches in place of the update whatever the number of
+    parameters (include/avmoe.h, avmoe_opt_sf_step): one thread advances weight_sum, f_max, c and d in a 32-byte block on the device
+    from the counters the finalize launch has just written, and one table walk reads y, the gradient, z, v and x and writes y, z, v and
+    x -- the norm call + 2, no host synchronisation, no step-dependent host scalar, capturable; a host implementation needs a handful
+    of foreach passes per step and two full passes over the weights at every train / eval switch.  Clipping, skipping (a skipped step
+    leaves every bit, the block included; behind a perturbation it writes the held weights back and nothing else), both decays, the
+    schedule, per-group rates and decays, per-parameter gradient norms, SAM (y is then the held value) and `ema_buffers=` (the buffers'
+    shadows take the same d) compose unchanged; `ema_decay`, `swa_start`, `trust_ratio`, `prodigy` or `muon` together with it raise
+    ValueError.  `ema_params`, `swap_ema()`, `ema_weights()`, `last_ema_decay` (= d), `adapter_state_dict(model, ema=opt)`,
+    `save_adapters(..., ema=opt)` and `reestimate_bn(model, batches, ema=opt)` serve x unchanged.  `schedule_free`, `sf_r`,
+    `sf_lr_power` are host attributes; `sf_c` (fp32), `sf_weight_sum` (fp64), `sf_lr_max` (fp32) DEVICE views of the block; `sf_z`
+    DEVICE views of z in `params` order; `sf_weights_next(...)` is the host's copy of the scalar rule.  `state_dict()` keeps torch's
+    format (exp_avg is z) and carries "schedule_free", "sf_r", "sf_lr_power", "sf_weight_sum", "sf_lr_max", "sf_c" (and "sf_d") under
+    "flat_adam", with x in the "ema" list; `load_state_dict()` restores them; a dict saved with the option does not load into an
+    optimizer built without it (ValueError); one without it keeps exp_avg_sq and the counters, re-seeds z = x = the CURRENT parameters
+    and zeroes the block, so load the model first.  Under data parallelism the gradients agree on every rank after `red.finish()` and
+    so does every step: no communication is added (verified on one rank only).  NOT covered: the per-epoch StepLR decay (`step_size`
+    / `gamma`) scales the rate through the range table but is not part of f, so it does not enter the averaging weights; the plain
+    (non-device) path; parameters outside the reducer (neither stepped nor averaged); the schedulefree package's bits (its bias
+    correction rides in the rate and its weights use lr_max: another order of operations).
+
     Resuming.  `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format: `state[i] = {"step", "exp_avg", "exp_avg_sq"}` (CPU
     tensors shaped like the parameter), `param_groups` with lr / betas / eps / weight_decay / params, plus one extra key "flat_adam" (t, epoch,
     counters, options, the schedule) that torch ignores.  With a schedule a group's "lr" is the rate of the NEXT step, lr0 * decay *
@@ -434,7 +473,8 @@ class FlatAdam:
                  trust_clip: Optional[float] = None, prodigy: bool = False, prodigy_d0: float = 1e-6, prodigy_d_coef: float = 1.0,
                  prodigy_growth: Optional[float] = None, prodigy_safeguard_warmup: bool = False, muon: bool = False,
                  muon_momentum: float = 0.95, muon_nesterov: bool = True, muon_ns_steps: int = 5, muon_scale: str = "match_rms_adamw",
-                 muon_max_numel: int = 262144, muon_large: bool = False, muon_large_max_numel: int = 1 << 23):
+                 muon_max_numel: int = 262144, muon_large: bool = False, muon_large_max_numel: int = 1 << 23,
+                 schedule_free: bool = False, sf_r: float = 0.0, sf_lr_power: float = 2.0):
         """max_grad_norm: clip the global gradient norm to it (None: off).  decoupled_weight_decay: torch.optim.AdamW instead of Adam's L2
         term.  skip_nonfinite: a step whose gradient norm is Inf / NaN changes nothing and is counted in `skipped_steps`.  lr_schedule: a
         per-step LRSchedule evaluated on the device.  ema_decay: keep an exponential moving average of the parameters with this decay in
@@ -457,9 +497,14 @@ class FlatAdam:
         muon_large: also orthogonalise the matrices the small rule declines, on the tiled engine (class docstring, "The large
         matrices"): short side at most 2048 and numel at most `muon_large_max_numel` (ValueError for a non-bool, without `muon`, for a
         bad `muon_large_max_numel` or one given without `muon_large`).
-        Any of the eleven selects the device path (class docstring); with all at their
+        schedule_free: schedule-free AdamW (class docstring, "Schedule-free"): a constant rate, the gradient taken at an interpolation of
+        a base sequence and its running average, which `ema_params` / `ema_weights()` serve; sf_r >= 0 and sf_lr_power >= 0 (held as
+        fp32): a step's weight in the average grows like n^sf_r * (largest schedule factor so far)^sf_lr_power (ValueError for a bad
+        value, for one given without `schedule_free`, and for `schedule_free` with `ema_decay`, `swa_start`, `trust_ratio`, `prodigy`
+        or `muon`).
+        Any of the twelve selects the device path (class docstring); with all at their
         defaults step() is the per-bucket avmoe_adam_step path.  ema_buffers: a torch.nn.Module (its named_buffers()) or an iterable of (name, tensor) to average
-        and swap with the weights; needs `ema_decay` or `swa_start`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
+        and swap with the weights; needs `ema_decay`, `swa_start` or `schedule_free`.  Floating-point buffers must be contiguous fp32 on the optimizer's GPU (ValueError
         otherwise); integer and empty ones are left out, and a tensor listed twice (same address) is held once.
         param_groups: the list `select_trainable` returns ({"params": p, "lr": ...} per parameter, as handed to
         torch.optim.Adam at AVE/main_trans_v3.py:313-322): each parameter is stepped with ITS group's learning rate (the
@@ -498,6 +543,13 @@ class FlatAdam:
         self.muon_large, self.muon_large_max_numel = self._check_muon_large(muon_large, muon_large_max_numel, self.muon)
         if self.muon and (self.trust_ratio or self.prodigy):
             raise ValueError("muon and trust_ratio / prodigy are different rules for the step: choose one")
+        self.schedule_free, self.sf_r, self.sf_lr_power = self._check_sf(schedule_free, sf_r, sf_lr_power)
+        if self.schedule_free:
+            other = [k for k, on in (("ema_decay", self.ema_decay is not None), ("swa_start", self.swa_start is not None),
+                                     ("trust_ratio", self.trust_ratio), ("prodigy", self.prodigy), ("muon", self.muon)) if on]
+            if other:
+                raise ValueError(f"schedule_free and {' / '.join(other)} do not combine: schedule_free keeps its own average in the shadow "
+                                 "buffers and its own rule for the step")
         for grp in (param_groups or []):                 # before anything is touched
             if "trust_ratio" in grp and not isinstance(grp["trust_ratio"], bool):
                 raise ValueError(f"a parameter group's \"trust_ratio\" must be True or False, not {grp['trust_ratio']!r}")
@@ -541,10 +593,12 @@ class FlatAdam:
             self._add_side_buffer("s")
         if self.muon:                                    # the work buffer: the bucket's layout once more; holds O after a step
             self._add_side_buffer("o")
+        if self.schedule_free:                           # z lives in exp_avg and starts, like the average x, at the parameters
+            self._seed_sf()
         self._rebuild_plain_ranges()
         self._device = self.max_grad_norm is not None or self.decoupled_weight_decay or self.skip_nonfinite or lr_schedule is not None \
             or self._averaging or self.report_grad_norms or self.sam_rho is not None or self.trust_ratio \
-            or self.prodigy or self.muon
+            or self.prodigy or self.muon or self.schedule_free
         if self._device:
             self._build_device_state()
 
@@ -641,8 +695,9 @@ class FlatAdam:
 
     @property
     def _averaging(self) -> bool:
-        """the optimizer keeps an average of the weights: the exponential one (ema_decay) or the uniform one (swa_start)"""
-        return self.ema_decay is not None or self.swa_start is not None
+        """the optimizer keeps an average of the weights: the exponential one (ema_decay), the uniform one (swa_start) or schedule-free
+        AdamW's x (schedule_free)"""
+        return self.ema_decay is not None or self.swa_start is not None or self.schedule_free
 
     def _decay_at(self, n: int) -> float:
         """the decay word of the state block after n applied steps, by the rule of the average that is on"""
@@ -655,7 +710,8 @@ class FlatAdam:
         if spec is None:
             return []
         if not self._averaging:
-            raise ValueError("ema_buffers needs ema_decay or swa_start: the buffers are averaged with the decay of the weight average")
+            raise ValueError("ema_buffers needs ema_decay, swa_start or schedule_free: the buffers are averaged with the decay of the weight "
+                             "average")
         items = spec.named_buffers() if isinstance(spec, torch.nn.Module) else spec
         dev = reducer.buckets[0].flat.device if reducer.buckets else None
         out, seen = [], set()
@@ -721,7 +777,7 @@ class FlatAdam:
     def ema_params(self) -> List[torch.Tensor]:
         """the averages as DEVICE tensors shaped like `params` and in that order: views of the shadow buffers (inside `ema_weights()`
         they hold the raw parameters)"""
-        self._need(self._averaging, "ema_params", "ema_decay or swa_start")
+        self._need(self._averaging, "ema_params", "ema_decay, swa_start or schedule_free")
         return list(self._ema_views)
 
     @property
@@ -729,7 +785,7 @@ class FlatAdam:
         """fp32 DEVICE scalar: the decay d_n the last applied step averaged with (a skipped step leaves it).  A view of the state block,
         like `last_lr_factor`; only with `ema_decay` or `swa_start` (there: 0 before the average starts, k / (k + 1) on an averaging
         step, 1 between two)."""
-        self._need(self._averaging, "last_ema_decay", "ema_decay or swa_start")
+        self._need(self._averaging, "last_ema_decay", "ema_decay, swa_start or schedule_free")
         return self._state_view("ema_decay")
 
     def swap_ema(self):
@@ -737,7 +793,7 @@ class FlatAdam:
         synchronisation.  Call it again to swap back; until then step(), state_dict() and load_state_dict() raise.  With `ema_buffers` a
         second launch exchanges the buffers (BatchNorm running statistics) with their averages, in place: no `module._buffers` entry is
         re-bound.  Without it buffers stay as they are."""
-        self._need(self._averaging, "swap_ema", "ema_decay or swa_start")
+        self._need(self._averaging, "swap_ema", "ema_decay, swa_start or schedule_free")
         self._not_perturbed("swap_ema()")
         stream = self._exchange(self._shadow_ptrs)
         if self._ebufs:
@@ -758,7 +814,7 @@ class FlatAdam:
         after it, also when the body raises.  step() inside raises.  With `ema_buffers` the BatchNorm running statistics are their
         averages inside too, and what the raw weights' forward passes left again after it; without the option they are not averaged, and
         an evaluation inside sees the raw weights' statistics."""
-        self._need(self._averaging, "ema_weights", "ema_decay or swa_start")
+        self._need(self._averaging, "ema_weights", "ema_decay, swa_start or schedule_free")
         self._not_swapped("ema_weights()")
         self._not_perturbed("ema_weights()")
         self.swap_ema()
@@ -773,6 +829,8 @@ class FlatAdam:
             extra.update(ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema=[e.detach().cpu().clone() for e in self._ema_views])
         if self.swa_start is not None:                   # the uniform average: the same "ema" list, with the constants that say so
             extra.update(swa_start=self.swa_start, swa_freq=self.swa_freq, ema=[e.detach().cpu().clone() for e in self._ema_views])
+        if self.schedule_free:                           # x: the same "ema" list, beside the keys _save_sf writes
+            extra.update(ema=[e.detach().cpu().clone() for e in self._ema_views])
 
     def _check_saved_average(self, extra):
         """load_state_dict(): -> (saved averages, the saved constants of this optimizer's rule), or None where the averages are re-seeded"""
@@ -780,7 +838,8 @@ class FlatAdam:
             raise ValueError("the state dict carries a uniform weight average (swa_start), which this optimizer does not keep: build it "
                              "with swa_start (the saved swa_start / swa_freq then replace the constructor's)")
         # averages of the other kind (an exponential average's into a uniform one, or the reverse) are not this optimizer's: re-seed
-        own_kind = (extra.get("swa_start") is not None) == (self.swa_start is not None)
+        own_kind = (extra.get("swa_start") is not None) == (self.swa_start is not None) \
+            and (extra.get("schedule_free") is True) == self.schedule_free
         saved = extra.get("ema") if self._averaging and own_kind else None
         if saved is None:
             return None
@@ -791,6 +850,8 @@ class FlatAdam:
                 raise ValueError(f"parameter index {i}: ema has shape {tuple(e.shape)}, the parameter {tuple(r.p.shape)}")
         if self.swa_start is not None:
             return saved, self._check_swa(extra["swa_start"], extra.get("swa_freq", self.swa_freq))
+        if self.schedule_free:                           # x has no constants of its own: _check_saved_sf reads the rule's
+            return saved, None
         return saved, self._check_ema(self.ema_decay if extra.get("ema_decay") is None else extra["ema_decay"],
                                       self.ema_warmup if extra.get("ema_warmup") is None else extra["ema_warmup"])
 
@@ -799,14 +860,15 @@ class FlatAdam:
             saved, consts = payload
             if self.swa_start is not None:
                 self._set_swa(*consts)
-            else:
+            elif not self.schedule_free:
                 self._set_ema(*consts)
             for view, e in zip(self._ema_views, saved):
                 view.copy_(e.to(torch.float32))
         else:                                            # no averages in the dict: start them from the parameters as they are now
             for s in self.state:
                 s["e"].copy_(s["p"])
-        self._views["ema_decay"].fill_(self._decay_at(applied) if applied > 0 else 0.0)
+        if not self.schedule_free:                       # (there the word is the block's d: _apply_saved_sf writes it)
+            self._views["ema_decay"].fill_(self._decay_at(applied) if applied > 0 else 0.0)
 
     def _save_buffers(self, extra):
         extra.update(ema_buffers=[v.detach().cpu().clone() for v in self._ebuf_views], ema_buffer_names=self.ema_buffer_names)
@@ -923,8 +985,8 @@ class FlatAdam:
     def _update(self, L, stream, n, scale, flags, shadows):
         """the update launch of a device step: avmoe_opt_adam_step_ema, or behind a sam_perturb() avmoe_opt_adam_step_sam, which reads
         the parameters from the hold buffers and so brings the unperturbed weights back; with `trust_ratio` avmoe_opt_lamb_step (three
-        launches in place of one), with `prodigy` avmoe_opt_prodigy_step and with `muon` avmoe_opt_muon_step (two) serve both cases:
-        they take the hold pointers only behind a sam_perturb()"""
+        launches in place of one), with `prodigy` avmoe_opt_prodigy_step, with `muon` avmoe_opt_muon_step and with `schedule_free`
+        avmoe_opt_sf_step (two each) serve both cases: they take the hold pointers only behind a sam_perturb()"""
         hold = self._hold_ptrs.data_ptr() if self._perturbed else None
         if self.muon:
             entry, tail = L.avmoe_opt_muon_step, (hold, self._muon_image.data_ptr(), len(self._muon_order), self._muon_work_ptrs.data_ptr(),
@@ -936,6 +998,8 @@ class FlatAdam:
         elif self.prodigy:
             entry, tail = L.avmoe_opt_prodigy_step, (hold, self._prodigy_x0_ptrs.data_ptr(), self._prodigy_s_ptrs.data_ptr(),
                                                      C.byref(self._prodigy_c), self._prodigy_block.data_ptr(), self._prodigy_ws.data_ptr())
+        elif self.schedule_free:                         # x is required, whatever the flags: the shadows' place takes it
+            entry, shadows, tail = L.avmoe_opt_sf_step, self._shadow_ptrs.data_ptr(), (hold, C.byref(self._sf_c), self._sf_block.data_ptr())
         elif self.trust_ratio:
             entry, tail = L.avmoe_opt_lamb_step, (hold, self._trust_limits.data_ptr(), self._trust_ws.data_ptr(), self._trust_report.data_ptr())
         elif self._perturbed:
@@ -1178,6 +1242,124 @@ class FlatAdam:
         """DEVICE views in `params` order: the running gradient sum s of every parameter"""
         self._need(self.prodigy, "prodigy_s", "prodigy")
         return list(self._prodigy_s_views)
+
+    # ---- schedule-free AdamW --------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_sf(on, r, lr_power):
+        """-> (schedule_free, sf_r, sf_lr_power) with the numbers as the fp32 values the device gets"""
+        if not isinstance(on, bool):
+            raise ValueError(f"schedule_free must be True or False, not {on!r}")
+        out = []
+        for name, v in (("sf_r", r), ("sf_lr_power", lr_power)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{name} (schedule_free) must be a finite number >= 0, not {v!r}")
+            x = float(v)
+            if not (x >= 0.0) or x > 3.4028234663852886e38:
+                raise ValueError(f"{name} (schedule_free) must be a finite number >= 0 (as fp32), not {v!r}")
+            out.append(_f32(x))
+        if not on and (out[0] != 0.0 or out[1] != 2.0):
+            raise ValueError("sf_r / sf_lr_power need schedule_free: there is no average to weight")
+        return on, out[0], out[1]
+
+    @staticmethod
+    def sf_weights_next(weight_sum: float, f_max: float, n: int, f: float, r: float = 0.0, lr_power: float = 2.0) -> tuple:
+        """The host's copy of the rule kk_opt_sf_weights applies on an applied step, in its operation order: from the block's words before
+        the step (weight_sum, f_max as an fp32 value), n = applied_steps after the step (the first has n = 1) and the step's schedule
+        factor f (1 without a schedule) -> (weight_sum, f_max, c, d) as the block holds them after it.  In double from the fp32
+        constants: f_max = max(f_max, f); w = n^r * f_max^lr_power (pow(., 0) = 1); weight_sum += w; c = w / weight_sum, 0 where
+        weight_sum is not > 0; d = 1 - c; c and d each rounded once to fp32."""
+        f, f_max = _f32(float(f)), _f32(float(f_max))
+        f_max = f if f > f_max else f_max
+        w = math.pow(float(int(n)), _f32(float(r))) * math.pow(f_max, _f32(float(lr_power)))
+        total = float(weight_sum) + w
+        c = w / total if total > 0.0 else 0.0
+        return total, f_max, _f32(c), _f32(1.0 - c)
+
+    def _seed_sf(self):
+        """the start of a run: z (exp_avg) = x (the shadow) = the parameters as they are now (padding zero)"""
+        for s in self.state:
+            s["m"].copy_(s["p"])
+            s["e"].copy_(s["p"])
+
+    def _build_sf(self):
+        """the 32-byte block on the device (all zero), its views, the views of z and the constants step() hands over"""
+        self._lib_with("avmoe_opt_sf_step", "schedule-free AdamW")
+        self._sf_block = torch.zeros(C.sizeof(cm.OptSfState), dtype=torch.uint8, device=self._dev)
+        self._sf_views = {k: self._sf_block[o:o + (8 if dt == "float64" else 4)].view(getattr(torch, dt))[0]
+                          for k, (o, dt) in cm.OPT_SF_FIELDS.items()}
+        self._sf_z_views = [r.view("m") for r in self._recs]
+        self._set_sf(self.sf_r, self.sf_lr_power)
+
+    def _set_sf(self, r, lr_power):
+        self.sf_r, self.sf_lr_power = r, lr_power
+        self._sf_c = cm.OptSf(r=r, lr_power=lr_power)
+
+    def _save_sf(self, extra):
+        """state_dict(): the constants and the block (z is "exp_avg", x the "ema" list _save_average writes)"""
+        blk = {k: v.item() for k, v in self._sf_views.items()}
+        extra.update(schedule_free=True, sf_r=self.sf_r, sf_lr_power=self.sf_lr_power, sf_weight_sum=blk["weight_sum"],
+                     sf_lr_max=blk["f_max"], sf_c=blk["c"], sf_d=blk["d"])
+
+    def _check_saved_sf(self, extra):
+        """load_state_dict(): -> (constants, the block's words), or None where z, x and the block are re-seeded"""
+        if extra.get("schedule_free") is True and not self.schedule_free:
+            raise ValueError("the state dict was saved with schedule_free (its exp_avg is the base sequence z, not a momentum), which this "
+                             "optimizer was built without: build it with schedule_free=True")
+        if not (self.schedule_free and extra.get("schedule_free") is True):
+            return None
+        if extra.get("ema") is None:
+            raise ValueError("the state dict was saved with schedule_free but carries no average (\"ema\")")
+        consts = self._check_sf(True, extra.get("sf_r", self.sf_r), extra.get("sf_lr_power", self.sf_lr_power))[1:]
+        ws, fm, c = float(extra.get("sf_weight_sum", 0.0)), float(extra.get("sf_lr_max", 0.0)), float(extra.get("sf_c", 0.0))
+        if not (math.isfinite(ws) and ws >= 0.0 and math.isfinite(fm) and fm >= 0.0 and 0.0 <= c <= 1.0):
+            raise ValueError(f"the state dict's sf_weight_sum / sf_lr_max / sf_c must be finite and >= 0 with sf_c <= 1, not {ws!r} / {fm!r} / {c!r}")
+        d = float(extra.get("sf_d", _f32(1.0 - c) if ws > 0.0 else 0.0))      # informative: every applied step writes d before it reads it
+        if not (0.0 <= d <= 1.0):
+            raise ValueError(f"the state dict's sf_d must be in [0, 1], not {d!r}")
+        return consts, {"weight_sum": ws, "f_max": fm, "c": c, "d": d}
+
+    def _apply_saved_sf(self, payload):
+        self._sf_block.zero_()
+        if payload is None:                              # nothing saved: the run starts here, from the parameters as they are now
+            self._views["ema_decay"].fill_(0.0)
+            return self._seed_sf()
+        consts, blk = payload
+        self._set_sf(*consts)
+        for k, val in blk.items():
+            self._sf_views[k].fill_(val)
+        self._views["ema_decay"].fill_(blk["d"])
+
+    @property
+    def sf_c(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the weight c = w / weight_sum the last applied step's z entered the average x with (1 at the first one;
+        `last_ema_decay` is d = 1 - c).  A view of the 32-byte schedule-free block, rewritten by every applied step and by every replay
+        of a captured one (a skipped step leaves it): `.item()` is the caller's synchronisation.  Only with `schedule_free`."""
+        self._need(self.schedule_free, "sf_c", "schedule_free")
+        return self._sf_views["c"]
+
+    @property
+    def sf_weight_sum(self) -> torch.Tensor:
+        """fp64 DEVICE scalar: the sum of the steps' averaging weights so far.  As `sf_c`."""
+        self._need(self.schedule_free, "sf_weight_sum", "schedule_free")
+        return self._sf_views["weight_sum"]
+
+    @property
+    def sf_lr_max(self) -> torch.Tensor:
+        """fp32 DEVICE scalar: the largest schedule factor an applied step has seen (1 without a schedule).  As `sf_c`."""
+        self._need(self.schedule_free, "sf_lr_max", "schedule_free")
+        return self._sf_views["f_max"]
+
+    @property
+    def sf_block(self) -> Dict[str, torch.Tensor]:
+        """every word of the schedule-free block as DEVICE scalars: weight_sum (fp64), f_max, c, d (fp32).  As `sf_c`."""
+        self._need(self.schedule_free, "sf_block", "schedule_free")
+        return dict(self._sf_views)
+
+    @property
+    def sf_z(self) -> List[torch.Tensor]:
+        """DEVICE views in `params` order: the base sequence z of every parameter (it lives in exp_avg)"""
+        self._need(self.schedule_free, "sf_z", "schedule_free")
+        return list(self._sf_z_views)
 
     # ---- orthogonalised momentum (Muon) ---------------------------------------------------------------------------
     MUON_MAX_DIM = 128                                   # AVMOE_MUON_MAX_DIM: the short side one workgroup's LDS holds the Gram matrix of
@@ -1470,6 +1652,8 @@ class FlatAdam:
             self._build_prodigy()
         if self.muon:
             self._build_muon()
+        if self.schedule_free:
+            self._build_sf()
 
     def _build_report(self):
         """the report buffer (header, then one float per parameter) and the two views the properties hand out"""
@@ -1486,6 +1670,8 @@ class FlatAdam:
     def _build_shadows(self):
         """the views `ema_params` hands out and the device array of one shadow pointer per range, beside the range table"""
         self._ema_views, self._shadow_ptrs = self._side_views("e", "a shadow")
+        if self.schedule_free:                           # no flag: the norm call writes no decay, avmoe_opt_sf_step does
+            return
         if self.swa_start is not None:
             self._set_swa(self.swa_start, self.swa_freq)
         else:
@@ -1696,7 +1882,7 @@ class FlatAdam:
                  "skip_nonfinite": self.skip_nonfinite, "step_size": self.step_size, "gamma": self.gamma}
         for on, save in ((self.lr_schedule is not None, self._save_schedule), (self._averaging, self._save_average),
                          (self._ebufs, self._save_buffers), (self.sam_rho is not None, self._save_sam), (self.trust_ratio, self._save_trust),
-                         (self.prodigy, self._save_prodigy), (self.muon, self._save_muon)):
+                         (self.prodigy, self._save_prodigy), (self.muon, self._save_muon), (self.schedule_free, self._save_sf)):
             if on:
                 save(extra)
         if self.report_grad_norms:                       # informative, like the other path options; absent when off
@@ -1721,7 +1907,10 @@ class FlatAdam:
         parameters, s = 0, d = d0, so load the model first.  Without the option a dict that carries "prodigy" raises ValueError: its
         rates are multipliers of d, not learning rates.  With `muon`: the saved constants ("muon_momentum", "muon_nesterov", "muon_ns_steps",
         "muon_scale") replace the constructor's; which parameters are orthogonalised stays what the constructor says; a dict without
-        "muon" loads as before.  Without the option a dict that carries "muon" raises ValueError."""
+        "muon" loads as before.  Without the option a dict that carries "muon" raises ValueError.  With `schedule_free`: the saved
+        constants, block words ("sf_weight_sum", "sf_lr_max", "sf_c") and x ("ema") are restored, exp_avg is z; a dict without
+        "schedule_free" keeps exp_avg_sq and the counters and re-seeds z = x = the CURRENT parameters with a zeroed block, so load the
+        model first.  Without the option a dict that carries "schedule_free" raises ValueError: its exp_avg is no momentum."""
         self._not_swapped("load_state_dict()")
         self._not_perturbed("load_state_dict()")
         # 1. the groups and the moments
@@ -1760,6 +1949,7 @@ class FlatAdam:
         trust = self._check_saved_trust(extra)
         prodigy = self._check_saved_prodigy(extra)
         muon = self._check_saved_muon(extra)
+        sf = self._check_saved_sf(extra)
         buffers = self._check_saved_buffers(extra)
         with torch.no_grad():
             # 3. moments, groups and rates
@@ -1807,6 +1997,8 @@ class FlatAdam:
             self._apply_saved_muon(muon)
             if self.prodigy:
                 self._apply_saved_prodigy(prodigy)
+            if self.schedule_free:
+                self._apply_saved_sf(sf)
             self._upload_table()
 
     def _rebuild_plain_ranges(self):

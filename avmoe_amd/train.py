@@ -137,7 +137,7 @@ def reestimate_bn(model: torch.nn.Module, batches: Iterable, forward=None, ema: 
     `batch[0]`, which cannot drive a model that takes two modalities).
 
     ema=None: update_bn's behaviour -- the model's own statistics are the re-estimated ones and the counters are left at the number of
-    batches.  ema=opt (a FlatAdam with `ema_decay` and `ema_buffers`): everything runs inside `opt.ema_weights()`, so the forward
+    batches.  ema=opt (a FlatAdam with `ema_decay`, `swa_start` or `schedule_free`, and `ema_buffers`): everything runs inside `opt.ema_weights()`, so the forward
     passes see the AVERAGED weights and write the buffers that hold the averaged statistics meanwhile; after the swap back
     `opt.ema_buffers` are the re-estimated statistics, the model's raw weights and raw statistics are bit for bit what they were, and
     the counters (integer buffers, outside the optimizer's table: not swapped) are copied back in place.  ValueError, before anything
@@ -198,7 +198,7 @@ def reestimate_bn(model: torch.nn.Module, batches: Iterable, forward=None, ema: 
 
 def adapter_state_dict(model: torch.nn.Module, substrings=("adapter",), ema: Optional[FlatAdam] = None) -> Dict[str, torch.Tensor]:
     """The adapter / router entries of model.state_dict() (keys containing 'adapter': `*_adapter_blocks_p{1,2}.*`).
-    ema: a FlatAdam built with `ema_decay` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), and with
+    ema: a FlatAdam built with `ema_decay`, `swa_start` or `schedule_free` -- every parameter it holds is written with its AVERAGED value (`opt.ema_params`), and with
     `ema_buffers` every buffer it holds (BatchNorm running statistics) with its averaged value too (`opt.ema_buffers`); everything else
     (other buffers, parameters outside the optimizer) as it is.  The model is not modified, and the result loads with `load_adapters`
     like any other.  RuntimeError while `ema` holds perturbed weights (sam_perturb)."""

@@ -396,7 +396,8 @@ typedef struct avmoe_opt_state {
   int64_t skipped_steps;      /* steps held back because the norm was not finite */
   int32_t skip;               /* this step is held back */
   float lr_factor;            /* AVMOE_OPT_LR_SCHEDULE / AVMOE_OPT_SWA_LR: the factor of the last applied step (below); never written without one of them */
-  float ema_decay;            /* AVMOE_OPT_EMA / AVMOE_OPT_SWA: the weight average's decay d of the last applied step (below); never written without one of them */
+  float ema_decay;            /* AVMOE_OPT_EMA / AVMOE_OPT_SWA: the weight average's decay d of the last applied step (below); never written without one of them
+                                 -- except by avmoe_opt_sf_step, the ONE step entry point that writes the state block: it leaves its d = 1 - c here */
   int32_t reserved[5];
 } avmoe_opt_state;
 
@@ -779,6 +780,64 @@ int avmoe_opt_prodigy_step(const void* table, int32_t n_ranges, int64_t n_blocks
                            float* const* hold /* DEVICE, or NULL */, float* const* x0 /* DEVICE */, float* const* s /* DEVICE */,
                            const avmoe_opt_prodigy* consts /* HOST */, avmoe_opt_prodigy_state* block /* DEVICE, 16-byte aligned */,
                            double* workspace /* DEVICE */);
+
+/* Schedule-free AdamW (Defazio et al. 2024, "The Road Less Scheduled"; added under ABI 11 like the blocks above; found by symbol): a
+ * constant rate after a warm-up, the gradient taken at an interpolation y of a base sequence z and a running average x, and x -- the
+ * weights one evaluates -- as good as a tuned decay at whatever step the run stops.  No flag and no new word in the state block:
+ * avmoe_opt_sf_step is called IN PLACE of avmoe_opt_adam_step_ema / avmoe_opt_adam_step_sam, behind the unchanged norm call of a step
+ * (made WITHOUT AVMOE_OPT_EMA / AVMOE_OPT_SWA), on the same stream with the same grad_scale and betas.
+ * State: y is the range's `param`, z lives in its `exp_avg`, v in `exp_avg_sq`, x in a flat side buffer per range addressed by a DEVICE
+ * array of n_ranges float* under the rules of `shadows` (it IS the shadow: avmoe_opt_swap_ema exchanges y and x); z and x start as
+ * copies of the parameters; and the 32-byte avmoe_opt_sf_state on the device, which starts all zero.  Constants of a run (avmoe_opt_sf,
+ * HOST): r >= 0 and lr_power >= 0, both finite.
+ * An applied step, with n = applied_steps after it (the first has n = 1) and f = lr_factor under AVMOE_OPT_LR_SCHEDULE, else 1.  First
+ * ONE thread advances the block, in double, contraction off (the same for every range: a range's constant rate cancels in the ratio):
+ *     f_max      = max(f_max, f)
+ *     w          = pow(n, r) * pow(f_max, lr_power)          (pow(., 0) = 1)
+ *     weight_sum = weight_sum + w
+ *     c          = w / weight_sum                            (0 where weight_sum is not > 0: a warm-up that starts at factor 0)
+ *     d          = fp32(1 - c)                               (c and d each rounded once to fp32)
+ * and copies d into state->ema_decay, so that avmoe_opt_ema_buffers behind it averages the buffers with the same weight: the one place
+ * a step entry point writes the state block.  Then per element, with gscale = grad_scale * clip_coef and y the parameter (with
+ * hold != NULL the held value), every operation rounded to fp32 in the order written (csrc/adam_elem.h: sf_elem; contraction off):
+ *     coupled decay:              gr = fma(gscale, grad, wd * y)
+ *     AVMOE_OPT_DECOUPLED_DECAY:  gr = grad * gscale
+ *     v = fma(b2, v, ((1 - b2) * gr) * gr)                   (Adam's bits for v from the same gr)
+ *     u = gr / (sqrt(v) / bc2_sqrt + eps)                    (AVMOE_OPT_DECOUPLED_DECAY: u = u + wd * y)
+ *     z = z - (lr_r * f) * u
+ *     x = fma(d, x, (1 - d) * z)
+ *     y = fma(b1, x, (1 - b1) * z)                           -> param
+ * There is no momentum buffer and no first-moment bias correction: beta1 is the interpolation.  The first applied step has c = 1,
+ * d = 0 and x = z exactly; beta1 = 0 gives y = z exactly.
+ * avmoe_opt_sf_step is TWO launches on `stream` whatever the number of ranges (kk_opt_sf_weights: one block; kk_opt_sf_update<DECOUPLED,
+ * SCHED, HOLD>: the table walk, five 4-byte streams read and four written per element), without a host synchronisation and without a
+ * host scalar that changes from step to step, so it replays from a captured graph.  No floating-point atomics.
+ * When state->skip is set nothing is written -- the block and state->ema_decay included; with hold != NULL param = hold and nothing
+ * else.  Gradients are only read; alignment padding belongs to no range and is not touched.  A launch that does not match its table's
+ * header touches nothing; a range whose x / hold entry is not 16-byte aligned, or pointer arrays made for another range count, are left
+ * out likewise.
+ * `flags`: AVMOE_OPT_CLIP, AVMOE_OPT_SKIP_NONFINITE, AVMOE_OPT_DECOUPLED_DECAY, AVMOE_OPT_LR_SCHEDULE (the averaging is implied: any
+ * other flag is unknown).  hold == NULL is the step without a perturbation before it.
+ * Errors (before any launch): everything avmoe_opt_adam_step_sam refuses (hold != NULL) or avmoe_opt_adam_step_ema refuses (hold == NULL);
+ * AVMOE_ERR_BAD_ARG for NULL x, consts or block and for an r or lr_power that is not a finite number >= 0 (NaN included);
+ * AVMOE_ERR_ALIGNMENT for a block that is not 16-byte or a pointer array that is not 8-byte aligned.                                  */
+typedef struct avmoe_opt_sf_state {
+  double weight_sum;          /* the sum of the steps' averaging weights w so far */
+  float f_max;                /* the largest lr_factor so far (1 after the first applied step without a schedule) */
+  float c;                    /* the last applied step's weight in the average, w / weight_sum */
+  float d;                    /* 1 - c: the decay the average took (also state->ema_decay) */
+  int32_t reserved[3];
+} avmoe_opt_sf_state;
+
+typedef struct avmoe_opt_sf {
+  float r;                    /* >= 0: a step's weight grows like n^r (0: none) */
+  float lr_power;             /* >= 0: ... and like f_max^lr_power (2: the paper's; 0: none) */
+} avmoe_opt_sf;
+
+int avmoe_opt_sf_step(const void* table, int32_t n_ranges, int64_t n_blocks, avmoe_opt_state* state, float beta1, float beta2, float eps,
+                      float grad_scale, int32_t flags, void* stream, float* const* x /* DEVICE: the shadows, required */,
+                      float* const* hold /* DEVICE, or NULL */, const avmoe_opt_sf* consts /* HOST */,
+                      avmoe_opt_sf_state* block /* DEVICE, 16-byte aligned */);
 
 /* Muon: orthogonalised momentum for small hidden matrices (Jordan et al. 2024; torch.optim.Muon's rule with the iteration in fp32; added
  * under ABI 11 like the blocks above; found by symbol).  A range that is listed as a matrix steps along the nearest semi-orthogonal

@@ -40,6 +40,10 @@
                    event pairs around every step()
 --muon-large       (with --muon) FlatAdam(muon=True, muon_large=True): the matrices the small rule declines go through the tiled engine --
                    2 + 1 + 3 * ns_steps * classes (+ split-K reduces) + 1 launches in place of the one update launch
+--sched-free       (device mode) FlatAdam(schedule_free=True, decoupled_weight_decay=True): schedule-free AdamW -- two launches (one thread
+                   for the averaging weight, the table walk over y, the gradient, z, v and x) in place of the one update launch: the norm
+                   call's + 2 per step.  The alternative to --ema / --swa / --lamb / --prodigy / --muon; combines with --schedule (a
+                   warm-up without a decay there), --ema-buffers, --report, --sam
 --model two_bucket the model of tests/test_flat_adam_device_gpu.py ; eight_site the model of tests/test_training_loop_gpu.py ;
         wide_site  one AVE MoEAdapter at Swin-L / HTS-AT widths (C = 768, 196 x 1024 tokens, a 768-wide other modality), parameters as
                    plain ranges: conv_adapter is 196 x 1024 and fc 768 x 768, the matrices only --muon-large orthogonalises
@@ -105,6 +109,7 @@ def main():
     ap.add_argument("--adamw", action="store_true")
     ap.add_argument("--muon", action="store_true")
     ap.add_argument("--muon-large", action="store_true")
+    ap.add_argument("--sched-free", action="store_true")
     a = ap.parse_args()
     if (a.schedule or a.schedule_upload) and a.mode != "device":
         ap.error("--schedule / --schedule-upload go with --mode device")
@@ -118,8 +123,10 @@ def main():
         ap.error("--ema and --ema-foreach are the two sides of one comparison")
     if a.swa and (a.mode != "device" or a.ema or a.ema_foreach or a.schedule_upload or a.ema_buffers_foreach):
         ap.error("--swa goes with --mode device and is the alternative to --ema; it combines with --schedule, --ema-buffers and --report")
-    if a.ema_buffers and not (a.ema or a.swa):
-        ap.error("--ema-buffers goes with --ema or --swa")
+    if a.sched_free and (a.mode != "device" or a.ema or a.ema_foreach or a.swa or a.lamb or a.prodigy or a.muon or a.schedule_upload):
+        ap.error("--sched-free goes with --mode device and is the alternative to --ema / --swa / --lamb / --prodigy / --muon")
+    if a.ema_buffers and not (a.ema or a.swa or a.sched_free):
+        ap.error("--ema-buffers goes with --ema, --swa or --sched-free")
     if a.ema_buffers_foreach and not a.ema:
         ap.error("--ema-buffers-foreach goes with --ema")
     if a.ema_buffers and a.ema_buffers_foreach:
@@ -152,6 +159,8 @@ def main():
         swa_lr = dict(swa_start=total // 2, swa_factor=0.2, swa_anneal_steps=max(1, total // 8)) if a.swa else {}
         sched = LRSchedule(warmup_steps=total // 4, warmup_start=0.1, decay_kind="cosine", total_steps=max(total, total // 4 + 1), min_factor=0.05,
                            **swa_lr)
+        if a.sched_free:                                 # the recipe: a warm-up and no decay
+            sched = LRSchedule(warmup_steps=total // 4, warmup_start=0.1)
     if a.schedule:
         kw["lr_schedule"] = sched
     ema_decay, ema_warmup = 0.999, 10.0
@@ -179,6 +188,8 @@ def main():
         kw.update(muon=True)
     if a.muon_large:
         kw.update(muon_large=True)
+    if a.sched_free:
+        kw.update(schedule_free=True, decoupled_weight_decay=True)
     opt = FlatAdam(red, lr=1.0 if a.prodigy else 1e-3, weight_decay=1e-2, **kw)
     shadows = [p.detach().clone() for p in opt.params] if a.ema_foreach else None
     views = [p.data for p in opt.params]
@@ -294,7 +305,12 @@ def main():
     if a.muon_large:
         extra["large_matrices"] = [list(r.muon_shape) for r in opt._recs if r.muon_path == "large"]
         extra["large_classes"] = getattr(opt, "_muon_large_classes", 0)
-    if a.adamw or a.muon:
+    if a.sched_free:
+        extra["sched_free"] = "device"
+        extra["sf_c"], extra["sf_weight_sum"], extra["sf_lr_max"] = float(opt.sf_c.item()), float(opt.sf_weight_sum.item()), float(opt.sf_lr_max.item())
+        extra["last_ema_decay"] = float(opt.last_ema_decay.item())
+        extra["x_minus_y_max"] = max(float((e - p).abs().max()) for e, p in zip(opt.ema_params, views))
+    if a.adamw or a.muon or a.sched_free:
         extra["decay"] = "decoupled"
     if a.report:
         extra["report"] = "device"
