@@ -534,7 +534,8 @@ int k_colmean(int bf16, const void* X, int S, int N, int C, float* out, long out
 // ---------------------------------------------------------------------------------------------
 // One launch after Q = T0 Wf:
 //   blocks [0, nb_q): qr[kc] = T0[kc] . rw ; qb[kc] = T0[kc] . bf  (one wave per latent row), written into qrqb AND into the
-//                     extension columns of every frame's Rext row:  Rext[s][kc][M] = qr[kc], [M+1] = qb[kc], rest of the padding 0
+//                     extension columns of every frame's Rext row:  Rext[s][kc][M] = qr[kc], [M+1] = qb[kc], rest of the padding 0;
+//                     BmX[s][kc][M+1 .. Mb) = 0 (the padding behind ab, which the [Bm | ab] product does not write)
 //   the others:       Rext[s][Kcy][:] = 0 (the ybar row has no logits) ; BmX[s][Kcy][:] = wbar
 template <typename T>
 __global__ void __launch_bounds__(256) kk_qrqb_fill(const void* T0T_, const float* rw, const float* bf, float* qrqb, void* Rext_, void* BmX_,
@@ -560,6 +561,13 @@ __global__ void __launch_bounds__(256) kk_qrqb_fill(const void* T0T_, const floa
     for (int i = lane; i < S * padw; i += 64) {
       const int s = i / padw, w = i - s * padw;
       stT<T>(Rext, ((long)s * Kcyb + kc) * Mk + M + w, w == 0 ? a : (w == 1 ? b : 0.f));
+    }
+    // the columns of BmX behind ab: [Bm | ab] = A1 [Wc | bc] writes M + 1 of a row's Mb entries, the rest held whatever the workspace
+    // arrived with (row Kcy gets wbar's zero padding below) -- zero like the padding of every other operand of the chain
+    const int padb = Mb - M - 1;
+    for (int i = lane; i < S * padb; i += 64) {
+      const int s = i / padb, w = i - s * padb;
+      stT<T>(BmX, ((long)s * Kcyb + kc) * Mb + M + 1 + w, 0.f);
     }
     return;
   }
