@@ -21,11 +21,41 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "common.h"
 
 namespace avmoe {
 
 enum GemmDtype { GEMM_F32 = 0, GEMM_BF16 = 1 };
 enum GemmLayout { K_MAJOR = 0, MN_MAJOR = 1 };
+
+inline int gemm_dtype_bytes(int dtype) { return dtype == GEMM_BF16 ? 2 : 4; }
+
+// A tensor as a batch of row-major matrices: where one operand of a product lies.  `rows` x `cols` with leading dimension `ld` is the STORED
+// shape of one matrix; `s1` steps from frame to frame (the first batch level of a product), `s2` along its second batch level; `t` = the
+// product reads the transpose of what is stored.  Strides and `ld` in elements of `esz` bytes.  The site's tensors are stated once, in
+// site_views.h; a call site cuts and regroups them with the methods below and binds them with GemmArgs::product, which derives M / N / K,
+// layouts, leading dimensions and strides from them and refuses operands that do not fit each other.
+struct Mat {
+  const void* p = nullptr;
+  int esz = 0;                          // 0: an invalid view (flat() of frames that do not abut) -- every binding refuses it
+  int rows = 0, cols = 0;
+  long ld = 0, s1 = 0, s2 = 0;
+  bool t = false;
+  Mat moved(long elements) const { Mat m = *this; if (p) m.p = (const char*)p + elements * esz; return m; }      // (a null base stays null: shape-only queries)
+  Mat T() const { Mat m = *this; m.t = !t; return m; }
+  Mat rows_at(long r0, int n) const { Mat m = moved(r0 * ld); m.rows = n; return m; }
+  Mat cols_at(long c0, int n) const { Mat m = moved(c0); m.cols = n; return m; }
+  Mat frames_at(long f0) const { return moved(f0 * s1); }                                                       // frame f0 becomes frame 0
+  // `frames` frames as the rows of one matrix
+  Mat flat(int frames) const {
+    Mat m = *this; m.rows = frames * rows; m.s1 = 0;
+    if (s1 != (long)rows * ld) { set_last_error("Mat::flat: frames of %d rows x ld %ld lie %ld elements apart", rows, ld, s1); m.esz = 0; }
+    return m;
+  }
+  Mat groups(int g) const { Mat m = *this; m.cols = cols / g; m.s2 = m.cols; return m; }                        // g equal column groups as the second batch level
+  Mat row_blocks(int step, int n) const { Mat m = *this; m.rows = n; m.s2 = step * ld; return m; }              // blocks of n rows, `step` rows apart, as the second batch level
+  Mat planes(long stride) const { Mat m = *this; m.s2 = stride; return m; }                                     // whole copies of the tensor, `stride` elements apart, as the second batch level
+};
 
 // One K segment of a product:  sum_k A[b][i][k] * B[b][j][k].  The layouts are per segment and always meant: the engine and the streaming
 // wrappers refuse a segment whose layouts they have no kernel for.
@@ -33,6 +63,18 @@ struct GemmSeg {
   const void* A = nullptr; const void* B = nullptr; int K = 0;
   int a_layout = K_MAJOR, b_layout = K_MAJOR;
   long lda = 0, ldb = 0, sA1 = 0, sA2 = 0, sB1 = 0, sB2 = 0;   // leading dimensions and batch strides, elements
+  // The segment of the product A B (A: M x K, B: K x N, as views).  From  C[i][j] = sum_k A[i][k] B[j][k] : an A stored M x K is K_MAJOR, read
+  // as the transpose of a stored K x M MN_MAJOR; a B stored K x N is MN_MAJOR, read as the transpose of a stored N x K K_MAJOR.
+  // Returns M and N; refuses (ERR_BAD_ARG) when the two disagree on K or on the element type `esz`.
+  int bind(const Mat& a, const Mat& b, int esz, int* M, int* N) {
+    const int ka = a.t ? a.rows : a.cols, kb = b.t ? b.cols : b.rows;
+    if (a.esz != esz || b.esz != esz) { set_last_error("product: operands of %d and %d bytes per element, dtype has %d", a.esz, b.esz, esz); return ERR_BAD_ARG; }
+    if (ka != kb) { set_last_error("product: A has K = %d, B has K = %d", ka, kb); return ERR_BAD_ARG; }
+    A = a.p; a_layout = a.t ? MN_MAJOR : K_MAJOR; lda = a.ld; sA1 = a.s1; sA2 = a.s2;
+    B = b.p; b_layout = b.t ? K_MAJOR : MN_MAJOR; ldb = b.ld; sB1 = b.s1; sB2 = b.s2;
+    K = ka; *M = a.t ? a.cols : a.rows; *N = b.t ? b.rows : b.cols;
+    return OK;
+  }
 };
 
 // A product: its first K segment (the base: A, B, K, a_layout .. sB2), up to three further ones (`seg`), the output, the batch levels, optional terms
@@ -111,6 +153,31 @@ struct GemmArgs : GemmSeg {
     const void* B = nullptr; int N = 0; long ldb = 0, sB1 = 0, sB2 = 0;
     float* C = nullptr; long ldc = 0, sC1 = 0, sC2 = 0;
   } xcols;
+
+  // C = A B from views: the operands through GemmSeg::bind, M and N from them, C's strides from its view (a C that is the transpose of a stored
+  // N x M gets sCi = 1, sCj = ld).  Set dtype / out_dtype (and Cx / nsplit) first: C must have out_dtype's element and the product's shape -- with a
+  // split output its nsplit columns.  Batch counts, alpha, accumulate, ksplit and the epilogues stay the caller's.
+  int product(const Mat& c, const Mat& a, const Mat& b) {
+    AVMOE_TRY(bind(a, b, gemm_dtype_bytes(dtype), &M, &N));
+    const int ci = c.t ? c.cols : c.rows, cj = c.t ? c.rows : c.cols;
+    if (c.esz != gemm_dtype_bytes(out_dtype)) { set_last_error("product: C of %d bytes per element, out_dtype has %d", c.esz, gemm_dtype_bytes(out_dtype)); return ERR_BAD_ARG; }
+    if (ci != M || cj != (nsplit ? nsplit : N)) { set_last_error("product: C is %d x %d, A B is %d x %d", ci, cj, M, N); return ERR_BAD_ARG; }
+    C = const_cast<void*>(c.p); sCi = c.t ? 1 : c.ld; sCj = c.t ? c.ld : 1; sC1 = c.s1; sC2 = c.s2;
+    return OK;
+  }
+  // + A B as K segment i = 1 .. 3 (seg[i - 1]) of a product already bound: it must have the product's M x N
+  int add_segment(int i, const Mat& a, const Mat& b) {
+    int m = 0, n = 0;
+    AVMOE_TRY(seg[i - 1].bind(a, b, gemm_dtype_bytes(dtype), &m, &n));
+    if (m != M || n != N) { set_last_error("product: segment %d is %d x %d, the product %d x %d", i, m, n, M, N); seg[i - 1] = GemmSeg(); return ERR_BAD_ARG; }
+    return OK;
+  }
+  // + row_scale * D (or the D of GEMM_EPI_MULSUB): D stored M x N, in dtype
+  int add_term(const Mat& dm) {
+    if (dm.esz != gemm_dtype_bytes(dtype) || dm.t || dm.rows != M || dm.cols != N) { set_last_error("product: D is %d x %d of %d bytes, the product %d x %d", dm.rows, dm.cols, dm.esz, M, N); return ERR_BAD_ARG; }
+    D = dm.p; sDi = dm.ld; sD1 = dm.s1; sD2 = dm.s2;
+    return OK;
+  }
 };
 
 // The block tile launch_gemm picks by itself for an (M, N) product, before it looks at the block count: what sizes split-K slabs (choose_ksplit)

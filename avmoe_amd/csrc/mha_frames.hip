@@ -16,7 +16,7 @@
 #include "moe_run.h"
 #include "device_utils.h"
 #include "prof.h"
-#include "gemm.h"
+#include "site_views.h"
 #include <algorithm>
 #include <cmath>
 
@@ -82,27 +82,6 @@ int colsum_rows(int bf16, const void* rows, long nrows, int cols, float* part /*
   return k_colsum_f32(part, chunks, cols, cols, 1, 0, out, 0, 1.f, st);
 }
 
-struct Slot {
-  const Dims& d;
-  char* sv; char* sc; const Plan& pl;
-  int slot;
-  size_t esz;
-  char* Win() const { return sv + pl.o_mWin + (size_t)slot * 3 * d.C * d.C * esz; }
-  char* Wout() const { return sv + pl.o_mWout + (size_t)slot * d.C * d.C * esz; }
-  char* QKV() const { return sv + pl.o_mQKV + (size_t)slot * d.NT * 3 * d.C * esz; }
-  char* P() const { return sv + pl.o_mP + (size_t)slot * d.N * d.H * d.S * d.Sp * esz; }
-  char* Pd() const { return sv + pl.o_mPd + (size_t)slot * d.N * d.H * d.S * d.Sp * esz; }
-  char* O() const { return sv + pl.o_mO + (size_t)slot * d.NT * d.C * esz; }
-  char* xr() const { return sv + pl.o_xr + (size_t)slot * d.NT * d.C * esz; }
-};
-
-// the per-(token, head) views of [q | k | v] / of a (S, N, C) tensor: frame s is the row, stride N * width
-void head_view_a(GemmArgs& g, const Dims& d, int width) { g.lda = (long)d.N * width; g.sA1 = width; g.sA2 = d.dh; }
-void head_view_b(GemmArgs& g, const Dims& d, int width) { g.ldb = (long)d.N * width; g.sB1 = width; g.sB2 = d.dh; }
-void head_view_c(GemmArgs& g, const Dims& d, int width) { g.sCi = (long)d.N * width; g.sC1 = width; g.sC2 = d.dh; }
-void mat_view_a(GemmArgs& g, const Dims& d) { g.lda = d.Sp; g.sA1 = (long)d.H * d.S * d.Sp; g.sA2 = (long)d.S * d.Sp; }
-void mat_view_c(GemmArgs& g, const Dims& d) { g.sCi = d.Sp; g.sC1 = (long)d.H * d.S * d.Sp; g.sC2 = (long)d.S * d.Sp; }
-
 }  // namespace
 
 int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& ep, int slot, char* sv, char* sc, hipStream_t st) {
@@ -110,45 +89,46 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
   ProfScope ps_("mha_frames_forward", 0.0, 0.0, st);
   if (!ep.sa_in_w || !ep.sa_in_b || !ep.sa_out_w || !ep.sa_out_b) { set_last_error("moe: self_attention.* pointers missing"); return ERR_BAD_ARG; }
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
-  const Slot b{d, sv, sc, pl, slot, (size_t)d.esz};
   const long mats = (long)d.N * d.H;
-  auto base = [&]() { GemmArgs g; g.dtype = dt; g.out_dtype = dt; return g; };
-  AVMOE_TRY(k_cast(d.bf16, ep.sa_in_w, 3L * d.C, d.C, d.C, b.Win(), d.C, st));
-  AVMOE_TRY(k_cast(d.bf16, ep.sa_out_w, d.C, d.C, d.C, b.Wout(), d.C, st));
+  namespace vw = views;
+  const Mat Xs = vw::tokens_x(d, X), Win = vw::mWin(pl, sv, slot), Wout = vw::mWout(pl, sv, slot), QKV = vw::mQKV(pl, sv, slot), O = vw::mO(pl, sv, slot);
+  const Mat P = vw::mP(pl, sv, slot), Sc = vw::mSc(pl, sc), xr = vw::xr(pl, sv, slot);
+  const Mat hd = vw::per_token(d, QKV), q = hd.cols_at(0, d.C).groups(d.H), k = hd.cols_at(d.C, d.C).groups(d.H), v = hd.cols_at(2 * d.C, d.C).groups(d.H);
+  auto base = [&](int out_dt) { GemmArgs g; g.dtype = dt; g.out_dtype = out_dt; return g; };
+  AVMOE_TRY(k_cast(d.bf16, ep.sa_in_w, 3L * d.C, d.C, d.C, (void*)Win.p, d.C, st));
+  AVMOE_TRY(k_cast(d.bf16, ep.sa_out_w, d.C, d.C, d.C, (void*)Wout.p, d.C, st));
   {                                                        // [q | k | v] = X Win^T (+ bin)
-    GemmArgs g = base();
-    g.A = X; g.B = b.Win(); g.C = b.QKV(); g.M = d.NT; g.N = 3 * d.C; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.sCi = 3L * d.C;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(QKV.flat(d.S), Xs.flat(d.S), Win.T()));
     AVMOE_TRY(launch_gemm(g, st));
   }
-  DISPATCH_T(d.bf16, km_add_bias, dim3(grid1d((long)d.NT * 3 * d.C, 8192)), dim3(256), 0, st, (void*)b.QKV(), (const float*)ep.sa_in_b, (long)d.NT, 3 * d.C);
+  DISPATCH_T(d.bf16, km_add_bias, dim3(grid1d((long)d.NT * 3 * d.C, 8192)), dim3(256), 0, st, (void*)QKV.p, (const float*)ep.sa_in_b, (long)d.NT, 3 * d.C);
   AVMOE_CHECK_LAUNCH("mha add_bias");
   {                                                        // scores[n][h] = q k^T / sqrt(dh)
-    GemmArgs g = base();
-    g.A = b.QKV(); g.B = b.QKV() + (size_t)d.C * d.esz; g.C = sc + pl.o_mSc; g.out_dtype = GEMM_F32;
-    g.M = d.S; g.N = d.S; g.K = d.dh; g.nb1 = d.N; g.nb2 = d.H; g.alpha = 1.f / std::sqrt((float)d.dh);
-    head_view_a(g, d, 3 * d.C); head_view_b(g, d, 3 * d.C); mat_view_c(g, d);
+    GemmArgs g = base(GEMM_F32);
+    AVMOE_TRY(g.product(Sc.row_blocks(d.S, d.S), q, k.T()));
+    g.nb1 = d.N; g.nb2 = d.H; g.alpha = 1.f / std::sqrt((float)d.dh);
     AVMOE_TRY(launch_gemm(g, st));
   }
-  AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_mSc), mats * d.S, d.S, d.Sp, b.P(), d.Sp, 1, 1, 1, 1, st));
-  const char* Pd = b.P();
+  AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)Sc.p, mats * d.S, d.S, (int)Sc.ld, (void*)P.p, (int)P.ld, 1, 1, 1, 1, st));
+  Mat Pd = P;
   if (ep.sa_keep) {
-    DISPATCH_T(d.bf16, km_keep, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, (const void*)b.P(), (const float*)ep.sa_keep, (void*)b.Pd(), mats, d.S, d.Sp);
+    Pd = vw::mPd(pl, sv, slot);
+    DISPATCH_T(d.bf16, km_keep, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, P.p, (const float*)ep.sa_keep, (void*)Pd.p, mats, d.S, d.Sp);
     AVMOE_CHECK_LAUNCH("mha keep");
-    Pd = b.Pd();
   }
   {                                                        // o[n][h] = Pd v  -> O (S, N, C)
-    GemmArgs g = base();
-    g.A = Pd; g.B = b.QKV() + (size_t)2 * d.C * d.esz; g.C = b.O();
-    g.M = d.S; g.N = d.dh; g.K = d.S; g.nb1 = d.N; g.nb2 = d.H; g.b_layout = MN_MAJOR;
-    mat_view_a(g, d); head_view_b(g, d, 3 * d.C); head_view_c(g, d, d.C);
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(vw::per_token(d, O).groups(d.H), Pd.row_blocks(d.S, d.S), v));
+    g.nb1 = d.N; g.nb2 = d.H;
     AVMOE_TRY(launch_gemm(g, st));
   }
   {                                                        // xr = O Wout^T + bout - X
-    GemmArgs g = base();
-    g.A = b.O(); g.B = b.Wout(); g.C = b.xr(); g.M = d.NT; g.N = d.C; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.sCi = d.C;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(xr.flat(d.S), O.flat(d.S), Wout.T()));
     AVMOE_TRY(launch_gemm(g, st));
   }
-  DISPATCH_T(d.bf16, km_finish, dim3(grid1d((long)d.NT * d.C, 8192)), dim3(256), 0, st, (void*)b.xr(), (const float*)ep.sa_out_b, X, (long)d.NT, d.C);
+  DISPATCH_T(d.bf16, km_finish, dim3(grid1d((long)d.NT * d.C, 8192)), dim3(256), 0, st, (void*)xr.p, (const float*)ep.sa_out_b, X, (long)d.NT, d.C);
   AVMOE_CHECK_LAUNCH("mha finish");
   return OK;
 }
@@ -160,17 +140,20 @@ int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& 
   const Dims& d = pl.d;
   ProfScope ps_("mha_frames_backward", 0.0, 0.0, st);
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
-  const Slot b{d, sv, sc, pl, slot, (size_t)d.esz};
   const long mats = (long)d.N * d.H;
   float* sink = (float*)(sc + pl.o_mdW);                   // [3C * C | 3C | C]  for gradients nobody asked for
   float* dWin = eg.sa_in_w ? eg.sa_in_w : sink;
   float* dWout = eg.sa_out_w ? eg.sa_out_w : sink;
   float* dbin = eg.sa_in_b ? eg.sa_in_b : sink + (size_t)3 * d.C * d.C;
   float* dbout = eg.sa_out_b ? eg.sa_out_b : sink + (size_t)3 * d.C * d.C + 3 * d.C;
-  const char* Pd = ep.sa_keep ? b.Pd() : b.P();
-  char* dO = sc + pl.o_mdO; char* dS = sc + pl.o_mdS; char* dQKV = sc + pl.o_mdQKV; float* dP = (float*)(sc + pl.o_mSc);
+  namespace vw = views;
+  const Mat Xs = vw::tokens_x(d, X), dxs = vw::tokens_x(d, dxr), Win = vw::mWin(pl, sv, slot), Wout = vw::mWout(pl, sv, slot), O = vw::mO(pl, sv, slot);
+  const Mat P = vw::mP(pl, sv, slot), Pd = (ep.sa_keep ? vw::mPd(pl, sv, slot) : P).row_blocks(d.S, d.S);
+  const Mat dO = vw::mdO(pl, sc), dOh = vw::per_token(d, dO).groups(d.H), dS = vw::mdS(pl, sc), dSm = dS.row_blocks(d.S, d.S), dP = vw::mSc(pl, sc), dQKV = vw::mdQKV(pl, sc);
+  const Mat hd = vw::per_token(d, vw::mQKV(pl, sv, slot)), q = hd.cols_at(0, d.C).groups(d.H), k = hd.cols_at(d.C, d.C).groups(d.H), v = hd.cols_at(2 * d.C, d.C).groups(d.H);
+  const Mat dhd = vw::per_token(d, dQKV), dq = dhd.cols_at(0, d.C).groups(d.H), dk = dhd.cols_at(d.C, d.C).groups(d.H), dv = dhd.cols_at(2 * d.C, d.C).groups(d.H);
   const float alpha = 1.f / std::sqrt((float)d.dh);
-  auto base = [&]() { GemmArgs g; g.dtype = dt; g.out_dtype = dt; g.slabs = slabs; return g; };
+  auto base = [&](int out_dt) { GemmArgs g; g.dtype = dt; g.out_dtype = out_dt; g.slabs = slabs; return g; };
   auto run = [&](GemmArgs& g, bool split) {
     if (split) g.ksplit = choose_ksplit(g, slab_cap);
     return launch_gemm(g, st);
@@ -178,60 +161,54 @@ int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& 
   float* part = (float*)(sc + pl.o_mpart);
   AVMOE_TRY(colsum_rows(d.bf16, dxr, (long)d.NT, d.C, part, dbout, st));
   {                                                        // d Wout = dxr^T O
-    GemmArgs g = base();
-    g.A = dxr; g.B = b.O(); g.C = dWout; g.out_dtype = GEMM_F32;
-    g.M = d.C; g.N = d.C; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.C; g.ldb = d.C; g.sCi = d.C;
+    GemmArgs g = base(GEMM_F32);
+    AVMOE_TRY(g.product(vw::view(dWout, 0, 4, d.C, d.C, d.C), dxs.flat(d.S).T(), O.flat(d.S)));
     AVMOE_TRY(run(g, true));
   }
   {                                                        // d O = dxr Wout
-    GemmArgs g = base();
-    g.A = dxr; g.B = b.Wout(); g.C = dO; g.M = d.NT; g.N = d.C; g.K = d.C; g.lda = d.C; g.b_layout = MN_MAJOR; g.ldb = d.C; g.sCi = d.C;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dO.flat(d.S), dxs.flat(d.S), Wout));
     AVMOE_TRY(run(g, false));
   }
   {                                                        // d Pd[n][h] = dO v^T
-    GemmArgs g = base();
-    g.A = dO; g.B = b.QKV() + (size_t)2 * d.C * d.esz; g.C = dP; g.out_dtype = GEMM_F32;
-    g.M = d.S; g.N = d.S; g.K = d.dh; g.nb1 = d.N; g.nb2 = d.H;
-    head_view_a(g, d, d.C); head_view_b(g, d, 3 * d.C); mat_view_c(g, d);
+    GemmArgs g = base(GEMM_F32);
+    AVMOE_TRY(g.product(dP.row_blocks(d.S, d.S), dOh, v.T()));
+    g.nb1 = d.N; g.nb2 = d.H;
     AVMOE_TRY(run(g, false));
   }
   {                                                        // d v[n][h] = Pd^T dO
-    GemmArgs g = base();
-    g.A = Pd; g.B = dO; g.C = dQKV + (size_t)2 * d.C * d.esz;
-    g.M = d.S; g.N = d.dh; g.K = d.S; g.nb1 = d.N; g.nb2 = d.H; g.a_layout = g.b_layout = MN_MAJOR;
-    mat_view_a(g, d); head_view_b(g, d, d.C); head_view_c(g, d, 3 * d.C);
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dv, Pd.T(), dOh));
+    g.nb1 = d.N; g.nb2 = d.H;
     AVMOE_TRY(run(g, false));
   }
   if (ep.sa_keep) {
-    hipLaunchKernelGGL(km_keep_bwd, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, dP, (const float*)ep.sa_keep, mats, d.S, d.Sp);
+    hipLaunchKernelGGL(km_keep_bwd, dim3(grid1d(mats * d.S * d.Sp, 8192)), dim3(256), 0, st, (float*)dP.p, (const float*)ep.sa_keep, mats, d.S, d.Sp);
     AVMOE_CHECK_LAUNCH("mha keep_bwd");
   }
-  AVMOE_TRY(k_softmax_rows_bwd(d.bf16, b.P(), dP, mats * d.S, d.S, d.Sp, dS, nullptr, 1, 1, st));
+  AVMOE_TRY(k_softmax_rows_bwd(d.bf16, P.p, (const float*)dP.p, mats * d.S, d.S, (int)P.ld, (void*)dS.p, nullptr, 1, 1, st));
   {                                                        // d q[n][h] = dS k / sqrt(dh)
-    GemmArgs g = base();
-    g.A = dS; g.B = b.QKV() + (size_t)d.C * d.esz; g.C = dQKV; g.alpha = alpha;
-    g.M = d.S; g.N = d.dh; g.K = d.S; g.nb1 = d.N; g.nb2 = d.H; g.b_layout = MN_MAJOR;
-    mat_view_a(g, d); head_view_b(g, d, 3 * d.C); head_view_c(g, d, 3 * d.C);
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dq, dSm, k));
+    g.nb1 = d.N; g.nb2 = d.H; g.alpha = alpha;
     AVMOE_TRY(run(g, false));
   }
   {                                                        // d k[n][h] = dS^T q / sqrt(dh)
-    GemmArgs g = base();
-    g.A = dS; g.B = b.QKV(); g.C = dQKV + (size_t)d.C * d.esz; g.alpha = alpha;
-    g.M = d.S; g.N = d.dh; g.K = d.S; g.nb1 = d.N; g.nb2 = d.H; g.a_layout = g.b_layout = MN_MAJOR;
-    mat_view_a(g, d); head_view_b(g, d, 3 * d.C); head_view_c(g, d, 3 * d.C);
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dk, dSm.T(), q));
+    g.nb1 = d.N; g.nb2 = d.H; g.alpha = alpha;
     AVMOE_TRY(run(g, false));
   }
-  AVMOE_TRY(colsum_rows(d.bf16, dQKV, (long)d.NT, 3 * d.C, part, dbin, st));
+  AVMOE_TRY(colsum_rows(d.bf16, dQKV.p, (long)d.NT, 3 * d.C, part, dbin, st));
   {                                                        // d Win = dQKV^T X
-    GemmArgs g = base();
-    g.A = dQKV; g.B = X; g.C = dWin; g.out_dtype = GEMM_F32;
-    g.M = 3 * d.C; g.N = d.C; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = 3L * d.C; g.ldb = d.C; g.sCi = d.C;
+    GemmArgs g = base(GEMM_F32);
+    AVMOE_TRY(g.product(vw::view(dWin, 0, 4, 3 * d.C, d.C, d.C), dQKV.flat(d.S).T(), Xs.flat(d.S)));
     AVMOE_TRY(run(g, true));
   }
   {                                                        // dX += dQKV Win
-    GemmArgs g = base();
-    g.A = dQKV; g.B = b.Win(); g.C = dX; g.M = d.NT; g.N = d.C; g.K = 3 * d.C; g.lda = 3L * d.C; g.b_layout = MN_MAJOR; g.ldb = d.C;
-    g.sCi = d.C; g.accumulate = 1;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(vw::tokens_x(d, dX).flat(d.S), dQKV.flat(d.S), Win));
+    g.accumulate = 1;
     AVMOE_TRY(run(g, false));
   }
   return OK;

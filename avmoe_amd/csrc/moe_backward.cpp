@@ -6,6 +6,7 @@
 #include "pass.h"
 #include "moe_run.h"
 #include "side.h"
+#include "site_views.h"
 
 namespace avmoe {
 
@@ -27,26 +28,14 @@ static const char* at(const char* base, size_t off) { return base ? base + off :
 // Sections are stream-ordered through `scratch`: a caller may put event records / waits between them (AdapterPair orders the
 // two sites' accumulations into the shared token gradients this way) but nothing that touches the workspaces.
 // the operands of  dX[s] = dZx[s] Wt + [dL2 | dsx | 1][s] [T ; 1 ; dm1/N][s] + 2 dSxx X[s]  (phase 5; moe_backward_dx_dy adds the other site's dY to it)
-static void fill_dx_args(GemmArgs& g, const Plan& pl, const void* X, const char* sv, const char* sc, void* dX) {
+static int dx_product(GemmArgs& g, const Plan& pl, const void* X, const char* sv, const char* sc, void* dX) {
   const Dims& d = pl.d;
-  g.A = at(sc, pl.o_Zw); g.B = at(sv, pl.o_Wt); g.C = dX;
-  g.M = d.N; g.N = d.Cg; g.K = d.E * d.dgp; g.a_layout = K_MAJOR; g.b_layout = MN_MAJOR; g.lda = d.DZ; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
-  g.sA1 = (long)d.N * d.DZ; g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg;
-  g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.sC2 = d.Cg; g.out_dtype = d.bf16 ? GEMM_BF16 : GEMM_F32;
-  g.row_scale = (const float*)at(sc, pl.o_rs2x); g.sRS1 = d.N; g.D = X; g.sDi = d.C; g.sD1 = (long)d.N * d.C; g.sD2 = d.Cg;
-  GemmSeg& t = g.seg[0]; t.A = at(sc, pl.o_dL2x); t.B = at(sv, pl.o_Text); t.K = d.KLT; t.a_layout = K_MAJOR; t.b_layout = MN_MAJOR; t.lda = d.KLp; t.ldb = d.C;
-  t.sA1 = (long)d.N * d.KLp; t.sB1 = (long)d.KLT * d.C; t.sB2 = d.Cg;
-}
-// the operands of  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  (phase 6; without a cross-modal expert: wbar (x) d ybar[s] alone, `q` stays unset) as the
-// K segments `v` and `q` of a product.  sB2: what B advances by per group of that product -- 0 for the site's own ungrouped one, the other site's Cg
-// when moe_backward_dx_dy hangs the two behind that site's dX product
-static void fill_dy_args(GemmSeg& v, GemmSeg& q, const Plan& pl, const char* sv, const char* sc, long sB2) {
-  const Dims& d = pl.d;
-  v.A = at(sv, pl.o_BmX); v.B = at(sc, pl.o_dV); v.K = d.Kcyb; v.a_layout = v.b_layout = MN_MAJOR; v.lda = d.Mb; v.ldb = d.Cy;
-  v.sA1 = (long)d.Kcyb * d.Mb; v.sB1 = (long)d.Kcyb * d.Cy; v.sB2 = sB2;
-  if (d.Kcy == 0) return;
-  q.A = at(sc, pl.o_dRT); q.B = at(sv, pl.o_Qx); q.K = d.Kcy; q.a_layout = K_MAJOR; q.b_layout = MN_MAJOR; q.lda = d.Kcyp; q.ldb = d.Cy;
-  q.sA1 = (long)d.M * d.Kcyp; q.sB2 = sB2;
+  g.out_dtype = d.bf16 ? GEMM_BF16 : GEMM_F32;
+  AVMOE_TRY(g.product(views::tokens_x(d, dX).groups(d.g), views::Zw(pl, sc).groups(d.g), views::Wt(pl, sv)));
+  AVMOE_TRY(g.add_segment(1, views::dL2x(pl, sc), views::Text(pl, sv).groups(d.g)));
+  AVMOE_TRY(g.add_term(views::tokens_x(d, X).groups(d.g)));
+  g.nb1 = d.S; g.nb2 = d.g; g.row_scale = (const float*)at(sc, pl.o_rs2x); g.sRS1 = d.N;
+  return OK;
 }
 
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const void* dOut, const float* lb_grad,
@@ -63,7 +52,7 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
   float* slabs = (float*)(sc + pl.o_slabs);
   const size_t slab_cap = slab_floats(d);
-  auto base = [&]() { GemmArgs g; g.dtype = dt; g.out_dtype = GEMM_F32; g.slabs = slabs; g.split3 = AVMOE_BWD_PLANES; return g; };      // (split3: fp32 sites only, gemm.h; moe_run.h: two planes in the backward)
+  auto base = [&](int out_dt = GEMM_F32) { GemmArgs g; g.dtype = dt; g.out_dtype = out_dt; g.slabs = slabs; g.split3 = AVMOE_BWD_PLANES; return g; };      // (split3: fp32 sites only, gemm.h; moe_run.h: two planes in the backward)
   auto run_on = [&](GemmArgs& g, bool split, hipStream_t on) {
     if (split) g.ksplit = choose_ksplit(g, slab_cap);
     return launch_gemm(g, on);
@@ -80,6 +69,13 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   Side* side = side_worth(d) ? side_acquire(st) : nullptr;
   SideScope fk1(side, st), fk2(side, st);                  // joined on every way out (error returns included)
   const size_t esz = d.esz;
+  // the site's tensors (site_views.h); `f`: all frames as one matrix, `g`: the channel groups as the second batch level
+  namespace vw = views;
+  const Mat Xs = vw::tokens_x(d, X), Ys = vw::tokens_y(d, Y), dXs = vw::tokens_x(d, dX), Xfg = Xs.flat(d.S).groups(d.g), dOfg = vw::tokens_x(d, dOut).flat(d.S).groups(d.g);
+  const Mat Wt = vw::Wt(pl, sv), Text = vw::Text(pl, sv), WfT = vw::WfT(pl, sv), T0 = vw::T0T(pl, sv), WcK = vw::WcK(pl, sv), Qx = vw::Qx(pl, sv), BmX = vw::BmX(pl, sv);
+  const Mat Zw = vw::Zw(pl, sc), Zwfg = Zw.flat(d.S).groups(d.g), dZRfg = vw::dZR(pl, sc).flat(d.S).groups(d.g), dxr = vw::dxr(pl, sc), dxrfg = dxr.flat(d.S).groups(d.g);
+  const Mat dWt = vw::dWt(pl, sc), dTW = vw::dTW(pl, sc), dT = vw::dT(pl, sc), dTT = vw::dTT(pl, sc), dL2x = vw::dL2x(pl, sc), dT0 = vw::dT0(pl, sc);
+  const Mat dTy = vw::dTy(pl, sc), dV = vw::dV(pl, sc), dBmT = vw::dBmT(pl, sc), dWcK = vw::dWcK(pl, sc), dRT = vw::dRT(pl, sc), dQT = vw::dQT(pl, sc), dWf = vw::dWf(pl, sc);
   // development builds: AVMOE_BWD_STOP=n returns after the n-th step of section 1 (1 the two GEMMs against dOut, 2 post_small_bwd, 3 the
   // Gram products, 4 post_prep_bwd, 5 mid_bwd, 6 router_bwd) -- workspaces as that step left them (tests/dev/race_buffers.py)
 #define BWD_STOP(n) do { if (sw.bwd_stop == (n)) return OK; } while (0)
@@ -92,21 +88,22 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   // a GEMM of the helper stream runs -- tile_gen.inc::gen_lds_request has the reason)
   const bool fork1 = side && (sw.side_mask & 2) && (d.gram64 || !d.ln_post) && !d.gen;
   int dap16 = 1;     // dApost stored as [E x 32 bottleneck columns in T | 3 E scalar columns in fp32 (dApx)]: the register-resident bf16 path
+  const int npost = (d.KP % 4 == 0) ? d.KP : d.KPp;      // dApost's columns: KP, or the padded KPp when KP is not a multiple of 4 (2 or 3 experts): Bpost's
+                                                         // padding columns are zero, the streaming kernel wants whole 4-column vectors, and nobody reads the padding of dAp
+  const Mat Bpg = vw::Bpost(pl, sv).row_blocks(d.Cg, d.Cg).cols_at(0, npost);
   GemmArgs gb = base();                                    // dBpost = dOut^T Apost
-  gb.A = dOut; gb.B = sv + pl.o_Apost; gb.C = sc + pl.o_dBp;
-  gb.M = d.Cg; gb.N = d.KP; gb.K = d.NT; gb.a_layout = gb.b_layout = MN_MAJOR; gb.lda = d.C; gb.ldb = (long)d.g * d.KPp; gb.nb2 = d.g;
-  gb.sA2 = d.Cg; gb.sB2 = d.KPp; gb.sCi = d.KPp; gb.sC2 = (long)d.Cg * d.KPp;
+  AVMOE_TRY(gb.product(vw::dBp(pl, sc).row_blocks(d.Cg, d.Cg).cols_at(0, d.KP), dOfg.T(), vw::Apost(pl, sv).groups(d.g).cols_at(0, d.KP)));
+  gb.nb2 = d.g;
   leaf(gb, 1);
   GemmArgs ga = base();                                    // dApost = dOut Bpost
-  ga.A = dOut; ga.B = sv + pl.o_Bpost; ga.C = sc + pl.o_dAp;
-  // N = KP, or the padded KPp when KP is not a multiple of 4 (2 or 3 experts): Bpost's padding columns are zero, the streaming
-  // kernel wants whole 4-column vectors, and nobody reads the padding of dAp
-  ga.M = d.NT; ga.N = (d.KP % 4 == 0) ? d.KP : d.KPp; ga.K = d.Cg; ga.lda = d.C; ga.b_layout = MN_MAJOR; ga.ldb = d.KPp; ga.nb2 = d.g;
-  ga.sA2 = d.Cg; ga.sB2 = (long)d.Cg * d.KPp; ga.sCi = (long)d.g * d.KPp; ga.sC2 = d.KPp;
-  // ... as bf16 main columns + fp32 scalar columns (sites that keep z in bf16): 640 instead of 1152 bytes per token, written and re-read
-  GemmArgs h = ga;
-  h.out_dtype = GEMM_BF16; h.Cx = (float*)(sc + pl.o_dApx); h.nsplit = d.E * d.dgp; h.ldcx = (long)d.g * d.XW; h.sCx2 = d.XW;
-  h.sCi = (long)d.g * h.nsplit; h.sC2 = h.nsplit;        // the T columns as rows of their own (E * dgp wide: whole 128-byte lines), not inside KPp-wide rows
+  AVMOE_TRY(ga.product(vw::dAp(pl, sc).groups(d.g).cols_at(0, npost), dOfg, Bpg));
+  ga.nb2 = d.g;
+  // ... as bf16 main columns + fp32 scalar columns (sites that keep z in bf16): 640 instead of 1152 bytes per token, written and re-read;
+  // the T columns as rows of their own (E * dgp wide: whole 128-byte lines), not inside KPp-wide rows
+  GemmArgs h = base(GEMM_BF16);
+  h.Cx = (float*)(sc + pl.o_dApx); h.nsplit = d.E * d.dgp; h.ldcx = (long)d.g * d.XW; h.sCx2 = d.XW;
+  AVMOE_TRY(h.product(vw::dAp_split(pl, sc).groups(d.g), dOfg, Bpg));
+  h.nb2 = d.g;
   // The forms, in order: both products from one pass over dOut (dpost_pair.hip: the tuned bf16 shape); else dBpost on the engine (forked beside) and
   // dApost in its split form from the streaming GEMM; else dApost in one fp32 array from the engine (dap16 = 0)
   const bool split = d.zsz == 2;                           // (sites that keep z in bf16: a property of the plan, which no descriptor carries)
@@ -130,9 +127,8 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
                        (const float*)(sv + pl.o_bn1)));
   } else if (d.ln_post) {                                  // ... as batched engine GEMMs on Zw = dSoo z'
     GemmArgs g = base();
-    g.A = sc + pl.o_Zw; g.B = sc + pl.o_Zp; g.C = sc + pl.o_dGq;
-    g.M = d.dgp; g.N = d.dgp; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = g.ldb = d.DZ;
-    g.nb2 = d.g * d.E; g.sA2 = g.sB2 = d.dgp; g.sCi = d.dgp; g.sC2 = (long)d.dgp * d.dgp;
+    AVMOE_TRY(g.product(vw::dGq(pl, sc).row_blocks(d.dgp, d.dgp), Zw.flat(d.S).groups(d.g * d.E).T(), vw::Zp(pl, sc).flat(d.S).groups(d.g * d.E)));
+    g.nb2 = d.g * d.E;
     AVMOE_TRY(run(g, true));
   }
   if (fk1.open) AVMOE_TRY(fk1.join());                     // (forked only when dpost_pair did not serve)
@@ -149,14 +145,13 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   AVMOE_TRY(k_pre_small_bwd(pass, grads, st));
   }
   if (parts & (2 | 32 | 64)) {   // =============================== section 2: phase 5 ====================================
-  const char* dZx = sc + pl.o_Zw;
   const bool do_dx = (parts & (2 | 64)) != 0, do_rest = (parts & (2 | 32)) != 0;
   const bool fork2 = side && (sw.side_mask & 4) && !d.mha && !d.nxn && (parts & 2);             // (those variants go on accumulating into dX below)
 
   // ---- phase 5: GEMMs against X --------------------------------------------------------------------
   if (do_dx) {   // dX[s] = dZx[s] Wt + [dL2 | dsx | 1][s] [T ; 1 ; dm1/N][s] + 2 dSxx X[s]   -- one pass: two K segments + row-scale epilogue
     GemmArgs g = base();
-    fill_dx_args(g, pl, X, sv, sc, dX);
+    AVMOE_TRY(dx_product(g, pl, X, sv, sc, dX));
     g.accumulate = d.acc_dx;
     leaf(g, 16);
     if (fork2) AVMOE_TRY(fk2.fork());
@@ -168,12 +163,10 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
       if (!d.nxn_of_e[e]) continue;
       const int slot = d.xr_of_e[e];
       {                                                    // dxr = dZR[:, expert e] Wt_e + (2 dSxx) xr
-        GemmArgs g = base();
-        g.A = sc + pl.o_dZR + (size_t)e * d.dgp * esz; g.B = sv + pl.o_Wt + (size_t)e * d.dgp * d.Cg * esz; g.C = sc + pl.o_dxr;
-        g.M = d.NT; g.N = d.Cg; g.K = d.dgp; g.lda = d.DZ; g.b_layout = MN_MAJOR; g.ldb = d.Cg; g.nb2 = d.g;
-        g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.C; g.sC2 = d.Cg; g.out_dtype = dt;
-        g.row_scale = (const float*)(sc + pl.o_dsr) + (size_t)slot * 3 * d.NT + d.NT;
-        g.D = sv + pl.o_xr + (size_t)slot * d.NT * d.C * esz; g.sDi = d.C; g.sD2 = d.Cg;
+        GemmArgs g = base(dt);
+        AVMOE_TRY(g.product(dxrfg, dZRfg.cols_at(e * d.dgp, d.dgp), Wt.rows_at(e * d.dgp, d.dgp)));
+        AVMOE_TRY(g.add_term(vw::xr(pl, sv, slot).flat(d.S).groups(d.g)));
+        g.nb2 = d.g; g.row_scale = (const float*)(sc + pl.o_dsr) + (size_t)slot * 3 * d.NT + d.NT;
         AVMOE_TRY(run(g, false));
       }
       AVMOE_TRY(k_nxn_axpy(pl, X, sv, sc, dX, slot, 1, st));   // dxr += dsr2 X + dsr0 ; dX += dsr2 xr - dxr (input replaced)
@@ -181,149 +174,130 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
     }
   } else if (d.nxn) {   // ---- AVVP N x N block: back through ZR = xr Wt^T, the three row sums and xr = att^T X --------------------
     {                                                      // dxr = dZR Wt + (2 g^2 dSxx) xr
-      GemmArgs g = base();
-      g.A = sc + pl.o_dZR; g.B = sv + pl.o_Wt; g.C = sc + pl.o_dxr;
-      g.M = d.NT; g.N = d.Cg; g.K = d.E * d.dgp; g.lda = d.DZ; g.b_layout = MN_MAJOR; g.ldb = d.Cg; g.nb2 = d.g;
-      g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.C; g.sC2 = d.Cg; g.out_dtype = dt;
-      g.row_scale = (const float*)(sc + pl.o_dsr) + d.NT; g.D = sv + pl.o_xr; g.sDi = d.C; g.sD2 = d.Cg;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(dxrfg, dZRfg, Wt));
+      AVMOE_TRY(g.add_term(vw::xr(pl, sv, 0).flat(d.S).groups(d.g)));
+      g.nb2 = d.g; g.row_scale = (const float*)(sc + pl.o_dsr) + d.NT;
       AVMOE_TRY(run(g, false));
     }
     AVMOE_TRY(k_nxn_axpy(pl, X, sv, sc, dX, 0, 0, st));      // dxr += dsr2 X + dsr0 ; dX += dsr2 xr
     for (int s0 = 0; s0 < d.S; s0 += d.nxc) {              // d.nxc frames at a time (all of them when the forward kept att: moe_plan.cpp)
       const int ns = std::min(d.nxc, d.S - s0);
-      const size_t xo = (size_t)s0 * d.N * d.C * esz;
-      const char* Xc = (const char*)X + xo;
-      const char* dxc = sc + pl.o_dxr + xo;
-      char* dXc = (char*)dX + xo;
+      const Mat Xm = Xs.frames_at(s0), dxm = dxr.frames_at(s0), dXm = dXs.frames_at(s0), att = vw::att(pl, sv), dSc = vw::dSc(pl, sc);
+      const void* Xc = Xm.p; const void* dxc = dxm.p; void* dXc = (void*)dXm.p;
+      const int Np = (int)att.ld;                          // (row stride of att / dSc: what the strip kernels take)
       if (d.nflash) {
         // the strip kernels re-form att from the kept row log-sum-exp in their accumulators: neither the softmax nor y = att dxr exists in memory
         const float* lse = (const float*)(sv + pl.o_nlse) + (size_t)s0 * d.N;
-        AVMOE_TRY(k_nxn_y(Xc, dxc, ns, d.N, d.C, d.Np, lse, (float*)(sc + pl.o_nrd), dXc, st));           // rowdot = X . (att dxr) ; dX += att dxr
+        AVMOE_TRY(k_nxn_y(Xc, dxc, ns, d.N, d.C, Np, lse, (float*)(sc + pl.o_nrd), dXc, st));           // rowdot = X . (att dxr) ; dX += att dxr
         // dX += dS X + dS^T X, dS = att * (X dxr^T - rowdot) formed in the accumulators of both kernels
-        AVMOE_TRY(k_nxn_dx(0, Xc, dxc, ns, d.N, d.C, d.Np, lse, (const float*)(sc + pl.o_nrd), dXc, st));
-        AVMOE_TRY(k_nxn_dx(1, Xc, dxc, ns, d.N, d.C, d.Np, lse, (const float*)(sc + pl.o_nrd), dXc, st));
+        AVMOE_TRY(k_nxn_dx(0, Xc, dxc, ns, d.N, d.C, Np, lse, (const float*)(sc + pl.o_nrd), dXc, st));
+        AVMOE_TRY(k_nxn_dx(1, Xc, dxc, ns, d.N, d.C, Np, lse, (const float*)(sc + pl.o_nrd), dXc, st));
         continue;
       } else {
-        if (d.nxc < d.S && nxn_att_ok(d.bf16, d.N, d.C, d.Np)) {
-          AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, d.Np, (float*)(sv + pl.o_nlse) + (size_t)s0 * d.N, sv + pl.o_att, 1, st));
+        if (d.nxc < d.S && nxn_att_ok(d.bf16, d.N, d.C, Np)) {
+          AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, Np, (float*)(sv + pl.o_nlse) + (size_t)s0 * d.N, sv + pl.o_att, 1, st));
         } else if (d.nxc < d.S) {                            // the forward ran in chunks too: att of these frames again, from the kept row log-sum-exp
-          GemmArgs g = base();
-          g.A = Xc; g.B = Xc; g.C = sv + pl.o_att;
-          g.M = d.N; g.N = d.N; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = ns; g.sA1 = g.sB1 = (long)d.N * d.C;
-          g.sCi = d.Np; g.sC1 = (long)d.N * d.Np; g.out_dtype = dt;
+          GemmArgs g = base(dt);
+          AVMOE_TRY(g.product(att, Xm, Xm.T()));
+          g.nb1 = ns;
           g.epi = GEMM_EPI_EXP; g.row_lse = (const float*)(sv + pl.o_nlse) + (size_t)s0 * d.N;
           g.split3 = AVMOE_FWD_SPLIT3;                       // (the forward's arithmetic: the chunked site must re-form the very att the unchunked one kept)
           AVMOE_TRY(run(g, false));
         }
         {                                                    // y[s] = att[s] dxr[s]   (fp32): the direct term of dX and the softmax's row term
           GemmArgs g = base();
-          g.A = sv + pl.o_att; g.B = dxc; g.C = sc + pl.o_nyt;
-          g.M = d.N; g.N = d.C; g.K = d.N; g.lda = d.Np; g.b_layout = MN_MAJOR; g.ldb = d.C; g.nb1 = ns;
-          g.sA1 = (long)d.N * d.Np; g.sB1 = (long)d.N * d.C; g.sCi = d.C; g.sC1 = (long)d.N * d.C;
+          AVMOE_TRY(g.product(vw::nyt(pl, sc), att, dxm));
+          g.nb1 = ns;
           AVMOE_TRY(run(g, true));
         }
         // dX[s] += y[s] ; rowdot_i = X_i . y_i  ( = sum_j att_ij d att_ij, with d att_ij = X_i . dxr_j )
         AVMOE_TRY(k_nxn_rowdot(d.bf16, Xc, (const float*)(sc + pl.o_nyt), (long)ns * d.N, d.C, dXc, (float*)(sc + pl.o_nrd), st));
-        if (nxn_att_ok(d.bf16, d.N, d.C, d.Np)) {            // dSc[s] = att[s] * (X[s] dxr[s]^T - rowdot): d att never leaves the chip
-          AVMOE_TRY(k_nxn_att_bwd(Xc, dxc, ns, d.N, d.C, d.Np, (const float*)(sc + pl.o_nrd), sv + pl.o_att, sc + pl.o_dSc, st));
+        if (nxn_att_ok(d.bf16, d.N, d.C, Np)) {            // dSc[s] = att[s] * (X[s] dxr[s]^T - rowdot): d att never leaves the chip
+          AVMOE_TRY(k_nxn_att_bwd(Xc, dxc, ns, d.N, d.C, Np, (const float*)(sc + pl.o_nrd), sv + pl.o_att, sc + pl.o_dSc, st));
         } else {
-          GemmArgs g = base();
-          g.A = Xc; g.B = dxc; g.C = sc + pl.o_dSc;
-          g.M = d.N; g.N = d.N; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = ns; g.sA1 = g.sB1 = (long)d.N * d.C;
-          g.sCi = d.Np; g.sC1 = (long)d.N * d.Np; g.out_dtype = dt;
-          g.epi = GEMM_EPI_MULSUB; g.row_lse = (const float*)(sc + pl.o_nrd); g.D = sv + pl.o_att; g.sDi = d.Np; g.sD1 = (long)d.N * d.Np;
+          GemmArgs g = base(dt);
+          AVMOE_TRY(g.product(dSc, Xm, dxm.T()));
+          AVMOE_TRY(g.add_term(att));
+          g.nb1 = ns; g.epi = GEMM_EPI_MULSUB; g.row_lse = (const float*)(sc + pl.o_nrd);
           AVMOE_TRY(run(g, false));
         }
       }
       for (int tr = 0; tr < 2; ++tr) {                     // dX[s] += dSc[s] X[s]  and  dSc[s]^T X[s]
-        GemmArgs g = base();
-        g.A = sc + pl.o_dSc; g.B = Xc; g.C = dXc;
-        g.M = d.N; g.N = d.C; g.K = d.N; g.a_layout = tr ? MN_MAJOR : K_MAJOR; g.lda = d.Np; g.b_layout = MN_MAJOR; g.ldb = d.C;
-        g.nb1 = ns; g.sA1 = (long)d.N * d.Np; g.sB1 = (long)d.N * d.C; g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.out_dtype = dt;
-        g.accumulate = 1;
+        GemmArgs g = base(dt);
+        AVMOE_TRY(g.product(dXm, tr ? dSc.T() : dSc, Xm));
+        g.nb1 = ns; g.accumulate = 1;
         AVMOE_TRY(run(g, true));
       }
     }
   }
   if (d.El > 0) {                                          // dTW[s][slot l] = gate * a^T dzraw  (own expert's columns), all slots in one launch
     const int e0 = d.e_of_lat[0];                          // (latent experts are consecutive: the multimodal ones come first, AVS v2 makes all of them latent)
-    GemmArgs g = base();
-    g.A = sc + pl.o_ag; g.B = dZx + (size_t)e0 * d.dgp * esz;
-    g.C = sc + pl.o_dTW + (size_t)e0 * d.dgp * esz;
-    g.M = d.K; g.N = d.dgp; g.K = d.N; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Kp; g.ldb = d.DZ; g.nb1 = d.S; g.nb2 = d.g; g.nb3 = d.El;
-    g.sA1 = (long)d.N * d.Kp; g.sB1 = (long)d.N * d.DZ; g.sB2 = (long)d.E * d.dgp;
-    g.sA3 = d.aL; g.sB3 = d.dgp; g.sC3 = (long)d.Kp * d.DZ + d.dgp;      // (ag: per-slot planes [slot][token][Kp])
-    g.sCi = d.DZ; g.sC1 = (long)d.KLT * d.DZ; g.sC2 = (long)d.E * d.dgp; g.out_dtype = dt;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dTW.rows_at(0, d.K).groups(d.g).cols_at(e0 * d.dgp, d.dgp), vw::ag(pl, sc).T(), Zw.groups(d.g).cols_at(e0 * d.dgp, d.dgp)));
+    g.nb1 = d.S; g.nb2 = d.g; g.nb3 = d.El;               // third level: the latent slots -- ag's planes, the experts' columns, dTW's Kp-row slots
+    g.sA3 = d.aL; g.sB3 = d.dgp; g.sC3 = (long)d.Kp * d.DZ + d.dgp;
     AVMOE_TRY(run(g, false));
   }
   bool pair_done = d.bf16 && d.El > 0;                     // dWt = dZx^T X and dT[s] = dL2[s]^T X[s] in ONE pass over X (bf16 sites with latent tokens: TokPairArgs has no dtype)
   if (pair_done) {
-    TokPairArgs t;
-    t.A1 = dZx; t.lda1 = d.DZ; t.M1 = d.E * d.dgp; t.sA1g = (long)d.E * d.dgp;
-    t.A2 = sc + pl.o_dL2x; t.lda2 = d.KLp; t.M2 = d.KL;
-    t.X = X; t.ldx = d.C; t.S = d.S; t.N = d.N; t.g = d.g; t.Cg = d.Cg;
-    t.C1 = (float*)(sc + pl.o_dWt); t.C2 = (float*)(sc + pl.o_dT); t.slabs = slabs; t.slab_cap = slab_cap;
+    const Mat l2 = dL2x.cols_at(0, d.KL);
+    TokPairArgs t{Zwfg.p, Zwfg.ld, Zwfg.cols, Zwfg.s2, l2.p, l2.ld, l2.cols, Xs.p, Xs.ld, d.S, d.N, d.g, d.Cg, (float*)dWt.p, (float*)dT.p, slabs, slab_cap};
     // as one streaming pass with every accumulator in registers (tok_pair2.hip: the tuned shape), or in the tiled form, or as the two engine products below
     auto two_products = [&](const TokPairArgs&, hipStream_t) { pair_done = false; return (int)OK; };
     AVMOE_TRY(try_forms(t, st, launch_tok_pair2, launch_gemm_tokpair, two_products));
   }
   {                                                        // dWt = dZx^T X  + dTW^T Text
     GemmArgs g = base();
-    g.A = dZx; g.B = X; g.C = sc + pl.o_dWt;
-    g.M = d.E * d.dgp; g.N = d.Cg; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.DZ; g.ldb = d.C; g.nb2 = d.g;
-    g.sA2 = (long)d.E * d.dgp; g.sB2 = d.Cg; g.sCi = d.Cg; g.sC2 = (long)d.E * d.dgp * d.Cg;
+    AVMOE_TRY(g.product(dWt, Zwfg.T(), Xfg));
+    g.nb2 = d.g;
     leaf(g, 2);
     if (!pair_done) AVMOE_TRY(run(g, true));
     if (d.El > 0) {
       GemmArgs h = g;
-      h.A = sc + pl.o_dTW; h.B = sv + pl.o_Text; h.K = d.S * d.KLT; h.accumulate = 1; h.ksplit = 1;
+      AVMOE_TRY(h.product(dWt, dTW.flat(d.S).groups(d.g).T(), Text.flat(d.S).groups(d.g)));
+      h.accumulate = 1; h.ksplit = 1;
       AVMOE_TRY(run(h, true));
     }
     if (d.mha) {                                           // + dZR[:, expert e]^T xr_e
       for (int e = 0; e < d.E; ++e) {
         if (!d.nxn_of_e[e]) continue;
         GemmArgs h = g;
-        h.A = sc + pl.o_dZR + (size_t)e * d.dgp * esz; h.B = sv + pl.o_xr + (size_t)d.xr_of_e[e] * d.NT * d.C * esz;
-        h.C = sc + pl.o_dWt + (size_t)e * d.dgp * d.Cg * 4; h.M = d.dgp; h.accumulate = 1; h.ksplit = 1;
+        AVMOE_TRY(h.product(dWt.rows_at(e * d.dgp, d.dgp), dZRfg.cols_at(e * d.dgp, d.dgp).T(), vw::xr(pl, sv, d.xr_of_e[e]).flat(d.S).groups(d.g)));
+        h.accumulate = 1; h.ksplit = 1;
         AVMOE_TRY(run(h, true));
       }
     } else if (d.nxn) {                                    // + dZR^T xr
       GemmArgs h = g;
-      h.A = sc + pl.o_dZR; h.B = sv + pl.o_xr; h.accumulate = 1; h.ksplit = 1;
+      AVMOE_TRY(h.product(dWt, dZRfg.T(), vw::xr(pl, sv, 0).flat(d.S).groups(d.g)));
+      h.accumulate = 1; h.ksplit = 1;
       AVMOE_TRY(run(h, true));
     }
   }
   if (d.El > 0) {
     if (!pair_done) {                                      // dT[s] = dL2[s]^T X[s]
       GemmArgs g = base();
-      g.A = sc + pl.o_dL2x; g.B = X; g.C = sc + pl.o_dT;
-      g.M = d.KL; g.N = d.C; g.K = d.N; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.KLp; g.ldb = d.C; g.nb1 = d.S;
-      g.sA1 = (long)d.N * d.KLp; g.sB1 = (long)d.N * d.C; g.sCi = d.C; g.sC1 = (long)d.KL * d.C;
+      AVMOE_TRY(g.product(dT, dL2x.cols_at(0, d.KL).T(), Xs));
+      g.nb1 = d.S;
       leaf(g, 4);
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dT += dTW Wt
       GemmArgs g = base();
-      g.A = sc + pl.o_dTW; g.B = sv + pl.o_Wt; g.C = sc + pl.o_dT;
-      g.M = d.KL; g.N = d.Cg; g.K = d.E * d.dgp; g.lda = d.DZ; g.b_layout = MN_MAJOR; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
-      g.sA1 = (long)d.KLT * d.DZ; g.sA2 = (long)d.E * d.dgp; g.sB2 = (long)d.E * d.dgp * d.Cg;
-      g.sCi = d.C; g.sC1 = (long)d.KL * d.C; g.sC2 = d.Cg; g.accumulate = 1;
+      AVMOE_TRY(g.product(dT.groups(d.g), dTW.rows_at(0, d.KL).groups(d.g), Wt));
+      g.nb1 = d.S; g.nb2 = d.g; g.accumulate = 1;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dTT[s][l] = sum_t du3 a a^T   (symmetric)
-      GemmArgs g = base();
-      g.A = sc + pl.o_aw; g.B = sv + pl.o_a; g.C = sc + pl.o_dTT;
-      g.M = d.K; g.N = d.K; g.K = d.N; g.a_layout = g.b_layout = MN_MAJOR; g.lda = g.ldb = d.Kp; g.nb1 = d.S; g.nb2 = d.El;
-      g.sA1 = g.sB1 = (long)d.N * d.Kp; g.sA2 = g.sB2 = d.aL;      // (aw, a: per-slot planes)
-      g.sCi = d.Kp; g.sC1 = (long)d.El * d.K * d.Kp; g.sC2 = (long)d.K * d.Kp; g.out_dtype = dt;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(dTT.row_blocks(d.K, d.K), vw::aw(pl, sc).planes(d.aL).T(), vw::a(pl, sv).planes(d.aL)));      // (aw, a: per-slot planes)
+      g.nb1 = d.S; g.nb2 = d.El;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dT += 2 dTT T
       GemmArgs g = base();
-      g.A = sc + pl.o_dTT; g.B = sv + pl.o_Text; g.C = sc + pl.o_dT;
-      g.M = d.K; g.N = d.C; g.K = d.K; g.lda = d.Kp; g.b_layout = MN_MAJOR; g.ldb = d.C; g.nb1 = d.S; g.nb2 = d.El;
-      g.sA1 = (long)d.El * d.K * d.Kp; g.sA2 = (long)d.K * d.Kp; g.sB1 = (long)d.KLT * d.C; g.sB2 = (long)d.Kp * d.C;
-      g.sCi = d.C; g.sC1 = (long)d.KL * d.C; g.sC2 = (long)d.Kp * d.C; g.alpha = 2.f; g.accumulate = 1;
+      AVMOE_TRY(g.product(dT.row_blocks(d.Kp, d.K), dTT.row_blocks(d.K, d.K), Text.row_blocks(d.Kp, d.K)));
+      g.nb1 = d.S; g.nb2 = d.El; g.alpha = 2.f; g.accumulate = 1;
       AVMOE_TRY(run(g, false));
     }
   }
@@ -340,23 +314,20 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   if (do6a) {
   // ---- phase 6a: cross-modal hop-1 chain back to Y and the remap parameters -------------------------
   {                                                        // dV = dTy Wf   (row Kcy: d ybar)
-    GemmArgs g = base();
-    g.A = sc + pl.o_dTy; g.B = sv + pl.o_WfT; g.C = sc + pl.o_dV;
-    g.M = d.S * d.Kcyb; g.N = d.Cy; g.K = d.C; g.lda = d.C; g.b_layout = MN_MAJOR; g.ldb = d.Cy; g.sCi = d.Cy; g.out_dtype = dt;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(dV.flat(d.S), dTy.flat(d.S), WfT));
     AVMOE_TRY(run(g, false));
   }
   {                                                        // dWf = dTy^T V
     GemmArgs g = base();
-    g.A = sc + pl.o_dTy; g.B = sv + pl.o_V; g.C = sc + pl.o_dWf;
-    g.M = d.C; g.N = d.Cy; g.K = d.S * d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.C; g.ldb = d.Cy; g.sCi = d.Cy;
+    AVMOE_TRY(g.product(dWf, dTy.flat(d.S).T(), vw::V(pl, sv).flat(d.S)));
     leaf(g, 8);
     AVMOE_TRY(run(g, true));
   }
   {                                                        // dBm[s] = dV[s] Y[s]^T
     GemmArgs g = base();
-    g.A = sc + pl.o_dV; g.B = Y; g.C = sc + pl.o_dBm;
-    g.M = d.Kcyb; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S;
-    g.sA1 = (long)d.Kcyb * d.Cy; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Mb; g.sC1 = (long)d.Kcyb * d.Mb;
+    AVMOE_TRY(g.product(vw::dBm(pl, sc).cols_at(0, d.M), dV, Ys.T()));
+    g.nb1 = d.S;
     AVMOE_TRY(try_forms(g, st, launch_hop1_yk, engine(false)));      // (hop1_stream.hip: dV[s] stationary per frame)
   }
   AVMOE_TRY(k_prep_dBm(pl, sc, st));
@@ -364,63 +335,57 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   if (d.Kcy > 0 && do6a) {
     {                                                      // dA1[s] = [dBm | dab][s] [Wc | bc]^T
       GemmArgs g = base();
-      g.A = sc + pl.o_dBmT; g.B = sv + pl.o_WcK; g.C = sc + pl.o_L1;
-      g.M = d.Kcyb; g.N = d.N; g.K = d.M + 1; g.lda = d.Mb; g.ldb = d.Mk; g.nb1 = d.S;
-      g.sA1 = (long)d.Kcyb * d.Mb; g.sCi = d.Np; g.sC1 = (long)d.Kcyb * d.Np;
+      AVMOE_TRY(g.product(vw::L1(pl, sc, d.Kcyb), dBmT, WcK.cols_at(0, d.M + 1).T()));
+      g.nb1 = d.S;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dWcK[:, :M+1] += A1^T [dBm | dab]
       GemmArgs g = base();
-      g.A = sv + pl.o_A1y; g.B = sc + pl.o_dBmT; g.C = sc + pl.o_dWcK;
-      g.M = d.N; g.N = d.M + 1; g.K = d.S * d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Np; g.ldb = d.Mb;
-      g.sCi = d.Mk; g.accumulate = 1;
+      AVMOE_TRY(g.product(dWcK.cols_at(0, d.M + 1), vw::A1y(pl, sv).flat(d.S).T(), dBmT.flat(d.S)));
+      g.accumulate = 1;
       leaf(g, 8);
       AVMOE_TRY(run(g, true));
     }
-    AVMOE_TRY(k_softmax_rows_bwd(d.bf16, sv + pl.o_A1y, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcyb, d.N, d.Np,
+    AVMOE_TRY(k_softmax_rows_bwd(d.bf16, sv + pl.o_A1y, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcyb, d.N, (int)vw::A1y(pl, sv).ld,
                                  sc + pl.o_dL1, nullptr, 1, 1, st));
     {                                                      // dR[s]^T = (dL1[s] Wc)^T   stored [m][kc]
-      GemmArgs g = base();
-      g.A = sc + pl.o_dL1; g.B = sv + pl.o_WcT; g.C = sc + pl.o_dRT;
-      g.M = d.Kcy; g.N = d.M; g.K = d.N; g.lda = d.Np; g.ldb = d.Np; g.nb1 = d.S; g.sA1 = (long)d.Kcyb * d.Np;
-      g.sCi = 1; g.sCj = d.Kcyp; g.sC1 = (long)d.M * d.Kcyp; g.out_dtype = dt;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(dRT.T(), vw::dL1(pl, sc, d.Kcyb).rows_at(0, d.Kcy), vw::WcT(pl, sv).rows_at(0, d.M).T()));
+      g.nb1 = d.S;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dWcK[:, :M+2] += dL1^T [R | qr | qb]
       GemmArgs g = base();
-      g.A = sc + pl.o_dL1; g.B = sv + pl.o_Rext; g.C = sc + pl.o_dWcK;
-      g.M = d.N; g.N = d.M + 2; g.K = d.S * d.Kcyb; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Np; g.ldb = d.Mk;
-      g.sCi = d.Mk; g.accumulate = 1;
+      AVMOE_TRY(g.product(dWcK, vw::dL1(pl, sc, d.Kcyb).flat(d.S).T(), vw::Rext(pl, sv).flat(d.S)));
+      g.accumulate = 1;
       leaf(g, 8);
       AVMOE_TRY(run(g, true));
     }
     AVMOE_TRY(k_dqrqb(pl, sc, prm.conv_b, st));
     {                                                      // dQ = sum_s dR[s] Y[s]
-      GemmArgs g = base();
-      g.A = sc + pl.o_dRT; g.B = Y; g.C = sc + pl.o_dQT; g.out_dtype = dt;      // (straight in the operand dtype of its two consumers)
-      g.M = d.Kcy; g.N = d.Cy; g.K = d.S * d.M; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Kcyp; g.ldb = d.Cy; g.sCi = d.Cy;
+      GemmArgs g = base(dt);                               // (straight in the operand dtype of its two consumers)
+      AVMOE_TRY(g.product(dQT, dRT.flat(d.S).T(), Ys.flat(d.S)));
       AVMOE_TRY(try_forms(g, st, with(launch_hop1_yt_sum, slab_cap), engine(true)));      // (hop1_stream.hip: one pass over Y with every accumulator in registers + a slab sum)
     }
   }
   if (do6b) {   // dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q   -- one pass over dY (two K segments; no cross-modal expert: wbar (x) d ybar[s] alone)
-    GemmArgs g = base();
-    fill_dy_args(g, g.seg[0], pl, sv, sc, 0);
-    g.C = dY; g.M = d.M; g.N = d.Cy; g.nb1 = d.S; g.sCi = d.Cy; g.sC1 = (long)d.M * d.Cy; g.out_dtype = dt;
-    g.accumulate = d.acc_dy;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(vw::tokens_y(d, dY), BmX.cols_at(0, d.M).T(), dV));
+    if (d.Kcy > 0) AVMOE_TRY(g.add_segment(1, dRT, Qx));
+    g.nb1 = d.S; g.accumulate = d.acc_dy;
     if (d.Kcy > 0) leaf(g, 16);                            // (the one-segment product has always stayed on AVMOE_BWD_PLANES)
     AVMOE_TRY(run(g, false));
   }
   if (d.Kcy > 0 && do6a) {
     {                                                      // dT0[y slots] += dQ Wf^T
       GemmArgs g = base();
-      g.A = sc + pl.o_dQT; g.B = sv + pl.o_WfT; g.C = sc + pl.o_dT0;
-      g.M = d.Kcy; g.N = d.C; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.sCi = d.C; g.accumulate = 1;
+      AVMOE_TRY(g.product(dT0.rows_at(0, d.Kcy), dQT, WfT.T()));
+      g.accumulate = 1;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dWf += T0^T dQ
       GemmArgs g = base();
-      g.A = sv + pl.o_T0T; g.B = sc + pl.o_dQT; g.C = sc + pl.o_dWf;
-      g.M = d.C; g.N = d.Cy; g.K = d.Kcy; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.C; g.ldb = d.Cy; g.sCi = d.Cy;
+      AVMOE_TRY(g.product(dWf, T0.rows_at(0, d.Kcy).T(), dQT));
       g.accumulate = 1;
       leaf(g, 8);
       AVMOE_TRY(run(g, false));
@@ -428,35 +393,31 @@ int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_p
   }
   // ---- phase 6b: latent self attention on X (AVS v2) ----------------------------------------------
   if (d.Kcx > 0) {
-    const char* T0x = sv + pl.o_T0T + (size_t)d.Kcy * d.C * esz;
+    const Mat dTx = vw::dTx(pl, sc), A1x = vw::A1x(pl, sv), dL1xT = vw::dL1xT(pl, sc);
     {                                                      // dA1x[s] = dTx[s] X[s]^T
       GemmArgs g = base();
-      g.A = sc + pl.o_dTx; g.B = X; g.C = sc + pl.o_L1;
-      g.M = d.Kcx; g.N = d.N; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = d.S;
-      g.sA1 = (long)d.Kcx * d.C; g.sB1 = (long)d.N * d.C; g.sCi = d.Np; g.sC1 = (long)d.Kcx * d.Np;
+      AVMOE_TRY(g.product(vw::L1(pl, sc, d.Kcx), dTx, Xs.T()));
+      g.nb1 = d.S;
       AVMOE_TRY(run(g, false));
     }
     {                                                      // dX[s] += A1x[s]^T dTx[s]
-      GemmArgs g = base();
-      g.A = sv + pl.o_A1x; g.B = sc + pl.o_dTx; g.C = dX;
-      g.M = d.N; g.N = d.C; g.K = d.Kcx; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Np; g.ldb = d.C; g.nb1 = d.S;
-      g.sA1 = (long)d.Kcx * d.Np; g.sB1 = (long)d.Kcx * d.C; g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.out_dtype = dt; g.accumulate = 1;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(dXs, A1x.T(), dTx));
+      g.nb1 = d.S; g.accumulate = 1;
       AVMOE_TRY(run(g, false));
     }
     MEMSET0(sc + pl.o_dL1xT, (size_t)d.NT * d.Kcxp * esz);
-    AVMOE_TRY(k_softmax_rows_bwd(d.bf16, sv + pl.o_A1x, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcx, d.N, d.Np,
-                                 sc + pl.o_dL1, sc + pl.o_dL1xT, d.Kcx, d.Kcxp, st));
+    AVMOE_TRY(k_softmax_rows_bwd(d.bf16, A1x.p, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcx, d.N, (int)A1x.ld,
+                                 sc + pl.o_dL1, (void*)dL1xT.p, d.Kcx, (int)dL1xT.ld, st));
     {                                                      // dT0[x slots] += sum_{s,n} dL1x^T X
       GemmArgs g = base();
-      g.A = sc + pl.o_dL1xT; g.B = X; g.C = sc + pl.o_dT0 + (size_t)d.Kcy * d.C * 4;
-      g.M = d.Kcx; g.N = d.C; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Kcxp; g.ldb = d.C; g.sCi = d.C;
+      AVMOE_TRY(g.product(dT0.rows_at(d.Kcy, d.Kcx), dL1xT.flat(d.S).T(), Xs.flat(d.S)));
       g.accumulate = 1;
       AVMOE_TRY(run(g, true));
     }
     {                                                      // dX += dL1x^T T0x
-      GemmArgs g = base();
-      g.A = sc + pl.o_dL1xT; g.B = T0x; g.C = dX;
-      g.M = d.NT; g.N = d.C; g.K = d.Kcx; g.lda = d.Kcxp; g.b_layout = MN_MAJOR; g.ldb = d.C; g.sCi = d.C; g.out_dtype = dt;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(dXs.flat(d.S), dL1xT.flat(d.S), T0.rows_at(d.Kcy, d.Kcx)));
       g.accumulate = 1;
       AVMOE_TRY(run(g, false));
     }
@@ -475,8 +436,9 @@ int moe_backward_dx_dy(const Plan& pa, const void* X, char* sva, char* sca, cons
   // site A's dX product with site B's  dY[s] = [Bm ; wbar][s]^T dV[s] + dR[s]^T Q  as a third and a fourth K segment (gemm.h: GemmArgs::seg)
   GemmArgs g; g.dtype = a.bf16 ? GEMM_BF16 : GEMM_F32; g.split3 = (AVMOE_LEAF2 & 16) ? 2 : AVMOE_BWD_PLANES;
   g.slabs = (float*)at(sca, pa.o_slabs);                   // (the streaming form's dump word)
-  fill_dx_args(g, pa, X, sva, sca, dX);
-  fill_dy_args(g.seg[1], g.seg[2], pb, svb, scb, a.Cg);
+  AVMOE_TRY(dx_product(g, pa, X, sva, sca, dX));
+  AVMOE_TRY(g.add_segment(2, views::BmX(pb, svb).cols_at(0, b.M).T(), views::dV(pb, scb).groups(a.g)));
+  if (b.Kcy > 0) AVMOE_TRY(g.add_segment(3, views::dRT(pb, scb), views::Qx(pb, svb).groups(a.g)));
   // The streaming form (dx_stream3.hip: the tuned bf16 shape), or, round 6, the same sum on the tiled engine: the token gradient is written
   // once instead of written by site A and read back + added by site B.  fp32 sites only (AVMOE_DXDY_GEN = 1; 3 = bf16 sites of the
   // generalised shapes too: measured, moe_run.h).

@@ -4,6 +4,7 @@
 #include "pass.h"
 #include "moe_run.h"
 #include "side.h"
+#include "site_views.h"
 
 namespace avmoe {
 
@@ -50,7 +51,11 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
   float* slabs = (float*)(sc + pl.o_slabs);
   const size_t slab_cap = slab_floats(d);
-  auto base = [&]() { GemmArgs g; g.dtype = dt; g.out_dtype = GEMM_F32; g.slabs = slabs; g.split3 = AVMOE_FWD_SPLIT3; return g; };      // (split3: fp32 sites only, gemm.h)
+  auto base = [&](int out_dt = GEMM_F32) { GemmArgs g; g.dtype = dt; g.out_dtype = out_dt; g.slabs = slabs; g.split3 = AVMOE_FWD_SPLIT3; return g; };      // (split3: fp32 sites only, gemm.h)
+  // the site's tensors (site_views.h); the token tensors all frames as one matrix too
+  namespace vw = views;
+  const Mat Xs = vw::tokens_x(d, X), Ys = vw::tokens_y(d, Y), Wt = vw::Wt(pl, sv), Text = vw::Text(pl, sv), WfT = vw::WfT(pl, sv), T0 = vw::T0T(pl, sv);
+  const Mat Qx = vw::Qx(pl, sv), Rext = vw::Rext(pl, sv), A1y = vw::A1y(pl, sv), BmX = vw::BmX(pl, sv), V = vw::V(pl, sv), Z = vw::Z(pl, sv);
 
   // ---- weights-derived operands --------------------------------------------------------------
   AVMOE_TRY(k_prep_all(pl, sv, prm, st));                  // (also scal[1] = 1: the unit gate of with_unit_gates)
@@ -59,15 +64,14 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   // Zx = X Wt^T per frame, with the row sums / column sums of X as side products (fused statistics).  It depends on X and the
   // weights only, the hop-1 chain below on Y and the weights only: the two run on two streams and meet at the router.
   auto fused_down = [&](hipStream_t xs) -> int {
-    GemmArgs g = base();
+    GemmArgs g = base(GEMM_BF16);
     int tiles = 0;
-    g.A = X; g.B = sv + pl.o_Wt; g.C = sv + pl.o_Z; g.out_dtype = GEMM_BF16;
-    g.M = d.N; g.N = d.E * d.dgp; g.K = d.Cg; g.lda = d.C; g.ldb = d.Cg; g.nb1 = d.S; g.nb2 = d.g;
-    g.sA1 = (long)d.N * d.C; g.sA2 = d.Cg; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.DZ; g.sC1 = (long)d.N * d.DZ; g.sC2 = (long)d.E * d.dgp;
+    AVMOE_TRY(g.product(Z.groups(d.g), Xs.groups(d.g), Wt.T()));
+    g.nb1 = d.S; g.nb2 = d.g;
     g.st_rows = (float*)(sc + pl.o_sxp); g.st_cols = (float*)(sc + pl.o_xpart); g.st_ntot = d.NT; g.st_tiles = &tiles;
     if (d.fuse_l2) {                                       // + L2g[gi][s] = X[s][:, group gi] T[s][:, group gi]^T : the hop-2 logits, per group
-      auto& x = g.xcols; x.B = sv + pl.o_Text; x.N = d.KL; x.ldb = d.C; x.sB1 = (long)d.KLT * d.C; x.sB2 = d.Cg;
-      x.C = (float*)(sc + pl.o_L2g); x.ldc = d.KL; x.sC1 = (long)d.N * d.KL; x.sC2 = (long)d.NT * d.KL;
+      const Mat T = Text.groups(d.g), L = vw::L2g(pl, sc);
+      g.xcols = {T.p, d.KL, T.ld, T.s1, T.s2, (float*)L.p, L.ld, L.s1, L.s2};
     }
     const int rc = launch_gemm_stream(g, xs);              // (the one form that leaves the statistics: no chain, no engine behind it)
     if (rc != OK) {
@@ -91,70 +95,60 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
 
   // ---- hop 1, cross-modal experts: latent tokens read the (never materialised) remapped Y -----
   if (d.Kcy > 0) {
-    GemmArgs g = base();                                   // Q = T0 Wf
-    g.A = sv + pl.o_T0T; g.B = sv + pl.o_WfT; g.C = sv + pl.o_Qx;
-    g.M = d.Kcy; g.N = d.Cy; g.K = d.C; g.lda = d.C; g.b_layout = MN_MAJOR; g.ldb = d.Cy;
-    g.sCi = d.Cy; g.out_dtype = dt;
+    GemmArgs g = base(dt);                                 // Q = T0 Wf
+    AVMOE_TRY(g.product(Qx, T0.rows_at(0, d.Kcy), WfT));
     AVMOE_TRY(launch_gemm(g, st));
   }
   AVMOE_TRY(k_qrqb_fill(pl, sv, prm.fc_b, st));
   if (d.Kcy > 0) {
     {                                                      // R[s] = Q Y[s]^T
-      GemmArgs g = base();
-      g.A = sv + pl.o_Qx; g.B = Y; g.C = sv + pl.o_Rext;
-      g.M = d.Kcy; g.N = d.M; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.nb1 = d.S; g.sB1 = (long)d.M * d.Cy;
-      g.sCi = d.Mk; g.sC1 = (long)d.Kcyb * d.Mk; g.out_dtype = dt;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(Rext.rows_at(0, d.Kcy).cols_at(0, d.M), Qx, Ys.T()));
+      g.nb1 = d.S;
       AVMOE_TRY(try_forms(g, st, launch_hop1_yk, launch_gemm));      // (hop1_stream.hip: Q stationary, Y streamed in whole token rows)
     }
     {                                                      // L1[s] = [R | qr | qb] [Wc | bc | 1]^T
       GemmArgs g = base();
-      g.A = sv + pl.o_Rext; g.B = sv + pl.o_WcK; g.C = sc + pl.o_L1;
-      g.M = d.Kcy; g.N = d.N; g.K = d.M + 2; g.lda = d.Mk; g.ldb = d.Mk; g.nb1 = d.S; g.sA1 = (long)d.Kcyb * d.Mk;
-      g.sCi = d.Np; g.sC1 = (long)d.Kcyb * d.Np;
+      AVMOE_TRY(g.product(vw::L1(pl, sc, d.Kcyb).rows_at(0, d.Kcy), Rext.rows_at(0, d.Kcy), vw::WcK(pl, sv).T()));
+      g.nb1 = d.S;
       AVMOE_TRY(launch_gemm(g, st));
     }
-    AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcyb, d.N, d.Np, sv + pl.o_A1y, d.Np,
+    AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcyb, d.N, vw::L1(pl, sc, d.Kcyb).ld, (void*)A1y.p, A1y.ld,
                              d.Kcyb, d.Kcy, d.Kp, d.K, st));
     {                                                      // [Bm | ab][s] = A1[s] [Wc | bc]
-      GemmArgs g = base();
-      g.A = sv + pl.o_A1y; g.B = sv + pl.o_WcT; g.C = sv + pl.o_BmX;
-      g.M = d.Kcy; g.N = d.M + 1; g.K = d.N; g.lda = d.Np; g.ldb = d.Np; g.nb1 = d.S; g.sA1 = (long)d.Kcyb * d.Np;
-      g.sCi = d.Mb; g.sC1 = (long)d.Kcyb * d.Mb; g.out_dtype = dt;
+      GemmArgs g = base(dt);
+      AVMOE_TRY(g.product(BmX.rows_at(0, d.Kcy), A1y.rows_at(0, d.Kcy), vw::WcT(pl, sv).T()));
+      g.nb1 = d.S;
       AVMOE_TRY(launch_gemm(g, st));
     }
   }
   {                                                        // V[s] = [Bm ; wbar][s] Y[s]   (token contraction)
-    GemmArgs g = base();
-    g.A = sv + pl.o_BmX; g.B = Y; g.C = sv + pl.o_V;
-    g.M = d.Kcyb; g.N = d.Cy; g.K = d.M; g.lda = d.Mb; g.b_layout = MN_MAJOR; g.ldb = d.Cy; g.nb1 = d.S;
-    g.sA1 = (long)d.Kcyb * d.Mb; g.sB1 = (long)d.M * d.Cy; g.sCi = d.Cy; g.sC1 = (long)d.Kcyb * d.Cy; g.out_dtype = dt;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(V, BmX.cols_at(0, d.M), Ys));
+    g.nb1 = d.S;
     AVMOE_TRY(try_forms(g, st, launch_hop1_yt_frames, launch_gemm));      // (hop1_stream.hip)
   }
   {                                                        // TV = V Wf^T
     GemmArgs g = base();
-    g.A = sv + pl.o_V; g.B = sv + pl.o_WfT; g.C = sc + pl.o_TV;
-    g.M = d.S * d.Kcyb; g.N = d.C; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.sCi = d.C;
+    AVMOE_TRY(g.product(vw::TV(pl, sc, d.Kcyb).flat(d.S), V.flat(d.S), WfT.T()));
     AVMOE_TRY(launch_gemm(g, st));
   }
   AVMOE_TRY(k_finish_T(pl, sv, sc, prm, 0, st));
 
   // ---- hop 1, latent self attention on X (AVS v2) ----------------------------------------------
   if (d.Kcx > 0) {
-    const char* T0x = sv + pl.o_T0T + (size_t)d.Kcy * d.C * d.esz;
-    {
+    {                                                      // L1x[s] = T0x X[s]^T
       GemmArgs g = base();
-      g.A = T0x; g.B = X; g.C = sc + pl.o_L1;
-      g.M = d.Kcx; g.N = d.N; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = d.S; g.sB1 = (long)d.N * d.C;
-      g.sCi = d.Np; g.sC1 = (long)d.Kcx * d.Np;
+      AVMOE_TRY(g.product(vw::L1(pl, sc, d.Kcx), T0.rows_at(d.Kcy, d.Kcx), Xs.T()));
+      g.nb1 = d.S;
       AVMOE_TRY(launch_gemm(g, st));
     }
-    AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcx, d.N, d.Np, sv + pl.o_A1x, d.Np,
+    AVMOE_TRY(k_softmax_rows(d.bf16, (const float*)(sc + pl.o_L1), (long)d.S * d.Kcx, d.N, vw::L1(pl, sc, d.Kcx).ld, (void*)vw::A1x(pl, sv).p, vw::A1x(pl, sv).ld,
                              d.Kcx, d.Kcx, d.Kp, d.K, st));
-    {
+    {                                                      // TVx[s] = A1x[s] X[s]
       GemmArgs g = base();
-      g.A = sv + pl.o_A1x; g.B = X; g.C = sc + pl.o_TV;
-      g.M = d.Kcx; g.N = d.C; g.K = d.N; g.lda = d.Np; g.b_layout = MN_MAJOR; g.ldb = d.C; g.nb1 = d.S;
-      g.sA1 = (long)d.Kcx * d.Np; g.sB1 = (long)d.N * d.C; g.sCi = d.C; g.sC1 = (long)d.Kcx * d.C;
+      AVMOE_TRY(g.product(vw::TV(pl, sc, d.Kcx), vw::A1x(pl, sv), Xs));
+      g.nb1 = d.S;
       AVMOE_TRY(launch_gemm(g, st));
     }
     AVMOE_TRY(k_finish_T(pl, sv, sc, prm, 1, st));
@@ -164,34 +158,31 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   // (row sums of Text: k_finish_T writes them with the rows, k_prep_all those of the constant rows)
   if (d.El > 0) {                                          // TT[s][l] = T T^T
     GemmArgs g = base();
-    g.A = sv + pl.o_Text; g.B = sv + pl.o_Text; g.C = sv + pl.o_TT;
-    g.M = d.K; g.N = d.K; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = d.S; g.nb2 = d.El;
-    g.sA1 = g.sB1 = (long)d.KLT * d.C; g.sA2 = g.sB2 = (long)d.Kp * d.C;
-    g.sCi = d.K; g.sC1 = (long)d.El * d.K * d.K; g.sC2 = (long)d.K * d.K;
+    const Mat T = Text.row_blocks(d.Kp, d.K);              // (the K used rows of every latent slot)
+    AVMOE_TRY(g.product(vw::TT(pl, sv).row_blocks(d.K, d.K), T, T.T()));
+    g.nb1 = d.S; g.nb2 = d.El;
     AVMOE_TRY(launch_gemm(g, st));
   }
-  auto down_gemm = [&](const void* rows, long nrows, void* dst, int out_dt = GEMM_F32) {   // rows (nrows, C) -> (nrows, DZ) through Wt
-    GemmArgs g = base();
-    g.A = rows; g.B = sv + pl.o_Wt; g.C = dst; g.out_dtype = out_dt;
-    g.M = (int)nrows; g.N = d.E * d.dgp; g.K = d.Cg; g.lda = d.C; g.ldb = d.Cg; g.nb2 = d.g;
-    g.sA2 = d.Cg; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.DZ; g.sC2 = (long)d.E * d.dgp;
+  auto down_gemm = [&](const Mat& rows, const Mat& dst) {    // rows (nrows, C) -> (nrows, DZ) through Wt
+    GemmArgs g = base(dst.esz == 2 ? GEMM_BF16 : GEMM_F32);
+    AVMOE_TRY(g.product(dst.groups(d.g), rows.groups(d.g), Wt.T()));
+    g.nb2 = d.g;
     return launch_gemm(g, st);
   };
-  AVMOE_TRY(down_gemm(sv + pl.o_Text, (long)d.S * d.KLT, sv + pl.o_TW));   // TW (all latent rows x all experts)
+  AVMOE_TRY(down_gemm(Text.flat(d.S), vw::TW(pl, sv).flat(d.S)));          // TW (all latent rows x all experts)
   // ---- the X-side GEMMs ------------------------------------------------------------------------
   if (d.fuse_xs) {
     if (side) AVMOE_TRY(fk.join());
     else AVMOE_TRY(fused_down(st));
   } else {
-    AVMOE_TRY(down_gemm(X, d.NT, sv + pl.o_Z, d.zsz == 2 ? GEMM_BF16 : GEMM_F32));                              // Zx = X Wt^T
+    AVMOE_TRY(down_gemm(Xs.flat(d.S), Z.flat(d.S)));                        // Zx = X Wt^T
   }
   // ---- router (its input: the token means of X -- after the statistics above) ----------------------
   AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm, aux_out, load_out, mix_scale));
   if (d.KL > 0 && !d.fuse_l2) {                            // L2[s] = X[s] T[s]^T   (fused: per-group partial sums came out of the down projection; pre_small adds them into L2)
     GemmArgs g = base();
-    g.A = X; g.B = sv + pl.o_Text; g.C = sv + pl.o_L2;
-    g.M = d.N; g.N = d.KL; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = d.S;
-    g.sA1 = (long)d.N * d.C; g.sB1 = (long)d.KLT * d.C; g.sCi = d.KL; g.sC1 = (long)d.N * d.KL;
+    AVMOE_TRY(g.product(vw::L2(pl, sv), Xs, Text.rows_at(0, d.KL).T()));
+    g.nb1 = d.S;
     AVMOE_TRY(launch_gemm(g, st));
   }
   // ---- AVVP unimodal N x N block (mgn.py:132-139): xr = softmax_rows(X X^T)^T X, shared by the unimodal experts;
@@ -203,48 +194,46 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
       AVMOE_TRY(mha_frames_forward(pl, X, prm.e[e], slot, sv, sc, st));
       AVMOE_TRY(k_xrstats(pl, X, sv, slot, st));
       GemmArgs g = base();                                 // ZR[:, expert e] = xr Wt_e^T
-      g.A = sv + pl.o_xr + (size_t)slot * d.NT * d.C * d.esz; g.B = sv + pl.o_Wt + (size_t)e * d.dgp * d.Cg * d.esz;
-      g.C = sv + pl.o_ZR + (size_t)e * d.dgp * 4;
-      g.M = d.NT; g.N = d.dgp; g.K = d.Cg; g.lda = d.C; g.ldb = d.Cg; g.nb2 = d.g;
-      g.sA2 = d.Cg; g.sB2 = (long)d.E * d.dgp * d.Cg; g.sCi = d.DZ; g.sC2 = (long)d.E * d.dgp;
+      AVMOE_TRY(g.product(vw::ZR(pl, sv).flat(d.S).groups(d.g).cols_at(e * d.dgp, d.dgp), vw::xr(pl, sv, slot).flat(d.S).groups(d.g),
+                          Wt.rows_at(e * d.dgp, d.dgp).T()));
+      g.nb2 = d.g;
       AVMOE_TRY(launch_gemm(g, st));
     }
   } else if (d.nxn) {
     for (int s0 = 0; s0 < d.S; s0 += d.nxc) {              // d.nxc frames at a time through one workspace (all of them when they fit: moe_plan.cpp)
       const int ns = std::min(d.nxc, d.S - s0);
-      const char* Xc = (const char*)X + (size_t)s0 * d.N * d.C * d.esz;
+      const Mat Xm = Xs.frames_at(s0), xrm = vw::xr(pl, sv, 0).frames_at(s0), att = vw::att(pl, sv);
+      const void* Xc = Xm.p;
       // att[s] = softmax_rows(X[s] X[s]^T) without the scores leaving the chip: the product runs twice with softmax epilogues -- (max, sum exp)
       // per row and column tile, then exp(score - lse) straight to att; the row log-sum-exp is kept for the backward
       float* lse = (float*)(sv + pl.o_nlse) + (size_t)s0 * d.N;
       if (d.nflash) {     // the large-N sites: row statistics, then xr = att^T X with att re-formed in the accumulators (nxn_att.hip)
-        AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, d.Np, lse, nullptr, 0, st));
-        AVMOE_TRY(k_nxn_xr(Xc, ns, d.N, d.C, d.Np, lse, sv + pl.o_xr + (size_t)s0 * d.N * d.C * d.esz, st));
+        AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, (int)att.ld, lse, nullptr, 0, st));
+        AVMOE_TRY(k_nxn_xr(Xc, ns, d.N, d.C, (int)att.ld, lse, (void*)xrm.p, st));
         continue;
       }
-      if (nxn_att_ok(d.bf16, d.N, d.C, d.Np)) {                 // ... as one kernel for the large-N sites (nxn_att.hip)
-        AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, d.Np, lse, sv + pl.o_att, 0, st));
+      if (nxn_att_ok(d.bf16, d.N, d.C, (int)att.ld)) {                 // ... as one kernel for the large-N sites (nxn_att.hip)
+        AVMOE_TRY(k_nxn_att(Xc, ns, d.N, d.C, (int)att.ld, lse, (void*)att.p, 0, st));
       } else
       for (int pass = 0; pass < 2; ++pass) {
-        GemmArgs g = base();
-        g.A = Xc; g.B = Xc; g.C = sv + pl.o_att;
-        g.M = d.N; g.N = d.N; g.K = d.C; g.lda = d.C; g.ldb = d.C; g.nb1 = ns; g.sA1 = g.sB1 = (long)d.N * d.C;
-        g.sCi = d.Np; g.sC1 = (long)d.N * d.Np; g.out_dtype = dt;
+        GemmArgs g = base(dt);
+        AVMOE_TRY(g.product(att, Xm, Xm.T()));
+        g.nb1 = ns;
         if (pass == 0) { g.epi = GEMM_EPI_ROWSTATS; g.row_part = (float*)(sc + pl.o_npart); }
         else { g.epi = GEMM_EPI_EXP; g.row_lse = lse; }
         AVMOE_TRY(launch_gemm(g, st));
         if (pass == 0) AVMOE_TRY(gemm_row_lse((const float*)(sc + pl.o_npart), (long)ns * d.N, cdiv(d.N, 128), lse, st));
       }
       {                                                    // xr[s] = att[s]^T X[s]
-        GemmArgs g = base();
-        g.A = sv + pl.o_att; g.B = Xc; g.C = sv + pl.o_xr + (size_t)s0 * d.N * d.C * d.esz;
-        g.M = d.N; g.N = d.C; g.K = d.N; g.a_layout = g.b_layout = MN_MAJOR; g.lda = d.Np; g.ldb = d.C; g.nb1 = ns;
-        g.sA1 = (long)d.N * d.Np; g.sB1 = (long)d.N * d.C; g.sCi = d.C; g.sC1 = (long)d.N * d.C; g.out_dtype = dt;
+        GemmArgs g = base(dt);
+        AVMOE_TRY(g.product(xrm, att.T(), Xm));
+        g.nb1 = ns;
         g.ksplit = choose_ksplit(g, slab_cap);             // few frames x few column tiles: split the token contraction to fill the chip
         AVMOE_TRY(launch_gemm(g, st));
       }
     }
     AVMOE_TRY(k_xrstats(pl, X, sv, 0, st));
-    AVMOE_TRY(down_gemm(sv + pl.o_xr, d.NT, sv + pl.o_ZR));
+    AVMOE_TRY(down_gemm(vw::xr(pl, sv, 0).flat(d.S), vw::ZR(pl, sv).flat(d.S)));
   }
   // ---- bottleneck space --------------------------------------------------------------------------
   PassCall pass(pl, sv, sc, prm);                          // (pass.h: each pass tries its forms in order)
@@ -258,9 +247,9 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
                        (const float*)(sv + pl.o_bn1), (float*)(sc + pl.o_gcolT), (float*)(sv + pl.o_mz)));
   } else if (d.use_bn && d.training) {                     // ... as 8 batched token contractions of the engine
     GemmArgs g = base();
-    g.A = sc + pl.o_Zp; g.B = sc + pl.o_Zp; g.C = sv + pl.o_Szz;
-    g.M = d.dgp; g.N = d.dgp; g.K = d.NT; g.a_layout = g.b_layout = MN_MAJOR; g.lda = g.ldb = d.DZ;
-    g.nb2 = d.g * d.E; g.sA2 = g.sB2 = d.dgp; g.sCi = d.dgp; g.sC2 = (long)d.dgp * d.dgp;
+    const Mat Zp = vw::Zp(pl, sc).flat(d.S).groups(d.g * d.E);      // Szz[i][e] = z'^T z' / NT
+    AVMOE_TRY(g.product(vw::Szz(pl, sv).row_blocks(d.dgp, d.dgp), Zp.T(), Zp));
+    g.nb2 = d.g * d.E;
     g.alpha = 1.f / (float)d.NT;
     g.ksplit = choose_ksplit(g, slab_cap);
     AVMOE_TRY(launch_gemm(g, st));
@@ -268,10 +257,10 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
   AVMOE_TRY(k_post_prep(pl, sv, sc, prm, st));
   AVMOE_TRY(k_post_small(pass, st));
   {                                                        // out = Apost Bpost^T  (mixture, gates, BN2, LN-post folded in)
-    GemmArgs g = base();
-    g.A = sv + pl.o_Apost; g.B = sv + pl.o_Bpost; g.C = out;
-    g.M = d.NT; g.N = d.Cg; g.K = d.KP; g.lda = (long)d.g * d.KPp; g.ldb = d.KPp; g.nb2 = d.g;
-    g.sA2 = d.KPp; g.sB2 = (long)d.Cg * d.KPp; g.sCi = d.C; g.sC2 = d.Cg; g.out_dtype = dt;
+    GemmArgs g = base(dt);
+    AVMOE_TRY(g.product(vw::tokens_x(d, out).flat(d.S).groups(d.g), vw::Apost(pl, sv).groups(d.g).cols_at(0, d.KP),
+                        vw::Bpost(pl, sv).row_blocks(d.Cg, d.Cg).cols_at(0, d.KP).T()));
+    g.nb2 = d.g;
     g.accumulate = d.acc_out;
     AVMOE_TRY(launch_gemm(g, st));
   }
@@ -319,6 +308,7 @@ int remap_forward(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, void
   const Dims& d = pl.d;
   if (!prm.fc_b) { set_last_error("remap_forward: fc.bias missing"); return ERR_BAD_ARG; }
   const int dt = d.bf16 ? GEMM_BF16 : GEMM_F32;
+  const Mat Yts = views::view(Yt, 0, d.esz, d.N, d.Cy, d.Cy, (long)d.N * d.Cy);      // the remapped Y: (S, N, Cy)
   // k_prep_all also prepares the experts' operands, by the plan's group layout: a merged-groups site (Dims::mg) must hand it the dense
   // block-diagonal copies, as moe_forward does -- with the grouped down_sampler it would read g times the tensor's length
   avmoe_moe_ptrs p = prm;
@@ -329,16 +319,14 @@ int remap_forward(const Plan& pl, const void* Y, const avmoe_moe_ptrs& prm, void
   AVMOE_TRY(k_prep_all(pl, sv, p, st));
   {                                                        // Yt[s] = Wc Y[s]
     GemmArgs g; g.dtype = dt; g.out_dtype = dt; g.slabs = (float*)(sc + pl.o_slabs);
-    g.A = sv + pl.o_WcK; g.B = Y; g.C = Yt;
-    g.M = d.N; g.N = d.Cy; g.K = d.M; g.lda = d.Mk; g.b_layout = MN_MAJOR; g.ldb = d.Cy; g.nb1 = d.S; g.sB1 = (long)d.M * d.Cy;
-    g.sCi = d.Cy; g.sC1 = (long)d.N * d.Cy;
+    AVMOE_TRY(g.product(Yts, views::WcK(pl, sv).cols_at(0, d.M), views::tokens_y(d, Y)));
+    g.nb1 = d.S;
     AVMOE_TRY(launch_gemm(g, st));
   }
   AVMOE_TRY(k_add_bias(d.bf16, Yt, (long)d.S * d.N, d.Cy, d.N, prm.conv_b, nullptr, st));
   {                                                        // Yf = Yt Wf^T
     GemmArgs g; g.dtype = dt; g.out_dtype = dt; g.slabs = (float*)(sc + pl.o_slabs);
-    g.A = Yt; g.B = sv + pl.o_WfT; g.C = Yf;
-    g.M = d.S * d.N; g.N = d.C; g.K = d.Cy; g.lda = d.Cy; g.ldb = d.Cy; g.sCi = d.C;
+    AVMOE_TRY(g.product(views::tokens_x(d, Yf).flat(d.S), Yts.flat(d.S), views::WfT(pl, sv).T()));
     AVMOE_TRY(launch_gemm(g, st));
   }
   return k_add_bias(d.bf16, Yf, (long)d.S * d.N, d.C, 1, nullptr, prm.fc_b, st);

@@ -4,6 +4,7 @@
 // `scratch` is transient per call.  Both are caller-allocated (C ABI: the library never allocates).
 // Every buffer has a name so tests can pull any intermediate out of the workspace and compare it with
 // the same-named tensor of oracle/algebra_ref.py (avmoe_moe_buffer_info).
+// How a buffer is laid out as a matrix (shape, leading dimension, frame stride) is stated once, in site_views.h: the products are built from those views.
 #pragma once
 #include "../../include/avmoe.h"
 #include "common.h"
