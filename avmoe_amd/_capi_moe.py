@@ -233,6 +233,12 @@ def declare(L):
         L.avmoe_moe_backward_reg.argtypes = head + [C.c_void_p] * 8 + [C.POINTER(MoePtrs), C.c_int32, C.c_void_p]
         L.avmoe_mix_drop_draw.restype = C.c_int
         L.avmoe_mix_drop_draw.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    # aux-loss-free balancing (found by symbol: a bias on the top-k selection, the selection counts, and the update of the bias)
+    L.avmoe_site_bias = L.avmoe_site_reg and hasattr(L, "avmoe_moe_forward_bias") and hasattr(L, "avmoe_router_bias_update")
+    if L.avmoe_site_bias:
+        L.avmoe_moe_forward_bias.restype, L.avmoe_moe_forward_bias.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 12
+        L.avmoe_router_bias_update.restype = C.c_int
+        L.avmoe_router_bias_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

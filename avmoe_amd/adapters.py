@@ -166,7 +166,8 @@ def _draw_mix(module, L, S, E, p, q, dev, stream):
 
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
     """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
-    losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call.
+    losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call;
+    or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too).
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
@@ -197,6 +198,18 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     reg = bool(module.training and (drop_p > 0.0 or drop_q > 0.0))      # (eval mode ignores both settings)
     if reg and not getattr(L, "avmoe_site_reg", False):
         raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_reg / avmoe_mix_drop_draw: it serves neither drop_path nor expert_dropout")
+    # aux-loss-free balancing (avmoe_amd.train.RouterBiasBalancer; include/avmoe.h at avmoe_moe_forward_bias): the bias on the selection,
+    # and -- in training mode only -- the tensor the selection counts are added to.  Eval mode applies the bias and counts nothing.
+    sel_bias = module.router_select_bias
+    sel_count = module.router_select_count if module.training else None
+    if sel_bias is not None and not k:
+        raise ValueError("router_select_bias needs top-k gating (router_top_k in [1, E)): a dense mixture has no selection")
+    for what, t_ in (("router_select_bias", sel_bias), ("router_select_count", sel_count)):
+        if t_ is not None and not (torch.is_tensor(t_) and t_.dtype == torch.float32 and t_.device == X.device and t_.numel() == E and t_.is_contiguous()):
+            raise ValueError(f"{what} must be a contiguous float32 tensor of {E} elements on the tokens' device")
+    biased = sel_bias is not None or sel_count is not None
+    if biased and not getattr(L, "avmoe_site_bias", False):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_bias / avmoe_router_bias_update: it serves no router selection bias")
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -216,7 +229,13 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
     mix = _draw_mix(module, L, S, E, drop_p, drop_q, X.device, stream) if reg else None
     module.__dict__["_mix_last"] = mix
-    if mix is not None:                                  # the multiplier on the mixture weights, drawn just above on the same stream
+    if biased:                                           # the selection bias / counts (and the multiplier, when one was drawn)
+        fn = "avmoe_moe_forward_bias"
+        st = L.avmoe_moe_forward_bias(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix), _ptr(sel_bias),
+                                      _ptr(sel_count), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
+                                      aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None, saved.data_ptr(),
+                                      scratch.data_ptr(), stream)
+    elif mix is not None:                                # the multiplier on the mixture weights, drawn just above on the same stream
         fn = "avmoe_moe_forward_reg"
         st = L.avmoe_moe_forward_reg(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, mix.data_ptr(),
                                      out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
@@ -687,6 +706,25 @@ class MoEAdapter(nn.Module):
         """How many multipliers the site's generator has drawn since it was (re)started, read from the device (synchronises)."""
         st = self.__dict__.get("_mix_state")
         return int(st[1].item()) if st is not None else 0
+
+    @property
+    def router_select_bias(self):
+        """None, or a device tensor (view) of E floats: the bias on the top-k SELECTION of aux-loss-free balancing (the mixture weights do not
+        see it).  A plain attribute -- no parameter, no buffer, no state_dict key; avmoe_amd.train.RouterBiasBalancer owns and sets it."""
+        return self.__dict__.get("_router_select_bias")   # (.get: a module pickled before the setting existed has none)
+
+    @router_select_bias.setter
+    def router_select_bias(self, t):
+        self.__dict__["_router_select_bias"] = t
+
+    @property
+    def router_select_count(self):
+        """None, or a device tensor (view) of E floats that every TRAINING forward adds its selection counts to (eval forwards do not)."""
+        return self.__dict__.get("_router_select_count")
+
+    @router_select_count.setter
+    def router_select_count(self, t):
+        self.__dict__["_router_select_count"] = t
 
     @property
     def router_aux(self):

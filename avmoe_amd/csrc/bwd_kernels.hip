@@ -168,6 +168,8 @@ struct RouterBwdArgs {
 // otherwise  dp_e = m_e dw_e.  The load-balancing term, dprobs and the softmax Jacobian then act on p.
 // a.mix: the forward's multiplier c on the mixture weights (such a forward always leaves k > 0: k_router).  `probs` then holds c w and dp is
 // dL/d(c w): dw_e = c_e dp_e, while sum_j w_j dw_j = sum_j (c w)_j dp_j needs no factor.  c has no gradient.  NULL: a uniform branch not taken.
+// mode[2] (avmoe_moe_forward_bias): the forward ranked the experts on p + b; the selection is recomputed with the bias words the forward
+// left in mode[16 .. 16 + E) -- not with the live bias tensor, which the balancer may have updated since.  The bias has no gradient.
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
@@ -197,7 +199,12 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
     if (top_k) {
       for (int e = 0; e < a.E; ++e) s_p[e] = probs[(long)s * a.E + e];
       float kept, wd = 0.f;
-      const unsigned m = topk_select(s_p, a.E, top_k, &kept);
+      unsigned m;
+      if (mode[2]) {                               // (uniform over the grid) a forward with a selection bias: the values it USED
+        float bs[MAX_E];
+        for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[16 + e]);
+        m = topk_select_biased(s_p, bs, a.E, top_k, &kept);
+      } else m = topk_select(s_p, a.E, top_k, &kept);
       if (renorm)
         for (int e = 0; e < a.E; ++e) wd += wt[(long)s * a.E + e] * dp[(long)s * a.E + e];
       for (int e = 0; e < a.E; ++e) {

@@ -46,6 +46,23 @@ __device__ __forceinline__ unsigned topk_select(const float* p, int E, int k, fl
   return m;
 }
 
+// The same with a selection bias b (avmoe_moe_forward_bias: aux-loss-free balancing): the experts are ranked on the score
+// sc_e = p_e + b_e -- ONE fp32 addition, so the selection repeats bit for bit from p and b -- with the same tie rule on the scores,
+// and *kept stays the sum of the kept UNBIASED probabilities, added in expert order: the bias enters the selection only.
+__device__ __forceinline__ unsigned topk_select_biased(const float* p, const float* b, int E, int k, float* kept) {
+  float sc[16];                                    // (AVMOE_MAX_EXPERTS)
+  for (int e = 0; e < E; ++e) sc[e] = __fadd_rn(p[e], b[e]);      // (never contracted into a neighbouring product)
+  unsigned m = 0u;
+  float s = 0.f;
+  for (int e = 0; e < E; ++e) {
+    int rank = 0;
+    for (int f = 0; f < E; ++f) rank += (sc[f] > sc[e]) || (sc[f] == sc[e] && f < e);
+    if (rank < k) { m |= 1u << e; s += p[e]; }
+  }
+  *kept = s;
+  return m;
+}
+
 // element access for the activation / operand type T (float or __bf16)
 template <typename T> __device__ __forceinline__ float ldT(const T* p, long i);
 template <> __device__ __forceinline__ float ldT<float>(const float* p, long i) { return p[i]; }

@@ -774,6 +774,7 @@ struct RouterArgs {
   const float *W1, *b1, *W2, *b2, *W3, *b3, *noise;
   int C2, E, S, top_k, renorm;    // top_k: 0 = the dense mixture
   const float* mix;               // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg), or NULL; k_router then runs the top-k form
+  const float* bias;              // (E) selection bias of the top-k gating (avmoe_moe_forward_bias), or NULL
 };
 // one block per frame: layer-1 pre-activations from the engine GEMM -- summed here over its split-K slabs, in slab order, when it
 // ran split (no separate reduce pass) --, then bias / ReLU, the two small layers, softmax and first-max argmax.  fp32, fixed order.
@@ -785,13 +786,18 @@ struct RouterArgs {
 // a.mix (avmoe_moe_forward_reg: stochastic depth / expert dropout) multiplies the weights that go to `probs`, behind top-k; psm,
 // probs_out, idx_out and lse do not see it.  k_router gives a.top_k = E, a.renorm = 0 for a dense site with a multiplier (w = p, every
 // expert kept), so that psm keeps the softmax for the backward and the losses.  NULL: a uniform branch not taken.
+// a.bias (avmoe_moe_forward_bias: aux-loss-free balancing) enters the SELECTION only: the experts are ranked on p_e + b_e
+// (topk_select_biased), the weights are still m_e p_e / kept or m_e p_e with kept the sum of the kept unbiased p; probs_out, idx_out, psm
+// and lse do not see it.  Block 0 leaves mode[2] = 1 and the bits of the bias it used in mode[16 .. 16 + E): the router backward takes its
+// selection from there, not from the live tensor, which the balancer may have moved on by then.  NULL: a uniform branch not taken, mode[2] = 0.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
   __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
-  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; }
+  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; mode[2] = a.bias ? 1 : 0; }
+  if (a.bias && s == 0 && t < a.E) mode[16 + t] = __float_as_int(a.bias[t]);
   {
     float pre;
     if (ks > 1) {
@@ -833,7 +839,7 @@ __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, 
     if (idx_out) idx_out[s] = best;
     if (a.top_k) {                                 // (the kept sum holds the frame's largest probability, >= 1 / E: no division by 0)
       float kept;
-      const unsigned m = topk_select(s_p, a.E, a.top_k, &kept);
+      const unsigned m = a.bias ? topk_select_biased(s_p, a.bias, a.E, a.top_k, &kept) : topk_select(s_p, a.E, a.top_k, &kept);
       for (int e = 0; e < a.E; ++e) {
         float w = ((m >> e) & 1u) ? (a.renorm ? s_p[e] / kept : s_p[e]) : 0.f;
         if (a.mix) w *= a.mix[(long)s * a.E + e];
@@ -862,8 +868,12 @@ __global__ void __launch_bounds__(256) kk_lb_loss(const float* probs, int S, int
 // counts are integers below 2^24, exact in fp32 in any order.  The column sums of p are formed exactly as kk_lb_loss forms them: with
 // do_lb this launch writes the load-balancing loss too, bit-equal, and kk_lb_loss is not launched.  load goes to `load_sv` (saved:
 // the router backward reads it) and, when asked for, to `load_out`.
+// bias (avmoe_moe_forward_bias): the selection is the mixture's ACTUAL one, topk_select_biased on p[s] + bias, and load / balance are
+// that selection's.  select_count (E): += the number of frames that selected each expert -- the block sums of integer counts are exact
+// in fp32, one thread adds them in: no atomics.  NULL each: uniform branches not taken, today's instructions.
 __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float* lse, int S, int E, int kp, int do_lb, float* lb,
-                                                     float* aux, float* load_out, float* load_sv) {
+                                                     float* aux, float* load_out, float* load_sv, const float* bias,
+                                                     float* select_count) {
   __shared__ float red[4];
   __shared__ float s_P[MAX_E], s_ld[MAX_E];
   __shared__ float s_pr[256][MAX_E + 1];                 // one frame's probabilities per thread (+ 1: no bank conflicts)
@@ -884,7 +894,7 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
   for (int s = threadIdx.x; s < S; s += 256) {
     for (int e = 0; e < E; ++e) pr[e] = p[(long)s * E + e];
     float kept;
-    const unsigned m = topk_select(pr, E, kp, &kept);
+    const unsigned m = bias ? topk_select_biased(pr, bias, E, kp, &kept) : topk_select(pr, E, kp, &kept);
 #pragma unroll
     for (int e = 0; e < MAX_E; ++e) cnt[e] += (int)((m >> e) & 1u);
     const float l = lse[s];
@@ -895,7 +905,10 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
   for (int e = 0; e < MAX_E; ++e)
     if (e < E) {                                         // (uniform over the block)
       const float c = block_sum256((float)cnt[e], red);
-      if (threadIdx.x == 0) s_ld[e] = c / slots;
+      if (threadIdx.x == 0) {
+        s_ld[e] = c / slots;
+        if (select_count) select_count[e] += c;
+      }
     }
   zz = block_sum256(zz, red);
   if (threadIdx.x == 0) {
@@ -909,9 +922,32 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
     aux[1] = (float)E * b;
   }
 }
+// The counts alone, for a site call with select_count and without the auxiliary losses: ONE block, the selection and the sums of
+// kk_router_aux (thread t takes the frames t, t + 256, ...).
+__global__ void __launch_bounds__(256) kk_router_count(const float* p, int S, int E, int kp, const float* bias, float* select_count) {
+  __shared__ float red[4];
+  __shared__ float s_pr[256][MAX_E + 1];
+  int cnt[MAX_E];
+#pragma unroll
+  for (int e = 0; e < MAX_E; ++e) cnt[e] = 0;
+  float* pr = s_pr[threadIdx.x];
+  for (int s = threadIdx.x; s < S; s += 256) {
+    for (int e = 0; e < E; ++e) pr[e] = p[(long)s * E + e];
+    float kept;
+    const unsigned m = bias ? topk_select_biased(pr, bias, E, kp, &kept) : topk_select(pr, E, kp, &kept);
+#pragma unroll
+    for (int e = 0; e < MAX_E; ++e) cnt[e] += (int)((m >> e) & 1u);
+  }
+#pragma unroll
+  for (int e = 0; e < MAX_E; ++e)
+    if (e < E) {                                         // (uniform over the block)
+      const float c = block_sum256((float)cnt[e], red);
+      if (threadIdx.x == 0) select_count[e] += c;
+    }
+}
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out,
-             const float* mix_scale) {
+             const float* mix_scale, const float* select_bias, float* select_count) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
@@ -922,7 +958,7 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
   // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
   const bool mix_dense = mix_scale && !top_k;
   const int k_mix = mix_dense ? d.E : top_k;
-  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0, mix_scale};
+  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0, mix_scale, select_bias};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;
@@ -941,11 +977,15 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
   const float* dense = (const float*)(saved + (k_mix ? pl.o_psm : pl.o_probs));
   if (aux_out) {                                           // the auxiliary losses -- and the load-balancing loss from the same launch
     hipLaunchKernelGGL(kk_router_aux, dim3(1), dim3(256), 0, st, dense, (const float*)(saved + pl.o_lse), d.S, d.E, top_k ? top_k : 1,
-                       (lb_out && d.lb_loss) ? 1 : 0, lb_out, aux_out, load_out, (float*)(saved + pl.o_load));
+                       (lb_out && d.lb_loss) ? 1 : 0, lb_out, aux_out, load_out, (float*)(saved + pl.o_load), select_bias, select_count);
     AVMOE_CHECK_LAUNCH("router_aux");
   } else if (lb_out && d.lb_loss) {                        // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
     hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, dense, d.S, d.E, lb_out);
     AVMOE_CHECK_LAUNCH("lb_loss");
+  }
+  if (select_count && !aux_out) {                          // the balancer's counts without the auxiliary losses: their own one-block launch
+    hipLaunchKernelGGL(kk_router_count, dim3(1), dim3(256), 0, st, dense, d.S, d.E, top_k ? top_k : 1, select_bias, select_count);
+    AVMOE_CHECK_LAUNCH("router_count");
   }
   return OK;
 }

@@ -158,11 +158,23 @@ struct Ctx {
   V w;                              // the mixture weights: p, or the top-k weights
   const float* mix = nullptr;       // (S, E) multiplier on the mixture weights (avmoe_host_moe_forward_reg: stochastic depth / expert dropout), or NULL
   V wm;                             // mix * w: what the experts' outputs are multiplied by (= w without mix)
+  const float* bias = nullptr;      // (E) bias on the top-k selection alone (avmoe_host_moe_forward_bias: aux-loss-free balancing), or NULL
   std::vector<unsigned> sel;        // top-k: the kept experts of each frame (bit e)
+  std::vector<long> cnt;            // frames that selected each expert (the numerator of load)
   V lse, load;                      // router auxiliary losses (avmoe_host_moe_forward_aux): log-sum-exp per frame, share of the slots per expert
   float aux[2] = {0.f, 0.f};        // [z, balance]
   std::vector<Expert> ex;
 };
+
+// the experts of one frame that come before e in the top-k order: higher score first, equal scores in expert order; the score is the
+// probability, or with a selection bias p + b formed as one fp32 addition (volatile: no excess precision, no contraction)
+int rank_of(const float* ps, const float* bias, int E, int e) {
+  auto score = [&](int f) { volatile float v = bias ? ps[f] + bias[f] : ps[f]; return (float)v; };
+  const float se = score(e);
+  int rank = 0;
+  for (int f = 0; f < E; ++f) { const float sf = score(f); rank += (sf > se) || (sf == se && f < e); }
+  return rank;
+}
 
 int setup(const avmoe_moe_desc* q, Ctx& c) {
   if (!q) return fail(AVMOE_ERR_BAD_ARG, "host: null descriptor");
@@ -228,11 +240,8 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
     for (int s = 0; s < S; ++s) {
       const float* ps = c.p.data() + (long)s * E;
       float kept = 0.f;
-      for (int e = 0; e < E; ++e) {
-        int rank = 0;
-        for (int f = 0; f < E; ++f) rank += (ps[f] > ps[e]) || (ps[f] == ps[e] && f < e);
-        if (rank < c.topk) { c.sel[s] |= 1u << e; kept += ps[e]; }
-      }
+      for (int e = 0; e < E; ++e)
+        if (rank_of(ps, c.bias, E, e) < c.topk) { c.sel[s] |= 1u << e; kept += ps[e]; }      // (the bias ranks; the weights stay unbiased)
       for (int e = 0; e < E; ++e) c.w[s * E + e] = ((c.sel[s] >> e) & 1u) ? (c.renorm ? ps[e] / kept : ps[e]) : 0.f;
     }
   c.wm = c.w;                        // the regularisers' multiplier, behind the top-k weights; probs / idx / lb / aux stay those of the dense site
@@ -252,11 +261,8 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
       for (int e = 0; e < E; ++e) sum += std::exp((double)lg[e] - mx);
       const double l = mx + std::log(sum);
       c.lse[s] = (float)l; z += l * l;
-      for (int e = 0; e < E; ++e) {
-        int rank = 0;
-        for (int f = 0; f < E; ++f) rank += (ps[f] > ps[e]) || (ps[f] == ps[e] && f < e);
-        if (rank < kp) ++cnt[e];
-      }
+      for (int e = 0; e < E; ++e)
+        if (rank_of(ps, c.bias, E, e) < kp) ++cnt[e];      // (the load is the actual selection's: biased when a bias is given)
     }
     for (int e = 0; e < E; ++e) {
       double m = 0.0;
@@ -265,6 +271,7 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
       bal += (double)c.load[e] * (m / S);
     }
     c.aux[0] = (float)(z / S); c.aux[1] = (float)(E * bal);
+    c.cnt = cnt;
   }
   if (lb) {      // -sum_e log(mean_s p): the reference's kl_div against the constant 1 (PVT_AVSModel_v2.py:314-318)
     double v = 0.0;
@@ -376,17 +383,20 @@ int forward(Ctx& c, const float* X, const float* Y, const avmoe_moe_ptrs& P, con
 
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
              const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
-             const float* aux_grad, const float* mix_scale);
+             const float* aux_grad, const float* mix_scale, const float* select_bias);
 
-// the one forward behind avmoe_host_moe_forward / _topk / _aux / _reg (k_min: the smallest top_k the entry point takes)
+// the one forward behind avmoe_host_moe_forward / _topk / _aux / _reg / _bias (k_min: the smallest top_k the entry point takes)
 int forward_entry(int k_min, const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, int top_k,
-                  int renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, const float* mix_scale) {
+                  int renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, const float* mix_scale,
+                  const float* select_bias, float* select_count) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
   if (!X || !Y || !params || !out) return fail(AVMOE_ERR_BAD_ARG, "host forward: null pointer");
   if (top_k < k_min || top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host forward: top_k %d not in [%d, %d]", top_k, k_min, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale;
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale; c.bias = select_bias;
+  if (select_bias && !c.topk) return fail(AVMOE_ERR_BAD_ARG, "host forward: select_bias needs top-k gating, 0 < top_k < E (top_k %d, E %d)", top_k, c.E);
   if (int rc = forward(c, X, Y, *params, noise, out, probs, idx, lb, true)) return rc;
+  if (select_count) for (int e = 0; e < c.E; ++e) select_count[e] += (float)c.cnt[e];
   if (aux) {
     aux[0] = c.aux[0]; aux[1] = c.aux[1];
     if (load) for (int e = 0; e < c.E; ++e) load[e] = c.load[e];
@@ -404,7 +414,7 @@ size_t avmoe_host_moe_saved_bytes(const avmoe_moe_desc* desc) { (void)desc; retu
 int avmoe_host_moe_forward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, float* out,
                            float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  return forward_entry(0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr);
+  return forward_entry(0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
@@ -416,46 +426,60 @@ int avmoe_host_moe_backward(const avmoe_moe_desc* desc, const float* X, const fl
 int avmoe_host_moe_forward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, void* saved) {
   (void)saved;
-  return forward_entry(1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr);
+  return forward_entry(1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 int avmoe_host_moe_backward_topk(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                  const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                  const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 1) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, nullptr, nullptr);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, nullptr, nullptr, nullptr);
 }
 int avmoe_host_moe_forward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                int32_t top_k, int32_t renorm, float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
                                void* saved) {
   (void)saved;
-  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr);
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr, nullptr, nullptr);
 }
 int avmoe_host_moe_backward_aux(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, void* saved,
                                 float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, nullptr);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, nullptr, nullptr);
 }
 int avmoe_host_moe_forward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                int32_t top_k, int32_t renorm, const float* mix_scale, float* out, float* probs, int64_t* idx, float* lb,
                                float* aux, float* load, void* saved) {
   (void)saved;
-  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale);
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr);
 }
 int avmoe_host_moe_backward_reg(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
                                 void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm) {
   (void)saved;
   if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, mix_scale);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, mix_scale, nullptr);
+}
+int avmoe_host_moe_forward_bias(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                int32_t top_k, int32_t renorm, const float* mix_scale, const float* select_bias, float* select_count,
+                                float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved) {
+  (void)saved;
+  return forward_entry(0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count);
+}
+int avmoe_host_moe_backward_bias(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
+                                 const float* select_bias, void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k,
+                                 int32_t renorm) {
+  (void)saved;
+  if (top_k < 0) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [0, E]", top_k);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, top_k, renorm, aux_grad, mix_scale, select_bias);
 }
 int avmoe_host_moe_backward_ex(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
                                const float* dOut, const float* dprobs, const float* lb_grad, void* saved, float* dX, float* dY,
                                const avmoe_moe_ptrs* grads) {
   (void)saved;
-  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1, nullptr, nullptr);
+  return backward(desc, X, Y, params, noise, dOut, dprobs, lb_grad, dX, dY, grads, 0, 1, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"
@@ -465,11 +489,12 @@ namespace {
 // the reverse pass (the forward recomputed); top_k 0 or E: the dense mixture
 int backward(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise, const float* dOut,
              const float* dprobs, const float* lb_grad, float* dX, float* dY, const avmoe_moe_ptrs* grads, int top_k, int renorm,
-             const float* aux_grad, const float* mix_scale) {
+             const float* aux_grad, const float* mix_scale, const float* select_bias) {
   Ctx c;
   if (int rc = setup(desc, c)) return rc;
   if (top_k > c.E) return fail(AVMOE_ERR_BAD_ARG, "host backward: top_k %d not in [1, %d]", top_k, c.E);
-  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale;
+  c.topk = top_k == c.E ? 0 : top_k; c.renorm = renorm != 0; c.mix = mix_scale; c.bias = select_bias;
+  if (select_bias && !c.topk) return fail(AVMOE_ERR_BAD_ARG, "host backward: select_bias needs top-k gating, 0 < top_k < E (top_k %d, E %d)", top_k, c.E);
   if (!X || !Y || !params || !dX || !dY || !grads) return fail(AVMOE_ERR_BAD_ARG, "host backward: null pointer");
   const avmoe_moe_ptrs& P = *params; const avmoe_moe_ptrs& G = *grads;
   const int S = c.S, N = c.N, C = c.C, M = c.M, Cy = c.Cy, E = c.E, K = c.K, d = c.d;

@@ -41,7 +41,8 @@ int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float*
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm,            // top_k 0: the dense mixture
              float* aux_out, float* load_out,                                                    // aux_out: [z, balance] (avmoe_moe_forward_aux)
-             const float* mix_scale);                                                            // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg) or NULL
+             const float* mix_scale,                                                             // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg) or NULL
+             const float* select_bias, float* select_count);                                     // (E) selection bias / (E) counts added to (avmoe_moe_forward_bias), NULL each
 // ---- forward: per token -----------------------------------------------------------------------
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);

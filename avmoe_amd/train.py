@@ -8,6 +8,8 @@
                                second pass)
   * `reestimate_bn`         -- BatchNorm statistics re-estimated with forward passes (momentum=None, torch's update_bn), for the
                                raw weights or, with `ema=opt`, for FlatAdam's averaged weights
+  * `RouterBiasBalancer`    -- aux-loss-free expert balancing of top-k sites: a bias on the selection, updated on the device after
+                               every optimizer step
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
                                site), main_trans_v3.py:155-226
   * `save_adapters` / `load_adapters` / `strip_prefix` -- adapter-only checkpoints with the reference's state_dict keys
@@ -100,6 +102,88 @@ def router_aux_total(sites, z_weight: float = 0.0, balance_weight: float = 0.0) 
     if not terms:
         raise ValueError("router_aux_total: no sites")
     return torch.stack(terms).sum()
+
+
+class RouterBiasBalancer:
+    """Aux-loss-free expert balancing of top-k sites (Wang et al. 2024; include/avmoe.h at avmoe_moe_forward_bias): every site gets a
+    per-expert bias that enters its top-k SELECTION only, every training forward adds its selection counts to the site's row of
+    `counts`, and `step()` -- once per optimizer step, after `opt.step()` -- lowers the bias of the experts that were selected more often
+    than the mean by `rate`, raises the others' and clears the counts: ONE launch for all sites (avmoe_router_bias_update), no gradient,
+    no loss term.  bias and counts are flat (n_sites, 16) fp32 tensors on the sites' device, the sites hold views of their rows
+    (`site.router_select_bias`, `site.router_select_count`: plain attributes, no state_dict key).  The sites must run with
+    `router_top_k` in [1, E).  With `group` of more than one rank, step() first sums the counts over the ranks, so every rank makes the
+    same update."""
+
+    ROW = 16                                             # AVMOE_MAX_EXPERTS: the row length of bias / counts
+
+    def __init__(self, sites, rate: float = 1e-3, group=None):
+        self.sites = list(sites)
+        if not self.sites:
+            raise ValueError("RouterBiasBalancer: no sites")
+        self.rate = self._rate(rate)
+        self.group = group
+        self.E = [int(s.num_multimodal_experts + s.num_singlemodal_experts) for s in self.sites]
+        for i, e in enumerate(self.E):
+            if not 1 <= e <= self.ROW:
+                raise ValueError(f"RouterBiasBalancer: site {i} has {e} experts, outside [1, {self.ROW}]")
+        devs = {next(s.parameters()).device for s in self.sites}
+        if len(devs) != 1:
+            raise ValueError(f"RouterBiasBalancer: the sites live on several devices ({sorted(map(str, devs))})")
+        self.device = devs.pop()
+        n = len(self.sites)
+        self.bias = torch.zeros(n, self.ROW, dtype=torch.float32, device=self.device)
+        self.counts = torch.zeros(n, self.ROW, dtype=torch.float32, device=self.device)
+        self.E_table = torch.tensor(self.E, dtype=torch.int32, device=self.device)
+        for i, (s, e) in enumerate(zip(self.sites, self.E)):      # each site its own row: the two sites of a pair never share one
+            s.router_select_bias, s.router_select_count = self.bias[i, :e], self.counts[i, :e]
+
+    @staticmethod
+    def _rate(rate):
+        import math
+        if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not math.isfinite(rate) or rate < 0:
+            raise ValueError(f"RouterBiasBalancer: rate must be a finite number >= 0, got {rate!r}")
+        return float(rate)
+
+    def step(self):
+        """The update after an optimizer step: (the counts summed over `group`,) one avmoe_router_bias_update launch on the current stream."""
+        L = capi.lib()
+        if not getattr(L, "avmoe_site_bias", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_bias / avmoe_router_bias_update: it serves no router selection bias")
+        if not self.bias.is_cuda:
+            raise capi.AvmoeError("RouterBiasBalancer.step runs on the GPU (no CPU fallback)")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(self.counts, op=dist.ReduceOp.SUM, group=self.group)      # integers in fp32: exact, the same on every rank
+        st = L.avmoe_router_bias_update(self.bias.data_ptr(), self.counts.data_ptr(), self.E_table.data_ptr(), len(self.sites),
+                                        self.rate, torch.cuda.current_stream(self.device).cuda_stream)
+        capi.check(st, "avmoe_router_bias_update")
+
+    def loads(self) -> List[torch.Tensor]:
+        """Per site, the share of the selections each expert received since the last step() ((E_i,) tensors that sum to 1; zeros when
+        nothing was counted).  The counts are not cleared."""
+        out = []
+        for i, e in enumerate(self.E):
+            c = self.counts[i, :e]
+            out.append(c / c.sum().clamp_min(1.0))
+        return out
+
+    def state_dict(self) -> dict:
+        return {"bias": self.bias.detach().cpu().clone(), "counts": self.counts.detach().cpu().clone(), "E": list(self.E), "rate": self.rate}
+
+    def load_state_dict(self, state: dict):
+        if list(state["E"]) != self.E:
+            raise ValueError(f"RouterBiasBalancer.load_state_dict: the state is for sites with {list(state['E'])} experts, these have {self.E}")
+        for name in ("bias", "counts"):
+            t = torch.as_tensor(state[name], dtype=torch.float32)
+            if tuple(t.shape) != (len(self.sites), self.ROW):
+                raise ValueError(f"RouterBiasBalancer.load_state_dict: {name} has shape {tuple(t.shape)}, expected {(len(self.sites), self.ROW)}")
+            getattr(self, name).copy_(t)                 # in place: the sites keep their views
+        self.rate = self._rate(state["rate"])
+
+    def detach(self):
+        """Gives the sites back their None: they run unbiased again, and count nothing."""
+        for s in self.sites:
+            s.router_select_bias = s.router_select_count = None
 
 
 @contextlib.contextmanager

@@ -304,6 +304,43 @@ int avmoe_moe_backward_reg(const avmoe_moe_desc* desc, const void* X, const void
  * AVMOE_ERR_BAD_ARG, with nothing launched and nothing written: a NULL pointer, p or q outside [0, 1), S < 1, E outside [1, 16].       */
 int avmoe_mix_drop_draw(void* state, int64_t S, int32_t E, float p, float q, float* mix_scale, void* stream);
 
+/* avmoe_moe_forward_bias / avmoe_router_bias_update (found by symbol, as above; AVMOE_ABI_VERSION stays 11) -- aux-loss-free expert
+ * balancing of the top-k gating (Wang et al. 2024, DeepSeek-V3): a per-expert bias b that enters the SELECTION only.  With p the dense
+ * softmax of a frame and 0 < k < E:
+ *     sc_e   = p_e + b_e                     ONE fp32 addition
+ *     S_k(s) = the k experts with the highest score (higher score first, equal scores in expert order: the tie rule of the top-k mixture)
+ *     kept   = sum of the kept p_e           unbiased, added in expert order
+ *     w_e    = m_e p_e / kept (renorm) or m_e p_e ,  then times mix_scale          -- the weights never see b
+ * avmoe_moe_forward_bias is avmoe_moe_forward_reg plus
+ *   select_bias:  DEVICE pointer to E floats, or NULL.  Read by the call, never written.  It has no gradient.
+ *   select_count: DEVICE pointer to E floats, or NULL.  ADDED to, not overwritten: select_count[e] += the number of frames of this call
+ *                 that selected expert e (the actual, biased selection; without a bias the plain one; a dense site counts every frame's
+ *                 first-max expert, as `load` does).  Integers kept in fp32, exact below 2^24; one thread of one block adds them in.
+ * Both NULL: avmoe_moe_forward_reg, launch for launch and bit for bit.  With a bias, probs, idx, lb, the z-loss, the BatchNorm statistics
+ * and every saved tensor but the weights are those of the call without it, bit for bit, and a bias of zeros gives the bits of NULL in
+ * every output.  `load` (and the balance loss formed from it) is the share of the ACTUAL selection.  select_count with aux comes out of
+ * the auxiliary-loss launch; without aux it costs one more one-block launch.
+ * select_bias != NULL with top_k == 0 or top_k == E: AVMOE_ERR_BAD_ARG before anything is launched (a dense mixture has no selection).
+ * `saved`: word [2] of the `mode` buffer (64 four-byte words; [0] = k, [1] = renorm) is 1 when the forward used a bias and 0 otherwise
+ * -- every router forward writes it --, and words [16, 16 + E) hold the bits of the bias values it USED.  No buffer is added and
+ * avmoe_moe_saved_bytes does not change.  There is no new backward entry point: every existing one recomputes the selection from the
+ * saved softmax and THOSE words, so a bias updated between a forward and its backward does not change the backward's selection.
+ *
+ * avmoe_router_bias_update -- the update after an optimizer step, ONE launch for all sites of a model (csrc/router_bias.hip).  bias and
+ * counts: DEVICE (n_sites, 16) f32, row i belongs to site i, E: DEVICE (n_sites) int32.  For every site i with E_i in [1, 16]:
+ *     tot = sum_e counts[i][e]  (expert order) ;  tot == 0: the row is left alone ;  otherwise  d_e = tot - E_i counts[i][e]  and
+ *     bias[i][e] += +rate (d_e > 0: below the mean count), -rate (d_e < 0), nothing (d_e == 0) ;  then counts[i][e] = 0.
+ * The sign test is exact while tot and E_i counts[i][e] stay below 2^24 (1 048 576 routing slots per site between two updates at E = 16).
+ * Columns e >= E_i are neither read nor written; a row whose E_i is outside [1, 16] is skipped.  No host scalar changes between two
+ * calls: the launch is capturable.  AVMOE_ERR_BAD_ARG, with nothing launched: a NULL pointer, n_sites < 1, rate negative or not finite. */
+int avmoe_moe_forward_bias(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                           const float* noise, int32_t top_k /* 0: dense */, int32_t renorm, const float* mix_scale /* (S,E) f32 or NULL */,
+                           const float* select_bias /* (E) f32 or NULL */, float* select_count /* (E) f32, added to, or NULL */,
+                           void* out, float* probs, int64_t* idx, float* lb, float* aux /* [z, balance] or NULL */,
+                           float* load /* (E) or NULL */, void* saved, void* scratch, void* stream);
+int avmoe_router_bias_update(float* bias /* DEVICE (n_sites, 16) */, float* counts /* DEVICE (n_sites, 16) */,
+                             const int32_t* E /* DEVICE (n_sites) */, int32_t n_sites, float rate, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B

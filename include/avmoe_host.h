@@ -72,6 +72,21 @@ int avmoe_host_moe_backward_reg(const avmoe_moe_desc* desc, const float* X, cons
                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
                                 void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k, int32_t renorm);
 
+/* as avmoe_moe_forward_bias: avmoe_host_moe_forward_reg plus the selection bias of aux-loss-free balancing.  select_bias: (E) HOST
+ * pointer or NULL; the k experts are chosen on p + b (one fp32 addition, the tie rule of the top-k mixture), the weights are formed
+ * from the unbiased p, and load / balance are the actual selection's.  select_count: (E) HOST pointer or NULL, ADDED to: the number of
+ * frames that selected each expert.  select_bias with top_k == 0 or E: AVMOE_ERR_BAD_ARG.  Both NULL: avmoe_host_moe_forward_reg.     */
+int avmoe_host_moe_forward_bias(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                int32_t top_k, int32_t renorm, const float* mix_scale, const float* select_bias, float* select_count,
+                                float* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved);
+
+/* avmoe_host_moe_backward_reg of such a forward.  The host backward recomputes the forward, so it takes the bias the forward saw as an
+ * argument (the device library reads it from `saved`); the bias and the selection carry no gradient.                                 */
+int avmoe_host_moe_backward_bias(const avmoe_moe_desc* desc, const float* X, const float* Y, const avmoe_moe_ptrs* params, const float* noise,
+                                 const float* dOut, const float* dprobs, const float* lb_grad, const float* aux_grad, const float* mix_scale,
+                                 const float* select_bias, void* saved, float* dX, float* dY, const avmoe_moe_ptrs* grads, int32_t top_k,
+                                 int32_t renorm);
+
 #ifdef __cplusplus
 }
 #endif
