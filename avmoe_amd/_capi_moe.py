@@ -239,6 +239,12 @@ def declare(L):
         L.avmoe_moe_forward_bias.restype, L.avmoe_moe_forward_bias.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 12
         L.avmoe_router_bias_update.restype = C.c_int
         L.avmoe_router_bias_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]
+    # expert-choice gating (found by symbol: the site forward with a per-expert selection of frames, and the selection as a sub-op)
+    L.avmoe_site_choice = L.avmoe_site_reg and hasattr(L, "avmoe_moe_forward_choice") and hasattr(L, "avmoe_expert_choice")
+    if L.avmoe_site_choice:
+        L.avmoe_moe_forward_choice.restype, L.avmoe_moe_forward_choice.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 11
+        L.avmoe_expert_choice.restype = C.c_int
+        L.avmoe_expert_choice.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

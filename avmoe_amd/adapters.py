@@ -19,7 +19,9 @@ from __future__ import annotations
 
 import ctypes as C
 import itertools
+import math
 from collections import namedtuple
+from fractions import Fraction
 from typing import Dict
 
 import numbers
@@ -146,6 +148,11 @@ def _rate(name, v):
     return float(v)
 
 
+def expert_choice_capacity(k, S, E):
+    """c = min(S, max(1, ceil(k S / E))) of expert-choice gating with a mean of k experts per frame, evaluated exactly (Fraction(k))."""
+    return min(S, max(1, math.ceil(Fraction(k) * S / E)))
+
+
 def _draw_mix(module, L, S, E, p, q, dev, stream):
     """The (S, E) multiplier of one training-mode call, drawn on `stream` by avmoe_mix_drop_draw into the site's cached tensor.  The site
     owns the generator's state block {seed, calls} on the device: nothing the host writes changes between two calls, so a captured
@@ -167,12 +174,22 @@ def _draw_mix(module, L, S, E, p, q, dev, stream):
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
     """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
     losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call;
-    or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too).
+    or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too);
+    or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike.
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
     stream: the handle (int) of the CURRENT stream when the caller already has it (AdapterPair), else looked up."""
+    choice_k = module.router_expert_choice
+    if choice_k is not None:                              # (the site's settings first: a contradiction in them does not depend on the call)
+        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
+        if (module.router_top_k is not None and module.router_top_k < E_) or module.router_select_bias is not None \
+                or module.router_select_count is not None:
+            raise ValueError("router_expert_choice selects per expert: it combines with neither router_top_k in [1, E) nor router_select_bias / "
+                             "router_select_count (a RouterBiasBalancer)")
+        if not getattr(capi.lib(), "avmoe_site_choice", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_choice / avmoe_expert_choice: it serves no expert-choice gating")
     if not (X.is_cuda and Y.is_cuda):
         raise capi.AvmoeError("avmoe_amd runs on MI355X only: tensors must live on a GPU (no CPU fallback)")
     if stream is None:
@@ -210,6 +227,13 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     biased = sel_bias is not None or sel_count is not None
     if biased and not getattr(L, "avmoe_site_bias", False):
         raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_bias / avmoe_router_bias_update: it serves no router selection bias")
+    # expert-choice gating (include/avmoe.h at avmoe_moe_forward_choice): each expert takes its c frames, c from the mean number of
+    # experts per frame -- exactly, in rationals --; a function of S alone, so a captured call keeps its capacity
+    capacity, choice = 0, None
+    if choice_k is not None:
+        capacity = expert_choice_capacity(choice_k, S, E)
+        choice = torch.empty(S, device=X.device, dtype=torch.int32)
+    module.__dict__["_last_expert_choice"] = choice
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -229,7 +253,13 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
     mix = _draw_mix(module, L, S, E, drop_p, drop_q, X.device, stream) if reg else None
     module.__dict__["_mix_last"] = mix
-    if biased:                                           # the selection bias / counts (and the multiplier, when one was drawn)
+    if choice is not None:                               # expert choice (and the multiplier, when one was drawn)
+        fn = "avmoe_moe_forward_choice"
+        st = L.avmoe_moe_forward_choice(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), capacity,
+                                        int(module.router_expert_choice_renorm), _ptr(mix), out.data_ptr(), probs.data_ptr(), idx.data_ptr(),
+                                        lb.data_ptr(), aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None,
+                                        choice.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+    elif biased:                                         # the selection bias / counts (and the multiplier, when one was drawn)
         fn = "avmoe_moe_forward_bias"
         st = L.avmoe_moe_forward_bias(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix), _ptr(sel_bias),
                                       _ptr(sel_count), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
@@ -455,6 +485,8 @@ class _PairFunction(torch.autograd.Function):
             join(ctx_ev[3])
             for t_ in (out_b, idx_b, pr_b, lb_b, st_b[1]) + (ax_b if ax_b is not None else ()):
                 t_.record_stream(main)
+            if site_b.last_expert_choice is not None:    # (made on the side stream like the outputs above)
+                site_b.last_expert_choice.record_stream(main)
         else:
             out_a, pr_a, idx_a, lb_a, st_a, ax_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, stream=main.cuda_stream)
             out_b, pr_b, idx_b, lb_b, st_b, ax_b = _site_forward(site_b, st_a[3], st_a[2], noises[1], names_b, pb, add_to=base_b, stream=main.cuda_stream)
@@ -648,6 +680,9 @@ class MoEAdapter(nn.Module):
         # the router auxiliary losses (z-loss, Switch balance loss: include/avmoe.h at avmoe_moe_forward_aux) beside every forward; a
         # plain attribute like the two above.  Off: the entry points and launches of a site without them.
         self.router_aux = getattr(opt, "router_aux", False)
+        # expert-choice gating (include/avmoe.h at avmoe_moe_forward_choice): each expert takes its share of the frames.  Plain attributes too.
+        self.router_expert_choice = getattr(opt, "router_expert_choice", None)
+        self.router_expert_choice_renorm = getattr(opt, "router_expert_choice_renorm", False)
         # the regularisers of the mixture (include/avmoe.h at avmoe_moe_forward_reg): stochastic depth on the adapter branch and expert
         # dropout, training mode only.  Plain attributes like the ones above, not state: no state_dict key, no buffer.
         self.__dict__["_mix_index"] = next(_MIX_SITES)
@@ -755,6 +790,38 @@ class MoEAdapter(nn.Module):
                 raise ValueError(f"router_top_k must be None or an integer in [1, {E}], got {k!r}")
             k = int(k)
         self.__dict__["_router_top_k"] = k
+
+    @property
+    def router_expert_choice(self):
+        """None (off), or k in (0, E]: expert-choice gating with a mean of k experts per frame -- each expert takes the
+        c = min(S, max(1, ceil(k S / E))) frames of the call on which the router scores it highest; a frame may get no expert (its output is 0)
+        or several.  It applies in training and eval mode alike, so an evaluation depends on the batch.  It combines with neither
+        `router_top_k` in [1, E) nor a selection bias (checked when the site runs)."""
+        return self.__dict__.get("_router_expert_choice")  # (.get: a module pickled before the setting existed has none)
+
+    @router_expert_choice.setter
+    def router_expert_choice(self, k):
+        E = self.num_multimodal_experts + self.num_singlemodal_experts
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (numbers.Real, Fraction)) or not (math.isfinite(k) and 0 < k <= E):
+                raise ValueError(f"router_expert_choice must be None or a number in (0, {E}], got {k!r}")
+        self.__dict__["_router_expert_choice"] = k
+
+    @property
+    def router_expert_choice_renorm(self):
+        """False (the default, as in Zhou et al. 2022): a frame's weights are the probabilities of the experts that took it; True: divided
+        by their sum (a frame no expert took keeps weights of 0)."""
+        return self.__dict__.get("_router_expert_choice_renorm", False)
+
+    @router_expert_choice_renorm.setter
+    def router_expert_choice_renorm(self, v):
+        self.__dict__["_router_expert_choice_renorm"] = bool(v)
+
+    @property
+    def last_expert_choice(self):
+        """The (S,) int32 bitmask of the last forward -- bit e set where expert e took the frame --, detached; None when it ran without
+        `router_expert_choice` (or none ran yet)."""
+        return self.__dict__.get("_last_expert_choice")
 
     @property
     def router_top_k_renorm(self):
@@ -876,7 +943,7 @@ class MoEAdapter(nn.Module):
     def __getstate__(self):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
         for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux", "_mix_state", "_mix_buf",
-                  "_mix_last", "_mix_draws"):
+                  "_mix_last", "_mix_draws", "_last_expert_choice"):
             st.pop(k, None)
         return st
 

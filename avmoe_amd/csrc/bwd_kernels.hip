@@ -170,11 +170,16 @@ struct RouterBwdArgs {
 // dL/d(c w): dw_e = c_e dp_e, while sum_j w_j dw_j = sum_j (c w)_j dp_j needs no factor.  c has no gradient.  NULL: a uniform branch not taken.
 // mode[2] (avmoe_moe_forward_bias): the forward ranked the experts on p + b; the selection is recomputed with the bias words the forward
 // left in mode[16 .. 16 + E) -- not with the live bias tensor, which the balancer may have updated since.  The bias has no gradient.
+// mode[3] = c > 0 (avmoe_moe_forward_choice): expert-choice gating.  The forward left the dense-with-a-multiplier form in mode[0 .. 2] and,
+// per expert, T_e in mode[32 + e] and L_e in mode[48 + e]; m_e = ec_member(p_e, T_e, L_e, s) is the forward's mask, never a selection run
+// again, and kept = sum_e m_e p_e in expert order.  mode[4] is the renorm of the choice:  dp_e = m_e (dw_e - sum_j (c w)_j dp_j) / kept, or
+// m_e dw_e without it; a frame no expert took gets dp = 0.  The selection has no gradient.
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x;
-  const int top_k = mode[0], renorm = mode[1];   // (uniform over the grid)
+  const int top_k = mode[0];                     // (uniform over the grid)
+  int renorm = mode[1];
   const float* wt = probs;                       // the mixture weights
   if (top_k) probs = psm;                        // from here on: the softmax
   float* dh1 = rbw + (long)s * 128;
@@ -200,7 +205,12 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
       for (int e = 0; e < a.E; ++e) s_p[e] = probs[(long)s * a.E + e];
       float kept, wd = 0.f;
       unsigned m;
-      if (mode[2]) {                               // (uniform over the grid) a forward with a selection bias: the values it USED
+      if (mode[3]) {                               // (uniform over the grid) an expert-choice forward: the mask from p and the two words per expert
+        m = 0u; kept = 0.f;
+        for (int e = 0; e < a.E; ++e)
+          if (ec_member(s_p[e], __int_as_float(mode[32 + e]), mode[48 + e], s)) { m |= 1u << e; kept += s_p[e]; }
+        renorm = mode[4];                          // (a frame no expert took has m = 0: nothing is divided by its kept = 0)
+      } else if (mode[2]) {                             // (uniform over the grid) a forward with a selection bias: the values it USED
         float bs[MAX_E];
         for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[16 + e]);
         m = topk_select_biased(s_p, bs, a.E, top_k, &kept);

@@ -63,6 +63,21 @@ __device__ __forceinline__ unsigned topk_select_biased(const float* p, const flo
   return m;
 }
 
+// Expert-choice gating (avmoe_moe_forward_choice, expert_choice.hip): the order-preserving 32-bit key of an fp32 value -- a larger value
+// has a larger key, -0 and +0 share one, so that for numbers key order IS the order of `>` / `==` -- and the membership test of frame s in
+// an expert's selection from its two words: T = the c-th largest value of the column, L = the last frame taken among the values equal to T.
+// The forward and the router backward call ec_member on the same p, T, L: the same mask.
+__device__ __forceinline__ unsigned ec_key(float v) {
+  unsigned u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ec_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ bool ec_member(float p, float T, int L, long s) {
+  const unsigned kp = ec_key(p), kt = ec_key(T);
+  return kp > kt || (kp == kt && s <= (long)L);
+}
+
 // element access for the activation / operand type T (float or __bf16)
 template <typename T> __device__ __forceinline__ float ldT(const T* p, long i);
 template <> __device__ __forceinline__ float ldT<float>(const float* p, long i) { return p[i]; }

@@ -775,6 +775,7 @@ struct RouterArgs {
   int C2, E, S, top_k, renorm;    // top_k: 0 = the dense mixture
   const float* mix;               // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg), or NULL; k_router then runs the top-k form
   const float* bias;              // (E) selection bias of the top-k gating (avmoe_moe_forward_bias), or NULL
+  int choice_c, choice_renorm;    // expert-choice gating (avmoe_moe_forward_choice): the capacity (0: off) and its renorm, for the mode words
 };
 // one block per frame: layer-1 pre-activations from the engine GEMM -- summed here over its split-K slabs, in slab order, when it
 // ran split (no separate reduce pass) --, then bias / ReLU, the two small layers, softmax and first-max argmax.  fp32, fixed order.
@@ -790,13 +791,16 @@ struct RouterArgs {
 // (topk_select_biased), the weights are still m_e p_e / kept or m_e p_e with kept the sum of the kept unbiased p; probs_out, idx_out, psm
 // and lse do not see it.  Block 0 leaves mode[2] = 1 and the bits of the bias it used in mode[16 .. 16 + E): the router backward takes its
 // selection from there, not from the live tensor, which the balancer may have moved on by then.  NULL: a uniform branch not taken, mode[2] = 0.
+// a.choice_c (avmoe_moe_forward_choice): block 0 leaves mode[3] = c and mode[4] = its renorm (0 / 0: off -- every router forward writes them).
+// k_router then runs the dense-with-a-multiplier form without the multiplier (psm = p, probs = p), and the two launches of expert_choice.hip
+// behind this one put the selection words into mode[32 ..) / mode[48 ..) and the weights into `probs`.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
   __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
-  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; mode[2] = a.bias ? 1 : 0; }
+  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; mode[2] = a.bias ? 1 : 0; mode[3] = a.choice_c; mode[4] = a.choice_renorm; }
   if (a.bias && s == 0 && t < a.E) mode[16 + t] = __float_as_int(a.bias[t]);
   {
     float pre;
@@ -947,7 +951,7 @@ __global__ void __launch_bounds__(256) kk_router_count(const float* p, int S, in
 }
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out,
-             const float* mix_scale, const float* select_bias, float* select_count) {
+             const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
@@ -956,9 +960,12 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
   if (top_k < 0 || top_k > d.E) { set_last_error("moe: top_k %d not in [0, %d]", top_k, d.E); return ERR_BAD_ARG; }
   // A dense site with a multiplier runs as top-k with k = E without renormalisation: w = p exactly, every expert kept, and the softmax
   // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
-  const bool mix_dense = mix_scale && !top_k;
+  // Expert choice (top_k == 0, no bias: the callers see to it) takes that form too, WITHOUT the multiplier: k_expert_choice, launched by
+  // moe_forward behind this wrapper, overwrites `probs` with the weights of its selection, times the multiplier.
+  const bool mix_dense = (mix_scale || choice) && !top_k;
   const int k_mix = mix_dense ? d.E : top_k;
-  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0, mix_scale, select_bias};
+  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0,
+               choice ? nullptr : mix_scale, select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;

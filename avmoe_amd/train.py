@@ -8,6 +8,7 @@
                                second pass)
   * `reestimate_bn`         -- BatchNorm statistics re-estimated with forward passes (momentum=None, torch's update_bn), for the
                                raw weights or, with `ema=opt`, for FlatAdam's averaged weights
+  * `expert_choice_mask`    -- expert-choice gating as a function: which frames each expert takes from an (S, E) matrix, on the device
   * `RouterBiasBalancer`    -- aux-loss-free expert balancing of top-k sites: a bias on the selection, updated on the device after
                                every optimizer step
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
@@ -85,6 +86,24 @@ def topk_experts(probs: torch.Tensor, k: int) -> torch.Tensor:
                                       torch.cuda.current_stream(p.device).cuda_stream)
     capi.check(st, "avmoe_router_topk")
     return out
+
+
+def expert_choice_mask(probs: torch.Tensor, capacity: int) -> torch.Tensor:
+    """(S, E) bool: expert-choice gating as a function (include/avmoe.h at avmoe_expert_choice) -- column e is True on the `capacity`
+    frames with the highest probs[:, e], higher probability first, equal probabilities in frame order.  The sites' own selection
+    (`site.router_expert_choice`) on a caller's matrix."""
+    L = capi.lib()
+    if not getattr(L, "avmoe_site_choice", False):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_choice / avmoe_expert_choice: it serves no expert-choice gating")
+    if not probs.is_cuda:
+        raise capi.AvmoeError("expert_choice_mask runs on the GPU (no CPU fallback)")
+    p = probs.reshape(-1, probs.shape[-1]).to(torch.float32).contiguous()
+    S, E = p.shape
+    bits = torch.empty(S, dtype=torch.int32, device=p.device)
+    st = L.avmoe_expert_choice(p.data_ptr(), S, E, int(capacity), 0, None, None, bits.data_ptr(), None, None,
+                               torch.cuda.current_stream(p.device).cuda_stream)
+    capi.check(st, "avmoe_expert_choice")
+    return (bits[:, None] >> torch.arange(E, device=p.device, dtype=torch.int32)[None, :]) & 1 != 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

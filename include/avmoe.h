@@ -341,6 +341,49 @@ int avmoe_moe_forward_bias(const avmoe_moe_desc* desc, const void* X, const void
 int avmoe_router_bias_update(float* bias /* DEVICE (n_sites, 16) */, float* counts /* DEVICE (n_sites, 16) */,
                              const int32_t* E /* DEVICE (n_sites) */, int32_t n_sites, float rate, void* stream);
 
+/* avmoe_moe_forward_choice / avmoe_expert_choice (found by symbol, as above; AVMOE_ABI_VERSION stays 11) -- expert-choice gating (Zhou et
+ * al. 2022; csrc/expert_choice.hip): each EXPERT takes the `capacity` frames on which the router scores it highest, so the load is balanced
+ * by construction -- no loss weight, no update rate -- and a frame may be served by no, one or several experts.  With p the dense softmax
+ * of the call, (S, E) fp32, AVS noise included, and capacity = c in [1, S]:
+ *     C_e     = the c frames with the highest p[s, e]: higher probability first, equal probabilities in frame order (lower s first)
+ *     m[s, e] = 1[s in C_e] ,   n_s = sum_e m[s, e] ,   kept_s = sum_e m[s, e] p[s, e]       added in expert order
+ *     w[s, e] = m[s, e] p[s, e]                         renorm == 0
+ *     w[s, e] = m[s, e] p[s, e] / kept_s                renorm != 0 ;  w[s, :] = 0 where n_s == 0
+ *     w is then multiplied by mix_scale[s, e] if one is given, and out[s] = sum_e w[s, e] expert_e(x)[s]  (out[s] = 0 exactly where n_s == 0).
+ * Only the weights change: every expert still runs on every frame, and the BatchNorm batch and running statistics, probs (the dense
+ * softmax), idx (its first-max argmax), lb, aux and load are those of the dense call, bit for bit -- the auxiliary losses keep the dense
+ * site's rule k' = 1 (the load of the actual selection is 1 / E by construction and carries no information).  The selection has no gradient.
+ * The selection of expert e is fully described by two words: T_e, the c-th largest value of column e, and L_e, the largest frame index
+ * taken among the frames equal to T_e;  m[s, e] = (p[s, e] > T_e) || (p[s, e] == T_e && s <= L_e)  exactly.
+ * Backward, with g = dL/d(mix w) arriving as today and dw_e = mix_e g_e:  dp_e = m_e dw_e (renorm == 0) ;
+ * dp_e = m_e (dw_e - sum_j (mix w)_j g_j) / kept_s (renorm != 0), dp = 0 where n_s == 0 ;  then dprobs, lb, the auxiliary terms and the
+ * softmax Jacobian as ever.  It evaluates the mask per frame from the saved softmax and the words below and never runs the selection again.
+ * There is no new backward entry point and no further backward launch: every existing one serves a choice forward (avmoe_moe_backward_reg
+ * when a multiplier was used; dOut == NULL takes the router-only path; avmoe_moe_backward_dx_dy is untouched).
+ * `saved`, `mode` buffer:  [3] = c (0: expert choice off -- every router forward writes it), [4] = renorm of the choice,
+ * [32 + e] = the bits of T_e, [48 + e] = L_e.  A choice forward leaves [0] = E, [1] = 0, the "dense with a multiplier" form, so the saved
+ * softmax is kept; [2] and [16, 32) are as without it.  No buffer is added and avmoe_moe_saved_bytes does not change.
+ * Non-finite probabilities give an unspecified selection; every access stays in bounds and exactly c frames per expert are marked.
+ *
+ * avmoe_moe_forward_choice is avmoe_moe_forward_reg with top_k = 0, plus the choice: choice[s] (DEVICE (S) int32, or NULL) has bit e set
+ * iff s in C_e.  There is no selection bias and no selection count in this mode.  It adds two launches to the forward (one block per
+ * expert for T and L; one thread per frame for the weights and the bitmask); no host scalar changes between calls, so it is capturable.
+ * capacity outside [1, S]: AVMOE_ERR_BAD_ARG with nothing launched.  capacity == S without renorm and without a multiplier gives
+ * avmoe_moe_forward's bits in every output.
+ *
+ * avmoe_expert_choice -- the same kernels on a caller's DEVICE (S, E) fp32 matrix p.  w (S, E), choice (S), thr (E: T_e) and last (E: L_e)
+ * may each be NULL; w must not overlap p.  With w or choice asked for but thr or last NULL, the call takes the 128 bytes for the missing
+ * words from the stream's memory pool (hipMallocAsync / hipFreeAsync): it allocates, and capturing that form needs a runtime that captures
+ * pool allocations -- pass thr and last to avoid it (the site call never allocates: its words live in `saved`).
+ * AVMOE_ERR_BAD_ARG, with nothing launched: p NULL, S outside [1, 2^31 - 1] (L_e is an int32), E outside [1, 16], capacity outside [1, S]. */
+int avmoe_moe_forward_choice(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                             const float* noise, int32_t capacity, int32_t renorm, const float* mix_scale /* (S,E) f32 or NULL */,
+                             void* out, float* probs, int64_t* idx, float* lb, float* aux /* [z, balance] or NULL */,
+                             float* load /* (E) or NULL */, int32_t* choice /* (S) or NULL */, void* saved, void* scratch, void* stream);
+int avmoe_expert_choice(const float* p, int64_t S, int32_t E, int32_t capacity, int32_t renorm, const float* mix_scale /* (S,E) or NULL */,
+                        float* w /* (S,E) or NULL */, int32_t* choice /* (S) or NULL */, float* thr /* (E) or NULL */,
+                        int32_t* last /* (E) or NULL */, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B
