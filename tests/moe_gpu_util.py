@@ -23,7 +23,7 @@ def make_desc(cfg, S, bf16, training):
 class MoeRun:
     """One forward (+ optional backward) of the HIP path on cuda:0."""
 
-    def __init__(self, cfg, P, B, X, Y, bf16=False, training=True, noise=None, mha_keep=None):
+    def __init__(self, cfg, P, B, X, Y, bf16=False, training=True, noise=None, mha_keep=None, counters=False):
         self.L = capi.lib()
         self.cfg, self.bf16, self.training = cfg, bf16, training
         dev = torch.device("cuda:0")
@@ -36,6 +36,8 @@ class MoeRun:
         self.params = {k: v.detach().to(dev, torch.float32).contiguous() for k, v in P.items()}
         self.buffers = {k: v.detach().to(dev, torch.float32).contiguous() for k, v in B.items()
                         if v.is_floating_point()}
+        # counters: the int64 num_batches_tracked of every BatchNorm too (a training forward bumps them; off by default, as before)
+        self.nbt = {k: v.detach().to(dev).contiguous() for k, v in B.items() if counters and not v.is_floating_point()}
         self.X = X.to(dev, tdt).contiguous()
         self.Y = Y.to(dev, tdt).contiguous()
         self.noise = noise.to(dev, torch.float32).contiguous() if noise is not None else None
@@ -61,7 +63,7 @@ class MoeRun:
         self.lb = torch.zeros(1, device=dev, dtype=torch.float32)
         # "v1" experts: dropout multipliers of the attention weights, {expert prefix: (N * heads, S, S)} (include/avmoe.h sa_keep)
         self.keep = {f"{pre}.{cm.SA_KEEP}": v.detach().to(dev, torch.float32).contiguous() for pre, v in (mha_keep or {}).items()}
-        self.ptrs = cm.make_ptrs({**self.params, **self.buffers, **self.keep}, cfg.E_m, cfg.E_s)
+        self.ptrs = cm.make_ptrs({**self.params, **self.buffers, **self.nbt, **self.keep}, cfg.E_m, cfg.E_s)
 
     def forward(self):
         st = self.L.avmoe_moe_forward(C.byref(self.desc), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs),

@@ -46,7 +46,22 @@ bound already carries or an argument of the function:
                        bracketed, so the extra fold is inside colsum_ref's (NT + 2) EPS_ACC.  expert_scalar (tile_gen.inc:103-111) only
                        feeds blkscal, which no per-token output reads.
     rounds of experts  dL2x[:, KL] / rs2x add the experts round by round through dsxs (tile_gen.inc:822-831; tile_kernels.hip:929-930 expert by
-                       expert): still E terms in expert order, an fp32 partial in between (no extra rounding)."""
+                       expert): still E terms in expert order, an fp32 partial in between (no extra rounding).
+
+The switches.  ln_before, ln_post, use_gate, use_bn and training are run-time branches inside every form of every pass (F_LN_BEFORE ..
+F_USE_GATE in tile_fast.hip; a.ln_before, a.use_bn, a.bn_train, a.ln_post, a.use_gate, a.moments in the other three files); every function
+whose map they change takes them as keyword arguments that default to the training-mode site with everything on:
+    ln_before=False    rmu_ref / rmu_off_ref (exactly (1, 0), stored by all four forms), z_map_ref (two operations), pre_small_bwd_ref (Zw = dz,
+                       dSx = dSxx = dL2x[:, KL] = rs2x = 0 exactly)
+    ln_post=False      post_small_ref (rp = 1, mup = 0, Apost = rnd_T(q z')), scalar_cols_ref ([q, -0, q]; neg_zero), post_mid_bwd_ref (no dSoo)
+    bn / mode          bn1_ref mode "eval" / "off", pre_small_bwd_ref bn "eval" (dz = scale dy) / "off" (dz = dy); post_mid_bwd_ref
+                       moments=False (use_bn && training is false: mid_bwd adds literal zeros).  zprime and dsm34_ref read bn1 AS STORED and
+                       need no switch: their counts of two and three roundings cover the exact products with scale = 1, shift = 0.
+    use_gate           no argument: every launcher passes use_gate && !gate_w and the plan folds the gate into Bpost (Dims::gate_w,
+                       moe_plan.cpp:35), so qv = probs whether the gate is on or off -- the callers pass probs and the third scalar column of
+                       Apost, q itself, shows which arm ran.  The kernels' token-space arm (q = probs * gate) runs only under the
+                       development switch that clears gate_w (sw.gate_token): no test reaches it, it stays unexercised.
+In a branch where the kernel's value is exact the bound is 0 and check_bound demands equality."""
 import torch
 
 from tests.stream_product_ref import EPS_ACC, EPS_BF16, EPS_PLANES, ProductMismatch, check_bound
@@ -94,12 +109,22 @@ def _first_order(r, evar, what):
     assert worst <= 0.125, f"{what}: r^2 * bound(var) = {worst:.3g} > 1/8 at token {int((r * r * evar).reshape(r.shape[0], -1).max(1).values.argmax())}"
 
 
-def post_small_ref(Z, bn1, Gq, us, vh, H1p, H2p, qv, relu, C, ln_eps, *, planes, out_bf16):
+def post_small_ref(Z, bn1, Gq, us, vh, H1p, H2p, qv, relu, C, ln_eps, *, planes, out_bf16, ln_post=True):
     """tile_fast.hip:274-311 (tile_gen.inc:300-361, tile_kernels.hip:457-516).  Z (NT, g, E, GD); Gq (g, E, GD, GD); us, vh (g, E, GD);
-    H1p, H2p (g, E): the per-group parts the kernel adds (:256; tile_gen.inc:301); qv (NT, E) = probs * gate.
+    H1p, H2p (g, E): the per-group parts the kernel adds (:256; tile_gen.inc:301); qv (NT, E) = probs * gate -- probs alone when the
+    site has no gate, and also when the plan folded the gate into Bpost (Dims::gate_w, moe_plan.cpp:35: every launcher passes
+    use_gate && !gate_w, tile_fast.hip:1132, tile_stream.hip:1419, tile_gen.inc:1147, tile_kernels.hip:526).
+    ln_post=False: every form initialises rp = 1, mup = 0 and skips the statistics (tile_fast.hip:282-283, tile_stream.hip:679-680,
+    tile_gen.inc:327, tile_kernels.hip:472-473), stores that pair, and forms Apost = rnd_T((qv * 1) * z'): the product with 1 is exact,
+    ONE fp32 rounding is left.
     -> {"rp", "mup": (NT, E); "Apost": (NT, g, E, GD)}, each (ref, bound)"""
     zp, ezp, _y, _ym, _k = zprime(Z, bn1, relu)
     us, vh, qv = us.double(), vh.double(), qv.double()
+    if not ln_post:
+        one, zero = torch.ones_like(qv), torch.zeros_like(qv)
+        A = qv[:, None, :, None] * zp
+        pre = qv.abs()[:, None, :, None] * ezp + U32 * A.abs()
+        return {"rp": (one, zero), "mup": (zero, zero.clone()), "Apost": (A, _store(A, pre, out_bf16))}
     w, wmag, ew = matvec(zp, ezp, Gq, planes)                                  # :288
     H1, H2 = H1p.double().sum(0), H2p.double().sum(0)
     H1m, H2m = H1p.double().abs().sum(0), H2p.double().abs().sum(0)
@@ -127,30 +152,73 @@ def post_small_ref(Z, bn1, Gq, us, vh, H1p, H2p, qv, relu, C, ln_eps, *, planes,
     return {"rp": (rp, erp), "mup": (mup, emup), "Apost": (A, _store(A, pre, out_bf16))}
 
 
-def scalar_cols_ref(qv, rp, mup, *, out_bf16):
-    """[q rp, -q rp mup, q] from rp / mup AS STORED (tile_fast.hip:321-339, tile_stream.hip:723-738): two fp32 products and a store.
+def scalar_cols_ref(qv, rp, mup, *, out_bf16, ln_post=True):
+    """[q rp, -q rp mup, q] from rp / mup AS STORED (tile_fast.hip:321-339, tile_stream.hip:723-738, tile_gen.inc:358,
+    tile_kernels.hip:509): two fp32 products and a store.
+    ln_post=False: the stored pair is (1, 0), so the columns are [q * 1, (-q * 1) * 0, q] = [q, -0, q]: both products exact (arithmetic
+    bound 0), the middle column a NEGATIVE zero in either type (q >= 0: a probability; -q * 1 = -q, and (-q) * (+0) = -0 also when
+    q = 0) -- neg_zero() asserts that bit pattern, which a comparison of values cannot see.
     -> (ref, bound), (NT, E, 3)"""
     qv, rp, mup = qv.double(), rp.double(), mup.double()
     ref = torch.stack([qv * rp, -qv * rp * mup, qv], -1)
+    if not ln_post:
+        return ref, _store(ref, torch.zeros_like(ref), out_bf16)
     pre = torch.stack([U32 * (qv * rp).abs(), 2 * U32 * (qv * rp * mup).abs(), torch.zeros_like(qv)], -1)
     return ref, _store(ref, pre, out_bf16)
 
 
-def post_mid_bwd_ref(dAp, dApx, Z, bn1, Gq, us, vh, qv, rp, mup, dm, sdSzz, relu, C, *, planes, out_bf16):
+def neg_zero(x, name):
+    """every element of x is -0 (sign bit set, magnitude 0): the middle scalar column of Apost without LayerNorm-post"""
+    bad = ~((x == 0) & torch.signbit(x))
+    if bool(bad.any()):
+        i = tuple(int(k) for k in bad.nonzero()[0])
+        raise ProductMismatch(f"{name}: {int(bad.sum())} of {x.numel()} elements are not -0, first {float(x[i])!r} at {i}")
+
+
+def post_mid_bwd_ref(dAp, dApx, Z, bn1, Gq, us, vh, qv, rp, mup, dm, sdSzz, relu, C, *, planes, out_bf16, ln_post=True, moments=True):
     """post_small_bwd (tile_fast.hip:434-506) followed by mid_bwd (:133-161) as ONE map to the final dzp; the first pass's store of dz' is one
     named rounding of the intermediate.  dAp (NT, g, E, GD); dApx (NT, g, E, 3); rp, mup (NT, E) as stored; dm = dsm[2] (g, E, GD).
     The generalised kernels spell the same expressions (tile_gen.inc:451-458, :483-485, :254-255), the any-shape ones too
     (tile_kernels.hip:663-670, :686-688, :781-782) but keep dz' in fp32 whatever the site's type (out_bf16=False there).
+    ln_post=False: dSo = dSoo = 0 exactly, no Gq mat-vec, dz' = (qv rp) dAp with rp = 1 as stored -- the product qv * 1 is exact, ONE
+    rounding (tile_fast.hip:459-485, tile_stream.hip:312-326, tile_gen.inc:452-484, tile_kernels.hip:664-687).
+    moments=False (a.moments = use_bn && training, tile_fast.hip:1169: eval mode or no BatchNorm): mid_bwd reads neither sdSzz nor
+    dsm[2] and adds two literal zeros, d = dz' + 0.f + 0.f (tile_fast.hip:102, :146, :153; tile_stream.hip:473, :543; tile_gen.inc:216-218,
+    :247; tile_kernels.hip:743, :770): exact, so the only roundings behind the first store are that store read back and the final one.
+    dm / sdSzz are then not read here either (pass None: the buffers hold whatever the workspace held).
     -> {"dSoo": (ref, bound) (NT, E); "dzp": (unmasked ref, bound, mask, kink) (NT, g, E, GD)}"""
     zp, ezp, y, _ym, kink = zprime(Z, bn1, relu)
-    d, us, vh, qv, rp, mup, dm = dAp.double(), us.double(), vh.double(), qv.double(), rp.double(), mup.double(), dm.double()
-    g = Z.shape[1]
+    r = relu.to(zp.device).view(1, 1, -1, 1)
+    mask = ~r | (y > 0)                                                      # :154: relu && z' <= 0 -> 0
+    d, us, vh, qv, rp, mup = dAp.double(), us.double(), vh.double(), qv.double(), rp.double(), mup.double()
+    if ln_post:
+        dz1, dz1m, e1, dSoo, edSoo, ew = _post_bwd_ln(d, dApx, zp, ezp, Gq, us, vh, qv, rp, mup, C, Z.shape[1], Z.shape[3], planes)
+    else:
+        k1 = (qv * rp)[:, None, :, None]                                     # :472 (rp is 1: exact), :483
+        dz1 = k1 * d
+        dz1m, e1 = dz1.abs(), U32 * dz1.abs()
+        dSoo = torch.zeros_like(qv)
+        edSoo = torch.zeros_like(qv)
+    e1 = _store(dz1, e1, out_bf16)                                           # :496 st_row<T>: the intermediate dz' as mid_bwd reads it back
+    if moments:
+        dm = dm.double()
+        w2, w2mag, ew2 = matvec(zp, ezp, sdSzz, planes)                      # :146
+        d2 = dz1 + dm + w2                                                   # :153: two adds
+        pre = e1 + ew2 + 2 * U32 * (dz1m + dm.abs() + w2mag)
+    else:                                                                    # :153 with dm = 0.f and w = 0.f: exact, and :154 rounds a value
+        return {"dSoo": (dSoo, edSoo), "dzp": (dz1, e1, mask, kink)}         # that the first store already rounded to T: exact too
+    return {"dSoo": (dSoo, edSoo), "dzp": (d2, _store(d2, pre, out_bf16), mask, kink)}     # :154 rndT<T>
+
+
+def _post_bwd_ln(d, dApx, zp, ezp, Gq, us, vh, qv, rp, mup, C, g, GD, planes):
+    """the LayerNorm-post arm of post_small_bwd (tile_fast.hip:449-485) -> dz' before its store, its magnitude and arithmetic bound,
+    dSoo with its bound"""
     da = dApx.double().sum(1)                                                # :423 / :449: group 0 + group 1, one rounding (tile_gen.inc:444: g - 1 of them)
     dam = dApx.double().abs().sum(1)
     eda = (g - 1) * U32 * dam
     zz = (d * zp).sum((1, 3))                                                # :457-458
     zzm = (d.abs() * zp.abs()).sum((1, 3))
-    ezz = (d.abs() * ezp).sum((1, 3)) + (_nsum(g, Z.shape[3]) + 2) * EPS_ACC * zzm
+    ezz = (d.abs() * ezp).sum((1, 3)) + (_nsum(g, GD) + 2) * EPS_ACC * zzm
     drp = qv * (zz + da[..., 0] - mup * da[..., 1])                          # :463: four products, two sums
     drpm = qv.abs() * (zzm + dam[..., 0] + mup.abs() * dam[..., 1])
     edrp = qv.abs() * (ezz + eda[..., 0] + mup.abs() * eda[..., 1]) + 6 * U32 * drpm
@@ -174,28 +242,41 @@ def post_mid_bwd_ref(dAp, dApx, Z, bn1, Gq, us, vh, qv, rp, mup, dm, sdSzz, relu
     dz1 = k1 * d + x(dSo) * us + x(dSoo) * tt                                # :483-485: k1, k1 d, dSo us, the sum in brackets, dSoo (..), two adds
     dz1m = (k1 * d).abs() + x(dSom) * us.abs() + x(dSoom) * ttm
     e1 = x(edSo) * us.abs() + x(edSoo) * ttm + x(dSoom) * 2 * ew + 7 * U32 * dz1m
-    e1 = _store(dz1, e1, out_bf16)                                               # :496 st_row<T>: the intermediate dz' as mid_bwd reads it back
-    w2, w2mag, ew2 = matvec(zp, ezp, sdSzz, planes)                          # :146
-    d2 = dz1 + dm + w2                                                       # :153: two adds
-    pre = e1 + ew2 + 2 * U32 * (dz1m + dm.abs() + w2mag)
-    r = relu.to(d2.device).view(1, 1, -1, 1)
-    mask = ~r | (y > 0)                                                      # :154: relu && z' <= 0 -> 0
-    return {"dSoo": (dSoo, edSoo), "dzp": (d2, _store(d2, pre, out_bf16), mask, kink)}     # :154 rndT<T>
+    return dz1, dz1m, e1, dSoo, edSoo, ew
 
 
-def pre_small_bwd_ref(dy, Z, bn1, mdy, mdyz, rr, mu, wsum, dconst, C, *, out_bf16):
+def pre_small_bwd_ref(dy, Z, bn1, mdy, mdyz, rr, mu, wsum, dconst, C, *, out_bf16, bn="train", ln_before=True):
     """tile_fast.hip:753-838, tile_gen.inc:740-831, tile_kernels.hip:876-931, :1012-1020 (training-mode BatchNorm-1, folded LayerNorm).
     dy: the final dzp as stored (NT, g, E, GD); mdy, mdyz = dsm[3], dsm[4] (g, E, GD); rr, mu (NT, E) as stored; `zraw - mu wsum` is (z - dconst) / rr from the STORED z, as in the kernel (:770).
+    bn: "train" as above; "eval" (use_bn && !training): dz = scale * dy, ONE rounding, dsm[3, 4] not read (tile_fast.hip:711, :767;
+    tile_stream.hip:1073, :1168; tile_gen.inc:725, :765; tile_kernels.hip:866, :898); "off" (!use_bn): dz = dy exactly (:765).
+    mdy / mdyz may be None unless bn == "train".
+    ln_before=False: the kernels take rr = 1, mu = 0 WITHOUT reading rmu (tile_fast.hip:727-733, tile_stream.hip:1150, tile_gen.inc:740-741,
+    tile_kernels.hip:878-879), Zw = rnd_T(dz) (:774 / :905: no product), and dSx = dSxx = 0 (:798-806), so the sum over the experts
+    dL2x[:, KL] is 0 and rs2x = 2 * 0 = 0, all exact (bound 0).
     -> {"Zw": (NT, g, E, GD), "dzr": the same before its store (what the fused streamed pass hands to its hop-2 block); "dSx", "dSxx": (NT, E) (dslat holds the cross-modal experts' pair); "dL2x_KL", "rs2x": (NT,)}"""
     dy, z = dy.double(), Z.double()
     mean, rstd, sc = bn1[0].double(), bn1[1].double(), bn1[2].double()
-    mdy, mdyz, ws, dc = mdy.double(), mdyz.double(), wsum.double(), dconst.double()
+    ws, dc = wsum.double(), dconst.double()
     rr_, mu_ = rr.double(), mu.double()
     rr, mu = rr_[:, None, :, None], mu_[:, None, :, None]
-    zh3 = (z - mean) * rstd * mdyz                                           # :766: -, *, *, then -, -, * : six roundings
-    dz = sc * (dy - mdy - zh3)
-    dzm = sc.abs() * (dy.abs() + mdy.abs() + zh3.abs())
-    edz = 6 * U32 * dzm
+    if bn == "train":
+        mdy, mdyz = mdy.double(), mdyz.double()
+        zh3 = (z - mean) * rstd * mdyz                                       # :766: -, *, *, then -, -, * : six roundings
+        dz = sc * (dy - mdy - zh3)
+        dzm = sc.abs() * (dy.abs() + mdy.abs() + zh3.abs())
+        edz = 6 * U32 * dzm
+    elif bn == "eval":
+        dz = sc * dy                                                         # :767
+        dzm = dz.abs()
+        edz = U32 * dzm
+    else:
+        assert bn == "off", bn
+        dz, dzm, edz = dy, dy.abs(), torch.zeros_like(dy)                    # :764
+    if not ln_before:
+        zt, zn = torch.zeros_like(rr_), torch.zeros(dy.shape[0], dtype=torch.float64, device=dy.device)
+        return {"Zw": (dz, _store(dz, edz, out_bf16)), "dzr": (dz, edz), "dSx": (zt, zt.clone()), "dSxx": (zt.clone(), zt.clone()),
+                "dL2x_KL": (zn, zn.clone()), "rs2x": (zn.clone(), zn.clone())}
     zc = (z - dc) / rr                                                       # :747, :770: 1 / rr, the difference, the product
     ezc = 3 * U32 * zc.abs()
     k = _nsum(Z.shape[1], Z.shape[3]) + 2
@@ -227,6 +308,18 @@ def pre_small_bwd_ref(dy, Z, bn1, mdy, mdyz, rr, mu, wsum, dconst, C, *, out_bf1
     return {"Zw": Zw, "dzr": (v, ev), "dSx": (dSx, edSx), "dSxx": (dSxx, edSxx), "dL2x_KL": (ax, _store(ax, eax, out_bf16)), "rs2x": (axx, eaxx)}
 
 
+def state_unchanged(now, uploaded, name):
+    """a BatchNorm buffer (running mean, running variance, num_batches_tracked) after a forward that does not train BatchNorm -- eval mode,
+    or no BatchNorm at all (bn1_finalize_col writes rm / rv / nbt only under use_bn && training, fwd_kernels.hip:1054-1067) -- is
+    bit-identical to what was uploaded"""
+    now, uploaded = now.detach().cpu(), uploaded.detach().cpu().to(now.dtype)
+    if now.shape != uploaded.shape:
+        raise ProductMismatch(f"{name}: shape {tuple(now.shape)} against {tuple(uploaded.shape)} uploaded")
+    same = now.reshape(-1).contiguous().view(torch.uint8) == uploaded.reshape(-1).contiguous().view(torch.uint8)
+    if not bool(same.all()):
+        raise ProductMismatch(f"{name}: changed by a forward that does not train BatchNorm ({int((~same).sum())} bytes differ)")
+
+
 def check_masked(got, ref, bound, mask, kink, name):
     """got == mask * ref within bound, where an element at the ReLU kink (zprime's `kink`) may sit on either branch: exactly 0, or the
     unmasked value within its bound.  The one exclusion there is; capped at KINK_CAP of the tensor, count printed.  -> worst err / bound"""
@@ -251,10 +344,31 @@ def colsum_ref(x, scale, *, extra_terms=0):
     return x.sum(0) * scale, (nt + 2 + extra_terms) * EPS_ACC * x.abs().sum(0) * abs(scale)
 
 
-def bn1_ref(Z, w, b, bn_eps):
+def bn1_ref(Z, w, b, bn_eps, *, mode="train", rm=None, rv=None):
     """BatchNorm-1 (training mode) from the stored z: the two fp32 column sums over NT tokens (tile_fast.hip:654 per-lane accumulators ->
     colsum_fin.h block partials), then fwd_kernels.hip:988-1004 in double up to the casts: mean = fl32(s0 / NT), var = fl32(s1 / NT - m^2),
-    rstd = rsqrtf(var + eps), scale = w * rstd, shift = b - mean * scale.  Z (NT, g, E, 32); w, b (g, E, 32).  -> (ref, bound), (4, g, E, 32)"""
+    rstd = rsqrtf(var + eps), scale = w * rstd, shift = b - mean * scale.  Z (NT, g, E, 32); w, b (g, E, 32).  -> (ref, bound), (4, g, E, 32)
+    mode="eval" (bn1_finalize_col, fwd_kernels.hip:1068-1071: use_bn && !training): mean = running_mean and var = running_var AS
+    UPLOADED (rm, rv (g, E, 32): exact), then the same fp32 tail: the sum var + eps (one rounding), rsqrtf (EPS_RSQRT), scale = w * rstd
+    (one), shift = b - mean * scale (two).  Z is not read.
+    mode="off" (:1051, !use_bn): exactly (0, 1, 1, 0), bound 0.
+    The padding entries dg..dgp of all four rows are 0 in every mode (:1043, :1049, :1074); the callers pass the real entries and assert
+    the padding by itself."""
+    if mode == "off":
+        one, zero = torch.ones_like(w, dtype=torch.float64), torch.zeros_like(w, dtype=torch.float64)
+        return torch.stack([zero, one, one, zero]), torch.zeros(4, *w.shape, dtype=torch.float64, device=w.device)
+    if mode == "eval":
+        w, b, mean, var = w.double(), b.double(), rm.double(), rv.double()
+        rstd = torch.rsqrt(var + bn_eps)
+        evar = U32 * (var + bn_eps)
+        _first_order(rstd[None], evar[None], "bn1 rstd (eval)")
+        erstd = 0.5 * rstd ** 3 * evar + EPS_RSQRT * rstd
+        sc = w * rstd
+        esc = w.abs() * erstd + U32 * sc.abs()
+        sh = b - mean * sc
+        esh = mean.abs() * esc + 2 * U32 * (b.abs() + (mean * sc).abs())
+        return torch.stack([mean, rstd, sc, sh]), torch.stack([torch.zeros_like(mean), erstd, esc, esh])
+    assert mode == "train", mode
     z, w, b = Z.double(), w.double(), b.double()
     nt = z.shape[0]
     k = (nt + 2) * EPS_ACC                                                   # NT terms (each z * z product rounded once) + the partials' folds
@@ -309,14 +423,24 @@ def softmax_ref(L2, *, out_bf16, K=None):
     return a, bound
 
 
-def rmu_ref(sx, L2, a, TT, Tsum, gv, C, ln_eps, *, planes):
+def rmu_off_ref(NT, E, device):
+    """rmu without LayerNorm-before: every form initialises mu = 0, rr = 1 (tile_fast.hip:634, tile_stream.hip:952, tile_gen.inc:638,
+    tile_kernels.hip:341), skips the statistics and STORES the pair unconditionally (tile_fast.hip:667, tile_stream.hip:977,
+    tile_gen.inc:670, tile_kernels.hip:373): exactly (1, 0) in all four forms, bound 0.  -> {"rr", "mu": (ref, bound)}"""
+    one, zero = torch.ones(NT, E, dtype=torch.float64, device=device), torch.zeros(NT, E, dtype=torch.float64, device=device)
+    return {"rr": (one, zero), "mu": (zero.clone(), zero.clone())}
+
+
+def rmu_ref(sx, L2, a, TT, Tsum, gv, C, ln_eps, *, planes, ln_before=True):
     """rmu = (rr, mu) of every expert (tile_fast.hip:572-637) from the stored row sums of X, the logits and a AS STORED (the kernel forms
     u1, u2, u3 from the rounded a, :612-614).  sx (2, NT); L2, a (NT, El, Kp); TT (NT, El, K, K) -- the token's frame's -- or per frame
     (S, El, K, K), K <= Kp the real latent tokens of a slot; Tsum (NT, El, Kp); gv (E,): the latent gate (gate_av / gate_self) of the experts
     that own a latent slot, 0 for the others (the first El experts own the slots).  The generalised kernels index TT with the true K and
     everything else with Kp (tile_gen.inc:527-535 stage_latent; tile_kernels.hip:269-278); slots K..Kp enter no sum (u2 is masked,
     tile_gen.inc:617; tb and TT are staged as 0 there and a is exactly 0: softmax_ref), so the sums here run over the K real slots while
-    the term counts stay those of the Kp-wide loops.  -> {"rr", "mu": (ref, bound)}, each (NT, E)"""
+    the term counts stay those of the Kp-wide loops.  ln_before=False: rmu_off_ref.  -> {"rr", "mu": (ref, bound)}, each (NT, E)"""
+    if not ln_before:
+        return rmu_off_ref(a.shape[0], gv.shape[0], a.device)
     s0, s1, lg, a, TT, gv = sx[0].double(), sx[1].double(), L2.double(), a.double(), TT.double(), gv.double().to(sx.device)
     NT, El, Kp, K = a.shape[0], a.shape[1], a.shape[2], TT.shape[-1]
     E = gv.shape[0]
@@ -469,11 +593,16 @@ def dgq_engine_ref(Z, bn1, relu, Zp, dSoo, edSoo, *, out_bf16, prod_eps=0.0):
     return G, torch.einsum("tgej,tgel->gejl", ezw, Zp.abs()) + ((nt + 2) * EPS_ACC + prod_eps) * mag
 
 
-def z_map_ref(Zx, eZx, pw, epw, rr, mu, wsum, dconst, *, out_bf16):
+def z_map_ref(Zx, eZx, pw, epw, rr, mu, wsum, dconst, *, out_bf16, ln_before=True):
     """z = rnd_T(rr (Zx + gv pw - mu wsum) + dconst) (tile_fast.hip:651-652, tile_stream.hip:962-963) with rr, mu AS STORED (NT, E).  Z holds Zx
     only until the pass overwrites it in place, so Zx (NT, g, E, 32) is the down projection recomputed with its own bound eZx, and pw the
     latent term gv * (a . TW) with its bound (zero for the unimodal experts).  Six fp32 operations, each rounding a value no larger than
-    |rr| (|Zx| + |pw| + |mu wsum|) + |dconst|.  -> (ref, bound)"""
+    |rr| (|Zx| + |pw| + |mu wsum|) + |dconst|.
+    ln_before=False: z = rnd_T(Zx + gv pw) (the `: zr` arm of tile_fast.hip:652, tile_stream.hip:963, tile_gen.inc:662, tile_kernels.hip:361):
+    the product with gv and the sum, TWO fp32 operations, no wsum / dconst term; rr, mu, wsum, dconst are not read.  -> (ref, bound)"""
+    if not ln_before:
+        z = Zx + pw
+        return z, _store(z, eZx + epw + 2 * U32 * (Zx.abs() + pw.abs()), out_bf16)
     rr, mu = rr.double()[:, None, :, None], mu.double()[:, None, :, None]
     ws, dc = wsum.double(), dconst.double()
     z = rr * (Zx + pw - mu * ws) + dc

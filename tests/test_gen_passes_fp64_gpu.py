@@ -44,8 +44,10 @@ many_blocks (16.5 M elements of dzp: 165).  The seeds were chosen on the CPU (te
 oracle's own fp32 z has no ReLU pre-activation within 16 x the kink window at any case but many_blocks, whose 9.4 M pre-activations put
 several into that window at any seed; its seed, the best of 880, keeps the nearest one 6.7 windows away.
 
-NOT covered here: the XR instantiations (N x N and frame-attention experts: sxr, ZR, dZR, dsr); sites with ln_before, ln_post, use_gate or
-use_bn off, and eval mode; the streaming products around the passes (tests/test_stream_products_gpu.py).
+NOT covered here: the XR instantiations (N x N and frame-attention experts: sxr, ZR, dZR, dsr); the streaming products around the passes
+(tests/test_stream_products_gpu.py).  Every site here runs in training mode with BatchNorm, both LayerNorms and the gate on: the run-time
+branches for ln_before, ln_post, use_gate or use_bn off and for eval mode are held per token by tests/test_pass_variants_fp64_gpu.py (at
+g2c3_k32_e6, merged_k2 and kt_three_groups_50 of this module's cases).
 """
 import time
 

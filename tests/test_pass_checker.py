@@ -69,10 +69,13 @@ def _zp(o):
     return torch.where(RELU.view(1, 1, E, 1), y.clamp_min(0.0), y), y
 
 
-def emu_post_small(o, planes, out_bf16, seed, qv=None, vh_factor=2.0):
+def emu_post_small(o, planes, out_bf16, seed, qv=None, vh_factor=2.0, ln_post=True):
     st = _bf if out_bf16 else (lambda x: x)
     qv = o["qv"] if qv is None else qv
     zp, _ = _zp(o)
+    if not ln_post:                                      # rp = 1, mup = 0, no statistics
+        rp, mup = torch.ones_like(qv), torch.zeros_like(qv)
+        return dict(rp=rp, mup=mup, Apost=st((qv * rp)[:, None, :, None] * zp))
     w = _mv(zp, o["Gq"], planes, seed)
     So = _ssum(_tok(zp * o["us"]), seed + 1) + (o["H1p"][0] + o["H1p"][1])
     Soo = _ssum(_tok(zp * (w + vh_factor * o["vh"])), seed + 2) + (o["H2p"][0] + o["H2p"][1])
@@ -86,31 +89,44 @@ def emu_scalar_cols(qv, rp, mup, out_bf16):
     return st(torch.stack([qv * rp, -qv * rp * mup, qv], -1))
 
 
-def emu_post_mid_bwd(o, rp, mup, planes, out_bf16, seed, qv=None, with_dm=True):
+def emu_post_mid_bwd(o, rp, mup, planes, out_bf16, seed, qv=None, with_dm=True, ln_post=True, moments=True):
     st = _bf if out_bf16 else (lambda x: x)
     qv = o["qv"] if qv is None else qv
     zp, y = _zp(o)
-    da = o["dApx"][:, 0] + o["dApx"][:, 1]
-    zz = _ssum(_tok(o["dAp"] * zp), seed)
-    drp = qv * zz + qv * da[..., 0] - qv * mup * da[..., 1]
-    dmup = -qv * rp * da[..., 1]
-    dvarp = drp * (-0.5) * rp * rp * rp
-    dSoo = dvarp / C
-    dmup = dmup - 2.0 * mup * dvarp
-    dSo = dmup / C
-    w = _mv(zp, o["Gq"], planes, seed + 1)
     x = lambda v: v[:, None, :, None]
-    dz1 = st(x(qv * rp) * o["dAp"] + x(dSo) * o["us"] + x(dSoo) * (2.0 * w + 2.0 * o["vh"]))
-    w2 = _mv(zp, o["sdSzz"], planes, seed + 2)
-    d2 = dz1 + o["dm"] + w2 if with_dm else dz1 + w2
+    if ln_post:
+        da = o["dApx"][:, 0] + o["dApx"][:, 1]
+        zz = _ssum(_tok(o["dAp"] * zp), seed)
+        drp = qv * zz + qv * da[..., 0] - qv * mup * da[..., 1]
+        dmup = -qv * rp * da[..., 1]
+        dvarp = drp * (-0.5) * rp * rp * rp
+        dSoo = dvarp / C
+        dmup = dmup - 2.0 * mup * dvarp
+        dSo = dmup / C
+        w = _mv(zp, o["Gq"], planes, seed + 1)
+        dz1 = st(x(qv * rp) * o["dAp"] + x(dSo) * o["us"] + x(dSoo) * (2.0 * w + 2.0 * o["vh"]))
+    else:
+        dSoo = torch.zeros_like(qv)
+        dz1 = st(x(qv * rp) * o["dAp"])
+    if moments:
+        w2 = _mv(zp, o["sdSzz"], planes, seed + 2)
+        d2 = dz1 + o["dm"] + w2 if with_dm else dz1 + w2
+    else:
+        d2 = dz1 + 0.0 + 0.0                             # dm = 0.f, w = 0.f
     return dict(dSoo=dSoo, dzp=torch.where(RELU.view(1, 1, E, 1) & (zp <= 0), torch.zeros_like(d2), st(d2)))
 
 
-def emu_pre_small_bwd(o, dy, out_bf16, seed, experts=range(E)):
+def emu_pre_small_bwd(o, dy, out_bf16, seed, experts=range(E), bn="train", ln_before=True):
     st = _bf if out_bf16 else (lambda x: x)
     mean, rstd, sc = o["bn1"][0], o["bn1"][1], o["bn1"][2]
     rr, mu = o["rr"][:, None, :, None], o["mu"][:, None, :, None]
-    dz = sc * (dy - o["mdy"] - (o["Z"] - mean) * rstd * o["mdyz"])
+    if bn == "train":
+        dz = sc * (dy - o["mdy"] - (o["Z"] - mean) * rstd * o["mdyz"])
+    else:
+        dz = sc * dy if bn == "eval" else dy
+    if not ln_before:                                    # rr = 1, mu = 0 without reading rmu; no sums
+        zero = torch.zeros(NT)
+        return dict(Zw=st(dz), dSx=torch.zeros(NT, E), dSxx=torch.zeros(NT, E), dL2x_KL=st(zero), rs2x=2.0 * zero)
     zc = (o["Z"] - o["dconst"]) * (1.0 / rr)
     sdr, sdm = _ssum(_tok(dz * zc), seed), _ssum(_tok(dz * o["wsum"]), seed + 1)
     dmu = -o["rr"] * sdm
@@ -639,3 +655,245 @@ def test_engine_path_dgq_and_z_map():
     with pytest.raises(ProductMismatch) as e:
         check_bound(bad, *zref, "z")
     assert "= (21," in str(e.value)
+
+
+# ---- the switches: ln_before, ln_post, use_gate, use_bn off and eval mode ---------------------------------------------------------------------
+# Every switch is a run-time branch inside every form of every pass; tests/pass_ref.py carries one argument per branch and
+# tests/test_pass_variants_fp64_gpu.py holds the kernels to them.  Here: the honest emulation of each of that module's seven variants stays
+# inside the new bounds in two summation orders, each planted fault fails its tag, and the seeds keep the oracle clear of the ReLU kink.
+from tests.pass_variant_cases import SITES, VARIANTS, kink_clearance      # noqa: E402
+
+BN_EPS = 1e-5
+
+
+def _variant_flags(variant):
+    fields, training = VARIANTS[variant]
+    use_bn = fields.get("use_bn", True)
+    return dict(ln_before=fields.get("ln_before", True), ln_post=fields.get("ln_post", True), use_gate=fields.get("use_gate", True),
+                bn="off" if not use_bn else ("train" if training else "eval"), moments=use_bn and training)
+
+
+def _bn_params(seed=50):
+    """BatchNorm-1 weight, bias and running statistics as O.init_params(randomize=True) draws them: means in +-0.2, variances in [0.5, 1.5]"""
+    g = torch.Generator().manual_seed(seed)
+    return dict(w=1.0 + 0.1 * torch.randn(G, E, D, generator=g), b=0.3 * torch.randn(G, E, D, generator=g),
+                rm=0.4 * torch.rand(G, E, D, generator=g) - 0.2, rv=0.5 + torch.rand(G, E, D, generator=g))
+
+
+def emu_bn1(p, mode, eps=BN_EPS, mean=None, var=None, scale=None):
+    """bn1_finalize_col's eval and no-BatchNorm arms (fwd_kernels.hip:1051, :1068-1071) in fp32, one operation at a time; mean / var / scale:
+    a planted fault's replacement"""
+    if mode == "off":
+        z, o = torch.zeros(G, E, D), torch.ones(G, E, D)
+        return torch.stack([z, o, o if scale is None else scale, z])
+    mean = p["rm"] if mean is None else mean
+    var = p["rv"] if var is None else var
+    rstd = torch.rsqrt(var + torch.tensor(eps, dtype=F32))
+    sc = p["w"] * rstd
+    return torch.stack([mean, rstd, sc, p["b"] - mean * sc])
+
+
+def ref_bn1(p, mode, Z=None):
+    return R.bn1_ref(Z, p["w"], p["b"], BN_EPS, mode=mode, rm=p["rm"], rv=p["rv"])
+
+
+# The operands are the synthetic tuned-width ones of _operands(), not the GPU sites' own, and tests/gen_pass_emu.py is not taught the switches:
+# every arm a switch adds is element-wise or exact (a product with scale, a sum with gv * pw, a stored constant, a literal zero).  None
+# holds a sum whose term count depends on g, dgp or Kp, none runs a mat-vec, so no new bound has a width in it; the sums and mat-vecs of the
+# arms that stay on are the train-mode ones, which tests/test_gen_pass_checker.py already emulates at the generalised widths.
+def _variant_operands(variant, seed=0):
+    """the operands of _operands() with bn1 as the variant's BatchNorm mode leaves it"""
+    f = _variant_flags(variant)
+    o = _operands(seed)
+    if f["bn"] != "train":
+        o["bn1"] = emu_bn1(_bn_params(), f["bn"])
+    return o, f
+
+
+def _run_variant(o, f, planes, out_bf16, seed):
+    """forward, post_small_bwd + mid_bwd, pre_small_bwd of one variant -> {output: worst err / bound}"""
+    fwd = emu_post_small(o, planes, out_bf16, seed=seed, ln_post=f["ln_post"])
+    r = check_all(fwd, R.post_small_ref(o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["H1p"], o["H2p"], o["qv"], RELU, C, EPS, planes=planes, out_bf16=out_bf16,
+                                        ln_post=f["ln_post"]), "post_small")
+    r["cols"] = check_bound(emu_scalar_cols(o["qv"], fwd["rp"], fwd["mup"], out_bf16), *R.scalar_cols_ref(o["qv"], fwd["rp"], fwd["mup"], out_bf16=out_bf16, ln_post=f["ln_post"]),
+                            "Apost scalar columns")
+    bwd = emu_post_mid_bwd(o, fwd["rp"], fwd["mup"], planes, out_bf16, seed=seed + 10, ln_post=f["ln_post"], moments=f["moments"])
+    rb = R.post_mid_bwd_ref(o["dAp"], o["dApx"], o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["qv"], fwd["rp"], fwd["mup"], o["dm"] if f["moments"] else None,
+                            o["sdSzz"] if f["moments"] else None, RELU, C, planes=planes, out_bf16=out_bf16, ln_post=f["ln_post"], moments=f["moments"])
+    r.update({"b_" + k: v for k, v in check_all(bwd, rb, "post_small_bwd + mid_bwd").items()})
+    train = f["bn"] == "train"
+    pre = emu_pre_small_bwd(o, bwd["dzp"], out_bf16, seed=seed + 20, bn=f["bn"], ln_before=f["ln_before"])
+    rp_ = R.pre_small_bwd_ref(bwd["dzp"], o["Z"], o["bn1"], o["mdy"] if train else None, o["mdyz"] if train else None, o["rr"], o["mu"], o["wsum"], o["dconst"], C,
+                              out_bf16=out_bf16, bn=f["bn"], ln_before=f["ln_before"])
+    r.update({"p_" + k: v for k, v in check_all(pre, rp_, "pre_small_bwd").items()})
+    return r, fwd, bwd, pre
+
+
+@pytest.mark.parametrize("planes", [False, True])
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_honest_emulation_of_every_variant_stays_inside_its_bounds_in_two_orders(variant, planes):
+    """(an output that is ONE correctly rounded operation, or exact, reaches its bound or has none: the ratio is bounded by 1, not by a half)"""
+    o, f = _variant_operands(variant)
+    for out_bf16 in (False, True):
+        for seed in (1, 101):                            # two summation orders
+            r, fwd, _bwd, pre = _run_variant(o, f, planes, out_bf16, seed)
+            assert max(r.values()) <= 1.0, (variant, out_bf16, seed, r)
+            if not f["ln_post"]:
+                assert bool((fwd["rp"] == 1).all() and (fwd["mup"] == 0).all())
+                R.neg_zero(emu_scalar_cols(o["qv"], fwd["rp"], fwd["mup"], out_bf16)[..., 1], "Apost middle scalar column")
+            if not f["ln_before"]:
+                assert bool((pre["rs2x"] == 0).all() and (pre["dL2x_KL"] == 0).all() and (pre["dSx"] == 0).all())
+
+
+def test_bn1_eval_and_off_references():
+    p = _bn_params()
+    assert check_bound(emu_bn1(p, "eval"), *ref_bn1(p, "eval"), "bn1 (eval)") <= 1.0
+    ref, bound = ref_bn1(p, "off")
+    assert float(bound.max()) == 0.0 and check_bound(emu_bn1(p, "off"), ref, bound, "bn1 (off)") == 0.0
+    assert torch.equal(ref, torch.stack([torch.zeros(G, E, D), torch.ones(G, E, D), torch.ones(G, E, D), torch.zeros(G, E, D)]).double())
+    rr = R.rmu_off_ref(NT, E, "cpu")
+    assert bool((rr["rr"][0] == 1).all() and (rr["mu"][0] == 0).all() and (rr["rr"][1] == 0).all() and (rr["mu"][1] == 0).all())
+
+
+# ---- planted faults, one per branch -------------------------------------------------------------------------------------------------------------
+def test_eval_backward_that_keeps_the_batch_mean_terms_fails():
+    o, f = _variant_operands("eval")
+    _r, _fwd, bwd, _pre = _run_variant(o, f, True, True, 1)
+    bad = emu_pre_small_bwd(o, bwd["dzp"], True, seed=21, bn="train")                    # - mdy - zh * mdyz kept
+    ref = R.pre_small_bwd_ref(bwd["dzp"], o["Z"], o["bn1"], None, None, o["rr"], o["mu"], o["wsum"], o["dconst"], C, out_bf16=True, bn="eval")
+    with pytest.raises(ProductMismatch, match="P9 Zw"):
+        check_bound(bad["Zw"], *ref["Zw"], "P9 Zw")
+
+
+@pytest.mark.parametrize("fault", ["batch statistics", "no eps"])
+def test_eval_bn1_from_the_batch_statistics_or_without_eps_fails(fault):
+    p = _bn_params()
+    o = _operands()
+    if fault == "batch statistics":
+        z = o["Z"]
+        bad = emu_bn1(p, "eval", mean=z.mean(0), var=z.var(0, unbiased=False))
+    else:
+        bad = emu_bn1(p, "eval", eps=0.0)
+    with pytest.raises(ProductMismatch, match="P2 bn1"):
+        check_bound(bad, *ref_bn1(p, "eval"), "P2 bn1")
+
+
+def test_scale_w_without_batchnorm_fails():
+    p = _bn_params()
+    with pytest.raises(ProductMismatch, match="P2 bn1"):
+        check_bound(emu_bn1(p, "off", scale=p["w"]), *ref_bn1(p, "off"), "P2 bn1")
+
+
+def test_stale_rr_without_layernorm_before_fails():
+    o, f = _variant_operands("no_ln_before")
+    _r, _fwd, bwd, pre = _run_variant(o, f, True, True, 1)
+    ref = R.pre_small_bwd_ref(bwd["dzp"], o["Z"], o["bn1"], o["mdy"], o["mdyz"], o["rr"], o["mu"], o["wsum"], o["dconst"], C, out_bf16=True, ln_before=False)
+    assert check_bound(pre["Zw"], *ref["Zw"], "P9 Zw") <= 1.0
+    bad = _bf(o["rr"][:, None, :, None] * pre["Zw"])                                     # Zw = rr * dz with the rr some earlier site left in rmu
+    with pytest.raises(ProductMismatch, match="P9 Zw"):
+        check_bound(bad, *ref["Zw"], "P9 Zw")
+
+
+def test_nonzero_rs2x_without_layernorm_before_fails():
+    o, f = _variant_operands("bare")
+    _r, _fwd, bwd, pre = _run_variant(o, f, True, True, 1)
+    ref = R.pre_small_bwd_ref(bwd["dzp"], o["Z"], o["bn1"], None, None, o["rr"], o["mu"], o["wsum"], o["dconst"], C, out_bf16=True, bn="off", ln_before=False)
+    bad = pre["rs2x"].clone()
+    bad[33] = 1e-30
+    with pytest.raises(ProductMismatch, match=r"P9 rs2x.*= \(33,\)"):
+        check_bound(bad, *ref["rs2x"], "P9 rs2x")
+
+
+def test_rp_from_a_layernorm_that_is_off_fails():
+    o, f = _variant_operands("no_ln_post")
+    ref = R.post_small_ref(o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["H1p"], o["H2p"], o["qv"], RELU, C, EPS, planes=True, out_bf16=True, ln_post=False)
+    bad = emu_post_small(o, True, True, seed=1, ln_post=True)
+    for k in ("rp", "mup", "Apost"):
+        with pytest.raises(ProductMismatch, match=f"P4 {k}"):
+            check_bound(bad[k], *ref[k], f"P4 {k}")
+
+
+@pytest.mark.parametrize("variant", ["no_gate", "eval"])
+def test_gate_applied_in_token_space_fails(variant):
+    """no_gate: the gate applied with use_gate off.  eval (gate on): the plan folds the gate into Bpost (Dims::gate_w), so a kernel that
+    multiplies it in as well applies it twice.  Either way q must be probs as stored, and the third scalar column is q itself."""
+    o, f = _variant_operands(variant)
+    gate = torch.tensor([0.9, 1.1, 0.8, 1.2])
+    qbad = o["qv"] * gate
+    ref = R.post_small_ref(o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["H1p"], o["H2p"], o["qv"], RELU, C, EPS, planes=True, out_bf16=True, ln_post=f["ln_post"])
+    good = emu_post_small(o, True, True, seed=1, ln_post=f["ln_post"])
+    bad = emu_post_small(o, True, True, seed=1, qv=qbad, ln_post=f["ln_post"])
+    assert check_bound(good["Apost"], *ref["Apost"], "P4 Apost") <= 1.0
+    with pytest.raises(ProductMismatch, match="P4 Apost"):
+        check_bound(bad["Apost"], *ref["Apost"], "P4 Apost")
+    cols = R.scalar_cols_ref(o["qv"], good["rp"], good["mup"], out_bf16=True, ln_post=f["ln_post"])
+    with pytest.raises(ProductMismatch, match="scalar columns"):
+        check_bound(emu_scalar_cols(qbad, good["rp"], good["mup"], True), *cols, "P4 Apost scalar columns")
+    with pytest.raises(ProductMismatch, match="scalar columns"):                        # ... and the third column alone shows it
+        check_bound(emu_scalar_cols(qbad, good["rp"], good["mup"], True)[..., 2], cols[0][..., 2], cols[1][..., 2], "P4 Apost scalar columns [q]")
+
+
+def test_one_token_with_the_neighbouring_experts_running_mean_fails():
+    o, f = _variant_operands("eval")
+    p = _bn_params()
+    ref = R.post_small_ref(o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["H1p"], o["H2p"], o["qv"], RELU, C, EPS, planes=True, out_bf16=True)
+    good = emu_post_small(o, True, True, seed=1)
+    assert check_bound(good["Apost"], *ref["Apost"], "P4 Apost") <= 1.0
+    t, e = 47, 2
+    other = emu_bn1(p, "eval", mean=p["rm"].roll(1, 1))                                  # every expert with its neighbour's running mean
+    o2 = dict(o, bn1=o["bn1"].clone())
+    o2["bn1"][3, :, e] = other[3, :, e]
+    wrong = emu_post_small(o2, True, True, seed=1)
+    bad = good["Apost"].clone()
+    bad[t, :, e] = wrong["Apost"][t, :, e]
+    with pytest.raises(ProductMismatch) as x:
+        check_bound(bad, *ref["Apost"], "P4 Apost")
+    assert f"= ({t}," in str(x.value) and "P4 Apost" in str(x.value), str(x.value)
+
+
+@pytest.mark.parametrize("variant", ["no_ln_post", "bare"])
+def test_one_bf16_ulp_in_apost_fails(variant):
+    o, f = _variant_operands(variant)
+    ref, bound = R.post_small_ref(o["Z"], o["bn1"], o["Gq"], o["us"], o["vh"], o["H1p"], o["H2p"], o["qv"], RELU, C, EPS, planes=True, out_bf16=True, ln_post=False)["Apost"]
+    good = emu_post_small(o, True, True, seed=1, ln_post=False)["Apost"]
+    assert check_bound(good, ref, bound, "P4 Apost") <= 1.0
+    idx = (33, 1, 3, 5)                                  # (an expert without the ReLU)
+    assert float(good[idx]) != 0.0
+    bits = good.contiguous().view(torch.int32).clone()
+    away = (good[idx].double() >= ref[idx]) == (good[idx] > 0)                           # one ulp AWAY from the reference
+    bits[idx] += (1 << 16) if away else -(1 << 16)
+    with pytest.raises(ProductMismatch, match="1 of") as x:
+        check_bound(bits.view(F32), ref, bound, "P4 Apost")
+    assert "= (33, 1, 3, 5)" in str(x.value)
+
+
+def test_a_running_statistic_changed_by_an_eval_forward_fails():
+    p = _bn_params()
+    R.state_unchanged(p["rv"].clone(), p["rv"], "bn1.running_var")
+    R.state_unchanged(torch.tensor(7), torch.tensor(7), "bn1.num_batches_tracked")
+    bits = p["rv"].clone().view(torch.int32)
+    bits[1, 2, 3] += 1                                   # one fp32 ulp in one entry
+    with pytest.raises(ProductMismatch, match="running_var"):
+        R.state_unchanged(bits.view(F32), p["rv"], "bn1.running_var")
+    with pytest.raises(ProductMismatch, match="num_batches_tracked"):
+        R.state_unchanged(torch.tensor(8), torch.tensor(7), "bn1.num_batches_tracked")
+
+
+def test_negative_zero_is_told_from_positive_zero():
+    R.neg_zero(torch.full((4, 3), -0.0), "middle column")
+    R.neg_zero(torch.full((4, 3), -0.0).bfloat16().float(), "middle column")
+    with pytest.raises(ProductMismatch, match="middle column"):
+        R.neg_zero(torch.zeros(4, 3), "middle column")
+
+
+# ---- the seeds of the variant sites ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_the_seeds_keep_the_oracles_variants_clear_of_the_relu_kink(variant):
+    """the criterion of tests/test_gen_pass_checker.py at every site of tests/test_pass_variants_fp64_gpu.py, in the variant's BatchNorm mode: the
+    oracle's own fp32 pre-activation has nothing within 16 kink windows, so the reference alone satisfies KINK_CAP (0 elements at these sizes)"""
+    seen = {}
+    for site, (_form, what, _bf16, _hook) in SITES.items():
+        if what not in seen:
+            seen[what] = kink_clearance(site, variant, R.KINK)
+            print(f"{variant} {what}: nearest ReLU pre-activation at {seen[what]:.1f} kink windows")
+    assert min(seen.values()) > 16.0, seen

@@ -40,7 +40,11 @@ dsm[0..2] are written by k_post_prep_bwd (:140) before mid_bwd reads them, dsm[3
 (tile_fast.hip:711), and nothing later in section 1 rewrites any of them; dzp is last written by mid_bwd, Zw / dL2x / rs2x / dslat by
 pre_small_bwd (Zw held dSoo z' before, in the non-Gram path only: that operand of the engine's dGq is gone by then, Zp is not).  dApost
 arrives split (bf16 columns + fp32 dApx) or whole (one fp32 array, moe_backward.cpp:113); which one is read off the workspace: the poison
-survives in dApx exactly when the whole form ran."""
+survives in dApx exactly when the whole form ran.
+
+Every site here runs in training mode with BatchNorm, both LayerNorms and the gate on.  The run-time branches of the same kernels for
+ln_before, ln_post, use_gate or use_bn off and for eval mode are held per token by tests/test_pass_variants_fp64_gpu.py (at ragged_196,
+short_frame_20 and three_experts of this module's shapes).  NOT checked in either: the XR instantiations (N x N and frame-attention experts)."""
 import pytest
 import torch
 

@@ -67,19 +67,20 @@ def _cfg(N, M, E_m, E_s):
     return O.AdapterConfig(Cx=768, Nx=N, Cy=768, Ny=M, reduction=12, groups=2, K=32, E_m=E_m, E_s=E_s, variant="ave")
 
 
-class Site:
-    """One bf16 training-mode site on cuda:0 with its workspaces (tests/moe_gpu_util.py::MoeRun: NaN-poisoned, guard bands), the
-    backward in sections, and every named buffer as a device view."""
+def draw_inputs(cfg, S, seed, X=None, Y=None):
+    """X, Y and dOut of a site, drawn from the seed on the CPU (a given X or Y is kept and not drawn)"""
+    g = torch.Generator().manual_seed(seed + 100)
+    X = 0.3 * torch.randn(S, cfg.Nx, cfg.Cx, generator=g) if X is None else X
+    Y = 0.3 * torch.randn(S, cfg.Ny, cfg.Cy, generator=g) if Y is None else Y
+    return X, Y, torch.randn(S, cfg.Nx, cfg.Cx, generator=g)
 
-    def __init__(self, cfg, S, seed, X=None, Y=None):
-        from tests.moe_gpu_util import MoeRun
-        P, B = O.init_params(cfg, seed=seed)
-        g = torch.Generator().manual_seed(seed + 100)
-        X = 0.3 * torch.randn(S, cfg.Nx, cfg.Cx, generator=g) if X is None else X
-        Y = 0.3 * torch.randn(S, cfg.Ny, cfg.Cy, generator=g) if Y is None else Y
-        self.G = torch.randn(S, cfg.Nx, cfg.Cx, generator=g)
-        self.P, self.cfg, self.S = P, cfg, S
-        self.run = MoeRun(cfg, P, B, X, Y, bf16=True, training=True)
+
+class Site:
+    """One site on cuda:0 (bf16 and training mode unless told otherwise) with its workspaces (tests/moe_gpu_util.py::MoeRun: NaN-poisoned,
+    guard bands), the backward in sections, and every named buffer as a device view.  self.B: the BatchNorm buffers as uploaded."""
+
+    def __init__(self, cfg, S, seed, X=None, Y=None, training=True):
+        self.make_run(cfg, S, seed, X, Y, training=training)
         r = self.run
         self.E, self.g, self.Cg, self.N, self.M, self.Cc, self.Cy = cfg.E, cfg.groups, cfg.Cx // cfg.groups, cfg.Nx, cfg.Ny, cfg.Cx, cfg.Cy
         self.NT = S * self.N
@@ -96,6 +97,16 @@ class Site:
         self.XW = -(-(self.KPp - E * self.dgp) // 16) * 16
         self.Mk, self.Mb = -(-(self.M + 2) // 8) * 8, -(-(self.M + 1) // 8) * 8
         assert self.dgp == 32 and r.table["Text"][2] == S * self.KLT * self.Cc * 2 and r.table["Z"][2] == self.NT * E * g * self.dgp * 2       # (the tuned layout)
+
+    def make_run(self, cfg, S, seed, X=None, Y=None, training=True, bf16=True, counters=False):
+        """parameters, buffers and inputs from the seed, and the MoeRun: the part of a site that no layout enters (the subclasses for
+        other layouts and element types start here).  counters: upload num_batches_tracked too"""
+        from tests.moe_gpu_util import MoeRun
+        P, B = O.init_params(cfg, seed=seed)
+        X, Y, self.G = draw_inputs(cfg, S, seed, X, Y)
+        self.P, self.B, self.cfg, self.S, self.training, self.bf16 = P, B, cfg, S, training, bf16
+        self.T = torch.bfloat16 if bf16 else torch.float32
+        self.run = MoeRun(cfg, P, B, X, Y, bf16=bf16, training=training, counters=counters)
 
     def dev(self, name, dtype, shape):
         region, off, nbytes = self.run.table[name]
