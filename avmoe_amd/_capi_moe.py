@@ -245,6 +245,12 @@ def declare(L):
         L.avmoe_moe_forward_choice.restype, L.avmoe_moe_forward_choice.argtypes = C.c_int, head + [C.c_int32, C.c_int32] + [C.c_void_p] * 11
         L.avmoe_expert_choice.restype = C.c_int
         L.avmoe_expert_choice.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    # Sinkhorn-balanced top-k (found by symbol: the site forward with the selection balanced within the call, and the two kernels as a sub-op)
+    L.avmoe_site_sinkhorn = L.avmoe_site_reg and hasattr(L, "avmoe_moe_forward_sinkhorn") and hasattr(L, "avmoe_router_sinkhorn")
+    if L.avmoe_site_sinkhorn:
+        L.avmoe_moe_forward_sinkhorn.restype, L.avmoe_moe_forward_sinkhorn.argtypes = C.c_int, head + [C.c_int32] * 3 + [C.c_void_p] * 12
+        L.avmoe_router_sinkhorn.restype = C.c_int
+        L.avmoe_router_sinkhorn.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

@@ -137,6 +137,17 @@ def _ws_sizes(module, L, desc):
     return sizes
 
 
+def _mode_offset(module, L, desc):
+    """Byte offset of the `mode` words in the saved workspace of a call shape (the named-buffer table, walked once per shape and kept on the
+    module under _ws_sizes' key): where a Sinkhorn forward leaves its column scale."""
+    key = (desc.S, desc.N, desc.M, desc.dtype, desc.training, desc.shared_gpu, *capi._hooks)
+    cache = module.__dict__.setdefault("_mode_off", {})
+    off = cache.get(key)
+    if off is None:
+        off = cache[key] = next(o for n, _r, o, _b in cm.buffer_table(L, desc) if n == "mode")
+    return off
+
+
 def _ptr(t):
     return t.data_ptr() if t is not None else None
 
@@ -146,6 +157,11 @@ def _rate(name, v):
     if isinstance(v, bool) or not isinstance(v, numbers.Real) or not 0.0 <= float(v) < 1.0:
         raise ValueError(f"{name} must be a number in [0, 1), got {v!r}")
     return float(v)
+
+
+# `site.last_sinkhorn`: the column scale v (E) fp32 the last Sinkhorn forward ranked with, the number of frames that took each expert (E) int32,
+# and the (S) int32 bitmask of the selection (bit e: expert e took the frame) -- device tensors
+SinkhornReport = namedtuple("SinkhornReport", ["scale", "count", "choice"])
 
 
 def expert_choice_capacity(k, S, E):
@@ -175,7 +191,9 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
     losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call;
     or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too);
-    or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike.
+    or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike;
+    or, with `router_sinkhorn` set, one avmoe_moe_forward_sinkhorn call (which takes the multiplier too) -- in eval mode only with
+    `router_sinkhorn_eval`, else the plain top-k call.
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
@@ -190,6 +208,18 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
                              "router_select_count (a RouterBiasBalancer)")
         if not getattr(capi.lib(), "avmoe_site_choice", False):
             raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_choice / avmoe_expert_choice: it serves no expert-choice gating")
+    sk_iters = module.router_sinkhorn
+    if sk_iters is not None:                              # (the site's settings first, in eval mode too)
+        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
+        if module.router_top_k is None or not 1 <= module.router_top_k < E_:
+            raise ValueError(f"router_sinkhorn balances a top-k selection: it needs router_top_k in [1, {E_}), got {module.router_top_k!r}")
+        if choice_k is not None or module.router_select_bias is not None or module.router_select_count is not None:
+            raise ValueError("router_sinkhorn balances within the call: it combines with neither router_select_bias / router_select_count "
+                             "(a RouterBiasBalancer) nor router_expert_choice")
+        if not getattr(capi.lib(), "avmoe_site_sinkhorn", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn: it serves no Sinkhorn routing")
+        if not (module.training or module.router_sinkhorn_eval):
+            sk_iters = None                               # eval mode routes greedily (S-BASE): the plain top-k call
     if not (X.is_cuda and Y.is_cuda):
         raise capi.AvmoeError("avmoe_amd runs on MI355X only: tensors must live on a GPU (no CPU fallback)")
     if stream is None:
@@ -234,6 +264,12 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         capacity = expert_choice_capacity(choice_k, S, E)
         choice = torch.empty(S, device=X.device, dtype=torch.int32)
     module.__dict__["_last_expert_choice"] = choice
+    # Sinkhorn-balanced top-k (include/avmoe.h at avmoe_moe_forward_sinkhorn): the reports of the call's actual selection
+    sk_choice = sk_count = None
+    if sk_iters is not None:
+        sk_choice = torch.empty(S, device=X.device, dtype=torch.int32)
+        sk_count = torch.empty(E, device=X.device, dtype=torch.int32)
+    module.__dict__["_last_sinkhorn"] = None
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -259,6 +295,12 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
                                         int(module.router_expert_choice_renorm), _ptr(mix), out.data_ptr(), probs.data_ptr(), idx.data_ptr(),
                                         lb.data_ptr(), aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None,
                                         choice.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+    elif sk_iters is not None:                           # Sinkhorn-balanced top-k (and the multiplier, when one was drawn)
+        fn = "avmoe_moe_forward_sinkhorn"
+        st = L.avmoe_moe_forward_sinkhorn(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, sk_iters, _ptr(mix),
+                                          out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
+                                          aux[1].data_ptr() if aux else None, sk_choice.data_ptr(), sk_count.data_ptr(), saved.data_ptr(),
+                                          scratch.data_ptr(), stream)
     elif biased:                                         # the selection bias / counts (and the multiplier, when one was drawn)
         fn = "avmoe_moe_forward_bias"
         st = L.avmoe_moe_forward_bias(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix), _ptr(sel_bias),
@@ -281,6 +323,9 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
                                  idx.data_ptr(), lb.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
     desc.accumulate_out = 0
     capi.check(st, fn)
+    if sk_iters is not None:                              # the scale the call used: a copy of its E words in `saved` (no sync; `saved` is not kept alive)
+        off = _mode_offset(module, L, desc) + 64
+        module.__dict__["_last_sinkhorn"] = SinkhornReport(saved[off:off + 4 * E].view(torch.float32).clone(), sk_count, sk_choice)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
     mix = (mix, module.__dict__["_mix_draws"]) if mix is not None else None      # (the tensor is the site's cached one: with its draw number)
@@ -487,6 +532,9 @@ class _PairFunction(torch.autograd.Function):
                 t_.record_stream(main)
             if site_b.last_expert_choice is not None:    # (made on the side stream like the outputs above)
                 site_b.last_expert_choice.record_stream(main)
+            if site_b.last_sinkhorn is not None:
+                for t_ in site_b.last_sinkhorn:
+                    t_.record_stream(main)
         else:
             out_a, pr_a, idx_a, lb_a, st_a, ax_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, stream=main.cuda_stream)
             out_b, pr_b, idx_b, lb_b, st_b, ax_b = _site_forward(site_b, st_a[3], st_a[2], noises[1], names_b, pb, add_to=base_b, stream=main.cuda_stream)
@@ -683,6 +731,9 @@ class MoEAdapter(nn.Module):
         # expert-choice gating (include/avmoe.h at avmoe_moe_forward_choice): each expert takes its share of the frames.  Plain attributes too.
         self.router_expert_choice = getattr(opt, "router_expert_choice", None)
         self.router_expert_choice_renorm = getattr(opt, "router_expert_choice_renorm", False)
+        # Sinkhorn-balanced top-k (include/avmoe.h at avmoe_moe_forward_sinkhorn): the top-k selection balanced within each call.  Plain attributes too.
+        self.router_sinkhorn = getattr(opt, "router_sinkhorn", None)
+        self.router_sinkhorn_eval = getattr(opt, "router_sinkhorn_eval", False)
         # the regularisers of the mixture (include/avmoe.h at avmoe_moe_forward_reg): stochastic depth on the adapter branch and expert
         # dropout, training mode only.  Plain attributes like the ones above, not state: no state_dict key, no buffer.
         self.__dict__["_mix_index"] = next(_MIX_SITES)
@@ -824,6 +875,39 @@ class MoEAdapter(nn.Module):
         return self.__dict__.get("_last_expert_choice")
 
     @property
+    def router_sinkhorn(self):
+        """None (off), or n in [1, 64]: Sinkhorn-balanced top-k routing -- n rounds of row / column normalisation of the call's softmax give a
+        scale v per expert, and every frame takes the `router_top_k` experts with the largest p v; the weights stay those of the unscaled p.
+        It balances within each call (under data parallel: each rank over its own frames), keeps exactly k experts per frame, and has no
+        loss term, no rate and no state.  It needs `router_top_k` in [1, E) and combines with neither a selection bias nor
+        `router_expert_choice` (checked when the site runs).  Training mode only unless `router_sinkhorn_eval`."""
+        return self.__dict__.get("_router_sinkhorn")      # (.get: a module pickled before the setting existed has none)
+
+    @router_sinkhorn.setter
+    def router_sinkhorn(self, n):
+        if n is not None:
+            if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= int(n) <= 64:
+                raise ValueError(f"router_sinkhorn must be None or an integer in [1, 64], got {n!r}")
+            n = int(n)
+        self.__dict__["_router_sinkhorn"] = n
+
+    @property
+    def router_sinkhorn_eval(self):
+        """False (the default, as S-BASE routes at inference): in eval mode the site runs plain top-k, since a balanced assignment depends on
+        the rest of the batch; True: Sinkhorn stays on in eval mode."""
+        return self.__dict__.get("_router_sinkhorn_eval", False)
+
+    @router_sinkhorn_eval.setter
+    def router_sinkhorn_eval(self, v):
+        self.__dict__["_router_sinkhorn_eval"] = bool(v)
+
+    @property
+    def last_sinkhorn(self):
+        """SinkhornReport(scale (E) fp32, count (E) int32, choice (S) int32) of the last forward, device tensors -- the column scale it ranked
+        with, the frames each expert took and the bitmask of the selection --; None when it ran without Sinkhorn (or none ran yet)."""
+        return self.__dict__.get("_last_sinkhorn")
+
+    @property
     def router_top_k_renorm(self):
         """True: the kept probabilities are renormalised to sum 1 (a softmax over the kept logits); False: taken as they are (Switch)."""
         return self.__dict__.get("_router_top_k_renorm", True)
@@ -943,7 +1027,7 @@ class MoEAdapter(nn.Module):
     def __getstate__(self):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
         for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux", "_mix_state", "_mix_buf",
-                  "_mix_last", "_mix_draws", "_last_expert_choice"):
+                  "_mix_last", "_mix_draws", "_last_expert_choice", "_last_sinkhorn", "_mode_off"):
             st.pop(k, None)
         return st
 

@@ -174,6 +174,8 @@ struct RouterBwdArgs {
 // per expert, T_e in mode[32 + e] and L_e in mode[48 + e]; m_e = ec_member(p_e, T_e, L_e, s) is the forward's mask, never a selection run
 // again, and kept = sum_e m_e p_e in expert order.  mode[4] is the renorm of the choice:  dp_e = m_e (dw_e - sum_j (c w)_j dp_j) / kept, or
 // m_e dw_e without it; a frame no expert took gets dp = 0.  The selection has no gradient.
+// mode[2] == 2 (avmoe_moe_forward_sinkhorn): the forward ranked the experts on p v; the selection is recomputed by topk_select_scaled with
+// the words of v the forward left in mode[16 .. 16 + E), and dp_e is the top-k formula with that mask.  v has no gradient (a stop-gradient).
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
@@ -210,6 +212,10 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
         for (int e = 0; e < a.E; ++e)
           if (ec_member(s_p[e], __int_as_float(mode[32 + e]), mode[48 + e], s)) { m |= 1u << e; kept += s_p[e]; }
         renorm = mode[4];                          // (a frame no expert took has m = 0: nothing is divided by its kept = 0)
+      } else if (mode[2] == 2) {                   // (uniform over the grid) a Sinkhorn-balanced forward: ranked on p v, the v it USED
+        float vs[MAX_E];
+        for (int e = 0; e < a.E; ++e) vs[e] = __int_as_float(mode[16 + e]);
+        m = topk_select_scaled(s_p, vs, a.E, top_k, &kept);
       } else if (mode[2]) {                             // (uniform over the grid) a forward with a selection bias: the values it USED
         float bs[MAX_E];
         for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[16 + e]);

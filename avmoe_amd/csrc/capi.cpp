@@ -49,11 +49,11 @@ size_t avmoe_moe_scratch_bytes(const avmoe_moe_desc* desc) {
 
 }  // extern "C"
 
-// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
+// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
 static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                         const float* noise, int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux,
                         float* load, const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice,
-                        void* saved, void* scratch, void* stream) {
+                        const RouterSinkhorn* sinkhorn, void* saved, void* scratch, void* stream) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
   if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("%s: null pointer", fn); return ERR_BAD_ARG; }
@@ -65,8 +65,12 @@ static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, c
   if (choice && (choice->capacity < 1 || choice->capacity > pl.d.S)) {      // (nothing launched)
     set_last_error("%s: capacity %d not in [1, %d]", fn, choice->capacity, pl.d.S); return ERR_BAD_ARG;
   }
+  if (sinkhorn) {                                       // (nothing launched; E >= 2 follows from a top_k in [1, E))
+    if (top_k < 1 || top_k >= pl.d.E) { set_last_error("%s: top_k %d not in [1, %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG; }
+    if (sinkhorn->iters < 1 || sinkhorn->iters > 64) { set_last_error("%s: iters %d not in [1, 64]", fn, sinkhorn->iters); return ERR_BAD_ARG; }
+  }
   return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0,
-                     aux, aux ? load : nullptr, mix_scale, select_bias, select_count, choice);
+                     aux, aux ? load : nullptr, mix_scale, select_bias, select_count, choice, sinkhorn);
 }
 
 // The one backward behind avmoe_moe_backward / _part / _ex / _aux / _reg (null_dout: dOut == NULL asks for the router-only backward, else it is refused)
@@ -94,38 +98,46 @@ extern "C" {
 int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                       const float* noise, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
                       void* stream) {
-  return site_forward("avmoe_moe_forward", 0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward", 0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                            int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
                            void* stream) {
-  return site_forward("avmoe_moe_forward_topk", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_topk", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                           int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
                           void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_aux", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_aux", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_reg(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                           int32_t top_k, int32_t renorm, const float* mix_scale, void* out, float* probs, int64_t* idx, float* lb,
                           float* aux, float* load, void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_reg", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_reg", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_bias(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                            int32_t top_k, int32_t renorm, const float* mix_scale, const float* select_bias, float* select_count, void* out,
                            float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_bias", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_bias", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count, nullptr, nullptr, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_choice(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                              int32_t capacity, int32_t renorm, const float* mix_scale, void* out, float* probs, int64_t* idx, float* lb,
                              float* aux, float* load, int32_t* choice, void* saved, void* scratch, void* stream) {
   const RouterChoice ch{capacity, renorm != 0, choice};
-  return site_forward("avmoe_moe_forward_choice", 0, desc, X, Y, params, noise, 0, 0, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, &ch, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_choice", 0, desc, X, Y, params, noise, 0, 0, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, &ch, nullptr, saved, scratch, stream);
+}
+
+int avmoe_moe_forward_sinkhorn(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, int32_t iters, const float* mix_scale, void* out, float* probs, int64_t* idx,
+                               float* lb, float* aux, float* load, int32_t* choice, int32_t* count, void* saved, void* scratch,
+                               void* stream) {
+  const RouterSinkhorn sk{iters, choice, count};
+  return site_forward("avmoe_moe_forward_sinkhorn", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, &sk, saved, scratch, stream);
 }
 
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
@@ -176,7 +188,7 @@ int avmoe_router_forward(const avmoe_moe_desc* desc, const float* rin, const avm
   if (hipMemcpyAsync((char*)saved + pl.o_rin, rin, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
     set_last_error("avmoe_router_forward: copy of rin failed"); return ERR_LAUNCH;
   }
-  return k_router(pl, (char*)saved, (char*)scratch, *params, noise, probs, idx, lb, (hipStream_t)stream, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return k_router(pl, (char*)saved, (char*)scratch, *params, noise, probs, idx, lb, (hipStream_t)stream, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 int avmoe_expert_forward_cross(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, int32_t j,

@@ -78,6 +78,24 @@ __device__ __forceinline__ bool ec_member(float p, float T, int L, long s) {
   return kp > kt || (kp == kt && s <= (long)L);
 }
 
+// Sinkhorn-balanced top-k (avmoe_moe_forward_sinkhorn, router_sinkhorn.hip): the experts are ranked on the score q_e = p_e v_e -- ONE fp32
+// multiplication, so the selection repeats bit for bit from p and the E words v -- with the tie rule of topk_select on q, and *kept stays
+// the sum of the kept UNSCALED probabilities, added in expert order: v enters the selection only.  The ranks are taken on ec_key(q), for
+// numbers the order of `>` / `==` and a total order on every bit pattern: exactly k experts are marked whatever p holds.
+__device__ __forceinline__ unsigned topk_select_scaled(const float* p, const float* v, int E, int k, float* kept) {
+  unsigned q[16];                                  // (AVMOE_MAX_EXPERTS)
+  for (int e = 0; e < E; ++e) q[e] = ec_key(__fmul_rn(p[e], v[e]));   // (never contracted into a neighbouring sum)
+  unsigned m = 0u;
+  float s = 0.f;
+  for (int e = 0; e < E; ++e) {
+    int rank = 0;
+    for (int f = 0; f < E; ++f) rank += (q[f] > q[e]) || (q[f] == q[e] && f < e);
+    if (rank < k) { m |= 1u << e; s += p[e]; }
+  }
+  *kept = s;
+  return m;
+}
+
 // element access for the activation / operand type T (float or __bf16)
 template <typename T> __device__ __forceinline__ float ldT(const T* p, long i);
 template <> __device__ __forceinline__ float ldT<float>(const float* p, long i) { return p[i]; }

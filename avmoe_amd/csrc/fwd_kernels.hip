@@ -776,6 +776,7 @@ struct RouterArgs {
   const float* mix;               // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg), or NULL; k_router then runs the top-k form
   const float* bias;              // (E) selection bias of the top-k gating (avmoe_moe_forward_bias), or NULL
   int choice_c, choice_renorm;    // expert-choice gating (avmoe_moe_forward_choice): the capacity (0: off) and its renorm, for the mode words
+  int sk_iters, sk_k, sk_renorm;  // Sinkhorn-balanced top-k (avmoe_moe_forward_sinkhorn): the rounds (0: off), k and renorm, for the mode words
 };
 // one block per frame: layer-1 pre-activations from the engine GEMM -- summed here over its split-K slabs, in slab order, when it
 // ran split (no separate reduce pass) --, then bias / ReLU, the two small layers, softmax and first-max argmax.  fp32, fixed order.
@@ -794,13 +795,19 @@ struct RouterArgs {
 // a.choice_c (avmoe_moe_forward_choice): block 0 leaves mode[3] = c and mode[4] = its renorm (0 / 0: off -- every router forward writes them).
 // k_router then runs the dense-with-a-multiplier form without the multiplier (psm = p, probs = p), and the two launches of expert_choice.hip
 // behind this one put the selection words into mode[32 ..) / mode[48 ..) and the weights into `probs`.
+// a.sk_iters (avmoe_moe_forward_sinkhorn): k_router runs that form too (psm = p, probs = p), and block 0 leaves mode[0] = k, mode[1] = renorm
+// -- the caller's, not the form's --, mode[2] = 2 ("ranked on p v, the words in mode[16 .. 16 + E)") and mode[5] = the rounds (0: off).  The
+// two launches of router_sinkhorn.hip behind this one put the bits of v into mode[16 ..) and the weights into `probs`.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
   __shared__ float s_h1[128], s_h2[32], s_lg[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
-  if (s == 0 && t == 0) { mode[0] = a.top_k; mode[1] = a.renorm; mode[2] = a.bias ? 1 : 0; mode[3] = a.choice_c; mode[4] = a.choice_renorm; }
+  if (s == 0 && t == 0) {
+    mode[0] = a.sk_iters ? a.sk_k : a.top_k; mode[1] = a.sk_iters ? a.sk_renorm : a.renorm; mode[2] = a.sk_iters ? 2 : (a.bias ? 1 : 0);
+    mode[3] = a.choice_c; mode[4] = a.choice_renorm; mode[5] = a.sk_iters;
+  }
   if (a.bias && s == 0 && t < a.E) mode[16 + t] = __float_as_int(a.bias[t]);
   {
     float pre;
@@ -951,7 +958,8 @@ __global__ void __launch_bounds__(256) kk_router_count(const float* p, int S, in
 }
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
              int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out,
-             const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice) {
+             const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice,
+             const RouterSinkhorn* sinkhorn) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
@@ -962,10 +970,13 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
   // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
   // Expert choice (top_k == 0, no bias: the callers see to it) takes that form too, WITHOUT the multiplier: k_expert_choice, launched by
   // moe_forward behind this wrapper, overwrites `probs` with the weights of its selection, times the multiplier.
-  const bool mix_dense = (mix_scale || choice) && !top_k;
+  // Sinkhorn-balanced top-k (top_k in [1, E), no bias, no choice: the callers see to it) takes it as well: k_sk_apply overwrites `probs`.
+  // The mode words keep the caller's k and renorm (RouterArgs::sk_k / sk_renorm), and so do the auxiliary losses below.
+  const bool mix_dense = ((mix_scale || choice) && !top_k) || sinkhorn;
   const int k_mix = mix_dense ? d.E : top_k;
   RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0,
-               choice ? nullptr : mix_scale, select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0};
+               (choice || sinkhorn) ? nullptr : mix_scale, select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0,
+               sinkhorn ? sinkhorn->iters : 0, sinkhorn ? top_k : 0, (sinkhorn && renorm) ? 1 : 0};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;

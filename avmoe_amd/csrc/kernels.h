@@ -37,6 +37,7 @@ int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs&
                hipStream_t st);
 // ---- forward: router --------------------------------------------------------------------------
 struct RouterChoice { int capacity, renorm; int32_t* choice; };     // avmoe_moe_forward_choice: c in [1, S], renorm, (S) bitmask out or NULL
+struct RouterSinkhorn { int iters; int32_t* choice; int32_t* count; };   // avmoe_moe_forward_sinkhorn: n in [1, 64], (S) bitmask out or NULL, (E) counts out or NULL
 int k_onehot_noise(float* noise, int S, int E, int hot, float value, hipStream_t st);      // sub-ops of the C ABI (fwd_kernels.hip)
 int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float* rowb, const float* colb, hipStream_t st);
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
@@ -44,12 +45,20 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
              float* aux_out, float* load_out,                                                    // aux_out: [z, balance] (avmoe_moe_forward_aux)
              const float* mix_scale,                                                             // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg) or NULL
              const float* select_bias, float* select_count,                                      // (E) selection bias / (E) counts added to (avmoe_moe_forward_bias), NULL each
-             const RouterChoice* choice);                                                        // expert-choice gating (avmoe_moe_forward_choice): the mode words and the dense-with-multiplier form; NULL: off
+             const RouterChoice* choice,                                                         // expert-choice gating (avmoe_moe_forward_choice): the mode words and the dense-with-multiplier form; NULL: off
+             const RouterSinkhorn* sinkhorn);                                                    // Sinkhorn-balanced top-k (avmoe_moe_forward_sinkhorn): the mode words and that form too; NULL: off
 // expert-choice gating (expert_choice.hip): per column e of p (S, E) the threshold T_e = its c-th largest value and L_e = the last frame taken
 // among the ties (one block per expert), then per frame the mask, the weights w (times mix) and the bitmask word.  thr_bits / last: E words
 // each, written by the first launch and read by the second; w / choice: NULL = not written.  Two launches, no host scalar that changes.
 int k_expert_choice(const float* p, long S, int E, int capacity, int renorm, const float* mix, float* w, int32_t* choice, int* thr_bits,
                     int* last, hipStream_t st);
+// Sinkhorn-balanced top-k (router_sinkhorn.hip): k_sk_scale, ONE block, runs the `iters` rounds of row / column normalisation on p (S, E),
+// leaves the bits of the column scale v in v_bits (E words) and clears count (E words, or NULL); k_sk_apply, one thread per frame, ranks
+// on p v and writes the weights w (times mix), the bitmask word and the counts of the selection (added into count).  w / choice / count:
+// NULL = not written.  No host scalar that changes.
+int k_sk_scale(const float* p, long S, int E, int iters, int* v_bits, int* count, hipStream_t st);
+int k_sk_apply(const float* p, long S, int E, int top_k, int renorm, const float* mix, const int* v_bits, float* w, int32_t* choice,
+               int* count, hipStream_t st);
 // ---- forward: per token -----------------------------------------------------------------------
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);

@@ -34,7 +34,7 @@ avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* 
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const float* noise, void* out,
                 float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm,
                 float* aux_out, float* load_out, const float* mix_scale, const float* select_bias, float* select_count,
-                const RouterChoice* choice) {
+                const RouterChoice* choice, const RouterSinkhorn* sinkhorn) {
   const Dims& d = pl.d;
   // Cumulative BatchNorm average (bn_momentum < 0): the statistic kernels form 1 / (counter + 1) on the device, so every counter must be there
   const bool cumul = d.use_bn && d.training && d.bn_momentum < 0.f;
@@ -180,12 +180,24 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     AVMOE_TRY(down_gemm(Xs.flat(d.S), Z.flat(d.S)));                        // Zx = X Wt^T
   }
   // ---- router (its input: the token means of X -- after the statistics above) ----------------------
-  AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm, aux_out, load_out, mix_scale, select_bias, select_count, choice));
+  AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm, aux_out, load_out, mix_scale, select_bias, select_count, choice, sinkhorn));
   if (choice) {                                            // expert-choice gating: the selection words into `mode`, the weights into `probs`
     ProfScope ps_("k_expert_choice", 0.0, 0.0, st);
     int* mode = (int*)(sv + pl.o_mode);
     AVMOE_TRY(k_expert_choice((const float*)(sv + pl.o_psm), d.S, d.E, choice->capacity, choice->renorm, mix_scale, (float*)(sv + pl.o_probs),
                               choice->choice, mode + 32, mode + 48, st));
+  }
+  if (sinkhorn) {                                          // Sinkhorn-balanced top-k: the column scale into `mode`, the weights of its selection into `probs`
+    int* mode = (int*)(sv + pl.o_mode);
+    const float* p = (const float*)(sv + pl.o_psm);
+    {
+      ProfScope ps_("k_sk_scale", 0.0, 0.0, st);
+      AVMOE_TRY(k_sk_scale(p, d.S, d.E, sinkhorn->iters, mode + 16, sinkhorn->count, st));
+    }
+    {
+      ProfScope ps_("k_sk_apply", 0.0, 0.0, st);
+      AVMOE_TRY(k_sk_apply(p, d.S, d.E, top_k, renorm, mix_scale, mode + 16, (float*)(sv + pl.o_probs), sinkhorn->choice, sinkhorn->count, st));
+    }
   }
   if (d.KL > 0 && !d.fuse_l2) {                            // L2[s] = X[s] T[s]^T   (fused: per-group partial sums came out of the down projection; pre_small adds them into L2)
     GemmArgs g = base();
@@ -306,7 +318,7 @@ int expert_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe
       q.e[o].bn1_nbt = q.e[o].bn2_nbt = dump_n;
     }
   }
-  return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // The remap MATERIALISED (the product path folds it away): Yt = conv_adapter(Y) (S, N, Cy), then

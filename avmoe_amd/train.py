@@ -9,6 +9,8 @@
   * `reestimate_bn`         -- BatchNorm statistics re-estimated with forward passes (momentum=None, torch's update_bn), for the
                                raw weights or, with `ema=opt`, for FlatAdam's averaged weights
   * `expert_choice_mask`    -- expert-choice gating as a function: which frames each expert takes from an (S, E) matrix, on the device
+  * `sinkhorn_scale` / `sinkhorn_topk` -- Sinkhorn-balanced top-k routing as functions: the column scale of an (S, E) matrix and the
+                               selection it gives, on the device
   * `RouterBiasBalancer`    -- aux-loss-free expert balancing of top-k sites: a bias on the selection, updated on the device after
                                every optimizer step
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
@@ -104,6 +106,35 @@ def expert_choice_mask(probs: torch.Tensor, capacity: int) -> torch.Tensor:
                                torch.cuda.current_stream(p.device).cuda_stream)
     capi.check(st, "avmoe_expert_choice")
     return (bits[:, None] >> torch.arange(E, device=p.device, dtype=torch.int32)[None, :]) & 1 != 0
+
+
+def _sinkhorn(probs, k, iters, want_mask):
+    L = capi.lib()
+    if not getattr(L, "avmoe_site_sinkhorn", False):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn: it serves no Sinkhorn routing")
+    if not probs.is_cuda:
+        raise capi.AvmoeError("sinkhorn_scale / sinkhorn_topk run on the GPU (no CPU fallback)")
+    p = probs.reshape(-1, probs.shape[-1]).to(torch.float32).contiguous()
+    S, E = p.shape
+    v = torch.empty(E, dtype=torch.float32, device=p.device)
+    bits = torch.empty(S, dtype=torch.int32, device=p.device) if want_mask else None
+    st = L.avmoe_router_sinkhorn(p.data_ptr(), S, E, int(k), 0, int(iters), None, None, bits.data_ptr() if want_mask else None, None,
+                                 v.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream)
+    capi.check(st, "avmoe_router_sinkhorn")
+    return v, bits, E
+
+
+def sinkhorn_scale(probs: torch.Tensor, iters: int) -> torch.Tensor:
+    """(E,) float32: the column scale v of Sinkhorn-balanced routing (include/avmoe.h at avmoe_router_sinkhorn) after `iters` rounds of
+    row / column normalisation of the (S, E) matrix `probs`.  The sites' own kernel (`site.router_sinkhorn`) on a caller's matrix."""
+    return _sinkhorn(probs, 1, iters, False)[0]
+
+
+def sinkhorn_topk(probs: torch.Tensor, k: int, iters: int) -> torch.Tensor:
+    """(S, E) bool: row s is True on the k experts with the largest probs[s, e] * v[e], v = sinkhorn_scale(probs, iters); equal products
+    in expert order.  Exactly k experts per frame."""
+    _v, bits, E = _sinkhorn(probs, k, iters, True)
+    return (bits[:, None] >> torch.arange(E, device=bits.device, dtype=torch.int32)[None, :]) & 1 != 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

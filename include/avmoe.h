@@ -384,6 +384,50 @@ int avmoe_expert_choice(const float* p, int64_t S, int32_t E, int32_t capacity, 
                         float* w /* (S,E) or NULL */, int32_t* choice /* (S) or NULL */, float* thr /* (E) or NULL */,
                         int32_t* last /* (E) or NULL */, void* stream);
 
+/* avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn (found by symbol, as above; AVMOE_ABI_VERSION stays 11) -- Sinkhorn-balanced top-k
+ * routing (S-BASE, Clark et al. 2022; BASE layers, Lewis et al. 2021; csrc/router_sinkhorn.hip): the selection is balanced within the call,
+ * and every frame is still served by exactly k experts.  No loss weight, no update rate, no persistent state.  With p the dense softmax of
+ * the call, (S, E) fp32, AVS noise included, n = iters in [1, 64] and k = top_k in [1, E):
+ *     v_e = 1 ;  n times:  u_s = 1 / sum_e p[s, e] v_e        (row step)
+ *                          v_e = (S / E) / sum_s p[s, e] u_s   (column step)
+ *     q[s, e] = p[s, e] * v_e                                  ONE fp32 multiplication: the selection repeats from p and v
+ *     m[s, :] = the k experts with the largest q[s, :], equal q in expert order          (the tie rule of top-k gating, on q)
+ *     kept_s  = sum_e m[s, e] p[s, e]                          the UNSCALED p, added in expert order
+ *     w[s, e] = m[s, e] p[s, e] / kept_s  (renorm != 0)  |  m[s, e] p[s, e]  (renorm == 0) ;  then multiplied by mix_scale[s, e] if given.
+ * u_s does not change a row's ranking, so the E words v describe the selection of the whole call; v enters the selection only, the weights
+ * come from the unscaled p (as with a selection bias).  v has no gradient (a stop-gradient, as in S-BASE), and neither has the selection.
+ * A column whose sum is 0 gets the largest finite fp32: v is never Inf or NaN.  Every sum of the iteration has one fixed order (one block:
+ * frames per thread in frame order, shuffles within a wave, the waves in wave order), so the same input gives the same bits on every call.
+ * Only the weights change: every expert still runs on every frame, and the BatchNorm batch and running statistics, probs (the dense
+ * softmax), idx, lb, aux and load are those of avmoe_moe_forward_reg with the same top_k, renorm and mix_scale, bit for bit -- the losses
+ * keep describing the router's own preference, not the balanced selection, which is reported through choice and count.
+ * Backward:  dp_e is the top-k formula (at avmoe_moe_forward_topk / _reg) with m from the scaled selection; dprobs, lb, the auxiliary terms
+ * and the softmax Jacobian follow unchanged.  The mask is recomputed per frame from the saved softmax and the words of v the forward USED.
+ * There is no new backward entry point and no further backward launch: every existing one serves a Sinkhorn forward (avmoe_moe_backward_reg
+ * when a multiplier was used; dOut == NULL takes the router-only path).
+ * `saved`, `mode` buffer:  [0] = k, [1] = renorm, [2] = 2 ("ranked on p v"; 1 is the selection bias, 0 neither -- every router forward
+ * writes it, so a later plain forward on the same workspace switches the mode off), [5] = n, [16 + e] = the bits of v_e.  No buffer is
+ * added and avmoe_moe_saved_bytes does not change.
+ * Non-finite probabilities give an unspecified selection; every access stays in bounds and exactly k experts are marked per frame.
+ *
+ * avmoe_moe_forward_sinkhorn is avmoe_moe_forward_reg plus iters and the two reports: choice[s] (DEVICE (S) int32, or NULL) has bit e set
+ * iff frame s took expert e; count[e] (DEVICE (E) int32, or NULL; overwritten) is the number of frames that took expert e -- integer adds,
+ * the same on every call.  There is no selection bias and no expert choice in this mode.  It adds two launches to the forward (one block
+ * for v; one thread per frame for the weights, the bitmask and the counts); no host scalar changes between calls, so it is capturable.
+ * top_k outside [1, E) or iters outside [1, 64]: AVMOE_ERR_BAD_ARG with nothing launched.
+ *
+ * avmoe_router_sinkhorn -- the same kernels on a caller's DEVICE (S, E) fp32 matrix p.  w (S, E), choice (S) and count (E) may each be NULL;
+ * v (E) is required, so the call never allocates.  AVMOE_ERR_BAD_ARG, with nothing launched: p or v NULL, E outside [2, 16], S outside
+ * [1, 2^31 - 1], top_k outside [1, E), iters outside [1, 64], w overlapping p. */
+int avmoe_moe_forward_sinkhorn(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                               const float* noise, int32_t top_k, int32_t renorm, int32_t iters, const float* mix_scale /* (S,E) f32 or NULL */,
+                               void* out, float* probs, int64_t* idx, float* lb, float* aux /* [z, balance] or NULL */,
+                               float* load /* (E) or NULL */, int32_t* choice /* (S) int32 or NULL */, int32_t* count /* (E) int32 or NULL */,
+                               void* saved, void* scratch, void* stream);
+int avmoe_router_sinkhorn(const float* p, int64_t S, int32_t E, int32_t top_k, int32_t renorm, int32_t iters,
+                          const float* mix_scale /* (S,E) or NULL */, float* w /* (S,E) or NULL */, int32_t* choice /* (S) or NULL */,
+                          int32_t* count /* (E) or NULL */, float* v /* (E) */, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B

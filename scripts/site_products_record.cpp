@@ -227,7 +227,7 @@ int k_pre_small_bwd(PassCall&, avmoe_moe_ptrs const&, hipStream_t) { return note
 int k_prep_all(Plan const&, char*, avmoe_moe_ptrs const&, hipStream_t) { return note("k_prep_all"); }
 int k_prep_dBm(Plan const&, char*, hipStream_t) { return note("k_prep_dBm"); }
 int k_qrqb_fill(Plan const&, char*, float const*, hipStream_t) { return note("k_qrqb_fill"); }
-int k_router(Plan const&, char*, char*, avmoe_moe_ptrs const&, float const*, float*, int64_t*, float*, hipStream_t, int, int, float*, float*, float const*, float const*, float*, RouterChoice const*) { return note("k_router"); }
+int k_router(Plan const&, char*, char*, avmoe_moe_ptrs const&, float const*, float*, int64_t*, float*, hipStream_t, int, int, float*, float*, float const*, float const*, float*, RouterChoice const*, RouterSinkhorn const*) { return note("k_router"); }
 int k_router_bwd(Plan const&, char*, char*, avmoe_moe_ptrs const&, avmoe_moe_ptrs const&, float const*, float const*, hipStream_t, float const*, float const*) { return note("k_router_bwd"); }
 int k_softmax_rows(int, float const*, long, int, int, void*, int, int, int, int, int, hipStream_t) { return note("k_softmax_rows"); }
 int k_softmax_rows_bwd(int, void const*, float const*, long, int, int, void*, void*, int, int, hipStream_t) { return note("k_softmax_rows_bwd"); }
@@ -283,7 +283,7 @@ static void forward(const Site& s) {
   if (!plan_of(s, &pl)) return;
   begin("forward", s, pl);
   const long c0 = g_count;
-  end(moe_forward(pl, base(R_X), base(R_Y), g_prm, nullptr, base(R_OUT), (float*)base(R_PROBS), nullptr, nullptr, base(R_SV), base(R_SC), nullptr, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), c0);
+  end(moe_forward(pl, base(R_X), base(R_Y), g_prm, nullptr, base(R_OUT), (float*)base(R_PROBS), nullptr, nullptr, base(R_SV), base(R_SC), nullptr, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), c0);
 }
 static void backward(const Site& s, int parts, int acc = 0) {
   Plan pl;
