@@ -251,6 +251,13 @@ def declare(L):
         L.avmoe_moe_forward_sinkhorn.restype, L.avmoe_moe_forward_sinkhorn.argtypes = C.c_int, head + [C.c_int32] * 3 + [C.c_void_p] * 12
         L.avmoe_router_sinkhorn.restype = C.c_int
         L.avmoe_router_sinkhorn.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+    # expert capacity behind top-k (found by symbol: the site forward that drops the pairs beyond each expert's budget, and the kernels as a sub-op)
+    L.avmoe_site_capacity = bool(L.avmoe_site_bias and hasattr(L, "avmoe_moe_forward_capacity") and hasattr(L, "avmoe_router_capacity"))
+    if L.avmoe_site_capacity:
+        L.avmoe_moe_forward_capacity.restype = C.c_int
+        L.avmoe_moe_forward_capacity.argtypes = head + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 13
+        L.avmoe_router_capacity.restype = C.c_int
+        L.avmoe_router_capacity.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

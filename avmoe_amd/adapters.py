@@ -169,6 +169,20 @@ def expert_choice_capacity(k, S, E):
     return min(S, max(1, math.ceil(Fraction(k) * S / E)))
 
 
+# `site.last_capacity`: the capacity c of the last forward with an expert capacity (a host int), the (S) int32 bitmask of the kept pairs (bit e:
+# expert e kept the frame), and per expert the number of frames that selected it and the number it kept, (E) int32 each -- device tensors
+CapacityReport = namedtuple("CapacityReport", ["capacity", "kept", "demand", "kept_count"])
+
+
+def router_capacity(f, k, S, E):
+    """c = min(S, max(1, ceil(f k S / E))) of an expert capacity with capacity factor f behind top-k routing (GShard, Switch), evaluated
+    exactly (Fraction(f), Fraction(k)): the budget of frames per expert and call."""
+    return min(S, max(1, math.ceil(Fraction(f) * Fraction(k) * S / E)))
+
+
+_CAPACITY_POLICIES = {"order": 0, "priority": 1}
+
+
 def _draw_mix(module, L, S, E, p, q, dev, stream):
     """The (S, E) multiplier of one training-mode call, drawn on `stream` by avmoe_mix_drop_draw into the site's cached tensor.  The site
     owns the generator's state block {seed, calls} on the device: nothing the host writes changes between two calls, so a captured
@@ -193,7 +207,9 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too);
     or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike;
     or, with `router_sinkhorn` set, one avmoe_moe_forward_sinkhorn call (which takes the multiplier too) -- in eval mode only with
-    `router_sinkhorn_eval`, else the plain top-k call.
+    `router_sinkhorn_eval`, else the plain top-k call;
+    or, with `router_capacity_factor` set, one avmoe_moe_forward_capacity call (which takes the multiplier, the selection bias and the
+    counts too) -- in eval mode only with `router_capacity_eval_factor`, else the call the site makes without a capacity.
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
@@ -220,6 +236,22 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
             raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn: it serves no Sinkhorn routing")
         if not (module.training or module.router_sinkhorn_eval):
             sk_iters = None                               # eval mode routes greedily (S-BASE): the plain top-k call
+    cap_f = module.router_capacity_factor
+    if cap_f is not None:                                 # (the site's settings first, in eval mode too)
+        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
+        if module.router_top_k is None or not 1 <= module.router_top_k < E_:
+            raise ValueError(f"router_capacity_factor bounds the frames of a top-k selection: it needs router_top_k in [1, {E_}), "
+                             f"got {module.router_top_k!r}")
+        if choice_k is not None:
+            raise ValueError("router_capacity_factor does not combine with router_expert_choice: expert choice already gives every expert "
+                             "exactly its share of the frames")
+        if module.router_sinkhorn is not None:
+            raise ValueError("router_capacity_factor does not combine with router_sinkhorn: a capacity acts on the plain (or biased) top-k "
+                             "selection, not on one balanced within the call")
+        if not getattr(capi.lib(), "avmoe_site_capacity", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_capacity / avmoe_router_capacity: it serves no expert capacity")
+        if not module.training:
+            cap_f = module.router_capacity_eval_factor    # None: eval mode drops nothing (an evaluation should not depend on the batch)
     if not (X.is_cuda and Y.is_cuda):
         raise capi.AvmoeError("avmoe_amd runs on MI355X only: tensors must live on a GPU (no CPU fallback)")
     if stream is None:
@@ -270,6 +302,15 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         sk_choice = torch.empty(S, device=X.device, dtype=torch.int32)
         sk_count = torch.empty(E, device=X.device, dtype=torch.int32)
     module.__dict__["_last_sinkhorn"] = None
+    # expert capacity (include/avmoe.h at avmoe_moe_forward_capacity): c from the factor -- exactly, in rationals; a function of S alone, so a
+    # captured call keeps its capacity --, the multiplier for the backward (this call's own tensor) and the reports
+    cap_c, cap_scale, cap_rep = 0, None, None
+    if cap_f is not None:
+        cap_c = router_capacity(cap_f, k, S, E)
+        cap_scale = torch.empty(S, E, device=X.device, dtype=torch.float32)
+        cap_rep = CapacityReport(cap_c, torch.empty(S, device=X.device, dtype=torch.int32), torch.empty(E, device=X.device, dtype=torch.int32),
+                                 torch.empty(E, device=X.device, dtype=torch.int32))
+    module.__dict__["_last_capacity"] = cap_rep
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -301,6 +342,14 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
                                           out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
                                           aux[1].data_ptr() if aux else None, sk_choice.data_ptr(), sk_count.data_ptr(), saved.data_ptr(),
                                           scratch.data_ptr(), stream)
+    elif cap_f is not None:                              # expert capacity behind top-k (and the multiplier, the bias, the counts)
+        fn = "avmoe_moe_forward_capacity"
+        st = L.avmoe_moe_forward_capacity(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix),
+                                          _ptr(sel_bias), _ptr(sel_count), cap_c, _CAPACITY_POLICIES[module.router_capacity_policy],
+                                          cap_scale.data_ptr(), cap_rep.kept.data_ptr(), cap_rep.demand.data_ptr(),
+                                          cap_rep.kept_count.data_ptr(), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
+                                          aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None, saved.data_ptr(),
+                                          scratch.data_ptr(), stream)
     elif biased:                                         # the selection bias / counts (and the multiplier, when one was drawn)
         fn = "avmoe_moe_forward_bias"
         st = L.avmoe_moe_forward_bias(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix), _ptr(sel_bias),
@@ -326,9 +375,15 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     if sk_iters is not None:                              # the scale the call used: a copy of its E words in `saved` (no sync; `saved` is not kept alive)
         off = _mode_offset(module, L, desc) + 64
         module.__dict__["_last_sinkhorn"] = SinkhornReport(saved[off:off + 4 * E].view(torch.float32).clone(), sk_count, sk_choice)
+    if cap_rep is not None and module.training:           # avmoe_amd.train.CapacityMeter: two adds on this stream, no sync
+        for meter in module.__dict__.get("_capacity_meters", ()):
+            meter.update(module, cap_rep)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
-    mix = (mix, module.__dict__["_mix_draws"]) if mix is not None else None      # (the tensor is the site's cached one: with its draw number)
+    if cap_scale is not None:                            # the backward's multiplier is this call's own cap_scale (it holds the draw too): no draw number
+        mix = (cap_scale, None)
+    else:
+        mix = (mix, module.__dict__["_mix_draws"]) if mix is not None else None      # (the tensor is the site's cached one: with its draw number)
     return out, probs, idx, lb, ((desc, keep, ptrs, mix), saved, X, Y), aux
 
 
@@ -344,7 +399,7 @@ class _SiteBackward:
         (desc, keep, fwd_ptrs, mix), self.saved, self.X, self.Y = state
         self.mix = None                                  # the forward's multiplier on the mixture weights (drop_path / expert_dropout), given again
         if mix is not None:
-            if module.__dict__.get("_mix_draws") != mix[1]:
+            if mix[1] is not None and module.__dict__.get("_mix_draws") != mix[1]:
                 raise capi.AvmoeError("drop_path / expert_dropout: the site ran another training forward before this one's backward, and the "
                                       "site's one multiplier tensor now holds that call's draw (run each forward's backward before the next forward)")
             self.mix = mix[0]
@@ -534,6 +589,9 @@ class _PairFunction(torch.autograd.Function):
                 site_b.last_expert_choice.record_stream(main)
             if site_b.last_sinkhorn is not None:
                 for t_ in site_b.last_sinkhorn:
+                    t_.record_stream(main)
+            if site_b.last_capacity is not None:         # (and the backward's multiplier of such a call)
+                for t_ in site_b.last_capacity[1:] + (st_b[0][3][0],):
                     t_.record_stream(main)
         else:
             out_a, pr_a, idx_a, lb_a, st_a, ax_a = _site_forward(site_a, Xa, Xb, noises[0], names_a, pa, add_to=base_a, stream=main.cuda_stream)
@@ -734,6 +792,10 @@ class MoEAdapter(nn.Module):
         # Sinkhorn-balanced top-k (include/avmoe.h at avmoe_moe_forward_sinkhorn): the top-k selection balanced within each call.  Plain attributes too.
         self.router_sinkhorn = getattr(opt, "router_sinkhorn", None)
         self.router_sinkhorn_eval = getattr(opt, "router_sinkhorn_eval", False)
+        # expert capacity behind top-k (include/avmoe.h at avmoe_moe_forward_capacity): overflow pairs dropped within each call.  Plain attributes too.
+        self.router_capacity_factor = getattr(opt, "router_capacity_factor", None)
+        self.router_capacity_policy = getattr(opt, "router_capacity_policy", "order")
+        self.router_capacity_eval_factor = getattr(opt, "router_capacity_eval_factor", None)
         # the regularisers of the mixture (include/avmoe.h at avmoe_moe_forward_reg): stochastic depth on the adapter branch and expert
         # dropout, training mode only.  Plain attributes like the ones above, not state: no state_dict key, no buffer.
         self.__dict__["_mix_index"] = next(_MIX_SITES)
@@ -907,6 +969,56 @@ class MoEAdapter(nn.Module):
         with, the frames each expert took and the bitmask of the selection --; None when it ran without Sinkhorn (or none ran yet)."""
         return self.__dict__.get("_last_sinkhorn")
 
+    @staticmethod
+    def _capacity_factor(name, f):
+        if f is not None:
+            if isinstance(f, bool) or not isinstance(f, numbers.Real) or not math.isfinite(f) or not f > 0:
+                raise ValueError(f"{name} must be None or a finite number > 0, got {f!r}")
+        return f
+
+    @property
+    def router_capacity_factor(self):
+        """None (off), or a finite number f > 0: an expert capacity behind top-k routing (GShard, Switch, V-MoE) -- every expert serves at
+        most c = router_capacity(f, router_top_k, S, E) = ceil(f k S / E) of the call's frames; the token-expert pairs beyond that budget
+        are dropped (weight exactly 0, nothing renormalised afterwards), and a frame that lost every pair passes through the residual.
+        It needs `router_top_k` in [1, E) and combines with neither `router_expert_choice` nor `router_sinkhorn` (checked when the site
+        runs); it does combine with a selection bias and its counts (which keep counting demand), `drop_path` / `expert_dropout` and
+        `router_aux`.  Training mode only unless `router_capacity_eval_factor`."""
+        return self.__dict__.get("_router_capacity_factor")      # (.get: a module pickled before the setting existed has none)
+
+    @router_capacity_factor.setter
+    def router_capacity_factor(self, f):
+        self.__dict__["_router_capacity_factor"] = self._capacity_factor("router_capacity_factor", f)
+
+    @property
+    def router_capacity_policy(self):
+        """"order" (the default; GShard / Switch): an expert keeps the first c frames, in frame order, that selected it; "priority"
+        (batch-prioritised routing, V-MoE): the c selecting frames on which the router scores it highest, equal scores in frame order."""
+        return self.__dict__.get("_router_capacity_policy", "order")
+
+    @router_capacity_policy.setter
+    def router_capacity_policy(self, v):
+        if v not in _CAPACITY_POLICIES:
+            raise ValueError(f"router_capacity_policy must be 'order' or 'priority', got {v!r}")
+        self.__dict__["_router_capacity_policy"] = v
+
+    @property
+    def router_capacity_eval_factor(self):
+        """None (the default): in eval mode the site drops nothing -- the call it makes without a capacity --, since what a capacity drops
+        depends on the rest of the batch; a finite number > 0: the capacity factor of eval mode (Switch's eval_capacity_factor)."""
+        return self.__dict__.get("_router_capacity_eval_factor")
+
+    @router_capacity_eval_factor.setter
+    def router_capacity_eval_factor(self, f):
+        self.__dict__["_router_capacity_eval_factor"] = self._capacity_factor("router_capacity_eval_factor", f)
+
+    @property
+    def last_capacity(self):
+        """CapacityReport(capacity, kept (S) int32, demand (E) int32, kept_count (E) int32) of the last forward -- the budget c (a host int),
+        the bitmask of the kept pairs, the frames that selected each expert and the frames it kept; device tensors, nothing synchronised --;
+        None when it ran without a capacity (or none ran yet)."""
+        return self.__dict__.get("_last_capacity")
+
     @property
     def router_top_k_renorm(self):
         """True: the kept probabilities are renormalised to sum 1 (a softmax over the kept logits); False: taken as they are (Switch)."""
@@ -1027,7 +1139,8 @@ class MoEAdapter(nn.Module):
     def __getstate__(self):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
         for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux", "_mix_state", "_mix_buf",
-                  "_mix_last", "_mix_draws", "_last_expert_choice", "_last_sinkhorn", "_mode_off"):
+                  "_mix_last", "_mix_draws", "_last_expert_choice", "_last_sinkhorn", "_mode_off",
+                  "_last_capacity", "_capacity_meters"):
             st.pop(k, None)
         return st
 

@@ -49,11 +49,11 @@ size_t avmoe_moe_scratch_bytes(const avmoe_moe_desc* desc) {
 
 }  // extern "C"
 
-// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
+// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn / _capacity (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
 static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                         const float* noise, int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux,
                         float* load, const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice,
-                        const RouterSinkhorn* sinkhorn, void* saved, void* scratch, void* stream) {
+                        const RouterSinkhorn* sinkhorn, void* saved, void* scratch, void* stream, const RouterCapacity* capacity = nullptr) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
   if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("%s: null pointer", fn); return ERR_BAD_ARG; }
@@ -69,8 +69,16 @@ static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, c
     if (top_k < 1 || top_k >= pl.d.E) { set_last_error("%s: top_k %d not in [1, %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG; }
     if (sinkhorn->iters < 1 || sinkhorn->iters > 64) { set_last_error("%s: iters %d not in [1, 64]", fn, sinkhorn->iters); return ERR_BAD_ARG; }
   }
+  if (capacity) {                                       // (nothing launched; E >= 2 follows from a top_k in [1, E))
+    if (top_k < 1 || top_k >= pl.d.E) { set_last_error("%s: top_k %d not in [1, %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG; }
+    if (capacity->capacity < 1 || capacity->capacity > pl.d.S) {
+      set_last_error("%s: capacity %d not in [1, %d]", fn, capacity->capacity, pl.d.S); return ERR_BAD_ARG;
+    }
+    if (capacity->policy != 0 && capacity->policy != 1) { set_last_error("%s: policy %d not in {0, 1}", fn, capacity->policy); return ERR_BAD_ARG; }
+    if (!capacity->cap_scale) { set_last_error("%s: cap_scale is NULL (the backward's multiplier is required)", fn); return ERR_BAD_ARG; }
+  }
   return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0,
-                     aux, aux ? load : nullptr, mix_scale, select_bias, select_count, choice, sinkhorn);
+                     aux, aux ? load : nullptr, mix_scale, select_bias, select_count, choice, sinkhorn, capacity);
 }
 
 // The one backward behind avmoe_moe_backward / _part / _ex / _aux / _reg (null_dout: dOut == NULL asks for the router-only backward, else it is refused)
@@ -138,6 +146,15 @@ int avmoe_moe_forward_sinkhorn(const avmoe_moe_desc* desc, const void* X, const 
                                void* stream) {
   const RouterSinkhorn sk{iters, choice, count};
   return site_forward("avmoe_moe_forward_sinkhorn", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, &sk, saved, scratch, stream);
+}
+
+int avmoe_moe_forward_capacity(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                               int32_t top_k, int32_t renorm, const float* mix_scale, const float* select_bias, float* select_count,
+                               int32_t capacity, int32_t policy, float* cap_scale, int32_t* kept, int32_t* demand, int32_t* kept_count,
+                               void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved, void* scratch,
+                               void* stream) {
+  const RouterCapacity cap{capacity, policy, cap_scale, kept, demand, kept_count};
+  return site_forward("avmoe_moe_forward_capacity", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count, nullptr, nullptr, saved, scratch, stream, &cap);
 }
 
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,

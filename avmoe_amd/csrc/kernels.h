@@ -59,6 +59,17 @@ int k_expert_choice(const float* p, long S, int E, int capacity, int renorm, con
 int k_sk_scale(const float* p, long S, int E, int iters, int* v_bits, int* count, hipStream_t st);
 int k_sk_apply(const float* p, long S, int E, int top_k, int renorm, const float* mix, const int* v_bits, float* w, int32_t* choice,
                int* count, hipStream_t st);
+// Expert capacity for top-k routing (router_capacity.hip), behind a k_router call in the top-k form: k_cap_mask, one thread per frame, leaves
+// the selection word of every frame (topk_select / topk_select_biased on p); k_cap_select, one block per expert, the two words per expert
+// (policy 0 "order": the c-th selecting frame; policy 1 "priority": the c-th largest p among the selecting frames and the last tied frame
+// taken), demand and kept_count (E words each, or NULL); k_cap_apply, one thread per frame, sets the dropped entries of w to +0.0f and writes
+// cap_scale (S, E) = keep ? mix (or 1) : 0 and the bitmask of the kept pairs (w / cap_scale / kept: NULL = not written; kept may be mask).
+struct RouterCapacity { int capacity, policy; float* cap_scale; int32_t* kept; int32_t* demand; int32_t* kept_count; };   // avmoe_moe_forward_capacity
+int k_cap_mask(const float* p, long S, int E, int top_k, const float* bias, int32_t* mask, hipStream_t st);
+int k_cap_select(const float* p, const int32_t* mask, long S, int E, int capacity, int policy, int* thr_bits, int* last, int32_t* demand,
+                 int32_t* kept_count, hipStream_t st);
+int k_cap_apply(const float* p, const int32_t* mask, long S, int E, int policy, const int* thr_bits, const int* last, const float* mix,
+                float* w, float* cap_scale, int32_t* kept, hipStream_t st);
 // ---- forward: per token -----------------------------------------------------------------------
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);

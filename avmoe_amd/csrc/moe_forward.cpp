@@ -34,7 +34,7 @@ avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* 
 int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const float* noise, void* out,
                 float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm,
                 float* aux_out, float* load_out, const float* mix_scale, const float* select_bias, float* select_count,
-                const RouterChoice* choice, const RouterSinkhorn* sinkhorn) {
+                const RouterChoice* choice, const RouterSinkhorn* sinkhorn, const RouterCapacity* capacity) {
   const Dims& d = pl.d;
   // Cumulative BatchNorm average (bn_momentum < 0): the statistic kernels form 1 / (counter + 1) on the device, so every counter must be there
   const bool cumul = d.use_bn && d.training && d.bn_momentum < 0.f;
@@ -197,6 +197,25 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     {
       ProfScope ps_("k_sk_apply", 0.0, 0.0, st);
       AVMOE_TRY(k_sk_apply(p, d.S, d.E, top_k, renorm, mix_scale, mode + 16, (float*)(sv + pl.o_probs), sinkhorn->choice, sinkhorn->count, st));
+    }
+  }
+  if (capacity) {                                          // expert capacity behind top-k: the dropped entries of `probs` set to 0, the multiplier for the backward out
+    // (the selection words and the words per expert live in `rbw`, a buffer of the router backward: S + 2 MAX_E words of its S (E + 160 + 2 C))
+    int32_t* mask = (int32_t*)(sc + pl.o_rbw);
+    int* tl = (int*)mask + d.S;
+    const float* p = (const float*)(sv + pl.o_psm);
+    {
+      ProfScope ps_("k_cap_mask", 0.0, 0.0, st);
+      AVMOE_TRY(k_cap_mask(p, d.S, d.E, top_k, select_bias, mask, st));
+    }
+    {
+      ProfScope ps_("k_cap_select", 0.0, 0.0, st);
+      AVMOE_TRY(k_cap_select(p, mask, d.S, d.E, capacity->capacity, capacity->policy, tl, tl + MAX_E, capacity->demand, capacity->kept_count, st));
+    }
+    {
+      ProfScope ps_("k_cap_apply", 0.0, 0.0, st);
+      AVMOE_TRY(k_cap_apply(p, mask, d.S, d.E, capacity->policy, tl, tl + MAX_E, mix_scale, (float*)(sv + pl.o_probs), capacity->cap_scale,
+                            capacity->kept, st));
     }
   }
   if (d.KL > 0 && !d.fuse_l2) {                            // L2[s] = X[s] T[s]^T   (fused: per-group partial sums came out of the down projection; pre_small adds them into L2)

@@ -11,6 +11,7 @@
   * `expert_choice_mask`    -- expert-choice gating as a function: which frames each expert takes from an (S, E) matrix, on the device
   * `sinkhorn_scale` / `sinkhorn_topk` -- Sinkhorn-balanced top-k routing as functions: the column scale of an (S, E) matrix and the
                                selection it gives, on the device
+  * `CapacityMeter`         -- the demand and the kept frames of sites with an expert capacity, accumulated on the device
   * `RouterBiasBalancer`    -- aux-loss-free expert balancing of top-k sites: a bias on the selection, updated on the device after
                                every optimizer step
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
@@ -75,6 +76,58 @@ class ExpertActivationCounter:
     def numpy(self) -> Dict[str, "object"]:
         c = self.counts.cpu().numpy()
         return {n: c[i] for i, n in enumerate(self.names)}
+
+
+class CapacityMeter:
+    """How much an expert capacity drops (`site.router_capacity_factor`; include/avmoe.h at avmoe_moe_forward_capacity): `demand` and
+    `kept_count` of every TRAINING forward of `sites`, accumulated per site into (E_i,) int64 tensors on the reports' device -- two adds on
+    the forward's own stream, no host synchronisation (the companion of `ExpertActivationCounter`).  The sites tell their meters
+    themselves, so the two sites of an `AdapterPair` and captured steps are counted like any other call.  `overflow()` gives the dropped
+    share per site and expert and synchronises; `reset()` clears the totals; `close()` detaches the meter from the sites."""
+
+    def __init__(self, sites):
+        self.sites = list(sites)
+        if not self.sites:
+            raise ValueError("CapacityMeter: no sites")
+        self.demand = [None] * len(self.sites)
+        self.kept = [None] * len(self.sites)
+        self.calls = [0] * len(self.sites)
+        for s in self.sites:
+            s.__dict__.setdefault("_capacity_meters", []).append(self)
+
+    def update(self, site, report):
+        """Add one call's CapacityReport of `site` (a site of this meter, or its index) to the totals."""
+        i = site if isinstance(site, int) else next(j for j, s in enumerate(self.sites) if s is site)
+        d, k = report.demand.to(torch.int64), report.kept_count.to(torch.int64)
+        if self.demand[i] is None or self.demand[i].device != d.device:
+            self.demand[i], self.kept[i] = torch.zeros_like(d), torch.zeros_like(k)
+        self.demand[i] += d
+        self.kept[i] += k
+        self.calls[i] += 1
+
+    def overflow(self) -> List[torch.Tensor]:
+        """Per site, the share of the token-expert pairs each expert dropped since the last reset(): (E_i,) float64 CPU tensors,
+        (demand - kept) / demand, 0 where nothing selected the expert; None for a site that has not reported.  Synchronises."""
+        out = []
+        for d, k in zip(self.demand, self.kept):
+            if d is None:
+                out.append(None)
+                continue
+            d, k = d.cpu().to(torch.float64), k.cpu().to(torch.float64)
+            out.append(torch.where(d > 0, (d - k) / d.clamp_min(1.0), torch.zeros_like(d)))
+        return out
+
+    def reset(self):
+        for t in self.demand + self.kept:
+            if t is not None:
+                t.zero_()
+        self.calls = [0] * len(self.sites)
+
+    def close(self):
+        for s in self.sites:
+            m = s.__dict__.get("_capacity_meters", [])
+            if self in m:
+                m.remove(self)
 
 
 def topk_experts(probs: torch.Tensor, k: int) -> torch.Tensor:

@@ -428,6 +428,58 @@ int avmoe_router_sinkhorn(const float* p, int64_t S, int32_t E, int32_t top_k, i
                           const float* mix_scale /* (S,E) or NULL */, float* w /* (S,E) or NULL */, int32_t* choice /* (S) or NULL */,
                           int32_t* count /* (E) or NULL */, float* v /* (E) */, void* stream);
 
+/* avmoe_moe_forward_capacity / avmoe_router_capacity (found by symbol, as above; AVMOE_ABI_VERSION stays 11) -- an expert capacity behind
+ * top-k routing (GShard, Lepikhin et al. 2020; Switch, Fedus et al. 2021; batch-prioritised routing: V-MoE, Riquelme et al. 2021;
+ * csrc/router_capacity.hip): every expert serves at most c = capacity frames of the call, the token-expert pairs beyond that budget are
+ * dropped, and a frame that lost every pair passes through the residual.  With p the dense softmax of the call, (S, E) fp32, AVS noise
+ * included, k = top_k in [1, E), c in [1, S] and
+ *     m[s, e]  = 1[e in S_k(s)]          the selection the top-k form makes: on p, or on p + select_bias when a bias is given
+ *     demand_e = sum_s m[s, e]
+ *   policy 0, "order" (GShard / Switch):  expert e keeps the first c frames, in frame order, that selected it;
+ *   policy 1, "priority" (V-MoE):         expert e keeps the c selecting frames with the largest p[s, e] -- the unbiased, unscaled p; equal
+ *                                         values in frame order.  For k = 1 this is V-MoE's rule; for k > 1 the priority is PER PAIR
+ *                                         (a frame's second choice competes with its own p[s, e], not with the frame's best score).
+ *   demand_e <= c: everything is kept.     keep[s, e] = m[s, e] and "kept by expert e";  kept_e = min(demand_e, c).
+ *     w[s, e]         = keep[s, e] * w_topk[s, e] * mix_scale[s, e]
+ *     cap_scale[s, e] = keep[s, e] ? (mix_scale ? mix_scale[s, e] : 1.0f) : 0.0f
+ * w_topk is exactly what the top-k form writes: with renorm it is normalised over the FULL top-k set (as GShard normalises before it
+ * drops), and nothing is renormalised after dropping.  A dropped pair's weight is exactly +0.0f: set, not multiplied.  A frame that lost
+ * every pair has output 0 (with accumulate_out: nothing is added).  Each expert's outcome is two words as in expert choice, a threshold T_e
+ * and a last frame L_e: keep = m && s <= L_e (policy 0; T_e = -Inf), keep = m && (p > T_e || (p == T_e && s <= L_e)) (policy 1);
+ * within the budget T_e = -Inf, L_e = S - 1.
+ * Only the weights change: every expert still runs on every frame, and probs (the dense softmax), idx, lb, aux, load, the saved softmax and
+ * log-sum-exp, the mode words, the BatchNorm batch and running statistics and select_count are those of avmoe_moe_forward_bias with the same
+ * arguments, bit for bit -- select_count means DEMAND, which is what a balancer should see.
+ * Backward:  the keep mask is a {0, 1} factor on the mixture weights behind top-k, which is what mix_scale means: the backward of such a
+ * forward is avmoe_moe_backward_reg with mix_scale = cap_scale, and the whole call equals avmoe_moe_forward_bias with mix_scale = cap_scale
+ * bit for bit.  Nothing else is recorded: no new backward entry point, no backward launch, no mode word, no buffer;
+ * avmoe_moe_saved_bytes and avmoe_moe_scratch_bytes do not change.
+ * Non-finite probabilities give an unspecified selection; every access stays in bounds.
+ *
+ * avmoe_moe_forward_capacity is avmoe_moe_forward_bias plus capacity, policy, cap_scale (DEVICE (S, E) fp32, required) and three optional
+ * reports: kept[s] (DEVICE (S) int32) has bit e set iff the pair (s, e) was kept, demand[e] and kept_count[e] (DEVICE (E) int32 each) are
+ * demand_e and kept_e -- integer counts, the same bytes on every call.  It adds three launches to the forward behind the router (one thread
+ * per frame for the selection words, one block per expert for its two words, one thread per frame for the weights); no host scalar changes
+ * between calls, so it is capturable.  AVMOE_ERR_BAD_ARG with nothing launched: top_k outside [1, E), capacity outside [1, S], policy
+ * outside {0, 1}, cap_scale NULL.
+ *
+ * avmoe_router_capacity -- the same kernels on a caller's DEVICE (S, E) fp32 matrix p.  w (S, E), or NULL, is in and out: it holds the top-k
+ * weights (times the multiplier) and gets its dropped entries set to +0.0f.  cap_scale (S, E), kept (S), demand (E), kept_count (E),
+ * thr (E, T_e) and last (E, L_e) may each be NULL.  The call takes S + 32 words from the stream's memory pool for the selection words.
+ * AVMOE_ERR_BAD_ARG, with nothing launched: p NULL, E outside [2, 16], S outside [1, 2^31 - 1], top_k outside [1, E), capacity outside
+ * [1, S], policy outside {0, 1}, w overlapping p. */
+int avmoe_moe_forward_capacity(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                               const float* noise, int32_t top_k, int32_t renorm, const float* mix_scale /* (S,E) f32 or NULL */,
+                               const float* select_bias /* (E) or NULL */, float* select_count /* (E) or NULL */, int32_t capacity,
+                               int32_t policy, float* cap_scale /* (S,E) f32 */, int32_t* kept /* (S) int32 or NULL */,
+                               int32_t* demand /* (E) int32 or NULL */, int32_t* kept_count /* (E) int32 or NULL */, void* out, float* probs,
+                               int64_t* idx, float* lb, float* aux /* [z, balance] or NULL */, float* load /* (E) or NULL */, void* saved,
+                               void* scratch, void* stream);
+int avmoe_router_capacity(const float* p, int64_t S, int32_t E, int32_t top_k, const float* select_bias /* (E) or NULL */, int32_t capacity,
+                          int32_t policy, const float* mix_scale /* (S,E) or NULL */, float* w /* (S,E) in/out or NULL */,
+                          float* cap_scale /* (S,E) or NULL */, int32_t* kept /* (S) or NULL */, int32_t* demand /* (E) or NULL */,
+                          int32_t* kept_count /* (E) or NULL */, float* thr /* (E) or NULL */, int32_t* last /* (E) or NULL */, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B
