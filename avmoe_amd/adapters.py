@@ -201,57 +201,63 @@ def _draw_mix(module, L, S, E, p, q, dev, stream):
     return buf
 
 
+_Routing = namedtuple("_Routing", ["choice_k", "sk_iters", "cap_f"])      # what one call does about each selection stage; None: off
+
+
+def _routing_of(module):
+    """The selection stage of the call `module` is about to make, from the site's settings alone (a contradiction in them does not depend on
+    the call: reported first, in eval mode too), the eval-mode rules resolved: without `router_sinkhorn_eval` an eval call routes greedily
+    (S-BASE: the plain top-k call), and `router_capacity_eval_factor` stands in for the factor (None: an evaluation drops nothing, it
+    should not depend on the batch)."""
+    E = module.num_multimodal_experts + module.num_singlemodal_experts
+    top_k, biased = module.router_top_k, module.router_select_bias is not None or module.router_select_count is not None
+    choice_k, sk_iters, cap_f = module.router_expert_choice, module.router_sinkhorn, module.router_capacity_factor
+    if choice_k is not None:
+        if (top_k is not None and top_k < E) or biased:
+            raise ValueError("router_expert_choice selects per expert: it combines with neither router_top_k in [1, E) nor router_select_bias / "
+                             "router_select_count (a RouterBiasBalancer)")
+        if not getattr(capi.lib(), "avmoe_site_choice", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_choice / avmoe_expert_choice: it serves no expert-choice gating")
+    if sk_iters is not None:
+        if top_k is None or not 1 <= top_k < E:
+            raise ValueError(f"router_sinkhorn balances a top-k selection: it needs router_top_k in [1, {E}), got {top_k!r}")
+        if choice_k is not None or biased:
+            raise ValueError("router_sinkhorn balances within the call: it combines with neither router_select_bias / router_select_count "
+                             "(a RouterBiasBalancer) nor router_expert_choice")
+        if not getattr(capi.lib(), "avmoe_site_sinkhorn", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn: it serves no Sinkhorn routing")
+    if cap_f is not None:
+        if top_k is None or not 1 <= top_k < E:
+            raise ValueError(f"router_capacity_factor bounds the frames of a top-k selection: it needs router_top_k in [1, {E}), "
+                             f"got {top_k!r}")
+        if choice_k is not None:
+            raise ValueError("router_capacity_factor does not combine with router_expert_choice: expert choice already gives every expert "
+                             "exactly its share of the frames")
+        if sk_iters is not None:
+            raise ValueError("router_capacity_factor does not combine with router_sinkhorn: a capacity acts on the plain (or biased) top-k "
+                             "selection, not on one balanced within the call")
+        if not getattr(capi.lib(), "avmoe_site_capacity", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_capacity / avmoe_router_capacity: it serves no expert capacity")
+    if not module.training:
+        sk_iters = sk_iters if module.router_sinkhorn_eval else None
+        cap_f = module.router_capacity_eval_factor if cap_f is not None else None
+    return _Routing(choice_k, sk_iters, cap_f)
+
+
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
     """One avmoe_moe_forward_aux call: every site goes through it, with top_k = 0 for a dense one and aux = NULL without the auxiliary
     losses -- or, in training mode with `drop_path` / `expert_dropout` on, the draw of the multiplier and one avmoe_moe_forward_reg call;
     or, with `router_select_bias` / `router_select_count` set, one avmoe_moe_forward_bias call (which takes the multiplier too);
     or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike;
-    or, with `router_sinkhorn` set, one avmoe_moe_forward_sinkhorn call (which takes the multiplier too) -- in eval mode only with
-    `router_sinkhorn_eval`, else the plain top-k call;
+    or, with `router_sinkhorn` set, one avmoe_moe_forward_sinkhorn call (which takes the multiplier too);
     or, with `router_capacity_factor` set, one avmoe_moe_forward_capacity call (which takes the multiplier, the selection bias and the
-    counts too) -- in eval mode only with `router_capacity_eval_factor`, else the call the site makes without a capacity.
+    counts too) -- the last two in eval mode by the rules of _routing_of, else the call the site makes without them.
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
     stream: the handle (int) of the CURRENT stream when the caller already has it (AdapterPair), else looked up."""
-    choice_k = module.router_expert_choice
-    if choice_k is not None:                              # (the site's settings first: a contradiction in them does not depend on the call)
-        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
-        if (module.router_top_k is not None and module.router_top_k < E_) or module.router_select_bias is not None \
-                or module.router_select_count is not None:
-            raise ValueError("router_expert_choice selects per expert: it combines with neither router_top_k in [1, E) nor router_select_bias / "
-                             "router_select_count (a RouterBiasBalancer)")
-        if not getattr(capi.lib(), "avmoe_site_choice", False):
-            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_choice / avmoe_expert_choice: it serves no expert-choice gating")
-    sk_iters = module.router_sinkhorn
-    if sk_iters is not None:                              # (the site's settings first, in eval mode too)
-        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
-        if module.router_top_k is None or not 1 <= module.router_top_k < E_:
-            raise ValueError(f"router_sinkhorn balances a top-k selection: it needs router_top_k in [1, {E_}), got {module.router_top_k!r}")
-        if choice_k is not None or module.router_select_bias is not None or module.router_select_count is not None:
-            raise ValueError("router_sinkhorn balances within the call: it combines with neither router_select_bias / router_select_count "
-                             "(a RouterBiasBalancer) nor router_expert_choice")
-        if not getattr(capi.lib(), "avmoe_site_sinkhorn", False):
-            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_sinkhorn / avmoe_router_sinkhorn: it serves no Sinkhorn routing")
-        if not (module.training or module.router_sinkhorn_eval):
-            sk_iters = None                               # eval mode routes greedily (S-BASE): the plain top-k call
-    cap_f = module.router_capacity_factor
-    if cap_f is not None:                                 # (the site's settings first, in eval mode too)
-        E_ = module.num_multimodal_experts + module.num_singlemodal_experts
-        if module.router_top_k is None or not 1 <= module.router_top_k < E_:
-            raise ValueError(f"router_capacity_factor bounds the frames of a top-k selection: it needs router_top_k in [1, {E_}), "
-                             f"got {module.router_top_k!r}")
-        if choice_k is not None:
-            raise ValueError("router_capacity_factor does not combine with router_expert_choice: expert choice already gives every expert "
-                             "exactly its share of the frames")
-        if module.router_sinkhorn is not None:
-            raise ValueError("router_capacity_factor does not combine with router_sinkhorn: a capacity acts on the plain (or biased) top-k "
-                             "selection, not on one balanced within the call")
-        if not getattr(capi.lib(), "avmoe_site_capacity", False):
-            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_capacity / avmoe_router_capacity: it serves no expert capacity")
-        if not module.training:
-            cap_f = module.router_capacity_eval_factor    # None: eval mode drops nothing (an evaluation should not depend on the batch)
+    choice_k, sk_iters, cap_f = _routing_of(module)
     if not (X.is_cuda and Y.is_cuda):
         raise capi.AvmoeError("avmoe_amd runs on MI355X only: tensors must live on a GPU (no CPU fallback)")
     if stream is None:
@@ -330,50 +336,30 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         aux = (torch.empty(2, device=X.device, dtype=torch.float32), torch.empty(E, device=X.device, dtype=torch.float32))
     mix = _draw_mix(module, L, S, E, drop_p, drop_q, X.device, stream) if reg else None
     module.__dict__["_mix_last"] = mix
+    head = (C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise))
+    outs = (out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None)
+    ws = (saved.data_ptr(), scratch.data_ptr(), stream)
     if choice is not None:                               # expert choice (and the multiplier, when one was drawn)
-        fn = "avmoe_moe_forward_choice"
-        st = L.avmoe_moe_forward_choice(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), capacity,
-                                        int(module.router_expert_choice_renorm), _ptr(mix), out.data_ptr(), probs.data_ptr(), idx.data_ptr(),
-                                        lb.data_ptr(), aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None,
-                                        choice.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_choice", (capacity, int(module.router_expert_choice_renorm), _ptr(mix), *outs, choice.data_ptr())
     elif sk_iters is not None:                           # Sinkhorn-balanced top-k (and the multiplier, when one was drawn)
-        fn = "avmoe_moe_forward_sinkhorn"
-        st = L.avmoe_moe_forward_sinkhorn(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, sk_iters, _ptr(mix),
-                                          out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
-                                          aux[1].data_ptr() if aux else None, sk_choice.data_ptr(), sk_count.data_ptr(), saved.data_ptr(),
-                                          scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_sinkhorn", (k, renorm, sk_iters, _ptr(mix), *outs, sk_choice.data_ptr(), sk_count.data_ptr())
     elif cap_f is not None:                              # expert capacity behind top-k (and the multiplier, the bias, the counts)
-        fn = "avmoe_moe_forward_capacity"
-        st = L.avmoe_moe_forward_capacity(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix),
-                                          _ptr(sel_bias), _ptr(sel_count), cap_c, _CAPACITY_POLICIES[module.router_capacity_policy],
-                                          cap_scale.data_ptr(), cap_rep.kept.data_ptr(), cap_rep.demand.data_ptr(),
-                                          cap_rep.kept_count.data_ptr(), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
-                                          aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None, saved.data_ptr(),
-                                          scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_capacity", (k, renorm, _ptr(mix), _ptr(sel_bias), _ptr(sel_count), cap_c,
+                                                  _CAPACITY_POLICIES[module.router_capacity_policy], cap_scale.data_ptr(), cap_rep.kept.data_ptr(),
+                                                  cap_rep.demand.data_ptr(), cap_rep.kept_count.data_ptr(), *outs)
     elif biased:                                         # the selection bias / counts (and the multiplier, when one was drawn)
-        fn = "avmoe_moe_forward_bias"
-        st = L.avmoe_moe_forward_bias(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, _ptr(mix), _ptr(sel_bias),
-                                      _ptr(sel_count), out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(),
-                                      aux[0].data_ptr() if aux else None, aux[1].data_ptr() if aux else None, saved.data_ptr(),
-                                      scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_bias", (k, renorm, _ptr(mix), _ptr(sel_bias), _ptr(sel_count), *outs)
     elif mix is not None:                                # the multiplier on the mixture weights, drawn just above on the same stream
-        fn = "avmoe_moe_forward_reg"
-        st = L.avmoe_moe_forward_reg(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, mix.data_ptr(),
-                                     out.data_ptr(), probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
-                                     aux[1].data_ptr() if aux else None, saved.data_ptr(), scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_reg", (k, renorm, mix.data_ptr(), *outs)
     elif L.avmoe_site_aux:
-        fn = "avmoe_moe_forward_aux"
-        st = L.avmoe_moe_forward_aux(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), k, renorm, out.data_ptr(),
-                                     probs.data_ptr(), idx.data_ptr(), lb.data_ptr(), aux[0].data_ptr() if aux else None,
-                                     aux[1].data_ptr() if aux else None, saved.data_ptr(), scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward_aux", (k, renorm, *outs)
     else:                                                # a library from before the _aux entry points (AVMOE_LIB): the plain site, the one second path
-        fn = "avmoe_moe_forward"
-        st = L.avmoe_moe_forward(C.byref(desc), X.data_ptr(), Y.data_ptr(), C.byref(ptrs), _ptr(noise), out.data_ptr(), probs.data_ptr(),
-                                 idx.data_ptr(), lb.data_ptr(), saved.data_ptr(), scratch.data_ptr(), stream)
+        fn, args = "avmoe_moe_forward", outs[:4]
+    st = getattr(L, fn)(*head, *args, *ws)
     desc.accumulate_out = 0
     capi.check(st, fn)
     if sk_iters is not None:                              # the scale the call used: a copy of its E words in `saved` (no sync; `saved` is not kept alive)
-        off = _mode_offset(module, L, desc) + 64
+        off = _mode_offset(module, L, desc) + 4 * 16      # (csrc/kernels.h: MODE_SELECT_WORDS = 16, the bits of the column scale)
         module.__dict__["_last_sinkhorn"] = SinkhornReport(saved[off:off + 4 * E].view(torch.float32).clone(), sk_count, sk_choice)
     if cap_rep is not None and module.training:           # avmoe_amd.train.CapacityMeter: two adds on this stream, no sync
         for meter in module.__dict__.get("_capacity_meters", ()):

@@ -168,20 +168,20 @@ struct RouterBwdArgs {
 // otherwise  dp_e = m_e dw_e.  The load-balancing term, dprobs and the softmax Jacobian then act on p.
 // a.mix: the forward's multiplier c on the mixture weights (such a forward always leaves k > 0: k_router).  `probs` then holds c w and dp is
 // dL/d(c w): dw_e = c_e dp_e, while sum_j w_j dw_j = sum_j (c w)_j dp_j needs no factor.  c has no gradient.  NULL: a uniform branch not taken.
-// mode[2] (avmoe_moe_forward_bias): the forward ranked the experts on p + b; the selection is recomputed with the bias words the forward
-// left in mode[16 .. 16 + E) -- not with the live bias tensor, which the balancer may have updated since.  The bias has no gradient.
-// mode[3] = c > 0 (avmoe_moe_forward_choice): expert-choice gating.  The forward left the dense-with-a-multiplier form in mode[0 .. 2] and,
-// per expert, T_e in mode[32 + e] and L_e in mode[48 + e]; m_e = ec_member(p_e, T_e, L_e, s) is the forward's mask, never a selection run
-// again, and kept = sum_e m_e p_e in expert order.  mode[4] is the renorm of the choice:  dp_e = m_e (dw_e - sum_j (c w)_j dp_j) / kept, or
+// MODE_SELECT set (avmoe_moe_forward_bias): the forward ranked the experts on p + b; the selection is recomputed with the bias words the forward
+// left in MODE_SELECT_WORDS -- not with the live bias tensor, which the balancer may have updated since.  The bias has no gradient.
+// MODE_CHOICE_C = c > 0 (avmoe_moe_forward_choice): expert-choice gating.  The forward left the dense-with-a-multiplier form in the first three
+// words and, per expert, T_e in MODE_CHOICE_THR and L_e in MODE_CHOICE_LAST; m_e = ec_member(p_e, T_e, L_e, s) is the forward's mask, never a selection run
+// again, and kept = sum_e m_e p_e in expert order.  MODE_CHOICE_RENORM is the renorm of the choice:  dp_e = m_e (dw_e - sum_j (c w)_j dp_j) / kept, or
 // m_e dw_e without it; a frame no expert took gets dp = 0.  The selection has no gradient.
-// mode[2] == 2 (avmoe_moe_forward_sinkhorn): the forward ranked the experts on p v; the selection is recomputed by topk_select_scaled with
-// the words of v the forward left in mode[16 .. 16 + E), and dp_e is the top-k formula with that mask.  v has no gradient (a stop-gradient).
+// MODE_SELECT == MODE_SELECT_SINKHORN (avmoe_moe_forward_sinkhorn): the forward ranked the experts on p v; the selection is recomputed by topk_select_scaled
+// with the words of v the forward left in MODE_SELECT_WORDS, and dp_e is the top-k formula with that mask.  v has no gradient (a stop-gradient).
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
   const int s = blockIdx.x;
-  const int top_k = mode[0];                     // (uniform over the grid)
-  int renorm = mode[1];
+  const int top_k = mode[MODE_K];                // (uniform over the grid)
+  int renorm = mode[MODE_RENORM];
   const float* wt = probs;                       // the mixture weights
   if (top_k) probs = psm;                        // from here on: the softmax
   float* dh1 = rbw + (long)s * 128;
@@ -207,18 +207,18 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
       for (int e = 0; e < a.E; ++e) s_p[e] = probs[(long)s * a.E + e];
       float kept, wd = 0.f;
       unsigned m;
-      if (mode[3]) {                               // (uniform over the grid) an expert-choice forward: the mask from p and the two words per expert
+      if (mode[MODE_CHOICE_C]) {                   // (uniform over the grid) an expert-choice forward: the mask from p and the two words per expert
         m = 0u; kept = 0.f;
         for (int e = 0; e < a.E; ++e)
-          if (ec_member(s_p[e], __int_as_float(mode[32 + e]), mode[48 + e], s)) { m |= 1u << e; kept += s_p[e]; }
-        renorm = mode[4];                          // (a frame no expert took has m = 0: nothing is divided by its kept = 0)
-      } else if (mode[2] == 2) {                   // (uniform over the grid) a Sinkhorn-balanced forward: ranked on p v, the v it USED
+          if (ec_member(s_p[e], __int_as_float(mode[MODE_CHOICE_THR + e]), mode[MODE_CHOICE_LAST + e], s)) { m |= 1u << e; kept += s_p[e]; }
+        renorm = mode[MODE_CHOICE_RENORM];         // (a frame no expert took has m = 0: nothing is divided by its kept = 0)
+      } else if (mode[MODE_SELECT] == MODE_SELECT_SINKHORN) {   // (uniform over the grid) a Sinkhorn-balanced forward: ranked on p v, the v it USED
         float vs[MAX_E];
-        for (int e = 0; e < a.E; ++e) vs[e] = __int_as_float(mode[16 + e]);
+        for (int e = 0; e < a.E; ++e) vs[e] = __int_as_float(mode[MODE_SELECT_WORDS + e]);
         m = topk_select_scaled(s_p, vs, a.E, top_k, &kept);
-      } else if (mode[2]) {                             // (uniform over the grid) a forward with a selection bias: the values it USED
+      } else if (mode[MODE_SELECT]) {                   // (uniform over the grid) a forward with a selection bias: the values it USED
         float bs[MAX_E];
-        for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[16 + e]);
+        for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[MODE_SELECT_WORDS + e]);
         m = topk_select_biased(s_p, bs, a.E, top_k, &kept);
       } else m = topk_select(s_p, a.E, top_k, &kept);
       if (renorm)

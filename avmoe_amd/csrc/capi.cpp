@@ -49,36 +49,34 @@ size_t avmoe_moe_scratch_bytes(const avmoe_moe_desc* desc) {
 
 }  // extern "C"
 
-// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn / _capacity (`fn`: the name in the error strings; k_min: the smallest top_k the entry point takes)
-static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
-                        const float* noise, int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux,
-                        float* load, const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice,
-                        const RouterSinkhorn* sinkhorn, void* saved, void* scratch, void* stream, const RouterCapacity* capacity = nullptr) {
+// The ranges of a site call's routing, checked once before anything is launched (`fn`: the entry point's name in the error strings; k_min: the smallest top_k it takes)
+static int route_check(const char* fn, int k_min, const Dims& d, const RouteCall& r) {
+  const int k = r.top_k;
+  if (k < k_min || k > d.E) { set_last_error("%s: top_k %d not in [%d, %d]", fn, k, k_min, d.E); return ERR_BAD_ARG; }
+  if (r.select_bias && (k == 0 || k == d.E)) {           // a dense mixture has no selection
+    set_last_error("%s: select_bias needs top-k gating, 0 < top_k < E (top_k %d, E %d)", fn, k, d.E); return ERR_BAD_ARG;
+  }
+  const auto *ch = std::get_if<RouterChoice>(&r.stage); const auto *sk = std::get_if<RouterSinkhorn>(&r.stage);
+  const auto *cap = std::get_if<RouterCapacity>(&r.stage);
+  if ((sk || cap) && (k < 1 || k >= d.E)) { set_last_error("%s: top_k %d not in [1, %d)", fn, k, d.E); return ERR_BAD_ARG; }      // (both act on a top-k selection; E >= 2 follows)
+  const int c = ch ? ch->capacity : cap ? cap->capacity : 1;      // (no stage with a capacity: nothing to refuse)
+  if (c < 1 || c > d.S) { set_last_error("%s: capacity %d not in [1, %d]", fn, c, d.S); return ERR_BAD_ARG; }
+  if (sk && (sk->iters < 1 || sk->iters > 64)) { set_last_error("%s: iters %d not in [1, 64]", fn, sk->iters); return ERR_BAD_ARG; }
+  if (cap && cap->policy != 0 && cap->policy != 1) { set_last_error("%s: policy %d not in {0, 1}", fn, cap->policy); return ERR_BAD_ARG; }
+  if (cap && !cap->cap_scale) { set_last_error("%s: cap_scale is NULL (the backward's multiplier is required)", fn); return ERR_BAD_ARG; }
+  return OK;
+}
+
+// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn / _capacity
+static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, void* out,
+                        const RouteCall& route, void* saved, void* scratch, void* stream) {
   Plan pl;
   AVMOE_TRY(make_plan(desc, &pl));
   if (!X || !Y || !params || !out || !saved || !scratch) { set_last_error("%s: null pointer", fn); return ERR_BAD_ARG; }
-  if (top_k < k_min || top_k > pl.d.E) { set_last_error("%s: top_k %d not in [%d, %d]", fn, top_k, k_min, pl.d.E); return ERR_BAD_ARG; }
-  const int k = top_k == pl.d.E ? 0 : top_k;            // 0 and E: the dense mixture, whatever renorm says (the load then counts every frame's first expert)
-  if (select_bias && !k) {                              // a dense mixture has no selection
-    set_last_error("%s: select_bias needs top-k gating, 0 < top_k < E (top_k %d, E %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG;
-  }
-  if (choice && (choice->capacity < 1 || choice->capacity > pl.d.S)) {      // (nothing launched)
-    set_last_error("%s: capacity %d not in [1, %d]", fn, choice->capacity, pl.d.S); return ERR_BAD_ARG;
-  }
-  if (sinkhorn) {                                       // (nothing launched; E >= 2 follows from a top_k in [1, E))
-    if (top_k < 1 || top_k >= pl.d.E) { set_last_error("%s: top_k %d not in [1, %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG; }
-    if (sinkhorn->iters < 1 || sinkhorn->iters > 64) { set_last_error("%s: iters %d not in [1, 64]", fn, sinkhorn->iters); return ERR_BAD_ARG; }
-  }
-  if (capacity) {                                       // (nothing launched; E >= 2 follows from a top_k in [1, E))
-    if (top_k < 1 || top_k >= pl.d.E) { set_last_error("%s: top_k %d not in [1, %d)", fn, top_k, pl.d.E); return ERR_BAD_ARG; }
-    if (capacity->capacity < 1 || capacity->capacity > pl.d.S) {
-      set_last_error("%s: capacity %d not in [1, %d]", fn, capacity->capacity, pl.d.S); return ERR_BAD_ARG;
-    }
-    if (capacity->policy != 0 && capacity->policy != 1) { set_last_error("%s: policy %d not in {0, 1}", fn, capacity->policy); return ERR_BAD_ARG; }
-    if (!capacity->cap_scale) { set_last_error("%s: cap_scale is NULL (the backward's multiplier is required)", fn); return ERR_BAD_ARG; }
-  }
-  return moe_forward(pl, X, Y, *params, noise, out, probs, idx, lb, (char*)saved, (char*)scratch, (hipStream_t)stream, k, renorm != 0,
-                     aux, aux ? load : nullptr, mix_scale, select_bias, select_count, choice, sinkhorn, capacity);
+  AVMOE_TRY(route_check(fn, k_min, pl.d, route));
+  RouteCall r = route;
+  if (r.top_k == pl.d.E) r.top_k = 0;                    // 0 and E: the dense mixture, whatever renorm says (the load then counts every frame's first expert)
+  return moe_forward(pl, X, Y, *params, out, r, (char*)saved, (char*)scratch, (hipStream_t)stream);
 }
 
 // The one backward behind avmoe_moe_backward / _part / _ex / _aux / _reg (null_dout: dOut == NULL asks for the router-only backward, else it is refused)
@@ -101,51 +99,64 @@ static int site_backward(const char* fn, bool null_dout, const avmoe_moe_desc* d
                       aux_grad, mix_scale);
 }
 
+// the routing fields every site entry point has
+static RouteCall route_of(const float* noise, int32_t top_k, int32_t renorm, float* probs, int64_t* idx, float* lb) {
+  RouteCall r;
+  r.noise = noise; r.top_k = top_k; r.renorm = renorm != 0; r.probs_out = probs; r.idx_out = idx; r.lb_out = lb;
+  return r;
+}
+
 extern "C" {
 
 int avmoe_moe_forward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
                       const float* noise, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
                       void* stream) {
-  return site_forward("avmoe_moe_forward", 0, desc, X, Y, params, noise, 0, 1, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward", 0, desc, X, Y, params, out, route_of(noise, 0, 1, probs, idx, lb), saved, scratch, stream);
 }
 
 int avmoe_moe_forward_topk(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                            int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, void* saved, void* scratch,
                            void* stream) {
-  return site_forward("avmoe_moe_forward_topk", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  return site_forward("avmoe_moe_forward_topk", 1, desc, X, Y, params, out, route_of(noise, top_k, renorm, probs, idx, lb), saved, scratch, stream);
 }
 
 int avmoe_moe_forward_aux(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                           int32_t top_k, int32_t renorm, void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load,
                           void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_aux", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, nullptr, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  RouteCall r = route_of(noise, top_k, renorm, probs, idx, lb); r.aux_out = aux; r.load_out = load;
+  return site_forward("avmoe_moe_forward_aux", 0, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_reg(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                           int32_t top_k, int32_t renorm, const float* mix_scale, void* out, float* probs, int64_t* idx, float* lb,
                           float* aux, float* load, void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_reg", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, nullptr, saved, scratch, stream);
+  RouteCall r = route_of(noise, top_k, renorm, probs, idx, lb); r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale;
+  return site_forward("avmoe_moe_forward_reg", 0, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_bias(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                            int32_t top_k, int32_t renorm, const float* mix_scale, const float* select_bias, float* select_count, void* out,
                            float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved, void* scratch, void* stream) {
-  return site_forward("avmoe_moe_forward_bias", 0, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count, nullptr, nullptr, saved, scratch, stream);
+  RouteCall r = route_of(noise, top_k, renorm, probs, idx, lb);
+  r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale; r.select_bias = select_bias; r.select_count = select_count;
+  return site_forward("avmoe_moe_forward_bias", 0, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_choice(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                              int32_t capacity, int32_t renorm, const float* mix_scale, void* out, float* probs, int64_t* idx, float* lb,
                              float* aux, float* load, int32_t* choice, void* saved, void* scratch, void* stream) {
-  const RouterChoice ch{capacity, renorm != 0, choice};
-  return site_forward("avmoe_moe_forward_choice", 0, desc, X, Y, params, noise, 0, 0, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, &ch, nullptr, saved, scratch, stream);
+  RouteCall r = route_of(noise, 0, 0, probs, idx, lb); r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale;
+  r.stage = RouterChoice{capacity, renorm != 0, choice};
+  return site_forward("avmoe_moe_forward_choice", 0, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_sinkhorn(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
                                int32_t top_k, int32_t renorm, int32_t iters, const float* mix_scale, void* out, float* probs, int64_t* idx,
                                float* lb, float* aux, float* load, int32_t* choice, int32_t* count, void* saved, void* scratch,
                                void* stream) {
-  const RouterSinkhorn sk{iters, choice, count};
-  return site_forward("avmoe_moe_forward_sinkhorn", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, nullptr, nullptr, nullptr, &sk, saved, scratch, stream);
+  RouteCall r = route_of(noise, top_k, renorm, probs, idx, lb); r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale;
+  r.stage = RouterSinkhorn{iters, choice, count};
+  return site_forward("avmoe_moe_forward_sinkhorn", 1, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_forward_capacity(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
@@ -153,8 +164,10 @@ int avmoe_moe_forward_capacity(const avmoe_moe_desc* desc, const void* X, const 
                                int32_t capacity, int32_t policy, float* cap_scale, int32_t* kept, int32_t* demand, int32_t* kept_count,
                                void* out, float* probs, int64_t* idx, float* lb, float* aux, float* load, void* saved, void* scratch,
                                void* stream) {
-  const RouterCapacity cap{capacity, policy, cap_scale, kept, demand, kept_count};
-  return site_forward("avmoe_moe_forward_capacity", 1, desc, X, Y, params, noise, top_k, renorm, out, probs, idx, lb, aux, load, mix_scale, select_bias, select_count, nullptr, nullptr, saved, scratch, stream, &cap);
+  RouteCall r = route_of(noise, top_k, renorm, probs, idx, lb);
+  r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale; r.select_bias = select_bias; r.select_count = select_count;
+  r.stage = RouterCapacity{capacity, policy, cap_scale, kept, demand, kept_count};
+  return site_forward("avmoe_moe_forward_capacity", 1, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
@@ -205,7 +218,7 @@ int avmoe_router_forward(const avmoe_moe_desc* desc, const float* rin, const avm
   if (hipMemcpyAsync((char*)saved + pl.o_rin, rin, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
     set_last_error("avmoe_router_forward: copy of rin failed"); return ERR_LAUNCH;
   }
-  return k_router(pl, (char*)saved, (char*)scratch, *params, noise, probs, idx, lb, (hipStream_t)stream, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return k_router(pl, (char*)saved, (char*)scratch, *params, route_of(noise, 0, 1, probs, idx, lb), (hipStream_t)stream);
 }
 
 int avmoe_expert_forward_cross(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, int32_t j,

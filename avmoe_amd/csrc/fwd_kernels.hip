@@ -790,14 +790,14 @@ struct RouterArgs {
 // expert kept), so that psm keeps the softmax for the backward and the losses.  NULL: a uniform branch not taken.
 // a.bias (avmoe_moe_forward_bias: aux-loss-free balancing) enters the SELECTION only: the experts are ranked on p_e + b_e
 // (topk_select_biased), the weights are still m_e p_e / kept or m_e p_e with kept the sum of the kept unbiased p; probs_out, idx_out, psm
-// and lse do not see it.  Block 0 leaves mode[2] = 1 and the bits of the bias it used in mode[16 .. 16 + E): the router backward takes its
-// selection from there, not from the live tensor, which the balancer may have moved on by then.  NULL: a uniform branch not taken, mode[2] = 0.
-// a.choice_c (avmoe_moe_forward_choice): block 0 leaves mode[3] = c and mode[4] = its renorm (0 / 0: off -- every router forward writes them).
+// and lse do not see it.  Block 0 leaves mode[MODE_SELECT] = MODE_SELECT_BIASED and the bits of the bias it used in the MODE_SELECT_WORDS: the router backward takes its
+// selection from there, not from the live tensor, which the balancer may have moved on by then.  NULL: a uniform branch not taken, mode[MODE_SELECT] = 0.
+// a.choice_c (avmoe_moe_forward_choice): block 0 leaves mode[MODE_CHOICE_C] = c and mode[MODE_CHOICE_RENORM] = its renorm (0 / 0: off -- every router forward writes them).
 // k_router then runs the dense-with-a-multiplier form without the multiplier (psm = p, probs = p), and the two launches of expert_choice.hip
-// behind this one put the selection words into mode[32 ..) / mode[48 ..) and the weights into `probs`.
-// a.sk_iters (avmoe_moe_forward_sinkhorn): k_router runs that form too (psm = p, probs = p), and block 0 leaves mode[0] = k, mode[1] = renorm
-// -- the caller's, not the form's --, mode[2] = 2 ("ranked on p v, the words in mode[16 .. 16 + E)") and mode[5] = the rounds (0: off).  The
-// two launches of router_sinkhorn.hip behind this one put the bits of v into mode[16 ..) and the weights into `probs`.
+// behind this one put the selection words into MODE_CHOICE_THR / MODE_CHOICE_LAST and the weights into `probs`.
+// a.sk_iters (avmoe_moe_forward_sinkhorn): k_router runs that form too (psm = p, probs = p), and block 0 leaves mode[MODE_K] = k, mode[MODE_RENORM] = renorm
+// -- the caller's, not the form's --, mode[MODE_SELECT] = MODE_SELECT_SINKHORN and mode[MODE_SK_ITERS] = the rounds (0: off).  The two launches of
+// router_sinkhorn.hip behind this one put the bits of v into MODE_SELECT_WORDS and the weights into `probs`.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
@@ -805,10 +805,11 @@ __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, 
   const int s = blockIdx.x, t = threadIdx.x;
   if (lb_zero && s == 0 && t == 0) *lb_zero = 0.f;          // (sites without the load-balancing loss report 0)
   if (s == 0 && t == 0) {
-    mode[0] = a.sk_iters ? a.sk_k : a.top_k; mode[1] = a.sk_iters ? a.sk_renorm : a.renorm; mode[2] = a.sk_iters ? 2 : (a.bias ? 1 : 0);
-    mode[3] = a.choice_c; mode[4] = a.choice_renorm; mode[5] = a.sk_iters;
+    mode[MODE_K] = a.sk_iters ? a.sk_k : a.top_k; mode[MODE_RENORM] = a.sk_iters ? a.sk_renorm : a.renorm;
+    mode[MODE_SELECT] = a.sk_iters ? MODE_SELECT_SINKHORN : (a.bias ? MODE_SELECT_BIASED : 0);
+    mode[MODE_CHOICE_C] = a.choice_c; mode[MODE_CHOICE_RENORM] = a.choice_renorm; mode[MODE_SK_ITERS] = a.sk_iters;
   }
-  if (a.bias && s == 0 && t < a.E) mode[16 + t] = __float_as_int(a.bias[t]);
+  if (a.bias && s == 0 && t < a.E) mode[MODE_SELECT_WORDS + t] = __float_as_int(a.bias[t]);
   {
     float pre;
     if (ks > 1) {
@@ -956,27 +957,49 @@ __global__ void __launch_bounds__(256) kk_router_count(const float* p, int S, in
       if (threadIdx.x == 0) select_count[e] += c;
     }
 }
-int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm, float* aux_out, float* load_out,
-             const float* mix_scale, const float* select_bias, float* select_count, const RouterChoice* choice,
-             const RouterSinkhorn* sinkhorn) {
+// The selection stage behind the router, and the one home of its workspace slots: it reads the dense softmax in `psm`, leaves the weights of its
+// selection in `probs` and its words per expert in `mode`.  Capacity leaves nothing in `saved` (cap_scale is the backward's multiplier): its
+// selection words (S) and two words per expert borrow the head of `rbw`, a buffer of the router backward -- S + 2 MAX_E of its S (E + 160 + 2 C) words.
+static int route_stage(const Plan& pl, char* saved, char* scratch, const RouteCall& r, hipStream_t st) {
+  const Dims& d = pl.d;
+  int* mode = (int*)(saved + pl.o_mode);
+  const float* p = (const float*)(saved + pl.o_psm);
+  float* w = (float*)(saved + pl.o_probs);
+  if (const auto* ch = std::get_if<RouterChoice>(&r.stage)) {
+    ProfScope ps_("k_expert_choice", 0.0, 0.0, st);
+    AVMOE_TRY(k_expert_choice(p, d.S, d.E, ch->capacity, ch->renorm, r.mix_scale, w, ch->choice, mode + MODE_CHOICE_THR, mode + MODE_CHOICE_LAST, st));
+  } else if (const auto* sk = std::get_if<RouterSinkhorn>(&r.stage)) {
+    int* v_bits = mode + MODE_SELECT_WORDS;                // the column scale
+    { ProfScope ps_("k_sk_scale", 0.0, 0.0, st); AVMOE_TRY(k_sk_scale(p, d.S, d.E, sk->iters, v_bits, sk->count, st)); }
+    { ProfScope ps_("k_sk_apply", 0.0, 0.0, st); AVMOE_TRY(k_sk_apply(p, d.S, d.E, r.top_k, r.renorm, r.mix_scale, v_bits, w, sk->choice, sk->count, st)); }
+  } else if (const auto* cap = std::get_if<RouterCapacity>(&r.stage)) {      // the dropped entries of `probs` set to 0, the multiplier for the backward out
+    int32_t* mask = (int32_t*)(scratch + pl.o_rbw);
+    int *thr = (int*)mask + d.S, *last = thr + MAX_E;
+    { ProfScope ps_("k_cap_mask", 0.0, 0.0, st); AVMOE_TRY(k_cap_mask(p, d.S, d.E, r.top_k, r.select_bias, mask, st)); }
+    { ProfScope ps_("k_cap_select", 0.0, 0.0, st); AVMOE_TRY(k_cap_select(p, mask, d.S, d.E, cap->capacity, cap->policy, thr, last, cap->demand, cap->kept_count, st)); }
+    { ProfScope ps_("k_cap_apply", 0.0, 0.0, st); AVMOE_TRY(k_cap_apply(p, mask, d.S, d.E, cap->policy, thr, last, r.mix_scale, w, cap->cap_scale, cap->kept, st)); }
+  }
+  return OK;
+}
+static int router_launch(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const RouteCall& r, hipStream_t st) {
   ProfScope ps_("k_router", 0.0, 0.0, st);
   const Dims& d = pl.d;
+  const int top_k = r.top_k;
+  const auto *choice = std::get_if<RouterChoice>(&r.stage); const auto *sinkhorn = std::get_if<RouterSinkhorn>(&r.stage);
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
     set_last_error("moe: router parameters missing"); return ERR_BAD_ARG;
   }
   if (top_k < 0 || top_k > d.E) { set_last_error("moe: top_k %d not in [0, %d]", top_k, d.E); return ERR_BAD_ARG; }
   // A dense site with a multiplier runs as top-k with k = E without renormalisation: w = p exactly, every expert kept, and the softmax
   // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
-  // Expert choice (top_k == 0, no bias: the callers see to it) takes that form too, WITHOUT the multiplier: k_expert_choice, launched by
-  // moe_forward behind this wrapper, overwrites `probs` with the weights of its selection, times the multiplier.
-  // Sinkhorn-balanced top-k (top_k in [1, E), no bias, no choice: the callers see to it) takes it as well: k_sk_apply overwrites `probs`.
-  // The mode words keep the caller's k and renorm (RouterArgs::sk_k / sk_renorm), and so do the auxiliary losses below.
-  const bool mix_dense = ((mix_scale || choice) && !top_k) || sinkhorn;
+  // Expert choice takes that form too, WITHOUT the multiplier: k_expert_choice (route_stage) overwrites `probs` with the weights of its
+  // selection, times the multiplier.  Sinkhorn-balanced top-k takes it as well: k_sk_apply overwrites `probs`.  The mode words keep the
+  // caller's k and renorm (RouterArgs::sk_k / sk_renorm), and so do the auxiliary losses below.
+  const bool mix_dense = ((r.mix_scale || choice) && !top_k) || sinkhorn;
   const int k_mix = mix_dense ? d.E : top_k;
-  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, noise, 2 * d.C, d.E, d.S, k_mix, (renorm && !mix_dense) ? 1 : 0,
-               (choice || sinkhorn) ? nullptr : mix_scale, select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0,
-               sinkhorn ? sinkhorn->iters : 0, sinkhorn ? top_k : 0, (sinkhorn && renorm) ? 1 : 0};
+  RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, r.noise, 2 * d.C, d.E, d.S, k_mix, (r.renorm && !mix_dense) ? 1 : 0,
+               (choice || sinkhorn) ? nullptr : r.mix_scale, r.select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0,
+               sinkhorn ? sinkhorn->iters : 0, sinkhorn ? top_k : 0, (sinkhorn && r.renorm) ? 1 : 0};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
     GemmArgs g;
@@ -989,23 +1012,27 @@ int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& p
     AVMOE_TRY(launch_gemm(g, st));
   }
   hipLaunchKernelGGL(kk_router_tail, dim3(d.S), dim3(128), 0, st, a, (float*)(saved + pl.o_rh1), (const float*)(scratch + pl.o_slabs), ks,
-                     (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), probs_out, idx_out, (lb_out && !d.lb_loss) ? lb_out : nullptr,
+                     (float*)(saved + pl.o_rh2), (float*)(saved + pl.o_probs), r.probs_out, r.idx_out, (r.lb_out && !d.lb_loss) ? r.lb_out : nullptr,
                      (float*)(saved + pl.o_psm), (int*)(saved + pl.o_mode), (float*)(saved + pl.o_lse));
   AVMOE_CHECK_LAUNCH("router");
   const float* dense = (const float*)(saved + (k_mix ? pl.o_psm : pl.o_probs));
-  if (aux_out) {                                           // the auxiliary losses -- and the load-balancing loss from the same launch
+  if (r.aux_out) {                                         // the auxiliary losses -- and the load-balancing loss from the same launch
     hipLaunchKernelGGL(kk_router_aux, dim3(1), dim3(256), 0, st, dense, (const float*)(saved + pl.o_lse), d.S, d.E, top_k ? top_k : 1,
-                       (lb_out && d.lb_loss) ? 1 : 0, lb_out, aux_out, load_out, (float*)(saved + pl.o_load), select_bias, select_count);
+                       (r.lb_out && d.lb_loss) ? 1 : 0, r.lb_out, r.aux_out, r.load_out, (float*)(saved + pl.o_load), r.select_bias, r.select_count);
     AVMOE_CHECK_LAUNCH("router_aux");
-  } else if (lb_out && d.lb_loss) {                        // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
-    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, dense, d.S, d.E, lb_out);
+  } else if (r.lb_out && d.lb_loss) {                      // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
+    hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, dense, d.S, d.E, r.lb_out);
     AVMOE_CHECK_LAUNCH("lb_loss");
   }
-  if (select_count && !aux_out) {                          // the balancer's counts without the auxiliary losses: their own one-block launch
-    hipLaunchKernelGGL(kk_router_count, dim3(1), dim3(256), 0, st, dense, d.S, d.E, top_k ? top_k : 1, select_bias, select_count);
+  if (r.select_count && !r.aux_out) {                      // the balancer's counts without the auxiliary losses: their own one-block launch
+    hipLaunchKernelGGL(kk_router_count, dim3(1), dim3(256), 0, st, dense, d.S, d.E, top_k ? top_k : 1, r.select_bias, r.select_count);
     AVMOE_CHECK_LAUNCH("router_count");
   }
   return OK;
+}
+int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const RouteCall& r, hipStream_t st) {
+  AVMOE_TRY(router_launch(pl, saved, scratch, prm, r, st));          // (its profiler scope ends with it: the stage's launches are their own)
+  return route_stage(pl, saved, scratch, r, st);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #pragma once
 #include "moe_plan.h"
 #include <hip/hip_runtime.h>
+#include <variant>
 
 namespace avmoe {
 
@@ -36,17 +37,37 @@ int k_softmax_rows(int bf16_out, const float* in, long rows, int n, int ld_in, v
 int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, int src /*0 y, 1 x*/,
                hipStream_t st);
 // ---- forward: router --------------------------------------------------------------------------
+// The words of `saved + o_mode` (moe_plan.h: 64 ints).  Block 0 of every router forward writes the first six, the selection stage behind it
+// the words per expert; the router backward reads them -- it takes the forward's selection from here, never from live tensors.
+constexpr int MODE_K = 0, MODE_RENORM = 1;                  // the k of the mixture weights in `probs` (0: dense, `psm` unused; E: dense behind a multiplier or a stage), their renorm
+constexpr int MODE_SELECT = 2;                              // what the experts were ranked on: 0 = p, or
+constexpr int MODE_SELECT_BIASED = 1, MODE_SELECT_SINKHORN = 2;   // p + b (avmoe_moe_forward_bias) ; p v (avmoe_moe_forward_sinkhorn) -- the bits of b / v in MODE_SELECT_WORDS
+constexpr int MODE_CHOICE_C = 3, MODE_CHOICE_RENORM = 4;    // expert choice: the capacity (0: off), its renorm
+constexpr int MODE_SK_ITERS = 5;                            // Sinkhorn: the rounds (0: off)
+constexpr int MODE_SELECT_WORDS = 16;                       // [16, 16 + E): the bits of the selection bias, or of the Sinkhorn column scale, the forward used
+constexpr int MODE_CHOICE_THR = 32, MODE_CHOICE_LAST = 48;  // [32, 32 + E) / [48, 48 + E): expert choice, the bits of the thresholds T_e / the last frames taken L_e
+
 struct RouterChoice { int capacity, renorm; int32_t* choice; };     // avmoe_moe_forward_choice: c in [1, S], renorm, (S) bitmask out or NULL
 struct RouterSinkhorn { int iters; int32_t* choice; int32_t* count; };   // avmoe_moe_forward_sinkhorn: n in [1, 64], (S) bitmask out or NULL, (E) counts out or NULL
+struct RouterCapacity { int capacity, policy; float* cap_scale; int32_t* kept; int32_t* demand; int32_t* kept_count; };   // avmoe_moe_forward_capacity: c in [1, S], 0 "order" / 1 "priority", (S, E) multiplier out, (S) bitmask / (E) / (E) counts out or NULL
+// How one call routes: every field's default means "off", a call site names what it sets.  route_check (capi.cpp) holds the ranges.
+struct RouteCall {
+  const float* noise = nullptr;           // (S, E) added to the router's logits
+  int top_k = 0;                          // > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture
+  int renorm = 1;                         // the kept weights renormalised (k = 0: it only lands in the mode word of `saved`, unread -- a dense site records 1)
+  float* probs_out = nullptr; int64_t* idx_out = nullptr; float* lb_out = nullptr;      // (S, E) the dense softmax, (S) its argmax, the load-balancing loss (0 for a site without it)
+  float *aux_out = nullptr, *load_out = nullptr;      // [z, balance], the router auxiliary losses (avmoe_moe_forward_aux), (E) the share of the routing slots per expert (read with aux_out only)
+  const float* mix_scale = nullptr;       // (S, E) multiplier on the mixture weights behind top-k (avmoe_moe_forward_reg / _backward_reg: stochastic depth, expert dropout)
+  const float* select_bias = nullptr; float* select_count = nullptr;      // (E) bias on the top-k selection alone, (E) selection counts added to (avmoe_moe_forward_bias: aux-loss-free balancing)
+  // The stage behind the router, a variant (two at once cannot be written down) -- none; expert choice: each expert takes its `capacity` frames (top_k 0,
+  // no selection bias); Sinkhorn-balanced top-k: the experts are ranked on p v, v from `iters` rounds on the call's softmax (top_k in [1, E), no selection bias);
+  // expert capacity: every expert keeps at most `capacity` of the frames that selected it (top_k in [1, E); the router runs as without it, the dropped weights are zeroed)
+  std::variant<std::monostate, RouterChoice, RouterSinkhorn, RouterCapacity> stage;
+};
 int k_onehot_noise(float* noise, int S, int E, int hot, float value, hipStream_t st);      // sub-ops of the C ABI (fwd_kernels.hip)
 int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float* rowb, const float* colb, hipStream_t st);
-int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const float* noise, float* probs_out,
-             int64_t* idx_out, float* lb_out, hipStream_t st, int top_k, int renorm,            // top_k 0: the dense mixture
-             float* aux_out, float* load_out,                                                    // aux_out: [z, balance] (avmoe_moe_forward_aux)
-             const float* mix_scale,                                                             // (S, E) multiplier on the mixture weights (avmoe_moe_forward_reg) or NULL
-             const float* select_bias, float* select_count,                                      // (E) selection bias / (E) counts added to (avmoe_moe_forward_bias), NULL each
-             const RouterChoice* choice,                                                         // expert-choice gating (avmoe_moe_forward_choice): the mode words and the dense-with-multiplier form; NULL: off
-             const RouterSinkhorn* sinkhorn);                                                    // Sinkhorn-balanced top-k (avmoe_moe_forward_sinkhorn): the mode words and that form too; NULL: off
+// the router, then the call's selection stage (k_expert_choice ; k_sk_scale, k_sk_apply ; k_cap_mask, k_cap_select, k_cap_apply) on the same stream
+int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const RouteCall& r, hipStream_t st);
 // expert-choice gating (expert_choice.hip): per column e of p (S, E) the threshold T_e = its c-th largest value and L_e = the last frame taken
 // among the ties (one block per expert), then per frame the mask, the weights w (times mix) and the bitmask word.  thr_bits / last: E words
 // each, written by the first launch and read by the second; w / choice: NULL = not written.  Two launches, no host scalar that changes.
@@ -64,7 +85,6 @@ int k_sk_apply(const float* p, long S, int E, int top_k, int renorm, const float
 // (policy 0 "order": the c-th selecting frame; policy 1 "priority": the c-th largest p among the selecting frames and the last tied frame
 // taken), demand and kept_count (E words each, or NULL); k_cap_apply, one thread per frame, sets the dropped entries of w to +0.0f and writes
 // cap_scale (S, E) = keep ? mix (or 1) : 0 and the bitmask of the kept pairs (w / cap_scale / kept: NULL = not written; kept may be mask).
-struct RouterCapacity { int capacity, policy; float* cap_scale; int32_t* kept; int32_t* demand; int32_t* kept_count; };   // avmoe_moe_forward_capacity
 int k_cap_mask(const float* p, long S, int E, int top_k, const float* bias, int32_t* mask, hipStream_t st);
 int k_cap_select(const float* p, const int32_t* mask, long S, int E, int capacity, int policy, int* thr_bits, int* last, int32_t* demand,
                  int32_t* kept_count, hipStream_t st);

@@ -31,10 +31,8 @@ avmoe_moe_ptrs with_unit_gates(const Plan& pl, const avmoe_moe_ptrs& prm, char* 
   return p;
 }
 
-int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, const float* noise, void* out,
-                float* probs_out, int64_t* idx_out, float* lb_out, char* sv, char* sc, hipStream_t st, int top_k, int renorm,
-                float* aux_out, float* load_out, const float* mix_scale, const float* select_bias, float* select_count,
-                const RouterChoice* choice, const RouterSinkhorn* sinkhorn, const RouterCapacity* capacity) {
+int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm_in, void* out, const RouteCall& route, char* sv, char* sc,
+                hipStream_t st) {
   const Dims& d = pl.d;
   // Cumulative BatchNorm average (bn_momentum < 0): the statistic kernels form 1 / (counter + 1) on the device, so every counter must be there
   const bool cumul = d.use_bn && d.training && d.bn_momentum < 0.f;
@@ -180,44 +178,7 @@ int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_pt
     AVMOE_TRY(down_gemm(Xs.flat(d.S), Z.flat(d.S)));                        // Zx = X Wt^T
   }
   // ---- router (its input: the token means of X -- after the statistics above) ----------------------
-  AVMOE_TRY(k_router(pl, sv, sc, prm, noise, probs_out, idx_out, lb_out, st, top_k, renorm, aux_out, load_out, mix_scale, select_bias, select_count, choice, sinkhorn));
-  if (choice) {                                            // expert-choice gating: the selection words into `mode`, the weights into `probs`
-    ProfScope ps_("k_expert_choice", 0.0, 0.0, st);
-    int* mode = (int*)(sv + pl.o_mode);
-    AVMOE_TRY(k_expert_choice((const float*)(sv + pl.o_psm), d.S, d.E, choice->capacity, choice->renorm, mix_scale, (float*)(sv + pl.o_probs),
-                              choice->choice, mode + 32, mode + 48, st));
-  }
-  if (sinkhorn) {                                          // Sinkhorn-balanced top-k: the column scale into `mode`, the weights of its selection into `probs`
-    int* mode = (int*)(sv + pl.o_mode);
-    const float* p = (const float*)(sv + pl.o_psm);
-    {
-      ProfScope ps_("k_sk_scale", 0.0, 0.0, st);
-      AVMOE_TRY(k_sk_scale(p, d.S, d.E, sinkhorn->iters, mode + 16, sinkhorn->count, st));
-    }
-    {
-      ProfScope ps_("k_sk_apply", 0.0, 0.0, st);
-      AVMOE_TRY(k_sk_apply(p, d.S, d.E, top_k, renorm, mix_scale, mode + 16, (float*)(sv + pl.o_probs), sinkhorn->choice, sinkhorn->count, st));
-    }
-  }
-  if (capacity) {                                          // expert capacity behind top-k: the dropped entries of `probs` set to 0, the multiplier for the backward out
-    // (the selection words and the words per expert live in `rbw`, a buffer of the router backward: S + 2 MAX_E words of its S (E + 160 + 2 C))
-    int32_t* mask = (int32_t*)(sc + pl.o_rbw);
-    int* tl = (int*)mask + d.S;
-    const float* p = (const float*)(sv + pl.o_psm);
-    {
-      ProfScope ps_("k_cap_mask", 0.0, 0.0, st);
-      AVMOE_TRY(k_cap_mask(p, d.S, d.E, top_k, select_bias, mask, st));
-    }
-    {
-      ProfScope ps_("k_cap_select", 0.0, 0.0, st);
-      AVMOE_TRY(k_cap_select(p, mask, d.S, d.E, capacity->capacity, capacity->policy, tl, tl + MAX_E, capacity->demand, capacity->kept_count, st));
-    }
-    {
-      ProfScope ps_("k_cap_apply", 0.0, 0.0, st);
-      AVMOE_TRY(k_cap_apply(p, mask, d.S, d.E, capacity->policy, tl, tl + MAX_E, mix_scale, (float*)(sv + pl.o_probs), capacity->cap_scale,
-                            capacity->kept, st));
-    }
-  }
+  AVMOE_TRY(k_router(pl, sv, sc, prm, route, st));        // (and the selection stage behind it, when the call has one)
   if (d.KL > 0 && !d.fuse_l2) {                            // L2[s] = X[s] T[s]^T   (fused: per-group partial sums came out of the down projection; pre_small adds them into L2)
     GemmArgs g = base();
     AVMOE_TRY(g.product(vw::L2(pl, sv), Xs, Text.rows_at(0, d.KL).T()));
@@ -337,7 +298,8 @@ int expert_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe
       q.e[o].bn1_nbt = q.e[o].bn2_nbt = dump_n;
     }
   }
-  return moe_forward(pl, X, Y, q, noise, out, nullptr, nullptr, nullptr, sv, sc, st, 0, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  RouteCall route; route.noise = noise;                    // the dense mixture on the one-hot softmax, nothing reported
+  return moe_forward(pl, X, Y, q, out, route, sv, sc, st);
 }
 
 // The remap MATERIALISED (the product path folds it away): Yt = conv_adapter(Y) (S, N, Cy), then

@@ -211,7 +211,7 @@ inline int ro_chunks(const Dims& d) { return (d.M + RO_ROWS - 1) / RO_ROWS; }
   X(ro, 1, 4, (size_t)d.S * ((2 + ro_chunks(d)) * (size_t)d.Cy + d.M + 1))   /* router-only backward: u | ybar | ybar chunk partials | dWc rows | sum u, per frame */ \
   /* ---- top-k gating (appended: the indices of the buffers above stay) ---- */                                           \
   X(psm, 0, 4, (size_t)d.S * d.E)                   /* top-k mode: the dense softmax (probs then holds the mixture weights) */ \
-  X(mode, 0, 4, 64)                                 /* [0] = k (0: dense mixture), [1] = renorm, [2] = 1: a selection bias was used, [16, 16 + E) = its bits; 2: Sinkhorn-balanced, [16, 16 + E) = the bits of v, [5] = its rounds; [3] = expert-choice capacity (0: off), [4] = its renorm, [32, 32 + E) / [48, 48 + E) = its T_e bits / L_e; written by every router forward */ \
+  X(mode, 0, 4, 64)                                 /* how the forward routed, for the router backward: the words by name in kernels.h (MODE_*); written by every router forward */ \
   /* ---- router auxiliary losses (appended: the offsets of the buffers above stay) ---- */                                \
   X(lse, 0, 4, (size_t)d.S)                         /* log-sum-exp of every frame's router logits; written by every router forward */ \
   X(load, 0, 4, (size_t)MAX_E)                      /* share of the routing slots per expert; written by avmoe_moe_forward_aux */

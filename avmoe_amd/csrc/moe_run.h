@@ -49,18 +49,9 @@ int mha_frames_forward(const Plan& pl, const void* X, const avmoe_expert_ptrs& e
 int mha_frames_backward(const Plan& pl, const void* X, const avmoe_expert_ptrs& ep, const avmoe_expert_ptrs& eg, int slot, const void* dxr,
                         char* saved, char* scratch, float* slabs, size_t slab_cap, void* dX, hipStream_t st);
 
-// Every caller states every option (no defaulted parameters: one that forgets an argument must not compile).
-// top_k > 0 (< E): top-k gating of the mixture (avmoe_moe_forward_topk); 0 = the dense mixture (renorm then only lands in the mode word of `saved`, unread for k = 0)
-// aux_out: [z, balance], the router auxiliary losses (avmoe_moe_forward_aux), load_out (E) with them; NULL: not formed
-// mix_scale: (S, E) multiplier on the mixture weights behind top-k (avmoe_moe_forward_reg / _backward_reg: stochastic depth, expert dropout); NULL: off
-// choice: expert-choice gating (avmoe_moe_forward_choice: each expert takes its `capacity` frames; top_k must be 0, no selection bias); NULL: off
-// sinkhorn: Sinkhorn-balanced top-k (avmoe_moe_forward_sinkhorn: the experts are ranked on p v, v from `iters` rounds on the call's softmax; top_k in [1, E), no selection bias, no choice); NULL: off
-// capacity: expert capacity behind top-k (avmoe_moe_forward_capacity: every expert keeps at most `capacity` of the frames that selected it; top_k in [1, E), no choice, no sinkhorn; the router runs as without it, the three launches of router_capacity.hip zero the dropped weights); NULL: off
-// select_bias: (E) bias on the top-k selection alone, select_count: (E) selection counts added to (avmoe_moe_forward_bias: aux-loss-free balancing); NULL: off
-int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const float* noise, void* out,
-                float* probs_out, int64_t* idx_out, float* lb_out, char* saved, char* scratch, hipStream_t st, int top_k,
-                int renorm, float* aux_out, float* load_out, const float* mix_scale, const float* select_bias, float* select_count,
-                const RouterChoice* choice, const RouterSinkhorn* sinkhorn, const RouterCapacity* capacity = nullptr);
+// route: how the call routes (kernels.h: RouteCall -- every option off by default, a caller names what it sets)
+int moe_forward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, void* out, const RouteCall& route, char* saved,
+                char* scratch, hipStream_t st);
 
 // aux_grad: [g_z, g_balance] after a forward with aux_out (avmoe_moe_backward_aux), or NULL
 int moe_backward(const Plan& pl, const void* X, const void* Y, const avmoe_moe_ptrs& prm, const void* dOut, const float* lb_grad,

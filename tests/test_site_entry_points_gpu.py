@@ -46,9 +46,14 @@ class Site(MoeRun):
         self.idx = torch.full((self.S,), -7, device=DEV, dtype=torch.int64)
         self.lb = torch.full((1,), sentinel, device=DEV)
 
-    def forward_by(self, entry, k=0, renorm=1):
-        """one forward from a fresh state -> (status, {out, probs, idx, lb, saved, buffers} as raw bytes on the CPU)"""
+    def forward_by(self, entry, k=0, renorm=1, policy=0, iters=1, cap_scale=True):
+        """one forward from a fresh state -> (status, {out, probs, idx, lb, saved, buffers} as raw bytes on the CPU).  The newer entry
+        points run with their own options off (mix_scale, select_bias, select_count, aux and load NULL); "capacity" with a capacity of S
+        frames under `policy`, its cap_scale (S, E) and kept (S) left on the object (cap_scale = False: passed as NULL); "sinkhorn" with
+        `iters` rounds"""
         self.fresh()
+        self.cap_scale = torch.full((self.S, self.cfg.E), float("nan"), device=DEV)
+        self.kept = torch.full((self.S,), -7, device=DEV, dtype=torch.int32)
         head = (C.byref(self.desc), self.X.data_ptr(), self.Y.data_ptr(), C.byref(self.ptrs), _ptr(self.noise))
         outs = (self.out.data_ptr(), self.probs.data_ptr(), self.idx.data_ptr(), self.lb.data_ptr())
         ws = (self.saved.data_ptr(), self.scratch.data_ptr(), self.stream)
@@ -56,8 +61,18 @@ class Site(MoeRun):
             st = self.L.avmoe_moe_forward(*head, *outs, *ws)
         elif entry == "topk":
             st = self.L.avmoe_moe_forward_topk(*head, k, renorm, *outs, *ws)
-        else:
+        elif entry == "aux":
             st = self.L.avmoe_moe_forward_aux(*head, k, renorm, *outs, None, None, *ws)
+        elif entry == "reg":
+            st = self.L.avmoe_moe_forward_reg(*head, k, renorm, None, *outs, None, None, *ws)
+        elif entry == "bias":
+            st = self.L.avmoe_moe_forward_bias(*head, k, renorm, None, None, None, *outs, None, None, *ws)
+        elif entry == "capacity":
+            st = self.L.avmoe_moe_forward_capacity(*head, k, renorm, None, None, None, self.S, policy, _ptr(self.cap_scale if cap_scale else None),
+                                                   self.kept.data_ptr(), None, None, *outs, None, None, *ws)
+        else:
+            assert entry == "sinkhorn"
+            st = self.L.avmoe_moe_forward_sinkhorn(*head, k, renorm, iters, None, *outs, None, None, None, None, *ws)
         torch.cuda.synchronize()
         assert self.guards_intact()
         res = dict(out=self.out, probs=self.probs, idx=self.idx, lb=self.lb, saved=self.saved,
@@ -113,6 +128,10 @@ def test_dense_forward_is_one_forward(site):
     assert not torch.isnan(site.out.float()).any()
     _same(plain, topk, "forward vs forward_topk(k = E)")
     _same(plain, aux, "forward vs forward_aux(k = 0)")
+    for entry in ("reg", "bias"):                                      # ... == _reg(mix NULL) == _bias(mix, bias, count NULL)
+        st, got = site.forward_by(entry, 0, 1)
+        assert st == 0
+        _same(aux, got, f"forward_aux vs forward_{entry} (k = 0, every option NULL)")
 
 
 @pytest.mark.parametrize("renorm", [0, 1])
@@ -124,6 +143,20 @@ def test_top1_forward_is_one_forward(site, renorm):
     _same(topk, aux, f"forward_topk vs forward_aux (k = 1, renorm = {renorm})")
     _, dense = site.forward_by("plain")
     assert not torch.equal(dense["out"], topk["out"]) and torch.equal(dense["probs"], topk["probs"])
+    for entry in ("reg", "bias"):                                      # ... == _reg(mix NULL) == _bias(mix, bias, count NULL)
+        st, got = site.forward_by(entry, 1, renorm)
+        assert st == 0
+        _same(aux, got, f"forward_aux vs forward_{entry} (k = 1, renorm = {renorm}, every option NULL)")
+    # ... == _capacity(capacity = S: nothing is dropped) under either policy.  Capacity works in `scratch`, which is not compared; its own
+    # outputs: every kept word is the frame's one selected expert (k = 1: the first maximum of the softmax, idx), cap_scale its one-hot
+    want_kept = (1 << site.idx).to(torch.int32)
+    want_scale = torch.nn.functional.one_hot(site.idx, site.cfg.E).float()
+    for policy in (0, 1):
+        st, got = site.forward_by("capacity", 1, renorm, policy=policy)
+        assert st == 0
+        _same(aux, got, f"forward_aux vs forward_capacity (k = 1, renorm = {renorm}, capacity = S, policy {policy})")
+        assert torch.equal(site.kept, want_kept), policy
+        assert torch.equal(site.cap_scale, want_scale), policy
 
 
 def test_whole_backward_is_one_backward(site):
@@ -147,13 +180,16 @@ def test_sectioned_backward_is_one_backward(site):
 
 
 def test_refusals_keep_their_status_and_launch_nothing(site):
-    """_topk(k = 0): BAD_ARG ; _part(dOut = NULL): BAD_ARG ; _ex(dOut = NULL, parts = 1): UNSUPPORTED -- every output keeps its sentinel"""
-    st, res = site.forward_by("topk", 0, 1)
-    assert st == BAD_ARG
-    assert bool(torch.isnan(site.out.float()).all()) and bool(torch.isnan(site.probs).all()) and bool(torch.isnan(site.lb).all())
-    assert bool((site.idx == -7).all()) and bool((res["saved"] == 0xFF).all()) and bool((site.scratch == 0xFF).all())
-    for k, v in site.bufs.items():
-        assert torch.equal(v, site.buffers[k]), k
+    """_topk(k = 0), _sinkhorn(iters = 0), _capacity(cap_scale = NULL): BAD_ARG ; _part(dOut = NULL): BAD_ARG ; _ex(dOut = NULL, parts = 1):
+    UNSUPPORTED -- every output keeps its sentinel"""
+    for entry, k, opts in (("topk", 0, {}), ("sinkhorn", 1, dict(iters=0)), ("capacity", 1, dict(cap_scale=False))):
+        st, res = site.forward_by(entry, k, 1, **opts)
+        assert st == BAD_ARG, entry
+        assert bool(torch.isnan(site.out.float()).all()) and bool(torch.isnan(site.probs).all()) and bool(torch.isnan(site.lb).all()), entry
+        assert bool((site.idx == -7).all()) and bool((res["saved"] == 0xFF).all()) and bool((site.scratch == 0xFF).all()), entry
+        assert bool(torch.isnan(site.cap_scale).all()) and bool((site.kept == -7).all()), entry
+        for b, v in site.bufs.items():
+            assert torch.equal(v, site.buffers[b]), (entry, b)
     for entry, parts, want in (("part", 0, BAD_ARG), ("ex", 1, UNSUPPORTED)):
         sts, g = site.backward_by(entry, (parts,), dO=False, sentinel=float("nan"))
         assert sts == [want], (entry, sts)
