@@ -708,11 +708,12 @@ int launch_gemm_stream(const GemmArgs& a_in, hipStream_t st) {
 #endif
 #define STREAM_CASE(COND, KS_, KS2_, TPW_, NW_, BM_, PERCU_, A2MN_, ACCOK_, NAME)   \
   if ((COND) && a2mn == A2MN_ && ks <= KS_ && ks2 <= KS2_ && (ks2 > 0) == (KS2_ > 0) && tiles <= TPW_ * NW_) {   \
+    if (!ACCOK_ && a.accumulate) return 1;     /* (before the profiler scope: a form that steps aside leaves no record) */ \
     s.tps = cdiv(a.M, BM_); s.ntiles = s.tps * a.nb1;                               \
     ProfScope ps(NAME, (long)a.M * a.nb1, abytes, flops, st);                       \
     if constexpr (ACCOK_) {                                                         \
       if (a.accumulate) return launch_inst<KS_, KS2_, TPW_, NW_, BM_, A2MN_, true, stream_minw(NW_, PERCU_)>(s, a.nb2, PERCU_, st);   \
-    } else if (a.accumulate) return 1;                                              \
+    }                                                                               \
     return launch_inst<KS_, KS2_, TPW_, NW_, BM_, A2MN_, false, stream_minw(NW_, PERCU_)>(s, a.nb2, PERCU_, st);   \
   }
   // narrow channel groups (C / g <= 64: the first stages of Swin / HTS-AT): long row tiles, few waves -- the wide configurations
