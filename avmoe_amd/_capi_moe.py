@@ -258,6 +258,13 @@ def declare(L):
         L.avmoe_moe_forward_capacity.argtypes = head + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 13
         L.avmoe_router_capacity.restype = C.c_int
         L.avmoe_router_capacity.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+    # top-p routing (found by symbol: the site forward where each frame takes the fewest experts reaching the mass P, and the kernels as a sub-op)
+    L.avmoe_site_top_p = bool(L.avmoe_site_reg and hasattr(L, "avmoe_moe_forward_top_p") and hasattr(L, "avmoe_router_top_p"))
+    if L.avmoe_site_top_p:
+        L.avmoe_moe_forward_top_p.restype = C.c_int
+        L.avmoe_moe_forward_top_p.argtypes = head + [C.c_float] + [C.c_int32] * 3 + [C.c_void_p] * 13
+        L.avmoe_router_top_p.restype = C.c_int
+        L.avmoe_router_top_p.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6
     if hasattr(L, "avmoe_moe_backward_dx_dy"):       # (ABI 10; a development A/B may load an older library through AVMOE_LIB, with AVMOE_NO_FUSED_DX=1)
         L.avmoe_moe_backward_dx_dy.restype = C.c_int
         L.avmoe_moe_backward_dx_dy.argtypes = [C.POINTER(MoeDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MoeDesc), C.c_void_p, C.c_void_p,

@@ -183,6 +183,11 @@ def router_capacity(f, k, S, E):
 _CAPACITY_POLICIES = {"order": 0, "priority": 1}
 
 
+# `site.last_top_p`: of the last top-p forward, the (S) int32 bitmask of the selection (bit e: frame s took expert e), the number of frames that
+# took each expert (E) int32, and the number of frames served by j experts (E + 1) int32 -- device tensors
+TopPReport = namedtuple("TopPReport", ["choice", "count", "khist"])
+
+
 def _draw_mix(module, L, S, E, p, q, dev, stream):
     """The (S, E) multiplier of one training-mode call, drawn on `stream` by avmoe_mix_drop_draw into the site's cached tensor.  The site
     owns the generator's state block {seed, calls} on the device: nothing the host writes changes between two calls, so a captured
@@ -201,14 +206,14 @@ def _draw_mix(module, L, S, E, p, q, dev, stream):
     return buf
 
 
-_Routing = namedtuple("_Routing", ["choice_k", "sk_iters", "cap_f"])      # what one call does about each selection stage; None: off
+_Routing = namedtuple("_Routing", ["choice_k", "sk_iters", "cap_f", "top_p"])      # what one call does about each selection stage; None: off
 
 
 def _routing_of(module):
     """The selection stage of the call `module` is about to make, from the site's settings alone (a contradiction in them does not depend on
     the call: reported first, in eval mode too), the eval-mode rules resolved: without `router_sinkhorn_eval` an eval call routes greedily
     (S-BASE: the plain top-k call), and `router_capacity_eval_factor` stands in for the factor (None: an evaluation drops nothing, it
-    should not depend on the batch)."""
+    should not depend on the batch).  Top-p is per frame: the same call in training and eval mode."""
     E = module.num_multimodal_experts + module.num_singlemodal_experts
     top_k, biased = module.router_top_k, module.router_select_bias is not None or module.router_select_count is not None
     choice_k, sk_iters, cap_f = module.router_expert_choice, module.router_sinkhorn, module.router_capacity_factor
@@ -238,10 +243,30 @@ def _routing_of(module):
                              "selection, not on one balanced within the call")
         if not getattr(capi.lib(), "avmoe_site_capacity", False):
             raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_capacity / avmoe_router_capacity: it serves no expert capacity")
+    top_p = module.router_top_p
+    if top_p is not None:
+        if choice_k is not None:
+            raise ValueError("router_top_p does not combine with router_expert_choice: there each expert picks its frames, here each frame "
+                             "picks as many experts as reach the mass p")
+        if sk_iters is not None:
+            raise ValueError("router_top_p does not combine with router_sinkhorn: Sinkhorn balances a selection of exactly k experts per frame, "
+                             "top-p lets the number of experts vary")
+        if cap_f is not None:
+            raise ValueError("router_top_p does not combine with router_capacity_factor: the budget c = ceil(f k S / E) needs a fixed number "
+                             "of experts per frame")
+        if biased:
+            raise ValueError("router_top_p does not combine with router_select_bias / router_select_count (a RouterBiasBalancer): a bias on "
+                             "the ranking would change which probabilities the running mass adds up")
+        if not 1 <= module.router_top_p_min_k <= (top_k if (top_k is not None and 1 <= top_k < E) else E):
+            raise ValueError(f"router_top_p_min_k {module.router_top_p_min_k} must lie in [1, k_max], k_max = router_top_k in [1, {E}) or else {E}")
+        if E < 2:
+            raise ValueError("router_top_p needs at least two experts")
+        if not getattr(capi.lib(), "avmoe_site_top_p", False):
+            raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_top_p / avmoe_router_top_p: it serves no top-p routing")
     if not module.training:
         sk_iters = sk_iters if module.router_sinkhorn_eval else None
         cap_f = module.router_capacity_eval_factor if cap_f is not None else None
-    return _Routing(choice_k, sk_iters, cap_f)
+    return _Routing(choice_k, sk_iters, cap_f, top_p)
 
 
 def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=None, stream=None):
@@ -251,13 +276,14 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     or, with `router_expert_choice` set, one avmoe_moe_forward_choice call (which takes the multiplier too), in training and eval mode alike;
     or, with `router_sinkhorn` set, one avmoe_moe_forward_sinkhorn call (which takes the multiplier too);
     or, with `router_capacity_factor` set, one avmoe_moe_forward_capacity call (which takes the multiplier, the selection bias and the
-    counts too) -- the last two in eval mode by the rules of _routing_of, else the call the site makes without them.
+    counts too) -- the last two in eval mode by the rules of _routing_of, else the call the site makes without them;
+    or, with `router_top_p` set, one avmoe_moe_forward_top_p call (which takes the multiplier too), in training and eval mode alike.
     Returns (out, probs, idx, lb, state, aux) with state = what the backward needs and aux = None or ((2,) [z, balance], load (E,)):
     the router auxiliary losses of a site with `router_aux` on.
     add_to: a contiguous tensor like X that receives `+= adapter(X, Y)` in place (avmoe_moe_desc.accumulate_out) and is
     returned as `out`.  shared_gpu: True = another stream's kernels may run beside this call (AdapterPair); None = _shared_gpu_of.
     stream: the handle (int) of the CURRENT stream when the caller already has it (AdapterPair), else looked up."""
-    choice_k, sk_iters, cap_f = _routing_of(module)
+    choice_k, sk_iters, cap_f, top_p = _routing_of(module)
     if not (X.is_cuda and Y.is_cuda):
         raise capi.AvmoeError("avmoe_amd runs on MI355X only: tensors must live on a GPU (no CPU fallback)")
     if stream is None:
@@ -317,6 +343,12 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         cap_rep = CapacityReport(cap_c, torch.empty(S, device=X.device, dtype=torch.int32), torch.empty(E, device=X.device, dtype=torch.int32),
                                  torch.empty(E, device=X.device, dtype=torch.int32))
     module.__dict__["_last_capacity"] = cap_rep
+    # top-p routing (include/avmoe.h at avmoe_moe_forward_top_p): k_max is the site's top_k, the reports are this call's own tensors
+    tp_rep = None
+    if top_p is not None:
+        tp_rep = TopPReport(torch.empty(S, device=X.device, dtype=torch.int32), torch.empty(E, device=X.device, dtype=torch.int32),
+                            torch.empty(E + 1, device=X.device, dtype=torch.int32))
+    module.__dict__["_last_top_p"] = tp_rep
     sizes = _ws_sizes(module, L, desc)
     saved = torch.empty(sizes[0], dtype=torch.uint8, device=X.device)
     scratch = _scratch(X.device, sizes[1], stream=stream)
@@ -347,6 +379,9 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
         fn, args = "avmoe_moe_forward_capacity", (k, renorm, _ptr(mix), _ptr(sel_bias), _ptr(sel_count), cap_c,
                                                   _CAPACITY_POLICIES[module.router_capacity_policy], cap_scale.data_ptr(), cap_rep.kept.data_ptr(),
                                                   cap_rep.demand.data_ptr(), cap_rep.kept_count.data_ptr(), *outs)
+    elif top_p is not None:                              # top-p: k_max = the site's k, or E (and the multiplier, when one was drawn)
+        fn, args = "avmoe_moe_forward_top_p", (top_p, module.router_top_p_min_k, k if k else E, int(module.router_top_k_renorm), _ptr(mix), *outs,
+                                               tp_rep.choice.data_ptr(), tp_rep.count.data_ptr(), tp_rep.khist.data_ptr())
     elif biased:                                         # the selection bias / counts (and the multiplier, when one was drawn)
         fn, args = "avmoe_moe_forward_bias", (k, renorm, _ptr(mix), _ptr(sel_bias), _ptr(sel_count), *outs)
     elif mix is not None:                                # the multiplier on the mixture weights, drawn just above on the same stream
@@ -364,6 +399,9 @@ def _site_forward(module, X, Y, noise, names, params, add_to=None, shared_gpu=No
     if cap_rep is not None and module.training:           # avmoe_amd.train.CapacityMeter: two adds on this stream, no sync
         for meter in module.__dict__.get("_capacity_meters", ()):
             meter.update(module, cap_rep)
+    if tp_rep is not None:                                # avmoe_amd.train.TopPMeter: two adds on this stream, no sync
+        for meter in module.__dict__.get("_top_p_meters", ()):
+            meter.update(module, tp_rep)
     if module.__dict__.get("_keep_saved"):                # avmoe_amd.debug.keep_saved: checker-side view of the last call's workspace
         module.__dict__["_last_saved"] = (desc, saved)
     if cap_scale is not None:                            # the backward's multiplier is this call's own cap_scale (it holds the draw too): no draw number
@@ -576,6 +614,9 @@ class _PairFunction(torch.autograd.Function):
             if site_b.last_sinkhorn is not None:
                 for t_ in site_b.last_sinkhorn:
                     t_.record_stream(main)
+            if site_b.last_top_p is not None:
+                for t_ in site_b.last_top_p:
+                    t_.record_stream(main)
             if site_b.last_capacity is not None:         # (and the backward's multiplier of such a call)
                 for t_ in site_b.last_capacity[1:] + (st_b[0][3][0],):
                     t_.record_stream(main)
@@ -780,6 +821,9 @@ class MoEAdapter(nn.Module):
         self.router_sinkhorn_eval = getattr(opt, "router_sinkhorn_eval", False)
         # expert capacity behind top-k (include/avmoe.h at avmoe_moe_forward_capacity): overflow pairs dropped within each call.  Plain attributes too.
         self.router_capacity_factor = getattr(opt, "router_capacity_factor", None)
+        # top-p routing (include/avmoe.h at avmoe_moe_forward_top_p): each frame takes the fewest experts that reach the mass p.  Plain attributes too.
+        self.router_top_p = getattr(opt, "router_top_p", None)
+        self.router_top_p_min_k = getattr(opt, "router_top_p_min_k", 1)
         self.router_capacity_policy = getattr(opt, "router_capacity_policy", "order")
         self.router_capacity_eval_factor = getattr(opt, "router_capacity_eval_factor", None)
         # the regularisers of the mixture (include/avmoe.h at avmoe_moe_forward_reg): stochastic depth on the adapter branch and expert
@@ -955,6 +999,43 @@ class MoEAdapter(nn.Module):
         with, the frames each expert took and the bitmask of the selection --; None when it ran without Sinkhorn (or none ran yet)."""
         return self.__dict__.get("_last_sinkhorn")
 
+    @property
+    def router_top_p(self):
+        """None (off), or a real number P in (0, 1]: top-p ("dynamic-k") routing -- every frame takes the fewest of its ranked experts whose
+        probability mass reaches P, at least `router_top_p_min_k` and at most `router_top_k` of them (E when that is unset or not in
+        [1, E)); `router_top_k_renorm` says whether the kept weights are renormalised.  Per frame and independent of the batch: training and
+        eval mode alike, no parameter, no loss weight, no state.  It combines with none of `router_expert_choice`, `router_sinkhorn`,
+        `router_capacity_factor`, `router_select_bias` / `router_select_count` (checked when the site runs)."""
+        return self.__dict__.get("_router_top_p")         # (.get: a module pickled before the setting existed has none)
+
+    @router_top_p.setter
+    def router_top_p(self, p):
+        if p is not None:
+            if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 < float(p) <= 1.0:
+                raise ValueError(f"router_top_p must be None or a number in (0, 1], got {p!r}")
+            p = float(p)
+            if not 0.0 < C.c_float(p).value <= 1.0:       # (the call takes it in fp32)
+                raise ValueError(f"router_top_p must lie in (0, 1] as an fp32 number, got {p!r}")
+        self.__dict__["_router_top_p"] = p
+
+    @property
+    def router_top_p_min_k(self):
+        """The fewest experts a frame takes under `router_top_p` (default 1); at most k_max, checked when the site runs."""
+        return self.__dict__.get("_router_top_p_min_k", 1)
+
+    @router_top_p_min_k.setter
+    def router_top_p_min_k(self, k):
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or int(k) < 1:
+            raise ValueError(f"router_top_p_min_k must be an integer >= 1, got {k!r}")
+        self.__dict__["_router_top_p_min_k"] = int(k)
+
+    @property
+    def last_top_p(self):
+        """TopPReport(choice (S) int32, count (E) int32, khist (E + 1) int32) of the last forward, device tensors -- the bitmask of the
+        selection, the frames each expert took and the number of frames served by j experts --; None when it ran without top-p (or none
+        ran yet)."""
+        return self.__dict__.get("_last_top_p")
+
     @staticmethod
     def _capacity_factor(name, f):
         if f is not None:
@@ -1126,7 +1207,7 @@ class MoEAdapter(nn.Module):
         st = self.__dict__.copy()                                      # per-process bookkeeping does not travel (deepcopy / pickle)
         for k in ("_avmoe_cache", "_last_saved", "_ptrs_cache", "_gptrs_cache", "_ws_sizes", "_last_router_aux", "_mix_state", "_mix_buf",
                   "_mix_last", "_mix_draws", "_last_expert_choice", "_last_sinkhorn", "_mode_off",
-                  "_last_capacity", "_capacity_meters"):
+                  "_last_capacity", "_capacity_meters", "_last_top_p", "_top_p_meters"):
             st.pop(k, None)
         return st
 

@@ -176,6 +176,8 @@ struct RouterBwdArgs {
 // m_e dw_e without it; a frame no expert took gets dp = 0.  The selection has no gradient.
 // MODE_SELECT == MODE_SELECT_SINKHORN (avmoe_moe_forward_sinkhorn): the forward ranked the experts on p v; the selection is recomputed by topk_select_scaled
 // with the words of v the forward left in MODE_SELECT_WORDS, and dp_e is the top-k formula with that mask.  v has no gradient (a stop-gradient).
+// MODE_SELECT == MODE_SELECT_TOP_P (avmoe_moe_forward_top_p): the frame took the smallest ranked prefix reaching P; the selection is recomputed by topp_select
+// with MODE_K = k_max and the words the forward left in MODE_SELECT_WORDS (the bits of P, k_min), and dp_e is the top-k formula with that mask.
 __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const float* probs, const float* dp, const float* rh1,
                                                        const float* rh2, float* rbw, const float* psm, const int* mode) {
   __shared__ float s_dl[MAX_E], s_d2[32], s_pm[MAX_E], s_p[MAX_E];
@@ -216,6 +218,8 @@ __global__ void __launch_bounds__(256) kk_router_bwd_a(RouterBwdArgs a, const fl
         float vs[MAX_E];
         for (int e = 0; e < a.E; ++e) vs[e] = __int_as_float(mode[MODE_SELECT_WORDS + e]);
         m = topk_select_scaled(s_p, vs, a.E, top_k, &kept);
+      } else if (mode[MODE_SELECT] == MODE_SELECT_TOP_P) {      // (uniform over the grid) a top-p forward: the prefix of the ranked experts reaching P
+        m = topp_select(s_p, a.E, __int_as_float(mode[MODE_SELECT_WORDS]), mode[MODE_SELECT_WORDS + 1], top_k, &kept);
       } else if (mode[MODE_SELECT]) {                   // (uniform over the grid) a forward with a selection bias: the values it USED
         float bs[MAX_E];
         for (int e = 0; e < a.E; ++e) bs[e] = __int_as_float(mode[MODE_SELECT_WORDS + e]);

@@ -64,10 +64,11 @@ static int route_check(const char* fn, int k_min, const Dims& d, const RouteCall
   if (sk && (sk->iters < 1 || sk->iters > 64)) { set_last_error("%s: iters %d not in [1, 64]", fn, sk->iters); return ERR_BAD_ARG; }
   if (cap && cap->policy != 0 && cap->policy != 1) { set_last_error("%s: policy %d not in {0, 1}", fn, cap->policy); return ERR_BAD_ARG; }
   if (cap && !cap->cap_scale) { set_last_error("%s: cap_scale is NULL (the backward's multiplier is required)", fn); return ERR_BAD_ARG; }
+  if (const auto* tp = std::get_if<RouterTopP>(&r.stage)) AVMOE_TRY(top_p_check(fn, d.E, tp->p, tp->k_min, tp->k_max));      // (E >= 2, P in (0, 1], 1 <= k_min <= k_max <= E)
   return OK;
 }
 
-// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn / _capacity
+// The one forward behind avmoe_moe_forward / _topk / _aux / _reg / _bias / _choice / _sinkhorn / _capacity / _top_p
 static int site_forward(const char* fn, int k_min, const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, void* out,
                         const RouteCall& route, void* saved, void* scratch, void* stream) {
   Plan pl;
@@ -168,6 +169,15 @@ int avmoe_moe_forward_capacity(const avmoe_moe_desc* desc, const void* X, const 
   r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale; r.select_bias = select_bias; r.select_count = select_count;
   r.stage = RouterCapacity{capacity, policy, cap_scale, kept, demand, kept_count};
   return site_forward("avmoe_moe_forward_capacity", 1, desc, X, Y, params, out, r, saved, scratch, stream);
+}
+
+int avmoe_moe_forward_top_p(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params, const float* noise,
+                            float top_p, int32_t k_min, int32_t k_max, int32_t renorm, const float* mix_scale, void* out, float* probs,
+                            int64_t* idx, float* lb, float* aux, float* load, int32_t* choice, int32_t* count, int32_t* khist, void* saved,
+                            void* scratch, void* stream) {
+  RouteCall r = route_of(noise, 0, renorm, probs, idx, lb); r.aux_out = aux; r.load_out = load; r.mix_scale = mix_scale;
+  r.stage = RouterTopP{top_p, k_min, k_max, choice, count, khist};
+  return site_forward("avmoe_moe_forward_top_p", 0, desc, X, Y, params, out, r, saved, scratch, stream);
 }
 
 int avmoe_moe_backward(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,

@@ -96,6 +96,37 @@ __device__ __forceinline__ unsigned topk_select_scaled(const float* p, const flo
   return m;
 }
 
+// Top-p routing (avmoe_moe_forward_top_p, router_top_p.hip): the frame takes the shortest prefix of its ranked experts whose mass reaches P,
+// at least k_min and at most k_max of them.  The ranks are those of topk_select, taken on ec_key(p) as in topk_select_scaled (a total order
+// on every bit pattern: a permutation of 0 .. E - 1, packed four bits per expert); the running mass c_j = c_(j-1) + p_(j) is ONE fp32
+// addition per rank, in rank order, and k* = the first j with c_j >= P (E when none does).  *kept = the sum of the kept p in expert order,
+// as topk_select forms it: with k_min = k_max = k the bits of plain top-k.  The forward, the auxiliary losses and the router backward call
+// it on the same p, P, k_min, k_max: the same selection.
+__device__ __forceinline__ unsigned topp_select(const float* p, int E, float P, int k_min, int k_max, float* kept) {
+  unsigned long long ranks = 0ull;                 // nibble e: the rank of expert e
+  for (int e = 0; e < E; ++e) {
+    const unsigned qe = ec_key(p[e]);
+    int rank = 0;
+    for (int f = 0; f < E; ++f) { const unsigned qf = ec_key(p[f]); rank += (qf > qe) || (qf == qe && f < e); }
+    ranks |= (unsigned long long)rank << (4 * e);
+  }
+  int ks = E;
+  float c = 0.f;
+  for (int j = 0; j < E; ++j) {                    // the expert of rank j (exactly one)
+    float pj = 0.f;
+    for (int e = 0; e < E; ++e) if ((int)((ranks >> (4 * e)) & 15ull) == j) pj = p[e];
+    c = __fadd_rn(c, pj);                          // (never contracted, never reassociated)
+    if (c >= P) { ks = j + 1; break; }
+  }
+  ks = min(max(ks, k_min), k_max);
+  unsigned m = 0u;
+  float s = 0.f;
+  for (int e = 0; e < E; ++e)
+    if ((int)((ranks >> (4 * e)) & 15ull) < ks) { m |= 1u << e; s += p[e]; }
+  *kept = s;
+  return m;
+}
+
 // element access for the activation / operand type T (float or __bf16)
 template <typename T> __device__ __forceinline__ float ldT(const T* p, long i);
 template <> __device__ __forceinline__ float ldT<float>(const float* p, long i) { return p[i]; }

@@ -798,6 +798,9 @@ struct RouterArgs {
 // a.sk_iters (avmoe_moe_forward_sinkhorn): k_router runs that form too (psm = p, probs = p), and block 0 leaves mode[MODE_K] = k, mode[MODE_RENORM] = renorm
 // -- the caller's, not the form's --, mode[MODE_SELECT] = MODE_SELECT_SINKHORN and mode[MODE_SK_ITERS] = the rounds (0: off).  The two launches of
 // router_sinkhorn.hip behind this one put the bits of v into MODE_SELECT_WORDS and the weights into `probs`.
+// Top-p routing (avmoe_moe_forward_top_p) needs nothing of this kernel: k_router runs the same dense form (psm = p, probs = p), block 0 leaves the words of a
+// dense-with-a-multiplier forward, and k_top_p_apply (router_top_p.hip) behind it on the stream overwrites `probs` and MODE_K, MODE_RENORM, MODE_SELECT and two
+// of the MODE_SELECT_WORDS.
 __global__ void __launch_bounds__(128) kk_router_tail(RouterArgs a, float* rh1, const float* slabs, int ks, float* rh2, float* probs,
                                                       float* probs_out, int64_t* idx_out, float* lb_zero, float* psm, int* mode,
                                                       float* lse) {
@@ -883,9 +886,12 @@ __global__ void __launch_bounds__(256) kk_lb_loss(const float* probs, int S, int
 // bias (avmoe_moe_forward_bias): the selection is the mixture's ACTUAL one, topk_select_biased on p[s] + bias, and load / balance are
 // that selection's.  select_count (E): += the number of frames that selected each expert -- the block sums of integer counts are exact
 // in fp32, one thread adds them in: no atomics.  NULL each: uniform branches not taken, today's instructions.
+// tp_kmax > 0 (avmoe_moe_forward_top_p): the selection is topp_select(p[s], tp_P, tp_kmin, tp_kmax), the mixture's ACTUAL one, and the
+// slots handed out are its own total:  load_e = count_e / sum_e count_e  (the counts added in expert order; integers, exact in fp32).
+// 0: a uniform branch not taken.
 __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float* lse, int S, int E, int kp, int do_lb, float* lb,
                                                      float* aux, float* load_out, float* load_sv, const float* bias,
-                                                     float* select_count) {
+                                                     float* select_count, float tp_P, int tp_kmin, int tp_kmax) {
   __shared__ float red[4];
   __shared__ float s_P[MAX_E], s_ld[MAX_E];
   __shared__ float s_pr[256][MAX_E + 1];                 // one frame's probabilities per thread (+ 1: no bank conflicts)
@@ -906,7 +912,8 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
   for (int s = threadIdx.x; s < S; s += 256) {
     for (int e = 0; e < E; ++e) pr[e] = p[(long)s * E + e];
     float kept;
-    const unsigned m = bias ? topk_select_biased(pr, bias, E, kp, &kept) : topk_select(pr, E, kp, &kept);
+    const unsigned m = tp_kmax ? topp_select(pr, E, tp_P, tp_kmin, tp_kmax, &kept)
+                               : (bias ? topk_select_biased(pr, bias, E, kp, &kept) : topk_select(pr, E, kp, &kept));
 #pragma unroll
     for (int e = 0; e < MAX_E; ++e) cnt[e] += (int)((m >> e) & 1u);
     const float l = lse[s];
@@ -918,12 +925,17 @@ __global__ void __launch_bounds__(256) kk_router_aux(const float* p, const float
     if (e < E) {                                         // (uniform over the block)
       const float c = block_sum256((float)cnt[e], red);
       if (threadIdx.x == 0) {
-        s_ld[e] = c / slots;
+        s_ld[e] = tp_kmax ? c : c / slots;               // (top-p: the count itself, divided by the total below)
         if (select_count) select_count[e] += c;
       }
     }
   zz = block_sum256(zz, red);
   if (threadIdx.x == 0) {
+    if (tp_kmax) {                                         // (uniform) thread 0 wrote s_ld itself
+      float handed = 0.f;
+      for (int e = 0; e < E; ++e) handed += s_ld[e];
+      for (int e = 0; e < E; ++e) s_ld[e] = s_ld[e] / handed;
+    }
     float b = 0.f;
     for (int e = 0; e < E; ++e) {
       b += s_ld[e] * s_P[e];
@@ -960,6 +972,7 @@ __global__ void __launch_bounds__(256) kk_router_count(const float* p, int S, in
 // The selection stage behind the router, and the one home of its workspace slots: it reads the dense softmax in `psm`, leaves the weights of its
 // selection in `probs` and its words per expert in `mode`.  Capacity leaves nothing in `saved` (cap_scale is the backward's multiplier): its
 // selection words (S) and two words per expert borrow the head of `rbw`, a buffer of the router backward -- S + 2 MAX_E of its S (E + 160 + 2 C) words.
+// Top-p borrows the same S words for its bitmask when the caller takes none.
 static int route_stage(const Plan& pl, char* saved, char* scratch, const RouteCall& r, hipStream_t st) {
   const Dims& d = pl.d;
   int* mode = (int*)(saved + pl.o_mode);
@@ -978,6 +991,10 @@ static int route_stage(const Plan& pl, char* saved, char* scratch, const RouteCa
     { ProfScope ps_("k_cap_mask", 0.0, 0.0, st); AVMOE_TRY(k_cap_mask(p, d.S, d.E, r.top_k, r.select_bias, mask, st)); }
     { ProfScope ps_("k_cap_select", 0.0, 0.0, st); AVMOE_TRY(k_cap_select(p, mask, d.S, d.E, cap->capacity, cap->policy, thr, last, cap->demand, cap->kept_count, st)); }
     { ProfScope ps_("k_cap_apply", 0.0, 0.0, st); AVMOE_TRY(k_cap_apply(p, mask, d.S, d.E, cap->policy, thr, last, r.mix_scale, w, cap->cap_scale, cap->kept, st)); }
+  } else if (const auto* tp = std::get_if<RouterTopP>(&r.stage)) {         // the weights of the per-frame prefix into `probs`, the mode words of the backward
+    int32_t* words = tp->choice ? tp->choice : (int32_t*)(scratch + pl.o_rbw);      // (no caller's bitmask: the count launch reads the words from the head of `rbw`)
+    { ProfScope ps_("k_top_p_apply", 0.0, 0.0, st); AVMOE_TRY(k_top_p_apply(p, d.S, d.E, tp->p, tp->k_min, tp->k_max, r.renorm, r.mix_scale, w, words, mode, st)); }
+    if (tp->count || tp->khist) { ProfScope ps_("k_top_p_count", 0.0, 0.0, st); AVMOE_TRY(k_top_p_count(p, words, d.S, d.E, tp->p, tp->k_min, tp->k_max, tp->count, tp->khist, st)); }
   }
   return OK;
 }
@@ -986,6 +1003,7 @@ static int router_launch(const Plan& pl, char* saved, char* scratch, const avmoe
   const Dims& d = pl.d;
   const int top_k = r.top_k;
   const auto *choice = std::get_if<RouterChoice>(&r.stage); const auto *sinkhorn = std::get_if<RouterSinkhorn>(&r.stage);
+  const auto *top_p = std::get_if<RouterTopP>(&r.stage);
   if (!prm.r0_w || !prm.r0_b || !prm.r2_w || !prm.r2_b || !prm.r4_w || !prm.r4_b) {
     set_last_error("moe: router parameters missing"); return ERR_BAD_ARG;
   }
@@ -994,11 +1012,12 @@ static int router_launch(const Plan& pl, char* saved, char* scratch, const avmoe
   // stays in psm -- the mode word then tells the router backward so, which needs no case of its own.  The auxiliary losses keep the caller's k.
   // Expert choice takes that form too, WITHOUT the multiplier: k_expert_choice (route_stage) overwrites `probs` with the weights of its
   // selection, times the multiplier.  Sinkhorn-balanced top-k takes it as well: k_sk_apply overwrites `probs`.  The mode words keep the
-  // caller's k and renorm (RouterArgs::sk_k / sk_renorm), and so do the auxiliary losses below.
-  const bool mix_dense = ((r.mix_scale || choice) && !top_k) || sinkhorn;
+  // caller's k and renorm (RouterArgs::sk_k / sk_renorm), and so do the auxiliary losses below.  Top-p (top_k 0) takes the form of expert choice;
+  // k_top_p_apply overwrites `probs` and, behind kk_router_tail on the stream, the mode words; the auxiliary losses count its selection.
+  const bool mix_dense = ((r.mix_scale || choice || top_p) && !top_k) || sinkhorn;
   const int k_mix = mix_dense ? d.E : top_k;
   RouterArgs a{prm.r0_w, prm.r0_b, prm.r2_w, prm.r2_b, prm.r4_w, prm.r4_b, r.noise, 2 * d.C, d.E, d.S, k_mix, (r.renorm && !mix_dense) ? 1 : 0,
-               (choice || sinkhorn) ? nullptr : r.mix_scale, r.select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0,
+               (choice || sinkhorn || top_p) ? nullptr : r.mix_scale, r.select_bias, choice ? choice->capacity : 0, choice ? (choice->renorm ? 1 : 0) : 0,
                sinkhorn ? sinkhorn->iters : 0, sinkhorn ? top_k : 0, (sinkhorn && r.renorm) ? 1 : 0};
   int ks = 1;
   {   // layer 1 on the matrix pipe in exact fp32 whatever the activation dtype (bit-stable argmax): rh1 = rin W1^T
@@ -1018,7 +1037,8 @@ static int router_launch(const Plan& pl, char* saved, char* scratch, const avmoe
   const float* dense = (const float*)(saved + (k_mix ? pl.o_psm : pl.o_probs));
   if (r.aux_out) {                                         // the auxiliary losses -- and the load-balancing loss from the same launch
     hipLaunchKernelGGL(kk_router_aux, dim3(1), dim3(256), 0, st, dense, (const float*)(saved + pl.o_lse), d.S, d.E, top_k ? top_k : 1,
-                       (r.lb_out && d.lb_loss) ? 1 : 0, r.lb_out, r.aux_out, r.load_out, (float*)(saved + pl.o_load), r.select_bias, r.select_count);
+                       (r.lb_out && d.lb_loss) ? 1 : 0, r.lb_out, r.aux_out, r.load_out, (float*)(saved + pl.o_load), r.select_bias, r.select_count,
+                       top_p ? top_p->p : 0.f, top_p ? top_p->k_min : 0, top_p ? top_p->k_max : 0);
     AVMOE_CHECK_LAUNCH("router_aux");
   } else if (r.lb_out && d.lb_loss) {                      // (on the dense softmax in top-k mode too: PVT_AVSModel_v2.py:314-318)
     hipLaunchKernelGGL(kk_lb_loss, dim3(1), dim3(256), 0, st, dense, d.S, d.E, r.lb_out);

@@ -42,14 +42,16 @@ int k_finish_T(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs&
 constexpr int MODE_K = 0, MODE_RENORM = 1;                  // the k of the mixture weights in `probs` (0: dense, `psm` unused; E: dense behind a multiplier or a stage), their renorm
 constexpr int MODE_SELECT = 2;                              // what the experts were ranked on: 0 = p, or
 constexpr int MODE_SELECT_BIASED = 1, MODE_SELECT_SINKHORN = 2;   // p + b (avmoe_moe_forward_bias) ; p v (avmoe_moe_forward_sinkhorn) -- the bits of b / v in MODE_SELECT_WORDS
+constexpr int MODE_SELECT_TOP_P = 3;                        // p, the smallest ranked prefix reaching P (avmoe_moe_forward_top_p): MODE_K = k_max, the bits of P in MODE_SELECT_WORDS, k_min in the word behind it
 constexpr int MODE_CHOICE_C = 3, MODE_CHOICE_RENORM = 4;    // expert choice: the capacity (0: off), its renorm
 constexpr int MODE_SK_ITERS = 5;                            // Sinkhorn: the rounds (0: off)
-constexpr int MODE_SELECT_WORDS = 16;                       // [16, 16 + E): the bits of the selection bias, or of the Sinkhorn column scale, the forward used
+constexpr int MODE_SELECT_WORDS = 16;                       // [16, 16 + E): the bits of the selection bias, or of the Sinkhorn column scale, the forward used; top-p: [16] = the bits of P, [17] = k_min
 constexpr int MODE_CHOICE_THR = 32, MODE_CHOICE_LAST = 48;  // [32, 32 + E) / [48, 48 + E): expert choice, the bits of the thresholds T_e / the last frames taken L_e
 
 struct RouterChoice { int capacity, renorm; int32_t* choice; };     // avmoe_moe_forward_choice: c in [1, S], renorm, (S) bitmask out or NULL
 struct RouterSinkhorn { int iters; int32_t* choice; int32_t* count; };   // avmoe_moe_forward_sinkhorn: n in [1, 64], (S) bitmask out or NULL, (E) counts out or NULL
 struct RouterCapacity { int capacity, policy; float* cap_scale; int32_t* kept; int32_t* demand; int32_t* kept_count; };   // avmoe_moe_forward_capacity: c in [1, S], 0 "order" / 1 "priority", (S, E) multiplier out, (S) bitmask / (E) / (E) counts out or NULL
+struct RouterTopP { float p; int k_min, k_max; int32_t *choice, *count, *khist; };   // avmoe_moe_forward_top_p: P in (0, 1], 1 <= k_min <= k_max <= E, (S) bitmask / (E) frames per expert / (E + 1) frames per number of experts out or NULL
 // How one call routes: every field's default means "off", a call site names what it sets.  route_check (capi.cpp) holds the ranges.
 struct RouteCall {
   const float* noise = nullptr;           // (S, E) added to the router's logits
@@ -61,12 +63,13 @@ struct RouteCall {
   const float* select_bias = nullptr; float* select_count = nullptr;      // (E) bias on the top-k selection alone, (E) selection counts added to (avmoe_moe_forward_bias: aux-loss-free balancing)
   // The stage behind the router, a variant (two at once cannot be written down) -- none; expert choice: each expert takes its `capacity` frames (top_k 0,
   // no selection bias); Sinkhorn-balanced top-k: the experts are ranked on p v, v from `iters` rounds on the call's softmax (top_k in [1, E), no selection bias);
-  // expert capacity: every expert keeps at most `capacity` of the frames that selected it (top_k in [1, E); the router runs as without it, the dropped weights are zeroed)
-  std::variant<std::monostate, RouterChoice, RouterSinkhorn, RouterCapacity> stage;
+  // expert capacity: every expert keeps at most `capacity` of the frames that selected it (top_k in [1, E); the router runs as without it, the dropped weights are zeroed);
+  // top-p: each frame takes the fewest ranked experts whose mass reaches p, between k_min and k_max of them (top_k 0, no selection bias; renorm is the call's)
+  std::variant<std::monostate, RouterChoice, RouterSinkhorn, RouterCapacity, RouterTopP> stage;
 };
 int k_onehot_noise(float* noise, int S, int E, int hot, float value, hipStream_t st);      // sub-ops of the C ABI (fwd_kernels.hip)
 int k_add_bias(bool bf16, void* Z, long rows, int cols, int period, const float* rowb, const float* colb, hipStream_t st);
-// the router, then the call's selection stage (k_expert_choice ; k_sk_scale, k_sk_apply ; k_cap_mask, k_cap_select, k_cap_apply) on the same stream
+// the router, then the call's selection stage (k_expert_choice ; k_sk_scale, k_sk_apply ; k_cap_mask, k_cap_select, k_cap_apply ; k_top_p_apply, k_top_p_count) on the same stream
 int k_router(const Plan& pl, char* saved, char* scratch, const avmoe_moe_ptrs& prm, const RouteCall& r, hipStream_t st);
 // expert-choice gating (expert_choice.hip): per column e of p (S, E) the threshold T_e = its c-th largest value and L_e = the last frame taken
 // among the ties (one block per expert), then per frame the mask, the weights w (times mix) and the bitmask word.  thr_bits / last: E words
@@ -90,6 +93,16 @@ int k_cap_select(const float* p, const int32_t* mask, long S, int E, int capacit
                  int32_t* kept_count, hipStream_t st);
 int k_cap_apply(const float* p, const int32_t* mask, long S, int E, int policy, const int* thr_bits, const int* last, const float* mix,
                 float* w, float* cap_scale, int32_t* kept, hipStream_t st);
+// Top-p routing (router_top_p.hip): k_top_p_apply, one thread per frame, runs topp_select on p (S, E) and writes the weights w (times mix),
+// the bitmask word and -- mode not NULL -- the mode words of the router backward (MODE_K = k_max, MODE_RENORM, MODE_SELECT = MODE_SELECT_TOP_P,
+// the bits of P and k_min in MODE_SELECT_WORDS); k_top_p_count, ONE block, overwrites count (E) and khist (E + 1) with integer sums in a fixed
+// order, from the bitmask words when `choice` holds them, else from its own topp_select on p.  w / choice / count / khist: NULL = not written.
+// No host scalar that changes, no clear.
+int k_top_p_apply(const float* p, long S, int E, float top_p, int k_min, int k_max, int renorm, const float* mix, float* w, int32_t* choice,
+                  int* mode, hipStream_t st);
+int k_top_p_count(const float* p, const int32_t* choice, long S, int E, float top_p, int k_min, int k_max, int32_t* count, int32_t* khist,
+                  hipStream_t st);
+int top_p_check(const char* fn, int E, float top_p, int k_min, int k_max);      // the ranges of both entry points: 0, or AVMOE_ERR_BAD_ARG with the message set
 // ---- forward: per token -----------------------------------------------------------------------
 struct PassCall;       // pass.h: the description of a bottleneck-space pass call, the forms of every pass and their protocol
 int k_pre_small(PassCall& c, hipStream_t st);

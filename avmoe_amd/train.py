@@ -12,6 +12,8 @@
   * `sinkhorn_scale` / `sinkhorn_topk` -- Sinkhorn-balanced top-k routing as functions: the column scale of an (S, E) matrix and the
                                selection it gives, on the device
   * `CapacityMeter`         -- the demand and the kept frames of sites with an expert capacity, accumulated on the device
+  * `top_p_mask`            -- top-p routing as a function: which experts each frame of an (S, E) matrix takes, on the device
+  * `TopPMeter`             -- how many experts the frames of top-p sites take, accumulated on the device
   * `RouterBiasBalancer`    -- aux-loss-free expert balancing of top-k sites: a bias on the selection, updated on the device after
                                every optimizer step
   * `ExpertActivationCounter` -- per-layer expert-activation tables accumulated on the device (no idx.tolist() sync per
@@ -126,6 +128,76 @@ class CapacityMeter:
     def close(self):
         for s in self.sites:
             m = s.__dict__.get("_capacity_meters", [])
+            if self in m:
+                m.remove(self)
+
+
+def top_p_mask(probs: torch.Tensor, p: float, k_min: int = 1, k_max: Optional[int] = None) -> torch.Tensor:
+    """(S, E) bool: row s is True on the fewest ranked experts of probs[s] whose running mass reaches `p` (higher probability first, equal
+    ones in expert order), at least `k_min` and at most `k_max` (default E) of them -- include/avmoe.h at avmoe_router_top_p.  The sites'
+    own kernel (`site.router_top_p`) on a caller's matrix."""
+    L = capi.lib()
+    if not getattr(L, "avmoe_site_top_p", False):
+        raise capi.AvmoeError("this libavmoe_hip.so predates avmoe_moe_forward_top_p / avmoe_router_top_p: it serves no top-p routing")
+    if not probs.is_cuda:
+        raise capi.AvmoeError("top_p_mask runs on the GPU (no CPU fallback)")
+    q = probs.reshape(-1, probs.shape[-1]).to(torch.float32).contiguous()
+    S, E = q.shape
+    bits = torch.empty(S, dtype=torch.int32, device=q.device)
+    st = L.avmoe_router_top_p(q.data_ptr(), S, E, float(p), int(k_min), int(E if k_max is None else k_max), 0, None, None, bits.data_ptr(),
+                              None, None, torch.cuda.current_stream(q.device).cuda_stream)
+    capi.check(st, "avmoe_router_top_p")
+    return (bits[:, None] >> torch.arange(E, device=q.device, dtype=torch.int32)[None, :]) & 1 != 0
+
+
+class TopPMeter:
+    """How many experts the frames of top-p sites take (`site.router_top_p`; include/avmoe.h at avmoe_moe_forward_top_p): `khist` and
+    `count` of every forward of `sites`, accumulated per site into (E_i + 1,) and (E_i,) int64 tensors on the reports' device -- two adds on
+    the forward's own stream, no host synchronisation (the companion of `CapacityMeter`).  The sites tell their meters themselves, so the
+    two sites of an `AdapterPair` and captured steps are counted like any other call.  `mean_experts()` gives the mean number of experts
+    per frame and site and synchronises; `reset()` clears the totals; `close()` detaches the meter from the sites."""
+
+    def __init__(self, sites):
+        self.sites = list(sites)
+        if not self.sites:
+            raise ValueError("TopPMeter: no sites")
+        self.khist = [None] * len(self.sites)
+        self.count = [None] * len(self.sites)
+        self.calls = [0] * len(self.sites)
+        for s in self.sites:
+            s.__dict__.setdefault("_top_p_meters", []).append(self)
+
+    def update(self, site, report):
+        """Add one call's TopPReport of `site` (a site of this meter, or its index) to the totals."""
+        i = site if isinstance(site, int) else next(j for j, s in enumerate(self.sites) if s is site)
+        h, c = report.khist.to(torch.int64), report.count.to(torch.int64)
+        if self.khist[i] is None or self.khist[i].device != h.device:
+            self.khist[i], self.count[i] = torch.zeros_like(h), torch.zeros_like(c)
+        self.khist[i] += h
+        self.count[i] += c
+        self.calls[i] += 1
+
+    def mean_experts(self) -> List[Optional[float]]:
+        """Per site, the mean number of experts a frame took since the last reset(): sum_j j khist[j] / sum_j khist[j]; None for a site
+        that has not reported.  Synchronises."""
+        out = []
+        for h in self.khist:
+            if h is None or int(h.sum()) == 0:
+                out.append(None)
+                continue
+            h = h.cpu().to(torch.float64)
+            out.append(float((h * torch.arange(h.numel(), dtype=torch.float64)).sum() / h.sum()))
+        return out
+
+    def reset(self):
+        for t in self.khist + self.count:
+            if t is not None:
+                t.zero_()
+        self.calls = [0] * len(self.sites)
+
+    def close(self):
+        for s in self.sites:
+            m = s.__dict__.get("_top_p_meters", [])
             if self in m:
                 m.remove(self)
 

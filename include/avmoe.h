@@ -480,6 +480,54 @@ int avmoe_router_capacity(const float* p, int64_t S, int32_t E, int32_t top_k, c
                           float* cap_scale /* (S,E) or NULL */, int32_t* kept /* (S) or NULL */, int32_t* demand /* (E) or NULL */,
                           int32_t* kept_count /* (E) or NULL */, float* thr /* (E) or NULL */, int32_t* last /* (E) or NULL */, void* stream);
 
+/* avmoe_moe_forward_top_p / avmoe_router_top_p (found by symbol, as above; AVMOE_ABI_VERSION stays 11) -- top-p routing ("dynamic-k"
+ * routing: Huang et al. 2024, "Harder tasks need more experts"; csrc/router_top_p.hip): the router decides how many experts a frame needs.
+ * A frame whose softmax is peaked is served by one expert, an ambiguous one by as many as it takes to cover the probability mass P.  The
+ * rule is per frame and independent of the batch: the same in eval mode and under data parallel.  No parameter, no loss weight, no state.
+ * With p the dense softmax of the call, (S, E) fp32, AVS noise included, P = top_p fp32 in (0, 1], 1 <= k_min <= k_max <= E and
+ * 2 <= E <= 16, per frame s:
+ *     rank     the experts as top-k gating does: higher p first, equal p in expert order (on the order-preserving key of p: a total order
+ *              on every bit pattern)
+ *     c_0 = 0 ;  c_j = c_(j-1) + p_(j)  for j = 1 .. E         the running mass in rank order, ONE fp32 addition per step
+ *     k*       = the smallest j with c_j >= P  (an fp32 comparison) ;  E when no j reaches P (P = 1 and an fp32 row sum that falls short)
+ *     k_s      = min(max(k*, k_min), k_max)
+ *     m[s, e]  = 1 iff rank(e) < k_s
+ *     kept_s   = sum_e m[s, e] p[s, e]                          added in expert order: with k_min = k_max = k the bits of plain top-k
+ *     w[s, e]  = m[s, e] p[s, e] / kept_s  (renorm != 0)  |  m[s, e] p[s, e]  (renorm == 0) ;  then multiplied by mix_scale[s, e] if given.
+ * The selection carries no gradient.  Only the weights change: every expert still runs on every frame, and the BatchNorm batch and running
+ * statistics, probs (the dense softmax), idx and lb are those of avmoe_moe_forward_reg on the same inputs, bit for bit.
+ * Backward:  dp_e is the top-k formula (at avmoe_moe_forward_topk / _reg) with this mask; dprobs, lb, the auxiliary terms and the softmax
+ * Jacobian follow unchanged.  The mask is recomputed per frame from the saved softmax and the words the forward left in `mode`.  There is
+ * no new backward entry point and no further backward launch: every existing one serves a top-p forward (avmoe_moe_backward_reg when a
+ * multiplier was used; dOut == NULL takes the router-only path).
+ * Auxiliary losses (aux, load):  load_e = count_e / sum_e count_e, the share of the routing slots actually handed out, and
+ * balance = E sum_e load_e P_e; z is unchanged, and the backward's balance term keeps using the saved load.
+ * `saved`, `mode` buffer:  [0] = k_max, [1] = renorm, [2] = 3 ("smallest ranked prefix reaching P"; 2 is Sinkhorn, 1 the selection bias,
+ * 0 neither -- every router forward writes it, so a later plain forward on the same workspace switches the mode off), [16] = the bits of
+ * P, [17] = k_min; [3], [4], [5] as a plain forward writes them.  No buffer is added and avmoe_moe_saved_bytes does not change.
+ * Non-finite probabilities give an unspecified selection; every access stays in bounds and between k_min and k_max experts are marked per
+ * frame.
+ *
+ * avmoe_moe_forward_top_p is avmoe_moe_forward_reg with top_p, k_min, k_max in place of top_k, plus three reports, each DEVICE int32 or
+ * NULL and each OVERWRITTEN with the same bits on every call: choice[s] (S) has bit e set iff frame s took expert e; count[e] (E) is the
+ * number of frames that took expert e; khist[j] (E + 1) is the number of frames with k_s = j.  There is no selection bias, no Sinkhorn, no
+ * capacity and no expert choice in this mode.  It adds one launch to the forward (one thread per frame: the weights, the bitmask, the mode
+ * words) and, only when count or khist is asked for, a second one (one block: integer sums in a fixed order, nothing cleared); nothing is
+ * allocated and no host scalar changes between calls, so it is capturable.  AVMOE_ERR_BAD_ARG with nothing launched: top_p not in (0, 1]
+ * or NaN, k_min or k_max outside [1, E], k_min > k_max, E outside [2, 16].
+ *
+ * avmoe_router_top_p -- the same kernels on a caller's DEVICE (S, E) fp32 matrix p.  w (S, E), choice (S), count (E) and khist (E + 1) may
+ * each be NULL.  AVMOE_ERR_BAD_ARG, with nothing launched: the refusals above, p NULL, S outside [1, 2^31 - 1], w overlapping p. */
+int avmoe_moe_forward_top_p(const avmoe_moe_desc* desc, const void* X, const void* Y, const avmoe_moe_ptrs* params,
+                            const float* noise, float top_p, int32_t k_min, int32_t k_max, int32_t renorm,
+                            const float* mix_scale /* (S,E) f32 or NULL */, void* out, float* probs, int64_t* idx, float* lb,
+                            float* aux /* [z, balance] or NULL */, float* load /* (E) or NULL */, int32_t* choice /* (S) int32 or NULL */,
+                            int32_t* count /* (E) int32 or NULL */, int32_t* khist /* (E + 1) int32 or NULL */, void* saved, void* scratch,
+                            void* stream);
+int avmoe_router_top_p(const float* p, int64_t S, int32_t E, float top_p, int32_t k_min, int32_t k_max, int32_t renorm,
+                       const float* mix_scale /* (S,E) or NULL */, float* w /* (S,E) or NULL */, int32_t* choice /* (S) or NULL */,
+                       int32_t* count /* (E) or NULL */, int32_t* khist /* (E + 1) or NULL */, void* stream);
+
 /* ABI 10 -- the gradient of a token tensor T that is X of site A and Y of site B (the two adapter sites of one backbone layer:
  * the audio tokens are X of the audio site and Y of the visual site, net_trans_v3.py:695-698), written ONCE:
  *     dT = dX_A + dY_B
